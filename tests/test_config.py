@@ -1,15 +1,17 @@
 """config.yaml schema contract (reference config.yaml:13-94): the loader yields every key the reference code reads,
-on the product's shipped yaml and -- where the reference tree is present (the build container) -- on the reference's own file.
+on the product's shipped yaml and on a file laid out like the reference's own (hydra's keys, no runtime section).
 tests/golden/config_schema.json holds the reference file's key paths and leaf types (names only; made by walking the yaml)."""
 import json
 import os
 
-import pytest
+import yaml
 
 from distributed_multi_agent_reinforcement_learning_amd.config import DEFAULT_YAML, SECTIONS, baseline_config, load_config
 from tests.helpers import GOLDEN
 
-REFERENCE_YAML = "/root/reference/config.yaml"
+# where the reference's shipped values differ from ours (config.yaml:13-94); every other key it carries equals the shipped yaml's
+REFERENCE_VALUES = {"env": {"num_defender": 15}, "map": {"map_size": [60, 55], "center": [30, 25]},
+                    "algo": {"depth": 1, "use_reward_norm": False}}
 SCHEMA = json.load(open(os.path.join(GOLDEN, "config_schema.json")))
 
 
@@ -39,11 +41,24 @@ def test_shipped_yaml_has_the_reference_schema():
         _check_schema(baseline_config(name))
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE_YAML), reason="the reference tree exists in the build container only")
-def test_reference_yaml_loads_with_every_key():
-    """The reference's own config.yaml through the product's loader: the sections of config.yaml:13-94 with the shipped values
-    (15 defenders on 60 x 55, depth 1, use_reward_norm false), hydra's own keys ignored, runtime defaults added."""
-    cfg = load_config(REFERENCE_YAML)
+def reference_layout_yaml(path):
+    """A config.yaml laid out like the reference's: hydra's own top-level keys, the sections with the reference's values
+    (REFERENCE_VALUES over the shipped yaml), no runtime section."""
+    raw = yaml.safe_load(open(DEFAULT_YAML))
+    raw.pop("runtime", None)
+    for section, values in REFERENCE_VALUES.items():
+        raw[section].update(values)
+    raw = {"defaults": ["_self_"], "hydra": {"run": {"dir": "outputs/${now:%Y-%m-%d_%H-%M-%S}"}, "output_subdir": None}, "main": None, **raw}
+    with open(path, "w") as f:
+        yaml.safe_dump(raw, f, sort_keys=False)
+    return str(path)
+
+
+def test_reference_yaml_loads_with_every_key(tmp_path):
+    """A reference-layout config.yaml through the product's loader: the sections of config.yaml:13-94 with the reference's
+    values (15 defenders on 60 x 55, depth 1, use_reward_norm false), hydra's own keys ignored, runtime defaults added."""
+    path = reference_layout_yaml(tmp_path / "config.yaml")
+    cfg = load_config(path)
     _check_schema(cfg)
     assert (cfg.env.num_defender, cfg.map.map_size, cfg.map.center, cfg.map.num_max_obstacle) == (15, [60, 55], [30, 25], 176)
     assert (cfg.env.max_steps, cfg.env.difficulty, cfg.env.action_dim, cfg.env.state_dim) == (150, 10, 9, 4)
@@ -59,4 +74,4 @@ def test_reference_yaml_loads_with_every_key():
     assert (c.W, c.H, c.P, c.O, c.max_steps, c.difficulty, c.num_beams, c.lidar_radius) == (60, 55, 15, 176, 150, 10, 36, 8)
     assert (c.def_tau, c.def_dt, c.eva_vmax, c.def_comm_range) == (0.2, 0.1, 4.0, 16.0)
     # overrides address the same dotted paths
-    assert load_config(REFERENCE_YAML, **{"env.num_defender": 8}).env.num_defender == 8
+    assert load_config(path, **{"env.num_defender": 8}).env.num_defender == 8
