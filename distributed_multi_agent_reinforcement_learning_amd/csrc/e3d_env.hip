@@ -19,6 +19,7 @@
 
 #include "e3d_env.h"
 #include "rng_replica.hpp"
+#include "slsqp_box.hpp"
 
 namespace {
 
@@ -146,6 +147,113 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d(const e3d_config c, const e3
         o.pe_adj[(int64_t)env * o.pe_adj_stride + a] = (s.act != 0.0 && sq3(s.x - e.x, s.y - e.y, s.z - e.z) <= th.sen) ? 1.f : 0.f;
 }
 
+// ---- the reference's evader: eva.e_f (eva.py:87-148), a bounded SLSQP minimisation of obj_func (:212-240) ----
+
+constexpr double E3D_E_SEN_RANGE = 3.0;  // particle_env.py:86 'e_sen_range' (not a field of e3d_config)
+// obj_func's own Point (eva.py:214-227): ang_lmt pi/4, v_lmt 0.4 and step_size 0.5 are literals there, not the environment's
+constexpr double OBJ_ANG_LMT = PI / 4, OBJ_V_LMT = 0.4, OBJ_STEP = 0.5;
+
+// obj_func of one evader.  q holds the predicted positions of the n pursuers in sensing range: x at q[k * qs], y at
+// q[(P + k) * qs], z at q[(2P + k) * qs] (LDS on the device, a host array in the CPU path).
+template <int PM>
+struct E3dObjective {
+    double ex, ey, ez, egamma, ev, v_max, tx, ty, tz, kill;
+    int n, P, qs;
+    const double *q;
+    __host__ __device__ double operator()(const double *a) const {
+        // Point.step (eva.py:51-84) with the objective's constants: the position moves along the COMMANDED heading phi
+        const double phi = a[0] * PI, gamma = a[1] * PI / 2, v = (a[2] + 1) / 2 * v_max;
+        const double g = egamma + slsqp::clampd(gamma - egamma, -OBJ_ANG_LMT, OBJ_ANG_LMT);
+        const double vv = ev + slsqp::clampd(v - ev, -OBJ_V_LMT, OBJ_V_LMT);
+        const double nx = ex + vv * cos(g) * cos(phi) * OBJ_STEP, ny = ey + vv * cos(g) * sin(phi) * OBJ_STEP;
+        const double nz = ez + vv * sin(g) * OBJ_STEP;
+        double d[PM];
+#pragma unroll
+        for (int k = 0; k < PM; k++) {
+            d[k] = INFINITY;
+            if (k < n) {
+                const double dx = nx - q[k * qs], dy = ny - q[(P + k) * qs], dz = nz - q[(2 * P + k) * qs];
+                d[k] = sqrt(dx * dx + dy * dy + dz * dz);
+            }
+        }
+        slsqp::sort_asc<PM>(d);
+        double sdd = 0.0;
+#pragma unroll
+        for (int k = 0; k < PM; k++)
+            if (k < n) sdd = sdd + 1.0 / pow(d[k] / kill, 5.0);
+        const double dx = nx - tx, dy = ny - ty, dz = nz - tz;
+        return 1.0 * sqrt(dx * dx + dy * dy + dz * dz) + sdd;
+    }
+};
+
+// e_f for the evader of one environment (records p [7][P], e [7]): cmd [3] in [-1, 1]; zeros when the evader is inactive
+// or no pursuer is active (evader_step is not called then, see the tick).  Returns the iterations taken.
+template <int PM>
+__host__ __device__ inline int e3d_evader_one(const e3d_config &c, const double *p, const double *e, const double *tg, double *q, int qs,
+                                              double *cmd) {
+    const int P = c.P;
+    cmd[0] = cmd[1] = cmd[2] = 0.0;
+    if (e[6] == 0.0) return 0;
+    const double ex = e[0], ey = e[1], ez = e[2], ephi = e[3], egam = e[4], ev = e[5];
+    int n = 0, alive = 0;
+    for (int j = 0; j < P; j++) {  // the active pursuers (get_team_state rules=True) inside the evader's sensing range
+        if (p[6 * P + j] == 0.0) continue;
+        alive++;
+        const double dx = ex - p[j], dy = ey - p[P + j], dz = ez - p[2 * P + j];
+        if (!(sqrt(dx * dx + dy * dy + dz * dz) <= E3D_E_SEN_RANGE)) continue;
+        const double nphi = p[3 * P + j], ngam = p[4 * P + j], nv = p[5 * P + j];
+        q[n * qs] = p[j] + nv * cos(nphi) * cos(ngam) * c.step_size;
+        q[(P + n) * qs] = p[P + j] + nv * sin(nphi) * cos(ngam) * c.step_size;
+        q[(2 * P + n) * qs] = p[2 * P + j] + nv * sin(ngam) * c.step_size;
+        n++;
+    }
+    if (alive == 0) return 0;
+    E3dObjective<PM> fn{ex, ey, ez, egam, ev, c.e_vmax, tg[0], tg[1], tg[2], c.kill_radius, n, P, qs, q};
+    // bounds from the environment's rate limits (eva.py:130-135), start at the current state (:137-139)
+    const double lb[3] = {slsqp::clampd((ephi - c.ang_lmt) / PI, -1, 1), slsqp::clampd((egam - c.ang_lmt) / (PI / 2), -1, 1),
+                          slsqp::clampd((ev - c.v_lmt) * 2 - 1, -1, 1)};
+    const double ub[3] = {slsqp::clampd((ephi + c.ang_lmt) / PI, -1, 1), slsqp::clampd((egam + c.ang_lmt) / (PI / 2), -1, 1),
+                          slsqp::clampd((ev + c.v_lmt) * 2 - 1, -1, 1)};
+    double x[3] = {ephi / PI, egam / (PI / 2), ev * 2 - 1};
+    const int it = slsqp::minimize<3>(fn, x, lb, ub);
+    cmd[0] = x[0]; cmd[1] = x[1]; cmd[2] = x[2];
+    return it;
+}
+
+// one lane per environment, one wavefront (half of one above 64 KB of LDS) per block; the lane's pursuer predictions
+// live in LDS at stride blockDim.x
+template <int PM>
+__global__ __launch_bounds__(WAVE) void k_e3d_evader(const e3d_config c, const e3d_state st, double *e_cmd, int32_t *nit) {
+    extern __shared__ double q_lds[];
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= st.N) return;
+    double cmd[3];
+    const int it = e3d_evader_one<PM>(c, st.p + (size_t)env * 7 * c.P, st.e + (size_t)env * 7, st.target + 3 * env, q_lds + threadIdx.x,
+                                      (int)blockDim.x, cmd);
+    e_cmd[3 * env] = cmd[0]; e_cmd[3 * env + 1] = cmd[1]; e_cmd[3 * env + 2] = cmd[2];
+    if (nit) nit[env] = it;
+}
+
+int launch_e3d_evader(const e3d_config *c, const e3d_state *st, double *e_cmd, int32_t *nit, hipStream_t s) {
+    if (st->N == 0) return 0;
+    const int tpb = (size_t)3 * c->P * WAVE * sizeof(double) <= 65536 ? WAVE : WAVE / 2;
+    const unsigned blocks = (unsigned)((st->N + tpb - 1) / tpb);
+    const size_t lds = (size_t)3 * c->P * tpb * sizeof(double);
+#define E3D_EV(PM) hipLaunchKernelGGL((k_e3d_evader<PM>), dim3(blocks), dim3(tpb), lds, s, *c, *st, e_cmd, nit)
+    if (c->P <= 8) E3D_EV(8); else if (c->P <= 16) E3D_EV(16); else if (c->P <= 32) E3D_EV(32); else E3D_EV(64);
+#undef E3D_EV
+    return (int)hipGetLastError();
+}
+
+template <int PM>
+void e3d_evader_host_pm(const e3d_config &c, int N, const double *p, const double *e, const double *tg, double *e_cmd, int32_t *nit) {
+    std::vector<double> q((size_t)3 * c.P);
+    for (int env = 0; env < N; env++) {
+        const int it = e3d_evader_one<PM>(c, p + (size_t)env * 7 * c.P, e + (size_t)env * 7, tg + 3 * env, q.data(), 1, e_cmd + 3 * env);
+        if (nit) nit[env] = it;
+    }
+}
+
 // [N][P][7] host order -> [N][7][P] records
 __global__ void k_aos_to_soa7(int N, int A, const double *aos, double *soa) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -213,6 +321,29 @@ int e3d_env_tick(const e3d_config *cfg, const e3d_state *st, const double *actio
     e3d_obs_out o0;
     memset(&o0, 0, sizeof o0);
     return launch<true>(cfg, st, actions, e_cmd, reward, active, done, out ? *out : o0, (hipStream_t)stream);
+}
+
+int e3d_evader_slsqp(const e3d_config *cfg, const e3d_state *st, double *e_cmd, void *stream) {
+    return e3d_evader_slsqp_nit(cfg, st, e_cmd, nullptr, stream);
+}
+
+int e3d_evader_slsqp_nit(const e3d_config *cfg, const e3d_state *st, double *e_cmd, int32_t *nit, void *stream) {
+    if (!cfg || !st || !e_cmd) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    return launch_e3d_evader(cfg, st, e_cmd, nit, (hipStream_t)stream);
+}
+
+int e3d_evader_slsqp_host(const e3d_config *cfg, int32_t N, const double *p, const double *e, const double *target, double *e_cmd,
+                          int32_t *nit) {
+    if (!cfg || !p || !e || !target || !e_cmd) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (cfg->P <= 8) e3d_evader_host_pm<8>(*cfg, N, p, e, target, e_cmd, nit);
+    else if (cfg->P <= 16) e3d_evader_host_pm<16>(*cfg, N, p, e, target, e_cmd, nit);
+    else if (cfg->P <= 32) e3d_evader_host_pm<32>(*cfg, N, p, e, target, e_cmd, nit);
+    else e3d_evader_host_pm<64>(*cfg, N, p, e, target, e_cmd, nit);
+    return 0;
 }
 
 void *e3d_resetter_create(const e3d_config *cfg, int32_t N, const uint32_t *seeds) {

@@ -15,6 +15,7 @@
 
 #include "n2n_env.h"
 #include "rng_replica.hpp"
+#include "slsqp_box.hpp"
 
 namespace {
 
@@ -162,6 +163,103 @@ int launch_n2n(const n2n_config *c, const n2n_state *st, const int32_t *actions,
     return (int)hipGetLastError();
 }
 
+// ---- the reference's evader: eva.e_f (eva.py:36-80), a bounded SLSQP minimisation of obj_func over the heading ----
+
+constexpr double N2N_E_SEN_RANGE = 3.0;  // particle_env.py:114 'e_sen_range' (not a field of n2n_config)
+
+// obj_func (eva.py:60-80) of one evader.  q holds the predicted positions of the n pursuers in sensing range, x at q[k * qs],
+// y at q[(P + k) * qs] (LDS on the device, a host array in the CPU path).
+template <int PM>
+struct N2nObjective {
+    double ex, ey, ev, tx, ty;
+    int n, P, qs;
+    const double *q;
+    __host__ __device__ double operator()(const double *b) const {
+        const double nx = ex + ev * cos(b[0]), ny = ey + ev * sin(b[0]);
+        double d[PM];
+#pragma unroll
+        for (int k = 0; k < PM; k++) {
+            d[k] = INFINITY;
+            if (k < n) {
+                const double dx = nx - q[k * qs], dy = ny - q[(P + k) * qs];
+                d[k] = sqrt(dx * dx + dy * dy);
+            }
+        }
+        slsqp::sort_asc<PM>(d);
+        double sdd = 0.0;
+#pragma unroll
+        for (int k = 0; k < PM; k++)
+            if (k < n) sdd = sdd + 0.5 / d[k];
+        const double dx = nx - tx, dy = ny - ty;
+        return 0.5 * sqrt(dx * dx + dy * dy) + sdd;
+    }
+};
+
+// e_f for evader a of one environment (records p [5][P], e [5][E]); writes q, returns the normalised heading (0 for an
+// inactive evader, which the reference never calls e_f on) and the iterations taken.
+template <int PM>
+__host__ __device__ inline double n2n_evader_one(const n2n_config &c, const double *p, const double *e, const double *tg, int a,
+                                                 double *q, int qs, int *nit) {
+    const int P = c.P, E = c.E;
+    *nit = 0;
+    if (e[4 * E + a] == 0.0) return 0.0;
+    const double ex = e[a], ey = e[E + a];
+    int n = 0;
+    for (int j = 0; j < P; j++) {  // the active pursuers (get_team_state rules=True) inside the evader's sensing range
+        if (p[4 * P + j] == 0.0) continue;
+        const double dx = ex - p[j], dy = ey - p[P + j];
+        if (!(sqrt(dx * dx + dy * dy) <= N2N_E_SEN_RANGE)) continue;
+        const double v = p[3 * P + n];  // p_v0[ne]: the speed of the n-th pursuer of the FULL list (eva.py:67)
+        q[n * qs] = p[j] + v * cos(p[2 * P + j]);
+        q[(P + n) * qs] = p[P + j] + v * sin(p[2 * P + j]);
+        n++;
+    }
+    N2nObjective<PM> fn{ex, ey, e[3 * E + a], tg[0], tg[1], n, P, qs, q};
+    double x[1] = {0.0};
+    const double lb[1] = {-PI}, ub[1] = {PI};
+    *nit = slsqp::minimize<1>(fn, x, lb, ub);
+    return x[0] / PI;
+}
+
+// one lane per (environment, evader), one wavefront (half of one above 64 KB of LDS) per block; the lane's pursuer
+// predictions live in LDS at stride blockDim.x
+template <int PM>
+__global__ __launch_bounds__(WAVE) void k_n2n_evader(const n2n_config c, const n2n_state st, double *e_cmd, int32_t *nit) {
+    extern __shared__ double q_lds[];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= st.N * c.E) return;
+    const int env = i / c.E, a = i - env * c.E;
+    int it;
+    const double cmd = n2n_evader_one<PM>(c, st.p + (size_t)env * 5 * c.P, st.e + (size_t)env * 5 * c.E, st.target + 2 * env, a,
+                                          q_lds + threadIdx.x, (int)blockDim.x, &it);
+    e_cmd[i] = cmd;
+    if (nit) nit[i] = it;
+}
+
+int launch_n2n_evader(const n2n_config *c, const n2n_state *st, double *e_cmd, int32_t *nit, hipStream_t s) {
+    const long long lanes = (long long)st->N * c->E;
+    if (lanes == 0) return 0;
+    const int tpb = (size_t)2 * c->P * WAVE * sizeof(double) <= 65536 ? WAVE : WAVE / 2;
+    const unsigned blocks = (unsigned)((lanes + tpb - 1) / tpb);
+    const size_t lds = (size_t)2 * c->P * tpb * sizeof(double);
+#define N2N_EV(PM) hipLaunchKernelGGL((k_n2n_evader<PM>), dim3(blocks), dim3(tpb), lds, s, *c, *st, e_cmd, nit)
+    if (c->P <= 8) N2N_EV(8); else if (c->P <= 16) N2N_EV(16); else if (c->P <= 32) N2N_EV(32); else N2N_EV(64);
+#undef N2N_EV
+    return (int)hipGetLastError();
+}
+
+template <int PM>
+void n2n_evader_host_pm(const n2n_config &c, int N, const double *p, const double *e, const double *tg, double *e_cmd, int32_t *nit) {
+    std::vector<double> q((size_t)2 * c.P);
+    for (int env = 0; env < N; env++)
+        for (int a = 0; a < c.E; a++) {
+            int it;
+            e_cmd[(size_t)env * c.E + a] = n2n_evader_one<PM>(c, p + (size_t)env * 5 * c.P, e + (size_t)env * 5 * c.E, tg + 2 * env, a,
+                                                              q.data(), 1, &it);
+            if (nit) nit[(size_t)env * c.E + a] = it;
+        }
+}
+
 // [N][A][5] host order -> [N][5][A] records
 __global__ void k_aos_to_soa(int N, int A, const double *aos, double *soa) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -229,6 +327,29 @@ int n2n_env_tick(const n2n_config *cfg, const n2n_state *st, const int32_t *acti
     n2n_obs_out o0;
     memset(&o0, 0, sizeof o0);
     return launch_n2n<true>(cfg, st, actions, e_cmd, reward, active, done, out ? *out : o0, (hipStream_t)stream);
+}
+
+int n2n_evader_slsqp(const n2n_config *cfg, const n2n_state *st, double *e_cmd, void *stream) {
+    return n2n_evader_slsqp_nit(cfg, st, e_cmd, nullptr, stream);
+}
+
+int n2n_evader_slsqp_nit(const n2n_config *cfg, const n2n_state *st, double *e_cmd, int32_t *nit, void *stream) {
+    if (!cfg || !st || !e_cmd) return N2N_ERR_NULL;
+    const int rc = n2n_config_check(cfg);
+    if (rc) return rc;
+    return launch_n2n_evader(cfg, st, e_cmd, nit, (hipStream_t)stream);
+}
+
+int n2n_evader_slsqp_host(const n2n_config *cfg, int32_t N, const double *p, const double *e, const double *target, double *e_cmd,
+                          int32_t *nit) {
+    if (!cfg || !p || !e || !target || !e_cmd) return N2N_ERR_NULL;
+    const int rc = n2n_config_check(cfg);
+    if (rc) return rc;
+    if (cfg->P <= 8) n2n_evader_host_pm<8>(*cfg, N, p, e, target, e_cmd, nit);
+    else if (cfg->P <= 16) n2n_evader_host_pm<16>(*cfg, N, p, e, target, e_cmd, nit);
+    else if (cfg->P <= 32) n2n_evader_host_pm<32>(*cfg, N, p, e, target, e_cmd, nit);
+    else n2n_evader_host_pm<64>(*cfg, N, p, e, target, e_cmd, nit);
+    return 0;
 }
 
 void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seeds) {

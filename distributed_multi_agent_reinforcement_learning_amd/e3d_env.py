@@ -5,8 +5,9 @@ Mirrors environment/env_3d/particle_env.py:76-404 of the reference for N indepen
 dimension.  Pursuer actions are continuous, a in [-1, 1]^3 (heading, pitch, speed; Point.step :25-55).  Kinematics / reward /
 culling / done run in csrc/e3d_env.hip (C ABI include/e3d_env.h), the reset in the same library's host part with a replica
 of numpy's legacy generator per environment.  The reference's evader is driven by scipy's SLSQP (eva.py:87-148): here its
-command is an input (`evader_step(cmd)`), or, when none is given, a closed-form rule (head for the target at full speed) that
-is NOT the reference's optimiser.
+command is an input (`evader_step(cmd)`), or, when none is given, either a closed-form rule (head for the target at full
+speed; `evader="rule"`, the default) or the reference's optimiser itself, Kraft's SLSQP on the GPU (`evader="slsqp"`,
+e3d_evader_slsqp in the same library).
 """
 import ctypes as C
 import math
@@ -50,6 +51,9 @@ def load_library():
         L.e3d_resetter_create.argtypes = [vp, C.c_int32, vp]
         L.e3d_resetter_create.restype = vp
         L.e3d_resetter_destroy.argtypes = [vp]
+        L.e3d_evader_slsqp.argtypes = [vp] * 4
+        L.e3d_evader_slsqp_nit.argtypes = [vp] * 5
+        L.e3d_evader_slsqp_host.argtypes = [vp, C.c_int32] + [vp] * 5
         L.e3d_resetter_reset.argtypes = [vp, vp, vp, vp, C.c_int32]
         _lib = L
     return _lib
@@ -69,7 +73,10 @@ class ParticleEnv:
     """cfg values are the reference's hard-coded defaults (particle_env.py:78-121)."""
 
     def __init__(self, num_envs=1, seeds=None, device="cuda", p_vmax=0.7, e_vmax=1.0, p_sen_range=3.0, p_comm_range=6.0, kill_radius=0.5,
-                 ang_lmt=math.pi / 4, v_lmt=0.4, step_size=0.5, max_step=200):
+                 ang_lmt=math.pi / 4, v_lmt=0.4, step_size=0.5, max_step=200, evader="rule"):
+        if evader not in ("rule", "slsqp"):
+            raise ValueError(f"evader must be 'rule' or 'slsqp', not {evader!r}")
+        self.evader = evader
         self.L = load_library()
         if not torch.cuda.is_available():
             raise RuntimeError("ParticleEnv needs a GPU (MI355X); there is no CPU path")
@@ -110,6 +117,7 @@ class ParticleEnv:
         self.reward_t = f(P)
         self.active_t = torch.ones((N, P), dtype=torch.uint8, device=dev)
         self.done_t = torch.zeros((N,), dtype=torch.uint8, device=dev)
+        self._cmd_slsqp = torch.zeros((N, 3), dtype=torch.float64, device=dev)  # the kernel's own output buffer
         s = np.ascontiguousarray(self.seeds, np.uint32)
         self.resetter = self.L.e3d_resetter_create(C.byref(c), N, s.ctypes.data_as(C.c_void_p))
         if not self.resetter:
@@ -161,9 +169,19 @@ class ParticleEnv:
     def get_active(self):
         return self.active_t
 
-    def evader_step(self, cmd=None):
+    def evader_step(self, cmd=None, nit=None):
         """Sets the evader's command (heading, pitch, speed) in [-1, 1]^3 for the next step (the reference computes it with
-        SLSQP, :354-378).  Without `cmd`: full speed straight at the target."""
+        SLSQP, :354-378).  Without `cmd`, evader="rule": full speed straight at the target; evader="slsqp": the reference's
+        SLSQP evader, launched on the current stream without a host synchronisation (it can be captured in a graph).  nit, an
+        int32 (N,) device tensor, receives the SLSQP iterations taken per environment."""
+        if cmd is None and self.evader == "slsqp":
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+            if nit is not None:
+                assert nit.dtype == torch.int32 and nit.is_contiguous() and nit.numel() == self.num_envs
+            _check(self.L.e3d_evader_slsqp_nit(C.byref(self.c), C.byref(self.st), ptr(self._cmd_slsqp), ptr(nit), _stream()),
+                   "e3d_evader_slsqp")
+            self._cmd = self._cmd_slsqp
+            return
         if cmd is None:
             d = self.target - self.e[:, :3]
             cmd = torch.stack((torch.atan2(d[:, 1], d[:, 0]) / math.pi, torch.atan2(d[:, 2], torch.hypot(d[:, 0], d[:, 1])) / (math.pi / 2),

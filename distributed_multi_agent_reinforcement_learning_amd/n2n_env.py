@@ -4,9 +4,10 @@ Mirrors environment/env_n2n/particle_env.py:105-462 of the reference for N indep
 `reset`, `evader_step`, `step`, `get_team_state`, `get_adj_mat`, `get_active` keep their names; tensors carry a leading
 environment dimension.  The kinematics / reward / culling / done logic runs in csrc/n2n_env.hip (C ABI include/n2n_env.h),
 the reset in the same library's host part with a replica of numpy's legacy generator per environment.
-The reference's evader is driven by scipy's SLSQP (eva.py:36-53): here the heading command is an input
-(`evader_step(cmd)`), or, when none is given, a simple closed-form rule (head for the target, turn away from the nearest
-pursuer in sensing range) that is NOT the reference's optimiser.
+The reference's evader is driven by scipy's SLSQP (eva.py:36-80).  Here the heading command is an input (`evader_step(cmd)`),
+or, when none is given, either a simple closed-form rule (head for the target, turn away from the nearest pursuer in sensing
+range; `evader="rule"`, the default) or the reference's optimiser itself, Kraft's SLSQP on the GPU (`evader="slsqp"`,
+n2n_evader_slsqp in the same library).
 """
 import ctypes as C
 import math
@@ -50,6 +51,9 @@ def load_library():
         L.n2n_resetter_create.argtypes = [vp, C.c_int32, vp]
         L.n2n_resetter_create.restype = vp
         L.n2n_resetter_destroy.argtypes = [vp]
+        L.n2n_evader_slsqp.argtypes = [vp] * 4
+        L.n2n_evader_slsqp_nit.argtypes = [vp] * 5
+        L.n2n_evader_slsqp_host.argtypes = [vp, C.c_int32] + [vp] * 5
         L.n2n_resetter_reset.argtypes = [vp, vp, vp, vp, C.c_int32]
         _lib = L
     return _lib
@@ -68,7 +72,10 @@ class ParticleEnv:
     """cfg values are the reference's hard-coded defaults (particle_env.py:108-121,143-147)."""
 
     def __init__(self, num_envs=1, seeds=None, device="cuda", p_vmax=0.3, e_vmax=1.0, p_sen_range=3.0, p_comm_range=6.0,
-                 kill_radius=0.5, ang_lmt=math.pi / 4, step_size=0.5, episode_limit=100):
+                 kill_radius=0.5, ang_lmt=math.pi / 4, step_size=0.5, episode_limit=100, evader="rule"):
+        if evader not in ("rule", "slsqp"):
+            raise ValueError(f"evader must be 'rule' or 'slsqp', not {evader!r}")
+        self.evader = evader
         self.L = load_library()
         if not torch.cuda.is_available():
             raise RuntimeError("ParticleEnv needs a GPU (MI355X); there is no CPU path")
@@ -107,6 +114,7 @@ class ParticleEnv:
         self.reward_t = f(self.p_num)
         self.active_t = torch.ones((N, self.p_num), dtype=torch.uint8, device=dev)
         self.done_t = torch.zeros((N,), dtype=torch.uint8, device=dev)
+        self._cmd_slsqp = torch.zeros((N, self.e_num), dtype=torch.float64, device=dev)  # the kernel's own output buffer
         s = np.ascontiguousarray(self.seeds, np.uint32)
         self.resetter = self.L.n2n_resetter_create(C.byref(c), N, s.ctypes.data_as(C.c_void_p))
         if not self.resetter:
@@ -156,9 +164,19 @@ class ParticleEnv:
     def get_active(self):
         return self.active_t
 
-    def evader_step(self, cmd=None):
+    def evader_step(self, cmd=None, nit=None):
         """Sets the evaders' normalised heading command in [-1, 1] for the next step (the reference computes it with SLSQP,
-        :179-198).  Without `cmd`: head for the target, but away from the nearest pursuer inside the sensing range."""
+        :179-198).  Without `cmd`, evader="rule": head for the target, but away from the nearest pursuer inside the sensing range;
+        evader="slsqp": the reference's SLSQP evader, launched on the current stream without a host synchronisation (it can be
+        captured in a graph).  nit, an int32 (N, E) device tensor, receives the SLSQP iterations taken per evader."""
+        if cmd is None and self.evader == "slsqp":
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+            if nit is not None:
+                assert nit.dtype == torch.int32 and nit.is_contiguous() and nit.numel() == self.num_envs * self.e_num
+            _check(self.L.n2n_evader_slsqp_nit(C.byref(self.c), C.byref(self.st), ptr(self._cmd_slsqp), ptr(nit), _stream()),
+                   "n2n_evader_slsqp")
+            self._cmd = self._cmd_slsqp
+            return
         if cmd is None:
             ex, ey = self.e[:, 0], self.e[:, 1]
             to_t = torch.atan2(self.target[:, 1:2] - ey, self.target[:, 0:1] - ex)

@@ -5,8 +5,8 @@
  * Replaces, for N independent environments, the methods of the reference class
  * environment/env_3d/particle_env.py:76 `ParticleEnv` cited per entry point.  Pursuer actions are CONTINUOUS
  * (a in [-1, 1]^3: heading, pitch, speed; Point.step :25-55).  The evader's command -- in the reference the result of eva.e_f
- * (scipy SLSQP, eva.py:87-148) -- is an INPUT.  Conventions as in pe_env.h: device pointers owned by the caller, caller's
- * hipStream_t as void*, 0 == success.
+ * (scipy SLSQP, eva.py:87-148) -- is an input of the tick; e3d_evader_slsqp computes it.  Conventions as in pe_env.h: device
+ * pointers owned by the caller, caller's hipStream_t as void*, 0 == success.
  * Several environments share one 64-lane wavefront (lane = (environment, pursuer), 8 environments per wave for P <= 8).
  */
 #ifndef E3D_ENV_H
@@ -53,6 +53,18 @@ int e3d_env_observe(const e3d_config *cfg, const e3d_state *st, const e3d_obs_ou
  * reward [N][P] fp32, active [N][P] u8, done [N] u8. */
 int e3d_env_tick(const e3d_config *cfg, const e3d_state *st, const double *actions, const double *e_cmd, float *reward,
                  uint8_t *active, uint8_t *done, const e3d_obs_out *out, void *stream);
+
+/* The reference's evader: eva.e_f (eva.py:87-148) -- scipy's SLSQP (ftol 1e-6, <= 100 iterations, 2-point finite-difference
+ * gradient) minimising obj_func (:212-240) over (heading, pitch, speed), started at the evader's state, bounded by the
+ * environment's ang_lmt / v_lmt (:130-135) -- written as the command e_cmd [N][3] that e3d_env_tick consumes; zeros when the
+ * evader is inactive or no pursuer is active (the tick does not move it then).  Only active pursuers within e_sen_range
+ * (3, particle_env.py:86) count; the objective's own kinematics use the literals ang_lmt pi/4, v_lmt 0.4, step 0.5 (:214-227).
+ * One lane per environment, no host synchronisation.  The _nit form also writes the major iterations taken, nit [N]. */
+int e3d_evader_slsqp(const e3d_config *cfg, const e3d_state *st, double *e_cmd, void *stream);
+int e3d_evader_slsqp_nit(const e3d_config *cfg, const e3d_state *st, double *e_cmd, int32_t *nit, void *stream);
+/* The same computation on the host, on host records laid out as the device ones (p [N][7][P], e [N][7], target [N][3]). */
+int e3d_evader_slsqp_host(const e3d_config *cfg, int32_t N, const double *p, const double *e, const double *target, double *e_cmd,
+                          int32_t *nit);
 
 /* Host side of ParticleEnv.reset (:137-203) with a bit-exact replica of numpy's legacy RandomState per environment
  * (np.random.seed(seeds[n])).  Fills host arrays p [N][P][7], e [N][7], target [N][3]. */

@@ -2,7 +2,9 @@
 env_n2n 16 pursuers x 8192 envs (config 4) and env_3d 8 pursuers x 2048 envs (config 5; also at 8192 envs to fill the chip).
 The T ticks are captured once as a hipGraph and replayed: elapsed / T = kernel + same-stream boundary, no Python in between.
 Algorithmic bytes per env-step: state read + write (f64 fields per agent), actions, evader command, reward / active / done,
-fp32 observations."""
+fp32 observations.
+Beside each tick: the SLSQP evader launch (evader="slsqp": n2n_evader_slsqp / e3d_evader_slsqp), timed the same way on the
+state reached after a few closed-loop steps, with the SLSQP iterations it took (mean / max over the evaders of one launch)."""
 import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,6 +30,32 @@ def run(name, env, step_args, B, N, P, T=50):
                       "bytes_per_env_step": B, "achieved_GBps": round(N * B / dt / 1e9, 1), "frac_of_8TBps": round(N * B / dt / 8e12, 4)}), flush=True)
 
 
+def run_evader(name, env, step_args, nit, N, P, T=50, warm=10):
+    env.reset()
+    for t in range(warm):  # a few closed-loop steps: pursuers close in and enter the evaders' sensing range
+        env.evader_step()
+        env.step(*step_args(t))
+    env.evader_step(nit=nit)
+    torch.cuda.synchronize()
+    it = nit.float()
+    called = it[nit > 0]
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for t in range(T):
+            env.evader_step()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    tot = 0.0
+    for rep in range(5):
+        torch.cuda.synchronize()
+        e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
+        tot += e0.elapsed_time(e1)
+    dt = tot / 5 / T * 1e-3
+    print(json.dumps({"kernel": name, "envs": N, "pursuers": P, "evaders": nit.numel(), "us_per_launch": round(dt * 1e6, 2),
+                      "evader_solves_per_s": round(nit.numel() / dt), "evaders_solved": int(called.numel()),
+                      "iters_mean": round(float(called.mean()), 3) if called.numel() else 0.0, "iters_max": int(nit.max()),
+                      "warm_steps": warm}), flush=True)
+
+
 def n2n(N):
     from distributed_multi_agent_reinforcement_learning_amd.n2n_env import ParticleEnv
     P, E, T = 16, 1, 50
@@ -37,6 +65,8 @@ def n2n(N):
     env._cmd = torch.rand(N, E, dtype=torch.float64, device="cuda") * 2 - 1
     B = 2 * (P + E) * 5 * 8 + 4 * P + 8 * E + 4 * P + P + 1 + 4 * (3 * P + 3 * E + P * P + P * E)
     run("k_n2n<tick>", env, lambda t: (acts[t],), B, N, P, T)
+    env.evader = "slsqp"
+    run_evader("k_n2n_evader", env, lambda t: (acts[t],), torch.zeros(N, E, dtype=torch.int32, device="cuda"), N, P, T)
 
 
 def e3d(N):
@@ -48,6 +78,8 @@ def e3d(N):
     env._cmd = torch.rand(N, 3, dtype=torch.float64, device="cuda") * 2 - 1
     B = 2 * (P + 1) * 7 * 8 + 24 * P + 24 + 24 + 4 * P + P + 1 + 4 * (6 * P + 6 + P * P + P)
     run("k_e3d<tick>", env, lambda t: (acts[t],), B, N, P, T)
+    env.evader = "slsqp"
+    run_evader("k_e3d_evader", env, lambda t: (acts[t],), torch.zeros(N, dtype=torch.int32, device="cuda"), N, P, T)
 
 
 if __name__ == "__main__":
