@@ -14,6 +14,7 @@
 #include "mappo_ops.h"
 #include "mappo_ops_diag.h"
 #include "sb_common.hpp"
+#include "sb_wgrad.hpp"
 
 namespace {
 
@@ -2060,171 +2061,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(int S, int MN, const float
     }
 }
 
-// ---- weight gradient  C[M][N] = A^T B in the split arithmetic (k_sb_wgrad; A [K][M], B [K][N], K ~ 5e5 rows) ---------------------
-// One workgroup (8 waves, two per SIMD: one wave's splitting runs under the other's MFMAs) owns the WHOLE M x N output in its
-// accumulators and a contiguous range of the rows (split-K, partials reduced in a fixed order afterwards).  Rows arrive in chunks
-// of 16: a thread loads 4 consecutive rows x 4 features with 16-byte loads -- a wave reads 1 KB contiguous pieces of a row --,
-// splits them and writes, per feature and piece, its 4 rows as half of a 16-byte LDS word that holds 8 consecutive rows of one
-// feature: exactly the 8 contraction steps a lane feeds to v_mfma_f32_32x32x16_bf16 (lane (i, g): tile row/column i, steps
-// 8 g .. 8 g + 7), so an operand is one ds_read_b128 and the transposition K-major -> feature-major costs nothing.  Features
-// inside a 64-byte block are XOR-swizzled by (feature / 8) % 4 to spread the writes (lane stride 64 bytes) over the banks; readers
-// of 32 consecutive features stay conflict-free.  The LDS image is double-buffered (2 x 48 KB): chunk c + 1 is split and written
-// while chunk c is multiplied, one barrier per chunk; the raw rows of the next SB_DEPTH chunks are in flight in registers (128 KB
-// per CU: one chunk ahead left the HBM latency exposed, 3.4 us under load against a 2 us matrix phase).
-constexpr int SB_DEPTH = 4;
-
-template <int MT, int NT>
-struct SbWgCfg {
-    static constexpr int M = 128 * MT, N = 128 * NT, COLS = M + N, FQ = COLS / 4;
-    static constexpr int CR = 16, NO = 2;                // rows and row octets per chunk
-    static constexpr int WGM = MT >= NT ? 4 : 2;         // wave grid WGM x WGN over the output, TM x TN tiles of 32 x 32 per wave
-    static constexpr int WGN = 8 / WGM;
-    static constexpr int TM = M / 32 / WGM, TN = N / 32 / WGN;
-    static constexpr int UNITS = 2 * NO * FQ;            // (row octet, half, feature quad) load units per chunk: one per thread
-    static constexpr int IMG = 3 * NO * COLS;            // uint4 per LDS image
-    static constexpr int LDS_BYTES = 2 * IMG * 16;
-};
-
-// feature f's slot in the LDS image
-__device__ __forceinline__ int sb_swz(int f) { return (f & ~3) | ((f & 3) ^ ((f >> 3) & 3)); }
-// A may come in two column blocks (A2 != nullptr: columns M1 .. M - 1 from A2, row stride lda2): the GRU's dW_hh = [dr dz | dnr]^T h_prev
-// takes (dr, dz) from dgi and dnr from its own tensor in ONE pass over h_prev.
-template <int MT, int NT>
-__global__ __launch_bounds__(512) void k_sb_wgrad(const float *__restrict__ A, int64_t lda, const float *__restrict__ B, int64_t ldb, int64_t K,
-                                                  float *__restrict__ part, const float *__restrict__ A2, int64_t lda2, int M1) {
-    using C = SbWgCfg<MT, NT>;
-    extern __shared__ uint4 sb_lds[];                    // [buffer][piece][octet][feature slot] x 16 bytes
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, g = lane >> 5;
-    // loader role: thread -> (octet, half, feature quad)
-    const bool on = tid < C::UNITS;
-    const int rest = on ? tid / C::FQ : 0, col = 4 * (tid % C::FQ);
-    const int row_in_chunk = 4 * rest;                   // = 8 octet + 4 half
-    const bool in_a2 = A2 != nullptr && col >= M1 && col < C::M;
-    const int64_t ld = in_a2 ? lda2 : (col < C::M ? lda : ldb);
-    const float *src = (in_a2 ? A2 + (col - M1) : (col < C::M ? A + col : B + (col - C::M))) + row_in_chunk * ld;
-    const int slot2 = 2 * ((rest >> 1) * C::COLS + col) + (rest & 1), sx = (col >> 3) & 3;   // in 8-byte units
-    // multiplier role
-    const int wm = wave / C::WGN, wn = wave % C::WGN;
-    const int64_t chunks = K / C::CR;                    // full chunks; the K % 16 tail rows are the last workgroup's epilogue
-    const int64_t c_beg = chunks * blockIdx.x / gridDim.x, c_end = chunks * (blockIdx.x + 1) / gridDim.x;
-
-    f32x16 acc[C::TM][C::TN];
-#pragma unroll
-    for (int a = 0; a < C::TM; a++)
-#pragma unroll
-        for (int b = 0; b < C::TN; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
-
-    float4 raw[SB_DEPTH][4];
-    auto fetch = [&](float4 (&r)[4], int64_t c) {
-        if (!on || c >= c_end) return;
-        const float *p = src + c * C::CR * ld;
-#pragma unroll
-        for (int j = 0; j < 4; j++) r[j] = *(const float4 *)(p + j * ld);
-    };
-    // registers -> three bf16 pieces -> LDS image
-    auto stage = [&](const float4 (&r)[4], uint4 *img) {
-        if (!on) return;
-        uint2 *img2 = (uint2 *)img;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            uint32_t p[3][2];
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const float x0 = t == 0 ? r[2 * q].x : t == 1 ? r[2 * q].y : t == 2 ? r[2 * q].z : r[2 * q].w;
-                const float x1 = t == 0 ? r[2 * q + 1].x : t == 1 ? r[2 * q + 1].y : t == 2 ? r[2 * q + 1].z : r[2 * q + 1].w;
-                sb_split2(x0, x1, p[0][q], p[1][q], p[2][q]);
-            }
-#pragma unroll
-            for (int s = 0; s < 3; s++) img2[2 * s * C::NO * C::COLS + slot2 + 2 * (t ^ sx)] = make_uint2(p[s][0], p[s][1]);
-        }
-    };
-    auto multiply = [&](const uint4 *buf) {
-        const uint4 *img = buf + g * C::COLS;
-        constexpr int PS = C::NO * C::COLS;              // piece stride
-        if constexpr (C::TN <= C::TM) {                  // the narrower side's operands stay in registers across the other's tiles
-            uint4 b[C::TN][3];
-#pragma unroll
-            for (int nt = 0; nt < C::TN; nt++) {
-                const int f = sb_swz(C::M + 32 * (wn * C::TN + nt) + i);
-#pragma unroll
-                for (int s = 0; s < 3; s++) b[nt][s] = img[s * PS + f];
-            }
-#pragma unroll
-            for (int mt = 0; mt < C::TM; mt++) {
-                const int f = sb_swz(32 * (wm * C::TM + mt) + i);
-                uint4 a[3];
-#pragma unroll
-                for (int s = 0; s < 3; s++) a[s] = img[s * PS + f];
-#pragma unroll
-                for (int nt = 0; nt < C::TN; nt++) acc[mt][nt] = sb_mma6_32(a, b[nt], acc[mt][nt]);
-            }
-        } else {
-            uint4 a[C::TM][3];
-#pragma unroll
-            for (int mt = 0; mt < C::TM; mt++) {
-                const int f = sb_swz(32 * (wm * C::TM + mt) + i);
-#pragma unroll
-                for (int s = 0; s < 3; s++) a[mt][s] = img[s * PS + f];
-            }
-#pragma unroll
-            for (int nt = 0; nt < C::TN; nt++) {
-                const int f = sb_swz(C::M + 32 * (wn * C::TN + nt) + i);
-                uint4 b[3];
-#pragma unroll
-                for (int s = 0; s < 3; s++) b[s] = img[s * PS + f];
-#pragma unroll
-                for (int mt = 0; mt < C::TM; mt++) acc[mt][nt] = sb_mma6_32(a[mt], b, acc[mt][nt]);
-            }
-        }
-    };
-#pragma unroll
-    for (int d = 0; d < SB_DEPTH; d++) fetch(raw[d], c_beg + d);
-    if (c_beg < c_end) {
-        stage(raw[0], sb_lds);
-        fetch(raw[0], c_beg + SB_DEPTH);
-    }
-    lds_barrier();
-    // invariant at the top of step c: image (c - c_beg) % 2 holds chunk c; raw[(c + k - c_beg) % DEPTH] holds chunk c + k, k = 1 .. DEPTH
-    for (int64_t c = c_beg; c < c_end; c += SB_DEPTH) {
-#pragma unroll
-        for (int d = 0; d < SB_DEPTH; d++) {
-            const int64_t cc = c + d;
-            if (cc >= c_end) break;
-            uint4 *cur = sb_lds + (d & 1) * C::IMG, *nxt = sb_lds + ((d + 1) & 1) * C::IMG;   // SB_DEPTH is even: parity of d = parity of cc - c_beg
-            // the two waves of a SIMD (w and w + 4) run out of phase: one splits the next chunk while the other multiplies
-            if (wave < 4) {
-                if (cc + 1 < c_end) stage(raw[(d + 1) % SB_DEPTH], nxt);
-                fetch(raw[(d + 1) % SB_DEPTH], cc + 1 + SB_DEPTH);
-                multiply(cur);
-            } else {
-                multiply(cur);
-                if (cc + 1 < c_end) stage(raw[(d + 1) % SB_DEPTH], nxt);
-                fetch(raw[(d + 1) % SB_DEPTH], cc + 1 + SB_DEPTH);
-            }
-            lds_barrier();
-        }
-    }
-    if (blockIdx.x == gridDim.x - 1 && (K % C::CR)) {     // the K % 16 tail rows, zero-filled
-        float4 r[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            r[j] = (on && chunks * C::CR + row_in_chunk + j < K) ? *(const float4 *)(src + (chunks * C::CR + j) * ld) : make_float4(0.f, 0.f, 0.f, 0.f);
-        stage(r, sb_lds);
-        lds_barrier();
-        multiply(sb_lds);
-    }
-    // D tile (32 x 32): lane (i, g), register r -> row 8 (r / 4) + 4 g + r % 4 (the A operand's tile row: an M index), column i
-    float *po = part + (size_t)blockIdx.x * C::M * C::N + (size_t)(32 * wm * C::TM + 4 * g) * C::N + 32 * wn * C::TN + i;
-#pragma unroll
-    for (int mt = 0; mt < C::TM; mt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++)
-#pragma unroll
-            for (int nt = 0; nt < C::TN; nt++) po[(size_t)(32 * mt + 8 * (r / 4) + (r % 4)) * C::N + 32 * nt] = acc[mt][nt][r];
-}
+// ---- weight gradient  C[M][N] = A^T B in the split arithmetic: k_sb_wgrad, csrc/sb_wgrad.hpp ------------------------------------------
 
 
 // ---- neighbour mean of the fixed-depth recursive aggregation (DHGN.fcra, DHGN/mappo_parallel.py:204-233) ----------------------
@@ -2560,12 +2397,11 @@ template <int MT, int NT>
 int launch_sb_wgrad(int64_t K, const float *A, int64_t lda, const float *B, int64_t ldb, float *Cm, int accumulate, float *part, hipStream_t st,
                     const float *A2 = nullptr, int64_t lda2 = 0, int M1 = 0) {
     using C = SbWgCfg<MT, NT>;
-    static_assert(C::UNITS <= 512 && C::WGM * C::WGN == 8 && C::TM * C::WGM * 32 == C::M && C::TN * C::WGN * 32 == C::N && SB_DEPTH % 2 == 0, "tiling");
     static std::once_flag once;
     static hipError_t attr_rc = hipSuccess;
     std::call_once(once, [] { attr_rc = hipFuncSetAttribute((const void *)k_sb_wgrad<MT, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES); });
     if (attr_rc != hipSuccess) return (int)attr_rc;
-    hipLaunchKernelGGL((k_sb_wgrad<MT, NT>), dim3(SB_WGRAD_WGS), dim3(512), C::LDS_BYTES, st, A, lda, B, ldb, K, part, A2, lda2, M1);
+    hipLaunchKernelGGL((k_sb_wgrad<MT, NT>), dim3(SB_WGRAD_WGS), dim3(SB_WG_THREADS), C::LDS_BYTES, st, A, lda, B, ldb, K, part, A2, lda2, M1);
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((C::M * C::N + 63) / 64), dim3(256), 0, st, SB_WGRAD_WGS, C::M * C::N, (const float *)part, Cm, accumulate);
     return (int)hipGetLastError();
 }
