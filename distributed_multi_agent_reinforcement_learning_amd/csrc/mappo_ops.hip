@@ -966,10 +966,15 @@ __global__ void k_categorical(int R, int A, const float *probs, uint64_t seed, u
         uint32_t o[4];
         const uint64_t ctr = offset + (uint64_t)r;
         philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-        const float u = ((float)(o[0] >> 8) + 0.5f) * (1.0f / 16777216.0f) * tot;  // (0, tot)
+        // (0, tot]: the top of the grid, 0xFFFFFF + 0.5, rounds to 2^24 (ties to even), so u == tot and no bin edge lies above it
+        const float u = ((float)(o[0] >> 8) + 0.5f) * (1.0f / 16777216.0f) * tot;
         float cum = 0.f;
-        a = A - 1;
-        for (int k = 0; k < A; k++) { cum += p[k]; if (u < cum) { a = k; break; } }
+        a = A - 1;  // (every probability 0)
+        for (int k = 0; k < A; k++) {
+            cum += p[k];
+            if (p[k] > 0.f) a = k;  // the last category with p > 0 so far: where the top draw ends
+            if (u < cum) break;     // a hit bin has p > 0, so a = k
+        }
     }
     action[r] = a;
     if (logp) {
@@ -1077,7 +1082,7 @@ __global__ __launch_bounds__(256) void k_head(int R, int A, const float *__restr
                     uint32_t o[4];
                     const uint64_t ctr = offset + (uint64_t)r;
                     philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-                    const float u = ((float)(o[0] >> 8) + 0.5f) * (1.0f / 16777216.0f) * tot;  // (0, tot)
+                    const float u = ((float)(o[0] >> 8) + 0.5f) * (1.0f / 16777216.0f) * tot;  // (0, tot], as in k_categorical
                     float cum = 0.f;
                     bool found = false;
                     act = AT - 1;
@@ -1085,10 +1090,11 @@ __global__ __launch_bounds__(256) void k_head(int R, int A, const float *__restr
 #pragma unroll
                     for (int a = 0; a < AT; a++) {
                         cum += p[a];
-                        const bool hit = !found && u < cum;
-                        act = hit ? a : act;
-                        pa = hit ? p[a] : pa;
-                        found = found || hit;
+                        // the last category with p > 0 until the hit (which has p > 0): u == tot hits no bin and ends there
+                        const bool take = !found && p[a] > 0.f;
+                        act = take ? a : act;
+                        pa = take ? p[a] : pa;
+                        found = found || u < cum;
                     }
                 }
                 action[r] = act;

@@ -138,6 +138,7 @@ int gae_advnorm(int32_t N, int32_t T, int32_t P, const float *r, const float *v,
  * Categorical(probs).sample() + log_prob for a batch of rows (DHGN/mappo_parallel.py:446-448) with a counter-based
  * generator (Philox4x32-10; stream = (seed, offset + row)): probs [R][A] -> action [R] int32, logp [R].
  * greedy != 0 gives probs.argmax(-1) instead (choose_action(deterministic=True), :442-444; first maximum wins).
+ * A category of probability 0 is never sampled from a row whose total is positive ("Sampling").
  */
 int categorical_sample(int32_t R, int32_t A, const float *probs, uint64_t seed, uint64_t offset, int32_t greedy,
                        int32_t *action, float *logp, void *stream);
