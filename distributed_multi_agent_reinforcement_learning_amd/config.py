@@ -76,8 +76,13 @@ def baseline_config(name="cfg2", **overrides):
         # sequential step scoring of the tick; the P = 15 shipped geometry is what the parity tests cover).
         "cfg4": {"env.num_defender": 16, "map.map_size": [64, 64], "map.center": [32, 32], "map.variance": 12,
                  "map.num_obstacle_block": 5, "algo.depth": 3, "runtime.num_envs": 1024},
+        # BASELINE config 5: env_3d pursuit, 8 agents, 2048 environments over 4 GPUs = 512 per rank, GRU actor / critic.  The
+        # reference has no learner for it: the package's diagonal-Gaussian MAPPO (e3d_agent.py)
+        # with the reference's SLSQP evader.  No reward normalisation on this path.
+        "cfg5": {"runtime.env": "e3d", "env.num_defender": 8, "env.max_steps": 200, "env.action_dim": 3, "algo.depth": 0,
+                 "algo.use_reward_norm": False, "runtime.num_envs": 512, "runtime.e3d_evader": "slsqp"},
     }[name]
-    ov = dict(base)
-    ov["algo.use_reward_norm"] = True  # the shipped `false` crashes the reference's run_episode
+    ov = {"algo.use_reward_norm": True}  # the shipped `false` crashes the reference's run_episode
+    ov.update(base)
     ov.update(overrides)
     return load_config(**ov)

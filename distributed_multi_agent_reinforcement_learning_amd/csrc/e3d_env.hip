@@ -274,6 +274,48 @@ int launch(const e3d_config *c, const e3d_state *st, const double *actions, cons
     return (int)hipGetLastError();
 }
 
+// policy features of the trainer (include/e3d_env.h e3d_policy_features): one thread per (environment, pursuer), differences and
+// means in f64 on the records, stored as fp32.  The actor sees its sensed evader and its communication neighbours (the observation's
+// adjacencies), the critic the whole state.
+constexpr int E3D_FEAT = 16;
+__global__ __launch_bounds__(256) void k_e3d_features(const e3d_config c, const e3d_state st, const e3d_obs_out o, float *af, float *cf) {
+    const int P = c.P;
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)st.N * P) return;
+    const int env = (int)(idx / P), i = (int)(idx - (int64_t)env * P);
+    const double *gp = st.p + (size_t)env * 7 * P, *ge = st.e + (size_t)env * 7;
+    float *fa = af + idx * E3D_FEAT, *fc = cf + idx * E3D_FEAT;
+    if (gp[6 * P + i] == 0.0) {
+        for (int k = 0; k < E3D_FEAT; k++) fa[k] = fc[k] = 0.f;
+        return;
+    }
+    double s[6];
+    for (int k = 0; k < 6; k++) s[k] = gp[k * P + i];
+    const double pe = (double)o.pe_adj[(int64_t)env * o.pe_adj_stride + i], ae = ge[6];
+    const float *pp = o.pp_adj + (int64_t)env * o.pp_adj_stride + (int64_t)i * P;
+    double ma[3] = {0, 0, 0}, mc[3] = {0, 0, 0};
+    int na = 0, nc = 0;
+    for (int j = 0; j < P; j++) {
+        if (j == i) continue;
+        const bool in_a = pp[j] == 1.f, in_c = gp[6 * P + j] != 0.0;
+        if (!in_a && !in_c) continue;
+        const double dx = gp[j] - s[0], dy = gp[P + j] - s[1], dz = gp[2 * P + j] - s[2];
+        if (in_a) { ma[0] += dx; ma[1] += dy; ma[2] += dz; na++; }
+        if (in_c) { mc[0] += dx; mc[1] += dy; mc[2] += dz; nc++; }
+    }
+    for (int k = 0; k < 6; k++) {
+        fa[k] = fc[k] = (float)s[k];
+        fa[6 + k] = (float)((ge[k] - s[k]) * pe);
+        fc[6 + k] = (float)((ge[k] - s[k]) * ae);
+    }
+    fa[12] = (float)pe;
+    fc[12] = (float)ae;
+    for (int k = 0; k < 3; k++) {
+        fa[13 + k] = na ? (float)(ma[k] / na) : 0.f;
+        fc[13 + k] = nc ? (float)(mc[k] / nc) : 0.f;
+    }
+}
+
 struct E3dResetter { e3d_config cfg; int N; std::vector<rngrep::NpRandom> rng; };
 
 }  // namespace
@@ -321,6 +363,16 @@ int e3d_env_tick(const e3d_config *cfg, const e3d_state *st, const double *actio
     e3d_obs_out o0;
     memset(&o0, 0, sizeof o0);
     return launch<true>(cfg, st, actions, e_cmd, reward, active, done, out ? *out : o0, (hipStream_t)stream);
+}
+
+int e3d_policy_features(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, float *actor_feat, float *critic_feat, void *stream) {
+    if (!cfg || !st || !out || !out->pp_adj || !out->pe_adj || !actor_feat || !critic_feat) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    const int64_t rows = (int64_t)st->N * cfg->P;
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(k_e3d_features, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cfg, *st, *out, actor_feat, critic_feat);
+    return (int)hipGetLastError();
 }
 
 int e3d_evader_slsqp(const e3d_config *cfg, const e3d_state *st, double *e_cmd, void *stream) {

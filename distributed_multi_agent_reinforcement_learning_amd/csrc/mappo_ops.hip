@@ -2393,6 +2393,8 @@ int launch_msgw3(const mo_msg_rel *rel, int R, int P, int E, const float *p, int
 
 }  // namespace
 
+#include "gauss_policy.hpp"   // the Gaussian policy head and loss of the env_3d trainer (reuses the helpers above)
+
 constexpr int SB_WGRAD_WGS = 256;  // one workgroup per CU (96 KB of LDS each)
 
 static bool sb_wgrad_shape_ok(int M, int N) {

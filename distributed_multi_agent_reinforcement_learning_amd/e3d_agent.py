@@ -1,0 +1,330 @@
+"""MAPPO with a diagonal-Gaussian policy on env_3d (continuous 3-D pursuit, BASELINE config 5).
+
+The reference has no learner for env_3d (DHGN/mappo_parallel.py:7 imports torch.distributions.Normal and never uses it).
+This module is the package's own: the PPO update, GAE and data-parallel protocol of `MAPPO` / `Trainer`, with
+* features: csrc/e3d_env.hip k_e3d_features (16 per pursuer, actor and critic),
+* encoder: Linear(16 -> 128) + ReLU, Linear(128 -> 128) + ReLU per network, then the 2-layer GRU trunk of `SharedActor`,
+* actor head: Mean = Linear(128 -> A) and a state-independent log_std (A), a = mu + exp(log_std) z, z ~ N(0, 1), unclipped in the
+  buffer and clamped to [-1, 1] for the environment (ops.gauss_head_sample, one launch per tick),
+* critic head: the spectrally normalised value head of `SharedCritic`,
+* loss: ops.ppo_loss_gauss (Normal.log_prob / entropy inside the PPO launch, gradients for mu, log_std and the values).
+"""
+import json
+import os
+import time
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.nn.utils import spectral_norm
+
+from . import ops
+from .e3d_env import ParticleEnv
+from .model import HeadLinear, _make_linear, _ortho_linear, _Trunk
+from .trainer import GradBucket, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed
+
+FEAT = 16   # e3d_policy_features columns (include/e3d_env.h)
+
+
+class E3dEncoder(nn.Module):
+    """Linear(16 -> E) + ReLU, Linear(E -> E) + ReLU on the policy features (rows, 16) -> (rows, E)"""
+
+    def __init__(self, in_dim, embedding_dim):
+        super().__init__()
+        self.fc1 = nn.Linear(in_dim, embedding_dim)
+        self.fc2 = nn.Linear(embedding_dim, embedding_dim)
+
+    def forward(self, x):
+        h = F.relu(ops.linear_skinny(x, self.fc1.weight, self.fc1.bias))
+        return ops.linear(h, self.fc2.weight, self.fc2.bias, relu=True)
+
+
+class GaussianActor(_Trunk):
+    def __init__(self, in_dim, embedding_dim, action_dim, num_layers, rnn_hidden_dim, log_std_init=0.0, is_sn=False):
+        super().__init__()
+        self.shared_net = E3dEncoder(in_dim, embedding_dim)
+        self.num_layers, self.rnn_input_dim, self.rnn_hidden_dim = num_layers, embedding_dim, rnn_hidden_dim
+        self.GRU = nn.GRU(embedding_dim, rnn_hidden_dim, num_layers)
+        self.Mean = _make_linear(rnn_hidden_dim, action_dim, is_sn, HeadLinear)
+        self.log_std = nn.Parameter(torch.full((action_dim,), float(log_std_init)))
+
+
+class E3dCritic(_Trunk):
+    def __init__(self, in_dim, embedding_dim, num_layers, rnn_hidden_dim, is_sn=False):
+        super().__init__()
+        self.shared_net = E3dEncoder(in_dim, embedding_dim)
+        self.num_layers, self.rnn_input_dim, self.rnn_hidden_dim = num_layers, embedding_dim, rnn_hidden_dim
+        self.GRU = nn.GRU(embedding_dim, rnn_hidden_dim, num_layers)
+        head = _ortho_linear(rnn_hidden_dim, 1, HeadLinear)
+        self.Mean = spectral_norm(head) if is_sn else head
+
+
+class _E3dRollout:
+    """static device storage of one lockstep rollout of N environments (the GRU states ping-pong between two buffers: the
+    split-bf16 cell cannot update in place) and the position of its action-sampling stream"""
+
+    def __init__(self, agent, N, P):
+        dev, L, H, A = agent.device, agent.num_layers, agent.rnn_hidden_dim, agent.action_dim
+        z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)
+        self.N, self.P = N, P
+        self.fa, self.fc = z(N, P, FEAT), z(N, P, FEAT)
+        self.hbuf_a, self.hbuf_c = z(2, L, N * P, H), z(2, L, N * P, H)
+        self.action, self.env_action, self.logp, self.v = z(N, P, A), z(N, P, A, dt=torch.float64), z(N, P), z(N, P)
+        self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.t = 0
+
+
+class E3dMAPPO:
+    """rollout (run_episode / explore_env) and PPO update (train) of the Gaussian policy on env_3d"""
+
+    def __init__(self, cfg, batch_size, mini_batch_size, device="cuda"):
+        a = cfg.algo
+        if bool(a.get("use_reward_norm", False)):
+            raise ValueError("algo.use_reward_norm: true is not supported on env_3d (runtime.env: e3d); set it to false")
+        self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
+        self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
+        self.epsilon, self.entropy_coef = a.epsilon, a.entropy_coef
+        self.use_grad_clip, self.use_lr_decay = a.use_grad_clip, a.use_lr_decay
+        self.use_adv_norm, self.use_value_clip = a.use_adv_norm, a.use_value_clip
+        self.action_dim, self.num_layers = int(cfg.env.action_dim), int(a.num_layers)
+        self.embedding_dim, self.rnn_hidden_dim = int(a.embedding_dim), int(a.rnn_hidden_dim)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("E3dMAPPO runs on the GPU only (HIP kernels, no CPU fallback)")
+        sn = bool(a.use_spectral_norm)
+        self.actor = GaussianActor(FEAT, self.embedding_dim, self.action_dim, self.num_layers, self.rnn_hidden_dim,
+                                   float(a.get("log_std_init", 0.0)), sn).to(self.device)
+        self.critic = E3dCritic(FEAT, self.embedding_dim, self.num_layers, self.rnn_hidden_dim, sn).to(self.device)
+        self.ac_parameters = list(self.actor.parameters()) + list(self.critic.parameters())
+        self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
+        rt = cfg.get("runtime", {})
+        self.sample_seed = int(rt.get("seed", 0))
+        self.sample_rank = int(rt.get("sample_rank", 0))   # Philox counter of rank r starts at r << 40 (as MAPPO)
+        self.total_step = 0
+        self.grad_bucket = None
+        self.buffer = None
+        self._states = {}
+
+    # ---- rollout -------------------------------------------------------------------------------------------------------------
+    def _state(self, env):
+        st = self._states.get(id(env))
+        if st is None or st.N != env.num_envs:
+            st = self._states[id(env)] = _E3dRollout(self, env.num_envs, env.p_num)
+        return st
+
+    def _policy_step(self, st, greedy=False):
+        """features -> both encoders -> both GRU cells (one launch per layer) -> value -> Gaussian head and sample"""
+        N, P, E = st.N, st.P, self.embedding_dim
+        emb_a = self.actor.shared_net(st.fa.view(N * P, FEAT))
+        emb_c = self.critic.shared_net(st.fc.view(N * P, FEAT))
+        cur, nxt = st.t & 1, (st.t + 1) & 1
+        fa, fc = ops.gru_step_multi([emb_a.reshape(-1, E), emb_c.reshape(-1, E)], [st.hbuf_a[cur], st.hbuf_c[cur]], [self.actor.GRU, self.critic.GRU],
+                                    hiddens_out=[st.hbuf_a[nxt], st.hbuf_c[nxt]])
+        self.critic.head(fc.contiguous(), out=st.v)
+        m = self.actor.Mean
+        ops.gauss_head_sample(fa.contiguous(), m.weight, m.bias, self.actor.log_std, self.sample_seed, st.counter, st.ticket,
+                              (st.action, st.env_action, st.logp), greedy=greedy)
+        st.t += 1
+
+    def _bootstrap_value(self, st):
+        """the critic's value of the state after the last step (its encoder, GRU cell and head only)"""
+        N, P = st.N, st.P
+        emb_c = self.critic.shared_net(st.fc.view(N * P, FEAT))
+        (fc,) = ops.gru_step_multi([emb_c.reshape(N * P, -1)], [st.hbuf_c[st.t & 1]], [self.critic.GRU], hiddens_out=[st.hbuf_c[(st.t + 1) & 1]])
+        return self.critic.head(fc.contiguous()).reshape(N, P)
+
+    def new_buffer(self, N, T, P):
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)
+        return dict(feat_a=z(N, T, P, FEAT), feat_c=z(N, T, P, FEAT), a_n=z(N, T, P, self.action_dim), a_logprob_n=z(N, T, P), r=z(N, T, P),
+                    active=z(N, T, P), v_n=z(N, T + 1, P))
+
+    @torch.no_grad()
+    def run_episode(self, env, buf=None, greedy=False):
+        """N episodes in lockstep for T = env.max_step ticks.  Row (n, t, p) is live iff environment n was not done before step t and
+        pursuer p was active at its start; rewards, values and the `active` mask of other rows are zero, so is v_n[n, t + 1, p] when
+        pursuer p or episode n ended in step t for any reason but the time limit; v_n[:, T] is the critic's bootstrap value.
+        Returns per-environment (return, captured, length) device tensors."""
+        N, P, T = env.num_envs, env.p_num, env.max_step
+        env.reset()
+        st = self._state(env)
+        st.hbuf_a.zero_()
+        st.hbuf_c.zero_()
+        st.t = 0
+        dev = self.device
+        done_before = torch.zeros(N, dtype=torch.bool, device=dev)
+        ended = torch.zeros(N, dtype=torch.bool, device=dev)       # ended for a reason other than the time limit
+        captured = torch.zeros(N, dtype=torch.bool, device=dev)
+        ret, length = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+        kill_sq = env.kill_radius ** 2
+        for t in range(T):
+            live = env.active_t.float() * (~done_before).float()[:, None]
+            env.policy_features(st.fa, st.fc)
+            self._policy_step(st, greedy)
+            env.evader_step()
+            r, done, active = env.step(st.env_action)
+            rl = r * live
+            if buf is not None:
+                buf["feat_a"][:, t].copy_(st.fa)
+                buf["feat_c"][:, t].copy_(st.fc)
+                buf["a_n"][:, t].copy_(st.action)
+                buf["a_logprob_n"][:, t].copy_(st.logp)
+                buf["v_n"][:, t].copy_(st.v * live)
+                buf["r"][:, t].copy_(rl)
+                buf["active"][:, t].copy_(live)
+            ret += rl.sum(-1)
+            e_dead = env.e[:, 6] == 0
+            reach = ((env.e[:, :3] - env.target) ** 2).sum(-1) <= kill_sq
+            end_nt = (e_dead | (active.sum(-1) == 0) | reach) & ~done_before
+            captured |= e_dead & ~done_before
+            length += (~done_before).float()
+            ended |= end_nt
+            done_before |= done.bool()
+        if buf is not None:
+            env.policy_features(st.fa, st.fc)
+            vmask = env.active_t.float() * (~ended).float()[:, None]
+            buf["v_n"][:, T].copy_(self._bootstrap_value(st) * vmask)
+        return ret, captured, length
+
+    def explore_env(self, env):
+        """one episode per environment into a fresh buffer -> (mean return, buffer, env-steps, stats)"""
+        N, P, T = env.num_envs, env.p_num, env.max_step
+        if self.buffer is None or self.buffer["r"].shape != (N, T, P):
+            self.buffer = self.new_buffer(N, T, P)
+        ret, captured, length = self.run_episode(env, self.buffer)
+        mean_r, cap, mlen = torch.stack((ret.mean(), captured.float().mean(), length.mean())).tolist()
+        return mean_r, self.buffer, N * T, dict(capture_rate=cap, episode_length=mlen)
+
+    # ---- update ------------------------------------------------------------------------------------------------------------------
+    def sequence_forward(self, feat_a, feat_c, batch, steps):
+        """(batch, T, P, 16) features of whole episodes -> mu (batch, T, P, A) and values (batch, T, P), time-major views"""
+        P = feat_a.shape[2]
+        R = batch * steps * P
+        emb_a, emb_c = self.actor.shared_net(feat_a.reshape(R, FEAT)), self.critic.shared_net(feat_c.reshape(R, FEAT))
+        h0 = [torch.zeros(m.num_layers, batch * P, m.rnn_hidden_dim, dtype=emb_a.dtype, device=emb_a.device) for m in (self.actor, self.critic)]
+        fa, fc = ops.gru_multi([emb_a, emb_c], h0, [self.actor.GRU, self.critic.GRU], agents=P, steps=steps, zero_state=True)
+        fa, fc = fa.reshape(steps, batch, P, -1), fc.reshape(steps, batch, P, -1)
+        mu = self.actor.Mean(fa).permute(1, 0, 2, 3)
+        values = self.critic.Mean(fc).permute(1, 0, 2, 3)[..., 0]
+        return mu, values
+
+    def train(self, buf, total_steps):
+        """GAE + advantage normalisation over all rows (ops.gae_advnorm), then sequential mini-batches of whole episodes, the
+        gradient clipped to 5.0 after each (as MAPPO.train).  Returns (critic loss, actor loss) averaged over the mini-batches."""
+        N, T, P = buf["r"].shape
+        with torch.no_grad():
+            adv, v_target = ops.gae_advnorm(buf["r"], buf["v_n"], buf["active"], self.gamma, self.lamda, self.use_adv_norm)
+        if self.grad_bucket is not None:
+            self.grad_bucket.zero()
+        else:
+            self.ac_optimizer.zero_grad()
+        obj_c = obj_a = 0.0
+        k = 0
+        for n0 in range(0, N, self.mini_batch_size):
+            n1 = min(n0 + self.mini_batch_size, N)
+            mu, values = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, T)
+            la, lc = ops.ppo_loss_gauss(mu, self.actor.log_std, buf["a_n"][n0:n1], values, buf["a_logprob_n"][n0:n1], adv[n0:n1],
+                                        buf["active"][n0:n1], buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1],
+                                        self.epsilon, self.entropy_coef, self.use_value_clip)
+            (la + lc).backward()
+            if self.use_grad_clip:
+                torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
+            obj_c = obj_c + lc.detach().double()
+            obj_a = obj_a + la.detach().double()
+            k += 1
+        if self.use_lr_decay:
+            self.lr_decay(total_steps)
+        return float(obj_c) / k, float(obj_a) / k
+
+    def lr_decay(self, total_steps):
+        lr_now = self.lr * (1 - total_steps / self.max_train_steps)
+        for p in self.ac_optimizer.param_groups:
+            p["lr"] = lr_now
+        self.total_step = total_steps
+
+    def save_model(self, cwd):
+        os.makedirs(cwd, exist_ok=True)
+        torch.save({"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}, os.path.join(cwd, "e3d_state_dicts.pt"))
+
+
+def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0):
+    """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env)"""
+    base = int(cfg.runtime.get("seed", 0)) + seed_offset + max(1000, num_envs) * rank
+    env = ParticleEnv(num_envs=num_envs, seeds=[base + n for n in range(num_envs)], device=device, max_step=int(cfg.env.max_steps),
+                      evader=str(cfg.runtime.get("e3d_evader", "slsqp")))
+    env.initialize(int(cfg.env.num_defender))
+    return env
+
+
+class E3dTrainer:
+    """One rank of the data-parallel env_3d job: rollout, then epochs x (update, gradient all-reduce, Adam step)."""
+
+    def __init__(self, cfg, num_envs=None, num_eval_envs=64, eval_every=0, tuned_gemms=True):
+        self.rank, self.local_rank, self.world = init_distributed()
+        self.tuned_gemms = enable_tuned_gemms() if tuned_gemms else False
+        self.cfg = cfg
+        self.device = torch.device("cuda", self.local_rank % max(1, torch.cuda.device_count()))
+        torch.cuda.set_device(self.device)
+        self.num_envs = int(num_envs if num_envs is not None else cfg.runtime.num_envs)
+        self.env = make_env(cfg, self.num_envs, self.rank, self.device)
+        torch.manual_seed(int(cfg.runtime.get("seed", 0)))
+        self.agent = E3dMAPPO(cfg, self.num_envs, max(1, round(self.num_envs / 10)), self.device)
+        self.agent.sample_rank = self.rank
+        self.bucket = GradBucket(self.agent.ac_parameters)
+        self.agent.grad_bucket = self.bucket
+        broadcast_weights_([self.agent.actor, self.agent.critic])
+        self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
+        self.eval_env = None
+        self.total_steps = 0
+        self.iteration = 0
+
+    def iterate(self):
+        """-> (env-steps of this iteration over all ranks, log record)"""
+        cfg, agent = self.cfg, self.agent
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        mean_r, buf, steps, stats = agent.explore_env(self.env)
+        ev[1].record()
+        self.total_steps += steps * self.world
+        for _ in range(int(cfg.algo.epochs)):
+            with torch.enable_grad():
+                obj_c, obj_a = agent.train(buf, self.total_steps)
+            allreduce_sum_(self.bucket.flat)
+            agent.ac_optimizer.step()
+        ev[2].record()
+        self.iteration += 1
+        self.last_events = ev
+        log = dict(iteration=self.iteration, total_steps=self.total_steps, mean_return=mean_r, capture_rate=stats["capture_rate"],
+                   episode_length=stats["episode_length"], critic_loss=obj_c, actor_loss=obj_a)
+        if self.eval_every and self.iteration % self.eval_every == 0 and self.rank == 0:
+            log.update(self.evaluate())
+        return steps * self.world, log
+
+    def evaluate(self):
+        """synchronous greedy episode (a = mu) on num_eval_envs environments of their own seeds and sampling stream"""
+        if self.eval_env is None:
+            self.eval_env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6)
+        ret, captured, length = self.agent.run_episode(self.eval_env, None, greedy=True)
+        r, c, l = torch.stack((ret.mean(), captured.float().mean(), length.mean())).tolist()
+        return dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+
+    def last_breakdown_ms(self):
+        ev = self.last_events
+        return ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+
+
+def train_e3d(cfg, max_iterations=None, num_eval_envs=64, eval_every=1):
+    """the env_3d training loop (main --config cfg5): until max_train_steps env-steps or max_iterations; rank 0 prints one JSON log
+    line per iteration and saves the final weights under algo.save_cwd"""
+    tr = E3dTrainer(cfg, num_eval_envs=num_eval_envs, eval_every=eval_every)
+    while tr.total_steps < cfg.algo.max_train_steps:
+        t0 = time.time()
+        steps, log = tr.iterate()
+        if tr.rank == 0:
+            log["seconds"] = round(time.time() - t0, 3)
+            print(json.dumps(log), flush=True)
+        if max_iterations is not None and tr.iteration >= max_iterations:
+            break
+    if tr.rank == 0:
+        tr.agent.save_model(cfg.algo.save_cwd)
+    return tr

@@ -55,6 +55,7 @@ def load_library():
         L.e3d_evader_slsqp_nit.argtypes = [vp] * 5
         L.e3d_evader_slsqp_host.argtypes = [vp, C.c_int32] + [vp] * 5
         L.e3d_resetter_reset.argtypes = [vp, vp, vp, vp, C.c_int32]
+        L.e3d_policy_features.argtypes = [vp] * 6
         _lib = L
     return _lib
 
@@ -187,6 +188,15 @@ class ParticleEnv:
             cmd = torch.stack((torch.atan2(d[:, 1], d[:, 0]) / math.pi, torch.atan2(d[:, 2], torch.hypot(d[:, 0], d[:, 1])) / (math.pi / 2),
                                torch.ones_like(d[:, 0])), -1)
         self._cmd = torch.as_tensor(cmd, dtype=torch.float64, device=self.device).reshape(self.num_envs, 3).contiguous()
+
+    def policy_features(self, actor_feat, critic_feat):
+        """the trainer's (N, P, 16) fp32 features of the current state into the two dense tensors (e3d_policy_features,
+        include/e3d_env.h): the actor's from its sensed evader and communication neighbours, the critic's from the whole state"""
+        for t in (actor_feat, critic_feat):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (self.num_envs, self.p_num, 16) and t.device == self.p.device
+        _check(self.L.e3d_policy_features(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_void_p(actor_feat.data_ptr()),
+                                          C.c_void_p(critic_feat.data_ptr()), _stream()), "e3d_policy_features")
+        return actor_feat, critic_feat
 
     def step(self, action):
         """:205-219 (preceded by the evader's move with the command of evader_step) -> (reward (N,P), done (N,), active (N,P));

@@ -3,14 +3,20 @@
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg3 --iterations 10
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m distributed_multi_agent_reinforcement_learning_amd.main
 
-`--config` is one of the BASELINE configurations (cfg1..cfg3) or the path of a reference-schema config.yaml;
-dotted overrides follow as KEY=VALUE (e.g. runtime.num_envs=1024 algo.depth=1).
+`--config` is one of the BASELINE configurations (cfg1..cfg5) or the path of a reference-schema config.yaml;
+dotted overrides follow as KEY=VALUE (e.g. runtime.num_envs=1024 algo.depth=1).  cfg5 (or runtime.env=e3d) trains the
+diagonal-Gaussian MAPPO on env_3d (e3d_agent.train_e3d):
+
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --iterations 50
 """
 import argparse
 import ast
 
 from .config import baseline_config, load_config
+from .e3d_agent import train_e3d
 from .trainer import train_agent_multiprocessing
+
+BASELINES = ("cfg1", "cfg2", "cfg3", "cfg4", "cfg5")
 
 
 def main(argv=None):
@@ -28,8 +34,10 @@ def main(argv=None):
             ov[k] = ast.literal_eval(v)
         except (ValueError, SyntaxError):
             ov[k] = v
-    cfg = baseline_config(args.config, **ov) if args.config in ("cfg1", "cfg2", "cfg3", "cfg4") else load_config(args.config, **ov)
-    train_agent_multiprocessing(cfg, max_iterations=args.iterations, num_eval_envs=args.eval_envs, eval_every=args.eval_every)
+    cfg = baseline_config(args.config, **ov) if args.config in BASELINES else load_config(args.config, **ov)
+    if str(cfg.runtime.get("env", "pursuit")) == "e3d":
+        return train_e3d(cfg, max_iterations=args.iterations, num_eval_envs=args.eval_envs, eval_every=args.eval_every)
+    return train_agent_multiprocessing(cfg, max_iterations=args.iterations, num_eval_envs=args.eval_envs, eval_every=args.eval_every)
 
 
 if __name__ == "__main__":

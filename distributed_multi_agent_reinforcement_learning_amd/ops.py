@@ -16,7 +16,7 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "dhgn_msg_agg_ones_sorted_bwd", "dhgn_msg_agg_ones_sorted_workspace", "gae_advnorm", "gae_advnorm_workspace", "categorical_sample",
            "categorical_sample_counter",
            "gru_gates_fwd", "gru_gates_bwd", "gru_cell_fwd", "gru_cell_fwd_multi", "gru_cell_split_fwd_multi", "sb_gemm_n128", "sb_gemm", "gru_seq_fwd", "gru_seq_fwd_multi", "gru_seq_split_fwd_multi", "gru_seq_split_bwd_multi", "gru_seq_save_elems", "gru_seq_bwd", "gru_seq_bwd_multi", "gru_seq_bwd_workspace", "wgrad_tn", "wgrad_tn_workspace", "wgrad_split_tn", "wgrad_split_tn2", "wgrad_split_workspace", "rollout_record", "ppo_loss_fwd_bwd", "ppo_loss_prob_fwd_bwd", "ppo_loss_workspace",
-           "mappo_ops_error_string")
+           "gauss_head_sample", "ppo_loss_gauss_fwd_bwd", "ppo_loss_gauss_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -96,6 +96,10 @@ def load_library():
         L.ppo_loss_workspace.restype = i64
         L.ppo_loss_fwd_bwd.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp, vp]
         L.ppo_loss_prob_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp]
+        L.gauss_head_sample.argtypes = [i32, i32, i32, vp, vp, vp, vp, C.c_uint64, vp, vp, i32, vp, vp, vp, vp]
+        L.ppo_loss_gauss_workspace.restype = i64
+        L.ppo_loss_gauss_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, f32, f32,
+                                             i32, vp, vp, vp, vp, vp]
         L.sb_split_diag.argtypes = [i64, vp, vp, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
@@ -561,6 +565,25 @@ def head_sample(feat, W, b, seed, counter, ticket, out, greedy=False):
     _check(L.head_sample(R, W.shape[0], HEAD_FEATURES, _ptr(feat), _ptr(W.detach().contiguous()), _ptr(b.detach().contiguous()), int(seed),
                          _ptr(counter), _ptr(ticket), 1 if greedy else 0, _ptr(action), _ptr(logp), _stream()), "head_sample")
     return action, logp
+
+
+def gauss_head_sample(feat, W, b, log_std, seed, counter, ticket, out, greedy=False):
+    """a = mu + exp(log_std) z, z ~ N(0, 1), mu = feat W^T + b (a = mu when greedy), for a diagonal-Gaussian head with <= 16 outputs on
+    128 features in one launch (csrc/gauss_policy.hpp k_gauss_head).  The noise comes from the Philox stream of head_sample: row r at
+    counter *counter + r, block j of four dimensions at counter word c2 = j; `counter` (int64, one element) advances by the number of
+    rows (replayable in a captured graph).  ticket: a zero int32 tensor of one element.  out = (action fp32 (.., A) unclipped,
+    env_action f64 (.., A) = clamp(action, -1, 1), logp fp32 (..) = Normal(mu, sigma).log_prob(action).sum(-1))."""
+    assert _head_ok(feat, W, b) and log_std.shape == (W.shape[0],)
+    L = load_library()
+    action, env_action, logp = out
+    A, R = W.shape[0], feat.numel() // HEAD_FEATURES
+    assert action.dtype == torch.float32 and env_action.dtype == torch.float64 and logp.dtype == torch.float32
+    assert all(t.is_contiguous() for t in out) and action.numel() == R * A and env_action.numel() == R * A and logp.numel() == R
+    assert counter.dtype == torch.int64 and counter.numel() == 1 and ticket.dtype == torch.int32 and ticket.numel() == 1
+    _check(L.gauss_head_sample(R, A, HEAD_FEATURES, _ptr(feat), _ptr(W.detach().contiguous()), _ptr(b.detach().contiguous()),
+                               _ptr(log_std.detach().contiguous()), int(seed), _ptr(counter), _ptr(ticket), 1 if greedy else 0, _ptr(action),
+                               _ptr(env_action), _ptr(logp), _stream()), "gauss_head_sample")
+    return action, env_action, logp
 
 
 WGRAD_MIN_ROWS = 4096  # below this the BLAS library's single-workgroup-tile GEMMs are as fast
@@ -1193,6 +1216,51 @@ def ppo_loss_prob(prob, action, values_now, logp_old, adv, active, values_old, v
     :692-706; csrc/mappo_ops.hip k_ppo_loss_prob).  prob (mb, T, P, A), values_now (mb, T, P): any strides over the first three
     dimensions (the heads' outputs are time-major views)."""
     return _PPOLossProb.apply(prob, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip)
+
+
+class _PPOLossGauss(torch.autograd.Function):
+    """(actor_loss, critic_loss) of one mini-batch of a diagonal-Gaussian policy: Normal(mu, exp(log_std)).log_prob(action).sum(-1) and
+    .entropy().sum(-1) inside the loss launch (ppo_loss_gauss_fwd_bwd), which also writes the gradients w.r.t. mu and log_std."""
+
+    @staticmethod
+    def forward(ctx, mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip):
+        L = load_library()
+        _need_gpu(mu, "ppo_loss_gauss")
+        A = mu.shape[-1]
+        d0, d1, d2 = mu.shape[:3]
+        n = d0 * d1 * d2
+        ts = [t.contiguous() for t in (logp_old, adv, active, v_target)]
+        act = action.contiguous()
+        ls = log_std.detach().contiguous()
+        vo = values_old.contiguous() if values_old is not None else None
+        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == mu.shape[:3]
+        assert act.shape == mu.shape and act.dtype == torch.float32 and ls.shape == (A,) and mu.stride(3) == 1
+        dev = mu.device
+        asum = active.sum().reshape(1)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)      # the layout of mu (a time-major view)
+        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
+        g_ls = torch.empty(A, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.ppo_loss_gauss_workspace(), dtype=torch.uint8, device=dev)
+        ms, vs = mu.stride(), values_now.stride()
+        _check(L.ppo_loss_gauss_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(act), _ptr(ts[0]), _ptr(ts[1]),
+                                        _ptr(ts[2]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon),
+                                        float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(g_ls), _ptr(ws), _stream()),
+               "ppo_loss_gauss_fwd_bwd")
+        ctx.save_for_backward(g_mu, g_ls, g_v)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, ga, gc):
+        g_mu, g_ls, g_v = ctx.saved_tensors
+        return g_mu * ga, g_ls * ga, g_v * gc, None, None, None, None, None, None, None, None, None
+
+
+def ppo_loss_gauss(mu, log_std, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True):
+    """ppo_loss(Normal(mu, exp(log_std)).log_prob(action).sum(-1), Normal(..).entropy().sum(-1), ...) in one launch with the gradients
+    w.r.t. mu, log_std and values_now (csrc/gauss_policy.hpp k_ppo_loss_gauss).  mu (mb, T, P, A) and values_now (mb, T, P): any strides
+    over the first three dimensions (time-major views), mu's last dimension dense; action (mb, T, P, A), the rest (mb, T, P)."""
+    return _PPOLossGauss.apply(mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip)
 
 
 def ppo_loss(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True):

@@ -54,6 +54,15 @@ int e3d_env_observe(const e3d_config *cfg, const e3d_state *st, const e3d_obs_ou
 int e3d_env_tick(const e3d_config *cfg, const e3d_state *st, const double *actions, const double *e_cmd, float *reward,
                  uint8_t *active, uint8_t *done, const e3d_obs_out *out, void *stream);
 
+/* Policy features of the env_3d trainer, both (N, P, 16) fp32 tensors (dense) in one launch; reads the records and out->pp_adj /
+ * out->pe_adj of the current state (e3d_env_observe / e3d_env_tick fill them).  Pursuer i, state s_i = (x, y, z, phi, gamma, v), evader e:
+ *   cols 0-5   s_i                                  (both)
+ *   cols 6-11  (e - s_i) pe_adj[i]  |  (e - s_i) active_e
+ *   col  12    pe_adj[i]            |  active_e
+ *   cols 13-15 mean of pos_j - pos_i over j != i with pp_adj[i][j] = 1  |  over every active j != i  (0 if there is none)
+ * (actor | critic); rows of inactive pursuers are zero. */
+int e3d_policy_features(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, float *actor_feat, float *critic_feat, void *stream);
+
 /* The reference's evader: eva.e_f (eva.py:87-148) -- scipy's SLSQP (ftol 1e-6, <= 100 iterations, 2-point finite-difference
  * gradient) minimising obj_func (:212-240) over (heading, pitch, speed), started at the evader's state, bounded by the
  * environment's ang_lmt / v_lmt (:130-135) -- written as the command e_cmd [N][3] that e3d_env_tick consumes; zeros when the

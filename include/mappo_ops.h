@@ -298,6 +298,26 @@ int ppo_loss_prob_fwd_bwd(int64_t n, int32_t A, const float *prob, float *grad_p
                           float entropy_coef, int32_t use_value_clip, float *losses, float *grad_values, void *workspace, void *stream);
 
 /*
+ * Diagonal-Gaussian policy of the env_3d trainer (csrc/gauss_policy.hpp), A <= 16 action dimensions on H = 128 features.
+ * gauss_head_sample: mu = feat [R][H] W^T + b, a = mu + exp(log_std) z with z ~ N(0, 1) from the Philox stream of head_sample (row r:
+ *   counter *counter + r, key seed; noise block j = dims 4 j .. 4 j + 3 uses counter word c2 = j; u = ((o >> 8) + 1/2) 2^-24 per output
+ *   word, Box-Muller on (o0, o1) and (o2, o3)); a = mu when greedy != 0 (z = 0).  action [R][A] fp32 (unclipped), env_action [R][A]
+ *   f64 = clamp(a, -1, 1), logp [R] = sum_d (-z_d^2 / 2 - log_std_d - ln sqrt(2 pi)).  *counter advances by R; ticket as head_sample.
+ * ppo_loss_gauss_fwd_bwd: the losses of ppo_loss_prob_fwd_bwd with logp_now = Normal(mu, exp(log_std)).log_prob(action).sum(-1) and
+ *   entropy = Normal.entropy().sum(-1); mu / grad_mu [.., A] at i0 m_s0 + i1 m_s1 + i2 m_s2, values_now as in ppo_loss_prob_fwd_bwd;
+ *   action [n][A] dense.  Also writes grad_log_std [A] = d losses[0] / d log_std (f64 per-block partials, fixed order);
+ *   workspace >= ppo_loss_gauss_workspace() bytes.
+ */
+int gauss_head_sample(int32_t R, int32_t A, int32_t H, const float *feat, const float *W, const float *b, const float *log_std, uint64_t seed,
+                      uint64_t *counter, uint32_t *ticket, int32_t greedy, float *action, double *env_action, float *logp, void *stream);
+int64_t ppo_loss_gauss_workspace(void);
+int ppo_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
+                           const float *log_std, const float *action, const float *logp_old, const float *adv, const float *active,
+                           const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                           const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses, float *grad_values,
+                           float *grad_log_std, void *workspace, void *stream);
+
+/*
  * Records one rollout tick into the replay buffer (MAPPO.run_episode's minibuffer.store_transition,
  * DHGN/mappo_parallel.py:783-805, for N environments at once): for every item, row n of the dense [N][row_bytes] source
  * goes to dst + n * dst_row_stride (slot [n, t] of an (N, T, ...) buffer tensor); i32_to_f32 converts int32 actions to

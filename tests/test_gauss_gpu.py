@@ -1,0 +1,354 @@
+"""GPU checks of the env_3d Gaussian policy: gauss_head_sample and ppo_loss_gauss against tests/gauss_ref.py, e3d_policy_features
+against numpy, and the E3dMAPPO agent / E3dTrainer (buffer invariants, rollout-update agreement, gradients against an f64 torch
+re-evaluation, determinism, training steps, the full cfg5 size)."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import gauss_ref
+
+pytestmark = pytest.mark.gpu
+
+
+def _ops():
+    from distributed_multi_agent_reinforcement_learning_amd import ops
+    return ops
+
+
+def _head_inputs(R, A, seed):
+    g = torch.Generator().manual_seed(seed)
+    feat = (torch.randn(R, 128, generator=g) * 0.3).cuda()
+    W, b = (torch.randn(A, 128, generator=g) * 0.1).cuda(), (torch.randn(A, generator=g) * 0.3).cuda()
+    ls = (torch.randn(A, generator=g) * 0.4).cuda()
+    return feat, W, b, ls
+
+
+def _head_call(feat, W, b, ls, seed, counter, greedy=False):
+    R, A = feat.shape[0], W.shape[0]
+    out = (torch.empty(R, A, device="cuda"), torch.empty(R, A, dtype=torch.float64, device="cuda"), torch.empty(R, device="cuda"))
+    ticket = torch.zeros(1, dtype=torch.int32, device="cuda")
+    with torch.no_grad():
+        _ops().gauss_head_sample(feat, W, b, ls, seed, counter, ticket, out, greedy=greedy)
+    assert int(ticket.item()) == 0
+    return out
+
+
+GRID_STRIDE_R = 1024 * 256 + 4099   # more rows than the launch's 1024 workgroups x 256 lanes cover in one pass
+
+
+@pytest.mark.parametrize("A,R", [(A, R) for A in (1, 2, 3, 4, 8, 16) for R in (1, 63, 64, 65, 16384)] + [(3, GRID_STRIDE_R), (16, GRID_STRIDE_R)])
+def test_gauss_head_sample_matches_reference(A, R):
+    feat, W, b, ls = _head_inputs(R, A, 7 * A + R)
+    seed, c0 = 0x5EED0000ABCD + A, (3 << 40) + 0xFFFFFF00   # a counter whose low word carries inside the launch
+    counter = torch.full((1,), c0, dtype=torch.int64, device="cuda")
+    a, ea, lp = _head_call(feat, W, b, ls, seed, counter)
+    assert int(counter.item()) == c0 + R
+    mu_dev, ea_g, lp_g = _head_call(feat, W, b, ls, seed, torch.full((1,), c0, dtype=torch.int64, device="cuda"), greedy=True)
+    mu_ref, z_ref, _, _, lp_ref = gauss_ref.head_sample(feat.cpu().numpy(), W.cpu().numpy(), b.cpu().numpy(), ls.cpu().numpy(), seed, c0)
+    mu_dev = mu_dev.double().cpu().numpy()
+    np.testing.assert_allclose(mu_dev, mu_ref, rtol=0, atol=2e-5)                    # greedy gives mu
+    np.testing.assert_array_equal(ea_g.cpu().numpy(), np.clip(mu_dev, -1, 1))
+    sigma = np.exp(ls.double().cpu().numpy())
+    z_dev = (a.double().cpu().numpy() - mu_dev) / sigma
+    assert np.all(np.abs(z_dev - z_ref) <= 4e-6 * (1 + np.abs(z_ref))), np.abs(z_dev - z_ref).max()
+    np.testing.assert_allclose(lp.double().cpu().numpy(), lp_ref, rtol=1e-5, atol=1e-5)
+    np.testing.assert_array_equal(ea.cpu().numpy(), np.clip(a.cpu().numpy(), -1, 1).astype(np.float64))   # clamp of the stored action
+    np.testing.assert_allclose(lp_g.double().cpu().numpy(), np.full(R, -(ls.double().cpu().numpy() + gauss_ref.HALF_LN_2PI).sum()), rtol=1e-6)
+
+
+@pytest.mark.parametrize("A,R", [(3, 65), (16, 16384)])
+def test_gauss_head_sample_two_calls_equal_one(A, R):
+    feat, W, b, ls = _head_inputs(2 * R, A, 3)
+    c1 = torch.full((1,), 12345, dtype=torch.int64, device="cuda")
+    one = _head_call(feat, W, b, ls, 9, c1)
+    c2 = torch.full((1,), 12345, dtype=torch.int64, device="cuda")
+    first, second = _head_call(feat[:R].contiguous(), W, b, ls, 9, c2), _head_call(feat[R:].contiguous(), W, b, ls, 9, c2)
+    assert int(c1.item()) == int(c2.item()) == 12345 + 2 * R
+    for k in range(3):
+        assert torch.equal(one[k], torch.cat((first[k], second[k])))
+
+
+def test_gauss_head_sample_graph_replay_equals_eager():
+    A, R = 3, 16384
+    feat, W, b, ls = _head_inputs(R, A, 5)
+    ops = _ops()
+    ticket = torch.zeros(1, dtype=torch.int32, device="cuda")
+    eager = []
+    c = torch.full((1,), 1 << 40, dtype=torch.int64, device="cuda")
+    for _ in range(3):
+        eager.append(_head_call(feat, W, b, ls, 4, c))
+    out = (torch.empty(R, A, device="cuda"), torch.empty(R, A, dtype=torch.float64, device="cuda"), torch.empty(R, device="cuda"))
+    cg = torch.full((1,), 1 << 40, dtype=torch.int64, device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s), torch.no_grad():
+        ops.gauss_head_sample(feat, W, b, ls, 4, cg, ticket, out)   # warm-up (also the first draw)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    cg.fill_(1 << 40)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g), torch.no_grad():
+        ops.gauss_head_sample(feat, W, b, ls, 4, cg, ticket, out)
+    cg.fill_(1 << 40)
+    for k in range(3):
+        g.replay()
+        torch.cuda.synchronize()
+        for j in range(3):
+            assert torch.equal(out[j], eager[k][j]), (k, j)
+    assert int(cg.item()) == (1 << 40) + 3 * R
+
+
+def _loss_case(A, use_value_clip, mb=32, T=50, P=8, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    mu_tm = r(T, mb, P, A) * 0.5                      # the heads' outputs are time-major: (T, mb, P, ..) permuted
+    ls = r(A) * 0.3
+    act = mu_tm.permute(1, 0, 2, 3) + torch.exp(ls) * r(mb, T, P, A)
+    lp = torch.distributions.Normal(mu_tm.permute(1, 0, 2, 3), torch.exp(ls)).log_prob(act).sum(-1)
+    lp_old = lp + r(mb, T, P) * 0.1
+    eps = 0.05
+    for edge in (1 - eps, 1 + eps):       # keep every ratio clear of the clip edges, where the gradient jumps
+        lp_old = torch.where((torch.exp(lp - lp_old) - edge).abs() < 1e-3, lp_old - 0.01, lp_old)
+    v_tm = r(T, mb, P, 1)
+    vo = v_tm.permute(1, 0, 2, 3)[..., 0] + r(mb, T, P) * 0.1
+    vo = torch.where(((v_tm.permute(1, 0, 2, 3)[..., 0] - vo).abs() - eps).abs() < 1e-3, vo + 0.01, vo)
+    adv, vt = r(mb, T, P), r(mb, T, P)
+    active = (torch.rand(mb, T, P, generator=g) < 0.8).double()
+    return dict(mu_tm=mu_tm, ls=ls, act=act, lp_old=lp_old, v_tm=v_tm, vo=vo if use_value_clip else None, adv=adv, vt=vt, active=active)
+
+
+def _gpu_loss(c, use_value_clip, eps=0.05, ent=0.05):
+    f = lambda x: None if x is None else x.float().cuda()
+    mu_tm, ls, v_tm = (f(c[k]).requires_grad_() for k in ("mu_tm", "ls", "v_tm"))
+    la, lc = _ops().ppo_loss_gauss(mu_tm.permute(1, 0, 2, 3), ls, f(c["act"]), v_tm.permute(1, 0, 2, 3)[..., 0], f(c["lp_old"]), f(c["adv"]),
+                                   f(c["active"]), f(c["vo"]), f(c["vt"]), eps, ent, use_value_clip)
+    (la + lc).backward()
+    return la.detach(), lc.detach(), mu_tm.grad, ls.grad, v_tm.grad
+
+
+@pytest.mark.parametrize("use_value_clip", [True, False])
+@pytest.mark.parametrize("A", [3, 16])
+def test_ppo_loss_gauss_matches_f64_torch(A, use_value_clip):
+    c = _loss_case(A, use_value_clip, seed=A)
+    la, lc, gmu, gls, gv = _gpu_loss(c, use_value_clip)
+    # f64 torch on the fp32-rounded inputs
+    d = {k: (None if v is None else v.float().double().cuda()) for k, v in c.items()}
+    mu_tm, ls, v_tm = (d[k].clone().requires_grad_() for k in ("mu_tm", "ls", "v_tm"))
+    ra, rc = gauss_ref.torch_ppo_loss_gauss(mu_tm.permute(1, 0, 2, 3), ls, d["act"], v_tm.permute(1, 0, 2, 3)[..., 0], d["lp_old"], d["adv"], d["active"],
+                                            d["vo"], d["vt"], 0.05, 0.05, use_value_clip)
+    (ra + rc).backward()
+    assert abs(la.item() - ra.item()) <= 1e-5 * abs(ra.item()) + 1e-7
+    assert abs(lc.item() - rc.item()) <= 1e-5 * abs(rc.item()) + 1e-7
+    for got, ref in ((gmu, mu_tm.grad), (gls, ls.grad), (gv, v_tm.grad)):
+        assert got.shape == ref.shape and got.stride() == ref.stride()
+        err = (got.double() - ref).abs().max().item()
+        assert err <= 1e-5 * ref.abs().max().item() + 1e-12, (err, ref.abs().max().item())
+    # reruns are bit-identical (f64 partials added in a fixed order)
+    again = _gpu_loss(c, use_value_clip)
+    for x, y in zip((la, lc, gmu, gls, gv), again):
+        assert torch.equal(x, y)
+
+
+# ---- e3d_policy_features ---------------------------------------------------------------------------------------------------------
+def _features_ref(p, e, pp, pe):
+    """p (N, 7, P), e (N, 7) f64 records; pp (N, P, P), pe (N, P) -> actor, critic (N, P, 16) fp32"""
+    N, _, P = p.shape
+    fa, fc = np.zeros((N, P, 16), np.float32), np.zeros((N, P, 16), np.float32)
+    for n in range(N):
+        for i in range(P):
+            if p[n, 6, i] == 0:
+                continue
+            s = p[n, :6, i]
+            ae = e[n, 6]
+            fa[n, i, :6] = fc[n, i, :6] = s
+            fa[n, i, 6:12] = (e[n, :6] - s) * pe[n, i]
+            fc[n, i, 6:12] = (e[n, :6] - s) * ae
+            fa[n, i, 12], fc[n, i, 12] = pe[n, i], ae
+            ja = [j for j in range(P) if j != i and pp[n, i, j] == 1]
+            jc = [j for j in range(P) if j != i and p[n, 6, j] != 0]
+            for js, f in ((ja, fa), (jc, fc)):
+                if js:
+                    f[n, i, 13:16] = np.mean([p[n, :3, j] - p[n, :3, i] for j in js], axis=0)
+    return fa, fc
+
+
+@pytest.mark.parametrize("P", [3, 8, 12])
+def test_policy_features_match_numpy(P):
+    from distributed_multi_agent_reinforcement_learning_amd.e3d_env import ParticleEnv
+    N = 37
+    env = ParticleEnv(num_envs=N)
+    env.initialize(P)
+    env.reset()
+    g = torch.Generator().manual_seed(P)
+    env.p.copy_(torch.randn(N, 7, P, generator=g, dtype=torch.float64) * 5)
+    env.p[:, 6] = (torch.rand(N, P, generator=g) < 0.75).double()            # dead pursuers
+    env.e.copy_(torch.randn(N, 7, generator=g, dtype=torch.float64) * 5)
+    env.e[:, 6] = (torch.rand(N, generator=g) < 0.7).double()                # dead evaders
+    env.obs["pp_adj"].copy_((torch.rand(N, P, P, generator=g) < 0.5).float())  # random adjacency
+    env.obs["pe_adj"].copy_((torch.rand(N, P, 1, generator=g) < 0.5).float())
+    fa, fc = torch.full((N, P, 16), 7.0, device="cuda"), torch.full((N, P, 16), 7.0, device="cuda")
+    env.policy_features(fa, fc)
+    ra, rc = _features_ref(env.p.cpu().numpy(), env.e.cpu().numpy(), env.obs["pp_adj"].cpu().numpy(), env.obs["pe_adj"].cpu().numpy()[..., 0])
+    np.testing.assert_allclose(fa.cpu().numpy(), ra, rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(fc.cpu().numpy(), rc, rtol=1e-6, atol=1e-6)
+
+
+# ---- agent ----------------------------------------------------------------------------------------------------------------------------
+N_AGENT, T_AGENT = 64, 100
+
+
+def _agent(seed=0, **ov):
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config
+    from distributed_multi_agent_reinforcement_learning_amd.e3d_agent import E3dMAPPO, make_env
+    cfg = baseline_config("cfg5", **{"runtime.num_envs": N_AGENT, "env.max_steps": T_AGENT, "runtime.seed": seed, **ov})
+    env = make_env(cfg, N_AGENT)
+    torch.manual_seed(seed)
+    return E3dMAPPO(cfg, N_AGENT, max(1, round(N_AGENT / 10))), env
+
+
+def _explore(agent, env):
+    mean_r, buf, steps, stats = agent.explore_env(env)
+    return {k: v.clone() for k, v in buf.items()}, steps, stats
+
+
+def test_agent_buffer_invariants():
+    agent, env = _agent()
+    buf, steps, stats = _explore(agent, env)
+    N, T, P = buf["r"].shape
+    assert steps == N * T and (N, T, P) == (N_AGENT, T_AGENT, 8)
+    act, r, v = buf["active"], buf["r"], buf["v_n"]
+    assert torch.all((act == 0) | (act == 1))
+    assert torch.all(act[:, 1:] <= act[:, :-1])               # a row once not live stays not live
+    assert torch.all(r[act == 0] == 0) and torch.all(v[:, :T][act == 0] == 0)
+    # an environment that ended before T: every later row is not live, and its terminal values are zero
+    alive_env = act.amax(-1)                                  # (N, T): some pursuer live
+    length = alive_env.sum(-1)
+    ended = length < T
+    for n in torch.nonzero(ended).flatten().tolist():
+        L = int(length[n])
+        assert torch.all(alive_env[n, :L] == 1) and torch.all(act[n, L:] == 0)
+        assert torch.all(v[n, L:] == 0)
+    assert abs(stats["episode_length"] - length.float().mean().item()) < 1e-3
+    assert torch.isfinite(buf["a_n"]).all() and torch.isfinite(buf["a_logprob_n"]).all() and torch.isfinite(v).all()
+    print(f"environments ended before T: {int(ended.sum())} / {N}; capture rate {stats['capture_rate']:.3f}")
+
+
+def test_agent_update_forward_reproduces_rollout():
+    agent, env = _agent(1)
+    buf, _, _ = _explore(agent, env)
+    T = buf["r"].shape[1]
+    with torch.enable_grad():
+        mu, values = agent.sequence_forward(buf["feat_a"], buf["feat_c"], N_AGENT, T)
+    lp = torch.distributions.Normal(mu.detach(), torch.exp(agent.actor.log_std.detach())).log_prob(buf["a_n"]).sum(-1)
+    live = buf["active"] == 1
+    assert live.sum() > 0
+    assert (lp - buf["a_logprob_n"])[live].abs().max().item() <= 1e-4
+    assert (values.detach() - buf["v_n"][:, :T])[live].abs().max().item() <= 1e-4
+
+
+def _oracle_grads(agent0_actor, agent0_critic, buf, adv, v_target, mb, eps, ent, clip, dtype, device):
+    """f64 (or fp32) torch re-evaluation of one update: nn.GRU, F.linear, Normal and the reference's PPO formula; gradients summed over
+    the sequential mini-batches (no clipping) -> dict name -> grad"""
+    actor, critic = copy.deepcopy(agent0_actor).to(device, dtype), copy.deepcopy(agent0_critic).to(device, dtype)
+    N, T, P = buf["r"].shape
+    cv = lambda x: None if x is None else x.to(device, dtype)
+
+    def enc(m, x):
+        h = F.relu(F.linear(x, m.shared_net.fc1.weight, m.shared_net.fc1.bias))
+        return F.relu(F.linear(h, m.shared_net.fc2.weight, m.shared_net.fc2.bias))
+
+    for n0 in range(0, N, mb):
+        n1 = min(n0 + mb, N)
+        B = n1 - n0
+        outs = []
+        for m, key in ((actor, "feat_a"), (critic, "feat_c")):
+            x = enc(m, cv(buf[key][n0:n1]))                                  # (B, T, P, E)
+            x = x.permute(1, 0, 2, 3).reshape(T, B * P, -1)
+            y, _ = m.GRU(x)
+            outs.append(y.reshape(T, B, P, -1))
+        mu = F.linear(outs[0], actor.Mean.weight, actor.Mean.bias).permute(1, 0, 2, 3)
+        values = critic.Mean(outs[1]).permute(1, 0, 2, 3)[..., 0]
+        la, lc = gauss_ref.torch_ppo_loss_gauss(mu, actor.log_std, cv(buf["a_n"][n0:n1]), values, cv(buf["a_logprob_n"][n0:n1]), cv(adv[n0:n1]),
+                                                cv(buf["active"][n0:n1]), cv(buf["v_n"][n0:n1, :-1]) if clip else None, cv(v_target[n0:n1]),
+                                                eps, ent, clip)
+        (la + lc).backward()
+    return {("actor." + k): p.grad.double().cpu() for k, p in actor.named_parameters()} | \
+           {("critic." + k): p.grad.double().cpu() for k, p in critic.named_parameters()}
+
+
+def test_agent_gradients_match_f64_torch():
+    agent, env = _agent(2)
+    buf, steps, _ = _explore(agent, env)
+    with torch.no_grad():                    # move the policy away from the rollout's: ratios leave 1 on both sides of the clip
+        g = torch.Generator(device="cuda").manual_seed(0)
+        agent.actor.log_std.add_(0.1)
+        for p in list(agent.actor.Mean.parameters()) + list(agent.actor.shared_net.fc2.parameters()):
+            p.add_(torch.randn(p.shape, generator=g, device="cuda") * 0.05 * p.abs().mean())
+    T = buf["r"].shape[1]
+    with torch.no_grad():                    # the loss sees ratios on both sides of the clip range
+        mu, _ = agent.sequence_forward(buf["feat_a"], buf["feat_c"], N_AGENT, T)
+        lp = torch.distributions.Normal(mu, torch.exp(agent.actor.log_std)).log_prob(buf["a_n"]).sum(-1)
+        ratio = torch.exp(lp - buf["a_logprob_n"])[buf["active"] == 1]
+        assert (ratio < 1 - agent.epsilon).any() and (ratio > 1 + agent.epsilon).any()
+    actor0, critic0 = copy.deepcopy(agent.actor), copy.deepcopy(agent.critic)   # (the critic's spectral-norm vectors as the update finds them)
+    agent.use_grad_clip = False
+    with torch.enable_grad():
+        agent.train(buf, steps)
+    adv, v_target = _ops().gae_advnorm(buf["r"], buf["v_n"], buf["active"], agent.gamma, agent.lamda, agent.use_adv_norm)
+    args = (buf, adv, v_target, agent.mini_batch_size, agent.epsilon, agent.entropy_coef, agent.use_value_clip)
+    ref = _oracle_grads(actor0, critic0, *args, torch.float64, "cuda")
+    o32 = [_oracle_grads(actor0, critic0, *args, torch.float32, "cuda"), _oracle_grads(actor0, critic0, *args, torch.float32, "cpu")]
+    got = {("actor." + k): p.grad for k, p in agent.actor.named_parameters()} | {("critic." + k): p.grad for k, p in agent.critic.named_parameters()}
+    assert set(got) == set(ref) and "actor.log_std" in got
+    for k, r in ref.items():
+        gk = got[k].double().cpu()
+        noise = max((o[k] - r).abs().max().item() for o in o32)
+        scale = r.abs().max().item()
+        err = (gk - r).abs().max().item()
+        assert err <= 4 * noise + 2e-5 * scale, (k, err, noise, scale)
+
+
+def test_agent_determinism():
+    def run():
+        agent, env = _agent(3)
+        buf, steps, _ = _explore(agent, env)
+        with torch.enable_grad():
+            agent.train(buf, steps)
+        agent.ac_optimizer.step()
+        return buf, [p.detach().clone() for p in agent.ac_parameters]
+    b1, p1 = run()
+    b2, p2 = run()
+    for k in b1:
+        assert torch.equal(b1[k], b2[k]), k
+    for x, y in zip(p1, p2):
+        assert torch.equal(x, y)
+
+
+def test_trainer_iterates():
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config
+    from distributed_multi_agent_reinforcement_learning_amd.e3d_agent import E3dTrainer
+    cfg = baseline_config("cfg5", **{"runtime.num_envs": N_AGENT, "env.max_steps": 50})
+    tr = E3dTrainer(cfg, num_eval_envs=16, eval_every=2)
+    before = [p.detach().clone() for p in tr.agent.ac_parameters]
+    ls0 = tr.agent.actor.log_std.detach().clone()
+    logs = [tr.iterate()[1] for _ in range(2)]
+    for log in logs:
+        assert np.isfinite(log["critic_loss"]) and np.isfinite(log["actor_loss"]) and np.isfinite(log["mean_return"])
+        assert 0 <= log["capture_rate"] <= 1 and 0 < log["episode_length"] <= 50
+    assert "eval_return" in logs[1] and np.isfinite(logs[1]["eval_return"])
+    assert not torch.equal(tr.agent.actor.log_std.detach(), ls0)
+    assert sum(not torch.equal(a, b.detach()) for a, b in zip(before, tr.agent.ac_parameters)) >= len(before) - 1
+    assert tr.total_steps == 2 * N_AGENT * 50
+
+
+def test_cfg5_full_size_one_iteration():
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config
+    from distributed_multi_agent_reinforcement_learning_amd.e3d_agent import E3dTrainer
+    tr = E3dTrainer(baseline_config("cfg5", **{"runtime.num_envs": 2048}))
+    steps, log = tr.iterate()
+    assert steps == 2048 * 200
+    assert np.isfinite(log["critic_loss"]) and np.isfinite(log["actor_loss"])
+    print("cfg5 2048 envs:", log, "rollout / update ms:", tr.last_breakdown_ms())
