@@ -5,13 +5,17 @@ in the loop (fused HIP env tick + batched actor/critic forward), GAE, PPO-clip/v
 samples, gradient all-reduce (RCCL) and the Adam step.  value = env-steps of all ranks / wall time.
 Synthetic data: seeded random maps, random-init weights (no datasets or checkpoints exist for this workload).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4] [--num-envs E] [--no-cpu-baseline] [--no-secondary]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4] [--num-envs E]
                   [--scaling weak|strong [--total-envs E]] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-secondary] [--no-kernel-probes] [--tick-samples S]]
 
 `--gpus N` with N > 1 starts its own N rank processes (a `torch.distributed.run` child, one rank per GPU over RCCL) before
 anything in this process touches the GPU; under an outer `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.
-The headline line is BASELINE config 2 (depth 0, "GRU"); the same line carries `configs.cfg3` (DHGN depth 3, the
-configuration with end-to-end reference parity) measured the same way right after it.
+The headline line is BASELINE config 2 (depth 0, "GRU").  A plain run does only what that figure needs: set-up, warm-up, the
+K timed iterations, the dump if asked for, and the result line.  `--full` adds everything else the benchmark measures, each
+in runs of its own: the CPU baseline (before the GPU is opened), the environment tick's roofline and the isolated kernel
+timings after the headline's timed iterations, then `configs.cfg3` (DHGN depth 3, the configuration with end-to-end reference
+parity) and `configs.cfg2_fp32_mfma` measured the same way; the `--no-*` options leave parts of that out.
 `--dump-outputs DIR` writes what the last timed iteration of the headline configuration produced as DIR/<name>.npy (see
 dump_outputs); the inputs depend only on the arguments, so two builds can be compared output for output.
 """
@@ -531,10 +535,12 @@ def main():
     ap.add_argument("--num-envs", type=int, default=None, help="environments per GPU (default: the config's)")
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--update-group", default=None, help="runtime.update_group: mini-batches per autograd graph of the update (default: auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-probes", action="store_true", help="skip the isolated kernel timings (roofline_compute_kernels): profiling runs")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the cfg3 measurement that rides along with cfg2")
-    ap.add_argument("--tick-samples", type=int, default=150)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baseline, rooflines, kernel timings, cfg3 and fp32 runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-probes", action="store_true", help="--full: skip the isolated kernel timings (roofline_compute_kernels): profiling runs")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the cfg3 and fp32 measurements that ride along with cfg2")
+    ap.add_argument("--tick-samples", type=int, default=150, help="--full: environment ticks of the roofline measurement")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): every rank owns the config's environments; strong: --total-envs (default: the config's count) divided over the ranks")
     ap.add_argument("--total-envs", type=int, default=None, help="--scaling strong: environments of the whole job")
@@ -555,16 +561,16 @@ def main():
     # The CPU baseline runs FIRST, while this process has not touched the GPU: its one-process-per-core workers are started from a
     # clean parent (the GPU box allows only a few processes with the device open; a worker never opens it -- tools/probe_gpu_open.py).
     cpu = None
-    if not args.no_cpu_baseline and world_env == 1:
+    if args.full and not args.no_cpu_baseline and world_env == 1:
         T_cpu = min(args.max_steps or 150, 150)
         cpu = cpu_baseline(args.config, T_cpu)
 
     import torch.distributed as dist
     from distributed_multi_agent_reinforcement_learning_amd.trainer import dist_env
     rank, local_rank, world = dist_env()
-    main_res = run_config(args.config, args, with_roofline=True, dump_dir=args.dump_outputs)
+    main_res = run_config(args.config, args, with_roofline=args.full, dump_dir=args.dump_outputs)
     second = fp32_run = None
-    if args.config == "cfg2" and not args.no_secondary:
+    if args.full and args.config == "cfg2" and not args.no_secondary:
         second = run_config("cfg3", args, with_roofline=False)
         # the same headline configuration with every matrix product on the fp32 MFMA kernels / the BLAS library (runtime.matmul: fp32),
         # for comparison: the default evaluates fp32 products from exact three-way bf16 operand splits
@@ -585,8 +591,9 @@ def main():
                       if main_res["matmul"] == "split_bf16" else "f64 environment / f32 policy"),
             "data": "synthetic (seeded random maps, random-init weights)",
             "matmul": ("fp32 products from exact three-way bf16 splits of the fp32 operands (6 bf16 MFMAs per product, fp32 accumulation, fp32 storage; error "
-                       "against f64 = an fp32 GEMM's, tests/test_ops_gpu.py); configs.cfg2_fp32_mfma is the same run on fp32 MFMA / BLAS"
+                       "against f64 = an fp32 GEMM's, tests/test_ops_gpu.py); with --full, configs.cfg2_fp32_mfma is the same run on fp32 MFMA / BLAS"
                        if main_res["matmul"] == "split_bf16" else "fp32 MFMA kernels / BLAS library fp32 GEMMs"),
+            "full": args.full,
             "config": {"workload": main_res["workload"], "envs_per_gpu": main_res["envs_per_gpu"], "episode_steps": main_res["episode_steps"],
                        "mini_batch_size": main_res["mini_batch_size"], "update_group": main_res["update_group"],
                        "parallelism": f"dp{world} ({args.scaling} scaling: " + (f"{main_res['envs_per_gpu'] * world} environments in total, {main_res['envs_per_gpu']} per rank)"
@@ -594,10 +601,11 @@ def main():
                        "collective": (f"torch.distributed {main_res['backend']} all_reduce(SUM) of one flat fp32 gradient bucket per epoch"
                                       if world > 1 else None)},
             "ppo_updates_per_s": main_res["ppo_updates_per_s"], "breakdown_ms": main_res["breakdown_ms"], "hbm_peak_GB": main_res["hbm_peak_GB"],
-            "roofline": main_res["roofline"], "roofline_packed_rows": main_res["roofline_packed_rows"],
-            "roofline_iteration": main_res["roofline_iteration"], "roofline_replan_tick": main_res["roofline_replan_tick"],
-            "roofline_compute_kernels": main_res.get("roofline_compute_kernels", {}),
+            "roofline_iteration": main_res["roofline_iteration"],
         }
+        if args.full:
+            out.update(roofline=main_res["roofline"], roofline_packed_rows=main_res["roofline_packed_rows"],
+                       roofline_replan_tick=main_res["roofline_replan_tick"], roofline_compute_kernels=main_res.get("roofline_compute_kernels", {}))
         dom = main_res.get("roofline_compute_kernels", {}).get("gru_seq_bwd_grouped")
         if dom is not None:   # where the iteration's largest launch stands, without opening profiles/
             out["dominant_kernel"] = {"kernel": dom["kernel"], "us_per_launch": dom["us_per_launch"], "launches_per_iteration": int(2 * main_res.get("epochs", 1)),

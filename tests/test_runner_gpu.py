@@ -71,12 +71,13 @@ def test_training_loop_checkpoints_and_recorder(tmp_path):
 def test_two_rank_bench_rehearsal(tmp_path):
     """`python bench.py --gpus 2` -- the driver's own command form -- starts its two ranks itself (torch.distributed.run child)
     before touching the GPU; here both ranks share the one GPU, so gloo stands in for RCCL.  The N > 1 path -- shard seeds per
-    rank, gradient all-reduce, max-over-ranks timing, one JSON line from rank 0 -- runs end to end."""
+    rank, gradient all-reduce, max-over-ranks timing, one JSON line from rank 0 -- runs end to end, with --full so that the
+    roofline measurement of every rank and rank 0's kernel timings run too."""
     env = dict(os.environ, DMARL_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "cfg1",
-           "--num-envs", "16", "--max-steps", "12", "--tick-samples", "12"]
+           "--num-envs", "16", "--max-steps", "12", "--full", "--tick-samples", "12"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -84,6 +85,7 @@ def test_two_rank_bench_rehearsal(tmp_path):
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["scaling"] == "weak" and j["value"] > 0 and "gloo" in j["config"]["collective"]
     assert abs(j["value"] - 2 * 16 * 12 / (j["ms_per_step"] * 1e-3)) / j["value"] < 1e-3
+    assert j["full"] and j["roofline"]["us_per_launch"] > 0
     # a launcher whose world size contradicts --gpus is an error, not silently ignored
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=dict(env, WORLD_SIZE="3", RANK="0"),
                          capture_output=True, text=True, timeout=120)
