@@ -81,6 +81,11 @@ def baseline_config(name="cfg2", **overrides):
         # with the reference's SLSQP evader.  No reward normalisation on this path.
         "cfg5": {"runtime.env": "e3d", "env.num_defender": 8, "env.max_steps": 200, "env.action_dim": 3, "algo.depth": 0,
                  "algo.use_reward_norm": False, "runtime.num_envs": 512, "runtime.e3d_evader": "slsqp"},
+        # BASELINE config 4 on the environment it names: env_n2n, 16 pursuers, 8192 environments over 8 GPUs = 1024 per rank, the DHGN
+        # actor / critic (n2n_agent.py) against the reference's SLSQP evader; max_steps = the reference's
+        # episode_limit.  No reward normalisation on this path.
+        "cfg4_n2n": {"runtime.env": "n2n", "env.num_defender": 16, "env.num_evader": 1, "env.max_steps": 100, "algo.depth": 3,
+                     "algo.use_reward_norm": False, "runtime.num_envs": 1024, "runtime.n2n_evader": "slsqp"},
     }[name]
     ov = {"algo.use_reward_norm": True}  # the shipped `false` crashes the reference's run_episode
     ov.update(base)

@@ -1738,9 +1738,12 @@ __global__ void k_gru_bias_reduce(int nblk, const float *partials, float *db_ih,
     }
 }
 
+// K = 0 (an empty relation: env_n2n has no obstacles) is valid: no neighbour is read (q and adj may be NULL), the forward writes
+// 0 * 1 / 1e-12 = 0 into the relation's slot and the backward's partials, hence dW and db, are exactly 0 -- the reference's
+// normalize(adj, p=1) of an empty neighbour set, for the observed adjacency and the critic's ones alike.
 int check_msg(int R, int P, int K, int E, int din, int q_div, int adj_mode, const void *adj, const void *kvalid, const void *e) {
-    if (R < 0 || P < 1 || P > MAX_P || K < 1 || E < 64 || E > 256 || (E & 63) || (din != 4 && din != 8) || q_div < 1) return MO_ERR_BAD_ARG;
-    if ((adj_mode == MO_ADJ_TENSOR || adj_mode == MO_ADJ_BITS) && !adj) return MO_ERR_BAD_ARG;
+    if (R < 0 || P < 1 || P > MAX_P || K < 0 || E < 64 || E > 256 || (E & 63) || (din != 4 && din != 8) || q_div < 1) return MO_ERR_BAD_ARG;
+    if ((adj_mode == MO_ADJ_TENSOR || adj_mode == MO_ADJ_BITS) && !adj && K > 0) return MO_ERR_BAD_ARG;
     if (adj_mode == MO_ADJ_VALID && !kvalid) return MO_ERR_BAD_ARG;
     if (adj_mode < 0 || adj_mode > 3) return MO_ERR_BAD_ARG;
     if (din == 8 && !e) return MO_ERR_BAD_ARG;

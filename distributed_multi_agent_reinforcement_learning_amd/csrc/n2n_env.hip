@@ -150,17 +150,114 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n(const n2n_config c, const n2
         }
 }
 
+// the lane layout of the tick and of the policy kernels: PT (group of lanes per environment) and the workgroups covering N environments
+int n2n_lanes(const n2n_config *c, int N, int *blocks) {
+    const int m = c->P > c->E ? c->P : c->E;
+    const int pt = m <= 8 ? 8 : (m <= 16 ? 16 : (m <= 32 ? 32 : 64));
+    const int envs_per_block = (WAVE / pt) * WPB;
+    *blocks = (N + envs_per_block - 1) / envs_per_block;
+    return pt;
+}
+
 template <bool TICK>
 int launch_n2n(const n2n_config *c, const n2n_state *st, const int32_t *actions, const double *e_cmd, float *reward, uint8_t *active, uint8_t *done,
                const n2n_obs_out &o, hipStream_t s) {
-    const int m = c->P > c->E ? c->P : c->E;
-    const int pt = m <= 8 ? 8 : (m <= 16 ? 16 : (m <= 32 ? 32 : 64));
-    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    int blocks;
+    const int pt = n2n_lanes(c, st->N, &blocks);
     const N2nThr th{sq_threshold(c->kill_radius), sq_threshold(c->p_comm_range), sq_threshold(c->p_sen_range)};
 #define N2N_GO(PT) hipLaunchKernelGGL((k_n2n<PT, TICK>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, actions, e_cmd, reward, active, done, o, th)
     if (pt == 8) N2N_GO(8); else if (pt == 16) N2N_GO(16); else if (pt == 32) N2N_GO(32); else N2N_GO(64);
 #undef N2N_GO
     return (int)hipGetLastError();
+}
+
+// ---- MAPPO on env_n2n (n2n_agent.py): the policy's inputs before a tick, the buffer bookkeeping after it ----
+// Lane layout of k_n2n: a group of PT lanes per environment, slot a = pursuer a and evader a.  The per-group masks (live pursuers,
+// active evaders) are ballots, so the adjacency loops run a uniform trip count over the group's lanes with no shuffles.
+
+template <int PT>
+__device__ __forceinline__ unsigned long long group_bits(bool v, int base) {
+    constexpr unsigned long long GM = (PT == 64) ? ~0ull : ((1ull << PT) - 1ull);
+    return (__ballot(v) >> base) & GM;
+}
+
+__device__ __forceinline__ void store4(float *d, bool on, double x, double y, double phi, double v) {
+    d[0] = on ? (float)x : 0.f;
+    d[1] = on ? (float)y : 0.f;
+    d[2] = on ? (float)(v * cos(phi)) : 0.f;
+    d[3] = on ? (float)(v * sin(phi)) : 0.f;
+}
+
+template <int PT>
+__global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_inputs(const n2n_config c, const n2n_state st, const uint8_t *done_before,
+                                                                  const n2n_policy_io io) {
+    constexpr int G = WAVE / PT;
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT, base = lane - a;
+    const int env = wave * G + g, P = c.P, E = c.E;
+    const bool ev = env < st.N, pv = ev && a < P, evv = ev && a < E;
+    const double *gp = st.p + (size_t)(ev ? env : 0) * 5 * P, *ge = st.e + (size_t)(ev ? env : 0) * 5 * E;
+    const bool db = ev && done_before && done_before[env] != 0;
+    const bool live = pv && gp[4 * P + a] != 0.0 && !db;
+    const bool e_on = evv && ge[4 * E + a] != 0.0;
+    const unsigned long long lm = group_bits<PT>(live, base), em = group_bits<PT>(e_on, base);
+    if (pv && io.live) io.live[(int64_t)env * io.live_rs + a] = live ? 1.f : 0.f;
+    if (pv && io.p4) store4(io.p4 + (int64_t)env * io.p4_rs + 4 * a, live, gp[a], gp[P + a], gp[2 * P + a], gp[3 * P + a]);
+    if (evv && io.e4) store4(io.e4 + (int64_t)env * io.e4_rs + 4 * a, e_on, ge[a], ge[E + a], ge[2 * E + a], ge[3 * E + a]);
+    // e_ref: the lowest-index active evader (its lane writes), zeros from slot 0 when none is active
+    const int first = em ? __ffsll((long long)em) - 1 : 0;
+    if (ev && io.e_ref && a == first)
+        store4(io.e_ref + (int64_t)env * io.e_ref_rs, e_on, ge[first], ge[E + first], ge[2 * E + first], ge[3 * E + first]);
+    // the actor's adjacencies: entries between live pursuers (pp), between a live pursuer and an active evader (pe)
+    if (io.pp_adj)
+        for (int k0 = 0; k0 < P * P; k0 += PT) {
+            const int k = k0 + a, i = k / P, j = k - i * P;
+            if (ev && k < P * P)
+                io.pp_adj[(int64_t)env * io.pp_adj_rs + k] = ((lm >> i) & (lm >> j) & 1ull) ? io.pp_in[(int64_t)env * io.pp_in_rs + k] : 0.f;
+        }
+    if (io.pe_adj)
+        for (int k0 = 0; k0 < P * E; k0 += PT) {
+            const int k = k0 + a, i = k / E, j = k - i * E;
+            if (ev && k < P * E)
+                io.pe_adj[(int64_t)env * io.pe_adj_rs + k] = ((lm >> i) & (em >> j) & 1ull) ? io.pe_in[(int64_t)env * io.pe_in_rs + k] : 0.f;
+        }
+}
+
+template <int PT>
+__global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_config c, const n2n_state st, const float *reward, const uint8_t *done,
+                                                                  const n2n_record_io io, const n2n_policy_acc acc, const double kill) {
+    constexpr int G = WAVE / PT;
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT, base = lane - a;
+    const int env = wave * G + g, P = c.P, E = c.E;
+    const bool ev = env < st.N, pv = ev && a < P, evv = ev && a < E;
+    const double *gp = st.p + (size_t)(ev ? env : 0) * 5 * P, *ge = st.e + (size_t)(ev ? env : 0) * 5 * E;
+    const float live = pv ? io.live[(int64_t)env * io.live_rs + a] : 0.f;
+    const float rl = pv ? reward[(size_t)env * P + a] * live : 0.f;
+    if (pv) {
+        if (io.r) io.r[(int64_t)env * io.r_rs + a] = rl;
+        if (io.active) io.active[(int64_t)env * io.active_rs + a] = live;
+        if (io.v) io.v[(int64_t)env * io.v_rs + a] = io.value[(int64_t)env * io.value_rs + a] * live;
+    }
+    // the state after the tick (the records): why the episode may have ended, as get_done of the tick evaluates it
+    const bool p_on = pv && gp[4 * P + a] != 0.0, e_on = evv && ge[4 * E + a] != 0.0;
+    double tx = 0, ty = 0;
+    if (ev) { tx = st.target[2 * env]; ty = st.target[2 * env + 1]; }
+    const bool reach = evv && sq2(ge[a] - tx, ge[E + a] - ty) <= kill;
+    const int pa = __popcll(group_bits<PT>(p_on, base)), ea = __popcll(group_bits<PT>(e_on, base));
+    const bool rc = group_bits<PT>(reach, base) != 0ull;
+    float s = 0.f;  // the step's team reward, summed in agent order
+    for (int k = 0; k < P; k++) s += __shfl(rl, base + k);
+    const bool db = ev && acc.done_before[env] != 0;
+    const bool ended = ev && (acc.ended[env] != 0 || ((rc || pa == 0 || ea == 0) && !db));
+    if (pv && io.v_next && (!p_on || ended)) io.v_next[(int64_t)env * io.v_next_rs + a] = 0.f;
+    if (ev && a == 0) {
+        acc.ended[env] = ended;
+        if (ea == 0 && !db) acc.captured[env] = 1;
+        if (!db) acc.length[env] += 1.f;
+        acc.ret[env] += s;
+        acc.done_before[env] = db || done[env] != 0;
+    }
 }
 
 // ---- the reference's evader: eva.e_f (eva.py:36-80), a bounded SLSQP minimisation of obj_func over the heading ----
@@ -350,6 +447,37 @@ int n2n_evader_slsqp_host(const n2n_config *cfg, int32_t N, const double *p, con
     else if (cfg->P <= 32) n2n_evader_host_pm<32>(*cfg, N, p, e, target, e_cmd, nit);
     else n2n_evader_host_pm<64>(*cfg, N, p, e, target, e_cmd, nit);
     return 0;
+}
+
+int n2n_policy_inputs(const n2n_config *cfg, const n2n_state *st, const uint8_t *done_before, const n2n_policy_io *io, void *stream) {
+    if (!cfg || !st || !io || (io->pp_adj && !io->pp_in) || (io->pe_adj && !io->pe_in)) return N2N_ERR_NULL;
+    const int rc = n2n_config_check(cfg);
+    if (rc) return rc;
+    if (st->N < 1) return 0;
+    int blocks;
+    const int pt = n2n_lanes(cfg, st->N, &blocks);
+    hipStream_t s = (hipStream_t)stream;
+#define N2N_IN(PT) hipLaunchKernelGGL((k_n2n_policy_inputs<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, done_before, *io)
+    if (pt == 8) N2N_IN(8); else if (pt == 16) N2N_IN(16); else if (pt == 32) N2N_IN(32); else N2N_IN(64);
+#undef N2N_IN
+    return (int)hipGetLastError();
+}
+
+int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
+                      const n2n_policy_acc *acc, void *stream) {
+    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value)) return N2N_ERR_NULL;
+    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return N2N_ERR_NULL;
+    const int rc = n2n_config_check(cfg);
+    if (rc) return rc;
+    if (st->N < 1) return 0;
+    int blocks;
+    const int pt = n2n_lanes(cfg, st->N, &blocks);
+    const double kill = sq_threshold(cfg->kill_radius);
+    hipStream_t s = (hipStream_t)stream;
+#define N2N_REC(PT) hipLaunchKernelGGL((k_n2n_policy_record<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, reward, done, *io, *acc, kill)
+    if (pt == 8) N2N_REC(8); else if (pt == 16) N2N_REC(16); else if (pt == 32) N2N_REC(32); else N2N_REC(64);
+#undef N2N_REC
+    return (int)hipGetLastError();
 }
 
 void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seeds) {

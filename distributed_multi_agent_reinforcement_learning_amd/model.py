@@ -69,13 +69,15 @@ class DHGN(nn.Module):
             self.AGG_layers[f"AGG_fcra_{k}"] = _make_linear(E, E, is_sn)
 
     # -- encoder (:241-304) ----------------------------------------------------------------------------
-    def encoder(self, p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid=None, q_div=1, out=None):
+    def encoder(self, p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid=None, q_div=1, out=None, e_ref=None):
         """p (R,P,4), e (R,1,4), o (R/q_div,O,4), adj_* (R,P,{P,1,O}) (adj_o may be bit-packed int32 rows) -> h0 (R,P,E).
         is_critic: adjacency := ones (AttributeDataset, :64-65); in a batched rollout the obstacle relation uses ones
-        over the first o_kvalid[row] (real) obstacles, in training over all padded slots."""
+        over the first o_kvalid[row] (real) obstacles, in training over all padded slots.
+        env_n2n: e (R,K_e,4) with several evaders and e_ref (R,4) the one the defender relation's p_i - e term reads (None: e
+        itself, K_e = 1); O = 0 is an empty obstacle relation."""
         M = self.MSG_layers
         m3 = ops.msg_agg3(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
-                          is_critic, o_kvalid, q_div)                                  # (R, P, 3, E)
+                          is_critic, o_kvalid, q_div, e_ref)                           # (R, P, 3, E)
         return self._after_messages(p, m3, out)
 
     def _after_messages(self, p, m3, out=None):
@@ -97,12 +99,12 @@ class DHGN(nn.Module):
             h0 = ops.linear(e2, Ws[:, ind:], ops.linear_skinny(p2, Ws[:, :ind], self.semantic_layer.bias), consume_addend=True, x_link=link)
         return h0.reshape(R, P, E)
 
-    def encoder_pair_train(self, p, e, o, adj_p, adj_e, adj_o, q_div=1):
+    def encoder_pair_train(self, p, e, o, adj_p, adj_e, adj_o, q_div=1, e_ref=None):
         """the update's encoder of actor and critic together -> (h0_actor, h0_critic): one message pass for both networks
         (ops.msg_agg3_pair_train), then the layers per network; same numbers as encoder(.., False) and encoder(.., True)."""
         M = self.MSG_layers
         m3a, m3c = ops.msg_agg3_pair_train(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
-                                           q_div)
+                                           q_div, e_ref)
         return self._after_messages(p, m3a), self._after_messages(p, m3c)
 
     # -- fixed-depth recursive aggregation over neighbours' historical embeddings (:204-233) --------------
@@ -123,9 +125,9 @@ class DHGN(nn.Module):
         h.relu_link = carry[1]   # for a caller that is the ONLY consumer of h (the update hands it to the first GRU layer)
         return h
 
-    def forward(self, p, e, o, adj_p, adj_e, adj_o, hist, is_critic, o_kvalid=None, q_div=1, out=None):
+    def forward(self, p, e, o, adj_p, adj_e, adj_o, hist, is_critic, o_kvalid=None, q_div=1, out=None, e_ref=None):
         """out (R,P,E), rollout only: the embedding is written into it (static storage of the captured tick program)."""
-        h0 = self.encoder(p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid, q_div, out if self.depth == 0 else None)
+        h0 = self.encoder(p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid, q_div, out if self.depth == 0 else None, e_ref)
         return self.fcra(h0, hist, adj_p, is_critic, out)
 
     # -- actor and critic of one rollout tick together ---------------------------------------------------------------------
@@ -133,7 +135,7 @@ class DHGN(nn.Module):
     # are the same layers applied to the same observation with two adjacencies (the observed one / ones).  forward_pair runs
     # them as one batch of 2R rows: one message pass, one GEMM per layer instead of two, the position part of the semantic
     # layer once.  Slot 0 = actor, slot 1 = critic; the numbers are those of forward(.., False) and forward(.., True).
-    def forward_pair(self, p, e, o, adj_p, adj_e, adj_o, hist_a, hist_c, o_kvalid=None, q_div=1, out=None):
+    def forward_pair(self, p, e, o, adj_p, adj_e, adj_o, hist_a, hist_c, o_kvalid=None, q_div=1, out=None, e_ref=None):
         """-> (2, R, P, E); out: static storage of that shape (rollout).  No autograd."""
         R, P = p.shape[0], p.shape[1]
         E, ind = self.embedding_dim, self.input_dim
@@ -152,7 +154,7 @@ class DHGN(nn.Module):
         fused_pos = ind == 4
         # the message launch also leaves the semantic layer's position part (the same for both networks) in h0
         m3 = ops.msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
-                               o_kvalid, q_div, pos=(Ws[:, :ind], self.semantic_layer.bias, h0) if fused_pos else None)   # (2, R, P, 3, E)
+                               o_kvalid, q_div, pos=(Ws[:, :ind], self.semantic_layer.bias, h0) if fused_pos else None, e_ref=e_ref)   # (2, R, P, 3, E)
         agg0 = self.AGG_layers["AGG_vertex_0"]
         m3_2d = m3.view(-1, E)
         if ops.split_linear_ok(m3_2d, agg0.weight):     # the rollout's Linear layers on the split-bf16 kernel (ops.CELL_MODE)
@@ -331,15 +333,18 @@ class SharedCritic(_Trunk):
 
 
 def pair_embeddings(actor, critic, obs, hist_a, hist_c):
-    """the encoder half of sequence_forward_pair: (emb_a, emb_c), rows in (episode, step, agent) order"""
+    """the encoder half of sequence_forward_pair: (emb_a, emb_c), rows in (episode, step, agent) order.  obs may carry `e_ref`
+    (R, 4), the defender relation's evader (DHGN.encoder; env_n2n)."""
     enc, q_div = actor.shared_net, obs.get("q_div", 1)
+    e_ref = obs.get("e_ref")
+    kw = {} if e_ref is None else {"e_ref": e_ref}
     if (enc is critic.shared_net and isinstance(enc, DHGN) and obs["p_adj"].dtype == torch.float32
             and ops.msg_agg3_pair_train_ok(obs["p_state"], obs["o_state"], enc.MSG_layers[2].weight, q_div)):
         # shared DHGN: one message pass for both networks, forward and backward
-        h0a, h0c = enc.encoder_pair_train(obs["p_state"], obs["e_state"], obs["o_state"], obs["p_adj"], obs["e_adj"], _o_adj(obs), q_div)
+        h0a, h0c = enc.encoder_pair_train(obs["p_state"], obs["e_state"], obs["o_state"], obs["p_adj"], obs["e_adj"], _o_adj(obs), q_div, **kw)
         return enc.fcra(h0a, hist_a, obs["p_adj"], False), enc.fcra(h0c, hist_c, obs["p_adj"], True)
-    emb_a = actor.shared_net(obs["p_state"], obs["e_state"], obs["o_state"], obs["p_adj"], obs["e_adj"], _o_adj(obs), hist_a, False, None, q_div, None)
-    emb_c = critic.shared_net(obs["p_state"], obs["e_state"], obs["o_state"], obs["p_adj"], obs["e_adj"], _o_adj(obs), hist_c, True, None, q_div, None)
+    emb_a = actor.shared_net(obs["p_state"], obs["e_state"], obs["o_state"], obs["p_adj"], obs["e_adj"], _o_adj(obs), hist_a, False, None, q_div, None, **kw)
+    emb_c = critic.shared_net(obs["p_state"], obs["e_state"], obs["o_state"], obs["p_adj"], obs["e_adj"], _o_adj(obs), hist_c, True, None, q_div, None, **kw)
     return emb_a, emb_c
 
 

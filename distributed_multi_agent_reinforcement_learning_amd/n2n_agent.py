@@ -1,0 +1,320 @@
+"""MAPPO on env_n2n (continuous 2-D pursuit, several evaders, no obstacles): BASELINE config 4 on the environment it names.
+
+The reference has no env_n2n learner.  This module drives the pursuit model itself -- `build_actor_critic`: the DHGN encoder
+shared by `SharedActor` (2-layer GRU, 9-way Categorical head) and `SharedCritic` (spectrally normalised value head), so the state_dict
+keys are the reference's -- with the PPO update, GAE and data-parallel protocol of `MAPPO` / `Trainer`.  DESIGN.md section 7b.
+* inputs: ParticleEnv.policy_inputs (csrc/n2n_env.hip n2n_policy_inputs, one launch per tick): pursuers and evaders as
+  (x, y, v cos phi, v sin phi), the live mask, the masked adjacencies and e_ref, the evader of the defender relation's p_i - e term;
+* relations: defender (P x P), evader (P x E, E >= 1) and an EMPTY obstacle relation (K = 0: its slot is zero, its dW and db are 0);
+* bookkeeping: ParticleEnv.policy_record (n2n_policy_record, one launch per tick): masked reward / value / active rows of the buffer and
+  the per-environment return, length, capture and end flags.
+"""
+import json
+import os
+import time
+
+import torch
+
+from . import ops
+from .model import build_actor_critic, sequence_forward_pair
+from .n2n_env import ParticleEnv
+from .trainer import GradBucket, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed
+
+MAX_P = 16   # the message kernels' agents per row (csrc/mappo_ops.hip MAX_P)
+
+
+class _N2nRollout:
+    """static device storage of one lockstep rollout of N environments: the policy inputs, the history ring (slot t % M holds tick t's
+    actor [0] and critic [1] embedding; M = depth + 1, each network reads its own last `depth` embeddings), the GRU states (ping-pong
+    between two buffers), the episode accumulators and the position of the action-sampling stream"""
+
+    def __init__(self, agent, env):
+        dev, L, H, Em, d = agent.device, agent.num_layers, agent.rnn_hidden_dim, agent.embedding_dim, agent.depth
+        N, P, E = env.num_envs, env.p_num, env.e_num
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+        self.N, self.P, self.E, self.d, self.M = N, P, E, d, d + 1
+        self.p4, self.e4, self.e_ref, self.live = z(N, P, 4), z(N, E, 4), z(N, 4), z(N, P)
+        self.pp, self.pe = z(N, P, P), z(N, P, E)
+        self.o, self.o_adj = z(N, 0, 4), z(N, P, 0)          # env_n2n has no obstacles: the third relation is empty
+        self.ring = z(self.M, 2, N, P, Em)
+        self.hbuf_a, self.hbuf_c = z(2, L, N * P, H), z(2, L, N * P, H)
+        self.a_n = torch.zeros((N, P), dtype=torch.int32, device=dev)
+        self.logp, self.v = z(N, P), z(N, P)
+        self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.t = 0
+
+    def reset(self):
+        for x in (self.ring, self.hbuf_a, self.hbuf_c):
+            x.zero_()
+        self.t = 0
+
+    def hops(self, t):
+        """hop k = the embedding of tick t - 1 - k (zero before the episode's first tick), per network"""
+        return [self.ring[(t - 1 - k) % self.M][0] for k in range(self.d)], [self.ring[(t - 1 - k) % self.M][1] for k in range(self.d)]
+
+
+class N2nMAPPO:
+    """rollout (run_episode / explore_env) and PPO update (train) of the DHGN actor / critic on env_n2n"""
+
+    def __init__(self, cfg, batch_size, mini_batch_size, device="cuda"):
+        a = cfg.algo
+        if bool(a.get("use_reward_norm", False)):
+            raise ValueError("algo.use_reward_norm: true is not supported on env_n2n (runtime.env: n2n); set it to false")
+        if int(cfg.env.num_defender) > MAX_P:
+            raise ValueError(f"env.num_defender={cfg.env.num_defender}: the DHGN message kernels take at most {MAX_P} pursuers per row")
+        if int(cfg.env.state_dim) != 4 or int(cfg.env.action_dim) != 9 or int(a.num_relation) != 3:
+            raise ValueError("env_n2n runs the pursuit model: env.state_dim 4, env.action_dim 9, algo.num_relation 3")
+        self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
+        self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
+        self.epsilon, self.entropy_coef = a.epsilon, a.entropy_coef
+        self.use_grad_clip, self.use_lr_decay = a.use_grad_clip, a.use_lr_decay
+        self.use_adv_norm, self.use_value_clip = a.use_adv_norm, a.use_value_clip
+        self.num_layers, self.embedding_dim, self.rnn_hidden_dim = int(a.num_layers), int(a.embedding_dim), int(a.rnn_hidden_dim)
+        self.depth = int(a.depth)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("N2nMAPPO runs on the GPU only (HIP kernels, no CPU fallback)")
+        if str(a.get("encoder", "dhgn")).lower() != "dhgn":
+            raise ValueError("env_n2n trains the DHGN encoder only (algo.encoder: dhgn)")
+        self.actor, self.critic = build_actor_critic(cfg, self.device)
+        if not (self.actor.use_rnn and self.critic.use_rnn):
+            raise ValueError("env_n2n trains the GRU actor / critic only (algo.use_rnn: true)")
+        enc = self.actor.shared_net
+        # the parameter order of MAPPO.ac_parameters (the reference's, :631)
+        self.ac_parameters = (list(enc.parameters()) + list(self.actor.GRU.parameters()) + list(self.critic.GRU.parameters())
+                              + list(self.critic.Mean.parameters()) + list(self.actor.Mean.parameters()))
+        self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
+        rt = cfg.get("runtime", {})
+        self.sample_seed = int(rt.get("seed", 0))
+        self.sample_rank = int(rt.get("sample_rank", 0))   # Philox counter of rank r starts at r << 40 (as MAPPO)
+        self.total_step = 0
+        self.grad_bucket = None
+        self.buffer = None
+        self._states = {}
+
+    # ---- rollout -------------------------------------------------------------------------------------------------------------
+    def _state(self, env):
+        st = self._states.get(id(env))
+        if st is None or st.N != env.num_envs:
+            st = self._states[id(env)] = _N2nRollout(self, env)
+        return st
+
+    def _policy_step(self, st, greedy=False):
+        """DHGN for both networks in one pass (forward_pair, into the ring) -> both GRU cells (one launch per layer) -> value ->
+        Categorical head and sample (ops.head_sample, int32 actions)"""
+        N, P, Em = st.N, st.P, self.embedding_dim
+        hops_a, hops_c = st.hops(st.t)
+        slot = st.ring[st.t % st.M]
+        emb = self.actor.shared_net.forward_pair(st.p4, st.e4, st.o, st.pp, st.pe, st.o_adj, hops_a, hops_c, None, 1, slot, e_ref=st.e_ref)
+        cur, nxt = st.t & 1, (st.t + 1) & 1
+        fa, fc = ops.gru_step_multi([emb[0].reshape(-1, Em), emb[1].reshape(-1, Em)], [st.hbuf_a[cur], st.hbuf_c[cur]],
+                                    [self.actor.GRU, self.critic.GRU], hiddens_out=[st.hbuf_a[nxt], st.hbuf_c[nxt]])
+        self.critic.head(fc.reshape(N, P, -1), out=st.v)
+        w_a = self.actor.head_weight()
+        ops.head_sample(fa.contiguous(), w_a, self.actor.Mean.bias, self.sample_seed, st.counter, st.ticket, (st.a_n, st.logp), greedy=greedy)
+        st.t += 1
+
+    def _bootstrap_value(self, st):
+        """the critic's value of the state after the last step: its DHGN pass (history = its own last embeddings), GRU cell and head"""
+        N, P = st.N, st.P
+        _, hops_c = st.hops(st.t)
+        enc = self.critic.shared_net
+        emb = enc(st.p4, st.e4, st.o, st.pp, st.pe, st.o_adj, hops_c, True, None, 1, None, e_ref=st.e_ref)
+        (fc,) = ops.gru_step_multi([emb.reshape(N * P, -1)], [st.hbuf_c[st.t & 1]], [self.critic.GRU], hiddens_out=[st.hbuf_c[(st.t + 1) & 1]])
+        return self.critic.head(fc.reshape(N, P, -1)).reshape(N, P)
+
+    def new_buffer(self, N, T, P, E):
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)
+        d, Em = self.depth, self.embedding_dim
+        return dict(p_state=z(N, T, P, 4), e_state=z(N, T, E, 4), e_ref=z(N, T, 4), p_adj=z(N, T, P, P), e_adj=z(N, T, P, E),
+                    actor_historical_embedding=z(N, T + d, P, Em), critic_historical_embedding=z(N, T + d, P, Em),
+                    a_n=z(N, T, P), a_logprob_n=z(N, T, P), r=z(N, T, P), active=z(N, T, P), v_n=z(N, T + 1, P))
+
+    @torch.no_grad()
+    def run_episode(self, env, buf=None, greedy=False):
+        """N episodes in lockstep for T = env.episode_limit ticks.  Per tick: policy_inputs, the policy step, the SLSQP evader, the tick,
+        policy_record, and (with a buffer) one rollout_record launch.  Row (n, t, p) is live iff pursuer p was active at the start of step t
+        and environment n was not done before it; r, v_n and `active` of other rows are zero, so is v_n[n, t + 1, p] when pursuer p or
+        episode n ended in step t for a reason other than the time limit; v_n[:, T] is the critic's bootstrap value under that rule.
+        Returns the per-environment accumulators (done_before, ended, captured, ret, length)."""
+        N, P, T, d = env.num_envs, env.p_num, env.episode_limit, self.depth
+        env.reset()
+        st = self._state(env)
+        st.reset()
+        acc = env.new_accumulators()
+        for t in range(T):
+            env.policy_inputs(st.p4, st.e4, st.e_ref, st.live, st.pp, st.pe, acc["done_before"])
+            self._policy_step(st, greedy)
+            env.evader_step()
+            env.step(st.a_n)
+            if buf is None:
+                env.policy_record(acc, st.live)
+                continue
+            env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1])
+            items = [(st.p4, buf["p_state"][:, t]), (st.e4, buf["e_state"][:, t]), (st.e_ref, buf["e_ref"][:, t]), (st.pp, buf["p_adj"][:, t]),
+                     (st.pe, buf["e_adj"][:, t]), (st.a_n, buf["a_n"][:, t]), (st.logp, buf["a_logprob_n"][:, t])]
+            if d:   # the update reads the stored embeddings as FCRA history only
+                slot = st.ring[(st.t - 1) % st.M]
+                items += [(slot[0], buf["actor_historical_embedding"][:, t + d]), (slot[1], buf["critic_historical_embedding"][:, t + d])]
+            ops.rollout_record(items)
+        if buf is not None:
+            # the state after the last step without the done mask: the time limit sets done for every environment in the last tick, and
+            # the truncated episodes are the ones whose bootstrap value counts (vmask removes those that ended for another reason)
+            env.policy_inputs(st.p4, st.e4, st.e_ref, st.live, st.pp, st.pe, None)
+            vmask = env.active_t.float() * (acc["ended"] == 0).float()[:, None]
+            buf["v_n"][:, T].copy_(self._bootstrap_value(st) * vmask)
+        return acc
+
+    def explore_env(self, env):
+        """one episode per environment into the buffer -> (mean return, buffer, env-steps, stats)"""
+        N, P, E, T = env.num_envs, env.p_num, env.e_num, env.episode_limit
+        if self.buffer is None or self.buffer["r"].shape != (N, T, P) or self.buffer["e_state"].shape[2] != E:
+            self.buffer = self.new_buffer(N, T, P, E)
+        acc = self.run_episode(env, self.buffer)
+        mean_r, cap, mlen = torch.stack((acc["ret"].mean(), acc["captured"].float().mean(), acc["length"].mean())).tolist()
+        return mean_r, self.buffer, N * T, dict(capture_rate=cap, episode_length=mlen)
+
+    # ---- update ------------------------------------------------------------------------------------------------------------------
+    def minibatch_inputs(self, buf, n0, n1):
+        """episodes [n0, n1) of the buffer as one sequence batch: (obs dict, actor history slices, critic history slices)"""
+        T, P, E, d = buf["r"].shape[1], buf["r"].shape[2], buf["e_state"].shape[2], self.depth
+        R = (n1 - n0) * T
+        dev = buf["r"].device
+        obs = dict(p_state=buf["p_state"][n0:n1].reshape(R, P, 4), e_state=buf["e_state"][n0:n1].reshape(R, E, 4),
+                   e_ref=buf["e_ref"][n0:n1].reshape(R, 4), o_state=torch.zeros((R, 0, 4), device=dev), q_div=1,
+                   p_adj=buf["p_adj"][n0:n1].reshape(R, P, P), e_adj=buf["e_adj"][n0:n1].reshape(R, P, E),
+                   o_adj=torch.zeros((R, P, 0), device=dev))
+        hist_a = [buf["actor_historical_embedding"][n0:n1, d - 1 - k: d - 1 - k + T] for k in range(d)]
+        hist_c = [buf["critic_historical_embedding"][n0:n1, d - 1 - k: d - 1 - k + T] for k in range(d)]
+        return obs, hist_a, hist_c
+
+    def sequence_forward(self, buf, n0, n1):
+        """-> prob (B, T, P, 9), values (B, T, P) of episodes [n0, n1) (model.sequence_forward_pair)"""
+        obs, hist_a, hist_c = self.minibatch_inputs(buf, n0, n1)
+        prob, values = sequence_forward_pair(self.actor, self.critic, obs, hist_a, hist_c, n1 - n0, buf["r"].shape[1])
+        return prob, values[..., 0]
+
+    def train(self, buf, total_steps):
+        """GAE + advantage normalisation over all rows (ops.gae_advnorm), then sequential mini-batches of whole episodes, the
+        gradient clipped to 5.0 after each (as MAPPO.train).  Returns (critic loss, actor loss) averaged over the mini-batches."""
+        N = buf["r"].shape[0]
+        with torch.no_grad():
+            adv, v_target = ops.gae_advnorm(buf["r"], buf["v_n"], buf["active"], self.gamma, self.lamda, self.use_adv_norm)
+        if self.grad_bucket is not None:
+            self.grad_bucket.zero()
+        else:
+            self.ac_optimizer.zero_grad()
+        obj_c = obj_a = 0.0
+        k = 0
+        for n0 in range(0, N, self.mini_batch_size):
+            n1 = min(n0 + self.mini_batch_size, N)
+            prob, values = self.sequence_forward(buf, n0, n1)
+            la, lc = ops.ppo_loss_prob(prob, buf["a_n"][n0:n1], values, buf["a_logprob_n"][n0:n1], adv[n0:n1], buf["active"][n0:n1],
+                                       buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1], self.epsilon,
+                                       self.entropy_coef, self.use_value_clip)
+            (la + lc).backward()
+            if self.use_grad_clip:
+                torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
+            obj_c = obj_c + lc.detach().double()
+            obj_a = obj_a + la.detach().double()
+            k += 1
+        if self.use_lr_decay:
+            self.lr_decay(total_steps)
+        return float(obj_c) / k, float(obj_a) / k
+
+    def lr_decay(self, total_steps):
+        lr_now = self.lr * (1 - total_steps / self.max_train_steps)
+        for p in self.ac_optimizer.param_groups:
+            p["lr"] = lr_now
+        self.total_step = total_steps
+
+    def save_model(self, cwd):
+        os.makedirs(cwd, exist_ok=True)
+        torch.save(self.actor.state_dict(), os.path.join(cwd, "n2n_actor.pth"))
+        torch.save(self.critic.state_dict(), os.path.join(cwd, "n2n_critic.pth"))
+
+
+def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0):
+    """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env)"""
+    base = int(cfg.runtime.get("seed", 0)) + seed_offset + max(1000, num_envs) * rank
+    env = ParticleEnv(num_envs=num_envs, seeds=[base + n for n in range(num_envs)], device=device, episode_limit=int(cfg.env.max_steps),
+                      evader=str(cfg.runtime.get("n2n_evader", "slsqp")))
+    env.initialize(int(cfg.env.num_defender), int(cfg.env.num_evader))
+    return env
+
+
+class N2nTrainer:
+    """One rank of the data-parallel env_n2n job: rollout, then epochs x (update, gradient all-reduce, Adam step)."""
+
+    def __init__(self, cfg, num_envs=None, num_eval_envs=64, eval_every=0, tuned_gemms=True):
+        self.rank, self.local_rank, self.world = init_distributed()
+        self.tuned_gemms = enable_tuned_gemms() if tuned_gemms else False
+        self.cfg = cfg
+        self.device = torch.device("cuda", self.local_rank % max(1, torch.cuda.device_count()))
+        torch.cuda.set_device(self.device)
+        self.num_envs = int(num_envs if num_envs is not None else cfg.runtime.num_envs)
+        self.env = make_env(cfg, self.num_envs, self.rank, self.device)
+        torch.manual_seed(int(cfg.runtime.get("seed", 0)))
+        self.agent = N2nMAPPO(cfg, self.num_envs, max(1, round(self.num_envs / 10)), self.device)
+        self.agent.sample_rank = self.rank
+        self.bucket = GradBucket(self.agent.ac_parameters)
+        self.agent.grad_bucket = self.bucket
+        broadcast_weights_([self.agent.actor, self.agent.critic])
+        self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
+        self.eval_env = None
+        self.total_steps = 0
+        self.iteration = 0
+
+    def iterate(self):
+        """-> (env-steps of this iteration over all ranks, log record)"""
+        cfg, agent = self.cfg, self.agent
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        mean_r, buf, steps, stats = agent.explore_env(self.env)
+        ev[1].record()
+        self.total_steps += steps * self.world
+        for _ in range(int(cfg.algo.epochs)):
+            with torch.enable_grad():
+                obj_c, obj_a = agent.train(buf, self.total_steps)
+            allreduce_sum_(self.bucket.flat)
+            agent.ac_optimizer.step()
+        ev[2].record()
+        self.iteration += 1
+        self.last_events = ev
+        log = dict(iteration=self.iteration, total_steps=self.total_steps, mean_return=mean_r, capture_rate=stats["capture_rate"],
+                   episode_length=stats["episode_length"], critic_loss=obj_c, actor_loss=obj_a)
+        if self.eval_every and self.iteration % self.eval_every == 0 and self.rank == 0:
+            log.update(self.evaluate())
+        return steps * self.world, log
+
+    def evaluate(self):
+        """synchronous greedy episode (argmax) on num_eval_envs environments of their own seeds"""
+        if self.eval_env is None:
+            self.eval_env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6)
+        acc = self.agent.run_episode(self.eval_env, None, greedy=True)
+        r, c, l = torch.stack((acc["ret"].mean(), acc["captured"].float().mean(), acc["length"].mean())).tolist()
+        return dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+
+    def last_breakdown_ms(self):
+        torch.cuda.synchronize()
+        ev = self.last_events
+        return ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+
+
+def train_n2n(cfg, max_iterations=None, num_eval_envs=64, eval_every=1):
+    """the env_n2n training loop (main --config cfg4_n2n): until max_train_steps env-steps or max_iterations; rank 0 prints one JSON log
+    line per iteration and saves the final weights under algo.save_cwd"""
+    tr = N2nTrainer(cfg, num_eval_envs=num_eval_envs, eval_every=eval_every)
+    while tr.total_steps < cfg.algo.max_train_steps:
+        t0 = time.time()
+        steps, log = tr.iterate()
+        if tr.rank == 0:
+            rollout_ms, update_ms = tr.last_breakdown_ms()
+            log.update(rollout_ms=round(rollout_ms, 2), update_ms=round(update_ms, 2), seconds=round(time.time() - t0, 3))
+            print(json.dumps(log), flush=True)
+        if max_iterations is not None and tr.iteration >= max_iterations:
+            break
+    if tr.rank == 0:
+        tr.agent.save_model(cfg.algo.save_cwd)
+    return tr

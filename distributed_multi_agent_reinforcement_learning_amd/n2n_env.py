@@ -33,6 +33,27 @@ class N2nObsOut(C.Structure):
                 ("pp_adj", C.c_void_p), ("pp_adj_stride", C.c_int64), ("pe_adj", C.c_void_p), ("pe_adj_stride", C.c_int64)]
 
 
+class N2nPolicyIO(C.Structure):
+    _fields_ = [(n, t) for k in ("pp_in", "pe_in", "p4", "e4", "e_ref", "live", "pp_adj", "pe_adj") for n, t in ((k, C.c_void_p), (k + "_rs", C.c_int64))]
+
+
+class N2nPolicyAcc(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("done_before", "ended", "captured", "ret", "length")]
+
+
+class N2nRecordIO(C.Structure):
+    _fields_ = [(n, t) for k in ("live", "value", "r", "active", "v", "v_next") for n, t in ((k, C.c_void_p), (k + "_rs", C.c_int64))]
+
+
+def _rows(t, shape, name):
+    """a float32 (N, ...) device tensor whose environment rows are dense (rows may be strided: buffer[:, t]) -> (pointer, row stride)"""
+    if t is None:
+        return None, 0
+    assert t.dtype == torch.float32 and t.is_cuda and tuple(t.shape) == tuple(shape), (name, tuple(t.shape), tuple(shape))
+    assert t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= t[0].numel()), f"{name}: rows must be dense"
+    return t.data_ptr(), t.stride(0)
+
+
 _lib = None
 
 
@@ -55,6 +76,8 @@ def load_library():
         L.n2n_evader_slsqp_nit.argtypes = [vp] * 5
         L.n2n_evader_slsqp_host.argtypes = [vp, C.c_int32] + [vp] * 5
         L.n2n_resetter_reset.argtypes = [vp, vp, vp, vp, C.c_int32]
+        L.n2n_policy_inputs.argtypes = [vp] * 5
+        L.n2n_policy_record.argtypes = [vp] * 7
         _lib = L
     return _lib
 
@@ -195,3 +218,46 @@ class ParticleEnv:
                                    ptr(self.done_t), C.byref(self._obs_struct), _stream()), "n2n_env_tick")
         self.time_step += 1
         return self.reward_t, self.done_t, self.active_t
+
+    # ---- MAPPO on env_n2n (n2n_agent.py): one launch before the policy step, one after the tick ------------------------------------
+    def new_accumulators(self):
+        """zeroed per-environment episode accumulators for policy_record: done_before, ended, captured (uint8), return, length"""
+        N, dev = self.num_envs, self.device
+        u8 = lambda: torch.zeros(N, dtype=torch.uint8, device=dev)
+        return dict(done_before=u8(), ended=u8(), captured=u8(), ret=torch.zeros(N, device=dev), length=torch.zeros(N, device=dev))
+
+    def policy_inputs(self, p4, e4, e_ref, live, pp_adj, pe_adj, done_before=None):
+        """the DHGN's fp32 inputs of the current state (n2n_policy_inputs, include/n2n_env.h): p4 (N,P,4), e4 (N,E,4), e_ref (N,4),
+        live (N,P), pp_adj (N,P,P), pe_adj (N,P,E), each None (skipped) or a tensor with dense environment rows, e.g. buffer[:, t].
+        done_before: the uint8 (N,) accumulator of policy_record (None: no environment is done)."""
+        N, P, E = self.num_envs, self.p_num, self.e_num
+        io = N2nPolicyIO()
+        io.pp_in, io.pp_in_rs = self.obs["pp_adj"].data_ptr(), self.obs["pp_adj"].stride(0)
+        io.pe_in, io.pe_in_rs = self.obs["pe_adj"].data_ptr(), self.obs["pe_adj"].stride(0)
+        for k, t, shape in (("p4", p4, (N, P, 4)), ("e4", e4, (N, E, 4)), ("e_ref", e_ref, (N, 4)), ("live", live, (N, P)),
+                            ("pp_adj", pp_adj, (N, P, P)), ("pe_adj", pe_adj, (N, P, E))):
+            ptr, rs = _rows(t, shape, k)
+            setattr(io, k, ptr)
+            setattr(io, k + "_rs", rs)
+        if done_before is not None:
+            assert done_before.dtype == torch.uint8 and done_before.is_contiguous() and done_before.shape == (N,)
+        _check(self.L.n2n_policy_inputs(C.byref(self.c), C.byref(self.st), C.c_void_p(done_before.data_ptr() if done_before is not None else None),
+                                        C.byref(io), _stream()), "n2n_policy_inputs")
+
+    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None):
+        """after step(): r = reward * live, active = live, v = value * live (row t of the buffer, None skips), v_next (row t + 1 of v_n)
+        zeroed where the pursuer is inactive or its episode ended for a reason other than the time limit; updates the accumulators
+        of new_accumulators() (n2n_policy_record, include/n2n_env.h)."""
+        N, P = self.num_envs, self.p_num
+        io = N2nRecordIO()
+        for k, t in (("live", live), ("value", value), ("r", r), ("active", active), ("v", v), ("v_next", v_next)):
+            ptr, rs = _rows(t, (N, P), k)
+            setattr(io, k, ptr)
+            setattr(io, k + "_rs", rs)
+        a = N2nPolicyAcc()
+        for k, dt in (("done_before", torch.uint8), ("ended", torch.uint8), ("captured", torch.uint8), ("ret", torch.float32), ("length", torch.float32)):
+            t = acc[k]
+            assert t.dtype == dt and t.is_contiguous() and t.shape == (N,) and t.device == self.p.device, k
+            setattr(a, k, t.data_ptr())
+        _check(self.L.n2n_policy_record(C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()),
+                                        C.byref(io), C.byref(a), _stream()), "n2n_policy_record")

@@ -280,10 +280,17 @@ def _msg3_call(L, p, rels, out, E):
            "dhgn_msg_agg3_fwd")
 
 
-def msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, o_kvalid=None, q_div=1, out=None, pos=None):
+def _e_slot(e, e_ref, R):
+    """the evader of the defender relation's p_i - e term: e (R, 1, 4) itself, or e_ref (R, 4) -- one chosen evader per row when the
+    evader relation has several (env_n2n)"""
+    return e.reshape(R, 4) if e_ref is None else e_ref
+
+
+def msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, o_kvalid=None, q_div=1, out=None, pos=None, e_ref=None):
     """(2, R, P, 3, E): msg_agg3 of the actor (slot 0: the observed adjacency) and of the critic (slot 1: ones, for the obstacle
     relation over the first o_kvalid[row] obstacles when given) from ONE pass over the messages -- the two networks share the
-    encoder weights (DHGN/mappo_parallel.py:582-616).  Rollout only (no autograd); bit-identical to two msg_agg3 calls."""
+    encoder weights (DHGN/mappo_parallel.py:582-616).  Rollout only (no autograd); bit-identical to two msg_agg3 calls.
+    A relation may be empty (o of shape (R, 0, 4)): its slot is zero.  e_ref (R, 4): see msg_agg3."""
     assert not (torch.is_grad_enabled() and any(t.requires_grad for t in (W0, b0, W1, b1, W2, b2))), "msg_agg3_pair has no backward"
     L = load_library()
     _need_gpu(p, "dhgn_msg_agg3_pair")
@@ -294,7 +301,7 @@ def msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, o_kvalid
         out = torch.empty((2, R, P, 3, E), dtype=torch.float32, device=p.device)
     assert out.shape == (2, R, P, 3, E) and out.is_contiguous() and out.dtype == torch.float32
     mode_o = ADJ_BITS if adj_o.dtype == torch.int32 else ADJ_TENSOR
-    arr = _msg3_rels(p, ((p, e.reshape(R, 4), adj_p, None, ws[0], ws[1], ADJ_TENSOR, 1), (e, None, adj_e, None, ws[2], ws[3], ADJ_TENSOR, 1),
+    arr = _msg3_rels(p, ((p, _e_slot(e, e_ref, R), adj_p, None, ws[0], ws[1], ADJ_TENSOR, 1), (e, None, adj_e, None, ws[2], ws[3], ADJ_TENSOR, 1),
                          (o, None, adj_o, None, ws[4], ws[5], mode_o, q_div)))
     if o_kvalid is not None:
         assert o_kvalid.dtype == torch.int32 and o_kvalid.is_contiguous() and o_kvalid.shape[0] * q_div == R
@@ -343,13 +350,13 @@ class _MsgAgg3(torch.autograd.Function):
     the shared AGG_vertex_0 layer runs as a single GEMM on a view and no stack / concatenate copies exist."""
 
     @staticmethod
-    def forward(ctx, p, e, o, adj_p, adj_e, adj_o, kvalid, W0, b0, W1, b1, W2, b2, mode, mode_o, q_div):
+    def forward(ctx, p, e, o, adj_p, adj_e, adj_o, kvalid, W0, b0, W1, b1, W2, b2, mode, mode_o, q_div, e_ref=None):
         L = load_library()
         _need_gpu(p, "dhgn_msg_agg")
         R, P = p.shape[0], p.shape[1]
         E = W0.shape[0]
         ws = [t.detach().contiguous() for t in (W0, b0, W1, b1, W2, b2)]
-        e2 = e.reshape(R, 4)
+        e2 = _e_slot(e, e_ref, R)
         out = torch.empty((R, P, 3, E), dtype=torch.float32, device=p.device)
         slot = lambda r: C.c_void_p(out.data_ptr() + 4 * r * E)
         save_m = qtab = None
@@ -357,7 +364,7 @@ class _MsgAgg3(torch.autograd.Function):
         if not ctx.sorted_o:   # the three relations in one launch
             _msg3_call(L, p, ((p, e2, adj_p, None, ws[0], ws[1], mode, 1), (e, None, adj_e, None, ws[2], ws[3], mode, 1),
                               (o, None, adj_o, kvalid, ws[4], ws[5], mode_o, q_div)), out, E)
-            ctx.save_for_backward(p, e, o, adj_p, adj_e, adj_o, kvalid, save_m, qtab, *ws)
+            ctx.save_for_backward(p, e, o, adj_p, adj_e, adj_o, kvalid, save_m, qtab, e2, *ws)
             ctx.meta = (mode, mode_o, q_div)
             return out
         _msg_call("fwd", L, p, p, e2, adj_p, None, ws[0], ws[1], mode, 1, slot(0), 3 * E)
@@ -371,21 +378,21 @@ class _MsgAgg3(torch.autograd.Function):
                                                   _ptr(save_m), _ptr(qtab), _stream()), "dhgn_msg_agg_ones_sorted_fwd")
         else:
             _msg_call("fwd", L, p, o, None, adj_o, kvalid, ws[4], ws[5], mode_o, q_div, slot(2), 3 * E)
-        ctx.save_for_backward(p, e, o, adj_p, adj_e, adj_o, kvalid, save_m, qtab, *ws)
+        ctx.save_for_backward(p, e, o, adj_p, adj_e, adj_o, kvalid, save_m, qtab, e2, *ws)
         ctx.meta = (mode, mode_o, q_div)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         L = load_library()
-        p, e, o, adj_p, adj_e, adj_o, kvalid, save_m, qtab, W0, b0, W1, b1, W2, b2 = ctx.saved_tensors
+        p, e, o, adj_p, adj_e, adj_o, kvalid, save_m, qtab, e2, W0, b0, W1, b1, W2, b2 = ctx.saved_tensors
         mode, mode_o, q_div = ctx.meta
         R, P = p.shape[0], p.shape[1]
         E = W0.shape[0]
         gout = gout.contiguous()
         slot = lambda r: C.c_void_p(gout.data_ptr() + 4 * r * E)
         grads = []
-        for r, (q, ee, adj, kv, W, b, m, qd) in enumerate(((p, e.reshape(R, 4), adj_p, None, W0, b0, mode, 1), (e, None, adj_e, None, W1, b1, mode, 1),
+        for r, (q, ee, adj, kv, W, b, m, qd) in enumerate(((p, e2, adj_p, None, W0, b0, mode, 1), (e, None, adj_e, None, W1, b1, mode, 1),
                                                            (o, None, adj_o, kvalid, W2, b2, mode_o, q_div))):
             dW, db = torch.empty_like(W), torch.empty_like(b)
             if r == 2 and ctx.sorted_o:
@@ -397,7 +404,7 @@ class _MsgAgg3(torch.autograd.Function):
             ws = _workspace(p.device, E, W.shape[1])
             _msg_call("bwd", L, p, q, ee, adj, kv, W, b, m, qd, slot(r), 3 * E, (_ptr(dW), _ptr(db), _ptr(ws)))
             grads += [dW, db]
-        return (None,) * 7 + tuple(grads) + (None, None, None)
+        return (None,) * 7 + tuple(grads) + (None, None, None, None)
 
 
 class _MsgAgg3Pair(torch.autograd.Function):
@@ -406,21 +413,28 @@ class _MsgAgg3Pair(torch.autograd.Function):
     Forward: one launch for the actor's three relations plus the critic's relations 0 and 1 (the messages are computed once); the
     critic's obstacle relation (ones over all padded slots in training) is the sorted all-ones kernel.  Backward: relations
     0 and 1 are ONE pass each for both networks (dhgn_msg_agg_bwd_pair: the two gradients share the ReLU mask and sum into one dW),
-    relation 2 the actor's bit-walk kernel plus the sorted kernel.  The numbers are those of two _MsgAgg3 nodes."""
+    relation 2 the actor's bit-walk kernel plus the sorted kernel.  The numbers are those of two _MsgAgg3 nodes.
+    An empty obstacle relation (K = 0, env_n2n) takes the one-launch pair form for the forward (zero slots) and contributes zero dW, db."""
 
     @staticmethod
-    def forward(ctx, p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, q_div):
+    def forward(ctx, p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, q_div, e_ref=None):
         L = load_library()
         _need_gpu(p, "dhgn_msg_agg")
         R, P = p.shape[0], p.shape[1]
         E, K = W0.shape[0], o.shape[1]
         ws = [t.detach().contiguous() for t in (W0, b0, W1, b1, W2, b2)]
-        e2 = e.reshape(R, 4)
+        e2 = _e_slot(e, e_ref, R)
         out_a = torch.empty((R, P, 3, E), dtype=torch.float32, device=p.device)
         out_c = torch.empty((R, P, 3, E), dtype=torch.float32, device=p.device)
         mode_o = ADJ_BITS if adj_o.dtype == torch.int32 else ADJ_TENSOR
         arr = _msg3_rels(p, ((p, e2, adj_p, None, ws[0], ws[1], ADJ_TENSOR, 1), (e, None, adj_e, None, ws[2], ws[3], ADJ_TENSOR, 1),
                              (o, None, adj_o, None, ws[4], ws[5], mode_o, q_div)))
+        ctx.meta = (mode_o, q_div)
+        if K == 0:   # ones over all K = 0 slots: the critic's obstacle slot is zero like the actor's, no sorted kernel
+            _check(L.dhgn_msg_agg3_pair_fwd(C.cast(arr, C.c_void_p), R, P, E, _ptr(p), p.stride(0), None, _ptr(out_a), _ptr(out_c), 3 * E, _stream()),
+                   "dhgn_msg_agg3_pair_fwd")
+            ctx.save_for_backward(p, e, o, adj_p, adj_e, adj_o, None, None, e2, *ws)
+            return out_a, out_c
         _check(L.dhgn_msg_agg3_pair01_fwd(C.cast(arr, C.c_void_p), R, P, E, _ptr(p), p.stride(0), _ptr(out_a), _ptr(out_c), 3 * E, _stream()),
                "dhgn_msg_agg3_pair01_fwd")
         need = any(ctx.needs_input_grad)
@@ -429,21 +443,20 @@ class _MsgAgg3Pair(torch.autograd.Function):
         _check(L.dhgn_msg_agg_ones_sorted_fwd(R, P, K, E, _ptr(p), p.stride(0), _ptr(o), o.stride(0), q_div, _ptr(ws[4]), _ptr(ws[5]),
                                               C.c_void_p(out_c.data_ptr() + 4 * 2 * E), 3 * E, _ptr(save_m), _ptr(qtab), _stream()),
                "dhgn_msg_agg_ones_sorted_fwd")
-        ctx.save_for_backward(p, e, o, adj_p, adj_e, adj_o, save_m, qtab, *ws)
-        ctx.meta = (mode_o, q_div)
+        ctx.save_for_backward(p, e, o, adj_p, adj_e, adj_o, save_m, qtab, e2, *ws)
         return out_a, out_c
 
     @staticmethod
     def backward(ctx, ga, gc):
         L = load_library()
-        p, e, o, adj_p, adj_e, adj_o, save_m, qtab, W0, b0, W1, b1, W2, b2 = ctx.saved_tensors
+        p, e, o, adj_p, adj_e, adj_o, save_m, qtab, e2, W0, b0, W1, b1, W2, b2 = ctx.saved_tensors
         mode_o, q_div = ctx.meta
         R, P = p.shape[0], p.shape[1]
         E = W0.shape[0]
         ga, gc = ga.contiguous(), gc.contiguous()
         slot = lambda g, r: C.c_void_p(g.data_ptr() + 4 * r * E)
         grads = []
-        for r, (q, ee, adj, W, b) in enumerate(((p, e.reshape(R, 4), adj_p, W0, b0), (e, None, adj_e, W1, b1))):
+        for r, (q, ee, adj, W, b) in enumerate(((p, e2, adj_p, W0, b0), (e, None, adj_e, W1, b1))):
             K, din = q.shape[1], W.shape[1]
             dW, db = torch.empty_like(W), torch.empty_like(b)
             ws = _workspace(p.device, E, din)
@@ -455,32 +468,36 @@ class _MsgAgg3Pair(torch.autograd.Function):
         # the obstacle relation: actor (bit-packed / float adjacency) and critic (sorted all-ones), summed
         dWa, dba = torch.empty_like(W2), torch.empty_like(b2)
         _msg_call("bwd", L, p, o, None, adj_o, None, W2, b2, mode_o, q_div, slot(ga, 2), 3 * E, (_ptr(dWa), _ptr(dba), _ptr(_workspace(p.device, E, 4))))
+        if o.shape[1] == 0:   # an empty relation: the kernel's dW, db are exactly zero and the critic adds nothing
+            return (None,) * 6 + tuple(grads) + (dWa, dba, None, None)
         dWc, dbc = torch.empty_like(W2), torch.empty_like(b2)
         part = torch.empty((R // q_div) * 5 * E, dtype=torch.float32, device=p.device)
         _check(L.dhgn_msg_agg_ones_sorted_bwd(R, P, o.shape[1], E, _ptr(p), p.stride(0), q_div, slot(gc, 2), 3 * E, _ptr(save_m), _ptr(qtab),
                                               _ptr(dWc), _ptr(dbc), _ptr(part), _stream()), "dhgn_msg_agg_ones_sorted_bwd")
         grads += [dWa + dWc, dba + dbc]
-        return (None,) * 6 + tuple(grads) + (None,)
+        return (None,) * 6 + tuple(grads) + (None, None)
 
 
 def msg_agg3_pair_train_ok(p, o, W2, q_div):
-    """shapes the paired update path covers (the critic's obstacle relation must take the sorted all-ones kernels)"""
-    return p.is_cuda and _sorted_ones_ok(load_library(), p, o, W2, ADJ_ONES, q_div)
+    """shapes the paired update path covers (the critic's obstacle relation must take the sorted all-ones kernels, or be empty)"""
+    return p.is_cuda and (o.shape[1] == 0 or _sorted_ones_ok(load_library(), p, o, W2, ADJ_ONES, q_div))
 
 
-def msg_agg3_pair_train(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, q_div=1):
+def msg_agg3_pair_train(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, q_div=1, e_ref=None):
     """-> (m3_actor, m3_critic) with autograd: msg_agg3(.., False) and msg_agg3(.., True) of one mini-batch from shared passes"""
-    return _MsgAgg3Pair.apply(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, q_div)
+    return _MsgAgg3Pair.apply(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, q_div, e_ref)
 
 
-def msg_agg3(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, is_critic, o_kvalid=None, q_div=1):
-    """(R, P, 3, E): the message/aggregate of the defender, evader and obstacle relation (DHGN/mappo_parallel.py:256-281)."""
+def msg_agg3(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, is_critic, o_kvalid=None, q_div=1, e_ref=None):
+    """(R, P, 3, E): the message/aggregate of the defender, evader and obstacle relation (DHGN/mappo_parallel.py:256-281).
+    e (R, K_e, 4) with K_e >= 1 evaders; the defender relation's p_i - e term reads e itself (K_e = 1) or e_ref (R, 4) when given.
+    o may be empty, (R / q_div, 0, 4): that relation's slot is zero and its dW, db are exactly zero."""
     mode = ADJ_ONES if is_critic else ADJ_TENSOR
     mode_o = ADJ_VALID if (is_critic and o_kvalid is not None) else mode
     if mode_o == ADJ_TENSOR and adj_o.dtype == torch.int32:  # bit-packed LiDAR rows (env o_adj_bits): same results, 1/29 of the bytes
         mode_o = ADJ_BITS
     return _MsgAgg3.apply(p, e, o, adj_p, adj_e, adj_o, o_kvalid if mode_o == ADJ_VALID else None, W0, b0, W1, b1, W2, b2, mode,
-                          mode_o, q_div)
+                          mode_o, q_div, e_ref)
 
 
 def gae_advnorm(r, v, active, gamma, lamda, use_adv_norm=True):

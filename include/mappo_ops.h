@@ -31,6 +31,7 @@ enum { MO_ADJ_TENSOR = 0,   /* actor: the observed adjacency                    
  * i.e. DHGN.coordinate + DHGN.message + the matmul of DHGN.mean_operator (DHGN/mappo_parallel.py:235-239,
  * 323-334, 346-347) for relation 0 (q = p, din = 8, e given), 1 (q = e, K = 1) and 2 (q = obstacles).
  *   R rows, P agents, K neighbours, E features (multiple of 64, <= 256), din in {4, 8};
+ *   K = 0 is an empty relation (env_n2n: no obstacles): q and adj may be NULL, out gets zeros, the backward exact zero dW, db;
  *   p [R][P][4] (rows p_row_stride elements apart, likewise e and adj: rows may be slices buffer[:, t] of (N,T,..)
  *   replay-buffer tensors); q [R/q_div][K][4] (q_div p-rows share one q-row: obstacles are static over an episode);
  *   e [R][4] or NULL (din == 4); adj [R][P][K] float (MO_ADJ_TENSOR) or packed words (MO_ADJ_BITS); kvalid [R/q_div] (MO_ADJ_VALID);

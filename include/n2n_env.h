@@ -62,6 +62,47 @@ int n2n_evader_slsqp_nit(const n2n_config *cfg, const n2n_state *st, double *e_c
 int n2n_evader_slsqp_host(const n2n_config *cfg, int32_t N, const double *p, const double *e, const double *target, double *e_cmd,
                           int32_t *nit);
 
+/* ---- MAPPO on env_n2n (n2n_agent.py) ----
+ * Same lane layout as the tick (lane = (environment, agent slot)).  fp32 outputs with *_rs = elements between environments, so
+ * they may land in dense static storage or in step t of (N, T, ...) buffers; a NULL output is skipped.  A row is LIVE when its
+ * pursuer is active at the start of the step and its environment was not done before it. */
+typedef struct n2n_policy_io {
+    const float *pp_in; int64_t pp_in_rs;   /* [N][P][P] the tick's pp_adj (n2n_obs_out), required with pp_adj          */
+    const float *pe_in; int64_t pe_in_rs;   /* [N][P][E] the tick's pe_adj, required with pe_adj                        */
+    float *p4;    int64_t p4_rs;            /* [N][P][4] (x, y, v cos phi, v sin phi); cos / sin in f64, then rounded;
+                                               a row that is not live is zero                                          */
+    float *e4;    int64_t e4_rs;            /* [N][E][4] the same for the evaders; an inactive evader's row is zero     */
+    float *e_ref; int64_t e_ref_rs;         /* [N][4] the lowest-index active evader's row, zeros when none is active    */
+    float *live;  int64_t live_rs;          /* [N][P] 1 / 0                                                             */
+    float *pp_adj; int64_t pp_adj_rs;       /* [N][P][P] pp_in where pursuers i and j are both live, else 0             */
+    float *pe_adj; int64_t pe_adj_rs;       /* [N][P][E] pe_in where pursuer i is live and evader k active, else 0     */
+} n2n_policy_io;
+
+typedef struct n2n_policy_acc {  /* per-environment episode accumulators [N], zeroed by the caller before the first step */
+    uint8_t *done_before;        /* the environment reported done in an earlier step                                  */
+    uint8_t *ended;              /* it ended for a reason other than the time limit (evader at target, no pursuer or no
+                                    evader left), in this or an earlier step                                          */
+    uint8_t *captured;           /* every evader was captured before done                                             */
+    float *ret;                  /* sum over steps of sum_p reward * live (fp32, agents summed in order per step)      */
+    float *length;               /* steps taken before done                                                            */
+} n2n_policy_acc;
+
+typedef struct n2n_record_io {
+    const float *live;  int64_t live_rs;    /* [N][P] this step's live mask (n2n_policy_inputs), required               */
+    const float *value; int64_t value_rs;   /* [N][P] the critic's value of this step, required with v                  */
+    float *r;      int64_t r_rs;            /* [N][P] reward * live                                                     */
+    float *active; int64_t active_rs;       /* [N][P] live                                                              */
+    float *v;      int64_t v_rs;            /* [N][P] value * live                                                      */
+    float *v_next; int64_t v_next_rs;       /* [N][P] set to 0 where the pursuer is inactive after the step or its
+                                               environment has ended (time limit excepted); other entries untouched     */
+} n2n_record_io;
+
+/* Before the policy step: the DHGN's inputs from the records p, e, the tick's adjacencies and done_before [N] (NULL: none done). */
+int n2n_policy_inputs(const n2n_config *cfg, const n2n_state *st, const uint8_t *done_before, const n2n_policy_io *io, void *stream);
+/* After n2n_env_tick: buffer row t and the accumulators from the tick's reward [N][P] and done [N] and the records after it. */
+int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
+                      const n2n_policy_acc *acc, void *stream);
+
 /* Host side of ParticleEnv.reset (:200-281) with a bit-exact replica of numpy's legacy RandomState per environment
  * (np.random.seed(seeds[n])).  Fills host arrays p [N][P][5], e [N][E][5], target [N][2]. */
 void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seeds);

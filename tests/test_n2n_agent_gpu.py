@@ -1,0 +1,440 @@
+"""GPU checks of MAPPO on env_n2n: n2n_policy_inputs / n2n_policy_record against tests/n2n_policy_ref.py, the message kernels with an
+empty obstacle relation and several evaders against an f64 torch restatement of the reference's DHGN encoder, and the N2nMAPPO agent /
+N2nTrainer (buffer invariants, rollout-update agreement, gradients against an f64 re-evaluation, determinism, training, cfg4_n2n)."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import n2n_policy_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+
+def _ops():
+    from distributed_multi_agent_reinforcement_learning_amd import ops
+    return ops
+
+
+def _env(N, P, E, seed0=0, episode_limit=100):
+    from distributed_multi_agent_reinforcement_learning_amd.n2n_env import ParticleEnv
+    env = ParticleEnv(num_envs=N, seeds=list(range(seed0, seed0 + N)), episode_limit=episode_limit, evader="slsqp")
+    env.initialize(P, E)
+    return env
+
+
+def _strided(shape):
+    """a (N, ...) view with strided environment rows, like buffer[:, t] of an (N, 3, ...) tensor"""
+    big = torch.full((shape[0], 3, *shape[1:]), 7.0, device="cuda")
+    return big[:, 1]
+
+
+def _ulp_close(got, want64):
+    """every element within one fp32 ulp of the float64 value"""
+    want32 = want64.astype(np.float32)
+    ulp = np.spacing(np.abs(want32)).astype(np.float64)
+    return np.all(np.abs(got.astype(np.float64) - want64) <= ulp)
+
+
+# ---- n2n_policy_inputs / n2n_policy_record -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("P", [4, 8, 16])
+@pytest.mark.parametrize("E", [1, 2, 4])
+def test_policy_inputs_and_record_match_numpy(P, E):
+    rng = np.random.default_rng(100 * P + E)
+    N = 150
+    env = _env(N, P, E)
+    p, e, target, pp_in, pe_in = ref.random_records(rng, N, P, E)
+    acc_np = ref.new_accumulators(N)
+    acc_np["done_before"][:] = rng.random(N) < 0.2
+    acc_np["ended"][:] = acc_np["done_before"] & (rng.random(N) < 0.5)
+    acc_np["ret"][:] = rng.standard_normal(N).astype(np.float32)
+    acc_np["length"][:] = rng.integers(0, 50, N).astype(np.float32)
+    env.p.copy_(torch.from_numpy(p))
+    env.e.copy_(torch.from_numpy(e))
+    env.target.copy_(torch.from_numpy(target))
+    env.obs["pp_adj"].copy_(torch.from_numpy(pp_in))
+    env.obs["pe_adj"].copy_(torch.from_numpy(pe_in))
+    acc = {k: torch.from_numpy(v).cuda() for k, v in acc_np.items()}
+    outs = dict(p4=_strided((N, P, 4)), e4=_strided((N, E, 4)), e_ref=_strided((N, 4)), live=_strided((N, P)), pp_adj=_strided((N, P, P)),
+                pe_adj=_strided((N, P, E)))
+    env.policy_inputs(**outs, done_before=acc["done_before"])
+    want = ref.policy_inputs(p, e, pp_in, pe_in, acc_np["done_before"])
+    got = {k: v.cpu().numpy() for k, v in outs.items()}
+    for k in ("live", "pp_adj", "pe_adj"):
+        assert np.array_equal(got[k], want[k]), k
+    live = want["live"].astype(bool)
+    e_on = e[:, 4] != 0
+    # features: within one fp32 ulp of the float64 value; zero rows exactly zero
+    for k, rec, on in (("p4", p, live), ("e4", e, e_on)):
+        f64 = np.stack((rec[:, 0], rec[:, 1], rec[:, 3] * np.cos(rec[:, 2]), rec[:, 3] * np.sin(rec[:, 2])), -1)
+        assert _ulp_close(got[k][on], f64[on]), k
+        assert np.all(got[k][~on] == 0), k
+    for n in range(N):
+        k = np.flatnonzero(e_on[n])
+        if k.size:
+            f64 = np.array([e[n, 0, k[0]], e[n, 1, k[0]], e[n, 3, k[0]] * np.cos(e[n, 2, k[0]]), e[n, 3, k[0]] * np.sin(e[n, 2, k[0]])])
+            assert _ulp_close(got["e_ref"][n], f64)
+        else:
+            assert np.all(got["e_ref"][n] == 0)
+    assert live.any() and (~live).any() and acc_np["done_before"].any()
+    # record, after a "tick": reward and done as the tick leaves them, rows written into strided buffer slices
+    reward = rng.integers(-2, 3, (N, P)).astype(np.float32) * (p[:, 4] != 0)
+    done = (rng.random(N) < 0.3).astype(np.uint8)
+    value = rng.standard_normal((N, P)).astype(np.float32)
+    env.reward_t.copy_(torch.from_numpy(reward))
+    env.done_t.copy_(torch.from_numpy(done))
+    bufs = dict(r=_strided((N, P)), active=_strided((N, P)), v=_strided((N, P)), v_next=_strided((N, P)))
+    env.policy_record(acc, outs["live"], torch.from_numpy(value).cuda(), **bufs)
+    r, active, v, vz, acc_want = ref.policy_record(p, e, target, reward, done, want["live"], value, acc_np, env.kill_radius)
+    assert np.array_equal(bufs["r"].cpu().numpy(), r) and np.array_equal(bufs["active"].cpu().numpy(), active)
+    assert np.array_equal(bufs["v"].cpu().numpy(), v)
+    assert np.array_equal(bufs["v_next"].cpu().numpy(), np.where(vz, np.float32(0), np.float32(7)))
+    for k, x in acc_want.items():
+        assert np.array_equal(acc[k].cpu().numpy(), x), k
+    assert acc_want["ended"].sum() > acc_np["ended"].sum() and acc_want["captured"].any()
+
+
+# ---- message kernels: empty obstacle relation, several evaders, e_ref --------------------------------------------------------------
+def _f64_encoder(enc, p, e, e_ref, adj_p, adj_e, is_critic):
+    """the reference's DHGN.encoder (DHGN/mappo_parallel.py:241-304) restated in torch on whole tensors: coordinate, message, the
+    L1-normalised mean per relation (ones for the critic), AGG_vertex_0 + ReLU, the semantic layer; the obstacle relation is empty"""
+    M = enc.MSG_layers
+    R, P = p.shape[0], p.shape[1]
+    rel0 = torch.cat(((p[:, :, None] - p[:, None, :]), (p - e_ref[:, None])[:, :, None].expand(R, P, P, 4)), -1)
+    rel1 = p[:, :, None] - e[:, None, :]
+    m = []
+    for r, (rel, adj) in enumerate(((rel0, adj_p), (rel1, adj_e))):
+        msg = F.relu(F.linear(rel, M[r].weight, M[r].bias))
+        a = F.normalize(torch.ones_like(adj) if is_critic else adj, p=1, dim=-1)
+        m.append((a[..., None] * msg).sum(-2))
+    m.append(torch.zeros_like(m[0]))        # normalize() of an empty neighbour set
+    agg0 = enc.AGG_layers["AGG_vertex_0"]
+    embs = [F.relu(F.linear(x, agg0.weight, agg0.bias)) for x in m]
+    return m, enc.semantic_layer(torch.cat([p] + embs, -1))
+
+
+def _msg_inputs(R, P, K, seed):
+    g = torch.Generator().manual_seed(seed)
+    p = torch.rand(R, P, 4, generator=g) * 20
+    e = torch.rand(R, K, 4, generator=g) * 20
+    e_ref = e[torch.arange(R), torch.randint(0, K, (R,), generator=g)]
+    adj_p = (torch.rand(R, P, P, generator=g) < 0.5).float()
+    adj_e = (torch.rand(R, P, K, generator=g) < 0.5).float()
+    adj_p[0] = 0
+    adj_e[1] = 0
+    return p, e, e_ref, adj_p, adj_e
+
+
+def _enc(seed=0):
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config
+    from distributed_multi_agent_reinforcement_learning_amd.model import build_actor_critic
+    torch.manual_seed(seed)
+    actor, critic = build_actor_critic(baseline_config("cfg4_n2n"), "cuda")
+    return actor, critic
+
+
+@pytest.mark.parametrize("P,K", [(8, 1), (8, 2), (8, 4), (16, 4), (16, 8)])
+def test_message_kernels_empty_obstacles_and_several_evaders(P, K):
+    ops = _ops()
+    actor, _ = _enc(P + K)
+    enc = actor.shared_net
+    M = enc.MSG_layers
+    W = [M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias]
+    R = 96
+    p, e, e_ref, adj_p, adj_e = (x.cuda() for x in _msg_inputs(R, P, K, 7 * P + K))
+    o, adj_o = torch.zeros(R, 0, 4, device="cuda"), torch.zeros(R, P, 0, device="cuda")
+    enc64 = copy.deepcopy(enc).double()
+    refs = {}
+    for crit in (False, True):
+        m_ref, _ = _f64_encoder(enc64, p.double(), e.double(), e_ref.double(), adj_p.double(), adj_e.double(), crit)
+        refs[crit] = torch.stack(m_ref, 2)
+    # one network at a time (the critic: ones over every slot), forward and backward
+    gouts = [torch.randn(R, P, 3, 128, device="cuda", dtype=torch.float64) for _ in range(2)]
+    grads = {}
+    for crit in (False, True):
+        out = ops.msg_agg3(p, e, o, adj_p, adj_e, adj_o, *W, crit, e_ref=e_ref)
+        assert torch.allclose(out.double(), refs[crit], rtol=2e-5, atol=2e-5), crit
+        assert torch.all(out[:, :, 2] == 0)
+        gs = torch.autograd.grad(out, W, gouts[crit].float())
+        assert torch.all(gs[4] == 0) and torch.all(gs[5] == 0)
+        grads[crit] = gs
+    # the rollout's paired forward (no autograd): bit-identical to the two calls
+    with torch.no_grad():
+        pair = ops.msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, *W, e_ref=e_ref)
+        for crit in (False, True):
+            assert torch.equal(pair[int(crit)], ops.msg_agg3(p, e, o, adj_p, adj_e, adj_o, *W, crit, e_ref=e_ref))
+    # the update's paired pass: same forward, the summed gradient of both networks
+    assert ops.msg_agg3_pair_train_ok(p, o, W[4], 1)
+    ma, mc = ops.msg_agg3_pair_train(p, e, o, adj_p, adj_e, adj_o, *W, 1, e_ref=e_ref)
+    assert torch.equal(ma, ops.msg_agg3(p, e, o, adj_p, adj_e, adj_o, *W, False, e_ref=e_ref))
+    assert torch.equal(mc, ops.msg_agg3(p, e, o, adj_p, adj_e, adj_o, *W, True, e_ref=e_ref))
+    gp = torch.autograd.grad((ma, mc), W, (gouts[0].float(), gouts[1].float()))
+    assert torch.all(gp[4] == 0) and torch.all(gp[5] == 0)
+    # gradients against the f64 restatement
+    W64 = [w.detach().double().requires_grad_(True) for w in W]
+    enc64.MSG_layers[0].weight, enc64.MSG_layers[0].bias = torch.nn.Parameter(W64[0]), torch.nn.Parameter(W64[1])
+    enc64.MSG_layers[1].weight, enc64.MSG_layers[1].bias = torch.nn.Parameter(W64[2]), torch.nn.Parameter(W64[3])
+    tot = [torch.zeros_like(w) for w in W64[:4]]
+    for crit in (False, True):
+        m_ref, _ = _f64_encoder(enc64, p.double(), e.double(), e_ref.double(), adj_p.double(), adj_e.double(), crit)
+        g64 = torch.autograd.grad(torch.stack(m_ref, 2), [enc64.MSG_layers[r // 2].weight if r % 2 == 0 else enc64.MSG_layers[r // 2].bias
+                                                            for r in range(4)], gouts[crit])
+        for i in range(4):
+            gi = grads[crit][i].double()
+            assert torch.allclose(gi, g64[i], rtol=2e-4, atol=2e-4 * g64[i].abs().max().item()), (crit, i)
+            tot[i] += g64[i]
+    for i in range(4):
+        assert torch.allclose(gp[i].double(), tot[i], rtol=2e-4, atol=2e-4 * tot[i].abs().max().item()), i
+
+
+def test_e_ref_none_is_todays_call():
+    """pursuit's shapes (one evader, obstacles): e_ref=None and an explicit e_ref equal to e give the very same bits as before"""
+    ops = _ops()
+    actor, _ = _enc(5)
+    M = actor.shared_net.MSG_layers
+    W = [M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias]
+    R, P, O = 64, 8, 40
+    p, e, _, adj_p, adj_e = (x.cuda() for x in _msg_inputs(R, P, 1, 3))
+    g = torch.Generator(device="cuda").manual_seed(1)
+    o = torch.rand(R, O, 4, device="cuda", generator=g) * 20
+    adj_o = (torch.rand(R, P, O, device="cuda", generator=g) < 0.2).float()
+    for crit in (False, True):
+        a = ops.msg_agg3(p, e, o, adj_p, adj_e, adj_o, *W, crit)
+        b = ops.msg_agg3(p, e, o, adj_p, adj_e, adj_o, *W, crit, e_ref=e.reshape(R, 4))
+        assert torch.equal(a, b)
+        ga = torch.autograd.grad(a, W, torch.ones_like(a))
+        gb = torch.autograd.grad(b, W, torch.ones_like(b))
+        assert all(torch.equal(x, y) for x, y in zip(ga, gb))
+    with torch.no_grad():
+        assert torch.equal(ops.msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, *W), ops.msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, *W, e_ref=e.reshape(R, 4)))
+
+
+# ---- agent ----------------------------------------------------------------------------------------------------------------------------
+def _agent(seed=0, N=48, T=40, P=8, E=2, depth=3, **ov):
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config
+    from distributed_multi_agent_reinforcement_learning_amd.n2n_agent import N2nMAPPO, make_env
+    cfg = baseline_config("cfg4_n2n", **{"runtime.num_envs": N, "env.max_steps": T, "env.num_defender": P, "env.num_evader": E,
+                                         "algo.depth": depth, "runtime.seed": seed, **ov})
+    env = make_env(cfg, N)
+    torch.manual_seed(seed)
+    return N2nMAPPO(cfg, N, max(1, round(N / 10))), env
+
+
+def _explore(agent, env):
+    mean_r, buf, steps, stats = agent.explore_env(env)
+    return {k: v.clone() for k, v in buf.items()}, steps, stats
+
+
+@pytest.mark.parametrize("depth", [1, 3])
+def test_agent_buffer_invariants(depth):
+    agent, env = _agent(depth=depth)
+    N, T, P, E = env.num_envs, env.episode_limit, env.p_num, env.e_num
+    buf = agent.new_buffer(N, T, P, E)
+    acc = agent.run_episode(env, buf)
+    act, r, v = buf["active"], buf["r"], buf["v_n"]
+    assert torch.all((act == 0) | (act == 1)) and torch.all(act[:, 1:] <= act[:, :-1])
+    dead = act == 0
+    assert dead.any() and torch.all(r[dead] == 0) and torch.all(v[:, :T][dead] == 0)
+    assert torch.all(buf["p_state"][dead] == 0) and torch.all(buf["p_adj"][dead] == 0) and torch.all(buf["e_adj"][dead] == 0)
+    a = buf["a_n"]
+    assert torch.all((a >= 0) & (a < 9)) and torch.all(a == a.round())
+    # the accumulated return is the buffer's reward summed; the length counts the steps with a live row or before done
+    assert torch.allclose(acc["ret"], r.sum((1, 2)), rtol=1e-5, atol=1e-4)
+    assert torch.all(acc["length"] >= act.amax(-1).sum(-1))
+    # the stored log-probabilities: log softmax of the actor re-evaluated at the stored inputs
+    with torch.no_grad():
+        prob, _ = agent.sequence_forward(buf, 0, N)
+    lp = torch.log_softmax(torch.log(prob), -1).gather(-1, a.long()[..., None])[..., 0]
+    live = act == 1
+    err = (lp - buf["a_logprob_n"])[live].abs().max().item()
+    print(f"depth {depth}: capture rate {acc['captured'].float().mean().item():.3f}, length {acc['length'].mean().item():.1f}, "
+          f"live rows {int(live.sum())}, log-prob error {err:.2e}")
+    assert err <= 1e-5
+    assert torch.isfinite(buf["a_logprob_n"]).all() and torch.isfinite(v).all()
+
+
+def test_agent_update_forward_reproduces_rollout():
+    agent, env = _agent(1)
+    buf, _, _ = _explore(agent, env)
+    N, T = buf["r"].shape[:2]
+    with torch.enable_grad():
+        prob, values = agent.sequence_forward(buf, 0, N)
+    lp = torch.distributions.Categorical(prob.detach()).log_prob(buf["a_n"])
+    live = buf["active"] == 1
+    assert live.sum() > 0
+    assert (lp - buf["a_logprob_n"])[live].abs().max().item() <= 1e-4
+    assert (values.detach() - buf["v_n"][:, :T])[live].abs().max().item() <= 1e-4
+
+
+def _final_inputs(env, mask_pursuers=True):
+    """the state after the last step as the critic's inputs, restated in torch from the records without the done mask (float64);
+    mask_pursuers=False zeroes every pursuer row and adjacency -- what a done mask over all environments leaves"""
+    p, e = env.p, env.e
+    pon, eon = (p[:, 4] != 0).double(), (e[:, 4] != 0).double()
+    if not mask_pursuers:
+        pon = torch.zeros_like(pon)
+    rows = lambda r, on: torch.stack((r[:, 0], r[:, 1], r[:, 3] * torch.cos(r[:, 2]), r[:, 3] * torch.sin(r[:, 2])), -1) * on[..., None]
+    p4, e4 = rows(p, pon), rows(e, eon)
+    first = torch.argmax(eon, -1)
+    e_ref = e4[torch.arange(e4.shape[0], device=e4.device), first] * eon.amax(-1)[:, None]
+    pp = env.obs["pp_adj"].double() * pon[:, :, None] * pon[:, None, :]
+    pe = env.obs["pe_adj"].double() * pon[:, :, None] * eon[:, None, :]
+    return p4, e4, e_ref, pp, pe
+
+
+def test_bootstrap_value_is_the_critic_on_the_final_state():
+    """v_n[:, T] of the episodes cut by the time limit: the critic continued one step past the buffer's T steps on the state after the
+    last step (unmasked records, the stored history), re-evaluated in float64"""
+    agent, env = _agent(4, N=48, T=40, depth=2)
+    N, T, P, E = env.num_envs, env.episode_limit, env.p_num, env.e_num
+    buf = agent.new_buffer(N, T, P, E)
+    agent.run_episode(env, buf)
+    kept = buf["v_n"][:, T] != 0
+    assert kept.sum() > 0
+    actor64, critic64 = copy.deepcopy(agent.actor).double(), copy.deepcopy(agent.critic).double()
+    critic64.shared_net = actor64.shared_net
+
+    def boot(mask_pursuers):
+        p4, e4, e_ref, pp, pe = _final_inputs(env, mask_pursuers)
+        ext = {k: buf[k].double() for k in ("actor_historical_embedding", "critic_historical_embedding")}
+        for k, x in (("p_state", p4), ("e_state", e4), ("e_ref", e_ref), ("p_adj", pp), ("e_adj", pe)):
+            ext[k] = torch.cat((buf[k].double(), x[:, None]), 1)
+        ext["r"] = torch.zeros(N, T + 1, P, dtype=torch.float64, device="cuda")
+        with torch.no_grad():
+            _, values = _f64_forward(actor64, critic64, ext, 0, N, agent.depth)
+        return values[:, T]
+
+    want = boot(True)
+    err = (buf["v_n"][:, T].double() - want)[kept].abs().max().item()
+    zeroed = (buf["v_n"][:, T].double() - boot(False))[kept].abs().max().item()
+    print(f"bootstrap rows kept {int(kept.sum())}: error {err:.2e}; against the all-masked state {zeroed:.2e}")
+    assert err <= 5e-4
+    assert zeroed > 1e-2      # the test tells the two states apart
+
+
+def _f64_forward(actor, critic, buf, n0, n1, depth):
+    """f64 (or fp32) torch re-evaluation of the update's forward: _f64_encoder, the FCRA hops on the stored history, nn.GRU, the heads"""
+    enc = actor.shared_net
+    dt = enc.semantic_layer.weight.dtype
+    T, P, E = buf["r"].shape[1], buf["r"].shape[2], buf["e_state"].shape[2]
+    B = n1 - n0
+    R = B * T
+    cv = lambda x: x.to(dt)
+    p, e = cv(buf["p_state"][n0:n1].reshape(R, P, 4)), cv(buf["e_state"][n0:n1].reshape(R, E, 4))
+    e_ref, adj_p, adj_e = cv(buf["e_ref"][n0:n1].reshape(R, 4)), cv(buf["p_adj"][n0:n1].reshape(R, P, P)), cv(buf["e_adj"][n0:n1].reshape(R, P, E))
+    outs = []
+    for crit, net, key in ((False, actor, "actor_historical_embedding"), (True, critic, "critic_historical_embedding")):
+        _, h = _f64_encoder(enc, p, e, e_ref, adj_p, adj_e, crit)
+        a = F.normalize(torch.ones_like(adj_p) if crit else adj_p, p=1, dim=-1)
+        for k in range(depth):
+            hist = cv(buf[key][n0:n1, depth - 1 - k: depth - 1 - k + T].reshape(R, P, -1))
+            nb = F.relu(enc.AGG_layers[f"AGG_fcra_{k}"](a @ hist))
+            h = F.relu(enc.FCRA_layers[k](torch.cat((nb, h), -1)))
+        x = h.reshape(B, T, P, -1).permute(1, 0, 2, 3).reshape(T, B * P, -1)
+        y, _ = net.GRU(x)
+        outs.append(y.reshape(T, B, P, -1))
+    prob = torch.softmax(F.linear(outs[0], actor.Mean.weight, actor.Mean.bias), -1).permute(1, 0, 2, 3)
+    values = critic.Mean(outs[1]).permute(1, 0, 2, 3)[..., 0]
+    return prob, values
+
+
+def _ppo(prob, values, b, adv, v_target, n0, n1, eps, ent, clip):
+    cv = lambda x: x[n0:n1].to(prob.dtype)
+    dist = torch.distributions.Categorical(prob)
+    ratios = torch.exp(dist.log_prob(b["a_n"][n0:n1].to(prob.device)) - cv(b["a_logprob_n"]))
+    A, act = cv(adv), cv(b["active"])
+    actor_loss = -torch.min(ratios * A, torch.clamp(ratios, 1 - eps, 1 + eps) * A) - ent * dist.entropy()
+    actor_loss = (actor_loss * act).sum() / act.sum()
+    vt = cv(v_target)
+    if clip:
+        vo = b["v_n"][n0:n1, :-1].to(prob.dtype)
+        critic_loss = torch.max((torch.clamp(values - vo, -eps, eps) + vo - vt) ** 2, (values - vt) ** 2)
+    else:
+        critic_loss = (values - vt) ** 2
+    return actor_loss, (critic_loss * act).sum() / act.sum()
+
+
+def _oracle_grads(actor0, critic0, buf, adv, v_target, agent, dtype, device):
+    actor, critic = copy.deepcopy(actor0).to(device, dtype), copy.deepcopy(critic0).to(device, dtype)
+    critic.shared_net = actor.shared_net
+    b = {k: v.to(device) for k, v in buf.items()}
+    adv, v_target = adv.to(device), v_target.to(device)
+    N = buf["r"].shape[0]
+    for n0 in range(0, N, agent.mini_batch_size):
+        n1 = min(n0 + agent.mini_batch_size, N)
+        prob, values = _f64_forward(actor, critic, b, n0, n1, agent.depth)
+        la, lc = _ppo(prob, values, b, adv, v_target, n0, n1, agent.epsilon, agent.entropy_coef, agent.use_value_clip)
+        (la + lc).backward()
+    named = {("actor." + k): p for k, p in actor.named_parameters()} | {("critic." + k): p for k, p in critic.named_parameters()}
+    return {k: p.grad.double().cpu() for k, p in named.items() if p.grad is not None}
+
+
+def test_agent_gradients_match_f64_torch():
+    agent, env = _agent(2, N=30, T=24, depth=2)
+    buf, steps, _ = _explore(agent, env)
+    with torch.no_grad():      # move the policy away from the rollout's: ratios leave 1 on both sides of the clip
+        g = torch.Generator(device="cuda").manual_seed(0)
+        for p in agent.actor.Mean.parameters():
+            p.add_(torch.randn(p.shape, generator=g, device="cuda") * 0.3 * p.abs().mean())
+    actor0, critic0 = copy.deepcopy(agent.actor), copy.deepcopy(agent.critic)
+    agent.use_grad_clip = False
+    with torch.enable_grad():
+        agent.train(buf, steps)
+    adv, v_target = _ops().gae_advnorm(buf["r"], buf["v_n"], buf["active"], agent.gamma, agent.lamda, agent.use_adv_norm)
+    ref64 = _oracle_grads(actor0, critic0, buf, adv, v_target, agent, torch.float64, "cuda")
+    o32 = [_oracle_grads(actor0, critic0, buf, adv, v_target, agent, torch.float32, d) for d in ("cuda", "cpu")]
+    got = {("actor." + k): p.grad for k, p in agent.actor.named_parameters() if p.grad is not None} | \
+          {("critic." + k): p.grad for k, p in agent.critic.named_parameters() if p.grad is not None}
+    empty = {k for k in got if ".MSG_layers.2." in k}      # the empty obstacle relation: the restatement has no such layer
+    assert len(empty) == 4 and all(torch.all(got[k] == 0) for k in empty)
+    assert set(got) - empty == set(ref64) and "actor.shared_net.MSG_layers.1.weight" in got
+    for k, r in ref64.items():
+        gk = got[k].double().cpu()
+        noise = max((o[k] - r).abs().max().item() for o in o32)
+        scale = r.abs().max().item()
+        err = (gk - r).abs().max().item()
+        assert err <= 4 * noise + 2e-5 * scale, (k, err, noise, scale)
+
+
+def test_agent_determinism():
+    def run():
+        agent, env = _agent(3, N=32, T=30)
+        buf, steps, _ = _explore(agent, env)
+        with torch.enable_grad():
+            agent.train(buf, steps)
+        agent.ac_optimizer.step()
+        return buf, [p.detach().clone() for p in agent.ac_parameters]
+    b1, p1 = run()
+    b2, p2 = run()
+    for k in b1:
+        assert torch.equal(b1[k], b2[k]), k
+    for x, y in zip(p1, p2):
+        assert torch.equal(x, y)
+
+
+def test_trainer_iterates():
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config
+    from distributed_multi_agent_reinforcement_learning_amd.n2n_agent import N2nTrainer
+    cfg = baseline_config("cfg4_n2n", **{"runtime.num_envs": 64, "env.num_defender": 4, "env.max_steps": 50})
+    tr = N2nTrainer(cfg, num_eval_envs=16, eval_every=3)
+    before = [p.detach().clone() for p in tr.agent.ac_parameters]
+    logs = [tr.iterate()[1] for _ in range(3)]
+    for log in logs:
+        assert np.isfinite(log["critic_loss"]) and np.isfinite(log["actor_loss"]) and np.isfinite(log["mean_return"])
+        assert 0 <= log["capture_rate"] <= 1 and 0 < log["episode_length"] <= 50
+    assert "eval_return" in logs[2] and np.isfinite(logs[2]["eval_return"])
+    changed = sum(not torch.equal(a, b.detach()) for a, b in zip(before, tr.agent.ac_parameters))
+    assert changed >= len(before) - 2          # all but the empty obstacle relation's MSG layer
+    assert tr.total_steps == 3 * 64 * 50
+
+
+def test_cfg4_n2n_full_size_one_iteration():
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config
+    from distributed_multi_agent_reinforcement_learning_amd.n2n_agent import N2nTrainer
+    tr = N2nTrainer(baseline_config("cfg4_n2n"))
+    steps, log = tr.iterate()
+    assert steps == 1024 * 100
+    assert np.isfinite(log["critic_loss"]) and np.isfinite(log["actor_loss"])
+    print("cfg4_n2n 1024 x 16:", log, "rollout / update ms:", tr.last_breakdown_ms())
