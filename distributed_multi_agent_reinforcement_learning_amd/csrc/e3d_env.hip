@@ -410,6 +410,26 @@ void *e3d_resetter_create(const e3d_config *cfg, int32_t N, const uint32_t *seed
 
 void e3d_resetter_destroy(void *h) { delete (E3dResetter *)h; }
 
+// Resume support: every environment's generator (rng_replica.hpp ResetterStateHeader, then one NpRandom record each; E = 1).
+static rngrep::ResetterStateHeader e3d_state_header(const E3dResetter &R) {
+    return rngrep::ResetterStateHeader{E3D_RESETTER_STATE_TAG, R.N, R.cfg.P, 1};
+}
+
+int64_t e3d_resetter_state_bytes(void *h) { return h ? rngrep::resetter_state_bytes(((E3dResetter *)h)->N) : 0; }
+
+int e3d_resetter_get_state(void *h, void *out) {
+    if (!h || !out) return E3D_ERR_NULL;
+    E3dResetter &R = *(E3dResetter *)h;
+    rngrep::resetter_state_get(e3d_state_header(R), R.rng.data(), out);
+    return 0;
+}
+
+int e3d_resetter_set_state(void *h, const void *in) {
+    if (!h || !in) return E3D_ERR_NULL;
+    E3dResetter &R = *(E3dResetter *)h;
+    return rngrep::resetter_state_set(e3d_state_header(R), R.rng.data(), in) ? 0 : E3D_ERR_BAD_STATE;
+}
+
 int e3d_resetter_reset(void *h, double *p, double *e, double *target, int32_t n_threads) {
     if (!h || !p || !e || !target) return E3D_ERR_NULL;
     E3dResetter &R = *(E3dResetter *)h;

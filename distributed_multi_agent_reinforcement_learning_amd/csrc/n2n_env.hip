@@ -492,6 +492,26 @@ void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seed
 
 void n2n_resetter_destroy(void *h) { delete (N2nResetter *)h; }
 
+// Resume support: every environment's generator (rng_replica.hpp ResetterStateHeader, then one NpRandom record each).
+static rngrep::ResetterStateHeader n2n_state_header(const N2nResetter &R) {
+    return rngrep::ResetterStateHeader{N2N_RESETTER_STATE_TAG, R.N, R.cfg.P, R.cfg.E};
+}
+
+int64_t n2n_resetter_state_bytes(void *h) { return h ? rngrep::resetter_state_bytes(((N2nResetter *)h)->N) : 0; }
+
+int n2n_resetter_get_state(void *h, void *out) {
+    if (!h || !out) return N2N_ERR_NULL;
+    N2nResetter &R = *(N2nResetter *)h;
+    rngrep::resetter_state_get(n2n_state_header(R), R.rng.data(), out);
+    return 0;
+}
+
+int n2n_resetter_set_state(void *h, const void *in) {
+    if (!h || !in) return N2N_ERR_NULL;
+    N2nResetter &R = *(N2nResetter *)h;
+    return rngrep::resetter_state_set(n2n_state_header(R), R.rng.data(), in) ? 0 : N2N_ERR_BAD_STATE;
+}
+
 int n2n_resetter_reset(void *h, double *p, double *e, double *target, int32_t n_threads) {
     if (!h || !p || !e || !target) return N2N_ERR_NULL;
     N2nResetter &R = *(N2nResetter *)h;

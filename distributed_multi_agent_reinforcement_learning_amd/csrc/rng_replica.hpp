@@ -3,7 +3,9 @@
 // RandomState (MT19937 + init_genrand seeding, random_sample, polar Box-Muller legacy_gauss with its cached value).
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 namespace rngrep {
 
@@ -93,5 +95,58 @@ struct NpRandom {
     }
     double normal(double loc, double scale) { return loc + scale * legacy_gauss(); }
 };
+
+// Resume blobs: one NpRandom as a fixed little-endian record independent of struct padding -- the MT19937 key (624 x u32),
+// its position (i32), has_gauss (i32, 0 or 1) and the cached gauss (f64).
+constexpr size_t NP_RANDOM_STATE_BYTES = 624 * 4 + 4 + 4 + 8;
+
+inline void np_random_pack(const NpRandom &r, unsigned char *out) {
+    const int32_t idx = r.g.idx, hg = r.has_gauss ? 1 : 0;
+    memcpy(out, r.g.mt, 624 * 4);
+    memcpy(out + 624 * 4, &idx, 4);
+    memcpy(out + 624 * 4 + 4, &hg, 4);
+    memcpy(out + 624 * 4 + 8, &r.gauss, 8);
+}
+
+// false (r untouched) when the record cannot come from np_random_pack: position outside [0, 624] or has_gauss not 0 / 1
+inline bool np_random_unpack(NpRandom &r, const unsigned char *in) {
+    int32_t idx, hg;
+    memcpy(&idx, in + 624 * 4, 4);
+    memcpy(&hg, in + 624 * 4 + 4, 4);
+    if (idx < 0 || idx > 624 || (hg != 0 && hg != 1)) return false;
+    memcpy(r.g.mt, in, 624 * 4);
+    r.g.idx = idx;
+    r.has_gauss = hg != 0;
+    memcpy(&r.gauss, in + 624 * 4 + 8, 8);
+    return true;
+}
+
+// Header of a resetter's state blob (n2n_resetter_get_state, e3d_resetter_get_state): a format tag and the shape it was taken
+// from; the NpRandom records of environments 0 .. N-1 follow.
+struct ResetterStateHeader {
+    uint32_t tag;
+    int32_t N, P, E;
+};
+
+inline int64_t resetter_state_bytes(int N) { return (int64_t)sizeof(ResetterStateHeader) + (int64_t)N * (int64_t)NP_RANDOM_STATE_BYTES; }
+
+inline void resetter_state_get(const ResetterStateHeader &h, const NpRandom *rng, void *out) {
+    unsigned char *o = (unsigned char *)out;
+    memcpy(o, &h, sizeof(h));
+    for (int n = 0; n < h.N; n++) np_random_pack(rng[n], o + sizeof(h) + (size_t)n * NP_RANDOM_STATE_BYTES);
+}
+
+// all or nothing: false (rng untouched) when the blob's header is not `want` or one of its records is malformed
+inline bool resetter_state_set(const ResetterStateHeader &want, NpRandom *rng, const void *in) {
+    const unsigned char *b = (const unsigned char *)in;
+    ResetterStateHeader h;
+    memcpy(&h, b, sizeof(h));
+    if (h.tag != want.tag || h.N != want.N || h.P != want.P || h.E != want.E) return false;
+    NpRandom probe;
+    for (int n = 0; n < h.N; n++)
+        if (!np_random_unpack(probe, b + sizeof(h) + (size_t)n * NP_RANDOM_STATE_BYTES)) return false;
+    for (int n = 0; n < h.N; n++) np_random_unpack(rng[n], b + sizeof(h) + (size_t)n * NP_RANDOM_STATE_BYTES);
+    return true;
+}
 
 }  // namespace rngrep

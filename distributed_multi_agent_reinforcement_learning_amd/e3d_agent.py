@@ -21,7 +21,8 @@ from torch.nn.utils import spectral_norm
 from . import ops
 from .e3d_env import ParticleEnv
 from .model import HeadLinear, _make_linear, _ortho_linear, _Trunk
-from .trainer import GradBucket, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed
+from .trainer import (GradBucket, ParticleRunState, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed,
+                      resume_path, save_resume_atomic)
 
 FEAT = 16   # e3d_policy_features columns (include/e3d_env.h)
 
@@ -242,9 +243,17 @@ class E3dMAPPO:
             p["lr"] = lr_now
         self.total_step = total_steps
 
-    def save_model(self, cwd):
+    def save_model(self, cwd, best=False):
+        """cwd/e3d_state_dicts.pt (best: e3d_state_dicts_best.pt), the actor's and critic's state_dicts"""
         os.makedirs(cwd, exist_ok=True)
-        torch.save({"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}, os.path.join(cwd, "e3d_state_dicts.pt"))
+        torch.save({"actor": self.actor.state_dict(), "critic": self.critic.state_dict()},
+                   os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt"))
+
+    def load_model(self, cwd, best=False):
+        """the weights save_model(cwd, best) wrote"""
+        sd = torch.load(os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt"), map_location=self.device)
+        self.actor.load_state_dict(sd["actor"])
+        self.critic.load_state_dict(sd["critic"])
 
 
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0):
@@ -256,7 +265,7 @@ def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0):
     return env
 
 
-class E3dTrainer:
+class E3dTrainer(ParticleRunState):
     """One rank of the data-parallel env_3d job: rollout, then epochs x (update, gradient all-reduce, Adam step)."""
 
     def __init__(self, cfg, num_envs=None, num_eval_envs=64, eval_every=0, tuned_gemms=True):
@@ -275,6 +284,8 @@ class E3dTrainer:
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
         self.eval_env = None
+        self.eval_return_std = None
+        self.recorder, self.best_eval_return = [], -float("inf")
         self.total_steps = 0
         self.iteration = 0
 
@@ -301,28 +312,43 @@ class E3dTrainer:
         return steps * self.world, log
 
     def evaluate(self):
-        """synchronous greedy episode (a = mu) on num_eval_envs environments of their own seeds and sampling stream"""
+        """synchronous greedy episode (a = mu) on num_eval_envs environments of their own seeds and sampling stream; the std of the
+        return over them goes to self.eval_return_std (a recorder column, not a log key)"""
+        ev = self.make_eval_env()
+        ret, captured, length = self.agent.run_episode(ev, None, greedy=True)
+        sd = ret.std() if ret.numel() > 1 else ret.new_zeros(())
+        r, c, l, self.eval_return_std = torch.stack((ret.mean(), captured.float().mean(), length.mean(), sd)).tolist()
+        return dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+
+    def make_eval_env(self):
+        """the evaluation environments (created once): num_eval_envs of their own seeds, seed + 10^6 + n"""
         if self.eval_env is None:
             self.eval_env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6)
-        ret, captured, length = self.agent.run_episode(self.eval_env, None, greedy=True)
-        r, c, l = torch.stack((ret.mean(), captured.float().mean(), length.mean())).tolist()
-        return dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+        return self.eval_env
 
     def last_breakdown_ms(self):
         ev = self.last_events
         return ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
 
 
-def train_e3d(cfg, max_iterations=None, num_eval_envs=64, eval_every=1):
+def train_e3d(cfg, max_iterations=None, num_eval_envs=64, eval_every=1, save_resume=None, resume=None):
     """the env_3d training loop (main --config cfg5): until max_train_steps env-steps or max_iterations; rank 0 prints one JSON log
-    line per iteration and saves the final weights under algo.save_cwd"""
+    line per iteration, records every evaluation (recorder.npy, learning curve, the _best weights: ParticleRunState.record_evaluation)
+    and saves the final weights under algo.save_cwd.  resume / save_resume: directories of the per-rank resume bundles read before the
+    first iteration / written after every one."""
     tr = E3dTrainer(cfg, num_eval_envs=num_eval_envs, eval_every=eval_every)
+    if resume is not None:
+        tr.load_resume(resume_path(resume, tr.rank))
     while tr.total_steps < cfg.algo.max_train_steps:
         t0 = time.time()
         steps, log = tr.iterate()
         if tr.rank == 0:
             log["seconds"] = round(time.time() - t0, 3)
             print(json.dumps(log), flush=True)
+            if "eval_return" in log:
+                tr.record_evaluation(log, cfg.algo.save_cwd)
+        if save_resume is not None:
+            save_resume_atomic(tr, save_resume)
         if max_iterations is not None and tr.iteration >= max_iterations:
             break
     if tr.rank == 0:

@@ -55,6 +55,10 @@ def load_library():
         L.e3d_evader_slsqp_nit.argtypes = [vp] * 5
         L.e3d_evader_slsqp_host.argtypes = [vp, C.c_int32] + [vp] * 5
         L.e3d_resetter_reset.argtypes = [vp, vp, vp, vp, C.c_int32]
+        L.e3d_resetter_state_bytes.argtypes = [vp]
+        L.e3d_resetter_state_bytes.restype = C.c_int64
+        L.e3d_resetter_get_state.argtypes = [vp, vp]
+        L.e3d_resetter_set_state.argtypes = [vp, vp]
         L.e3d_policy_features.argtypes = [vp] * 6
         _lib = L
     return _lib
@@ -154,6 +158,21 @@ class ParticleEnv:
         self._cmd = torch.zeros((N, 3), dtype=torch.float64, device=self.device)
         self.active_t.fill_(1)
         self.observe()
+
+    def get_resetter_state(self):
+        """the reset generators of every environment (include/e3d_env.h e3d_resetter_get_state) as a uint8 array"""
+        buf = np.empty(self.L.e3d_resetter_state_bytes(self.resetter), np.uint8)
+        _check(self.L.e3d_resetter_get_state(self.resetter, buf.ctypes.data_as(C.c_void_p)), "e3d_resetter_get_state")
+        return buf
+
+    def set_resetter_state(self, blob):
+        """restores get_resetter_state(); ValueError when the blob comes from another number of environments / agents"""
+        buf = np.ascontiguousarray(blob, np.uint8)
+        if buf.size != self.L.e3d_resetter_state_bytes(self.resetter):
+            raise ValueError("resetter state does not match this number of environments")
+        rc = self.L.e3d_resetter_set_state(self.resetter, buf.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise ValueError(f"resetter state does not match this configuration (e3d_resetter_set_state code {rc})")
 
     def observe(self):
         _check(self.L.e3d_env_observe(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), _stream()), "e3d_env_observe")

@@ -10,13 +10,22 @@ diagonal-Gaussian MAPPO on env_3d (e3d_agent.train_e3d); cfg4_n2n (or runtime.en
 
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --iterations 50
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg4_n2n --iterations 5
+
+Run protocol (all three environments): `--save-resume DIR` writes every rank's resume bundle DIR/resume_rank{r}.pt after each
+iteration, `--resume DIR` continues from them.  `--evaluate CWD` (env_3d and env_n2n) loads the final weights algo.save_cwd held
+(save_model), runs one greedy evaluation on --eval-envs environments, prints its JSON line and exits without training:
+
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --iterations 50 --save-resume ckpt
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --iterations 100 --resume ckpt --save-resume ckpt
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --evaluate ./model
 """
 import argparse
 import ast
+import json
 
 from .config import baseline_config, load_config
-from .e3d_agent import train_e3d
-from .n2n_agent import train_n2n
+from .e3d_agent import E3dTrainer, train_e3d
+from .n2n_agent import N2nTrainer, train_n2n
 from .trainer import train_agent_multiprocessing
 
 BASELINES = ("cfg1", "cfg2", "cfg3", "cfg4", "cfg5", "cfg4_n2n")
@@ -28,6 +37,10 @@ def main(argv=None):
     ap.add_argument("--iterations", type=int, default=None, help="stop after this many iterations (default: max_train_steps)")
     ap.add_argument("--eval-envs", type=int, default=64)
     ap.add_argument("--eval-every", type=int, default=1)
+    ap.add_argument("--save-resume", metavar="DIR", default=None, help="write DIR/resume_rank{r}.pt after every iteration")
+    ap.add_argument("--resume", metavar="DIR", default=None, help="load DIR/resume_rank{r}.pt before the first iteration")
+    ap.add_argument("--evaluate", metavar="CWD", default=None,
+                    help="env_3d / env_n2n: evaluate the weights saved under CWD on --eval-envs environments and exit")
     ap.add_argument("overrides", nargs="*", help="dotted overrides KEY=VALUE")
     args = ap.parse_args(argv)
     ov = {}
@@ -38,11 +51,32 @@ def main(argv=None):
         except (ValueError, SyntaxError):
             ov[k] = v
     cfg = baseline_config(args.config, **ov) if args.config in BASELINES else load_config(args.config, **ov)
-    if str(cfg.runtime.get("env", "pursuit")) == "e3d":
-        return train_e3d(cfg, max_iterations=args.iterations, num_eval_envs=args.eval_envs, eval_every=args.eval_every)
-    if str(cfg.runtime.get("env", "pursuit")) == "n2n":
-        return train_n2n(cfg, max_iterations=args.iterations, num_eval_envs=args.eval_envs, eval_every=args.eval_every)
-    return train_agent_multiprocessing(cfg, max_iterations=args.iterations, num_eval_envs=args.eval_envs, eval_every=args.eval_every)
+    env = str(cfg.runtime.get("env", "pursuit"))
+    if args.evaluate is not None:
+        if env not in ("e3d", "n2n"):
+            ap.error("--evaluate is for runtime.env e3d and n2n (cfg5, cfg4_n2n)")
+        return evaluate_saved(E3dTrainer if env == "e3d" else N2nTrainer, cfg, args.evaluate, args.eval_envs)
+    kw = dict(max_iterations=args.iterations, num_eval_envs=args.eval_envs, eval_every=args.eval_every)
+    if args.save_resume is not None:
+        kw["save_resume"] = args.save_resume
+    if args.resume is not None:
+        kw["resume"] = args.resume
+    if env == "e3d":
+        return train_e3d(cfg, **kw)
+    if env == "n2n":
+        return train_n2n(cfg, **kw)
+    return train_agent_multiprocessing(cfg, **kw)
+
+
+def evaluate_saved(trainer_cls, cfg, cwd, num_eval_envs):
+    """one synchronous greedy evaluation (trainer.evaluate: the eval seeds of a training run) of the weights save_model wrote under
+    cwd; rank 0 prints the eval keys as one JSON line"""
+    tr = trainer_cls(cfg, num_eval_envs=num_eval_envs)
+    tr.agent.load_model(cwd)
+    res = tr.evaluate()
+    if tr.rank == 0:
+        print(json.dumps(res), flush=True)
+    return res
 
 
 if __name__ == "__main__":

@@ -18,7 +18,8 @@ import torch
 from . import ops
 from .model import build_actor_critic, sequence_forward_pair
 from .n2n_env import ParticleEnv
-from .trainer import GradBucket, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed
+from .trainer import (GradBucket, ParticleRunState, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed,
+                      resume_path, save_resume_atomic)
 
 MAX_P = 16   # the message kernels' agents per row (csrc/mappo_ops.hip MAX_P)
 
@@ -229,10 +230,18 @@ class N2nMAPPO:
             p["lr"] = lr_now
         self.total_step = total_steps
 
-    def save_model(self, cwd):
+    def save_model(self, cwd, best=False):
+        """cwd/n2n_actor.pth and n2n_critic.pth (best: n2n_actor_best.pth, n2n_critic_best.pth), the two state_dicts"""
         os.makedirs(cwd, exist_ok=True)
-        torch.save(self.actor.state_dict(), os.path.join(cwd, "n2n_actor.pth"))
-        torch.save(self.critic.state_dict(), os.path.join(cwd, "n2n_critic.pth"))
+        sfx = "_best" if best else ""
+        torch.save(self.actor.state_dict(), os.path.join(cwd, f"n2n_actor{sfx}.pth"))
+        torch.save(self.critic.state_dict(), os.path.join(cwd, f"n2n_critic{sfx}.pth"))
+
+    def load_model(self, cwd, best=False):
+        """the weights save_model(cwd, best) wrote"""
+        sfx = "_best" if best else ""
+        self.actor.load_state_dict(torch.load(os.path.join(cwd, f"n2n_actor{sfx}.pth"), map_location=self.device))
+        self.critic.load_state_dict(torch.load(os.path.join(cwd, f"n2n_critic{sfx}.pth"), map_location=self.device))
 
 
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0):
@@ -244,7 +253,7 @@ def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0):
     return env
 
 
-class N2nTrainer:
+class N2nTrainer(ParticleRunState):
     """One rank of the data-parallel env_n2n job: rollout, then epochs x (update, gradient all-reduce, Adam step)."""
 
     def __init__(self, cfg, num_envs=None, num_eval_envs=64, eval_every=0, tuned_gemms=True):
@@ -263,6 +272,8 @@ class N2nTrainer:
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
         self.eval_env = None
+        self.eval_return_std = None
+        self.recorder, self.best_eval_return = [], -float("inf")
         self.total_steps = 0
         self.iteration = 0
 
@@ -289,12 +300,20 @@ class N2nTrainer:
         return steps * self.world, log
 
     def evaluate(self):
-        """synchronous greedy episode (argmax) on num_eval_envs environments of their own seeds"""
+        """synchronous greedy episode (argmax) on num_eval_envs environments of their own seeds; the std of the return over them goes to
+        self.eval_return_std (a recorder column, not a log key)"""
+        ev = self.make_eval_env()
+        acc = self.agent.run_episode(ev, None, greedy=True)
+        ret = acc["ret"]
+        sd = ret.std() if ret.numel() > 1 else ret.new_zeros(())
+        r, c, l, self.eval_return_std = torch.stack((ret.mean(), acc["captured"].float().mean(), acc["length"].mean(), sd)).tolist()
+        return dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+
+    def make_eval_env(self):
+        """the evaluation environments (created once): num_eval_envs of their own seeds, seed + 10^6 + n"""
         if self.eval_env is None:
             self.eval_env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6)
-        acc = self.agent.run_episode(self.eval_env, None, greedy=True)
-        r, c, l = torch.stack((acc["ret"].mean(), acc["captured"].float().mean(), acc["length"].mean())).tolist()
-        return dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+        return self.eval_env
 
     def last_breakdown_ms(self):
         torch.cuda.synchronize()
@@ -302,10 +321,14 @@ class N2nTrainer:
         return ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
 
 
-def train_n2n(cfg, max_iterations=None, num_eval_envs=64, eval_every=1):
+def train_n2n(cfg, max_iterations=None, num_eval_envs=64, eval_every=1, save_resume=None, resume=None):
     """the env_n2n training loop (main --config cfg4_n2n): until max_train_steps env-steps or max_iterations; rank 0 prints one JSON log
-    line per iteration and saves the final weights under algo.save_cwd"""
+    line per iteration, records every evaluation (recorder.npy, learning curve, the _best weights: ParticleRunState.record_evaluation)
+    and saves the final weights under algo.save_cwd.  resume / save_resume: directories of the per-rank resume bundles read before the
+    first iteration / written after every one."""
     tr = N2nTrainer(cfg, num_eval_envs=num_eval_envs, eval_every=eval_every)
+    if resume is not None:
+        tr.load_resume(resume_path(resume, tr.rank))
     while tr.total_steps < cfg.algo.max_train_steps:
         t0 = time.time()
         steps, log = tr.iterate()
@@ -313,6 +336,10 @@ def train_n2n(cfg, max_iterations=None, num_eval_envs=64, eval_every=1):
             rollout_ms, update_ms = tr.last_breakdown_ms()
             log.update(rollout_ms=round(rollout_ms, 2), update_ms=round(update_ms, 2), seconds=round(time.time() - t0, 3))
             print(json.dumps(log), flush=True)
+            if "eval_return" in log:
+                tr.record_evaluation(log, cfg.algo.save_cwd)
+        if save_resume is not None:
+            save_resume_atomic(tr, save_resume)
         if max_iterations is not None and tr.iteration >= max_iterations:
             break
     if tr.rank == 0:

@@ -76,6 +76,10 @@ def load_library():
         L.n2n_evader_slsqp_nit.argtypes = [vp] * 5
         L.n2n_evader_slsqp_host.argtypes = [vp, C.c_int32] + [vp] * 5
         L.n2n_resetter_reset.argtypes = [vp, vp, vp, vp, C.c_int32]
+        L.n2n_resetter_state_bytes.argtypes = [vp]
+        L.n2n_resetter_state_bytes.restype = C.c_int64
+        L.n2n_resetter_get_state.argtypes = [vp, vp]
+        L.n2n_resetter_set_state.argtypes = [vp, vp]
         L.n2n_policy_inputs.argtypes = [vp] * 5
         L.n2n_policy_record.argtypes = [vp] * 7
         _lib = L
@@ -171,6 +175,21 @@ class ParticleEnv:
         self.n_episode += 1
         self._cmd = torch.zeros((N, self.e_num), dtype=torch.float64, device=self.device)
         self.observe()
+
+    def get_resetter_state(self):
+        """the reset generators of every environment (include/n2n_env.h n2n_resetter_get_state) as a uint8 array"""
+        buf = np.empty(self.L.n2n_resetter_state_bytes(self.resetter), np.uint8)
+        _check(self.L.n2n_resetter_get_state(self.resetter, buf.ctypes.data_as(C.c_void_p)), "n2n_resetter_get_state")
+        return buf
+
+    def set_resetter_state(self, blob):
+        """restores get_resetter_state(); ValueError when the blob comes from another number of environments / agents"""
+        buf = np.ascontiguousarray(blob, np.uint8)
+        if buf.size != self.L.n2n_resetter_state_bytes(self.resetter):
+            raise ValueError("resetter state does not match this number of environments")
+        rc = self.L.n2n_resetter_set_state(self.resetter, buf.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise ValueError(f"resetter state does not match this configuration (n2n_resetter_set_state code {rc})")
 
     def observe(self):
         _check(self.L.n2n_env_observe(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), _stream()), "n2n_env_observe")

@@ -129,6 +129,79 @@ def save_checkpoint(actor, critic, cwd, suffix=""):
     torch.save({"actor": actor.state_dict(), "critic": critic.state_dict()}, f"{cwd}/state_dicts{suffix}.pt")
 
 
+def resume_path(directory, rank):
+    """the resume bundle of one rank under `main --save-resume DIR` / `--resume DIR`"""
+    return os.path.join(directory, f"resume_rank{rank}.pt")
+
+
+def save_resume_atomic(trainer, directory):
+    """trainer.save_resume into DIR/resume_rank{r}.pt through a temporary file and os.replace: a job killed while writing leaves
+    the previous bundle, never a torn one"""
+    os.makedirs(directory, exist_ok=True)
+    path = resume_path(directory, trainer.rank)
+    tmp = f"{path}.tmp{os.getpid()}"
+    trainer.save_resume(tmp)
+    os.replace(tmp, path)
+
+
+class ParticleRunState:
+    """Run protocol of the env_3d / env_n2n trainers (E3dTrainer, N2nTrainer): resume bundle, evaluation record and best
+    checkpoint.  The trainer provides env, eval_env and make_eval_env(), agent (rollout state `agent._state(env)` with the sampling
+    counter; save_model / load_model), total_steps, iteration, num_envs, world, rank, device, eval_return_std, recorder and
+    best_eval_return.  Every environment episode starts from a reset and every rollout from zero GRU states and history, so the
+    reset generators, the sampling counters, the weights and Adam are all the state a run carries from one iteration to the next."""
+
+    def save_resume(self, path):
+        agent, ev = self.agent, self.eval_env
+        bundle = dict(actor=agent.actor.state_dict(), critic=agent.critic.state_dict(), optimizer=agent.ac_optimizer.state_dict(),
+                      total_steps=self.total_steps, iteration=self.iteration, lr=agent.ac_optimizer.param_groups[0]["lr"],
+                      resetter=self.env.get_resetter_state(), n_episode=self.env.n_episode, sample_counter=agent._state(self.env).counter.cpu(),
+                      eval_resetter=None if ev is None else ev.get_resetter_state(), eval_n_episode=None if ev is None else ev.n_episode,
+                      eval_sample_counter=None if ev is None else agent._state(ev).counter.cpu(),
+                      recorder=list(self.recorder), best_eval_return=self.best_eval_return,
+                      num_envs=self.num_envs, world=self.world, rank=self.rank)
+        torch.save(bundle, path)
+
+    def load_resume(self, path):
+        """restores save_resume(path) into this trainer, fresh or not (the rollout states are created here when missing)"""
+        b = torch.load(path, map_location=self.device, weights_only=False)  # our own file (numpy blobs inside)
+        if b["num_envs"] != self.num_envs or b["world"] != self.world or b["rank"] != self.rank:
+            raise ValueError("resume bundle was written for another num_envs / world size / rank")
+        agent = self.agent
+        agent.actor.load_state_dict(b["actor"])
+        agent.critic.load_state_dict(b["critic"])
+        agent.ac_optimizer.load_state_dict(b["optimizer"])
+        self.total_steps, self.iteration = b["total_steps"], b["iteration"]
+        if agent.use_lr_decay:
+            agent.lr_decay(self.total_steps)
+        else:
+            for g in agent.ac_optimizer.param_groups:
+                g["lr"] = b["lr"]
+        self.env.set_resetter_state(b["resetter"])
+        self.env.n_episode = b["n_episode"]
+        agent._state(self.env).counter.copy_(b["sample_counter"])
+        if b["eval_resetter"] is not None:
+            ev = self.make_eval_env()
+            ev.set_resetter_state(b["eval_resetter"])
+            ev.n_episode = b["eval_n_episode"]
+            agent._state(ev).counter.copy_(b["eval_sample_counter"])
+        self.recorder, self.best_eval_return = list(b["recorder"]), b["best_eval_return"]
+
+    def record_evaluation(self, log, cwd):
+        """after an iteration that evaluated (rank 0): one recorder row (total_steps, eval_return, eval_return_std, mean_return,
+        critic_loss, actor_loss), saved as cwd/recorder.npy with its learning curve, and the weights under the _best suffix when the
+        greedy return did not get worse (main.py:139-156, evaluator.EvaluatorProc.evaluate_and_save)"""
+        self.recorder.append((log["total_steps"], log["eval_return"], self.eval_return_std, log["mean_return"], log["critic_loss"],
+                              log["actor_loss"]))
+        os.makedirs(cwd, exist_ok=True)
+        rec = np.array(self.recorder, dtype=np.float64)
+        np.save(os.path.join(cwd, "recorder.npy"), rec)
+        draw_learning_curve(recorder=rec, cwd=cwd)
+        if log["eval_return"] >= self.best_eval_return:
+            self.best_eval_return = log["eval_return"]
+            self.agent.save_model(cwd, best=True)
+
+
 class _Done:
     """stand-in for an already finished prefetch thread"""
 
@@ -229,7 +302,7 @@ def _device_weights(module):
     return {k: v.detach().clone() for k, v in module.state_dict().items()}
 
 
-def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval_every=1, async_eval=None):
+def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval_every=1, async_eval=None, save_resume=None, resume=None):
     """main.py:41-172 on the Trainer: runs until the evaluator says stop (total_step > max_train_steps).
 
     Evaluation is asynchronous like the reference's (main.py:135-158: `evaluator.run.remote(...)`, polled with `ray.wait(...,
@@ -237,9 +310,13 @@ def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval
     rank 0's GPU -- that works on a device-side snapshot of the weights; the training loop only collects a finished evaluation and
     starts the next one with the current weights, it never waits for one.  No rank sits in a collective for the length of an
     evaluation: the per-iteration flag broadcast carries whatever verdict rank 0 holds at that moment.
-    `runtime.async_eval: false` (or async_eval=False) evaluates inline on rank 0 (deterministic recorder rows per iteration)."""
+    `runtime.async_eval: false` (or async_eval=False) evaluates inline on rank 0 (deterministic recorder rows per iteration).
+    save_resume: a directory each rank writes its resume bundle to after every iteration; resume: the directory each rank loads its
+    bundle from before the first one (main --save-resume / --resume)."""
     from . import ray_shim
     tr = Trainer(cfg)
+    if resume is not None:
+        tr.load_resume(resume_path(resume, tr.rank))
     if async_eval is None:
         async_eval = bool(cfg.runtime.get("async_eval", True))
     evaluator = None
@@ -281,6 +358,8 @@ def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval
             flag = torch.tensor([1 if if_train else 0], device=tr.device if dist.get_backend() != "gloo" else "cpu")
             dist.broadcast(flag, src=0)
             if_train = bool(flag.item())
+        if save_resume is not None:
+            save_resume_atomic(tr, save_resume)
         if max_iterations is not None and tr.iteration >= max_iterations:
             break
     if tr.rank == 0:

@@ -21,6 +21,8 @@ extern "C" {
 #define E3D_ERR_BAD_CONFIG 40001
 #define E3D_ERR_NULL 40002
 #define E3D_ERR_RESET_FAILED 40003   /* gen_init_p_pos (:151-164) found no placement within E3D_RESET_MAX_DRAWS draws */
+#define E3D_ERR_BAD_STATE 40004      /* e3d_resetter_set_state: the blob's header does not match this resetter */
+#define E3D_RESETTER_STATE_TAG 0x31523345u   /* "E3R1": format of e3d_resetter_get_state */
 #define E3D_RESET_MAX_DRAWS 100000
 
 typedef struct e3d_config {      /* particle_env.py:78-121 */
@@ -80,6 +82,13 @@ int e3d_evader_slsqp_host(const e3d_config *cfg, int32_t N, const double *p, con
 void *e3d_resetter_create(const e3d_config *cfg, int32_t N, const uint32_t *seeds);
 void e3d_resetter_destroy(void *resetter);
 int e3d_resetter_reset(void *resetter, double *p, double *e, double *target, int32_t n_threads);
+/* Resume support: the generator of every environment as one blob of e3d_resetter_state_bytes bytes -- a 16-byte header
+ * (u32 tag E3D_RESETTER_STATE_TAG, i32 N, P, E = 1), then per environment the MT19937 key (624 x u32), its position (i32),
+ * has_gauss (i32) and the cached gauss (f64).  set_state restores a blob of get_state; a blob whose header does not match this
+ * resetter (or with a malformed record) is rejected with E3D_ERR_BAD_STATE and leaves the resetter as it was. */
+int64_t e3d_resetter_state_bytes(void *resetter);
+int e3d_resetter_get_state(void *resetter, void *out);
+int e3d_resetter_set_state(void *resetter, const void *in);
 
 #ifdef __cplusplus
 }

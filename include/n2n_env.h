@@ -19,6 +19,8 @@ extern "C" {
 #define N2N_MAX_E 8
 #define N2N_ERR_BAD_CONFIG 30001
 #define N2N_ERR_NULL 30002
+#define N2N_ERR_BAD_STATE 30003      /* n2n_resetter_set_state: the blob's header does not match this resetter */
+#define N2N_RESETTER_STATE_TAG 0x3152324eu   /* "N2R1": format of n2n_resetter_get_state */
 
 typedef struct n2n_config {      /* particle_env.py:108-121,147 */
     int32_t P, E, episode_limit, pad0;
@@ -108,6 +110,13 @@ int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *r
 void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seeds);
 void n2n_resetter_destroy(void *resetter);
 int n2n_resetter_reset(void *resetter, double *p, double *e, double *target, int32_t n_threads);
+/* Resume support: the generator of every environment as one blob of n2n_resetter_state_bytes bytes -- a 16-byte header
+ * (u32 tag N2N_RESETTER_STATE_TAG, i32 N, P, E), then per environment the MT19937 key (624 x u32), its position (i32),
+ * has_gauss (i32) and the cached gauss (f64).  set_state restores a blob of get_state; a blob whose header does not match this
+ * resetter (or with a malformed record) is rejected with N2N_ERR_BAD_STATE and leaves the resetter as it was. */
+int64_t n2n_resetter_state_bytes(void *resetter);
+int n2n_resetter_get_state(void *resetter, void *out);
+int n2n_resetter_set_state(void *resetter, const void *in);
 
 #ifdef __cplusplus
 }
