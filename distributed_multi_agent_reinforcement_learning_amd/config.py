@@ -4,6 +4,7 @@ The reference resolves its config with hydra (main.py:40); neither hydra nor ome
 so the same yaml is read with PyYAML into an attribute dict.  An optional ``runtime`` section (ours) carries what
 the reference hard-codes in main.py:42-50 (number of environments, seed, ...).
 """
+import ast
 import copy
 import os
 
@@ -91,3 +92,16 @@ def baseline_config(name="cfg2", **overrides):
     ov.update(base)
     ov.update(overrides)
     return load_config(**ov)
+
+
+def parse_overrides(items):
+    """command-line KEY=VALUE items -> {dotted key: value}; a value Python can read as a literal (numbers, booleans, lists) becomes
+    one, anything else stays a string (main and tools/bench_e3d.py)"""
+    ov = {}
+    for item in items:
+        k, _, v = item.partition("=")
+        try:
+            ov[k] = ast.literal_eval(v)
+        except (ValueError, SyntaxError):
+            ov[k] = v
+    return ov

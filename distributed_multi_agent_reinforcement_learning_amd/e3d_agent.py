@@ -8,6 +8,10 @@ This module is the package's own: the PPO update, GAE and data-parallel protocol
   buffer and clamped to [-1, 1] for the environment (ops.gauss_head_sample, one launch per tick),
 * critic head: the spectrally normalised value head of `SharedCritic`,
 * loss: ops.ppo_loss_gauss (Normal.log_prob / entropy inside the PPO launch, gradients for mu, log_std and the values).
+Two options, both off by default: `algo.gauss_std: state` replaces the log_std vector by a head
+LogStd = Linear(128 -> A) on the GRU features, `algo.gauss_squash: tanh` sends tanh(u) to the environment instead of clamp(u, -1, 1)
+and subtracts log(1 - tanh(u)^2) from the log-probability; ls is clamped to [algo.log_std_min, algo.log_std_max].  With either on,
+the rollout takes ops.gauss_head_sample_ex and the update ops.ppo_loss_gauss_ex; with both off, the calls above.
 """
 import json
 import os
@@ -40,14 +44,27 @@ class E3dEncoder(nn.Module):
         return ops.linear(h, self.fc2.weight, self.fc2.bias, relu=True)
 
 
+GAUSS_STD, GAUSS_SQUASH = ("param", "state"), ("clip", "tanh")
+GAUSS_SD_MAX_A = 8   # state mode: a lane of the rollout head holds 2 A x 8 weights (csrc/gauss_policy.hpp k_gauss_head_ex)
+
+
 class GaussianActor(_Trunk):
-    def __init__(self, in_dim, embedding_dim, action_dim, num_layers, rnn_hidden_dim, log_std_init=0.0, is_sn=False):
+    """gauss_std "param": log_std is a parameter vector; "state": LogStd = Linear(128 -> A) on the GRU features, created after Mean
+    (it draws from the generator like any layer) and then set to weight 0, bias log_std_init, so that sigma starts as param mode's"""
+
+    def __init__(self, in_dim, embedding_dim, action_dim, num_layers, rnn_hidden_dim, log_std_init=0.0, is_sn=False, gauss_std="param"):
         super().__init__()
         self.shared_net = E3dEncoder(in_dim, embedding_dim)
         self.num_layers, self.rnn_input_dim, self.rnn_hidden_dim = num_layers, embedding_dim, rnn_hidden_dim
         self.GRU = nn.GRU(embedding_dim, rnn_hidden_dim, num_layers)
         self.Mean = _make_linear(rnn_hidden_dim, action_dim, is_sn, HeadLinear)
-        self.log_std = nn.Parameter(torch.full((action_dim,), float(log_std_init)))
+        if gauss_std == "state":
+            self.LogStd = HeadLinear(rnn_hidden_dim, action_dim)
+            with torch.no_grad():
+                self.LogStd.weight.zero_()
+                self.LogStd.bias.fill_(float(log_std_init))
+        else:
+            self.log_std = nn.Parameter(torch.full((action_dim,), float(log_std_init)))
 
 
 class E3dCritic(_Trunk):
@@ -76,6 +93,22 @@ class _E3dRollout:
         self.t = 0
 
 
+def gauss_policy_options(cfg):
+    """-> (gauss_std, gauss_squash, log_std_min, log_std_max) of cfg.algo, validated (ValueError naming the key)"""
+    a = cfg.algo
+    std, squash = str(a.get("gauss_std", "param")), str(a.get("gauss_squash", "clip"))
+    if std not in GAUSS_STD:
+        raise ValueError(f"algo.gauss_std: {std!r} is not one of {GAUSS_STD}")
+    if squash not in GAUSS_SQUASH:
+        raise ValueError(f"algo.gauss_squash: {squash!r} is not one of {GAUSS_SQUASH}")
+    lo, hi = float(a.get("log_std_min", -5.0)), float(a.get("log_std_max", 2.0))
+    if not lo < hi:
+        raise ValueError(f"algo.log_std_min ({lo}) must be below algo.log_std_max ({hi})")
+    if std == "state" and int(cfg.env.action_dim) > GAUSS_SD_MAX_A:
+        raise ValueError(f"algo.gauss_std: state supports env.action_dim <= {GAUSS_SD_MAX_A} (got {int(cfg.env.action_dim)})")
+    return std, squash, lo, hi
+
+
 class E3dMAPPO:
     """rollout (run_episode / explore_env) and PPO update (train) of the Gaussian policy on env_3d"""
 
@@ -83,6 +116,8 @@ class E3dMAPPO:
         a = cfg.algo
         if bool(a.get("use_reward_norm", False)):
             raise ValueError("algo.use_reward_norm: true is not supported on env_3d (runtime.env: e3d); set it to false")
+        self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
+        self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
         self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
         self.epsilon, self.entropy_coef = a.epsilon, a.entropy_coef
@@ -95,7 +130,7 @@ class E3dMAPPO:
             raise RuntimeError("E3dMAPPO runs on the GPU only (HIP kernels, no CPU fallback)")
         sn = bool(a.use_spectral_norm)
         self.actor = GaussianActor(FEAT, self.embedding_dim, self.action_dim, self.num_layers, self.rnn_hidden_dim,
-                                   float(a.get("log_std_init", 0.0)), sn).to(self.device)
+                                   float(a.get("log_std_init", 0.0)), sn, self.gauss_std).to(self.device)
         self.critic = E3dCritic(FEAT, self.embedding_dim, self.num_layers, self.rnn_hidden_dim, sn).to(self.device)
         self.ac_parameters = list(self.actor.parameters()) + list(self.critic.parameters())
         self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
@@ -124,8 +159,14 @@ class E3dMAPPO:
                                     hiddens_out=[st.hbuf_a[nxt], st.hbuf_c[nxt]])
         self.critic.head(fc.contiguous(), out=st.v)
         m = self.actor.Mean
-        ops.gauss_head_sample(fa.contiguous(), m.weight, m.bias, self.actor.log_std, self.sample_seed, st.counter, st.ticket,
-                              (st.action, st.env_action, st.logp), greedy=greedy)
+        if self.policy_ex:
+            ls = (self.actor.LogStd.weight, self.actor.LogStd.bias) if self.gauss_std == "state" else self.actor.log_std
+            ops.gauss_head_sample_ex(fa.contiguous(), m.weight, m.bias, ls, self.sample_seed, st.counter, st.ticket,
+                                     (st.action, st.env_action, st.logp), greedy=greedy, log_std_min=self.log_std_min,
+                                     log_std_max=self.log_std_max, squash=self.gauss_squash)
+        else:
+            ops.gauss_head_sample(fa.contiguous(), m.weight, m.bias, self.actor.log_std, self.sample_seed, st.counter, st.ticket,
+                                  (st.action, st.env_action, st.logp), greedy=greedy)
         st.t += 1
 
     def _bootstrap_value(self, st):
@@ -197,8 +238,9 @@ class E3dMAPPO:
         return mean_r, self.buffer, N * T, dict(capture_rate=cap, episode_length=mlen)
 
     # ---- update ------------------------------------------------------------------------------------------------------------------
-    def sequence_forward(self, feat_a, feat_c, batch, steps):
-        """(batch, T, P, 16) features of whole episodes -> mu (batch, T, P, A) and values (batch, T, P), time-major views"""
+    def sequence_forward(self, feat_a, feat_c, batch, steps, return_ls_raw=False):
+        """(batch, T, P, 16) features of whole episodes -> mu (batch, T, P, A) and values (batch, T, P), time-major views; with
+        return_ls_raw also ls_raw (state mode: the LogStd head on the same GRU features, (batch, T, P, A); param mode: log_std)"""
         P = feat_a.shape[2]
         R = batch * steps * P
         emb_a, emb_c = self.actor.shared_net(feat_a.reshape(R, FEAT)), self.critic.shared_net(feat_c.reshape(R, FEAT))
@@ -207,7 +249,10 @@ class E3dMAPPO:
         fa, fc = fa.reshape(steps, batch, P, -1), fc.reshape(steps, batch, P, -1)
         mu = self.actor.Mean(fa).permute(1, 0, 2, 3)
         values = self.critic.Mean(fc).permute(1, 0, 2, 3)[..., 0]
-        return mu, values
+        if not return_ls_raw:
+            return mu, values
+        ls_raw = self.actor.LogStd(fa).permute(1, 0, 2, 3) if self.gauss_std == "state" else self.actor.log_std
+        return mu, values, ls_raw
 
     def train(self, buf, total_steps):
         """GAE + advantage normalisation over all rows (ops.gae_advnorm), then sequential mini-batches of whole episodes, the
@@ -223,10 +268,15 @@ class E3dMAPPO:
         k = 0
         for n0 in range(0, N, self.mini_batch_size):
             n1 = min(n0 + self.mini_batch_size, N)
-            mu, values = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, T)
-            la, lc = ops.ppo_loss_gauss(mu, self.actor.log_std, buf["a_n"][n0:n1], values, buf["a_logprob_n"][n0:n1], adv[n0:n1],
-                                        buf["active"][n0:n1], buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1],
-                                        self.epsilon, self.entropy_coef, self.use_value_clip)
+            mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, T, return_ls_raw=True)
+            args = (buf["a_n"][n0:n1], values, buf["a_logprob_n"][n0:n1], adv[n0:n1], buf["active"][n0:n1],
+                    buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1], self.epsilon, self.entropy_coef,
+                    self.use_value_clip)
+            if self.policy_ex:
+                la, lc = ops.ppo_loss_gauss_ex(mu, ls_raw, *args, log_std_min=self.log_std_min, log_std_max=self.log_std_max,
+                                               squash=self.gauss_squash)
+            else:
+                la, lc = ops.ppo_loss_gauss(mu, ls_raw, *args)
             (la + lc).backward()
             if self.use_grad_clip:
                 torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
@@ -243,15 +293,41 @@ class E3dMAPPO:
             p["lr"] = lr_now
         self.total_step = total_steps
 
+    def policy_meta(self):
+        """the "policy" entry of checkpoints and resume bundles: None in the default mode (param, clip), whose files carry none"""
+        if not self.policy_ex:
+            return None
+        return dict(gauss_std=self.gauss_std, gauss_squash=self.gauss_squash, log_std_min=self.log_std_min, log_std_max=self.log_std_max)
+
+    def check_policy_meta(self, meta, what):
+        """ValueError naming the config key when a file's policy (its "policy" entry; None = the default mode) is not this agent's:
+        gauss_std and gauss_squash, and with an option on (where the bounds act) log_std_min / log_std_max as well -- other bounds would
+        neither reproduce the saved policy nor continue its run bit for bit"""
+        meta = meta or {}
+        for key, default in (("gauss_std", "param"), ("gauss_squash", "clip")):
+            theirs, mine = meta.get(key, default), getattr(self, key)
+            if theirs != mine:
+                raise ValueError(f"{what} was written with algo.{key}: {theirs}, this agent has algo.{key}: {mine}")
+        if self.policy_ex:   # (the default mode has no bounds; its files carry no entry)
+            for key in ("log_std_min", "log_std_max"):
+                theirs, mine = float(meta[key]), getattr(self, key)
+                if theirs != mine:
+                    raise ValueError(f"{what} was written with algo.{key}: {theirs}, this agent has algo.{key}: {mine}")
+
     def save_model(self, cwd, best=False):
-        """cwd/e3d_state_dicts.pt (best: e3d_state_dicts_best.pt), the actor's and critic's state_dicts"""
+        """cwd/e3d_state_dicts.pt (best: e3d_state_dicts_best.pt), the actor's and critic's state_dicts (and, with a non-default
+        algo.gauss_std / gauss_squash, the "policy" entry of policy_meta)"""
         os.makedirs(cwd, exist_ok=True)
-        torch.save({"actor": self.actor.state_dict(), "critic": self.critic.state_dict()},
-                   os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt"))
+        sd = {"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}
+        if self.policy_ex:
+            sd["policy"] = self.policy_meta()
+        torch.save(sd, os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt"))
 
     def load_model(self, cwd, best=False):
-        """the weights save_model(cwd, best) wrote"""
-        sd = torch.load(os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt"), map_location=self.device)
+        """the weights save_model(cwd, best) wrote; ValueError when they belong to another gauss_std / gauss_squash"""
+        path = os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt")
+        sd = torch.load(path, map_location=self.device)
+        self.check_policy_meta(sd.get("policy"), path)
         self.actor.load_state_dict(sd["actor"])
         self.critic.load_state_dict(sd["critic"])
 

@@ -20,10 +20,9 @@ iteration, `--resume DIR` continues from them.  `--evaluate CWD` (env_3d and env
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --evaluate ./model
 """
 import argparse
-import ast
 import json
 
-from .config import baseline_config, load_config
+from .config import baseline_config, load_config, parse_overrides
 from .e3d_agent import E3dTrainer, train_e3d
 from .n2n_agent import N2nTrainer, train_n2n
 from .trainer import train_agent_multiprocessing
@@ -43,13 +42,7 @@ def main(argv=None):
                     help="env_3d / env_n2n: evaluate the weights saved under CWD on --eval-envs environments and exit")
     ap.add_argument("overrides", nargs="*", help="dotted overrides KEY=VALUE")
     args = ap.parse_args(argv)
-    ov = {}
-    for item in args.overrides:
-        k, _, v = item.partition("=")
-        try:
-            ov[k] = ast.literal_eval(v)
-        except (ValueError, SyntaxError):
-            ov[k] = v
+    ov = parse_overrides(args.overrides)
     cfg = baseline_config(args.config, **ov) if args.config in BASELINES else load_config(args.config, **ov)
     env = str(cfg.runtime.get("env", "pursuit"))
     if args.evaluate is not None:

@@ -16,7 +16,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "dhgn_msg_agg_ones_sorted_bwd", "dhgn_msg_agg_ones_sorted_workspace", "gae_advnorm", "gae_advnorm_workspace", "categorical_sample",
            "categorical_sample_counter",
            "gru_gates_fwd", "gru_gates_bwd", "gru_cell_fwd", "gru_cell_fwd_multi", "gru_cell_split_fwd_multi", "sb_gemm_n128", "sb_gemm", "gru_seq_fwd", "gru_seq_fwd_multi", "gru_seq_split_fwd_multi", "gru_seq_split_bwd_multi", "gru_seq_save_elems", "gru_seq_bwd", "gru_seq_bwd_multi", "gru_seq_bwd_workspace", "wgrad_tn", "wgrad_tn_workspace", "wgrad_split_tn", "wgrad_split_tn2", "wgrad_split_workspace", "rollout_record", "ppo_loss_fwd_bwd", "ppo_loss_prob_fwd_bwd", "ppo_loss_workspace",
-           "gauss_head_sample", "ppo_loss_gauss_fwd_bwd", "ppo_loss_gauss_workspace", "mappo_ops_error_string")
+           "gauss_head_sample", "ppo_loss_gauss_fwd_bwd", "ppo_loss_gauss_workspace", "gauss_head_sample_ex", "ppo_loss_gauss_ex_fwd_bwd",
+           "ppo_loss_gauss_ex_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -100,6 +101,10 @@ def load_library():
         L.ppo_loss_gauss_workspace.restype = i64
         L.ppo_loss_gauss_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, f32, f32,
                                              i32, vp, vp, vp, vp, vp]
+        L.gauss_head_sample_ex.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, i32, C.c_uint64, vp, vp, i32, vp, vp, vp, vp]
+        L.ppo_loss_gauss_ex_workspace.restype = i64
+        L.ppo_loss_gauss_ex_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, f32, f32, i32, vp, vp, vp, vp,
+                                                vp, i64, i64, i64, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp]
         L.sb_split_diag.argtypes = [i64, vp, vp, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
@@ -600,6 +605,39 @@ def gauss_head_sample(feat, W, b, log_std, seed, counter, ticket, out, greedy=Fa
     _check(L.gauss_head_sample(R, A, HEAD_FEATURES, _ptr(feat), _ptr(W.detach().contiguous()), _ptr(b.detach().contiguous()),
                                _ptr(log_std.detach().contiguous()), int(seed), _ptr(counter), _ptr(ticket), 1 if greedy else 0, _ptr(action),
                                _ptr(env_action), _ptr(logp), _stream()), "gauss_head_sample")
+    return action, env_action, logp
+
+
+GAUSS_SQUASH = {"clip": 0, "tanh": 1}
+
+
+def gauss_head_sample_ex(feat, W, b, log_std, seed, counter, ticket, out, greedy=False, log_std_min=-float("inf"), log_std_max=float("inf"),
+                         squash="clip"):
+    """gauss_head_sample with a state-dependent log-std and / or tanh squashing in one launch (csrc/gauss_policy.hpp k_gauss_head_ex).
+    log_std: the (A,) vector (param mode) or a pair (W_ls (A, 128), b_ls (A,)) whose head on feat gives ls_raw per row (state mode,
+    A <= 8); ls = clamp(ls_raw, log_std_min, log_std_max), u = mu + exp(ls) z with gauss_head_sample's noise and counter.
+    out = (action fp32 (.., A) = u, env_action f64 (.., A) = clamp(u, -1, 1) (squash "clip") or tanh(u) (squash "tanh"),
+    logp fp32 (..) = Normal(mu, exp(ls)).log_prob(u).sum(-1), minus sum log(1 - tanh(u)^2) when squash is "tanh")."""
+    state = isinstance(log_std, (tuple, list))
+    A = W.shape[0]
+    assert _head_ok(feat, W, b) and squash in GAUSS_SQUASH
+    if state:
+        W_ls, b_ls = (t.detach().contiguous() for t in log_std)
+        assert W_ls.shape == W.shape and b_ls.shape == (A,) and W_ls.dtype == b_ls.dtype == torch.float32 and A <= 8
+        ls = None
+    else:
+        assert log_std.shape == (A,)
+        W_ls = b_ls = None
+        ls = log_std.detach().contiguous()
+    L = load_library()
+    action, env_action, logp = out
+    R = feat.numel() // HEAD_FEATURES
+    assert action.dtype == torch.float32 and env_action.dtype == torch.float64 and logp.dtype == torch.float32
+    assert all(t.is_contiguous() for t in out) and action.numel() == R * A and env_action.numel() == R * A and logp.numel() == R
+    assert counter.dtype == torch.int64 and counter.numel() == 1 and ticket.dtype == torch.int32 and ticket.numel() == 1
+    _check(L.gauss_head_sample_ex(R, A, HEAD_FEATURES, _ptr(feat), _ptr(W.detach().contiguous()), _ptr(b.detach().contiguous()), _ptr(W_ls),
+                                  _ptr(b_ls), _ptr(ls), float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], int(seed), _ptr(counter),
+                                  _ptr(ticket), 1 if greedy else 0, _ptr(action), _ptr(env_action), _ptr(logp), _stream()), "gauss_head_sample_ex")
     return action, env_action, logp
 
 
@@ -1278,6 +1316,66 @@ def ppo_loss_gauss(mu, log_std, action, values_now, logp_old, adv, active, value
     w.r.t. mu, log_std and values_now (csrc/gauss_policy.hpp k_ppo_loss_gauss).  mu (mb, T, P, A) and values_now (mb, T, P): any strides
     over the first three dimensions (time-major views), mu's last dimension dense; action (mb, T, P, A), the rest (mb, T, P)."""
     return _PPOLossGauss.apply(mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip)
+
+
+class _PPOLossGaussEx(torch.autograd.Function):
+    """ppo_loss_gauss_ex: ppo_loss_gauss_ex_fwd_bwd writes the losses and the gradients w.r.t. mu, ls_raw (per row or the vector)
+    and the values in one pass."""
+
+    @staticmethod
+    def forward(ctx, mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
+                log_std_min, log_std_max, squash):
+        L = load_library()
+        _need_gpu(mu, "ppo_loss_gauss_ex")
+        A = mu.shape[-1]
+        d0, d1, d2 = mu.shape[:3]
+        n = d0 * d1 * d2
+        ts = [t.contiguous() for t in (logp_old, adv, active, v_target)]
+        act = action.contiguous()
+        vo = values_old.contiguous() if values_old is not None else None
+        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == mu.shape[:3]
+        assert act.shape == mu.shape and act.dtype == torch.float32 and mu.stride(3) == 1 and squash in GAUSS_SQUASH
+        dev = mu.device
+        ls = ls_raw.detach()
+        if ls.dim() == 1:            # param mode: one vector, stride 0 over the rows
+            assert ls.shape == (A,)
+            ls = ls.contiguous()
+            g_ls = torch.empty(A, dtype=torch.float32, device=dev)
+            lstr = (0, 0, 0)
+        else:                        # state mode: per row, any strides over the first three dimensions (a time-major view)
+            assert ls.shape == mu.shape and ls.stride(3) == 1 and ls.dtype == torch.float32
+            g_ls = torch.empty_strided(ls.shape, ls.stride(), dtype=torch.float32, device=dev)
+            lstr = ls.stride()[:3]
+            assert any(lstr), "a per-row ls_raw needs a nonzero row stride"
+        asum = active.sum().reshape(1)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)
+        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.ppo_loss_gauss_ex_workspace(), dtype=torch.uint8, device=dev)
+        ms, vs = mu.stride(), values_now.stride()
+        _check(L.ppo_loss_gauss_ex_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
+                                           float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], _ptr(act), _ptr(ts[0]), _ptr(ts[1]),
+                                           _ptr(ts[2]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon),
+                                           float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream()),
+               "ppo_loss_gauss_ex_fwd_bwd")
+        ctx.save_for_backward(g_mu, g_ls, g_v)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, ga, gc):
+        g_mu, g_ls, g_v = ctx.saved_tensors
+        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 12
+
+
+def ppo_loss_gauss_ex(mu, ls_raw, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True,
+                      log_std_min=-float("inf"), log_std_max=float("inf"), squash="clip"):
+    """ppo_loss_gauss with ls = clamp(ls_raw, log_std_min, log_std_max) and optional tanh squashing (csrc/gauss_policy.hpp
+    k_ppo_loss_gauss_ex).  ls_raw: the (A,) vector (param mode) or a tensor of mu's shape (state mode, any strides over the first three
+    dimensions, the last dense).  action holds the unsquashed samples u; with squash "tanh" the log-probability subtracts
+    sum log(1 - tanh(u)^2), which carries no gradient.  Gradients flow to mu, ls_raw (0 where ls_raw is outside the bounds) and
+    values_now."""
+    return _PPOLossGaussEx.apply(mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef,
+                                 use_value_clip, log_std_min, log_std_max, squash)
 
 
 def ppo_loss(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True):

@@ -160,6 +160,9 @@ class ParticleRunState:
                       eval_sample_counter=None if ev is None else agent._state(ev).counter.cpu(),
                       recorder=list(self.recorder), best_eval_return=self.best_eval_return,
                       num_envs=self.num_envs, world=self.world, rank=self.rank)
+        meta = agent.policy_meta() if hasattr(agent, "policy_meta") else None
+        if meta is not None:   # env_3d with a non-default algo.gauss_std / gauss_squash (E3dMAPPO.policy_meta); default bundles carry none
+            bundle["policy"] = meta
         torch.save(bundle, path)
 
     def load_resume(self, path):
@@ -168,6 +171,8 @@ class ParticleRunState:
         if b["num_envs"] != self.num_envs or b["world"] != self.world or b["rank"] != self.rank:
             raise ValueError("resume bundle was written for another num_envs / world size / rank")
         agent = self.agent
+        if hasattr(agent, "check_policy_meta"):
+            agent.check_policy_meta(b.get("policy"), "resume bundle " + str(path))
         agent.actor.load_state_dict(b["actor"])
         agent.critic.load_state_dict(b["critic"])
         agent.ac_optimizer.load_state_dict(b["optimizer"])

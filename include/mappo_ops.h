@@ -319,6 +319,30 @@ int ppo_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu
                            float *grad_log_std, void *workspace, void *stream);
 
 /*
+ * The same policy with a state-dependent log-std and / or tanh squashing.
+ * gauss_head_sample_ex: ls_raw = feat W_ls^T + b_ls (state mode: W_ls [A][H] and b_ls [A] non-NULL, log_std NULL, A <= 8) or the
+ *   log_std [A] vector (param mode: W_ls = b_ls = NULL, A <= 16); ls = clamp(ls_raw, log_std_min, log_std_max) (min < max, +-inf allowed);
+ *   u = mu + exp(ls) z with the noise, counter and ticket of gauss_head_sample.  action [R][A] = u (both squash modes), env_action f64 =
+ *   clamp(u, -1, 1) (squash 0) or tanh(u) (squash 1), logp = sum_d (-z_d^2 / 2 - ls_d - ln sqrt(2 pi)) - squash * sum_d c(u_d) with
+ *   c(u) = log(1 - tanh(u)^2) = 2 (ln 2 - u - softplus(-2 u)).  Param mode, squash 0 and bounds -inf / +inf give gauss_head_sample's bits.
+ * ppo_loss_gauss_ex_fwd_bwd: ppo_loss_gauss_fwd_bwd with logp_now = Normal(mu, exp(ls)).log_prob(action).sum(-1) - squash * sum c(action)
+ *   (c carries no gradient), entropy = sum_d (1/2 + ln sqrt(2 pi) + ls_d), ls = clamp(ls_raw, log_std_min, log_std_max).  ls_raw [.., A]
+ *   at i0 l_s0 + i1 l_s1 + i2 l_s2: per row (state mode; grad_log_std written per row at the same offsets) or, with l_s0 = l_s1 = l_s2 =
+ *   0, one [A] vector (param mode; grad_log_std [A] summed through the f64 per-block partials).  The ls_raw gradient is 0 where ls_raw
+ *   lies outside [log_std_min, log_std_max].  workspace >= ppo_loss_gauss_ex_workspace() bytes.
+ */
+int gauss_head_sample_ex(int32_t R, int32_t A, int32_t H, const float *feat, const float *W, const float *b, const float *W_ls, const float *b_ls,
+                         const float *log_std, float log_std_min, float log_std_max, int32_t squash, uint64_t seed, uint64_t *counter,
+                         uint32_t *ticket, int32_t greedy, float *action, double *env_action, float *logp, void *stream);
+int64_t ppo_loss_gauss_ex_workspace(void);
+int ppo_loss_gauss_ex_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
+                              const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min,
+                              float log_std_max, int32_t squash, const float *action, const float *logp_old, const float *adv, const float *active,
+                              const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                              const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses, float *grad_values,
+                              void *workspace, void *stream);
+
+/*
  * Records one rollout tick into the replay buffer (MAPPO.run_episode's minibuffer.store_transition,
  * DHGN/mappo_parallel.py:783-805, for N environments at once): for every item, row n of the dense [N][row_bytes] source
  * goes to dst + n * dst_row_stride (slot [n, t] of an (N, T, ...) buffer tensor); i32_to_f32 converts int32 actions to
