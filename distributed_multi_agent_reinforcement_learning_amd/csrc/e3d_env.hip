@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "e3d_env.h"
+#include "reward_scale.hpp"
 #include "rng_replica.hpp"
 #include "slsqp_box.hpp"
 
@@ -316,6 +317,77 @@ __global__ __launch_bounds__(256) void k_e3d_features(const e3d_config c, const 
     }
 }
 
+// MAPPO bookkeeping of one tick (include/e3d_env.h e3d_policy_record): the tick's lane layout, lane = (environment, pursuer).  Every lane
+// masks its own buffer entries; the group's flags (pursuers left, evader dead, evader at the target) come from the records after the
+// tick, the team reward from shuffles in agent order; slot 0 writes the accumulators after every lane of the group has read them (one
+// wave, program order).  SCALED: the reward row is the reference's RewardScaling of the raw reward (csrc/reward_scale.hpp); the state
+// rs [N][1 + 3P] is read and written once per lane, n by slot 0.
+template <int PT, bool SCALED>
+__global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_config c, const e3d_state st, const float *reward, const uint8_t *done,
+                                                                  const e3d_record_io io, const e3d_policy_acc acc, const double kill,
+                                                                  double *rs, const double gamma) {
+    constexpr int G = WAVE / PT;
+    constexpr unsigned long long GM = (PT == 64) ? ~0ull : ((1ull << PT) - 1ull);
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT, base = lane - a;
+    const int env = wave * G + g, P = c.P;
+    const bool ev = env < st.N, pv = ev && a < P;
+    const float live = pv ? io.live[(int64_t)env * io.live_rs + a] : 0.f;
+    const float raw = pv ? reward[(size_t)env * P + a] : 0.f;
+    const float rl = raw * live;
+    const bool db = ev && acc.done_before[env] != 0;
+    float rb = rl;  // the buffer's reward
+    if (SCALED && pv && !db) {
+        double *q = rs + (size_t)env * (1 + 3 * P);
+        const double n = q[0] + 1.0;
+        double mean = q[1 + a], S = q[1 + P + a], R = q[1 + 2 * P + a];
+        rb = (float)rscale::step((double)raw, gamma, n, mean, S, R) * live;
+        q[1 + a] = mean; q[1 + P + a] = S; q[1 + 2 * P + a] = R;
+        if (a == 0) q[0] = n;
+    }
+    if (pv) {
+        if (io.r) io.r[(int64_t)env * io.r_rs + a] = rb;
+        if (io.active) io.active[(int64_t)env * io.active_rs + a] = live;
+        if (io.v) io.v[(int64_t)env * io.v_rs + a] = io.value[(int64_t)env * io.value_rs + a] * live;
+    }
+    // the state after the tick (the records): why the episode may have ended, as get_done of the tick evaluates it
+    const bool p_on = pv && st.p[(size_t)env * 7 * P + 6 * P + a] != 0.0;
+    const int pa = __popcll((__ballot(p_on) >> base) & GM);
+    bool e_dead = false, reach = false;
+    if (ev) {
+        const double *ge = st.e + (size_t)env * 7, *tg = st.target + (size_t)env * 3;
+        e_dead = ge[6] == 0.0;
+        reach = sq3(ge[0] - tg[0], ge[1] - tg[1], ge[2] - tg[2]) <= kill;
+    }
+    float s = 0.f;  // the step's team reward, summed in agent order
+    for (int k = 0; k < P; k++) s += __shfl(rl, base + k);
+    const bool ended = ev && (acc.ended[env] != 0 || ((reach || pa == 0 || e_dead) && !db));
+    const bool dn = ev && (db || done[env] != 0);
+    if (pv) {
+        if (io.v_next && (!p_on || ended)) io.v_next[(int64_t)env * io.v_next_rs + a] = 0.f;
+        if (io.live_next) io.live_next[(int64_t)env * io.live_next_rs + a] = (p_on && !dn) ? 1.f : 0.f;
+    }
+    if (ev && a == 0) {
+        acc.ended[env] = ended;
+        if (e_dead && !db) acc.captured[env] = 1;
+        if (!db) acc.length[env] += 1.f;
+        acc.ret[env] += s;
+        acc.done_before[env] = dn;
+    }
+}
+
+template <bool SCALED>
+int e3d_record_launch(const e3d_config *c, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io &io,
+                      const e3d_policy_acc &acc, double *rs, double gamma, hipStream_t s) {
+    const int pt = c->P <= 8 ? 8 : (c->P <= 16 ? 16 : (c->P <= 32 ? 32 : 64));
+    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    const double kill = sq_threshold(c->kill_radius);
+#define E3D_REC(PT) hipLaunchKernelGGL((k_e3d_policy_record<PT, SCALED>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, reward, done, io, acc, kill, rs, gamma)
+    if (pt == 8) E3D_REC(8); else if (pt == 16) E3D_REC(16); else if (pt == 32) E3D_REC(32); else E3D_REC(64);
+#undef E3D_REC
+    return (int)hipGetLastError();
+}
+
 struct E3dResetter { e3d_config cfg; int N; std::vector<rngrep::NpRandom> rng; };
 
 }  // namespace
@@ -373,6 +445,17 @@ int e3d_policy_features(const e3d_config *cfg, const e3d_state *st, const e3d_ob
     if (rows == 0) return 0;
     hipLaunchKernelGGL(k_e3d_features, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cfg, *st, *out, actor_feat, critic_feat);
     return (int)hipGetLastError();
+}
+
+int e3d_policy_record(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
+                      const e3d_policy_acc *acc, double *rs, double gamma, void *stream) {
+    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value)) return E3D_ERR_NULL;
+    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (st->N < 1) return 0;
+    if (rs) return e3d_record_launch<true>(cfg, st, reward, done, *io, *acc, rs, gamma, (hipStream_t)stream);
+    return e3d_record_launch<false>(cfg, st, reward, done, *io, *acc, nullptr, 0.0, (hipStream_t)stream);
 }
 
 int e3d_evader_slsqp(const e3d_config *cfg, const e3d_state *st, double *e_cmd, void *stream) {

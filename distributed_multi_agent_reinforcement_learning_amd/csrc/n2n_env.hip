@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "n2n_env.h"
+#include "reward_scale.hpp"
 #include "rng_replica.hpp"
 #include "slsqp_box.hpp"
 
@@ -223,9 +224,13 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_inputs(const n2n_conf
         }
 }
 
-template <int PT>
+// SCALED: the reward row is the reference's RewardScaling of the raw reward (csrc/reward_scale.hpp) for environments not done before
+// the step; rs [N][1 + 3P] (n, mean[P], S[P], R[P]) is read and written once per lane, n by slot 0 after every lane of the group has
+// loaded it (one wave, program order).  The return accumulator keeps the raw reward.
+template <int PT, bool SCALED>
 __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_config c, const n2n_state st, const float *reward, const uint8_t *done,
-                                                                  const n2n_record_io io, const n2n_policy_acc acc, const double kill) {
+                                                                  const n2n_record_io io, const n2n_policy_acc acc, const double kill,
+                                                                  double *rs, const double gamma) {
     constexpr int G = WAVE / PT;
     const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
     const int g = lane / PT, a = lane - g * PT, base = lane - a;
@@ -233,9 +238,19 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_conf
     const bool ev = env < st.N, pv = ev && a < P, evv = ev && a < E;
     const double *gp = st.p + (size_t)(ev ? env : 0) * 5 * P, *ge = st.e + (size_t)(ev ? env : 0) * 5 * E;
     const float live = pv ? io.live[(int64_t)env * io.live_rs + a] : 0.f;
-    const float rl = pv ? reward[(size_t)env * P + a] * live : 0.f;
+    const float raw = pv ? reward[(size_t)env * P + a] : 0.f;
+    const float rl = raw * live;
+    float rb = rl;  // the buffer's reward
+    if (SCALED && pv && acc.done_before[env] == 0) {
+        double *q = rs + (size_t)env * (1 + 3 * P);
+        const double n = q[0] + 1.0;
+        double mean = q[1 + a], S = q[1 + P + a], R = q[1 + 2 * P + a];
+        rb = (float)rscale::step((double)raw, gamma, n, mean, S, R) * live;
+        q[1 + a] = mean; q[1 + P + a] = S; q[1 + 2 * P + a] = R;
+        if (a == 0) q[0] = n;
+    }
     if (pv) {
-        if (io.r) io.r[(int64_t)env * io.r_rs + a] = rl;
+        if (io.r) io.r[(int64_t)env * io.r_rs + a] = rb;
         if (io.active) io.active[(int64_t)env * io.active_rs + a] = live;
         if (io.v) io.v[(int64_t)env * io.v_rs + a] = io.value[(int64_t)env * io.value_rs + a] * live;
     }
@@ -380,6 +395,25 @@ void sample_points(rngrep::NpRandom &g, int n, double lx, double ly, double lo, 
     }
 }
 
+// n2n_policy_record / n2n_policy_record_scaled: one launch, the tick's lane layout
+template <bool SCALED>
+int n2n_record_launch(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
+                      const n2n_policy_acc *acc, double *rs, double gamma, void *stream) {
+    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value) || (SCALED && !rs)) return N2N_ERR_NULL;
+    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return N2N_ERR_NULL;
+    const int rc = n2n_config_check(cfg);
+    if (rc) return rc;
+    if (st->N < 1) return 0;
+    int blocks;
+    const int pt = n2n_lanes(cfg, st->N, &blocks);
+    const double kill = sq_threshold(cfg->kill_radius);
+    hipStream_t s = (hipStream_t)stream;
+#define N2N_REC(PT) hipLaunchKernelGGL((k_n2n_policy_record<PT, SCALED>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, reward, done, *io, *acc, kill, rs, gamma)
+    if (pt == 8) N2N_REC(8); else if (pt == 16) N2N_REC(16); else if (pt == 32) N2N_REC(32); else N2N_REC(64);
+#undef N2N_REC
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -465,19 +499,12 @@ int n2n_policy_inputs(const n2n_config *cfg, const n2n_state *st, const uint8_t 
 
 int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
                       const n2n_policy_acc *acc, void *stream) {
-    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value)) return N2N_ERR_NULL;
-    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return N2N_ERR_NULL;
-    const int rc = n2n_config_check(cfg);
-    if (rc) return rc;
-    if (st->N < 1) return 0;
-    int blocks;
-    const int pt = n2n_lanes(cfg, st->N, &blocks);
-    const double kill = sq_threshold(cfg->kill_radius);
-    hipStream_t s = (hipStream_t)stream;
-#define N2N_REC(PT) hipLaunchKernelGGL((k_n2n_policy_record<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, reward, done, *io, *acc, kill)
-    if (pt == 8) N2N_REC(8); else if (pt == 16) N2N_REC(16); else if (pt == 32) N2N_REC(32); else N2N_REC(64);
-#undef N2N_REC
-    return (int)hipGetLastError();
+    return n2n_record_launch<false>(cfg, st, reward, done, io, acc, nullptr, 0.0, stream);
+}
+
+int n2n_policy_record_scaled(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
+                             const n2n_policy_acc *acc, double *rs, double gamma, void *stream) {
+    return n2n_record_launch<true>(cfg, st, reward, done, io, acc, rs, gamma, stream);
 }
 
 void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seeds) {

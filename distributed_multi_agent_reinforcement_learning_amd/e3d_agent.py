@@ -90,6 +90,7 @@ class _E3dRollout:
         self.action, self.env_action, self.logp, self.v = z(N, P, A), z(N, P, A, dt=torch.float64), z(N, P), z(N, P)
         self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.live = z(N, P)   # this step's live mask (e3d_policy_record keeps it current)
         self.t = 0
 
 
@@ -116,6 +117,7 @@ class E3dMAPPO:
         a = cfg.algo
         if bool(a.get("use_reward_norm", False)):
             raise ValueError("algo.use_reward_norm: true is not supported on env_3d (runtime.env: e3d); set it to false")
+        self.use_reward_scaling = bool(a.get("use_reward_scaling", False))   # the reference's RewardScaling in policy_record
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
         self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
@@ -185,7 +187,9 @@ class E3dMAPPO:
     def run_episode(self, env, buf=None, greedy=False):
         """N episodes in lockstep for T = env.max_step ticks.  Row (n, t, p) is live iff environment n was not done before step t and
         pursuer p was active at its start; rewards, values and the `active` mask of other rows are zero, so is v_n[n, t + 1, p] when
-        pursuer p or episode n ended in step t for any reason but the time limit; v_n[:, T] is the critic's bootstrap value.
+        pursuer p or episode n ended in step t for any reason but the time limit; v_n[:, T] is the critic's bootstrap value.  The masks
+        and the per-environment accumulators are one launch per tick (ParticleEnv.policy_record); with algo.use_reward_scaling and a
+        buffer, r is the scaled reward (env.reward_scale advances) while the return stays the raw one.
         Returns per-environment (return, captured, length) device tensors."""
         N, P, T = env.num_envs, env.p_num, env.max_step
         env.reset()
@@ -193,40 +197,28 @@ class E3dMAPPO:
         st.hbuf_a.zero_()
         st.hbuf_c.zero_()
         st.t = 0
-        dev = self.device
-        done_before = torch.zeros(N, dtype=torch.bool, device=dev)
-        ended = torch.zeros(N, dtype=torch.bool, device=dev)       # ended for a reason other than the time limit
-        captured = torch.zeros(N, dtype=torch.bool, device=dev)
-        ret, length = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
-        kill_sq = env.kill_radius ** 2
+        st.live.copy_(env.active_t)   # no environment is done; policy_record writes the next step's mask
+        acc = env.new_accumulators()
+        scale_gamma = self.gamma if (self.use_reward_scaling and buf is not None) else None   # evaluation never scales
         for t in range(T):
-            live = env.active_t.float() * (~done_before).float()[:, None]
             env.policy_features(st.fa, st.fc)
             self._policy_step(st, greedy)
             env.evader_step()
-            r, done, active = env.step(st.env_action)
-            rl = r * live
-            if buf is not None:
-                buf["feat_a"][:, t].copy_(st.fa)
-                buf["feat_c"][:, t].copy_(st.fc)
-                buf["a_n"][:, t].copy_(st.action)
-                buf["a_logprob_n"][:, t].copy_(st.logp)
-                buf["v_n"][:, t].copy_(st.v * live)
-                buf["r"][:, t].copy_(rl)
-                buf["active"][:, t].copy_(live)
-            ret += rl.sum(-1)
-            e_dead = env.e[:, 6] == 0
-            reach = ((env.e[:, :3] - env.target) ** 2).sum(-1) <= kill_sq
-            end_nt = (e_dead | (active.sum(-1) == 0) | reach) & ~done_before
-            captured |= e_dead & ~done_before
-            length += (~done_before).float()
-            ended |= end_nt
-            done_before |= done.bool()
+            env.step(st.env_action)
+            if buf is None:
+                env.policy_record(acc, st.live, live_next=st.live)
+                continue
+            buf["feat_a"][:, t].copy_(st.fa)
+            buf["feat_c"][:, t].copy_(st.fc)
+            buf["a_n"][:, t].copy_(st.action)
+            buf["a_logprob_n"][:, t].copy_(st.logp)
+            env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1], st.live,
+                              scale_gamma=scale_gamma)
         if buf is not None:
             env.policy_features(st.fa, st.fc)
-            vmask = env.active_t.float() * (~ended).float()[:, None]
+            vmask = env.active_t.float() * (acc["ended"] == 0).float()[:, None]
             buf["v_n"][:, T].copy_(self._bootstrap_value(st) * vmask)
-        return ret, captured, length
+        return acc["ret"], acc["captured"] != 0, acc["length"]
 
     def explore_env(self, env):
         """one episode per environment into a fresh buffer -> (mean return, buffer, env-steps, stats)"""
@@ -332,12 +324,15 @@ class E3dMAPPO:
         self.critic.load_state_dict(sd["critic"])
 
 
-def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0):
-    """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env)"""
+def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
+    """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env).  A training
+    environment owns the RewardScaling state when algo.use_reward_scaling is on; evaluation environments (training=False) never do."""
     base = int(cfg.runtime.get("seed", 0)) + seed_offset + max(1000, num_envs) * rank
     env = ParticleEnv(num_envs=num_envs, seeds=[base + n for n in range(num_envs)], device=device, max_step=int(cfg.env.max_steps),
                       evader=str(cfg.runtime.get("e3d_evader", "slsqp")))
     env.initialize(int(cfg.env.num_defender))
+    if training and bool(cfg.algo.get("use_reward_scaling", False)):
+        env.enable_reward_scaling()
     return env
 
 
@@ -399,7 +394,7 @@ class E3dTrainer(ParticleRunState):
     def make_eval_env(self):
         """the evaluation environments (created once): num_eval_envs of their own seeds, seed + 10^6 + n"""
         if self.eval_env is None:
-            self.eval_env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6)
+            self.eval_env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6, training=False)
         return self.eval_env
 
     def last_breakdown_ms(self):

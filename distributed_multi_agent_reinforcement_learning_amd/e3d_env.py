@@ -33,6 +33,23 @@ class E3dObsOut(C.Structure):
                 ("pp_adj", C.c_void_p), ("pp_adj_stride", C.c_int64), ("pe_adj", C.c_void_p), ("pe_adj_stride", C.c_int64)]
 
 
+class E3dPolicyAcc(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("done_before", "ended", "captured", "ret", "length")]
+
+
+class E3dRecordIO(C.Structure):
+    _fields_ = [(n, t) for k in ("live", "value", "r", "active", "v", "v_next", "live_next") for n, t in ((k, C.c_void_p), (k + "_rs", C.c_int64))]
+
+
+def _rows(t, shape, name):
+    """a float32 (N, ...) device tensor whose environment rows are dense (rows may be strided: buffer[:, t]) -> (pointer, row stride)"""
+    if t is None:
+        return None, 0
+    assert t.dtype == torch.float32 and t.is_cuda and tuple(t.shape) == tuple(shape), (name, tuple(t.shape), tuple(shape))
+    assert t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= t[0].numel()), f"{name}: rows must be dense"
+    return t.data_ptr(), t.stride(0)
+
+
 _lib = None
 
 
@@ -60,6 +77,7 @@ def load_library():
         L.e3d_resetter_get_state.argtypes = [vp, vp]
         L.e3d_resetter_set_state.argtypes = [vp, vp]
         L.e3d_policy_features.argtypes = [vp] * 6
+        L.e3d_policy_record.argtypes = [vp] * 7 + [C.c_double, vp]
         _lib = L
     return _lib
 
@@ -99,6 +117,7 @@ class ParticleEnv:
         self.p_num = None
         self.e_num = 1
         self.resetter = None
+        self.reward_scale = None
 
     def initialize(self, p_num):
         """particle_env.py:133-135, plus the allocation of the device records"""
@@ -157,6 +176,8 @@ class ParticleEnv:
         self.n_episode += 1
         self._cmd = torch.zeros((N, 3), dtype=torch.float64, device=self.device)
         self.active_t.fill_(1)
+        if self.reward_scale is not None:
+            self.reward_scale[:, 1 + 2 * self.p_num:].zero_()   # RewardScaling.reset: R; n, mean, S persist
         self.observe()
 
     def get_resetter_state(self):
@@ -216,6 +237,46 @@ class ParticleEnv:
         _check(self.L.e3d_policy_features(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_void_p(actor_feat.data_ptr()),
                                           C.c_void_p(critic_feat.data_ptr()), _stream()), "e3d_policy_features")
         return actor_feat, critic_feat
+
+    # ---- MAPPO on env_3d (e3d_agent.py): the bookkeeping of one lockstep tick, one launch after step() ------------------------------
+    def new_accumulators(self):
+        """zeroed per-environment episode accumulators for policy_record: done_before, ended, captured (uint8), return, length"""
+        N, dev = self.num_envs, self.device
+        u8 = lambda: torch.zeros(N, dtype=torch.uint8, device=dev)
+        return dict(done_before=u8(), ended=u8(), captured=u8(), ret=torch.zeros(N, device=dev), length=torch.zeros(N, device=dev))
+
+    def enable_reward_scaling(self):
+        """allocates the RewardScaling state of a training environment (algo.use_reward_scaling): reward_scale (N, 1 + 3P) f64, per
+        environment n, mean[P], S[P], R[P] (csrc/reward_scale.hpp); reset() zeroes R, the rest persists over episodes"""
+        self.reward_scale = torch.zeros((self.num_envs, 1 + 3 * self.p_num), dtype=torch.float64, device=self.device)
+        return self.reward_scale
+
+    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, live_next=None, scale_gamma=None):
+        """after step(): r = reward * live, active = live, v = value * live (row t of the buffer, None skips), v_next (row t + 1 of v_n)
+        zeroed where the pursuer is inactive or its episode ended for a reason other than the time limit, live_next = the next step's
+        live mask (may be `live` itself); updates the accumulators of new_accumulators() (e3d_policy_record, include/e3d_env.h).
+        scale_gamma: the discount of the reference's RewardScaling; r is then the scaled reward * live and reward_scale
+        (enable_reward_scaling) advances, in the same launch."""
+        N, P = self.num_envs, self.p_num
+        io = E3dRecordIO()
+        for k, t in (("live", live), ("value", value), ("r", r), ("active", active), ("v", v), ("v_next", v_next), ("live_next", live_next)):
+            ptr, rs = _rows(t, (N, P), k)
+            setattr(io, k, ptr)
+            setattr(io, k + "_rs", rs)
+        a = E3dPolicyAcc()
+        for k, dt in (("done_before", torch.uint8), ("ended", torch.uint8), ("captured", torch.uint8), ("ret", torch.float32), ("length", torch.float32)):
+            t = acc[k]
+            assert t.dtype == dt and t.is_contiguous() and t.shape == (N,) and t.device == self.p.device, k
+            setattr(a, k, t.data_ptr())
+        rs_ptr, gamma = None, 0.0
+        if scale_gamma is not None:
+            rs = self.reward_scale
+            if rs is None:
+                raise RuntimeError("policy_record(scale_gamma=...) needs enable_reward_scaling() on this environment")
+            assert rs.dtype == torch.float64 and rs.is_contiguous() and rs.shape == (N, 1 + 3 * P) and rs.device == self.p.device
+            rs_ptr, gamma = rs.data_ptr(), float(scale_gamma)
+        _check(self.L.e3d_policy_record(C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()),
+                                        C.byref(io), C.byref(a), C.c_void_p(rs_ptr), C.c_double(gamma), _stream()), "e3d_policy_record")
 
     def step(self, action):
         """:205-219 (preceded by the evader's move with the command of evader_step) -> (reward (N,P), done (N,), active (N,P));

@@ -62,6 +62,7 @@ class N2nMAPPO:
         a = cfg.algo
         if bool(a.get("use_reward_norm", False)):
             raise ValueError("algo.use_reward_norm: true is not supported on env_n2n (runtime.env: n2n); set it to false")
+        self.use_reward_scaling = bool(a.get("use_reward_scaling", False))   # the reference's RewardScaling in policy_record
         if int(cfg.env.num_defender) > MAX_P:
             raise ValueError(f"env.num_defender={cfg.env.num_defender}: the DHGN message kernels take at most {MAX_P} pursuers per row")
         if int(cfg.env.state_dim) != 4 or int(cfg.env.action_dim) != 9 or int(a.num_relation) != 3:
@@ -138,12 +139,14 @@ class N2nMAPPO:
         policy_record, and (with a buffer) one rollout_record launch.  Row (n, t, p) is live iff pursuer p was active at the start of step t
         and environment n was not done before it; r, v_n and `active` of other rows are zero, so is v_n[n, t + 1, p] when pursuer p or
         episode n ended in step t for a reason other than the time limit; v_n[:, T] is the critic's bootstrap value under that rule.
+        With algo.use_reward_scaling and a buffer, r is the scaled reward (env.reward_scale advances); acc["ret"] stays the raw return.
         Returns the per-environment accumulators (done_before, ended, captured, ret, length)."""
         N, P, T, d = env.num_envs, env.p_num, env.episode_limit, self.depth
         env.reset()
         st = self._state(env)
         st.reset()
         acc = env.new_accumulators()
+        scale_gamma = self.gamma if (self.use_reward_scaling and buf is not None) else None   # evaluation never scales
         for t in range(T):
             env.policy_inputs(st.p4, st.e4, st.e_ref, st.live, st.pp, st.pe, acc["done_before"])
             self._policy_step(st, greedy)
@@ -152,7 +155,8 @@ class N2nMAPPO:
             if buf is None:
                 env.policy_record(acc, st.live)
                 continue
-            env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1])
+            env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1],
+                              scale_gamma=scale_gamma)
             items = [(st.p4, buf["p_state"][:, t]), (st.e4, buf["e_state"][:, t]), (st.e_ref, buf["e_ref"][:, t]), (st.pp, buf["p_adj"][:, t]),
                      (st.pe, buf["e_adj"][:, t]), (st.a_n, buf["a_n"][:, t]), (st.logp, buf["a_logprob_n"][:, t])]
             if d:   # the update reads the stored embeddings as FCRA history only
@@ -244,12 +248,15 @@ class N2nMAPPO:
         self.critic.load_state_dict(torch.load(os.path.join(cwd, f"n2n_critic{sfx}.pth"), map_location=self.device))
 
 
-def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0):
-    """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env)"""
+def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
+    """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env).  A training
+    environment owns the RewardScaling state when algo.use_reward_scaling is on; evaluation environments (training=False) never do."""
     base = int(cfg.runtime.get("seed", 0)) + seed_offset + max(1000, num_envs) * rank
     env = ParticleEnv(num_envs=num_envs, seeds=[base + n for n in range(num_envs)], device=device, episode_limit=int(cfg.env.max_steps),
                       evader=str(cfg.runtime.get("n2n_evader", "slsqp")))
     env.initialize(int(cfg.env.num_defender), int(cfg.env.num_evader))
+    if training and bool(cfg.algo.get("use_reward_scaling", False)):
+        env.enable_reward_scaling()
     return env
 
 
@@ -312,7 +319,7 @@ class N2nTrainer(ParticleRunState):
     def make_eval_env(self):
         """the evaluation environments (created once): num_eval_envs of their own seeds, seed + 10^6 + n"""
         if self.eval_env is None:
-            self.eval_env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6)
+            self.eval_env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6, training=False)
         return self.eval_env
 
     def last_breakdown_ms(self):

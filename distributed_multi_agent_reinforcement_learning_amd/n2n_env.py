@@ -82,6 +82,7 @@ def load_library():
         L.n2n_resetter_set_state.argtypes = [vp, vp]
         L.n2n_policy_inputs.argtypes = [vp] * 5
         L.n2n_policy_record.argtypes = [vp] * 7
+        L.n2n_policy_record_scaled.argtypes = [vp] * 7 + [C.c_double, vp]
         _lib = L
     return _lib
 
@@ -118,6 +119,7 @@ class ParticleEnv:
         self.n_episode = 0
         self.p_num = self.e_num = None
         self.resetter = None
+        self.reward_scale = None
 
     def initialize(self, p_num, e_num):
         """particle_env.py:160-162, plus the allocation of the device records"""
@@ -174,6 +176,8 @@ class ParticleEnv:
         self.time_step = 0
         self.n_episode += 1
         self._cmd = torch.zeros((N, self.e_num), dtype=torch.float64, device=self.device)
+        if self.reward_scale is not None:
+            self.reward_scale[:, 1 + 2 * self.p_num:].zero_()   # RewardScaling.reset: R; n, mean, S persist
         self.observe()
 
     def get_resetter_state(self):
@@ -245,6 +249,12 @@ class ParticleEnv:
         u8 = lambda: torch.zeros(N, dtype=torch.uint8, device=dev)
         return dict(done_before=u8(), ended=u8(), captured=u8(), ret=torch.zeros(N, device=dev), length=torch.zeros(N, device=dev))
 
+    def enable_reward_scaling(self):
+        """allocates the RewardScaling state of a training environment (algo.use_reward_scaling): reward_scale (N, 1 + 3P) f64, per
+        environment n, mean[P], S[P], R[P] (csrc/reward_scale.hpp); reset() zeroes R, the rest persists over episodes"""
+        self.reward_scale = torch.zeros((self.num_envs, 1 + 3 * self.p_num), dtype=torch.float64, device=self.device)
+        return self.reward_scale
+
     def policy_inputs(self, p4, e4, e_ref, live, pp_adj, pe_adj, done_before=None):
         """the DHGN's fp32 inputs of the current state (n2n_policy_inputs, include/n2n_env.h): p4 (N,P,4), e4 (N,E,4), e_ref (N,4),
         live (N,P), pp_adj (N,P,P), pe_adj (N,P,E), each None (skipped) or a tensor with dense environment rows, e.g. buffer[:, t].
@@ -263,10 +273,11 @@ class ParticleEnv:
         _check(self.L.n2n_policy_inputs(C.byref(self.c), C.byref(self.st), C.c_void_p(done_before.data_ptr() if done_before is not None else None),
                                         C.byref(io), _stream()), "n2n_policy_inputs")
 
-    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None):
+    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, scale_gamma=None):
         """after step(): r = reward * live, active = live, v = value * live (row t of the buffer, None skips), v_next (row t + 1 of v_n)
         zeroed where the pursuer is inactive or its episode ended for a reason other than the time limit; updates the accumulators
-        of new_accumulators() (n2n_policy_record, include/n2n_env.h)."""
+        of new_accumulators() (n2n_policy_record, include/n2n_env.h).  scale_gamma: the discount of the reference's RewardScaling; r is
+        then the scaled reward * live and reward_scale (enable_reward_scaling) advances, in the same launch (n2n_policy_record_scaled)."""
         N, P = self.num_envs, self.p_num
         io = N2nRecordIO()
         for k, t in (("live", live), ("value", value), ("r", r), ("active", active), ("v", v), ("v_next", v_next)):
@@ -278,5 +289,13 @@ class ParticleEnv:
             t = acc[k]
             assert t.dtype == dt and t.is_contiguous() and t.shape == (N,) and t.device == self.p.device, k
             setattr(a, k, t.data_ptr())
-        _check(self.L.n2n_policy_record(C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()),
-                                        C.byref(io), C.byref(a), _stream()), "n2n_policy_record")
+        args = (C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()), C.byref(io), C.byref(a))
+        if scale_gamma is None:
+            _check(self.L.n2n_policy_record(*args, _stream()), "n2n_policy_record")
+            return
+        rs = self.reward_scale
+        if rs is None:
+            raise RuntimeError("policy_record(scale_gamma=...) needs enable_reward_scaling() on this environment")
+        assert rs.dtype == torch.float64 and rs.is_contiguous() and rs.shape == (N, 1 + 3 * P) and rs.device == self.p.device
+        _check(self.L.n2n_policy_record_scaled(*args, C.c_void_p(rs.data_ptr()), C.c_double(float(scale_gamma)), _stream()),
+               "n2n_policy_record_scaled")

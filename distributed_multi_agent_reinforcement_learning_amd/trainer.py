@@ -149,7 +149,8 @@ class ParticleRunState:
     checkpoint.  The trainer provides env, eval_env and make_eval_env(), agent (rollout state `agent._state(env)` with the sampling
     counter; save_model / load_model), total_steps, iteration, num_envs, world, rank, device, eval_return_std, recorder and
     best_eval_return.  Every environment episode starts from a reset and every rollout from zero GRU states and history, so the
-    reset generators, the sampling counters, the weights and Adam are all the state a run carries from one iteration to the next."""
+    reset generators, the sampling counters, the weights and Adam are all the state a run carries from one iteration to the next --
+    and, with algo.use_reward_scaling, the training environment's reward_scale (the bundle's "reward_scaling" entry)."""
 
     def save_resume(self, path):
         agent, ev = self.agent, self.eval_env
@@ -163,6 +164,8 @@ class ParticleRunState:
         meta = agent.policy_meta() if hasattr(agent, "policy_meta") else None
         if meta is not None:   # env_3d with a non-default algo.gauss_std / gauss_squash (E3dMAPPO.policy_meta); default bundles carry none
             bundle["policy"] = meta
+        if getattr(agent, "use_reward_scaling", False):   # algo.use_reward_scaling: n, mean, S (and R) of every environment; off: no entry
+            bundle["reward_scaling"] = self.env.reward_scale.cpu()
         torch.save(bundle, path)
 
     def load_resume(self, path):
@@ -173,6 +176,10 @@ class ParticleRunState:
         agent = self.agent
         if hasattr(agent, "check_policy_meta"):
             agent.check_policy_meta(b.get("policy"), "resume bundle " + str(path))
+        theirs, mine = "reward_scaling" in b, bool(getattr(agent, "use_reward_scaling", False))
+        if theirs != mine:
+            raise ValueError(f"resume bundle {path} was written with algo.use_reward_scaling: {str(theirs).lower()}, "
+                             f"this agent has algo.use_reward_scaling: {str(mine).lower()}")
         agent.actor.load_state_dict(b["actor"])
         agent.critic.load_state_dict(b["critic"])
         agent.ac_optimizer.load_state_dict(b["optimizer"])
@@ -185,6 +192,8 @@ class ParticleRunState:
         self.env.set_resetter_state(b["resetter"])
         self.env.n_episode = b["n_episode"]
         agent._state(self.env).counter.copy_(b["sample_counter"])
+        if mine:
+            self.env.reward_scale.copy_(b["reward_scaling"])
         if b["eval_resetter"] is not None:
             ev = self.make_eval_env()
             ev.set_resetter_state(b["eval_resetter"])

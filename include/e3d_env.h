@@ -65,6 +65,37 @@ int e3d_env_tick(const e3d_config *cfg, const e3d_state *st, const double *actio
  * (actor | critic); rows of inactive pursuers are zero. */
 int e3d_policy_features(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, float *actor_feat, float *critic_feat, void *stream);
 
+/* ---- MAPPO bookkeeping of one lockstep tick (e3d_agent.py), the structs of n2n_env.h for env_3d ----
+ * fp32 rows with *_rs = elements between environments (dense storage or step t of an (N, T, P) buffer); a NULL output is skipped.
+ * A row is LIVE when its pursuer was active at the start of the step and its environment was not done before it. */
+typedef struct e3d_policy_acc {  /* per-environment episode accumulators [N], zeroed by the caller before the first step */
+    uint8_t *done_before;        /* the environment reported done in an earlier step                                          */
+    uint8_t *ended;              /* it ended for a reason other than the time limit (evader dead, no pursuer active, evader
+                                    within the kill radius of the target), in this or an earlier step                         */
+    uint8_t *captured;           /* the evader was captured before done                                                        */
+    float *ret;                  /* sum over steps of sum_p reward * live (fp32, agents summed in order per step); raw reward  */
+    float *length;               /* steps taken before done                                                                    */
+} e3d_policy_acc;
+
+typedef struct e3d_record_io {
+    const float *live;  int64_t live_rs;    /* [N][P] this step's live mask, required (first step: the active flags after reset) */
+    const float *value; int64_t value_rs;   /* [N][P] the critic's value of this step, required with v                           */
+    float *r;      int64_t r_rs;            /* [N][P] reward * live (with rs: the scaled reward * live)                          */
+    float *active; int64_t active_rs;       /* [N][P] live                                                                       */
+    float *v;      int64_t v_rs;            /* [N][P] value * live                                                               */
+    float *v_next; int64_t v_next_rs;       /* [N][P] set to 0 where the pursuer is inactive after the step or its environment
+                                               has ended (time limit excepted); other entries untouched                         */
+    float *live_next; int64_t live_next_rs; /* [N][P] the next step's live mask: active after the step and the environment not
+                                               done after it; may be the storage of `live` (every lane reads its entry first)    */
+} e3d_record_io;
+
+/* After e3d_env_tick: buffer row t, the next live mask and the accumulators from the tick's reward [N][P] and done [N] and the records
+ * after it.  rs: NULL, or the RewardScaling state [N][1 + 3P] f64 (n, mean[P], S[P], R[P]; csrc/reward_scale.hpp, semantics as
+ * n2n_policy_record_scaled of n2n_env.h) with its discount gamma: the reward row is then the scaled one for environments not done
+ * before the step, and rs of the others is left untouched.  One launch, the tick's lane layout. */
+int e3d_policy_record(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
+                      const e3d_policy_acc *acc, double *rs, double gamma, void *stream);
+
 /* The reference's evader: eva.e_f (eva.py:87-148) -- scipy's SLSQP (ftol 1e-6, <= 100 iterations, 2-point finite-difference
  * gradient) minimising obj_func (:212-240) over (heading, pitch, speed), started at the evader's state, bounded by the
  * environment's ang_lmt / v_lmt (:130-135) -- written as the command e_cmd [N][3] that e3d_env_tick consumes; zeros when the

@@ -104,6 +104,14 @@ int n2n_policy_inputs(const n2n_config *cfg, const n2n_state *st, const uint8_t 
 /* After n2n_env_tick: buffer row t and the accumulators from the tick's reward [N][P] and done [N] and the records after it. */
 int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
                       const n2n_policy_acc *acc, void *stream);
+/* n2n_policy_record with the reference's RewardScaling (DHGN/normalization.py:38-52, csrc/reward_scale.hpp) on the reward row, in the
+ * same launch.  rs [N][1 + 3P] f64: n, mean[P], S[P], R[P] per environment; the caller zeroes it once (and R at every episode start:
+ * RewardScaling.reset).  For an environment that was not done before the step, with x = reward[P] (every pursuer's, an inactive one's 0
+ * included): R = gamma R + x; n += 1; n == 1: mean = std = R, else mean' = mean + (R - mean) / n, S += (R - mean)(R - mean'),
+ * std = sqrt(S / n); io->r = (float)(x / (std + 1e-8)) * live.  Environments done before the step leave rs untouched (r = reward * live,
+ * zero).  acc->ret keeps the raw reward.  Everything else as n2n_policy_record. */
+int n2n_policy_record_scaled(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
+                             const n2n_policy_acc *acc, double *rs, double gamma, void *stream);
 
 /* Host side of ParticleEnv.reset (:200-281) with a bit-exact replica of numpy's legacy RandomState per environment
  * (np.random.seed(seeds[n])).  Fills host arrays p [N][P][5], e [N][E][5], target [N][2]. */

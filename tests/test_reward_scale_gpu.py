@@ -1,0 +1,248 @@
+"""GPU checks of algo.use_reward_scaling (the reference's RewardScaling in n2n_policy_record_scaled / e3d_policy_record) and of the
+env_3d record kernel: fixture replay through both kernels bit for bit, e3d_policy_record against a torch restatement of the
+bookkeeping it replaces, one training iteration per environment against tests/reward_scale_ref.py, and resume."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import reward_scale_ref as ref
+from tests.conftest import GOLDEN
+
+pytestmark = pytest.mark.gpu
+
+CONFIG = {"e3d": "cfg5", "n2n": "cfg4_n2n"}
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(os.path.join(GOLDEN, "reward_scaling.npz"))
+
+
+def _env(kind, N, P, T=100):
+    if kind == "n2n":
+        from distributed_multi_agent_reinforcement_learning_amd.n2n_env import ParticleEnv
+        env = ParticleEnv(num_envs=N, seeds=list(range(N)), episode_limit=T, evader="slsqp")
+        env.initialize(P, 1)
+    else:
+        from distributed_multi_agent_reinforcement_learning_amd.e3d_env import ParticleEnv
+        env = ParticleEnv(num_envs=N, seeds=list(range(N)), max_step=T, evader="slsqp")
+        env.initialize(P)
+    return env
+
+
+def _cfg(kind, **ov):
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config
+    return baseline_config(CONFIG[kind], **ov)
+
+
+def _trainer(kind, cfg, **kw):
+    if kind == "e3d":
+        from distributed_multi_agent_reinforcement_learning_amd.e3d_agent import E3dTrainer as T
+    else:
+        from distributed_multi_agent_reinforcement_learning_amd.n2n_agent import N2nTrainer as T
+    return T(cfg, **kw)
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+# ---- both kernels replay the fixture ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,P", [("n2n", 16), ("n2n", 8), ("e3d", 8), ("e3d", 16)])
+def test_kernels_replay_the_fixture_bit_for_bit(gold, kind, P):
+    """13 environments in one launch per tick, each on its own stream: whole fixture streams (checked against the fixture itself),
+    the same episodes cut after 7 steps (done early), and the episodes in reverse order; pursuer 2 of every odd environment is not
+    live.  Every tick: r and the whole state against the numpy restatement, environments done before the step unchanged."""
+    g = float(gold["gamma"])
+    streams = [ref.Stream(gold, k) for k in (("n2n",) if P == 16 else ("syn", "e3d"))]
+    N = 13
+    plans, full = [], {}
+    for n in range(N):
+        s = streams[n % len(streams)]
+        eps = [s.x[a:b] for a, b in s.episodes]
+        mode = (n // len(streams)) % 3
+        if mode == 0:
+            full[n] = s
+        plans.append(eps if mode == 0 else [e[:7] for e in eps] if mode == 1 else eps[::-1])
+    env = _env(kind, N, P)
+    env.enable_reward_scaling()
+    state = ref.new_state(N, P)
+    rbuf = torch.full((N, 3, P), 7.0, device="cuda")[:, 1]    # strided rows, like buffer[:, t]
+    got_r = {n: [] for n in full}
+    for j in range(max(len(p) for p in plans)):
+        lens = np.array([len(p[j]) if j < len(p) else 0 for p in plans])
+        env.reward_scale[:, 1 + 2 * P:].fill_(3.0)
+        env.reset()                                            # zeroes R and nothing else of the state
+        ref.reset(state, P)
+        assert np.array_equal(_bits(env.reward_scale.cpu().numpy()), _bits(state))
+        acc = env.new_accumulators()
+        acc["done_before"].copy_(torch.from_numpy((lens == 0).astype(np.uint8)))
+        for t in range(int(lens.max())):
+            db = t >= lens
+            x = np.stack([plans[n][j][t] if not db[n] else np.full(P, -1.0) for n in range(N)])
+            live = np.ones((N, P), np.float32)
+            live[1::2, 2] = 0
+            live[db] = 0
+            env.reward_t.copy_(torch.from_numpy(x.astype(np.float32)))
+            env.done_t.copy_(torch.from_numpy((t == lens - 1).astype(np.uint8)))
+            before = env.reward_scale.cpu().numpy()
+            env.policy_record(acc, torch.from_numpy(live).cuda(), r=rbuf, scale_gamma=g)
+            want = ref.step(state, x, live, db, g)
+            got, st = rbuf.cpu().numpy(), env.reward_scale.cpu().numpy()
+            assert np.array_equal(_bits(got), _bits(want)), (j, t)
+            assert np.array_equal(_bits(st), _bits(state)), (j, t)
+            assert np.array_equal(_bits(st[db]), _bits(before[db]))
+            assert np.array_equal(acc["done_before"].cpu().numpy() != 0, t >= lens - 1)
+            for n in full:
+                if not db[n]:
+                    got_r[n].append((got[n], live[n]))
+    st = env.reward_scale.cpu().numpy()
+    for n, s in full.items():
+        r, live = np.stack([a for a, _ in got_r[n]]), np.stack([b for _, b in got_r[n]])
+        assert np.array_equal(_bits(r), _bits(s.y.astype(np.float32) * live))
+        assert np.array_equal(_bits(st[n]), _bits(s.final))
+
+
+def test_scaled_record_needs_the_state():
+    env = _env("e3d", 4, 3)
+    env.reset()
+    acc = env.new_accumulators()
+    with pytest.raises(RuntimeError, match="enable_reward_scaling"):
+        env.policy_record(acc, torch.ones(4, 3, device="cuda"), scale_gamma=0.99)
+
+
+# ---- e3d_policy_record, scaling off, against the bookkeeping it replaces ----------------------------------------------------------------
+@pytest.mark.parametrize("P", [3, 4, 8])
+@torch.no_grad()
+def test_e3d_record_matches_the_torch_bookkeeping(P):
+    """a cfg5 rollout of 48 environments: per tick, the torch element-wise bookkeeping of the former run_episode (live mask, masked
+    reward / value / active rows, return, length, captured, ended, done) beside one e3d_policy_record launch"""
+    from distributed_multi_agent_reinforcement_learning_amd.e3d_agent import E3dMAPPO, make_env
+    N, T = 48, 120
+    cfg = _cfg("e3d", **{"runtime.num_envs": N, "env.num_defender": P, "env.max_steps": T, "runtime.seed": 11 + P})
+    torch.manual_seed(P)
+    env, agent = make_env(cfg, N), E3dMAPPO(cfg, N, 8)
+    env.reset()
+    st = agent._state(env)
+    st.hbuf_a.zero_(); st.hbuf_c.zero_()
+    st.t = 0
+    dev = "cuda"
+    done_before = torch.zeros(N, dtype=torch.bool, device=dev)
+    ended, captured = torch.zeros_like(done_before), torch.zeros_like(done_before)
+    ret, length = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+    kill_sq = env.kill_radius ** 2
+    want = {k: torch.zeros(N, T, P, device=dev) for k in ("r", "active", "v")}
+    got = {k: torch.zeros(N, T, P, device=dev) for k in ("r", "active", "v")}
+    vnext = torch.full((N, T, P), 7.0, device=dev)
+    vz_want = torch.zeros(N, T, P, dtype=torch.bool, device=dev)
+    st.live.copy_(env.active_t)
+    acc = env.new_accumulators()
+    for t in range(T):
+        live = env.active_t.float() * (~done_before).float()[:, None]
+        assert torch.equal(live, st.live), t                   # the kernel's live_next of the step before
+        env.policy_features(st.fa, st.fc)
+        agent._policy_step(st)
+        env.evader_step()
+        r, done, active = env.step(st.env_action)
+        rl = r * live
+        want["v"][:, t].copy_(st.v * live); want["r"][:, t].copy_(rl); want["active"][:, t].copy_(live)
+        ret += rl.sum(-1)
+        e_dead = env.e[:, 6] == 0
+        reach = ((env.e[:, :3] - env.target) ** 2).sum(-1) <= kill_sq
+        end_nt = (e_dead | (active.sum(-1) == 0) | reach) & ~done_before
+        captured |= e_dead & ~done_before
+        length += (~done_before).float()
+        ended |= end_nt
+        done_before |= done.bool()
+        vz_want[:, t] = (active == 0) | ended[:, None]
+        env.policy_record(acc, st.live, st.v, got["r"][:, t], got["active"][:, t], got["v"][:, t], vnext[:, t], st.live)
+        assert torch.equal(acc["done_before"] != 0, done_before) and torch.equal(acc["ended"] != 0, ended), t
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
+    assert torch.equal(vnext == 0, vz_want) and torch.all(vnext[~vz_want] == 7)
+    assert torch.equal(acc["captured"] != 0, captured) and torch.equal(acc["length"], length)
+    # the bootstrap mask of run_episode
+    assert torch.equal(env.active_t.float() * (acc["ended"] == 0).float()[:, None], env.active_t.float() * (~ended).float()[:, None])
+    rel = ((acc["ret"] - ret).abs() / ret.abs().clamp_min(1.0)).max().item()
+    print(f"P={P}: ended {int(ended.sum())}/{N}, captured {int(captured.sum())}, mean length {length.mean().item():.1f}, "
+          f"pursuers lost {int((env.active_t == 0).sum())}, nonzero rewards {int((want['r'] != 0).sum())}, ret rel err {rel:.2e}")
+    assert rel <= 1e-6
+    assert ended.any() and (length < T).any()    # (rewards are rare under an untrained policy: their count is printed, not required)
+
+
+# ---- one training iteration with the option on ------------------------------------------------------------------------------------------
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("kind", ["e3d", "n2n"])
+def test_iteration_with_scaling_matches_the_reference_restatement(kind):
+    """env_3d rewards are rare under an untrained policy (capture rate below 1 %): 256 environments there, so that the
+    seeded rollouts hold some (their count is printed)"""
+    N = 24 if kind == "n2n" else 256
+    ov = {"runtime.num_envs": N}
+    on = _trainer(kind, _cfg(kind, **{**ov, "algo.use_reward_scaling": True}), num_eval_envs=8, eval_every=1)
+    off = _trainer(kind, _cfg(kind, **ov), num_eval_envs=8, eval_every=1)
+    assert on.agent.use_reward_scaling and not off.agent.use_reward_scaling
+    assert off.env.reward_scale is None and on.env.reward_scale.shape == (N, 1 + 3 * on.env.p_num)
+    g = float(on.cfg.algo.gamma)
+    state = ref.new_state(N, on.env.p_num)
+    for it in range(2):      # the second rollout starts from the persisted n, mean, S (the two runs' policies differ by then)
+        if it == 1:
+            off.agent.actor.load_state_dict(on.agent.actor.state_dict()); off.agent.critic.load_state_dict(on.agent.critic.state_dict())
+        mean_on, buf_on, steps, stats_on = on.agent.explore_env(on.env)
+        mean_off, buf_off, _, stats_off = off.agent.explore_env(off.env)
+        for k in buf_off:
+            if k != "r":
+                assert torch.equal(buf_on[k], buf_off[k]), k      # scaling touches the reward row only
+        assert mean_on == mean_off and stats_on == stats_off         # the return stays the raw reward
+        raw, live = buf_off["r"].cpu().numpy(), buf_off["active"].cpu().numpy()
+        length = live.max(-1).sum(-1)                                # an environment is live until it is done
+        want = ref.rollout(state, raw, live, length, g)
+        assert np.array_equal(_bits(buf_on["r"].cpu().numpy()), _bits(want)), it
+        assert np.array_equal(_bits(on.env.reward_scale.cpu().numpy()), _bits(state)), it
+        print(f"{kind} iteration {it}: {int((raw != 0).sum())} nonzero rewards, max |r| scaled {np.abs(want).max():.3f}")
+        assert np.isfinite(want).all() and (raw != 0).any()
+        with torch.enable_grad():
+            obj_c, obj_a = on.agent.train(buf_on, steps)
+        on.agent.ac_optimizer.step()
+        assert np.isfinite(obj_c) and np.isfinite(obj_a)
+    before = on.env.reward_scale.clone()
+    res = on.evaluate()
+    assert np.isfinite(res["eval_return"]) and on.eval_env.reward_scale is None
+    assert torch.equal(on.env.reward_scale, before)                 # evaluation neither scales nor touches the state
+    assert float(before[:, 0].min()) > 0
+
+
+# ---- resume -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("kind", ["e3d", "n2n"])
+def test_resume_with_scaling_continues_bit_for_bit(tmp_path, kind):
+    ov = {"runtime.num_envs": 16, "algo.save_cwd": str(tmp_path / "model"), "algo.use_reward_scaling": True}
+    a = _trainer(kind, _cfg(kind, **ov), num_eval_envs=8, eval_every=1)
+    a.iterate(); a.iterate()
+    path = str(tmp_path / "resume.pt")
+    a.save_resume(path)
+    assert "reward_scaling" in torch.load(path, weights_only=False)
+    logs_a = [a.iterate()[1] for _ in range(2)]
+    b = _trainer(kind, _cfg(kind, **ov), num_eval_envs=8, eval_every=1)
+    b.load_resume(path)
+    logs_b = [b.iterate()[1] for _ in range(2)]
+    assert torch.equal(a.env.reward_scale, b.env.reward_scale) and float(a.env.reward_scale[:, 0].min()) > 0
+    for x, y in ((a.agent.actor, b.agent.actor), (a.agent.critic, b.agent.critic)):
+        sx, sy = x.state_dict(), y.state_dict()
+        assert all(torch.equal(sx[k], sy[k]) for k in sx)
+    for la, lb in zip(logs_a, logs_b):
+        for k in ("mean_return", "critic_loss", "actor_loss", "eval_return"):
+            assert la[k] == lb[k], k
+    assert torch.equal(a.agent.buffer["r"], b.agent.buffer["r"])
+    # a bundle of the other setting is refused, both ways; an option-off bundle keeps its layout
+    c = _trainer(kind, _cfg(kind, **{**ov, "algo.use_reward_scaling": False}), num_eval_envs=8)
+    with pytest.raises(ValueError, match="algo.use_reward_scaling"):
+        c.load_resume(path)
+    c.iterate()
+    path_off = str(tmp_path / "resume_off.pt")
+    c.save_resume(path_off)
+    assert "reward_scaling" not in torch.load(path_off, weights_only=False)
+    with pytest.raises(ValueError, match="algo.use_reward_scaling"):
+        b.load_resume(path_off)
