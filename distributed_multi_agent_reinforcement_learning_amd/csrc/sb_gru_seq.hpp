@@ -133,6 +133,22 @@ inline int launch_gru_seq_fwd_sb(int n_nets, const mo_gru_seq_net *nets, int T, 
     return (int)hipGetLastError();
 }
 
+// One 16-byte LDS-direct load per lane (global_load_lds_dwordx4): the wave's 1 KiB lands lane-linear at the wave-uniform LDS byte
+// address `dst`, with no register destination; it counts in vmcnt until it has landed.  Inline assembly, so the compiler neither sees
+// the load nor waits for it: the kernel counts its own vmcnt.  `after_reads`: wait for the wave's LDS reads first (the slot is reused).
+__device__ __forceinline__ void sbr_glds16(const void *src, uint32_t dst, bool after_reads) {
+    uint32_t keep;
+    if (after_reads)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+}
+// Ring of the backward kernel, per wave: slots 0-4 and 5-9 hold r, z, n, h_prev, dout of two steps (each loaded two steps before it is
+// used), slot 10 holds hn (one step ahead).  11 KiB x 8 waves = 88 KB beside the 72 KB image: the CU's 160 KB.
+constexpr int SBR_RING_SLOTS = 11;
+
 // ---- backward: the reverse recurrence of the same 16 rows ------------------------------------------------------------------------
 // dh_t = dout_t + dcarry;  (dr, dz, dn, dnr) from the saved gates;  dcarry' = dh z + [dr dz dnr] W_hh  (contraction over the 384 gate
 // columns).  Wave w owns the 16 output units 16 w .. of dcarry (A operand: the W_hh^T tile as 12 chunks x 3 pieces); the lanes' gate
@@ -148,8 +164,9 @@ __global__ __launch_bounds__(512) void k_gru_seq_bwd_sb(int T, int Bmax, SbGruBw
                 *__restrict__ w_hh = net.w_hh;
     float *__restrict__ dgi = net.dgi, *__restrict__ dgh = net.dgh, *__restrict__ dnr_out = net.dnr, *__restrict__ dh0 = net.dh0;
     float *__restrict__ bias_partials = net.db_ih ? (float *)net.workspace : nullptr;
-    extern __shared__ uint4 sbr_gimg[];                   // [buffer][piece][chunk 12][lane]: 2 x 36 KB
+    extern __shared__ uint4 sbr_lds[];                    // [ring: wave][slot][lane] 88 KB | [buffer][piece][chunk 12][lane]: 2 x 36 KB
     constexpr int IMG = 3 * 12 * 64;
+    uint4 *const sbr_gimg = sbr_lds + SBR_RING_SLOTS * 8 * 64;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 15, gq = l >> 4;
     const int b0 = blockIdx.x * SBR_RB;
     // A operand = W_hh^T: lane (unit i, octet gq) holds W_hh[32 c + 8 gq + s][16 w + i], s = 0 .. 7, for the 12 chunks c
@@ -168,23 +185,37 @@ __global__ __launch_bounds__(512) void k_gru_seq_bwd_sb(int T, int Bmax, SbGruBw
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 sb_r = zero4, sb_z = zero4, sb_n = zero4, sb_nr = zero4;
     float4 dcarry = zero4;
-    float4 pr, pz, pn, phn, php, pdo;   // one step ahead: none of them depends on the recurrence
-    auto prefetch = [&](int t) {
-        pr = pz = pn = phn = php = pdo = zero4;
-        if (live) {
-            const float4 *s4 = sv + (size_t)t * nblk * 4 * 512;
-            pr = s4[0]; pz = s4[512]; pn = s4[1024]; phn = s4[1536];
-            const size_t o = (size_t)(b0 + row) * SBR_H + u0;
-            php = *(const float4 *)(t > 0 ? out + (size_t)(t - 1) * B * SBR_H + o : h0 + o);
-            pdo = *(const float4 *)(dout + (size_t)t * B * SBR_H + o);
-        }
+    // The six per-lane inputs of a step reach the lane through its wave's ring (see SBR_RING_SLOTS): fetch(t, par) issues step t's
+    // LDS-direct loads, unconditionally -- rows past B re-load row b0 and steps before 0 re-load step 0, both zeroed after the
+    // read-back -- with hn first: it is the stream that is only one step ahead, so the wait that retires it leaves the five
+    // younger loads (and the step's stores) in flight.
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const uint32_t ring0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)sbr_lds + wu * SBR_RING_SLOTS * 1024;
+    const float4 *ring = (const float4 *)sbr_lds + wu * SBR_RING_SLOTS * 64 + l;
+    const size_t orow = (size_t)(live ? b0 + row : b0) * SBR_H + u0;
+    auto fetch_hn = [&](int t) { sbr_glds16(sv + (size_t)(t > 0 ? t : 0) * nblk * 4 * 512 + 1536, ring0 + 10 * 1024, true); };
+    auto fetch5 = [&](int t, int par) {
+        const int tc = t > 0 ? t : 0;
+        const float4 *s4 = sv + (size_t)tc * nblk * 4 * 512;
+        const uint32_t dst = ring0 + par * 5 * 1024;
+        sbr_glds16(s4, dst, false); sbr_glds16(s4 + 512, dst + 1024, false); sbr_glds16(s4 + 1024, dst + 2048, false);
+        sbr_glds16(tc > 0 ? out + (size_t)(tc - 1) * B * SBR_H + orow : h0 + orow, dst + 3072, false);
+        sbr_glds16(dout + (size_t)tc * B * SBR_H + orow, dst + 4096, false);
     };
-    prefetch(T - 1);
-    int buf = 0;
+    // the weight loads above are the compiler's own: retire them where it can see it, so that it never counts a wait of its own
+    // across the hand-counted loads below
+    __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0)
+    fetch_hn(T - 1); fetch5(T - 1, 0); fetch5(T - 2, 1);
+    asm volatile("s_waitcnt vmcnt(5)" ::: "memory");      // step T - 1 has landed; step T - 2's five stay in flight
+    int buf = 0, par = 0;
     for (int t = T - 1; t >= 0; t--) {
         float4 dr, dz, dn, dnr, dhz;
         {
-            const float4 r = pr, z = pz, n = pn, hn = phn, hp = php, dO = pdo;
+            float4 r = ring[(par * 5 + 0) * 64], z = ring[(par * 5 + 1) * 64], n = ring[(par * 5 + 2) * 64], hp = ring[(par * 5 + 3) * 64],
+                   dO = ring[(par * 5 + 4) * 64], hn = ring[10 * 64];
+            fetch_hn(t - 1);                              // opens with lgkmcnt(0): the slots are read before they are filled again
+            fetch5(t - 2, par);
+            if (!live) r = z = n = hp = dO = hn = zero4;
 #define SBR_ONE(f)                                               \
             {                                                    \
                 const float dh = dO.f + dcarry.f;                \
@@ -197,8 +228,8 @@ __global__ __launch_bounds__(512) void k_gru_seq_bwd_sb(int T, int Bmax, SbGruBw
             SBR_ONE(x) SBR_ONE(y) SBR_ONE(z) SBR_ONE(w)
 #undef SBR_ONE
         }
-        if (t > 0) prefetch(t - 1);
-        uint4 *gb = sbr_gimg + buf * IMG;   // dead rows carry zeros (their loads were skipped)
+        par ^= 1;
+        uint4 *gb = sbr_gimg + buf * IMG;   // dead rows carry zeros
         sbr_put4(gb, 12, u0, row, dr);
         sbr_put4(gb, 12, SBR_H + u0, row, dz);
         sbr_put4(gb, 12, 2 * SBR_H + u0, row, dnr);
@@ -232,7 +263,13 @@ __global__ __launch_bounds__(512) void k_gru_seq_bwd_sb(int T, int Bmax, SbGruBw
         const f32x4 s = (hi0 + hi1) + ((lo0 + lo1) + lo2);
         dcarry.x = dhz.x + s[0]; dcarry.y = dhz.y + s[1]; dcarry.z = dhz.z + s[2]; dcarry.w = dhz.w + s[3];
         buf ^= 1;   // the other image: its last readers passed this step's barrier before anyone writes it again
+        // The next step's inputs: everything up to this step's hn load.  After it the wave issued five loads and the step's stores
+        // (three of dgi, three of dgh or one of dnr; row 0 of a workgroup is live, so every wave issues them), and on gfx9 stores
+        // count in vmcnt beside the loads, in issue order.
+        if (dgh) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-direct load may land after the workgroup has left the CU
     if (live) *(float4 *)(dh0 + (size_t)(b0 + row) * SBR_H + u0) = dcarry;
     // bias gradients: sums over this workgroup's 16 rows (the lanes of a 16-lane group) and all steps
     if (bias_partials) {
@@ -266,7 +303,7 @@ __global__ void k_sbr_bias_reduce(int nblk, const float *partials, float *db_ih,
     }
 }
 
-constexpr int SBR_BWD_LDS = 2 * 3 * 12 * 64 * 16;
+constexpr int SBR_BWD_LDS = SBR_RING_SLOTS * 8 * 1024 + 2 * 3 * 12 * 64 * 16;   // ring + two images = 163 840 B
 
 inline int launch_gru_seq_bwd_sb(int n_nets, const mo_gru_seq_bwd_net *nets, int T, int B, int gi_agents, hipStream_t st) {
     static std::once_flag once;
