@@ -2397,6 +2397,7 @@ int launch_msgw3(const mo_msg_rel *rel, int R, int P, int E, const float *p, int
 }  // namespace
 
 #include "gauss_policy.hpp"   // the Gaussian policy head and loss of the env_3d trainer (reuses the helpers above)
+#include "value_norm.hpp"     // algo.use_value_norm: GAE on denormalised values, the running statistics and the normalised targets
 
 constexpr int SB_WGRAD_WGS = 256;  // one workgroup per CU (96 KB of LDS each)
 

@@ -23,6 +23,7 @@ import torch.nn.functional as F
 from torch.nn.utils import spectral_norm
 
 from . import ops
+from . import value_norm as vnorm
 from .e3d_env import ParticleEnv
 from .model import HeadLinear, _make_linear, _ortho_linear, _Trunk
 from .trainer import (GradBucket, ParticleRunState, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed,
@@ -118,6 +119,7 @@ class E3dMAPPO:
         if bool(a.get("use_reward_norm", False)):
             raise ValueError("algo.use_reward_norm: true is not supported on env_3d (runtime.env: e3d); set it to false")
         self.use_reward_scaling = bool(a.get("use_reward_scaling", False))   # the reference's RewardScaling in policy_record
+        self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
         self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
@@ -136,6 +138,7 @@ class E3dMAPPO:
         self.critic = E3dCritic(FEAT, self.embedding_dim, self.num_layers, self.rnn_hidden_dim, sn).to(self.device)
         self.ac_parameters = list(self.actor.parameters()) + list(self.critic.parameters())
         self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
+        self.value_norm = vnorm.ValueNorm(self.value_norm_beta, self.device) if self.use_value_norm else None
         rt = cfg.get("runtime", {})
         self.sample_seed = int(rt.get("seed", 0))
         self.sample_rank = int(rt.get("sample_rank", 0))   # Philox counter of rank r starts at r << 40 (as MAPPO)
@@ -180,8 +183,11 @@ class E3dMAPPO:
 
     def new_buffer(self, N, T, P):
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)
-        return dict(feat_a=z(N, T, P, FEAT), feat_c=z(N, T, P, FEAT), a_n=z(N, T, P, self.action_dim), a_logprob_n=z(N, T, P), r=z(N, T, P),
-                    active=z(N, T, P), v_n=z(N, T + 1, P))
+        buf = dict(feat_a=z(N, T, P, FEAT), feat_c=z(N, T, P, FEAT), a_n=z(N, T, P, self.action_dim), a_logprob_n=z(N, T, P), r=z(N, T, P),
+                   active=z(N, T, P), v_n=z(N, T + 1, P))
+        if self.value_norm is not None:
+            buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
+        return buf
 
     @torch.no_grad()
     def run_episode(self, env, buf=None, greedy=False):
@@ -218,6 +224,8 @@ class E3dMAPPO:
             env.policy_features(st.fa, st.fc)
             vmask = env.active_t.float() * (acc["ended"] == 0).float()[:, None]
             buf["v_n"][:, T].copy_(self._bootstrap_value(st) * vmask)
+            if self.value_norm is not None:   # the denormalisation of v_n[:, T] needs the mask itself: 0 std + mean is not 0
+                buf["v_mask"].copy_(vmask)
         return acc["ret"], acc["captured"] != 0, acc["length"]
 
     def explore_env(self, env):
@@ -251,7 +259,10 @@ class E3dMAPPO:
         gradient clipped to 5.0 after each (as MAPPO.train).  Returns (critic loss, actor loss) averaged over the mini-batches."""
         N, T, P = buf["r"].shape
         with torch.no_grad():
-            adv, v_target = ops.gae_advnorm(buf["r"], buf["v_n"], buf["active"], self.gamma, self.lamda, self.use_adv_norm)
+            if self.value_norm is not None:   # GAE on denormalised values, the state's step, the targets under the new statistics
+                adv, v_target = self.value_norm.gae_targets(buf, self.gamma, self.lamda, self.use_adv_norm)
+            else:
+                adv, v_target = ops.gae_advnorm(buf["r"], buf["v_n"], buf["active"], self.gamma, self.lamda, self.use_adv_norm)
         if self.grad_bucket is not None:
             self.grad_bucket.zero()
         else:
@@ -308,20 +319,25 @@ class E3dMAPPO:
 
     def save_model(self, cwd, best=False):
         """cwd/e3d_state_dicts.pt (best: e3d_state_dicts_best.pt), the actor's and critic's state_dicts (and, with a non-default
-        algo.gauss_std / gauss_squash, the "policy" entry of policy_meta)"""
+        algo.gauss_std / gauss_squash, the "policy" entry of policy_meta; with algo.use_value_norm the "value_norm" entry: beta and the state)"""
         os.makedirs(cwd, exist_ok=True)
         sd = {"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}
         if self.policy_ex:
             sd["policy"] = self.policy_meta()
+        if self.value_norm is not None:   # algo.use_value_norm: the critic's outputs mean nothing without the statistics
+            sd["value_norm"] = self.value_norm.entry()
         torch.save(sd, os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt"))
 
     def load_model(self, cwd, best=False):
-        """the weights save_model(cwd, best) wrote; ValueError when they belong to another gauss_std / gauss_squash"""
+        """the weights save_model(cwd, best) wrote; ValueError when they belong to another gauss_std / gauss_squash or algo.use_value_norm"""
         path = os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt")
         sd = torch.load(path, map_location=self.device)
         self.check_policy_meta(sd.get("policy"), path)
+        vnorm.check_entry(self, sd.get("value_norm"), path, check_beta=False)
         self.actor.load_state_dict(sd["actor"])
         self.critic.load_state_dict(sd["critic"])
+        if self.value_norm is not None:
+            self.value_norm.load_entry(sd["value_norm"])
 
 
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
@@ -352,6 +368,8 @@ class E3dTrainer(ParticleRunState):
         self.agent.sample_rank = self.rank
         self.bucket = GradBucket(self.agent.ac_parameters)
         self.agent.grad_bucket = self.bucket
+        if self.agent.value_norm is not None:
+            self.agent.value_norm.allreduce = allreduce_sum_   # (S1, S2, c) over ranks; without a process group a no-op
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
         self.eval_env = None

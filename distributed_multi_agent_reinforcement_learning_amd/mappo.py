@@ -205,6 +205,9 @@ class MAPPO:
         if bool(a.get("use_reward_scaling", False)):
             raise ValueError("algo.use_reward_scaling: true is built for runtime.env n2n and e3d only; the pursuit tick has "
                              "algo.use_reward_norm (set use_reward_scaling to false)")
+        if bool(a.get("use_value_norm", False)):
+            raise ValueError("algo.use_value_norm: true is built for runtime.env n2n and e3d only; the pursuit update is pinned to the "
+                             "reference's (set use_value_norm to false)")
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
         self.epsilon, self.K_epochs, self.entropy_coef = a.epsilon, a.epochs, a.entropy_coef
         self.use_grad_clip, self.use_lr_decay = a.use_grad_clip, a.use_lr_decay

@@ -16,6 +16,7 @@ import time
 import torch
 
 from . import ops
+from . import value_norm as vnorm
 from .model import build_actor_critic, sequence_forward_pair
 from .n2n_env import ParticleEnv
 from .trainer import (GradBucket, ParticleRunState, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed,
@@ -63,6 +64,7 @@ class N2nMAPPO:
         if bool(a.get("use_reward_norm", False)):
             raise ValueError("algo.use_reward_norm: true is not supported on env_n2n (runtime.env: n2n); set it to false")
         self.use_reward_scaling = bool(a.get("use_reward_scaling", False))   # the reference's RewardScaling in policy_record
+        self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
         if int(cfg.env.num_defender) > MAX_P:
             raise ValueError(f"env.num_defender={cfg.env.num_defender}: the DHGN message kernels take at most {MAX_P} pursuers per row")
         if int(cfg.env.state_dim) != 4 or int(cfg.env.action_dim) != 9 or int(a.num_relation) != 3:
@@ -87,6 +89,7 @@ class N2nMAPPO:
         self.ac_parameters = (list(enc.parameters()) + list(self.actor.GRU.parameters()) + list(self.critic.GRU.parameters())
                               + list(self.critic.Mean.parameters()) + list(self.actor.Mean.parameters()))
         self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
+        self.value_norm = vnorm.ValueNorm(self.value_norm_beta, self.device) if self.use_value_norm else None
         rt = cfg.get("runtime", {})
         self.sample_seed = int(rt.get("seed", 0))
         self.sample_rank = int(rt.get("sample_rank", 0))   # Philox counter of rank r starts at r << 40 (as MAPPO)
@@ -129,9 +132,12 @@ class N2nMAPPO:
     def new_buffer(self, N, T, P, E):
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)
         d, Em = self.depth, self.embedding_dim
-        return dict(p_state=z(N, T, P, 4), e_state=z(N, T, E, 4), e_ref=z(N, T, 4), p_adj=z(N, T, P, P), e_adj=z(N, T, P, E),
-                    actor_historical_embedding=z(N, T + d, P, Em), critic_historical_embedding=z(N, T + d, P, Em),
-                    a_n=z(N, T, P), a_logprob_n=z(N, T, P), r=z(N, T, P), active=z(N, T, P), v_n=z(N, T + 1, P))
+        buf = dict(p_state=z(N, T, P, 4), e_state=z(N, T, E, 4), e_ref=z(N, T, 4), p_adj=z(N, T, P, P), e_adj=z(N, T, P, E),
+                   actor_historical_embedding=z(N, T + d, P, Em), critic_historical_embedding=z(N, T + d, P, Em),
+                   a_n=z(N, T, P), a_logprob_n=z(N, T, P), r=z(N, T, P), active=z(N, T, P), v_n=z(N, T + 1, P))
+        if self.value_norm is not None:
+            buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
+        return buf
 
     @torch.no_grad()
     def run_episode(self, env, buf=None, greedy=False):
@@ -169,6 +175,8 @@ class N2nMAPPO:
             env.policy_inputs(st.p4, st.e4, st.e_ref, st.live, st.pp, st.pe, None)
             vmask = env.active_t.float() * (acc["ended"] == 0).float()[:, None]
             buf["v_n"][:, T].copy_(self._bootstrap_value(st) * vmask)
+            if self.value_norm is not None:   # the denormalisation of v_n[:, T] needs the mask itself: 0 std + mean is not 0
+                buf["v_mask"].copy_(vmask)
         return acc
 
     def explore_env(self, env):
@@ -205,7 +213,10 @@ class N2nMAPPO:
         gradient clipped to 5.0 after each (as MAPPO.train).  Returns (critic loss, actor loss) averaged over the mini-batches."""
         N = buf["r"].shape[0]
         with torch.no_grad():
-            adv, v_target = ops.gae_advnorm(buf["r"], buf["v_n"], buf["active"], self.gamma, self.lamda, self.use_adv_norm)
+            if self.value_norm is not None:   # GAE on denormalised values, the state's step, the targets under the new statistics
+                adv, v_target = self.value_norm.gae_targets(buf, self.gamma, self.lamda, self.use_adv_norm)
+            else:
+                adv, v_target = ops.gae_advnorm(buf["r"], buf["v_n"], buf["active"], self.gamma, self.lamda, self.use_adv_norm)
         if self.grad_bucket is not None:
             self.grad_bucket.zero()
         else:
@@ -235,17 +246,28 @@ class N2nMAPPO:
         self.total_step = total_steps
 
     def save_model(self, cwd, best=False):
-        """cwd/n2n_actor.pth and n2n_critic.pth (best: n2n_actor_best.pth, n2n_critic_best.pth), the two state_dicts"""
+        """cwd/n2n_actor.pth and n2n_critic.pth (best: n2n_actor_best.pth, n2n_critic_best.pth), the two state_dicts; with
+        algo.use_value_norm the sibling n2n_value_norm.pth (n2n_value_norm_best.pth): beta and the state"""
         os.makedirs(cwd, exist_ok=True)
         sfx = "_best" if best else ""
         torch.save(self.actor.state_dict(), os.path.join(cwd, f"n2n_actor{sfx}.pth"))
         torch.save(self.critic.state_dict(), os.path.join(cwd, f"n2n_critic{sfx}.pth"))
+        vn_path = os.path.join(cwd, f"n2n_value_norm{sfx}.pth")
+        if self.value_norm is not None:
+            torch.save(self.value_norm.entry(), vn_path)
+        elif os.path.exists(vn_path):   # a file of an earlier option-on run in the same directory does not belong to these weights
+            os.remove(vn_path)
 
     def load_model(self, cwd, best=False):
-        """the weights save_model(cwd, best) wrote"""
+        """the weights save_model(cwd, best) wrote; ValueError when they belong to the other algo.use_value_norm"""
         sfx = "_best" if best else ""
+        vn_path = os.path.join(cwd, f"n2n_value_norm{sfx}.pth")
+        entry = torch.load(vn_path, map_location="cpu") if os.path.exists(vn_path) else None
+        vnorm.check_entry(self, entry, os.path.join(cwd, f"n2n_critic{sfx}.pth"), check_beta=False)
         self.actor.load_state_dict(torch.load(os.path.join(cwd, f"n2n_actor{sfx}.pth"), map_location=self.device))
         self.critic.load_state_dict(torch.load(os.path.join(cwd, f"n2n_critic{sfx}.pth"), map_location=self.device))
+        if self.value_norm is not None:
+            self.value_norm.load_entry(entry)
 
 
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
@@ -276,6 +298,8 @@ class N2nTrainer(ParticleRunState):
         self.agent.sample_rank = self.rank
         self.bucket = GradBucket(self.agent.ac_parameters)
         self.agent.grad_bucket = self.bucket
+        if self.agent.value_norm is not None:
+            self.agent.value_norm.allreduce = allreduce_sum_   # (S1, S2, c) over ranks; without a process group a no-op
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
         self.eval_env = None

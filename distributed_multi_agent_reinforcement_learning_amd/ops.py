@@ -17,7 +17,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "categorical_sample_counter",
            "gru_gates_fwd", "gru_gates_bwd", "gru_cell_fwd", "gru_cell_fwd_multi", "gru_cell_split_fwd_multi", "sb_gemm_n128", "sb_gemm", "gru_seq_fwd", "gru_seq_fwd_multi", "gru_seq_split_fwd_multi", "gru_seq_split_bwd_multi", "gru_seq_save_elems", "gru_seq_bwd", "gru_seq_bwd_multi", "gru_seq_bwd_workspace", "wgrad_tn", "wgrad_tn_workspace", "wgrad_split_tn", "wgrad_split_tn2", "wgrad_split_workspace", "rollout_record", "ppo_loss_fwd_bwd", "ppo_loss_prob_fwd_bwd", "ppo_loss_workspace",
            "gauss_head_sample", "ppo_loss_gauss_fwd_bwd", "ppo_loss_gauss_workspace", "gauss_head_sample_ex", "ppo_loss_gauss_ex_fwd_bwd",
-           "ppo_loss_gauss_ex_workspace", "mappo_ops_error_string")
+           "ppo_loss_gauss_ex_workspace", "gae_advnorm_vn", "gae_advnorm_vn_workspace", "value_norm_update", "value_norm_targets",
+           "mappo_ops_error_string")
 
 _lib = None
 
@@ -52,6 +53,10 @@ def load_library():
         L.dhgn_msg_agg_ones_sorted_bwd.argtypes = [i32, i32, i32, i32, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp]
         L.gae_advnorm.argtypes = [i32, i32, i32, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp]
         L.gae_advnorm_workspace.restype = i64
+        L.gae_advnorm_vn.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp]
+        L.gae_advnorm_vn_workspace.restype = i64
+        L.value_norm_update.argtypes = [vp, vp, C.c_double, vp]
+        L.value_norm_targets.argtypes = [i64, vp, vp, vp, vp, vp]
         L.categorical_sample.argtypes = [i32, i32, vp, C.c_uint64, C.c_uint64, i32, vp, vp, vp]
         L.categorical_sample_counter.argtypes = [i32, i32, vp, C.c_uint64, vp, i32, vp, vp, vp]
         L.head_linear.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
@@ -518,6 +523,65 @@ def gae_advnorm(r, v, active, gamma, lamda, use_adv_norm=True):
     _check(L.gae_advnorm(N, T, P, _ptr(r), _ptr(v), _ptr(active), float(gamma), float(lamda), 1 if use_adv_norm else 0,
                          _ptr(adv), _ptr(v_target), _ptr(stats), _stream()), "gae_advnorm")
     return adv, v_target
+
+
+# launches of the value-normalisation ops since import (tests: a run with algo.use_value_norm off leaves them at 0)
+value_norm_calls = {"gae_advnorm_vn": 0, "value_norm_update": 0, "value_norm_targets": 0}
+
+
+def value_norm_state(device):
+    """the state of algo.use_value_norm: (m, q, d) f64 on the device, all 0 (the identity: mean 0, std 1)"""
+    return torch.zeros(3, dtype=torch.float64, device=device)
+
+
+def _vn_state_ok(state):
+    assert state.dtype == torch.float64 and state.shape == (3,) and state.is_contiguous() and state.is_cuda
+
+
+def gae_advnorm_vn(r, v, active, vmask, state, gamma, lamda, use_adv_norm=True):
+    """gae_advnorm on the denormalised values v std + mean under `state` (value_norm_state), v[:, t] masked by active[:, t] and
+    v[:, T] by vmask (N, P): a masked value stays exactly 0.  -> (adv, v_target, sums); sums = (S1, S2, c) f64 on the device, the sum,
+    sum of squares and count of v_target over the live rows.  With the identity state adv and v_target are gae_advnorm's bits."""
+    L = load_library()
+    _need_gpu(r, "gae_advnorm_vn")
+    N, T, P = r.shape
+    assert v.shape == (N, T + 1, P) and active.shape == r.shape and vmask.shape == (N, P)
+    assert r.dtype == v.dtype == active.dtype == vmask.dtype == torch.float32
+    _vn_state_ok(state)
+    r, v, active, vmask = r.contiguous(), v.contiguous(), active.contiguous(), vmask.contiguous()
+    adv = torch.empty_like(r)
+    v_target = torch.empty_like(r)
+    stats = torch.empty(L.gae_advnorm_vn_workspace() // 8, dtype=torch.float64, device=r.device)
+    sums = torch.empty(3, dtype=torch.float64, device=r.device)
+    value_norm_calls["gae_advnorm_vn"] += 1
+    _check(L.gae_advnorm_vn(N, T, P, _ptr(r), _ptr(v), _ptr(active), _ptr(vmask), _ptr(state), float(gamma), float(lamda),
+                            1 if use_adv_norm else 0, _ptr(adv), _ptr(v_target), _ptr(stats), _ptr(sums), _stream()), "gae_advnorm_vn")
+    return adv, v_target, sums
+
+
+def value_norm_update(state, sums, beta):
+    """the moving-average step of `state` from sums = (S1, S2, c) (gae_advnorm_vn's, possibly summed over ranks), in place:
+    m = beta m + (1 - beta) S1 / c, q likewise with S2, d = beta d + (1 - beta); c == 0 changes nothing"""
+    L = load_library()
+    _need_gpu(state, "value_norm_update")
+    _vn_state_ok(state)
+    assert sums.dtype == torch.float64 and sums.shape == (3,) and sums.is_contiguous() and sums.is_cuda
+    value_norm_calls["value_norm_update"] += 1
+    _check(L.value_norm_update(_ptr(state), _ptr(sums), float(beta), _stream()), "value_norm_update")
+    return state
+
+
+def value_norm_targets(v_target, active, state):
+    """(v_target - mean) / std under `state` where active != 0, exactly 0 elsewhere: what the critic loss regresses on"""
+    L = load_library()
+    _need_gpu(v_target, "value_norm_targets")
+    assert active.shape == v_target.shape and v_target.dtype == active.dtype == torch.float32
+    _vn_state_ok(state)
+    v_target, active = v_target.contiguous(), active.contiguous()
+    out = torch.empty_like(v_target)
+    value_norm_calls["value_norm_targets"] += 1
+    _check(L.value_norm_targets(v_target.numel(), _ptr(v_target), _ptr(active), _ptr(state), _ptr(out), _stream()), "value_norm_targets")
+    return out
 
 
 def categorical_sample(probs, seed, offset, greedy=False, counter=None, out=None):

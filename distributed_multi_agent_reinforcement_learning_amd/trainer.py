@@ -16,6 +16,7 @@ import torch.distributed as dist
 from .evaluator import EvaluatorProc, draw_learning_curve
 from .mappo import MAPPO
 from .pursuit_env import Pursuit_Env
+from .value_norm import check_entry as check_value_norm_entry
 
 
 TUNED_GEMM_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tunableop_gfx950.csv")
@@ -150,7 +151,8 @@ class ParticleRunState:
     counter; save_model / load_model), total_steps, iteration, num_envs, world, rank, device, eval_return_std, recorder and
     best_eval_return.  Every environment episode starts from a reset and every rollout from zero GRU states and history, so the
     reset generators, the sampling counters, the weights and Adam are all the state a run carries from one iteration to the next --
-    and, with algo.use_reward_scaling, the training environment's reward_scale (the bundle's "reward_scaling" entry)."""
+    and, with algo.use_reward_scaling, the training environment's reward_scale (the bundle's "reward_scaling" entry), with
+    algo.use_value_norm the agent's value-normaliser state (the "value_norm" entry)."""
 
     def save_resume(self, path):
         agent, ev = self.agent, self.eval_env
@@ -166,6 +168,8 @@ class ParticleRunState:
             bundle["policy"] = meta
         if getattr(agent, "use_reward_scaling", False):   # algo.use_reward_scaling: n, mean, S (and R) of every environment; off: no entry
             bundle["reward_scaling"] = self.env.reward_scale.cpu()
+        if getattr(agent, "value_norm", None) is not None:   # algo.use_value_norm: beta and the state (m, q, d); off: no entry
+            bundle["value_norm"] = agent.value_norm.entry()
         torch.save(bundle, path)
 
     def load_resume(self, path):
@@ -180,9 +184,12 @@ class ParticleRunState:
         if theirs != mine:
             raise ValueError(f"resume bundle {path} was written with algo.use_reward_scaling: {str(theirs).lower()}, "
                              f"this agent has algo.use_reward_scaling: {str(mine).lower()}")
+        check_value_norm_entry(agent, b.get("value_norm"), f"resume bundle {path}")
         agent.actor.load_state_dict(b["actor"])
         agent.critic.load_state_dict(b["critic"])
         agent.ac_optimizer.load_state_dict(b["optimizer"])
+        if agent.value_norm is not None:
+            agent.value_norm.load_entry(b["value_norm"])
         self.total_steps, self.iteration = b["total_steps"], b["iteration"]
         if agent.use_lr_decay:
             agent.lr_decay(self.total_steps)

@@ -136,6 +136,26 @@ int gae_advnorm(int32_t N, int32_t T, int32_t P, const float *r, const float *v,
                 float lamda, int32_t use_adv_norm, float *adv, float *v_target, double *stats, void *stream);
 
 /*
+ * Value normalisation of the env_3d / env_n2n trainers (algo.use_value_norm; csrc/value_norm.hpp, tests/value_norm_ref.py).
+ * vn_state: 3 f64 on the device, (m, q, d), all 0 at the start.  d == 0: mean 0, std 1; else mean = m / d and
+ * std = sqrt(max(q / d - mean^2, 1e-2)).  The state never visits the host.
+ *
+ * gae_advnorm_vn: gae_advnorm on the denormalised values v std + mean, where v[:, t] of t < T is masked by active[:, t] and
+ *   v[:, T] by vmask [N][P] (a masked value is exactly 0, not the mean).  With d == 0 adv and v_target are gae_advnorm's bits.
+ *   sums (3 f64, device) <- S1 = sum y, S2 = sum y^2, c = the count over the live rows (active != 0) of the fp32 v_target, f64
+ *   through per-workgroup partials added in index order (no atomics).  stats: gae_advnorm_vn_workspace() bytes, as gae_advnorm's.
+ * value_norm_update: m = beta m + (1 - beta) (S1 / c), q likewise with S2, d = beta d + (1 - beta); nothing when c == 0.
+ *   sums may have been summed over ranks.  0 < beta < 1.
+ * value_norm_targets: out[i] = (v_target[i] - mean) / std where active[i] != 0, else 0; n elements, pointers 16-byte aligned.
+ */
+int64_t gae_advnorm_vn_workspace(void);
+int gae_advnorm_vn(int32_t N, int32_t T, int32_t P, const float *r, const float *v, const float *active, const float *vmask,
+                   const double *vn_state, float gamma, float lamda, int32_t use_adv_norm, float *adv, float *v_target, double *stats,
+                   double *sums, void *stream);
+int value_norm_update(double *vn_state, const double *sums, double beta, void *stream);
+int value_norm_targets(int64_t n, const float *v_target, const float *active, const double *vn_state, float *out, void *stream);
+
+/*
  * Categorical(probs).sample() + log_prob for a batch of rows (DHGN/mappo_parallel.py:446-448) with a counter-based
  * generator (Philox4x32-10; stream = (seed, offset + row)): probs [R][A] -> action [R] int32, logp [R].
  * greedy != 0 gives probs.argmax(-1) instead (choose_action(deterministic=True), :442-444; first maximum wins).
