@@ -19,6 +19,7 @@
 
 #include "e3d_env.h"
 #include "reward_scale.hpp"
+#include "reward_shaping.hpp"
 #include "rng_replica.hpp"
 #include "slsqp_box.hpp"
 
@@ -317,15 +318,23 @@ __global__ __launch_bounds__(256) void k_e3d_features(const e3d_config c, const 
     }
 }
 
+// the shaping potential of pursuer a of environment env in the current records (p_on, e_on: their active flags)
+__device__ __forceinline__ double e3d_potential(const e3d_state &st, int env, int P, int a, bool p_on, bool e_on, double coef) {
+    const double *gp = st.p + (size_t)env * 7 * P + a, *ge = st.e + (size_t)env * 7;
+    return rshape::potential(coef, p_on, e_on, rshape::dist3(gp[0] - ge[0], gp[P] - ge[1], gp[2 * P] - ge[2]));
+}
+
 // MAPPO bookkeeping of one tick (include/e3d_env.h e3d_policy_record): the tick's lane layout, lane = (environment, pursuer).  Every lane
 // masks its own buffer entries; the group's flags (pursuers left, evader dead, evader at the target) come from the records after the
 // tick, the team reward from shuffles in agent order; slot 0 writes the accumulators after every lane of the group has read them (one
 // wave, program order).  SCALED: the reward row is the reference's RewardScaling of the raw reward (csrc/reward_scale.hpp); the state
-// rs [N][1 + 3P] is read and written once per lane, n by slot 0.
-template <int PT, bool SCALED>
+// rs [N][1 + 3P] is read and written once per lane, n by slot 0.  SHAPED: potential-based distance shaping (csrc/reward_shaping.hpp) goes
+// into the reward row -- and into RewardScaling when SCALED -- once the terminal predicate of v_next is known; every lane loads and
+// stores its own phi [N][P] entry once.  The unshaped instantiations are the code they were before SHAPED existed.
+template <int PT, bool SCALED, bool SHAPED>
 __global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_config c, const e3d_state st, const float *reward, const uint8_t *done,
                                                                   const e3d_record_io io, const e3d_policy_acc acc, const double kill,
-                                                                  double *rs, const double gamma) {
+                                                                  double *rs, const double gamma, double *phi, const double coef) {
     constexpr int G = WAVE / PT;
     constexpr unsigned long long GM = (PT == 64) ? ~0ull : ((1ull << PT) - 1ull);
     const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
@@ -337,7 +346,7 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_conf
     const float rl = raw * live;
     const bool db = ev && acc.done_before[env] != 0;
     float rb = rl;  // the buffer's reward
-    if (SCALED && pv && !db) {
+    if (SCALED && !SHAPED && pv && !db) {
         double *q = rs + (size_t)env * (1 + 3 * P);
         const double n = q[0] + 1.0;
         double mean = q[1 + a], S = q[1 + P + a], R = q[1 + 2 * P + a];
@@ -346,7 +355,7 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_conf
         if (a == 0) q[0] = n;
     }
     if (pv) {
-        if (io.r) io.r[(int64_t)env * io.r_rs + a] = rb;
+        if (!SHAPED && io.r) io.r[(int64_t)env * io.r_rs + a] = rb;
         if (io.active) io.active[(int64_t)env * io.active_rs + a] = live;
         if (io.v) io.v[(int64_t)env * io.v_rs + a] = io.value[(int64_t)env * io.value_rs + a] * live;
     }
@@ -363,6 +372,24 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_conf
     for (int k = 0; k < P; k++) s += __shfl(rl, base + k);
     const bool ended = ev && (acc.ended[env] != 0 || ((reach || pa == 0 || e_dead) && !db));
     const bool dn = ev && (db || done[env] != 0);
+    if (SHAPED && pv) {
+        if (!db) {
+            double ph = phi[(size_t)env * P + a];
+            const double x = rshape::step((double)raw, gamma, ph, e3d_potential(st, env, P, a, p_on, !e_dead, coef), !p_on || ended, (double)live);
+            phi[(size_t)env * P + a] = ph;
+            if (SCALED) {
+                double *q = rs + (size_t)env * (1 + 3 * P);
+                const double n = q[0] + 1.0;
+                double mean = q[1 + a], S = q[1 + P + a], R = q[1 + 2 * P + a];
+                rb = (float)rscale::step(x, gamma, n, mean, S, R) * live;
+                q[1 + a] = mean; q[1 + P + a] = S; q[1 + 2 * P + a] = R;
+                if (a == 0) q[0] = n;
+            } else {
+                rb = (float)x * live;
+            }
+        }
+        if (io.r) io.r[(int64_t)env * io.r_rs + a] = rb;
+    }
     if (pv) {
         if (io.v_next && (!p_on || ended)) io.v_next[(int64_t)env * io.v_next_rs + a] = 0.f;
         if (io.live_next) io.live_next[(int64_t)env * io.live_next_rs + a] = (p_on && !dn) ? 1.f : 0.f;
@@ -376,13 +403,25 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_conf
     }
 }
 
-template <bool SCALED>
+// phi [N][P] = the shaping potential of the current records (e3d_shaping_begin): the tick's lane layout, one store per lane
+template <int PT>
+__global__ __launch_bounds__(WAVE * WPB) void k_e3d_shaping_begin(const e3d_config c, const e3d_state st, double *phi, const double coef) {
+    constexpr int G = WAVE / PT;
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT;
+    const int env = wave * G + g, P = c.P;
+    if (env >= st.N || a >= P) return;
+    const bool p_on = st.p[(size_t)env * 7 * P + 6 * P + a] != 0.0, e_on = st.e[(size_t)env * 7 + 6] != 0.0;
+    phi[(size_t)env * P + a] = e3d_potential(st, env, P, a, p_on, e_on, coef);
+}
+
+template <bool SCALED, bool SHAPED>
 int e3d_record_launch(const e3d_config *c, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io &io,
-                      const e3d_policy_acc &acc, double *rs, double gamma, hipStream_t s) {
+                      const e3d_policy_acc &acc, double *rs, double gamma, double *phi, double coef, hipStream_t s) {
     const int pt = c->P <= 8 ? 8 : (c->P <= 16 ? 16 : (c->P <= 32 ? 32 : 64));
     const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
     const double kill = sq_threshold(c->kill_radius);
-#define E3D_REC(PT) hipLaunchKernelGGL((k_e3d_policy_record<PT, SCALED>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, reward, done, io, acc, kill, rs, gamma)
+#define E3D_REC(PT) hipLaunchKernelGGL((k_e3d_policy_record<PT, SCALED, SHAPED>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, reward, done, io, acc, kill, rs, gamma, phi, coef)
     if (pt == 8) E3D_REC(8); else if (pt == 16) E3D_REC(16); else if (pt == 32) E3D_REC(32); else E3D_REC(64);
 #undef E3D_REC
     return (int)hipGetLastError();
@@ -454,8 +493,33 @@ int e3d_policy_record(const e3d_config *cfg, const e3d_state *st, const float *r
     const int rc = e3d_config_check(cfg);
     if (rc) return rc;
     if (st->N < 1) return 0;
-    if (rs) return e3d_record_launch<true>(cfg, st, reward, done, *io, *acc, rs, gamma, (hipStream_t)stream);
-    return e3d_record_launch<false>(cfg, st, reward, done, *io, *acc, nullptr, 0.0, (hipStream_t)stream);
+    if (rs) return e3d_record_launch<true, false>(cfg, st, reward, done, *io, *acc, rs, gamma, nullptr, 0.0, (hipStream_t)stream);
+    return e3d_record_launch<false, false>(cfg, st, reward, done, *io, *acc, nullptr, 0.0, nullptr, 0.0, (hipStream_t)stream);
+}
+
+int e3d_policy_record_shaped(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
+                             const e3d_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream) {
+    if (!cfg || !st || !reward || !done || !io || !acc || !phi || !io->live || (io->v && !io->value)) return E3D_ERR_NULL;
+    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (st->N < 1) return 0;
+    if (rs) return e3d_record_launch<true, true>(cfg, st, reward, done, *io, *acc, rs, gamma, phi, coef, (hipStream_t)stream);
+    return e3d_record_launch<false, true>(cfg, st, reward, done, *io, *acc, nullptr, gamma, phi, coef, (hipStream_t)stream);
+}
+
+int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, double coef, void *stream) {
+    if (!cfg || !st || !phi) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (st->N < 1) return 0;
+    const int pt = cfg->P <= 8 ? 8 : (cfg->P <= 16 ? 16 : (cfg->P <= 32 ? 32 : 64));
+    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    hipStream_t s = (hipStream_t)stream;
+#define E3D_SB(PT) hipLaunchKernelGGL((k_e3d_shaping_begin<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, phi, coef)
+    if (pt == 8) E3D_SB(8); else if (pt == 16) E3D_SB(16); else if (pt == 32) E3D_SB(32); else E3D_SB(64);
+#undef E3D_SB
+    return (int)hipGetLastError();
 }
 
 int e3d_evader_slsqp(const e3d_config *cfg, const e3d_state *st, double *e_cmd, void *stream) {

@@ -15,6 +15,7 @@
 
 #include "n2n_env.h"
 #include "reward_scale.hpp"
+#include "reward_shaping.hpp"
 #include "rng_replica.hpp"
 #include "slsqp_box.hpp"
 
@@ -224,13 +225,30 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_inputs(const n2n_conf
         }
 }
 
+// the shaping potential of pursuer a in the current records gp / ge of its environment (p_on: its active flag): the nearest active evader
+__device__ __forceinline__ double n2n_potential(const double *gp, const double *ge, int P, int E, int a, bool p_on, double coef) {
+    const double px = gp[a], py = gp[P + a];
+    double dmin = 0.0;
+    bool any = false;
+    for (int k = 0; k < E; k++) {
+        if (ge[4 * E + k] == 0.0) continue;
+        const double d = rshape::dist2(px - ge[k], py - ge[E + k]);
+        dmin = (any && dmin < d) ? dmin : d;
+        any = true;
+    }
+    return rshape::potential(coef, p_on, any, dmin);
+}
+
 // SCALED: the reward row is the reference's RewardScaling of the raw reward (csrc/reward_scale.hpp) for environments not done before
 // the step; rs [N][1 + 3P] (n, mean[P], S[P], R[P]) is read and written once per lane, n by slot 0 after every lane of the group has
-// loaded it (one wave, program order).  The return accumulator keeps the raw reward.
-template <int PT, bool SCALED>
+// loaded it (one wave, program order).  The return accumulator keeps the raw reward.  SHAPED: potential-based distance shaping
+// (csrc/reward_shaping.hpp) goes into the reward row -- and into RewardScaling when SCALED -- once the terminal predicate of v_next is
+// known; every lane loads and stores its own phi [N][P] entry once and walks the E evaders itself.  The unshaped instantiations are the
+// code they were before SHAPED existed.
+template <int PT, bool SCALED, bool SHAPED>
 __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_config c, const n2n_state st, const float *reward, const uint8_t *done,
                                                                   const n2n_record_io io, const n2n_policy_acc acc, const double kill,
-                                                                  double *rs, const double gamma) {
+                                                                  double *rs, const double gamma, double *phi, const double coef) {
     constexpr int G = WAVE / PT;
     const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
     const int g = lane / PT, a = lane - g * PT, base = lane - a;
@@ -241,7 +259,7 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_conf
     const float raw = pv ? reward[(size_t)env * P + a] : 0.f;
     const float rl = raw * live;
     float rb = rl;  // the buffer's reward
-    if (SCALED && pv && acc.done_before[env] == 0) {
+    if (SCALED && !SHAPED && pv && acc.done_before[env] == 0) {
         double *q = rs + (size_t)env * (1 + 3 * P);
         const double n = q[0] + 1.0;
         double mean = q[1 + a], S = q[1 + P + a], R = q[1 + 2 * P + a];
@@ -250,7 +268,7 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_conf
         if (a == 0) q[0] = n;
     }
     if (pv) {
-        if (io.r) io.r[(int64_t)env * io.r_rs + a] = rb;
+        if (!SHAPED && io.r) io.r[(int64_t)env * io.r_rs + a] = rb;
         if (io.active) io.active[(int64_t)env * io.active_rs + a] = live;
         if (io.v) io.v[(int64_t)env * io.v_rs + a] = io.value[(int64_t)env * io.value_rs + a] * live;
     }
@@ -265,6 +283,24 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_conf
     for (int k = 0; k < P; k++) s += __shfl(rl, base + k);
     const bool db = ev && acc.done_before[env] != 0;
     const bool ended = ev && (acc.ended[env] != 0 || ((rc || pa == 0 || ea == 0) && !db));
+    if (SHAPED && pv) {
+        if (!db) {
+            double ph = phi[(size_t)env * P + a];
+            const double x = rshape::step((double)raw, gamma, ph, n2n_potential(gp, ge, P, E, a, p_on, coef), !p_on || ended, (double)live);
+            phi[(size_t)env * P + a] = ph;
+            if (SCALED) {
+                double *q = rs + (size_t)env * (1 + 3 * P);
+                const double n = q[0] + 1.0;
+                double mean = q[1 + a], S = q[1 + P + a], R = q[1 + 2 * P + a];
+                rb = (float)rscale::step(x, gamma, n, mean, S, R) * live;
+                q[1 + a] = mean; q[1 + P + a] = S; q[1 + 2 * P + a] = R;
+                if (a == 0) q[0] = n;
+            } else {
+                rb = (float)x * live;
+            }
+        }
+        if (io.r) io.r[(int64_t)env * io.r_rs + a] = rb;
+    }
     if (pv && io.v_next && (!p_on || ended)) io.v_next[(int64_t)env * io.v_next_rs + a] = 0.f;
     if (ev && a == 0) {
         acc.ended[env] = ended;
@@ -395,11 +431,23 @@ void sample_points(rngrep::NpRandom &g, int n, double lx, double ly, double lo, 
     }
 }
 
-// n2n_policy_record / n2n_policy_record_scaled: one launch, the tick's lane layout
-template <bool SCALED>
+// phi [N][P] = the shaping potential of the current records (n2n_shaping_begin): the tick's lane layout, one store per lane
+template <int PT>
+__global__ __launch_bounds__(WAVE * WPB) void k_n2n_shaping_begin(const n2n_config c, const n2n_state st, double *phi, const double coef) {
+    constexpr int G = WAVE / PT;
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT;
+    const int env = wave * G + g, P = c.P, E = c.E;
+    if (env >= st.N || a >= P) return;
+    const double *gp = st.p + (size_t)env * 5 * P, *ge = st.e + (size_t)env * 5 * E;
+    phi[(size_t)env * P + a] = n2n_potential(gp, ge, P, E, a, gp[4 * P + a] != 0.0, coef);
+}
+
+// n2n_policy_record / n2n_policy_record_scaled / n2n_policy_record_shaped: one launch, the tick's lane layout
+template <bool SCALED, bool SHAPED>
 int n2n_record_launch(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                      const n2n_policy_acc *acc, double *rs, double gamma, void *stream) {
-    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value) || (SCALED && !rs)) return N2N_ERR_NULL;
+                      const n2n_policy_acc *acc, double *rs, double gamma, double *phi, double coef, void *stream) {
+    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value) || (SCALED && !rs) || (SHAPED && !phi)) return N2N_ERR_NULL;
     if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return N2N_ERR_NULL;
     const int rc = n2n_config_check(cfg);
     if (rc) return rc;
@@ -408,7 +456,7 @@ int n2n_record_launch(const n2n_config *cfg, const n2n_state *st, const float *r
     const int pt = n2n_lanes(cfg, st->N, &blocks);
     const double kill = sq_threshold(cfg->kill_radius);
     hipStream_t s = (hipStream_t)stream;
-#define N2N_REC(PT) hipLaunchKernelGGL((k_n2n_policy_record<PT, SCALED>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, reward, done, *io, *acc, kill, rs, gamma)
+#define N2N_REC(PT) hipLaunchKernelGGL((k_n2n_policy_record<PT, SCALED, SHAPED>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, reward, done, *io, *acc, kill, rs, gamma, phi, coef)
     if (pt == 8) N2N_REC(8); else if (pt == 16) N2N_REC(16); else if (pt == 32) N2N_REC(32); else N2N_REC(64);
 #undef N2N_REC
     return (int)hipGetLastError();
@@ -499,12 +547,32 @@ int n2n_policy_inputs(const n2n_config *cfg, const n2n_state *st, const uint8_t 
 
 int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
                       const n2n_policy_acc *acc, void *stream) {
-    return n2n_record_launch<false>(cfg, st, reward, done, io, acc, nullptr, 0.0, stream);
+    return n2n_record_launch<false, false>(cfg, st, reward, done, io, acc, nullptr, 0.0, nullptr, 0.0, stream);
 }
 
 int n2n_policy_record_scaled(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
                              const n2n_policy_acc *acc, double *rs, double gamma, void *stream) {
-    return n2n_record_launch<true>(cfg, st, reward, done, io, acc, rs, gamma, stream);
+    return n2n_record_launch<true, false>(cfg, st, reward, done, io, acc, rs, gamma, nullptr, 0.0, stream);
+}
+
+int n2n_policy_record_shaped(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
+                             const n2n_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream) {
+    if (rs) return n2n_record_launch<true, true>(cfg, st, reward, done, io, acc, rs, gamma, phi, coef, stream);
+    return n2n_record_launch<false, true>(cfg, st, reward, done, io, acc, nullptr, gamma, phi, coef, stream);
+}
+
+int n2n_shaping_begin(const n2n_config *cfg, const n2n_state *st, double *phi, double coef, void *stream) {
+    if (!cfg || !st || !phi) return N2N_ERR_NULL;
+    const int rc = n2n_config_check(cfg);
+    if (rc) return rc;
+    if (st->N < 1) return 0;
+    int blocks;
+    const int pt = n2n_lanes(cfg, st->N, &blocks);
+    hipStream_t s = (hipStream_t)stream;
+#define N2N_SB(PT) hipLaunchKernelGGL((k_n2n_shaping_begin<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, phi, coef)
+    if (pt == 8) N2N_SB(8); else if (pt == 16) N2N_SB(16); else if (pt == 32) N2N_SB(32); else N2N_SB(64);
+#undef N2N_SB
+    return (int)hipGetLastError();
 }
 
 void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seeds) {

@@ -24,6 +24,7 @@ from torch.nn.utils import spectral_norm
 
 from . import ops
 from . import value_norm as vnorm
+from .reward_shaping import reward_shaping_options
 from .e3d_env import ParticleEnv
 from .model import HeadLinear, _make_linear, _ortho_linear, _Trunk
 from .trainer import (GradBucket, ParticleRunState, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed,
@@ -120,6 +121,7 @@ class E3dMAPPO:
             raise ValueError("algo.use_reward_norm: true is not supported on env_3d (runtime.env: e3d); set it to false")
         self.use_reward_scaling = bool(a.get("use_reward_scaling", False))   # the reference's RewardScaling in policy_record
         self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
+        self.reward_shaping, self.shaping_coef = reward_shaping_options(cfg)   # distance shaping in policy_record
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
         self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
@@ -195,7 +197,8 @@ class E3dMAPPO:
         pursuer p was active at its start; rewards, values and the `active` mask of other rows are zero, so is v_n[n, t + 1, p] when
         pursuer p or episode n ended in step t for any reason but the time limit; v_n[:, T] is the critic's bootstrap value.  The masks
         and the per-environment accumulators are one launch per tick (ParticleEnv.policy_record); with algo.use_reward_scaling and a
-        buffer, r is the scaled reward (env.reward_scale advances) while the return stays the raw one.
+        buffer, r is the scaled reward (env.reward_scale advances) while the return stays the raw one; with algo.reward_shaping:
+        distance and a buffer, r (what is scaled, when both are on) carries the shaping term gamma Phi' - Phi (env.shaping_phi).
         Returns per-environment (return, captured, length) device tensors."""
         N, P, T = env.num_envs, env.p_num, env.max_step
         env.reset()
@@ -206,6 +209,9 @@ class E3dMAPPO:
         st.live.copy_(env.active_t)   # no environment is done; policy_record writes the next step's mask
         acc = env.new_accumulators()
         scale_gamma = self.gamma if (self.use_reward_scaling and buf is not None) else None   # evaluation never scales
+        shaping_gamma = self.gamma if (self.reward_shaping == "distance" and buf is not None) else None   # ... and never shapes
+        if shaping_gamma is not None:
+            env.shaping_begin()
         for t in range(T):
             env.policy_features(st.fa, st.fc)
             self._policy_step(st, greedy)
@@ -219,7 +225,7 @@ class E3dMAPPO:
             buf["a_n"][:, t].copy_(st.action)
             buf["a_logprob_n"][:, t].copy_(st.logp)
             env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1], st.live,
-                              scale_gamma=scale_gamma)
+                              scale_gamma=scale_gamma, shaping_gamma=shaping_gamma)
         if buf is not None:
             env.policy_features(st.fa, st.fc)
             vmask = env.active_t.float() * (acc["ended"] == 0).float()[:, None]
@@ -342,13 +348,17 @@ class E3dMAPPO:
 
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
     """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env).  A training
-    environment owns the RewardScaling state when algo.use_reward_scaling is on; evaluation environments (training=False) never do."""
+    environment owns the RewardScaling state when algo.use_reward_scaling is on and the shaping state when algo.reward_shaping is
+    distance; evaluation environments (training=False) never do."""
     base = int(cfg.runtime.get("seed", 0)) + seed_offset + max(1000, num_envs) * rank
     env = ParticleEnv(num_envs=num_envs, seeds=[base + n for n in range(num_envs)], device=device, max_step=int(cfg.env.max_steps),
                       evader=str(cfg.runtime.get("e3d_evader", "slsqp")))
     env.initialize(int(cfg.env.num_defender))
     if training and bool(cfg.algo.get("use_reward_scaling", False)):
         env.enable_reward_scaling()
+    mode, coef = reward_shaping_options(cfg)
+    if training and mode == "distance":
+        env.enable_reward_shaping(coef)
     return env
 
 

@@ -78,6 +78,8 @@ def load_library():
         L.e3d_resetter_set_state.argtypes = [vp, vp]
         L.e3d_policy_features.argtypes = [vp] * 6
         L.e3d_policy_record.argtypes = [vp] * 7 + [C.c_double, vp]
+        L.e3d_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
+        L.e3d_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
         _lib = L
     return _lib
 
@@ -118,6 +120,7 @@ class ParticleEnv:
         self.e_num = 1
         self.resetter = None
         self.reward_scale = None
+        self.shaping_phi, self.shaping_coef = None, None
 
     def initialize(self, p_num):
         """particle_env.py:133-135, plus the allocation of the device records"""
@@ -251,12 +254,30 @@ class ParticleEnv:
         self.reward_scale = torch.zeros((self.num_envs, 1 + 3 * self.p_num), dtype=torch.float64, device=self.device)
         return self.reward_scale
 
-    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, live_next=None, scale_gamma=None):
+    def enable_reward_shaping(self, coef):
+        """allocates the shaping state of a training environment (algo.reward_shaping: distance): shaping_phi (N, P) f64, the
+        potential -coef * |pursuer - evader| of the state the next tick starts from (csrc/reward_shaping.hpp); shaping_begin() writes
+        it at every episode start, so nothing of it outlives an episode"""
+        self.shaping_coef = float(coef)
+        self.shaping_phi = torch.zeros((self.num_envs, self.p_num), dtype=torch.float64, device=self.device)
+        return self.shaping_phi
+
+    def shaping_begin(self):
+        """after reset(): shaping_phi = the potential of the initial state (e3d_shaping_begin, one launch)"""
+        if self.shaping_phi is None:
+            raise RuntimeError("shaping_begin() needs enable_reward_shaping() on this environment")
+        _check(self.L.e3d_shaping_begin(C.byref(self.c), C.byref(self.st), C.c_void_p(self.shaping_phi.data_ptr()),
+                                        C.c_double(self.shaping_coef), _stream()), "e3d_shaping_begin")
+
+    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, live_next=None, scale_gamma=None,
+                      shaping_gamma=None):
         """after step(): r = reward * live, active = live, v = value * live (row t of the buffer, None skips), v_next (row t + 1 of v_n)
         zeroed where the pursuer is inactive or its episode ended for a reason other than the time limit, live_next = the next step's
         live mask (may be `live` itself); updates the accumulators of new_accumulators() (e3d_policy_record, include/e3d_env.h).
         scale_gamma: the discount of the reference's RewardScaling; r is then the scaled reward * live and reward_scale
-        (enable_reward_scaling) advances, in the same launch."""
+        (enable_reward_scaling) advances, in the same launch.  shaping_gamma: the discount of the distance shaping; the reward (what
+        RewardScaling receives, when both are on) gains gamma Phi' - Phi on live rows and shaping_phi (enable_reward_shaping) advances,
+        still in that one launch (e3d_policy_record_shaped)."""
         N, P = self.num_envs, self.p_num
         io = E3dRecordIO()
         for k, t in (("live", live), ("value", value), ("r", r), ("active", active), ("v", v), ("v_next", v_next), ("live_next", live_next)):
@@ -275,8 +296,18 @@ class ParticleEnv:
                 raise RuntimeError("policy_record(scale_gamma=...) needs enable_reward_scaling() on this environment")
             assert rs.dtype == torch.float64 and rs.is_contiguous() and rs.shape == (N, 1 + 3 * P) and rs.device == self.p.device
             rs_ptr, gamma = rs.data_ptr(), float(scale_gamma)
-        _check(self.L.e3d_policy_record(C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()),
-                                        C.byref(io), C.byref(a), C.c_void_p(rs_ptr), C.c_double(gamma), _stream()), "e3d_policy_record")
+        args = (C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()), C.byref(io), C.byref(a))
+        if shaping_gamma is None:
+            _check(self.L.e3d_policy_record(*args, C.c_void_p(rs_ptr), C.c_double(gamma), _stream()), "e3d_policy_record")
+            return
+        phi = self.shaping_phi
+        if phi is None:
+            raise RuntimeError("policy_record(shaping_gamma=...) needs enable_reward_shaping() on this environment")
+        if scale_gamma is not None and float(scale_gamma) != float(shaping_gamma):
+            raise ValueError("policy_record: scale_gamma and shaping_gamma are one discount (algo.gamma)")
+        assert phi.dtype == torch.float64 and phi.is_contiguous() and phi.shape == (N, P) and phi.device == self.p.device
+        _check(self.L.e3d_policy_record_shaped(*args, C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef), C.c_double(float(shaping_gamma)),
+                                               C.c_void_p(rs_ptr), _stream()), "e3d_policy_record_shaped")
 
     def step(self, action):
         """:205-219 (preceded by the evader's move with the command of evader_step) -> (reward (N,P), done (N,), active (N,P));

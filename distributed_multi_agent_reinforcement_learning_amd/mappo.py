@@ -205,6 +205,9 @@ class MAPPO:
         if bool(a.get("use_reward_scaling", False)):
             raise ValueError("algo.use_reward_scaling: true is built for runtime.env n2n and e3d only; the pursuit tick has "
                              "algo.use_reward_norm (set use_reward_scaling to false)")
+        if str(a.get("reward_shaping", "none")) != "none":
+            raise ValueError("algo.reward_shaping is built for runtime.env n2n and e3d only; the pursuit rollout is pinned to the "
+                             "reference's (set reward_shaping to none)")
         if bool(a.get("use_value_norm", False)):
             raise ValueError("algo.use_value_norm: true is built for runtime.env n2n and e3d only; the pursuit update is pinned to the "
                              "reference's (set use_value_norm to false)")

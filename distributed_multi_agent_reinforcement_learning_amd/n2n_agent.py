@@ -17,6 +17,7 @@ import torch
 
 from . import ops
 from . import value_norm as vnorm
+from .reward_shaping import reward_shaping_options
 from .model import build_actor_critic, sequence_forward_pair
 from .n2n_env import ParticleEnv
 from .trainer import (GradBucket, ParticleRunState, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed,
@@ -65,6 +66,7 @@ class N2nMAPPO:
             raise ValueError("algo.use_reward_norm: true is not supported on env_n2n (runtime.env: n2n); set it to false")
         self.use_reward_scaling = bool(a.get("use_reward_scaling", False))   # the reference's RewardScaling in policy_record
         self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
+        self.reward_shaping, self.shaping_coef = reward_shaping_options(cfg)   # distance shaping in policy_record
         if int(cfg.env.num_defender) > MAX_P:
             raise ValueError(f"env.num_defender={cfg.env.num_defender}: the DHGN message kernels take at most {MAX_P} pursuers per row")
         if int(cfg.env.state_dim) != 4 or int(cfg.env.action_dim) != 9 or int(a.num_relation) != 3:
@@ -146,6 +148,8 @@ class N2nMAPPO:
         and environment n was not done before it; r, v_n and `active` of other rows are zero, so is v_n[n, t + 1, p] when pursuer p or
         episode n ended in step t for a reason other than the time limit; v_n[:, T] is the critic's bootstrap value under that rule.
         With algo.use_reward_scaling and a buffer, r is the scaled reward (env.reward_scale advances); acc["ret"] stays the raw return.
+        With algo.reward_shaping: distance and a buffer, r (what is scaled, when both are on) carries the shaping term
+        gamma Phi' - Phi (env.shaping_phi, written by shaping_begin after the reset).
         Returns the per-environment accumulators (done_before, ended, captured, ret, length)."""
         N, P, T, d = env.num_envs, env.p_num, env.episode_limit, self.depth
         env.reset()
@@ -153,6 +157,9 @@ class N2nMAPPO:
         st.reset()
         acc = env.new_accumulators()
         scale_gamma = self.gamma if (self.use_reward_scaling and buf is not None) else None   # evaluation never scales
+        shaping_gamma = self.gamma if (self.reward_shaping == "distance" and buf is not None) else None   # ... and never shapes
+        if shaping_gamma is not None:
+            env.shaping_begin()
         for t in range(T):
             env.policy_inputs(st.p4, st.e4, st.e_ref, st.live, st.pp, st.pe, acc["done_before"])
             self._policy_step(st, greedy)
@@ -162,7 +169,7 @@ class N2nMAPPO:
                 env.policy_record(acc, st.live)
                 continue
             env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1],
-                              scale_gamma=scale_gamma)
+                              scale_gamma=scale_gamma, shaping_gamma=shaping_gamma)
             items = [(st.p4, buf["p_state"][:, t]), (st.e4, buf["e_state"][:, t]), (st.e_ref, buf["e_ref"][:, t]), (st.pp, buf["p_adj"][:, t]),
                      (st.pe, buf["e_adj"][:, t]), (st.a_n, buf["a_n"][:, t]), (st.logp, buf["a_logprob_n"][:, t])]
             if d:   # the update reads the stored embeddings as FCRA history only
@@ -272,13 +279,17 @@ class N2nMAPPO:
 
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
     """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env).  A training
-    environment owns the RewardScaling state when algo.use_reward_scaling is on; evaluation environments (training=False) never do."""
+    environment owns the RewardScaling state when algo.use_reward_scaling is on and the shaping state when algo.reward_shaping is
+    distance; evaluation environments (training=False) never do."""
     base = int(cfg.runtime.get("seed", 0)) + seed_offset + max(1000, num_envs) * rank
     env = ParticleEnv(num_envs=num_envs, seeds=[base + n for n in range(num_envs)], device=device, episode_limit=int(cfg.env.max_steps),
                       evader=str(cfg.runtime.get("n2n_evader", "slsqp")))
     env.initialize(int(cfg.env.num_defender), int(cfg.env.num_evader))
     if training and bool(cfg.algo.get("use_reward_scaling", False)):
         env.enable_reward_scaling()
+    mode, coef = reward_shaping_options(cfg)
+    if training and mode == "distance":
+        env.enable_reward_shaping(coef)
     return env
 
 

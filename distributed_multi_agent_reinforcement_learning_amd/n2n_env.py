@@ -83,6 +83,8 @@ def load_library():
         L.n2n_policy_inputs.argtypes = [vp] * 5
         L.n2n_policy_record.argtypes = [vp] * 7
         L.n2n_policy_record_scaled.argtypes = [vp] * 7 + [C.c_double, vp]
+        L.n2n_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
+        L.n2n_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
         _lib = L
     return _lib
 
@@ -120,6 +122,7 @@ class ParticleEnv:
         self.p_num = self.e_num = None
         self.resetter = None
         self.reward_scale = None
+        self.shaping_phi, self.shaping_coef = None, None
 
     def initialize(self, p_num, e_num):
         """particle_env.py:160-162, plus the allocation of the device records"""
@@ -255,6 +258,21 @@ class ParticleEnv:
         self.reward_scale = torch.zeros((self.num_envs, 1 + 3 * self.p_num), dtype=torch.float64, device=self.device)
         return self.reward_scale
 
+    def enable_reward_shaping(self, coef):
+        """allocates the shaping state of a training environment (algo.reward_shaping: distance): shaping_phi (N, P) f64, the
+        potential -coef * (distance to the nearest active evader) of the state the next tick starts from (csrc/reward_shaping.hpp);
+        shaping_begin() writes it at every episode start, so nothing of it outlives an episode"""
+        self.shaping_coef = float(coef)
+        self.shaping_phi = torch.zeros((self.num_envs, self.p_num), dtype=torch.float64, device=self.device)
+        return self.shaping_phi
+
+    def shaping_begin(self):
+        """after reset(): shaping_phi = the potential of the initial state (n2n_shaping_begin, one launch)"""
+        if self.shaping_phi is None:
+            raise RuntimeError("shaping_begin() needs enable_reward_shaping() on this environment")
+        _check(self.L.n2n_shaping_begin(C.byref(self.c), C.byref(self.st), C.c_void_p(self.shaping_phi.data_ptr()),
+                                        C.c_double(self.shaping_coef), _stream()), "n2n_shaping_begin")
+
     def policy_inputs(self, p4, e4, e_ref, live, pp_adj, pe_adj, done_before=None):
         """the DHGN's fp32 inputs of the current state (n2n_policy_inputs, include/n2n_env.h): p4 (N,P,4), e4 (N,E,4), e_ref (N,4),
         live (N,P), pp_adj (N,P,P), pe_adj (N,P,E), each None (skipped) or a tensor with dense environment rows, e.g. buffer[:, t].
@@ -273,11 +291,14 @@ class ParticleEnv:
         _check(self.L.n2n_policy_inputs(C.byref(self.c), C.byref(self.st), C.c_void_p(done_before.data_ptr() if done_before is not None else None),
                                         C.byref(io), _stream()), "n2n_policy_inputs")
 
-    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, scale_gamma=None):
+    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, scale_gamma=None, shaping_gamma=None):
         """after step(): r = reward * live, active = live, v = value * live (row t of the buffer, None skips), v_next (row t + 1 of v_n)
         zeroed where the pursuer is inactive or its episode ended for a reason other than the time limit; updates the accumulators
         of new_accumulators() (n2n_policy_record, include/n2n_env.h).  scale_gamma: the discount of the reference's RewardScaling; r is
-        then the scaled reward * live and reward_scale (enable_reward_scaling) advances, in the same launch (n2n_policy_record_scaled)."""
+        then the scaled reward * live and reward_scale (enable_reward_scaling) advances, in the same launch (n2n_policy_record_scaled).
+        shaping_gamma: the discount of the distance shaping; the reward (what RewardScaling receives, when both are on) gains
+        gamma Phi' - Phi on live rows and shaping_phi (enable_reward_shaping) advances, still in that one launch
+        (n2n_policy_record_shaped)."""
         N, P = self.num_envs, self.p_num
         io = N2nRecordIO()
         for k, t in (("live", live), ("value", value), ("r", r), ("active", active), ("v", v), ("v_next", v_next)):
@@ -290,12 +311,24 @@ class ParticleEnv:
             assert t.dtype == dt and t.is_contiguous() and t.shape == (N,) and t.device == self.p.device, k
             setattr(a, k, t.data_ptr())
         args = (C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()), C.byref(io), C.byref(a))
-        if scale_gamma is None:
+        if scale_gamma is None and shaping_gamma is None:
             _check(self.L.n2n_policy_record(*args, _stream()), "n2n_policy_record")
             return
-        rs = self.reward_scale
-        if rs is None:
-            raise RuntimeError("policy_record(scale_gamma=...) needs enable_reward_scaling() on this environment")
-        assert rs.dtype == torch.float64 and rs.is_contiguous() and rs.shape == (N, 1 + 3 * P) and rs.device == self.p.device
-        _check(self.L.n2n_policy_record_scaled(*args, C.c_void_p(rs.data_ptr()), C.c_double(float(scale_gamma)), _stream()),
-               "n2n_policy_record_scaled")
+        rs = None
+        if scale_gamma is not None:
+            rs = self.reward_scale
+            if rs is None:
+                raise RuntimeError("policy_record(scale_gamma=...) needs enable_reward_scaling() on this environment")
+            assert rs.dtype == torch.float64 and rs.is_contiguous() and rs.shape == (N, 1 + 3 * P) and rs.device == self.p.device
+        if shaping_gamma is None:
+            _check(self.L.n2n_policy_record_scaled(*args, C.c_void_p(rs.data_ptr()), C.c_double(float(scale_gamma)), _stream()),
+                   "n2n_policy_record_scaled")
+            return
+        phi = self.shaping_phi
+        if phi is None:
+            raise RuntimeError("policy_record(shaping_gamma=...) needs enable_reward_shaping() on this environment")
+        if scale_gamma is not None and float(scale_gamma) != float(shaping_gamma):
+            raise ValueError("policy_record: scale_gamma and shaping_gamma are one discount (algo.gamma)")
+        assert phi.dtype == torch.float64 and phi.is_contiguous() and phi.shape == (N, P) and phi.device == self.p.device
+        _check(self.L.n2n_policy_record_shaped(*args, C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef), C.c_double(float(shaping_gamma)),
+                                               C.c_void_p(rs.data_ptr() if rs is not None else None), _stream()), "n2n_policy_record_shaped")

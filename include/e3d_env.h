@@ -96,6 +96,18 @@ typedef struct e3d_record_io {
 int e3d_policy_record(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
                       const e3d_policy_acc *acc, double *rs, double gamma, void *stream);
 
+/* e3d_policy_record with potential-based distance shaping (algo.reward_shaping: distance; csrc/reward_shaping.hpp) on the reward row, in
+ * the same launch.  phi [N][P] f64 carries the potential of the state a tick starts from: Phi(n, p) = -coef * |pos_p - pos_e| (x, y, z;
+ * sqrt(dx dx + dy dy + dz dz) summed left to right), 0 when the pursuer or the evader is inactive.  e3d_shaping_begin writes Phi of the
+ * current records (after a reset).  For an environment that was not done before the step: Phi' = Phi of the records after the tick,
+ * Phi_next = 0 where v_next is zeroed (pursuer inactive after the step, or the episode ended, the time limit excepted), else Phi';
+ * x = reward + (gamma Phi_next - phi) live; phi = Phi'; io->r = (float)x * live, or, with rs (NULL, or the RewardScaling state of
+ * e3d_policy_record, discount gamma as well), the scaled x * live.  Environments done before the step leave phi (and rs) untouched.
+ * acc->ret keeps the raw reward; everything but io->r is what e3d_policy_record writes. */
+int e3d_policy_record_shaped(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
+                             const e3d_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream);
+int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, double coef, void *stream);
+
 /* The reference's evader: eva.e_f (eva.py:87-148) -- scipy's SLSQP (ftol 1e-6, <= 100 iterations, 2-point finite-difference
  * gradient) minimising obj_func (:212-240) over (heading, pitch, speed), started at the evader's state, bounded by the
  * environment's ang_lmt / v_lmt (:130-135) -- written as the command e_cmd [N][3] that e3d_env_tick consumes; zeros when the

@@ -112,6 +112,17 @@ int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *r
  * zero).  acc->ret keeps the raw reward.  Everything else as n2n_policy_record. */
 int n2n_policy_record_scaled(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
                              const n2n_policy_acc *acc, double *rs, double gamma, void *stream);
+/* n2n_policy_record with potential-based distance shaping (algo.reward_shaping: distance; csrc/reward_shaping.hpp) on the reward row, in
+ * the same launch.  phi [N][P] f64 carries the potential of the state a tick starts from: Phi(n, p) = -coef * min_k |pos_p - pos_k| over
+ * the ACTIVE evaders k (x, y; sqrt(dx dx + dy dy)), 0 when the pursuer is inactive or no evader is active.  n2n_shaping_begin writes Phi
+ * of the current records (after a reset).  For an environment that was not done before the step: Phi' = Phi of the records after the
+ * tick, Phi_next = 0 where v_next is zeroed (pursuer inactive after the step, or the episode ended, the time limit excepted), else Phi';
+ * x = reward + (gamma Phi_next - phi) live; phi = Phi'; io->r = (float)x * live, or, with rs (NULL, or the state of
+ * n2n_policy_record_scaled, discount gamma as well), the scaled x * live.  Environments done before the step leave phi (and rs)
+ * untouched.  acc->ret keeps the raw reward; everything but io->r is what n2n_policy_record writes. */
+int n2n_policy_record_shaped(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
+                             const n2n_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream);
+int n2n_shaping_begin(const n2n_config *cfg, const n2n_state *st, double *phi, double coef, void *stream);
 
 /* Host side of ParticleEnv.reset (:200-281) with a bit-exact replica of numpy's legacy RandomState per environment
  * (np.random.seed(seeds[n])).  Fills host arrays p [N][P][5], e [N][E][5], target [N][2]. */
