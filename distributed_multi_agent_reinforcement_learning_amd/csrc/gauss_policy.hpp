@@ -113,6 +113,8 @@ __global__ __launch_bounds__(256) void k_gauss_head(int R, const float *__restri
 // the four waves in a fixed order) that k_ppo_gauss_finish adds in block order: no atomics, the same bits every run.
 constexpr int GAUSS_PART = 2 + GAUSS_MAX_A;   // doubles per block: actor sum, critic sum, log_std gradient [A]
 
+// DIAG: the ppodiag::row step of live rows and its partials behind the PPO_BLOCKS x GAUSS_PART loss partials (as k_ppo_loss<DIAG>)
+template <bool DIAG>
 __global__ __launch_bounds__(256) void k_ppo_loss_gauss(long n, int A, const float *__restrict__ mu, PpoView mv, const float *__restrict__ log_std,
                                                         const float *__restrict__ action, const float *lp_old, const float *adv, const float *active,
                                                         const float *__restrict__ v_now, PpoView vv, const float *v_old, const float *v_tgt,
@@ -131,6 +133,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss(long n, int A, const flo
     double acc[GAUSS_PART];
 #pragma unroll
     for (int k = 0; k < GAUSS_PART; k++) acc[k] = 0.0;
+    double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const long i2 = i % mv.d2, i01 = i / mv.d2, i1 = i01 % mv.d1, i0 = i01 / mv.d1;
         const long mo = i0 * mv.s0 + i1 * mv.s1 + i2 * mv.s2;
@@ -146,6 +149,8 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss(long n, int A, const flo
         }
         const float act = active[i];
         const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        float d_lr = 0.f, d_vt = 0.f;
+        if (DIAG) { d_lr = lp - lp_old[i]; d_vt = v_tgt[i]; }
         const PpoElem e = ppo_elem(lp, ent, lp_old[i], adv[i], act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, ent_coef, value_clip);
         acc[0] += (double)(e.la * act);
         acc[1] += (double)(e.lc * act);
@@ -157,6 +162,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss(long n, int A, const flo
                 g_mu[mo + k] = e.g_lp * q;
                 acc[2 + k] += (double)(e.g_lp * (q * d[k] - 1.f) + e.g_ent);
             }
+        if (DIAG && act != 0.f) ppodiag::row(dg, d_lr, expf(d_lr), ent, vn, d_vt, eps);
     }
     __shared__ double red[GAUSS_PART][4];
 #pragma unroll
@@ -171,13 +177,13 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss(long n, int A, const flo
         const int k = threadIdx.x;
         partials[(size_t)blockIdx.x * GAUSS_PART + k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
     }
+    if (DIAG) ppo_diag_block_sums(dg, partials + (size_t)PPO_BLOCKS * GAUSS_PART);
 }
 
 // one wave per sum (2 + A workgroups): lane l adds the partials of blocks l, l + 64, .. in order, then a fixed butterfly -- the
 // same bits every run, without one lane walking all PPO_BLOCKS partials serially
-__global__ __launch_bounds__(64) void k_ppo_gauss_finish(int nblk, const double *partials, const float *active_sum, float *losses,
-                                                         float *grad_log_std) {
-    const int k = blockIdx.x;
+__device__ __forceinline__ void ppo_gauss_finish_wave(int k, int nblk, const double *partials, const float *active_sum, float *losses,
+                                                      float *grad_log_std) {
     double s = 0.0;
     for (int b = threadIdx.x; b < nblk; b += 64) s += partials[(size_t)b * GAUSS_PART + k];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
@@ -185,6 +191,18 @@ __global__ __launch_bounds__(64) void k_ppo_gauss_finish(int nblk, const double 
         if (k < 2) losses[k] = (float)s / active_sum[0];
         else grad_log_std[k - 2] = (float)s;
     }
+}
+
+__global__ __launch_bounds__(64) void k_ppo_gauss_finish(int nblk, const double *partials, const float *active_sum, float *losses,
+                                                         float *grad_log_std) {
+    ppo_gauss_finish_wave(blockIdx.x, nblk, partials, active_sum, losses, grad_log_std);
+}
+
+// k_ppo_gauss_finish in the first nsum workgroups, the eight diagnostic sums (ppo_diag_finish_wave) in the eight after them
+__global__ __launch_bounds__(64) void k_ppo_gauss_finish_diag(int nsum, int nblk, const double *partials, const float *active_sum, float *losses,
+                                                              float *grad_log_std, double *diag) {
+    if ((int)blockIdx.x < nsum) ppo_gauss_finish_wave(blockIdx.x, nblk, partials, active_sum, losses, grad_log_std);
+    else ppo_diag_finish_wave(blockIdx.x - nsum, nblk, partials + (size_t)PPO_BLOCKS * GAUSS_PART, diag);
 }
 
 // ---- state-dependent log-std and tanh squashing (gauss_head_sample_ex / ppo_loss_gauss_ex_fwd_bwd) ---------------------------------
@@ -304,7 +322,7 @@ __global__ __launch_bounds__(256) void k_gauss_head_ex(int R, const float *__res
 // AT > 0 fixes the action count (state mode: sigma = exp(ls) and 1 / sigma^2 are per row, so a row pays for AT of them, not for
 // GAUSS_MAX_A); AT = 0 takes the runtime A with k_ppo_loss_gauss's loop shape (param mode: sigma is computed once per thread, and
 // this shape keeps its bits equal to k_ppo_loss_gauss's).  Same expressions, in the same order, as k_ppo_loss_gauss.
-template <int AT, bool STATE, bool TANH>
+template <int AT, bool STATE, bool TANH, bool DIAG>
 __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, const float *__restrict__ mu, PpoView mv, const float *__restrict__ ls_raw,
                                                            PpoView lv, float ls_lo, float ls_hi, const float *__restrict__ action, const float *lp_old,
                                                            const float *adv, const float *active, const float *__restrict__ v_now, PpoView vv,
@@ -332,6 +350,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, con
     double acc[NSUM];
 #pragma unroll
     for (int k = 0; k < NSUM; k++) acc[k] = 0.0;
+    double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const long i2 = i % mv.d2, i01 = i / mv.d2, i1 = i01 % mv.d1, i0 = i01 / mv.d1;
         const long mo = i0 * mv.s0 + i1 * mv.s1 + i2 * mv.s2;
@@ -364,6 +383,8 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, con
         if (TANH) lp -= jac;
         const float act = active[i];
         const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        float d_lr = 0.f, d_vt = 0.f;
+        if (DIAG) { d_lr = lp - lp_old[i]; d_vt = v_tgt[i]; }
         const PpoElem e = ppo_elem(lp, ent, lp_old[i], adv[i], act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, ent_coef, value_clip);
         acc[0] += (double)(e.la * act);
         acc[1] += (double)(e.lc * act);
@@ -377,6 +398,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, con
                 if (STATE) g_ls[lo + k] = pass[k] ? gl : 0.f;
                 else acc[2 + k] += (double)(pass[k] ? gl : 0.f);
             }
+        if (DIAG && act != 0.f) ppodiag::row(dg, d_lr, expf(d_lr), ent, vn, d_vt, eps);
     }
     const int nsum = STATE ? 2 : 2 + A;
     __shared__ double red[NSUM][4];
@@ -392,6 +414,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, con
         const int k = threadIdx.x;
         partials[(size_t)blockIdx.x * GAUSS_PART + k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
     }
+    if (DIAG) ppo_diag_block_sums(dg, partials + (size_t)PPO_BLOCKS * GAUSS_PART);
 }
 
 }  // namespace
@@ -417,24 +440,55 @@ int gauss_head_sample(int32_t R, int32_t A, int32_t H, const float *feat, const 
 }
 
 int64_t ppo_loss_gauss_workspace(void) { return (int64_t)PPO_BLOCKS * GAUSS_PART * sizeof(double); }
+int64_t ppo_loss_gauss_diag_workspace(void) { return (int64_t)PPO_BLOCKS * (GAUSS_PART + ppodiag::NSUM) * sizeof(double); }
 
-int ppo_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
-                           const float *log_std, const float *action, const float *logp_old, const float *adv, const float *active,
-                           const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
-                           const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses, float *grad_values,
-                           float *grad_log_std, void *workspace, void *stream) {
+// diag == nullptr: the plain launches; else the DIAG instance and the finish with eight more workgroups (two launches either way)
+static int ppo_loss_gauss_launch(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                                 int64_t m_s2, const float *log_std, const float *action, const float *logp_old, const float *adv,
+                                 const float *active, const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old,
+                                 const float *v_target, const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip,
+                                 float *losses, float *grad_values, float *grad_log_std, void *workspace, double *diag, void *stream) {
     if (n < 1 || A < 1 || A > GAUSS_MAX_A || d1 < 1 || d2 < 1 || (n % (d1 * d2)) || !mu || !grad_mu || !log_std || !action || !logp_old || !adv ||
         !active || !values_now || !v_target || !active_sum || !losses || !grad_values || !grad_log_std || !workspace || (use_value_clip && !values_old))
         return MO_ERR_BAD_ARG;
     long blocks = (n + 255) / 256;
     if (blocks > PPO_BLOCKS) blocks = PPO_BLOCKS;
     const PpoView mv{d1, d2, m_s0, m_s1, m_s2}, vv{d1, d2, v_s0, v_s1, v_s2};
-    hipLaunchKernelGGL(k_ppo_loss_gauss, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long)n, (int)A, mu, mv, log_std, action, logp_old,
-                       adv, active, values_now, vv, values_old, v_target, active_sum, epsilon, entropy_coef, (int)use_value_clip, grad_mu, grad_values,
-                       (double *)workspace);
-    hipLaunchKernelGGL(k_ppo_gauss_finish, dim3(2 + A), dim3(64), 0, (hipStream_t)stream, (int)blocks, (const double *)workspace, active_sum, losses,
-                       grad_log_std);
+#define GAUSS_LOSS(D) hipLaunchKernelGGL((k_ppo_loss_gauss<D>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long)n, (int)A, mu, mv, \
+                                         log_std, action, logp_old, adv, active, values_now, vv, values_old, v_target, active_sum, epsilon, \
+                                         entropy_coef, (int)use_value_clip, grad_mu, grad_values, (double *)workspace)
+    if (diag) {
+        GAUSS_LOSS(true);
+        hipLaunchKernelGGL(k_ppo_gauss_finish_diag, dim3(2 + A + ppodiag::NSUM), dim3(64), 0, (hipStream_t)stream, 2 + (int)A, (int)blocks,
+                           (const double *)workspace, active_sum, losses, grad_log_std, diag);
+    } else {
+        GAUSS_LOSS(false);
+        hipLaunchKernelGGL(k_ppo_gauss_finish, dim3(2 + A), dim3(64), 0, (hipStream_t)stream, (int)blocks, (const double *)workspace, active_sum,
+                           losses, grad_log_std);
+    }
+#undef GAUSS_LOSS
     return (int)hipGetLastError();
+}
+
+int ppo_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
+                           const float *log_std, const float *action, const float *logp_old, const float *adv, const float *active,
+                           const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                           const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses, float *grad_values,
+                           float *grad_log_std, void *workspace, void *stream) {
+    return ppo_loss_gauss_launch(n, A, mu, grad_mu, d1, d2, m_s0, m_s1, m_s2, log_std, action, logp_old, adv, active, values_now, v_s0, v_s1, v_s2,
+                                 values_old, v_target, active_sum, epsilon, entropy_coef, use_value_clip, losses, grad_values, grad_log_std,
+                                 workspace, nullptr, stream);
+}
+
+int ppo_loss_gauss_fwd_bwd_diag(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                                int64_t m_s2, const float *log_std, const float *action, const float *logp_old, const float *adv,
+                                const float *active, const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old,
+                                const float *v_target, const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip,
+                                float *losses, float *grad_values, float *grad_log_std, void *workspace, void *stream, double *diag) {
+    if (!diag) return MO_ERR_BAD_ARG;
+    return ppo_loss_gauss_launch(n, A, mu, grad_mu, d1, d2, m_s0, m_s1, m_s2, log_std, action, logp_old, adv, active, values_now, v_s0, v_s1, v_s2,
+                                 values_old, v_target, active_sum, epsilon, entropy_coef, use_value_clip, losses, grad_values, grad_log_std,
+                                 workspace, diag, stream);
 }
 
 static bool gauss_ex_bounds_ok(float lo, float hi) { return lo < hi; }   // (NaN fails)
@@ -467,12 +521,12 @@ int gauss_head_sample_ex(int32_t R, int32_t A, int32_t H, const float *feat, con
 
 int64_t ppo_loss_gauss_ex_workspace(void) { return (int64_t)PPO_BLOCKS * GAUSS_PART * sizeof(double); }
 
-int ppo_loss_gauss_ex_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
-                              const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min,
-                              float log_std_max, int32_t squash, const float *action, const float *logp_old, const float *adv, const float *active,
-                              const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
-                              const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses, float *grad_values,
-                              void *workspace, void *stream) {
+static int ppo_loss_gauss_ex_launch(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                                    int64_t m_s2, const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2,
+                                    float log_std_min, float log_std_max, int32_t squash, const float *action, const float *logp_old,
+                                    const float *adv, const float *active, const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2,
+                                    const float *values_old, const float *v_target, const float *active_sum, float epsilon, float entropy_coef,
+                                    int32_t use_value_clip, float *losses, float *grad_values, void *workspace, double *diag, void *stream) {
     if (n < 1 || A < 1 || A > GAUSS_MAX_A || d1 < 1 || d2 < 1 || (n % (d1 * d2)) || !mu || !grad_mu || !ls_raw || !grad_log_std ||
         (squash != 0 && squash != 1) || !gauss_ex_bounds_ok(log_std_min, log_std_max) || !action || !logp_old || !adv || !active || !values_now ||
         !v_target || !active_sum || !losses || !grad_values || !workspace || (use_value_clip && !values_old))
@@ -482,27 +536,62 @@ int ppo_loss_gauss_ex_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad
     if (blocks > PPO_BLOCKS) blocks = PPO_BLOCKS;
     const PpoView mv{d1, d2, m_s0, m_s1, m_s2}, lv{d1, d2, l_s0, l_s1, l_s2}, vv{d1, d2, v_s0, v_s1, v_s2};
     hipStream_t st = (hipStream_t)stream;
-#define GAUSS_LOSS_EX(AT, S, T) hipLaunchKernelGGL((k_ppo_loss_gauss_ex<AT, S, T>), dim3((unsigned)blocks), dim3(256), 0, st, (long)n, (int)A, mu, \
-                                                   mv, ls_raw, lv, log_std_min, log_std_max, action, logp_old, adv, active, values_now, vv, values_old, \
-                                                   v_target, active_sum, epsilon, entropy_coef, (int)use_value_clip, grad_mu, grad_log_std, \
-                                                   grad_values, (double *)workspace)
+#define GAUSS_LOSS_EXD(AT, S, T, D) hipLaunchKernelGGL((k_ppo_loss_gauss_ex<AT, S, T, D>), dim3((unsigned)blocks), dim3(256), 0, st, (long)n, (int)A, \
+                                                       mu, mv, ls_raw, lv, log_std_min, log_std_max, action, logp_old, adv, active, values_now, vv, \
+                                                       values_old, v_target, active_sum, epsilon, entropy_coef, (int)use_value_clip, grad_mu, \
+                                                       grad_log_std, grad_values, (double *)workspace)
+#define GAUSS_LOSS_EX(AT, S, T) do { if (diag) GAUSS_LOSS_EXD(AT, S, T, true); else GAUSS_LOSS_EXD(AT, S, T, false); } while (0)
 #define GAUSS_LOSS_EX4(AT) case AT: if (squash) GAUSS_LOSS_EX(AT, true, true); else GAUSS_LOSS_EX(AT, true, false); break;
+#define GAUSS_LOSS_EX2(AT) case AT: if (squash) GAUSS_LOSS_EXD(AT, true, true, false); else GAUSS_LOSS_EXD(AT, true, false, false); break;
+    // the diagnostics in state mode stop at the action count the state-mode rollout head has (GAUSS_SD_MAX_A): beyond it no policy
+    // exists whose update could be diagnosed, and the A = 15 instance would be the one kernel here that needs scratch
+    if (diag && state && A > GAUSS_SD_MAX_A) return MO_ERR_BAD_ARG;
     if (!state) {   // param mode: the runtime-A shape of k_ppo_loss_gauss (sigma once per thread)
         if (squash) GAUSS_LOSS_EX(0, false, true);
         else GAUSS_LOSS_EX(0, false, false);
     } else {        // state mode: one instance per action count
         switch (A) {
             GAUSS_LOSS_EX4(1) GAUSS_LOSS_EX4(2) GAUSS_LOSS_EX4(3) GAUSS_LOSS_EX4(4) GAUSS_LOSS_EX4(5) GAUSS_LOSS_EX4(6) GAUSS_LOSS_EX4(7)
-            GAUSS_LOSS_EX4(8) GAUSS_LOSS_EX4(9) GAUSS_LOSS_EX4(10) GAUSS_LOSS_EX4(11) GAUSS_LOSS_EX4(12) GAUSS_LOSS_EX4(13) GAUSS_LOSS_EX4(14)
-            GAUSS_LOSS_EX4(15) GAUSS_LOSS_EX4(16)
+            GAUSS_LOSS_EX4(8) GAUSS_LOSS_EX2(9) GAUSS_LOSS_EX2(10) GAUSS_LOSS_EX2(11) GAUSS_LOSS_EX2(12) GAUSS_LOSS_EX2(13) GAUSS_LOSS_EX2(14)
+            GAUSS_LOSS_EX2(15) GAUSS_LOSS_EX2(16)
         }
     }
+#undef GAUSS_LOSS_EX2
 #undef GAUSS_LOSS_EX4
 #undef GAUSS_LOSS_EX
+#undef GAUSS_LOSS_EXD
     // state mode: the two loss sums only (grad_log_std was written per row); param mode: the A log_std sums as well
-    hipLaunchKernelGGL(k_ppo_gauss_finish, dim3(state ? 2 : 2 + A), dim3(64), 0, st, (int)blocks, (const double *)workspace, active_sum, losses,
-                       grad_log_std);
+    const int nsum = state ? 2 : 2 + A;
+    if (diag)
+        hipLaunchKernelGGL(k_ppo_gauss_finish_diag, dim3(nsum + ppodiag::NSUM), dim3(64), 0, st, nsum, (int)blocks, (const double *)workspace,
+                           active_sum, losses, grad_log_std, diag);
+    else
+        hipLaunchKernelGGL(k_ppo_gauss_finish, dim3(nsum), dim3(64), 0, st, (int)blocks, (const double *)workspace, active_sum, losses,
+                           grad_log_std);
     return (int)hipGetLastError();
+}
+
+int ppo_loss_gauss_ex_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
+                              const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min,
+                              float log_std_max, int32_t squash, const float *action, const float *logp_old, const float *adv, const float *active,
+                              const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                              const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses, float *grad_values,
+                              void *workspace, void *stream) {
+    return ppo_loss_gauss_ex_launch(n, A, mu, grad_mu, d1, d2, m_s0, m_s1, m_s2, ls_raw, grad_log_std, l_s0, l_s1, l_s2, log_std_min, log_std_max,
+                                    squash, action, logp_old, adv, active, values_now, v_s0, v_s1, v_s2, values_old, v_target, active_sum, epsilon,
+                                    entropy_coef, use_value_clip, losses, grad_values, workspace, nullptr, stream);
+}
+
+int ppo_loss_gauss_ex_fwd_bwd_diag(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                                   int64_t m_s2, const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2,
+                                   float log_std_min, float log_std_max, int32_t squash, const float *action, const float *logp_old,
+                                   const float *adv, const float *active, const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2,
+                                   const float *values_old, const float *v_target, const float *active_sum, float epsilon, float entropy_coef,
+                                   int32_t use_value_clip, float *losses, float *grad_values, void *workspace, void *stream, double *diag) {
+    if (!diag) return MO_ERR_BAD_ARG;
+    return ppo_loss_gauss_ex_launch(n, A, mu, grad_mu, d1, d2, m_s0, m_s1, m_s2, ls_raw, grad_log_std, l_s0, l_s1, l_s2, log_std_min, log_std_max,
+                                    squash, action, logp_old, adv, active, values_now, v_s0, v_s1, v_s2, values_old, v_target, active_sum, epsilon,
+                                    entropy_coef, use_value_clip, losses, grad_values, workspace, diag, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include "mappo_ops_diag.h"
 #include "sb_common.hpp"
 #include "sb_wgrad.hpp"
+#include "ppo_diag.hpp"
 
 namespace {
 
@@ -1819,20 +1820,45 @@ __device__ __forceinline__ void ppo_block_sums(double sa, double sc, double *par
     if (threadIdx.x == 0) { partials[2 * blockIdx.x] = red[0][0]; partials[2 * blockIdx.x + 1] = red[1][0]; }
 }
 
+// DIAG (algo.update_diagnostics): a live row also takes the ppodiag::row step (csrc/ppo_diag.hpp) after its gradient stores, and the
+// eight sums leave through per-block f64 partials behind the loss partials (ppo_diag_block_sums).  The losses and gradients are the
+// same expressions in the same order, hence the same bytes, and the DIAG = false instances are the kernels as they were.
+// diagnostic partials: [gridDim.x][ppodiag::NSUM] f64; wave butterflies, then the four waves in a fixed order
+__device__ __forceinline__ void ppo_diag_block_sums(const double (&dg)[ppodiag::NSUM], double *dpart) {
+    __shared__ double dred[ppodiag::NSUM][4];
+#pragma unroll
+    for (int k = 0; k < ppodiag::NSUM; k++) {
+        double s = dg[k];
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        if ((threadIdx.x & 63) == 0) dred[k][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < ppodiag::NSUM) {
+        const int k = threadIdx.x;
+        dpart[(size_t)blockIdx.x * ppodiag::NSUM + k] = (dred[k][0] + dred[k][1]) + (dred[k][2] + dred[k][3]);
+    }
+}
+
+template <bool DIAG>
 __global__ __launch_bounds__(256) void k_ppo_loss(long n, const float *lp_now, const float *ent, const float *lp_old, const float *adv,
                                                   const float *active, const float *v_now, const float *v_old, const float *v_tgt,
                                                   const float *active_sum, float eps, float ent_coef, int value_clip, float *g_lp,
                                                   float *g_ent, float *g_v, double *partials) {
     const float inv = 1.f / active_sum[0];
     double sa = 0.0, sc = 0.0;
+    double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float act = active[i];
+        float d_lr = 0.f, d_ent = 0.f, d_vn = 0.f, d_vt = 0.f;
+        if (DIAG) { d_lr = lp_now[i] - lp_old[i]; d_ent = ent[i]; d_vn = v_now[i]; d_vt = v_tgt[i]; }
         const PpoElem e = ppo_elem(lp_now[i], ent[i], lp_old[i], adv[i], act, v_now[i], value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, ent_coef, value_clip);
         sa += (double)(e.la * act);
         sc += (double)(e.lc * act);
         g_lp[i] = e.g_lp; g_ent[i] = e.g_ent; g_v[i] = e.g_v;
+        if (DIAG && act != 0.f) ppodiag::row(dg, d_lr, expf(d_lr), d_ent, d_vn, d_vt, eps);
     }
     ppo_block_sums(sa, sc, partials);
+    if (DIAG) ppo_diag_block_sums(dg, partials + 2 * PPO_BLOCKS);
 }
 
 // The same loss from the policy's PROBABILITIES: torch.distributions.Categorical(prob) -- renormalisation, probs_to_logits' clamp to
@@ -1842,6 +1868,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss(long n, const float *lp_now, c
 // read through 3-D views (index (i0, i1, i2) of the (mini-batch, T, P) rows): the heads' outputs are time-major.
 struct PpoView { long d1, d2, s0, s1, s2; };
 constexpr int PPO_MAX_A = 16;
+template <bool DIAG>
 __global__ __launch_bounds__(256) void k_ppo_loss_prob(long n, int A, const float *__restrict__ prob, PpoView pv, const float *__restrict__ action,
                                                        const float *lp_old, const float *adv, const float *active, const float *__restrict__ v_now, PpoView vv,
                                                        const float *v_old, const float *v_tgt, const float *active_sum, float eps, float ent_coef,
@@ -1849,6 +1876,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_prob(long n, int A, const floa
     const float inv = 1.f / active_sum[0];
     constexpr float P_EPS = 1.1920928955078125e-07f;      // torch.finfo(torch.float32).eps (clamp_probs)
     double sa = 0.0, sc = 0.0;
+    double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const long i2 = i % pv.d2, i01 = i / pv.d2, i1 = i01 % pv.d1, i0 = i01 / pv.d1;
         const long po = i0 * pv.s0 + i1 * pv.s1 + i2 * pv.s2;
@@ -1868,6 +1896,9 @@ __global__ __launch_bounds__(256) void k_ppo_loss_prob(long n, int A, const floa
             }
         const float act = active[i];
         const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        float d_lr = 0.f, d_vt = 0.f;
+        const float d_ent = -plp;
+        if (DIAG) { d_lr = lp - lp_old[i]; d_vt = v_tgt[i]; }
         const PpoElem e = ppo_elem(lp, -plp, lp_old[i], adv[i], act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, ent_coef, value_clip);
         sa += (double)(e.la * act);
         sc += (double)(e.lc * act);
@@ -1885,15 +1916,46 @@ __global__ __launch_bounds__(256) void k_ppo_loss_prob(long n, int A, const floa
 #pragma unroll
         for (int k = 0; k < PPO_MAX_A; k++)
             if (k < A) g_prob[po + k] = (l[k] - dot) / s;                        // through probs = prob / prob.sum(-1)
+        // (after the stores: p[] and l[] are dead, the f64 expm1 has their registers)
+        if (DIAG && act != 0.f) ppodiag::row(dg, d_lr, expf(d_lr), d_ent, vn, d_vt, eps);
     }
     ppo_block_sums(sa, sc, partials);
+    if (DIAG) ppo_diag_block_sums(dg, partials + 2 * PPO_BLOCKS);
 }
 
-__global__ void k_ppo_loss_finish(int nblk, const double *partials, const float *active_sum, float *losses) {
+__device__ __forceinline__ void ppo_loss_finish_sums(int nblk, const double *partials, const float *active_sum, float *losses) {
     if (threadIdx.x < 2) {
         double s = 0.0;
         for (int b = 0; b < nblk; b++) s += partials[2 * b + threadIdx.x];
         losses[threadIdx.x] = (float)s / active_sum[0];
+    }
+}
+
+__global__ void k_ppo_loss_finish(int nblk, const double *partials, const float *active_sum, float *losses) {
+    ppo_loss_finish_sums(nblk, partials, active_sum, losses);
+}
+
+// diagnostic sum k of a DIAG launch, one wave: lane l adds the partials of blocks l, l + 64, .. in order, then a fixed butterfly
+// (as k_ppo_gauss_finish), and diag[k] += s -- the caller zeroes diag once per update, the launches of a stream run in order
+__device__ __forceinline__ void ppo_diag_finish_wave(int k, int nblk, const double *dpart, double *diag) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 64) s += dpart[(size_t)b * ppodiag::NSUM + k];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (threadIdx.x == 0) diag[k] += s;
+}
+
+// k_ppo_loss_finish in workgroup 0, the eight diagnostic sums in workgroups 1..8
+__global__ __launch_bounds__(64) void k_ppo_loss_finish_diag(int nblk, const double *partials, const float *active_sum, float *losses, double *diag) {
+    if (blockIdx.x == 0) ppo_loss_finish_sums(nblk, partials, active_sum, losses);
+    else ppo_diag_finish_wave(blockIdx.x - 1, nblk, partials + 2 * PPO_BLOCKS, diag);
+}
+
+// lr and ratio of every row exactly as ppo_elem forms them (fp32), for checks and probes that need those bits
+__global__ __launch_bounds__(256) void k_ppo_ratio(long n, const float *lp_now, const float *lp_old, float *lr, float *ratio) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float d = lp_now[i] - lp_old[i];
+        lr[i] = d;
+        ratio[i] = expf(d);
     }
 }
 
@@ -2919,20 +2981,73 @@ int rollout_record(int32_t N, int32_t n_items, const mo_record_item *items, cons
 }
 
 int64_t ppo_loss_workspace(void) { return (int64_t)PPO_BLOCKS * 2 * sizeof(double); }
+int64_t ppo_loss_diag_workspace(void) { return (int64_t)PPO_BLOCKS * (2 + ppodiag::NSUM) * sizeof(double); }
 
-int ppo_loss_fwd_bwd(int64_t n, const float *logp_now, const float *entropy, const float *logp_old, const float *adv, const float *active,
-                     const float *values_now, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
-                     float entropy_coef, int32_t use_value_clip, float *losses, float *grad_logp, float *grad_entropy, float *grad_values,
-                     void *workspace, void *stream) {
+// diag == nullptr: the plain launches; else the DIAG instance and the finish with eight more workgroups (two launches either way)
+static int ppo_loss_launch(int64_t n, const float *logp_now, const float *entropy, const float *logp_old, const float *adv, const float *active,
+                           const float *values_now, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
+                           float entropy_coef, int32_t use_value_clip, float *losses, float *grad_logp, float *grad_entropy, float *grad_values,
+                           void *workspace, double *diag, void *stream) {
     if (n < 1 || !logp_now || !entropy || !logp_old || !adv || !active || !values_now || !v_target || !active_sum || !losses || !grad_logp ||
         !grad_entropy || !grad_values || !workspace || (use_value_clip && !values_old))
         return MO_ERR_BAD_ARG;
     long blocks = (n + 255) / 256;
     if (blocks > PPO_BLOCKS) blocks = PPO_BLOCKS;
-    hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long)n, logp_now, entropy, logp_old, adv, active,
-                       values_now, values_old, v_target, active_sum, epsilon, entropy_coef, (int)use_value_clip, grad_logp, grad_entropy,
-                       grad_values, (double *)workspace);
-    hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, (int)blocks, (const double *)workspace, active_sum, losses);
+#define PPO_LOSS(D) hipLaunchKernelGGL((k_ppo_loss<D>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long)n, logp_now, entropy, logp_old, \
+                                       adv, active, values_now, values_old, v_target, active_sum, epsilon, entropy_coef, (int)use_value_clip, \
+                                       grad_logp, grad_entropy, grad_values, (double *)workspace)
+    if (diag) {
+        PPO_LOSS(true);
+        hipLaunchKernelGGL(k_ppo_loss_finish_diag, dim3(1 + ppodiag::NSUM), dim3(64), 0, (hipStream_t)stream, (int)blocks, (const double *)workspace,
+                           active_sum, losses, diag);
+    } else {
+        PPO_LOSS(false);
+        hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, (int)blocks, (const double *)workspace, active_sum, losses);
+    }
+#undef PPO_LOSS
+    return (int)hipGetLastError();
+}
+
+int ppo_loss_fwd_bwd(int64_t n, const float *logp_now, const float *entropy, const float *logp_old, const float *adv, const float *active,
+                     const float *values_now, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
+                     float entropy_coef, int32_t use_value_clip, float *losses, float *grad_logp, float *grad_entropy, float *grad_values,
+                     void *workspace, void *stream) {
+    return ppo_loss_launch(n, logp_now, entropy, logp_old, adv, active, values_now, values_old, v_target, active_sum, epsilon, entropy_coef,
+                           use_value_clip, losses, grad_logp, grad_entropy, grad_values, workspace, nullptr, stream);
+}
+
+int ppo_loss_fwd_bwd_diag(int64_t n, const float *logp_now, const float *entropy, const float *logp_old, const float *adv, const float *active,
+                          const float *values_now, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
+                          float entropy_coef, int32_t use_value_clip, float *losses, float *grad_logp, float *grad_entropy, float *grad_values,
+                          void *workspace, void *stream, double *diag) {
+    if (!diag) return MO_ERR_BAD_ARG;
+    return ppo_loss_launch(n, logp_now, entropy, logp_old, adv, active, values_now, values_old, v_target, active_sum, epsilon, entropy_coef,
+                           use_value_clip, losses, grad_logp, grad_entropy, grad_values, workspace, diag, stream);
+}
+
+static int ppo_loss_prob_launch(int64_t n, int32_t A, const float *prob, float *grad_prob, int64_t d1, int64_t d2, int64_t p_s0, int64_t p_s1,
+                                int64_t p_s2, const float *action, const float *logp_old, const float *adv, const float *active,
+                                const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                                const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses,
+                                float *grad_values, void *workspace, double *diag, void *stream) {
+    if (n < 1 || A < 1 || A > PPO_MAX_A || d1 < 1 || d2 < 1 || (n % (d1 * d2)) || !prob || !grad_prob || !action || !logp_old || !adv || !active ||
+        !values_now || !v_target || !active_sum || !losses || !grad_values || !workspace || (use_value_clip && !values_old))
+        return MO_ERR_BAD_ARG;
+    long blocks = (n + 255) / 256;
+    if (blocks > PPO_BLOCKS) blocks = PPO_BLOCKS;
+    const PpoView pv{d1, d2, p_s0, p_s1, p_s2}, vv{d1, d2, v_s0, v_s1, v_s2};
+#define PPO_LOSS_PROB(D) hipLaunchKernelGGL((k_ppo_loss_prob<D>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long)n, (int)A, prob, pv, \
+                                            action, logp_old, adv, active, values_now, vv, values_old, v_target, active_sum, epsilon, entropy_coef, \
+                                            (int)use_value_clip, grad_prob, grad_values, (double *)workspace)
+    if (diag) {
+        PPO_LOSS_PROB(true);
+        hipLaunchKernelGGL(k_ppo_loss_finish_diag, dim3(1 + ppodiag::NSUM), dim3(64), 0, (hipStream_t)stream, (int)blocks, (const double *)workspace,
+                           active_sum, losses, diag);
+    } else {
+        PPO_LOSS_PROB(false);
+        hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, (int)blocks, (const double *)workspace, active_sum, losses);
+    }
+#undef PPO_LOSS_PROB
     return (int)hipGetLastError();
 }
 
@@ -2940,17 +3055,42 @@ int ppo_loss_prob_fwd_bwd(int64_t n, int32_t A, const float *prob, float *grad_p
                           const float *action, const float *logp_old, const float *adv, const float *active, const float *values_now, int64_t v_s0,
                           int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
                           float entropy_coef, int32_t use_value_clip, float *losses, float *grad_values, void *workspace, void *stream) {
-    if (n < 1 || A < 1 || A > PPO_MAX_A || d1 < 1 || d2 < 1 || (n % (d1 * d2)) || !prob || !grad_prob || !action || !logp_old || !adv || !active ||
-        !values_now || !v_target || !active_sum || !losses || !grad_values || !workspace || (use_value_clip && !values_old))
-        return MO_ERR_BAD_ARG;
+    return ppo_loss_prob_launch(n, A, prob, grad_prob, d1, d2, p_s0, p_s1, p_s2, action, logp_old, adv, active, values_now, v_s0, v_s1, v_s2,
+                                values_old, v_target, active_sum, epsilon, entropy_coef, use_value_clip, losses, grad_values, workspace, nullptr,
+                                stream);
+}
+
+int ppo_loss_prob_fwd_bwd_diag(int64_t n, int32_t A, const float *prob, float *grad_prob, int64_t d1, int64_t d2, int64_t p_s0, int64_t p_s1,
+                               int64_t p_s2, const float *action, const float *logp_old, const float *adv, const float *active,
+                               const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                               const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses,
+                               float *grad_values, void *workspace, void *stream, double *diag) {
+    if (!diag) return MO_ERR_BAD_ARG;
+    return ppo_loss_prob_launch(n, A, prob, grad_prob, d1, d2, p_s0, p_s1, p_s2, action, logp_old, adv, active, values_now, v_s0, v_s1, v_s2,
+                                values_old, v_target, active_sum, epsilon, entropy_coef, use_value_clip, losses, grad_values, workspace, diag,
+                                stream);
+}
+
+int ppo_ratio(int64_t n, const float *logp_now, const float *logp_old, float *lr, float *ratio, void *stream) {
+    if (n < 0 || !logp_now || !logp_old || !lr || !ratio) return MO_ERR_BAD_ARG;
+    if (n == 0) return 0;
     long blocks = (n + 255) / 256;
     if (blocks > PPO_BLOCKS) blocks = PPO_BLOCKS;
-    const PpoView pv{d1, d2, p_s0, p_s1, p_s2}, vv{d1, d2, v_s0, v_s1, v_s2};
-    hipLaunchKernelGGL(k_ppo_loss_prob, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long)n, (int)A, prob, pv, action, logp_old, adv, active,
-                       values_now, vv, values_old, v_target, active_sum, epsilon, entropy_coef, (int)use_value_clip, grad_prob, grad_values,
-                       (double *)workspace);
-    hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, (int)blocks, (const double *)workspace, active_sum, losses);
+    hipLaunchKernelGGL(k_ppo_ratio, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (long)n, logp_now, logp_old, lr, ratio);
     return (int)hipGetLastError();
+}
+
+// ppodiag::row on the host, one row per output line: terms [n][8] (an inactive row's line is 0).  The CPU checks compare it with
+// the numpy restatement bit for bit.
+int ppo_diag_rows_host(int64_t n, const float *lr, const float *ratio, const float *ent, const float *v_now, const float *v_tgt,
+                       const float *active, float eps, double *terms) {
+    if (n < 0 || !lr || !ratio || !ent || !v_now || !v_tgt || !active || !terms) return MO_ERR_BAD_ARG;
+    for (int64_t i = 0; i < n; i++) {
+        double acc[ppodiag::NSUM] = {};
+        if (active[i] != 0.f) ppodiag::row(acc, lr[i], ratio[i], ent[i], v_now[i], v_tgt[i], eps);
+        for (int k = 0; k < ppodiag::NSUM; k++) terms[i * ppodiag::NSUM + k] = acc[k];
+    }
+    return 0;
 }
 
 const char *mappo_ops_error_string(int code) {

@@ -25,6 +25,7 @@ from torch.nn.utils import spectral_norm
 from . import ops
 from . import value_norm as vnorm
 from .reward_shaping import reward_shaping_options
+from .update_diag import LOG_KEYS, UpdateDiag, first_epoch_over, update_diag_options
 from .e3d_env import ParticleEnv
 from .model import HeadLinear, _make_linear, _ortho_linear, _Trunk
 from .trainer import (GradBucket, ParticleRunState, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed,
@@ -123,6 +124,7 @@ class E3dMAPPO:
         self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
         self.reward_shaping, self.shaping_coef = reward_shaping_options(cfg)   # distance shaping in policy_record
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
+        self.update_diagnostics, self.target_kl = update_diag_options(cfg)   # what the update did, from the loss launches
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
         self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
@@ -141,6 +143,8 @@ class E3dMAPPO:
         self.ac_parameters = list(self.actor.parameters()) + list(self.critic.parameters())
         self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
         self.value_norm = vnorm.ValueNorm(self.value_norm_beta, self.device) if self.use_value_norm else None
+        self.diag = UpdateDiag(self.device) if self.update_diagnostics else None
+        self.last_update_diag = None   # algo.update_diagnostics: the dict of the last train() call
         rt = cfg.get("runtime", {})
         self.sample_seed = int(rt.get("seed", 0))
         self.sample_rank = int(rt.get("sample_rank", 0))   # Philox counter of rank r starts at r << 40 (as MAPPO)
@@ -275,25 +279,33 @@ class E3dMAPPO:
             self.ac_optimizer.zero_grad()
         obj_c = obj_a = 0.0
         k = 0
+        diag = self.diag   # algo.update_diagnostics: every loss call adds its eight sums (None: the plain calls)
+        if diag is not None:
+            diag.begin()
         for n0 in range(0, N, self.mini_batch_size):
             n1 = min(n0 + self.mini_batch_size, N)
             mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, T, return_ls_raw=True)
             args = (buf["a_n"][n0:n1], values, buf["a_logprob_n"][n0:n1], adv[n0:n1], buf["active"][n0:n1],
                     buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1], self.epsilon, self.entropy_coef,
                     self.use_value_clip)
+            dk = {} if diag is None else {"diag": diag.sums}
             if self.policy_ex:
                 la, lc = ops.ppo_loss_gauss_ex(mu, ls_raw, *args, log_std_min=self.log_std_min, log_std_max=self.log_std_max,
-                                               squash=self.gauss_squash)
+                                               squash=self.gauss_squash, **dk)
             else:
-                la, lc = ops.ppo_loss_gauss(mu, ls_raw, *args)
+                la, lc = ops.ppo_loss_gauss(mu, ls_raw, *args, **dk)
             (la + lc).backward()
             if self.use_grad_clip:
-                torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
+                norm = torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
+                if diag is not None:
+                    diag.note_grad_norm(norm)
             obj_c = obj_c + lc.detach().double()
             obj_a = obj_a + la.detach().double()
             k += 1
         if self.use_lr_decay:
             self.lr_decay(total_steps)
+        if diag is not None:   # one read for the two losses, the eight sums (all-reduced over ranks) and the gradient norm
+            (obj_c, obj_a), self.last_update_diag = diag.read(obj_c, obj_a)
         return float(obj_c) / k, float(obj_a) / k
 
     def lr_decay(self, total_steps):
@@ -380,6 +392,9 @@ class E3dTrainer(ParticleRunState):
         self.agent.grad_bucket = self.bucket
         if self.agent.value_norm is not None:
             self.agent.value_norm.allreduce = allreduce_sum_   # (S1, S2, c) over ranks; without a process group a no-op
+        if self.agent.diag is not None:
+            self.agent.diag.allreduce = allreduce_sum_         # the eight diagnostic sums over ranks, likewise
+        self.last_epoch_diags = []
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
         self.eval_env = None
@@ -396,16 +411,26 @@ class E3dTrainer(ParticleRunState):
         mean_r, buf, steps, stats = agent.explore_env(self.env)
         ev[1].record()
         self.total_steps += steps * self.world
+        self.last_epoch_diags, epochs_run = [], 0
         for _ in range(int(cfg.algo.epochs)):
             with torch.enable_grad():
                 obj_c, obj_a = agent.train(buf, self.total_steps)
+            if agent.diag is not None:
+                self.last_epoch_diags.append(agent.last_update_diag)
+                # algo.target_kl: the policy has moved past the target on this buffer -- this epoch's gradient is discarded (the next
+                # train() zeroes the bucket) and the remaining epochs are skipped; the sums are all-reduced, so every rank stops here
+                if first_epoch_over([agent.last_update_diag["approx_kl"]], agent.target_kl) is not None:
+                    break
             allreduce_sum_(self.bucket.flat)
             agent.ac_optimizer.step()
+            epochs_run += 1
         ev[2].record()
         self.iteration += 1
         self.last_events = ev
         log = dict(iteration=self.iteration, total_steps=self.total_steps, mean_return=mean_r, capture_rate=stats["capture_rate"],
                    episode_length=stats["episode_length"], critic_loss=obj_c, actor_loss=obj_a)
+        if agent.diag is not None:   # of the last train() call, like the two losses
+            log.update({k: agent.last_update_diag[k] for k in LOG_KEYS}, epochs_run=epochs_run)
         if self.eval_every and self.iteration % self.eval_every == 0 and self.rank == 0:
             log.update(self.evaluate())
         return steps * self.world, log

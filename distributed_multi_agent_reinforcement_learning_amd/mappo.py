@@ -20,6 +20,7 @@ import torch
 from . import ops
 from .model import build_actor_critic, pair_embeddings, pair_heads, sequence_forward_pair
 from .pe_env import status_or, status_text
+from .update_diag import UpdateDiag, update_diag_options
 
 _log = logging.getLogger(__name__)
 
@@ -211,6 +212,10 @@ class MAPPO:
         if bool(a.get("use_value_norm", False)):
             raise ValueError("algo.use_value_norm: true is built for runtime.env n2n and e3d only; the pursuit update is pinned to the "
                              "reference's (set use_value_norm to false)")
+        if a.get("target_kl", None) is not None:
+            raise ValueError("algo.target_kl is built for runtime.env n2n and e3d only; the pursuit update schedule is pinned to the "
+                             "reference's (leave target_kl out; algo.update_diagnostics reports the KL)")
+        self.update_diagnostics, _ = update_diag_options(cfg)   # what the update did, from the loss launches
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
         self.epsilon, self.K_epochs, self.entropy_coef = a.epsilon, a.epochs, a.entropy_coef
         self.use_grad_clip, self.use_lr_decay = a.use_grad_clip, a.use_lr_decay
@@ -253,6 +258,8 @@ class MAPPO:
         # the reference stores every tick's embedding regardless, DHGN/mappo_parallel.py:795-798).  true = record them anyway.
         self.record_unused_embeddings = bool(rt.get("record_unused_embeddings", False))
         self.last_adv = self.last_v_target = None
+        self.diag = UpdateDiag(self.device) if self.update_diagnostics else None
+        self.last_update_diag = None   # algo.update_diagnostics: the dict of the last train() call
 
     # ---- update (:638-723) ------------------------------------------------------------------------------------
     def train(self, replay_buffer, total_steps, return_grads=True):
@@ -270,6 +277,8 @@ class MAPPO:
             self.grad_bucket.zero()          # persistent flat gradient storage (trainer.GradBucket): zeroed, not dropped
         else:
             self.ac_optimizer.zero_grad()
+        if self.diag is not None:   # algo.update_diagnostics: every loss call adds its eight sums (_minibatch_losses)
+            self.diag.begin()
         starts = list(range(0, N, self.mini_batch_size))  # BatchSampler(SequentialSampler, mini_batch_size, drop_last=False)
         G = self._update_group(len(starts), min(self.mini_batch_size, N) * P, T)
         while G > 1:
@@ -288,6 +297,8 @@ class MAPPO:
                     self.grad_bucket.zero()
                 else:
                     self.ac_optimizer.zero_grad()
+                if self.diag is not None:
+                    self.diag.begin()
                 torch.cuda.empty_cache()
         for n0 in starts:
             n1 = min(n0 + self.mini_batch_size, N)
@@ -301,10 +312,14 @@ class MAPPO:
             actor_loss, critic_loss = self._minibatch_losses(batch, adv, v_target, n0, n1, prob, values_now)
             (actor_loss + critic_loss).backward()
             if self.use_grad_clip:  # on the gradients accumulated so far, after every mini-batch
-                torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
+                norm = torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
+                if self.diag is not None:
+                    self.diag.note_grad_norm(norm)
             object_critics = object_critics + critic_loss.detach().double()   # f64 sum on the device: no host sync per mini-batch
             object_actors = object_actors + actor_loss.detach().double()
             update_time += 1
+        if self.diag is not None:   # one read for the two losses, the eight sums and the gradient norm
+            (object_critics, object_actors), self.last_update_diag = self.diag.read(object_critics, object_actors)
         object_critics, object_actors = float(object_critics), float(object_actors)
         if self.use_lr_decay:
             self.lr_decay(total_steps)
@@ -327,15 +342,16 @@ class MAPPO:
 
     def _minibatch_losses(self, batch, adv, v_target, n0, n1, prob, values_now):
         v_old = batch["v_n"][n0:n1, :-1] if self.use_value_clip else None
+        dk = {} if self.diag is None else {"diag": self.diag.sums}   # algo.update_diagnostics: the loss call adds its eight sums
         if ops.ppo_loss_prob_ok(prob, values_now.squeeze(-1)):
             # Categorical(prob).log_prob / .entropy() (get_logprob_and_entropy, :451-456) evaluated inside the loss launch
             return ops.ppo_loss_prob(prob, batch["a_n"][n0:n1], values_now.squeeze(-1), batch["a_logprob_n"][n0:n1], adv[n0:n1], batch["active"][n0:n1],
-                                     v_old, v_target[n0:n1], self.epsilon, self.entropy_coef, self.use_value_clip)
+                                     v_old, v_target[n0:n1], self.epsilon, self.entropy_coef, self.use_value_clip, **dk)
         dist = torch.distributions.Categorical(prob)      # get_logprob_and_entropy (:451-456)
         a_logprob_n_now, dist_entropy = dist.log_prob(batch["a_n"][n0:n1]), dist.entropy()
         return ops.ppo_loss(a_logprob_n_now, dist_entropy, values_now.squeeze(-1), batch["a_logprob_n"][n0:n1], adv[n0:n1],
                             batch["active"][n0:n1], batch["v_n"][n0:n1, :-1] if self.use_value_clip else None,
-                            v_target[n0:n1], self.epsilon, self.entropy_coef, self.use_value_clip)
+                            v_target[n0:n1], self.epsilon, self.entropy_coef, self.use_value_clip, **dk)
 
     def _update_group(self, n_minibatches, rows, T):
         """how many consecutive mini-batches run as one autograd graph (`runtime.update_group`: an int, or "auto" = all of them:
@@ -405,7 +421,9 @@ class MAPPO:
             for k, (actor_loss, critic_loss) in enumerate(losses):
                 torch._foreach_add_(main_grads, segs.grads(k))
                 if self.use_grad_clip:  # on the gradients accumulated so far, after every mini-batch
-                    torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
+                    norm = torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
+                    if self.diag is not None:
+                        self.diag.note_grad_norm(norm)
                 object_critics = object_critics + critic_loss.detach().double()
                 object_actors = object_actors + actor_loss.detach().double()
         return object_critics, object_actors

@@ -18,7 +18,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "gru_gates_fwd", "gru_gates_bwd", "gru_cell_fwd", "gru_cell_fwd_multi", "gru_cell_split_fwd_multi", "sb_gemm_n128", "sb_gemm", "gru_seq_fwd", "gru_seq_fwd_multi", "gru_seq_split_fwd_multi", "gru_seq_split_bwd_multi", "gru_seq_save_elems", "gru_seq_bwd", "gru_seq_bwd_multi", "gru_seq_bwd_workspace", "wgrad_tn", "wgrad_tn_workspace", "wgrad_split_tn", "wgrad_split_tn2", "wgrad_split_workspace", "rollout_record", "ppo_loss_fwd_bwd", "ppo_loss_prob_fwd_bwd", "ppo_loss_workspace",
            "gauss_head_sample", "ppo_loss_gauss_fwd_bwd", "ppo_loss_gauss_workspace", "gauss_head_sample_ex", "ppo_loss_gauss_ex_fwd_bwd",
            "ppo_loss_gauss_ex_workspace", "gae_advnorm_vn", "gae_advnorm_vn_workspace", "value_norm_update", "value_norm_targets",
-           "mappo_ops_error_string")
+           "ppo_loss_fwd_bwd_diag", "ppo_loss_prob_fwd_bwd_diag", "ppo_loss_gauss_fwd_bwd_diag", "ppo_loss_gauss_ex_fwd_bwd_diag",
+           "ppo_loss_diag_workspace", "ppo_loss_gauss_diag_workspace", "ppo_ratio", "ppo_diag_rows_host", "mappo_ops_error_string")
 
 _lib = None
 
@@ -110,6 +111,12 @@ def load_library():
         L.ppo_loss_gauss_ex_workspace.restype = i64
         L.ppo_loss_gauss_ex_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, f32, f32, i32, vp, vp, vp, vp,
                                                 vp, i64, i64, i64, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp]
+        for name in ("ppo_loss_fwd_bwd", "ppo_loss_prob_fwd_bwd", "ppo_loss_gauss_fwd_bwd", "ppo_loss_gauss_ex_fwd_bwd"):
+            getattr(L, name + "_diag").argtypes = getattr(L, name).argtypes + [vp]   # the plain call's arguments plus double *diag
+        L.ppo_loss_diag_workspace.restype = i64
+        L.ppo_loss_gauss_diag_workspace.restype = i64
+        L.ppo_ratio.argtypes = [i64, vp, vp, vp, vp, vp]
+        L.ppo_diag_rows_host.argtypes = [i64, vp, vp, vp, vp, vp, vp, f32, vp]
         L.sb_split_diag.argtypes = [i64, vp, vp, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
@@ -1261,11 +1268,26 @@ def fcra_hop(nb, h, carry, Wagg, bagg, Wf, bf, last, out=None):
 
 
 FUSED_CELL_MIN_ROWS = 1024  # single-step batches at least this large take the fused cell kernel
+
+
+PPO_DIAG_SUMS = 8   # csrc/ppo_diag.hpp: count, k3 KL, clipped, entropy, v_target, v_target^2, (v_target - v_now)^2, ratio
+
+
+def _diag_variant(L, name, plain_ws, diag_ws, diag, dev):
+    """-> (entry point, workspace bytes, trailing arguments) of a loss call: the plain one for diag None, else the _diag entry point
+    with the (8,) f64 device tensor the sums are added to"""
+    if diag is None:
+        return getattr(L, name), plain_ws(), ()
+    assert diag.dtype == torch.float64 and diag.shape == (PPO_DIAG_SUMS,) and diag.is_contiguous() and diag.device == dev
+    return getattr(L, name + "_diag"), diag_ws(), (_ptr(diag),)
+
+
 class _PPOLoss(torch.autograd.Function):
     """(actor_loss, critic_loss) of one mini-batch; the gradients are computed in the forward launch and scaled here."""
 
     @staticmethod
-    def forward(ctx, logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip):
+    def forward(ctx, logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
+                diag=None):
         L = load_library()
         _need_gpu(logp_now, "ppo_loss")
         ts = [t.contiguous() for t in (logp_now, entropy, logp_old, adv, active, values_now, v_target)]
@@ -1276,17 +1298,18 @@ class _PPOLoss(torch.autograd.Function):
         asum = active.sum().reshape(1)
         losses = torch.empty(2, dtype=torch.float32, device=dev)
         g = torch.empty((3,) + tuple(logp_now.shape), dtype=torch.float32, device=dev)
-        ws = torch.empty(L.ppo_loss_workspace(), dtype=torch.uint8, device=dev)
-        _check(L.ppo_loss_fwd_bwd(n, _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]), _ptr(ts[4]), _ptr(ts[5]), _ptr(vo), _ptr(ts[6]),
-                                  _ptr(asum), float(epsilon), float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g[0]),
-                                  _ptr(g[1]), _ptr(g[2]), _ptr(ws), _stream()), "ppo_loss_fwd_bwd")
+        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_fwd_bwd", L.ppo_loss_workspace, L.ppo_loss_diag_workspace, diag, dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _check(fn(n, _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]), _ptr(ts[4]), _ptr(ts[5]), _ptr(vo), _ptr(ts[6]),
+                  _ptr(asum), float(epsilon), float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g[0]),
+                  _ptr(g[1]), _ptr(g[2]), _ptr(ws), _stream(), *extra), "ppo_loss_fwd_bwd")
         ctx.save_for_backward(g)
         return losses[0], losses[1]
 
     @staticmethod
     def backward(ctx, ga, gc):
         (g,) = ctx.saved_tensors
-        return g[0] * ga, g[1] * ga, g[2] * gc, None, None, None, None, None, None, None, None
+        return g[0] * ga, g[1] * ga, g[2] * gc, None, None, None, None, None, None, None, None, None
 
 
 class _PPOLossProb(torch.autograd.Function):
@@ -1294,7 +1317,7 @@ class _PPOLossProb(torch.autograd.Function):
     loss launch (ppo_loss_prob_fwd_bwd), which also writes the gradient with respect to prob."""
 
     @staticmethod
-    def forward(ctx, prob, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip):
+    def forward(ctx, prob, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip, diag=None):
         L = load_library()
         _need_gpu(prob, "ppo_loss_prob")
         A = prob.shape[-1]
@@ -1308,18 +1331,19 @@ class _PPOLossProb(torch.autograd.Function):
         losses = torch.empty(2, dtype=torch.float32, device=dev)
         g_prob = torch.empty_strided(prob.shape, prob.stride(), dtype=torch.float32, device=dev)    # the layout of prob (a time-major view)
         g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.ppo_loss_workspace(), dtype=torch.uint8, device=dev)
+        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_prob_fwd_bwd", L.ppo_loss_workspace, L.ppo_loss_diag_workspace, diag, dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         ps, vs = prob.stride(), values_now.stride()
-        _check(L.ppo_loss_prob_fwd_bwd(n, A, _ptr(prob), _ptr(g_prob), d1, d2, ps[0], ps[1], ps[2], _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]),
-                                       _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[4]), _ptr(asum), float(epsilon), float(entropy_coef),
-                                       int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream()), "ppo_loss_prob_fwd_bwd")
+        _check(fn(n, A, _ptr(prob), _ptr(g_prob), d1, d2, ps[0], ps[1], ps[2], _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]),
+                  _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[4]), _ptr(asum), float(epsilon), float(entropy_coef),
+                  int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream(), *extra), "ppo_loss_prob_fwd_bwd")
         ctx.save_for_backward(g_prob, g_v)
         return losses[0], losses[1]
 
     @staticmethod
     def backward(ctx, ga, gc):
         g_prob, g_v = ctx.saved_tensors
-        return g_prob * ga, g_v * gc, None, None, None, None, None, None, None, None, None
+        return g_prob * ga, g_v * gc, None, None, None, None, None, None, None, None, None, None
 
 
 PPO_FROM_PROB = os.environ.get("MAPPO_PPO_FROM_PROB", "1") != "0"   # A/B switch: off = torch.distributions.Categorical + ppo_loss
@@ -1330,11 +1354,11 @@ def ppo_loss_prob_ok(prob, values_now):
             and values_now.dtype == torch.float32 and values_now.shape == prob.shape[:3] and prob.numel() > 0)
 
 
-def ppo_loss_prob(prob, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True):
+def ppo_loss_prob(prob, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True, diag=None):
     """ppo_loss(Categorical(prob).log_prob(action), Categorical(prob).entropy(), ...) in one launch (DHGN/mappo_parallel.py:451-456,
     :692-706; csrc/mappo_ops.hip k_ppo_loss_prob).  prob (mb, T, P, A), values_now (mb, T, P): any strides over the first three
-    dimensions (the heads' outputs are time-major views)."""
-    return _PPOLossProb.apply(prob, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip)
+    dimensions (the heads' outputs are time-major views).  diag: see ppo_loss."""
+    return _PPOLossProb.apply(prob, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip, diag)
 
 
 class _PPOLossGauss(torch.autograd.Function):
@@ -1342,7 +1366,8 @@ class _PPOLossGauss(torch.autograd.Function):
     .entropy().sum(-1) inside the loss launch (ppo_loss_gauss_fwd_bwd), which also writes the gradients w.r.t. mu and log_std."""
 
     @staticmethod
-    def forward(ctx, mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip):
+    def forward(ctx, mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
+                diag=None):
         L = load_library()
         _need_gpu(mu, "ppo_loss_gauss")
         A = mu.shape[-1]
@@ -1360,11 +1385,12 @@ class _PPOLossGauss(torch.autograd.Function):
         g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)      # the layout of mu (a time-major view)
         g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
         g_ls = torch.empty(A, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.ppo_loss_gauss_workspace(), dtype=torch.uint8, device=dev)
+        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_gauss_fwd_bwd", L.ppo_loss_gauss_workspace, L.ppo_loss_gauss_diag_workspace, diag, dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         ms, vs = mu.stride(), values_now.stride()
-        _check(L.ppo_loss_gauss_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(act), _ptr(ts[0]), _ptr(ts[1]),
-                                        _ptr(ts[2]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon),
-                                        float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(g_ls), _ptr(ws), _stream()),
+        _check(fn(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(act), _ptr(ts[0]), _ptr(ts[1]),
+                  _ptr(ts[2]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon),
+                  float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(g_ls), _ptr(ws), _stream(), *extra),
                "ppo_loss_gauss_fwd_bwd")
         ctx.save_for_backward(g_mu, g_ls, g_v)
         return losses[0], losses[1]
@@ -1372,14 +1398,17 @@ class _PPOLossGauss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ga, gc):
         g_mu, g_ls, g_v = ctx.saved_tensors
-        return g_mu * ga, g_ls * ga, g_v * gc, None, None, None, None, None, None, None, None, None
+        return g_mu * ga, g_ls * ga, g_v * gc, None, None, None, None, None, None, None, None, None, None
 
 
-def ppo_loss_gauss(mu, log_std, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True):
+def ppo_loss_gauss(mu, log_std, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True,
+                   diag=None):
     """ppo_loss(Normal(mu, exp(log_std)).log_prob(action).sum(-1), Normal(..).entropy().sum(-1), ...) in one launch with the gradients
     w.r.t. mu, log_std and values_now (csrc/gauss_policy.hpp k_ppo_loss_gauss).  mu (mb, T, P, A) and values_now (mb, T, P): any strides
-    over the first three dimensions (time-major views), mu's last dimension dense; action (mb, T, P, A), the rest (mb, T, P)."""
-    return _PPOLossGauss.apply(mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip)
+    over the first three dimensions (time-major views), mu's last dimension dense; action (mb, T, P, A), the rest (mb, T, P).
+    diag: see ppo_loss."""
+    return _PPOLossGauss.apply(mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
+                               diag)
 
 
 class _PPOLossGaussEx(torch.autograd.Function):
@@ -1388,7 +1417,7 @@ class _PPOLossGaussEx(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
-                log_std_min, log_std_max, squash):
+                log_std_min, log_std_max, squash, diag=None):
         L = load_library()
         _need_gpu(mu, "ppo_loss_gauss_ex")
         A = mu.shape[-1]
@@ -1415,12 +1444,14 @@ class _PPOLossGaussEx(torch.autograd.Function):
         losses = torch.empty(2, dtype=torch.float32, device=dev)
         g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)
         g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.ppo_loss_gauss_ex_workspace(), dtype=torch.uint8, device=dev)
+        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_gauss_ex_fwd_bwd", L.ppo_loss_gauss_ex_workspace, L.ppo_loss_gauss_diag_workspace, diag,
+                                            dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         ms, vs = mu.stride(), values_now.stride()
-        _check(L.ppo_loss_gauss_ex_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
-                                           float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], _ptr(act), _ptr(ts[0]), _ptr(ts[1]),
-                                           _ptr(ts[2]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon),
-                                           float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream()),
+        _check(fn(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
+                  float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], _ptr(act), _ptr(ts[0]), _ptr(ts[1]),
+                  _ptr(ts[2]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon),
+                  float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream(), *extra),
                "ppo_loss_gauss_ex_fwd_bwd")
         ctx.save_for_backward(g_mu, g_ls, g_v)
         return losses[0], losses[1]
@@ -1428,24 +1459,36 @@ class _PPOLossGaussEx(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ga, gc):
         g_mu, g_ls, g_v = ctx.saved_tensors
-        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 12
+        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 13
 
 
 def ppo_loss_gauss_ex(mu, ls_raw, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True,
-                      log_std_min=-float("inf"), log_std_max=float("inf"), squash="clip"):
+                      log_std_min=-float("inf"), log_std_max=float("inf"), squash="clip", diag=None):
     """ppo_loss_gauss with ls = clamp(ls_raw, log_std_min, log_std_max) and optional tanh squashing (csrc/gauss_policy.hpp
     k_ppo_loss_gauss_ex).  ls_raw: the (A,) vector (param mode) or a tensor of mu's shape (state mode, any strides over the first three
     dimensions, the last dense).  action holds the unsquashed samples u; with squash "tanh" the log-probability subtracts
     sum log(1 - tanh(u)^2), which carries no gradient.  Gradients flow to mu, ls_raw (0 where ls_raw is outside the bounds) and
-    values_now."""
+    values_now.  diag: see ppo_loss."""
     return _PPOLossGaussEx.apply(mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef,
-                                 use_value_clip, log_std_min, log_std_max, squash)
+                                 use_value_clip, log_std_min, log_std_max, squash, diag)
 
 
-def ppo_loss(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True):
+def ppo_loss(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True, diag=None):
     """Masked-mean PPO policy loss and (clipped) value loss of a mini-batch, one launch with the gradients
-    (DHGN/mappo_parallel.py:692-706; csrc/mappo_ops.hip k_ppo_loss)."""
-    return _PPOLoss.apply(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip)
+    (DHGN/mappo_parallel.py:692-706; csrc/mappo_ops.hip k_ppo_loss).  diag: None, or an (8,) f64 device tensor to which the call adds
+    the update diagnostics' sums over its live rows (csrc/ppo_diag.hpp) in the same two launches; losses and gradients keep their bytes."""
+    return _PPOLoss.apply(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip, diag)
+
+
+def ppo_ratio(logp_now, logp_old):
+    """-> (lr, ratio): the fp32 logp_now - logp_old and expf of it, exactly as the loss kernels form them"""
+    L = load_library()
+    _need_gpu(logp_now, "ppo_ratio")
+    a, b = logp_now.contiguous(), logp_old.contiguous()
+    assert a.dtype == b.dtype == torch.float32 and a.shape == b.shape
+    lr, ratio = torch.empty_like(a), torch.empty_like(a)
+    _check(L.ppo_ratio(a.numel(), _ptr(a), _ptr(b), _ptr(lr), _ptr(ratio), _stream()), "ppo_ratio")
+    return lr, ratio
 
 
 class RecordItem(C.Structure):

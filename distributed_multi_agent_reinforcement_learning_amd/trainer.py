@@ -6,6 +6,7 @@ parameter-server sum of numpy lists through the Ray object store (main.py:105-12
 single flat fp32 bucket (~0.6 M elements) over xGMI; weights are never re-broadcast because every rank applies the
 identical update.  Rollout data never leaves the GPU that produced it.
 """
+import json
 import os
 import time
 
@@ -250,6 +251,8 @@ class Trainer:
         self.agent.sample_rank = self.rank  # disjoint action-sampling streams per rank (mappo.MAPPO.sample_rank)
         self.bucket = GradBucket(self.agent.ac_parameters)   # .grad of every parameter lives in one flat tensor
         self.agent.grad_bucket = self.bucket
+        if self.agent.diag is not None:
+            self.agent.diag.allreduce = allreduce_sum_   # algo.update_diagnostics: the eight sums over ranks; no group, no collective
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.total_steps = 0
         self.iteration = 0
@@ -363,6 +366,9 @@ def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval
         steps, exp_r = tr.iterate()
         if tr.rank == 0:
             print(f"iteration {tr.iteration}: {steps} env-steps in {time.time() - t0:.2f}s")
+            if tr.agent.diag is not None:   # algo.update_diagnostics: the last update of the iteration, like last_log
+                print(json.dumps(dict(iteration=tr.iteration, critic_loss=tr.last_log[0], actor_loss=tr.last_log[1], **tr.agent.last_update_diag)),
+                      flush=True)
             if tr.iteration % eval_every == 0:
                 if eval_run_ref is not None:
                     done, _ = ray_shim.wait([eval_run_ref], num_returns=1, timeout=0 if async_eval else None)

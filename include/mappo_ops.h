@@ -363,6 +363,45 @@ int ppo_loss_gauss_ex_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad
                               void *workspace, void *stream);
 
 /*
+ * Update diagnostics (algo.update_diagnostics / algo.target_kl; csrc/ppo_diag.hpp).  The four *_diag calls are
+ * the plain calls -- same arguments, same losses and gradients byte for byte, the same two launches -- plus `double *diag`: eight f64
+ * sums over the call's live rows (active != 0, each counted once), ADDED to diag[0..7] on the device (zero it once per update):
+ *   0 the count; 1 expm1(lr) - lr in f64 (k3 estimator of KL(old || new), lr = fp32 logp_now - logp_old); 2 [ratio < 1 - eps or
+ *   ratio > 1 + eps] (ratio = expf(lr), the loss's own fp32 comparisons); 3 entropy; 4 v_target; 5 v_target^2; 6 (v_target - v_now)^2;
+ *   7 ratio.  logp_now and entropy are the fp32 values the row hands to the loss (formed inside the pass by the prob / gauss calls).
+ * Deterministic: f64 per-block partials behind the loss partials, added in a fixed order by eight more workgroups of the finish
+ * launch; no atomics.  workspace >= ppo_loss_diag_workspace() bytes (ppo_loss / ppo_loss_prob) or ppo_loss_gauss_diag_workspace()
+ * bytes (ppo_loss_gauss / ppo_loss_gauss_ex).  ppo_loss_gauss_ex_fwd_bwd_diag in state mode takes A <= 8, the state-mode head's limit.
+ * ppo_ratio: lr[i] = logp_now[i] - logp_old[i] and ratio[i] = expf(lr[i]) as the loss forms them (fp32), for checks and probes.
+ * ppo_diag_rows_host: the row step on the host (no device): terms [n][8], the eight terms of row i, 0 for an inactive row.
+ */
+int64_t ppo_loss_diag_workspace(void);
+int64_t ppo_loss_gauss_diag_workspace(void);
+int ppo_loss_fwd_bwd_diag(int64_t n, const float *logp_now, const float *entropy, const float *logp_old, const float *adv, const float *active,
+                          const float *values_now, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
+                          float entropy_coef, int32_t use_value_clip, float *losses, float *grad_logp, float *grad_entropy, float *grad_values,
+                          void *workspace, void *stream, double *diag);
+int ppo_loss_prob_fwd_bwd_diag(int64_t n, int32_t A, const float *prob, float *grad_prob, int64_t d1, int64_t d2, int64_t p_s0, int64_t p_s1,
+                               int64_t p_s2, const float *action, const float *logp_old, const float *adv, const float *active,
+                               const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                               const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip, float *losses,
+                               float *grad_values, void *workspace, void *stream, double *diag);
+int ppo_loss_gauss_fwd_bwd_diag(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                                int64_t m_s2, const float *log_std, const float *action, const float *logp_old, const float *adv,
+                                const float *active, const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old,
+                                const float *v_target, const float *active_sum, float epsilon, float entropy_coef, int32_t use_value_clip,
+                                float *losses, float *grad_values, float *grad_log_std, void *workspace, void *stream, double *diag);
+int ppo_loss_gauss_ex_fwd_bwd_diag(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                                   int64_t m_s2, const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2,
+                                   float log_std_min, float log_std_max, int32_t squash, const float *action, const float *logp_old,
+                                   const float *adv, const float *active, const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2,
+                                   const float *values_old, const float *v_target, const float *active_sum, float epsilon, float entropy_coef,
+                                   int32_t use_value_clip, float *losses, float *grad_values, void *workspace, void *stream, double *diag);
+int ppo_ratio(int64_t n, const float *logp_now, const float *logp_old, float *lr, float *ratio, void *stream);
+int ppo_diag_rows_host(int64_t n, const float *lr, const float *ratio, const float *ent, const float *v_now, const float *v_tgt,
+                       const float *active, float eps, double *terms);
+
+/*
  * Records one rollout tick into the replay buffer (MAPPO.run_episode's minibuffer.store_transition,
  * DHGN/mappo_parallel.py:783-805, for N environments at once): for every item, row n of the dense [N][row_bytes] source
  * goes to dst + n * dst_row_stride (slot [n, t] of an (N, T, ...) buffer tensor); i32_to_f32 converts int32 actions to

@@ -2,7 +2,8 @@
 
     python tools/bench_n2n.py [--num-envs 1024] [--warmup 2] [--steps 5] [--log-iterations 0 --log-out FILE] [KEY=VALUE ...]
 
-KEY=VALUE: dotted config overrides as `main` takes them, e.g. algo.use_reward_scaling=True, algo.reward_shaping=distance.
+KEY=VALUE: dotted config overrides as `main` takes them, e.g. algo.use_reward_scaling=True, algo.reward_shaping=distance,
+algo.update_diagnostics=True, algo.target_kl=0.02.
 
 rollout_ms / update_ms: device-event times per iteration (N2nTrainer.last_breakdown_ms); env_steps_per_s: environment steps over
 the wall time of the timed iterations (host clock around work that ends in a device synchronise); slsqp_share: the SLSQP evader's
