@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "e3d_env.h"
+#include "obs_norm.hpp"
 #include "reward_scale.hpp"
 #include "reward_shaping.hpp"
 #include "rng_replica.hpp"
@@ -318,6 +319,153 @@ __global__ __launch_bounds__(256) void k_e3d_features(const e3d_config c, const 
     }
 }
 
+// ---- algo.use_obs_norm (csrc/obs_norm.hpp; include/e3d_env.h e3d_policy_features_norm) ----
+//
+// k_e3d_features with the running mean / std normalisation applied to what it stores, and, with ACC, the statistics of the raw
+// features of the live rows added to this workgroup's slot.  k_e3d_features itself stays the code it was (the option-off path runs
+// it unchanged); the feature expressions below are its expressions in its order, and with n == 0 the outputs are its bits.
+//   * threads 0-31 turn the state into mean and std + eps per (network, column) in LDS once per workgroup, so a row does 32
+//     subtractions and divisions and no square root;
+//   * a row keeps its 2 x 16 fp32 features in registers, stores them normalised as 16-byte lanes;
+//   * ACC: the raw features go through LDS transposed -- column k at k * (TPB + 1), so the row-wise stores and the column-wise loads
+//     are both free of bank conflicts -- and thread (segment s = t / 32, column k = t % 32) adds d and d d of rows 32 s .. 32 s + 31
+//     in row order, then thread k adds the 8 segments in order: a fixed tree, f64, no atomics.  The slot belongs to this workgroup
+//     alone and is added to once per launch, so its contents are a sum in tick order.
+constexpr int E3D_FN_TPB = 256, E3D_FN_SEG = E3D_FN_TPB / 32, E3D_FN_K = 2 * E3D_FEAT;
+constexpr int E3D_SLOT = 2 * obsnorm::ROW;   // f64 per slot: (network, [c, S1[16], S2[16]])
+
+template <bool ACC>
+__global__ __launch_bounds__(E3D_FN_TPB) void k_e3d_features_norm(const e3d_config c, const e3d_state st, const e3d_obs_out o, float *af, float *cf,
+                                                                   const double *state, const double clipv, const float *live,
+                                                                   const int64_t live_rs, double *slots) {
+    __shared__ double s_mean[E3D_FN_K], s_den[E3D_FN_K], s_n[2];
+    __shared__ float s_x[ACC ? E3D_FN_K * (E3D_FN_TPB + 1) : 1];
+    __shared__ float s_live[ACC ? E3D_FN_TPB : 1];
+    __shared__ double s_part[ACC ? E3D_FN_SEG * 3 * E3D_FN_K : 1];
+    const int P = c.P, t = threadIdx.x;
+    if (t < E3D_FN_K) {
+        const double *row = state + (t >> 4) * obsnorm::ROW;
+        const double n = row[0];
+        s_mean[t] = row[1 + (t & 15)];
+        s_den[t] = n == 0.0 ? 1.0 : obsnorm::denom(n, row[1 + E3D_FEAT + (t & 15)]);
+        if ((t & 15) == 0) s_n[t >> 4] = n;
+    }
+    const int64_t idx = (int64_t)blockIdx.x * E3D_FN_TPB + t;
+    const bool valid = idx < (int64_t)st.N * P;
+    float f[E3D_FN_K];   // the raw features: 0-15 the actor's, 16-31 the critic's
+#pragma unroll
+    for (int k = 0; k < E3D_FN_K; k++) f[k] = 0.f;
+    bool on = false, counted = false;
+    if (valid) {
+        const int env = (int)(idx / P), i = (int)(idx - (int64_t)env * P);
+        const double *gp = st.p + (size_t)env * 7 * P, *ge = st.e + (size_t)env * 7;
+        on = gp[6 * P + i] != 0.0;
+        if (on) {
+            double s[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) s[k] = gp[k * P + i];
+            const double pe = (double)o.pe_adj[(int64_t)env * o.pe_adj_stride + i], ae = ge[6];
+            const float *pp = o.pp_adj + (int64_t)env * o.pp_adj_stride + (int64_t)i * P;
+            double ma[3] = {0, 0, 0}, mc[3] = {0, 0, 0};
+            int na = 0, nc = 0;
+            for (int j = 0; j < P; j++) {
+                if (j == i) continue;
+                const bool in_a = pp[j] == 1.f, in_c = gp[6 * P + j] != 0.0;
+                if (!in_a && !in_c) continue;
+                const double dx = gp[j] - s[0], dy = gp[P + j] - s[1], dz = gp[2 * P + j] - s[2];
+                if (in_a) { ma[0] += dx; ma[1] += dy; ma[2] += dz; na++; }
+                if (in_c) { mc[0] += dx; mc[1] += dy; mc[2] += dz; nc++; }
+            }
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                f[k] = f[E3D_FEAT + k] = (float)s[k];
+                f[6 + k] = (float)((ge[k] - s[k]) * pe);
+                f[E3D_FEAT + 6 + k] = (float)((ge[k] - s[k]) * ae);
+            }
+            f[12] = (float)pe;
+            f[E3D_FEAT + 12] = (float)ae;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                f[13 + k] = na ? (float)(ma[k] / na) : 0.f;
+                f[E3D_FEAT + 13 + k] = nc ? (float)(mc[k] / nc) : 0.f;
+            }
+            if (ACC) counted = live[(int64_t)env * live_rs + i] != 0.f;
+        }
+    }
+    __syncthreads();   // s_mean, s_den, s_n
+    if (valid) {
+        float y[E3D_FN_K];
+#pragma unroll
+        for (int k = 0; k < E3D_FN_K; k++)   // rows of inactive pursuers stay exactly 0: no -mean / std there
+            y[k] = (!on || s_n[k >> 4] == 0.0) ? f[k] : obsnorm::apply(f[k], s_mean[k], s_den[k], clipv);
+        float4 *da = reinterpret_cast<float4 *>(af + idx * E3D_FEAT), *dc = reinterpret_cast<float4 *>(cf + idx * E3D_FEAT);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            da[q] = make_float4(y[4 * q], y[4 * q + 1], y[4 * q + 2], y[4 * q + 3]);
+            dc[q] = make_float4(y[E3D_FEAT + 4 * q], y[E3D_FEAT + 4 * q + 1], y[E3D_FEAT + 4 * q + 2], y[E3D_FEAT + 4 * q + 3]);
+        }
+    }
+    if (ACC) {
+        s_live[t] = counted ? 1.f : 0.f;
+#pragma unroll
+        for (int k = 0; k < E3D_FN_K; k++) s_x[k * (E3D_FN_TPB + 1) + t] = f[k];
+        __syncthreads();
+        const int k = t & 31, seg = t >> 5;
+        const double mean = s_mean[k];
+        const float *col = s_x + k * (E3D_FN_TPB + 1) + seg * 32;
+        double cnt = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int r = 0; r < 32; r++) {
+            if (s_live[seg * 32 + r] != 0.f) {
+                const double d = (double)col[r] - mean;
+                cnt += 1.0; s1 += d; s2 += d * d;
+            }
+        }
+        double *part = s_part + (seg * E3D_FN_K + k) * 3;
+        part[0] = cnt; part[1] = s1; part[2] = s2;
+        __syncthreads();
+        if (t < E3D_FN_K) {
+            double C = 0.0, A = 0.0, Q = 0.0;
+            for (int g = 0; g < E3D_FN_SEG; g++) {
+                const double *q = s_part + (g * E3D_FN_K + t) * 3;
+                C += q[0]; A += q[1]; Q += q[2];
+            }
+            double *slot = slots + (size_t)blockIdx.x * E3D_SLOT + (t >> 4) * obsnorm::ROW;
+            if ((t & 15) == 0) slot[0] += C;
+            slot[1 + (t & 15)] += A;
+            slot[1 + E3D_FEAT + (t & 15)] += Q;
+        }
+    }
+}
+
+// sums [2][33] = the slots added in index order (e3d_obs_norm_reduce): one lane per entry
+__global__ __launch_bounds__(128) void k_e3d_obs_norm_reduce(const double *slots, const int nslots, double *sums) {
+    const int t = threadIdx.x;
+    if (t >= E3D_SLOT) return;
+    double s = 0.0;
+    for (int b = 0; b < nslots; b++) s += slots[(size_t)b * E3D_SLOT + t];
+    sums[t] = s;
+}
+
+// the merge of the totals into the state (e3d_obs_norm_update; obsnorm::merge), one lane per entry, then the slots are zeroed.  Every
+// lane reads what it needs before any lane writes (the lanes of n, mean and M2 of one column read each other's entries).
+__global__ __launch_bounds__(128) void k_e3d_obs_norm_update(double *state, const double *sums, double *slots, const int nslots) {
+    const int t = threadIdx.x;
+    double out = 0.0;
+    const bool lane = t < E3D_SLOT;
+    if (lane) {
+        const int net = t / obsnorm::ROW, j = t - net * obsnorm::ROW, col = j == 0 ? 0 : (j - 1) & 15;
+        const double *row = state + net * obsnorm::ROW, *sr = sums + net * obsnorm::ROW;
+        const double n = row[0], C = sr[0];
+        double mean = row[1 + col], M2 = row[1 + E3D_FEAT + col];
+        obsnorm::merge(n, C, sr[1 + col], sr[1 + E3D_FEAT + col], mean, M2);
+        out = j == 0 ? n + C : (j <= E3D_FEAT ? mean : M2);
+    }
+    __syncthreads();
+    if (lane) state[t] = out;
+    if (slots)
+        for (int i = t; i < nslots * E3D_SLOT; i += blockDim.x) slots[i] = 0.0;
+}
+
 // the shaping potential of pursuer a of environment env in the current records (p_on, e_on: their active flags)
 __device__ __forceinline__ double e3d_potential(const e3d_state &st, int env, int P, int a, bool p_on, bool e_on, double coef) {
     const double *gp = st.p + (size_t)env * 7 * P + a, *ge = st.e + (size_t)env * 7;
@@ -483,6 +631,37 @@ int e3d_policy_features(const e3d_config *cfg, const e3d_state *st, const e3d_ob
     const int64_t rows = (int64_t)st->N * cfg->P;
     if (rows == 0) return 0;
     hipLaunchKernelGGL(k_e3d_features, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cfg, *st, *out, actor_feat, critic_feat);
+    return (int)hipGetLastError();
+}
+
+int64_t e3d_obs_norm_slots(int64_t rows) { return rows <= 0 ? 0 : (rows + E3D_FN_TPB - 1) / E3D_FN_TPB; }
+
+int e3d_policy_features_norm(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, float *actor_feat, float *critic_feat,
+                             const double *norm_state, double clip, const float *live, int64_t live_rs, double *slots, void *stream) {
+    if (!cfg || !st || !out || !out->pp_adj || !out->pe_adj || !actor_feat || !critic_feat || !norm_state || (slots && !live)) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (!(clip > 0.0) || std::isinf(clip)) return E3D_ERR_BAD_CONFIG;
+    const int64_t rows = (int64_t)st->N * cfg->P;
+    if (rows == 0) return 0;
+    const dim3 grid((unsigned)e3d_obs_norm_slots(rows)), block(E3D_FN_TPB);
+    hipStream_t s = (hipStream_t)stream;
+    if (slots) hipLaunchKernelGGL(k_e3d_features_norm<true>, grid, block, 0, s, *cfg, *st, *out, actor_feat, critic_feat, norm_state, clip, live, live_rs, slots);
+    else hipLaunchKernelGGL(k_e3d_features_norm<false>, grid, block, 0, s, *cfg, *st, *out, actor_feat, critic_feat, norm_state, clip, nullptr, (int64_t)0, nullptr);
+    return (int)hipGetLastError();
+}
+
+int e3d_obs_norm_reduce(const double *slots, int64_t nslots, double *sums, void *stream) {
+    if (!slots || !sums) return E3D_ERR_NULL;
+    if (nslots < 0 || nslots > INT32_MAX / E3D_SLOT) return E3D_ERR_BAD_CONFIG;
+    hipLaunchKernelGGL(k_e3d_obs_norm_reduce, dim3(1), dim3(128), 0, (hipStream_t)stream, slots, (int)nslots, sums);
+    return (int)hipGetLastError();
+}
+
+int e3d_obs_norm_update(double *norm_state, const double *sums, double *slots, int64_t nslots, void *stream) {
+    if (!norm_state || !sums) return E3D_ERR_NULL;
+    if (nslots < 0 || nslots > INT32_MAX / E3D_SLOT) return E3D_ERR_BAD_CONFIG;
+    hipLaunchKernelGGL(k_e3d_obs_norm_update, dim3(1), dim3(128), 0, (hipStream_t)stream, norm_state, sums, slots, (int)nslots);
     return (int)hipGetLastError();
 }
 

@@ -12,6 +12,8 @@ Two options, both off by default: `algo.gauss_std: state`
 LogStd = Linear(128 -> A) on the GRU features, `algo.gauss_squash: tanh` sends tanh(u) to the environment instead of clamp(u, -1, 1)
 and subtracts log(1 - tanh(u)^2) from the log-probability; ls is clamped to [algo.log_std_min, algo.log_std_max].  With either on,
 the rollout takes ops.gauss_head_sample_ex and the update ops.ppo_loss_gauss_ex; with both off, the calls above.
+`algo.use_obs_norm` (off by default; obs_norm.py): both encoders read the features normalised by a running mean / std that is frozen
+during a rollout and merged once after it; the first rollout is the option-off one bit for bit.
 """
 import json
 import os
@@ -22,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.utils import spectral_norm
 
+from . import obs_norm as onorm
 from . import ops
 from . import value_norm as vnorm
 from .reward_shaping import reward_shaping_options
@@ -123,6 +126,7 @@ class E3dMAPPO:
         self.use_reward_scaling = bool(a.get("use_reward_scaling", False))   # the reference's RewardScaling in policy_record
         self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
         self.reward_shaping, self.shaping_coef = reward_shaping_options(cfg)   # distance shaping in policy_record
+        self.use_obs_norm, self.obs_norm_clip = onorm.obs_norm_options(cfg)   # running mean / std on the policy features
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.update_diagnostics, self.target_kl = update_diag_options(cfg)   # what the update did, from the loss launches
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
@@ -143,6 +147,7 @@ class E3dMAPPO:
         self.ac_parameters = list(self.actor.parameters()) + list(self.critic.parameters())
         self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
         self.value_norm = vnorm.ValueNorm(self.value_norm_beta, self.device) if self.use_value_norm else None
+        self.obs_norm = onorm.ObsNorm(self.obs_norm_clip, self.device) if self.use_obs_norm else None
         self.diag = UpdateDiag(self.device) if self.update_diagnostics else None
         self.last_update_diag = None   # algo.update_diagnostics: the dict of the last train() call
         rt = cfg.get("runtime", {})
@@ -180,6 +185,16 @@ class E3dMAPPO:
                                   (st.action, st.env_action, st.logp), greedy=greedy)
         st.t += 1
 
+    def _features(self, env, st, accumulate=False):
+        """the policy features of the current state into st.fa / st.fc; with algo.use_obs_norm normalised under the agent's state, and,
+        when `accumulate` (the ticks of a training rollout), the sums of the raw features of the live rows added to the slots"""
+        on = self.obs_norm
+        if on is None:
+            return env.policy_features(st.fa, st.fc)
+        if not accumulate:
+            return env.policy_features(st.fa, st.fc, on.state, on.clip)
+        return env.policy_features(st.fa, st.fc, on.state, on.clip, st.live, on.slots_for(st.N * st.P))
+
     def _bootstrap_value(self, st):
         """the critic's value of the state after the last step (its encoder, GRU cell and head only)"""
         N, P = st.N, st.P
@@ -203,6 +218,8 @@ class E3dMAPPO:
         and the per-environment accumulators are one launch per tick (ParticleEnv.policy_record); with algo.use_reward_scaling and a
         buffer, r is the scaled reward (env.reward_scale advances) while the return stays the raw one; with algo.reward_shaping:
         distance and a buffer, r (what is scaled, when both are on) carries the shaping term gamma Phi' - Phi (env.shaping_phi).
+        With algo.use_obs_norm the features (and feat_a / feat_c) are normalised under obs_norm.state, which no tick changes; with a
+        buffer every tick adds the sums of its live rows to obs_norm.slots (explore_env merges them).
         Returns per-environment (return, captured, length) device tensors."""
         N, P, T = env.num_envs, env.p_num, env.max_step
         env.reset()
@@ -217,7 +234,7 @@ class E3dMAPPO:
         if shaping_gamma is not None:
             env.shaping_begin()
         for t in range(T):
-            env.policy_features(st.fa, st.fc)
+            self._features(env, st, accumulate=buf is not None)   # evaluation never accumulates
             self._policy_step(st, greedy)
             env.evader_step()
             env.step(st.env_action)
@@ -231,7 +248,7 @@ class E3dMAPPO:
             env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1], st.live,
                               scale_gamma=scale_gamma, shaping_gamma=shaping_gamma)
         if buf is not None:
-            env.policy_features(st.fa, st.fc)
+            self._features(env, st)   # the state after the last step: normalised, not counted
             vmask = env.active_t.float() * (acc["ended"] == 0).float()[:, None]
             buf["v_n"][:, T].copy_(self._bootstrap_value(st) * vmask)
             if self.value_norm is not None:   # the denormalisation of v_n[:, T] needs the mask itself: 0 std + mean is not 0
@@ -244,6 +261,8 @@ class E3dMAPPO:
         if self.buffer is None or self.buffer["r"].shape != (N, T, P):
             self.buffer = self.new_buffer(N, T, P)
         ret, captured, length = self.run_episode(env, self.buffer)
+        if self.obs_norm is not None:   # one merge per rollout: the statistics the next rollout is normalised under
+            self.obs_norm.commit()
         mean_r, cap, mlen = torch.stack((ret.mean(), captured.float().mean(), length.mean())).tolist()
         return mean_r, self.buffer, N * T, dict(capture_rate=cap, episode_length=mlen)
 
@@ -337,25 +356,32 @@ class E3dMAPPO:
 
     def save_model(self, cwd, best=False):
         """cwd/e3d_state_dicts.pt (best: e3d_state_dicts_best.pt), the actor's and critic's state_dicts (and, with a non-default
-        algo.gauss_std / gauss_squash, the "policy" entry of policy_meta; with algo.use_value_norm the "value_norm" entry: beta and the state)"""
+        algo.gauss_std / gauss_squash, the "policy" entry of policy_meta; with algo.use_value_norm the "value_norm" entry: beta and the state;
+        with algo.use_obs_norm the "obs_norm" entry: the clip and the state)"""
         os.makedirs(cwd, exist_ok=True)
         sd = {"actor": self.actor.state_dict(), "critic": self.critic.state_dict()}
         if self.policy_ex:
             sd["policy"] = self.policy_meta()
         if self.value_norm is not None:   # algo.use_value_norm: the critic's outputs mean nothing without the statistics
             sd["value_norm"] = self.value_norm.entry()
+        if self.obs_norm is not None:     # algo.use_obs_norm: the weights mean nothing without the statistics of their inputs
+            sd["obs_norm"] = self.obs_norm.entry()
         torch.save(sd, os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt"))
 
     def load_model(self, cwd, best=False):
-        """the weights save_model(cwd, best) wrote; ValueError when they belong to another gauss_std / gauss_squash or algo.use_value_norm"""
+        """the weights save_model(cwd, best) wrote; ValueError when they belong to another gauss_std / gauss_squash, algo.use_value_norm or
+        algo.use_obs_norm"""
         path = os.path.join(cwd, f"e3d_state_dicts{'_best' if best else ''}.pt")
         sd = torch.load(path, map_location=self.device)
         self.check_policy_meta(sd.get("policy"), path)
         vnorm.check_entry(self, sd.get("value_norm"), path, check_beta=False)
+        onorm.check_entry(self, sd.get("obs_norm"), path, check_clip=False)
         self.actor.load_state_dict(sd["actor"])
         self.critic.load_state_dict(sd["critic"])
         if self.value_norm is not None:
             self.value_norm.load_entry(sd["value_norm"])
+        if self.obs_norm is not None:
+            self.obs_norm.load_entry(sd["obs_norm"])
 
 
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
@@ -392,6 +418,8 @@ class E3dTrainer(ParticleRunState):
         self.agent.grad_bucket = self.bucket
         if self.agent.value_norm is not None:
             self.agent.value_norm.allreduce = allreduce_sum_   # (S1, S2, c) over ranks; without a process group a no-op
+        if self.agent.obs_norm is not None:
+            self.agent.obs_norm.allreduce = allreduce_sum_     # the (2, 33) feature sums of a rollout over ranks, likewise
         if self.agent.diag is not None:
             self.agent.diag.allreduce = allreduce_sum_         # the eight diagnostic sums over ranks, likewise
         self.last_epoch_diags = []

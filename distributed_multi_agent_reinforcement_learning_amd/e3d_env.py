@@ -77,6 +77,11 @@ def load_library():
         L.e3d_resetter_get_state.argtypes = [vp, vp]
         L.e3d_resetter_set_state.argtypes = [vp, vp]
         L.e3d_policy_features.argtypes = [vp] * 6
+        L.e3d_policy_features_norm.argtypes = [vp] * 6 + [C.c_double, vp, C.c_int64, vp, vp]
+        L.e3d_obs_norm_slots.argtypes = [C.c_int64]
+        L.e3d_obs_norm_slots.restype = C.c_int64
+        L.e3d_obs_norm_reduce.argtypes = [vp, C.c_int64, vp, vp]
+        L.e3d_obs_norm_update.argtypes = [vp, vp, vp, C.c_int64, vp]
         L.e3d_policy_record.argtypes = [vp] * 7 + [C.c_double, vp]
         L.e3d_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
         L.e3d_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
@@ -232,13 +237,33 @@ class ParticleEnv:
                                torch.ones_like(d[:, 0])), -1)
         self._cmd = torch.as_tensor(cmd, dtype=torch.float64, device=self.device).reshape(self.num_envs, 3).contiguous()
 
-    def policy_features(self, actor_feat, critic_feat):
+    def policy_features(self, actor_feat, critic_feat, norm_state=None, clip=None, live=None, slots=None):
         """the trainer's (N, P, 16) fp32 features of the current state into the two dense tensors (e3d_policy_features,
-        include/e3d_env.h): the actor's from its sensed evader and communication neighbours, the critic's from the whole state"""
+        include/e3d_env.h): the actor's from its sensed evader and communication neighbours, the critic's from the whole state.
+        norm_state (algo.use_obs_norm): the (2, 33) f64 state of obs_norm.ObsNorm; the features are then written normalised under it
+        and clipped to +-clip (e3d_policy_features_norm; rows of inactive pursuers stay 0), and, with slots (ObsNorm.slots_for(N P)),
+        the same launch adds the sums of the raw features over the rows of the (N, P) mask `live` to them."""
         for t in (actor_feat, critic_feat):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (self.num_envs, self.p_num, 16) and t.device == self.p.device
-        _check(self.L.e3d_policy_features(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_void_p(actor_feat.data_ptr()),
-                                          C.c_void_p(critic_feat.data_ptr()), _stream()), "e3d_policy_features")
+        if norm_state is None:
+            assert clip is None and live is None and slots is None, "clip, live and slots belong to norm_state"
+            _check(self.L.e3d_policy_features(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_void_p(actor_feat.data_ptr()),
+                                              C.c_void_p(critic_feat.data_ptr()), _stream()), "e3d_policy_features")
+            return actor_feat, critic_feat
+        N, P = self.num_envs, self.p_num
+        assert norm_state.dtype == torch.float64 and norm_state.is_contiguous() and norm_state.shape == (2, 33) and norm_state.device == self.p.device
+        live_ptr, live_rs, slots_ptr = None, 0, None
+        if slots is not None:
+            n = self.L.e3d_obs_norm_slots(N * P)
+            assert slots.dtype == torch.float64 and slots.is_contiguous() and slots.shape == (n, 2, 33) and slots.device == self.p.device
+            if live is None:
+                raise ValueError("policy_features(slots=...) needs the live mask of the step")
+            live_ptr, live_rs = _rows(live, (N, P), "live")
+            slots_ptr = slots.data_ptr()
+        _check(self.L.e3d_policy_features_norm(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_void_p(actor_feat.data_ptr()),
+                                               C.c_void_p(critic_feat.data_ptr()), C.c_void_p(norm_state.data_ptr()), C.c_double(float(clip)),
+                                               C.c_void_p(live_ptr), C.c_int64(live_rs), C.c_void_p(slots_ptr), _stream()),
+               "e3d_policy_features_norm")
         return actor_feat, critic_feat
 
     # ---- MAPPO on env_3d (e3d_agent.py): the bookkeeping of one lockstep tick, one launch after step() ------------------------------

@@ -69,6 +69,9 @@ class N2nMAPPO:
         self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
         self.reward_shaping, self.shaping_coef = reward_shaping_options(cfg)   # distance shaping in policy_record
         self.update_diagnostics, self.target_kl = update_diag_options(cfg)   # what the update did, from the loss launches
+        if bool(a.get("use_obs_norm", False)):
+            raise ValueError("algo.use_obs_norm: true is built for runtime.env e3d only; the env_n2n inputs are node states whose "
+                             "differences the message kernels form and whose zero rows stand for absent nodes (set use_obs_norm to false)")
         if int(cfg.env.num_defender) > MAX_P:
             raise ValueError(f"env.num_defender={cfg.env.num_defender}: the DHGN message kernels take at most {MAX_P} pursuers per row")
         if int(cfg.env.state_dim) != 4 or int(cfg.env.action_dim) != 9 or int(a.num_relation) != 3:

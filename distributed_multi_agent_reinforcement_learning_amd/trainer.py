@@ -17,6 +17,7 @@ import torch.distributed as dist
 from .evaluator import EvaluatorProc, draw_learning_curve
 from .mappo import MAPPO
 from .pursuit_env import Pursuit_Env
+from .obs_norm import check_entry as check_obs_norm_entry
 from .value_norm import check_entry as check_value_norm_entry
 
 
@@ -153,7 +154,8 @@ class ParticleRunState:
     best_eval_return.  Every environment episode starts from a reset and every rollout from zero GRU states and history, so the
     reset generators, the sampling counters, the weights and Adam are all the state a run carries from one iteration to the next --
     and, with algo.use_reward_scaling, the training environment's reward_scale (the bundle's "reward_scaling" entry), with
-    algo.use_value_norm the agent's value-normaliser state (the "value_norm" entry)."""
+    algo.use_value_norm the agent's value-normaliser state (the "value_norm" entry), with algo.use_obs_norm (env_3d) the agent's
+    feature-normaliser state (the "obs_norm" entry; its slots are empty between iterations and are not saved)."""
 
     def save_resume(self, path):
         agent, ev = self.agent, self.eval_env
@@ -171,6 +173,8 @@ class ParticleRunState:
             bundle["reward_scaling"] = self.env.reward_scale.cpu()
         if getattr(agent, "value_norm", None) is not None:   # algo.use_value_norm: beta and the state (m, q, d); off: no entry
             bundle["value_norm"] = agent.value_norm.entry()
+        if getattr(agent, "obs_norm", None) is not None:     # algo.use_obs_norm: the clip and the state (2, 33); off: no entry
+            bundle["obs_norm"] = agent.obs_norm.entry()
         torch.save(bundle, path)
 
     def load_resume(self, path):
@@ -186,11 +190,14 @@ class ParticleRunState:
             raise ValueError(f"resume bundle {path} was written with algo.use_reward_scaling: {str(theirs).lower()}, "
                              f"this agent has algo.use_reward_scaling: {str(mine).lower()}")
         check_value_norm_entry(agent, b.get("value_norm"), f"resume bundle {path}")
+        check_obs_norm_entry(agent, b.get("obs_norm"), f"resume bundle {path}")
         agent.actor.load_state_dict(b["actor"])
         agent.critic.load_state_dict(b["critic"])
         agent.ac_optimizer.load_state_dict(b["optimizer"])
         if agent.value_norm is not None:
             agent.value_norm.load_entry(b["value_norm"])
+        if getattr(agent, "obs_norm", None) is not None:
+            agent.obs_norm.load_entry(b["obs_norm"])   # (zeroes the slots)
         self.total_steps, self.iteration = b["total_steps"], b["iteration"]
         if agent.use_lr_decay:
             agent.lr_decay(self.total_steps)

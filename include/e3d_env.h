@@ -65,6 +65,26 @@ int e3d_env_tick(const e3d_config *cfg, const e3d_state *st, const double *actio
  * (actor | critic); rows of inactive pursuers are zero. */
 int e3d_policy_features(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, float *actor_feat, float *critic_feat, void *stream);
 
+/* ---- algo.use_obs_norm: running mean / std normalisation of the policy features (csrc/obs_norm.hpp) ----
+ * norm_state [2][33] f64 on the device: row 0 the actor's features, row 1 the critic's, each n, mean[16], M2[16] (all 0 at the start).
+ * e3d_policy_features_norm writes, for the fp32 feature x that e3d_policy_features would write,
+ *   n == 0:  x                      (so the outputs are e3d_policy_features' bits until the first update)
+ *   else:    (float)min(max(((double)x - mean) / (sqrt(M2 / n) + 1e-8), -clip), clip)      (clip finite and > 0)
+ * rows of inactive pursuers stay exactly zero.  slots != NULL: the same launch adds, per network and column, c = the number of
+ * counted rows, S1 = sum d and S2 = sum d d, d = (double)x - mean, over the rows of active pursuers with live[n * live_rs + p] != 0
+ * (the live mask of e3d_record_io) to the slot of each workgroup: slots [e3d_obs_norm_slots(N P)][2][33] f64 (c, S1[16], S2[16]),
+ * zeroed by the caller before the first launch; a slot is owned by one workgroup, f64, fixed order, no atomics.  norm_state is
+ * only read.  slots == NULL: nothing is accumulated and live is not read. */
+int e3d_policy_features_norm(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, float *actor_feat, float *critic_feat,
+                             const double *norm_state, double clip, const float *live, int64_t live_rs, double *slots, void *stream);
+int64_t e3d_obs_norm_slots(int64_t rows);   /* slots of a launch over `rows` = N P feature rows */
+/* sums [2][33] = the nslots slots added in index order (what a data-parallel job all-reduces); the slots are left as they are */
+int e3d_obs_norm_reduce(const double *slots, int64_t nslots, double *sums, void *stream);
+/* Merges the totals C = sums[.][0], A = S1, Q = S2 into norm_state, per network and column: C == 0 changes nothing; otherwise
+ * n' = n + C, delta = A / C, mean' = mean + A / n', M2' = M2 + (Q - A delta) + delta delta (n C / n').  Then zeroes the nslots
+ * slots (slots == NULL: none). */
+int e3d_obs_norm_update(double *norm_state, const double *sums, double *slots, int64_t nslots, void *stream);
+
 /* ---- MAPPO bookkeeping of one lockstep tick (e3d_agent.py), the structs of n2n_env.h for env_3d ----
  * fp32 rows with *_rs = elements between environments (dense storage or step t of an (N, T, P) buffer); a NULL output is skipped.
  * A row is LIVE when its pursuer was active at the start of the step and its environment was not done before it. */
