@@ -2460,6 +2460,7 @@ int launch_msgw3(const mo_msg_rel *rel, int R, int P, int E, const float *p, int
 
 #include "gauss_policy.hpp"   // the Gaussian policy head and loss of the env_3d trainer (reuses the helpers above)
 #include "value_norm.hpp"     // algo.use_value_norm: GAE on denormalised values, the running statistics and the normalised targets
+#include "fused_adam.hpp"     // algo.minibatch_steps: the gradient clip and the Adam step of one mini-batch in two launches
 
 constexpr int SB_WGRAD_WGS = 256;  // one workgroup per CU (96 KB of LDS each)
 

@@ -215,6 +215,9 @@ class MAPPO:
         if bool(a.get("use_obs_norm", False)):
             raise ValueError("algo.use_obs_norm: true is built for runtime.env e3d only; the pursuit rollout is pinned to the "
                              "reference's (set use_obs_norm to false)")
+        if a.get("minibatch_steps", False):
+            raise ValueError("algo.minibatch_steps is built for runtime.env n2n and e3d only; the pursuit update (one optimiser step per "
+                             "epoch) is pinned to the reference's (set minibatch_steps to false)")
         if a.get("target_kl", None) is not None:
             raise ValueError("algo.target_kl is built for runtime.env n2n and e3d only; the pursuit update schedule is pinned to the "
                              "reference's (leave target_kl out; algo.update_diagnostics reports the KL)")

@@ -17,12 +17,13 @@ import torch
 
 from . import ops
 from . import value_norm as vnorm
+from .minibatch_steps import MAX_GRAD_NORM, minibatch_steps_options
 from .reward_shaping import reward_shaping_options
 from .update_diag import LOG_KEYS, UpdateDiag, first_epoch_over, update_diag_options
 from .model import build_actor_critic, sequence_forward_pair
 from .n2n_env import ParticleEnv
-from .trainer import (GradBucket, ParticleRunState, allreduce_sum_, broadcast_weights_, enable_tuned_gemms, init_distributed,
-                      resume_path, save_resume_atomic)
+from .trainer import (BUCKET_ALIGN, FusedAdam, GradBucket, ParamBucket, ParticleRunState, allreduce_sum_, broadcast_weights_,
+                      enable_tuned_gemms, init_distributed, resume_path, save_resume_atomic)
 
 MAX_P = 16   # the message kernels' agents per row (csrc/mappo_ops.hip MAX_P)
 
@@ -69,6 +70,7 @@ class N2nMAPPO:
         self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
         self.reward_shaping, self.shaping_coef = reward_shaping_options(cfg)   # distance shaping in policy_record
         self.update_diagnostics, self.target_kl = update_diag_options(cfg)   # what the update did, from the loss launches
+        self.minibatch_steps = minibatch_steps_options(cfg)   # one clip + Adam step per mini-batch, fused
         if bool(a.get("use_obs_norm", False)):
             raise ValueError("algo.use_obs_norm: true is built for runtime.env e3d only; the env_n2n inputs are node states whose "
                              "differences the message kernels form and whose zero rows stand for absent nodes (set use_obs_norm to false)")
@@ -95,7 +97,12 @@ class N2nMAPPO:
         # the parameter order of MAPPO.ac_parameters (the reference's, :631)
         self.ac_parameters = (list(enc.parameters()) + list(self.actor.GRU.parameters()) + list(self.critic.GRU.parameters())
                               + list(self.critic.Mean.parameters()) + list(self.actor.Mean.parameters()))
-        self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
+        self.param_bucket = None
+        if self.minibatch_steps:   # the parameters and their gradients as two flat tensors of one layout, stepped by two launches
+            self.param_bucket = ParamBucket(self.ac_parameters)
+            self.ac_optimizer = FusedAdam(self.param_bucket, lr=self.lr, eps=1e-5)
+        else:
+            self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
         self.value_norm = vnorm.ValueNorm(self.value_norm_beta, self.device) if self.use_value_norm else None
         self.diag = UpdateDiag(self.device) if self.update_diagnostics else None
         self.last_update_diag = None   # algo.update_diagnostics: the dict of the last train() call
@@ -103,7 +110,8 @@ class N2nMAPPO:
         self.sample_seed = int(rt.get("seed", 0))
         self.sample_rank = int(rt.get("sample_rank", 0))   # Philox counter of rank r starts at r << 40 (as MAPPO)
         self.total_step = 0
-        self.grad_bucket = None
+        self.grad_bucket = GradBucket(self.ac_parameters, BUCKET_ALIGN) if self.minibatch_steps else None   # (off: the trainer's)
+        self.last_optimizer_steps = self.last_skipped_steps = 0   # algo.minibatch_steps: of the last train() call
         self.buffer = None
         self._states = {}
 
@@ -224,7 +232,9 @@ class N2nMAPPO:
 
     def train(self, buf, total_steps):
         """GAE + advantage normalisation over all rows (ops.gae_advnorm), then sequential mini-batches of whole episodes, the
-        gradient clipped to 5.0 after each (as MAPPO.train).  Returns (critic loss, actor loss) averaged over the mini-batches."""
+        gradient clipped to 5.0 after each (as MAPPO.train).  With algo.minibatch_steps every mini-batch instead starts from a zeroed
+        bucket and ends with the gradient SUM over ranks and one fused clip + Adam step (FusedAdam.step), and
+        last_optimizer_steps / last_skipped_steps count them.  Returns (critic loss, actor loss) averaged over the mini-batches."""
         N = buf["r"].shape[0]
         with torch.no_grad():
             if self.value_norm is not None:   # GAE on denormalised values, the state's step, the targets under the new statistics
@@ -235,6 +245,7 @@ class N2nMAPPO:
             self.grad_bucket.zero()
         else:
             self.ac_optimizer.zero_grad()
+        opt = self.ac_optimizer if self.minibatch_steps else None   # FusedAdam: zero, backward, reduce and step per mini-batch
         obj_c = obj_a = 0.0
         k = 0
         diag = self.diag   # algo.update_diagnostics: every loss call adds its eight sums (None: the plain calls)
@@ -242,12 +253,19 @@ class N2nMAPPO:
             diag.begin()
         for n0 in range(0, N, self.mini_batch_size):
             n1 = min(n0 + self.mini_batch_size, N)
+            if opt is not None and n0:
+                self.grad_bucket.zero()
             prob, values = self.sequence_forward(buf, n0, n1)
             la, lc = ops.ppo_loss_prob(prob, buf["a_n"][n0:n1], values, buf["a_logprob_n"][n0:n1], adv[n0:n1], buf["active"][n0:n1],
                                        buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1], self.epsilon,
                                        self.entropy_coef, self.use_value_clip, **({} if diag is None else {"diag": diag.sums}))
             (la + lc).backward()
-            if self.use_grad_clip:
+            if opt is not None:   # the clip acts on the gradient summed over ranks: the same coefficient and weights everywhere
+                allreduce_sum_(self.grad_bucket.flat)
+                opt.step(self.grad_bucket.flat, MAX_GRAD_NORM if self.use_grad_clip else 0.0)
+                if diag is not None and self.use_grad_clip:
+                    diag.note_grad_norm(opt.grad_norm)
+            elif self.use_grad_clip:
                 norm = torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
                 if diag is not None:
                     diag.note_grad_norm(norm)
@@ -256,8 +274,14 @@ class N2nMAPPO:
             k += 1
         if self.use_lr_decay:
             self.lr_decay(total_steps)
+        extra = () if opt is None else (opt.skipped,)   # the count of skipped steps rides in the read the call has anyway
         if diag is not None:   # one read for the two losses, the eight sums (all-reduced over ranks) and the gradient norm
-            (obj_c, obj_a), self.last_update_diag = diag.read(obj_c, obj_a)
+            (obj_c, obj_a, *extra), self.last_update_diag = diag.read(obj_c, obj_a, *extra)
+        elif opt is not None:
+            obj_c, obj_a, *extra = torch.stack((obj_c, obj_a, *extra)).tolist()
+        if opt is not None:
+            self.last_optimizer_steps, self.last_skipped_steps = k, int(extra[0] - opt.skipped_seen)
+            opt.skipped_seen = extra[0]
         return float(obj_c) / k, float(obj_a) / k
 
     def lr_decay(self, total_steps):
@@ -308,7 +332,8 @@ def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True)
 
 
 class N2nTrainer(ParticleRunState):
-    """One rank of the data-parallel env_n2n job: rollout, then epochs x (update, gradient all-reduce, Adam step)."""
+    """One rank of the data-parallel env_n2n job: rollout, then epochs x (update, gradient all-reduce, Adam step); with
+    algo.minibatch_steps the update itself reduces and steps after every mini-batch and the epoch loop does neither."""
 
     def __init__(self, cfg, num_envs=None, num_eval_envs=64, eval_every=0, tuned_gemms=True):
         self.rank, self.local_rank, self.world = init_distributed()
@@ -321,7 +346,7 @@ class N2nTrainer(ParticleRunState):
         torch.manual_seed(int(cfg.runtime.get("seed", 0)))
         self.agent = N2nMAPPO(cfg, self.num_envs, max(1, round(self.num_envs / 10)), self.device)
         self.agent.sample_rank = self.rank
-        self.bucket = GradBucket(self.agent.ac_parameters)
+        self.bucket = self.agent.grad_bucket or GradBucket(self.agent.ac_parameters)   # (algo.minibatch_steps: the agent's own)
         self.agent.grad_bucket = self.bucket
         if self.agent.value_norm is not None:
             self.agent.value_norm.allreduce = allreduce_sum_   # (S1, S2, c) over ranks; without a process group a no-op
@@ -345,18 +370,28 @@ class N2nTrainer(ParticleRunState):
         ev[1].record()
         self.total_steps += steps * self.world
         self.last_epoch_diags, epochs_run = [], 0
+        per_minibatch, opt_steps, skipped = agent.minibatch_steps, 0, 0
         for _ in range(int(cfg.algo.epochs)):
             with torch.enable_grad():
                 obj_c, obj_a = agent.train(buf, self.total_steps)
+            over = False
             if agent.diag is not None:
                 self.last_epoch_diags.append(agent.last_update_diag)
-                # algo.target_kl: the policy has moved past the target on this buffer -- this epoch's gradient is discarded (the next
-                # train() zeroes the bucket) and the remaining epochs are skipped; the sums are all-reduced, so every rank stops here
-                if first_epoch_over([agent.last_update_diag["approx_kl"]], agent.target_kl) is not None:
+                # algo.target_kl: the policy has moved past the target on this buffer -- the remaining epochs are skipped; the sums are
+                # all-reduced, so every rank stops here.  Stepping once per epoch, this epoch's gradient is discarded as well (the next
+                # train() zeroes the bucket); with algo.minibatch_steps its steps were already taken and stand
+                over = first_epoch_over([agent.last_update_diag["approx_kl"]], agent.target_kl) is not None
+                if over and not per_minibatch:
                     break
-            allreduce_sum_(self.bucket.flat)
-            agent.ac_optimizer.step()
+            if per_minibatch:   # algo.minibatch_steps: train() reduced and stepped after every mini-batch; an epoch over the KL target
+                opt_steps += agent.last_optimizer_steps   # is the last one and its steps stand (there is nothing left to discard)
+                skipped += agent.last_skipped_steps
+            else:
+                allreduce_sum_(self.bucket.flat)
+                agent.ac_optimizer.step()
             epochs_run += 1
+            if over:
+                break
         ev[2].record()
         self.iteration += 1
         self.last_events = ev
@@ -364,6 +399,8 @@ class N2nTrainer(ParticleRunState):
                    episode_length=stats["episode_length"], critic_loss=obj_c, actor_loss=obj_a)
         if agent.diag is not None:   # of the last train() call, like the two losses
             log.update({k: agent.last_update_diag[k] for k in LOG_KEYS}, epochs_run=epochs_run)
+        if per_minibatch:
+            log.update(optimizer_steps=opt_steps, skipped_steps=skipped)
         if self.eval_every and self.iteration % self.eval_every == 0 and self.rank == 0:
             log.update(self.evaluate())
         return steps * self.world, log

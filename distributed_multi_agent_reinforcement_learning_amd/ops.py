@@ -19,7 +19,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "gauss_head_sample", "ppo_loss_gauss_fwd_bwd", "ppo_loss_gauss_workspace", "gauss_head_sample_ex", "ppo_loss_gauss_ex_fwd_bwd",
            "ppo_loss_gauss_ex_workspace", "gae_advnorm_vn", "gae_advnorm_vn_workspace", "value_norm_update", "value_norm_targets",
            "ppo_loss_fwd_bwd_diag", "ppo_loss_prob_fwd_bwd_diag", "ppo_loss_gauss_fwd_bwd_diag", "ppo_loss_gauss_ex_fwd_bwd_diag",
-           "ppo_loss_diag_workspace", "ppo_loss_gauss_diag_workspace", "ppo_ratio", "ppo_diag_rows_host", "mappo_ops_error_string")
+           "ppo_loss_diag_workspace", "ppo_loss_gauss_diag_workspace", "ppo_ratio", "ppo_diag_rows_host", "fused_adam_workspace",
+           "fused_adam_grid", "fused_adam_norm", "fused_adam_step", "fused_adam_advance_host", "fused_adam_rows_host", "mappo_ops_error_string")
 
 _lib = None
 
@@ -36,7 +37,7 @@ def load_library():
             raise RuntimeError(f"{path} is missing: build it with __graft_entry__.build() (hipcc --offload-arch=gfx950); "
                                "the fused MAPPO ops have no fallback")
         L = C.CDLL(path)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+        vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
         L.dhgn_msg_agg_fwd.argtypes = [i32, i32, i32, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, i64, vp]
         L.dhgn_msg_agg_bwd.argtypes = [i32, i32, i32, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp]
         L.dhgn_msg_agg3_fwd.argtypes = [vp, i32, i32, i32, vp, i64, vp, i64, vp]
@@ -117,6 +118,12 @@ def load_library():
         L.ppo_loss_gauss_diag_workspace.restype = i64
         L.ppo_ratio.argtypes = [i64, vp, vp, vp, vp, vp]
         L.ppo_diag_rows_host.argtypes = [i64, vp, vp, vp, vp, vp, vp, f32, vp]
+        L.fused_adam_workspace.restype = i64
+        L.fused_adam_grid.argtypes = [i64]
+        L.fused_adam_norm.argtypes = [i64, vp, vp, vp, f64, f64, f64, vp]
+        L.fused_adam_step.argtypes = [i64, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp]
+        L.fused_adam_advance_host.argtypes = [vp, f64, f64, f64, f64]
+        L.fused_adam_rows_host.argtypes = [i64, vp, vp, vp, vp, vp, f64, f64, f64, f64]
         L.sb_split_diag.argtypes = [i64, vp, vp, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
@@ -589,6 +596,36 @@ def value_norm_targets(v_target, active, state):
     value_norm_calls["value_norm_targets"] += 1
     _check(L.value_norm_targets(v_target.numel(), _ptr(v_target), _ptr(active), _ptr(state), _ptr(out), _stream()), "value_norm_targets")
     return out
+
+
+FUSED_ADAM_STATE = ("step", "b1t", "b2t", "norm", "coef", "skipped")
+
+
+def fused_adam_state(device):
+    """the state of one fused optimiser: (step, b1t, b2t, norm, coef, skipped) f64 on the device, before the first step"""
+    return torch.tensor([0.0, 1.0, 1.0, 0.0, 1.0, 0.0], dtype=torch.float64, device=device)
+
+
+def fused_adam_workspace(device):
+    """the zeroed workspace of fused_adam: the per-workgroup f64 partials and the ticket"""
+    return torch.zeros(load_library().fused_adam_workspace() // 8, dtype=torch.float64, device=device)
+
+
+def fused_adam(p, g, m, v, state, workspace, lr, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=0.0):
+    """one clip + Adam step in place on the flat fp32 tensors p, m, v from the gradient g (include/mappo_ops.h fused_adam_norm, then
+    fused_adam_step): state[3] <- |g|, the step under the coefficient min(1, max_norm / (|g| + 1e-6)) (max_norm <= 0: no clip); a
+    non-finite |g| changes nothing but state[5], the count of skipped steps.  Nothing visits the host."""
+    L = load_library()
+    _need_gpu(p, "fused_adam")
+    n = p.numel()
+    for t in (p, g, m, v):
+        assert t.dtype == torch.float32 and t.dim() == 1 and t.numel() == n and t.is_contiguous() and t.is_cuda and t.data_ptr() % 16 == 0
+    assert state.dtype == torch.float64 and state.shape == (len(FUSED_ADAM_STATE),) and state.is_contiguous() and state.is_cuda
+    assert workspace.dtype == torch.float64 and workspace.numel() * 8 >= L.fused_adam_workspace() and workspace.is_cuda
+    _check(L.fused_adam_norm(n, _ptr(g), _ptr(state), _ptr(workspace), float(max_norm), float(beta1), float(beta2), _stream()), "fused_adam_norm")
+    _check(L.fused_adam_step(n, _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(state), float(lr), float(beta1), float(beta2), float(eps), _stream()),
+           "fused_adam_step")
+    return state
 
 
 def categorical_sample(probs, seed, offset, greedy=False, counter=None, out=None):

@@ -14,8 +14,10 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import ops
 from .evaluator import EvaluatorProc, draw_learning_curve
 from .mappo import MAPPO
+from .minibatch_steps import check_entry as check_minibatch_steps_entry
 from .pursuit_env import Pursuit_Env
 from .obs_norm import check_entry as check_obs_norm_entry
 from .value_norm import check_entry as check_value_norm_entry
@@ -76,30 +78,117 @@ def allreduce_sum_(flat):
     return flat
 
 
+def bucket_offsets(params, align=1):
+    """-> (the element offset of every parameter in a flat bucket, the bucket's length): the parameters in order, each starting at a
+    multiple of `align` elements (the gaps stay zero); align = 1 is the dense layout"""
+    offsets, o = [], 0
+    for p in params:
+        offsets.append(o)
+        o += -(-p.numel() // align) * align
+    return offsets, o
+
+
 class GradBucket:
     """The gradients of `params` as views of ONE persistent flat fp32 tensor (ac_parameters order): autograd accumulates straight
     into the bucket, the collective reduces the bucket in place and the optimiser reads the same memory -- no torch.cat before the
     all-reduce and no per-parameter clone after it.  Parameters that receive no gradient (an unused GRU under algo.use_rnn: false)
     contribute zeros, which is what the SUM over learners of `None` entries amounts to (main.py:121-126)."""
 
-    def __init__(self, params):
+    def __init__(self, params, align=1):
         self.params = list(params)
-        total = sum(p.numel() for p in self.params)
+        self.offsets, total = bucket_offsets(self.params, align)   # align > 1: ParamBucket's layout (algo.minibatch_steps)
         self.flat = torch.zeros(total, dtype=torch.float32, device=self.params[0].device)
         self.attach()
 
     def attach(self):
-        o = 0
-        for p in self.params:
-            n = p.numel()
-            p.grad = self.flat[o:o + n].view_as(p)
-            o += n
+        for p, o in zip(self.params, self.offsets):
+            p.grad = self.flat[o:o + p.numel()].view_as(p)
 
     def zero(self):
         if any(p.grad is None or p.grad.data_ptr() < self.flat.data_ptr() or p.grad.data_ptr() >= self.flat.data_ptr() + self.flat.numel() * 4
                for p in self.params):
             self.attach()   # someone replaced a gradient tensor (e.g. a zero_grad(set_to_none=True)): re-attach the views
         self.flat.zero_()
+
+
+BUCKET_ALIGN = 4   # elements: every parameter of a ParamBucket starts on 16 bytes, which the kernels that read weights require
+
+
+class ParamBucket:
+    """algo.minibatch_steps: the parameters themselves as views of ONE persistent flat fp32 tensor (ac_parameters order, every
+    parameter on a 16-byte boundary; the gaps are zero and stay zero), so that the fused optimiser steps all of them in one launch.
+    The values are copied in and `p.data` is re-pointed; the matching gradient bucket is GradBucket(params, BUCKET_ALIGN)."""
+
+    def __init__(self, params):
+        self.params = list(params)
+        self.offsets, total = bucket_offsets(self.params, BUCKET_ALIGN)
+        self.flat = torch.zeros(total, dtype=torch.float32, device=self.params[0].device)
+        self.attach()
+
+    def view(self, k):
+        p, o = self.params[k], self.offsets[k]
+        return self.flat[o:o + p.numel()].view(p.shape)
+
+    def attached(self):
+        return all(p.data_ptr() == self.flat.data_ptr() + 4 * o and p.is_contiguous() for p, o in zip(self.params, self.offsets))
+
+    @torch.no_grad()
+    def attach(self):
+        """copies the values of every parameter that lives elsewhere into its slot and points the parameter at the slot"""
+        for k, (p, o) in enumerate(zip(self.params, self.offsets)):
+            if p.data_ptr() != self.flat.data_ptr() + 4 * o or not p.is_contiguous():
+                v = self.view(k)
+                v.copy_(p.data)
+                p.data = v
+
+    def ensure(self):
+        if not self.attached():
+            self.attach()   # someone re-pointed a parameter (a .to(), a p.data = ...): its values come back in, the views are restored
+
+
+class FusedAdam:
+    """algo.minibatch_steps: torch.optim.Adam(eps=1e-5) with clip_grad_norm_ in front, as two launches on the flat tensors
+    (ops.fused_adam; csrc/fused_adam.hpp).  Owns the moments m, v, the device state (step, b1t, b2t, norm, coef, skipped) and the
+    workspace; `param_groups` carries the learning rate the way torch's optimisers do, so lr_decay and the resume bundle read and
+    write it unchanged.  The kernel writes the weights behind autograd's back: nothing in the package caches a weight by version
+    counter (spectral norm recomputes from weight_orig every forward)."""
+
+    KIND = "fused_adam"
+
+    def __init__(self, bucket, lr, betas=(0.9, 0.999), eps=1e-5):
+        self.bucket = bucket
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.param_groups = [{"lr": float(lr)}]
+        dev = bucket.flat.device
+        self.m, self.v = torch.zeros_like(bucket.flat), torch.zeros_like(bucket.flat)
+        self.state = ops.fused_adam_state(dev)
+        self.workspace = ops.fused_adam_workspace(dev)
+        self.skipped_seen = 0.0   # state[5] as last read on the host (the agents' per-call count of skipped steps)
+
+    @property
+    def grad_norm(self):
+        """the gradient norm of the last step before clipping, a device scalar"""
+        return self.state[3]
+
+    @property
+    def skipped(self):
+        return self.state[5]
+
+    def step(self, grad_flat, max_norm=0.0):
+        self.bucket.ensure()
+        ops.fused_adam(self.bucket.flat, grad_flat, self.m, self.v, self.state, self.workspace, self.param_groups[0]["lr"], self.betas[0],
+                       self.betas[1], self.eps, max_norm)
+
+    def state_dict(self):
+        return dict(kind=self.KIND, state=self.state.cpu(), m=self.m.cpu(), v=self.v.cpu())
+
+    def load_state_dict(self, sd):
+        if not isinstance(sd, dict) or sd.get("kind") != self.KIND or sd["m"].shape != self.m.shape:
+            raise ValueError("optimizer state is not a fused_adam state of this parameter layout (algo.minibatch_steps)")
+        self.state.copy_(sd["state"])
+        self.m.copy_(sd["m"])
+        self.v.copy_(sd["v"])
+        self.skipped_seen = float(sd["state"][5])
 
 
 def broadcast_weights_(modules, src=0):
@@ -155,7 +244,8 @@ class ParticleRunState:
     reset generators, the sampling counters, the weights and Adam are all the state a run carries from one iteration to the next --
     and, with algo.use_reward_scaling, the training environment's reward_scale (the bundle's "reward_scaling" entry), with
     algo.use_value_norm the agent's value-normaliser state (the "value_norm" entry), with algo.use_obs_norm (env_3d) the agent's
-    feature-normaliser state (the "obs_norm" entry; its slots are empty between iterations and are not saved)."""
+    feature-normaliser state (the "obs_norm" entry; its slots are empty between iterations and are not saved).  With
+    algo.minibatch_steps the bundle says so ("minibatch_steps": True) and its "optimizer" is FusedAdam's state."""
 
     def save_resume(self, path):
         agent, ev = self.agent, self.eval_env
@@ -175,6 +265,8 @@ class ParticleRunState:
             bundle["value_norm"] = agent.value_norm.entry()
         if getattr(agent, "obs_norm", None) is not None:     # algo.use_obs_norm: the clip and the state (2, 33); off: no entry
             bundle["obs_norm"] = agent.obs_norm.entry()
+        if getattr(agent, "minibatch_steps", False):         # algo.minibatch_steps: "optimizer" is FusedAdam's state; off: no entry
+            bundle["minibatch_steps"] = True
         torch.save(bundle, path)
 
     def load_resume(self, path):
@@ -191,6 +283,7 @@ class ParticleRunState:
                              f"this agent has algo.use_reward_scaling: {str(mine).lower()}")
         check_value_norm_entry(agent, b.get("value_norm"), f"resume bundle {path}")
         check_obs_norm_entry(agent, b.get("obs_norm"), f"resume bundle {path}")
+        check_minibatch_steps_entry(agent, b.get("minibatch_steps"), f"resume bundle {path}")
         agent.actor.load_state_dict(b["actor"])
         agent.critic.load_state_dict(b["critic"])
         agent.ac_optimizer.load_state_dict(b["optimizer"])

@@ -156,6 +156,30 @@ int value_norm_update(double *vn_state, const double *sums, double beta, void *s
 int value_norm_targets(int64_t n, const float *v_target, const float *active, const double *vn_state, float *out, void *stream);
 
 /*
+ * The gradient clip and the Adam step of one mini-batch (algo.minibatch_steps of the env_3d / env_n2n trainers; csrc/fused_adam.hpp,
+ * tests/fused_adam_ref.py): two launches over flat fp32 arrays of n elements, all pointers 16-byte aligned.
+ * state: 6 f64 on the device, (step, b1t, b2t, norm, coef, skipped); at the start (0, 1, 1, 0, 1, 0).  workspace:
+ *   fused_adam_workspace() bytes, zero before the first call (per-workgroup partials and the ticket, which the kernel leaves zero).
+ * fused_adam_norm: norm = sqrt(sum (double)g[i]^2), f64 per-workgroup partials (fused_adam_grid(n) workgroups, each over a fixed
+ *   slice in a fixed order) that the last workgroup to arrive adds in index order: no float atomics, the same bits every run.
+ *   coef = min(1, max_norm / (norm + 1e-6)), exactly 1 when max_norm <= 0.  A finite norm: step += 1, b1t *= beta1, b2t *= beta2;
+ *   else skipped += 1 and coef = -1, under which fused_adam_step stores nothing.
+ * fused_adam_step: per element, in f64 from the fp32 inputs, no contraction, in this order:
+ *   gc = g coef; m64 = beta1 m + (1 - beta1) gc; v64 = beta2 v + ((1 - beta2) gc) gc; den = sqrt(v64) / sqrt(1 - b2t) + eps;
+ *   p64 = p - lr ((m64 / (1 - b1t)) / den); p, m, v <- (float) of p64, m64, v64.
+ * fused_adam_advance_host / fused_adam_rows_host: the end of launch 1 from a sum of squares and the element step of launch 2 on the
+ *   host (no device), the same inline functions; rows_host updates p, m, v [n] in place under state's coef, b1t, b2t.
+ */
+int64_t fused_adam_workspace(void);
+int fused_adam_grid(int64_t n);
+int fused_adam_norm(int64_t n, const float *g, double *state, void *workspace, double max_norm, double beta1, double beta2, void *stream);
+int fused_adam_step(int64_t n, float *p, const float *g, float *m, float *v, const double *state, double lr, double beta1, double beta2,
+                    double eps, void *stream);
+int fused_adam_advance_host(double *state, double sumsq, double max_norm, double beta1, double beta2);
+int fused_adam_rows_host(int64_t n, float *p, const float *g, float *m, float *v, const double *state, double lr, double beta1, double beta2,
+                         double eps);
+
+/*
  * Categorical(probs).sample() + log_prob for a batch of rows (DHGN/mappo_parallel.py:446-448) with a counter-based
  * generator (Philox4x32-10; stream = (seed, offset + row)): probs [R][A] -> action [R] int32, logp [R].
  * greedy != 0 gives probs.argmax(-1) instead (choose_action(deterministic=True), :442-444; first maximum wins).
