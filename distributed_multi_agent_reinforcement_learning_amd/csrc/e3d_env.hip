@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "e3d_env.h"
+#include "guidance.hpp"
 #include "obs_norm.hpp"
 #include "reward_scale.hpp"
 #include "reward_shaping.hpp"
@@ -575,6 +576,49 @@ int e3d_record_launch(const e3d_config *c, const e3d_state *st, const float *rew
     return (int)hipGetLastError();
 }
 
+// the scripted pursuers (include/e3d_env.h e3d_pursuer_guidance; csrc/guidance.hpp): the tick's lane layout, lane = (environment,
+// pursuer).  Every lane keeps its pursuer and its own copy of the evader in registers and reads its team-mates through shuffles inside
+// the group, in index order; no LDS, no atomics, three f64 stores per lane.  Every lane of the wave runs the shuffle loop (the trip
+// count is wave-uniform); only the lanes of real pursuers store.
+template <int PT>
+__global__ __launch_bounds__(WAVE * WPB) void k_e3d_guidance(const e3d_config c, const e3d_state st, const e3d_guidance_params gp, double *actions) {
+    constexpr int G = WAVE / PT;
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT, base = lane - a;
+    const int env = wave * G + g, P = c.P;
+    const bool ev = env < st.N, pv = ev && a < P;
+    double x = 0, y = 0, z = 0, phi = 0, gamma = 0, act = 0;
+    double ex = 0, ey = 0, ez = 0, ephi = 0, egam = 0, evel = 0, eact = 0;
+    if (pv) {
+        const double *q = st.p + (size_t)env * 7 * P + a;
+        x = q[0]; y = q[P]; z = q[2 * P]; phi = q[3 * P]; gamma = q[4 * P]; act = q[6 * P];
+    }
+    if (ev) {
+        const double *ge = st.e + (size_t)env * 7;
+        ex = ge[0]; ey = ge[1]; ez = ge[2]; ephi = ge[3]; egam = ge[4]; evel = ge[5]; eact = ge[6];
+    }
+    const double rx = ex - x, ry = ey - y, rz = ez - z;
+    const double t = guide::lead_time(rshape::dist3(rx, ry, rz), c.p_vmax, gp.lead);
+    const double cg = cos(egam);
+    double gx, gy, gz;
+    guide::unit(rx + t * (evel * cg * cos(ephi)), ry + t * (evel * cg * sin(ephi)), rz + t * (evel * sin(egam)), gx, gy, gz);
+    for (int k = 0; k < P; k++) {
+        const double kx = __shfl(x, base + k), ky = __shfl(y, base + k), kz = __shfl(z, base + k), ka = __shfl(act, base + k);
+        const double dx = x - kx, dy = y - ky, dz = z - kz, dij = rshape::dist3(dx, dy, dz);
+        if (k != a && ka != 0.0 && guide::in_sep(dij, gp.sep_range)) {
+            gx = gx + guide::repel(gp.sep_gain, dx, dij, gp.sep_range);
+            gy = gy + guide::repel(gp.sep_gain, dy, dij, gp.sep_range);
+            gz = gz + guide::repel(gp.sep_gain, dz, dij, gp.sep_range);
+        }
+    }
+    if (pv) {
+        double a0, a1, a2;
+        guide::e3d_command(act != 0.0 && eact != 0.0, gx, gy, gz, phi, gamma, a0, a1, a2);
+        double *d = actions + ((size_t)env * P + a) * 3;
+        d[0] = a0; d[1] = a1; d[2] = a2;
+    }
+}
+
 struct E3dResetter { e3d_config cfg; int N; std::vector<rngrep::NpRandom> rng; };
 
 }  // namespace
@@ -698,6 +742,22 @@ int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, d
 #define E3D_SB(PT) hipLaunchKernelGGL((k_e3d_shaping_begin<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, phi, coef)
     if (pt == 8) E3D_SB(8); else if (pt == 16) E3D_SB(16); else if (pt == 32) E3D_SB(32); else E3D_SB(64);
 #undef E3D_SB
+    return (int)hipGetLastError();
+}
+
+int e3d_pursuer_guidance(const e3d_config *cfg, const e3d_state *st, const e3d_guidance_params *params, double *actions, void *stream) {
+    if (!cfg || !st || !params || !actions) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (!guide::param_ok(params->lead) || !guide::param_ok(params->sep_range) || !guide::param_ok(params->sep_gain)) return E3D_ERR_BAD_CONFIG;
+    if (st->N < 1) return 0;
+    if (!st->p || !st->e) return E3D_ERR_NULL;
+    const int pt = cfg->P <= 8 ? 8 : (cfg->P <= 16 ? 16 : (cfg->P <= 32 ? 32 : 64));
+    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    hipStream_t s = (hipStream_t)stream;
+#define E3D_GD(PT) hipLaunchKernelGGL((k_e3d_guidance<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, *params, actions)
+    if (pt == 8) E3D_GD(8); else if (pt == 16) E3D_GD(16); else if (pt == 32) E3D_GD(32); else E3D_GD(64);
+#undef E3D_GD
     return (int)hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "n2n_env.h"
+#include "guidance.hpp"
 #include "reward_scale.hpp"
 #include "reward_shaping.hpp"
 #include "rng_replica.hpp"
@@ -443,6 +444,43 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_shaping_begin(const n2n_conf
     phi[(size_t)env * P + a] = n2n_potential(gp, ge, P, E, a, gp[4 * P + a] != 0.0, coef);
 }
 
+// the scripted pursuers (include/n2n_env.h n2n_pursuer_guidance; csrc/guidance.hpp): the tick's lane layout, slot a = pursuer a and
+// evader a in registers.  Every lane walks the E evaders (nearest active one, lowest index on ties) and then its P team-mates, in
+// index order, through shuffles inside the group; no LDS, no atomics, one int32 store per lane.  Every lane of the wave runs both
+// loops (the trip counts are wave-uniform); only the lanes of real pursuers store.
+template <int PT>
+__global__ __launch_bounds__(WAVE * WPB) void k_n2n_guidance(const n2n_config c, const n2n_state st, const n2n_guidance_params gp, int32_t *actions) {
+    constexpr int G = WAVE / PT;
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT, base = lane - a;
+    const int env = wave * G + g, P = c.P, E = c.E;
+    const bool ev = env < st.N, pv = ev && a < P, evv = ev && a < E;
+    const double *q = st.p + (size_t)(ev ? env : 0) * 5 * P, *ge = st.e + (size_t)(ev ? env : 0) * 5 * E;
+    double px = 0, py = 0, pact = 0, ex = 0, ey = 0, ephi = 0, evel = 0, eact = 0;
+    if (pv) { px = q[a]; py = q[P + a]; pact = q[4 * P + a]; }
+    if (evv) { ex = ge[a]; ey = ge[E + a]; ephi = ge[2 * E + a]; evel = ge[3 * E + a]; eact = ge[4 * E + a]; }
+    bool any = false;
+    double rx = 0, ry = 0, d = 0, tphi = 0, tvel = 0;   // the chosen evader: r = e_pos - p_i, d = |r|, its heading and speed
+    for (int k = 0; k < E; k++) {
+        const double kx = __shfl(ex, base + k), ky = __shfl(ey, base + k), kp = __shfl(ephi, base + k), kv = __shfl(evel, base + k);
+        const double ka = __shfl(eact, base + k);
+        const double dx = kx - px, dy = ky - py, dk = rshape::dist2(dx, dy);
+        if (ka != 0.0 && (!any || dk < d)) { any = true; rx = dx; ry = dy; d = dk; tphi = kp; tvel = kv; }
+    }
+    const double t = guide::lead_time(d, c.p_vmax, gp.lead);
+    double gx, gy, gz;
+    guide::unit(rx + t * (tvel * cos(tphi)), ry + t * (tvel * sin(tphi)), 0.0, gx, gy, gz);
+    for (int k = 0; k < P; k++) {
+        const double kx = __shfl(px, base + k), ky = __shfl(py, base + k), ka = __shfl(pact, base + k);
+        const double dx = px - kx, dy = py - ky, dij = rshape::dist2(dx, dy);
+        if (k != a && ka != 0.0 && guide::in_sep(dij, gp.sep_range)) {
+            gx = gx + guide::repel(gp.sep_gain, dx, dij, gp.sep_range);
+            gy = gy + guide::repel(gp.sep_gain, dy, dij, gp.sep_range);
+        }
+    }
+    if (pv) actions[(size_t)env * P + a] = guide::n2n_command(pact != 0.0 && any, gx, gy);
+}
+
 // n2n_policy_record / n2n_policy_record_scaled / n2n_policy_record_shaped: one launch, the tick's lane layout
 template <bool SCALED, bool SHAPED>
 int n2n_record_launch(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
@@ -572,6 +610,22 @@ int n2n_shaping_begin(const n2n_config *cfg, const n2n_state *st, double *phi, d
 #define N2N_SB(PT) hipLaunchKernelGGL((k_n2n_shaping_begin<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, phi, coef)
     if (pt == 8) N2N_SB(8); else if (pt == 16) N2N_SB(16); else if (pt == 32) N2N_SB(32); else N2N_SB(64);
 #undef N2N_SB
+    return (int)hipGetLastError();
+}
+
+int n2n_pursuer_guidance(const n2n_config *cfg, const n2n_state *st, const n2n_guidance_params *params, int32_t *actions, void *stream) {
+    if (!cfg || !st || !params || !actions) return N2N_ERR_NULL;
+    const int rc = n2n_config_check(cfg);
+    if (rc) return rc;
+    if (!guide::param_ok(params->lead) || !guide::param_ok(params->sep_range) || !guide::param_ok(params->sep_gain)) return N2N_ERR_BAD_CONFIG;
+    if (st->N < 1) return 0;
+    if (!st->p || !st->e) return N2N_ERR_NULL;
+    int blocks;
+    const int pt = n2n_lanes(cfg, st->N, &blocks);
+    hipStream_t s = (hipStream_t)stream;
+#define N2N_GD(PT) hipLaunchKernelGGL((k_n2n_guidance<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, *params, actions)
+    if (pt == 8) N2N_GD(8); else if (pt == 16) N2N_GD(16); else if (pt == 32) N2N_GD(32); else N2N_GD(64);
+#undef N2N_GD
     return (int)hipGetLastError();
 }
 

@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.utils import spectral_norm
 
+from . import guidance as gd
 from . import obs_norm as onorm
 from . import ops
 from . import value_norm as vnorm
@@ -131,6 +132,7 @@ class E3dMAPPO:
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.update_diagnostics, self.target_kl = update_diag_options(cfg)   # what the update did, from the loss launches
         self.minibatch_steps = minibatch_steps_options(cfg)   # one clip + Adam step per mini-batch, fused
+        self.guidance = gd.guidance_options(cfg)   # the scripted pursuers of run_episode(policy="guidance")
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
         self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
@@ -219,7 +221,7 @@ class E3dMAPPO:
         return buf
 
     @torch.no_grad()
-    def run_episode(self, env, buf=None, greedy=False):
+    def run_episode(self, env, buf=None, greedy=False, policy="network"):
         """N episodes in lockstep for T = env.max_step ticks.  Row (n, t, p) is live iff environment n was not done before step t and
         pursuer p was active at its start; rewards, values and the `active` mask of other rows are zero, so is v_n[n, t + 1, p] when
         pursuer p or episode n ended in step t for any reason but the time limit; v_n[:, T] is the critic's bootstrap value.  The masks
@@ -228,7 +230,12 @@ class E3dMAPPO:
         distance and a buffer, r (what is scaled, when both are on) carries the shaping term gamma Phi' - Phi (env.shaping_phi).
         With algo.use_obs_norm the features (and feat_a / feat_c) are normalised under obs_norm.state, which no tick changes; with a
         buffer every tick adds the sums of its live rows to obs_norm.slots (explore_env merges them).
+        policy="guidance" (buf must be None): the tick takes the scripted pursuers' actions (guidance_episode below) instead of the
+        network's; no network, sampler or sampling counter is touched, the accumulators and the returned triple are the same.
         Returns per-environment (return, captured, length) device tensors."""
+        gd.check_policy(policy, buf)
+        if policy == "guidance":
+            return guidance_episode(env)
         N, P, T = env.num_envs, env.p_num, env.max_step
         env.reset()
         st = self._state(env)
@@ -408,6 +415,23 @@ class E3dMAPPO:
             self.obs_norm.load_entry(sd["obs_norm"])
 
 
+@torch.no_grad()
+def guidance_episode(env):
+    """N episodes in lockstep for T = env.max_step ticks with the scripted lead-pursuit pursuers (ParticleEnv.guidance_actions, one
+    launch per tick) where run_episode has its policy step: the evader's command, the tick and policy_record are run_episode's, so the
+    raw return, the captured flag and the length mean what they mean there.  Needs no agent.
+    Returns per-environment (return, captured, length) device tensors."""
+    env.reset()
+    live = env.active_t.float()   # no environment is done; policy_record writes the next step's mask
+    acc = env.new_accumulators()
+    for _ in range(env.max_step):
+        actions = env.guidance_actions()
+        env.evader_step()
+        env.step(actions)
+        env.policy_record(acc, live, live_next=live)
+    return acc["ret"], acc["captured"] != 0, acc["length"]
+
+
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
     """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env).  A training
     environment owns the RewardScaling state when algo.use_reward_scaling is on and the shaping state when algo.reward_shaping is
@@ -421,6 +445,7 @@ def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True)
     mode, coef = reward_shaping_options(cfg)
     if training and mode == "distance":
         env.enable_reward_shaping(coef)
+    env.set_guidance(*gd.guidance_options(cfg))
     return env
 
 
@@ -451,6 +476,7 @@ class E3dTrainer(ParticleRunState):
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
         self.eval_env = None
+        self.eval_baseline, self.baseline_record = gd.eval_baseline_options(cfg), None   # runtime.eval_baseline
         self.eval_return_std = None
         self.recorder, self.best_eval_return = [], -float("inf")
         self.total_steps = 0
@@ -507,7 +533,20 @@ class E3dTrainer(ParticleRunState):
         ret, captured, length = self.agent.run_episode(ev, None, greedy=True)
         sd = ret.std() if ret.numel() > 1 else ret.new_zeros(())
         r, c, l, self.eval_return_std = torch.stack((ret.mean(), captured.float().mean(), length.mean(), sd)).tolist()
-        return dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+        rec = dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+        if self.eval_baseline is not None:
+            rec.update(self.baseline())
+        return rec
+
+    def baseline(self):
+        """runtime.eval_baseline: guidance -- the scripted pursuers' return, capture rate and episode length on num_eval_envs
+        environments of the evaluation seeds (seed + 10^6 + n), as baseline_* fields.  The law is deterministic and the environments
+        are its own (their first episode; the evaluation environments and their generators are not touched), so it runs once and
+        every later evaluation record carries the same figures."""
+        if self.baseline_record is None:
+            env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6, training=False)
+            self.baseline_record = gd.baseline_record(*self.agent.run_episode(env, None, policy="guidance"))
+        return dict(self.baseline_record)
 
     def make_eval_env(self):
         """the evaluation environments (created once): num_eval_envs of their own seeds, seed + 10^6 + n"""

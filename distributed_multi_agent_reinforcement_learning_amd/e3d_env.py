@@ -33,6 +33,10 @@ class E3dObsOut(C.Structure):
                 ("pp_adj", C.c_void_p), ("pp_adj_stride", C.c_int64), ("pe_adj", C.c_void_p), ("pe_adj_stride", C.c_int64)]
 
 
+class E3dGuidanceParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("lead", "sep_range", "sep_gain")]
+
+
 class E3dPolicyAcc(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("done_before", "ended", "captured", "ret", "length")]
 
@@ -85,6 +89,7 @@ def load_library():
         L.e3d_policy_record.argtypes = [vp] * 7 + [C.c_double, vp]
         L.e3d_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
         L.e3d_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
+        L.e3d_pursuer_guidance.argtypes = [vp] * 5
         _lib = L
     return _lib
 
@@ -126,6 +131,8 @@ class ParticleEnv:
         self.resetter = None
         self.reward_scale = None
         self.shaping_phi, self.shaping_coef = None, None
+        self._guidance_out = None
+        self.set_guidance()   # the scripted pursuers' defaults
 
     def initialize(self, p_num):
         """particle_env.py:133-135, plus the allocation of the device records"""
@@ -333,6 +340,28 @@ class ParticleEnv:
         assert phi.dtype == torch.float64 and phi.is_contiguous() and phi.shape == (N, P) and phi.device == self.p.device
         _check(self.L.e3d_policy_record_shaped(*args, C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef), C.c_double(float(shaping_gamma)),
                                                C.c_void_p(rs_ptr), _stream()), "e3d_policy_record_shaped")
+
+    # ---- scripted pursuers (guidance.py) --------------------------------------------------------------------------
+    def set_guidance(self, lead=1.0, sep_range=None, sep_gain=1.0):
+        """the parameters of guidance_actions (runtime.guidance_lead / guidance_sep_range / guidance_sep_gain): the longest look-ahead in
+        the environment's time units, the range inside which team-mates repel (None: 4 x kill_radius) and the weight of that repulsion"""
+        g = E3dGuidanceParams()
+        g.lead, g.sep_range, g.sep_gain = float(lead), float(4.0 * self.kill_radius if sep_range is None else sep_range), float(sep_gain)
+        self.guidance = g
+
+    def guidance_actions(self, out=None):
+        """the scripted lead-pursuit action of every pursuer for the current state, (N, P, 3) f64, what step() takes
+        (e3d_pursuer_guidance, include/e3d_env.h; specification: tests/guidance_ref.py): one launch, nothing but `out` is written.
+        out: a dense device tensor of that shape and type (None: the environment's own, allocated once)."""
+        N, P = self.num_envs, self.p_num
+        if out is None:
+            if self._guidance_out is None:
+                self._guidance_out = torch.zeros((N, P, 3), dtype=torch.float64, device=self.device)
+            out = self._guidance_out
+        assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (N, P, 3) and out.device == self.p.device
+        _check(self.L.e3d_pursuer_guidance(C.byref(self.c), C.byref(self.st), C.byref(self.guidance), C.c_void_p(out.data_ptr()), _stream()),
+               "e3d_pursuer_guidance")
+        return out
 
     def step(self, action):
         """:205-219 (preceded by the evader's move with the command of evader_step) -> (reward (N,P), done (N,), active (N,P));

@@ -18,12 +18,22 @@ iteration, `--resume DIR` continues from them.  `--evaluate CWD` (env_3d and env
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --iterations 50 --save-resume ckpt
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --iterations 100 --resume ckpt --save-resume ckpt
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --evaluate ./model
+
+`--baseline guidance` (env_3d and env_n2n) needs no model: it runs the scripted lead-pursuit pursuers (guidance.py, DESIGN.md section 7e;
+runtime.guidance_lead / guidance_sep_range / guidance_sep_gain) for one episode on --eval-envs environments of the evaluation seeds and
+prints the JSON keys of `--evaluate`, the yardstick to read a training log against:
+
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --baseline guidance --eval-envs 2048
 """
 import argparse
 import json
 
+import torch
+
 from .config import baseline_config, load_config, parse_overrides
+from . import e3d_agent, n2n_agent
 from .e3d_agent import E3dTrainer, train_e3d
+from .guidance import BASELINES as SCRIPTED_BASELINES
 from .n2n_agent import N2nTrainer, train_n2n
 from .trainer import train_agent_multiprocessing
 
@@ -40,11 +50,17 @@ def main(argv=None):
     ap.add_argument("--resume", metavar="DIR", default=None, help="load DIR/resume_rank{r}.pt before the first iteration")
     ap.add_argument("--evaluate", metavar="CWD", default=None,
                     help="env_3d / env_n2n: evaluate the weights saved under CWD on --eval-envs environments and exit")
+    ap.add_argument("--baseline", choices=SCRIPTED_BASELINES, default=None,
+                    help="env_3d / env_n2n: run the scripted pursuers on --eval-envs environments of the evaluation seeds and exit (no model)")
     ap.add_argument("overrides", nargs="*", help="dotted overrides KEY=VALUE")
     args = ap.parse_args(argv)
     ov = parse_overrides(args.overrides)
     cfg = baseline_config(args.config, **ov) if args.config in BASELINES else load_config(args.config, **ov)
     env = str(cfg.runtime.get("env", "pursuit"))
+    if args.baseline is not None:
+        if env not in ("e3d", "n2n"):
+            ap.error("--baseline is for runtime.env e3d and n2n (cfg5, cfg4_n2n); the pursuit configurations have no scripted pursuers")
+        return baseline_guidance(cfg, env, args.eval_envs)
     if args.evaluate is not None:
         if env not in ("e3d", "n2n"):
             ap.error("--evaluate is for runtime.env e3d and n2n (cfg5, cfg4_n2n)")
@@ -69,6 +85,19 @@ def evaluate_saved(trainer_cls, cfg, cwd, num_eval_envs):
     res = tr.evaluate()
     if tr.rank == 0:
         print(json.dumps(res), flush=True)
+    return res
+
+
+def baseline_guidance(cfg, env_kind, num_eval_envs):
+    """one episode of the scripted pursuers on num_eval_envs environments of the evaluation seeds (seed + 10^6 + n, the environments
+    trainer.evaluate starts from); prints the keys of --evaluate as one JSON line.  No trainer, no model, no process group."""
+    mod = e3d_agent if env_kind == "e3d" else n2n_agent
+    env = mod.make_env(cfg, int(num_eval_envs), 0, "cuda", seed_offset=10 ** 6, training=False)
+    out = mod.guidance_episode(env)
+    ret, captured, length = (out["ret"], out["captured"] != 0, out["length"]) if isinstance(out, dict) else out
+    r, c, l = torch.stack((ret.mean(), captured.float().mean(), length.mean())).tolist()
+    res = dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+    print(json.dumps(res), flush=True)
     return res
 
 

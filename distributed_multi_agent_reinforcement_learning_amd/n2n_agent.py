@@ -15,6 +15,7 @@ import time
 
 import torch
 
+from . import guidance as gd
 from . import ops
 from . import value_norm as vnorm
 from .minibatch_steps import MAX_GRAD_NORM, minibatch_steps_options
@@ -71,6 +72,7 @@ class N2nMAPPO:
         self.reward_shaping, self.shaping_coef = reward_shaping_options(cfg)   # distance shaping in policy_record
         self.update_diagnostics, self.target_kl = update_diag_options(cfg)   # what the update did, from the loss launches
         self.minibatch_steps = minibatch_steps_options(cfg)   # one clip + Adam step per mini-batch, fused
+        self.guidance = gd.guidance_options(cfg)   # the scripted pursuers of run_episode(policy="guidance")
         if bool(a.get("use_obs_norm", False)):
             raise ValueError("algo.use_obs_norm: true is built for runtime.env e3d only; the env_n2n inputs are node states whose "
                              "differences the message kernels form and whose zero rows stand for absent nodes (set use_obs_norm to false)")
@@ -157,7 +159,7 @@ class N2nMAPPO:
         return buf
 
     @torch.no_grad()
-    def run_episode(self, env, buf=None, greedy=False):
+    def run_episode(self, env, buf=None, greedy=False, policy="network"):
         """N episodes in lockstep for T = env.episode_limit ticks.  Per tick: policy_inputs, the policy step, the SLSQP evader, the tick,
         policy_record, and (with a buffer) one rollout_record launch.  Row (n, t, p) is live iff pursuer p was active at the start of step t
         and environment n was not done before it; r, v_n and `active` of other rows are zero, so is v_n[n, t + 1, p] when pursuer p or
@@ -165,7 +167,12 @@ class N2nMAPPO:
         With algo.use_reward_scaling and a buffer, r is the scaled reward (env.reward_scale advances); acc["ret"] stays the raw return.
         With algo.reward_shaping: distance and a buffer, r (what is scaled, when both are on) carries the shaping term
         gamma Phi' - Phi (env.shaping_phi, written by shaping_begin after the reset).
+        policy="guidance" (buf must be None): the tick takes the scripted pursuers' actions (guidance_episode below) instead of the
+        network's; no network, sampler or sampling counter is touched, the accumulators are the same.
         Returns the per-environment accumulators (done_before, ended, captured, ret, length)."""
+        gd.check_policy(policy, buf)
+        if policy == "guidance":
+            return guidance_episode(env)
         N, P, T, d = env.num_envs, env.p_num, env.episode_limit, self.depth
         env.reset()
         st = self._state(env)
@@ -315,6 +322,24 @@ class N2nMAPPO:
             self.value_norm.load_entry(entry)
 
 
+@torch.no_grad()
+def guidance_episode(env):
+    """N episodes in lockstep for T = env.episode_limit ticks with the scripted lead-pursuit pursuers (ParticleEnv.guidance_actions, one
+    launch per tick) where run_episode has its policy step: the live mask (policy_inputs), the evaders' command, the tick and
+    policy_record are run_episode's, so the raw return, the captured flag and the length mean what they mean there.  Needs no agent.
+    Returns the per-environment accumulators (done_before, ended, captured, ret, length)."""
+    env.reset()
+    live = torch.zeros((env.num_envs, env.p_num), dtype=torch.float32, device=env.device)
+    acc = env.new_accumulators()
+    for _ in range(env.episode_limit):
+        env.policy_inputs(None, None, None, live, None, None, acc["done_before"])
+        actions = env.guidance_actions()
+        env.evader_step()
+        env.step(actions)
+        env.policy_record(acc, live)
+    return acc
+
+
 def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True):
     """ParticleEnv of one rank: environment n of rank r is reset from seed + max(1000, num_envs) r + n (as Pursuit_Env).  A training
     environment owns the RewardScaling state when algo.use_reward_scaling is on and the shaping state when algo.reward_shaping is
@@ -328,6 +353,7 @@ def make_env(cfg, num_envs, rank=0, device="cuda", seed_offset=0, training=True)
     mode, coef = reward_shaping_options(cfg)
     if training and mode == "distance":
         env.enable_reward_shaping(coef)
+    env.set_guidance(*gd.guidance_options(cfg))
     return env
 
 
@@ -356,6 +382,7 @@ class N2nTrainer(ParticleRunState):
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
         self.eval_env = None
+        self.eval_baseline, self.baseline_record = gd.eval_baseline_options(cfg), None   # runtime.eval_baseline
         self.eval_return_std = None
         self.recorder, self.best_eval_return = [], -float("inf")
         self.total_steps = 0
@@ -413,7 +440,21 @@ class N2nTrainer(ParticleRunState):
         ret = acc["ret"]
         sd = ret.std() if ret.numel() > 1 else ret.new_zeros(())
         r, c, l, self.eval_return_std = torch.stack((ret.mean(), acc["captured"].float().mean(), acc["length"].mean(), sd)).tolist()
-        return dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+        rec = dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+        if self.eval_baseline is not None:
+            rec.update(self.baseline())
+        return rec
+
+    def baseline(self):
+        """runtime.eval_baseline: guidance -- the scripted pursuers' return, capture rate and episode length on num_eval_envs
+        environments of the evaluation seeds (seed + 10^6 + n), as baseline_* fields.  The law is deterministic and the environments
+        are its own (their first episode; the evaluation environments and their generators are not touched), so it runs once and
+        every later evaluation record carries the same figures."""
+        if self.baseline_record is None:
+            env = make_env(self.cfg, self.num_eval_envs, 0, self.device, seed_offset=10 ** 6, training=False)
+            acc = self.agent.run_episode(env, None, policy="guidance")
+            self.baseline_record = gd.baseline_record(acc["ret"], acc["captured"], acc["length"])
+        return dict(self.baseline_record)
 
     def make_eval_env(self):
         """the evaluation environments (created once): num_eval_envs of their own seeds, seed + 10^6 + n"""

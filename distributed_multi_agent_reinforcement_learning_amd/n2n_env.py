@@ -37,6 +37,10 @@ class N2nPolicyIO(C.Structure):
     _fields_ = [(n, t) for k in ("pp_in", "pe_in", "p4", "e4", "e_ref", "live", "pp_adj", "pe_adj") for n, t in ((k, C.c_void_p), (k + "_rs", C.c_int64))]
 
 
+class N2nGuidanceParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("lead", "sep_range", "sep_gain")]
+
+
 class N2nPolicyAcc(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("done_before", "ended", "captured", "ret", "length")]
 
@@ -85,6 +89,7 @@ def load_library():
         L.n2n_policy_record_scaled.argtypes = [vp] * 7 + [C.c_double, vp]
         L.n2n_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
         L.n2n_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
+        L.n2n_pursuer_guidance.argtypes = [vp] * 5
         _lib = L
     return _lib
 
@@ -123,6 +128,8 @@ class ParticleEnv:
         self.resetter = None
         self.reward_scale = None
         self.shaping_phi, self.shaping_coef = None, None
+        self._guidance_out = None
+        self.set_guidance()   # the scripted pursuers' defaults
 
     def initialize(self, p_num, e_num):
         """particle_env.py:160-162, plus the allocation of the device records"""
@@ -235,6 +242,28 @@ class ParticleEnv:
             away = torch.atan2(torch.gather(dy, 2, imin[..., None])[..., 0], torch.gather(dx, 2, imin[..., None])[..., 0])
             cmd = torch.where(dmin <= self._kw["p_sen_range"], away, to_t) / math.pi
         self._cmd = torch.as_tensor(cmd, dtype=torch.float64, device=self.device).reshape(self.num_envs, self.e_num).contiguous()
+
+    # ---- scripted pursuers (guidance.py) --------------------------------------------------------------------------
+    def set_guidance(self, lead=1.0, sep_range=None, sep_gain=1.0):
+        """the parameters of guidance_actions (runtime.guidance_lead / guidance_sep_range / guidance_sep_gain): the longest look-ahead in
+        the environment's time units, the range inside which team-mates repel (None: 4 x kill_radius) and the weight of that repulsion"""
+        g = N2nGuidanceParams()
+        g.lead, g.sep_range, g.sep_gain = float(lead), float(4.0 * self.kill_radius if sep_range is None else sep_range), float(sep_gain)
+        self.guidance = g
+
+    def guidance_actions(self, out=None):
+        """the scripted lead-pursuit action of every pursuer for the current state, (N, P) int32, what step() takes
+        (n2n_pursuer_guidance, include/n2n_env.h; specification: tests/guidance_ref.py): one launch, nothing but `out` is written.
+        out: a dense device tensor of that shape and type (None: the environment's own, allocated once)."""
+        N, P = self.num_envs, self.p_num
+        if out is None:
+            if self._guidance_out is None:
+                self._guidance_out = torch.zeros((N, P), dtype=torch.int32, device=self.device)
+            out = self._guidance_out
+        assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (N, P) and out.device == self.p.device
+        _check(self.L.n2n_pursuer_guidance(C.byref(self.c), C.byref(self.st), C.byref(self.guidance), C.c_void_p(out.data_ptr()), _stream()),
+               "n2n_pursuer_guidance")
+        return out
 
     def step(self, action):
         """:164-177 (preceded by the evader's move with the command of evader_step) -> (reward (N,P), done (N,), active (N,P))"""

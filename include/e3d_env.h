@@ -128,6 +128,19 @@ int e3d_policy_record_shaped(const e3d_config *cfg, const e3d_state *st, const f
                              const e3d_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream);
 int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, double coef, void *stream);
 
+/* ---- scripted pursuers: a deterministic lead-pursuit law as a yardstick policy (csrc/guidance.hpp) ----
+ * lead: the longest look-ahead in the environment's time units; a team-mate closer than sep_range pushes with weight sep_gain.
+ * Each must be finite and >= 0 (E3D_ERR_BAD_CONFIG otherwise). */
+typedef struct e3d_guidance_params { double lead, sep_range, sep_gain; } e3d_guidance_params;
+/* actions [N][P][3] f64 in [-1, 1], what e3d_env_tick takes, from the current records.  Active pursuer i, active evader:
+ *   r = e_pos - p_i, d = sqrt(rx rx + ry ry + rz rz); e_vel = v_e (cos gamma_e cos phi_e, cos gamma_e sin phi_e, sin gamma_e);
+ *   t = min(d / p_vmax, lead); g = aim / |aim| with aim = r + t e_vel (0 when |aim| is 0); every active team-mate j != i with
+ *   0 < d_ij < sep_range adds sep_gain (p_i - p_j) / d_ij (sep_range - d_ij) / sep_range, in index order;
+ *   a0 = atan2(g_y, g_x) / pi, a1 = atan2(g_z, sqrt(g_x g_x + g_y g_y)) / (pi / 2), a2 = 1.
+ * g exactly 0, or the pursuer or the evader inactive: hold, a0 = phi_i / pi, a1 = gamma_i / (pi / 2), a2 = -1.
+ * One launch in the tick's lane layout, team-mates through shuffles, f64, no host synchronisation; the records are only read. */
+int e3d_pursuer_guidance(const e3d_config *cfg, const e3d_state *st, const e3d_guidance_params *params, double *actions, void *stream);
+
 /* The reference's evader: eva.e_f (eva.py:87-148) -- scipy's SLSQP (ftol 1e-6, <= 100 iterations, 2-point finite-difference
  * gradient) minimising obj_func (:212-240) over (heading, pitch, speed), started at the evader's state, bounded by the
  * environment's ang_lmt / v_lmt (:130-135) -- written as the command e_cmd [N][3] that e3d_env_tick consumes; zeros when the

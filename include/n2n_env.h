@@ -124,6 +124,21 @@ int n2n_policy_record_shaped(const n2n_config *cfg, const n2n_state *st, const f
                              const n2n_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream);
 int n2n_shaping_begin(const n2n_config *cfg, const n2n_state *st, double *phi, double coef, void *stream);
 
+/* ---- scripted pursuers: a deterministic lead-pursuit law as a yardstick policy (csrc/guidance.hpp) ----
+ * lead: the longest look-ahead in the environment's time units; a team-mate closer than sep_range pushes with weight sep_gain.
+ * Each must be finite and >= 0 (N2N_ERR_BAD_CONFIG otherwise). */
+typedef struct n2n_guidance_params { double lead, sep_range, sep_gain; } n2n_guidance_params;
+/* actions [N][P] int32 in 0..8, what n2n_env_tick takes (and head_sample writes), from the current records.  Active pursuer i against
+ * the nearest active evader (lowest index on ties):
+ *   r = e_pos - p_i, d = sqrt(rx rx + ry ry); e_vel = v_e (cos phi_e, sin phi_e); t = min(d / p_vmax, lead);
+ *   g = aim / |aim| with aim = r + t e_vel (0 when |aim| is 0); every active team-mate j != i with 0 < d_ij < sep_range adds
+ *   sep_gain (p_i - p_j) / d_ij (sep_range - d_ij) / sep_range, in index order; k = rint(atan2(g_y, g_x) / (pi / 4)) reduced to 1..8
+ *   (0 and -8 map to 8; the tick turns k pi / 4 > pi into its negative angle).
+ * g exactly 0, the pursuer inactive, or no evader active: action 0 (stop, keep the heading).
+ * One launch in the tick's lane layout, evaders and team-mates through shuffles, f64, no host synchronisation; the records are only
+ * read. */
+int n2n_pursuer_guidance(const n2n_config *cfg, const n2n_state *st, const n2n_guidance_params *params, int32_t *actions, void *stream);
+
 /* Host side of ParticleEnv.reset (:200-281) with a bit-exact replica of numpy's legacy RandomState per environment
  * (np.random.seed(seeds[n])).  Fills host arrays p [N][P][5], e [N][E][5], target [N][2]. */
 void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seeds);
