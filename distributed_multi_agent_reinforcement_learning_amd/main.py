@@ -35,6 +35,7 @@ from . import e3d_agent, n2n_agent
 from .e3d_agent import E3dTrainer, train_e3d
 from .guidance import BASELINES as SCRIPTED_BASELINES
 from .n2n_agent import N2nTrainer, train_n2n
+from .particle_agent import episode_triple
 from .trainer import train_agent_multiprocessing
 
 BASELINES = ("cfg1", "cfg2", "cfg3", "cfg4", "cfg5", "cfg4_n2n")
@@ -93,8 +94,7 @@ def baseline_guidance(cfg, env_kind, num_eval_envs):
     trainer.evaluate starts from); prints the keys of --evaluate as one JSON line.  No trainer, no model, no process group."""
     mod = e3d_agent if env_kind == "e3d" else n2n_agent
     env = mod.make_env(cfg, int(num_eval_envs), 0, "cuda", seed_offset=10 ** 6, training=False)
-    out = mod.guidance_episode(env)
-    ret, captured, length = (out["ret"], out["captured"] != 0, out["length"]) if isinstance(out, dict) else out
+    ret, captured, length = episode_triple(mod.guidance_episode(env))
     r, c, l = torch.stack((ret.mean(), captured.float().mean(), length.mean())).tolist()
     res = dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
     print(json.dumps(res), flush=True)

@@ -237,9 +237,9 @@ def save_resume_atomic(trainer, directory):
 
 
 class ParticleRunState:
-    """Run protocol of the env_3d / env_n2n trainers (E3dTrainer, N2nTrainer): resume bundle, evaluation record and best
-    checkpoint.  The trainer provides env, eval_env and make_eval_env(), agent (rollout state `agent._state(env)` with the sampling
-    counter; save_model / load_model), total_steps, iteration, num_envs, world, rank, device, eval_return_std, recorder and
+    """Run protocol of the env_3d / env_n2n trainers (particle_agent.ParticleTrainer): resume bundle, evaluation record and best
+    checkpoint.  The trainer provides env, eval_env and make_eval_env(), agent (a ParticleMAPPO: rollout state `agent._state(env)` with
+    the sampling counter; save_model / load_model), total_steps, iteration, num_envs, world, rank, device, eval_return_std, recorder and
     best_eval_return.  Every environment episode starts from a reset and every rollout from zero GRU states and history, so the
     reset generators, the sampling counters, the weights and Adam are all the state a run carries from one iteration to the next --
     and, with algo.use_reward_scaling, the training environment's reward_scale (the bundle's "reward_scaling" entry), with
@@ -256,16 +256,16 @@ class ParticleRunState:
                       eval_sample_counter=None if ev is None else agent._state(ev).counter.cpu(),
                       recorder=list(self.recorder), best_eval_return=self.best_eval_return,
                       num_envs=self.num_envs, world=self.world, rank=self.rank)
-        meta = agent.policy_meta() if hasattr(agent, "policy_meta") else None
+        meta = agent.policy_meta()
         if meta is not None:   # env_3d with a non-default algo.gauss_std / gauss_squash (E3dMAPPO.policy_meta); default bundles carry none
             bundle["policy"] = meta
-        if getattr(agent, "use_reward_scaling", False):   # algo.use_reward_scaling: n, mean, S (and R) of every environment; off: no entry
+        if agent.use_reward_scaling:   # algo.use_reward_scaling: n, mean, S (and R) of every environment; off: no entry
             bundle["reward_scaling"] = self.env.reward_scale.cpu()
-        if getattr(agent, "value_norm", None) is not None:   # algo.use_value_norm: beta and the state (m, q, d); off: no entry
+        if agent.value_norm is not None:   # algo.use_value_norm: beta and the state (m, q, d); off: no entry
             bundle["value_norm"] = agent.value_norm.entry()
-        if getattr(agent, "obs_norm", None) is not None:     # algo.use_obs_norm: the clip and the state (2, 33); off: no entry
+        if agent.obs_norm is not None:     # algo.use_obs_norm: the clip and the state (2, 33); off: no entry
             bundle["obs_norm"] = agent.obs_norm.entry()
-        if getattr(agent, "minibatch_steps", False):         # algo.minibatch_steps: "optimizer" is FusedAdam's state; off: no entry
+        if agent.minibatch_steps:         # algo.minibatch_steps: "optimizer" is FusedAdam's state; off: no entry
             bundle["minibatch_steps"] = True
         torch.save(bundle, path)
 
@@ -275,9 +275,8 @@ class ParticleRunState:
         if b["num_envs"] != self.num_envs or b["world"] != self.world or b["rank"] != self.rank:
             raise ValueError("resume bundle was written for another num_envs / world size / rank")
         agent = self.agent
-        if hasattr(agent, "check_policy_meta"):
-            agent.check_policy_meta(b.get("policy"), "resume bundle " + str(path))
-        theirs, mine = "reward_scaling" in b, bool(getattr(agent, "use_reward_scaling", False))
+        agent.check_policy_meta(b.get("policy"), "resume bundle " + str(path))
+        theirs, mine = "reward_scaling" in b, agent.use_reward_scaling
         if theirs != mine:
             raise ValueError(f"resume bundle {path} was written with algo.use_reward_scaling: {str(theirs).lower()}, "
                              f"this agent has algo.use_reward_scaling: {str(mine).lower()}")
@@ -289,7 +288,7 @@ class ParticleRunState:
         agent.ac_optimizer.load_state_dict(b["optimizer"])
         if agent.value_norm is not None:
             agent.value_norm.load_entry(b["value_norm"])
-        if getattr(agent, "obs_norm", None) is not None:
+        if agent.obs_norm is not None:
             agent.obs_norm.load_entry(b["obs_norm"])   # (zeroes the slots)
         self.total_steps, self.iteration = b["total_steps"], b["iteration"]
         if agent.use_lr_decay:
