@@ -122,6 +122,11 @@ class E3dMAPPO(ParticleMAPPO):
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
         self.action_dim = int(cfg.env.action_dim)
+        if self.imitation.on and self.action_dim != 3:
+            raise ValueError(f"algo.bc_iterations > 0 needs env.action_dim 3 (heading, pitch, speed: what the scripted pursuers command), "
+                             f"got {self.action_dim}")
+        # the heading residual is taken modulo 2 in clip mode only: a periodic quantity through tanh has no wrap-around residual
+        self.bc_wrap0 = self.imitation.heading_wrap and self.gauss_squash == "clip"
 
     def _build(self, cfg):
         a, sn = cfg.algo, bool(cfg.algo.use_spectral_norm)
@@ -181,10 +186,12 @@ class E3dMAPPO(ParticleMAPPO):
                    active=z(N, T, P), v_n=z(N, T + 1, P))
         if self.value_norm is not None:
             buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
+        if self.imitation.on:
+            buf["a_star"] = z(N, T, P, 3)   # the scripted pursuers' action of every row, in the policy's pre-squash space (algo.bc_iterations only)
         return buf
 
     @torch.no_grad()
-    def run_episode(self, env, buf=None, greedy=False, policy="network"):
+    def run_episode(self, env, buf=None, greedy=False, policy="network", follow=None):
         """N episodes in lockstep for T = env.max_step ticks.  Row (n, t, p) is live iff environment n was not done before step t and
         pursuer p was active at its start; rewards, values and the `active` mask of other rows are zero, so is v_n[n, t + 1, p] when
         pursuer p or episode n ended in step t for any reason but the time limit; v_n[:, T] is the critic's bootstrap value.  The masks
@@ -195,6 +202,8 @@ class E3dMAPPO(ParticleMAPPO):
         buffer every tick adds the sums of its live rows to obs_norm.slots (explore_env merges them).
         policy="guidance" (buf must be None): the tick takes the scripted pursuers' actions (guidance_episode below) instead of the
         network's; no network, sampler or sampling counter is touched, the accumulators and the returned triple are the same.
+        follow (explore_expert; needs a buffer): a (N,) uint8 mask -- every tick labels buf["a_star"][:, t] with the scripted pursuers'
+        actions and executes them in the environments whose mask is set (_expert_tick).
         Returns per-environment (return, captured, length) device tensors."""
         gd.check_policy(policy, buf)
         if policy == "guidance":
@@ -210,6 +219,8 @@ class E3dMAPPO(ParticleMAPPO):
         for t in range(env.max_step):
             self._features(env, st, accumulate=buf is not None)   # evaluation never accumulates
             self._policy_step(st, greedy)
+            if follow is not None:
+                self._expert_tick(env, st.env_action, buf, t, follow)
             env.evader_step()
             env.step(st.env_action)
             if buf is None:
@@ -250,6 +261,18 @@ class E3dMAPPO(ParticleMAPPO):
             return ops.ppo_loss_gauss_ex(mu, ls_raw, *tail, log_std_min=self.log_std_min, log_std_max=self.log_std_max,
                                          squash=self.gauss_squash, **dk)
         return ops.ppo_loss_gauss(mu, ls_raw, *tail, **dk)
+
+    BC_METRIC = "bc_action_mse"
+
+    def bc_metric(self, sq_sum, rows):
+        """the mean squared residual per action dimension over the live rows (after the heading wrap), from the launches' two sums"""
+        return sq_sum / (self.action_dim * rows) if rows else float("nan")
+
+    def _imitation_loss(self, buf, n0, n1, v_target, sums):
+        mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True)
+        lo, hi = (self.log_std_min, self.log_std_max) if self.policy_ex else (-float("inf"), float("inf"))
+        return ops.bc_loss_gauss(mu, ls_raw, buf["a_star"][n0:n1], *self._imitation_tail(buf, n0, n1, values, v_target), log_std_min=lo,
+                                 log_std_max=hi, fit_std=self.imitation.fit_std, wrap0=self.bc_wrap0, sums=sums)
 
     def policy_meta(self):
         """the "policy" entry of checkpoints and resume bundles: None in the default mode (param, clip), whose files carry none"""

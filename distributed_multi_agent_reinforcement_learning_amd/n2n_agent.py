@@ -120,10 +120,12 @@ class N2nMAPPO(ParticleMAPPO):
                    a_n=z(N, T, P), a_logprob_n=z(N, T, P), r=z(N, T, P), active=z(N, T, P), v_n=z(N, T + 1, P))
         if self.value_norm is not None:
             buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
+        if self.imitation.on:
+            buf["a_star"] = z(N, T, P)   # the scripted pursuers' action of every row (algo.bc_iterations only)
         return buf
 
     @torch.no_grad()
-    def run_episode(self, env, buf=None, greedy=False, policy="network"):
+    def run_episode(self, env, buf=None, greedy=False, policy="network", follow=None):
         """N episodes in lockstep for T = env.episode_limit ticks.  Per tick: policy_inputs, the policy step, the SLSQP evader, the tick,
         policy_record, and (with a buffer) one rollout_record launch.  Row (n, t, p) is live iff pursuer p was active at the start of step t
         and environment n was not done before it; r, v_n and `active` of other rows are zero, so is v_n[n, t + 1, p] when pursuer p or
@@ -133,6 +135,8 @@ class N2nMAPPO(ParticleMAPPO):
         gamma Phi' - Phi (env.shaping_phi, written by shaping_begin after the reset).
         policy="guidance" (buf must be None): the tick takes the scripted pursuers' actions (guidance_episode below) instead of the
         network's; no network, sampler or sampling counter is touched, the accumulators are the same.
+        follow (explore_expert; needs a buffer): a (N,) uint8 mask -- every tick labels buf["a_star"][:, t] with the scripted pursuers'
+        actions and executes them in the environments whose mask is set (_expert_tick); buf["a_n"] then holds the executed action.
         Returns the per-environment accumulators (done_before, ended, captured, ret, length)."""
         gd.check_policy(policy, buf)
         if policy == "guidance":
@@ -146,6 +150,8 @@ class N2nMAPPO(ParticleMAPPO):
         for t in range(env.episode_limit):
             env.policy_inputs(st.p4, st.e4, st.e_ref, st.live, st.pp, st.pe, acc["done_before"])
             self._policy_step(st, greedy)
+            if follow is not None:
+                self._expert_tick(env, st.a_n, buf, t, follow)
             env.evader_step()
             env.step(st.a_n)
             if buf is None:
@@ -189,6 +195,16 @@ class N2nMAPPO(ParticleMAPPO):
     def _minibatch_loss(self, buf, n0, n1, adv, v_target, dk):
         prob, values = self.sequence_forward(buf, n0, n1)
         return ops.ppo_loss_prob(prob, *self._loss_tail(buf, n0, n1, values, adv, v_target), **dk)
+
+    BC_METRIC = "bc_accuracy"
+
+    def bc_metric(self, hits, rows):
+        """the share of live rows whose most probable action is the label, from the launches' two sums"""
+        return hits / rows if rows else float("nan")
+
+    def _imitation_loss(self, buf, n0, n1, v_target, sums):
+        prob, values = self.sequence_forward(buf, n0, n1)
+        return ops.bc_loss_cat(prob, buf["a_star"][n0:n1], *self._imitation_tail(buf, n0, n1, values, v_target), sums=sums)
 
     def save_model(self, cwd, best=False):
         """cwd/n2n_actor.pth and n2n_critic.pth (best: n2n_actor_best.pth, n2n_critic_best.pth), the two state_dicts; with

@@ -20,7 +20,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "ppo_loss_gauss_ex_workspace", "gae_advnorm_vn", "gae_advnorm_vn_workspace", "value_norm_update", "value_norm_targets",
            "ppo_loss_fwd_bwd_diag", "ppo_loss_prob_fwd_bwd_diag", "ppo_loss_gauss_fwd_bwd_diag", "ppo_loss_gauss_ex_fwd_bwd_diag",
            "ppo_loss_diag_workspace", "ppo_loss_gauss_diag_workspace", "ppo_ratio", "ppo_diag_rows_host", "fused_adam_workspace",
-           "fused_adam_grid", "fused_adam_norm", "fused_adam_step", "fused_adam_advance_host", "fused_adam_rows_host", "mappo_ops_error_string")
+           "fused_adam_grid", "fused_adam_norm", "fused_adam_step", "fused_adam_advance_host", "fused_adam_rows_host", "bc_loss_workspace",
+           "bc_loss_gauss_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "mappo_ops_error_string")
 
 _lib = None
 
@@ -124,6 +125,12 @@ def load_library():
         L.fused_adam_step.argtypes = [i64, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp]
         L.fused_adam_advance_host.argtypes = [vp, f64, f64, f64, f64]
         L.fused_adam_rows_host.argtypes = [i64, vp, vp, vp, vp, vp, f64, f64, f64, f64]
+        L.bc_loss_workspace.restype = i64
+        L.bc_loss_gauss_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, f32, f32, i32, i32, vp, vp, vp, i64, i64,
+                                            i64, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
+        L.bc_loss_cat_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
+        L.e3d_bc_select.argtypes = [i32, i32, vp, vp, i32, f64, vp, vp, i64, vp]
+        L.n2n_bc_select.argtypes = [i32, i32, vp, vp, vp, vp, i64, vp]
         L.sb_split_diag.argtypes = [i64, vp, vp, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
@@ -1508,6 +1515,138 @@ def ppo_loss_gauss_ex(mu, ls_raw, action, values_now, logp_old, adv, active, val
     values_now.  diag: see ppo_loss."""
     return _PPOLossGaussEx.apply(mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef,
                                  use_value_clip, log_std_min, log_std_max, squash, diag)
+
+
+BC_SUMS = 2   # csrc/imitation.hpp: the call's extra sum (sum of squared residuals / label hits over live rows) and its live-row count
+
+
+def _bc_sums_ok(sums, dev):
+    assert sums is None or (sums.dtype == torch.float64 and sums.shape == (BC_SUMS,) and sums.is_contiguous() and sums.device == dev)
+
+
+class _BCLossGauss(torch.autograd.Function):
+    """bc_loss_gauss: bc_loss_gauss_fwd_bwd writes the losses and the gradients w.r.t. mu, ls_raw (per row or the vector) and the
+    values in one pass."""
+
+    @staticmethod
+    def forward(ctx, mu, ls_raw, values_now, target, active, values_old, v_target, epsilon, use_value_clip, log_std_min, log_std_max, fit_std,
+                wrap0, sums=None):
+        L = load_library()
+        _need_gpu(mu, "bc_loss_gauss")
+        A = mu.shape[-1]
+        d0, d1, d2 = mu.shape[:3]
+        n = d0 * d1 * d2
+        ts = [t.contiguous() for t in (active, v_target)]
+        tgt = target.contiguous()
+        vo = values_old.contiguous() if values_old is not None else None
+        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == mu.shape[:3]
+        assert tgt.shape == mu.shape and tgt.dtype == torch.float32 and mu.stride(3) == 1
+        dev = mu.device
+        _bc_sums_ok(sums, dev)
+        ls = ls_raw.detach()
+        if ls.dim() == 1:            # param mode: one vector, stride 0 over the rows
+            assert ls.shape == (A,)
+            ls = ls.contiguous()
+            g_ls = torch.empty(A, dtype=torch.float32, device=dev)
+            lstr = (0, 0, 0)
+        else:                        # state mode: per row, any strides over the first three dimensions (a time-major view)
+            assert ls.shape == mu.shape and ls.stride(3) == 1 and ls.dtype == torch.float32
+            g_ls = torch.empty_strided(ls.shape, ls.stride(), dtype=torch.float32, device=dev)
+            lstr = ls.stride()[:3]
+            assert any(lstr), "a per-row ls_raw needs a nonzero row stride"
+        asum = active.sum().reshape(1)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)
+        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.bc_loss_workspace(), dtype=torch.uint8, device=dev)
+        ms, vs = mu.stride(), values_now.stride()
+        _check(L.bc_loss_gauss_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
+                                       float(log_std_min), float(log_std_max), int(bool(fit_std)), int(bool(wrap0)), _ptr(tgt), _ptr(ts[0]),
+                                       _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[1]), _ptr(asum), float(epsilon),
+                                       int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(ws), _stream()),
+               "bc_loss_gauss_fwd_bwd")
+        ctx.save_for_backward(g_mu, g_ls, g_v)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, ga, gc):
+        g_mu, g_ls, g_v = ctx.saved_tensors
+        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 11
+
+
+def bc_loss_gauss(mu, ls_raw, target, values_now, active, values_old, v_target, epsilon, use_value_clip=True, log_std_min=-float("inf"),
+                  log_std_max=float("inf"), fit_std=False, wrap0=False, sums=None):
+    """-> (actor_loss, critic_loss) of the imitation phase on env_3d (algo.bc_iterations; csrc/imitation.hpp k_bc_loss_gauss): the masked
+    mean of sum_a 0.5 d^2 exp(-2 ls) + (fit_std ? ls : 0) with d = target - mu (wrap0: dimension 0 modulo 2 into [-1, 1)) and
+    ls = clamp(ls_raw, log_std_min, log_std_max), and ppo_loss_gauss's critic loss with the same bits.  Shapes and views as
+    ppo_loss_gauss_ex; gradients flow to mu, ls_raw (exactly 0 without fit_std) and values_now.  sums: None, or a (2,) f64 device tensor to
+    which the call adds sum_rows active sum_a d^2 and sum active."""
+    return _BCLossGauss.apply(mu, ls_raw, values_now, target, active, values_old, v_target, epsilon, use_value_clip, log_std_min, log_std_max,
+                              fit_std, wrap0, sums)
+
+
+class _BCLossCat(torch.autograd.Function):
+    """bc_loss_cat: bc_loss_cat_fwd_bwd writes the losses and the gradients w.r.t. prob and the values in one pass."""
+
+    @staticmethod
+    def forward(ctx, prob, values_now, label, active, values_old, v_target, epsilon, use_value_clip, sums=None):
+        L = load_library()
+        _need_gpu(prob, "bc_loss_cat")
+        A = prob.shape[-1]
+        d0, d1, d2 = prob.shape[:3]
+        n = d0 * d1 * d2
+        ts = [t.contiguous() for t in (label, active, v_target)]
+        vo = values_old.contiguous() if values_old is not None else None
+        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == prob.shape[:3]
+        assert prob.stride(3) == 1 and prob.dtype == torch.float32 and 1 <= A <= 16
+        dev = prob.device
+        _bc_sums_ok(sums, dev)
+        asum = active.sum().reshape(1)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        g_prob = torch.empty_strided(prob.shape, prob.stride(), dtype=torch.float32, device=dev)    # the layout of prob (a time-major view)
+        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.bc_loss_workspace(), dtype=torch.uint8, device=dev)
+        ps, vs = prob.stride(), values_now.stride()
+        _check(L.bc_loss_cat_fwd_bwd(n, A, _ptr(prob), _ptr(g_prob), d1, d2, ps[0], ps[1], ps[2], _ptr(ts[0]), _ptr(ts[1]), _ptr(values_now),
+                                     vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[2]), _ptr(asum), float(epsilon), int(bool(use_value_clip)),
+                                     _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(ws), _stream()), "bc_loss_cat_fwd_bwd")
+        ctx.save_for_backward(g_prob, g_v)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, ga, gc):
+        g_prob, g_v = ctx.saved_tensors
+        return (g_prob * ga, g_v * gc) + (None,) * 7
+
+
+def bc_loss_cat(prob, label, values_now, active, values_old, v_target, epsilon, use_value_clip=True, sums=None):
+    """-> (actor_loss, critic_loss) of the imitation phase on env_n2n (algo.bc_iterations; csrc/imitation.hpp k_bc_loss_cat): the masked
+    mean of -Categorical(prob).log_prob(label), formed exactly as ppo_loss_prob forms its log-probability, and ppo_loss_prob's critic loss
+    with the same bits.  prob (mb, T, P, A <= 16), values_now (mb, T, P): any strides over the first three dimensions; label (mb, T, P)
+    as floats.  sums: None, or a (2,) f64 device tensor to which the call adds the number of live rows whose argmax (lowest index on
+    ties) is the label, and sum active."""
+    return _BCLossCat.apply(prob, values_now, label, active, values_old, v_target, epsilon, use_value_clip, sums)
+
+
+def bc_select(guide, follow, action, a_star_row, squash="clip", bound=0.999):
+    """one tick of an imitation rollout (csrc/imitation.hpp k_e3d_bc_select / k_n2n_bc_select): the scripted pursuers' actions `guide`
+    ((N, P, 3) f64 on env_3d, (N, P) int32 on env_n2n) become the labels in a_star_row (buffer["a_star"][:, t]: fp32, row-strided; with
+    squash "tanh" atanh of the action clamped to +-bound) and replace `action` (the network's, st.env_action / st.a_n, in place) in the
+    environments whose `follow` (N,) uint8 is set.  One launch on the current stream, no host synchronisation."""
+    L = load_library()
+    _need_gpu(guide, "bc_select")
+    N, P = guide.shape[:2]
+    assert follow.dtype == torch.uint8 and follow.shape == (N,) and follow.is_contiguous() and follow.device == guide.device
+    assert guide.is_contiguous() and action.is_contiguous() and action.shape == guide.shape and action.dtype == guide.dtype
+    assert a_star_row.dtype == torch.float32 and a_star_row.shape == guide.shape and (N == 1 or a_star_row[0].is_contiguous())
+    stride = a_star_row.stride(0) if N > 1 else a_star_row[0].numel()
+    if guide.dtype == torch.float64:
+        assert guide.dim() == 3 and guide.shape[2] == 3 and squash in GAUSS_SQUASH
+        _check(L.e3d_bc_select(N, P, _ptr(guide), _ptr(follow), GAUSS_SQUASH[squash], float(bound), _ptr(action), _ptr(a_star_row), stride,
+                               _stream()), "e3d_bc_select")
+    else:
+        assert guide.dim() == 2 and guide.dtype == torch.int32
+        _check(L.n2n_bc_select(N, P, _ptr(guide), _ptr(follow), _ptr(action), _ptr(a_star_row), stride, _stream()), "n2n_bc_select")
 
 
 def ppo_loss(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True, diag=None):

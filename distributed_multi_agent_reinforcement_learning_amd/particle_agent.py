@@ -8,6 +8,7 @@ import time
 import torch
 
 from . import guidance as gd
+from . import imitation as im
 from . import ops
 from . import value_norm as vnorm
 from .minibatch_steps import MAX_GRAD_NORM, minibatch_steps_options
@@ -38,10 +39,19 @@ def finish_env(env, cfg, training):
     return env
 
 
+class BcSums:
+    """the device side of the imitation metric: the two sums the bc loss launches of one train(imitation=True) call add to"""
+
+    def __init__(self, device):
+        self.sums = torch.zeros(ops.BC_SUMS, dtype=torch.float64, device=device)
+        self.allreduce = None      # the trainer's allreduce_sum_: the two sums over ranks, in place
+
+
 class ParticleMAPPO:
     """rollout bookkeeping (explore_env) and PPO update (train) of a policy on a particle environment.  A subclass names its
     environment (ENV) and provides _options (its own keys, before the device check), _build (actor, critic, ac_parameters), _rollout
-    (the storage of _state), _buffer_dims, new_buffer, run_episode, _bootstrap_value and _minibatch_loss."""
+    (the storage of _state), _buffer_dims, new_buffer, run_episode, _bootstrap_value, _minibatch_loss, and for algo.bc_iterations
+    _imitation_loss, BC_METRIC and bc_metric."""
 
     ENV = None        # "env_3d (runtime.env: e3d)": how the messages name the environment
     obs_norm = None   # algo.use_obs_norm (env_3d only): the agent's ObsNorm
@@ -56,6 +66,7 @@ class ParticleMAPPO:
         self.update_diagnostics, self.target_kl = update_diag_options(cfg)   # what the update did, from the loss launches
         self.minibatch_steps = minibatch_steps_options(cfg)   # one clip + Adam step per mini-batch, fused
         self.guidance = gd.guidance_options(cfg)   # the scripted pursuers of run_episode(policy="guidance")
+        self.imitation = im.imitation_options(cfg)   # algo.bc_iterations: the imitation warm start in front of PPO
         self._options(cfg)
         self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
@@ -75,6 +86,8 @@ class ParticleMAPPO:
             self.ac_optimizer = torch.optim.Adam(self.ac_parameters, lr=self.lr, eps=1e-5)
         self.value_norm = vnorm.ValueNorm(self.value_norm_beta, self.device) if self.use_value_norm else None
         self.diag = UpdateDiag(self.device) if self.update_diagnostics else None
+        self.bc = BcSums(self.device) if self.imitation.on else None
+        self.last_bc = None   # algo.bc_iterations: (the extra sum, the live rows) of the last train(imitation=True) call, over ranks
         self.last_update_diag = None   # algo.update_diagnostics: the dict of the last train() call
         rt = cfg.get("runtime", {})
         self.sample_seed = int(rt.get("seed", 0))
@@ -116,16 +129,32 @@ class ParticleMAPPO:
         if self.value_norm is not None:   # the denormalisation of v_n[:, T] needs the mask itself: 0 std + mean is not 0
             buf["v_mask"].copy_(vmask)
 
-    def explore_env(self, env):
-        """one episode per environment into the buffer (a fresh one when the sizes changed) -> (mean return, buffer, env-steps, stats)"""
+    def explore_env(self, env, follow=None):
+        """one episode per environment into the buffer (a fresh one when the sizes changed) -> (mean return, buffer, env-steps, stats);
+        follow: explore_expert's mask"""
         dims = self._buffer_dims(env)   # (N, T, P, ...): the arguments of new_buffer
         if self.buffer is None or self._buffer_for != dims:
             self.buffer, self._buffer_for = self.new_buffer(*dims), dims
-        ret, captured, length = episode_triple(self.run_episode(env, self.buffer))
+        kw = {} if follow is None else {"follow": follow}
+        ret, captured, length = episode_triple(self.run_episode(env, self.buffer, **kw))
         if self.obs_norm is not None:   # one merge per rollout: the statistics the next rollout is normalised under
             self.obs_norm.commit()
         mean_r, cap, mlen = torch.stack((ret.mean(), captured.float().mean(), length.mean())).tolist()
         return mean_r, self.buffer, dims[0] * dims[1], dict(capture_rate=cap, episode_length=mlen)
+
+    def explore_expert(self, env, beta):
+        """explore_env with the teacher in the loop (algo.bc_iterations): every tick also takes env.guidance_actions() and one
+        ops.bc_select launch before the environment steps -- the scripted pursuers' actions become the labels buffer["a_star"][:, t] of
+        every environment and the executed actions of environments 0 .. round(beta N) - 1; everything else is run_episode's"""
+        if not self.imitation.on:
+            raise ValueError(f"explore_expert needs {im.KEY} > 0 (the buffer has no a_star field otherwise)")
+        follow = torch.zeros(env.num_envs, dtype=torch.uint8, device=self.device)
+        follow[:im.follow_count(beta, env.num_envs)] = 1
+        return self.explore_env(env, follow)
+
+    def _expert_tick(self, env, action, buf, t, follow):
+        """the hook of explore_expert inside run_episode's loop, after the policy step and before env.step"""
+        ops.bc_select(env.guidance_actions(), follow, action, buf["a_star"][:, t], getattr(self, "gauss_squash", "clip"), self.imitation.target_bound)
 
     # ---- update ------------------------------------------------------------------------------------------------------------------
     def _loss_tail(self, buf, n0, n1, values, adv, v_target):
@@ -133,11 +162,19 @@ class ParticleMAPPO:
         return (buf["a_n"][n0:n1], values, buf["a_logprob_n"][n0:n1], adv[n0:n1], buf["active"][n0:n1],
                 buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1], self.epsilon, self.entropy_coef, self.use_value_clip)
 
-    def train(self, buf, total_steps):
+    def _imitation_tail(self, buf, n0, n1, values, v_target):
+        """the arguments both imitation loss launches take after the policy's own outputs and the labels, for episodes [n0, n1)"""
+        return (values, buf["active"][n0:n1], buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1], self.epsilon,
+                self.use_value_clip)
+
+    def train(self, buf, total_steps, imitation=False):
         """GAE + advantage normalisation over all rows (ops.gae_advnorm), then sequential mini-batches of whole episodes (forward and
         loss: the subclass's _minibatch_loss), the gradient clipped to MAX_GRAD_NORM after each (as MAPPO.train).  With
         algo.minibatch_steps every mini-batch instead starts from a zeroed bucket and ends with the gradient SUM over ranks and one
         fused clip + Adam step (FusedAdam.step), and last_optimizer_steps / last_skipped_steps count them.
+        imitation (algo.bc_iterations): the mini-batch loss is the subclass's _imitation_loss on buf["a_star"]; the update diagnostics,
+        the KL target and the learning-rate decay are skipped, everything else is unchanged; the two sums of the imitation metric go
+        over ranks and arrive in the call's one host read (last_bc).
         Returns (critic loss, actor loss) averaged over the mini-batches."""
         N = buf["r"].shape[0]
         with torch.no_grad():
@@ -152,7 +189,9 @@ class ParticleMAPPO:
         opt = self.ac_optimizer if self.minibatch_steps else None   # FusedAdam: zero, backward, reduce and step per mini-batch
         obj_c = obj_a = 0.0
         k = 0
-        diag = self.diag   # algo.update_diagnostics: every loss call adds its eight sums (None: the plain calls)
+        diag = None if imitation else self.diag   # algo.update_diagnostics: every loss call adds its eight sums (None: the plain calls)
+        if imitation:
+            self.bc.sums.zero_()
         if diag is not None:
             diag.begin()
         dk = {} if diag is None else {"diag": diag.sums}
@@ -160,7 +199,10 @@ class ParticleMAPPO:
             n1 = min(n0 + self.mini_batch_size, N)
             if opt is not None and n0:
                 self.grad_bucket.zero()
-            la, lc = self._minibatch_loss(buf, n0, n1, adv, v_target, dk)
+            if imitation:
+                la, lc = self._imitation_loss(buf, n0, n1, v_target, self.bc.sums)
+            else:
+                la, lc = self._minibatch_loss(buf, n0, n1, adv, v_target, dk)
             (la + lc).backward()
             if opt is not None:   # the clip acts on the gradient summed over ranks: the same coefficient and weights everywhere
                 allreduce_sum_(self.grad_bucket.flat)
@@ -174,10 +216,16 @@ class ParticleMAPPO:
             obj_c = obj_c + lc.detach().double()
             obj_a = obj_a + la.detach().double()
             k += 1
-        if self.use_lr_decay:
+        if self.use_lr_decay and not imitation:
             self.lr_decay(total_steps)
         extra = () if opt is None else (opt.skipped,)   # the count of skipped steps rides in the read the call has anyway
-        if diag is not None:   # one read for the two losses, the eight sums (all-reduced over ranks) and the gradient norm
+        if imitation:   # one read for the two losses, the skipped count and the two sums (all-reduced over ranks)
+            if self.bc.allreduce is not None:
+                self.bc.allreduce(self.bc.sums)
+            *head, s, c = torch.cat((torch.stack((obj_c, obj_a, *(e.double() for e in extra))), self.bc.sums)).tolist()
+            obj_c, obj_a, *extra = head
+            self.last_bc = (s, c)
+        elif diag is not None:   # one read for the two losses, the eight sums (all-reduced over ranks) and the gradient norm
             (obj_c, obj_a, *extra), self.last_update_diag = diag.read(obj_c, obj_a, *extra)
         elif opt is not None:
             obj_c, obj_a, *extra = torch.stack((obj_c, obj_a, *extra)).tolist()
@@ -185,6 +233,25 @@ class ParticleMAPPO:
             self.last_optimizer_steps, self.last_skipped_steps = k, int(extra[0] - opt.skipped_seen)
             opt.skipped_seen = extra[0]
         return float(obj_c) / k, float(obj_a) / k
+
+    def set_lr(self, lr):
+        for p in self.ac_optimizer.param_groups:
+            p["lr"] = lr
+
+    def reset_optimizer(self, total_steps):
+        """the step from the imitation phase to PPO: Adam's moments and step count back to zero (the moments of a supervised loss say
+        nothing about the PPO gradient) and the learning rate back on the schedule"""
+        opt = self.ac_optimizer
+        if isinstance(opt, FusedAdam):
+            opt.reset_moments()
+        else:
+            for st in opt.state.values():
+                for key in ("step", "exp_avg", "exp_avg_sq"):
+                    st[key].zero_()
+        if self.use_lr_decay:
+            self.lr_decay(total_steps)
+        else:
+            self.set_lr(self.lr)
 
     def lr_decay(self, total_steps):
         lr_now = self.lr * (1 - total_steps / self.max_train_steps)
@@ -214,9 +281,9 @@ class ParticleTrainer(ParticleRunState):
         self.agent.sample_rank = self.rank
         self.bucket = self.agent.grad_bucket or GradBucket(self.agent.ac_parameters)   # (algo.minibatch_steps: the agent's own)
         self.agent.grad_bucket = self.bucket
-        for part in (self.agent.value_norm, self.agent.obs_norm, self.agent.diag):
-            if part is not None:   # (S1, S2, c) / the (2, 33) feature sums of a rollout / the eight diagnostic sums over ranks;
-                part.allreduce = allreduce_sum_   # without a process group a no-op
+        for part in (self.agent.value_norm, self.agent.obs_norm, self.agent.diag, self.agent.bc):
+            if part is not None:   # (S1, S2, c) / the (2, 33) feature sums of a rollout / the eight diagnostic sums / the two imitation
+                part.allreduce = allreduce_sum_   # sums over ranks; without a process group a no-op
         self.last_epoch_diags = []
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
@@ -230,18 +297,28 @@ class ParticleTrainer(ParticleRunState):
     def iterate(self):
         """-> (env-steps of this iteration over all ranks, log record)"""
         cfg, agent = self.cfg, self.agent
+        bc = agent.imitation
+        imitating = self.iteration < bc.iterations   # algo.bc_iterations: the leading iterations imitate the scripted pursuers (DESIGN 7f)
+        if imitating:
+            agent.set_lr(bc.lr)   # constant over the phase
+        elif bc.on and self.iteration == bc.iterations:
+            agent.reset_optimizer(self.total_steps)   # the first PPO iteration starts from fresh moments, on the schedule
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
-        mean_r, buf, steps, stats = agent.explore_env(self.env)
+        if imitating:
+            beta = bc.beta_at(self.iteration)
+            mean_r, buf, steps, stats = agent.explore_expert(self.env, beta)
+        else:
+            mean_r, buf, steps, stats = agent.explore_env(self.env)
         ev[1].record()
         self.total_steps += steps * self.world
         self.last_epoch_diags, epochs_run = [], 0
         per_minibatch, opt_steps, skipped = agent.minibatch_steps, 0, 0
         for _ in range(int(cfg.algo.epochs)):
             with torch.enable_grad():
-                obj_c, obj_a = agent.train(buf, self.total_steps)
+                obj_c, obj_a = agent.train(buf, self.total_steps, **({"imitation": True} if imitating else {}))
             over = False
-            if agent.diag is not None:
+            if agent.diag is not None and not imitating:
                 self.last_epoch_diags.append(agent.last_update_diag)
                 # algo.target_kl: the policy has moved past the target on this buffer -- the remaining epochs are skipped; the sums are
                 # all-reduced, so every rank stops here.  Stepping once per epoch, this epoch's gradient is discarded as well (the next
@@ -263,7 +340,9 @@ class ParticleTrainer(ParticleRunState):
         self.last_events = ev
         log = dict(iteration=self.iteration, total_steps=self.total_steps, mean_return=mean_r, capture_rate=stats["capture_rate"],
                    episode_length=stats["episode_length"], critic_loss=obj_c, actor_loss=obj_a)
-        if agent.diag is not None:   # of the last train() call, like the two losses
+        if imitating:   # the metric of the last train() call, like the two losses
+            log.update(phase="imitation", bc_beta=beta, bc_loss=obj_a, **{agent.BC_METRIC: agent.bc_metric(*agent.last_bc)})
+        elif agent.diag is not None:   # of the last train() call, like the two losses
             log.update({k: agent.last_update_diag[k] for k in LOG_KEYS}, epochs_run=epochs_run)
         if per_minibatch:
             log.update(optimizer_steps=opt_steps, skipped_steps=skipped)

@@ -17,6 +17,7 @@ import torch.distributed as dist
 from . import ops
 from .evaluator import EvaluatorProc, draw_learning_curve
 from .mappo import MAPPO
+from .imitation import check_entry as check_imitation_entry
 from .minibatch_steps import check_entry as check_minibatch_steps_entry
 from .pursuit_env import Pursuit_Env
 from .obs_norm import check_entry as check_obs_norm_entry
@@ -179,6 +180,14 @@ class FusedAdam:
         ops.fused_adam(self.bucket.flat, grad_flat, self.m, self.v, self.state, self.workspace, self.param_groups[0]["lr"], self.betas[0],
                        self.betas[1], self.eps, max_norm)
 
+    def reset_moments(self):
+        """m, v and the step count (with the two beta powers) as before the first step; the norm, the coefficient and the count of
+        skipped steps stay"""
+        self.m.zero_()
+        self.v.zero_()
+        self.state[0].zero_()
+        self.state[1:3].fill_(1.0)
+
     def state_dict(self):
         return dict(kind=self.KIND, state=self.state.cpu(), m=self.m.cpu(), v=self.v.cpu())
 
@@ -245,7 +254,8 @@ class ParticleRunState:
     and, with algo.use_reward_scaling, the training environment's reward_scale (the bundle's "reward_scaling" entry), with
     algo.use_value_norm the agent's value-normaliser state (the "value_norm" entry), with algo.use_obs_norm (env_3d) the agent's
     feature-normaliser state (the "obs_norm" entry; its slots are empty between iterations and are not saved).  With
-    algo.minibatch_steps the bundle says so ("minibatch_steps": True) and its "optimizer" is FusedAdam's state."""
+    algo.minibatch_steps the bundle says so ("minibatch_steps": True) and its "optimizer" is FusedAdam's state.  With algo.bc_iterations
+    > 0 the bundle records it ("bc_iterations"): the phase of the next iteration follows from it and the saved iteration count."""
 
     def save_resume(self, path):
         agent, ev = self.agent, self.eval_env
@@ -267,6 +277,8 @@ class ParticleRunState:
             bundle["obs_norm"] = agent.obs_norm.entry()
         if agent.minibatch_steps:         # algo.minibatch_steps: "optimizer" is FusedAdam's state; off: no entry
             bundle["minibatch_steps"] = True
+        if agent.imitation.on:            # algo.bc_iterations: the phase of an iteration follows from it and `iteration`; off: no entry
+            bundle["bc_iterations"] = agent.imitation.iterations
         torch.save(bundle, path)
 
     def load_resume(self, path):
@@ -283,6 +295,7 @@ class ParticleRunState:
         check_value_norm_entry(agent, b.get("value_norm"), f"resume bundle {path}")
         check_obs_norm_entry(agent, b.get("obs_norm"), f"resume bundle {path}")
         check_minibatch_steps_entry(agent, b.get("minibatch_steps"), f"resume bundle {path}")
+        check_imitation_entry(agent, b.get("bc_iterations"), f"resume bundle {path}")
         agent.actor.load_state_dict(b["actor"])
         agent.critic.load_state_dict(b["critic"])
         agent.ac_optimizer.load_state_dict(b["optimizer"])

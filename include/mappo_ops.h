@@ -426,6 +426,37 @@ int ppo_diag_rows_host(int64_t n, const float *lr, const float *ratio, const flo
                        const float *active, float eps, double *terms);
 
 /*
+ * Imitation warm start of the env_3d / env_n2n trainers (algo.bc_iterations; csrc/imitation.hpp; specification: tests/imitation_ref.py).
+ * bc_loss_gauss_fwd_bwd: the Gaussian negative log-likelihood of the teacher's action `target` [n][A] under mu and
+ * ls = clamp(ls_raw, log_std_min, log_std_max), with the views and the ls_raw modes of ppo_loss_gauss_ex_fwd_bwd:
+ *   d = target - mu (wrap0 != 0: dimension 0 taken modulo 2 into [-1, 1)), la = sum_a 0.5 d^2 exp(-2 ls) + (fit_std ? ls : 0),
+ *   losses[0] = sum_i active la / sum active; grad_mu = -(active / sum active) d exp(-2 ls); grad_log_std (per row in state mode, [A] in
+ *   param mode) = (active / sum active)(1 - d^2 exp(-2 ls)) on the closed range of the bounds with fit_std, exactly 0 otherwise.
+ * bc_loss_cat_fwd_bwd: the cross-entropy -log clamp(p[label], eps32, 1 - eps32) of the renormalised row, exactly as
+ * ppo_loss_prob_fwd_bwd forms its log-probability, with its gradient through the clamp and the normalisation; label [n] as floats.
+ * Both: losses[1], grad_values are the critic part of the PPO calls with the same bits; sums (NULL: skipped) [2] f64, to which the call
+ * ADDS sum_i active sum_a d^2 (gauss) or the number of live rows whose argmax (lowest index on ties) is the label (cat), and sum active.
+ * workspace >= bc_loss_workspace() bytes.  Deterministic (f64 per-block partials added in a fixed order, no atomics).
+ * e3d_bc_select / n2n_bc_select: one launch per rollout tick.  guide: the scripted pursuers' actions ([N][P][3] f64 / [N][P] int32);
+ * the label of every row goes to a_star + n * row_stride (floats) + the row's offset -- (float)g, or with squash == 1
+ * (float)atanh(clamp(g, -bound, bound)) evaluated in f64, or (float)k -- and the guide's action replaces the network's
+ * (env_action / a_n) in the environments with follow[n] != 0.  Nothing else is written.
+ */
+int64_t bc_loss_workspace(void);
+int bc_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
+                          const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min, float log_std_max,
+                          int32_t fit_std, int32_t wrap0, const float *target, const float *active, const float *values_now, int64_t v_s0,
+                          int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
+                          int32_t use_value_clip, float *losses, float *grad_values, double *sums, void *workspace, void *stream);
+int bc_loss_cat_fwd_bwd(int64_t n, int32_t A, const float *prob, float *grad_prob, int64_t d1, int64_t d2, int64_t p_s0, int64_t p_s1, int64_t p_s2,
+                        const float *label, const float *active, const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2,
+                        const float *values_old, const float *v_target, const float *active_sum, float epsilon, int32_t use_value_clip,
+                        float *losses, float *grad_values, double *sums, void *workspace, void *stream);
+int e3d_bc_select(int32_t N, int32_t P, const double *guide, const uint8_t *follow, int32_t squash, double bound, double *env_action, float *a_star,
+                  int64_t row_stride, void *stream);
+int n2n_bc_select(int32_t N, int32_t P, const int32_t *guide, const uint8_t *follow, int32_t *a_n, float *a_star, int64_t row_stride, void *stream);
+
+/*
  * Records one rollout tick into the replay buffer (MAPPO.run_episode's minibuffer.store_transition,
  * DHGN/mappo_parallel.py:783-805, for N environments at once): for every item, row n of the dense [N][row_bytes] source
  * goes to dst + n * dst_row_stride (slot [n, t] of an (N, T, ...) buffer tensor); i32_to_f32 converts int32 actions to
