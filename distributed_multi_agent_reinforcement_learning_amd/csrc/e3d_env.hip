@@ -20,6 +20,7 @@
 #include "e3d_env.h"
 #include "guidance.hpp"
 #include "obs_norm.hpp"
+#include "pursuit_features.hpp"
 #include "reward_scale.hpp"
 #include "reward_shaping.hpp"
 #include "rng_replica.hpp"
@@ -619,6 +620,99 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_guidance(const e3d_config c,
     }
 }
 
+// the line-of-sight policy features (include/e3d_env.h e3d_pursuit_features; csrc/pursuit_features.hpp): the
+// tick's lane layout, lane = (environment, pursuer).  A lane keeps its pursuer, its own copy of the evader and of the target and its
+// row of pp_adj (one bit per team-mate) in registers; team-mates arrive through shuffles inside the group, in index order, and a
+// running (nearest, second) pair per network takes them with strict <: no sort, no LDS, no atomics.  Every lane of the wave runs
+// the loops (the trip counts are wave-uniform); only the lanes of real pursuers store, 2 x 8 16-byte stores each.
+// TEAM (evader_obs: team): a sighting travels along communication links.  Lane i's neighbour mask is its row OR the transposed bit
+// of every team-mate's row, cut to the active pursuers, plus itself; path doubling (reach_i <- OR of reach_j over j in reach_i, LOG2
+// rounds of P shuffles of the mask's 32-bit halves) closes it, and the lane knows the evader when its component holds a pursuer
+// that senses it (the group's ballot of pe_adj).
+template <int PT>
+__device__ __forceinline__ uint64_t e3d_shfl_mask(uint64_t m, int src) {
+    uint64_t r = (uint32_t)__shfl((int)(uint32_t)m, src);
+    if (PT == 64) r |= (uint64_t)(uint32_t)__shfl((int)(uint32_t)(m >> 32), src) << 32;   // (a narrower group has no high half)
+    return r;
+}
+
+template <int PT, bool TEAM>
+__global__ __launch_bounds__(WAVE * WPB) void k_e3d_pursuit(const e3d_config c, const e3d_state st, const e3d_obs_out o, const int sensed,
+                                                            float *af, float *cf) {
+    constexpr int G = WAVE / PT;
+    constexpr int LOG2 = PT == 8 ? 3 : (PT == 16 ? 4 : (PT == 32 ? 5 : 6));
+    constexpr uint64_t GM = PT == 64 ? ~0ull : ((1ull << PT) - 1ull);
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT, base = lane - a;
+    const int env = wave * G + g, P = c.P;
+    const bool ev = env < st.N, pv = ev && a < P;
+    double x = 0, y = 0, z = 0, phi = 0, gamma = 0, v = 0, act = 0;
+    double e[7] = {0, 0, 0, 0, 0, 0, 0}, tg[3] = {0, 0, 0};
+    int32_t ts = 0;
+    uint64_t rowm = 0;   // bit j: pp_adj[i][j] == 1
+    bool pe = false;
+    if (pv) {
+        const double *q = st.p + (size_t)env * 7 * P + a;
+        x = q[0]; y = q[P]; z = q[2 * P]; phi = q[3 * P]; gamma = q[4 * P]; v = q[5 * P]; act = q[6 * P];
+        const float *pp = o.pp_adj + (int64_t)env * o.pp_adj_stride + (int64_t)a * P;
+        for (int j = 0; j < P; j++) rowm |= (uint64_t)(pp[j] == 1.f) << j;
+        pe = o.pe_adj[(int64_t)env * o.pe_adj_stride + a] == 1.f;
+    }
+    if (ev) {
+        const double *ge = st.e + (size_t)env * 7;
+        for (int k = 0; k < 7; k++) e[k] = ge[k];
+        for (int k = 0; k < 3; k++) tg[k] = st.target[3 * (size_t)env + k];
+        ts = st.time_step[env];
+    }
+    const bool on = pv && act != 0.0;
+    const uint64_t amask = (__ballot(on) >> base) & GM;          // the group's active pursuers
+    const uint64_t smask = (__ballot(on && pe) >> base) & GM;    // ... that sense the evader
+    pfeat::Near na, nc;
+    pfeat::near_init(na);
+    pfeat::near_init(nc);
+    uint64_t nb = rowm;
+    for (int k = 0; k < P; k++) {
+        const double kx = __shfl(x, base + k), ky = __shfl(y, base + k), kz = __shfl(z, base + k);
+        if (TEAM) nb |= ((e3d_shfl_mask<PT>(rowm, base + k) >> a) & 1ull) << k;   // pp_adj[k][i]
+        if (k != a && ((amask >> k) & 1ull)) {
+            const double dx = kx - x, dy = ky - y, dz = kz - z;
+            pfeat::near_add(nc, dx, dy, dz);
+            if ((rowm >> k) & 1ull) pfeat::near_add(na, dx, dy, dz);
+        }
+    }
+    bool ka = sensed ? pe : true;   // sensed | global
+    if (TEAM) {
+        uint64_t reach = (nb & amask) | (1ull << a);
+#pragma unroll 1
+        for (int r = 0; r < LOG2; r++) {
+            uint64_t m = reach;
+            for (int k = 0; k < P; k++) {
+                const uint64_t rk = e3d_shfl_mask<PT>(reach, base + k);
+                if ((reach >> k) & 1ull) m |= rk;
+            }
+            reach = m;
+        }
+        ka = (reach & smask) != 0ull;
+    }
+    if (!pv) return;   // (after the last shuffle)
+    float fa[pfeat::FEAT], fc[pfeat::FEAT];
+    if (on) {
+        pfeat::Common cm;
+        pfeat::common(cm, x, y, z, phi, gamma, v, e[0], e[1], e[2], e[3], e[4], e[5], tg[0], tg[1], tg[2], E3D_WORLD, c.p_vmax, c.e_vmax, ts,
+                      c.max_step);
+        const bool e_on = e[6] != 0.0;
+        pfeat::row(fa, cm, ka && e_on, na, P, E3D_WORLD, c.kill_radius);
+        pfeat::row(fc, cm, e_on, nc, P, E3D_WORLD, c.kill_radius);
+    } else {
+        for (int q = 0; q < pfeat::FEAT; q++) fa[q] = fc[q] = 0.f;
+    }
+    float4 *da = reinterpret_cast<float4 *>(af + ((size_t)env * P + a) * pfeat::FEAT), *dc = reinterpret_cast<float4 *>(cf + ((size_t)env * P + a) * pfeat::FEAT);
+    for (int q = 0; q < pfeat::FEAT / 4; q++) {
+        da[q] = make_float4(fa[4 * q], fa[4 * q + 1], fa[4 * q + 2], fa[4 * q + 3]);
+        dc[q] = make_float4(fc[4 * q], fc[4 * q + 1], fc[4 * q + 2], fc[4 * q + 3]);
+    }
+}
+
 struct E3dResetter { e3d_config cfg; int N; std::vector<rngrep::NpRandom> rng; };
 
 }  // namespace
@@ -759,6 +853,82 @@ int e3d_pursuer_guidance(const e3d_config *cfg, const e3d_state *st, const e3d_g
     if (pt == 8) E3D_GD(8); else if (pt == 16) E3D_GD(16); else if (pt == 32) E3D_GD(32); else E3D_GD(64);
 #undef E3D_GD
     return (int)hipGetLastError();
+}
+
+int e3d_pursuit_features(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, int32_t evader_obs, float *actor_feat,
+                         float *critic_feat, void *stream) {
+    if (!cfg || !st || !out || !out->pp_adj || !out->pe_adj || !actor_feat || !critic_feat) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (evader_obs != E3D_EVADER_OBS_SENSED && evader_obs != E3D_EVADER_OBS_TEAM && evader_obs != E3D_EVADER_OBS_GLOBAL) return E3D_ERR_BAD_CONFIG;
+    if (((uintptr_t)actor_feat | (uintptr_t)critic_feat) % 16) return E3D_ERR_BAD_CONFIG;   // the rows are stored as 16-byte lanes
+    if (st->N < 1) return 0;
+    if (!st->p || !st->e || !st->target || !st->time_step) return E3D_ERR_NULL;
+    const int pt = cfg->P <= 8 ? 8 : (cfg->P <= 16 ? 16 : (cfg->P <= 32 ? 32 : 64));
+    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    hipStream_t s = (hipStream_t)stream;
+    const int sensed = evader_obs == E3D_EVADER_OBS_SENSED;
+#define E3D_PF(PT, TEAM) hipLaunchKernelGGL((k_e3d_pursuit<PT, TEAM>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, *out, sensed, actor_feat, critic_feat)
+    if (evader_obs == E3D_EVADER_OBS_TEAM) {
+        if (pt == 8) E3D_PF(8, true); else if (pt == 16) E3D_PF(16, true); else if (pt == 32) E3D_PF(32, true); else E3D_PF(64, true);
+    } else {
+        if (pt == 8) E3D_PF(8, false); else if (pt == 16) E3D_PF(16, false); else if (pt == 32) E3D_PF(32, false); else E3D_PF(64, false);
+    }
+#undef E3D_PF
+    return (int)hipGetLastError();
+}
+
+int e3d_pursuit_features_host(const e3d_config *cfg, int32_t N, const double *p, const double *e, const double *target, const int32_t *time_step,
+                              const float *pp_adj, const float *pe_adj, int32_t evader_obs, float *actor_feat, float *critic_feat) {
+    if (!cfg || !p || !e || !target || !time_step || !pp_adj || !pe_adj || !actor_feat || !critic_feat) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (evader_obs != E3D_EVADER_OBS_SENSED && evader_obs != E3D_EVADER_OBS_TEAM && evader_obs != E3D_EVADER_OBS_GLOBAL) return E3D_ERR_BAD_CONFIG;
+    const int P = cfg->P;
+    for (int32_t n = 0; n < N; n++) {
+        const double *q = p + (size_t)n * 7 * P, *ge = e + (size_t)n * 7, *tg = target + (size_t)n * 3;
+        const float *pp = pp_adj + (size_t)n * P * P, *pe = pe_adj + (size_t)n * P;
+        uint64_t amask = 0, smask = 0, reach[E3D_MAX_P];
+        for (int i = 0; i < P; i++) {
+            if (q[6 * P + i] == 0.0) continue;
+            amask |= 1ull << i;
+            if (pe[i] == 1.f) smask |= 1ull << i;
+        }
+        if (evader_obs == E3D_EVADER_OBS_TEAM) {
+            for (int i = 0; i < P; i++) {
+                uint64_t nb = 0;
+                for (int j = 0; j < P; j++) nb |= (uint64_t)(pp[i * P + j] == 1.f || pp[j * P + i] == 1.f) << j;
+                reach[i] = ((amask >> i) & 1ull) ? ((nb & amask) | (1ull << i)) : (1ull << i);
+            }
+            pfeat::close_masks(reach, P);
+        }
+        for (int i = 0; i < P; i++) {
+            float *fa = actor_feat + ((size_t)n * P + i) * pfeat::FEAT, *fc = critic_feat + ((size_t)n * P + i) * pfeat::FEAT;
+            if (!((amask >> i) & 1ull)) {
+                for (int k = 0; k < pfeat::FEAT; k++) fa[k] = fc[k] = 0.f;
+                continue;
+            }
+            pfeat::Near na, nc;
+            pfeat::near_init(na);
+            pfeat::near_init(nc);
+            for (int j = 0; j < P; j++) {
+                if (j == i || !((amask >> j) & 1ull)) continue;
+                const double dx = q[j] - q[i], dy = q[P + j] - q[P + i], dz = q[2 * P + j] - q[2 * P + i];
+                pfeat::near_add(nc, dx, dy, dz);
+                if (pp[i * P + j] == 1.f) pfeat::near_add(na, dx, dy, dz);
+            }
+            bool ka = true;
+            if (evader_obs == E3D_EVADER_OBS_SENSED) ka = pe[i] == 1.f;
+            else if (evader_obs == E3D_EVADER_OBS_TEAM) ka = (reach[i] & smask) != 0ull;
+            pfeat::Common cm;
+            pfeat::common(cm, q[i], q[P + i], q[2 * P + i], q[3 * P + i], q[4 * P + i], q[5 * P + i], ge[0], ge[1], ge[2], ge[3], ge[4], ge[5], tg[0],
+                          tg[1], tg[2], E3D_WORLD, cfg->p_vmax, cfg->e_vmax, time_step[n], cfg->max_step);
+            const bool e_on = ge[6] != 0.0;
+            pfeat::row(fa, cm, ka && e_on, na, P, E3D_WORLD, cfg->kill_radius);
+            pfeat::row(fc, cm, e_on, nc, P, E3D_WORLD, cfg->kill_radius);
+        }
+    }
+    return 0;
 }
 
 int e3d_evader_slsqp(const e3d_config *cfg, const e3d_state *st, double *e_cmd, void *stream) {

@@ -90,6 +90,8 @@ def load_library():
         L.e3d_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
         L.e3d_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
         L.e3d_pursuer_guidance.argtypes = [vp] * 5
+        L.e3d_pursuit_features.argtypes = [vp] * 3 + [C.c_int32] + [vp] * 3
+        L.e3d_pursuit_features_host.argtypes = [vp, C.c_int32] + [vp] * 6 + [C.c_int32, vp, vp]
         _lib = L
     return _lib
 
@@ -98,6 +100,17 @@ def _check(rc, what):
     if rc != 0:
         extra = " (no pursuer placement within E3D_RESET_MAX_DRAWS draws: too many pursuers for the 10^3 box at distance 4)" if rc == 40003 else ""
         raise RuntimeError(f"{what} failed with code {rc}{extra}")
+
+
+PURSUIT_FEAT = 32                              # E3D_FEAT2: the columns of pursuit_features
+EVADER_OBS = ("sensed", "team", "global")      # E3D_EVADER_OBS_SENSED / _TEAM / _GLOBAL = the index
+
+
+def evader_obs_code(name):
+    """the ABI's code of an evader_obs mode given by name; ValueError for a name that is none of EVADER_OBS"""
+    if name not in EVADER_OBS:
+        raise ValueError(f"evader_obs: {name!r} is not one of {EVADER_OBS}")
+    return EVADER_OBS.index(name)
 
 
 def _stream():
@@ -271,6 +284,19 @@ class ParticleEnv:
                                                C.c_void_p(critic_feat.data_ptr()), C.c_void_p(norm_state.data_ptr()), C.c_double(float(clip)),
                                                C.c_void_p(live_ptr), C.c_int64(live_rs), C.c_void_p(slots_ptr), _stream()),
                "e3d_policy_features_norm")
+        return actor_feat, critic_feat
+
+    def pursuit_features(self, actor_feat, critic_feat, evader_obs="sensed"):
+        """the (N, P, 32) fp32 line-of-sight features of the current state into the two dense tensors (algo.e3d_features: pursuit;
+        e3d_pursuit_features, include/e3d_env.h; specification: tests/e3d_features_ref.py): own position, heading and speed, the evader
+        as direction, range, velocity, closing speed and target offset, the nearest two visible team-mates, the clock.  evader_obs
+        says when the ACTOR knows the evader: "sensed" (pe_adj, the rule of policy_features), "team" (some pursuer of its communication
+        component senses it) or "global" (always); the critic always does.  One launch; nothing but the two tensors is written."""
+        code = evader_obs_code(evader_obs)
+        for t in (actor_feat, critic_feat):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (self.num_envs, self.p_num, PURSUIT_FEAT) and t.device == self.p.device
+        _check(self.L.e3d_pursuit_features(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_int32(code),
+                                           C.c_void_p(actor_feat.data_ptr()), C.c_void_p(critic_feat.data_ptr()), _stream()), "e3d_pursuit_features")
         return actor_feat, critic_feat
 
     # ---- MAPPO on env_3d (e3d_agent.py): the bookkeeping of one lockstep tick, one launch after step() ------------------------------

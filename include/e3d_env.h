@@ -141,6 +141,39 @@ typedef struct e3d_guidance_params { double lead, sep_range, sep_gain; } e3d_gui
  * One launch in the tick's lane layout, team-mates through shuffles, f64, no host synchronisation; the records are only read. */
 int e3d_pursuer_guidance(const e3d_config *cfg, const e3d_state *st, const e3d_guidance_params *params, double *actions, void *stream);
 
+/* ---- algo.e3d_features: pursuit -- line-of-sight policy features with a model of who knows where the evader is (csrc/pursuit_features.hpp,
+ * DESIGN.md section 7g; specification: tests/e3d_features_ref.py) ----
+ * Both (N, P, E3D_FEAT2) fp32 tensors (dense, 16-byte aligned) in one launch, from the records, st->target, st->time_step and out->pp_adj /
+ * out->pe_adj of the current state.  Pursuer i: position p_i, u_i = (cos gamma_i cos phi_i, cos gamma_i sin phi_i, sin gamma_i), speed v_i;
+ * r = e_pos - p_i, d = sqrt(rx rx + ry ry + rz rz), rh = r / d (0 when d is 0); e_vel = v_e (cos gamma_e cos phi_e, cos gamma_e sin phi_e,
+ * sin gamma_e); W = E3D_WORLD.  The columns, the same for both networks:
+ *   0-2   p_i / (W / 2) - 1          3-5   u_i                     6  v_i / p_vmax
+ *   7-9   k rh                       10    k d / W                 11-13  k e_vel / e_vmax
+ *   14    k (-rh . (e_vel - v_i u_i)) / (e_vmax + p_vmax)  (the closing speed)       15  k (u_i . rh)      16  k
+ *   17-19 k (target - e_pos) / W
+ *   20-24 the nearest visible team-mate j: (p_j - p_i) / d_ij (0 when d_ij is 0), d_ij / W, kill_radius / max(d_ij, kill_radius)
+ *   25-29 the second nearest, the same five (a missing team-mate leaves its block 0)
+ *   30    |V_i| / max(P - 1, 1)      31    time_step / max_step
+ * k, who knows the evader: the critic's is active_e; the actor's follows evader_obs --
+ *   SENSED  pe_adj[i] active_e (the rule of e3d_policy_features);
+ *   TEAM    active_e when some pursuer of i's connected component senses the evader (pe_adj[j] == 1), i included: the components of the
+ *           graph over the active pursuers with an edge i - j when pp_adj[i][j] == 1 or pp_adj[j][i] == 1 -- a sighting is relayed along
+ *           communication links, over as many hops as the component has;
+ *   GLOBAL  active_e (what the scripted pursuers read).
+ * V_i, the visible team-mates: the actor's are the active j != i with pp_adj[i][j] == 1, the critic's every active j != i; nearest by
+ * dx dx + dy dy + dz dz, the lowest index on ties.  Rows of inactive pursuers are zero; with the evader inactive columns 7-19 are zero.
+ * f64 arithmetic in the order written, rounded to fp32 at the store.  One launch in the tick's lane layout, team-mates through shuffles, no
+ * atomics, no host synchronisation; only the two outputs are written.  An evader_obs that is none of the three: E3D_ERR_BAD_CONFIG. */
+#define E3D_FEAT2 32
+#define E3D_WORLD 20.0   /* the side of the reset cube (particle_env.py:138-142) */
+enum { E3D_EVADER_OBS_SENSED = 0, E3D_EVADER_OBS_TEAM = 1, E3D_EVADER_OBS_GLOBAL = 2 };
+int e3d_pursuit_features(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, int32_t evader_obs, float *actor_feat,
+                         float *critic_feat, void *stream);
+/* The same computation on the host, on host records laid out as the device ones (p [N][7][P], e [N][7], target [N][3], time_step [N]) and
+ * dense adjacencies pp_adj [N][P][P], pe_adj [N][P]; no alignment is required of the outputs. */
+int e3d_pursuit_features_host(const e3d_config *cfg, int32_t N, const double *p, const double *e, const double *target, const int32_t *time_step,
+                              const float *pp_adj, const float *pe_adj, int32_t evader_obs, float *actor_feat, float *critic_feat);
+
 /* The reference's evader: eva.e_f (eva.py:87-148) -- scipy's SLSQP (ftol 1e-6, <= 100 iterations, 2-point finite-difference
  * gradient) minimising obj_func (:212-240) over (heading, pitch, speed), started at the evader's state, bounded by the
  * environment's ang_lmt / v_lmt (:130-135) -- written as the command e_cmd [N][3] that e3d_env_tick consumes; zeros when the
