@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "direction_action.hpp"
 #include "e3d_env.h"
 #include "guidance.hpp"
 #include "obs_norm.hpp"
@@ -928,6 +929,20 @@ int e3d_pursuit_features_host(const e3d_config *cfg, int32_t N, const double *p,
             pfeat::row(fc, cm, e_on, nc, P, E3D_WORLD, cfg->kill_radius);
         }
     }
+    return 0;
+}
+
+int gauss_direction_map_host(int32_t R, const float *u, double *env_action) {
+    if (!u || !env_action) return E3D_ERR_NULL;
+    if (R < 0) return E3D_ERR_BAD_CONFIG;
+    for (int32_t r = 0; r < R; r++) diract::to_env(u + (size_t)r * diract::LATENT, env_action + (size_t)r * diract::ENV_A);
+    return 0;
+}
+
+int e3d_direction_label_host(int32_t R, const double *g, float *a_star) {
+    if (!g || !a_star) return E3D_ERR_NULL;
+    if (R < 0) return E3D_ERR_BAD_CONFIG;
+    for (int32_t r = 0; r < R; r++) diract::label(g + (size_t)r * diract::ENV_A, a_star + (size_t)r * diract::LATENT);
     return 0;
 }
 

@@ -4,6 +4,7 @@
 // file's Philox4x32-10 (philox4x32_10), the 16-lane row sum (row16_sum), the wave-local LDS fence (wave_fence), the PPO row
 // (ppo_elem, PpoView, PPO_BLOCKS) and the head's feature width (HEAD_H).
 #pragma once
+#include "direction_action.hpp"
 
 namespace {
 
@@ -207,9 +208,13 @@ __global__ __launch_bounds__(64) void k_ppo_gauss_finish_diag(int nsum, int nblk
 
 // ---- state-dependent log-std and tanh squashing (gauss_head_sample_ex / ppo_loss_gauss_ex_fwd_bwd) ---------------------------------
 // u = mu + exp(ls) z with ls = clamp(ls_raw, log_std_min, log_std_max); ls_raw = feat W_ls^T + b_ls (state mode) or the log_std vector
-// (param mode).  The buffer keeps u in both squash modes; the environment gets clamp(u, -1, 1) (clip) or tanh(u) (tanh) in f64, and the
+// (param mode).  The buffer keeps u in every squash mode; the environment gets clamp(u, -1, 1) (clip) or tanh(u) (tanh) in f64, and the
 // tanh log-probability subtracts sum_a c(u_a), c(u) = log(1 - tanh(u)^2) = 2 (ln 2 - u - softplus(-2 u)).  The head and the loss both
 // call tanh_log_jac, so the rollout's and the update's correction are the same bits for the same u.
+// Direction mode: u = (u_x, u_y, u_z, s) has four dimensions and the environment gets the three commands of
+// diract::to_env (csrc/direction_action.hpp): the heading and the pitch of the vector, and s.  The map belongs to the environment: the
+// log-probability is the plain Normal one of u, as in clip mode, and the update takes the clip instance of the loss with A = 4.
+constexpr int GAUSS_CLIP = 0, GAUSS_TANH = 1, GAUSS_DIRECTION = 2;   // the squash argument of the C entries
 constexpr float GAUSS_LN2 = 0.69314718055994530942f;
 __device__ __forceinline__ float tanh_log_jac(float u) {
     const float x = -2.f * u;
@@ -220,13 +225,15 @@ __device__ __forceinline__ float tanh_log_jac(float u) {
 // the 2 AT dot products of a row go through row16_sum and LDS like mu's, hence AT <= 8 (2 AT <= 16 lanes of a row).  Same Philox
 // layout, expression order and ticket as k_gauss_head.
 constexpr int GAUSS_SD_MAX_A = 8;
-template <int AT, bool STATE, bool TANH>
+template <int AT, bool STATE, int MODE>
 __global__ __launch_bounds__(256) void k_gauss_head_ex(int R, const float *__restrict__ feat, const float *__restrict__ W, const float *__restrict__ b,
                                                        const float *__restrict__ W_ls, const float *__restrict__ b_ls, const float *__restrict__ log_std,
                                                        float ls_lo, float ls_hi, uint64_t seed, uint64_t *counter, unsigned int *done, int greedy,
                                                        float *__restrict__ action, double *__restrict__ env_action, float *__restrict__ logp) {
     constexpr int NO = STATE ? 2 * AT : AT;   // outputs per row: mu, then ls_raw in state mode
     static_assert(NO <= 16, "one output per lane of a 16-lane row");
+    static_assert(MODE != GAUSS_DIRECTION || AT == diract::LATENT, "the direction head has four latent dimensions");
+    constexpr bool TANH = MODE == GAUSS_TANH, DIR = MODE == GAUSS_DIRECTION;
     __shared__ float s_y[4][64][NO + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (gridDim.x * blockDim.x) >> 6;
     const int i = lane & 15, g = lane >> 4;
@@ -290,15 +297,23 @@ __global__ __launch_bounds__(256) void k_gauss_head_ex(int R, const float *__res
                 }
             }
             float lp = 0.f, jac = 0.f;
+            float xs[AT];   // (direction mode only)
 #pragma unroll
             for (int a = 0; a < AT; a++) {
                 const float ls_raw = STATE ? sy[lane][AT + a] + b_ls[a] : log_std[a];
                 const float ls = fminf(fmaxf(ls_raw, ls_lo), ls_hi);
                 const float x = sy[lane][a] + b[a] + expf(ls) * z[a];
                 action[(size_t)r * AT + a] = x;
-                env_action[(size_t)r * AT + a] = TANH ? tanh((double)x) : (double)fminf(fmaxf(x, -1.f), 1.f);
+                if (DIR) xs[a] = x;
+                else env_action[(size_t)r * AT + a] = TANH ? tanh((double)x) : (double)fminf(fmaxf(x, -1.f), 1.f);
                 lp += -0.5f * z[a] * z[a] - ls - HALF_LN_2PI;
                 if (TANH) jac += tanh_log_jac(x);
+            }
+            if constexpr (DIR) {   // env_action is (R, 3): the angles of the sampled vector and the speed
+                double env[diract::ENV_A];
+                diract::to_env(xs, env);
+#pragma unroll
+                for (int a = 0; a < diract::ENV_A; a++) env_action[(size_t)r * diract::ENV_A + a] = env[a];
             }
             logp[r] = TANH ? lp - jac : lp;
         }
@@ -498,18 +513,22 @@ int gauss_head_sample_ex(int32_t R, int32_t A, int32_t H, const float *feat, con
                          uint32_t *ticket, int32_t greedy, float *action, double *env_action, float *logp, void *stream) {
     const bool state = W_ls != nullptr;
     if (R < 0 || A < 1 || A > (state ? GAUSS_SD_MAX_A : GAUSS_MAX_A) || H != HEAD_H || !feat || !W || !b || state != (b_ls != nullptr) ||
-        state == (log_std != nullptr) || (squash != 0 && squash != 1) || !gauss_ex_bounds_ok(log_std_min, log_std_max) || !counter || !ticket ||
-        !action || !env_action || !logp || ((uintptr_t)feat & 15))
+        state == (log_std != nullptr) || (squash != GAUSS_CLIP && squash != GAUSS_TANH && squash != GAUSS_DIRECTION) ||
+        (squash == GAUSS_DIRECTION && A != diract::LATENT) || !gauss_ex_bounds_ok(log_std_min, log_std_max) || !counter || !ticket || !action ||
+        !env_action || !logp || ((uintptr_t)feat & 15))
         return MO_ERR_BAD_ARG;
     if (R == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int g0 = (R + 255) / 256, grid = g0 < 1024 ? g0 : 1024;
 #define GAUSS_EX(AT, S, T) hipLaunchKernelGGL((k_gauss_head_ex<AT, S, T>), dim3(grid), dim3(256), 0, st, R, feat, W, b, W_ls, b_ls, log_std, \
                                               log_std_min, log_std_max, seed, counter, ticket, (int)greedy, action, env_action, logp)
-#define GAUSS_EX4(AT) case AT: if (state) { if (squash) GAUSS_EX(AT, true, true); else GAUSS_EX(AT, true, false); } \
-                               else { if (squash) GAUSS_EX(AT, false, true); else GAUSS_EX(AT, false, false); } break;
-#define GAUSS_EX2(AT) case AT: if (squash) GAUSS_EX(AT, false, true); else GAUSS_EX(AT, false, false); break;
-    switch (A) {
+#define GAUSS_EX4(AT) case AT: if (state) { if (squash) GAUSS_EX(AT, true, GAUSS_TANH); else GAUSS_EX(AT, true, GAUSS_CLIP); } \
+                               else { if (squash) GAUSS_EX(AT, false, GAUSS_TANH); else GAUSS_EX(AT, false, GAUSS_CLIP); } break;
+#define GAUSS_EX2(AT) case AT: if (squash) GAUSS_EX(AT, false, GAUSS_TANH); else GAUSS_EX(AT, false, GAUSS_CLIP); break;
+    if (squash == GAUSS_DIRECTION) {   // A is 4: action (R, 4), env_action (R, 3)
+        if (state) GAUSS_EX(4, true, GAUSS_DIRECTION);
+        else GAUSS_EX(4, false, GAUSS_DIRECTION);
+    } else switch (A) {
         GAUSS_EX4(1) GAUSS_EX4(2) GAUSS_EX4(3) GAUSS_EX4(4) GAUSS_EX4(5) GAUSS_EX4(6) GAUSS_EX4(7) GAUSS_EX4(8) GAUSS_EX2(9) GAUSS_EX2(10)
         GAUSS_EX2(11) GAUSS_EX2(12) GAUSS_EX2(13) GAUSS_EX2(14) GAUSS_EX2(15) GAUSS_EX2(16)
     }
@@ -528,9 +547,13 @@ static int ppo_loss_gauss_ex_launch(int64_t n, int32_t A, const float *mu, float
                                     const float *values_old, const float *v_target, const float *active_sum, float epsilon, float entropy_coef,
                                     int32_t use_value_clip, float *losses, float *grad_values, void *workspace, double *diag, void *stream) {
     if (n < 1 || A < 1 || A > GAUSS_MAX_A || d1 < 1 || d2 < 1 || (n % (d1 * d2)) || !mu || !grad_mu || !ls_raw || !grad_log_std ||
-        (squash != 0 && squash != 1) || !gauss_ex_bounds_ok(log_std_min, log_std_max) || !action || !logp_old || !adv || !active || !values_now ||
-        !v_target || !active_sum || !losses || !grad_values || !workspace || (use_value_clip && !values_old))
+        (squash != GAUSS_CLIP && squash != GAUSS_TANH && squash != GAUSS_DIRECTION) || !gauss_ex_bounds_ok(log_std_min, log_std_max) || !action ||
+        !logp_old || !adv || !active || !values_now || !v_target || !active_sum || !losses || !grad_values || !workspace ||
+        (use_value_clip && !values_old))
         return MO_ERR_BAD_ARG;
+    // direction mode: the action of the MDP is the latent u and the map to the angles is the environment's, so its log-probability has no
+    // Jacobian term -- the clip instances
+    if (squash == GAUSS_DIRECTION) squash = GAUSS_CLIP;
     const bool state = (l_s0 | l_s1 | l_s2) != 0;
     long blocks = (n + 255) / 256;
     if (blocks > PPO_BLOCKS) blocks = PPO_BLOCKS;

@@ -12,10 +12,13 @@ namespace {
 // with fit_std g_ls = (active / sum active) (1 - d^2 iv) on the closed range [lo, hi], 0 outside, per row (STATE) or summed through the
 // partials (param mode); without fit_std it is exactly 0.  The critic's lc and g_v are ppo_elem's, and the reduction is
 // k_ppo_loss_gauss's (wave butterflies, the four waves in a fixed order, k_bc_gauss_finish in block order), so they carry the bits of
-// ppo_loss_gauss on the same inputs.  Sum 2 is sum_rows active sum_a d^2 (bc_action_mse).  No atomics: the same bits every run.
-constexpr int BC_GAUSS_PART = 3 + GAUSS_MAX_A;   // doubles per block: actor sum, critic sum, sum d^2, log_std gradient [A]
+// ppo_loss_gauss on the same inputs.  Sum 2 is sum_rows active sum_a d^2 (bc_action_mse), or with ANGLE (algo.gauss_squash: direction,
+// A >= 3) sum_rows active angle(mu[:3], target[:3]) in radians (diract::angle, fp32 per row; bc_angle_deg).  No atomics: the same bits
+// every run.
+constexpr int BC_GAUSS_PART = 3 + GAUSS_MAX_A;   // doubles per block: actor sum, critic sum, sum d^2 | sum angle, log_std gradient [A]
+constexpr int BC_METRIC_SQ = 0, BC_METRIC_ANGLE = 1;   // the metric argument of bc_loss_gauss_ex_fwd_bwd
 
-template <bool STATE>
+template <bool STATE, bool ANGLE>
 __global__ __launch_bounds__(256) void k_bc_loss_gauss(long n, int A, const float *__restrict__ mu, PpoView mv, const float *__restrict__ ls_raw,
                                                        PpoView lv, float ls_lo, float ls_hi, int fit_std, int wrap0,
                                                        const float *__restrict__ target, const float *active, const float *__restrict__ v_now,
@@ -45,6 +48,7 @@ __global__ __launch_bounds__(256) void k_bc_loss_gauss(long n, int A, const floa
         const float act = active[i];
         const float up = act * inv;
         float la = 0.f, sq = 0.f;
+        float m3[3] = {0.f, 0.f, 0.f}, t3[3] = {0.f, 0.f, 0.f};   // (ANGLE only)
 #pragma unroll
         for (int k = 0; k < GAUSS_MAX_A; k++)
             if (k < A) {
@@ -59,6 +63,7 @@ __global__ __launch_bounds__(256) void k_bc_loss_gauss(long n, int A, const floa
                     lsk = ls[k]; ivk = iv[k]; pk = pass[k];
                 }
                 float d = target[i * A + k] - mu[mo + k];
+                if (ANGLE && k < 3) { m3[k] = mu[mo + k]; t3[k] = target[i * A + k]; }
                 if (k == 0 && wrap0) d -= 2.f * floorf((d + 1.f) * 0.5f);   // heading / pi: +-1 are the same heading
                 const float dd = d * d;
                 la += 0.5f * dd * ivk + (fit_std ? lsk : 0.f);
@@ -72,7 +77,7 @@ __global__ __launch_bounds__(256) void k_bc_loss_gauss(long n, int A, const floa
         const PpoElem e = ppo_elem(0.f, 0.f, 0.f, 0.f, act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, 0.f, value_clip);
         acc[0] += (double)(la * act);
         acc[1] += (double)(e.lc * act);
-        acc[2] += (double)(sq * act);
+        acc[2] += (double)((ANGLE ? diract::angle(m3, t3) : sq) * act);
         g_v[i] = e.g_v;
     }
     const int nsum = STATE ? 3 : 3 + A;
@@ -182,20 +187,25 @@ __global__ __launch_bounds__(64) void k_bc_cat_finish(int nblk, const double *pa
 // ---- rollout: the teacher's label into the buffer, the teacher's action over the network's where the environment follows it --------
 // One lane per (environment, pursuer).  The label is written for every environment (DAgger labels the learner's own states); nothing
 // but row t of a_star (N rows, row_stride floats apart) and the followed rows of the action tensor is touched.
-template <bool TANH>
+// MODE GAUSS_DIRECTION: the label is the unit vector of the commanded angles and the speed (diract::label), four floats per pursuer.
+template <int MODE>
 __global__ __launch_bounds__(256) void k_e3d_bc_select(int N, int P, const double *__restrict__ guide, const unsigned char *__restrict__ follow,
                                                        double bound, double *__restrict__ env_action, float *__restrict__ a_star, long row_stride) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= N * P) return;
     const int env = idx / P, p = idx - env * P;
     const bool f = follow[env] != 0;
-    float *dst = a_star + (long)env * row_stride + (long)p * 3;
+    constexpr bool TANH = MODE == GAUSS_TANH, DIR = MODE == GAUSS_DIRECTION;
+    float *dst = a_star + (long)env * row_stride + (long)p * (DIR ? diract::LATENT : 3);
+    double gs[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         const double g = guide[(long)idx * 3 + a];
-        dst[a] = TANH ? (float)atanh(fmin(fmax(g, -bound), bound)) : (float)g;
+        gs[a] = g;
+        if (!DIR) dst[a] = TANH ? (float)atanh(fmin(fmax(g, -bound), bound)) : (float)g;
         if (f) env_action[(long)idx * 3 + a] = g;
     }
+    if (DIR) diract::label(gs, dst);
 }
 
 __global__ __launch_bounds__(256) void k_n2n_bc_select(int N, int P, const int *__restrict__ guide, const unsigned char *__restrict__ follow,
@@ -214,30 +224,43 @@ extern "C" {
 
 int64_t bc_loss_workspace(void) { return (int64_t)PPO_BLOCKS * BC_GAUSS_PART * sizeof(double); }   // (the categorical call needs 3 per block)
 
-int bc_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
-                          const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min, float log_std_max,
-                          int32_t fit_std, int32_t wrap0, const float *target, const float *active, const float *values_now, int64_t v_s0,
-                          int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
-                          int32_t use_value_clip, float *losses, float *grad_values, double *sums, void *workspace, void *stream) {
+int bc_loss_gauss_ex_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                             int64_t m_s2, const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min,
+                             float log_std_max, int32_t fit_std, int32_t wrap0, int32_t metric, const float *target, const float *active,
+                             const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                             const float *active_sum, float epsilon, int32_t use_value_clip, float *losses, float *grad_values, double *sums,
+                             void *workspace, void *stream) {
     if (n < 1 || A < 1 || A > GAUSS_MAX_A || d1 < 1 || d2 < 1 || (n % (d1 * d2)) || !mu || !grad_mu || !ls_raw || !grad_log_std ||
         !gauss_ex_bounds_ok(log_std_min, log_std_max) || !target || !active || !values_now || !v_target || !active_sum || !losses || !grad_values ||
-        !workspace || (use_value_clip && !values_old))
+        !workspace || (use_value_clip && !values_old) || (metric != BC_METRIC_SQ && metric != BC_METRIC_ANGLE) || (metric == BC_METRIC_ANGLE && A < 3))
         return MO_ERR_BAD_ARG;
+    if (metric == BC_METRIC_ANGLE) wrap0 = 0;   // a direction vector has no wrapped dimension
     const bool state = (l_s0 | l_s1 | l_s2) != 0;
     long blocks = (n + 255) / 256;
     if (blocks > PPO_BLOCKS) blocks = PPO_BLOCKS;
     const PpoView mv{d1, d2, m_s0, m_s1, m_s2}, lv{d1, d2, l_s0, l_s1, l_s2}, vv{d1, d2, v_s0, v_s1, v_s2};
     hipStream_t st = (hipStream_t)stream;
-#define BC_GAUSS(S) hipLaunchKernelGGL((k_bc_loss_gauss<S>), dim3((unsigned)blocks), dim3(256), 0, st, (long)n, (int)A, mu, mv, ls_raw, lv, log_std_min, \
-                                       log_std_max, (int)(fit_std != 0), (int)(wrap0 != 0), target, active, values_now, vv, values_old, v_target,       \
-                                       active_sum, epsilon, (int)use_value_clip, grad_mu, grad_log_std, grad_values, (double *)workspace)
-    if (state) BC_GAUSS(true);
-    else BC_GAUSS(false);
+#define BC_GAUSS(S, M) hipLaunchKernelGGL((k_bc_loss_gauss<S, M>), dim3((unsigned)blocks), dim3(256), 0, st, (long)n, (int)A, mu, mv, ls_raw, lv,  \
+                                          log_std_min, log_std_max, (int)(fit_std != 0), (int)(wrap0 != 0), target, active, values_now, vv, values_old, \
+                                          v_target, active_sum, epsilon, (int)use_value_clip, grad_mu, grad_log_std, grad_values, (double *)workspace)
+    if (metric == BC_METRIC_ANGLE) { if (state) BC_GAUSS(true, true); else BC_GAUSS(false, true); }
+    else if (state) BC_GAUSS(true, false);
+    else BC_GAUSS(false, false);
 #undef BC_GAUSS
     // state mode: the three sums only (grad_log_std was written per row); param mode: the A log_std sums as well
     hipLaunchKernelGGL(k_bc_gauss_finish, dim3(state ? 3 : 3 + A), dim3(64), 0, st, (int)blocks, (const double *)workspace, active_sum, losses,
                        grad_log_std, sums);
     return (int)hipGetLastError();
+}
+
+int bc_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
+                          const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min, float log_std_max,
+                          int32_t fit_std, int32_t wrap0, const float *target, const float *active, const float *values_now, int64_t v_s0,
+                          int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
+                          int32_t use_value_clip, float *losses, float *grad_values, double *sums, void *workspace, void *stream) {
+    return bc_loss_gauss_ex_fwd_bwd(n, A, mu, grad_mu, d1, d2, m_s0, m_s1, m_s2, ls_raw, grad_log_std, l_s0, l_s1, l_s2, log_std_min, log_std_max,
+                                    fit_std, wrap0, BC_METRIC_SQ, target, active, values_now, v_s0, v_s1, v_s2, values_old, v_target, active_sum,
+                                    epsilon, use_value_clip, losses, grad_values, sums, workspace, stream);
 }
 
 int bc_loss_cat_fwd_bwd(int64_t n, int32_t A, const float *prob, float *grad_prob, int64_t d1, int64_t d2, int64_t p_s0, int64_t p_s1, int64_t p_s2,
@@ -259,13 +282,17 @@ int bc_loss_cat_fwd_bwd(int64_t n, int32_t A, const float *prob, float *grad_pro
 
 int e3d_bc_select(int32_t N, int32_t P, const double *guide, const uint8_t *follow, int32_t squash, double bound, double *env_action, float *a_star,
                   int64_t row_stride, void *stream) {
-    if (N < 0 || P < 1 || (int64_t)N * P > INT32_MAX || !guide || !follow || !env_action || !a_star || row_stride < (int64_t)P * 3 ||
-        (squash != 0 && squash != 1) || (squash && !(bound > 0.0 && bound < 1.0)))
+    if (N < 0 || P < 1 || (int64_t)N * P > INT32_MAX || !guide || !follow || !env_action || !a_star ||
+        (squash != GAUSS_CLIP && squash != GAUSS_TANH && squash != GAUSS_DIRECTION) ||
+        row_stride < (int64_t)P * (squash == GAUSS_DIRECTION ? diract::LATENT : 3) || (squash == GAUSS_TANH && !(bound > 0.0 && bound < 1.0)))
         return MO_ERR_BAD_ARG;
     if (N == 0) return 0;
     const unsigned grid = (unsigned)(((int64_t)N * P + 255) / 256);
-    if (squash) hipLaunchKernelGGL((k_e3d_bc_select<true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (int)N, (int)P, guide, follow, bound, env_action, a_star, (long)row_stride);
-    else hipLaunchKernelGGL((k_e3d_bc_select<false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (int)N, (int)P, guide, follow, bound, env_action, a_star, (long)row_stride);
+#define E3D_SEL(M) hipLaunchKernelGGL((k_e3d_bc_select<M>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (int)N, (int)P, guide, follow, bound, env_action, a_star, (long)row_stride)
+    if (squash == GAUSS_DIRECTION) E3D_SEL(GAUSS_DIRECTION);   // the label row holds four floats per pursuer; bound is ignored
+    else if (squash) E3D_SEL(GAUSS_TANH);
+    else E3D_SEL(GAUSS_CLIP);
+#undef E3D_SEL
     return (int)hipGetLastError();
 }
 

@@ -12,11 +12,16 @@ Two options, both off by default: `algo.gauss_std: state`
 LogStd = Linear(128 -> A) on the GRU features, `algo.gauss_squash: tanh` sends tanh(u) to the environment instead of clamp(u, -1, 1)
 and subtracts log(1 - tanh(u)^2) from the log-probability; ls is clamped to [algo.log_std_min, algo.log_std_max].  With either on,
 the rollout takes ops.gauss_head_sample_ex and the update ops.ppo_loss_gauss_ex; with both off, the calls above.
+`algo.gauss_squash: direction` (needs env.action_dim 3): the policy is a Gaussian over a 4-vector u = (u_x, u_y,
+u_z, s) -- `latent_dim` 4 sizes the heads, the rollout's `action`, and the buffer's `a_n` / `a_star` -- and the environment receives the
+heading and the pitch of (u_x, u_y, u_z) and s (csrc/direction_action.hpp); the log-probability is the plain Normal one of u, the
+imitation label is the teacher's unit vector, and the logged imitation metric is `bc_angle_deg` instead of `bc_action_mse`.
 `algo.e3d_features: pursuit` (off by default) replaces the 16 features by the 32 line-of-sight features of
 ParticleEnv.pursuit_features, and `algo.e3d_evader_obs: sensed | team | global` says when the actor knows where the evader is.
 `algo.use_obs_norm` (off by default; obs_norm.py): both encoders read the features normalised by a running mean / std that is frozen
 during a rollout and merged once after it; the first rollout is the option-off one bit for bit.
 """
+import math
 import os
 
 import torch
@@ -49,7 +54,7 @@ class E3dEncoder(nn.Module):
         return ops.linear(h, self.fc2.weight, self.fc2.bias, relu=True)
 
 
-GAUSS_STD, GAUSS_SQUASH = ("param", "state"), ("clip", "tanh")
+GAUSS_STD, GAUSS_SQUASH = ("param", "state"), ("clip", "tanh", "direction")
 GAUSS_SD_MAX_A = 8   # state mode: a lane of the rollout head holds 2 A x 8 weights (csrc/gauss_policy.hpp k_gauss_head_ex)
 
 
@@ -87,12 +92,12 @@ class _E3dRollout:
     split-bf16 cell cannot update in place) and the position of its action-sampling stream"""
 
     def __init__(self, agent, N, P):
-        dev, L, H, A = agent.device, agent.num_layers, agent.rnn_hidden_dim, agent.action_dim
+        dev, L, H, A, U = agent.device, agent.num_layers, agent.rnn_hidden_dim, agent.action_dim, agent.latent_dim
         z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)
         self.N, self.P = N, P
         self.fa, self.fc = z(N, P, agent.feat_dim), z(N, P, agent.feat_dim)
         self.hbuf_a, self.hbuf_c = z(2, L, N * P, H), z(2, L, N * P, H)
-        self.action, self.env_action, self.logp, self.v = z(N, P, A), z(N, P, A, dt=torch.float64), z(N, P), z(N, P)
+        self.action, self.env_action, self.logp, self.v = z(N, P, U), z(N, P, A, dt=torch.float64), z(N, P), z(N, P)
         self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.live = z(N, P)   # this step's live mask (e3d_policy_record keeps it current)
@@ -110,9 +115,17 @@ def gauss_policy_options(cfg):
     lo, hi = float(a.get("log_std_min", -5.0)), float(a.get("log_std_max", 2.0))
     if not lo < hi:
         raise ValueError(f"algo.log_std_min ({lo}) must be below algo.log_std_max ({hi})")
-    if std == "state" and int(cfg.env.action_dim) > GAUSS_SD_MAX_A:
+    if squash == "direction" and int(cfg.env.action_dim) != ops.DIRECTION_ENV:
+        raise ValueError(f"algo.gauss_squash: direction needs env.action_dim {ops.DIRECTION_ENV} (heading, pitch, speed: the commands the "
+                         f"direction vector maps to), got {int(cfg.env.action_dim)}")
+    if std == "state" and latent_dim(squash, int(cfg.env.action_dim)) > GAUSS_SD_MAX_A:
         raise ValueError(f"algo.gauss_std: state supports env.action_dim <= {GAUSS_SD_MAX_A} (got {int(cfg.env.action_dim)})")
     return std, squash, lo, hi
+
+
+def latent_dim(gauss_squash, action_dim):
+    """the width of the policy's Gaussian: the four dimensions (u_x, u_y, u_z, s) in direction mode, else the environment's actions"""
+    return ops.DIRECTION_LATENT if gauss_squash == "direction" else action_dim
 
 
 def e3d_feature_options(cfg):
@@ -144,15 +157,19 @@ class E3dMAPPO(ParticleMAPPO):
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
         self.action_dim = int(cfg.env.action_dim)
+        self.latent_dim = latent_dim(self.gauss_squash, self.action_dim)   # what the heads emit and the buffer stores
+        if self.gauss_squash == "direction":
+            self.BC_METRIC = "bc_angle_deg"
         if self.imitation.on and self.action_dim != 3:
             raise ValueError(f"algo.bc_iterations > 0 needs env.action_dim 3 (heading, pitch, speed: what the scripted pursuers command), "
                              f"got {self.action_dim}")
-        # the heading residual is taken modulo 2 in clip mode only: a periodic quantity through tanh has no wrap-around residual
+        # the heading residual is taken modulo 2 in clip mode only: a periodic quantity through tanh has no wrap-around residual, and a
+        # direction vector has no periodic dimension at all
         self.bc_wrap0 = self.imitation.heading_wrap and self.gauss_squash == "clip"
 
     def _build(self, cfg):
         a, sn = cfg.algo, bool(cfg.algo.use_spectral_norm)
-        self.actor = GaussianActor(self.feat_dim, self.embedding_dim, self.action_dim, self.num_layers, self.rnn_hidden_dim,
+        self.actor = GaussianActor(self.feat_dim, self.embedding_dim, self.latent_dim, self.num_layers, self.rnn_hidden_dim,
                                    float(a.get("log_std_init", 0.0)), sn, self.gauss_std).to(self.device)
         self.critic = E3dCritic(self.feat_dim, self.embedding_dim, self.num_layers, self.rnn_hidden_dim, sn).to(self.device)
         self.ac_parameters = list(self.actor.parameters()) + list(self.critic.parameters())
@@ -207,12 +224,12 @@ class E3dMAPPO(ParticleMAPPO):
 
     def new_buffer(self, N, T, P):
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)
-        buf = dict(feat_a=z(N, T, P, self.feat_dim), feat_c=z(N, T, P, self.feat_dim), a_n=z(N, T, P, self.action_dim), a_logprob_n=z(N, T, P), r=z(N, T, P),
+        buf = dict(feat_a=z(N, T, P, self.feat_dim), feat_c=z(N, T, P, self.feat_dim), a_n=z(N, T, P, self.latent_dim), a_logprob_n=z(N, T, P), r=z(N, T, P),
                    active=z(N, T, P), v_n=z(N, T + 1, P))
         if self.value_norm is not None:
             buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
         if self.imitation.on:
-            buf["a_star"] = z(N, T, P, 3)   # the scripted pursuers' action of every row, in the policy's pre-squash space (algo.bc_iterations only)
+            buf["a_star"] = z(N, T, P, self.latent_dim)   # the scripted pursuers' action of every row, in the policy's pre-squash space (algo.bc_iterations only)
         return buf
 
     @torch.no_grad()
@@ -290,14 +307,21 @@ class E3dMAPPO(ParticleMAPPO):
     BC_METRIC = "bc_action_mse"
 
     def bc_metric(self, sq_sum, rows):
-        """the mean squared residual per action dimension over the live rows (after the heading wrap), from the launches' two sums"""
-        return sq_sum / (self.action_dim * rows) if rows else float("nan")
+        """the mean squared residual per action dimension over the live rows (after the heading wrap), from the launches' two sums;
+        in direction mode (BC_METRIC is bc_angle_deg) the first sum is of angles in radians: the mean angle between mu[:3] and the
+        teacher's unit vector, in degrees"""
+        if not rows:
+            return float("nan")
+        if self.gauss_squash == "direction":
+            return math.degrees(sq_sum / rows)
+        return sq_sum / (self.action_dim * rows)
 
     def _imitation_loss(self, buf, n0, n1, v_target, sums):
         mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True)
         lo, hi = (self.log_std_min, self.log_std_max) if self.policy_ex else (-float("inf"), float("inf"))
         return ops.bc_loss_gauss(mu, ls_raw, buf["a_star"][n0:n1], *self._imitation_tail(buf, n0, n1, values, v_target), log_std_min=lo,
-                                 log_std_max=hi, fit_std=self.imitation.fit_std, wrap0=self.bc_wrap0, sums=sums)
+                                 log_std_max=hi, fit_std=self.imitation.fit_std, wrap0=self.bc_wrap0, sums=sums,
+                                 metric="angle" if self.gauss_squash == "direction" else "mse")
 
     def policy_meta(self):
         """the "policy" entry of checkpoints and resume bundles: None in the default mode (param, clip, basic features), whose files

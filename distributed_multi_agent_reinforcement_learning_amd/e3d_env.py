@@ -92,6 +92,8 @@ def load_library():
         L.e3d_pursuer_guidance.argtypes = [vp] * 5
         L.e3d_pursuit_features.argtypes = [vp] * 3 + [C.c_int32] + [vp] * 3
         L.e3d_pursuit_features_host.argtypes = [vp, C.c_int32] + [vp] * 6 + [C.c_int32, vp, vp]
+        L.gauss_direction_map_host.argtypes = [C.c_int32, vp, vp]
+        L.e3d_direction_label_host.argtypes = [C.c_int32, vp, vp]
         _lib = L
     return _lib
 

@@ -13,7 +13,7 @@ import math
 
 KEY = "algo.bc_iterations"
 DEFAULT_BETA, DEFAULT_BETA_DECAY, DEFAULT_TARGET_BOUND = 1.0, 1.0, 0.999   # decay and bound: choices, not measurements
-LOG_KEYS = ("phase", "bc_beta", "bc_loss")   # of an imitation iteration, plus bc_action_mse (env_3d) or bc_accuracy (env_n2n)
+LOG_KEYS = ("phase", "bc_beta", "bc_loss")   # of an imitation iteration, plus bc_action_mse (env_3d; bc_angle_deg with gauss_squash: direction) or bc_accuracy (env_n2n)
 
 
 class ImitationOptions:

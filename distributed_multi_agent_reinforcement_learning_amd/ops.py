@@ -21,7 +21,7 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "ppo_loss_fwd_bwd_diag", "ppo_loss_prob_fwd_bwd_diag", "ppo_loss_gauss_fwd_bwd_diag", "ppo_loss_gauss_ex_fwd_bwd_diag",
            "ppo_loss_diag_workspace", "ppo_loss_gauss_diag_workspace", "ppo_ratio", "ppo_diag_rows_host", "fused_adam_workspace",
            "fused_adam_grid", "fused_adam_norm", "fused_adam_step", "fused_adam_advance_host", "fused_adam_rows_host", "bc_loss_workspace",
-           "bc_loss_gauss_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "mappo_ops_error_string")
+           "bc_loss_gauss_fwd_bwd", "bc_loss_gauss_ex_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "mappo_ops_error_string")
 
 _lib = None
 
@@ -128,6 +128,8 @@ def load_library():
         L.bc_loss_workspace.restype = i64
         L.bc_loss_gauss_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, f32, f32, i32, i32, vp, vp, vp, i64, i64,
                                             i64, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
+        L.bc_loss_gauss_ex_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, f32, f32, i32, i32, i32, vp, vp, vp, i64,
+                                               i64, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
         L.bc_loss_cat_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
         L.e3d_bc_select.argtypes = [i32, i32, vp, vp, i32, f64, vp, vp, i64, vp]
         L.n2n_bc_select.argtypes = [i32, i32, vp, vp, vp, vp, i64, vp]
@@ -723,7 +725,8 @@ def gauss_head_sample(feat, W, b, log_std, seed, counter, ticket, out, greedy=Fa
     return action, env_action, logp
 
 
-GAUSS_SQUASH = {"clip": 0, "tanh": 1}
+GAUSS_SQUASH = {"clip": 0, "tanh": 1, "direction": 2}
+DIRECTION_LATENT, DIRECTION_ENV = 4, 3   # csrc/direction_action.hpp: the latent action (u_x, u_y, u_z, s) and the environment's three commands
 
 
 def gauss_head_sample_ex(feat, W, b, log_std, seed, counter, ticket, out, greedy=False, log_std_min=-float("inf"), log_std_max=float("inf"),
@@ -732,7 +735,9 @@ def gauss_head_sample_ex(feat, W, b, log_std, seed, counter, ticket, out, greedy
     log_std: the (A,) vector (param mode) or a pair (W_ls (A, 128), b_ls (A,)) whose head on feat gives ls_raw per row (state mode,
     A <= 8); ls = clamp(ls_raw, log_std_min, log_std_max), u = mu + exp(ls) z with gauss_head_sample's noise and counter.
     out = (action fp32 (.., A) = u, env_action f64 (.., A) = clamp(u, -1, 1) (squash "clip") or tanh(u) (squash "tanh"),
-    logp fp32 (..) = Normal(mu, exp(ls)).log_prob(u).sum(-1), minus sum log(1 - tanh(u)^2) when squash is "tanh")."""
+    logp fp32 (..) = Normal(mu, exp(ls)).log_prob(u).sum(-1), minus sum log(1 - tanh(u)^2) when squash is "tanh").
+    squash "direction" (A = 4): u = (u_x, u_y, u_z, s), env_action f64 (.., 3) = the heading / pi and the
+    pitch / (pi / 2) of the vector and s, each clamped to [-1, 1]; logp is the Normal one of u."""
     state = isinstance(log_std, (tuple, list))
     A = W.shape[0]
     assert _head_ok(feat, W, b) and squash in GAUSS_SQUASH
@@ -748,7 +753,11 @@ def gauss_head_sample_ex(feat, W, b, log_std, seed, counter, ticket, out, greedy
     action, env_action, logp = out
     R = feat.numel() // HEAD_FEATURES
     assert action.dtype == torch.float32 and env_action.dtype == torch.float64 and logp.dtype == torch.float32
-    assert all(t.is_contiguous() for t in out) and action.numel() == R * A and env_action.numel() == R * A and logp.numel() == R
+    A_env = A
+    if squash == "direction":
+        assert A == DIRECTION_LATENT, "the direction head has four latent dimensions"
+        A_env = DIRECTION_ENV
+    assert all(t.is_contiguous() for t in out) and action.numel() == R * A and env_action.numel() == R * A_env and logp.numel() == R
     assert counter.dtype == torch.int64 and counter.numel() == 1 and ticket.dtype == torch.int32 and ticket.numel() == 1
     _check(L.gauss_head_sample_ex(R, A, HEAD_FEATURES, _ptr(feat), _ptr(W.detach().contiguous()), _ptr(b.detach().contiguous()), _ptr(W_ls),
                                   _ptr(b_ls), _ptr(ls), float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], int(seed), _ptr(counter),
@@ -1511,7 +1520,8 @@ def ppo_loss_gauss_ex(mu, ls_raw, action, values_now, logp_old, adv, active, val
     """ppo_loss_gauss with ls = clamp(ls_raw, log_std_min, log_std_max) and optional tanh squashing (csrc/gauss_policy.hpp
     k_ppo_loss_gauss_ex).  ls_raw: the (A,) vector (param mode) or a tensor of mu's shape (state mode, any strides over the first three
     dimensions, the last dense).  action holds the unsquashed samples u; with squash "tanh" the log-probability subtracts
-    sum log(1 - tanh(u)^2), which carries no gradient.  Gradients flow to mu, ls_raw (0 where ls_raw is outside the bounds) and
+    sum log(1 - tanh(u)^2), which carries no gradient; squash "direction" is "clip" on the four latent dimensions (the map to the
+    angles is the environment's: no Jacobian term).  Gradients flow to mu, ls_raw (0 where ls_raw is outside the bounds) and
     values_now.  diag: see ppo_loss."""
     return _PPOLossGaussEx.apply(mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef,
                                  use_value_clip, log_std_min, log_std_max, squash, diag)
@@ -1530,10 +1540,11 @@ class _BCLossGauss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mu, ls_raw, values_now, target, active, values_old, v_target, epsilon, use_value_clip, log_std_min, log_std_max, fit_std,
-                wrap0, sums=None):
+                wrap0, sums=None, metric="mse"):
         L = load_library()
         _need_gpu(mu, "bc_loss_gauss")
         A = mu.shape[-1]
+        assert metric in BC_GAUSS_METRIC and (metric == "mse" or A >= 3)
         d0, d1, d2 = mu.shape[:3]
         n = d0 * d1 * d2
         ts = [t.contiguous() for t in (active, v_target)]
@@ -1560,29 +1571,33 @@ class _BCLossGauss(torch.autograd.Function):
         g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
         ws = torch.empty(L.bc_loss_workspace(), dtype=torch.uint8, device=dev)
         ms, vs = mu.stride(), values_now.stride()
-        _check(L.bc_loss_gauss_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
-                                       float(log_std_min), float(log_std_max), int(bool(fit_std)), int(bool(wrap0)), _ptr(tgt), _ptr(ts[0]),
-                                       _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[1]), _ptr(asum), float(epsilon),
-                                       int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(ws), _stream()),
-               "bc_loss_gauss_fwd_bwd")
+        _check(L.bc_loss_gauss_ex_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
+                                          float(log_std_min), float(log_std_max), int(bool(fit_std)), int(bool(wrap0)), BC_GAUSS_METRIC[metric],
+                                          _ptr(tgt), _ptr(ts[0]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[1]), _ptr(asum),
+                                          float(epsilon), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(ws), _stream()),
+               "bc_loss_gauss_ex_fwd_bwd")
         ctx.save_for_backward(g_mu, g_ls, g_v)
         return losses[0], losses[1]
 
     @staticmethod
     def backward(ctx, ga, gc):
         g_mu, g_ls, g_v = ctx.saved_tensors
-        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 11
+        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 12
+
+
+BC_GAUSS_METRIC = {"mse": 0, "angle": 1}   # csrc/imitation.hpp: what bc_loss_gauss adds to sums[0]
 
 
 def bc_loss_gauss(mu, ls_raw, target, values_now, active, values_old, v_target, epsilon, use_value_clip=True, log_std_min=-float("inf"),
-                  log_std_max=float("inf"), fit_std=False, wrap0=False, sums=None):
+                  log_std_max=float("inf"), fit_std=False, wrap0=False, sums=None, metric="mse"):
     """-> (actor_loss, critic_loss) of the imitation phase on env_3d (algo.bc_iterations; csrc/imitation.hpp k_bc_loss_gauss): the masked
     mean of sum_a 0.5 d^2 exp(-2 ls) + (fit_std ? ls : 0) with d = target - mu (wrap0: dimension 0 modulo 2 into [-1, 1)) and
     ls = clamp(ls_raw, log_std_min, log_std_max), and ppo_loss_gauss's critic loss with the same bits.  Shapes and views as
     ppo_loss_gauss_ex; gradients flow to mu, ls_raw (exactly 0 without fit_std) and values_now.  sums: None, or a (2,) f64 device tensor to
-    which the call adds sum_rows active sum_a d^2 and sum active."""
+    which the call adds sum_rows active sum_a d^2 and sum active.  metric "angle" (the direction-vector head, A >= 3; wrap0 is ignored):
+    the first sum is sum_rows active angle(mu[:3], target[:3]) in radians instead (pi / 2 for a row whose mu[:3] is zero)."""
     return _BCLossGauss.apply(mu, ls_raw, values_now, target, active, values_old, v_target, epsilon, use_value_clip, log_std_min, log_std_max,
-                              fit_std, wrap0, sums)
+                              fit_std, wrap0, sums, metric)
 
 
 class _BCLossCat(torch.autograd.Function):
@@ -1631,14 +1646,16 @@ def bc_loss_cat(prob, label, values_now, active, values_old, v_target, epsilon, 
 def bc_select(guide, follow, action, a_star_row, squash="clip", bound=0.999):
     """one tick of an imitation rollout (csrc/imitation.hpp k_e3d_bc_select / k_n2n_bc_select): the scripted pursuers' actions `guide`
     ((N, P, 3) f64 on env_3d, (N, P) int32 on env_n2n) become the labels in a_star_row (buffer["a_star"][:, t]: fp32, row-strided; with
-    squash "tanh" atanh of the action clamped to +-bound) and replace `action` (the network's, st.env_action / st.a_n, in place) in the
+    squash "tanh" atanh of the action clamped to +-bound; with squash "direction" (N, P, 4): the unit vector of the commanded heading and
+    pitch, and the speed) and replace `action` (the network's, st.env_action / st.a_n, in place) in the
     environments whose `follow` (N,) uint8 is set.  One launch on the current stream, no host synchronisation."""
     L = load_library()
     _need_gpu(guide, "bc_select")
     N, P = guide.shape[:2]
     assert follow.dtype == torch.uint8 and follow.shape == (N,) and follow.is_contiguous() and follow.device == guide.device
     assert guide.is_contiguous() and action.is_contiguous() and action.shape == guide.shape and action.dtype == guide.dtype
-    assert a_star_row.dtype == torch.float32 and a_star_row.shape == guide.shape and (N == 1 or a_star_row[0].is_contiguous())
+    label_shape = (N, P, DIRECTION_LATENT) if (guide.dtype == torch.float64 and squash == "direction") else guide.shape
+    assert a_star_row.dtype == torch.float32 and a_star_row.shape == label_shape and (N == 1 or a_star_row[0].is_contiguous())
     stride = a_star_row.stride(0) if N > 1 else a_star_row[0].numel()
     if guide.dtype == torch.float64:
         assert guide.dim() == 3 and guide.shape[2] == 3 and squash in GAUSS_SQUASH

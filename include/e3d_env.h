@@ -174,6 +174,16 @@ int e3d_pursuit_features(const e3d_config *cfg, const e3d_state *st, const e3d_o
 int e3d_pursuit_features_host(const e3d_config *cfg, int32_t N, const double *p, const double *e, const double *target, const int32_t *time_step,
                               const float *pp_adj, const float *pe_adj, int32_t evader_obs, float *actor_feat, float *critic_feat);
 
+/* ---- algo.gauss_squash: direction -- the map of the direction-vector action head on the host (csrc/direction_action.hpp, DESIGN.md
+ * section 7h; specification: tests/direction_ref.py).  The device side is gauss_head_sample_ex / e3d_bc_select of mappo_ops.h ----
+ * gauss_direction_map_host: u [R][4] fp32, the policy's latent action (u_x, u_y, u_z, s) -> env_action [R][3] f64,
+ *   a0 = atan2(u_y, u_x) / pi, a1 = atan2(u_z, hypot(u_x, u_y)) / (pi / 2), a2 = s, each clamped to [-1, 1].
+ * e3d_direction_label_host: g [R][3] f64, guidance actions -> a_star [R][4] fp32, the label (cos gam cos phi, cos gam sin phi, sin gam, g2)
+ *   with phi = g0 pi, gam = g1 pi / 2.
+ * A null pointer: E3D_ERR_NULL; R < 0: E3D_ERR_BAD_CONFIG; R = 0 touches nothing. */
+int gauss_direction_map_host(int32_t R, const float *u, double *env_action);
+int e3d_direction_label_host(int32_t R, const double *g, float *a_star);
+
 /* The reference's evader: eva.e_f (eva.py:87-148) -- scipy's SLSQP (ftol 1e-6, <= 100 iterations, 2-point finite-difference
  * gradient) minimising obj_func (:212-240) over (heading, pitch, speed), started at the evader's state, bounded by the
  * environment's ang_lmt / v_lmt (:130-135) -- written as the command e_cmd [N][3] that e3d_env_tick consumes; zeros when the

@@ -374,6 +374,10 @@ int ppo_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu
  *   at i0 l_s0 + i1 l_s1 + i2 l_s2: per row (state mode; grad_log_std written per row at the same offsets) or, with l_s0 = l_s1 = l_s2 =
  *   0, one [A] vector (param mode; grad_log_std [A] summed through the f64 per-block partials).  The ls_raw gradient is 0 where ls_raw
  *   lies outside [log_std_min, log_std_max].  workspace >= ppo_loss_gauss_ex_workspace() bytes.
+ * squash 2, the direction-vector head (algo.gauss_squash: direction; csrc/direction_action.hpp): A must be 4,
+ *   u = (u_x, u_y, u_z, s); action [R][4] = u, env_action [R][3] f64 = (atan2(u_y, u_x) / pi, atan2(u_z, hypot(u_x, u_y)) / (pi / 2), s),
+ *   each clamped to [-1, 1]; logp is the plain Normal log-density of u over its four dimensions (the map belongs to the environment: no
+ *   Jacobian term).  All four Philox words of the row's one call are used.  ppo_loss_gauss_ex_fwd_bwd takes squash 2 as squash 0.
  */
 int gauss_head_sample_ex(int32_t R, int32_t A, int32_t H, const float *feat, const float *W, const float *b, const float *W_ls, const float *b_ls,
                          const float *log_std, float log_std_min, float log_std_max, int32_t squash, uint64_t seed, uint64_t *counter,
@@ -437,10 +441,15 @@ int ppo_diag_rows_host(int64_t n, const float *lr, const float *ratio, const flo
  * Both: losses[1], grad_values are the critic part of the PPO calls with the same bits; sums (NULL: skipped) [2] f64, to which the call
  * ADDS sum_i active sum_a d^2 (gauss) or the number of live rows whose argmax (lowest index on ties) is the label (cat), and sum active.
  * workspace >= bc_loss_workspace() bytes.  Deterministic (f64 per-block partials added in a fixed order, no atomics).
+ * bc_loss_gauss_ex_fwd_bwd: bc_loss_gauss_fwd_bwd with `metric`: 0 the call above, bit for bit (it forwards here); 1 (A >= 3, the
+ *   direction-vector head) sums[0] receives sum_i active angle_i instead, angle_i = atan2f(|mu x t|, mu . t) in fp32 radians between
+ *   mu[:3] and target[:3] of row i, pi / 2 where |mu[:3]|^2 is 0; wrap0 is then ignored.  Losses and gradients do not depend on metric.
  * e3d_bc_select / n2n_bc_select: one launch per rollout tick.  guide: the scripted pursuers' actions ([N][P][3] f64 / [N][P] int32);
  * the label of every row goes to a_star + n * row_stride (floats) + the row's offset -- (float)g, or with squash == 1
  * (float)atanh(clamp(g, -bound, bound)) evaluated in f64, or (float)k -- and the guide's action replaces the network's
- * (env_action / a_n) in the environments with follow[n] != 0.  Nothing else is written.
+ * (env_action / a_n) in the environments with follow[n] != 0.  Nothing else is written.  e3d_bc_select with squash == 2: the label has
+ * four floats per pursuer (row_stride >= 4 P), (cos gam cos phi, cos gam sin phi, sin gam, g2) with phi = g0 pi, gam = g1 pi / 2 in f64
+ * rounded to fp32; bound is ignored.
  */
 int64_t bc_loss_workspace(void);
 int bc_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1, int64_t m_s2,
@@ -448,6 +457,12 @@ int bc_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu,
                           int32_t fit_std, int32_t wrap0, const float *target, const float *active, const float *values_now, int64_t v_s0,
                           int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target, const float *active_sum, float epsilon,
                           int32_t use_value_clip, float *losses, float *grad_values, double *sums, void *workspace, void *stream);
+int bc_loss_gauss_ex_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                             int64_t m_s2, const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min,
+                             float log_std_max, int32_t fit_std, int32_t wrap0, int32_t metric, const float *target, const float *active,
+                             const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                             const float *active_sum, float epsilon, int32_t use_value_clip, float *losses, float *grad_values, double *sums,
+                             void *workspace, void *stream);
 int bc_loss_cat_fwd_bwd(int64_t n, int32_t A, const float *prob, float *grad_prob, int64_t d1, int64_t d2, int64_t p_s0, int64_t p_s1, int64_t p_s2,
                         const float *label, const float *active, const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2,
                         const float *values_old, const float *v_target, const float *active_sum, float epsilon, int32_t use_value_clip,
