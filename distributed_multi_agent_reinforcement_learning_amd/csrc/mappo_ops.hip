@@ -2460,6 +2460,7 @@ int launch_msgw3(const mo_msg_rel *rel, int R, int P, int E, const float *p, int
 
 #include "gauss_policy.hpp"   // the Gaussian policy head and loss of the env_3d trainer (reuses the helpers above)
 #include "imitation.hpp"      // algo.bc_iterations: the imitation losses and the per-tick label / override launch (after gauss_policy.hpp)
+#include "kickstart.hpp"      // algo.bc_coef: the PPO row and the imitation row of a sample in one loss launch (after imitation.hpp)
 #include "value_norm.hpp"     // algo.use_value_norm: GAE on denormalised values, the running statistics and the normalised targets
 #include "fused_adam.hpp"     // algo.minibatch_steps: the gradient clip and the Adam step of one mini-batch in two launches
 

@@ -160,6 +160,9 @@ class E3dMAPPO(ParticleMAPPO):
         self.latent_dim = latent_dim(self.gauss_squash, self.action_dim)   # what the heads emit and the buffer stores
         if self.gauss_squash == "direction":
             self.BC_METRIC = "bc_angle_deg"
+        if self.kick.on and self.action_dim != 3:
+            raise ValueError(f"algo.bc_coef > 0 needs env.action_dim 3 (heading, pitch, speed: what the scripted pursuers command), "
+                             f"got {self.action_dim}")
         if self.imitation.on and self.action_dim != 3:
             raise ValueError(f"algo.bc_iterations > 0 needs env.action_dim 3 (heading, pitch, speed: what the scripted pursuers command), "
                              f"got {self.action_dim}")
@@ -228,8 +231,8 @@ class E3dMAPPO(ParticleMAPPO):
                    active=z(N, T, P), v_n=z(N, T + 1, P))
         if self.value_norm is not None:
             buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
-        if self.imitation.on:
-            buf["a_star"] = z(N, T, P, self.latent_dim)   # the scripted pursuers' action of every row, in the policy's pre-squash space (algo.bc_iterations only)
+        if self.teacher:
+            buf["a_star"] = z(N, T, P, self.latent_dim)   # the scripted pursuers' action of every row, in the policy's pre-squash space (algo.bc_iterations / bc_coef only)
         return buf
 
     @torch.no_grad()
@@ -322,6 +325,14 @@ class E3dMAPPO(ParticleMAPPO):
         return ops.bc_loss_gauss(mu, ls_raw, buf["a_star"][n0:n1], *self._imitation_tail(buf, n0, n1, values, v_target), log_std_min=lo,
                                  log_std_max=hi, fit_std=self.imitation.fit_std, wrap0=self.bc_wrap0, sums=sums,
                                  metric="angle" if self.gauss_squash == "direction" else "mse")
+
+    def _kick_loss(self, buf, n0, n1, adv, v_target, coef, sums, dk):
+        mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True)
+        lo, hi = (self.log_std_min, self.log_std_max) if self.policy_ex else (-float("inf"), float("inf"))
+        a_n, *tail = self._loss_tail(buf, n0, n1, values, adv, v_target)
+        return ops.ppo_bc_loss_gauss(mu, ls_raw, a_n, buf["a_star"][n0:n1], *tail[:-1], coef, tail[-1], log_std_min=lo, log_std_max=hi,
+                                     squash=self.gauss_squash, fit_std=self.imitation.fit_std, wrap0=self.bc_wrap0,
+                                     metric="angle" if self.gauss_squash == "direction" else "mse", sums=sums, **dk)
 
     def policy_meta(self):
         """the "policy" entry of checkpoints and resume bundles: None in the default mode (param, clip, basic features), whose files

@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from .imitation import refuse_pursuit
+from .kickstart import refuse_pursuit as refuse_pursuit_kickstart
 from .model import build_actor_critic, pair_embeddings, pair_heads, sequence_forward_pair
 from .pe_env import status_or, status_text
 from .update_diag import UpdateDiag, update_diag_options
@@ -223,6 +224,7 @@ class MAPPO:
             raise ValueError("algo.target_kl is built for runtime.env n2n and e3d only; the pursuit update schedule is pinned to the "
                              "reference's (leave target_kl out; algo.update_diagnostics reports the KL)")
         refuse_pursuit(cfg)   # algo.bc_iterations: env_3d / env_n2n only
+        refuse_pursuit_kickstart(cfg)   # algo.bc_coef: likewise
         self.update_diagnostics, _ = update_diag_options(cfg)   # what the update did, from the loss launches
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
         self.epsilon, self.K_epochs, self.entropy_coef = a.epsilon, a.epochs, a.entropy_coef

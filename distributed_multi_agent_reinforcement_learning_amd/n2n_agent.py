@@ -120,8 +120,8 @@ class N2nMAPPO(ParticleMAPPO):
                    a_n=z(N, T, P), a_logprob_n=z(N, T, P), r=z(N, T, P), active=z(N, T, P), v_n=z(N, T + 1, P))
         if self.value_norm is not None:
             buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
-        if self.imitation.on:
-            buf["a_star"] = z(N, T, P)   # the scripted pursuers' action of every row (algo.bc_iterations only)
+        if self.teacher:
+            buf["a_star"] = z(N, T, P)   # the scripted pursuers' action of every row (algo.bc_iterations / bc_coef only)
         return buf
 
     @torch.no_grad()
@@ -205,6 +205,11 @@ class N2nMAPPO(ParticleMAPPO):
     def _imitation_loss(self, buf, n0, n1, v_target, sums):
         prob, values = self.sequence_forward(buf, n0, n1)
         return ops.bc_loss_cat(prob, buf["a_star"][n0:n1], *self._imitation_tail(buf, n0, n1, values, v_target), sums=sums)
+
+    def _kick_loss(self, buf, n0, n1, adv, v_target, coef, sums, dk):
+        prob, values = self.sequence_forward(buf, n0, n1)
+        a_n, *tail = self._loss_tail(buf, n0, n1, values, adv, v_target)
+        return ops.ppo_bc_loss_cat(prob, a_n, buf["a_star"][n0:n1], *tail[:-1], coef, tail[-1], sums=sums, **dk)
 
     def save_model(self, cwd, best=False):
         """cwd/n2n_actor.pth and n2n_critic.pth (best: n2n_actor_best.pth, n2n_critic_best.pth), the two state_dicts; with

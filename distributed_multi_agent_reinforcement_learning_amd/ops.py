@@ -21,7 +21,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "ppo_loss_fwd_bwd_diag", "ppo_loss_prob_fwd_bwd_diag", "ppo_loss_gauss_fwd_bwd_diag", "ppo_loss_gauss_ex_fwd_bwd_diag",
            "ppo_loss_diag_workspace", "ppo_loss_gauss_diag_workspace", "ppo_ratio", "ppo_diag_rows_host", "fused_adam_workspace",
            "fused_adam_grid", "fused_adam_norm", "fused_adam_step", "fused_adam_advance_host", "fused_adam_rows_host", "bc_loss_workspace",
-           "bc_loss_gauss_fwd_bwd", "bc_loss_gauss_ex_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "mappo_ops_error_string")
+           "bc_loss_gauss_fwd_bwd", "bc_loss_gauss_ex_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "ppo_bc_loss_workspace",
+           "ppo_bc_loss_gauss_fwd_bwd", "ppo_bc_loss_cat_fwd_bwd", "mappo_ops_error_string")
 
 _lib = None
 
@@ -131,6 +132,11 @@ def load_library():
         L.bc_loss_gauss_ex_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, f32, f32, i32, i32, i32, vp, vp, vp, i64,
                                                i64, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
         L.bc_loss_cat_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
+        L.ppo_bc_loss_workspace.restype = i64
+        L.ppo_bc_loss_gauss_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, f32, f32, i32, i32, i32, i32, vp, vp, vp,
+                                                vp, vp, vp, i64, i64, i64, vp, vp, vp, f32, f32, f32, i32, vp, vp, vp, vp, vp, vp]
+        L.ppo_bc_loss_cat_fwd_bwd.argtypes = [i64, i32, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, f32, f32, f32,
+                                              i32, vp, vp, vp, vp, vp, vp]
         L.e3d_bc_select.argtypes = [i32, i32, vp, vp, i32, f64, vp, vp, i64, vp]
         L.n2n_bc_select.argtypes = [i32, i32, vp, vp, vp, vp, i64, vp]
         L.sb_split_diag.argtypes = [i64, vp, vp, vp]
@@ -1641,6 +1647,126 @@ def bc_loss_cat(prob, label, values_now, active, values_old, v_target, epsilon, 
     as floats.  sums: None, or a (2,) f64 device tensor to which the call adds the number of live rows whose argmax (lowest index on
     ties) is the label, and sum active."""
     return _BCLossCat.apply(prob, values_now, label, active, values_old, v_target, epsilon, use_value_clip, sums)
+
+
+KICK_SUMS = 3   # csrc/kickstart.hpp: the imitation metric's sum, the live-row count, the sum of the unweighted imitation loss over live rows
+
+
+def _kick_args_ok(sums, diag, dev):
+    assert sums is None or (sums.dtype == torch.float64 and sums.shape == (KICK_SUMS,) and sums.is_contiguous() and sums.device == dev)
+    assert diag is None or (diag.dtype == torch.float64 and diag.shape == (PPO_DIAG_SUMS,) and diag.is_contiguous() and diag.device == dev)
+
+
+class _PPOBCLossGauss(torch.autograd.Function):
+    """ppo_bc_loss_gauss: ppo_bc_loss_gauss_fwd_bwd writes the losses and the gradients w.r.t. mu, ls_raw (per row or the vector) and
+    the values in one pass."""
+
+    @staticmethod
+    def forward(ctx, mu, ls_raw, values_now, action, target, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef,
+                use_value_clip, log_std_min, log_std_max, squash, fit_std, wrap0, metric, sums=None, diag=None):
+        L = load_library()
+        _need_gpu(mu, "ppo_bc_loss_gauss")
+        A = mu.shape[-1]
+        assert metric in BC_GAUSS_METRIC and (metric == "mse" or A >= 3) and squash in GAUSS_SQUASH
+        d0, d1, d2 = mu.shape[:3]
+        n = d0 * d1 * d2
+        ts = [t.contiguous() for t in (logp_old, adv, active, v_target)]
+        act, tgt = action.contiguous(), target.contiguous()
+        vo = values_old.contiguous() if values_old is not None else None
+        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == mu.shape[:3]
+        assert all(t.shape == mu.shape and t.dtype == torch.float32 for t in (act, tgt)) and mu.stride(3) == 1
+        dev = mu.device
+        _kick_args_ok(sums, diag, dev)
+        ls = ls_raw.detach()
+        if ls.dim() == 1:            # param mode: one vector, stride 0 over the rows
+            assert ls.shape == (A,)
+            ls = ls.contiguous()
+            g_ls = torch.empty(A, dtype=torch.float32, device=dev)
+            lstr = (0, 0, 0)
+        else:                        # state mode: per row, any strides over the first three dimensions (a time-major view)
+            assert ls.shape == mu.shape and ls.stride(3) == 1 and ls.dtype == torch.float32
+            g_ls = torch.empty_strided(ls.shape, ls.stride(), dtype=torch.float32, device=dev)
+            lstr = ls.stride()[:3]
+            assert any(lstr), "a per-row ls_raw needs a nonzero row stride"
+        asum = active.sum().reshape(1)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)
+        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.ppo_bc_loss_workspace(), dtype=torch.uint8, device=dev)
+        ms, vs = mu.stride(), values_now.stride()
+        _check(L.ppo_bc_loss_gauss_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
+                                           float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], int(bool(fit_std)), int(bool(wrap0)),
+                                           BC_GAUSS_METRIC[metric], _ptr(act), _ptr(tgt), _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(values_now),
+                                           vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon), float(entropy_coef), float(coef),
+                                           int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(diag), _ptr(ws), _stream()),
+               "ppo_bc_loss_gauss_fwd_bwd")
+        ctx.save_for_backward(g_mu, g_ls, g_v)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, ga, gc):
+        g_mu, g_ls, g_v = ctx.saved_tensors
+        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 19
+
+
+def ppo_bc_loss_gauss(mu, ls_raw, action, target, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef,
+                      use_value_clip=True, log_std_min=-float("inf"), log_std_max=float("inf"), squash="clip", fit_std=False, wrap0=False,
+                      metric="mse", sums=None, diag=None):
+    """-> (actor_loss, critic_loss) of teacher-regularised PPO on env_3d (algo.bc_coef; csrc/kickstart.hpp k_ppo_bc_loss_gauss): the
+    actor loss of ppo_loss_gauss_ex on `action` plus coef times the actor loss of bc_loss_gauss on `target`, and their gradients, from
+    one pass over mu / ls_raw / the values; the critic loss and its gradient carry the bits of ppo_loss_gauss_ex.  Shapes, views and the
+    policy arguments as ppo_loss_gauss_ex; fit_std, wrap0 and metric as bc_loss_gauss; coef finite and >= 0.  sums: None, or a (3,) f64
+    device tensor to which the call adds bc_loss_gauss's two sums and sum_rows active la_bc (the unweighted imitation loss); diag: see
+    ppo_loss (with a per-row ls_raw the diagnostics exist at A = 3 and 4, the widths a policy of this feature has)."""
+    return _PPOBCLossGauss.apply(mu, ls_raw, values_now, action, target, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef,
+                                 coef, use_value_clip, log_std_min, log_std_max, squash, fit_std, wrap0, metric, sums, diag)
+
+
+class _PPOBCLossCat(torch.autograd.Function):
+    """ppo_bc_loss_cat: ppo_bc_loss_cat_fwd_bwd writes the losses and the gradients w.r.t. prob and the values in one pass."""
+
+    @staticmethod
+    def forward(ctx, prob, values_now, action, label, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef, use_value_clip,
+                sums=None, diag=None):
+        L = load_library()
+        _need_gpu(prob, "ppo_bc_loss_cat")
+        A = prob.shape[-1]
+        d0, d1, d2 = prob.shape[:3]
+        n = d0 * d1 * d2
+        ts = [t.contiguous() for t in (action, label, logp_old, adv, active, v_target)]
+        vo = values_old.contiguous() if values_old is not None else None
+        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == prob.shape[:3]
+        assert prob.stride(3) == 1 and prob.dtype == torch.float32 and 1 <= A <= 16
+        dev = prob.device
+        _kick_args_ok(sums, diag, dev)
+        asum = active.sum().reshape(1)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        g_prob = torch.empty_strided(prob.shape, prob.stride(), dtype=torch.float32, device=dev)    # the layout of prob (a time-major view)
+        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.ppo_bc_loss_workspace(), dtype=torch.uint8, device=dev)
+        ps, vs = prob.stride(), values_now.stride()
+        _check(L.ppo_bc_loss_cat_fwd_bwd(n, A, _ptr(prob), _ptr(g_prob), d1, d2, ps[0], ps[1], ps[2], _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]),
+                                         _ptr(ts[3]), _ptr(ts[4]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[5]), _ptr(asum),
+                                         float(epsilon), float(entropy_coef), float(coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v),
+                                         _ptr(sums), _ptr(diag), _ptr(ws), _stream()), "ppo_bc_loss_cat_fwd_bwd")
+        ctx.save_for_backward(g_prob, g_v)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, ga, gc):
+        g_prob, g_v = ctx.saved_tensors
+        return (g_prob * ga, g_v * gc) + (None,) * 13
+
+
+def ppo_bc_loss_cat(prob, action, label, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef,
+                    use_value_clip=True, sums=None, diag=None):
+    """-> (actor_loss, critic_loss) of teacher-regularised PPO on env_n2n (algo.bc_coef; csrc/kickstart.hpp k_ppo_bc_loss_cat): the actor
+    loss of ppo_loss_prob on `action` plus coef times the actor loss of bc_loss_cat on `label`, and the gradient with respect to prob
+    through the one normalisation both share; the critic loss and its gradient carry the bits of ppo_loss_prob.  Shapes and views as
+    ppo_loss_prob; coef finite and >= 0.  sums: None, or a (3,) f64 device tensor to which the call adds bc_loss_cat's two sums (label
+    hits, live rows) and sum_rows active (-log p[label]); diag: see ppo_loss."""
+    return _PPOBCLossCat.apply(prob, values_now, action, label, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef,
+                               use_value_clip, sums, diag)
 
 
 def bc_select(guide, follow, action, a_star_row, squash="clip", bound=0.999):

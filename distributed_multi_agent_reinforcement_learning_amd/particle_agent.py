@@ -9,6 +9,7 @@ import torch
 
 from . import guidance as gd
 from . import imitation as im
+from . import kickstart as ks
 from . import ops
 from . import value_norm as vnorm
 from .minibatch_steps import MAX_GRAD_NORM, minibatch_steps_options
@@ -47,11 +48,20 @@ class BcSums:
         self.allreduce = None      # the trainer's allreduce_sum_: the two sums over ranks, in place
 
 
+class KickSums:
+    """the device side of the imitation term of teacher-regularised PPO (algo.bc_coef): the three sums the fused loss launches of one
+    train(kick=...) call add to"""
+
+    def __init__(self, device):
+        self.sums = torch.zeros(ks.KICK_SUMS, dtype=torch.float64, device=device)
+        self.allreduce = None      # the trainer's allreduce_sum_: the three sums over ranks, in place
+
+
 class ParticleMAPPO:
     """rollout bookkeeping (explore_env) and PPO update (train) of a policy on a particle environment.  A subclass names its
     environment (ENV) and provides _options (its own keys, before the device check), _build (actor, critic, ac_parameters), _rollout
-    (the storage of _state), _buffer_dims, new_buffer, run_episode, _bootstrap_value, _minibatch_loss, and for algo.bc_iterations
-    _imitation_loss, BC_METRIC and bc_metric."""
+    (the storage of _state), _buffer_dims, new_buffer, run_episode, _bootstrap_value, _minibatch_loss, for algo.bc_iterations
+    _imitation_loss, BC_METRIC and bc_metric, and for algo.bc_coef _kick_loss."""
 
     ENV = None        # "env_3d (runtime.env: e3d)": how the messages name the environment
     obs_norm = None   # algo.use_obs_norm (env_3d only): the agent's ObsNorm
@@ -67,6 +77,8 @@ class ParticleMAPPO:
         self.minibatch_steps = minibatch_steps_options(cfg)   # one clip + Adam step per mini-batch, fused
         self.guidance = gd.guidance_options(cfg)   # the scripted pursuers of run_episode(policy="guidance")
         self.imitation = im.imitation_options(cfg)   # algo.bc_iterations: the imitation warm start in front of PPO
+        self.kick = ks.kickstart_options(cfg)   # algo.bc_coef: the imitation term stays in the PPO loss, decaying
+        self.teacher = self.imitation.on or self.kick.on   # the rollout can be labelled: the buffer has the a_star field
         self._options(cfg)
         self.batch_size, self.mini_batch_size = int(batch_size), int(mini_batch_size)
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
@@ -88,6 +100,8 @@ class ParticleMAPPO:
         self.diag = UpdateDiag(self.device) if self.update_diagnostics else None
         self.bc = BcSums(self.device) if self.imitation.on else None
         self.last_bc = None   # algo.bc_iterations: (the extra sum, the live rows) of the last train(imitation=True) call, over ranks
+        self.kick_sums = KickSums(self.device) if self.kick.on else None
+        self.last_kick = None   # algo.bc_coef: (the metric's sum, the live rows, the sum of the unweighted term) of the last train(kick=) call
         self.last_update_diag = None   # algo.update_diagnostics: the dict of the last train() call
         rt = cfg.get("runtime", {})
         self.sample_seed = int(rt.get("seed", 0))
@@ -143,10 +157,10 @@ class ParticleMAPPO:
         return mean_r, self.buffer, dims[0] * dims[1], dict(capture_rate=cap, episode_length=mlen)
 
     def explore_expert(self, env, beta):
-        """explore_env with the teacher in the loop (algo.bc_iterations): every tick also takes env.guidance_actions() and one
+        """explore_env with the teacher in the loop (algo.bc_iterations; algo.bc_coef calls it with beta 0: labels only): every tick also takes env.guidance_actions() and one
         ops.bc_select launch before the environment steps -- the scripted pursuers' actions become the labels buffer["a_star"][:, t] of
         every environment and the executed actions of environments 0 .. round(beta N) - 1; everything else is run_episode's"""
-        if not self.imitation.on:
+        if not self.teacher:
             raise ValueError(f"explore_expert needs {im.KEY} > 0 (the buffer has no a_star field otherwise)")
         follow = torch.zeros(env.num_envs, dtype=torch.uint8, device=self.device)
         follow[:im.follow_count(beta, env.num_envs)] = 1
@@ -167,7 +181,7 @@ class ParticleMAPPO:
         return (values, buf["active"][n0:n1], buf["v_n"][n0:n1, :-1] if self.use_value_clip else None, v_target[n0:n1], self.epsilon,
                 self.use_value_clip)
 
-    def train(self, buf, total_steps, imitation=False):
+    def train(self, buf, total_steps, imitation=False, kick=None):
         """GAE + advantage normalisation over all rows (ops.gae_advnorm), then sequential mini-batches of whole episodes (forward and
         loss: the subclass's _minibatch_loss), the gradient clipped to MAX_GRAD_NORM after each (as MAPPO.train).  With
         algo.minibatch_steps every mini-batch instead starts from a zeroed bucket and ends with the gradient SUM over ranks and one
@@ -175,6 +189,9 @@ class ParticleMAPPO:
         imitation (algo.bc_iterations): the mini-batch loss is the subclass's _imitation_loss on buf["a_star"]; the update diagnostics,
         the KL target and the learning-rate decay are skipped, everything else is unchanged; the two sums of the imitation metric go
         over ranks and arrive in the call's one host read (last_bc).
+        kick (algo.bc_coef): lambda > 0 -- a PPO update in every respect (diagnostics, KL target, learning-rate decay) whose mini-batch
+        loss is the subclass's _kick_loss, the PPO loss plus lambda times the imitation loss on buf["a_star"] from one launch; its three
+        sums go over ranks and arrive in the same host read (last_kick).
         Returns (critic loss, actor loss) averaged over the mini-batches."""
         N = buf["r"].shape[0]
         with torch.no_grad():
@@ -190,8 +207,11 @@ class ParticleMAPPO:
         obj_c = obj_a = 0.0
         k = 0
         diag = None if imitation else self.diag   # algo.update_diagnostics: every loss call adds its eight sums (None: the plain calls)
+        kick = kick if (kick and not imitation) else None
         if imitation:
             self.bc.sums.zero_()
+        if kick is not None:
+            self.kick_sums.sums.zero_()
         if diag is not None:
             diag.begin()
         dk = {} if diag is None else {"diag": diag.sums}
@@ -201,6 +221,8 @@ class ParticleMAPPO:
                 self.grad_bucket.zero()
             if imitation:
                 la, lc = self._imitation_loss(buf, n0, n1, v_target, self.bc.sums)
+            elif kick is not None:
+                la, lc = self._kick_loss(buf, n0, n1, adv, v_target, kick, self.kick_sums.sums, dk)
             else:
                 la, lc = self._minibatch_loss(buf, n0, n1, adv, v_target, dk)
             (la + lc).backward()
@@ -226,7 +248,21 @@ class ParticleMAPPO:
             obj_c, obj_a, *extra = head
             self.last_bc = (s, c)
         elif diag is not None:   # one read for the two losses, the eight sums (all-reduced over ranks) and the gradient norm
-            (obj_c, obj_a, *extra), self.last_update_diag = diag.read(obj_c, obj_a, *extra)
+            tail = ()
+            if kick is not None:   # the three sums of the imitation term ride behind the skipped count
+                if self.kick_sums.allreduce is not None:
+                    self.kick_sums.allreduce(self.kick_sums.sums)
+                tail = tuple(self.kick_sums.sums)
+            (obj_c, obj_a, *extra), self.last_update_diag = diag.read(obj_c, obj_a, *extra, *tail)
+            if tail:
+                *extra, s, c, b = extra
+                self.last_kick = (s, c, b)
+        elif kick is not None:   # one read for the two losses, the skipped count and the three sums (all-reduced over ranks)
+            if self.kick_sums.allreduce is not None:
+                self.kick_sums.allreduce(self.kick_sums.sums)
+            *head, s, c, b = torch.cat((torch.stack((obj_c, obj_a, *(e.double() for e in extra))), self.kick_sums.sums)).tolist()
+            obj_c, obj_a, *extra = head
+            self.last_kick = (s, c, b)
         elif opt is not None:
             obj_c, obj_a, *extra = torch.stack((obj_c, obj_a, *extra)).tolist()
         if opt is not None:
@@ -281,9 +317,9 @@ class ParticleTrainer(ParticleRunState):
         self.agent.sample_rank = self.rank
         self.bucket = self.agent.grad_bucket or GradBucket(self.agent.ac_parameters)   # (algo.minibatch_steps: the agent's own)
         self.agent.grad_bucket = self.bucket
-        for part in (self.agent.value_norm, self.agent.obs_norm, self.agent.diag, self.agent.bc):
+        for part in (self.agent.value_norm, self.agent.obs_norm, self.agent.diag, self.agent.bc, self.agent.kick_sums):
             if part is not None:   # (S1, S2, c) / the (2, 33) feature sums of a rollout / the eight diagnostic sums / the two imitation
-                part.allreduce = allreduce_sum_   # sums over ranks; without a process group a no-op
+                part.allreduce = allreduce_sum_   # sums / the three of algo.bc_coef over ranks; without a process group a no-op
         self.last_epoch_diags = []
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.num_eval_envs, self.eval_every = int(num_eval_envs), int(eval_every)
@@ -303,11 +339,14 @@ class ParticleTrainer(ParticleRunState):
             agent.set_lr(bc.lr)   # constant over the phase
         elif bc.on and self.iteration == bc.iterations:
             agent.reset_optimizer(self.total_steps)   # the first PPO iteration starts from fresh moments, on the schedule
+        lam = 0.0 if imitating else agent.kick.coef_at(self.iteration - bc.iterations)   # algo.bc_coef: lambda_j of this PPO iteration
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
         if imitating:
             beta = bc.beta_at(self.iteration)
             mean_r, buf, steps, stats = agent.explore_expert(self.env, beta)
+        elif lam > 0.0:   # every tick labelled, no environment follows the teacher: the data stays on-policy
+            mean_r, buf, steps, stats = agent.explore_expert(self.env, 0.0)
         else:
             mean_r, buf, steps, stats = agent.explore_env(self.env)
         ev[1].record()
@@ -316,7 +355,7 @@ class ParticleTrainer(ParticleRunState):
         per_minibatch, opt_steps, skipped = agent.minibatch_steps, 0, 0
         for _ in range(int(cfg.algo.epochs)):
             with torch.enable_grad():
-                obj_c, obj_a = agent.train(buf, self.total_steps, **({"imitation": True} if imitating else {}))
+                obj_c, obj_a = agent.train(buf, self.total_steps, **({"imitation": True} if imitating else {"kick": lam} if lam > 0.0 else {}))
             over = False
             if agent.diag is not None and not imitating:
                 self.last_epoch_diags.append(agent.last_update_diag)
@@ -344,6 +383,9 @@ class ParticleTrainer(ParticleRunState):
             log.update(phase="imitation", bc_beta=beta, bc_loss=obj_a, **{agent.BC_METRIC: agent.bc_metric(*agent.last_bc)})
         elif agent.diag is not None:   # of the last train() call, like the two losses
             log.update({k: agent.last_update_diag[k] for k in LOG_KEYS}, epochs_run=epochs_run)
+        if lam > 0.0:   # of the last train() call: lambda_j, the unweighted imitation term and its metric
+            s, c, b = agent.last_kick
+            log.update(bc_coef=lam, bc_aux_loss=b / c if c else float("nan"), **{agent.BC_METRIC: agent.bc_metric(s, c)})
         if per_minibatch:
             log.update(optimizer_steps=opt_steps, skipped_steps=skipped)
         if self.eval_every and self.iteration % self.eval_every == 0 and self.rank == 0:

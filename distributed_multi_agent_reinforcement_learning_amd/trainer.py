@@ -18,6 +18,7 @@ from . import ops
 from .evaluator import EvaluatorProc, draw_learning_curve
 from .mappo import MAPPO
 from .imitation import check_entry as check_imitation_entry
+from .kickstart import check_entry as check_kickstart_entry
 from .minibatch_steps import check_entry as check_minibatch_steps_entry
 from .pursuit_env import Pursuit_Env
 from .obs_norm import check_entry as check_obs_norm_entry
@@ -255,7 +256,8 @@ class ParticleRunState:
     algo.use_value_norm the agent's value-normaliser state (the "value_norm" entry), with algo.use_obs_norm (env_3d) the agent's
     feature-normaliser state (the "obs_norm" entry; its slots are empty between iterations and are not saved).  With
     algo.minibatch_steps the bundle says so ("minibatch_steps": True) and its "optimizer" is FusedAdam's state.  With algo.bc_iterations
-    > 0 the bundle records it ("bc_iterations"): the phase of the next iteration follows from it and the saved iteration count."""
+    > 0 the bundle records it ("bc_iterations"): the phase of the next iteration follows from it and the saved iteration count; with
+    algo.bc_coef > 0 its "bc_coef" entry is (bc_coef, bc_coef_decay, bc_coef_iterations), from which lambda of every iteration follows."""
 
     def save_resume(self, path):
         agent, ev = self.agent, self.eval_env
@@ -279,6 +281,8 @@ class ParticleRunState:
             bundle["minibatch_steps"] = True
         if agent.imitation.on:            # algo.bc_iterations: the phase of an iteration follows from it and `iteration`; off: no entry
             bundle["bc_iterations"] = agent.imitation.iterations
+        if agent.kick.on:                 # algo.bc_coef: lambda of an iteration follows from the three values; off: no entry
+            bundle["bc_coef"] = agent.kick.entry()
         torch.save(bundle, path)
 
     def load_resume(self, path):
@@ -296,6 +300,7 @@ class ParticleRunState:
         check_obs_norm_entry(agent, b.get("obs_norm"), f"resume bundle {path}")
         check_minibatch_steps_entry(agent, b.get("minibatch_steps"), f"resume bundle {path}")
         check_imitation_entry(agent, b.get("bc_iterations"), f"resume bundle {path}")
+        check_kickstart_entry(agent, b.get("bc_coef"), f"resume bundle {path}")
         agent.actor.load_state_dict(b["actor"])
         agent.critic.load_state_dict(b["critic"])
         agent.ac_optimizer.load_state_dict(b["optimizer"])

@@ -472,6 +472,36 @@ int e3d_bc_select(int32_t N, int32_t P, const double *guide, const uint8_t *foll
 int n2n_bc_select(int32_t N, int32_t P, const int32_t *guide, const uint8_t *follow, int32_t *a_n, float *a_star, int64_t row_stride, void *stream);
 
 /*
+ * Teacher-regularised PPO of the env_3d / env_n2n trainers (algo.bc_coef; csrc/kickstart.hpp; specification: tests/kickstart_ref.py).
+ * ppo_bc_loss_gauss_fwd_bwd: the row of ppo_loss_gauss_ex_fwd_bwd (squash, the bounds, the ls_raw modes and views as there) and the row
+ * of bc_loss_gauss_ex_fwd_bwd (target, fit_std, wrap0, metric as there) on mu, ls and 1 / sigma^2 loaded once:
+ *   losses[0] = sum_i active la_ppo / sum active + coef sum_i active la_bc / sum active, losses[1] and grad_values: the critic part of
+ *   ppo_loss_gauss_ex_fwd_bwd with the same bits; grad_mu = grad_mu_ppo + coef grad_mu_bc, grad_log_std = grad_ls_ppo + coef grad_ls_bc
+ *   (per row in state mode, [A] in param mode; the imitation part exactly 0 without fit_std, the whole 0 outside the closed bounds).
+ * ppo_bc_loss_cat_fwd_bwd: the row of ppo_loss_prob_fwd_bwd and the row of bc_loss_cat_fwd_bwd on one normalised row of prob;
+ *   grad_prob is the sum of the two gradients through the shared normalisation; the critic part has ppo_loss_prob_fwd_bwd's bits.
+ * Both: coef finite and >= 0; sums (NULL: skipped) [3] f64, to which the call ADDS the imitation call's metric sum (sum_i active sum_a
+ * d*^2, or with metric 1 sum_i active angle_i; the label hits), sum active, and sum_i active la_bc (the unweighted imitation loss);
+ * diag (NULL: skipped; gauss with a per-row ls_raw: A 3 or 4 only, the widths a policy of this feature has) [8] f64, to which the call
+ * ADDS the PPO row's update diagnostics exactly as the _diag PPO calls do; losses and
+ * gradients do not depend on sums or diag.  workspace >= ppo_bc_loss_workspace() bytes.  Two launches; deterministic (f64 per-block
+ * partials added in a fixed order, no atomics).  A bad argument returns MO_ERR_BAD_ARG before anything is launched.
+ */
+int64_t ppo_bc_loss_workspace(void);
+int ppo_bc_loss_gauss_fwd_bwd(int64_t n, int32_t A, const float *mu, float *grad_mu, int64_t d1, int64_t d2, int64_t m_s0, int64_t m_s1,
+                              int64_t m_s2, const float *ls_raw, float *grad_log_std, int64_t l_s0, int64_t l_s1, int64_t l_s2, float log_std_min,
+                              float log_std_max, int32_t squash, int32_t fit_std, int32_t wrap0, int32_t metric, const float *action,
+                              const float *target, const float *logp_old, const float *adv, const float *active, const float *values_now,
+                              int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target, const float *active_sum,
+                              float epsilon, float entropy_coef, float coef, int32_t use_value_clip, float *losses, float *grad_values, double *sums,
+                              double *diag, void *workspace, void *stream);
+int ppo_bc_loss_cat_fwd_bwd(int64_t n, int32_t A, const float *prob, float *grad_prob, int64_t d1, int64_t d2, int64_t p_s0, int64_t p_s1,
+                            int64_t p_s2, const float *action, const float *label, const float *logp_old, const float *adv, const float *active,
+                            const float *values_now, int64_t v_s0, int64_t v_s1, int64_t v_s2, const float *values_old, const float *v_target,
+                            const float *active_sum, float epsilon, float entropy_coef, float coef, int32_t use_value_clip, float *losses,
+                            float *grad_values, double *sums, double *diag, void *workspace, void *stream);
+
+/*
  * Records one rollout tick into the replay buffer (MAPPO.run_episode's minibuffer.store_transition,
  * DHGN/mappo_parallel.py:783-805, for N environments at once): for every item, row n of the dense [N][row_bytes] source
  * goes to dst + n * dst_row_stride (slot [n, t] of an (N, T, ...) buffer tensor); i32_to_f32 converts int32 actions to
