@@ -6,6 +6,7 @@
 
 #include "mappo_ops.h"
 #include "sb_gemm.hpp"
+#include "sb_encoder_tail.hpp"
 #include "sb_gru_seq.hpp"
 
 extern "C" {
@@ -84,6 +85,16 @@ int sb_gemm_masked_bits(int64_t R, int32_t N, int32_t K, const float *X, int64_t
 int sb_gemm_n128(int64_t R, int32_t K, const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias, int32_t relu, const float *addend,
                  int64_t lda, float *Y, int64_t ldy, void *stream) {
     return sb_gemm(R, 128, K, X, ldx, W, ldw, bias, relu, addend, lda, Y, ldy, stream);
+}
+
+int sb_encoder_tail(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *Ws, int64_t ldw, const float *C,
+                    int64_t ldc, float *Y, int64_t ldy, void *stream) {
+    if (Rs < 0 || !m3 || !w_agg || !b_agg || !Ws || !C || !Y || ldx < 384 || ldw < 384 || ldc < 128 || ldy < 128) return MO_ERR_BAD_ARG;
+    if ((ldx & 3) || (ldw & 3) || (ldc & 3) || (ldy & 3) || ((uintptr_t)m3 & 15) || ((uintptr_t)w_agg & 15) || ((uintptr_t)b_agg & 15) || ((uintptr_t)Ws & 15) ||
+        ((uintptr_t)C & 15) || ((uintptr_t)Y & 15))
+        return MO_ERR_BAD_ARG;
+    if (Rs == 0) return 0;
+    return launch_sb_encoder_tail(Rs, m3, ldx, w_agg, b_agg, Ws, ldw, C, ldc, Y, ldy, (hipStream_t)stream);
 }
 
 int gru_seq_split_fwd_multi(int32_t n_nets, const mo_gru_seq_net *nets, int32_t T, int32_t B, int32_t H, int32_t gi_agents, void *stream) {

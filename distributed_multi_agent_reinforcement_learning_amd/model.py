@@ -156,21 +156,27 @@ class DHGN(nn.Module):
         m3 = ops.msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
                                o_kvalid, q_div, pos=(Ws[:, :ind], self.semantic_layer.bias, h0) if fused_pos else None, e_ref=e_ref)   # (2, R, P, 3, E)
         agg0 = self.AGG_layers["AGG_vertex_0"]
-        m3_2d = m3.view(-1, E)
-        if ops.split_linear_ok(m3_2d, agg0.weight):     # the rollout's Linear layers on the split-bf16 kernel (ops.CELL_MODE)
-            emb = ops.split_linear(m3_2d, agg0.weight, agg0.bias, relu=True).view(m3.shape)
+        m3_s, Wse = m3.view(2 * R * P, 3 * E), Ws[:, ind:]
+        if fused_pos and ops.encoder_tail_ok(m3_s, agg0.weight, agg0.bias, Wse, h0_2d):
+            # the AGG layer and the embedding part of the semantic layer as ONE launch: the (2 R P, 3 E) embedding never reaches
+            # memory (ops.ENCODER_TAIL; the same bits as the two launches below)
+            ops.encoder_tail(m3_s, agg0.weight, agg0.bias, Wse, h0_2d)
         else:
-            emb = ops.linear(m3, agg0.weight, agg0.bias, relu=True)
-        if not fused_pos:
-            torch.addmm(self.semantic_layer.bias, p.reshape(R * P, ind), Ws[:, :ind].t(), out=h0_2d[:R * P])
-            h0_2d[R * P:].copy_(h0_2d[:R * P])
-        emb_2d, Wse = emb.view(2 * R * P, 3 * E), Ws[:, ind:]
-        if ops.split_linear_ok(emb_2d, Wse, h0_2d, h0_2d):
-            ops.split_linear(emb_2d, Wse, None, False, out=h0_2d, addend=h0_2d)
-        elif d:   # h0 is the right half of the first hop's operand: accumulate into it in place (beta = 1, strided output)
-            ops.gemm_nt(emb_2d, Wse, None, False, out=h0_2d, addend=h0_2d)
-        else:
-            h0_2d.addmm_(emb_2d, Wse.t())
+            m3_2d = m3.view(-1, E)
+            if ops.split_linear_ok(m3_2d, agg0.weight):     # the rollout's Linear layers on the split-bf16 kernel (ops.CELL_MODE)
+                emb = ops.split_linear(m3_2d, agg0.weight, agg0.bias, relu=True).view(m3.shape)
+            else:
+                emb = ops.linear(m3, agg0.weight, agg0.bias, relu=True)
+            if not fused_pos:
+                torch.addmm(self.semantic_layer.bias, p.reshape(R * P, ind), Ws[:, :ind].t(), out=h0_2d[:R * P])
+                h0_2d[R * P:].copy_(h0_2d[:R * P])
+            emb_2d = emb.view(2 * R * P, 3 * E)
+            if ops.split_linear_ok(emb_2d, Wse, h0_2d, h0_2d):
+                ops.split_linear(emb_2d, Wse, None, False, out=h0_2d, addend=h0_2d)
+            elif d:   # h0 is the right half of the first hop's operand: accumulate into it in place (beta = 1, strided output)
+                ops.gemm_nt(emb_2d, Wse, None, False, out=h0_2d, addend=h0_2d)
+            else:
+                h0_2d.addmm_(emb_2d, Wse.t())
         if d == 0:
             return h0
         h = h0

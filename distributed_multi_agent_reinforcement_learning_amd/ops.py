@@ -15,7 +15,7 @@ ADJ_TENSOR, ADJ_ONES, ADJ_VALID, ADJ_BITS = 0, 1, 2, 3
 EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_msg_agg_bwd_workspace", "dhgn_msg_agg_ones_sorted_ok", "dhgn_msg_agg_ones_sorted_fwd",
            "dhgn_msg_agg_ones_sorted_bwd", "dhgn_msg_agg_ones_sorted_workspace", "gae_advnorm", "gae_advnorm_workspace", "categorical_sample",
            "categorical_sample_counter",
-           "gru_gates_fwd", "gru_gates_bwd", "gru_cell_fwd", "gru_cell_fwd_multi", "gru_cell_split_fwd_multi", "sb_gemm_n128", "sb_gemm", "gru_seq_fwd", "gru_seq_fwd_multi", "gru_seq_split_fwd_multi", "gru_seq_split_bwd_multi", "gru_seq_save_elems", "gru_seq_bwd", "gru_seq_bwd_multi", "gru_seq_bwd_workspace", "wgrad_tn", "wgrad_tn_workspace", "wgrad_split_tn", "wgrad_split_tn2", "wgrad_split_workspace", "rollout_record", "ppo_loss_fwd_bwd", "ppo_loss_prob_fwd_bwd", "ppo_loss_workspace",
+           "gru_gates_fwd", "gru_gates_bwd", "gru_cell_fwd", "gru_cell_fwd_multi", "gru_cell_split_fwd_multi", "sb_gemm_n128", "sb_gemm", "sb_encoder_tail", "gru_seq_fwd", "gru_seq_fwd_multi", "gru_seq_split_fwd_multi", "gru_seq_split_bwd_multi", "gru_seq_save_elems", "gru_seq_bwd", "gru_seq_bwd_multi", "gru_seq_bwd_workspace", "wgrad_tn", "wgrad_tn_workspace", "wgrad_split_tn", "wgrad_split_tn2", "wgrad_split_workspace", "rollout_record", "ppo_loss_fwd_bwd", "ppo_loss_prob_fwd_bwd", "ppo_loss_workspace",
            "gauss_head_sample", "ppo_loss_gauss_fwd_bwd", "ppo_loss_gauss_workspace", "gauss_head_sample_ex", "ppo_loss_gauss_ex_fwd_bwd",
            "ppo_loss_gauss_ex_workspace", "gae_advnorm_vn", "gae_advnorm_vn_workspace", "value_norm_update", "value_norm_targets",
            "ppo_loss_fwd_bwd_diag", "ppo_loss_prob_fwd_bwd_diag", "ppo_loss_gauss_fwd_bwd_diag", "ppo_loss_gauss_ex_fwd_bwd_diag",
@@ -74,6 +74,7 @@ def load_library():
         L.gru_cell_split_fwd_multi.argtypes = [i32, vp, i32, i32, vp]
         L.sb_gemm_n128.argtypes = [i64, i32, vp, i64, vp, i64, vp, i32, vp, i64, vp, i64, vp]
         L.sb_gemm.argtypes = [i64, i32, i32, vp, i64, vp, i64, vp, i32, vp, i64, vp, i64, vp]
+        L.sb_encoder_tail.argtypes = [i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp]
         L.gru_seq_fwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
         L.gru_seq_bwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
         L.gru_seq_split_fwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
@@ -2036,6 +2037,47 @@ def split_linear(x, W, bias=None, relu=False, out=None, addend=None, sign_bits=N
         return out
     _check(L.sb_gemm(R, N, K, _ptr(x), x.stride(0), _ptr(W), W.stride(0), _ptr(b), int(bool(relu)), _ptr(addend),
                      addend.stride(0) if addend is not None else 0, _ptr(out), out.stride(0), _stream()), "sb_gemm")
+    return out
+
+
+ENCODER_TAIL = os.environ.get("MAPPO_ENCODER_TAIL", "1") != "0"   # A/B switch (tools/ab_switch.py): off = the AGG layer and the semantic layer as two sb_gemm launches
+
+
+def _overlap(a, b):
+    """the address ranges of two strided 2-D tensors intersect"""
+    def span(t):
+        lo = t.data_ptr()
+        return lo, lo + 4 * ((t.shape[0] - 1) * t.stride(0) + t.shape[1]) if t.shape[0] else lo
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def encoder_tail_ok(m3, w_agg, b_agg, Ws, out):
+    """operands sb_encoder_tail covers: the rollout's kernels in split mode, no autograd, fp32, E = 128; m3 (Rs, 384) and out (Rs, 128)
+    2-D with unit column stride, row strides multiples of 4 floats, 16-byte aligned (split_linear_ok's rules); Ws (128, 384) may be a
+    column block; w_agg, b_agg dense; m3 does not overlap out"""
+    if not ENCODER_TAIL or CELL_MODE != "split_bf16" or torch.is_grad_enabled() or not m3.is_cuda:
+        return False
+    if m3.dim() != 2 or out.dim() != 2 or m3.shape[1] != 384 or tuple(out.shape) != (m3.shape[0], 128) or tuple(Ws.shape) != (128, 384):
+        return False
+    if tuple(w_agg.shape) != (128, 128) or not w_agg.is_contiguous() or b_agg is None or tuple(b_agg.shape) != (128,) or not b_agg.is_contiguous():
+        return False
+    for t in (m3, w_agg, Ws, out):
+        if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+            return False
+    if b_agg.dtype != torch.float32 or b_agg.data_ptr() % 16:
+        return False
+    return not _overlap(m3, out)
+
+
+def encoder_tail(m3, w_agg, b_agg, Ws, out):
+    """out += sum over r of Ws[:, 128 r:128 r + 128] relu(w_agg m3[:, 128 r:128 r + 128] + b_agg), in place: the rollout encoder's AGG
+    layer and the embedding part of its semantic layer in one launch (include/mappo_ops.h sb_encoder_tail), bit-identical to
+    split_linear(m3.view(-1, 128), w_agg, b_agg, relu=True) followed by split_linear(emb.view(-1, 384), Ws, out=out, addend=out).
+    The caller checks encoder_tail_ok."""
+    L = load_library()
+    _check(L.sb_encoder_tail(m3.shape[0], _ptr(m3), m3.stride(0), _ptr(w_agg.detach()), _ptr(b_agg.detach()), _ptr(Ws.detach()), Ws.stride(0),
+                             _ptr(out), out.stride(0), _ptr(out), out.stride(0), _stream()), "sb_encoder_tail")
     return out
 
 

@@ -300,6 +300,15 @@ int sb_gemm_n128(int64_t R, int32_t K, const float *X, int64_t ldx, const float 
  * x W_ih^T + b_ih, (256, 128) the input gradient of an FCRA layer. */
 int sb_gemm(int64_t R, int32_t N, int32_t K, const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias, int32_t relu, const float *C,
             int64_t ldc, float *Y, int64_t ldy, void *stream);
+/* The rollout encoder's tail as ONE launch (DHGN.forward_pair; DHGN/mappo_parallel.py:148-203):
+ *   Y[s] = sum over r = 0, 1, 2 of Ws[:, 128 r .. 128 r + 127] relu(w_agg m3[s][r] + b_agg) + C[s]      for the Rs semantic rows s,
+ * bit-identical to sb_gemm(3 Rs, 128, 128, m3, 128, w_agg, 128, b_agg, 1, NULL, 0, emb, 128) followed by
+ * sb_gemm(Rs, 128, 384, emb, 384, Ws, ldw, NULL, 0, C, ldc, Y, ldy) without the (Rs, 384) embedding in memory.  m3 [Rs][3][128] (row stride
+ * ldx >= 384: a row's three relation vectors are contiguous); w_agg [128][128] and b_agg [128] dense; Ws [128][384] (row stride ldw: a
+ * column block of the semantic layer's weight); C, Y [Rs][128] (row strides ldc, ldy; C may be Y, m3 must not overlap Y).  Strides in
+ * floats, multiples of 4; all pointers 16-byte aligned. */
+int sb_encoder_tail(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *Ws, int64_t ldw, const float *C,
+                    int64_t ldc, float *Y, int64_t ldy, void *stream);
 /* sb_gemm (N = 128, K in {128, 256}) that also writes the sign bits of its result: y_sign_bits[row * ld_bytes + j], bit k = (Y[row][8 j + k] > 0),
  * N / 8 bytes per row (rows ld_bytes apart: Y may be a column block of a wider matrix and the bytes a column block of its bit matrix).
  * Behind the ReLU epilogue these are relu'(Y): sb_gemm_masked_bits reads them in the backward of the layer that consumes Y. */

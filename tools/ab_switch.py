@@ -1,5 +1,6 @@
 """A/B of one boolean switch of ops (RELU_LINK: the ReLU backward in the input-gradient GEMMs' epilogues / separate passes;
-PPO_FROM_PROB: Categorical inside the loss launch / torch.distributions) in ONE process, alternating iteration by iteration: boxes of the
+PPO_FROM_PROB: Categorical inside the loss launch / torch.distributions; ENCODER_TAIL: the rollout encoder's AGG + semantic layers as
+one launch / two -- a rollout switch, so each setting keeps its own captured tick programs) in ONE process, alternating iteration by iteration: boxes of the
 pool differ by a few percent, two runs on two boxes cannot resolve a 1 % change.   python tools/ab_switch.py cfg3 RELU_LINK"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,9 +16,13 @@ for _ in range(3):
     tr.iterate()
 torch.cuda.synchronize()
 acc = {True: [], False: []}
+tick_programs = {}
 for i in range(14):
     setattr(ops, switch, i % 2 == 0)
     on = getattr(ops, switch)
+    st = getattr(tr.agent, "_rstate", None)
+    if st is not None and hasattr(st, "graphs"):    # the tick programs captured under this setting (a switch read while they are captured)
+        st.graphs = tick_programs.setdefault(on, {})
     torch.cuda.synchronize(); t0 = time.perf_counter()
     tr.iterate()
     t_host = 1e3 * (time.perf_counter() - t0)
