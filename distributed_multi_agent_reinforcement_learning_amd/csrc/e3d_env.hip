@@ -26,6 +26,7 @@
 #include "reward_shaping.hpp"
 #include "rng_replica.hpp"
 #include "slsqp_box.hpp"
+#include "team_reward.hpp"
 
 namespace {
 
@@ -481,11 +482,16 @@ __device__ __forceinline__ double e3d_potential(const e3d_state &st, int env, in
 // wave, program order).  SCALED: the reward row is the reference's RewardScaling of the raw reward (csrc/reward_scale.hpp); the state
 // rs [N][1 + 3P] is read and written once per lane, n by slot 0.  SHAPED: potential-based distance shaping (csrc/reward_shaping.hpp) goes
 // into the reward row -- and into RewardScaling when SCALED -- once the terminal predicate of v_next is known; every lane loads and
-// stores its own phi [N][P] entry once.  The unshaped instantiations are the code they were before SHAPED existed.
-template <int PT, bool SCALED, bool SHAPED>
+// stores its own phi [N][P] entry once.  The unshaped instantiations are the code they were before SHAPED existed.  TEAM: team reward
+// sharing (csrc/team_reward.hpp) -- m = (1 - alpha) raw + (alpha s) live, s the team's f64 sum of raw * live from shuffles in agent
+// order ahead of everything that reads a reward, takes the place of the raw reward in the shaping step, the RewardScaling step and
+// the buffer's row of environments not done before the step; acc.ret keeps the raw reward.  Every TEAM statement sits under
+// `if (TEAM)` or is `m` where `(double)raw` stood, so the TEAM = false instantiations are the instructions they were before it.
+template <int PT, bool SCALED, bool SHAPED, bool TEAM>
 __global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_config c, const e3d_state st, const float *reward, const uint8_t *done,
                                                                   const e3d_record_io io, const e3d_policy_acc acc, const double kill,
-                                                                  double *rs, const double gamma, double *phi, const double coef) {
+                                                                  double *rs, const double gamma, double *phi, const double coef,
+                                                                  const double alpha) {
     constexpr int G = WAVE / PT;
     constexpr unsigned long long GM = (PT == 64) ? ~0ull : ((1ull << PT) - 1ull);
     const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
@@ -497,11 +503,19 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_conf
     const float rl = raw * live;
     const bool db = ev && acc.done_before[env] != 0;
     float rb = rl;  // the buffer's reward
+    double m = (double)raw;  // what shaping, scaling and the buffer take for the reward
+    if (TEAM) {  // every lane of the wave runs the loop (the trip count is wave-uniform)
+        const double xl = (double)raw * (double)live;
+        double sd = 0.0;
+        for (int k = 0; k < P; k++) sd = sd + __shfl(xl, base + k);
+        if (!db) m = team::share(alpha, (double)raw, sd, (double)live);
+        if (!SCALED && !SHAPED) rb = (float)m * live;
+    }
     if (SCALED && !SHAPED && pv && !db) {
         double *q = rs + (size_t)env * (1 + 3 * P);
         const double n = q[0] + 1.0;
         double mean = q[1 + a], S = q[1 + P + a], R = q[1 + 2 * P + a];
-        rb = (float)rscale::step((double)raw, gamma, n, mean, S, R) * live;
+        rb = (float)rscale::step(m, gamma, n, mean, S, R) * live;
         q[1 + a] = mean; q[1 + P + a] = S; q[1 + 2 * P + a] = R;
         if (a == 0) q[0] = n;
     }
@@ -526,7 +540,7 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_policy_record(const e3d_conf
     if (SHAPED && pv) {
         if (!db) {
             double ph = phi[(size_t)env * P + a];
-            const double x = rshape::step((double)raw, gamma, ph, e3d_potential(st, env, P, a, p_on, !e_dead, coef), !p_on || ended, (double)live);
+            const double x = rshape::step(m, gamma, ph, e3d_potential(st, env, P, a, p_on, !e_dead, coef), !p_on || ended, (double)live);
             phi[(size_t)env * P + a] = ph;
             if (SCALED) {
                 double *q = rs + (size_t)env * (1 + 3 * P);
@@ -566,13 +580,13 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_shaping_begin(const e3d_conf
     phi[(size_t)env * P + a] = e3d_potential(st, env, P, a, p_on, e_on, coef);
 }
 
-template <bool SCALED, bool SHAPED>
+template <bool SCALED, bool SHAPED, bool TEAM = false>
 int e3d_record_launch(const e3d_config *c, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io &io,
-                      const e3d_policy_acc &acc, double *rs, double gamma, double *phi, double coef, hipStream_t s) {
+                      const e3d_policy_acc &acc, double *rs, double gamma, double *phi, double coef, hipStream_t s, double alpha = 0.0) {
     const int pt = c->P <= 8 ? 8 : (c->P <= 16 ? 16 : (c->P <= 32 ? 32 : 64));
     const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
     const double kill = sq_threshold(c->kill_radius);
-#define E3D_REC(PT) hipLaunchKernelGGL((k_e3d_policy_record<PT, SCALED, SHAPED>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, reward, done, io, acc, kill, rs, gamma, phi, coef)
+#define E3D_REC(PT) hipLaunchKernelGGL((k_e3d_policy_record<PT, SCALED, SHAPED, TEAM>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, reward, done, io, acc, kill, rs, gamma, phi, coef, alpha)
     if (pt == 8) E3D_REC(8); else if (pt == 16) E3D_REC(16); else if (pt == 32) E3D_REC(32); else E3D_REC(64);
 #undef E3D_REC
     return (int)hipGetLastError();
@@ -824,6 +838,21 @@ int e3d_policy_record_shaped(const e3d_config *cfg, const e3d_state *st, const f
     if (st->N < 1) return 0;
     if (rs) return e3d_record_launch<true, true>(cfg, st, reward, done, *io, *acc, rs, gamma, phi, coef, (hipStream_t)stream);
     return e3d_record_launch<false, true>(cfg, st, reward, done, *io, *acc, nullptr, gamma, phi, coef, (hipStream_t)stream);
+}
+
+int e3d_policy_record_team(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
+                           const e3d_policy_acc *acc, double alpha, double *phi, double coef, double gamma, double *rs, void *stream) {
+    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value)) return E3D_ERR_NULL;
+    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (!team::coef_ok(alpha)) return E3D_ERR_BAD_CONFIG;
+    if (st->N < 1) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (phi && rs) return e3d_record_launch<true, true, true>(cfg, st, reward, done, *io, *acc, rs, gamma, phi, coef, s, alpha);
+    if (phi) return e3d_record_launch<false, true, true>(cfg, st, reward, done, *io, *acc, nullptr, gamma, phi, coef, s, alpha);
+    if (rs) return e3d_record_launch<true, false, true>(cfg, st, reward, done, *io, *acc, rs, gamma, nullptr, 0.0, s, alpha);
+    return e3d_record_launch<false, false, true>(cfg, st, reward, done, *io, *acc, nullptr, 0.0, nullptr, 0.0, s, alpha);
 }
 
 int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, double coef, void *stream) {

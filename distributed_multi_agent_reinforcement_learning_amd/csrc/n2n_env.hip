@@ -19,6 +19,7 @@
 #include "reward_shaping.hpp"
 #include "rng_replica.hpp"
 #include "slsqp_box.hpp"
+#include "team_reward.hpp"
 
 namespace {
 
@@ -245,11 +246,16 @@ __device__ __forceinline__ double n2n_potential(const double *gp, const double *
 // loaded it (one wave, program order).  The return accumulator keeps the raw reward.  SHAPED: potential-based distance shaping
 // (csrc/reward_shaping.hpp) goes into the reward row -- and into RewardScaling when SCALED -- once the terminal predicate of v_next is
 // known; every lane loads and stores its own phi [N][P] entry once and walks the E evaders itself.  The unshaped instantiations are the
-// code they were before SHAPED existed.
-template <int PT, bool SCALED, bool SHAPED>
+// code they were before SHAPED existed.  TEAM: team reward sharing (csrc/team_reward.hpp) -- m = (1 - alpha) raw + (alpha s) live, s the
+// team's f64 sum of raw * live from shuffles in agent order ahead of everything that reads a reward, takes the place of the raw reward
+// in the shaping step, the RewardScaling step and the buffer's row of environments not done before the step; acc.ret keeps the raw
+// reward.  Every TEAM statement sits under `if (TEAM)` or is `m` where `(double)raw` stood, so the TEAM = false instantiations are the
+// instructions they were before it.
+template <int PT, bool SCALED, bool SHAPED, bool TEAM>
 __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_config c, const n2n_state st, const float *reward, const uint8_t *done,
                                                                   const n2n_record_io io, const n2n_policy_acc acc, const double kill,
-                                                                  double *rs, const double gamma, double *phi, const double coef) {
+                                                                  double *rs, const double gamma, double *phi, const double coef,
+                                                                  const double alpha) {
     constexpr int G = WAVE / PT;
     const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
     const int g = lane / PT, a = lane - g * PT, base = lane - a;
@@ -260,11 +266,19 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_conf
     const float raw = pv ? reward[(size_t)env * P + a] : 0.f;
     const float rl = raw * live;
     float rb = rl;  // the buffer's reward
+    double m = (double)raw;  // what shaping, scaling and the buffer take for the reward
+    if (TEAM) {  // every lane of the wave runs the loop (the trip count is wave-uniform)
+        const double xl = (double)raw * (double)live;
+        double sd = 0.0;
+        for (int k = 0; k < P; k++) sd = sd + __shfl(xl, base + k);
+        if (ev && acc.done_before[env] == 0) m = team::share(alpha, (double)raw, sd, (double)live);
+        if (!SCALED && !SHAPED) rb = (float)m * live;
+    }
     if (SCALED && !SHAPED && pv && acc.done_before[env] == 0) {
         double *q = rs + (size_t)env * (1 + 3 * P);
         const double n = q[0] + 1.0;
         double mean = q[1 + a], S = q[1 + P + a], R = q[1 + 2 * P + a];
-        rb = (float)rscale::step((double)raw, gamma, n, mean, S, R) * live;
+        rb = (float)rscale::step(m, gamma, n, mean, S, R) * live;
         q[1 + a] = mean; q[1 + P + a] = S; q[1 + 2 * P + a] = R;
         if (a == 0) q[0] = n;
     }
@@ -287,7 +301,7 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_policy_record(const n2n_conf
     if (SHAPED && pv) {
         if (!db) {
             double ph = phi[(size_t)env * P + a];
-            const double x = rshape::step((double)raw, gamma, ph, n2n_potential(gp, ge, P, E, a, p_on, coef), !p_on || ended, (double)live);
+            const double x = rshape::step(m, gamma, ph, n2n_potential(gp, ge, P, E, a, p_on, coef), !p_on || ended, (double)live);
             phi[(size_t)env * P + a] = ph;
             if (SCALED) {
                 double *q = rs + (size_t)env * (1 + 3 * P);
@@ -481,20 +495,21 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_guidance(const n2n_config c,
     if (pv) actions[(size_t)env * P + a] = guide::n2n_command(pact != 0.0 && any, gx, gy);
 }
 
-// n2n_policy_record / n2n_policy_record_scaled / n2n_policy_record_shaped: one launch, the tick's lane layout
-template <bool SCALED, bool SHAPED>
+// n2n_policy_record / n2n_policy_record_scaled / n2n_policy_record_shaped / n2n_policy_record_team: one launch, the tick's lane layout
+template <bool SCALED, bool SHAPED, bool TEAM = false>
 int n2n_record_launch(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                      const n2n_policy_acc *acc, double *rs, double gamma, double *phi, double coef, void *stream) {
+                      const n2n_policy_acc *acc, double *rs, double gamma, double *phi, double coef, void *stream, double alpha = 0.0) {
     if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value) || (SCALED && !rs) || (SHAPED && !phi)) return N2N_ERR_NULL;
     if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return N2N_ERR_NULL;
     const int rc = n2n_config_check(cfg);
     if (rc) return rc;
+    if (TEAM && !team::coef_ok(alpha)) return N2N_ERR_BAD_CONFIG;
     if (st->N < 1) return 0;
     int blocks;
     const int pt = n2n_lanes(cfg, st->N, &blocks);
     const double kill = sq_threshold(cfg->kill_radius);
     hipStream_t s = (hipStream_t)stream;
-#define N2N_REC(PT) hipLaunchKernelGGL((k_n2n_policy_record<PT, SCALED, SHAPED>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, reward, done, *io, *acc, kill, rs, gamma, phi, coef)
+#define N2N_REC(PT) hipLaunchKernelGGL((k_n2n_policy_record<PT, SCALED, SHAPED, TEAM>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, reward, done, *io, *acc, kill, rs, gamma, phi, coef, alpha)
     if (pt == 8) N2N_REC(8); else if (pt == 16) N2N_REC(16); else if (pt == 32) N2N_REC(32); else N2N_REC(64);
 #undef N2N_REC
     return (int)hipGetLastError();
@@ -597,6 +612,14 @@ int n2n_policy_record_shaped(const n2n_config *cfg, const n2n_state *st, const f
                              const n2n_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream) {
     if (rs) return n2n_record_launch<true, true>(cfg, st, reward, done, io, acc, rs, gamma, phi, coef, stream);
     return n2n_record_launch<false, true>(cfg, st, reward, done, io, acc, nullptr, gamma, phi, coef, stream);
+}
+
+int n2n_policy_record_team(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
+                           const n2n_policy_acc *acc, double alpha, double *phi, double coef, double gamma, double *rs, void *stream) {
+    if (phi && rs) return n2n_record_launch<true, true, true>(cfg, st, reward, done, io, acc, rs, gamma, phi, coef, stream, alpha);
+    if (phi) return n2n_record_launch<false, true, true>(cfg, st, reward, done, io, acc, nullptr, gamma, phi, coef, stream, alpha);
+    if (rs) return n2n_record_launch<true, false, true>(cfg, st, reward, done, io, acc, rs, gamma, nullptr, 0.0, stream, alpha);
+    return n2n_record_launch<false, false, true>(cfg, st, reward, done, io, acc, nullptr, 0.0, nullptr, 0.0, stream, alpha);
 }
 
 int n2n_shaping_begin(const n2n_config *cfg, const n2n_state *st, double *phi, double coef, void *stream) {

@@ -242,7 +242,8 @@ class E3dMAPPO(ParticleMAPPO):
         pursuer p or episode n ended in step t for any reason but the time limit; v_n[:, T] is the critic's bootstrap value.  The masks
         and the per-environment accumulators are one launch per tick (ParticleEnv.policy_record); with algo.use_reward_scaling and a
         buffer, r is the scaled reward (env.reward_scale advances) while the return stays the raw one; with algo.reward_shaping:
-        distance and a buffer, r (what is scaled, when both are on) carries the shaping term gamma Phi' - Phi (env.shaping_phi).
+        distance and a buffer, r (what is scaled, when both are on) carries the shaping term gamma Phi' - Phi (env.shaping_phi); with
+        algo.team_reward: alpha > 0 and a buffer, the reward that enters all of this is (1 - alpha) x + alpha (the team's sum of the step).
         With algo.use_obs_norm the features (and feat_a / feat_c) are normalised under obs_norm.state, which no tick changes; with a
         buffer every tick adds the sums of its live rows to obs_norm.slots (explore_env merges them).
         policy="guidance" (buf must be None): the tick takes the scripted pursuers' actions (guidance_episode below) instead of the
@@ -261,6 +262,7 @@ class E3dMAPPO(ParticleMAPPO):
         st.live.copy_(env.active_t)   # no environment is done; policy_record writes the next step's mask
         acc = env.new_accumulators()
         scale_gamma, shaping_gamma = self._shaping_gammas(env, buf)
+        team_coef = self._team_coef(buf)
         for t in range(env.max_step):
             self._features(env, st, accumulate=buf is not None)   # evaluation never accumulates
             self._policy_step(st, greedy)
@@ -276,7 +278,7 @@ class E3dMAPPO(ParticleMAPPO):
             buf["a_n"][:, t].copy_(st.action)
             buf["a_logprob_n"][:, t].copy_(st.logp)
             env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1], st.live,
-                              scale_gamma=scale_gamma, shaping_gamma=shaping_gamma)
+                              scale_gamma=scale_gamma, shaping_gamma=shaping_gamma, team_coef=team_coef)
         if buf is not None:
             self._features(env, st)   # the state after the last step: normalised, not counted
             self._record_bootstrap(env, st, buf, acc)

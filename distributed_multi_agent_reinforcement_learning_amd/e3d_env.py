@@ -88,6 +88,7 @@ def load_library():
         L.e3d_obs_norm_update.argtypes = [vp, vp, vp, C.c_int64, vp]
         L.e3d_policy_record.argtypes = [vp] * 7 + [C.c_double, vp]
         L.e3d_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
+        L.e3d_policy_record_team.argtypes = [vp] * 6 + [C.c_double, vp, C.c_double, C.c_double, vp, vp]
         L.e3d_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
         L.e3d_pursuer_guidance.argtypes = [vp] * 5
         L.e3d_pursuit_features.argtypes = [vp] * 3 + [C.c_int32] + [vp] * 3
@@ -330,14 +331,16 @@ class ParticleEnv:
                                         C.c_double(self.shaping_coef), _stream()), "e3d_shaping_begin")
 
     def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, live_next=None, scale_gamma=None,
-                      shaping_gamma=None):
+                      shaping_gamma=None, team_coef=None):
         """after step(): r = reward * live, active = live, v = value * live (row t of the buffer, None skips), v_next (row t + 1 of v_n)
         zeroed where the pursuer is inactive or its episode ended for a reason other than the time limit, live_next = the next step's
         live mask (may be `live` itself); updates the accumulators of new_accumulators() (e3d_policy_record, include/e3d_env.h).
         scale_gamma: the discount of the reference's RewardScaling; r is then the scaled reward * live and reward_scale
         (enable_reward_scaling) advances, in the same launch.  shaping_gamma: the discount of the distance shaping; the reward (what
         RewardScaling receives, when both are on) gains gamma Phi' - Phi on live rows and shaping_phi (enable_reward_shaping) advances,
-        still in that one launch (e3d_policy_record_shaped)."""
+        still in that one launch (e3d_policy_record_shaped).  team_coef: alpha in [0, 1] of the team reward sharing; the reward that
+        enters the row, the shaping and the scaling is (1 - alpha) reward + alpha (sum_p reward * live) on live rows, in the same
+        launch (e3d_policy_record_team); the accumulators keep the raw reward."""
         N, P = self.num_envs, self.p_num
         io = E3dRecordIO()
         for k, t in (("live", live), ("value", value), ("r", r), ("active", active), ("v", v), ("v_next", v_next), ("live_next", live_next)):
@@ -358,6 +361,10 @@ class ParticleEnv:
             rs_ptr, gamma = rs.data_ptr(), float(scale_gamma)
         args = (C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()), C.byref(io), C.byref(a))
         if shaping_gamma is None:
+            if team_coef is not None:
+                _check(self.L.e3d_policy_record_team(*args, C.c_double(float(team_coef)), None, C.c_double(0.0), C.c_double(gamma),
+                                                     C.c_void_p(rs_ptr), _stream()), "e3d_policy_record_team")
+                return
             _check(self.L.e3d_policy_record(*args, C.c_void_p(rs_ptr), C.c_double(gamma), _stream()), "e3d_policy_record")
             return
         phi = self.shaping_phi
@@ -366,6 +373,10 @@ class ParticleEnv:
         if scale_gamma is not None and float(scale_gamma) != float(shaping_gamma):
             raise ValueError("policy_record: scale_gamma and shaping_gamma are one discount (algo.gamma)")
         assert phi.dtype == torch.float64 and phi.is_contiguous() and phi.shape == (N, P) and phi.device == self.p.device
+        if team_coef is not None:
+            _check(self.L.e3d_policy_record_team(*args, C.c_double(float(team_coef)), C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef),
+                                                 C.c_double(float(shaping_gamma)), C.c_void_p(rs_ptr), _stream()), "e3d_policy_record_team")
+            return
         _check(self.L.e3d_policy_record_shaped(*args, C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef), C.c_double(float(shaping_gamma)),
                                                C.c_void_p(rs_ptr), _stream()), "e3d_policy_record_shaped")
 

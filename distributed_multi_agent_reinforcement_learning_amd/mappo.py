@@ -22,6 +22,7 @@ from .imitation import refuse_pursuit
 from .kickstart import refuse_pursuit as refuse_pursuit_kickstart
 from .model import build_actor_critic, pair_embeddings, pair_heads, sequence_forward_pair
 from .pe_env import status_or, status_text
+from .team_reward import team_reward_options
 from .update_diag import UpdateDiag, update_diag_options
 
 _log = logging.getLogger(__name__)
@@ -211,6 +212,9 @@ class MAPPO:
         if str(a.get("reward_shaping", "none")) != "none":
             raise ValueError("algo.reward_shaping is built for runtime.env n2n and e3d only; the pursuit rollout is pinned to the "
                              "reference's (set reward_shaping to none)")
+        if team_reward_options(cfg) != 0.0:
+            raise ValueError("algo.team_reward is built for runtime.env n2n and e3d only; the pursuit rollout is pinned to the "
+                             "reference's (set team_reward to 0)")
         if bool(a.get("use_value_norm", False)):
             raise ValueError("algo.use_value_norm: true is built for runtime.env n2n and e3d only; the pursuit update is pinned to the "
                              "reference's (set use_value_norm to false)")

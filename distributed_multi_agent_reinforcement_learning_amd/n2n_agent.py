@@ -132,7 +132,8 @@ class N2nMAPPO(ParticleMAPPO):
         episode n ended in step t for a reason other than the time limit; v_n[:, T] is the critic's bootstrap value under that rule.
         With algo.use_reward_scaling and a buffer, r is the scaled reward (env.reward_scale advances); acc["ret"] stays the raw return.
         With algo.reward_shaping: distance and a buffer, r (what is scaled, when both are on) carries the shaping term
-        gamma Phi' - Phi (env.shaping_phi, written by shaping_begin after the reset).
+        gamma Phi' - Phi (env.shaping_phi, written by shaping_begin after the reset).  With algo.team_reward: alpha > 0 and a buffer,
+        the reward that enters all of this is (1 - alpha) x + alpha (the team's sum of the step).
         policy="guidance" (buf must be None): the tick takes the scripted pursuers' actions (guidance_episode below) instead of the
         network's; no network, sampler or sampling counter is touched, the accumulators are the same.
         follow (explore_expert; needs a buffer): a (N,) uint8 mask -- every tick labels buf["a_star"][:, t] with the scripted pursuers'
@@ -147,6 +148,7 @@ class N2nMAPPO(ParticleMAPPO):
         st.reset()
         acc = env.new_accumulators()
         scale_gamma, shaping_gamma = self._shaping_gammas(env, buf)
+        team_coef = self._team_coef(buf)
         for t in range(env.episode_limit):
             env.policy_inputs(st.p4, st.e4, st.e_ref, st.live, st.pp, st.pe, acc["done_before"])
             self._policy_step(st, greedy)
@@ -158,7 +160,7 @@ class N2nMAPPO(ParticleMAPPO):
                 env.policy_record(acc, st.live)
                 continue
             env.policy_record(acc, st.live, st.v, buf["r"][:, t], buf["active"][:, t], buf["v_n"][:, t], buf["v_n"][:, t + 1],
-                              scale_gamma=scale_gamma, shaping_gamma=shaping_gamma)
+                              scale_gamma=scale_gamma, shaping_gamma=shaping_gamma, team_coef=team_coef)
             items = [(st.p4, buf["p_state"][:, t]), (st.e4, buf["e_state"][:, t]), (st.e_ref, buf["e_ref"][:, t]), (st.pp, buf["p_adj"][:, t]),
                      (st.pe, buf["e_adj"][:, t]), (st.a_n, buf["a_n"][:, t]), (st.logp, buf["a_logprob_n"][:, t])]
             if d:   # the update reads the stored embeddings as FCRA history only

@@ -88,6 +88,7 @@ def load_library():
         L.n2n_policy_record.argtypes = [vp] * 7
         L.n2n_policy_record_scaled.argtypes = [vp] * 7 + [C.c_double, vp]
         L.n2n_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
+        L.n2n_policy_record_team.argtypes = [vp] * 6 + [C.c_double, vp, C.c_double, C.c_double, vp, vp]
         L.n2n_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
         L.n2n_pursuer_guidance.argtypes = [vp] * 5
         _lib = L
@@ -320,14 +321,17 @@ class ParticleEnv:
         _check(self.L.n2n_policy_inputs(C.byref(self.c), C.byref(self.st), C.c_void_p(done_before.data_ptr() if done_before is not None else None),
                                         C.byref(io), _stream()), "n2n_policy_inputs")
 
-    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, scale_gamma=None, shaping_gamma=None):
+    def policy_record(self, acc, live, value=None, r=None, active=None, v=None, v_next=None, scale_gamma=None, shaping_gamma=None,
+                      team_coef=None):
         """after step(): r = reward * live, active = live, v = value * live (row t of the buffer, None skips), v_next (row t + 1 of v_n)
         zeroed where the pursuer is inactive or its episode ended for a reason other than the time limit; updates the accumulators
         of new_accumulators() (n2n_policy_record, include/n2n_env.h).  scale_gamma: the discount of the reference's RewardScaling; r is
         then the scaled reward * live and reward_scale (enable_reward_scaling) advances, in the same launch (n2n_policy_record_scaled).
         shaping_gamma: the discount of the distance shaping; the reward (what RewardScaling receives, when both are on) gains
         gamma Phi' - Phi on live rows and shaping_phi (enable_reward_shaping) advances, still in that one launch
-        (n2n_policy_record_shaped)."""
+        (n2n_policy_record_shaped).  team_coef: alpha in [0, 1] of the team reward sharing; the reward that enters the row, the shaping
+        and the scaling is (1 - alpha) reward + alpha (sum_p reward * live) on live rows, in the same launch (n2n_policy_record_team);
+        the accumulators keep the raw reward."""
         N, P = self.num_envs, self.p_num
         io = N2nRecordIO()
         for k, t in (("live", live), ("value", value), ("r", r), ("active", active), ("v", v), ("v_next", v_next)):
@@ -340,7 +344,7 @@ class ParticleEnv:
             assert t.dtype == dt and t.is_contiguous() and t.shape == (N,) and t.device == self.p.device, k
             setattr(a, k, t.data_ptr())
         args = (C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()), C.byref(io), C.byref(a))
-        if scale_gamma is None and shaping_gamma is None:
+        if scale_gamma is None and shaping_gamma is None and team_coef is None:
             _check(self.L.n2n_policy_record(*args, _stream()), "n2n_policy_record")
             return
         rs = None
@@ -350,6 +354,11 @@ class ParticleEnv:
                 raise RuntimeError("policy_record(scale_gamma=...) needs enable_reward_scaling() on this environment")
             assert rs.dtype == torch.float64 and rs.is_contiguous() and rs.shape == (N, 1 + 3 * P) and rs.device == self.p.device
         if shaping_gamma is None:
+            if team_coef is not None:
+                _check(self.L.n2n_policy_record_team(*args, C.c_double(float(team_coef)), None, C.c_double(0.0),
+                                                     C.c_double(0.0 if scale_gamma is None else float(scale_gamma)),
+                                                     C.c_void_p(rs.data_ptr() if rs is not None else None), _stream()), "n2n_policy_record_team")
+                return
             _check(self.L.n2n_policy_record_scaled(*args, C.c_void_p(rs.data_ptr()), C.c_double(float(scale_gamma)), _stream()),
                    "n2n_policy_record_scaled")
             return
@@ -359,5 +368,10 @@ class ParticleEnv:
         if scale_gamma is not None and float(scale_gamma) != float(shaping_gamma):
             raise ValueError("policy_record: scale_gamma and shaping_gamma are one discount (algo.gamma)")
         assert phi.dtype == torch.float64 and phi.is_contiguous() and phi.shape == (N, P) and phi.device == self.p.device
+        if team_coef is not None:
+            _check(self.L.n2n_policy_record_team(*args, C.c_double(float(team_coef)), C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef),
+                                                 C.c_double(float(shaping_gamma)), C.c_void_p(rs.data_ptr() if rs is not None else None),
+                                                 _stream()), "n2n_policy_record_team")
+            return
         _check(self.L.n2n_policy_record_shaped(*args, C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef), C.c_double(float(shaping_gamma)),
                                                C.c_void_p(rs.data_ptr() if rs is not None else None), _stream()), "n2n_policy_record_shaped")

@@ -14,6 +14,7 @@ from . import ops
 from . import value_norm as vnorm
 from .minibatch_steps import MAX_GRAD_NORM, minibatch_steps_options
 from .reward_shaping import reward_shaping_options
+from .team_reward import team_reward_options
 from .trainer import (BUCKET_ALIGN, FusedAdam, GradBucket, ParamBucket, ParticleRunState, allreduce_sum_, broadcast_weights_,
                       enable_tuned_gemms, init_distributed, resume_path, save_resume_atomic)
 from .update_diag import LOG_KEYS, UpdateDiag, first_epoch_over, update_diag_options
@@ -73,6 +74,7 @@ class ParticleMAPPO:
         self.use_reward_scaling = bool(a.get("use_reward_scaling", False))   # the reference's RewardScaling in policy_record
         self.use_value_norm, self.value_norm_beta = vnorm.value_norm_options(cfg)   # ValueNorm on the value targets
         self.reward_shaping, self.shaping_coef = reward_shaping_options(cfg)   # distance shaping in policy_record
+        self.team_reward = team_reward_options(cfg)   # team reward sharing in policy_record, 0: off
         self.update_diagnostics, self.target_kl = update_diag_options(cfg)   # what the update did, from the loss launches
         self.minibatch_steps = minibatch_steps_options(cfg)   # one clip + Adam step per mini-batch, fused
         self.guidance = gd.guidance_options(cfg)   # the scripted pursuers of run_episode(policy="guidance")
@@ -134,6 +136,11 @@ class ParticleMAPPO:
         if shaping_gamma is not None:
             env.shaping_begin()
         return scale_gamma, shaping_gamma
+
+    def _team_coef(self, buf):
+        """-> team_coef of policy_record for this episode: algo.team_reward on a training rollout, None (the unshared entry points)
+        when the option is off and in evaluation (no buffer)"""
+        return self.team_reward if (self.team_reward != 0.0 and buf is not None) else None
 
     def _record_bootstrap(self, env, st, buf, acc):
         """v_n[:, T] of a finished rollout: the critic's value of the state after the last step (its inputs are in `st`), zero where

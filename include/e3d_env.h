@@ -128,6 +128,16 @@ int e3d_policy_record_shaped(const e3d_config *cfg, const e3d_state *st, const f
                              const e3d_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream);
 int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, double coef, void *stream);
 
+/* e3d_policy_record with team reward sharing (algo.team_reward: alpha; csrc/team_reward.hpp), in the same launch.
+ * For an environment that was not done before the step, with x = reward[P] and s = sum_k x_k live_k (f64, index order):
+ * m_p = (1 - alpha) x_p + (alpha s) live_p takes the place of the raw reward in everything that follows: io->r = (float)m * live; with
+ * phi (NULL: no shaping; else the state of e3d_policy_record_shaped with its coef and gamma) the shaping step receives m; with rs
+ * (NULL: no scaling; else the RewardScaling state, discount gamma) the scaling step receives m, or the shaped m.  Environments done
+ * before the step are what the siblings make of them.  acc->ret keeps the raw reward; everything but io->r, phi and rs is what
+ * e3d_policy_record writes.  alpha must be a number in [0, 1]: E3D_ERR_BAD_CONFIG otherwise, before any launch. */
+int e3d_policy_record_team(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
+                           const e3d_policy_acc *acc, double alpha, double *phi, double coef, double gamma, double *rs, void *stream);
+
 /* ---- scripted pursuers: a deterministic lead-pursuit law as a yardstick policy (csrc/guidance.hpp) ----
  * lead: the longest look-ahead in the environment's time units; a team-mate closer than sep_range pushes with weight sep_gain.
  * Each must be finite and >= 0 (E3D_ERR_BAD_CONFIG otherwise). */
