@@ -648,9 +648,10 @@ def test_fcra_neighbour_mean_matches_torch(P, T, relu):
 
 @pytest.mark.parametrize("P,E", [(8, 128), (5, 128), (3, 128), (1, 128), (8, 256)])
 def test_fcra_neighbour_mean_at_size_into_a_column_block(P, E):
-    """fcra_mean at the update's row count (more rows than one pass of the grid), odd agent counts, and the result written into the
-    left half of an [agg | h] operand (row stride 2E): the wave-per-row kernel (E = 128, P <= 8) and the lane-per-feature kernel
-    (other widths) against f64; the right half of the operand stays untouched."""
+    """fcra_mean at 6 150 rows (one pass of either grid: 1 538 of up to 4 096 workgroups of the wave-per-row kernel, 6 150 of up to
+    16 384 of the lane-per-feature kernel; tests/test_nbr_mean_gpu.py passes both grids), odd agent counts, and the result written
+    into the left half of an [agg | h] operand (row stride 2E): the wave-per-row kernel (E = 128, P <= 8) and the lane-per-feature
+    kernel (other widths) against f64; the right half of the operand stays untouched."""
     from distributed_multi_agent_reinforcement_learning_amd import ops
     torch.manual_seed(P + E)
     n, T, d = 150, 41, 3

@@ -18,7 +18,8 @@ pytestmark = pytest.mark.gpu
 
 CONFIG = {"e3d": "cfg5", "n2n": "cfg4_n2n"}
 U = 2.0 ** -53          # f64 unit roundoff
-SHAPES = [(7, 13, 5), (64, 150, 8), (512, 200, 8), (1024, 100, 16)]   # ..., cfg5 and cfg4_n2n per rank
+SHAPES = [(7, 13, 5), (64, 150, 8), (512, 200, 8), (1024, 100, 16),   # ..., cfg5 and cfg4_n2n per rank
+          (65_537, 2, 1), (8_193, 3, 8)]   # past k_gae_scan_vn's 256 x 256 lanes: one sequence, and eight with P > 1, in the loop's second trip
 
 
 def _ops():
