@@ -2,8 +2,8 @@
 LDS-direct loads fill two steps ahead, with hand-counted vmcnt waits.  What that adds to get wrong sits at the ring's edges: sequences
 shorter than the pipeline is deep (T = 1, 2, 3), dead rows and tail tiles (B = 1, 15, 16, 17), the benchmark's two mini-batch sizes
 (3 280, 3 248), ragged records in one launch, both row orders, both output forms (dnr / full dgh) and launches with and without the
-bias gradients.  Every backward output is held to an f64 torch autograd GRU beside the fp32-route kernels (k_gru_seq_bwd2), with the
-bound of tests/test_split_bf16_gpu.py::test_split_gru_sequence_matches_f64_beside_the_fp32_kernels; launches repeat bit for bit and a
+bias gradients.  Every backward output, and the forward's `out` of both routes (k_gru_seq_fwd_sb, k_gru_seq_fwd2) at the same edges,
+is held to an f64 torch autograd GRU beside the fp32-route kernels (k_gru_seq_bwd2), with the bound of tests/test_split_bf16_gpu.py::test_split_gru_sequence_matches_f64_beside_the_fp32_kernels; launches repeat bit for bit and a
 captured graph replays the eager result.  Reference op: torch.nn.GRU over T steps, DHGN/mappo_parallel.py:397, :432-436."""
 import ctypes as C
 
@@ -107,7 +107,7 @@ def _reference(T, r, agents):
         hs.append(h)
     (torch.stack(hs) * r["dout"].double()).sum().backward()
     dgh = torch.stack([g.grad for g in ghs])
-    return dict(dgi=gi.grad, dgh=dgh, dnr=dgh[:, :, 2 * H:], dh0=h0.grad, db_ih=gi.grad.sum(0), db_hh=b.grad)
+    return dict(dgi=gi.grad, dgh=dgh, dnr=dgh[:, :, 2 * H:], dh0=h0.grad, db_ih=gi.grad.sum(0), db_hh=b.grad, out=torch.stack(hs).detach())
 
 
 def _err(a, ref):
@@ -124,11 +124,15 @@ RAGGED = [(150, [3280, 17, 3248, 1, 16], 0, "mixed", True), (2, [17, 3280, 1], 0
 
 @pytest.mark.parametrize("T,Bs,agents,form,bias", SMALL + LARGE + RAGGED)
 def test_split_backward_matches_f64_beside_the_fp32_route(T, Bs, agents, form, bias):
-    """every backward output of k_gru_seq_bwd_sb against f64, with k_gru_seq_bwd2's error beside it (the bound of
-    test_split_gru_sequence_matches_f64_beside_the_fp32_kernels: e_split <= 2 e_fp32 + 2e-6 and e_split < 2e-5, errors relative to the
-    tensor's largest reference magnitude)"""
+    """every backward output of k_gru_seq_bwd_sb and the forward's `out` (the live rows, time-major) against f64, with the fp32 route's
+    error beside it (the bound of test_split_gru_sequence_matches_f64_beside_the_fp32_kernels: e_split <= 2 e_fp32 + 2e-6 and
+    e_split < 2e-5, errors relative to the tensor's largest reference magnitude); the fp32 route's `out` on its own below 2e-6"""
     recs = _inputs(T, Bs, agents, 1000 * T + sum(Bs) + agents)
-    got = {route: _launch(route, T, recs, agents, form, bias) for route in ("fp32", "split")}
+    got = {}
+    for route in ("fp32", "split"):
+        got[route] = _launch(route, T, recs, agents, form, bias)
+        for o, r in zip(got[route], recs):
+            o["out"] = r["out"]          # this route's forward output, time-major [T][B][H] (the next launch allocates its own)
     for k, r in enumerate(recs):
         ref = _reference(T, r, agents)
         for nm, a in got["split"][k].items():
@@ -139,6 +143,9 @@ def test_split_backward_matches_f64_beside_the_fp32_route(T, Bs, agents, form, b
             print(f"T={T} B={r['B']} agents={agents} record {k} {nm}: split {e_s:.3e} fp32 {e_f:.3e}")
             assert e_s <= 2.0 * e_f + 2e-6, (k, nm, e_s, e_f)
             assert e_s < 2e-5, (k, nm, e_s)
+            if nm == "out":              # the fp32 route's forward on its own (the figure of test_split_gru_sequence_matches_f64_.. for `out`)
+                assert torch.isfinite(got["fp32"][k][nm]).all(), (k, nm)
+                assert e_f < 2e-6, (k, nm, e_f)
 
 
 @pytest.mark.parametrize("T,Bs,agents,form", [(150, [3280, 17, 3248], 0, "mixed"), (3, [17, 1, 3280], 8, "dgh"), (2, [15], 0, "dnr"), (1, [16, 17], 0, "mixed")])
