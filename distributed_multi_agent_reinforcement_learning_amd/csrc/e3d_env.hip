@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "central_critic.hpp"
 #include "direction_action.hpp"
 #include "e3d_env.h"
 #include "guidance.hpp"
@@ -728,6 +729,126 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_pursuit(const e3d_config c, 
     }
 }
 
+// the centralised critic input (include/e3d_env.h e3d_central_features; csrc/central_critic.hpp): k_e3d_pursuit's
+// launch -- the same lanes, the same actor rows and the same first 32 critic columns through the same pfeat:: calls -- whose critic
+// row goes on with one 8-column slot per active team-mate, nearest first.  PT <= 16, so every loop over the team is unrolled over
+// the compile-time PT (lanes past P are inactive, amask masks them) and the squared distances d2[PT] stay in registers: nothing is
+// indexed at run time but global memory.  A lane rounds its own u and v / p_vmax to fp32 once and the team reads them through
+// shuffles; a team-mate's slot is its rank, the count of the team-mates that sort ahead of it (ccrit::ahead), and its block goes
+// straight to that slot as two 16-byte stores, the slots past |V| and the rows of inactive pursuers as zero blocks: no sort, no
+// LDS, no atomics, no local row of 32 + 8 (P - 1) floats.  The second pass shuffles the positions again instead of keeping
+// 3 PT differences.
+template <int PT, bool TEAM>
+__global__ __launch_bounds__(WAVE * WPB) void k_e3d_central(const e3d_config c, const e3d_state st, const e3d_obs_out o, const int sensed,
+                                                            float *af, float *cf) {
+    static_assert(PT <= ccrit::MAX_P, "the team loops are unrolled over PT");
+    static_assert(ccrit::MATE == E3D_CENTRAL_MATE && ccrit::MAX_P == E3D_CENTRAL_MAX_P && ccrit::feat(3) == E3D_CENTRAL_FEAT(3), "include/e3d_env.h");
+    constexpr int G = WAVE / PT;
+    constexpr int LOG2 = PT == 8 ? 3 : 4;
+    constexpr uint64_t GM = (1ull << PT) - 1ull;
+    const int lane = threadIdx.x & (WAVE - 1), wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const int g = lane / PT, a = lane - g * PT, base = lane - a;
+    const int env = wave * G + g, P = c.P, CF = ccrit::feat(P);
+    const bool ev = env < st.N, pv = ev && a < P;
+    double x = 0, y = 0, z = 0, phi = 0, gamma = 0, v = 0, act = 0;
+    double e[7] = {0, 0, 0, 0, 0, 0, 0}, tg[3] = {0, 0, 0};
+    int32_t ts = 0;
+    uint64_t rowm = 0;   // bit j: pp_adj[i][j] == 1
+    bool pe = false;
+    if (pv) {
+        const double *q = st.p + (size_t)env * 7 * P + a;
+        x = q[0]; y = q[P]; z = q[2 * P]; phi = q[3 * P]; gamma = q[4 * P]; v = q[5 * P]; act = q[6 * P];
+        const float *pp = o.pp_adj + (int64_t)env * o.pp_adj_stride + (int64_t)a * P;
+        for (int j = 0; j < P; j++) rowm |= (uint64_t)(pp[j] == 1.f) << j;
+        pe = o.pe_adj[(int64_t)env * o.pe_adj_stride + a] == 1.f;
+    }
+    if (ev) {
+        const double *ge = st.e + (size_t)env * 7;
+        for (int k = 0; k < 7; k++) e[k] = ge[k];
+        for (int k = 0; k < 3; k++) tg[k] = st.target[3 * (size_t)env + k];
+        ts = st.time_step[env];
+    }
+    const bool on = pv && act != 0.0;
+    const uint64_t amask = (__ballot(on) >> base) & GM;          // the group's active pursuers
+    const uint64_t smask = (__ballot(on && pe) >> base) & GM;    // ... that sense the evader
+    const uint64_t vm = on ? amask & ~(1ull << a) : 0ull;        // V_i of the critic
+    pfeat::Near na, nc;
+    pfeat::near_init(na);
+    pfeat::near_init(nc);
+    uint64_t nb = rowm;
+    double d2[PT];
+#pragma unroll
+    for (int k = 0; k < PT; k++) {
+        const double kx = __shfl(x, base + k), ky = __shfl(y, base + k), kz = __shfl(z, base + k);
+        if (TEAM) nb |= ((e3d_shfl_mask<PT>(rowm, base + k) >> a) & 1ull) << k;   // pp_adj[k][i]
+        const double dx = kx - x, dy = ky - y, dz = kz - z;
+        d2[k] = pfeat::sq3(dx, dy, dz);
+        if (k != a && ((amask >> k) & 1ull)) {
+            pfeat::near_add(nc, dx, dy, dz);
+            if ((rowm >> k) & 1ull) pfeat::near_add(na, dx, dy, dz);
+        }
+    }
+    bool ka = sensed ? pe : true;   // sensed | global
+    if (TEAM) {
+        uint64_t reach = (nb & amask) | (1ull << a);
+#pragma unroll 1
+        for (int r = 0; r < LOG2; r++) {
+            uint64_t m = reach;
+            for (int k = 0; k < P; k++) {
+                const uint64_t rk = e3d_shfl_mask<PT>(reach, base + k);
+                if ((reach >> k) & 1ull) m |= rk;
+            }
+            reach = m;
+        }
+        ka = (reach & smask) != 0ull;
+    }
+    pfeat::Common cm;   // (every lane: the team reads this lane's share below)
+    pfeat::common(cm, x, y, z, phi, gamma, v, e[0], e[1], e[2], e[3], e[4], e[5], tg[0], tg[1], tg[2], E3D_WORLD, c.p_vmax, c.e_vmax, ts, c.max_step);
+    float h[4];
+    ccrit::share(h, cm);
+    float *crow = cf + ((size_t)env * P + a) * CF;   // (dereferenced by the lanes of real pursuers only)
+    if (pv) {
+        float fa[pfeat::FEAT], fc[pfeat::FEAT];
+        if (on) {
+            const bool e_on = e[6] != 0.0;
+            pfeat::row(fa, cm, ka && e_on, na, P, E3D_WORLD, c.kill_radius);
+            pfeat::row(fc, cm, e_on, nc, P, E3D_WORLD, c.kill_radius);
+        } else {
+            for (int q = 0; q < pfeat::FEAT; q++) fa[q] = fc[q] = 0.f;
+        }
+        float4 *da = reinterpret_cast<float4 *>(af + ((size_t)env * P + a) * pfeat::FEAT), *dc = reinterpret_cast<float4 *>(crow);
+        for (int q = 0; q < pfeat::FEAT / 4; q++) {
+            da[q] = make_float4(fa[4 * q], fa[4 * q + 1], fa[4 * q + 2], fa[4 * q + 3]);
+            dc[q] = make_float4(fc[4 * q], fc[4 * q + 1], fc[4 * q + 2], fc[4 * q + 3]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PT; k++) {
+        const double kx = __shfl(x, base + k), ky = __shfl(y, base + k), kz = __shfl(z, base + k);
+        float hk[4];
+        for (int q = 0; q < 4; q++) hk[q] = __shfl(h[q], base + k);
+        if ((vm >> k) & 1ull) {
+            int rank = 0;
+#pragma unroll
+            for (int j = 0; j < PT; j++)
+                if (j != k) rank += (int)(((vm >> j) & 1ull) && ccrit::ahead(d2[j], j, d2[k], k));
+            float f[ccrit::MATE];
+            ccrit::slot(f, pfeat::Mate{d2[k], kx - x, ky - y, kz - z}, hk, E3D_WORLD, c.kill_radius);
+            float4 *d = reinterpret_cast<float4 *>(crow + pfeat::FEAT + ccrit::MATE * rank);
+            d[0] = make_float4(f[0], f[1], f[2], f[3]);
+            d[1] = make_float4(f[4], f[5], f[6], f[7]);
+        }
+    }
+    if (!pv) return;
+    const int nv = __popcll(vm);
+#pragma unroll
+    for (int s = 0; s < PT - 1; s++)
+        if (s >= nv && s < P - 1) {
+            float4 *d = reinterpret_cast<float4 *>(crow + pfeat::FEAT + ccrit::MATE * s);
+            d[0] = d[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+}
+
 struct E3dResetter { e3d_config cfg; int N; std::vector<rngrep::NpRandom> rng; };
 
 }  // namespace
@@ -956,6 +1077,71 @@ int e3d_pursuit_features_host(const e3d_config *cfg, int32_t N, const double *p,
             const bool e_on = ge[6] != 0.0;
             pfeat::row(fa, cm, ka && e_on, na, P, E3D_WORLD, cfg->kill_radius);
             pfeat::row(fc, cm, e_on, nc, P, E3D_WORLD, cfg->kill_radius);
+        }
+    }
+    return 0;
+}
+
+int e3d_central_features(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, int32_t evader_obs, float *actor_feat,
+                         float *critic_feat, void *stream) {
+    if (!cfg || !st || !out || !out->pp_adj || !out->pe_adj || !actor_feat || !critic_feat) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (cfg->P > E3D_CENTRAL_MAX_P) return E3D_ERR_BAD_CONFIG;
+    if (evader_obs != E3D_EVADER_OBS_SENSED && evader_obs != E3D_EVADER_OBS_TEAM && evader_obs != E3D_EVADER_OBS_GLOBAL) return E3D_ERR_BAD_CONFIG;
+    if (((uintptr_t)actor_feat | (uintptr_t)critic_feat) % 16) return E3D_ERR_BAD_CONFIG;   // the rows are stored as 16-byte lanes
+    if (st->N < 1) return 0;
+    if (!st->p || !st->e || !st->target || !st->time_step) return E3D_ERR_NULL;
+    const int pt = cfg->P <= 8 ? 8 : 16;
+    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    hipStream_t s = (hipStream_t)stream;
+    const int sensed = evader_obs == E3D_EVADER_OBS_SENSED;
+#define E3D_CC(PT, TEAM) hipLaunchKernelGGL((k_e3d_central<PT, TEAM>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, *out, sensed, actor_feat, critic_feat)
+    if (evader_obs == E3D_EVADER_OBS_TEAM) {
+        if (pt == 8) E3D_CC(8, true); else E3D_CC(16, true);
+    } else {
+        if (pt == 8) E3D_CC(8, false); else E3D_CC(16, false);
+    }
+#undef E3D_CC
+    return (int)hipGetLastError();
+}
+
+int e3d_central_features_host(const e3d_config *cfg, int32_t N, const double *p, const double *e, const double *target, const int32_t *time_step,
+                              const float *pp_adj, const float *pe_adj, int32_t evader_obs, float *actor_feat, float *critic_feat) {
+    if (!cfg || !p || !e || !target || !time_step || !pp_adj || !pe_adj || !actor_feat || !critic_feat) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(cfg);
+    if (rc) return rc;
+    if (cfg->P > E3D_CENTRAL_MAX_P) return E3D_ERR_BAD_CONFIG;
+    if (evader_obs != E3D_EVADER_OBS_SENSED && evader_obs != E3D_EVADER_OBS_TEAM && evader_obs != E3D_EVADER_OBS_GLOBAL) return E3D_ERR_BAD_CONFIG;
+    if (N < 1) return 0;
+    const int P = cfg->P, CF = E3D_CENTRAL_FEAT(P);
+    // the actor rows and the first 32 critic columns are the pursuit entry's: its dense critic rows, then copied into the wide ones
+    std::vector<float> fc32((size_t)N * P * pfeat::FEAT);
+    const int rp = e3d_pursuit_features_host(cfg, N, p, e, target, time_step, pp_adj, pe_adj, evader_obs, actor_feat, fc32.data());
+    if (rp) return rp;
+    for (int32_t n = 0; n < N; n++) {
+        const double *q = p + (size_t)n * 7 * P;
+        float hs[ccrit::MAX_P][4];   // every pursuer's share, from its own row
+        for (int j = 0; j < P; j++)
+            for (int k = 0; k < 4; k++) hs[j][k] = fc32[((size_t)n * P + j) * pfeat::FEAT + 3 + k];
+        for (int i = 0; i < P; i++) {
+            float *fc = critic_feat + ((size_t)n * P + i) * CF;
+            for (int k = 0; k < pfeat::FEAT; k++) fc[k] = fc32[((size_t)n * P + i) * pfeat::FEAT + k];
+            for (int k = pfeat::FEAT; k < CF; k++) fc[k] = 0.f;
+            if (q[6 * P + i] == 0.0) continue;
+            pfeat::Mate m[ccrit::MAX_P];
+            bool in[ccrit::MAX_P];
+            for (int j = 0; j < P; j++) {
+                const double dx = q[j] - q[i], dy = q[P + j] - q[P + i], dz = q[2 * P + j] - q[2 * P + i];
+                m[j] = pfeat::Mate{pfeat::sq3(dx, dy, dz), dx, dy, dz};
+                in[j] = j != i && q[6 * P + j] != 0.0;
+            }
+            for (int k = 0; k < P; k++) {
+                if (!in[k]) continue;
+                int rank = 0;
+                for (int j = 0; j < P; j++) rank += (int)(j != k && in[j] && ccrit::ahead(m[j].d2, j, m[k].d2, k));
+                ccrit::slot(fc + pfeat::FEAT + ccrit::MATE * rank, m[k], hs[k], E3D_WORLD, cfg->kill_radius);
+            }
         }
     }
     return 0;

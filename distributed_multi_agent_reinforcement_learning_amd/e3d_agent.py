@@ -18,6 +18,9 @@ heading and the pitch of (u_x, u_y, u_z) and s (csrc/direction_action.hpp); the 
 imitation label is the teacher's unit vector, and the logged imitation metric is `bc_angle_deg` instead of `bc_action_mse`.
 `algo.e3d_features: pursuit` (off by default) replaces the 16 features by the 32 line-of-sight features of
 ParticleEnv.pursuit_features, and `algo.e3d_evader_obs: sensed | team | global` says when the actor knows where the evader is.
+`algo.e3d_critic: central` (off by default; needs the pursuit features): the critic alone reads
+ParticleEnv.central_features' row, the 32 columns plus 8 per team-mate (`critic_feat_dim`); the actor, the sampler and the environment
+are the ones of `local`, so execution stays decentralised.
 `algo.use_obs_norm` (off by default; obs_norm.py): both encoders read the features normalised by a running mean / std that is frozen
 during a rollout and merged once after it; the first rollout is the option-off one bit for bit.
 """
@@ -33,16 +36,17 @@ from . import guidance as gd
 from . import obs_norm as onorm
 from . import ops
 from . import value_norm as vnorm
-from .e3d_env import EVADER_OBS, PURSUIT_FEAT, ParticleEnv
+from .e3d_env import CENTRAL_MAX_P, EVADER_OBS, PURSUIT_FEAT, ParticleEnv, central_feat
 from .model import HeadLinear, _make_linear, _ortho_linear, _Trunk
 from .particle_agent import ParticleMAPPO, ParticleTrainer, finish_env, train_particle
 
 FEAT = 16   # e3d_policy_features columns (include/e3d_env.h); algo.e3d_features: pursuit has PURSUIT_FEAT
 E3D_FEATURES = ("basic", "pursuit")
+E3D_CRITIC = ("local", "central")
 
 
 class E3dEncoder(nn.Module):
-    """Linear(in_dim -> E) + ReLU, Linear(E -> E) + ReLU on the policy features (rows, in_dim = 16 or 32) -> (rows, E)"""
+    """Linear(in_dim -> E) + ReLU, Linear(E -> E) + ReLU on the policy features (rows, in_dim = 16, 32 or the central critic's) -> (rows, E)"""
 
     def __init__(self, in_dim, embedding_dim):
         super().__init__()
@@ -95,7 +99,7 @@ class _E3dRollout:
         dev, L, H, A, U = agent.device, agent.num_layers, agent.rnn_hidden_dim, agent.action_dim, agent.latent_dim
         z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)
         self.N, self.P = N, P
-        self.fa, self.fc = z(N, P, agent.feat_dim), z(N, P, agent.feat_dim)
+        self.fa, self.fc = z(N, P, agent.feat_dim), z(N, P, agent.critic_feat_dim)
         self.hbuf_a, self.hbuf_c = z(2, L, N * P, H), z(2, L, N * P, H)
         self.action, self.env_action, self.logp, self.v = z(N, P, U), z(N, P, A, dt=torch.float64), z(N, P), z(N, P)
         self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
@@ -145,6 +149,21 @@ def e3d_feature_options(cfg):
     return feats, obs
 
 
+def e3d_critic_options(cfg):
+    """-> e3d_critic of cfg.algo, validated (ValueError naming the key): "local", the critic reads the feature set's own critic row, or
+    "central" (DESIGN.md section 7k), ParticleEnv.central_features' row with every team-mate in it -- which extends the pursuit features
+    and is unrolled over at most CENTRAL_MAX_P pursuers"""
+    critic = str(cfg.algo.get("e3d_critic", "local"))
+    if critic not in E3D_CRITIC:
+        raise ValueError(f"algo.e3d_critic: {critic!r} is not one of {E3D_CRITIC}")
+    if critic == "central":
+        if str(cfg.algo.get("e3d_features", "basic")) != "pursuit":
+            raise ValueError("algo.e3d_critic: central needs algo.e3d_features: pursuit (its row is the pursuit critic row plus the team-mates)")
+        if int(cfg.env.num_defender) > CENTRAL_MAX_P:
+            raise ValueError(f"algo.e3d_critic: central supports env.num_defender <= {CENTRAL_MAX_P} (got {int(cfg.env.num_defender)})")
+    return critic
+
+
 class E3dMAPPO(ParticleMAPPO):
     """rollout (run_episode) and PPO loss (_minibatch_loss) of the Gaussian policy on env_3d; the update loop is ParticleMAPPO.train"""
 
@@ -153,6 +172,9 @@ class E3dMAPPO(ParticleMAPPO):
     def _options(self, cfg):
         self.e3d_features, self.e3d_evader_obs = e3d_feature_options(cfg)   # line-of-sight features
         self.feat_dim = PURSUIT_FEAT if self.e3d_features == "pursuit" else FEAT
+        self.e3d_critic = e3d_critic_options(cfg)   # the critic's input with every team-mate
+        # the width of the critic's rows; feat_dim stays the actor's
+        self.critic_feat_dim = central_feat(int(cfg.env.num_defender)) if self.e3d_critic == "central" else self.feat_dim
         self.use_obs_norm, self.obs_norm_clip = onorm.obs_norm_options(cfg)   # running mean / std on the policy features
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
@@ -174,7 +196,7 @@ class E3dMAPPO(ParticleMAPPO):
         a, sn = cfg.algo, bool(cfg.algo.use_spectral_norm)
         self.actor = GaussianActor(self.feat_dim, self.embedding_dim, self.latent_dim, self.num_layers, self.rnn_hidden_dim,
                                    float(a.get("log_std_init", 0.0)), sn, self.gauss_std).to(self.device)
-        self.critic = E3dCritic(self.feat_dim, self.embedding_dim, self.num_layers, self.rnn_hidden_dim, sn).to(self.device)
+        self.critic = E3dCritic(self.critic_feat_dim, self.embedding_dim, self.num_layers, self.rnn_hidden_dim, sn).to(self.device)
         self.ac_parameters = list(self.actor.parameters()) + list(self.critic.parameters())
         self.obs_norm = onorm.ObsNorm(self.obs_norm_clip, self.device) if self.use_obs_norm else None
 
@@ -189,7 +211,7 @@ class E3dMAPPO(ParticleMAPPO):
         """features -> both encoders -> both GRU cells (one launch per layer) -> value -> Gaussian head and sample"""
         N, P, E = st.N, st.P, self.embedding_dim
         emb_a = self.actor.shared_net(st.fa.view(N * P, self.feat_dim))
-        emb_c = self.critic.shared_net(st.fc.view(N * P, self.feat_dim))
+        emb_c = self.critic.shared_net(st.fc.view(N * P, self.critic_feat_dim))
         cur, nxt = st.t & 1, (st.t + 1) & 1
         fa, fc = ops.gru_step_multi([emb_a.reshape(-1, E), emb_c.reshape(-1, E)], [st.hbuf_a[cur], st.hbuf_c[cur]], [self.actor.GRU, self.critic.GRU],
                                     hiddens_out=[st.hbuf_a[nxt], st.hbuf_c[nxt]])
@@ -208,7 +230,10 @@ class E3dMAPPO(ParticleMAPPO):
     def _features(self, env, st, accumulate=False):
         """the policy features of the current state into st.fa / st.fc; with algo.use_obs_norm normalised under the agent's state, and,
         when `accumulate` (the ticks of a training rollout), the sums of the raw features of the live rows added to the slots;
-        with algo.e3d_features: pursuit the 32 line-of-sight features under algo.e3d_evader_obs (never normalised)"""
+        with algo.e3d_features: pursuit the 32 line-of-sight features under algo.e3d_evader_obs (never normalised), and with
+        algo.e3d_critic: central the wide critic rows from the same launch"""
+        if self.e3d_critic == "central":
+            return env.central_features(st.fa, st.fc, self.e3d_evader_obs)
         if self.e3d_features == "pursuit":
             return env.pursuit_features(st.fa, st.fc, self.e3d_evader_obs)
         on = self.obs_norm
@@ -221,13 +246,13 @@ class E3dMAPPO(ParticleMAPPO):
     def _bootstrap_value(self, st):
         """the critic's value of the state after the last step (its encoder, GRU cell and head only)"""
         N, P = st.N, st.P
-        emb_c = self.critic.shared_net(st.fc.view(N * P, self.feat_dim))
+        emb_c = self.critic.shared_net(st.fc.view(N * P, self.critic_feat_dim))
         (fc,) = ops.gru_step_multi([emb_c.reshape(N * P, -1)], [st.hbuf_c[st.t & 1]], [self.critic.GRU], hiddens_out=[st.hbuf_c[(st.t + 1) & 1]])
         return self.critic.head(fc.contiguous()).reshape(N, P)
 
     def new_buffer(self, N, T, P):
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)
-        buf = dict(feat_a=z(N, T, P, self.feat_dim), feat_c=z(N, T, P, self.feat_dim), a_n=z(N, T, P, self.latent_dim), a_logprob_n=z(N, T, P), r=z(N, T, P),
+        buf = dict(feat_a=z(N, T, P, self.feat_dim), feat_c=z(N, T, P, self.critic_feat_dim), a_n=z(N, T, P, self.latent_dim), a_logprob_n=z(N, T, P), r=z(N, T, P),
                    active=z(N, T, P), v_n=z(N, T + 1, P))
         if self.value_norm is not None:
             buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
@@ -286,11 +311,11 @@ class E3dMAPPO(ParticleMAPPO):
 
     # ---- update ------------------------------------------------------------------------------------------------------------------
     def sequence_forward(self, feat_a, feat_c, batch, steps, return_ls_raw=False):
-        """(batch, T, P, feat_dim) features of whole episodes -> mu (batch, T, P, A) and values (batch, T, P), time-major views; with
+        """(batch, T, P, feat_dim / critic_feat_dim) features of whole episodes -> mu (batch, T, P, A) and values (batch, T, P), time-major views; with
         return_ls_raw also ls_raw (state mode: the LogStd head on the same GRU features, (batch, T, P, A); param mode: log_std)"""
         P = feat_a.shape[2]
         R = batch * steps * P
-        emb_a, emb_c = self.actor.shared_net(feat_a.reshape(R, self.feat_dim)), self.critic.shared_net(feat_c.reshape(R, self.feat_dim))
+        emb_a, emb_c = self.actor.shared_net(feat_a.reshape(R, self.feat_dim)), self.critic.shared_net(feat_c.reshape(R, self.critic_feat_dim))
         h0 = [torch.zeros(m.num_layers, batch * P, m.rnn_hidden_dim, dtype=emb_a.dtype, device=emb_a.device) for m in (self.actor, self.critic)]
         fa, fc = ops.gru_multi([emb_a, emb_c], h0, [self.actor.GRU, self.critic.GRU], agents=P, steps=steps, zero_state=True)
         fa, fc = fa.reshape(steps, batch, P, -1), fc.reshape(steps, batch, P, -1)
@@ -338,21 +363,24 @@ class E3dMAPPO(ParticleMAPPO):
 
     def policy_meta(self):
         """the "policy" entry of checkpoints and resume bundles: None in the default mode (param, clip, basic features), whose files
-        carry none; e3d_features / e3d_evader_obs only with algo.e3d_features: pursuit"""
+        carry none; e3d_features / e3d_evader_obs only with algo.e3d_features: pursuit, e3d_critic only with algo.e3d_critic: central"""
         meta = {}
         if self.policy_ex:
             meta.update(gauss_std=self.gauss_std, gauss_squash=self.gauss_squash, log_std_min=self.log_std_min, log_std_max=self.log_std_max)
         if self.e3d_features == "pursuit":
             meta.update(e3d_features=self.e3d_features, e3d_evader_obs=self.e3d_evader_obs)
+        if self.e3d_critic == "central":
+            meta.update(e3d_critic=self.e3d_critic)
         return meta or None
 
     def check_policy_meta(self, meta, what):
         """ValueError naming the config key when a file's policy (its "policy" entry; None = the default mode) is not this agent's:
         gauss_std and gauss_squash, and with an option on (where the bounds act) log_std_min / log_std_max as well -- other bounds would
         neither reproduce the saved policy nor continue its run bit for bit; and the feature set and its evader model (a file without the
-        entries was written with basic, sensed): other inputs fit neither the first layer nor what the weights were trained on"""
+        entries was written with basic, sensed, local): other inputs fit neither the first layer nor what the weights were trained on"""
         meta = meta or {}
-        for key, default in (("e3d_features", "basic"), ("e3d_evader_obs", "sensed"), ("gauss_std", "param"), ("gauss_squash", "clip")):
+        for key, default in (("e3d_features", "basic"), ("e3d_evader_obs", "sensed"), ("e3d_critic", "local"), ("gauss_std", "param"),
+                             ("gauss_squash", "clip")):
             theirs, mine = meta.get(key, default), getattr(self, key, default)
             if theirs != mine:
                 raise ValueError(f"{what} was written with algo.{key}: {theirs}, this agent has algo.{key}: {mine}")

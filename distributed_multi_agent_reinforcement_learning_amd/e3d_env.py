@@ -93,6 +93,8 @@ def load_library():
         L.e3d_pursuer_guidance.argtypes = [vp] * 5
         L.e3d_pursuit_features.argtypes = [vp] * 3 + [C.c_int32] + [vp] * 3
         L.e3d_pursuit_features_host.argtypes = [vp, C.c_int32] + [vp] * 6 + [C.c_int32, vp, vp]
+        L.e3d_central_features.argtypes = [vp] * 3 + [C.c_int32] + [vp] * 3
+        L.e3d_central_features_host.argtypes = [vp, C.c_int32] + [vp] * 6 + [C.c_int32, vp, vp]
         L.gauss_direction_map_host.argtypes = [C.c_int32, vp, vp]
         L.e3d_direction_label_host.argtypes = [C.c_int32, vp, vp]
         _lib = L
@@ -107,6 +109,13 @@ def _check(rc, what):
 
 PURSUIT_FEAT = 32                              # E3D_FEAT2: the columns of pursuit_features
 EVADER_OBS = ("sensed", "team", "global")      # E3D_EVADER_OBS_SENSED / _TEAM / _GLOBAL = the index
+CENTRAL_MATE = 8                               # E3D_CENTRAL_MATE: the columns of one team-mate's slot in central_features' critic row
+CENTRAL_MAX_P = 16                             # E3D_CENTRAL_MAX_P
+
+
+def central_feat(P):
+    """E3D_CENTRAL_FEAT(P): the columns of central_features' critic row, the 32 of pursuit_features and a slot per team-mate"""
+    return PURSUIT_FEAT + CENTRAL_MATE * (P - 1)
 
 
 def evader_obs_code(name):
@@ -300,6 +309,19 @@ class ParticleEnv:
             assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (self.num_envs, self.p_num, PURSUIT_FEAT) and t.device == self.p.device
         _check(self.L.e3d_pursuit_features(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_int32(code),
                                            C.c_void_p(actor_feat.data_ptr()), C.c_void_p(critic_feat.data_ptr()), _stream()), "e3d_pursuit_features")
+        return actor_feat, critic_feat
+
+    def central_features(self, actor_feat, critic_feat, evader_obs="sensed"):
+        """pursuit_features with the centralised critic row (algo.e3d_critic: central; e3d_central_features, include/e3d_env.h;
+        specification: tests/central_critic_ref.py): actor_feat (N, P, 32) is what pursuit_features writes; critic_feat is
+        (N, P, central_feat(P)), the 32 critic columns and then, for every active team-mate in the order of distance, its direction,
+        range, heading and speed (8 columns; slots past the last team-mate are zero).  P <= CENTRAL_MAX_P.  One launch; nothing but
+        the two tensors is written."""
+        code = evader_obs_code(evader_obs)
+        for t, width in ((actor_feat, PURSUIT_FEAT), (critic_feat, central_feat(self.p_num))):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (self.num_envs, self.p_num, width) and t.device == self.p.device
+        _check(self.L.e3d_central_features(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_int32(code),
+                                           C.c_void_p(actor_feat.data_ptr()), C.c_void_p(critic_feat.data_ptr()), _stream()), "e3d_central_features")
         return actor_feat, critic_feat
 
     # ---- MAPPO on env_3d (e3d_agent.py): the bookkeeping of one lockstep tick, one launch after step() ------------------------------

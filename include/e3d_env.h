@@ -184,6 +184,29 @@ int e3d_pursuit_features(const e3d_config *cfg, const e3d_state *st, const e3d_o
 int e3d_pursuit_features_host(const e3d_config *cfg, int32_t N, const double *p, const double *e, const double *target, const int32_t *time_step,
                               const float *pp_adj, const float *pe_adj, int32_t evader_obs, float *actor_feat, float *critic_feat);
 
+/* ---- algo.e3d_critic: central -- the critic's row with every team-mate in it (csrc/central_critic.hpp, DESIGN.md section 7k;
+ * specification: tests/central_critic_ref.py) ----
+ * e3d_pursuit_features with a wider critic tensor, in one launch: actor_feat (N, P, E3D_FEAT2) is byte for byte what
+ * e3d_pursuit_features writes under the same evader_obs; critic_feat is (N, P, E3D_CENTRAL_FEAT(P)) fp32, dense, 16-byte aligned.
+ * The critic's row of an active pursuer i:
+ *   0-31             the critic row of e3d_pursuit_features
+ *   32 + 8 s ...     slot s = 0 .. P - 2: the s-th team-mate j of V_i, the active j != i in the order of dx dx + dy dy + dz dz (strict <:
+ *                    the lowest index first on an exact tie) --
+ *                    0-2 (p_j - p_i) / d_ij (0 when d_ij is 0)   3 d_ij / W   4-6 u_j   7 v_j / p_vmax
+ * Slots s >= |V_i| are zero, and so is the row of an inactive pursuer.  A slot's 0-3 are the values of the nearest-two blocks (columns
+ * 20-23, 25-28 for s = 0, 1), its 4-7 are columns 3-6 of team-mate j's own row.  f64 arithmetic in the order written, rounded to fp32
+ * at the store.  The tick's lane layout, team-mates through shuffles, no LDS, no atomics, no host synchronisation; only the two outputs
+ * are written.  P > E3D_CENTRAL_MAX_P, an evader_obs that is none of the three, or a misaligned output: E3D_ERR_BAD_CONFIG, before any
+ * launch; N = 0 touches nothing. */
+#define E3D_CENTRAL_MATE 8
+#define E3D_CENTRAL_MAX_P 16
+#define E3D_CENTRAL_FEAT(P) (E3D_FEAT2 + E3D_CENTRAL_MATE * ((P) - 1))
+int e3d_central_features(const e3d_config *cfg, const e3d_state *st, const e3d_obs_out *out, int32_t evader_obs, float *actor_feat,
+                         float *critic_feat, void *stream);
+/* The same computation on the host, on the inputs of e3d_pursuit_features_host; no alignment is required of the outputs. */
+int e3d_central_features_host(const e3d_config *cfg, int32_t N, const double *p, const double *e, const double *target, const int32_t *time_step,
+                              const float *pp_adj, const float *pe_adj, int32_t evader_obs, float *actor_feat, float *critic_feat);
+
 /* ---- algo.gauss_squash: direction -- the map of the direction-vector action head on the host (csrc/direction_action.hpp, DESIGN.md
  * section 7h; specification: tests/direction_ref.py).  The device side is gauss_head_sample_ex / e3d_bc_select of mappo_ops.h ----
  * gauss_direction_map_host: u [R][4] fp32, the policy's latent action (u_x, u_y, u_z, s) -> env_action [R][3] f64,
