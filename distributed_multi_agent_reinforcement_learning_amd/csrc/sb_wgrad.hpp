@@ -16,10 +16,11 @@
 // while the MFMA waves multiply chunk c, one barrier per chunk.  Each loader lane keeps the raw rows of DEPTH chunks in flight (96 KB
 // per CU at M + N = 512: 2 units per lane and chunk, 3 chunks; 64 KB at M + N = 256: 1 unit, 4 chunks), so the prefetch depth is no longer paid for out of the MFMA waves' registers, and
 // the MFMA stream of a SIMD is never interrupted by splitting.  All 12 waves get the same register allocation: 168 per lane at 3 waves
-// per SIMD; the kernels take 110 (128 x 128), 136 (128 x 256, 256 x 128), 149 (384 x 128) and 155 (128 x 384), no scratch
+// per SIMD; the kernels take 110 (128 x 128), 136 (128 x 256, 256 x 128), 148 (384 x 128) and 153 (128 x 384), no scratch
 // (hipcc -Rpass-analysis=kernel-resource-usage).  DESIGN.md section 11 has the kernel times.
 // The chunk ranges, the chunk order and the order of the six piece products are those of the 8-wave kernel this replaces: every
-// output sees the same sums in the same order, bit for bit.
+// output sees the same sums in the same order, bit for bit.  The K % 16 rows behind the last full chunk are the exception: the last
+// workgroup multiplies them in fp32 itself (see sb_wgrad_mma), after its chunks, the same way at every launch.
 constexpr int SB_WG_MMA_WAVES = 8, SB_WG_LOAD_WAVES = 4, SB_WG_THREADS = 64 * (SB_WG_MMA_WAVES + SB_WG_LOAD_WAVES);
 
 template <int MT, int NT>
@@ -121,15 +122,19 @@ __device__ __forceinline__ void sb_wgrad_loader(int lw, int lane, const float *_
             lds_barrier();
         }
     }
-    if (tail) {                                          // the K % 16 rows after the last full chunk, zero-filled
+    if (tail) {                                          // the K % 16 rows after the last full chunk, zero-filled: raw fp32, [row][COLS] over image 0
         const int64_t r0 = (K / C::CR) * C::CR;
-        float4 r[C::UL][4];
+        float4 *rawf = (float4 *)sb_lds;                 // 64 COLS of the image's 96 COLS bytes; every MFMA wave is past its last chunk here
 #pragma unroll
-        for (int u = 0; u < C::UL; u++)
+        for (int u = 0; u < C::UL; u++) {
+            if (!on[u]) continue;
+            const int unit = 64 * lw + lane + C::LT * u, col = 4 * (unit % C::FQ);
 #pragma unroll
-            for (int j = 0; j < 4; j++)
-                r[u][j] = (on[u] && r0 + row_in_chunk[u] + j < K) ? *(const float4 *)(src[u] + (r0 + j) * ld[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        stage(r, sb_lds);
+            for (int j = 0; j < 4; j++) {
+                const int row = row_in_chunk[u] + j;
+                rawf[(row * C::COLS + col) >> 2] = r0 + row < K ? *(const float4 *)(src[u] + (r0 + j) * ld[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
         lds_barrier();
     }
 }
@@ -192,8 +197,25 @@ __device__ __forceinline__ void sb_wgrad_mma(int wave, int lane, int64_t c_beg, 
         lds_barrier();
     }
     if (tail) {
+        // The tail rows are multiplied in fp32 itself (v_mfma_f32_32x32x2_f32: a chain of round-to-nearest multiply-adds; lane (i, g)
+        // feeds tile row / column i of row 2 s + g), not as piece products: a product of fewer than 16 rows, which is a tail alone,
+        // then meets the K 2^-24 bound of an fp32 dot product, which the bf16 instruction's truncated accumulation misses at K = 1
+        // (DESIGN.md section 3.7).  The benchmark's row counts are multiples of 16 and never come here.
         lds_barrier();
-        multiply(sb_lds);
+        const float *rawf = (const float *)sb_lds;
+#pragma unroll 1
+        for (int s = 0; s < C::CR / 2; s++) {
+            const float *row = rawf + (2 * s + g) * C::COLS;
+            float b[C::TN];
+#pragma unroll
+            for (int nt = 0; nt < C::TN; nt++) b[nt] = row[C::M + 32 * (wn * C::TN + nt) + i];
+#pragma unroll
+            for (int mt = 0; mt < C::TM; mt++) {
+                const float a = row[32 * (wm * C::TM + mt) + i];
+#pragma unroll
+                for (int nt = 0; nt < C::TN; nt++) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[nt], acc[mt][nt], 0, 0, 0);
+            }
+        }
     }
     // D tile (32 x 32): lane (i, g), register r -> row 8 (r / 4) + 4 g + r % 4 (the A operand's tile row: an M index), column i
     float *po = part + (size_t)blockIdx.x * C::M * C::N + (size_t)(32 * wm * C::TM + 4 * g) * C::N + 32 * wn * C::TN + i;

@@ -156,8 +156,9 @@ def test_fused_gru_matches_torch_gru(T, B):
 @pytest.mark.parametrize("K,M,N,pad", [(492000, 384, 128, 0), (492000, 128, 384, 4), (487203, 128, 128, 0), (4099, 256, 128, 0),
                                        (4096, 128, 256, 8), (65537, 384, 128, 0)])
 def test_wgrad_matches_f64_reference(K, M, N, pad):
-    """split-K MFMA weight-gradient GEMM (csrc/mappo_ops.hip k_wgrad) vs a float64 a^T b; K % 4 tails, strided rows,
-    accumulate, run-to-run determinism"""
+    """ops.wgrad vs a float64 a^T b; tails, strided rows, accumulate, run-to-run determinism.  In the default split_bf16 mode every
+    shape here is in SPLIT_WGRAD_SHAPES and runs csrc/sb_wgrad.hpp k_sb_wgrad (K % 16 tails); only MAPPO_WGRAD=fp32 sends them to
+    csrc/mappo_ops.hip k_wgrad (K % 4 tails), which tests/test_wgrad_edges_gpu.py runs on purpose"""
     from distributed_multi_agent_reinforcement_learning_amd import ops
     g = torch.Generator(device="cuda").manual_seed(K + M)
     a_full = torch.randn((K, M + pad), generator=g, device="cuda")

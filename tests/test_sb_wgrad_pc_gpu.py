@@ -2,8 +2,9 @@
 
 wgrad_split_tn / wgrad_split_tn2 against an f64 product, held to the bound tests/test_split_bf16_gpu.py holds the split kernels to
 (at most twice the fp32 library's error plus one fp32 ulp, in units of each dot product's own scale), and run twice for identical bits.
-Covers every loader layout (M + N = 256: one unit per loader lane; 512: two), the A2 column-block form of dW_hh, a K % 16 tail, row
-strides wider than the operands and accumulate=1.
+Covers every loader layout (M + N = 256: one unit per loader lane; 512: two; 384: two, the second switched off in two of the four
+loader waves), the A2 column-block form of dW_hh, a K % 16 tail, row strides wider than the operands and accumulate=1.  The chunk
+counts between these row counts and the few-row ones are in tests/test_wgrad_edges_gpu.py.
 """
 import pytest
 import torch
