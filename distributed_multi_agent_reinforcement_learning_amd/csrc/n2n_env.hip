@@ -402,6 +402,8 @@ __global__ __launch_bounds__(WAVE) void k_n2n_evader(const n2n_config c, const n
 int launch_n2n_evader(const n2n_config *c, const n2n_state *st, double *e_cmd, int32_t *nit, hipStream_t s) {
     const long long lanes = (long long)st->N * c->E;
     if (lanes == 0) return 0;
+    // 2 P 64 doubles is 65536 bytes at P = N2N_MAX_P = 64, so the 32-lane shape is never taken here (env_3d's, with 3 P, is from P = 43);
+    // it stays as the guard it is should N2N_MAX_P grow
     const int tpb = (size_t)2 * c->P * WAVE * sizeof(double) <= 65536 ? WAVE : WAVE / 2;
     const unsigned blocks = (unsigned)((lanes + tpb - 1) / tpb);
     const size_t lds = (size_t)2 * c->P * tpb * sizeof(double);
@@ -433,17 +435,23 @@ __global__ void k_aos_to_soa(int N, int A, const double *aos, double *soa) {
 
 struct N2nResetter { n2n_config cfg; int N; std::vector<rngrep::NpRandom> rng; };
 
-void sample_points(rngrep::NpRandom &g, int n, double lx, double ly, double lo, double hi, std::vector<double> &pts) {
+// false: the placement loop drew N2N_RESET_MAX_DRAWS candidates without seating all n points; it gives up like env_3d's (the
+// candidate past the bound is kept, so pts is full and the generator stream up to the bound is the reference's)
+bool sample_points(rngrep::NpRandom &g, int n, double lx, double ly, double lo, double hi, std::vector<double> &pts) {
     // gen_init_p_pos / gen_init_e_pos (:239-281): normal(loc, 2, size 2).clip(lo, hi), rejected when < 2 from an earlier point
     pts.clear();
+    int draws = 0;
+    bool placed = true;
     while ((int)pts.size() < 2 * n) {
         double x = g.normal(lx, 2.0), y = g.normal(ly, 2.0);
         x = x < lo ? lo : (x > hi ? hi : x);
         y = y < lo ? lo : (y > hi ? hi : y);
         bool ok = true;
-        for (size_t k = 0; k < pts.size() && ok; k += 2) ok = !(norm2(x - pts[k], y - pts[k + 1]) < 2.0);
+        if (++draws > N2N_RESET_MAX_DRAWS) placed = false;   // give up: keep this candidate, report the environment
+        else for (size_t k = 0; k < pts.size() && ok; k += 2) ok = !(norm2(x - pts[k], y - pts[k + 1]) < 2.0);
         if (ok) { pts.push_back(x); pts.push_back(y); }
     }
+    return placed;
 }
 
 // phi [N][P] = the shaping potential of the current records (n2n_shaping_begin): the tick's lane layout, one store per lane
@@ -690,18 +698,19 @@ int n2n_resetter_reset(void *h, double *p, double *e, double *target, int32_t n_
     const int P = R.cfg.P, E = R.cfg.E;
     if (n_threads < 1) n_threads = 1;
     if (n_threads > R.N) n_threads = R.N;
+    std::vector<int> failed(n_threads, 0);
     auto work = [&](int t) {
         std::vector<double> pts;
         for (int n = t; n < R.N; n += n_threads) {
             rngrep::NpRandom &g = R.rng[n];
             const double tx = g.random_sample() * 20, ty = g.random_sample() * 20;  // reset (:200-204)
             target[2 * n] = tx; target[2 * n + 1] = ty;
-            sample_points(g, P, 0.0, 0.0, -8.0, 8.0, pts);
+            if (!sample_points(g, P, 0.0, 0.0, -8.0, 8.0, pts)) failed[t] = 1;
             for (int i = 0; i < P; i++) {
                 double *s = p + ((size_t)n * P + i) * 5;
                 s[0] = pts[2 * i] + 10; s[1] = pts[2 * i + 1] + 10; s[2] = PI / 4; s[3] = 0.0; s[4] = 1.0;
             }
-            sample_points(g, E, 20 - tx, 20 - ty, 0.0, 20.0, pts);
+            if (!sample_points(g, E, 20 - tx, 20 - ty, 0.0, 20.0, pts)) failed[t] = 1;
             for (int i = 0; i < E; i++) {
                 double *s = e + ((size_t)n * E + i) * 5;
                 s[0] = pts[2 * i]; s[1] = pts[2 * i + 1]; s[2] = PI / 4; s[3] = R.cfg.e_vmax; s[4] = 1.0;
@@ -714,6 +723,8 @@ int n2n_resetter_reset(void *h, double *p, double *e, double *target, int32_t n_
         for (int t = 0; t < n_threads; t++) th.emplace_back(work, t);
         for (auto &x : th) x.join();
     }
+    for (int t = 0; t < n_threads; t++)
+        if (failed[t]) return N2N_ERR_RESET_FAILED;
     return 0;
 }
 

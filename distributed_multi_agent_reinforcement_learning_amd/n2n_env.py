@@ -97,7 +97,8 @@ def load_library():
 
 def _check(rc, what):
     if rc != 0:
-        raise RuntimeError(f"{what} failed with code {rc}")
+        extra = " (no placement within N2N_RESET_MAX_DRAWS draws: too many agents for the box at distance 2)" if rc == 30004 else ""
+        raise RuntimeError(f"{what} failed with code {rc}{extra}")
 
 
 def _stream():

@@ -20,7 +20,13 @@ extern "C" {
 #define N2N_ERR_BAD_CONFIG 30001
 #define N2N_ERR_NULL 30002
 #define N2N_ERR_BAD_STATE 30003      /* n2n_resetter_set_state: the blob's header does not match this resetter */
+#define N2N_ERR_RESET_FAILED 30004   /* gen_init_p_pos / gen_init_e_pos (:239-281) found no placement within N2N_RESET_MAX_DRAWS draws */
 #define N2N_RESETTER_STATE_TAG 0x3152324eu   /* "N2R1": format of n2n_resetter_get_state */
+/* The reference's placement loops reject a candidate closer than 2 to an earlier point and never give up; in the 16 x 16 box of the
+ * pursuers that stops converging between 40 and 48 of them.  Each loop here (pursuers, evaders) draws at most this many candidates, then
+ * keeps the last one and n2n_resetter_reset returns N2N_ERR_RESET_FAILED; the value and the meaning are those of E3D_RESET_MAX_DRAWS and
+ * PE_RESET_MAX_DRAWS.  A reset that succeeds consumes the generator exactly as the reference does. */
+#define N2N_RESET_MAX_DRAWS 100000
 
 typedef struct n2n_config {      /* particle_env.py:108-121,147 */
     int32_t P, E, episode_limit, pad0;
@@ -150,7 +156,8 @@ typedef struct n2n_guidance_params { double lead, sep_range, sep_gain; } n2n_gui
 int n2n_pursuer_guidance(const n2n_config *cfg, const n2n_state *st, const n2n_guidance_params *params, int32_t *actions, void *stream);
 
 /* Host side of ParticleEnv.reset (:200-281) with a bit-exact replica of numpy's legacy RandomState per environment
- * (np.random.seed(seeds[n])).  Fills host arrays p [N][P][5], e [N][E][5], target [N][2]. */
+ * (np.random.seed(seeds[n])).  Fills host arrays p [N][P][5], e [N][E][5], target [N][2].  N2N_ERR_RESET_FAILED when a placement loop
+ * of any environment gave up (N2N_RESET_MAX_DRAWS); the arrays are filled all the same, with points that may be closer than 2. */
 void *n2n_resetter_create(const n2n_config *cfg, int32_t N, const uint32_t *seeds);
 void n2n_resetter_destroy(void *resetter);
 int n2n_resetter_reset(void *resetter, double *p, double *e, double *target, int32_t n_threads);

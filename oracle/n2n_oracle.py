@@ -8,6 +8,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libn2n_oracle.so")
+MAX_DRAWS = 100000  # include/n2n_env.h N2N_RESET_MAX_DRAWS: bound on each of the reference's unbounded placement loops
 
 
 class N2nCfg(C.Structure):
@@ -72,13 +73,20 @@ class OracleN2n:
         return r, bool(done), act
 
 
+class ResetFailed(RuntimeError):
+    pass
+
+
 def reset_oracle(P, E, e_vmax=1.0, nprnd=np.random):
     """ParticleEnv.reset (:200-281): target, pursuers around (10, 10), evaders around (20, 20) - target; numpy global RNG."""
     target = [nprnd.rand() * 20, nprnd.rand() * 20]
 
     def sample(n, loc, lo, hi):
-        pts = []
+        pts, draws = [], 0
         while len(pts) < n:
+            draws += 1
+            if draws > MAX_DRAWS:
+                raise ResetFailed("gen_init_p_pos / gen_init_e_pos")
             newp = nprnd.normal(loc=loc, scale=2, size=(2,)).clip(lo, hi)
             if not any(np.linalg.norm(newp - q) < 2 for q in pts):
                 pts.append(newp)

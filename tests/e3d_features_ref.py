@@ -148,3 +148,26 @@ def nearest_gap(p, pp_adj=None):
             for a, b in zip(d, d[1:]):     # every adjacent pair: a subset's nearest two are adjacent in some subset, never closer than these
                 gap = min(gap, (b - a) / max(b, 1e-300))
     return gap, rows
+
+
+def policy_features(p, e, pp, pe):
+    """the 16 basic features of e3d_policy_features (algo.e3d_features: basic), which the GPU tests hold to 1e-6 (rtol and atol):
+    p (N, 7, P), e (N, 7) f64 records; pp (N, P, P), pe (N, P) -> actor, critic (N, P, 16) fp32"""
+    N, _, P = p.shape
+    fa, fc = np.zeros((N, P, 16), np.float32), np.zeros((N, P, 16), np.float32)
+    for n in range(N):
+        for i in range(P):
+            if p[n, 6, i] == 0:
+                continue
+            s = p[n, :6, i]
+            ae = e[n, 6]
+            fa[n, i, :6] = fc[n, i, :6] = s
+            fa[n, i, 6:12] = (e[n, :6] - s) * pe[n, i]
+            fc[n, i, 6:12] = (e[n, :6] - s) * ae
+            fa[n, i, 12], fc[n, i, 12] = pe[n, i], ae
+            ja = [j for j in range(P) if j != i and pp[n, i, j] == 1]
+            jc = [j for j in range(P) if j != i and p[n, 6, j] != 0]
+            for js, f in ((ja, fa), (jc, fc)):
+                if js:
+                    f[n, i, 13:16] = np.mean([p[n, :3, j] - p[n, :3, i] for j in js], axis=0)
+    return fa, fc

@@ -165,3 +165,73 @@ def e3d_check(groups, cmds):
             f_ref, f_dev = e3d_objective(g["ref"][i], *args), e3d_objective(c[i], *args)
             assert f_dev <= f_ref + 1e-6 * max(1.0, abs(f_ref)), (g["name"], i, f_dev, f_ref)
     return n, hit
+
+
+# ---- above 16 pursuers: evader_n2n_wide.npz / evader_e3d_wide.npz (tests/golden/gen/make_goldens_evader_wide.py) ----
+
+N2N_WIDE_P = (17, 32, 33, 64)                # PM 32, 32, 64, 64
+E3D_WIDE_P = (17, 32, 33, 42, 43, 64)        # ... and 42 / 43: the last 64-lane launch (64 512 B of LDS) and the first 32-lane one
+
+
+def n2n_wide_groups():
+    """as n2n_groups(), one group per pursuer count, with `stable`: the mask the generator computed from the reference alone (its
+    command moves by at most 1e-7 when every number of the problem moves by a relative 1e-12)"""
+    d = np.load(os.path.join(GOLDEN, "evader_n2n_wide.npz"))
+    out = []
+    for P in N2N_WIDE_P:
+        e = d[f"P{P}_e"]
+        out.append(dict(name=f"evader_n2n_wide_P{P}", cfg=d["cfg"], P=P, E=1, p=np.ascontiguousarray(d[f"P{P}_p"].transpose(0, 2, 1)),
+                        e=np.ascontiguousarray(e[:, :, None]), target=d[f"P{P}_target"], ref=d[f"P{P}_cmd"][:, None],
+                        called=(e[:, 4] > 0)[:, None], stable=d[f"P{P}_stable"][:, None]))
+    return out
+
+
+def e3d_wide_groups():
+    d = np.load(os.path.join(GOLDEN, "evader_e3d_wide.npz"))
+    out = []
+    for P in E3D_WIDE_P:
+        p, e = d[f"P{P}_p"], d[f"P{P}_e"]
+        out.append(dict(name=f"evader_e3d_wide_P{P}", cfg=d["cfg"], P=P, p=np.ascontiguousarray(p.transpose(0, 2, 1)), e=e,
+                        target=d[f"P{P}_target"], ref=d[f"P{P}_cmd"], called=(e[:, 6] > 0) & (p[:, :, 6] > 0).any(1),
+                        stable=d[f"P{P}_stable"]))
+    return out
+
+
+def check_nit(g, nit):
+    """the iteration count is in 1..100 exactly where the reference calls e_f"""
+    assert np.all((nit >= 1) == g["called"]) and nit.max() <= 100 and nit.min() >= 0, g["name"]
+
+
+def n2n_wide_check(g, cmd, nit):
+    """one wide env_n2n group: zeros and iteration counts on every problem; on the stable ones at least 97 % within 1e-6 of the
+    reference and none beyond 1e-3.  -> (stable calls, hits)"""
+    n2n_check([g], [cmd])                                                  # uncalled evaders get exactly 0
+    check_nit(g, nit)
+    err = np.abs(cmd - g["ref"])[g["called"] & g["stable"]]
+    hit = int((err <= 1e-6).sum())
+    print(f"{g['name']}: {hit} of {err.size} stable problems within 1e-6, worst {err.max(initial=0.0):.2e}; "
+          f"{int((g['called'] & ~g['stable']).sum())} unstable")
+    assert hit >= 0.97 * err.size, (g["name"], hit, err.size)
+    assert err.max(initial=0.0) <= 1e-3, (g["name"], err.max())
+    return err.size, hit
+
+
+def e3d_wide_check(g, cmd, nit):
+    """one wide env_3d group: zeros, iteration counts, bounds and the objective rule of e3d_check for misses beyond 1e-3 on every
+    problem; on the stable ones at least 90 % within 1e-6.  -> (stable calls, hits)"""
+    e3d_check([g], [cmd])
+    check_nit(g, nit)
+    cfg = dict(zip(E3D_KEYS, g["cfg"]))
+    for i in np.nonzero(g["called"])[0]:
+        lb, ub = e3d_bounds(g["e"][i], cfg["ang_lmt"], cfg["v_lmt"])
+        assert np.all(cmd[i] >= lb - 1e-12) and np.all(cmd[i] <= ub + 1e-12), (g["name"], i, cmd[i], lb, ub)
+    err = np.abs(cmd - g["ref"]).max(1)[g["called"] & g["stable"]]
+    hit = int((err <= 1e-6).sum())
+    print(f"{g['name']}: {hit} of {err.size} stable problems within 1e-6; {int((g['called'] & ~g['stable']).sum())} unstable")
+    assert hit >= 0.90 * err.size, (g["name"], hit, err.size)
+    return err.size, hit
+
+
+def stable_share(g):
+    """share of the problems the reference calls e_f on that are stable"""
+    return float(g["stable"][g["called"]].mean())

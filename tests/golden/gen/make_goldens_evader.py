@@ -60,74 +60,98 @@ def _kinds(rng):
     return rng.choice(["generic", "none_in_range", "kill", "inactive_ahead", "generic"])
 
 
+def n2n_problem(rng, P):
+    """one sampled env_n2n problem: e [5], p [P, 5], target [2]"""
+    kind = _kinds(rng)
+    e = np.array([rng.uniform(2, 18), rng.uniform(2, 18), rng.uniform(-np.pi, np.pi), 1.0, 1.0])
+    if rng.random() < 0.03:
+        e = np.array([1000.0, 1000.0, 0.0, 1.0, 0.0])  # a captured evader: e_f is not called
+    xy = _around(rng, e[:2], P, kind, 2)
+    p = np.zeros((P, 5))
+    p[:, :2] = xy
+    p[:, 2] = rng.uniform(-np.pi, np.pi, P)
+    p[:, 3] = np.where(rng.random(P) < 0.3, 0.0, rng.uniform(0.0, 0.3, P))  # distinct speeds expose p_v0[ne]
+    p[:, 4] = _active(rng, P, kind)
+    p[p[:, 4] == 0, :3] = (1000.0, 1000.0, 0.0)
+    tg = rng.uniform(0, 20, 2)
+    return _f32(e), _f32(p), _f32(tg)
+
+
+def n2n_command(eva, e, p, tg):
+    """the reference's command for one problem, 0 where evader_step does not call e_f"""
+    if not e[4] > 0:
+        return 0.0
+    on = p[:, 4] > 0
+    return float(eva.e_f(xy=np.array(e[:2]), e_ga=e[2], e_v=e[3], e_sr=E_SR, npx=list(p[on, 0]), npy=list(p[on, 1]),
+                         bet=list(p[on, 2]), p_v=list(p[:, 3]), p_=10, d_=1, m_=5, tp=list(tg)))
+
+
+N2N_CFG = np.asarray([0.3, 1.0, 3.0, 6.0, 0.5, np.pi / 4, 0.5])
+
+
 def n2n(rng, per_p):
     from environment.env_n2n import eva
     out = {}
     for P in PS:
         ps, es, ts, cs = [], [], [], []
         for _ in range(per_p):
-            kind = _kinds(rng)
-            e = np.array([rng.uniform(2, 18), rng.uniform(2, 18), rng.uniform(-np.pi, np.pi), 1.0, 1.0])
-            if rng.random() < 0.03:
-                e = np.array([1000.0, 1000.0, 0.0, 1.0, 0.0])  # a captured evader: e_f is not called
-            xy = _around(rng, e[:2], P, kind, 2)
-            p = np.zeros((P, 5))
-            p[:, :2] = xy
-            p[:, 2] = rng.uniform(-np.pi, np.pi, P)
-            p[:, 3] = np.where(rng.random(P) < 0.3, 0.0, rng.uniform(0.0, 0.3, P))  # distinct speeds expose p_v0[ne]
-            p[:, 4] = _active(rng, P, kind)
-            p[p[:, 4] == 0, :3] = (1000.0, 1000.0, 0.0)
-            tg = rng.uniform(0, 20, 2)
-            e, p, tg = _f32(e), _f32(p), _f32(tg)
-            cmd = 0.0
-            if e[4] > 0:
-                on = p[:, 4] > 0
-                cmd = float(eva.e_f(xy=np.array(e[:2]), e_ga=e[2], e_v=e[3], e_sr=E_SR, npx=list(p[on, 0]), npy=list(p[on, 1]),
-                                    bet=list(p[on, 2]), p_v=list(p[:, 3]), p_=10, d_=1, m_=5, tp=list(tg)))
-            ps.append(p); es.append(e); ts.append(tg); cs.append(cmd)
+            e, p, tg = n2n_problem(rng, P)
+            ps.append(p); es.append(e); ts.append(tg); cs.append(n2n_command(eva, e, p, tg))
         out[f"P{P}_p"], out[f"P{P}_e"], out[f"P{P}_target"], out[f"P{P}_cmd"] = map(np.asarray, (ps, es, ts, cs))
     # p_vmax, e_vmax, p_sen_range, p_comm_range, kill_radius, ang_lmt, step_size (particle_env.py:108-121,147)
-    out["cfg"] = np.asarray([0.3, 1.0, 3.0, 6.0, 0.5, np.pi / 4, 0.5])
+    out["cfg"] = N2N_CFG
     return out
+
+
+E3D_KILL, E3D_ANG, E3D_VL, E3D_H, E3D_VMAX = 0.5, np.pi / 4, 0.4, 0.5, 1.0
+# p_vmax, e_vmax, p_sen_range, p_comm_range, kill_radius, ang_lmt, v_lmt, step_size (particle_env.py:78-121)
+E3D_CFG = np.asarray([0.7, E3D_VMAX, 3.0, 6.0, E3D_KILL, E3D_ANG, E3D_VL, E3D_H])
+
+
+def e3d_problem(rng, P):
+    """one sampled env_3d problem: e [7], p [P, 7], target [3]"""
+    kind = _kinds(rng)
+    phi, gam, v = rng.uniform(-np.pi, np.pi), rng.uniform(-np.pi / 2, np.pi / 2), rng.uniform(0, 1)
+    if rng.random() < 0.25:  # bounds clipped at +-1: heading near +-pi, pitch near +-pi/2, speed near 0 or 1
+        phi = np.sign(rng.random() - 0.5) * rng.uniform(0.8 * np.pi, np.pi)
+        gam = np.sign(rng.random() - 0.5) * rng.uniform(0.35 * np.pi, 0.5 * np.pi)
+        v = rng.choice([rng.uniform(0, 0.3), rng.uniform(0.7, 1.0)])
+    e = np.array([*rng.uniform(2, 18, 3), phi, gam, v, 1.0])
+    if rng.random() < 0.03:
+        e[6] = 0.0
+    p = np.zeros((P, 7))
+    p[:, :3] = _around(rng, e[:3], P, kind, 3)
+    p[:, 3] = rng.uniform(-np.pi, np.pi, P)
+    p[:, 4] = rng.uniform(-np.pi / 2, np.pi / 2, P)
+    p[:, 5] = rng.uniform(0, 0.7, P)
+    p[:, 6] = _active(rng, P, kind)
+    if rng.random() < 0.03:
+        p[:, 6] = 0.0  # no pursuer left: evader_step is not called
+    tg = rng.uniform(0, 20, 3)
+    return _f32(e), _f32(p), _f32(tg)
+
+
+def e3d_command(eva, e, p, tg):
+    """the reference's command for one problem, zeros where evader_step does not call e_f"""
+    on = p[:, 6] > 0
+    if not (e[6] > 0 and on.any()):
+        return np.zeros(3)
+    return np.asarray(eva.e_f(xyz=np.array(e[:3]), e_phi=e[3], e_ga=e[4], e_v=e[5], e_v_max=E3D_VMAX, e_sr=E_SR,
+                              npx=list(p[on, 0]), npy=list(p[on, 1]), npz=list(p[on, 2]), nphi=list(p[on, 3]),
+                              ngamma=list(p[on, 4]), nv=list(p[on, 5]), tp=list(tg), time_step=E3D_H, ang_lmt=E3D_ANG, v_lmt=E3D_VL,
+                              kill_radius=E3D_KILL), np.float64)
 
 
 def e3d(rng, per_p):
     from environment.env_3d import eva
-    kill, ang, vl, h, vmax = 0.5, np.pi / 4, 0.4, 0.5, 1.0
     out = {}
     for P in PS:
         ps, es, ts, cs = [], [], [], []
         for _ in range(per_p):
-            kind = _kinds(rng)
-            phi, gam, v = rng.uniform(-np.pi, np.pi), rng.uniform(-np.pi / 2, np.pi / 2), rng.uniform(0, 1)
-            if rng.random() < 0.25:  # bounds clipped at +-1: heading near +-pi, pitch near +-pi/2, speed near 0 or 1
-                phi = np.sign(rng.random() - 0.5) * rng.uniform(0.8 * np.pi, np.pi)
-                gam = np.sign(rng.random() - 0.5) * rng.uniform(0.35 * np.pi, 0.5 * np.pi)
-                v = rng.choice([rng.uniform(0, 0.3), rng.uniform(0.7, 1.0)])
-            e = np.array([*rng.uniform(2, 18, 3), phi, gam, v, 1.0])
-            if rng.random() < 0.03:
-                e[6] = 0.0
-            p = np.zeros((P, 7))
-            p[:, :3] = _around(rng, e[:3], P, kind, 3)
-            p[:, 3] = rng.uniform(-np.pi, np.pi, P)
-            p[:, 4] = rng.uniform(-np.pi / 2, np.pi / 2, P)
-            p[:, 5] = rng.uniform(0, 0.7, P)
-            p[:, 6] = _active(rng, P, kind)
-            if rng.random() < 0.03:
-                p[:, 6] = 0.0  # no pursuer left: evader_step is not called
-            tg = rng.uniform(0, 20, 3)
-            e, p, tg = _f32(e), _f32(p), _f32(tg)
-            cmd = np.zeros(3)
-            on = p[:, 6] > 0
-            if e[6] > 0 and on.any():
-                cmd = np.asarray(eva.e_f(xyz=np.array(e[:3]), e_phi=e[3], e_ga=e[4], e_v=e[5], e_v_max=vmax, e_sr=E_SR,
-                                         npx=list(p[on, 0]), npy=list(p[on, 1]), npz=list(p[on, 2]), nphi=list(p[on, 3]),
-                                         ngamma=list(p[on, 4]), nv=list(p[on, 5]), tp=list(tg), time_step=h, ang_lmt=ang, v_lmt=vl,
-                                         kill_radius=kill), np.float64)
-            ps.append(p); es.append(e); ts.append(tg); cs.append(cmd)
+            e, p, tg = e3d_problem(rng, P)
+            ps.append(p); es.append(e); ts.append(tg); cs.append(e3d_command(eva, e, p, tg))
         out[f"P{P}_p"], out[f"P{P}_e"], out[f"P{P}_target"], out[f"P{P}_cmd"] = map(np.asarray, (ps, es, ts, cs))
-    # p_vmax, e_vmax, p_sen_range, p_comm_range, kill_radius, ang_lmt, v_lmt, step_size (particle_env.py:78-121)
-    out["cfg"] = np.asarray([0.7, vmax, 3.0, 6.0, kill, ang, vl, h])
+    out["cfg"] = E3D_CFG
     return out
 
 

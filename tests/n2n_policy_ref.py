@@ -67,6 +67,48 @@ def policy_record(p, e, target, reward, done, live, value, acc, kill_radius):
     return rl, live, v, v_next_zero, out
 
 
+def ulp_close(got, want64):
+    """every element within one fp32 ulp of the float64 value"""
+    want32 = want64.astype(np.float32)
+    ulp = np.spacing(np.abs(want32)).astype(np.float64)
+    return np.all(np.abs(got.astype(np.float64) - want64) <= ulp)
+
+
+def assert_policy_inputs(got, p, e, pp_in, pe_in, done_before):
+    """what the GPU tests hold n2n_policy_inputs to: got, a dict of the six outputs read back, against policy_inputs() -- masks and
+    adjacencies exactly, features within one fp32 ulp of the float64 value, zero rows exactly zero.  -> the reference's dict"""
+    want = policy_inputs(p, e, pp_in, pe_in, done_before)
+    N = p.shape[0]
+    for k in ("live", "pp_adj", "pe_adj"):
+        assert np.array_equal(got[k], want[k]), k
+    live = want["live"].astype(bool)
+    e_on = e[:, 4] != 0
+    for k, rec, on in (("p4", p, live), ("e4", e, e_on)):
+        f64 = np.stack((rec[:, 0], rec[:, 1], rec[:, 3] * np.cos(rec[:, 2]), rec[:, 3] * np.sin(rec[:, 2])), -1)
+        assert ulp_close(got[k][on], f64[on]), k
+        assert np.all(got[k][~on] == 0), k
+    for n in range(N):
+        k = np.flatnonzero(e_on[n])
+        if k.size:
+            f64 = np.array([e[n, 0, k[0]], e[n, 1, k[0]], e[n, 3, k[0]] * np.cos(e[n, 2, k[0]]), e[n, 3, k[0]] * np.sin(e[n, 2, k[0]])])
+            assert ulp_close(got["e_ref"][n], f64)
+        else:
+            assert np.all(got["e_ref"][n] == 0)
+    return want
+
+
+def assert_policy_record(bufs, acc_got, p, e, target, reward, done, live, value, acc_before, kill_radius, fill=7.0):
+    """what the GPU tests hold n2n_policy_record to: bufs (r, active, v, v_next read back; v_next was filled with `fill` before the
+    launch) and the accumulators read back, against policy_record(), all exactly.  -> the reference's accumulators"""
+    r, active, v, vz, acc_want = policy_record(p, e, target, reward, done, live, value, acc_before, kill_radius)
+    assert np.array_equal(bufs["r"], r) and np.array_equal(bufs["active"], active)
+    assert np.array_equal(bufs["v"], v)
+    assert np.array_equal(bufs["v_next"], np.where(vz, np.float32(0), np.float32(fill)))
+    for k, x in acc_want.items():
+        assert np.array_equal(acc_got[k], x), k
+    return acc_want
+
+
 def new_accumulators(N):
     return dict(done_before=np.zeros(N, np.uint8), ended=np.zeros(N, np.uint8), captured=np.zeros(N, np.uint8),
                 ret=np.zeros(N, np.float32), length=np.zeros(N, np.float32))

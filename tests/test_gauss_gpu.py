@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import e3d_features_ref
 from tests import gauss_ref
 
 pytestmark = pytest.mark.gpu
@@ -153,28 +154,6 @@ def test_ppo_loss_gauss_matches_f64_torch(A, use_value_clip):
 
 
 # ---- e3d_policy_features ---------------------------------------------------------------------------------------------------------
-def _features_ref(p, e, pp, pe):
-    """p (N, 7, P), e (N, 7) f64 records; pp (N, P, P), pe (N, P) -> actor, critic (N, P, 16) fp32"""
-    N, _, P = p.shape
-    fa, fc = np.zeros((N, P, 16), np.float32), np.zeros((N, P, 16), np.float32)
-    for n in range(N):
-        for i in range(P):
-            if p[n, 6, i] == 0:
-                continue
-            s = p[n, :6, i]
-            ae = e[n, 6]
-            fa[n, i, :6] = fc[n, i, :6] = s
-            fa[n, i, 6:12] = (e[n, :6] - s) * pe[n, i]
-            fc[n, i, 6:12] = (e[n, :6] - s) * ae
-            fa[n, i, 12], fc[n, i, 12] = pe[n, i], ae
-            ja = [j for j in range(P) if j != i and pp[n, i, j] == 1]
-            jc = [j for j in range(P) if j != i and p[n, 6, j] != 0]
-            for js, f in ((ja, fa), (jc, fc)):
-                if js:
-                    f[n, i, 13:16] = np.mean([p[n, :3, j] - p[n, :3, i] for j in js], axis=0)
-    return fa, fc
-
-
 @pytest.mark.parametrize("P", [3, 8, 12])
 def test_policy_features_match_numpy(P):
     from distributed_multi_agent_reinforcement_learning_amd.e3d_env import ParticleEnv
@@ -191,7 +170,7 @@ def test_policy_features_match_numpy(P):
     env.obs["pe_adj"].copy_((torch.rand(N, P, 1, generator=g) < 0.5).float())
     fa, fc = torch.full((N, P, 16), 7.0, device="cuda"), torch.full((N, P, 16), 7.0, device="cuda")
     env.policy_features(fa, fc)
-    ra, rc = _features_ref(env.p.cpu().numpy(), env.e.cpu().numpy(), env.obs["pp_adj"].cpu().numpy(), env.obs["pe_adj"].cpu().numpy()[..., 0])
+    ra, rc = e3d_features_ref.policy_features(env.p.cpu().numpy(), env.e.cpu().numpy(), env.obs["pp_adj"].cpu().numpy(), env.obs["pe_adj"].cpu().numpy()[..., 0])
     np.testing.assert_allclose(fa.cpu().numpy(), ra, rtol=1e-6, atol=1e-6)
     np.testing.assert_allclose(fc.cpu().numpy(), rc, rtol=1e-6, atol=1e-6)
 

@@ -31,13 +31,6 @@ def _strided(shape):
     return big[:, 1]
 
 
-def _ulp_close(got, want64):
-    """every element within one fp32 ulp of the float64 value"""
-    want32 = want64.astype(np.float32)
-    ulp = np.spacing(np.abs(want32)).astype(np.float64)
-    return np.all(np.abs(got.astype(np.float64) - want64) <= ulp)
-
-
 # ---- n2n_policy_inputs / n2n_policy_record -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("P", [4, 8, 16])
 @pytest.mark.parametrize("E", [1, 2, 4])
@@ -60,24 +53,9 @@ def test_policy_inputs_and_record_match_numpy(P, E):
     outs = dict(p4=_strided((N, P, 4)), e4=_strided((N, E, 4)), e_ref=_strided((N, 4)), live=_strided((N, P)), pp_adj=_strided((N, P, P)),
                 pe_adj=_strided((N, P, E)))
     env.policy_inputs(**outs, done_before=acc["done_before"])
-    want = ref.policy_inputs(p, e, pp_in, pe_in, acc_np["done_before"])
     got = {k: v.cpu().numpy() for k, v in outs.items()}
-    for k in ("live", "pp_adj", "pe_adj"):
-        assert np.array_equal(got[k], want[k]), k
+    want = ref.assert_policy_inputs(got, p, e, pp_in, pe_in, acc_np["done_before"])
     live = want["live"].astype(bool)
-    e_on = e[:, 4] != 0
-    # features: within one fp32 ulp of the float64 value; zero rows exactly zero
-    for k, rec, on in (("p4", p, live), ("e4", e, e_on)):
-        f64 = np.stack((rec[:, 0], rec[:, 1], rec[:, 3] * np.cos(rec[:, 2]), rec[:, 3] * np.sin(rec[:, 2])), -1)
-        assert _ulp_close(got[k][on], f64[on]), k
-        assert np.all(got[k][~on] == 0), k
-    for n in range(N):
-        k = np.flatnonzero(e_on[n])
-        if k.size:
-            f64 = np.array([e[n, 0, k[0]], e[n, 1, k[0]], e[n, 3, k[0]] * np.cos(e[n, 2, k[0]]), e[n, 3, k[0]] * np.sin(e[n, 2, k[0]])])
-            assert _ulp_close(got["e_ref"][n], f64)
-        else:
-            assert np.all(got["e_ref"][n] == 0)
     assert live.any() and (~live).any() and acc_np["done_before"].any()
     # record, after a "tick": reward and done as the tick leaves them, rows written into strided buffer slices
     reward = rng.integers(-2, 3, (N, P)).astype(np.float32) * (p[:, 4] != 0)
@@ -87,12 +65,8 @@ def test_policy_inputs_and_record_match_numpy(P, E):
     env.done_t.copy_(torch.from_numpy(done))
     bufs = dict(r=_strided((N, P)), active=_strided((N, P)), v=_strided((N, P)), v_next=_strided((N, P)))
     env.policy_record(acc, outs["live"], torch.from_numpy(value).cuda(), **bufs)
-    r, active, v, vz, acc_want = ref.policy_record(p, e, target, reward, done, want["live"], value, acc_np, env.kill_radius)
-    assert np.array_equal(bufs["r"].cpu().numpy(), r) and np.array_equal(bufs["active"].cpu().numpy(), active)
-    assert np.array_equal(bufs["v"].cpu().numpy(), v)
-    assert np.array_equal(bufs["v_next"].cpu().numpy(), np.where(vz, np.float32(0), np.float32(7)))
-    for k, x in acc_want.items():
-        assert np.array_equal(acc[k].cpu().numpy(), x), k
+    acc_want = ref.assert_policy_record({k: v.cpu().numpy() for k, v in bufs.items()}, {k: v.cpu().numpy() for k, v in acc.items()}, p, e, target,
+                                        reward, done, want["live"], value, acc_np, env.kill_radius)
     assert acc_want["ended"].sum() > acc_np["ended"].sum() and acc_want["captured"].any()
 
 

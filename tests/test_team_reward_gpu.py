@@ -3,8 +3,8 @@ tests/team_reward_ref.py bit for bit -- alone, with reward scaling, with distanc
 byte against the unshared launch, alpha = 0 against the unshared entry points, determinism, and the option in the trainers: absent,
 on, deterministic, resumed, and out of evaluation and the scripted pursuers' episodes.
 
-Five environments, so the last wave is partial; the group widths 8 (P = 3, 8) and 16 (P = 9, 16).  More than 16 pursuers is not
-covered."""
+Five environments, so the last wave is partial; the group widths 8 (P = 3, 8) and 16 (P = 9, 16).  More than 16 pursuers:
+tests/test_wide_teams_gpu.py."""
 import itertools
 
 import numpy as np
