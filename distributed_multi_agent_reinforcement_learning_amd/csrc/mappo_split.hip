@@ -7,6 +7,7 @@
 #include "mappo_ops.h"
 #include "sb_gemm.hpp"
 #include "sb_encoder_tail.hpp"
+#include "sb_encoder_tail_bwd.hpp"
 #include "sb_gru_seq.hpp"
 
 extern "C" {
@@ -94,7 +95,37 @@ int sb_encoder_tail(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg
         ((uintptr_t)C & 15) || ((uintptr_t)Y & 15))
         return MO_ERR_BAD_ARG;
     if (Rs == 0) return 0;
-    return launch_sb_encoder_tail(Rs, m3, ldx, w_agg, b_agg, Ws, ldw, C, ldc, Y, ldy, (hipStream_t)stream);
+    return launch_sb_encoder_tail<false>(Rs, m3, ldx, w_agg, b_agg, Ws, ldw, C, ldc, Y, ldy, (hipStream_t)stream);
+}
+
+int sb_encoder_tail_train(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *Ws, int64_t ldw, const float *C,
+                          int64_t ldc, float *Y, int64_t ldy, float *emb, int64_t lde, uint8_t *emb_sign_bits, int64_t ld_bytes, void *stream) {
+    if (Rs < 0 || !m3 || !w_agg || !b_agg || !Ws || !C || !Y || !emb || !emb_sign_bits || ldx < 384 || ldw < 384 || ldc < 128 || ldy < 128 || lde < 384 ||
+        ld_bytes < 48)
+        return MO_ERR_BAD_ARG;
+    if ((ldx & 3) || (ldw & 3) || (ldc & 3) || (ldy & 3) || (lde & 3) || ((uintptr_t)m3 & 15) || ((uintptr_t)w_agg & 15) || ((uintptr_t)b_agg & 15) ||
+        ((uintptr_t)Ws & 15) || ((uintptr_t)C & 15) || ((uintptr_t)Y & 15) || ((uintptr_t)emb & 15))
+        return MO_ERR_BAD_ARG;
+    if (Rs == 0) return 0;
+    return launch_sb_encoder_tail<true>(Rs, m3, ldx, w_agg, b_agg, Ws, ldw, C, ldc, Y, ldy, (hipStream_t)stream, emb, lde, emb_sign_bits, ld_bytes);
+}
+
+int64_t sb_encoder_tail_bwd_workspace(void) { return (int64_t)1024 * 384 * 4; }   // one row of partial sums per workgroup (<= CUs)
+
+int sb_encoder_tail_bwd(int64_t Rs, const float *g, int64_t ldg, const float *Ws, int64_t ldw, const float *w_agg, const uint8_t *emb_sign_bits,
+                        int64_t ld_bytes, float *ga, int64_t ldga, float *d_m3, int64_t ldd, float *colsum, void *workspace, void *stream) {
+    if (Rs < 0 || !g || !Ws || !w_agg || !emb_sign_bits || !ga || !d_m3 || !colsum || !workspace || ldg < 128 || ldw < 384 || ld_bytes < 48 || ldga < 384 ||
+        ldd < 384)
+        return MO_ERR_BAD_ARG;
+    if ((ldg & 3) || (ldw & 3) || (ldga & 3) || (ldd & 3) || ((uintptr_t)g & 15) || ((uintptr_t)Ws & 15) || ((uintptr_t)w_agg & 15) || ((uintptr_t)ga & 15) ||
+        ((uintptr_t)d_m3 & 15) || ((uintptr_t)colsum & 15) || ((uintptr_t)workspace & 15))
+        return MO_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (Rs == 0) return (int)hipMemsetAsync(colsum, 0, (size_t)384 * 4, st);
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    if (cus > 1024) return MO_ERR_BAD_ARG;         // (the workspace holds 1024 rows)
+    return launch_sb_encoder_tail_bwd(Rs, g, ldg, Ws, ldw, w_agg, emb_sign_bits, ld_bytes, ga, ldga, d_m3, ldd, (float *)workspace, colsum, cus, st);
 }
 
 int gru_seq_split_fwd_multi(int32_t n_nets, const mo_gru_seq_net *nets, int32_t T, int32_t B, int32_t H, int32_t gi_agents, void *stream) {

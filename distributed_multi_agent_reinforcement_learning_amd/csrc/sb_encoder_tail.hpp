@@ -29,9 +29,15 @@
 constexpr int SBE_IMG = 3 * 4 * 2 * 64;   // uint4 per operand image: [piece][chunk][row half][lane]
 constexpr int SBE_WIMG = 8 * 4 * 3 * 64;  // uint4 of the weight image: [wave][chunk][piece][lane]
 
+// SAVE (the update, sb_encoder_tail_train): at the hand-over the lanes that hold the AGG result also store it -- one 16-byte store per lane
+// into emb (Rs, 384), row stride lde -- and its sign bits in sb_gemm_signs' layout (bit k of byte j of a relation row: emb[..][8 j + k] > 0;
+// 16 bytes per relation, 48 per semantic row, row stride ldb bytes): what the backward (sb_encoder_tail_bwd.hpp) and the weight
+// gradients read.  The stores stay in flight across the barriers (lds_barrier); everything else is the rollout's kernel.
+template <bool SAVE>
 __global__ __launch_bounds__(512) void k_sb_encoder_tail(int64_t Rs, const float *__restrict__ X, int64_t ldx, const float *__restrict__ Wa,
                                                          const float *__restrict__ ba, const float *__restrict__ Ws, int64_t ldw, const float *C,
-                                                         int64_t ldc, float *Y, int64_t ldy) {
+                                                         int64_t ldc, float *Y, int64_t ldy, float *__restrict__ emb, int64_t lde,
+                                                         uint8_t *__restrict__ ebits, int64_t ldb) {
     extern __shared__ uint4 sbe_lds[];                  // [AGG weight image | m3 image | embedding image]
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, i = l & 15, gq = l >> 4;
     uint4 *const wimg = sbe_lds + w * (4 * 3 * 64) + l, *const mimg = sbe_lds + SBE_WIMG, *const eimg = mimg + SBE_IMG;
@@ -78,11 +84,15 @@ __global__ __launch_bounds__(512) void k_sb_encoder_tail(int64_t Rs, const float
     for (; t < n_t; t += G) {
         const bool more = t + G < n_t;
         float4 a4[2];
+        auto addend = [&]() {
 #pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-            const int64_t row = t * 32 + rt * 16 + i;
-            a4[rt] = row < Rs ? *(const float4 *)(C + row * ldc + 16 * w + 4 * gq) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+            for (int rt = 0; rt < 2; rt++) {
+                const int64_t row = t * 32 + rt * 16 + i;
+                a4[rt] = row < Rs ? *(const float4 *)(C + row * ldc + 16 * w + 4 * gq) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        };
+        if constexpr (!SAVE) addend();   // (SAVE: requested behind step 2's hand-over, in the registers the AGG accumulators release: beside
+                                         // the stores' addresses the eight do not fit across a hand-over -- 20 B of scratch wherever else)
         f32x4 acc_s[2];
         acc_s[0] = acc_s[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -106,6 +116,15 @@ __global__ __launch_bounds__(512) void k_sb_encoder_tail(int64_t Rs, const float
             for (int rt = 0; rt < 2; rt++) {
                 float4 v = make_float4(acc_a[rt][0] + b4.x, acc_a[rt][1] + b4.y, acc_a[rt][2] + b4.z, acc_a[rt][3] + b4.w);
                 v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                if constexpr (SAVE) {   // lanes (i, gq) and (i, gq ^ 1) hold the two nibbles of a byte (as k_sb_gemm_n128, OPT & 8)
+                    const int64_t row = t * 32 + rt * 16 + i;
+                    const unsigned nib = (unsigned)(v.x > 0.f) | ((unsigned)(v.y > 0.f) << 1) | ((unsigned)(v.z > 0.f) << 2) | ((unsigned)(v.w > 0.f) << 3);
+                    const unsigned other = (unsigned)__shfl_xor((int)nib, 16);
+                    if (row < Rs) {
+                        *(float4 *)(emb + row * lde + 128 * r + 16 * w + 4 * gq) = v;
+                        if (!(gq & 1)) ebits[row * ldb + 16 * r + 2 * w + (gq >> 1)] = (uint8_t)(nib | (other << 4));
+                    }
+                }
                 uint32_t lo[3], hi[3];
                 sb_split2(v.x, v.y, lo[0], lo[1], lo[2]);
                 sb_split2(v.z, v.w, hi[0], hi[1], hi[2]);
@@ -113,6 +132,7 @@ __global__ __launch_bounds__(512) void k_sb_encoder_tail(int64_t Rs, const float
                 for (int p = 0; p < 3; p++) edst[p * 8 * 64 * 2 + rt * 128] = make_uint2(lo[p], hi[p]);
             }
             lds_barrier();
+            if constexpr (SAVE) if (r == 2) addend();
             auto next_step = [&]() {   // step n + 1 -> the m3 image, step n + 2 requested
                 if (r < 2 || more) stage();
                 if (r == 0) fetch(t, 2);
@@ -145,17 +165,19 @@ __global__ __launch_bounds__(512) void k_sb_encoder_tail(int64_t Rs, const float
     }
 }
 
-inline int launch_sb_encoder_tail(int64_t Rs, const float *X, int64_t ldx, const float *Wa, const float *ba, const float *Ws, int64_t ldw,
-                                  const float *C, int64_t ldc, float *Y, int64_t ldy, hipStream_t st) {
+template <bool SAVE = false>
+int launch_sb_encoder_tail(int64_t Rs, const float *X, int64_t ldx, const float *Wa, const float *ba, const float *Ws, int64_t ldw, const float *C,
+                           int64_t ldc, float *Y, int64_t ldy, hipStream_t st, float *emb = nullptr, int64_t lde = 0, uint8_t *ebits = nullptr,
+                           int64_t ldb = 0) {
     constexpr int lds = (SBE_WIMG + 2 * SBE_IMG) * 16;
     static std::once_flag once;   // the evaluator's thread may launch concurrently with the trainer's
     static hipError_t attr_rc = hipSuccess;
-    std::call_once(once, [] { attr_rc = hipFuncSetAttribute((const void *)k_sb_encoder_tail, hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
+    std::call_once(once, [] { attr_rc = hipFuncSetAttribute((const void *)k_sb_encoder_tail<SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
     if (attr_rc != hipSuccess) return (int)attr_rc;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const int64_t n_t = (Rs + 31) / 32;
     const int grid = n_t < (int64_t)cus ? (int)n_t : cus;
-    hipLaunchKernelGGL(k_sb_encoder_tail, dim3(grid), dim3(512), lds, st, Rs, X, ldx, Wa, ba, Ws, ldw, C, ldc, Y, ldy);
+    hipLaunchKernelGGL(k_sb_encoder_tail<SAVE>, dim3(grid), dim3(512), lds, st, Rs, X, ldx, Wa, ba, Ws, ldw, C, ldc, Y, ldy, emb, lde, ebits, ldb);
     return (int)hipGetLastError();
 }

@@ -85,10 +85,18 @@ class DHGN(nn.Module):
         R, P = p.shape[0], p.shape[1]
         E, ind = self.embedding_dim, self.input_dim
         agg0 = self.AGG_layers["AGG_vertex_0"]
+        Ws = self.semantic_layer.weight
+        pos = None
+        if out is None and ops.ENCODER_TAIL_TRAIN and torch.is_grad_enabled() and m3.is_contiguous():
+            # the update: both layers as ONE launch forward and one backward, the embedding handed over in LDS (the same bits as the two
+            # linear calls below, their gradients included); the position part first, the launch accumulates into it
+            pos = ops.linear_skinny(p.reshape(R * P, ind), Ws[:, :ind], self.semantic_layer.bias)
+            m3_s, Wse = m3.view(R * P, 3 * E), Ws[:, ind:]
+            if pos.requires_grad and ops.encoder_tail_train_ok(m3_s, agg0.weight, agg0.bias, Wse, pos):
+                return ops.encoder_tail_train(m3_s, agg0.weight, agg0.bias, Wse, pos).reshape(R, P, E)
         link = ops.ReluLink()    # emb feeds the semantic layer only: its relu' and bias gradient ride in that layer's input gradient
         emb = ops.linear(m3, agg0.weight, agg0.bias, relu=True, y_link=link)          # one GEMM (+relu epilogue) for the three relations
         # semantic_layer([p, emb0, emb1, emb2]) without materialising the concatenation (:284-303)
-        Ws = self.semantic_layer.weight
         # the position part (K = 4) first, the embedding part accumulates INTO it (beta = 1, no copy of the addend)
         p2, e2 = p.reshape(R * P, ind), emb.reshape(R * P, 3 * E)
         if out is not None:  # rollout: both GEMMs write the static storage
@@ -96,7 +104,9 @@ class DHGN(nn.Module):
             torch.addmm(self.semantic_layer.bias, p2, Ws[:, :ind].t(), out=o2)
             h0 = o2.addmm_(e2, Ws[:, ind:].t())
         else:
-            h0 = ops.linear(e2, Ws[:, ind:], ops.linear_skinny(p2, Ws[:, :ind], self.semantic_layer.bias), consume_addend=True, x_link=link)
+            if pos is None:
+                pos = ops.linear_skinny(p2, Ws[:, :ind], self.semantic_layer.bias)
+            h0 = ops.linear(e2, Ws[:, ind:], pos, consume_addend=True, x_link=link)
         return h0.reshape(R, P, E)
 
     def encoder_pair_train(self, p, e, o, adj_p, adj_e, adj_o, q_div=1, e_ref=None):

@@ -75,6 +75,10 @@ def load_library():
         L.sb_gemm_n128.argtypes = [i64, i32, vp, i64, vp, i64, vp, i32, vp, i64, vp, i64, vp]
         L.sb_gemm.argtypes = [i64, i32, i32, vp, i64, vp, i64, vp, i32, vp, i64, vp, i64, vp]
         L.sb_encoder_tail.argtypes = [i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp]
+        L.sb_encoder_tail_train.argtypes = [i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+        L.sb_encoder_tail_bwd_workspace.argtypes = []
+        L.sb_encoder_tail_bwd_workspace.restype = i64
+        L.sb_encoder_tail_bwd.argtypes = [i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp]
         L.gru_seq_fwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
         L.gru_seq_bwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
         L.gru_seq_split_fwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
@@ -2084,6 +2088,91 @@ def encoder_tail(m3, w_agg, b_agg, Ws, out):
 def sign_bits_ok(N, K):
     """the shapes whose split-bf16 GEMM can write relu'(result) as bits beside the result (ReluLink.bits)"""
     return RELU_LINK and RELU_BITS and N == 128 and K in (128, 256)
+
+
+# The update's encoder tail (DHGN._after_messages under autograd): one launch each way instead of two (sb_encoder_tail_train /
+# sb_encoder_tail_bwd), the same bits.  A/B switch (tools/ab_switch.py): off = the two ops.linear calls with their ReluLink.
+ENCODER_TAIL_TRAIN = os.environ.get("MAPPO_ENCODER_TAIL_TRAIN", "1") != "0"
+# semantic rows from which the update takes the fused launches: the smallest size the fused rollout launch was measured ahead at
+# (DESIGN 13: 32 768 and 65 536 rows); the update's mini-batches are 5e5 rows.  (A name of its own: the fixtures that force the other
+# thresholds to 1 stay on the two-launch route.)
+ENCODER_TAIL_TRAIN_MIN_ROWS = 32768
+
+
+def encoder_tail_train_ok(m3, w_agg, b_agg, Ws, addend):
+    """operands _EncoderTailTrain covers (encoder_tail_ok's rules for the update): split mode with the ReLU link and its sign bits on,
+    fp32, E = 128; m3 (Rs, 384) and the addend (Rs, 128) -- the position part, a temporary the result accumulates into -- dense 2-D and
+    16-byte aligned; Ws (128, 384) may be a column block; w_agg, b_agg dense; at least ENCODER_TAIL_TRAIN_MIN_ROWS rows"""
+    if not ENCODER_TAIL_TRAIN or PROJ_MODE != "split_bf16" or not (RELU_LINK and RELU_BITS) or not m3.is_cuda:
+        return False
+    if m3.dim() != 2 or addend.dim() != 2 or m3.shape[1] != 384 or tuple(addend.shape) != (m3.shape[0], 128) or tuple(Ws.shape) != (128, 384):
+        return False
+    if m3.shape[0] < ENCODER_TAIL_TRAIN_MIN_ROWS or not m3.is_contiguous() or not addend.is_contiguous():
+        return False
+    if tuple(w_agg.shape) != (128, 128) or not w_agg.is_contiguous() or b_agg is None or tuple(b_agg.shape) != (128,) or not b_agg.is_contiguous():
+        return False
+    for t in (m3, w_agg, Ws, addend):
+        if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+            return False
+    if b_agg.dtype != torch.float32 or b_agg.data_ptr() % 16:
+        return False
+    return not _overlap(m3, addend)
+
+
+def encoder_tail_train_fwd(m3, w_agg, b_agg, Ws, C, Y, emb, bits):
+    """Y = C + sum over r of Ws_r relu(w_agg m3[:, r] + b_agg) (C may be Y), emb (Rs, 384) and its sign bits (Rs, 48) written beside it
+    (include/mappo_ops.h sb_encoder_tail_train).  No autograd, no checks beyond the entry point's."""
+    L = load_library()
+    _check(L.sb_encoder_tail_train(m3.shape[0], _ptr(m3), m3.stride(0), _ptr(w_agg.detach()), _ptr(b_agg.detach()), _ptr(Ws.detach()), Ws.stride(0),
+                                   _ptr(C), C.stride(0), _ptr(Y), Y.stride(0), _ptr(emb), emb.stride(0), _ptr(bits), bits.stride(0), _stream()),
+           "sb_encoder_tail_train")
+    return Y
+
+
+def encoder_tail_train_bwd(g, Ws, w_agg, bits):
+    """-> (ga (Rs, 384), d_m3 (Rs, 384), column sums of ga (384,)) for the gradient g (Rs, 128) of the tail's result
+    (include/mappo_ops.h sb_encoder_tail_bwd).  No autograd."""
+    L = load_library()
+    Rs = g.shape[0]
+    ga = torch.empty((Rs, 384), dtype=torch.float32, device=g.device)
+    d_m3 = torch.empty((Rs, 384), dtype=torch.float32, device=g.device)
+    cs = torch.empty(384, dtype=torch.float32, device=g.device)
+    ws = torch.empty(L.sb_encoder_tail_bwd_workspace(), dtype=torch.uint8, device=g.device)
+    _check(L.sb_encoder_tail_bwd(Rs, _ptr(g), g.stride(0), _ptr(Ws.detach()), Ws.stride(0), _ptr(w_agg.detach()), _ptr(bits), bits.stride(0), _ptr(ga),
+                                 ga.stride(0), _ptr(d_m3), d_m3.stride(0), _ptr(cs), _ptr(ws), _stream()), "sb_encoder_tail_bwd")
+    return ga, d_m3, cs
+
+
+class _EncoderTailTrain(torch.autograd.Function):
+    """h0 = addend + sum over r of Ws_r relu(w_agg m3[:, r] + b_agg), in place on the addend: DHGN._after_messages' AGG layer and the
+    embedding part of its semantic layer, one launch forward and one backward, bit-identical to linear(relu, y_link) -> linear(x_link)."""
+
+    @staticmethod
+    def forward(ctx, m3, w_agg, b_agg, Ws, addend):
+        Rs = m3.shape[0]
+        emb = torch.empty((Rs, 384), dtype=torch.float32, device=m3.device)
+        bits = torch.empty((Rs, 48), dtype=torch.uint8, device=m3.device)
+        ctx.mark_dirty(addend)
+        encoder_tail_train_fwd(m3, w_agg, b_agg, Ws, addend, addend, emb, bits)
+        ctx.save_for_backward(m3, emb, bits, w_agg, Ws)
+        return addend
+
+    @staticmethod
+    def backward(ctx, g):
+        m3, emb, bits, w_agg, Ws = ctx.saved_tensors
+        g2 = g.reshape(-1, 128)
+        if g2.stride(1) != 1 or g2.stride(0) % 4 or g2.data_ptr() % 16:
+            g2 = g2.contiguous()
+        ga, d_m3, cs = encoder_tail_train_bwd(g2, Ws, w_agg, bits)
+        dWs = wgrad(g2, emb) if ctx.needs_input_grad[3] else None
+        dWa = wgrad(ga.view(-1, 128), m3.view(-1, 128)) if ctx.needs_input_grad[1] else None
+        db = cs.view(-1, 128).sum(0) if ctx.needs_input_grad[2] else None
+        return (d_m3 if ctx.needs_input_grad[0] else None), dWa, db, dWs, (g if ctx.needs_input_grad[4] else None)
+
+
+def encoder_tail_train(m3, w_agg, b_agg, Ws, addend):
+    """see _EncoderTailTrain; the caller checks encoder_tail_train_ok.  addend must be a temporary: it becomes the result."""
+    return _EncoderTailTrain.apply(m3, w_agg, b_agg, Ws, addend)
 
 
 # the update's Linear layers, their input gradients and the GRU input projections gi = x W_ih^T + b_ih: the BLAS library | sb_gemm

@@ -325,6 +325,21 @@ int sb_gemm_masked(int64_t R, int32_t N, int32_t K, const float *X, int64_t ldx,
 /* The same with the mask as sign bits (sb_gemm_signs' layout, N / 8 bytes per row, row stride ld_bytes): 1 bit per element read instead of 4 bytes. */
 int sb_gemm_masked_bits(int64_t R, int32_t N, int32_t K, const float *X, int64_t ldx, const float *W, int64_t ldw, const uint8_t *sign_bits,
                         int64_t ld_bytes, int32_t mask_cols, float *Y, int64_t ldy, float *colsum, void *workspace, void *stream);
+/* The update encoder's tail (DHGN._after_messages) as one launch each way.
+ * sb_encoder_tail_train: sb_encoder_tail that also writes what the backward reads -- emb [Rs][384] (row stride lde floats, a multiple of 4:
+ * relu(w_agg m3[s][r] + b_agg) at columns 128 r ..) and its sign bits emb_sign_bits [Rs][48] (row stride ld_bytes; sb_gemm_signs' layout per
+ * relation row: byte 16 r + j, bit k = emb[s][128 r + 8 j + k] > 0).  Bit-identical to sb_gemm_signs(3 Rs, 128, 128, ..) + sb_gemm(Rs, 128, 384, ..).
+ * sb_encoder_tail_bwd: for the gradient g [Rs][128] (row stride ldg) of Y,
+ *   ga[s][r] = (g[s] Ws[:, 128 r .. 128 r + 127]) * (emb[s][r] > 0)  -> ga [Rs][384] (row stride ldga),   colsum[384] = column sums of ga,
+ *   d_m3[s][r] = ga[s][r] w_agg                                      -> d_m3 [Rs][384] (row stride ldd),
+ * bit-identical to sb_gemm_masked_bits(Rs, 384, 128, g, ldg, Ws^T, ..) followed by sb_gemm(3 Rs, 128, 128, ga, 128, w_agg^T, ..), the column
+ * sums included (per-workgroup partials in `workspace`, >= sb_encoder_tail_bwd_workspace() bytes, reduced in a fixed order).  Ws and w_agg
+ * are the weights as stored (no transposed copies).  Strides in floats, multiples of 4; all float pointers 16-byte aligned. */
+int sb_encoder_tail_train(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *Ws, int64_t ldw, const float *C,
+                          int64_t ldc, float *Y, int64_t ldy, float *emb, int64_t lde, uint8_t *emb_sign_bits, int64_t ld_bytes, void *stream);
+int64_t sb_encoder_tail_bwd_workspace(void);
+int sb_encoder_tail_bwd(int64_t Rs, const float *g, int64_t ldg, const float *Ws, int64_t ldw, const float *w_agg, const uint8_t *emb_sign_bits,
+                        int64_t ld_bytes, float *ga, int64_t ldga, float *d_m3, int64_t ldd, float *colsum, void *workspace, void *stream);
 
 /*
  * PPO clipped-surrogate policy loss and clipped value loss of one mini-batch with their gradients

@@ -1,0 +1,298 @@
+"""The update encoder's tail as one launch each way (sb_encoder_tail_train, sb_encoder_tail_bwd; ops.encoder_tail_train).
+The contract is bit-identity with the launches replaced -- sb_gemm_signs (AGG layer + sign bits), sb_gemm in place (semantic layer),
+sb_gemm_masked_bits (its masked input gradient + column sums), sb_gemm (the AGG layer's input gradient) -- for h0, emb, the bits, ga,
+d_m3, the three parameter gradients and the addend's gradient: around the 32-row tile, with more tiles than workgroups, with zero rows,
+strided operands, in a captured graph, through DHGN.encoder_pair_train, and with canary rows behind every output."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+E = 128
+PAD = 3            # canary rows behind every output
+CANARY = -7.25
+
+
+@pytest.fixture()
+def split_update():
+    from distributed_multi_agent_reinforcement_learning_amd import ops
+    modes = ops.matmul_modes()
+    old = (ops.ENCODER_TAIL_TRAIN, ops.ENCODER_TAIL_TRAIN_MIN_ROWS, ops.MASKED_GRAD_MIN_ROWS, ops.RELU_LINK, ops.RELU_BITS, ops.SORTED_ONES_MIN_QDIV)
+    ops.set_matmul_mode("split_bf16")
+    ops.ENCODER_TAIL_TRAIN, ops.RELU_LINK, ops.RELU_BITS = True, True, True
+    yield ops
+    ops.restore_matmul_modes(modes)
+    ops.ENCODER_TAIL_TRAIN, ops.ENCODER_TAIL_TRAIN_MIN_ROWS, ops.MASKED_GRAD_MIN_ROWS, ops.RELU_LINK, ops.RELU_BITS, ops.SORTED_ONES_MIN_QDIV = old
+
+
+def cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256
+
+
+def make_operands(Rs, seed=0, neg_row=None, zero_g_tile=None, dense_ws=False):
+    """m3 (Rs, 384), w_agg, b_agg, Ws as the column block [:, 4:] of a (128, 388) matrix (row stride 388) or dense, addend (Rs, 128), g
+    (Rs, 128).  About a third of the AGG pre-activations are negative (tests/test_encoder_tail_gpu.py make_operands)."""
+    gen = torch.Generator(device="cuda").manual_seed(1000 * seed + Rs % 997)
+    m3 = torch.randn(Rs, 3 * E, device="cuda", generator=gen)
+    w_agg = torch.randn(E, E, device="cuda", generator=gen) * 0.1
+    b_agg = torch.randn(E, device="cuda", generator=gen) * 0.6 + 0.55
+    Ws = (torch.randn(E, 3 * E + 4, device="cuda", generator=gen) * 0.1)[:, 4:]
+    add = torch.randn(Rs, E, device="cuda", generator=gen)
+    g = torch.randn(Rs, E, device="cuda", generator=gen)
+    if neg_row is not None:      # every pre-activation of this row is negative: its embedding is exactly zero, all its bits clear
+        m3[neg_row] = 0.0
+        b_agg = -b_agg.abs() - 0.01
+    if zero_g_tile is not None:
+        g[32 * zero_g_tile:32 * zero_g_tile + 32] = 0.0
+    if dense_ws:
+        Ws = Ws.contiguous()
+    return m3, w_agg, b_agg, Ws, add, g
+
+
+def padded(rows, cols, dtype=torch.float32):
+    """(rows + PAD, cols) canary-filled buffer -> (buffer, its first `rows` rows)"""
+    buf = torch.full((rows + PAD, cols), CANARY if dtype == torch.float32 else 0xA5, dtype=dtype, device="cuda")
+    return buf, buf[:rows]
+
+
+def canary_ok(buf, rows):
+    tail = buf[rows:]
+    return bool((tail == (CANARY if buf.dtype == torch.float32 else 0xA5)).all())
+
+
+def two_launches(ops, m3, w_agg, b_agg, Ws, add, g):
+    """the launches replaced, as _Linear.forward / backward issue them"""
+    L = ops.load_library()
+    Rs = m3.shape[0]
+    emb = torch.empty(3 * Rs, E, device="cuda")
+    bits = torch.empty(3 * Rs, E // 8, dtype=torch.uint8, device="cuda")
+    ops.split_linear(m3.view(-1, E), w_agg, b_agg, True, out=emb, sign_bits=bits)
+    h0 = add.clone()
+    ops.split_linear(emb.view(Rs, 3 * E), Ws, None, False, out=h0, addend=h0)
+    Wt = Ws.t().contiguous()
+    ga = torch.empty(Rs, 3 * E, device="cuda")
+    cs = torch.empty(3 * E, device="cuda")
+    ws = torch.empty(L.sb_gemm_masked_workspace(3 * E), dtype=torch.uint8, device="cuda")
+    b2 = bits.view(Rs, 3 * E // 8)
+    rc = L.sb_gemm_masked_bits(Rs, 3 * E, E, ops._ptr(g), g.stride(0), ops._ptr(Wt), Wt.stride(0), ops._ptr(b2), b2.stride(0), 3 * E, ops._ptr(ga),
+                               ga.stride(0), ops._ptr(cs), ops._ptr(ws), ops._stream())
+    assert rc == 0
+    d_m3 = ops.split_linear(ga.view(-1, E), w_agg.t().contiguous()).view(Rs, 3 * E)
+    return {"h0": h0, "emb": emb.view(Rs, 3 * E), "bits": b2, "ga": ga, "d_m3": d_m3, "dW_sem": ops.wgrad(g, emb.view(Rs, 3 * E)),
+            "dW_agg": ops.wgrad(ga.view(-1, E), m3.view(-1, E)), "db_agg": cs.view(-1, E).sum(0), "d_addend": g}
+
+
+def fused(ops, m3, w_agg, b_agg, Ws, add, g, wide=False):
+    """the two fused launches into canary-padded outputs; wide: h0 is the right half of a (Rs, 2E) operand.  -> (results, canaries intact)"""
+    L = ops.load_library()
+    Rs = m3.shape[0]
+    if wide:
+        ybuf, y2 = padded(Rs, 2 * E)
+        left = torch.randn(Rs, E, device="cuda")
+        y2[:, :E] = left
+        y = y2[:, E:]
+    else:
+        ybuf, y = padded(Rs, E)
+    y.copy_(add)
+    ebuf, emb = padded(Rs, 3 * E)
+    bbuf, bits = padded(Rs, 3 * E // 8, torch.uint8)
+    ops.encoder_tail_train_fwd(m3, w_agg, b_agg, Ws, y, y, emb, bits)
+    gbuf, ga = padded(Rs, 3 * E)
+    dbuf, d_m3 = padded(Rs, 3 * E)
+    cs = torch.empty(3 * E, device="cuda")
+    ws = torch.empty(L.sb_encoder_tail_bwd_workspace(), dtype=torch.uint8, device="cuda")
+    rc = L.sb_encoder_tail_bwd(Rs, ops._ptr(g), g.stride(0), ops._ptr(Ws), Ws.stride(0), ops._ptr(w_agg), ops._ptr(bits), bits.stride(0), ops._ptr(ga),
+                               ga.stride(0), ops._ptr(d_m3), d_m3.stride(0), ops._ptr(cs), ops._ptr(ws), ops._stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    intact = all(canary_ok(b, Rs) for b in (ybuf, ebuf, bbuf, gbuf, dbuf)) and (not wide or torch.equal(y2[:, :E], left))
+    res = {"h0": y, "emb": emb, "bits": bits, "ga": ga, "d_m3": d_m3, "dW_sem": ops.wgrad(g, emb), "dW_agg": ops.wgrad(ga.view(-1, E), m3.view(-1, E)),
+           "db_agg": cs.view(-1, E).sum(0), "d_addend": g}
+    return res, intact
+
+
+def same_bits(a, b):
+    if a.dtype == torch.uint8:
+        return torch.equal(a, b)
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def assert_same(one, two):
+    for k in two:
+        assert same_bits(one[k], two[k]), k
+
+
+def row_counts():
+    return [1, 31, 32, 33, 69, 32 * cus() + 7]
+
+
+@pytest.mark.parametrize("case", range(6))
+def test_fused_launches_are_bit_identical_to_the_launches_replaced(split_update, case):
+    """1 .. 69 rows: a short only tile, a full one, a short last one; 32 CUs + 7: one workgroup with two tiles, the second one short"""
+    ops = split_update
+    Rs = row_counts()[case]
+    with torch.no_grad():
+        ops_ = make_operands(Rs, seed=case)
+        two = two_launches(ops, *ops_)
+        frac = float((two["emb"] == 0).float().mean())
+        assert Rs < 64 or 0.2 < frac < 0.45, frac
+        one, intact = fused(ops, *ops_)
+        assert intact
+        assert_same(one, two)
+
+
+@pytest.mark.parametrize("variant", ["zero_m3_row", "zero_g_tile", "dense_ws", "wide_h0"])
+def test_fused_launches_zero_rows_and_strides(split_update, variant):
+    """a whole m3 row zero under a negative bias (all its bits clear), g zero on the second tile, Ws dense instead of the column block
+    [:, 4:] with row stride 388 every other case uses, h0 as the right half of a 2E-wide operand (the left half stays untouched)"""
+    ops = split_update
+    Rs = 69
+    with torch.no_grad():
+        ops_ = make_operands(Rs, seed=11, neg_row=Rs - 2 if variant == "zero_m3_row" else None, zero_g_tile=1 if variant == "zero_g_tile" else None,
+                             dense_ws=variant == "dense_ws")
+        assert ops_[3].stride(0) == (3 * E if variant == "dense_ws" else 3 * E + 4)
+        two = two_launches(ops, *ops_)
+        if variant == "zero_m3_row":
+            assert int(two["bits"][Rs - 2].max()) == 0 and float(two["emb"][Rs - 2].abs().max()) == 0.0 and float(two["ga"][Rs - 2].abs().max()) == 0.0
+        if variant == "zero_g_tile":
+            assert float(two["ga"][32:64].abs().max()) == 0.0 and float(two["ga"].abs().max()) > 0.0
+        one, intact = fused(ops, *ops_, wide=variant == "wide_h0")
+        assert intact
+        assert_same(one, two)
+
+
+def test_fused_launches_match_f64_as_the_launches_replaced_do(split_update):
+    """against an f64 evaluation of the two layers and their gradients (the ReLU mask taken from the fp32 bits both routes share): where the
+    bits of the two routes are equal the errors must be equal; were they not, the fused route may be no worse than twice the other"""
+    ops = split_update
+    Rs = 1000
+    with torch.no_grad():
+        m3, w_agg, b_agg, Ws, add, g = ops_ = make_operands(Rs, seed=7)
+        two = two_launches(ops, *ops_)
+        one, intact = fused(ops, *ops_)
+        assert intact
+        d = torch.float64
+        emb = torch.relu(m3.to(d).view(-1, E) @ w_agg.to(d).t() + b_agg.to(d)).view(Rs, 3 * E)
+        mask = (two["emb"] > 0).to(d)
+        ga = (g.to(d) @ Ws.to(d)) * mask
+        ref = {"h0": emb @ Ws.to(d).t() + add.to(d), "emb": emb, "ga": ga, "d_m3": (ga.view(-1, E) @ w_agg.to(d)).view(Rs, 3 * E),
+               "dW_sem": g.to(d).t() @ emb, "dW_agg": ga.view(-1, E).t() @ m3.to(d).view(-1, E), "db_agg": ga.view(-1, E).sum(0)}
+        depth = {"h0": 3 * E + 1, "emb": E, "ga": E, "d_m3": E, "dW_sem": Rs, "dW_agg": 3 * Rs, "db_agg": 3 * Rs}   # terms per result
+        for k, r in ref.items():
+            e_two, e_one = float((two[k].to(d) - r).abs().max()), float((one[k].to(d) - r).abs().max())
+            print(f"{k}: max |error| against f64: launches replaced {e_two:.3e}, fused {e_one:.3e}")
+            if same_bits(one[k], two[k]):
+                assert e_one == e_two, k
+            else:
+                assert e_one <= 2.0 * e_two, (k, e_one, e_two)
+            # (and neither route computes another formula: K roundings of 2^-23 of the largest result is loose for K fp32 accumulations)
+            assert e_one <= depth[k] * 2.0 ** -23 * max(1.0, float(r.abs().max())), (k, e_one)
+
+
+def test_three_launches_give_identical_bytes_and_a_graph_replays_them(split_update):
+    ops = split_update
+    L = ops.load_library()
+    Rs = 32 * cus() + 7
+    with torch.no_grad():
+        m3, w_agg, b_agg, Ws, add, g = ops_ = make_operands(Rs, seed=9)
+        runs = [fused(ops, *ops_)[0] for _ in range(3)]
+        runs = [{k: v.clone() for k, v in r.items()} for r in runs]
+        assert_same(runs[1], runs[0])
+        assert_same(runs[2], runs[0])
+        y, emb, ga, d_m3 = torch.empty(Rs, E, device="cuda"), torch.empty(Rs, 3 * E, device="cuda"), torch.empty(Rs, 3 * E, device="cuda"), torch.empty(Rs, 3 * E, device="cuda")
+        bits = torch.empty(Rs, 3 * E // 8, dtype=torch.uint8, device="cuda")
+        cs = torch.empty(3 * E, device="cuda")
+        ws = torch.empty(L.sb_encoder_tail_bwd_workspace(), dtype=torch.uint8, device="cuda")
+
+        def both():
+            y.copy_(add)
+            ops.encoder_tail_train_fwd(m3, w_agg, b_agg, Ws, y, y, emb, bits)
+            rc = L.sb_encoder_tail_bwd(Rs, ops._ptr(g), g.stride(0), ops._ptr(Ws), Ws.stride(0), ops._ptr(w_agg), ops._ptr(bits), bits.stride(0),
+                                       ops._ptr(ga), ga.stride(0), ops._ptr(d_m3), d_m3.stride(0), ops._ptr(cs), ops._ptr(ws), ops._stream())
+            assert rc == 0
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            both()                                   # warm-up on the capture stream (the launches' one-time attribute calls)
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            both()
+        for t in (y, emb, ga, d_m3, cs):
+            t.fill_(CANARY)
+        bits.fill_(0xA5)
+        graph.replay()
+        torch.cuda.synchronize()
+        got = {"h0": y, "emb": emb, "bits": bits, "ga": ga, "d_m3": d_m3, "db_agg": cs.view(-1, E).sum(0)}
+        for k, v in got.items():
+            assert same_bits(v, runs[0][k]), k
+
+
+def test_encoder_pair_train_gradients_are_the_same_with_the_switch_on_and_off(split_update):
+    """DHGN.encoder_pair_train under autograd on a rollout's own observations (5 environments, P = 8): h0 of both networks and every
+    parameter gradient bit for bit, the fused launches on the path with the switch on (the row thresholds forced to 1) and only then"""
+    ops = split_update
+    from distributed_multi_agent_reinforcement_learning_amd.mappo import MAPPO
+    from distributed_multi_agent_reinforcement_learning_amd.pursuit_env import Pursuit_Env
+    from tests.helpers import product_cfg
+    ops.ENCODER_TAIL_TRAIN_MIN_ROWS = 1
+    ops.MASKED_GRAD_MIN_ROWS = 1
+    ops.SORTED_ONES_MIN_QDIV = 1                                 # (the paired message pass at q_div = 1, as tests/test_update_parity_gpu.py)
+    cfg = product_cfg(8, 40, 40, T=6, depth=0, **{"runtime.use_graphs": False, "runtime.seed": 7})
+    torch.manual_seed(4)
+    agent = MAPPO(cfg, 5, 5, "Worker")
+    env = Pursuit_Env(cfg, num_envs=5)
+    agent.explore_env(env, 1)
+    st = agent._rollout_state(env)
+    o = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st._obs().items()}
+    net = agent.actor.shared_net
+    assert ops.msg_agg3_pair_train_ok(o["p_state"], o["o_state"], net.MSG_layers[2].weight, 1)
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    wa, wc = torch.randn(5, 8, E, device="cuda", generator=gen), torch.randn(5, 8, E, device="cuda", generator=gen)
+    params = [(n, q) for n, q in net.named_parameters() if q.requires_grad]
+    calls = []
+    real = ops.encoder_tail_train
+
+    def counting(*a):
+        calls.append(1)
+        return real(*a)
+    outs = {}
+    for on in (True, False):
+        ops.ENCODER_TAIL_TRAIN = on
+        ops.encoder_tail_train = counting
+        try:
+            for _, q in params:
+                q.grad = None
+            h0a, h0c = net.encoder_pair_train(o["p_state"], o["e_state"], o["o_state"], o["p_adj"], o["e_adj"], o["o_adj_bits"], 1)
+            ((h0a * wa).sum() + (h0c * wc).sum()).backward()
+        finally:
+            ops.encoder_tail_train = real
+        assert len(calls) == 2                                   # actor and critic, with the switch on only
+        outs[on] = {"h0a": h0a.detach().clone(), "h0c": h0c.detach().clone(), **{n: q.grad.clone() for n, q in params if q.grad is not None}}
+    assert {"AGG_layers.AGG_vertex_0.weight", "AGG_layers.AGG_vertex_0.bias", "semantic_layer.weight", "semantic_layer.bias",
+            "MSG_layers.0.weight"} <= set(outs[True])
+    assert set(outs[True]) == set(outs[False])
+    for k, v in outs[False].items():
+        assert float(v.abs().max()) > 0.0 or "MSG_layers.2" in k, k
+        assert same_bits(outs[True][k], v), k
+
+
+def test_predicate_keeps_small_batches_and_other_modes_on_the_two_launches(split_update):
+    ops = split_update
+    Rs = 40
+    m3, w_agg, b_agg, Ws, add, _ = make_operands(Rs, seed=2)
+    assert ops.ENCODER_TAIL_TRAIN_MIN_ROWS > 4096          # the parity fixtures (a few hundred rows) stay on sb_gemm / sb_gemm_signs / sb_gemm_masked_bits
+    assert not ops.encoder_tail_train_ok(m3, w_agg, b_agg, Ws, add)
+    ops.ENCODER_TAIL_TRAIN_MIN_ROWS = 1
+    assert ops.encoder_tail_train_ok(m3, w_agg, b_agg, Ws, add)
+    assert not ops.encoder_tail_train_ok(m3, w_agg, None, Ws, add)
+    assert not ops.encoder_tail_train_ok(m3[:, :2 * E], w_agg, b_agg, Ws, add)
+    assert not ops.encoder_tail_train_ok(m3, w_agg, b_agg, Ws, torch.zeros(Rs, 2 * E, device="cuda")[:, E:])     # the addend is a dense temporary
+    assert not ops.encoder_tail_train_ok(m3, w_agg, b_agg, torch.zeros(E, 3 * E + 3, device="cuda")[:, 3:], add)  # Ws block misaligned
+    assert not ops.encoder_tail_train_ok(m3.double(), w_agg, b_agg, Ws, add)
+    for name in ("ENCODER_TAIL_TRAIN", "RELU_LINK", "RELU_BITS"):
+        setattr(ops, name, False)
+        assert not ops.encoder_tail_train_ok(m3, w_agg, b_agg, Ws, add)
+        setattr(ops, name, True)
+    ops.set_matmul_mode("fp32")
+    assert not ops.encoder_tail_train_ok(m3, w_agg, b_agg, Ws, add)

@@ -1,6 +1,7 @@
 """A/B of one boolean switch of ops (RELU_LINK: the ReLU backward in the input-gradient GEMMs' epilogues / separate passes;
 PPO_FROM_PROB: Categorical inside the loss launch / torch.distributions; ENCODER_TAIL: the rollout encoder's AGG + semantic layers as
-one launch / two -- a rollout switch, so each setting keeps its own captured tick programs) in ONE process, alternating iteration by iteration: boxes of the
+one launch / two -- a rollout switch, so each setting keeps its own captured tick programs; ENCODER_TAIL_TRAIN: the same two layers of the
+update, one launch each way / the two linear calls with their ReluLink) in ONE process, alternating iteration by iteration: boxes of the
 pool differ by a few percent, two runs on two boxes cannot resolve a 1 % change.   python tools/ab_switch.py cfg3 RELU_LINK"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
