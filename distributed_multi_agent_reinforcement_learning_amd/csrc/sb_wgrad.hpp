@@ -14,13 +14,29 @@
 // Producer / consumer: 12 waves, three per SIMD.  Waves 0-7 (two per SIMD) only read operands from the LDS image and issue MFMAs; waves
 // 8-11 (one per SIMD) only load, split and stage.  The image is double-buffered (2 x 48 KB at M + N = 512): the loaders write chunk c + 1
 // while the MFMA waves multiply chunk c, one barrier per chunk.  Each loader lane keeps the raw rows of DEPTH chunks in flight (96 KB
-// per CU at M + N = 512: 2 units per lane and chunk, 3 chunks; 64 KB at M + N = 256: 1 unit, 4 chunks), so the prefetch depth is no longer paid for out of the MFMA waves' registers, and
-// the MFMA stream of a SIMD is never interrupted by splitting.  All 12 waves get the same register allocation: 168 per lane at 3 waves
-// per SIMD; the kernels take 110 (128 x 128), 136 (128 x 256, 256 x 128), 148 (384 x 128) and 153 (128 x 384), no scratch
-// (hipcc -Rpass-analysis=kernel-resource-usage).  DESIGN.md section 11 has the kernel times.
+// per CU at M + N = 512: 2 units per lane and chunk, 3 chunks; 64 KB at M + N = 256: 1 unit, 4 chunks), so the prefetch depth is not
+// paid for out of the MFMA waves' registers.  All 12 waves get the same register allocation: 168 per lane at 3 waves per SIMD; the
+// kernels take 107 (128 x 128), 132 (128 x 256, 256 x 128), 148 (384 x 128) and 153 (128 x 384), no scratch
+// (hipcc -Rpass-analysis=kernel-resource-usage).
+// What a loader wave may issue beside the MFMA waves of its SIMD (stamps in profiles/r20_sb_wgrad_lab.txt): its
+// loads, LDS stores and single-rate vector instructions overlap with their MFMAs; packed fp32 instructions (v_pk_add_f32, which the
+// compiler's SLP vectoriser makes of the two subtractions of a split) do not -- with them the loader advanced at a fifth of its speed
+// while MFMAs were in flight, and a chunk took the MFMA phase PLUS most of the staging.  Hence sb_wg_split2 below.  The prefetch depth,
+// a static s_setprio on either role and one MFMA wave per SIMD instead of two did not move the kernel's time and are not here.
 // The chunk ranges, the chunk order and the order of the six piece products are those of the 8-wave kernel this replaces: every
 // output sees the same sums in the same order, bit for bit.  The K % 16 rows behind the last full chunk are the exception: the last
 // workgroup multiplies them in fp32 itself (see sb_wgrad_mma), after its chunks, the same way at every launch.
+// Probe hooks and knock-outs: nothing in the product.  tools/microbench/sb_wgrad_lab.hip compiles this header with the hooks defined to
+// sum s_memtime cycles per phase and wave, and with SB_WG_KNOCK to leave one side of the pipeline out (timing only).
+#ifndef SB_WG_PROBE
+#define SB_WG_PROBE_BEGIN
+#define SB_WG_PROBE(phase)
+#define SB_WG_PROBE_USE(r)
+#define SB_WG_PROBE_END(wave, lane)
+#endif
+#ifndef SB_WG_KNOCK
+#define SB_WG_KNOCK 0
+#endif
 constexpr int SB_WG_MMA_WAVES = 8, SB_WG_LOAD_WAVES = 4, SB_WG_THREADS = 64 * (SB_WG_MMA_WAVES + SB_WG_LOAD_WAVES);
 
 template <int MT, int NT>
@@ -38,10 +54,25 @@ struct SbWgCfg {
     static constexpr int LDS_BYTES = 2 * IMG * 16;
 };
 
+// sb_split2 for the loader waves: the same operations on the same values, so the same pieces bit for bit, but one of the two
+// subtractions of each level passes through an empty asm.  That keeps the SLP vectoriser from pairing them into v_pk_add_f32
+// (plus the v_mov that line the pairs up), which does not issue beside the SIMD's MFMAs (see above): 64 v_sub_f32 per chunk and
+// lane instead of 32 v_pk_add_f32 + 24 v_mov_b32 took a 16-row chunk of the 512-column kernels from 4 050 to 3 050 cycles.
+__device__ __forceinline__ void sb_wg_split2(float x0, float x1, uint32_t &p1, uint32_t &p2, uint32_t &p3) {
+    p1 = sb_pk(x0, x1);
+    float r0 = x0 - __builtin_bit_cast(float, p1 << 16), r1 = x1 - __builtin_bit_cast(float, p1 & 0xffff0000u);
+    asm("" : "+v"(r0));
+    p2 = sb_pk(r0, r1);
+    float q0 = r0 - __builtin_bit_cast(float, p2 << 16), q1 = r1 - __builtin_bit_cast(float, p2 & 0xffff0000u);
+    asm("" : "+v"(q0));
+    p3 = sb_pk(q0, q1);
+}
+
 // feature f's slot in the LDS image
 __device__ __forceinline__ int sb_swz(int f) { return (f & ~3) | ((f & 3) ^ ((f >> 3) & 3)); }
 
-// Loader role (loader wave lw = wave - 8, wave-uniform): fetch rows into registers DEPTH chunks ahead, split them into the image the MFMA waves read next.
+// Loader role (loader wave lw = wave - 8, wave-uniform): fetch rows into registers DEPTH chunks ahead, split them into the image the
+// MFMA waves read next.
 // The barrier sequence (one before the first chunk, one per chunk, one before the tail) is the MFMA role's.
 template <int MT, int NT>
 __device__ __forceinline__ void sb_wgrad_loader(int lw, int lane, const float *__restrict__ A, int64_t lda, const float *__restrict__ B, int64_t ldb, int64_t K,
@@ -81,6 +112,13 @@ __device__ __forceinline__ void sb_wgrad_loader(int lw, int lane, const float *_
     // registers -> three bf16 pieces -> LDS image
     auto stage = [&](const float4 (&r)[C::UL][4], uint4 *img) {
         uint2 *img2 = (uint2 *)img;
+        if constexpr (SB_WG_KNOCK == 2) {                // no splits, no LDS stores: the loads are only waited for
+#pragma unroll
+            for (int u = 0; u < C::UL; u++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) asm volatile("" ::"v"(r[u][j].x), "v"(r[u][j].y), "v"(r[u][j].z), "v"(r[u][j].w));
+            return;
+        }
 #pragma unroll
         for (int u = 0; u < C::UL; u++) {
             if (!on[u]) continue;
@@ -92,13 +130,17 @@ __device__ __forceinline__ void sb_wgrad_loader(int lw, int lane, const float *_
                     const float4 &v0 = r[u][2 * q], &v1 = r[u][2 * q + 1];
                     const float x0 = t == 0 ? v0.x : t == 1 ? v0.y : t == 2 ? v0.z : v0.w;
                     const float x1 = t == 0 ? v1.x : t == 1 ? v1.y : t == 2 ? v1.z : v1.w;
-                    sb_split2(x0, x1, p[0][q], p[1][q], p[2][q]);
+                    sb_wg_split2(x0, x1, p[0][q], p[1][q], p[2][q]);
                 }
 #pragma unroll
-                for (int s = 0; s < 3; s++) img2[2 * s * C::NO * C::COLS + slot2[u] + 2 * (t ^ sx[u])] = make_uint2(p[s][0], p[s][1]);
+                for (int s = 0; s < 3; s++) {
+                    if constexpr (SB_WG_KNOCK == 3) asm volatile("" ::"v"(p[s][0]), "v"(p[s][1]));   // splits, no LDS stores
+                    else img2[2 * s * C::NO * C::COLS + slot2[u] + 2 * (t ^ sx[u])] = make_uint2(p[s][0], p[s][1]);
+                }
             }
         }
     };
+    SB_WG_PROBE_BEGIN
     if (c_beg < c_end) {
 #pragma unroll
         for (int d = 0; d < D; d++) fetch(raw[d], c_beg + d);
@@ -110,18 +152,25 @@ __device__ __forceinline__ void sb_wgrad_loader(int lw, int lane, const float *_
         fetch(raw[0], c_beg + D);
     }
     lds_barrier();
+    SB_WG_PROBE(0)
     // invariant at the top of step c: image (c - c_beg) % 2 holds chunk c; raw[(c + k - c_beg) % D] holds chunk c + k, k = 1 .. D
     for (int64_t c = c_beg; c < c_end; c += D) {
 #pragma unroll
         for (int d = 0; d < D; d++) {
             const int64_t cc = c + d;
             if (cc >= c_end) break;
+            SB_WG_PROBE_USE(raw[(d + 1) % D])
+            SB_WG_PROBE(4)
             // at cc = c_end - 1 this stages a copy of the last chunk into the image nobody reads again (no branch: see fetch)
             stage(raw[(d + 1) % D], sb_lds + ((cc + 1 - c_beg) & 1) * C::IMG);
+            SB_WG_PROBE(1)
             fetch(raw[(d + 1) % D], cc + 1 + D);
+            SB_WG_PROBE(2)
             lds_barrier();
+            SB_WG_PROBE(3)
         }
     }
+    SB_WG_PROBE_END(SB_WG_MMA_WAVES + lw, lane)
     if (tail) {                                          // the K % 16 rows after the last full chunk, zero-filled: raw fp32, [row][COLS] over image 0
         const int64_t r0 = (K / C::CR) * C::CR;
         float4 *rawf = (float4 *)sb_lds;                 // 64 COLS of the image's 96 COLS bytes; every MFMA wave is past its last chunk here
@@ -191,11 +240,16 @@ __device__ __forceinline__ void sb_wgrad_mma(int wave, int lane, int64_t c_beg, 
             }
         }
     };
+    SB_WG_PROBE_BEGIN
     lds_barrier();
+    SB_WG_PROBE(0)
     for (int64_t c = c_beg; c < c_end; c++) {
-        multiply(sb_lds + ((c - c_beg) & 1) * C::IMG);
+        if constexpr (SB_WG_KNOCK != 1) multiply(sb_lds + ((c - c_beg) & 1) * C::IMG);
+        SB_WG_PROBE(1)
         lds_barrier();
+        SB_WG_PROBE(3)
     }
+    SB_WG_PROBE_END(wave, lane)
     if (tail) {
         // The tail rows are multiplied in fp32 itself (v_mfma_f32_32x32x2_f32: a chain of round-to-nearest multiply-adds; lane (i, g)
         // feeds tile row / column i of row 2 s + g), not as piece products: a product of fewer than 16 rows, which is a tail alone,
