@@ -2463,6 +2463,7 @@ int launch_msgw3(const mo_msg_rel *rel, int R, int P, int E, const float *p, int
 #include "kickstart.hpp"      // algo.bc_coef: the PPO row and the imitation row of a sample in one loss launch (after imitation.hpp)
 #include "value_norm.hpp"     // algo.use_value_norm: GAE on denormalised values, the running statistics and the normalised targets
 #include "fused_adam.hpp"     // algo.minibatch_steps: the gradient clip and the Adam step of one mini-batch in two launches
+#include "team_attention.hpp" // algo.e3d_comm: masked multi-head attention between the pursuers of a team, forward and backward
 
 constexpr int SB_WGRAD_WGS = 256;  // one workgroup per CU (96 KB of LDS each)
 

@@ -23,6 +23,11 @@ ParticleEnv.central_features' row, the 32 columns plus 8 per team-mate (`critic_
 are the ones of `local`, so execution stays decentralised.
 `algo.use_obs_norm` (off by default; obs_norm.py): both encoders read the features normalised by a running mean / std that is frozen
 during a rollout and merged once after it; the first rollout is the option-off one bit for bit.
+`algo.e3d_comm: attention` (off by default; algo.e3d_comm_heads: 1 | 2 | 4 | 8, default 4): between the actor's
+encoder and its GRU, one round of multi-head attention between the embeddings of the pursuers that can talk to each other at that tick
+(TeamComm: emb_i + out(attention(qkv(emb))_i) over the hearing set M_i = {i} + the live j with pp_adj[i][j] and pp_adj[j][i]; one
+ops.comm_mask launch per tick writes the sets as 64-bit words into the buffer's `comm` field, ops.team_attention is the same kernel in
+the rollout and in the update).  comm.out starts at zero, so the first rollout is the option-off one bit for bit; the critic is untouched.
 """
 import math
 import os
@@ -43,6 +48,7 @@ from .particle_agent import ParticleMAPPO, ParticleTrainer, finish_env, train_pa
 FEAT = 16   # e3d_policy_features columns (include/e3d_env.h); algo.e3d_features: pursuit has PURSUIT_FEAT
 E3D_FEATURES = ("basic", "pursuit")
 E3D_CRITIC = ("local", "central")
+E3D_COMM = ("none", "attention")
 
 
 class E3dEncoder(nn.Module):
@@ -81,6 +87,25 @@ class GaussianActor(_Trunk):
             self.log_std = nn.Parameter(torch.full((action_dim,), float(log_std_init)))
 
 
+class TeamComm(nn.Module):
+    """algo.e3d_comm: attention -- emb (G P, E) rows in groups of P pursuers and their (G, P) hearing-set words -> emb + out(o), o the
+    masked multi-head attention of qkv(emb) inside every group (ops.team_attention); out starts at zero, so the layer starts as the identity"""
+
+    def __init__(self, embedding_dim, heads):
+        super().__init__()
+        self.heads = int(heads)
+        self.qkv = nn.Linear(embedding_dim, 3 * embedding_dim)
+        self.out = nn.Linear(embedding_dim, embedding_dim)
+        with torch.no_grad():
+            self.out.weight.zero_()
+            self.out.bias.zero_()
+
+    def forward(self, emb, words):
+        # (the kernels read dense words: the rollout's, a time slice of the buffer, are copied -- N P words; the update's are dense)
+        o = ops.team_attention(ops.linear(emb, self.qkv.weight, self.qkv.bias), words.contiguous(), self.heads)
+        return emb + ops.linear(o, self.out.weight, self.out.bias)
+
+
 class E3dCritic(_Trunk):
     def __init__(self, in_dim, embedding_dim, num_layers, rnn_hidden_dim, is_sn=False):
         super().__init__()
@@ -105,6 +130,8 @@ class _E3dRollout:
         self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.live = z(N, P)   # this step's live mask (e3d_policy_record keeps it current)
+        if agent.e3d_comm == "attention":
+            self.comm = z(N, P, dt=torch.int64)   # this step's hearing sets (ops.comm_mask), where no buffer row takes them
         self.t = 0
 
 
@@ -164,6 +191,30 @@ def e3d_critic_options(cfg):
     return critic
 
 
+def e3d_comm_options(cfg):
+    """-> (e3d_comm, e3d_comm_heads) of cfg.algo, validated (ValueError naming the key): "none", or "attention" (DESIGN.md section 7m), one
+    round of team attention between the actor's encoder and its GRU -- whose kernels are compiled for 128-wide embeddings and keep a
+    pursuer's hearing set in one 64-bit word"""
+    a = cfg.algo
+    comm = str(a.get("e3d_comm", "none"))
+    if comm not in E3D_COMM:
+        raise ValueError(f"algo.e3d_comm: {comm!r} is not one of {E3D_COMM}")
+    try:
+        heads = int(a.get("e3d_comm_heads", 4))
+    except (TypeError, ValueError):
+        heads = None
+    if heads not in ops.COMM_HEADS or isinstance(a.get("e3d_comm_heads", 4), bool):
+        raise ValueError(f"algo.e3d_comm_heads: {a.get('e3d_comm_heads')!r} is not one of {ops.COMM_HEADS}")
+    if comm == "attention":
+        if int(a.embedding_dim) != ops.COMM_E:
+            raise ValueError(f"algo.e3d_comm: attention needs algo.embedding_dim {ops.COMM_E} (the width its kernels are compiled for), "
+                             f"got {int(a.embedding_dim)}")
+        if int(cfg.env.num_defender) > ops.COMM_MAX_P:
+            raise ValueError(f"algo.e3d_comm: attention supports env.num_defender <= {ops.COMM_MAX_P} (one mask word per pursuer), "
+                             f"got {int(cfg.env.num_defender)}")
+    return comm, heads
+
+
 class E3dMAPPO(ParticleMAPPO):
     """rollout (run_episode) and PPO loss (_minibatch_loss) of the Gaussian policy on env_3d; the update loop is ParticleMAPPO.train"""
 
@@ -175,6 +226,7 @@ class E3dMAPPO(ParticleMAPPO):
         self.e3d_critic = e3d_critic_options(cfg)   # the critic's input with every team-mate
         # the width of the critic's rows; feat_dim stays the actor's
         self.critic_feat_dim = central_feat(int(cfg.env.num_defender)) if self.e3d_critic == "central" else self.feat_dim
+        self.e3d_comm, self.e3d_comm_heads = e3d_comm_options(cfg)   # team attention in the actor
         self.use_obs_norm, self.obs_norm_clip = onorm.obs_norm_options(cfg)   # running mean / std on the policy features
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
@@ -198,6 +250,9 @@ class E3dMAPPO(ParticleMAPPO):
                                    float(a.get("log_std_init", 0.0)), sn, self.gauss_std).to(self.device)
         self.critic = E3dCritic(self.critic_feat_dim, self.embedding_dim, self.num_layers, self.rnn_hidden_dim, sn).to(self.device)
         self.ac_parameters = list(self.actor.parameters()) + list(self.critic.parameters())
+        if self.e3d_comm == "attention":   # constructed last, after the critic: every other parameter keeps the generator draws of `none`
+            self.actor.comm = TeamComm(self.embedding_dim, self.e3d_comm_heads).to(self.device)
+            self.ac_parameters += list(self.actor.comm.parameters())
         self.obs_norm = onorm.ObsNorm(self.obs_norm_clip, self.device) if self.use_obs_norm else None
 
     # ---- rollout -------------------------------------------------------------------------------------------------------------
@@ -207,10 +262,13 @@ class E3dMAPPO(ParticleMAPPO):
     def _buffer_dims(self, env):
         return env.num_envs, env.max_step, env.p_num
 
-    def _policy_step(self, st, greedy=False):
-        """features -> both encoders -> both GRU cells (one launch per layer) -> value -> Gaussian head and sample"""
+    def _policy_step(self, st, greedy=False, words=None):
+        """features -> both encoders (with algo.e3d_comm: attention the actor's embeddings then hear their team under `words`, this tick's
+        (N, P) hearing sets) -> both GRU cells (one launch per layer) -> value -> Gaussian head and sample"""
         N, P, E = st.N, st.P, self.embedding_dim
         emb_a = self.actor.shared_net(st.fa.view(N * P, self.feat_dim))
+        if self.e3d_comm == "attention":
+            emb_a = self.actor.comm(emb_a.reshape(N * P, E), words)
         emb_c = self.critic.shared_net(st.fc.view(N * P, self.critic_feat_dim))
         cur, nxt = st.t & 1, (st.t + 1) & 1
         fa, fc = ops.gru_step_multi([emb_a.reshape(-1, E), emb_c.reshape(-1, E)], [st.hbuf_a[cur], st.hbuf_c[cur]], [self.actor.GRU, self.critic.GRU],
@@ -256,6 +314,8 @@ class E3dMAPPO(ParticleMAPPO):
                    active=z(N, T, P), v_n=z(N, T + 1, P))
         if self.value_norm is not None:
             buf["v_mask"] = z(N, P)   # the bootstrap mask of v_n[:, T] (algo.use_value_norm only)
+        if self.e3d_comm == "attention":
+            buf["comm"] = torch.zeros((N, T, P), dtype=torch.int64, device=self.device)   # the hearing sets of every row, one word each
         if self.teacher:
             buf["a_star"] = z(N, T, P, self.latent_dim)   # the scripted pursuers' action of every row, in the policy's pre-squash space (algo.bc_iterations / bc_coef only)
         return buf
@@ -290,7 +350,10 @@ class E3dMAPPO(ParticleMAPPO):
         team_coef = self._team_coef(buf)
         for t in range(env.max_step):
             self._features(env, st, accumulate=buf is not None)   # evaluation never accumulates
-            self._policy_step(st, greedy)
+            words = None
+            if self.e3d_comm == "attention":   # who hears whom at this tick, straight into the buffer's row
+                words = ops.comm_mask(env.obs["pp_adj"], st.live, st.comm if buf is None else buf["comm"][:, t])
+            self._policy_step(st, greedy, words)
             if follow is not None:
                 self._expert_tick(env, st.env_action, buf, t, follow)
             env.evader_step()
@@ -310,12 +373,15 @@ class E3dMAPPO(ParticleMAPPO):
         return acc["ret"], acc["captured"] != 0, acc["length"]
 
     # ---- update ------------------------------------------------------------------------------------------------------------------
-    def sequence_forward(self, feat_a, feat_c, batch, steps, return_ls_raw=False):
+    def sequence_forward(self, feat_a, feat_c, batch, steps, return_ls_raw=False, words=None):
         """(batch, T, P, feat_dim / critic_feat_dim) features of whole episodes -> mu (batch, T, P, A) and values (batch, T, P), time-major views; with
-        return_ls_raw also ls_raw (state mode: the LogStd head on the same GRU features, (batch, T, P, A); param mode: log_std)"""
+        return_ls_raw also ls_raw (state mode: the LogStd head on the same GRU features, (batch, T, P, A); param mode: log_std);
+        words (algo.e3d_comm: attention): the (batch, T, P) hearing sets of the rows, whose groups are P consecutive rows"""
         P = feat_a.shape[2]
         R = batch * steps * P
         emb_a, emb_c = self.actor.shared_net(feat_a.reshape(R, self.feat_dim)), self.critic.shared_net(feat_c.reshape(R, self.critic_feat_dim))
+        if self.e3d_comm == "attention":
+            emb_a = self.actor.comm(emb_a, words.reshape(batch * steps, P))
         h0 = [torch.zeros(m.num_layers, batch * P, m.rnn_hidden_dim, dtype=emb_a.dtype, device=emb_a.device) for m in (self.actor, self.critic)]
         fa, fc = ops.gru_multi([emb_a, emb_c], h0, [self.actor.GRU, self.critic.GRU], agents=P, steps=steps, zero_state=True)
         fa, fc = fa.reshape(steps, batch, P, -1), fc.reshape(steps, batch, P, -1)
@@ -326,8 +392,13 @@ class E3dMAPPO(ParticleMAPPO):
         ls_raw = self.actor.LogStd(fa).permute(1, 0, 2, 3) if self.gauss_std == "state" else self.actor.log_std
         return mu, values, ls_raw
 
+    def _words(self, buf, n0, n1):
+        """the hearing sets of episodes [n0, n1) (algo.e3d_comm: attention; None without it: the buffer has no such field)"""
+        return buf["comm"][n0:n1] if self.e3d_comm == "attention" else None
+
     def _minibatch_loss(self, buf, n0, n1, adv, v_target, dk):
-        mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True)
+        mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True,
+                                                     words=self._words(buf, n0, n1))
         tail = self._loss_tail(buf, n0, n1, values, adv, v_target)
         if self.policy_ex:
             return ops.ppo_loss_gauss_ex(mu, ls_raw, *tail, log_std_min=self.log_std_min, log_std_max=self.log_std_max,
@@ -347,14 +418,16 @@ class E3dMAPPO(ParticleMAPPO):
         return sq_sum / (self.action_dim * rows)
 
     def _imitation_loss(self, buf, n0, n1, v_target, sums):
-        mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True)
+        mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True,
+                                                     words=self._words(buf, n0, n1))
         lo, hi = (self.log_std_min, self.log_std_max) if self.policy_ex else (-float("inf"), float("inf"))
         return ops.bc_loss_gauss(mu, ls_raw, buf["a_star"][n0:n1], *self._imitation_tail(buf, n0, n1, values, v_target), log_std_min=lo,
                                  log_std_max=hi, fit_std=self.imitation.fit_std, wrap0=self.bc_wrap0, sums=sums,
                                  metric="angle" if self.gauss_squash == "direction" else "mse")
 
     def _kick_loss(self, buf, n0, n1, adv, v_target, coef, sums, dk):
-        mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True)
+        mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True,
+                                                     words=self._words(buf, n0, n1))
         lo, hi = (self.log_std_min, self.log_std_max) if self.policy_ex else (-float("inf"), float("inf"))
         a_n, *tail = self._loss_tail(buf, n0, n1, values, adv, v_target)
         return ops.ppo_bc_loss_gauss(mu, ls_raw, a_n, buf["a_star"][n0:n1], *tail[:-1], coef, tail[-1], log_std_min=lo, log_std_max=hi,
@@ -363,7 +436,8 @@ class E3dMAPPO(ParticleMAPPO):
 
     def policy_meta(self):
         """the "policy" entry of checkpoints and resume bundles: None in the default mode (param, clip, basic features), whose files
-        carry none; e3d_features / e3d_evader_obs only with algo.e3d_features: pursuit, e3d_critic only with algo.e3d_critic: central"""
+        carry none; e3d_features / e3d_evader_obs only with algo.e3d_features: pursuit, e3d_critic only with algo.e3d_critic: central,
+        e3d_comm / e3d_comm_heads only with algo.e3d_comm: attention"""
         meta = {}
         if self.policy_ex:
             meta.update(gauss_std=self.gauss_std, gauss_squash=self.gauss_squash, log_std_min=self.log_std_min, log_std_max=self.log_std_max)
@@ -371,19 +445,26 @@ class E3dMAPPO(ParticleMAPPO):
             meta.update(e3d_features=self.e3d_features, e3d_evader_obs=self.e3d_evader_obs)
         if self.e3d_critic == "central":
             meta.update(e3d_critic=self.e3d_critic)
+        if getattr(self, "e3d_comm", "none") == "attention":
+            meta.update(e3d_comm=self.e3d_comm, e3d_comm_heads=self.e3d_comm_heads)
         return meta or None
 
     def check_policy_meta(self, meta, what):
         """ValueError naming the config key when a file's policy (its "policy" entry; None = the default mode) is not this agent's:
         gauss_std and gauss_squash, and with an option on (where the bounds act) log_std_min / log_std_max as well -- other bounds would
         neither reproduce the saved policy nor continue its run bit for bit; and the feature set and its evader model (a file without the
-        entries was written with basic, sensed, local): other inputs fit neither the first layer nor what the weights were trained on"""
+        entries was written with basic, sensed, local): other inputs fit neither the first layer nor what the weights were trained on;
+        and e3d_comm with, where it is on, its head count (a file without the entry was written with none): the actor has the layer or not"""
         meta = meta or {}
-        for key, default in (("e3d_features", "basic"), ("e3d_evader_obs", "sensed"), ("e3d_critic", "local"), ("gauss_std", "param"),
-                             ("gauss_squash", "clip")):
+        for key, default in (("e3d_features", "basic"), ("e3d_evader_obs", "sensed"), ("e3d_critic", "local"), ("e3d_comm", "none"),
+                             ("gauss_std", "param"), ("gauss_squash", "clip")):
             theirs, mine = meta.get(key, default), getattr(self, key, default)
             if theirs != mine:
                 raise ValueError(f"{what} was written with algo.{key}: {theirs}, this agent has algo.{key}: {mine}")
+        if getattr(self, "e3d_comm", "none") == "attention":   # (heads split the same weights differently: the shapes would load)
+            theirs, mine = int(meta["e3d_comm_heads"]), self.e3d_comm_heads
+            if theirs != mine:
+                raise ValueError(f"{what} was written with algo.e3d_comm_heads: {theirs}, this agent has algo.e3d_comm_heads: {mine}")
         if self.policy_ex:   # (the default mode has no bounds; its files carry no entry)
             for key in ("log_std_min", "log_std_max"):
                 theirs, mine = float(meta[key]), getattr(self, key)

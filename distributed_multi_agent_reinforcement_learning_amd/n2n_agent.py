@@ -64,6 +64,9 @@ class N2nMAPPO(ParticleMAPPO):
         if bool(a.get("use_obs_norm", False)):
             raise ValueError("algo.use_obs_norm: true is built for runtime.env e3d only; the env_n2n inputs are node states whose "
                              "differences the message kernels form and whose zero rows stand for absent nodes (set use_obs_norm to false)")
+        if str(a.get("e3d_comm", "none")) != "none":
+            raise ValueError(f"algo.e3d_comm: {a.get('e3d_comm')} is built for runtime.env e3d only; the DHGN encoder of env_n2n already passes "
+                             "messages along pp_adj (leave the key out)")
         if int(cfg.env.num_defender) > MAX_P:
             raise ValueError(f"env.num_defender={cfg.env.num_defender}: the DHGN message kernels take at most {MAX_P} pursuers per row")
         if int(cfg.env.state_dim) != 4 or int(cfg.env.action_dim) != 9 or int(a.num_relation) != 3:

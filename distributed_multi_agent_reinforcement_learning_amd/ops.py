@@ -22,7 +22,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "ppo_loss_diag_workspace", "ppo_loss_gauss_diag_workspace", "ppo_ratio", "ppo_diag_rows_host", "fused_adam_workspace",
            "fused_adam_grid", "fused_adam_norm", "fused_adam_step", "fused_adam_advance_host", "fused_adam_rows_host", "bc_loss_workspace",
            "bc_loss_gauss_fwd_bwd", "bc_loss_gauss_ex_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "ppo_bc_loss_workspace",
-           "ppo_bc_loss_gauss_fwd_bwd", "ppo_bc_loss_cat_fwd_bwd", "mappo_ops_error_string")
+           "ppo_bc_loss_gauss_fwd_bwd", "ppo_bc_loss_cat_fwd_bwd", "team_comm_mask", "team_attention_fwd", "team_attention_bwd",
+           "team_comm_mask_host", "team_attention_fwd_host", "team_attention_bwd_host", "mappo_ops_error_string")
 
 _lib = None
 
@@ -144,6 +145,12 @@ def load_library():
                                               i32, vp, vp, vp, vp, vp, vp]
         L.e3d_bc_select.argtypes = [i32, i32, vp, vp, i32, f64, vp, vp, i64, vp]
         L.n2n_bc_select.argtypes = [i32, i32, vp, vp, vp, vp, i64, vp]
+        L.team_comm_mask.argtypes = [i64, i32, vp, i64, vp, i64, vp, i64, vp]
+        L.team_attention_fwd.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp]
+        L.team_attention_bwd.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.team_comm_mask_host.argtypes = [i64, i32, vp, i64, vp, i64, vp, i64]
+        L.team_attention_fwd_host.argtypes = [i64, i32, i32, vp, vp, vp, vp]
+        L.team_attention_bwd_host.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp]
         L.sb_split_diag.argtypes = [i64, vp, vp, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
@@ -2431,3 +2438,76 @@ def gru(x, h0, gru_module, inplace_hidden=False, agents=0, steps=None):
     if all(t.data_ptr() == h0[k].data_ptr() for k, t in enumerate(hn)):
         return inp, h0
     return inp, torch.stack(hn, 0)
+
+
+# ---- team attention of the env_3d actor (algo.e3d_comm: attention; include/mappo_ops.h team_*) ------------------
+COMM_E, COMM_HEADS, COMM_MAX_P = 128, (1, 2, 4, 8), 64
+
+
+def comm_mask(pp_adj, live, out):
+    """out[g, i] <- the hearing set of pursuer i of group g as an int64 word (team_comm_mask): bit j iff j == i, or i and j are both live
+    and each is in the other's communication range.  pp_adj (G, P, P) and live (G, P) fp32, dense inside a group; out (G, P) int64 whose
+    rows may be strided (a time slice of an (N, T, P) buffer).  One launch -> out"""
+    _need_gpu(pp_adj, "comm_mask")
+    assert pp_adj.dim() == 3 and pp_adj.shape[1] == pp_adj.shape[2], "comm_mask: pp_adj is (G, P, P)"
+    G, P = int(pp_adj.shape[0]), int(pp_adj.shape[1])
+    if not 1 <= P <= COMM_MAX_P:
+        raise ValueError(f"comm_mask: P = {P} pursuers, a word holds 1 .. {COMM_MAX_P}")
+    assert pp_adj.dtype == torch.float32 and (G == 0 or (pp_adj.stride(2) == 1 and pp_adj.stride(1) == P and pp_adj.stride(0) >= P * P)), "comm_mask: pp_adj"
+    assert live.dtype == torch.float32 and tuple(live.shape) == (G, P) and live.is_cuda and (G == 0 or (live.stride(1) == 1 and live.stride(0) >= P)), "comm_mask: live"
+    assert out.dtype == torch.int64 and tuple(out.shape) == (G, P) and out.is_cuda and (G == 0 or (out.stride(1) == 1 and out.stride(0) >= P)), "comm_mask: out"
+    if G:
+        _check(load_library().team_comm_mask(G, P, _ptr(pp_adj), pp_adj.stride(0), _ptr(live), live.stride(0), _ptr(out), out.stride(0), _stream()),
+               "team_comm_mask")
+    return out
+
+
+def _team_attention_args(qkv, words, heads):
+    _need_gpu(qkv, "team_attention")
+    if int(heads) not in COMM_HEADS:
+        raise ValueError(f"team_attention: heads = {heads} is not one of {COMM_HEADS}")
+    assert words.dim() == 2 and words.dtype == torch.int64 and words.is_cuda and words.is_contiguous(), "team_attention: words is a dense (G, P) int64 tensor"
+    G, P = int(words.shape[0]), int(words.shape[1])
+    if not 1 <= P <= COMM_MAX_P:
+        raise ValueError(f"team_attention: P = {P} pursuers, a word holds 1 .. {COMM_MAX_P}")
+    assert qkv.dtype == torch.float32 and tuple(qkv.shape) == (G * P, 3 * COMM_E) and qkv.is_contiguous() and qkv.data_ptr() % 16 == 0, \
+        "team_attention: qkv is a dense (G P, 384) fp32 tensor"
+    return G, P, int(heads)
+
+
+class _TeamAttention(torch.autograd.Function):
+    """saves qkv, words and the (G, H, P) log-sum-exp; the backward recomputes the probabilities from it (team_attention_bwd)"""
+
+    @staticmethod
+    def forward(ctx, qkv, words, heads):
+        G, P, H = _team_attention_args(qkv, words, heads)
+        out = torch.empty((G * P, COMM_E), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((G, H, P), dtype=torch.float32, device=qkv.device)
+        if G:   # (an empty tensor has no address to pass)
+            _check(load_library().team_attention_fwd(G, P, H, _ptr(qkv), _ptr(words), _ptr(out), _ptr(lse), _stream()), "team_attention_fwd")
+        ctx.save_for_backward(qkv, words, lse)
+        ctx.dims = (G, P, H)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        qkv, words, lse = ctx.saved_tensors
+        G, P, H = ctx.dims
+        d_out = d_out.contiguous()
+        d_qkv = torch.empty_like(qkv)
+        if G:
+            _check(load_library().team_attention_bwd(G, P, H, _ptr(qkv), _ptr(words), _ptr(lse), _ptr(d_out), _ptr(d_qkv), _stream()), "team_attention_bwd")
+        return d_qkv, None, None
+
+
+def team_attention(qkv, words, heads):
+    """masked multi-head attention inside every group of P consecutive rows (include/mappo_ops.h team_attention_fwd): qkv (G P, 384) fp32
+    = q | k | v, words (G, P) int64 hearing sets (comm_mask), heads in COMM_HEADS -> (G P, 128).  Under autograd the gradient of qkv is
+    team_attention_bwd's; without it (the rollout) no log-sum-exp is written."""
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        return _TeamAttention.apply(qkv, words, heads)
+    G, P, H = _team_attention_args(qkv, words, heads)
+    out = torch.empty((G * P, COMM_E), dtype=torch.float32, device=qkv.device)
+    if G:
+        _check(load_library().team_attention_fwd(G, P, H, _ptr(qkv), _ptr(words), _ptr(out), None, _stream()), "team_attention_fwd")
+    return out

@@ -526,6 +526,35 @@ int ppo_bc_loss_cat_fwd_bwd(int64_t n, int32_t A, const float *prob, float *grad
                             float *grad_values, double *sums, double *diag, void *workspace, void *stream);
 
 /*
+ * Team attention of the env_3d actor (algo.e3d_comm: attention; csrc/team_attention.hpp; specification: tests/team_attention_ref.py;
+ * DESIGN.md section 7m): one round of masked multi-head attention inside every group of P consecutive rows (the pursuers of one
+ * environment at one tick), 1 <= P <= 64, H in {1, 2, 4, 8} heads of D = 128 / H columns, fp32.
+ * team_comm_mask: words[g * words_stride + i] = the hearing set M_i of pursuer i of group g as a 64-bit word, bit j set iff j == i, or
+ *   live[g][i], live[g][j], pp_adj[g][i][j] and pp_adj[g][j][i] are all non-zero.  pp_adj [G][P][P] and live [G][P] are dense inside a
+ *   group; the strides are in elements between groups (words may be a time slice of an (N, T, P) buffer).  One launch.
+ * team_attention_fwd: qkv [G P][384] = q | k | v (dense rows, 16-byte aligned), head h in columns [h D, (h + 1) D) of each third:
+ *   s_ij = q_i^h . k_j^h / sqrt(D),  a_i. = softmax over j in M_i of s_ij (the maximum subtracted),  out [G P][128]: o_i^h = sum_j a_ij v_j^h,
+ *   lse [G][H][P] (NULL: not written) = log sum_{j in M_i} exp(s_ij).  Of words [G][P] the bits at or above P are ignored and bit i is
+ *   taken as set.  A query that hears only itself returns v_i exactly.
+ * team_attention_bwd: with a_ij = exp(s_ij - lse_i) recomputed (no [G][H][P][P] tensor exists anywhere), d_qkv [G P][384] = dQ | dK | dV:
+ *   dV_j = sum_i a_ij dO_i,  dS_ij = a_ij (dO_i . v_j - sum_l a_il dO_i . v_l),  dQ_i = sum_j dS_ij k_j / sqrt(D),  dK_j = sum_i dS_ij q_i / sqrt(D).
+ * A group never spans workgroups and every sum over i or j is taken by one lane in index order: no atomics, the same bits from run to
+ * run, and group g's result does not depend on G or on the other groups of the launch.  G = 0 succeeds and writes nothing; P, H, G out
+ * of range, a NULL or misaligned pointer or a stride below the dense one return MO_ERR_BAD_ARG before any launch or write.
+ * The _host entries run the same row functions on the host with no device (CPU tests, a sanitizer driver).
+ */
+int team_comm_mask(int64_t G, int32_t P, const float *pp_adj, int64_t adj_stride, const float *live, int64_t live_stride, int64_t *words,
+                   int64_t words_stride, void *stream);
+int team_attention_fwd(int64_t G, int32_t P, int32_t H, const float *qkv, const int64_t *words, float *out, float *lse, void *stream);
+int team_attention_bwd(int64_t G, int32_t P, int32_t H, const float *qkv, const int64_t *words, const float *lse, const float *d_out, float *d_qkv,
+                       void *stream);
+int team_comm_mask_host(int64_t G, int32_t P, const float *pp_adj, int64_t adj_stride, const float *live, int64_t live_stride, int64_t *words,
+                        int64_t words_stride);
+int team_attention_fwd_host(int64_t G, int32_t P, int32_t H, const float *qkv, const int64_t *words, float *out, float *lse);
+int team_attention_bwd_host(int64_t G, int32_t P, int32_t H, const float *qkv, const int64_t *words, const float *lse, const float *d_out,
+                            float *d_qkv);
+
+/*
  * Records one rollout tick into the replay buffer (MAPPO.run_episode's minibuffer.store_transition,
  * DHGN/mappo_parallel.py:783-805, for N environments at once): for every item, row n of the dense [N][row_bytes] source
  * goes to dst + n * dst_row_stride (slot [n, t] of an (N, T, ...) buffer tensor); i32_to_f32 converts int32 actions to
