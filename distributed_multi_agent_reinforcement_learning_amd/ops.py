@@ -1353,6 +1353,16 @@ def _diag_variant(L, name, plain_ws, diag_ws, diag, dev):
     return getattr(L, name + "_diag"), diag_ws(), (_ptr(diag),)
 
 
+def _own_rows(t):
+    """the rows (the first three dimensions) of a (d0, d1, d2, A) operand have storage of their own: no stride 0 over a dimension of
+    more than one entry.  The loss launches write g_prob / g_mu / g_ls through the operand's strides, one row per lane, so rows that
+    shared storage (an expand()ed view) would overwrite each other's gradient instead of adding to it."""
+    return all(s != 0 for n, s in zip(t.shape[:3], t.stride()[:3]) if n > 1)
+
+
+_SHARED_ROWS = "rows share storage (a stride of 0 over a row dimension): the gradient is written per row, pass a tensor with rows of its own"
+
+
 class _PPOLoss(torch.autograd.Function):
     """(actor_loss, critic_loss) of one mini-batch; the gradients are computed in the forward launch and scaled here."""
 
@@ -1428,7 +1438,8 @@ def ppo_loss_prob_ok(prob, values_now):
 def ppo_loss_prob(prob, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True, diag=None):
     """ppo_loss(Categorical(prob).log_prob(action), Categorical(prob).entropy(), ...) in one launch (DHGN/mappo_parallel.py:451-456,
     :692-706; csrc/mappo_ops.hip k_ppo_loss_prob).  prob (mb, T, P, A), values_now (mb, T, P): any strides over the first three
-    dimensions (the heads' outputs are time-major views).  diag: see ppo_loss."""
+    dimensions (the heads' outputs are time-major views), each row with storage of its own.  diag: see ppo_loss."""
+    assert _own_rows(prob), "prob: " + _SHARED_ROWS
     return _PPOLossProb.apply(prob, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip, diag)
 
 
@@ -1478,6 +1489,7 @@ def ppo_loss_gauss(mu, log_std, action, values_now, logp_old, adv, active, value
     w.r.t. mu, log_std and values_now (csrc/gauss_policy.hpp k_ppo_loss_gauss).  mu (mb, T, P, A) and values_now (mb, T, P): any strides
     over the first three dimensions (time-major views), mu's last dimension dense; action (mb, T, P, A), the rest (mb, T, P).
     diag: see ppo_loss."""
+    assert _own_rows(mu), "mu: " + _SHARED_ROWS
     return _PPOLossGauss.apply(mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
                                diag)
 
@@ -1541,6 +1553,8 @@ def ppo_loss_gauss_ex(mu, ls_raw, action, values_now, logp_old, adv, active, val
     sum log(1 - tanh(u)^2), which carries no gradient; squash "direction" is "clip" on the four latent dimensions (the map to the
     angles is the environment's: no Jacobian term).  Gradients flow to mu, ls_raw (0 where ls_raw is outside the bounds) and
     values_now.  diag: see ppo_loss."""
+    assert _own_rows(mu), "mu: " + _SHARED_ROWS
+    assert ls_raw.dim() == 1 or _own_rows(ls_raw), "ls_raw: " + _SHARED_ROWS
     return _PPOLossGaussEx.apply(mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef,
                                  use_value_clip, log_std_min, log_std_max, squash, diag)
 

@@ -42,9 +42,11 @@ def head_sample(feat, W, b, log_std, seed, counter, greedy=False, lo=-np.inf, hi
     return mu, ls_raw, z, u, env, logp
 
 
-def _ppo(lp, ent, vn, lo_old, ad, act, vo, vt, eps, ent_coef, use_value_clip):
-    """ppo_elem over all rows -> (actor_loss, critic_loss, g_lp, g_ent, g_v): tie rules of autograd for min / max / clamp"""
-    ratio = np.exp(lp - lo_old)
+def _ppo(lp, ent, vn, lo_old, ad, act, vo, vt, eps, ent_coef, use_value_clip, ratio=None):
+    """ppo_elem over all rows -> (actor_loss, critic_loss, g_lp, g_ent, g_v): tie rules of autograd for min / max / clamp.
+    ratio: None, or the rows' ratios as data in place of exp(lp - lo_old) (tests/ppo_edges_cases.py: the bits the device's expf gave,
+    so that a row built on a clip edge is on it in f64 too; g_lp is then the gradient that reaches lp through that ratio)"""
+    ratio = np.exp(lp - lo_old) if ratio is None else np.asarray(ratio, np.float64)
     s1, s2 = ratio * ad, np.clip(ratio, 1 - eps, 1 + eps) * ad
     la = -np.minimum(s1, s2) - ent_coef * ent
     asum = act.sum()
@@ -102,7 +104,13 @@ def torch_ppo_loss(mu, ls_raw, u, values_now, logp_old, adv, active, values_old,
     lp, ent = dist.log_prob(u).sum(-1), dist.entropy().sum(-1)
     if squash == "tanh":
         lp = lp - torch.log1p(-torch.tanh(u.detach()) ** 2).sum(-1)
-    ratios = torch.exp(lp - logp_old)
+    return torch_ppo_rows(torch.exp(lp - logp_old), ent, values_now, adv, active, values_old, v_target, eps, ent_coef, use_value_clip)
+
+
+def torch_ppo_rows(ratios, ent, values_now, adv, active, values_old, v_target, eps, ent_coef, use_value_clip=True):
+    """the op-by-op graph behind the policy: torch.min / torch.max / torch.clamp on the rows' ratios and entropies.  Its autograd
+    gradients are the specification of ppo_elem's tie and closed-range rules (tests/test_ppo_edges_cases_cpu.py)"""
+    import torch
     surr1 = ratios * adv
     surr2 = torch.clamp(ratios, 1 - eps, 1 + eps) * adv
     actor_loss = -torch.min(surr1, surr2) - ent_coef * ent

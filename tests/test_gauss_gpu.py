@@ -40,7 +40,9 @@ def _head_call(feat, W, b, ls, seed, counter, greedy=False):
 GRID_STRIDE_R = 1024 * 256 + 4099   # more rows than the launch's 1024 workgroups x 256 lanes cover in one pass
 
 
-@pytest.mark.parametrize("A,R", [(A, R) for A in (1, 2, 3, 4, 8, 16) for R in (1, 63, 64, 65, 16384)] + [(3, GRID_STRIDE_R), (16, GRID_STRIDE_R)])
+# every compiled k_gauss_head<AT>: the action counts the trainers use at every row count, the remaining instances at R in {1, 65}
+@pytest.mark.parametrize("A,R", [(A, R) for A in (1, 2, 3, 4, 8, 16) for R in (1, 63, 64, 65, 16384)] + [(3, GRID_STRIDE_R), (16, GRID_STRIDE_R)]
+                         + [(A, R) for A in range(1, 17) if A not in (1, 2, 3, 4, 8, 16) for R in (1, 65)])
 def test_gauss_head_sample_matches_reference(A, R):
     feat, W, b, ls = _head_inputs(R, A, 7 * A + R)
     seed, c0 = 0x5EED0000ABCD + A, (3 << 40) + 0xFFFFFF00   # a counter whose low word carries inside the launch

@@ -58,11 +58,14 @@ def _np(*ts):
 
 
 HEAD_CASES = [(A, R) for A in (1, 3, 8) for R in (1, 63, 64, 65, 16384)] + [(3, GRID_STRIDE_R), (8, GRID_STRIDE_R)]
+# every compiled k_gauss_head_ex<AT, STATE, MODE>: the remaining action counts at R in {1, 65}, 1 .. 8 in state mode (2 AT dot products
+# share a 16-lane row) and 1 .. 16 in param mode
+HEAD_CASES_ALL = ([(A, R, state) for A, R in HEAD_CASES for state in (False, True)]
+                  + [(A, R, state) for A in range(1, 17) if A not in (1, 3, 8) for R in (1, 65) for state in (False, True) if A <= 8 or not state])
 
 
 @pytest.mark.parametrize("squash", ["clip", "tanh"])
-@pytest.mark.parametrize("state", [False, True])
-@pytest.mark.parametrize("A,R", HEAD_CASES)
+@pytest.mark.parametrize("A,R,state", HEAD_CASES_ALL)
 def test_head_ex_matches_reference(A, R, state, squash):
     feat, W, b, W_ls, b_ls, ls = _head_inputs(R, A, 11 * A + R + state)
     src = (W_ls, b_ls) if state else ls

@@ -1,0 +1,233 @@
+"""The inputs and the reference of tests/test_ppo_loss_edges_gpu.py on their own, without a GPU (tests/ppo_edges_cases.py):
+on every row of the edge batch the f64 restatement gives torch autograd's gradients of the op-by-op graph (torch.min / torch.max /
+torch.clamp / Categorical / Normal), which pins torch's tie and closed-range rules as the specification independent of any kernel; the
+epsilons in use give the same clip edges in ppo_elem's fp32 arithmetic and in torch's clamp; the bulk generators meet their
+preconditions with no row dropped; the loss wrappers refuse a view whose rows share storage."""
+import numpy as np
+import pytest
+import torch
+
+from tests import gauss_sd_ref as gs
+from tests import ppo_edges_cases as pc
+
+F32 = np.float32
+T64 = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float64))
+
+
+def _host_ratios(d):
+    """a stand-in for the device's expf: any fp32 values will do, the batch takes its edge from them"""
+    return np.exp(pc.policy_clip_lrs(d).astype(np.float64)).astype(F32)
+
+
+def _rows_graph(c, ratios, ent, v, value_clip, dtype=torch.float64):
+    t = lambda k: torch.from_numpy(np.ascontiguousarray(c[k])).to(dtype)
+    eps = float(c["eps"])
+    return gs.torch_ppo_rows(ratios, ent, v, t("adv"), t("active"), t("v_old") if value_clip else None, t("v_tgt"), eps, float(c["ent_coef"]),
+                             value_clip)
+
+
+def _same(got, want, rtol=1e-12):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert got.shape == want.shape
+    assert np.all(np.abs(got - want) <= rtol * np.abs(want)), np.abs(got - want).max()       # (exact zeros stay exact zeros)
+
+
+# ---- the policy clip ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("value_clip", [True, False])
+@pytest.mark.parametrize("d", pc.POLICY_EDGES)
+def test_policy_clip_rows_follow_torch_autograd(d, value_clip):
+    c = pc.policy_clip_batch(d, _host_ratios(d))
+    side, factor = c["side"], c["factor"]
+    live = c["active"].reshape(-1) != 0
+    assert side[0] == 0 and {-1, 0, 1} <= set(side[live].tolist())               # on the edge, and both sides of it
+    for s in (-1, 0, 1):                                                          # each with adv > 0, adv < 0 and adv == 0, live and not
+        for sel in (c["adv"].reshape(-1) > 0, c["adv"].reshape(-1) < 0, (c["adv"].reshape(-1) == 0) & live, ~live):
+            assert ((side == s) & sel).any()
+    ref = pc.reference(c, value_clip)
+    r = T64(c["ratio"]).requires_grad_()
+    ent, v = T64(c["ent"]).requires_grad_(), T64(c["v_now"]).requires_grad_()
+    la, lc = _rows_graph(c, r, ent, v, value_clip)
+    (la + lc).backward()
+    _same(ref["la"], la.item())
+    _same(ref["lc"], lc.item())
+    _same(ref["grads"][0], (r.grad * r.detach()).numpy())                         # d ratio / d lp_now = ratio
+    _same(ref["grads"][1], ent.grad.numpy())
+    _same(ref["grads"][2], v.grad.numpy())
+    # the rule in words: the full gradient inside the range and on the edge itself (the clamp is closed, the tie of min() splits
+    # 1/2 + 1/2 and both halves reach the ratio); outside, the full one where min() picks the unclipped term and an exact 0 where it
+    # picks the clipped one; an exact 0 where adv == 0 and on inactive rows
+    act = c["active"].astype(np.float64).reshape(-1)
+    full = -(act / act.sum()) * c["adv"].astype(np.float64).reshape(-1) * c["ratio"].astype(np.float64).reshape(-1)
+    g_lp = ref["grads"][0].reshape(-1)
+    has = ~np.isnan(factor)
+    _same(g_lp[has], (full * np.nan_to_num(factor))[has], rtol=1e-15)
+    assert np.all(g_lp[~has] == 0) and np.all(g_lp[~live] == 0)
+    assert np.all(factor[(side == 0) & has] == 1) and set(factor[(side == 1) & has].tolist()) == {0.0, 1.0}
+    assert np.all(g_lp[(side == 1) & has & (factor == 0)] == 0) and np.all(g_lp[(side == 0) & has & live] != 0)
+
+
+def test_ratio_argument_is_optional():
+    c = pc.bulk_case("plain", (3, 17, 5))
+    lp, ent, vn, lo, ad, act, vo, vt = (c[k].astype(np.float64) for k in ("lp_now", "ent", "v_now", "lp_old", "adv", "active", "v_old", "v_tgt"))
+    a = gs._ppo(lp, ent, vn, lo, ad, act, vo, vt, 0.2, 0.01, True)
+    b = gs._ppo(lp, ent, vn, lo, ad, act, vo, vt, 0.2, 0.01, True, ratio=np.exp(lp - lo))
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+
+
+# ---- the value clip -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("value_clip", [True, False])
+def test_value_clip_rows_follow_torch_autograd(value_clip):
+    c = pc.value_clip_case("plain")
+    din32, pick32 = pc.value_decisions(c, np.float32)
+    din64, pick64 = pc.value_decisions(c, np.float64)
+    assert np.array_equal(din32, din64) and np.array_equal(pick32, pick64)        # fp32 and f64 sit on the same side of every decision
+    tags = np.array(c["tags"])
+    assert din64[tags == "on"].all() and din64[tags == "inside"].all() and not din64[tags == "outside"].any()
+    assert (pick64[tags == "on"] == 0).all() and (pick64[tags == "tie"] == 0).all() and not din64[tags == "tie"].any()
+    assert {-1.0, 1.0} <= set(pick64[tags == "outside"].tolist())                 # just outside: either branch of the maximum
+    assert (pick64[tags == "far_unclipped"] < 0).all() and (pick64[tags == "far_clipped"] > 0).all()
+    ref = pc.reference(c, value_clip)
+    lp, ent, v = (T64(c[k]).requires_grad_() for k in ("lp_now", "ent", "v_now"))
+    la, lc = _rows_graph(c, torch.exp(lp - T64(c["lp_old"])), ent, v, value_clip)
+    (la + lc).backward()
+    _same(ref["la"], la.item())
+    _same(ref["lc"], lc.item())
+    for got, want in zip(ref["grads"], (lp.grad, ent.grad, v.grad)):
+        _same(got, want.numpy())
+    act = c["active"].astype(np.float64).reshape(-1)
+    up, eo = act / act.sum(), (c["v_now"].astype(np.float64) - c["v_tgt"].astype(np.float64)).reshape(-1)
+    g_v = ref["grads"][2].reshape(-1)
+    live = act != 0
+    if value_clip:      # on the edge the clamp passes and the tie of max() splits: 2 eo; the tie outside has the clamp shut: eo
+        _same(g_v[tags == "on"], (up * 2 * eo)[tags == "on"], rtol=1e-15)
+        _same(g_v[tags == "tie"], (up * eo)[tags == "tie"], rtol=1e-15)
+        assert np.all(g_v[(tags == "far_clipped")] == 0) and np.all(g_v[(tags == "tie") & live] != 0)
+    else:
+        _same(g_v, up * 2 * eo, rtol=1e-15)
+    assert np.all(g_v[~live] == 0)
+
+
+# ---- the categorical clamp --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ent_coef", [0.0, pc.CAT_ENT])
+@pytest.mark.parametrize("A", [2, 16])
+def test_categorical_rows_follow_torch_autograd_in_fp32(A, ent_coef):
+    """torch's clamp constant is finfo(dtype).eps, so the specification of these rows is the fp32 graph, on the CPU.  Its gradient
+    through prob / prob.sum() is a difference of fp32 numbers: an element is held to 1e-5 of the largest element of its row, which is
+    of the size of the terms the difference is formed from (the restatement is f64 and has no such limit)."""
+    c = pc.categorical_case(A, ent_coef)
+    ref = pc.reference(c, True)
+    f = lambda k: torch.from_numpy(np.ascontiguousarray(c[k]))
+    prob, v = f("prob").requires_grad_(), f("v_now").requires_grad_()
+    dist = torch.distributions.Categorical(prob)
+    ratios = torch.exp(dist.log_prob(f("action")) - f("lp_old"))
+    la, lc = _rows_graph(c, ratios, dist.entropy(), v, True, torch.float32)
+    (la + lc).backward()
+    assert abs(la.item() - ref["la"]) <= 1e-5 * abs(ref["la"]) and abs(lc.item() - ref["lc"]) <= 1e-5 * abs(ref["lc"])
+    want, got = ref["grads"][0], prob.grad.double().numpy()
+    assert np.all(np.abs(got - want) <= 1e-5 * np.abs(want).max(-1, keepdims=True) + 1e-12), np.abs(got - want).max()
+    _same(ref["grads"][1], v.grad.double().numpy(), rtol=1e-5)
+    on = np.array([t[0] == "on" for t in c["tags"]])
+    live = c["active"].reshape(-1) != 0
+    rows = want.reshape(-1, A)
+    assert np.all(rows[~live] == 0) and np.all(rows[on & live] != 0)      # on the closed edges the gradient passes (and - sum_j gp_j p_j reaches every entry)
+    if ent_coef == 0.0:                                                                  # beyond them it is blocked: exact zeros
+        assert np.all(rows[~on] == 0) and np.all(got.reshape(-1, A)[~on] == 0)
+    else:
+        assert np.all((rows[~on & live] != 0).any(-1))                                   # (the entropy's own p log p term is not clamped)
+
+
+# ---- the log-std bounds -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("squash", ["clip", "tanh"])
+@pytest.mark.parametrize("state", [False, True], ids=["param", "state"])
+def test_log_std_rows_follow_torch_autograd(state, squash):
+    c = pc.log_std_case(state, squash)
+    raw = c["ls"]
+    assert np.array_equal(np.unique(raw), np.unique(pc.LS_VALUES)) and len(np.unique(raw)) == 6
+    assert np.array_equal((raw >= F32(pc.LS_LO)) & (raw <= F32(pc.LS_HI)), c["passes"].reshape(raw.shape))
+    assert (raw == F32(pc.LS_LO)).any() and (raw == F32(pc.LS_HI)).any() and (raw < F32(pc.LS_LO)).any() and (raw > F32(pc.LS_HI)).any()
+    ref = pc.reference(c, True)
+    mu, ls, v = (T64(c[k]).requires_grad_() for k in ("mu", "ls", "v_now"))
+    t = lambda k: T64(c[k])
+    la, lc = gs.torch_ppo_loss(mu, ls, t("action"), v, t("lp_old"), t("adv"), t("active"), t("v_old"), t("v_tgt"), c["eps"], c["ent_coef"], True,
+                               c["lo"], c["hi"], squash)
+    (la + lc).backward()
+    _same(ref["la"], la.item(), rtol=1e-11)
+    _same(ref["lc"], lc.item())
+    for got, want in zip(ref["grads"], (mu.grad, ls.grad, v.grad)):
+        got, want = np.asarray(got), want.numpy()
+        assert np.all(np.abs(got - want) <= 1e-11 * np.abs(want) + 1e-18), np.abs(got - want).max()
+    g_ls = ref["grads"][1]
+    passes = c["passes"].reshape(g_ls.shape)
+    live = np.broadcast_to(c["active"][..., None] != 0, c["mu"].shape) if state else np.ones(6, bool)
+    assert np.all(g_ls[~passes] == 0) and np.all(g_ls[passes & live] != 0)       # closed bounds: on lo and hi the gradient flows
+    cond = pc.log_std_condition(c)
+    print(f"state={state} {squash}: condition of g_ls at most {cond.max():.1f}")
+    assert cond.max() < 50                                                        # fp32's 6e-8 times this stays well inside 1e-5
+
+
+# ---- the epsilons ---------------------------------------------------------------------------------------------------------------------------------
+def _epsilons():
+    from distributed_multi_agent_reinforcement_learning_amd.config import baseline_config, load_config
+    eps = {float(load_config().algo.epsilon)}
+    eps |= {float(baseline_config(n).algo.epsilon) for n in ("cfg1", "cfg2", "cfg3", "cfg4", "cfg5", "cfg4_n2n")}
+    eps |= {0.05, 0.1, 0.2, 0.25, 0.3, pc.BULK_EPS, pc.V_EPS, pc.CAT_EPS, pc.LS_EPS}
+    eps |= {pc.policy_clip_batch(d, _host_ratios(d))["eps"] for d in pc.POLICY_EDGES}
+    return sorted(eps)
+
+
+def test_kernel_and_torch_share_their_clip_edges():
+    """ppo_elem forms 1.f - eps and 1.f + eps from the fp32 eps; torch's clamp of an fp32 tensor rounds the double 1 - eps to fp32"""
+    for e in _epsilons():
+        e32 = F32(e)
+        assert F32(1) - e32 == F32(1 - e) and F32(1) + e32 == F32(1 + e), e
+        lo, hi = torch.tensor(1 - e, dtype=torch.float32), torch.tensor(1 + e, dtype=torch.float32)
+        assert float(lo) == float(F32(1) - e32) and float(hi) == float(F32(1) + e32), e
+
+
+# ---- the bulk cases -------------------------------------------------------------------------------------------------------------------------------
+def test_bulk_cases_meet_their_preconditions_with_no_row_dropped():
+    keys = pc.bulk_keys()
+    assert len(keys) == len(set(keys))
+    nudged = 0
+    for key in keys:
+        c = pc.bulk_case(*key)
+        pc.assert_preconditions(c)
+        assert c["passes"] < 3, key                       # the third pass found nothing left to nudge
+        nudged += c["passes"] > 0
+        n = int(np.prod(key[1]))
+        assert all(c[k].shape == tuple(key[1]) for k in ("adv", "active", "v_now", "v_old", "v_tgt", "lp_old")) and c["active"].size == n
+        dead = c["active"] == 0
+        assert c["active"].reshape(-1)[0] == 1 and all(np.isfinite(c[k]).all() for k in ("adv", "v_now", "v_old", "v_tgt", "lp_old"))
+        if n > 200:
+            assert 0.2 < dead.mean() < 0.5
+            dv = np.abs(c["v_now"].astype(np.float64) - c["v_old"])
+            assert (dv < c["eps"]).any() and (dv > c["eps"]).any()            # both sides of the value clip
+    assert nudged > 0                                      # the big cases do have rows near an edge: the nudges are exercised
+    sharp = pc.bulk_case("prob", pc.VIEW_SHAPES[0], 9, False, "clip", pc.SHARP)
+    p = sharp["prob"] / sharp["prob"].sum(-1, keepdims=True)
+    assert (p < F32(2.0 ** -23)).any() and (p > F32(1 - 2.0 ** -23)).any()    # the clamp is active at both ends
+
+
+# ---- rows that share storage ------------------------------------------------------------------------------------------------------------------------
+def test_loss_wrappers_refuse_rows_that_share_storage():
+    """the launches write the policy's gradient through the operand's strides, one row per lane: a stride of 0 over a row dimension
+    would make rows overwrite each other.  Nothing in the package passes such a view; the wrappers refuse it before anything runs."""
+    from distributed_multi_agent_reinforcement_learning_amd import ops
+    d0, d1, d2, A = 2, 3, 4, 5
+    z = torch.zeros(d0, d1, d2)
+    tail = (z, z, z, z, z, z, 0.2, 0.01)
+    shared = torch.full((d0, 1, d2, A), 0.2).expand(d0, d1, d2, A)
+    own = torch.full((d0, d1, d2, A), 0.2)
+    with pytest.raises(AssertionError, match="rows share storage"):
+        ops.ppo_loss_prob(shared, z, *tail)
+    with pytest.raises(AssertionError, match="rows share storage"):
+        ops.ppo_loss_gauss(shared, torch.zeros(A), own, *tail)
+    with pytest.raises(AssertionError, match="rows share storage"):
+        ops.ppo_loss_gauss_ex(shared, torch.zeros(A), own, *tail)
+    with pytest.raises(AssertionError, match="ls_raw: rows share storage"):
+        ops.ppo_loss_gauss_ex(own, shared, own, *tail)
+    one = torch.full((1, 1, d2, A), 0.2).expand(1, 1, d2, A)        # (a stride over a dimension of one entry is never used)
+    assert ops._own_rows(own) and ops._own_rows(one) and ops._own_rows(own.permute(1, 0, 2, 3)) and not ops._own_rows(shared)
+    with pytest.raises(RuntimeError, match="GPU only"):             # a tensor with rows of its own gets as far as the device check
+        ops.ppo_loss_prob(own, z, *tail)
