@@ -2,7 +2,8 @@
 // gauss_head_sample / ppo_loss_gauss_fwd_bwd, and with a state-dependent log-std / tanh squashing gauss_head_sample_ex /
 // ppo_loss_gauss_ex_fwd_bwd).  Included once, from csrc/mappo_ops.hip after its anonymous namespace: it reuses that
 // file's Philox4x32-10 (philox4x32_10), the 16-lane row sum (row16_sum), the wave-local LDS fence (wave_fence), the PPO row
-// (ppo_elem, PpoView, PPO_BLOCKS) and the head's feature width (HEAD_H).
+// (ppo_elem, PPO_BLOCKS), the steps the strided loss kernels share (PpoView / ppo_row / ppo_offset, ppo_wave_block_sums, ppo_wave_sum, the
+// diagnostics' ppo_diag_block_sums / ppo_diag_finish_wave) and the head's feature width (HEAD_H).
 #pragma once
 #include "direction_action.hpp"
 
@@ -136,8 +137,8 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss(long n, int A, const flo
     for (int k = 0; k < GAUSS_PART; k++) acc[k] = 0.0;
     double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long i2 = i % mv.d2, i01 = i / mv.d2, i1 = i01 % mv.d1, i0 = i01 / mv.d1;
-        const long mo = i0 * mv.s0 + i1 * mv.s1 + i2 * mv.s2;
+        const PpoRow row = ppo_row(i, mv);
+        const long mo = ppo_offset(row, mv);
         float d[GAUSS_MAX_A];
         float lp = 0.f;
 #pragma unroll
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss(long n, int A, const flo
             }
         }
         const float act = active[i];
-        const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        const float vn = v_now[ppo_offset(row, vv)];
         float d_lr = 0.f, d_vt = 0.f;
         if (DIAG) { d_lr = lp - lp_old[i]; d_vt = v_tgt[i]; }
         const PpoElem e = ppo_elem(lp, ent, lp_old[i], adv[i], act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, ent_coef, value_clip);
@@ -165,29 +166,14 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss(long n, int A, const flo
             }
         if (DIAG && act != 0.f) ppodiag::row(dg, d_lr, expf(d_lr), ent, vn, d_vt, eps);
     }
-    __shared__ double red[GAUSS_PART][4];
-#pragma unroll
-    for (int k = 0; k < GAUSS_PART; k++)
-        if (k < 2 + A) {   // (A is uniform)
-            double s = acc[k];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < 2 + A) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * GAUSS_PART + k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    }
+    ppo_wave_block_sums(acc, 2 + A, partials + (size_t)blockIdx.x * GAUSS_PART);   // (A is uniform)
     if (DIAG) ppo_diag_block_sums(dg, partials + (size_t)PPO_BLOCKS * GAUSS_PART);
 }
 
-// one wave per sum (2 + A workgroups): lane l adds the partials of blocks l, l + 64, .. in order, then a fixed butterfly -- the
-// same bits every run, without one lane walking all PPO_BLOCKS partials serially
+// one wave per sum (2 + A workgroups, ppo_wave_sum)
 __device__ __forceinline__ void ppo_gauss_finish_wave(int k, int nblk, const double *partials, const float *active_sum, float *losses,
                                                       float *grad_log_std) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += partials[(size_t)b * GAUSS_PART + k];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const double s = ppo_wave_sum(nblk, partials, GAUSS_PART, k);
     if (threadIdx.x == 0) {
         if (k < 2) losses[k] = (float)s / active_sum[0];
         else grad_log_std[k - 2] = (float)s;
@@ -220,6 +206,17 @@ __device__ __forceinline__ float tanh_log_jac(float u) {
     const float x = -2.f * u;
     return 2.f * (GAUSS_LN2 - u - (fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)))));
 }
+
+// The log-std row of the update, shared by k_ppo_loss_gauss_ex, k_bc_loss_gauss and k_ppo_bc_loss_gauss: ls = clamp(ls_raw, lo, hi), and
+// torch.clamp's backward -- the gradient w.r.t. ls_raw passes on the closed range [lo, hi] and is 0 outside
+__device__ __forceinline__ float gauss_ls_clamp(float ls_raw, float lo, float hi) { return fminf(fmaxf(ls_raw, lo), hi); }
+__device__ __forceinline__ bool gauss_ls_pass(float ls_raw, float lo, float hi) { return ls_raw >= lo && ls_raw <= hi; }
+// 1 / sigma^2 with sigma = expf(ls), and a dimension's term of the entropy (the PPO launches; k_bc_loss_gauss has its own expf(-2 ls))
+__device__ __forceinline__ float gauss_inv_var(float ls) {
+    const float s = expf(ls);
+    return 1.f / (s * s);
+}
+__device__ __forceinline__ float gauss_ent_term(float ls) { return 0.5f + HALF_LN_2PI + ls; }
 
 // k_gauss_head with the log-std head folded into the same pass: in state mode a lane holds 2 AT x 8 weights (W's rows, then W_ls's),
 // the 2 AT dot products of a row go through row16_sum and LDS like mu's, hence AT <= 8 (2 AT <= 16 lanes of a row).  Same Philox
@@ -354,11 +351,10 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, con
 #pragma unroll
         for (int k = 0; k < NA; k++) {
             const float lr = k < A ? ls_raw[k] : 0.f;
-            ls[k] = fminf(fmaxf(lr, ls_lo), ls_hi);
-            pass[k] = lr >= ls_lo && lr <= ls_hi;
-            const float s = expf(ls[k]);
-            iv[k] = 1.f / (s * s);
-            if (k < A) ent += 0.5f + HALF_LN_2PI + ls[k];
+            ls[k] = gauss_ls_clamp(lr, ls_lo, ls_hi);
+            pass[k] = gauss_ls_pass(lr, ls_lo, ls_hi);
+            iv[k] = gauss_inv_var(ls[k]);
+            if (k < A) ent += gauss_ent_term(ls[k]);
         }
     }
     constexpr int NSUM = STATE ? 2 : 2 + NA;
@@ -367,20 +363,19 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, con
     for (int k = 0; k < NSUM; k++) acc[k] = 0.0;
     double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long i2 = i % mv.d2, i01 = i / mv.d2, i1 = i01 % mv.d1, i0 = i01 / mv.d1;
-        const long mo = i0 * mv.s0 + i1 * mv.s1 + i2 * mv.s2;
-        const long lo = STATE ? i0 * lv.s0 + i1 * lv.s1 + i2 * lv.s2 : 0;
+        const PpoRow row = ppo_row(i, mv);
+        const long mo = ppo_offset(row, mv);
+        const long lo = STATE ? ppo_offset(row, lv) : 0;
         if (STATE) {
             ent = 0.f;
 #pragma unroll
             for (int k = 0; k < NA; k++)
                 if (k < A) {
                     const float lr = ls_raw[lo + k];
-                    ls[k] = fminf(fmaxf(lr, ls_lo), ls_hi);
-                    pass[k] = lr >= ls_lo && lr <= ls_hi;
-                    const float s = expf(ls[k]);
-                    iv[k] = 1.f / (s * s);
-                    ent += 0.5f + HALF_LN_2PI + ls[k];
+                    ls[k] = gauss_ls_clamp(lr, ls_lo, ls_hi);
+                    pass[k] = gauss_ls_pass(lr, ls_lo, ls_hi);
+                    iv[k] = gauss_inv_var(ls[k]);
+                    ent += gauss_ent_term(ls[k]);
                 }
         }
         float d[NA];
@@ -397,7 +392,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, con
         }
         if (TANH) lp -= jac;
         const float act = active[i];
-        const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        const float vn = v_now[ppo_offset(row, vv)];
         float d_lr = 0.f, d_vt = 0.f;
         if (DIAG) { d_lr = lp - lp_old[i]; d_vt = v_tgt[i]; }
         const PpoElem e = ppo_elem(lp, ent, lp_old[i], adv[i], act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, ent_coef, value_clip);
@@ -415,20 +410,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_gauss_ex(long n, int A_rt, con
             }
         if (DIAG && act != 0.f) ppodiag::row(dg, d_lr, expf(d_lr), ent, vn, d_vt, eps);
     }
-    const int nsum = STATE ? 2 : 2 + A;
-    __shared__ double red[NSUM][4];
-#pragma unroll
-    for (int k = 0; k < NSUM; k++)
-        if (k < nsum) {   // (A is uniform)
-            double s = acc[k];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < nsum) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * GAUSS_PART + k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    }
+    ppo_wave_block_sums(acc, STATE ? 2 : 2 + A, partials + (size_t)blockIdx.x * GAUSS_PART);   // (A is uniform)
     if (DIAG) ppo_diag_block_sums(dg, partials + (size_t)PPO_BLOCKS * GAUSS_PART);
 }
 

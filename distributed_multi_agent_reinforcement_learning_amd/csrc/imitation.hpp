@@ -1,7 +1,9 @@
 // imitation.hpp -- the imitation warm start of the env_3d / env_n2n trainers (algo.bc_iterations; imitation.py; DESIGN.md section 7f;
 // C ABI: include/mappo_ops.h bc_loss_gauss_fwd_bwd / bc_loss_cat_fwd_bwd / e3d_bc_select / n2n_bc_select; specification:
-// tests/imitation_ref.py).  Included once, from csrc/mappo_ops.hip after gauss_policy.hpp: it reuses that file's PPO row (ppo_elem, PpoView,
-// PPO_BLOCKS, PPO_MAX_A, ppo_block_sums, ppo_loss_finish_sums) and gauss_policy.hpp's GAUSS_MAX_A and bounds check.
+// tests/imitation_ref.py).  Included once, from csrc/mappo_ops.hip after gauss_policy.hpp: it reuses that file's PPO row (ppo_elem, PPO_BLOCKS,
+// ppo_block_sums, ppo_loss_finish_sums), the steps the strided loss kernels share (PpoView / ppo_row / ppo_offset, ppo_wave_block_sums,
+// ppo_wave_sum, the categorical row: PPO_MAX_A, P_EPS, cat_clamp / cat_pass) and gauss_policy.hpp's GAUSS_MAX_A,
+// log-std clamp and pass rule (gauss_ls_clamp, gauss_ls_pass) and bounds check.
 #pragma once
 
 namespace {
@@ -32,8 +34,8 @@ __global__ __launch_bounds__(256) void k_bc_loss_gauss(long n, int A, const floa
 #pragma unroll
         for (int k = 0; k < GAUSS_MAX_A; k++) {
             const float lr = k < A ? ls_raw[k] : 0.f;
-            ls[k] = fminf(fmaxf(lr, ls_lo), ls_hi);
-            pass[k] = lr >= ls_lo && lr <= ls_hi;
+            ls[k] = gauss_ls_clamp(lr, ls_lo, ls_hi);
+            pass[k] = gauss_ls_pass(lr, ls_lo, ls_hi);
             iv[k] = expf(-2.f * ls[k]);
         }
     }
@@ -42,9 +44,9 @@ __global__ __launch_bounds__(256) void k_bc_loss_gauss(long n, int A, const floa
 #pragma unroll
     for (int k = 0; k < NSUM; k++) acc[k] = 0.0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long i2 = i % mv.d2, i01 = i / mv.d2, i1 = i01 % mv.d1, i0 = i01 / mv.d1;
-        const long mo = i0 * mv.s0 + i1 * mv.s1 + i2 * mv.s2;
-        const long lo = STATE ? i0 * lv.s0 + i1 * lv.s1 + i2 * lv.s2 : 0;
+        const PpoRow row = ppo_row(i, mv);
+        const long mo = ppo_offset(row, mv);
+        const long lo = STATE ? ppo_offset(row, lv) : 0;
         const float act = active[i];
         const float up = act * inv;
         float la = 0.f, sq = 0.f;
@@ -56,8 +58,8 @@ __global__ __launch_bounds__(256) void k_bc_loss_gauss(long n, int A, const floa
                 bool pk;
                 if (STATE) {
                     const float lr = ls_raw[lo + k];
-                    lsk = fminf(fmaxf(lr, ls_lo), ls_hi);
-                    pk = lr >= ls_lo && lr <= ls_hi;
+                    lsk = gauss_ls_clamp(lr, ls_lo, ls_hi);
+                    pk = gauss_ls_pass(lr, ls_lo, ls_hi);
                     ivk = expf(-2.f * lsk);
                 } else {
                     lsk = ls[k]; ivk = iv[k]; pk = pass[k];
@@ -73,38 +75,23 @@ __global__ __launch_bounds__(256) void k_bc_loss_gauss(long n, int A, const floa
                 if (STATE) g_ls[lo + k] = gl;
                 else acc[3 + k] += (double)gl;
             }
-        const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        const float vn = v_now[ppo_offset(row, vv)];
         const PpoElem e = ppo_elem(0.f, 0.f, 0.f, 0.f, act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, 0.f, value_clip);
         acc[0] += (double)(la * act);
         acc[1] += (double)(e.lc * act);
         acc[2] += (double)((ANGLE ? diract::angle(m3, t3) : sq) * act);
         g_v[i] = e.g_v;
     }
-    const int nsum = STATE ? 3 : 3 + A;
-    __shared__ double red[NSUM][4];
-#pragma unroll
-    for (int k = 0; k < NSUM; k++)
-        if (k < nsum) {   // (A is uniform)
-            double s = acc[k];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < nsum) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * BC_GAUSS_PART + k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    }
+    ppo_wave_block_sums(acc, STATE ? 3 : 3 + A, partials + (size_t)blockIdx.x * BC_GAUSS_PART);   // (A is uniform)
 }
 
-// one wave per sum: lane l adds the partials of blocks l, l + 64, .. in order, then a fixed butterfly (as k_ppo_gauss_finish).  Sums 0
+// one wave per sum (ppo_wave_sum, as k_ppo_gauss_finish).  Sums 0
 // and 1 become the two losses, sum 2 and the row count are ADDED to sums[0] / sums[1] (the caller zeroes them once per update; the
 // launches of a stream run in order), the sums behind them are the log_std gradient of param mode.
 __global__ __launch_bounds__(64) void k_bc_gauss_finish(int nblk, const double *partials, const float *active_sum, float *losses, float *grad_log_std,
                                                         double *sums) {
     const int k = blockIdx.x;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += partials[(size_t)b * BC_GAUSS_PART + k];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const double s = ppo_wave_sum(nblk, partials, BC_GAUSS_PART, k);
     if (threadIdx.x == 0) {
         if (k < 2) losses[k] = (float)s / active_sum[0];
         else if (k == 2) {
@@ -124,11 +111,11 @@ __global__ __launch_bounds__(256) void k_bc_loss_cat(long n, int A, const float 
                                                      const float *v_tgt, const float *active_sum, float eps, int value_clip,
                                                      float *__restrict__ g_prob, float *__restrict__ g_v, double *partials) {
     const float inv = 1.f / active_sum[0];
-    constexpr float P_EPS = 1.1920928955078125e-07f;      // torch.finfo(torch.float32).eps (clamp_probs)
-    double sa = 0.0, sc = 0.0, hit = 0.0;
+    double sa = 0.0, sc = 0.0;
+    double hit[1] = {0.0};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long i2 = i % pv.d2, i01 = i / pv.d2, i1 = i01 % pv.d1, i0 = i01 / pv.d1;
-        const long po = i0 * pv.s0 + i1 * pv.s1 + i2 * pv.s2;
+        const PpoRow row = ppo_row(i, pv);
+        const long po = ppo_offset(row, pv);
         float p[PPO_MAX_A];
         float s = 0.f;
 #pragma unroll
@@ -144,22 +131,22 @@ __global__ __launch_bounds__(256) void k_bc_loss_cat(long n, int A, const float 
         for (int k = 0; k < PPO_MAX_A; k++)
             if (k < A) {
                 p[k] = p[k] / s;                                              // Categorical.probs
-                if (k == a_idx) lp = logf(fminf(fmaxf(p[k], P_EPS), 1.f - P_EPS));   // probs_to_logits, gathered
+                if (k == a_idx) lp = logf(cat_clamp(p[k]));                   // probs_to_logits, gathered
             }
         const float act = active[i];
         const float up = act * inv;
-        const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        const float vn = v_now[ppo_offset(row, vv)];
         const PpoElem e = ppo_elem(0.f, 0.f, 0.f, 0.f, act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, 0.f, value_clip);
         sa += (double)(-lp * act);
         sc += (double)(e.lc * act);
-        if (act != 0.f && arg == a_idx) hit += 1.0;
+        if (act != 0.f && arg == a_idx) hit[0] += 1.0;
         g_v[i] = e.g_v;
         float gsel = 0.f, dot = 0.f;                                          // d / d probs[label] (the other entries are 0) and its dot with probs
 #pragma unroll
         for (int k = 0; k < PPO_MAX_A; k++)
             if (k < A && k == a_idx) {
-                const float c = fminf(fmaxf(p[k], P_EPS), 1.f - P_EPS);
-                const bool pass = p[k] >= P_EPS && p[k] <= 1.f - P_EPS;
+                const float c = cat_clamp(p[k]);
+                const bool pass = cat_pass(p[k]);
                 gsel = pass ? -up / c : 0.f;
                 dot = gsel * p[k];
             }
@@ -168,19 +155,13 @@ __global__ __launch_bounds__(256) void k_bc_loss_cat(long n, int A, const float 
             if (k < A) g_prob[po + k] = ((k == a_idx ? gsel : 0.f) - dot) / s;   // through probs = prob / prob.sum(-1)
     }
     ppo_block_sums(sa, sc, partials);
-    __shared__ double hred[4];
-    for (int off = 32; off > 0; off >>= 1) hit += __shfl_xor(hit, off);
-    if ((threadIdx.x & 63) == 0) hred[threadIdx.x >> 6] = hit;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[2 * PPO_BLOCKS + blockIdx.x] = (hred[0] + hred[1]) + (hred[2] + hred[3]);
+    ppo_wave_block_sums(hit, 1, partials + 2 * PPO_BLOCKS + blockIdx.x);
 }
 
 // workgroup 0: k_ppo_loss_finish; workgroup 1 (launched with sums only): the hit count and the row count, ADDED to sums[0] / sums[1]
 __global__ __launch_bounds__(64) void k_bc_cat_finish(int nblk, const double *partials, const float *active_sum, float *losses, double *sums) {
     if (blockIdx.x == 0) { ppo_loss_finish_sums(nblk, partials, active_sum, losses); return; }
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += partials[2 * PPO_BLOCKS + b];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const double s = ppo_wave_sum(nblk, partials + 2 * PPO_BLOCKS, 1, 0);
     if (threadIdx.x == 0) { sums[0] += s; sums[1] += (double)active_sum[0]; }
 }
 

@@ -1,7 +1,10 @@
 // kickstart.hpp -- teacher-regularised PPO of the env_3d / env_n2n trainers (algo.bc_coef; kickstart.py; C ABI:
 // include/mappo_ops.h ppo_bc_loss_gauss_fwd_bwd / ppo_bc_loss_cat_fwd_bwd; specification: tests/kickstart_ref.py).  Included once, from
-// csrc/mappo_ops.hip after imitation.hpp: it reuses the PPO row (ppo_elem, PpoView, PPO_BLOCKS, PPO_MAX_A, ppo_block_sums, ppodiag,
-// ppo_diag_block_sums, ppo_diag_finish_wave), gauss_policy.hpp's GAUSS_MAX_A, tanh_log_jac and bounds check, and imitation.hpp's metric codes.
+// csrc/mappo_ops.hip after imitation.hpp: it reuses the PPO row (ppo_elem, PPO_BLOCKS, ppo_block_sums), the steps the strided loss
+// kernels share (PpoView / ppo_row / ppo_offset, ppo_wave_block_sums, ppo_wave_sum, the categorical row: PPO_MAX_A, P_EPS,
+// cat_clamp / cat_pass), the diagnostics (ppodiag, ppo_diag_block_sums, ppo_diag_finish_wave), gauss_policy.hpp's
+// GAUSS_MAX_A, log-std row (gauss_ls_clamp / gauss_ls_pass, gauss_inv_var / gauss_ent_term), tanh_log_jac and bounds check, and
+// imitation.hpp's metric codes.
 #pragma once
 
 namespace {
@@ -35,11 +38,10 @@ __global__ __launch_bounds__(256) void k_ppo_bc_loss_gauss(long n, int A_rt, con
 #pragma unroll
         for (int k = 0; k < NA; k++) {
             const float lr = k < A ? ls_raw[k] : 0.f;
-            ls[k] = fminf(fmaxf(lr, ls_lo), ls_hi);
-            pass[k] = lr >= ls_lo && lr <= ls_hi;
-            const float s = expf(ls[k]);
-            iv[k] = 1.f / (s * s);
-            if (k < A) ent += 0.5f + HALF_LN_2PI + ls[k];
+            ls[k] = gauss_ls_clamp(lr, ls_lo, ls_hi);
+            pass[k] = gauss_ls_pass(lr, ls_lo, ls_hi);
+            iv[k] = gauss_inv_var(ls[k]);
+            if (k < A) ent += gauss_ent_term(ls[k]);
         }
     }
     constexpr int NSUM = STATE ? KS_GAUSS_HEAD : KS_GAUSS_HEAD + NA;
@@ -48,20 +50,19 @@ __global__ __launch_bounds__(256) void k_ppo_bc_loss_gauss(long n, int A_rt, con
     for (int k = 0; k < NSUM; k++) acc[k] = 0.0;
     double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long i2 = i % mv.d2, i01 = i / mv.d2, i1 = i01 % mv.d1, i0 = i01 / mv.d1;
-        const long mo = i0 * mv.s0 + i1 * mv.s1 + i2 * mv.s2;
-        const long lo = STATE ? i0 * lv.s0 + i1 * lv.s1 + i2 * lv.s2 : 0;
+        const PpoRow row = ppo_row(i, mv);
+        const long mo = ppo_offset(row, mv);
+        const long lo = STATE ? ppo_offset(row, lv) : 0;
         if (STATE) {
             ent = 0.f;
 #pragma unroll
             for (int k = 0; k < NA; k++)
                 if (k < A) {
                     const float lr = ls_raw[lo + k];
-                    ls[k] = fminf(fmaxf(lr, ls_lo), ls_hi);
-                    pass[k] = lr >= ls_lo && lr <= ls_hi;
-                    const float s = expf(ls[k]);
-                    iv[k] = 1.f / (s * s);
-                    ent += 0.5f + HALF_LN_2PI + ls[k];
+                    ls[k] = gauss_ls_clamp(lr, ls_lo, ls_hi);
+                    pass[k] = gauss_ls_pass(lr, ls_lo, ls_hi);
+                    iv[k] = gauss_inv_var(ls[k]);
+                    ent += gauss_ent_term(ls[k]);
                 }
         }
         float d[NA], ds[NA];                                       // action - mu, target - mu
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(256) void k_ppo_bc_loss_gauss(long n, int A_rt, con
         if (TANH) lp -= jac;
         const float act = active[i];
         const float up = act * inv, upc = up * coef;
-        const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        const float vn = v_now[ppo_offset(row, vv)];
         float d_lr = 0.f, d_vt = 0.f;
         if (DIAG) { d_lr = lp - lp_old[i]; d_vt = v_tgt[i]; }
         const PpoElem e = ppo_elem(lp, ent, lp_old[i], adv[i], act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, ent_coef, value_clip);
@@ -109,29 +110,8 @@ __global__ __launch_bounds__(256) void k_ppo_bc_loss_gauss(long n, int A_rt, con
             }
         if (DIAG && act != 0.f) ppodiag::row(dg, d_lr, expf(d_lr), ent, vn, d_vt, eps);
     }
-    const int nsum = STATE ? KS_GAUSS_HEAD : KS_GAUSS_HEAD + A;
-    __shared__ double red[NSUM][4];
-#pragma unroll
-    for (int k = 0; k < NSUM; k++)
-        if (k < nsum) {   // (A is uniform)
-            double s = acc[k];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-            if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < nsum) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * KS_GAUSS_PART + k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    }
+    ppo_wave_block_sums(acc, STATE ? KS_GAUSS_HEAD : KS_GAUSS_HEAD + A, partials + (size_t)blockIdx.x * KS_GAUSS_PART);   // (A is uniform)
     if (DIAG) ppo_diag_block_sums(dg, partials + (size_t)PPO_BLOCKS * KS_GAUSS_PART);
-}
-
-// sum k of the block partials by one wave: lane l adds blocks l, l + 64, .. in order, then a fixed butterfly (as k_ppo_gauss_finish)
-__device__ __forceinline__ double ks_wave_sum(int nblk, const double *partials, int stride, int k) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += partials[(size_t)b * stride + k];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
 }
 
 // Workgroup 0: losses[0] = mean PPO actor loss + coef * mean imitation loss, and the imitation sum ADDED to sums[2]; 1: losses[1] as
@@ -142,14 +122,14 @@ __global__ __launch_bounds__(64) void k_ppo_bc_gauss_finish(int nsum, int nblk, 
     const int k = blockIdx.x;
     if (k >= nsum) { ppo_diag_finish_wave(k - nsum, nblk, partials + (size_t)PPO_BLOCKS * KS_GAUSS_PART, diag); return; }
     if (k == 0) {
-        const double sp = ks_wave_sum(nblk, partials, KS_GAUSS_PART, 0), sb = ks_wave_sum(nblk, partials, KS_GAUSS_PART, 2);
+        const double sp = ppo_wave_sum(nblk, partials, KS_GAUSS_PART, 0), sb = ppo_wave_sum(nblk, partials, KS_GAUSS_PART, 2);
         if (threadIdx.x == 0) {
             losses[0] = (float)sp / active_sum[0] + coef * ((float)sb / active_sum[0]);
             if (sums) sums[2] += sb;
         }
         return;
     }
-    const double s = ks_wave_sum(nblk, partials, KS_GAUSS_PART, k == 1 ? 1 : (k == 2 ? 3 : k + 1));
+    const double s = ppo_wave_sum(nblk, partials, KS_GAUSS_PART, k == 1 ? 1 : (k == 2 ? 3 : k + 1));
     if (threadIdx.x == 0) {
         if (k == 1) losses[1] = (float)s / active_sum[0];
         else if (k == 2) {
@@ -172,12 +152,12 @@ __global__ __launch_bounds__(256) void k_ppo_bc_loss_cat(long n, int A, const fl
                                                          const float *v_tgt, const float *active_sum, float eps, float ent_coef, int value_clip,
                                                          float *__restrict__ g_prob, float *__restrict__ g_v, double *partials) {
     const float inv = 1.f / active_sum[0];
-    constexpr float P_EPS = 1.1920928955078125e-07f;      // torch.finfo(torch.float32).eps (clamp_probs)
-    double sa = 0.0, sc = 0.0, sb = 0.0, hit = 0.0;
+    double sa = 0.0, sc = 0.0;
+    double x[2] = {0.0, 0.0};   // the imitation sum, the label hits
     double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long i2 = i % pv.d2, i01 = i / pv.d2, i1 = i01 % pv.d1, i0 = i01 / pv.d1;
-        const long po = i0 * pv.s0 + i1 * pv.s1 + i2 * pv.s2;
+        const PpoRow row = ppo_row(i, pv);
+        const long po = ppo_offset(row, pv);
         float p[PPO_MAX_A], l[PPO_MAX_A];
         float s = 0.f;
 #pragma unroll
@@ -193,30 +173,30 @@ __global__ __launch_bounds__(256) void k_ppo_bc_loss_cat(long n, int A, const fl
         for (int k = 0; k < PPO_MAX_A; k++)
             if (k < A) {
                 p[k] = p[k] / s;                                              // Categorical.probs
-                l[k] = logf(fminf(fmaxf(p[k], P_EPS), 1.f - P_EPS));          // probs_to_logits
+                l[k] = logf(cat_clamp(p[k]));                                 // probs_to_logits
                 if (k == a_idx) lp = l[k];
                 if (k == b_idx) lpb = l[k];
                 plp += l[k] * p[k];
             }
         const float act = active[i];
         const float upc = act * inv * coef;
-        const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        const float vn = v_now[ppo_offset(row, vv)];
         float d_lr = 0.f, d_vt = 0.f;
         const float d_ent = -plp;
         if (DIAG) { d_lr = lp - lp_old[i]; d_vt = v_tgt[i]; }
         const PpoElem e = ppo_elem(lp, -plp, lp_old[i], adv[i], act, vn, value_clip ? v_old[i] : 0.f, v_tgt[i], inv, eps, ent_coef, value_clip);
         sa += (double)(e.la * act);
         sc += (double)(e.lc * act);
-        sb += (double)(-lpb * act);
-        if (act != 0.f && arg == b_idx) hit += 1.0;
+        x[0] += (double)(-lpb * act);
+        if (act != 0.f && arg == b_idx) x[1] += 1.0;
         g_v[i] = e.g_v;
         float dot = 0.f;
 #pragma unroll
         for (int k = 0; k < PPO_MAX_A; k++)
             if (k < A) {
-                const float c = fminf(fmaxf(p[k], P_EPS), 1.f - P_EPS);
-                const bool pass = p[k] >= P_EPS && p[k] <= 1.f - P_EPS;
                 // d / d logits[k]: log_prob's gather, entropy's logits * probs, and the label's -coef (active / sum active)
+                const float c = cat_clamp(p[k]);
+                const bool pass = cat_pass(p[k]);
                 const float gl = (k == a_idx ? e.g_lp : 0.f) - e.g_ent * p[k] - (k == b_idx ? upc : 0.f);
                 l[k] = (pass ? gl / c : 0.f) - e.g_ent * l[k];                    // d / d probs[k]
                 dot += l[k] * p[k];
@@ -227,14 +207,7 @@ __global__ __launch_bounds__(256) void k_ppo_bc_loss_cat(long n, int A, const fl
         if (DIAG && act != 0.f) ppodiag::row(dg, d_lr, expf(d_lr), d_ent, vn, d_vt, eps);
     }
     ppo_block_sums(sa, sc, partials);
-    __shared__ double xred[2][4];
-    for (int off = 32; off > 0; off >>= 1) { sb += __shfl_xor(sb, off); hit += __shfl_xor(hit, off); }
-    if ((threadIdx.x & 63) == 0) { xred[0][threadIdx.x >> 6] = sb; xred[1][threadIdx.x >> 6] = hit; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const int k = threadIdx.x;
-        partials[2 * PPO_BLOCKS + 2 * blockIdx.x + k] = (xred[k][0] + xred[k][1]) + (xred[k][2] + xred[k][3]);
-    }
+    ppo_wave_block_sums(x, 2, partials + 2 * PPO_BLOCKS + 2 * blockIdx.x);
     if (DIAG) ppo_diag_block_sums(dg, partials + KS_CAT_PART * PPO_BLOCKS);
 }
 
@@ -245,7 +218,7 @@ __global__ __launch_bounds__(64) void k_ppo_bc_cat_finish(int nblk, const double
                                                           double *sums, double *diag) {
     if (blockIdx.x >= 2) { ppo_diag_finish_wave(blockIdx.x - 2, nblk, partials + KS_CAT_PART * PPO_BLOCKS, diag); return; }
     if (blockIdx.x == 0) {
-        const double b = ks_wave_sum(nblk, partials + 2 * PPO_BLOCKS, 2, 0);
+        const double b = ppo_wave_sum(nblk, partials + 2 * PPO_BLOCKS, 2, 0);
         if (threadIdx.x < 2) {
             double s = 0.0;
             for (int j = 0; j < nblk; j++) s += partials[2 * j + threadIdx.x];
@@ -256,7 +229,7 @@ __global__ __launch_bounds__(64) void k_ppo_bc_cat_finish(int nblk, const double
         }
         return;
     }
-    const double h = ks_wave_sum(nblk, partials + 2 * PPO_BLOCKS, 2, 1);
+    const double h = ppo_wave_sum(nblk, partials + 2 * PPO_BLOCKS, 2, 1);
     if (threadIdx.x == 0 && sums) { sums[0] += h; sums[1] += (double)active_sum[0]; }
 }
 

@@ -1820,23 +1820,58 @@ __device__ __forceinline__ void ppo_block_sums(double sa, double sc, double *par
     if (threadIdx.x == 0) { partials[2 * blockIdx.x] = red[0][0]; partials[2 * blockIdx.x + 1] = red[1][0]; }
 }
 
-// DIAG (algo.update_diagnostics): a live row also takes the ppodiag::row step (csrc/ppo_diag.hpp) after its gradient stores, and the
-// eight sums leave through per-block f64 partials behind the loss partials (ppo_diag_block_sums).  The losses and gradients are the
-// same expressions in the same order, hence the same bytes, and the DIAG = false instances are the kernels as they were.
-// diagnostic partials: [gridDim.x][ppodiag::NSUM] f64; wave butterflies, then the four waves in a fixed order
-__device__ __forceinline__ void ppo_diag_block_sums(const double (&dg)[ppodiag::NSUM], double *dpart) {
-    __shared__ double dred[ppodiag::NSUM][4];
+// ---- the steps the strided loss kernels share (k_ppo_loss_prob and csrc/gauss_policy.hpp, imitation.hpp, kickstart.hpp) ----------------
+// A strided operand is read through a 3-D view: row i of the (mini-batch, T, P) rows has index (i0, i1, i2), computed once per row and
+// used for every view of that row (the heads' outputs are time-major).
+struct PpoView { long d1, d2, s0, s1, s2; };
+struct PpoRow { long i0, i1, i2; };
+__device__ __forceinline__ PpoRow ppo_row(long i, const PpoView &v) {
+    const long i2 = i % v.d2, i01 = i / v.d2;
+    return PpoRow{i01 / v.d1, i01 % v.d1, i2};
+}
+__device__ __forceinline__ long ppo_offset(const PpoRow &r, const PpoView &v) { return r.i0 * v.s0 + r.i1 * v.s1 + r.i2 * v.s2; }
+
+// NSUM per-thread f64 sums of a 256-thread block, the first nsum (uniform) live, to part[k]: wave butterflies, then the four waves in
+// a fixed order (the first-generation ppo_block_sums above is a 256-entry tree: another summation order, other bits)
+template <int NSUM>
+__device__ __forceinline__ void ppo_wave_block_sums(const double (&acc)[NSUM], int nsum, double *part) {
+    __shared__ double red[NSUM][4];
 #pragma unroll
-    for (int k = 0; k < ppodiag::NSUM; k++) {
-        double s = dg[k];
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if ((threadIdx.x & 63) == 0) dred[k][threadIdx.x >> 6] = s;
-    }
+    for (int k = 0; k < NSUM; k++)
+        if (k < nsum) {
+            double s = acc[k];
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
+        }
     __syncthreads();
-    if (threadIdx.x < ppodiag::NSUM) {
+    if (threadIdx.x < nsum) {
         const int k = threadIdx.x;
-        dpart[(size_t)blockIdx.x * ppodiag::NSUM + k] = (dred[k][0] + dred[k][1]) + (dred[k][2] + dred[k][3]);
+        part[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
     }
+}
+
+// sum k of the block partials (stride doubles per block) by one wave of a finish kernel: lane l adds blocks l, l + 64, .. in order,
+// then a fixed butterfly -- the same bits every run, without one lane walking all PPO_BLOCKS partials serially
+__device__ __forceinline__ double ppo_wave_sum(int nblk, const double *partials, int stride, int k) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 64) s += partials[(size_t)b * stride + k];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    return s;
+}
+
+// The categorical row: torch.distributions.Categorical(prob) renormalises, and probs_to_logits clamps to [P_EPS, 1 - P_EPS] before
+// the log; the clamp's backward passes the gradient on the closed range.  (The load-and-sum and the argmax loops stay written out in
+// the three kernels: as helpers over the register array they cost two of them 16 VGPRs)
+constexpr int PPO_MAX_A = 16;
+constexpr float P_EPS = 1.1920928955078125e-07f;      // torch.finfo(torch.float32).eps (clamp_probs)
+__device__ __forceinline__ float cat_clamp(float p) { return fminf(fmaxf(p, P_EPS), 1.f - P_EPS); }
+__device__ __forceinline__ bool cat_pass(float p) { return p >= P_EPS && p <= 1.f - P_EPS; }
+
+// DIAG (algo.update_diagnostics): a live row also takes the ppodiag::row step (csrc/ppo_diag.hpp) after its gradient stores, and the
+// eight sums leave through per-block f64 partials [gridDim.x][ppodiag::NSUM] behind the loss partials.  The losses and gradients are
+// the same expressions in the same order, hence the same bytes, and the DIAG = false instances are the kernels as they were.
+__device__ __forceinline__ void ppo_diag_block_sums(const double (&dg)[ppodiag::NSUM], double *dpart) {
+    ppo_wave_block_sums(dg, ppodiag::NSUM, dpart + (size_t)blockIdx.x * ppodiag::NSUM);
 }
 
 template <bool DIAG>
@@ -1866,20 +1901,17 @@ __global__ __launch_bounds__(256) void k_ppo_loss(long n, const float *lp_now, c
 // the gradient with respect to prob written straight out (autograd's rules: the clamp passes the gradient on its closed range).  One
 // launch instead of Categorical's ~16 element-wise kernels over (rows, A) and their backward.  prob / its gradient and the values are
 // read through 3-D views (index (i0, i1, i2) of the (mini-batch, T, P) rows): the heads' outputs are time-major.
-struct PpoView { long d1, d2, s0, s1, s2; };
-constexpr int PPO_MAX_A = 16;
 template <bool DIAG>
 __global__ __launch_bounds__(256) void k_ppo_loss_prob(long n, int A, const float *__restrict__ prob, PpoView pv, const float *__restrict__ action,
                                                        const float *lp_old, const float *adv, const float *active, const float *__restrict__ v_now, PpoView vv,
                                                        const float *v_old, const float *v_tgt, const float *active_sum, float eps, float ent_coef,
                                                        int value_clip, float *__restrict__ g_prob, float *__restrict__ g_v, double *partials) {
     const float inv = 1.f / active_sum[0];
-    constexpr float P_EPS = 1.1920928955078125e-07f;      // torch.finfo(torch.float32).eps (clamp_probs)
     double sa = 0.0, sc = 0.0;
     double dg[ppodiag::NSUM] = {};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long i2 = i % pv.d2, i01 = i / pv.d2, i1 = i01 % pv.d1, i0 = i01 / pv.d1;
-        const long po = i0 * pv.s0 + i1 * pv.s1 + i2 * pv.s2;
+        const PpoRow row = ppo_row(i, pv);
+        const long po = ppo_offset(row, pv);
         float p[PPO_MAX_A], l[PPO_MAX_A];
         float s = 0.f;
 #pragma unroll
@@ -1890,12 +1922,12 @@ __global__ __launch_bounds__(256) void k_ppo_loss_prob(long n, int A, const floa
         for (int k = 0; k < PPO_MAX_A; k++)
             if (k < A) {
                 p[k] = p[k] / s;                                              // Categorical.probs
-                l[k] = logf(fminf(fmaxf(p[k], P_EPS), 1.f - P_EPS));          // probs_to_logits
+                l[k] = logf(cat_clamp(p[k]));                                 // probs_to_logits
                 if (k == a_idx) lp = l[k];
                 plp += l[k] * p[k];
             }
         const float act = active[i];
-        const float vn = v_now[i0 * vv.s0 + i1 * vv.s1 + i2 * vv.s2];
+        const float vn = v_now[ppo_offset(row, vv)];
         float d_lr = 0.f, d_vt = 0.f;
         const float d_ent = -plp;
         if (DIAG) { d_lr = lp - lp_old[i]; d_vt = v_tgt[i]; }
@@ -1907,8 +1939,8 @@ __global__ __launch_bounds__(256) void k_ppo_loss_prob(long n, int A, const floa
 #pragma unroll
         for (int k = 0; k < PPO_MAX_A; k++)
             if (k < A) {
-                const float c = fminf(fmaxf(p[k], P_EPS), 1.f - P_EPS);
-                const bool pass = p[k] >= P_EPS && p[k] <= 1.f - P_EPS;
+                const float c = cat_clamp(p[k]);
+                const bool pass = cat_pass(p[k]);
                 const float gl = (k == a_idx ? e.g_lp : 0.f) - e.g_ent * p[k];   // d / d logits[k]: log_prob's gather, entropy's logits * probs
                 l[k] = (pass ? gl / c : 0.f) - e.g_ent * l[k];                    // d / d probs[k]
                 dot += l[k] * p[k];
@@ -1935,12 +1967,10 @@ __global__ void k_ppo_loss_finish(int nblk, const double *partials, const float 
     ppo_loss_finish_sums(nblk, partials, active_sum, losses);
 }
 
-// diagnostic sum k of a DIAG launch, one wave: lane l adds the partials of blocks l, l + 64, .. in order, then a fixed butterfly
-// (as k_ppo_gauss_finish), and diag[k] += s -- the caller zeroes diag once per update, the launches of a stream run in order
+// diagnostic sum k of a DIAG launch, one wave (ppo_wave_sum): diag[k] += s -- the caller zeroes diag once per update, the launches
+// of a stream run in order
 __device__ __forceinline__ void ppo_diag_finish_wave(int k, int nblk, const double *dpart, double *diag) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += dpart[(size_t)b * ppodiag::NSUM + k];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const double s = ppo_wave_sum(nblk, dpart, ppodiag::NSUM, k);
     if (threadIdx.x == 0) diag[k] += s;
 }
 

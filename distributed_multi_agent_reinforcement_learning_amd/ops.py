@@ -1342,15 +1342,29 @@ FUSED_CELL_MIN_ROWS = 1024  # single-step batches at least this large take the f
 
 
 PPO_DIAG_SUMS = 8   # csrc/ppo_diag.hpp: count, k3 KL, clipped, entropy, v_target, v_target^2, (v_target - v_now)^2, ratio
+BC_SUMS = 2         # csrc/imitation.hpp: the call's extra sum (sum of squared residuals / label hits over live rows) and its live-row count
+KICK_SUMS = 3       # csrc/kickstart.hpp: the imitation metric's sum, the live-row count, the sum of the unweighted imitation loss over live rows
+BC_GAUSS_METRIC = {"mse": 0, "angle": 1}   # csrc/imitation.hpp: what bc_loss_gauss adds to sums[0]
+PPO_FROM_PROB = os.environ.get("MAPPO_PPO_FROM_PROB", "1") != "0"   # A/B switch: off = torch.distributions.Categorical + ppo_loss
 
 
-def _diag_variant(L, name, plain_ws, diag_ws, diag, dev):
-    """-> (entry point, workspace bytes, trailing arguments) of a loss call: the plain one for diag None, else the _diag entry point
-    with the (8,) f64 device tensor the sums are added to"""
-    if diag is None:
-        return getattr(L, name), plain_ws(), ()
-    assert diag.dtype == torch.float64 and diag.shape == (PPO_DIAG_SUMS,) and diag.is_contiguous() and diag.device == dev
-    return getattr(L, name + "_diag"), diag_ws(), (_ptr(diag),)
+# ---- the eight fused loss launches: one autograd Function, one copy of each host step ------------------------------------------------------
+class _Loss(torch.autograd.Function):
+    """(actor_loss, critic_loss) of one mini-batch.  `launch` (built by the public wrapper) checks its operands, runs the loss launch,
+    which also writes every gradient, and returns (losses, gradients); the gradients are scaled here.  operands: the tensors the
+    gradients belong to, in their order; the first n_actor take the actor loss's gradient, the last one (values_now) the critic's."""
+
+    @staticmethod
+    def forward(ctx, launch, n_actor, *operands):
+        losses, grads = launch()
+        assert len(grads) == len(operands) == n_actor + 1
+        ctx.save_for_backward(*grads)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, ga, gc):
+        *g_actor, g_v = ctx.saved_tensors
+        return (None, None, *(g * ga for g in g_actor), g_v * gc)
 
 
 def _own_rows(t):
@@ -1363,71 +1377,85 @@ def _own_rows(t):
 _SHARED_ROWS = "rows share storage (a stride of 0 over a row dimension): the gradient is written per row, pass a tensor with rows of its own"
 
 
-class _PPOLoss(torch.autograd.Function):
-    """(actor_loss, critic_loss) of one mini-batch; the gradients are computed in the forward launch and scaled here."""
+def _sums_ok(t, length, dev):
+    """sums / diag: None, or the (length,) f64 device tensor a loss launch adds its sums to"""
+    assert t is None or (t.dtype == torch.float64 and t.shape == (length,) and t.is_contiguous() and t.device == dev)
 
-    @staticmethod
-    def forward(ctx, logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
-                diag=None):
-        L = load_library()
+
+def _diag_variant(L, name, plain_ws, diag_ws, diag, dev):
+    """-> (entry point, workspace bytes, trailing arguments) of a loss call: the plain one for diag None, else the _diag entry point
+    with the (8,) f64 device tensor the sums are added to"""
+    if diag is None:
+        return getattr(L, name), plain_ws(), ()
+    _sums_ok(diag, PPO_DIAG_SUMS, dev)
+    return getattr(L, name + "_diag"), diag_ws(), (_ptr(diag),)
+
+
+def _row_operands(n, per_row, values_old):
+    """-> (the per-row operands, values_old or None), contiguous: n fp32 entries each"""
+    rows = [t.contiguous() for t in per_row]
+    assert all(t.numel() == n and t.dtype == torch.float32 for t in rows)
+    return rows, values_old.contiguous() if values_old is not None else None
+
+
+def _loss_tail(active, ws_bytes, values_now=None):
+    """-> (sum of active, the two losses, the values' gradient (with values_now), the workspace) of a loss launch"""
+    dev = active.device
+    g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev) if values_now is not None else None
+    return (active.sum().reshape(1), torch.empty(2, dtype=torch.float32, device=dev), g_v, torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
+
+
+def _strided_args(x, values_now):
+    """the policy operand x (mb, T, P, A) of a loss launch: any strides over the first three dimensions (the heads' outputs are
+    time-major views), the last dense  -> (rows, A, its gradient in x's layout, the (x, g_x, d1, d2, s0, s1, s2) arguments)"""
+    d0, d1, d2, A = x.shape
+    assert x.stride(3) == 1 and x.dtype == torch.float32 and values_now.shape == x.shape[:3]
+    g = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
+    return d0 * d1 * d2, A, g, (_ptr(x), _ptr(g), d1, d2, *x.stride()[:3])
+
+
+def _value_args(values_now):
+    """the (values_now, s0, s1, s2) arguments: (mb, T, P) with any strides"""
+    return (_ptr(values_now), *values_now.stride())
+
+
+def _like(x, t):
+    """a per-entry operand (action, target) of x's shape, contiguous"""
+    t = t.contiguous()
+    assert t.shape == x.shape and t.dtype == torch.float32
+    return t
+
+
+def _log_std_args(ls_raw, mu):
+    """-> (ls, its gradient, ls's three row strides) of the log-std operand of a Gaussian loss launch"""
+    A = mu.shape[-1]
+    ls = ls_raw.detach()
+    if ls.dim() == 1:            # param mode: one vector, stride 0 over the rows
+        assert ls.shape == (A,)
+        return ls.contiguous(), torch.empty(A, dtype=torch.float32, device=mu.device), (0, 0, 0)
+    # state mode: per row, any strides over the first three dimensions (a time-major view)
+    assert ls.shape == mu.shape and ls.stride(3) == 1 and ls.dtype == torch.float32
+    lstr = ls.stride()[:3]
+    assert any(lstr), "a per-row ls_raw needs a nonzero row stride"
+    return ls, torch.empty_strided(ls.shape, ls.stride(), dtype=torch.float32, device=mu.device), lstr
+
+
+def ppo_loss(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True, diag=None):
+    """Masked-mean PPO policy loss and (clipped) value loss of a mini-batch, one launch with the gradients
+    (DHGN/mappo_parallel.py:692-706; csrc/mappo_ops.hip k_ppo_loss).  diag: None, or an (8,) f64 device tensor to which the call adds
+    the update diagnostics' sums over its live rows (csrc/ppo_diag.hpp) in the same two launches; losses and gradients keep their bytes."""
+    def launch():
         _need_gpu(logp_now, "ppo_loss")
-        ts = [t.contiguous() for t in (logp_now, entropy, logp_old, adv, active, values_now, v_target)]
-        vo = values_old.contiguous() if values_old is not None else None
-        n = ts[0].numel()
-        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts)
-        dev = logp_now.device
-        asum = active.sum().reshape(1)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        g = torch.empty((3,) + tuple(logp_now.shape), dtype=torch.float32, device=dev)
-        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_fwd_bwd", L.ppo_loss_workspace, L.ppo_loss_diag_workspace, diag, dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _check(fn(n, _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]), _ptr(ts[4]), _ptr(ts[5]), _ptr(vo), _ptr(ts[6]),
-                  _ptr(asum), float(epsilon), float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g[0]),
-                  _ptr(g[1]), _ptr(g[2]), _ptr(ws), _stream(), *extra), "ppo_loss_fwd_bwd")
-        ctx.save_for_backward(g)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, ga, gc):
-        (g,) = ctx.saved_tensors
-        return g[0] * ga, g[1] * ga, g[2] * gc, None, None, None, None, None, None, None, None, None
-
-
-class _PPOLossProb(torch.autograd.Function):
-    """(actor_loss, critic_loss) of one mini-batch from the policy's probabilities: Categorical(prob).log_prob / .entropy() inside the
-    loss launch (ppo_loss_prob_fwd_bwd), which also writes the gradient with respect to prob."""
-
-    @staticmethod
-    def forward(ctx, prob, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip, diag=None):
-        L = load_library()
-        _need_gpu(prob, "ppo_loss_prob")
-        A = prob.shape[-1]
-        d0, d1, d2 = prob.shape[:3]
-        n = d0 * d1 * d2
-        ts = [t.contiguous() for t in (action, logp_old, adv, active, v_target)]
-        vo = values_old.contiguous() if values_old is not None else None
-        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == prob.shape[:3]
-        dev = prob.device
-        asum = active.sum().reshape(1)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        g_prob = torch.empty_strided(prob.shape, prob.stride(), dtype=torch.float32, device=dev)    # the layout of prob (a time-major view)
-        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_prob_fwd_bwd", L.ppo_loss_workspace, L.ppo_loss_diag_workspace, diag, dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        ps, vs = prob.stride(), values_now.stride()
-        _check(fn(n, A, _ptr(prob), _ptr(g_prob), d1, d2, ps[0], ps[1], ps[2], _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(ts[3]),
-                  _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[4]), _ptr(asum), float(epsilon), float(entropy_coef),
-                  int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream(), *extra), "ppo_loss_prob_fwd_bwd")
-        ctx.save_for_backward(g_prob, g_v)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, ga, gc):
-        g_prob, g_v = ctx.saved_tensors
-        return g_prob * ga, g_v * gc, None, None, None, None, None, None, None, None, None, None
-
-
-PPO_FROM_PROB = os.environ.get("MAPPO_PPO_FROM_PROB", "1") != "0"   # A/B switch: off = torch.distributions.Categorical + ppo_loss
+        L, n = load_library(), logp_now.numel()
+        (lp, ent, lo, ad, ac, vn, vt), vo = _row_operands(n, (logp_now, entropy, logp_old, adv, active, values_now, v_target), values_old)
+        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_fwd_bwd", L.ppo_loss_workspace, L.ppo_loss_diag_workspace, diag, logp_now.device)
+        asum, losses, _, ws = _loss_tail(active, ws_bytes)
+        g = tuple(torch.empty((3,) + tuple(logp_now.shape), dtype=torch.float32, device=logp_now.device))
+        _check(fn(n, _ptr(lp), _ptr(ent), _ptr(lo), _ptr(ad), _ptr(ac), _ptr(vn), _ptr(vo), _ptr(vt), _ptr(asum), float(epsilon),
+                  float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(ws), _stream(), *extra),
+               "ppo_loss_fwd_bwd")
+        return losses, g
+    return _Loss.apply(launch, 2, logp_now, entropy, values_now)
 
 
 def ppo_loss_prob_ok(prob, values_now):
@@ -1436,51 +1464,24 @@ def ppo_loss_prob_ok(prob, values_now):
 
 
 def ppo_loss_prob(prob, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True, diag=None):
-    """ppo_loss(Categorical(prob).log_prob(action), Categorical(prob).entropy(), ...) in one launch (DHGN/mappo_parallel.py:451-456,
-    :692-706; csrc/mappo_ops.hip k_ppo_loss_prob).  prob (mb, T, P, A), values_now (mb, T, P): any strides over the first three
-    dimensions (the heads' outputs are time-major views), each row with storage of its own.  diag: see ppo_loss."""
+    """ppo_loss(Categorical(prob).log_prob(action), Categorical(prob).entropy(), ...) in one launch, which also writes the gradient with
+    respect to prob (DHGN/mappo_parallel.py:451-456, :692-706; csrc/mappo_ops.hip k_ppo_loss_prob).  prob (mb, T, P, A), values_now
+    (mb, T, P): any strides over the first three dimensions (the heads' outputs are time-major views), each row with storage of its own.
+    diag: see ppo_loss."""
     assert _own_rows(prob), "prob: " + _SHARED_ROWS
-    return _PPOLossProb.apply(prob, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip, diag)
 
-
-class _PPOLossGauss(torch.autograd.Function):
-    """(actor_loss, critic_loss) of one mini-batch of a diagonal-Gaussian policy: Normal(mu, exp(log_std)).log_prob(action).sum(-1) and
-    .entropy().sum(-1) inside the loss launch (ppo_loss_gauss_fwd_bwd), which also writes the gradients w.r.t. mu and log_std."""
-
-    @staticmethod
-    def forward(ctx, mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
-                diag=None):
+    def launch():
+        _need_gpu(prob, "ppo_loss_prob")
         L = load_library()
-        _need_gpu(mu, "ppo_loss_gauss")
-        A = mu.shape[-1]
-        d0, d1, d2 = mu.shape[:3]
-        n = d0 * d1 * d2
-        ts = [t.contiguous() for t in (logp_old, adv, active, v_target)]
-        act = action.contiguous()
-        ls = log_std.detach().contiguous()
-        vo = values_old.contiguous() if values_old is not None else None
-        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == mu.shape[:3]
-        assert act.shape == mu.shape and act.dtype == torch.float32 and ls.shape == (A,) and mu.stride(3) == 1
-        dev = mu.device
-        asum = active.sum().reshape(1)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)      # the layout of mu (a time-major view)
-        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        g_ls = torch.empty(A, dtype=torch.float32, device=dev)
-        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_gauss_fwd_bwd", L.ppo_loss_gauss_workspace, L.ppo_loss_gauss_diag_workspace, diag, dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        ms, vs = mu.stride(), values_now.stride()
-        _check(fn(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(act), _ptr(ts[0]), _ptr(ts[1]),
-                  _ptr(ts[2]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon),
-                  float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(g_ls), _ptr(ws), _stream(), *extra),
-               "ppo_loss_gauss_fwd_bwd")
-        ctx.save_for_backward(g_mu, g_ls, g_v)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, ga, gc):
-        g_mu, g_ls, g_v = ctx.saved_tensors
-        return g_mu * ga, g_ls * ga, g_v * gc, None, None, None, None, None, None, None, None, None, None
+        n, A, g_prob, prob_args = _strided_args(prob, values_now)
+        (act, lo, ad, ac, vt), vo = _row_operands(n, (action, logp_old, adv, active, v_target), values_old)
+        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_prob_fwd_bwd", L.ppo_loss_workspace, L.ppo_loss_diag_workspace, diag, prob.device)
+        asum, losses, g_v, ws = _loss_tail(active, ws_bytes, values_now)
+        _check(fn(n, A, *prob_args, _ptr(act), _ptr(lo), _ptr(ad), _ptr(ac), *_value_args(values_now), _ptr(vo), _ptr(vt), _ptr(asum),
+                  float(epsilon), float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream(), *extra),
+               "ppo_loss_prob_fwd_bwd")
+        return losses, (g_prob, g_v)
+    return _Loss.apply(launch, 1, prob, values_now)
 
 
 def ppo_loss_gauss(mu, log_std, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True,
@@ -1490,59 +1491,22 @@ def ppo_loss_gauss(mu, log_std, action, values_now, logp_old, adv, active, value
     over the first three dimensions (time-major views), mu's last dimension dense; action (mb, T, P, A), the rest (mb, T, P).
     diag: see ppo_loss."""
     assert _own_rows(mu), "mu: " + _SHARED_ROWS
-    return _PPOLossGauss.apply(mu, log_std, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
-                               diag)
 
-
-class _PPOLossGaussEx(torch.autograd.Function):
-    """ppo_loss_gauss_ex: ppo_loss_gauss_ex_fwd_bwd writes the losses and the gradients w.r.t. mu, ls_raw (per row or the vector)
-    and the values in one pass."""
-
-    @staticmethod
-    def forward(ctx, mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip,
-                log_std_min, log_std_max, squash, diag=None):
+    def launch():
+        _need_gpu(mu, "ppo_loss_gauss")
         L = load_library()
-        _need_gpu(mu, "ppo_loss_gauss_ex")
-        A = mu.shape[-1]
-        d0, d1, d2 = mu.shape[:3]
-        n = d0 * d1 * d2
-        ts = [t.contiguous() for t in (logp_old, adv, active, v_target)]
-        act = action.contiguous()
-        vo = values_old.contiguous() if values_old is not None else None
-        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == mu.shape[:3]
-        assert act.shape == mu.shape and act.dtype == torch.float32 and mu.stride(3) == 1 and squash in GAUSS_SQUASH
-        dev = mu.device
-        ls = ls_raw.detach()
-        if ls.dim() == 1:            # param mode: one vector, stride 0 over the rows
-            assert ls.shape == (A,)
-            ls = ls.contiguous()
-            g_ls = torch.empty(A, dtype=torch.float32, device=dev)
-            lstr = (0, 0, 0)
-        else:                        # state mode: per row, any strides over the first three dimensions (a time-major view)
-            assert ls.shape == mu.shape and ls.stride(3) == 1 and ls.dtype == torch.float32
-            g_ls = torch.empty_strided(ls.shape, ls.stride(), dtype=torch.float32, device=dev)
-            lstr = ls.stride()[:3]
-            assert any(lstr), "a per-row ls_raw needs a nonzero row stride"
-        asum = active.sum().reshape(1)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)
-        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_gauss_ex_fwd_bwd", L.ppo_loss_gauss_ex_workspace, L.ppo_loss_gauss_diag_workspace, diag,
-                                            dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        ms, vs = mu.stride(), values_now.stride()
-        _check(fn(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
-                  float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], _ptr(act), _ptr(ts[0]), _ptr(ts[1]),
-                  _ptr(ts[2]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon),
-                  float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream(), *extra),
-               "ppo_loss_gauss_ex_fwd_bwd")
-        ctx.save_for_backward(g_mu, g_ls, g_v)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, ga, gc):
-        g_mu, g_ls, g_v = ctx.saved_tensors
-        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 13
+        n, A, g_mu, mu_args = _strided_args(mu, values_now)
+        (lo, ad, ac, vt), vo = _row_operands(n, (logp_old, adv, active, v_target), values_old)
+        act = _like(mu, action)
+        assert log_std.dim() == 1
+        ls, g_ls, _ = _log_std_args(log_std, mu)
+        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_gauss_fwd_bwd", L.ppo_loss_gauss_workspace, L.ppo_loss_gauss_diag_workspace, diag, mu.device)
+        asum, losses, g_v, ws = _loss_tail(active, ws_bytes, values_now)
+        _check(fn(n, A, *mu_args, _ptr(ls), _ptr(act), _ptr(lo), _ptr(ad), _ptr(ac), *_value_args(values_now), _ptr(vo), _ptr(vt), _ptr(asum),
+                  float(epsilon), float(entropy_coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(g_ls), _ptr(ws), _stream(), *extra),
+               "ppo_loss_gauss_fwd_bwd")
+        return losses, (g_mu, g_ls, g_v)
+    return _Loss.apply(launch, 2, mu, log_std, values_now)
 
 
 def ppo_loss_gauss_ex(mu, ls_raw, action, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True,
@@ -1555,69 +1519,23 @@ def ppo_loss_gauss_ex(mu, ls_raw, action, values_now, logp_old, adv, active, val
     values_now.  diag: see ppo_loss."""
     assert _own_rows(mu), "mu: " + _SHARED_ROWS
     assert ls_raw.dim() == 1 or _own_rows(ls_raw), "ls_raw: " + _SHARED_ROWS
-    return _PPOLossGaussEx.apply(mu, ls_raw, values_now, action, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef,
-                                 use_value_clip, log_std_min, log_std_max, squash, diag)
 
-
-BC_SUMS = 2   # csrc/imitation.hpp: the call's extra sum (sum of squared residuals / label hits over live rows) and its live-row count
-
-
-def _bc_sums_ok(sums, dev):
-    assert sums is None or (sums.dtype == torch.float64 and sums.shape == (BC_SUMS,) and sums.is_contiguous() and sums.device == dev)
-
-
-class _BCLossGauss(torch.autograd.Function):
-    """bc_loss_gauss: bc_loss_gauss_fwd_bwd writes the losses and the gradients w.r.t. mu, ls_raw (per row or the vector) and the
-    values in one pass."""
-
-    @staticmethod
-    def forward(ctx, mu, ls_raw, values_now, target, active, values_old, v_target, epsilon, use_value_clip, log_std_min, log_std_max, fit_std,
-                wrap0, sums=None, metric="mse"):
+    def launch():
+        _need_gpu(mu, "ppo_loss_gauss_ex")
         L = load_library()
-        _need_gpu(mu, "bc_loss_gauss")
-        A = mu.shape[-1]
-        assert metric in BC_GAUSS_METRIC and (metric == "mse" or A >= 3)
-        d0, d1, d2 = mu.shape[:3]
-        n = d0 * d1 * d2
-        ts = [t.contiguous() for t in (active, v_target)]
-        tgt = target.contiguous()
-        vo = values_old.contiguous() if values_old is not None else None
-        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == mu.shape[:3]
-        assert tgt.shape == mu.shape and tgt.dtype == torch.float32 and mu.stride(3) == 1
-        dev = mu.device
-        _bc_sums_ok(sums, dev)
-        ls = ls_raw.detach()
-        if ls.dim() == 1:            # param mode: one vector, stride 0 over the rows
-            assert ls.shape == (A,)
-            ls = ls.contiguous()
-            g_ls = torch.empty(A, dtype=torch.float32, device=dev)
-            lstr = (0, 0, 0)
-        else:                        # state mode: per row, any strides over the first three dimensions (a time-major view)
-            assert ls.shape == mu.shape and ls.stride(3) == 1 and ls.dtype == torch.float32
-            g_ls = torch.empty_strided(ls.shape, ls.stride(), dtype=torch.float32, device=dev)
-            lstr = ls.stride()[:3]
-            assert any(lstr), "a per-row ls_raw needs a nonzero row stride"
-        asum = active.sum().reshape(1)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)
-        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.bc_loss_workspace(), dtype=torch.uint8, device=dev)
-        ms, vs = mu.stride(), values_now.stride()
-        _check(L.bc_loss_gauss_ex_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
-                                          float(log_std_min), float(log_std_max), int(bool(fit_std)), int(bool(wrap0)), BC_GAUSS_METRIC[metric],
-                                          _ptr(tgt), _ptr(ts[0]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[1]), _ptr(asum),
-                                          float(epsilon), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(ws), _stream()),
-               "bc_loss_gauss_ex_fwd_bwd")
-        ctx.save_for_backward(g_mu, g_ls, g_v)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, ga, gc):
-        g_mu, g_ls, g_v = ctx.saved_tensors
-        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 12
-
-
-BC_GAUSS_METRIC = {"mse": 0, "angle": 1}   # csrc/imitation.hpp: what bc_loss_gauss adds to sums[0]
+        n, A, g_mu, mu_args = _strided_args(mu, values_now)
+        (lo, ad, ac, vt), vo = _row_operands(n, (logp_old, adv, active, v_target), values_old)
+        act = _like(mu, action)
+        assert squash in GAUSS_SQUASH
+        ls, g_ls, lstr = _log_std_args(ls_raw, mu)
+        fn, ws_bytes, extra = _diag_variant(L, "ppo_loss_gauss_ex_fwd_bwd", L.ppo_loss_gauss_ex_workspace, L.ppo_loss_gauss_diag_workspace, diag,
+                                            mu.device)
+        asum, losses, g_v, ws = _loss_tail(active, ws_bytes, values_now)
+        _check(fn(n, A, *mu_args, _ptr(ls), _ptr(g_ls), *lstr, float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], _ptr(act), _ptr(lo),
+                  _ptr(ad), _ptr(ac), *_value_args(values_now), _ptr(vo), _ptr(vt), _ptr(asum), float(epsilon), float(entropy_coef),
+                  int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(ws), _stream(), *extra), "ppo_loss_gauss_ex_fwd_bwd")
+        return losses, (g_mu, g_ls, g_v)
+    return _Loss.apply(launch, 2, mu, ls_raw, values_now)
 
 
 def bc_loss_gauss(mu, ls_raw, target, values_now, active, values_old, v_target, epsilon, use_value_clip=True, log_std_min=-float("inf"),
@@ -1628,42 +1546,25 @@ def bc_loss_gauss(mu, ls_raw, target, values_now, active, values_old, v_target, 
     ppo_loss_gauss_ex; gradients flow to mu, ls_raw (exactly 0 without fit_std) and values_now.  sums: None, or a (2,) f64 device tensor to
     which the call adds sum_rows active sum_a d^2 and sum active.  metric "angle" (the direction-vector head, A >= 3; wrap0 is ignored):
     the first sum is sum_rows active angle(mu[:3], target[:3]) in radians instead (pi / 2 for a row whose mu[:3] is zero)."""
-    return _BCLossGauss.apply(mu, ls_raw, values_now, target, active, values_old, v_target, epsilon, use_value_clip, log_std_min, log_std_max,
-                              fit_std, wrap0, sums, metric)
+    assert _own_rows(mu), "mu: " + _SHARED_ROWS
+    assert ls_raw.dim() == 1 or _own_rows(ls_raw), "ls_raw: " + _SHARED_ROWS
 
-
-class _BCLossCat(torch.autograd.Function):
-    """bc_loss_cat: bc_loss_cat_fwd_bwd writes the losses and the gradients w.r.t. prob and the values in one pass."""
-
-    @staticmethod
-    def forward(ctx, prob, values_now, label, active, values_old, v_target, epsilon, use_value_clip, sums=None):
+    def launch():
+        _need_gpu(mu, "bc_loss_gauss")
         L = load_library()
-        _need_gpu(prob, "bc_loss_cat")
-        A = prob.shape[-1]
-        d0, d1, d2 = prob.shape[:3]
-        n = d0 * d1 * d2
-        ts = [t.contiguous() for t in (label, active, v_target)]
-        vo = values_old.contiguous() if values_old is not None else None
-        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == prob.shape[:3]
-        assert prob.stride(3) == 1 and prob.dtype == torch.float32 and 1 <= A <= 16
-        dev = prob.device
-        _bc_sums_ok(sums, dev)
-        asum = active.sum().reshape(1)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        g_prob = torch.empty_strided(prob.shape, prob.stride(), dtype=torch.float32, device=dev)    # the layout of prob (a time-major view)
-        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.bc_loss_workspace(), dtype=torch.uint8, device=dev)
-        ps, vs = prob.stride(), values_now.stride()
-        _check(L.bc_loss_cat_fwd_bwd(n, A, _ptr(prob), _ptr(g_prob), d1, d2, ps[0], ps[1], ps[2], _ptr(ts[0]), _ptr(ts[1]), _ptr(values_now),
-                                     vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[2]), _ptr(asum), float(epsilon), int(bool(use_value_clip)),
-                                     _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(ws), _stream()), "bc_loss_cat_fwd_bwd")
-        ctx.save_for_backward(g_prob, g_v)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, ga, gc):
-        g_prob, g_v = ctx.saved_tensors
-        return (g_prob * ga, g_v * gc) + (None,) * 7
+        n, A, g_mu, mu_args = _strided_args(mu, values_now)
+        (ac, vt), vo = _row_operands(n, (active, v_target), values_old)
+        tgt = _like(mu, target)
+        assert metric in BC_GAUSS_METRIC and (metric == "mse" or A >= 3)
+        _sums_ok(sums, BC_SUMS, mu.device)
+        ls, g_ls, lstr = _log_std_args(ls_raw, mu)
+        asum, losses, g_v, ws = _loss_tail(active, L.bc_loss_workspace(), values_now)
+        _check(L.bc_loss_gauss_ex_fwd_bwd(n, A, *mu_args, _ptr(ls), _ptr(g_ls), *lstr, float(log_std_min), float(log_std_max), int(bool(fit_std)),
+                                          int(bool(wrap0)), BC_GAUSS_METRIC[metric], _ptr(tgt), _ptr(ac), *_value_args(values_now), _ptr(vo),
+                                          _ptr(vt), _ptr(asum), float(epsilon), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums),
+                                          _ptr(ws), _stream()), "bc_loss_gauss_ex_fwd_bwd")
+        return losses, (g_mu, g_ls, g_v)
+    return _Loss.apply(launch, 2, mu, ls_raw, values_now)
 
 
 def bc_loss_cat(prob, label, values_now, active, values_old, v_target, epsilon, use_value_clip=True, sums=None):
@@ -1672,67 +1573,21 @@ def bc_loss_cat(prob, label, values_now, active, values_old, v_target, epsilon, 
     with the same bits.  prob (mb, T, P, A <= 16), values_now (mb, T, P): any strides over the first three dimensions; label (mb, T, P)
     as floats.  sums: None, or a (2,) f64 device tensor to which the call adds the number of live rows whose argmax (lowest index on
     ties) is the label, and sum active."""
-    return _BCLossCat.apply(prob, values_now, label, active, values_old, v_target, epsilon, use_value_clip, sums)
+    assert _own_rows(prob), "prob: " + _SHARED_ROWS
 
-
-KICK_SUMS = 3   # csrc/kickstart.hpp: the imitation metric's sum, the live-row count, the sum of the unweighted imitation loss over live rows
-
-
-def _kick_args_ok(sums, diag, dev):
-    assert sums is None or (sums.dtype == torch.float64 and sums.shape == (KICK_SUMS,) and sums.is_contiguous() and sums.device == dev)
-    assert diag is None or (diag.dtype == torch.float64 and diag.shape == (PPO_DIAG_SUMS,) and diag.is_contiguous() and diag.device == dev)
-
-
-class _PPOBCLossGauss(torch.autograd.Function):
-    """ppo_bc_loss_gauss: ppo_bc_loss_gauss_fwd_bwd writes the losses and the gradients w.r.t. mu, ls_raw (per row or the vector) and
-    the values in one pass."""
-
-    @staticmethod
-    def forward(ctx, mu, ls_raw, values_now, action, target, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef,
-                use_value_clip, log_std_min, log_std_max, squash, fit_std, wrap0, metric, sums=None, diag=None):
+    def launch():
+        _need_gpu(prob, "bc_loss_cat")
         L = load_library()
-        _need_gpu(mu, "ppo_bc_loss_gauss")
-        A = mu.shape[-1]
-        assert metric in BC_GAUSS_METRIC and (metric == "mse" or A >= 3) and squash in GAUSS_SQUASH
-        d0, d1, d2 = mu.shape[:3]
-        n = d0 * d1 * d2
-        ts = [t.contiguous() for t in (logp_old, adv, active, v_target)]
-        act, tgt = action.contiguous(), target.contiguous()
-        vo = values_old.contiguous() if values_old is not None else None
-        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == mu.shape[:3]
-        assert all(t.shape == mu.shape and t.dtype == torch.float32 for t in (act, tgt)) and mu.stride(3) == 1
-        dev = mu.device
-        _kick_args_ok(sums, diag, dev)
-        ls = ls_raw.detach()
-        if ls.dim() == 1:            # param mode: one vector, stride 0 over the rows
-            assert ls.shape == (A,)
-            ls = ls.contiguous()
-            g_ls = torch.empty(A, dtype=torch.float32, device=dev)
-            lstr = (0, 0, 0)
-        else:                        # state mode: per row, any strides over the first three dimensions (a time-major view)
-            assert ls.shape == mu.shape and ls.stride(3) == 1 and ls.dtype == torch.float32
-            g_ls = torch.empty_strided(ls.shape, ls.stride(), dtype=torch.float32, device=dev)
-            lstr = ls.stride()[:3]
-            assert any(lstr), "a per-row ls_raw needs a nonzero row stride"
-        asum = active.sum().reshape(1)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        g_mu = torch.empty_strided(mu.shape, mu.stride(), dtype=torch.float32, device=dev)
-        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.ppo_bc_loss_workspace(), dtype=torch.uint8, device=dev)
-        ms, vs = mu.stride(), values_now.stride()
-        _check(L.ppo_bc_loss_gauss_fwd_bwd(n, A, _ptr(mu), _ptr(g_mu), d1, d2, ms[0], ms[1], ms[2], _ptr(ls), _ptr(g_ls), lstr[0], lstr[1], lstr[2],
-                                           float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash], int(bool(fit_std)), int(bool(wrap0)),
-                                           BC_GAUSS_METRIC[metric], _ptr(act), _ptr(tgt), _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), _ptr(values_now),
-                                           vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[3]), _ptr(asum), float(epsilon), float(entropy_coef), float(coef),
-                                           int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(diag), _ptr(ws), _stream()),
-               "ppo_bc_loss_gauss_fwd_bwd")
-        ctx.save_for_backward(g_mu, g_ls, g_v)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, ga, gc):
-        g_mu, g_ls, g_v = ctx.saved_tensors
-        return (g_mu * ga, g_ls * ga, g_v * gc) + (None,) * 19
+        n, A, g_prob, prob_args = _strided_args(prob, values_now)
+        (lab, ac, vt), vo = _row_operands(n, (label, active, v_target), values_old)
+        assert 1 <= A <= 16
+        _sums_ok(sums, BC_SUMS, prob.device)
+        asum, losses, g_v, ws = _loss_tail(active, L.bc_loss_workspace(), values_now)
+        _check(L.bc_loss_cat_fwd_bwd(n, A, *prob_args, _ptr(lab), _ptr(ac), *_value_args(values_now), _ptr(vo), _ptr(vt), _ptr(asum),
+                                     float(epsilon), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(ws), _stream()),
+               "bc_loss_cat_fwd_bwd")
+        return losses, (g_prob, g_v)
+    return _Loss.apply(launch, 1, prob, values_now)
 
 
 def ppo_bc_loss_gauss(mu, ls_raw, action, target, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef,
@@ -1744,44 +1599,27 @@ def ppo_bc_loss_gauss(mu, ls_raw, action, target, values_now, logp_old, adv, act
     policy arguments as ppo_loss_gauss_ex; fit_std, wrap0 and metric as bc_loss_gauss; coef finite and >= 0.  sums: None, or a (3,) f64
     device tensor to which the call adds bc_loss_gauss's two sums and sum_rows active la_bc (the unweighted imitation loss); diag: see
     ppo_loss (with a per-row ls_raw the diagnostics exist at A = 3 and 4, the widths a policy of this feature has)."""
-    return _PPOBCLossGauss.apply(mu, ls_raw, values_now, action, target, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef,
-                                 coef, use_value_clip, log_std_min, log_std_max, squash, fit_std, wrap0, metric, sums, diag)
+    assert _own_rows(mu), "mu: " + _SHARED_ROWS
+    assert ls_raw.dim() == 1 or _own_rows(ls_raw), "ls_raw: " + _SHARED_ROWS
 
-
-class _PPOBCLossCat(torch.autograd.Function):
-    """ppo_bc_loss_cat: ppo_bc_loss_cat_fwd_bwd writes the losses and the gradients w.r.t. prob and the values in one pass."""
-
-    @staticmethod
-    def forward(ctx, prob, values_now, action, label, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef, use_value_clip,
-                sums=None, diag=None):
+    def launch():
+        _need_gpu(mu, "ppo_bc_loss_gauss")
         L = load_library()
-        _need_gpu(prob, "ppo_bc_loss_cat")
-        A = prob.shape[-1]
-        d0, d1, d2 = prob.shape[:3]
-        n = d0 * d1 * d2
-        ts = [t.contiguous() for t in (action, label, logp_old, adv, active, v_target)]
-        vo = values_old.contiguous() if values_old is not None else None
-        assert all(t.numel() == n and t.dtype == torch.float32 for t in ts) and values_now.shape == prob.shape[:3]
-        assert prob.stride(3) == 1 and prob.dtype == torch.float32 and 1 <= A <= 16
-        dev = prob.device
-        _kick_args_ok(sums, diag, dev)
-        asum = active.sum().reshape(1)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        g_prob = torch.empty_strided(prob.shape, prob.stride(), dtype=torch.float32, device=dev)    # the layout of prob (a time-major view)
-        g_v = torch.empty(values_now.shape, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.ppo_bc_loss_workspace(), dtype=torch.uint8, device=dev)
-        ps, vs = prob.stride(), values_now.stride()
-        _check(L.ppo_bc_loss_cat_fwd_bwd(n, A, _ptr(prob), _ptr(g_prob), d1, d2, ps[0], ps[1], ps[2], _ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]),
-                                         _ptr(ts[3]), _ptr(ts[4]), _ptr(values_now), vs[0], vs[1], vs[2], _ptr(vo), _ptr(ts[5]), _ptr(asum),
-                                         float(epsilon), float(entropy_coef), float(coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v),
-                                         _ptr(sums), _ptr(diag), _ptr(ws), _stream()), "ppo_bc_loss_cat_fwd_bwd")
-        ctx.save_for_backward(g_prob, g_v)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, ga, gc):
-        g_prob, g_v = ctx.saved_tensors
-        return (g_prob * ga, g_v * gc) + (None,) * 13
+        n, A, g_mu, mu_args = _strided_args(mu, values_now)
+        (lo, ad, ac, vt), vo = _row_operands(n, (logp_old, adv, active, v_target), values_old)
+        act, tgt = _like(mu, action), _like(mu, target)
+        assert metric in BC_GAUSS_METRIC and (metric == "mse" or A >= 3) and squash in GAUSS_SQUASH
+        _sums_ok(sums, KICK_SUMS, mu.device)
+        _sums_ok(diag, PPO_DIAG_SUMS, mu.device)
+        ls, g_ls, lstr = _log_std_args(ls_raw, mu)
+        asum, losses, g_v, ws = _loss_tail(active, L.ppo_bc_loss_workspace(), values_now)
+        _check(L.ppo_bc_loss_gauss_fwd_bwd(n, A, *mu_args, _ptr(ls), _ptr(g_ls), *lstr, float(log_std_min), float(log_std_max), GAUSS_SQUASH[squash],
+                                           int(bool(fit_std)), int(bool(wrap0)), BC_GAUSS_METRIC[metric], _ptr(act), _ptr(tgt), _ptr(lo), _ptr(ad),
+                                           _ptr(ac), *_value_args(values_now), _ptr(vo), _ptr(vt), _ptr(asum), float(epsilon), float(entropy_coef),
+                                           float(coef), int(bool(use_value_clip)), _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(diag), _ptr(ws),
+                                           _stream()), "ppo_bc_loss_gauss_fwd_bwd")
+        return losses, (g_mu, g_ls, g_v)
+    return _Loss.apply(launch, 2, mu, ls_raw, values_now)
 
 
 def ppo_bc_loss_cat(prob, action, label, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef,
@@ -1791,8 +1629,22 @@ def ppo_bc_loss_cat(prob, action, label, values_now, logp_old, adv, active, valu
     through the one normalisation both share; the critic loss and its gradient carry the bits of ppo_loss_prob.  Shapes and views as
     ppo_loss_prob; coef finite and >= 0.  sums: None, or a (3,) f64 device tensor to which the call adds bc_loss_cat's two sums (label
     hits, live rows) and sum_rows active (-log p[label]); diag: see ppo_loss."""
-    return _PPOBCLossCat.apply(prob, values_now, action, label, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, coef,
-                               use_value_clip, sums, diag)
+    assert _own_rows(prob), "prob: " + _SHARED_ROWS
+
+    def launch():
+        _need_gpu(prob, "ppo_bc_loss_cat")
+        L = load_library()
+        n, A, g_prob, prob_args = _strided_args(prob, values_now)
+        (act, lab, lo, ad, ac, vt), vo = _row_operands(n, (action, label, logp_old, adv, active, v_target), values_old)
+        assert 1 <= A <= 16
+        _sums_ok(sums, KICK_SUMS, prob.device)
+        _sums_ok(diag, PPO_DIAG_SUMS, prob.device)
+        asum, losses, g_v, ws = _loss_tail(active, L.ppo_bc_loss_workspace(), values_now)
+        _check(L.ppo_bc_loss_cat_fwd_bwd(n, A, *prob_args, _ptr(act), _ptr(lab), _ptr(lo), _ptr(ad), _ptr(ac), *_value_args(values_now), _ptr(vo),
+                                         _ptr(vt), _ptr(asum), float(epsilon), float(entropy_coef), float(coef), int(bool(use_value_clip)),
+                                         _ptr(losses), _ptr(g_v), _ptr(sums), _ptr(diag), _ptr(ws), _stream()), "ppo_bc_loss_cat_fwd_bwd")
+        return losses, (g_prob, g_v)
+    return _Loss.apply(launch, 1, prob, values_now)
 
 
 def bc_select(guide, follow, action, a_star_row, squash="clip", bound=0.999):
@@ -1816,13 +1668,6 @@ def bc_select(guide, follow, action, a_star_row, squash="clip", bound=0.999):
     else:
         assert guide.dim() == 2 and guide.dtype == torch.int32
         _check(L.n2n_bc_select(N, P, _ptr(guide), _ptr(follow), _ptr(action), _ptr(a_star_row), stride, _stream()), "n2n_bc_select")
-
-
-def ppo_loss(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip=True, diag=None):
-    """Masked-mean PPO policy loss and (clipped) value loss of a mini-batch, one launch with the gradients
-    (DHGN/mappo_parallel.py:692-706; csrc/mappo_ops.hip k_ppo_loss).  diag: None, or an (8,) f64 device tensor to which the call adds
-    the update diagnostics' sums over its live rows (csrc/ppo_diag.hpp) in the same two launches; losses and gradients keep their bytes."""
-    return _PPOLoss.apply(logp_now, entropy, values_now, logp_old, adv, active, values_old, v_target, epsilon, entropy_coef, use_value_clip, diag)
 
 
 def ppo_ratio(logp_now, logp_old):

@@ -227,6 +227,24 @@ def test_loss_wrappers_refuse_rows_that_share_storage():
         ops.ppo_loss_gauss_ex(shared, torch.zeros(A), own, *tail)
     with pytest.raises(AssertionError, match="ls_raw: rows share storage"):
         ops.ppo_loss_gauss_ex(own, shared, own, *tail)
+    # the teacher launches write g_prob / g_mu / g_ls the same way
+    bc_tail, kick_tail = (z, z, z, z, 0.2), (z, z, z, z, z, z, 0.2, 0.01, 0.5)
+    with pytest.raises(AssertionError, match="prob: rows share storage"):
+        ops.bc_loss_cat(shared, z, *bc_tail)
+    with pytest.raises(AssertionError, match="prob: rows share storage"):
+        ops.ppo_bc_loss_cat(shared, z, z, *kick_tail)
+    with pytest.raises(AssertionError, match="mu: rows share storage"):
+        ops.bc_loss_gauss(shared, torch.zeros(A), own, *bc_tail)
+    with pytest.raises(AssertionError, match="ls_raw: rows share storage"):
+        ops.bc_loss_gauss(own, shared, own, *bc_tail)
+    with pytest.raises(AssertionError, match="mu: rows share storage"):
+        ops.ppo_bc_loss_gauss(shared, torch.zeros(A), own, own, *kick_tail)
+    with pytest.raises(AssertionError, match="ls_raw: rows share storage"):
+        ops.ppo_bc_loss_gauss(own, shared, own, own, *kick_tail)
+    for call in (lambda: ops.bc_loss_cat(own, z, *bc_tail), lambda: ops.ppo_bc_loss_cat(own, z, z, *kick_tail),
+                 lambda: ops.bc_loss_gauss(own, own, own, *bc_tail), lambda: ops.ppo_bc_loss_gauss(own, own, own, own, *kick_tail)):
+        with pytest.raises(RuntimeError, match="GPU only"):
+            call()
     one = torch.full((1, 1, d2, A), 0.2).expand(1, 1, d2, A)        # (a stride over a dimension of one entry is never used)
     assert ops._own_rows(own) and ops._own_rows(one) and ops._own_rows(own.permute(1, 0, 2, 3)) and not ops._own_rows(shared)
     with pytest.raises(RuntimeError, match="GPU only"):             # a tensor with rows of its own gets as far as the device check

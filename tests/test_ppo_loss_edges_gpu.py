@@ -173,7 +173,7 @@ def _diag_and_repeat(c, value_clip, out, tag, view="time_major"):
 def _teacher(c, value_clip, out, tag, ref=None):
     """ppo_bc_loss_gauss / ppo_bc_loss_cat at coef 0 on the same rows: the critic loss and g_v are the PPO launch's bytes, the actor
     outputs lie within the tolerances of checks 2-3 of tests/test_kickstart_gpu.py; with ref, they are also held to the restatement
-    element by element (these launches have their own copies of the two clamp rules)"""
+    element by element (the two clamp rules are the PPO launch's: cat_pass, gauss_ls_pass)"""
     t = _run(c, value_clip, teacher=True)
     if ref is not None:
         _each_all(t, ref, tag + " teacher")
