@@ -220,6 +220,18 @@ def _rows_ok(t):
     return t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= t[0].numel())
 
 
+def _ld_ok(t):
+    """a 2-D operand as the kernels' entry points take it: unit column stride, rows at least a row length apart in multiples of 4 floats
+    (a gradient broadcast over rows, as y.sum(0) sends back, has a row stride of 0), 16-byte aligned"""
+    return t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+
+
+def _dense16(t):
+    """t dense and 16-byte aligned (contiguous() alone keeps a dense tensor that starts off the boundary)"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 _workspaces = {}
 
 
@@ -277,7 +289,7 @@ class _MsgAgg(torch.autograd.Function):
         p, q, e, adj, kvalid, W, b = ctx.saved_tensors
         adj_mode, q_div = ctx.meta
         E, din = W.shape
-        gout = gout.contiguous()
+        gout = _dense16(gout)     # the kernels read the [E] vectors with wide loads
         dW, db = torch.empty_like(W), torch.empty_like(b)
         ws = _workspace(p.device, E, din)
         _msg_call("bwd", L, p, q, e, adj, kvalid, W, b, adj_mode, q_div, _ptr(gout), E, (_ptr(dW), _ptr(db), _ptr(ws)))
@@ -440,7 +452,7 @@ class _MsgAgg3(torch.autograd.Function):
         mode, mode_o, q_div = ctx.meta
         R, P = p.shape[0], p.shape[1]
         E = W0.shape[0]
-        gout = gout.contiguous()
+        gout = _dense16(gout)     # the kernels read the [E] vectors with wide loads
         slot = lambda r: C.c_void_p(gout.data_ptr() + 4 * r * E)
         grads = []
         for r, (q, ee, adj, kv, W, b, m, qd) in enumerate(((p, e2, adj_p, None, W0, b0, mode, 1), (e, None, adj_e, None, W1, b1, mode, 1),
@@ -504,7 +516,7 @@ class _MsgAgg3Pair(torch.autograd.Function):
         mode_o, q_div = ctx.meta
         R, P = p.shape[0], p.shape[1]
         E = W0.shape[0]
-        ga, gc = ga.contiguous(), gc.contiguous()
+        ga, gc = _dense16(ga), _dense16(gc)     # the kernels read the [E] vectors with wide loads
         slot = lambda g, r: C.c_void_p(g.data_ptr() + 4 * r * E)
         grads = []
         for r, (q, ee, adj, W, b) in enumerate(((p, e2, adj_p, W0, b0), (e, None, adj_e, W1, b1))):
@@ -801,8 +813,7 @@ def _wgrad_ok(a, b):
     return (a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 2 and b.dim() == 2
             and a.shape[0] == b.shape[0] and a.shape[0] >= WGRAD_MIN_ROWS
             and a.shape[1] % 128 == 0 and b.shape[1] % 128 == 0 and a.shape[1] <= 1024 and b.shape[1] <= 1024
-            and a.stride(1) == 1 and b.stride(1) == 1 and a.stride(0) % 4 == 0 and b.stride(0) % 4 == 0
-            and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0)
+            and _ld_ok(a) and _ld_ok(b))
 
 
 def wgrad(a, b, out=None, accumulate=False):
@@ -938,7 +949,7 @@ SKINNY_MIN_ROWS = 4096
 def _skinny_ok(s, x):
     return (s.is_cuda and s.dtype == torch.float32 and x.dtype == torch.float32 and s.dim() == 2 and x.dim() == 2 and s.shape[0] == x.shape[0]
             and s.shape[0] >= SKINNY_MIN_ROWS and 1 <= s.shape[1] <= SKINNY_MAX and x.shape[1] % 64 == 0 and 64 <= x.shape[1] <= 1024
-            and s.stride(1) == 1 and x.stride(1) == 1)
+            and s.stride(1) == 1 and x.stride(1) == 1 and s.stride(0) >= s.shape[1] and x.stride(0) >= x.shape[1])
 
 
 def wgrad_skinny(s, x, transposed=False, colsum_x=False, colsum_s=False):
@@ -1068,9 +1079,11 @@ class _Linear(torch.autograd.Function):
         want_db = bool(ctx.bias_kind and ctx.needs_input_grad[2])
         if ctx.relu:  # relu'(pre-activation) from the saved output; with a 1-D bias its gradient comes out of the same pass
             if ctx.y_link is not None and ctx.y_link.db is not None:
-                # the consumer's input-gradient GEMM applied relu' and summed the columns (ReluLink)
+                # the consumer's input-gradient GEMM applied relu' and summed the columns (ReluLink); taken whether or not the bias
+                # gradient is wanted, so that the link never carries sums from one backward into the next
+                cs = ctx.y_link.take()
                 if want_db and ctx.bias_kind == 1:
-                    db = ctx.y_link.take().view(-1, W.shape[0]).sum(0)
+                    db = cs.view(-1, W.shape[0]).sum(0)
             elif want_db and ctx.bias_kind == 1:
                 g, db = relu_bwd_colsum(g, y)
             else:
@@ -1140,7 +1153,7 @@ def input_grad_masked(g2, W, y, mask_cols, bits=None):
         return None
     Wt = W.detach().t().contiguous()
     for t in (g2, y):
-        if t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+        if not _ld_ok(t):
             return None
     L = load_library()
     R = g2.shape[0]
@@ -1317,7 +1330,7 @@ class _FcraHop(torch.autograd.Function):
         if fused is not None:
             dcat, cs = fused
             ga, dbagg = dcat[:, :E], cs[:E]
-            if ctx.h_link is not None:
+            if ctx.h_link is not None and ctx.needs_input_grad[1]:    # (a frozen previous hop has no backward that would take it)
                 ctx.h_link.db = cs[E:]
         else:
             dcat = input_grad(gin, Wf)
@@ -1789,7 +1802,7 @@ class _GRULayer(torch.autograd.Function):
         x, h0, w_ih, w_hh, out, save = ctx.saved_tensors
         T, B, I = ctx.dims
         H = w_hh.shape[1]
-        dout = dout.contiguous()
+        dout = _dense16(dout)
         dgi = torch.empty((T * B, 3 * H), dtype=x.dtype, device=x.device)   # rows in x's order
         dh_direct = torch.empty((B, H), dtype=x.dtype, device=x.device)
         dcarry = None
@@ -1883,7 +1896,7 @@ def split_linear_ok(x, W, out=None, addend=None, mode=None, shapes=None):
             or tuple(W.shape) not in (SPLIT_LINEAR_SHAPES if shapes is None else shapes)):
         return False
     for t in (x, W) + ((out,) if out is not None else ()) + ((addend,) if addend is not None else ()):
-        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+        if t.dtype != torch.float32 or t.dim() != 2 or not _ld_ok(t):
             return False
     return x.shape[1] == W.shape[1]
 
@@ -1933,7 +1946,7 @@ def encoder_tail_ok(m3, w_agg, b_agg, Ws, out):
     if tuple(w_agg.shape) != (128, 128) or not w_agg.is_contiguous() or b_agg is None or tuple(b_agg.shape) != (128,) or not b_agg.is_contiguous():
         return False
     for t in (m3, w_agg, Ws, out):
-        if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+        if t.dtype != torch.float32 or not _ld_ok(t):
             return False
     if b_agg.dtype != torch.float32 or b_agg.data_ptr() % 16:
         return False
@@ -1978,7 +1991,7 @@ def encoder_tail_train_ok(m3, w_agg, b_agg, Ws, addend):
     if tuple(w_agg.shape) != (128, 128) or not w_agg.is_contiguous() or b_agg is None or tuple(b_agg.shape) != (128,) or not b_agg.is_contiguous():
         return False
     for t in (m3, w_agg, Ws, addend):
-        if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+        if t.dtype != torch.float32 or not _ld_ok(t):
             return False
     if b_agg.dtype != torch.float32 or b_agg.data_ptr() % 16:
         return False
@@ -2027,8 +2040,8 @@ class _EncoderTailTrain(torch.autograd.Function):
     def backward(ctx, g):
         m3, emb, bits, w_agg, Ws = ctx.saved_tensors
         g2 = g.reshape(-1, 128)
-        if g2.stride(1) != 1 or g2.stride(0) % 4 or g2.data_ptr() % 16:
-            g2 = g2.contiguous()
+        if not _ld_ok(g2):
+            g2 = _dense16(g2)
         ga, d_m3, cs = encoder_tail_train_bwd(g2, Ws, w_agg, bits)
         dWs = wgrad(g2, emb) if ctx.needs_input_grad[3] else None
         dWa = wgrad(ga.view(-1, 128), m3.view(-1, 128)) if ctx.needs_input_grad[1] else None
@@ -2162,7 +2175,7 @@ class _GRULayerMulti(torch.autograd.Function):
         for k in range(n):
             x, h0, w_ih, w_hh, out, save = sv[6 * k: 6 * k + 6]
             dev, dt, B = x.device, x.dtype, Bs[k]
-            dout = douts[k].contiguous()
+            dout = _dense16(douts[k])
             dgi = torch.empty((T * B, 3 * H), dtype=dt, device=dev)
             dgh = None if split else torch.empty((T, B, 3 * H), dtype=dt, device=dev)
             dnr = torch.empty((T, B, H), dtype=dt, device=dev) if split else None

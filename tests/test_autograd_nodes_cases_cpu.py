@@ -1,0 +1,196 @@
+"""tests/autograd_nodes_cases.py checked on the host: each restatement with masks reproduces torch autograd of the plain ReLU network in
+f64, the case tables are well formed, and the nodes of ops.py that accept host tensors (ops.linear, ops.linear_skinny: their torch
+routes) give the restatement's gradients under every gradient subset; ops.gru refuses host tensors."""
+import pytest
+import torch
+
+from tests import autograd_nodes_cases as cases
+
+MAKERS = {
+    "linear": lambda: cases.make_linear(69),
+    "linear_addend": lambda: cases.make_linear_addend(33),
+    "linear_nobias": lambda: cases.make_linear_nobias(33),
+    "skinny_in": lambda: cases.make_skinny_in(33),
+    "skinny_out": lambda: cases.make_skinny_out(33),
+    "chain": lambda: cases.make_chain(69),
+    "hops": lambda: cases.make_hops(33),
+    "gru": lambda: cases.make_gru(3, 17),
+    "gru_multi": lambda: cases.make_gru_multi(2, (15, 17, 16)),
+    "hop_gru": lambda: cases.make_hop_gru(11, 3),
+    "tail_hop": lambda: cases.make_tail_hop(23),
+}
+
+
+def _rel(a, b):
+    s = float(b.abs().max())
+    return float((a - b).abs().max()) / s if s > 0 else float((a - b).abs().max())
+
+
+@pytest.mark.parametrize("node", sorted(MAKERS))
+def test_restatement_with_masks_is_the_plain_relu_network(node):
+    """fed the masks of torch's fp32 evaluation on the CPU -- which, for the seeds chosen, take every decision as the f64 network does;
+    that is asserted, so this half can never fall away unnoticed -- and the plain f64 network's own masks, the masked restatement gives
+    the plain network's output and gradients to 1e-12"""
+    t = MAKERS[node]()
+    y, grads, masks = cases.evaluate(node, t)
+    assert set(grads) == set(cases.grad_names(node, t)) and all(g is not None and float(g.abs().max()) > 0 for g in grads.values())
+    _, _, m32 = cases.evaluate(node, t, None, torch.float32)
+    bad, tot = cases.mask_mismatch(m32, masks)
+    assert bad == 0, (node, bad, tot, "choose another seed: the fp32 evaluation takes a relu decision the other way")
+    for m in (masks, m32):
+        if not m:
+            continue
+        y2, g2, seen = cases.evaluate(node, t, {k: v.to(torch.float32) for k, v in m.items()})
+        assert cases.mask_mismatch(seen, masks) == (0, tot)
+        for a, b in zip(y2, y):
+            assert _rel(a, b) <= 1e-12
+        for k in grads:
+            assert _rel(g2[k], grads[k]) <= 1e-12, (node, k)
+    if masks:    # about a third of the activations are negative: a wrong mask would show
+        frac = sum(float((~v).sum()) for v in masks.values()) / tot
+        assert 0.05 < frac < 0.6, (node, frac)
+
+
+GPU_SHAPES = ([(n, (lambda n=n, r=r: MAKERS_AT[n](r)), r) for n in ("linear", "chain") for r in cases.LINEAR_ROWS]
+              + [("hops", (lambda r=r: cases.make_hops(r // cases.HOP_P)), r) for r in cases.HOP_ROWS]
+              + [("hop_gru", (lambda e=e, T=T: cases.make_hop_gru(e, T)), (e, T)) for e, T in ((1, 2), (11, 3))]
+              + [("tail_hop", (lambda R=R: cases.make_tail_hop(R)), R) for R in (1, 11, 33)])
+MAKERS_AT = {"linear": cases.make_linear, "chain": cases.make_chain}
+
+
+@pytest.mark.parametrize("node, make, shape", GPU_SHAPES, ids=[f"{n}-{s}" for n, _, s in GPU_SHAPES])
+def test_seeds_stay_within_the_mask_cap_at_every_gpu_shape(node, make, shape):
+    """at every shape the GPU file runs a node with a ReLU at, torch's own fp32 evaluation differs from the f64 network in at most MASK_CAP
+    of the relu decisions, and about a third of the activations are negative"""
+    t = make()
+    _, _, masks = cases.evaluate(node, t)
+    _, _, m32 = cases.evaluate(node, t, None, torch.float32)
+    bad, tot = cases.mask_mismatch(m32, masks)
+    assert bad <= cases.MASK_CAP * tot, (node, shape, bad, tot)
+    frac = sum(float((~v).sum()) for v in masks.values()) / tot
+    assert 0.05 < frac < 0.6, (node, shape, frac)
+
+
+def test_a_wrong_mask_moves_the_gradients():
+    """the negative control of the test above: one flipped decision is seen"""
+    t = cases.make_linear(33)
+    _, grads, masks = cases.evaluate("linear", t)
+    m = {"y": masks["y"].clone()}
+    m["y"][5, 7] = ~m["y"][5, 7]
+    _, g2, _ = cases.evaluate("linear", t, m)
+    assert _rel(g2["W"], grads["W"]) > 1e-6
+
+
+@pytest.mark.parametrize("node", sorted(MAKERS))
+def test_subset_tables_are_well_formed(node):
+    t = MAKERS[node]()
+    names = cases.grad_names(node, t)
+    subs = cases.subsets(node, t, cases.CHAIN_PRODUCERS.get(node))
+    assert subs["all"] == frozenset(names) and len(subs) >= len(names) + 3
+    for label, s in subs.items():
+        assert s and s <= frozenset(names), (node, label)
+    assert all(f"frozen:{k}" in subs and k not in subs[f"frozen:{k}"] for k in names)
+    assert subs["inputs_only"] | subs["parameters_only"] == subs["all"] and not (subs["inputs_only"] & subs["parameters_only"])
+    if node in cases.CHAIN_PRODUCERS:
+        assert subs["producer_frozen"] | subs["consumer_frozen"] == subs["all"] and not (subs["producer_frozen"] & subs["consumer_frozen"])
+        assert set(cases.CHAIN_PRODUCERS[node]) <= set(names)
+    for k in cases.NODES[node][1]:       # stored data: in the case, never trained
+        assert k in t and k not in names
+
+
+def test_shape_tables():
+    assert cases.LINEAR_ROWS == (1, 31, 32, 33, 69) and cases.HOP_ROWS == tuple(r * cases.HOP_P for r in (1, 11, 33))
+    assert len(cases.gru_shapes()) == 12 and all(a == 0 or (B % a == 0 and B // a in cases.GRU_B) for _, B, a in cases.gru_shapes())
+    assert cases.LAYOUTS == ("dense", "column_block", "transposed", "off_by_4_bytes", "row_broadcast")
+
+
+def test_threshold_cases_name_switches_of_ops_and_lie_on_both_sides():
+    """every threshold is an integer switch of ops.py whose default lies above the test shapes (so forcing it is what reaches the kernel).
+    The *_ok predicates ask for a device tensor before they look at the rows (a meta or host tensor is refused whatever the threshold,
+    which is asserted here), so which side R and R + 1 lie on is asserted on the GPU
+    (tests/test_autograd_nodes_gpu.py::test_both_sides_of_each_row_threshold): from _wgrad_ok for WGRAD_MIN_ROWS, _skinny_ok for
+    SKINNY_MIN_ROWS, input_grad_masked for MASKED_GRAD_MIN_ROWS and encoder_tail_train_ok for ENCODER_TAIL_TRAIN_MIN_ROWS;
+    RELU_BWD_MIN_ROWS and PERSISTENT_GRU_MIN_T are compared inline (relu_bwd_colsum, _GRULayer.forward) and have no predicate: their
+    side shows in the entry-point census alone."""
+    from distributed_multi_agent_reinforcement_learning_amd import ops
+    seen = set()
+    for name, node, R in cases.threshold_cases():
+        v = getattr(ops, name)
+        assert isinstance(v, int) and node in cases.NODES
+        if name != "PERSISTENT_GRU_MIN_T":
+            assert v > max(cases.LINEAR_ROWS), name
+        seen.add(name)
+    assert seen == {"WGRAD_MIN_ROWS", "RELU_BWD_MIN_ROWS", "SKINNY_MIN_ROWS", "MASKED_GRAD_MIN_ROWS", "ENCODER_TAIL_TRAIN_MIN_ROWS", "PERSISTENT_GRU_MIN_T"}
+    # the host side of the predicates: a host tensor is never routed to a kernel, whatever the threshold
+    a, b = torch.zeros(33, 128), torch.zeros(33, 128)
+    old = ops.WGRAD_MIN_ROWS, ops.SKINNY_MIN_ROWS
+    try:
+        ops.WGRAD_MIN_ROWS = ops.SKINNY_MIN_ROWS = 1
+        assert not ops._wgrad_ok(a, b) and not ops._skinny_ok(a[:, :4], b)
+        assert not ops._wgrad_ok(a.to("meta"), b.to("meta")) and not ops._skinny_ok(a[:, :4].to("meta"), b.to("meta"))
+        assert ops.input_grad_masked(a, torch.zeros(128, 384), torch.zeros(33, 384), 384) is None
+    finally:
+        ops.WGRAD_MIN_ROWS, ops.SKINNY_MIN_ROWS = old
+
+
+def _product(node, t):
+    """the node through ops.py on host tensors -> output"""
+    from distributed_multi_agent_reinforcement_learning_amd import ops
+    if node == "linear":
+        return ops.linear(t["x"], t["W"], t["b"], relu=True)
+    if node == "linear_addend":
+        return ops.linear(t["x"], t["W"], t["add"])
+    if node == "linear_nobias":
+        return ops.linear(t["x"], t["W"])
+    if node in ("skinny_in", "skinny_out"):
+        return ops.linear_skinny(t["x"], t["W"], t["b"])
+    if node == "chain":
+        link = ops.ReluLink()
+        emb = ops.linear(t["m3"], t["Wa"], t["ba"], relu=True, y_link=link)
+        y = ops.linear(emb.reshape(-1, 3 * cases.E), t["Ws"], t["add"].clone(), consume_addend=True, x_link=link)
+        assert link.db is None and link.bits is None
+        y.link, y.emb = link, emb
+        return y
+    raise KeyError(node)
+
+
+HOST_NODES = ("linear", "linear_addend", "linear_nobias", "skinny_in", "skinny_out", "chain")
+
+
+@pytest.mark.parametrize("node", HOST_NODES)
+def test_host_routes_give_the_restatement_gradients_under_every_subset(node):
+    """ops.linear / ops.linear_skinny on host tensors (their torch routes, tests/test_ops_cpu_fallbacks.py): a frozen tensor gets None, a
+    trained one the f64 gradient within 4 noise + 2e-5 scale, bit for bit the all-on run's; no link keeps a db"""
+    t = MAKERS[node]()
+    subs = cases.subsets(node, t, cases.CHAIN_PRODUCERS.get(node))
+    ref, base = None, None
+    for label in ["all"] + [k for k in subs if k != "all"]:
+        leaves = {k: (v.clone().requires_grad_(k in subs[label]) if k in subs["all"] else v) for k, v in t.items()}
+        y = _product(node, leaves)
+        masks = {"y": y.detach() > 0} if node == "linear" else ({"emb": y.emb.detach() > 0} if node == "chain" else {})
+        (y * t["gout"]).sum().backward()
+        if ref is None:
+            ref = cases.Reference(node, t, masks)
+            assert ref.mismatch[0] <= cases.MASK_CAP * max(ref.mismatch[1], 1)
+            assert float((y.detach().double() - ref.plain_y[0]).abs().max()) <= cases.FWD_REL * float(ref.plain_y[0].abs().max())
+            base = {k: leaves[k].grad.clone() for k in subs["all"]}
+        for k in subs["all"]:
+            g = leaves[k].grad
+            if k not in subs[label]:
+                assert g is None, (node, label, k)
+                continue
+            assert g is not None, (node, label, k)
+            assert ref.ratio(k, g) <= 1.0, (node, label, k, ref.ratio(k, g))
+            assert torch.equal(g, base[k]), (node, label, k)
+        if node == "chain":
+            assert y.link.db is None, label
+
+
+def test_gru_nodes_refuse_host_tensors():
+    from distributed_multi_agent_reinforcement_learning_amd import ops
+    t = cases.make_gru(2, 15)
+    m = torch.nn.GRU(cases.H, cases.H, num_layers=2)
+    with pytest.raises(RuntimeError, match="GPU only"):
+        ops.gru(t["x"], t["h0"], m)
+    with pytest.raises(RuntimeError, match="GPU only"):
+        ops.gru_multi([t["x"], t["x"]], [t["h0"], t["h0"]], [m, m])

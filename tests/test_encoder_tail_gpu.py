@@ -5,6 +5,8 @@ a captured graph, and through DHGN.forward_pair."""
 import pytest
 import torch
 
+from tests.helpers import no_gc_during_capture
+
 pytestmark = pytest.mark.gpu
 
 E = 128
@@ -145,7 +147,7 @@ def test_encoder_tail_graph_replay_equals_eager(split_mode):
         torch.cuda.current_stream().wait_stream(s)
         static.copy_(add)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with no_gc_during_capture(), torch.cuda.graph(g):
             ops.encoder_tail(m3, w_agg, b_agg, Ws, static)
         static.copy_(add)
         g.replay()

@@ -6,6 +6,8 @@ strided operands, in a captured graph, through DHGN.encoder_pair_train, and with
 import pytest
 import torch
 
+from tests.helpers import no_gc_during_capture
+
 pytestmark = pytest.mark.gpu
 
 E = 128
@@ -216,7 +218,7 @@ def test_three_launches_give_identical_bytes_and_a_graph_replays_them(split_upda
             both()                                   # warm-up on the capture stream (the launches' one-time attribute calls)
         torch.cuda.current_stream().wait_stream(s)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with no_gc_during_capture(), torch.cuda.graph(graph):
             both()
         for t in (y, emb, ga, d_m3, cs):
             t.fill_(CANARY)

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import no_gc_during_capture
+
 from tests import evader_cases as ec
 
 pytestmark = pytest.mark.gpu
@@ -193,7 +195,7 @@ def test_captured_evader_and_step_replay_like_eager(which):
         cap.step(act)
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with no_gc_during_capture(), torch.cuda.graph(graph):
         graphed.evader_step()
         graphed.step(act)
     for _ in range(K):

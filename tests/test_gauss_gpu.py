@@ -6,6 +6,8 @@ import copy
 import numpy as np
 import pytest
 import torch
+
+from tests.helpers import no_gc_during_capture
 import torch.nn.functional as F
 
 from tests import e3d_features_ref
@@ -93,7 +95,7 @@ def test_gauss_head_sample_graph_replay_equals_eager():
     torch.cuda.synchronize()
     cg.fill_(1 << 40)
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g), torch.no_grad():
+    with no_gc_during_capture(), torch.cuda.graph(g), torch.no_grad():
         ops.gauss_head_sample(feat, W, b, ls, 4, cg, ticket, out)
     cg.fill_(1 << 40)
     for k in range(3):

@@ -7,6 +7,8 @@ import copy
 import numpy as np
 import pytest
 import torch
+
+from tests.helpers import no_gc_during_capture
 import torch.nn.functional as F
 
 from tests import gauss_sd_ref
@@ -226,7 +228,7 @@ def test_head_ex_graph_replay_equals_eager():
     torch.cuda.current_stream().wait_stream(s)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g), torch.no_grad():
+    with no_gc_during_capture(), torch.cuda.graph(g), torch.no_grad():
         ops.gauss_head_sample_ex(feat, W, b, src, 4, cg, ticket, out, **kw)
     cg.fill_(1 << 40)
     for k in range(3):

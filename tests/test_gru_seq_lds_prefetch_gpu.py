@@ -10,6 +10,8 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.helpers import no_gc_during_capture
+
 pytestmark = pytest.mark.gpu
 
 H = 128
@@ -213,7 +215,7 @@ def test_split_backward_through_ops_and_in_a_captured_graph(T, B, agents):
     torch.cuda.current_stream().wait_stream(stream)
     graph = torch.cuda.CUDAGraph()
     holder = {}
-    with torch.cuda.graph(graph):
+    with no_gc_during_capture(), torch.cuda.graph(graph):
         holder["o"] = _launch_captured(T, recs, agents, "dgh" if agents else "mixed")
     for o in holder["o"]:
         for nm, a in o.items():

@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import no_gc_during_capture
+
 from tests import sampling_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -248,7 +250,7 @@ def test_samplers_replay_in_a_captured_graph():
     a_c, lp_c = torch.empty(R, dtype=torch.int32, device="cuda"), torch.empty(R, device="cuda")
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph):
+    with no_gc_during_capture(), torch.no_grad(), torch.cuda.graph(graph):
         ops.head_sample(feat_d, W_d, b_d, sh, c_head, ticket, (a_h, lp_h))
         ops.categorical_sample(p_d, sc, 0, counter=c_cat, out=(a_c, lp_c))
     torch.cuda.synchronize()

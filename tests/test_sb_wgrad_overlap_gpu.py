@@ -14,6 +14,8 @@ bound; canary floats behind C and behind the workspace are untouched; a captured
 import pytest
 import torch
 
+from tests.helpers import no_gc_during_capture
+
 from tests.test_sb_wgrad_pc_gpu import _check, _lib, _operands
 
 pytestmark = pytest.mark.gpu
@@ -86,7 +88,7 @@ def test_sb_wgrad_pipeline_edges(form, M, N, chunks, r):
         run()
     torch.cuda.current_stream().wait_stream(s)
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    with no_gc_during_capture(), torch.cuda.graph(g):
         run()
     run.c.fill_(CANARY)
     g.replay()

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import no_gc_during_capture
+
 from tests import e3d_features_ref
 from tests import evader_cases as ec
 from tests import guidance_cases as gc
@@ -494,7 +496,7 @@ def test_captured_evader_step_and_record_replay_like_eager(case):
     torch.cuda.current_stream().wait_stream(side)
     graphed, g_graphed, io_graphed = make()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with no_gc_during_capture(), torch.cuda.graph(graph):
         calls(graphed, io_graphed)
     for _ in range(K):
         graph.replay()
