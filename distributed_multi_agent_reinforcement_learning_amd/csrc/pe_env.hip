@@ -57,6 +57,14 @@ struct SqThr {
     int32_t rw_shift;   // log2 of the raser row length in words when it is a power of two, else -1
 };
 __host__ __device__ inline int raser_row_words(int O) { return (((O + 31) >> 5) + 3) & ~3; }  // 16-byte aligned rows
+// The kernel's own run-time choices, stated once for the device code and for the host's launch plan (pe_diag_launch_plan):
+// dev_observe gathers the P LiDAR rows with one load per lane when they fit the wave; k_tick stages the grid through registers
+// requested up front ("wide", at most 4 x 64 x 16 bytes) or through copy_in, whose width follows size and source alignment.
+__host__ __device__ inline bool obs_one_load(int P, int RW) { return P * RW <= WAVE; }
+__host__ __device__ inline bool grid_wide(int WH) { return (WH & 15) == 0 && WH <= 4096; }
+__host__ __device__ inline int copy_in_width(int nbytes, uintptr_t src) {
+    return ((nbytes & 15) == 0 && (src & 15) == 0) ? 16 : ((nbytes & 3) == 0 && (src & 3) == 0) ? 4 : 1;
+}
 
 // One wave per workgroup: the lanes only ever exchange data with lanes of their own wave.  A wave's LDS and vector-memory
 // instructions execute in program order through the same LDS / L1, so a wavefront-scope fence (no s_waitcnt, no s_barrier)
@@ -177,11 +185,12 @@ __host__ __device__ inline size_t lds_layout(const pe_config &c, bool with_obs, 
 
 // ---- coalesced copies between HBM records and LDS ------------------------------------------------------
 __device__ __forceinline__ void copy_in(void *dst, const void *src, int nbytes, int lane) {
-    if ((nbytes & 15) == 0 && (((uintptr_t)src) & 15) == 0) {
+    const int width = copy_in_width(nbytes, (uintptr_t)src);
+    if (width == 16) {
         const uint4 *s = (const uint4 *)src;
         uint4 *d = (uint4 *)dst;
         for (int i = lane; i < (nbytes >> 4); i += WAVE) d[i] = s[i];
-    } else if ((nbytes & 3) == 0 && (((uintptr_t)src) & 3) == 0) {
+    } else if (width == 4) {
         const uint32_t *s = (const uint32_t *)src;
         uint32_t *d = (uint32_t *)dst;
         for (int i = lane; i < (nbytes >> 2); i += WAVE) d[i] = s[i];
@@ -387,7 +396,7 @@ template <bool FAST8>
 __device__ void dev_observe(const pe_config &c, const SqThr &th, const Lds &l, int lane, int env, const pe_obs_out &o, const uint32_t *raser_env) {
     const int P = c.P, O = c.O, RW = raser_row_words(O);
     uint32_t r_row = 0u;
-    const bool one_load = P * RW <= WAVE;
+    const bool one_load = obs_one_load(P, RW);
     const bool want_rows = o.o_adj || o.o_adj_bits;
     if (want_rows && one_load && lane < P * RW) {
         const int i = th.rw_shift >= 0 ? lane >> th.rw_shift : lane / RW, w = lane - i * RW;
@@ -781,7 +790,7 @@ __global__ __launch_bounds__(WAVE * WPB) void k_tick(const pe_config c, const pe
     // ---- ONE batch of global loads: every record this tick needs is requested before the first wait, so a wave pays the
     // HBM/L2 latency once instead of once per phase
     const uint8_t *gsrc = st.grid + (size_t)env * WH;
-    const bool wide = (WH & 15) == 0 && WH <= 4096;
+    const bool wide = grid_wide(WH);
     const int ng = WH >> 4;
     const uint4 *g4 = (const uint4 *)gsrc;
     const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
@@ -1008,51 +1017,82 @@ uint32_t div_magic20(uint32_t d, uint32_t n) {
     return M;
 }
 
+// Every run-time choice of a tick launch, made in ONE place: launch() / launch2() / launch3() pick their template instance and
+// their launch parameters from this record and pe_diag_launch_plan hands the same record to the tests (which kernel variant, how
+// many waves per workgroup, how much LDS, which of the kernel's wave-uniform branches the constants in SqThr select).
+struct LaunchPlan {
+    pe_launch_plan p;
+    SqThr th;
+};
+LaunchPlan plan_launch(const pe_config &c, bool obs, bool eva, bool replan) {
+    LaunchPlan L;
+    memset(&L, 0, sizeof L);
+    const bool with_replan = eva && replan;
+    const size_t lds_env = align16(lds_layout(c, obs, with_replan, nullptr, nullptr));
+    // four environments per workgroup unless the per-environment LDS is large (replan scratch, very large maps)
+    const bool fat = !with_replan && 4 * lds_env <= 48 * 1024;
+    L.p.wpb = fat ? 4 : 1;
+    L.p.lds_per_env = (int32_t)lds_env;
+    L.p.lds_bytes = (int32_t)(lds_env * L.p.wpb);
+    L.p.needs_attr = L.p.lds_bytes > 48 * 1024;
+    L.p.fast8 = c.P <= 8;
+    SqThr &th = L.th;
+    th.inv_def_tau = div_const_reciprocal(c.def_tau);
+    th.inv_eva_tau = div_const_reciprocal(c.eva_tau);
+    th.inv_six = div_const_reciprocal(6.0);
+    th.coll_le = sq_threshold(c.def_collision_radius, false);
+    th.comm_le = sq_threshold(c.def_comm_range, false);
+    th.sen_le = sq_threshold(c.def_sen_range, false);
+    th.evacoll_le = sq_threshold(c.eva_collision_radius, false);
+    th.res_lt = sq_threshold(c.resolution, true);
+    th.o4_magic = div_magic20((uint32_t)(c.O >> 2), (uint32_t)(c.P * (c.O >> 2)));
+    const int rw = raser_row_words(c.O);
+    th.rw_shift = -1;
+    for (int sft = 0; sft < 16; sft++)
+        if ((1 << sft) == rw) th.rw_shift = sft;
+    L.p.rw_shift = th.rw_shift;
+    L.p.o4_magic = th.o4_magic;
+    L.p.inv_def_tau = th.inv_def_tau;
+    L.p.inv_eva_tau = th.inv_eva_tau;
+    L.p.inv_six = th.inv_six;
+    L.p.one_load = obs_one_load(c.P, rw);
+    // grid records start 16-byte aligned (the state tensors are) and follow each other W*H bytes apart
+    L.p.grid_copy = grid_wide(c.W * c.H) ? PE_GRID_WIDE : copy_in_width(c.W * c.H, (uintptr_t)0);
+    L.p.tape_loop = c.tape_len > PE_TAPE_LDS;
+    return L;
+}
+
 template <bool STEP, bool OBS, bool EVA, bool REPLAN, bool FAST8, int WPB>
-int launch3(const pe_config *cfg, const pe_state *st, const int32_t *actions, const pe_step_out *so, const pe_obs_out *oo, void *stream) {
-    const size_t lds_env = align16(lds_layout(*cfg, OBS, EVA && REPLAN, nullptr, nullptr));
-    const size_t lds = lds_env * WPB;
+int launch3(const LaunchPlan &pl, const pe_config *cfg, const pe_state *st, const int32_t *actions, const pe_step_out *so, const pe_obs_out *oo,
+            void *stream) {
     auto kern = k_tick<STEP, OBS, EVA, REPLAN, FAST8, WPB>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (pl.p.needs_attr) {
+        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, pl.p.lds_bytes);
         if (e != hipSuccess) return (int)e;
     }
     pe_step_out s0;
     memset(&s0, 0, sizeof s0);
     pe_obs_out o0;
     memset(&o0, 0, sizeof o0);
-    SqThr th;
-    th.inv_def_tau = div_const_reciprocal(cfg->def_tau);
-    th.inv_eva_tau = div_const_reciprocal(cfg->eva_tau);
-    th.inv_six = div_const_reciprocal(6.0);
-    th.coll_le = sq_threshold(cfg->def_collision_radius, false);
-    th.comm_le = sq_threshold(cfg->def_comm_range, false);
-    th.sen_le = sq_threshold(cfg->def_sen_range, false);
-    th.evacoll_le = sq_threshold(cfg->eva_collision_radius, false);
-    th.res_lt = sq_threshold(cfg->resolution, true);
-    th.o4_magic = div_magic20((uint32_t)(cfg->O >> 2), (uint32_t)(cfg->P * (cfg->O >> 2)));
-    const int rw = raser_row_words(cfg->O);
-    th.rw_shift = -1;
-    for (int sft = 0; sft < 16; sft++)
-        if ((1 << sft) == rw) th.rw_shift = sft;
-    hipLaunchKernelGGL(kern, dim3((st->N + WPB - 1) / WPB), dim3(WAVE * WPB), lds, (hipStream_t)stream, *cfg, *st, actions, so ? *so : s0, oo ? *oo : o0, th,
-                       (int)lds_env);
+    hipLaunchKernelGGL(kern, dim3((st->N + WPB - 1) / WPB), dim3(WAVE * WPB), (size_t)pl.p.lds_bytes, (hipStream_t)stream, *cfg, *st, actions,
+                       so ? *so : s0, oo ? *oo : o0, pl.th, pl.p.lds_per_env);
     return (int)hipGetLastError();
 }
 
 template <bool STEP, bool OBS, bool EVA, bool REPLAN, bool FAST8>
-int launch2(const pe_config *cfg, const pe_state *st, const int32_t *actions, const pe_step_out *so, const pe_obs_out *oo, void *stream) {
-    // four environments per workgroup unless the per-environment LDS is large (replan scratch, very large maps)
-    const bool fat = !(EVA && REPLAN) && 4 * align16(lds_layout(*cfg, OBS, false, nullptr, nullptr)) <= 48 * 1024;
-    return fat ? launch3<STEP, OBS, EVA, REPLAN, FAST8, (EVA && REPLAN) ? 1 : 4>(cfg, st, actions, so, oo, stream)
-               : launch3<STEP, OBS, EVA, REPLAN, FAST8, 1>(cfg, st, actions, so, oo, stream);
+int launch2(const LaunchPlan &pl, const pe_config *cfg, const pe_state *st, const int32_t *actions, const pe_step_out *so, const pe_obs_out *oo,
+            void *stream) {
+    // the replan form never runs four waves per workgroup: no such instance is built
+    return pl.p.wpb == 4 ? launch3<STEP, OBS, EVA, REPLAN, FAST8, (EVA && REPLAN) ? 1 : 4>(pl, cfg, st, actions, so, oo, stream)
+                         : launch3<STEP, OBS, EVA, REPLAN, FAST8, 1>(pl, cfg, st, actions, so, oo, stream);
 }
 
 template <bool STEP, bool OBS, bool EVA, bool REPLAN>
 int launch(const pe_config *cfg, const pe_state *st, const int32_t *actions, const pe_step_out *so, const pe_obs_out *oo, void *stream) {
     if (OBS && !st->raser) return PE_ERR_NULL;
-    return cfg->P <= 8 ? launch2<STEP, OBS, EVA, REPLAN, true>(cfg, st, actions, so, oo, stream)
-                       : launch2<STEP, OBS, EVA, REPLAN, false>(cfg, st, actions, so, oo, stream);
+    const LaunchPlan pl = plan_launch(*cfg, OBS, EVA, REPLAN);
+    return pl.p.fast8 ? launch2<STEP, OBS, EVA, REPLAN, true>(pl, cfg, st, actions, so, oo, stream)
+                      : launch2<STEP, OBS, EVA, REPLAN, false>(pl, cfg, st, actions, so, oo, stream);
 }
 
 // the per-episode tables derived from the grid and the obstacle list: bidx, fresh meta / waypoint records, raser rows
@@ -1533,6 +1573,14 @@ int pe_diag_norm2(int32_t n, const double *a, const double *b, double *out, doub
 // diagnostics (host only, no GPU needed): the comparison thresholds / reciprocals launch() hands to the tick kernel
 double pe_diag_sq_threshold(double r, int32_t strict) { return sq_threshold(r, strict != 0); }
 double pe_diag_div_reciprocal(double b) { return div_const_reciprocal(b); }
+// ... and everything else launch() chooses for a configuration and a launch form (the record the launcher itself launches from)
+int pe_diag_launch_plan(const pe_config *cfg, int32_t form, pe_launch_plan *out) {
+    if (!cfg || !out) return PE_ERR_NULL;
+    const int rc = pe_config_check(cfg);
+    if (rc) return rc;
+    *out = plan_launch(*cfg, (form & PE_FORM_OBS) != 0, (form & PE_FORM_EVA) != 0, (form & PE_FORM_REPLAN) != 0).p;
+    return 0;
+}
 
 const char *pe_error_string(int code) {
     if (code == PE_ERR_BAD_CONFIG) return "pe_env: configuration outside kernel limits";

@@ -57,6 +57,27 @@ class PeHostInitOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("grid", "obs_xy", "n_obs", "def_", "eva", "target", "tape")]
 
 
+class PeLaunchPlan(C.Structure):
+    """include/pe_env_diag.h pe_launch_plan"""
+    _fields_ = [(n, C.c_int32) for n in ("wpb", "lds_per_env", "lds_bytes", "needs_attr", "fast8", "rw_shift")] + \
+               [("o4_magic", C.c_uint32)] + [(n, C.c_int32) for n in ("one_load", "grid_copy", "tape_loop")] + \
+               [(n, C.c_double) for n in ("inv_def_tau", "inv_eva_tau", "inv_six")]
+
+
+FORM_STEP, FORM_OBS, FORM_EVA, FORM_REPLAN = 1, 2, 4, 8
+# the launch form of every entry point (pe_env_diag.h); evader_step and tick also exist with FORM_REPLAN
+FORMS = dict(observe=FORM_OBS, step=FORM_STEP, step_observe=FORM_STEP | FORM_OBS, evader_step=FORM_EVA, tick=FORM_STEP | FORM_OBS | FORM_EVA,
+             evader_step_replan=FORM_EVA | FORM_REPLAN, tick_replan=FORM_STEP | FORM_OBS | FORM_EVA | FORM_REPLAN)
+
+
+def launch_plan(pe_cfg, form):
+    """What the launcher chooses for this configuration and launch form (host only, no GPU): a dict of pe_launch_plan's fields."""
+    L = load_library()
+    p = PeLaunchPlan()
+    _check(L.pe_diag_launch_plan(C.byref(pe_cfg), int(FORMS.get(form, form)), C.byref(p)), "pe_diag_launch_plan")
+    return {n: getattr(p, n) for n, _ in PeLaunchPlan._fields_}
+
+
 EXPORTS = ("pe_config_check", "pe_tick_lds_bytes", "pe_env_load", "pe_env_observe", "pe_evader_step", "pe_env_step",
            "pe_env_demon", "pe_env_tick", "pe_env_step_observe", "pe_astar_batch", "pe_error_string")
 
@@ -89,6 +110,7 @@ def load_library():
         L.pe_env_step_observe.argtypes = [vp, vp, vp, vp, vp, vp]
         L.pe_astar_batch.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp]
         L.pe_diag_norm2.argtypes = [C.c_int32, vp, vp, vp, C.c_double, C.c_double, vp]
+        L.pe_diag_launch_plan.argtypes = [vp, C.c_int32, vp]
         L.pe_resetter_create.argtypes = [vp, vp, C.c_int32, vp]
         L.pe_resetter_create.restype = vp
         L.pe_resetter_destroy.argtypes = [vp]

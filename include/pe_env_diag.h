@@ -6,6 +6,8 @@
 #define PE_ENV_DIAG_H
 #include <stdint.h>
 
+#include "pe_env.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -17,6 +19,28 @@ int pe_diag_norm2(int32_t n, const double *a, const double *b, double *out, doub
 double pe_diag_sq_threshold(double r, int32_t strict);
 /* ... and the reciprocal it divides by a constant with (0 = the plain IEEE division is used). */
 double pe_diag_div_reciprocal(double b);
+
+/* Host only (no GPU): what the launcher chooses for a configuration and a launch form -- every run-time selected code path of the
+ * tick kernel.  The launcher itself launches from this record (csrc/pe_env.hip plan_launch), the kernel's own two choices
+ * (one_load, grid staging) are the same inline predicates, so the record cannot drift from what runs.
+ * form: OR of PE_FORM_*; the entry points are observe = OBS, step = STEP, step_observe = STEP|OBS, evader_step = EVA (|REPLAN),
+ * tick = STEP|OBS|EVA (|REPLAN). */
+enum { PE_FORM_STEP = 1, PE_FORM_OBS = 2, PE_FORM_EVA = 4, PE_FORM_REPLAN = 8 };
+enum { PE_GRID_WIDE = 0, PE_GRID_COPY16 = 16, PE_GRID_COPY4 = 4, PE_GRID_COPY1 = 1 };
+typedef struct pe_launch_plan {
+    int32_t wpb;            /* wavefronts (= environments) per workgroup: 4 or 1 */
+    int32_t lds_per_env;    /* bytes of LDS per environment (16-byte aligned) */
+    int32_t lds_bytes;      /* dynamic LDS of the launch = wpb * lds_per_env */
+    int32_t needs_attr;     /* lds_bytes > 48 KB: hipFuncAttributeMaxDynamicSharedMemorySize is raised first */
+    int32_t fast8;          /* P <= 8: the 8 x 8 lane tiles of dev_step / dev_observe */
+    int32_t rw_shift;       /* log2 of the raser row length in words, -1 = not a power of two (lane / RW) */
+    uint32_t o4_magic;      /* multiply-shift constant of idx / (O / 4), 0 = plain division */
+    int32_t one_load;       /* P * RW <= 64: the LiDAR rows are gathered with one load per lane (else a loop) */
+    int32_t grid_copy;      /* PE_GRID_*: registers up front (wide) or copy_in's 16 / 4 / 1-byte form */
+    int32_t tape_loop;      /* tape_len > 32: the tape's tail is staged by a second, looped copy */
+    double inv_def_tau, inv_eva_tau, inv_six;  /* div_const reciprocals, 0 = IEEE division */
+} pe_launch_plan;
+int pe_diag_launch_plan(const pe_config *cfg, int32_t form, pe_launch_plan *out);
 
 #ifdef __cplusplus
 }

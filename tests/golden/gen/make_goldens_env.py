@@ -3,6 +3,7 @@
 Runs the REAL reference (read-only under /root/reference, imported through the tiny shims in ./stubs) in the
 build container and writes small .npz fixtures under tests/golden/.  The reference never travels to the GPU
 box; only these data files do.  Usage:  python tests/golden/gen/make_goldens_env.py
+(--config-only: just the envcfg_trace_* fixtures recorded off the default configuration, CONFIG_JOBS below).
 """
 import os
 import random
@@ -18,9 +19,12 @@ refload.activate()
 OUT = os.path.dirname(HERE)
 
 
-def capture_trace(seed, P, W, H, blocks, variance, T, policy, save_raser):
+def capture_trace(seed, P, W, H, blocks, variance, T, policy, save_raser, overrides=None, late=None):
+    """overrides: {"section.key": value} of the reference's config.yaml, set before the environment is built.  late: the same, set
+    after reset() -- for values at which the reference's own placement loops never end (a communication range nobody is within, a
+    sensing range of 0); the agents' copies of the two ranges are set with them."""
     from environment.pursuit_evasion_game.pursuit_env import Pursuit_Env
-    cfg = refload.load_cfg(num_defender=P, map_size=(W, H), blocks=blocks, variance=variance, max_steps=T)
+    cfg = refload.load_cfg(num_defender=P, map_size=(W, H), blocks=blocks, variance=variance, max_steps=T, overrides=overrides)
     refload.seed_all(seed)
     env = Pursuit_Env(cfg)
     drawn = []
@@ -31,6 +35,10 @@ def capture_trace(seed, P, W, H, blocks, variance, T, policy, save_raser):
         drawn.append(tuple(env.target[0]))
     env.init_target = logged_init_target
     env.reset()
+    if late:
+        refload.set_dotted(cfg, late)
+        for d in env.defender_list:
+            d.sen_range, d.comm_range = cfg.defender.sen_range, cfg.defender.comm_range
     n_obs = len(env.boundary_map.obstacles)
     init = dict(
         grid=np.asarray(env.occupied_map.grid_map, np.uint8),
@@ -90,6 +98,12 @@ def capture_trace(seed, P, W, H, blocks, variance, T, policy, save_raser):
     out["drawn_targets"] = np.asarray(drawn, np.int32)  # [0] is the reset draw, the rest are mid-episode re-draws
     out["meta"] = np.asarray([seed, P, W, H, blocks, variance, T], np.int64)
     out["collision_flag"] = np.int32(bool(env.collision))
+    if overrides or late:
+        # the reference configuration values this trace was recorded at: at reset (cfg_*) and from then on (late_*)
+        out["cfg_keys"] = np.asarray(sorted(overrides or {}), dtype="U40")
+        out["cfg_vals"] = np.asarray([(overrides or {})[k] for k in sorted(overrides or {})], np.float64)
+        out["late_keys"] = np.asarray(sorted(late or {}), dtype="U40")
+        out["late_vals"] = np.asarray([(late or {})[k] for k in sorted(late or {})], np.float64)
     if save_raser:
         out["raser"] = np.packbits(np.asarray(env.raser_map, np.uint8).reshape(W * H, n_obs), axis=-1)
     return out
@@ -167,6 +181,8 @@ def main():
         ("env_trace_40x40_p8_s3", 3, 8, 40, 40, 5, 10, 150, "random", False),
         ("env_trace_40x40_p8_s4", 4, 8, 40, 40, 5, 10, 150, "demon", False),
     ]
+    if "--config-only" in sys.argv:   # the non-default configurations below only (the fixtures above are unchanged)
+        return config_traces()
     if "--stress-only" in sys.argv:   # round 2 additions (the round-1 fixtures above are unchanged)
         jobs = []
     jobs += [
@@ -183,7 +199,35 @@ def main():
         return
     np.savez_compressed(os.path.join(OUT, "astar_cases.npz"), **capture_astar_cases())
     np.savez_compressed(os.path.join(OUT, "reward_norm.npz"), **capture_reward_norm())
+    config_traces()
     print("done")
+
+
+# Short traces at non-default values of everything the reference's environment reads from its configuration besides the sizes:
+# sensor.num_beams / radius, env.difficulty, attacker.extend_dis / sen_range / tau / step_size, defender.tau / step_size /
+# comm_range / sen_range.  20 x 20, 4 defenders, 40 steps each.  (name, seed, policy, raser, overrides, late)
+CONFIG_JOBS = [
+    ("beams7_r6", 11, "demon", True, {"sensor.num_beams": 7, "sensor.radius": 6}, None),
+    ("beams64_r20", 12, "random", True, {"sensor.num_beams": 64, "sensor.radius": 20}, None),
+    ("beams1_r1", 13, "random", True, {"sensor.num_beams": 1, "sensor.radius": 1}, None),
+    ("difficulty3_extend0", 14, "demon", False, {"env.difficulty": 3, "attacker.extend_dis": 0}, None),
+    ("difficulty25_extend3_view3", 15, "random", False, {"env.difficulty": 25, "attacker.extend_dis": 3, "attacker.sen_range": 3}, None),
+    ("view0", 16, "demon", False, {"attacker.sen_range": 0}, None),
+    ("tau_step", 17, "demon", False, {"defender.tau": 0.3, "defender.step_size": 0.05, "attacker.tau": 0.7, "attacker.step_size": 0.2}, None),
+    ("tau_all_ones", 18, "random", False, {"defender.tau": float(np.nextafter(0.25, 0.0)), "attacker.tau": float(np.nextafter(0.25, 0.0)),
+                                           "defender.step_size": 0.12, "attacker.step_size": 0.08}, None),
+    ("ranges", 19, "demon", False, {"defender.comm_range": 6, "defender.sen_range": 4}, None),
+    ("comm_neg_sen0", 20, "demon", False, None, {"defender.comm_range": -1, "defender.sen_range": 0}),
+    ("comm0", 21, "random", False, None, {"defender.comm_range": 0}),
+]
+
+
+def config_traces():
+    for (name, seed, pol, ras, ov, late) in CONFIG_JOBS:
+        out = capture_trace(seed, 4, 20, 20, 2, 4, 40, pol, ras, overrides=ov, late=late)
+        np.savez_compressed(os.path.join(OUT, "envcfg_trace_20x20_p4_" + name + ".npz"), **out)
+        print(name, "n_obs", int(out["n_obs"]), "redraws", len(out["drawn_targets"]) - 1, "sum r", out["reward"].sum(),
+              "e_adj hits", int(out["e_adj"].sum()), "o_adj bits", int(np.unpackbits(out["o_adj"]).sum()), flush=True)
 
 
 if __name__ == "__main__":

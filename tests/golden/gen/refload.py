@@ -29,7 +29,15 @@ def activate():
             sys.path.insert(0, p)
 
 
-def load_cfg(num_defender=8, map_size=(40, 40), blocks=5, variance=10, depth=1, max_steps=150):
+def set_dotted(cfg, overrides):
+    """{"section.key": value} into a loaded configuration"""
+    for k, v in (overrides or {}).items():
+        sec, key = k.split(".")
+        assert key in cfg[sec], k          # only values the reference's own config.yaml carries
+        cfg[sec][key] = v
+
+
+def load_cfg(num_defender=8, map_size=(40, 40), blocks=5, variance=10, depth=1, max_steps=150, overrides=None):
     raw = yaml.safe_load(open(os.path.join(REF, "config.yaml")))
     cfg = to_ns({k: raw[k] for k in ("env", "sensor", "map", "attacker", "defender", "algo")})
     cfg.env.num_defender = num_defender
@@ -43,6 +51,7 @@ def load_cfg(num_defender=8, map_size=(40, 40), blocks=5, variance=10, depth=1, 
     cfg.algo.learner_device = "cpu"
     cfg.algo.worker_device = "cpu"
     cfg.algo.evaluator_device = "cpu"
+    set_dotted(cfg, overrides)
     return cfg
 
 

@@ -55,9 +55,10 @@ def init_from_traces(traces, O=176, tape_len=16):
     return init
 
 
-def oracle_envs_from_init(init, P, W, H, T, O=176, tape_len=16):
+def oracle_envs_from_init(init, P, W, H, T, O=176, tape_len=16, **oracle_cfg):
+    """oracle_cfg: any further field of oracle.pe_oracle.make_config (difficulty, extend_dis, num_beams, def_tau, ...)"""
     from oracle import pe_oracle
-    cfg = pe_oracle.make_config(W=W, H=H, P=P, O=O, max_steps=T, tape_len=tape_len)
+    cfg = pe_oracle.make_config(W=W, H=H, P=P, O=O, max_steps=T, tape_len=tape_len, **oracle_cfg)
     envs = []
     for n in range(len(init["n_obs"])):
         e = pe_oracle.OracleEnv(cfg)
@@ -67,8 +68,9 @@ def oracle_envs_from_init(init, P, W, H, T, O=176, tape_len=16):
     return cfg, envs
 
 
-def random_init(N, P, W, H, blocks, variance, seed, O=176, tape_len=16):
-    """Host initial conditions from the oracle's reset restatement (seeded per environment)."""
+def random_init(N, P, W, H, blocks, variance, seed, O=176, tape_len=16, **reset_kw):
+    """Host initial conditions from the oracle's reset restatement (seeded per environment).  reset_kw: comm_range / sen_range /
+    min_dist of oracle.reset_oracle.reset_oracle (placement rules)."""
     import random
     from oracle import reset_oracle
     init = dict(grid=np.zeros((N, W, H), np.uint8), obs_xy=np.zeros((N, O, 2), np.int32), n_obs=np.zeros(N, np.int32),
@@ -76,7 +78,7 @@ def random_init(N, P, W, H, blocks, variance, seed, O=176, tape_len=16):
                 tape=np.zeros((N, tape_len, 2), np.int32))
     for n in range(N):
         random.seed(seed + n); np.random.seed(seed + n)
-        r = reset_oracle.reset_oracle(W, H, P, blocks, [W // 2, H // 2], variance, tape_len=tape_len)
+        r = reset_oracle.reset_oracle(W, H, P, blocks, [W // 2, H // 2], variance, tape_len=tape_len, **reset_kw)
         k = len(r["obs_xy"])
         init["grid"][n] = r["grid"]; init["obs_xy"][n, :k] = r["obs_xy"]; init["n_obs"][n] = k
         init["defenders"][n] = r["defenders"]; init["evader"][n] = r["evader"]; init["target"][n] = r["target"]

@@ -11,14 +11,50 @@ from tests.helpers import load_trace, padded_tape, trace_files
 TAPE = 16
 
 
+# reference config.yaml key -> oracle.pe_oracle.make_config argument, for the traces recorded off the default configuration
+# (tests/golden/envcfg_trace_*.npz, tests/golden/gen/make_goldens_env.py CONFIG_JOBS)
+CFG_FIELDS = {"sensor.num_beams": "num_beams", "sensor.radius": "lidar_radius", "env.difficulty": "difficulty",
+              "attacker.extend_dis": "extend_dis", "attacker.sen_range": "evader_view", "attacker.tau": "eva_tau",
+              "attacker.step_size": "eva_dt", "defender.tau": "def_tau", "defender.step_size": "def_dt",
+              "defender.comm_range": "def_comm_range", "defender.sen_range": "def_sen_range"}
+INT_FIELDS = ("num_beams", "lidar_radius", "difficulty", "extend_dis", "evader_view")
+
+
+def trace_cfg(d, reset=False):
+    """make_config arguments a config trace was recorded at (reset=True: the values its reset ran at, before the late ones)"""
+    kw = {}
+    for keys, vals in (("cfg_keys", "cfg_vals"),) + (() if reset else (("late_keys", "late_vals"),)):
+        for k, v in zip(d.get(keys, ()), d.get(vals, ())):
+            f = CFG_FIELDS[str(k)]
+            kw[f] = int(v) if f in INT_FIELDS else float(v)
+    return kw
+
+
 def make_env(d):
-    cfg = pe_oracle.make_config(W=d["W"], H=d["H"], P=d["P"], O=176, max_steps=d["T"], tape_len=TAPE)
+    cfg = pe_oracle.make_config(W=d["W"], H=d["H"], P=d["P"], O=176, max_steps=d["T"], tape_len=TAPE, **trace_cfg(d))
     env = pe_oracle.OracleEnv(cfg)
     env.load(d["grid"], d["obs_xy"], d["defenders0"], d["evader0"], d["target0"], padded_tape(d, TAPE))
     return cfg, env
 
 
-@pytest.mark.parametrize("path", trace_files(), ids=lambda p: p.split("/")[-1][:-4])
+CONFIG_TRACES = trace_files("envcfg_trace_*.npz")
+
+
+def test_config_traces_cover_what_the_reference_reads():
+    """every configuration value the reference's environment reads besides the sizes has a trace off its default"""
+    assert len(CONFIG_TRACES) == 11
+    seen = {}
+    for p in CONFIG_TRACES:
+        d = load_trace(p)
+        for k, v in trace_cfg(d).items():
+            seen.setdefault(k, set()).add(v)
+    assert set(seen) == set(CFG_FIELDS.values())
+    assert {1, 7, 64} <= seen["num_beams"] and {0, 3} <= seen["evader_view"] and {0, 3} <= seen["extend_dis"]
+    assert {-1.0, 0.0, 6.0} <= seen["def_comm_range"] and {0.0, 4.0} <= seen["def_sen_range"]
+    assert float(np.nextafter(0.25, 0.0)) in seen["def_tau"] and 0.7 in seen["eva_tau"]
+
+
+@pytest.mark.parametrize("path", trace_files() + CONFIG_TRACES, ids=lambda p: p.split("/")[-1][:-4])
 def test_env_trace_matches_reference(path):
     d = load_trace(path)
     cfg, env = make_env(d)
@@ -52,7 +88,8 @@ def test_env_trace_matches_reference(path):
     assert env.state()["tape_pos"] == len(d["tape"])
 
 
-@pytest.mark.parametrize("path", trace_files("env_trace_*_s[02].npz"), ids=lambda p: p.split("/")[-1][:-4])
+@pytest.mark.parametrize("path", trace_files("env_trace_*_s[02].npz") + trace_files("envcfg_trace_*_beams*.npz"),
+                         ids=lambda p: p.split("/")[-1][:-4])
 def test_lidar_matches_reference_raser_map(path):
     d = load_trace(path)
     if "raser" not in d:
@@ -89,12 +126,14 @@ def test_reward_norm_matches_reference():
     assert n == int(z["n"]) and np.array_equal(mean, z["mean"]) and np.array_equal(S, z["S"])
 
 
-@pytest.mark.parametrize("path", trace_files(), ids=lambda p: p.split("/")[-1][:-4])
+@pytest.mark.parametrize("path", trace_files() + CONFIG_TRACES, ids=lambda p: p.split("/")[-1][:-4])
 def test_reset_restatement_reproduces_reference_rng(path):
     d = load_trace(path)
     random.seed(d["seed"]); np.random.seed(d["seed"])
+    at_reset = trace_cfg(d, reset=True)   # the two ranges the reference's placement reads (base_env.py:103, :142)
+    ranges = {k: at_reset["def_" + k] for k in ("comm_range", "sen_range") if "def_" + k in at_reset}
     r = reset_oracle.reset_oracle(d["W"], d["H"], d["P"], d["blocks"], [d["W"] // 2, d["H"] // 2], d["variance"],
-                                  tape_len=len(d["tape"]))
+                                  tape_len=len(d["tape"]), **ranges)
     assert np.array_equal(r["grid"], d["grid"])
     assert np.array_equal(r["inflated"], d["inflated"])
     assert np.array_equal(r["obs_xy"], d["obs_xy"])
