@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "mappo_ops.h"
 #include "mappo_ops_diag.h"
@@ -44,6 +45,57 @@ struct MsgDims {
     int R, P, K, E, din, q_div, adj_mode, rpb;  // rpb: rows per workgroup
     int64_t p_rs, q_rs, e_rs, adj_rs, o_is;
 };
+
+// FULL instantiations (the k_msgw*_full kernels; selected by the launchers, msg_full_rel): the team is full (P == PT == 8, one wave per
+// row) and the relation has the model's shape, so what today's forms read from MsgDims at run time is a constant of the instantiation --
+// P, din, the adjacency mode, and for the defender / evader relations K (8 / 1) and q_div (1); the obstacle relation keeps its
+// run-time K and q_div.  The constants are written over the kernel's copy of MsgDims (fix), so the helpers below fold every i < P
+// guard and din test, unroll the K loops (msg_for_k) and hand v_readlane immediate lanes; the arithmetic, its order and the memory
+// accesses are those of the generic forms (MsgAny: nothing fixed), so the two give the same bits.
+template <int FP, int FK_, int FD, int FM, int FQ>
+struct MsgFix {
+    static constexpr bool FULL = FP > 0;
+    static constexpr int FK = FK_;
+    static __device__ __forceinline__ MsgDims fix(MsgDims d) {
+        if (FP > 0) {
+            d.P = FP; d.din = FD; d.adj_mode = FM;
+            if (FK_ > 0) d.K = FK_;
+            if (FQ > 0) d.q_div = FQ;
+        }
+        return d;
+    }
+};
+using MsgAny = MsgFix<0, 0, 0, 0, 0>;
+// REL: 0 defender (K = P, din 8), 1 evader (K = 1, din 4), 2 obstacle (packed rows, K at run time, din 4)
+template <int REL>
+using MsgFull = MsgFix<8, REL == 0 ? 8 : (REL == 1 ? 1 : 0), REL == 0 ? 8 : 4, REL == 2 ? (int)MO_ADJ_BITS : (int)MO_ADJ_TENSOR, REL == 2 ? 0 : 1>;
+
+// the neighbour loop: unrolled over a compile-time count FK > 0, today's run-time loop for FK == 0 (body returns instead of `continue`)
+template <int FK, class F>
+__device__ __forceinline__ void msg_for_k(int K, F &&body) {
+    if constexpr (FK > 0) {
+#pragma unroll
+        for (int j = 0; j < FK; j++) {
+            body(j);
+            __builtin_amdgcn_sched_barrier(0);  // keeps the read-backs of later neighbours from being hoisted (scalar registers)
+        }
+    } else if constexpr (FK < 0) {  // kept rolled although K is a constant: the FULL forms' cold path (a weighted adjacency)
+#pragma unroll 1
+        for (int j = 0; j < K; j++) body(j);
+    } else {
+        for (int j = 0; j < K; j++) body(j);
+    }
+}
+// a wave-uniform flag as a compile-time value inside body (ZO = 1 / 0), branching once -- or left at run time (ZO = -1; !HOIST: today's forms)
+template <int V> struct MsgTag { static constexpr int value = V; };
+template <bool HOIST, class F>
+__device__ __forceinline__ void msg_hoist(bool flag, F &&body) {
+    if constexpr (HOIST) {
+        if (flag) body(MsgTag<1>()); else body(MsgTag<0>());
+    } else {
+        body(MsgTag<-1>());
+    }
+}
 
 __device__ __forceinline__ float rl_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 __device__ __forceinline__ uint32_t rl_u(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
@@ -103,8 +155,11 @@ __device__ __forceinline__ MsgMask msgw_mask(const MsgRow &m, int P, int K) {
     for (int i = 0; i < P; i++) k.col |= 1ull << (i * K);
     return k;
 }
+#define MSG_ZO(ZO, k) ((ZO) < 0 ? (k).zero_one : (ZO) != 0)   // the zero/one flag: read per use (today's forms) or hoisted (msg_hoist)
+#define MSG_INL __attribute__((always_inline))              // the loop bodies below are lambdas: always inlined, their captures stay registers
+template <int ZO = -1>
 __device__ __forceinline__ float msgw_row_norm(const MsgRow &m, const MsgMask &k, int i, int K) {
-    if (k.zero_one) return (float)__popcll((k.nz >> (i * K)) & ((K >= 64) ? ~0ull : ((1ull << K) - 1ull)));
+    if (MSG_ZO(ZO, k)) return (float)__popcll((k.nz >> (i * K)) & ((K >= 64) ? ~0ull : ((1ull << K) - 1ull)));
     float s = 0.f;
     for (int j = 0; j < K; j++) s += fabsf(__uint_as_float(rl_u(m.va0, i * K + j)));
     return s;
@@ -201,7 +256,7 @@ __device__ __forceinline__ void msgw_center(const MsgDims &d, const MsgRow &m, c
 }
 
 // the actor's aggregate of one row: acc[i] = sum_j adj_ij relu(c_i - d_j), inv[i] = 1 / max(sum_j |adj_ij|, 1e-12), for agents i0 .. i0 + PT - 1
-template <int PT, bool QS, bool AS, int EV>
+template <int PT, bool QS, bool AS, int EV, class FX = MsgAny>
 __device__ __forceinline__ void msgw_actor_row(const MsgDims &d, int r, const MsgRow &m, const float4 *__restrict__ q4,
                                                const void *__restrict__ adj, const FV<EV> (&w)[8], const FV<EV> (&c)[PT], FV<EV> (&acc)[PT],
                                                float (&inv)[PT], int i0 = 0) {
@@ -230,27 +285,30 @@ __device__ __forceinline__ void msgw_actor_row(const MsgDims &d, int r, const Ms
         }
     } else if (AS) {  // MO_ADJ_TENSOR held in one register: the non-zero pattern as a 64-bit mask (bit i K + j)
         const MsgMask k = msgw_mask(m, P, K);
-        uint64_t col = 0ull;                   // bit i K of this wave's agents
+        msg_hoist<FX::FULL>(k.zero_one, [&](auto zo) MSG_INL {
+            constexpr int ZO = decltype(zo)::value;
+            uint64_t col = 0ull;                   // bit i K of this wave's agents
 #pragma unroll
-        for (int i = 0; i < PT; i++) {
-            acc[i] = FV<EV>(0.f);
-            inv[i] = 0.f;
-            if (i0 + i < P) {
-                inv[i] = 1.f / fmaxf(msgw_row_norm(m, k, i0 + i, K), 1e-12f);
-                col |= 1ull << ((i0 + i) * K);
-            }
-        }
-        for (int j = 0; j < K; j++) {
-            const uint64_t cm = (k.nz >> j) & col;  // bit i K: agent i sees neighbour j
-            if (cm == 0ull) continue;
-            const FV<EV> dj = msg_dot4v(w, msgw_q<QS>(m, q4, j));
-#pragma unroll
-            for (int i = 0; i < PT; i++)
-                if (i0 + i < P && ((cm >> ((i0 + i) * K)) & 1ull)) {
-                    const float aij = k.zero_one ? 1.f : __uint_as_float(rl_u(m.va0, (i0 + i) * K + j));
-                    acc[i] = fv_fma(fv_relu(c[i] - dj), aij, acc[i]);
+            for (int i = 0; i < PT; i++) {
+                acc[i] = FV<EV>(0.f);
+                inv[i] = 0.f;
+                if (i0 + i < P) {
+                    inv[i] = 1.f / fmaxf(msgw_row_norm<ZO>(m, k, i0 + i, K), 1e-12f);
+                    col |= 1ull << ((i0 + i) * K);
                 }
-        }
+            }
+            msg_for_k<(ZO == 0 ? -1 : FX::FK)>(K, [&](int j) MSG_INL {   // (a weighted adjacency, ZO == 0: a rolled loop)
+                const uint64_t cm = (k.nz >> j) & col;  // bit i K: agent i sees neighbour j
+                if (cm == 0ull) return;
+                const FV<EV> dj = msg_dot4v(w, msgw_q<QS>(m, q4, j));
+#pragma unroll
+                for (int i = 0; i < PT; i++)
+                    if (i0 + i < P && ((cm >> ((i0 + i) * K)) & 1ull)) {
+                        const float aij = MSG_ZO(ZO, k) ? 1.f : __uint_as_float(rl_u(m.va0, (i0 + i) * K + j));
+                        acc[i] = fv_fma(fv_relu(c[i] - dj), aij, acc[i]);
+                    }
+            });
+        });
     } else {  // MO_ADJ_TENSOR read through uniform addresses
         const float *__restrict__ ar = (const float *)adj + (size_t)r * d.adj_rs + (size_t)i0 * K;
         const int pn = P - i0 < PT ? P - i0 : PT;      // this wave's agents
@@ -280,11 +338,19 @@ __device__ __forceinline__ void msgw_actor_row(const MsgDims &d, int r, const Ms
 }
 
 // the critic's aggregate: ones over the first kv neighbours (coordinates fetched four columns at a time)
-template <int PT, bool QS, int EV>
+template <int PT, bool QS, int EV, class FX = MsgAny>
 __device__ __forceinline__ void msgw_ones_row(int kv, const MsgRow &m, const float4 *__restrict__ q4, const FV<EV> (&w)[8], const FV<EV> (&c)[PT],
                                               FV<EV> (&acc)[PT]) {
 #pragma unroll
     for (int i = 0; i < PT; i++) acc[i] = FV<EV>(0.f);
+    if constexpr (QS && FX::FK > 0) {  // kv is the relation's K (no kvalid on the defender / evader relations)
+        msg_for_k<FX::FK>(kv, [&](int j) MSG_INL {
+            const FV<EV> dj = msg_dot4v(w, msgw_q<QS>(m, q4, j));
+#pragma unroll
+            for (int i = 0; i < PT; i++) acc[i] = acc[i] + fv_relu(c[i] - dj);
+        });
+        return;
+    }
     int j = 0;
     if (!QS) {
         for (; j + 4 <= kv; j += 4) {
@@ -308,11 +374,12 @@ __device__ __forceinline__ void msgw_ones_row(int kv, const MsgRow &m, const flo
 
 // one relation for this workgroup's rows.  out_c == nullptr: one network (d.adj_mode decides);  else actor (out) and critic
 // (out_c; c_valid: over the first kvalid[row] neighbours) from the same messages.
-template <int PT, bool QS, bool AS, int EV>
-__device__ __forceinline__ void msgw_fwd_rows(const MsgDims &d, const float *__restrict__ p, const float *__restrict__ q,
+template <int PT, bool QS, bool AS, int EV, class FX = MsgAny>
+__device__ __forceinline__ void msgw_fwd_rows(const MsgDims &d_, const float *__restrict__ p, const float *__restrict__ q,
                                               const float *__restrict__ e, const void *__restrict__ adj, const int32_t *__restrict__ kvalid,
                                               const float *__restrict__ W, const float *__restrict__ b, float *__restrict__ out,
                                               float *__restrict__ out_c, bool c_valid, int i0 = 0) {
+    const MsgDims d = FX::fix(d_);
     const int P = d.P, f = threadIdx.x, fs = blockDim.x;
     FV<EV> w[8], bias;
     msgw_weights<EV>(d, W, b, f, w, bias, fs);
@@ -328,16 +395,16 @@ __device__ __forceinline__ void msgw_fwd_rows(const MsgDims &d, const float *__r
         msgw_center<PT, EV>(d, m, w, bias, c, i0);
         if (out_c != nullptr) {
             FV<EV> acv[PT];
-            msgw_ones_row<PT, QS, EV>(m.kv, m, q4, w, c, acv);
+            msgw_ones_row<PT, QS, EV, FX>(m.kv, m, q4, w, c, acv);
             const float inv_c = 1.f / fmaxf((float)m.kv, 1e-12f);
 #pragma unroll
             for (int i = 0; i < PT; i++)
                 if (i0 + i < P) fv_store<EV>(out_c + ((size_t)r * P + i0 + i) * d.o_is, f, fs, acv[i] * inv_c);
-            msgw_actor_row<PT, QS, AS, EV>(d, r, m, q4, adj, w, c, acc, inv, i0);
+            msgw_actor_row<PT, QS, AS, EV, FX>(d, r, m, q4, adj, w, c, acc, inv, i0);
         } else if (d.adj_mode == MO_ADJ_TENSOR || d.adj_mode == MO_ADJ_BITS) {
-            msgw_actor_row<PT, QS, AS, EV>(d, r, m, q4, adj, w, c, acc, inv, i0);
+            msgw_actor_row<PT, QS, AS, EV, FX>(d, r, m, q4, adj, w, c, acc, inv, i0);
         } else {
-            msgw_ones_row<PT, QS, EV>(m.kv, m, q4, w, c, acc);
+            msgw_ones_row<PT, QS, EV, FX>(m.kv, m, q4, w, c, acc);
             const float iv = 1.f / fmaxf((float)m.kv, 1e-12f);
 #pragma unroll
             for (int i = 0; i < PT; i++) inv[i] = iv;
@@ -359,27 +426,33 @@ __global__ __launch_bounds__(256) void k_msgw_fwd(MsgDims d, const float *__rest
 // the three relations of DHGN.encoder (defender, evader: small neighbour sets; obstacle: large) of one network (out_c == nullptr)
 // or of actor and critic together, one launch.  (kvalid2 is handed to all three calls: a literal null there crashes this
 // hipcc's inliner; relations 0 and 1 never read it.)
-template <int PT, bool S01, bool AS2, int EV>
-__global__ __launch_bounds__(256) void k_msgw3_fwd(MsgDims d0, MsgDims d1, MsgDims d2, const float *__restrict__ p, const float *__restrict__ q0,
-                            const float *__restrict__ e0, const void *__restrict__ adj0, const float *__restrict__ W0,
-                            const float *__restrict__ b0, const float *__restrict__ q1, const void *__restrict__ adj1,
-                            const float *__restrict__ W1, const float *__restrict__ b1, const float *__restrict__ q2,
-                            const void *__restrict__ adj2, const int32_t *__restrict__ kvalid2, const float *__restrict__ W2,
-                            const float *__restrict__ b2, float *__restrict__ out, float *__restrict__ out_c, int c_valid, int c_rel2,
-                            const float *__restrict__ Wp, int64_t wp_rs, const float *__restrict__ bp, float *__restrict__ pos_a,
-                            float *__restrict__ pos_c, int64_t pos_ld) {
+#define MSGW3_PARAMS                                                                                                                     \
+    MsgDims d0, MsgDims d1, MsgDims d2, const float *__restrict__ p, const float *__restrict__ q0, const float *__restrict__ e0,                \
+        const void *__restrict__ adj0, const float *__restrict__ W0, const float *__restrict__ b0, const float *__restrict__ q1,                \
+        const void *__restrict__ adj1, const float *__restrict__ W1, const float *__restrict__ b1, const float *__restrict__ q2,                \
+        const void *__restrict__ adj2, const int32_t *__restrict__ kvalid2, const float *__restrict__ W2, const float *__restrict__ b2,         \
+        float *__restrict__ out, float *__restrict__ out_c, int c_valid, int c_rel2, const float *__restrict__ Wp, int64_t wp_rs,               \
+        const float *__restrict__ bp, float *__restrict__ pos_a, float *__restrict__ pos_c, int64_t pos_ld
+#define MSGW3_ARGS d0, d1, d2, p, q0, e0, adj0, W0, b0, q1, adj1, W1, b1, q2, adj2, kvalid2, W2, b2, out, out_c, c_valid, c_rel2, Wp, wp_rs, bp, pos_a, pos_c, pos_ld
+// FULL (k_msgw3_fwd_full: the pair forms of a full team of 8, packed obstacle rows held in registers): see MsgFix
+template <int PT, bool S01, bool AS2, int EV, bool FULL>
+__device__ __forceinline__ void msgw3_fwd(MSGW3_PARAMS) {
+    using F0 = std::conditional_t<FULL, MsgFull<0>, MsgAny>;
+    using F1 = std::conditional_t<FULL, MsgFull<1>, MsgAny>;
+    using F2 = std::conditional_t<FULL, MsgFull<2>, MsgAny>;
     const int E = d0.E;
     // blockIdx.y: which PT agents of the row this wave serves (launch_msgw3 divides a row between waves when there are few rows: a
     // wave's work on a row is one long dependent stream -- 45 us per row at the rollout's shapes whatever the row count)
-    const int i0 = blockIdx.y * PT;
-    msgw_fwd_rows<PT, S01, S01, EV>(d0, p, q0, e0, adj0, kvalid2, W0, b0, out, out_c, false, i0);
-    msgw_fwd_rows<PT, S01, S01, EV>(d1, p, q1, e0, adj1, kvalid2, W1, b1, out + E, out_c ? out_c + E : nullptr, false, i0);
+    const int i0 = FULL ? 0 : blockIdx.y * PT;
+    if (FULL) __builtin_assume(out_c != nullptr);
+    msgw_fwd_rows<PT, S01, S01, EV, F0>(d0, p, q0, e0, adj0, kvalid2, W0, b0, out, out_c, false, i0);
+    msgw_fwd_rows<PT, S01, S01, EV, F1>(d1, p, q1, e0, adj1, kvalid2, W1, b1, out + E, out_c ? out_c + E : nullptr, false, i0);
     // c_rel2 == 0 (the update): the critic's obstacle relation is left to the sorted all-ones kernel (k_msg_ones_sorted_fwd)
-    msgw_fwd_rows<PT, false, AS2, EV>(d2, p, q2, e0, adj2, kvalid2, W2, b2, out + 2 * E, (out_c && c_rel2) ? out_c + 2 * E : nullptr, c_valid != 0, i0);
+    msgw_fwd_rows<PT, false, AS2, EV, F2>(d2, p, q2, e0, adj2, kvalid2, W2, b2, out + 2 * E, (out_c && c_rel2) ? out_c + 2 * E : nullptr, c_valid != 0, i0);
     if (pos_a != nullptr) {
         // the position part of DHGN's semantic layer, bp + Wp p_i (Wp = the first four input columns, :284-303), for the same rows:
         // the addend the embedding part of that layer accumulates into; identical for actor and critic, written to both
-        const int P = d0.P, f = threadIdx.x, fs = blockDim.x, lane = threadIdx.x & 63;
+        const int P = F0::fix(d0).P, f = threadIdx.x, fs = blockDim.x, lane = threadIdx.x & 63;
         FV<EV> wp[4], bias = fv_load<EV>(bp, f, fs);
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -400,16 +473,24 @@ __global__ __launch_bounds__(256) void k_msgw3_fwd(MsgDims d0, MsgDims d1, MsgDi
         }
     }
 }
+template <int PT, bool S01, bool AS2, int EV>
+__global__ __launch_bounds__(256) void k_msgw3_fwd(MSGW3_PARAMS) { msgw3_fwd<PT, S01, AS2, EV, false>(MSGW3_ARGS); }
+template <int EV>
+__global__ __launch_bounds__(256) void k_msgw3_fwd_full(MSGW3_PARAMS) { msgw3_fwd<8, true, true, EV, true>(MSGW3_ARGS); }
+#undef MSGW3_ARGS
+#undef MSGW3_PARAMS
 
 // backward: per-thread partial sums over the workgroup's rows -> partials [gridDim.x][din + 1][E] (reduced by
 // k_msg_agg_bwd_reduce).  dW[:, k<4] = sum_i G_i p_i[k] - sum_j H_j q_j[k] with G_i = sum_j g_ij, H_j = sum_i g_ij,
 // g_ij = [z_ij > 0] abar_ij gout_i ; dW[:, 4+k] = sum_i G_i (p_i - e)[k] ; db = sum_i G_i.  For MO_ADJ_BITS the
 // neighbour-coordinate term is summed edge by edge instead of column by column (fp32 reassociation only).
-template <int PT, bool QS, bool AS, int EV, bool PAIR>
-__global__ __launch_bounds__(256) void k_msgw_bwd(MsgDims d, const float *__restrict__ p, const float *__restrict__ q, const float *__restrict__ e,
-                           const void *__restrict__ adj, const int32_t *__restrict__ kvalid, const float *__restrict__ W,
-                           const float *__restrict__ b, const float *__restrict__ gout, const float *__restrict__ gout_c,
-                           float *__restrict__ partials) {
+#define MSGW_BWD_PARAMS                                                                                                                    \
+    MsgDims d_, const float *__restrict__ p, const float *__restrict__ q, const float *__restrict__ e, const void *__restrict__ adj,            \
+        const int32_t *__restrict__ kvalid, const float *__restrict__ W, const float *__restrict__ b, const float *__restrict__ gout,           \
+        const float *__restrict__ gout_c, float *__restrict__ partials
+template <int PT, bool QS, bool AS, int EV, bool PAIR, class FX>
+__device__ __forceinline__ void msgw_bwd(MSGW_BWD_PARAMS) {
+    const MsgDims d = FX::fix(d_);
     // PAIR (a separate instantiation: the second gradient costs 30 registers, which the single-network kernels must not pay),
     // gout_c != nullptr (MO_ADJ_TENSOR only): the SAME relation of the critic (adjacency = ones over all K neighbours, shared weights)
     // in the same pass -- the two networks' messages share z_ij, so g_ij = [z_ij > 0] (abar_ij gout_i + gout_c_i / K) and the sum of
@@ -474,46 +555,50 @@ __global__ __launch_bounds__(256) void k_msgw_bwd(MsgDims d, const float *__rest
             const float *__restrict__ ar = (const float *)adj + (size_t)r * d.adj_rs;   // (!AS: through uniform addresses)
             MsgMask k;
             if (AS) k = msgw_mask(m, P, K);
-            FV<EV> gi[PT];
+            else k.zero_one = false;
+            msg_hoist<FX::FULL && AS>(k.zero_one, [&](auto zo) MSG_INL {
+                constexpr int ZO = decltype(zo)::value;
+                FV<EV> gi[PT];
 #pragma unroll
-            for (int i = 0; i < PT; i++) {
-                gi[i] = FV<EV>(0.f);
-                if (i < P) {
-                    float s = 0.f;
-                    if (AS) s = msgw_row_norm(m, k, i, K);
-                    else for (int j = 0; j < K; j++) s += fabsf(ar[i * K + j]);
-                    gi[i] = go[i] * (1.f / fmaxf(s, 1e-12f));
-                }
-            }
-            for (int j = 0; j < K; j++) {
-                uint64_t cm = 0ull;
-                if (AS) {
-                    cm = (k.nz >> j) & k.col;
-                    if (cm == 0ull && !PAIR) continue;
-                } else if (!PAIR) {
-                    bool any = false;
-                    for (int i = 0; i < P; i++) any |= ar[i * K + j] != 0.f;
-                    if (!any) continue;
-                }
-                const float4 qv = msgw_q<QS>(m, q4, j);
-                const FV<EV> dj = msg_dot4v(w, qv);
-                FV<EV> hj(0.f);
-#pragma unroll
-                for (int i = 0; i < PT; i++)
+                for (int i = 0; i < PT; i++) {
+                    gi[i] = FV<EV>(0.f);
                     if (i < P) {
-                        float aij;
-                        if (AS) {
-                            aij = ((cm >> (i * K)) & 1ull) ? (k.zero_one ? 1.f : __uint_as_float(rl_u(m.va0, i * K + j))) : 0.f;
-                        } else {
-                            aij = ar[i * K + j];
-                        }
-                        if (aij == 0.f && !PAIR) continue;
-                        const FV<EV> g = fv_pos(c[i] - dj, PAIR ? fv_fma(gi[i], aij, goc[i]) : gi[i] * aij);   // actor: abar_ij gout_i; critic: gout_c_i / K
-                        G[i] = G[i] + g;
-                        hj = hj + g;
+                        float s = 0.f;
+                        if (AS) s = msgw_row_norm<ZO>(m, k, i, K);
+                        else for (int j = 0; j < K; j++) s += fabsf(ar[i * K + j]);
+                        gi[i] = go[i] * (1.f / fmaxf(s, 1e-12f));
                     }
-                hq0 = fv_fma(hj, qv.x, hq0); hq1 = fv_fma(hj, qv.y, hq1); hq2 = fv_fma(hj, qv.z, hq2); hq3 = fv_fma(hj, qv.w, hq3);
-            }
+                }
+                msg_for_k<(ZO == 0 ? -1 : FX::FK)>(K, [&](int j) MSG_INL {   // (a weighted adjacency, ZO == 0: a rolled loop)
+                    uint64_t cm = 0ull;
+                    if (AS) {
+                        cm = (k.nz >> j) & k.col;
+                        if (cm == 0ull && !PAIR) return;
+                    } else if (!PAIR) {
+                        bool any = false;
+                        for (int i = 0; i < P; i++) any |= ar[i * K + j] != 0.f;
+                        if (!any) return;
+                    }
+                    const float4 qv = msgw_q<QS>(m, q4, j);
+                    const FV<EV> dj = msg_dot4v(w, qv);
+                    FV<EV> hj(0.f);
+#pragma unroll
+                    for (int i = 0; i < PT; i++)
+                        if (i < P) {
+                            float aij;
+                            if (AS) {
+                                aij = ((cm >> (i * K)) & 1ull) ? (MSG_ZO(ZO, k) ? 1.f : __uint_as_float(rl_u(m.va0, i * K + j))) : 0.f;
+                            } else {
+                                aij = ar[i * K + j];
+                            }
+                            if (aij == 0.f && !PAIR) continue;
+                            const FV<EV> g = fv_pos(c[i] - dj, PAIR ? fv_fma(gi[i], aij, goc[i]) : gi[i] * aij);   // actor: abar_ij gout_i; critic: gout_c_i / K
+                            G[i] = G[i] + g;
+                            hj = hj + g;
+                        }
+                    hq0 = fv_fma(hj, qv.x, hq0); hq1 = fv_fma(hj, qv.y, hq1); hq2 = fv_fma(hj, qv.z, hq2); hq3 = fv_fma(hj, qv.w, hq3);
+                });
+            });
         } else {
             const int kv = m.kv;
             const float iv = 1.f / fmaxf((float)kv, 1e-12f);
@@ -554,6 +639,15 @@ __global__ __launch_bounds__(256) void k_msgw_bwd(MsgDims d, const float *__rest
     for (int k = 0; k < d.din; k++) fv_store<EV>(dst + k * d.E, f, fs, gw[k]);
     fv_store<EV>(dst + d.din * d.E, f, fs, gb);
 }
+#define MSGW_BWD_ARGS d_, p, q, e, adj, kvalid, W, b, gout, gout_c, partials
+template <int PT, bool QS, bool AS, int EV, bool PAIR>
+__global__ __launch_bounds__(256) void k_msgw_bwd(MSGW_BWD_PARAMS) { msgw_bwd<PT, QS, AS, EV, PAIR, MsgAny>(MSGW_BWD_ARGS); }
+// a full team of 8 (MsgFix).  REL 0 / 1: the defender / evader relation of both networks (PAIR), adjacency and coordinates in
+// registers;  REL 2: the actor's obstacle relation, packed rows in registers, coordinates through uniform addresses
+template <int REL, int EV>
+__global__ __launch_bounds__(256, EV == 2 ? 2 : 4) void k_msgw_bwd_full(MSGW_BWD_PARAMS) { msgw_bwd<8, REL != 2, true, EV, REL != 2, MsgFull<REL>>(MSGW_BWD_ARGS); }
+#undef MSGW_BWD_ARGS
+#undef MSGW_BWD_PARAMS
 
 // one workgroup per output element group: 64 lanes split the partial blocks, then a wave reduction (deterministic order)
 __global__ void k_msg_agg_bwd_reduce(int nblk, int E, int din, const float *partials, float *dW, float *db) {
@@ -1760,6 +1854,18 @@ bool msg_adj_small(int P, int K, int adj_mode) {
     return true;
 }
 
+// The full-team instantiations (MsgFix) are taken where g_msg_full_team is set (ops.MSG_FULL_TEAM through dhgn_msg_full_team; off =
+// the generic forms for every shape) and the relation has the model's shape for a team of 8: -> 0 defender, 1 evader, 2 obstacle
+// (packed rows that fit the registers, coordinates that do not), -1 none.  g_msg_full_launches counts their launches for the tests.
+int g_msg_full_team = 1;
+int64_t g_msg_full_launches = 0;
+int msg_full_rel(int P, int K, int din, int q_div, int adj_mode) {
+    if (!g_msg_full_team || P != 8) return -1;
+    if (adj_mode == MO_ADJ_TENSOR && q_div == 1) return (K == 8 && din == 8) ? 0 : ((K == 1 && din == 4) ? 1 : -1);
+    if (adj_mode == MO_ADJ_BITS && din == 4 && !msg_q_small(K) && msg_adj_small(P, K, adj_mode)) return 2;
+    return -1;
+}
+
 MsgDims msg_dims(int R, int P, int K, int E, int din, int q_div, int adj_mode, int64_t p_rs, int64_t q_rs, int64_t e_rs, int64_t adj_rs,
                  int64_t o_is, int max_blocks, int *grid) {
     const int g0 = R < max_blocks ? (R > 0 ? R : 1) : max_blocks;
@@ -2473,8 +2579,12 @@ int launch_msgw3(const mo_msg_rel *rel, int R, int P, int E, const float *p, int
     // is why launches with more rows keep one wave per row (measured at 4 096 rows: 77 us whole, 83 us halved; at 512 rows: see DESIGN 6).
     const bool halves = R <= 2048 && P > 4;
     const int pt = halves ? (P <= 8 ? 4 : 8) : (P <= 8 ? 8 : 16), gy = (P + pt - 1) / pt;
+    // the pair forms of a full team of 8, one wave per row (same grid, same rows per workgroup): k_msgw3_fwd_full
+    bool full = pair && out_c != nullptr && !halves && s01 && as2;
+    for (int r = 0; r < 3; r++) full = full && msg_full_rel(P, rel[r].K, rel[r].din, rel[r].q_div, rel[r].adj_mode) == r;
+    g_msg_full_launches += full;
 #define MSGW3_LAUNCH1(PT, S01, AS2, EV)                                                                                                     \
-    hipLaunchKernelGGL((k_msgw3_fwd<PT, S01, AS2, EV>), dim3(grid, gy), dim3(E / EV), 0, (hipStream_t)stream, d[0], d[1], d[2], p, rel[0].q,   \
+    hipLaunchKernelGGL((full ? k_msgw3_fwd_full<EV> : k_msgw3_fwd<PT, S01, AS2, EV>), dim3(grid, gy), dim3(E / EV), 0, (hipStream_t)stream, d[0], d[1], d[2], p, rel[0].q,   \
                        rel[0].e, rel[0].adj, rel[0].W, rel[0].b, rel[1].q, rel[1].adj, rel[1].W, rel[1].b, rel[2].q, rel[2].adj, kvalid2,      \
                        rel[2].W, rel[2].b, out, out_c, c_valid, c_rel2, Wp, wp_rs, bp, pos_a, pos_c, pos_ld ? pos_ld : (int64_t)E)
 #define MSGW3_LAUNCH(PT, S01, AS2) do { if (ev2) MSGW3_LAUNCH1(PT, S01, AS2, 2); else MSGW3_LAUNCH1(PT, S01, AS2, 1); } while (0)
@@ -2572,6 +2682,13 @@ int dhgn_msg_agg3_pair_pos_fwd(const mo_msg_rel *rel, int32_t R, int32_t P, int3
                         pos_actor, pos_critic, pos_stride);
 }
 
+int dhgn_msg_full_team(int on) {
+    const int was = g_msg_full_team;
+    g_msg_full_team = on != 0;
+    return was;
+}
+int64_t dhgn_msg_full_team_launches(void) { return g_msg_full_launches; }
+
 int64_t dhgn_msg_agg_bwd_workspace(int32_t E, int32_t din) { return (int64_t)BWD_BLOCKS * (din + 1) * E * sizeof(float); }
 
 static int msg_agg_bwd_launch(int32_t R, int32_t P, int32_t K, int32_t E, int32_t din, const float *p, int64_t p_rs, const float *q,
@@ -2586,8 +2703,12 @@ static int msg_agg_bwd_launch(int32_t R, int32_t P, int32_t K, int32_t E, int32_
     int grid;
     const MsgDims d = msg_dims(R, P, K, E, din, q_div, adj_mode, p_rs, q_rs, e_rs, adj_rs, gout_stride, BWD_BLOCKS, &grid);
     const bool qs = msg_q_small(K), as = msg_adj_small(P, K, adj_mode), ev2 = (E % 128) == 0;
+    // a full team of 8: relations 0 / 1 of both networks (PAIR), or the actor's packed obstacle rows -- k_msgw_bwd_full, same grid
+    int full = msg_full_rel(P, K, din, q_div, adj_mode);
+    if ((full == 2) != (gout_c == nullptr) || !qs == (full != 2) || !as) full = -1;
+    g_msg_full_launches += full >= 0;
 #define MSGW_BWD2(PT, QS, AS, EV, PAIR) \
-    hipLaunchKernelGGL((k_msgw_bwd<PT, QS, AS, EV, PAIR>), dim3(grid), dim3(E / EV), 0, (hipStream_t)stream, d, p, q, e, adj, kvalid, W, b, gout, gout_c, (float *)workspace)
+    hipLaunchKernelGGL((full == 0 ? k_msgw_bwd_full<0, EV> : full == 1 ? k_msgw_bwd_full<1, EV> : full == 2 ? k_msgw_bwd_full<2, EV> : k_msgw_bwd<PT, QS, AS, EV, PAIR>), dim3(grid), dim3(E / EV), 0, (hipStream_t)stream, d, p, q, e, adj, kvalid, W, b, gout, gout_c, (float *)workspace)
 #define MSGW_BWD1(PT, QS, AS, EV) do { if (gout_c) MSGW_BWD2(PT, QS, AS, EV, true); else MSGW_BWD2(PT, QS, AS, EV, false); } while (0)
 #define MSGW_BWD(PT, QS, AS) do { if (ev2) MSGW_BWD1(PT, QS, AS, 2); else MSGW_BWD1(PT, QS, AS, 1); } while (0)
 #define MSGW_BWD_PT(PT) { if (qs && as) MSGW_BWD(PT, true, true); else if (qs) MSGW_BWD(PT, true, false); else if (as) MSGW_BWD(PT, false, true); else MSGW_BWD(PT, false, false); }

@@ -51,6 +51,8 @@ def load_library():
         L.spectral_norm_weight.argtypes = [i32, i32, vp, vp, vp, f32, i32, vp, vp]
         L.dhgn_msg_agg_bwd_workspace.argtypes = [i32, i32]
         L.dhgn_msg_agg_bwd_workspace.restype = i64
+        L.dhgn_msg_full_team.argtypes = [i32]
+        L.dhgn_msg_full_team_launches.restype = i64
         L.dhgn_msg_agg_ones_sorted_ok.argtypes = [i32] * 6
         L.dhgn_msg_agg_ones_sorted_workspace.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp]
         L.dhgn_msg_agg_ones_sorted_workspace.restype = i64
@@ -245,8 +247,27 @@ def _workspace(device, E, din):
     return ws
 
 
+MSG_FULL_TEAM = os.environ.get("MAPPO_MSG_FULL_TEAM", "1") != "0"   # A/B switch (tools/ab_switch.py): off = the generic message kernels for every shape
+_msg_full_team_set = None
+
+
+def _msg_route(L):
+    """MSG_FULL_TEAM as it stands now -> the library, whose launchers select the instantiation (read at launch, so at capture for a tick program)"""
+    global _msg_full_team_set
+    want = bool(MSG_FULL_TEAM)
+    if _msg_full_team_set != want:
+        L.dhgn_msg_full_team(int(want))
+        _msg_full_team_set = want
+
+
+def msg_full_team_launches():
+    """test-only (include/mappo_ops_diag.h): launches of the full-team message kernels so far"""
+    return int(load_library().dhgn_msg_full_team_launches())
+
+
 def _msg_call(kind, L, p, q, e, adj, kvalid, W, b, adj_mode, q_div, io, io_stride, extra=()):
     """one relation: io = out (fwd) or gout (bwd) slot pointer with io_stride elements between [E] vectors"""
+    _msg_route(L)
     R, P = p.shape[0], p.shape[1]
     K = q.shape[1]
     E, din = W.shape
@@ -357,6 +378,7 @@ def msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, o_kvalid
     assert not (torch.is_grad_enabled() and any(t.requires_grad for t in (W0, b0, W1, b1, W2, b2))), "msg_agg3_pair has no backward"
     L = load_library()
     _need_gpu(p, "dhgn_msg_agg3_pair")
+    _msg_route(L)
     R, P = p.shape[0], p.shape[1]
     E = W0.shape[0]
     ws = [t.detach().contiguous() for t in (W0, b0, W1, b1, W2, b2)]
@@ -483,6 +505,7 @@ class _MsgAgg3Pair(torch.autograd.Function):
     def forward(ctx, p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, q_div, e_ref=None):
         L = load_library()
         _need_gpu(p, "dhgn_msg_agg")
+        _msg_route(L)
         R, P = p.shape[0], p.shape[1]
         E, K = W0.shape[0], o.shape[1]
         ws = [t.detach().contiguous() for t in (W0, b0, W1, b1, W2, b2)]
@@ -512,6 +535,7 @@ class _MsgAgg3Pair(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ga, gc):
         L = load_library()
+        _msg_route(L)
         p, e, o, adj_p, adj_e, adj_o, save_m, qtab, e2, W0, b0, W1, b1, W2, b2 = ctx.saved_tensors
         mode_o, q_div = ctx.meta
         R, P = p.shape[0], p.shape[1]

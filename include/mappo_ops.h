@@ -81,6 +81,12 @@ int dhgn_msg_agg_bwd_pair(int32_t R, int32_t P, int32_t K, int32_t E, int32_t di
                           int64_t q_row_stride, int32_t q_div, const float *e, int64_t e_row_stride, const float *adj, int64_t adj_row_stride,
                           const float *W, const float *b, const float *gout_actor, const float *gout_critic, int64_t gout_stride, float *dW,
                           float *db, void *workspace, void *stream);
+/* The pair forms above (forward: one wave per row, R > 2048; backward: dhgn_msg_agg_bwd_pair and the packed obstacle rows of
+ * dhgn_msg_agg_bwd) have instantiations for a FULL team of 8 with the model's relation shapes (defender K = 8 / din 8, evader K = 1 /
+ * din 4, packed obstacle rows with 16 < K and 8 MO_ADJ_ROW_WORDS(K) <= 128), in which those shapes are compile-time constants: the same
+ * arithmetic in the same order, bit-identical results.  on = 0 sends every shape to the generic forms (the A/B switch
+ * ops.MSG_FULL_TEAM); returns the previous setting.  Not thread-safe against concurrent launches. */
+int dhgn_msg_full_team(int on);
 /* The same launch, which also writes the position part of DHGN's semantic layer for these rows, pos[r][i][:] = bp + Wp p[r][i]
  * (Wp [E][4]: the first four input columns of semantic_layer.weight, wp_row_stride elements between its rows; mappo_parallel.py:
  * 284-303) -- the addend the embedding part of that layer accumulates into; the same numbers for both networks, written to

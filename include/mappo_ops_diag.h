@@ -16,6 +16,10 @@ extern "C" {
  * not round to infinity; tests/test_ops_gpu.py test_split_bf16_pieces_sum_exactly). */
 int sb_split_diag(int64_t n, const float *x, float *pieces, void *stream);
 
+/* Launches of the full-team message kernels (k_msgw3_fwd_full, k_msgw_bwd_full; mappo_ops.h dhgn_msg_full_team) since the library was
+ * loaded: a test reads it before and after a call to tell which instantiation the launcher selected. */
+int64_t dhgn_msg_full_team_launches(void);
+
 #ifdef __cplusplus
 }
 #endif
