@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include <cmath>
+#include <vector>
 
 #include "pe_env.h"
 #include "pe_env_diag.h"
@@ -29,7 +30,7 @@ constexpr int PE_TAPE_LDS = 32;   // tape entries prefetched with the first batc
 constexpr int PE_WP_WINDOW = 16;  // waypoints kept next to the meta record (>= pops between two replans)
 constexpr double SQRT2 = 0x1.6a09e667f3bcdp+0;  // math.hypot(1, 1)  (astar.py:96)
 
-__device__ __forceinline__ int py_round(double v) { return (int)__builtin_rint(v); }
+__host__ __device__ __forceinline__ int py_round(double v) { return (int)__builtin_rint(v); }
 __device__ __forceinline__ double norm2(double a, double b) { return __builtin_sqrt(__builtin_fma(b, b, a * a)); }
 // norm2(a, b) <= r without the f64 square root on the device: sqrt is correctly rounded and monotone, so
 // { x : sqrt(x) <= r } = { x : x <= t } for the largest double t with sqrt(t) <= r (likewise for <).  The thresholds of
@@ -40,7 +41,7 @@ __device__ __forceinline__ double norm2sq(double a, double b) { return __builtin
 // q = RN(a y), r = a - b q (exact in one fma) the corrected q' = RN(q + r y) is the correctly rounded quotient
 // (Markstein) unless b's significand is all ones -- the host checks that and the exponent range and then passes y = 0,
 // which selects the plain division.  r == 0 keeps q (also keeps the sign of a zero quotient).
-__device__ __forceinline__ double div_const(double a, double b, double y) {
+__host__ __device__ __forceinline__ double div_const(double a, double b, double y) {
     if (y == 0.0) return a / b;  // wave-uniform
     const double q = a * y;
     const double r = __builtin_fma(-q, b, a);
@@ -211,7 +212,7 @@ __device__ __forceinline__ void copy_out_f32(float *dst, const float *src, int n
 }
 
 // ---- agent.py:74-104 : first-order lag integrated with RK4, association exactly as written -------------
-__device__ __forceinline__ void dynamic(double tau, double itau, double i6, double h, double x, double y, double vx0, double vy0, double ux,
+__host__ __device__ __forceinline__ void dynamic(double tau, double itau, double i6, double h, double x, double y, double vx0, double vy0, double ux,
                                         double uy, double *o) {
     double k1 = div_const(ux - vx0, tau, itau);
     double k2 = div_const(ux - (vx0 + h * k1 / 2), tau, itau);
@@ -229,7 +230,36 @@ __device__ __forceinline__ void dynamic(double tau, double itau, double i6, doub
     o[3] = vy;
 }
 
-__device__ __forceinline__ bool in_bound_i(const pe_config &c, int x, int y) { return x < c.W && x >= 0 && y < c.H && y >= 0; }
+__host__ __device__ __forceinline__ bool in_bound_i(const pe_config &c, int x, int y) { return x < c.W && x >= 0 && y < c.H && y >= 0; }
+
+// One probe of dev_step's 3 x 3 test of the static map (pursuit_env.py:152-163): the cell under (x + a r, y + b r), a, b in
+// {-1, 0, 1}; only in-bound probes count.  Shared with the pathfinder's look-ahead (pe_pathfinder.hpp), host and device.
+__host__ __device__ __forceinline__ bool probe_hit(const pe_config &c, const uint8_t *grid, double x, double y, int a, int b, double r) {
+    const double qx = x + (double)a * r, qy = y + (double)b * r;
+    const int ix = py_round(qx), iy = py_round(qy);
+    return in_bound_i(c, ix, iy) && grid[ix * c.H + iy] != 0;
+}
+
+// find_attacker's cell walk (agent.py:319-341): Bresenham from (x0, y0) to (x1, y1), false as soon as a cell of the line is
+// occupied (ONLY_ONE: holds a 1, find_attacker's own test; else: is not 0).  Bounded: the line has at most dx + dy + 1 cells.
+// Shared with the pathfinder's line of sight.  unroll 1: the loop as the tick has always run it (left alone, the compiler
+// unrolls the lifted form by four).
+template <bool ONLY_ONE>
+__host__ __device__ __forceinline__ bool walk_clear(const uint8_t *grid, int H, int x0, int y0, int x1, int y1, int cap) {
+    int dx = abs(x1 - x0), dy = abs(y1 - y0);
+    int sx = x0 > x1 ? -1 : 1, sy = y0 > y1 ? -1 : 1;
+    int err = dx - dy;
+    bool clear = true;
+#pragma unroll 1
+    for (int it = 0; it < cap; it++) {
+        if (ONLY_ONE ? grid[x0 * H + y0] == 1 : grid[x0 * H + y0] != 0) { clear = false; break; }
+        if (x0 == x1 && y0 == y1) break;
+        int e2 = 2 * err;
+        if (e2 > -dy) { err -= dy; x0 += sx; }
+        if (e2 < dx) { err += dx; y0 += sy; }
+    }
+    return clear;
+}
 
 // ---- defenders: Pursuit_Env.step + defender_reward + collision_detection (pursuit_env.py:104-177) ------
 // The reference scores the defenders one after the other and clips an accepted proposal IN PLACE before the next one is
@@ -285,12 +315,8 @@ __device__ void dev_step(const pe_config &c, const SqThr &th, const Lds &l, int 
         unsigned long long HA, HB;
         {
             const int a3 = (j * 11) >> 5;  // j / 3 for j < 8
-            const double qx = xi + (double)(a3 - 1) * r, qy = yi + (double)(j - 3 * a3 - 1) * r;
-            const int ix = py_round(qx), iy = py_round(qy);
-            HA = __ballot(iv && in_bound_i(c, ix, iy) && l.grid[ix * c.H + iy] != 0);  // all eight probes, whatever P is
-            const double q8x = xi + r, q8y = yi + r;  // (double)1 * r == r
-            const int jx = py_round(q8x), jy = py_round(q8y);
-            HB = __ballot(iv && j == 0 && in_bound_i(c, jx, jy) && l.grid[jx * c.H + jy] != 0);
+            HA = __ballot(iv && probe_hit(c, l.grid, xi, yi, a3 - 1, j - 3 * a3 - 1, r));  // all eight probes, whatever P is
+            HB = __ballot(iv && j == 0 && probe_hit(c, l.grid, xi, yi, 1, 1, r));  // (double)1 * r == r
         }
         unsigned long long M = Mu;
         for (unsigned int todo = outb; todo;) {  // wave-uniform; empty unless a proposal left the clip box
@@ -329,10 +355,7 @@ __device__ void dev_step(const pe_config &c, const SqThr &th, const Lds &l, int 
             // 3x3 probe of the static map at half-radius offsets; only in-bound probes count (pursuit_env.py:152-163)
             bool hit = false;
             if (lane < 9) {
-                int a = lane / 3 - 1, b = lane % 3 - 1;
-                double qx = sx + (double)a * r, qy = sy + (double)b * r;
-                int ix = py_round(qx), iy = py_round(qy);
-                if (in_bound_i(c, ix, iy)) hit = l.grid[ix * c.H + iy] != 0;
+                hit = probe_hit(c, l.grid, sx, sy, lane / 3 - 1, lane % 3 - 1, r);
             }
             int col = __ballot(hit) != 0ull;
             int rew = -(cnt - 1) - col;
@@ -429,17 +452,7 @@ __device__ void dev_observe(const pe_config &c, const SqThr &th, const Lds &l, i
         int x1 = py_round(l.eva[0]), y1 = py_round(l.eva[1]);
         float seen = 0.f;
         if (norm2sq((double)(x0 - x1), (double)(y0 - y1)) <= th.sen_le) {
-            int dx = abs(x1 - x0), dy = abs(y1 - y0);
-            int sx = x0 > x1 ? -1 : 1, sy = y0 > y1 ? -1 : 1;
-            int err = dx - dy;
-            seen = 1.f;
-            for (int it = 0; it < 4 * (c.W + c.H); it++) {  // bounded: the line has at most dx+dy+1 cells
-                if (l.grid[x0 * c.H + y0] == 1) { seen = 0.f; break; }
-                if (x0 == x1 && y0 == y1) break;
-                int e2 = 2 * err;
-                if (e2 > -dy) { err -= dy; x0 += sx; }
-                if (e2 < dx) { err += dx; y0 += sy; }
-            }
+            seen = walk_clear<true>(l.grid, c.H, x0, y0, x1, y1, 4 * (c.W + c.H)) ? 1.f : 0.f;
         }
         o.e_adj[(int64_t)env * o.e_adj_stride + lane] = seen;
     }
@@ -971,6 +984,114 @@ __global__ void k_demon(int N, int P, const double *__restrict__ def, const doub
         if (dk < bd) { bd = dk; best = k; }   // list.index(min(..)): the first minimum
     }
     actions[i] = best;
+}
+
+}  // namespace
+
+#include "pe_pathfinder.hpp"
+
+namespace {
+
+// ---- the scripted path-finding pursuers (pe_pathfinder.hpp) ---------------------------------------------
+// One workgroup of four waves per environment, not one wave as in the tick: the cost is the relaxation of the distance field, every
+// sweep of which is independent work over W*H cells (1600 .. 8192), and the number of sweeps is set by the map, not by the lanes -- four
+// waves quarter the cells a lane relaxes per sweep, and a workgroup barrier per sweep is what the termination test needs anyway.
+// grid, D, the neighbour words and the penalty bits live in LDS.  Sweeps relax in place: a lane may read a neighbour before or
+// after another wave lowered it; both are upper bounds that only ever fall, and a sweep in which no lane wrote anything read the
+// final values everywhere, so the loop ends exactly at the fixed point -- or at the W*H trip bound (a shortest path has fewer than W*H
+// edges and every sweep settles one more), which sets PE_STATUS_PATH_CAP.  The P x 9 (pursuer, candidate) pairs are evaluated one per lane
+// on waves 0..2 while lanes of wave 3 find the P headings; no atomics, no scratch, no host read.
+__global__ __launch_bounds__(pepath::THREADS) void k_pathfinder(const pe_config c, const pe_state st, const pe_pathfinder_params prm, const double itau,
+                                                                const double i6, int32_t *__restrict__ actions, const pe_pathfinder_diag dg,
+                                                                int32_t *__restrict__ sweeps_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    using namespace pepath;
+    const int env = blockIdx.x, tid = threadIdx.x, W = c.W, H = c.H, WH = W * H, P = c.P;
+    const size_t WH16 = ((size_t)WH + 15) & ~(size_t)15;
+    double *def = (double *)smem;                      // [4][P]
+    double *eva = def + 4 * P;                         // [4]
+    int32_t *D = (int32_t *)(eva + 4);                 // [WH]
+    int32_t *flag = D + WH;                            // [2][4] "this wave changed a cell", by sweep parity (+ padding to 16)
+    int32_t *kst = flag + 16;                          // [PE_MAX_P]
+    uint16_t *nb = (uint16_t *)(kst + PE_MAX_P);       // [WH]
+    uint8_t *grid = (uint8_t *)(nb + WH);              // [WH]
+    uint8_t *pen = grid + WH16;                        // [WH]
+    uint8_t *bl = pen + WH16;                          // [P][16] candidate k of pursuer i is blocked
+    uint8_t *cr = bl + 16 * PE_MAX_P;                  // [P][16] ... is crowded
+    const uint8_t *gsrc = st.grid + (size_t)env * WH;
+    if ((WH & 3) == 0 && (((uintptr_t)gsrc) & 3) == 0) {
+        for (int i = tid; i < (WH >> 2); i += THREADS) ((uint32_t *)grid)[i] = ((const uint32_t *)gsrc)[i];
+    } else {
+        for (int i = tid; i < WH; i += THREADS) grid[i] = gsrc[i];
+    }
+    if (tid < 4 * P) def[tid] = st.def[(size_t)env * 4 * P + tid];
+    if (tid < 4) eva[tid] = st.eva[(size_t)env * 4 + tid];
+    __syncthreads();
+    const int s = cell_id(c, eva[0], eva[1]);
+    for (int id = tid; id < WH; id += THREADS) {
+        const int x = id / H;
+        pen[id] = pen_cell(c, grid, x, id - x * H, s);
+        D[id] = id == s ? 0 : UNREACHED;
+    }
+    __syncthreads();
+    for (int id = tid; id < WH; id += THREADS) {
+        const int x = id / H;
+        nb[id] = neighbour_word(c, grid, pen, x, id - x * H, s);
+    }
+    __syncthreads();
+    bool capped = false;
+    int sweep = 0;
+    for (;; sweep++) {   // leaves after at most W*H sweeps
+        bool changed = false;
+        for (int id = tid; id < WH; id += THREADS) {
+            const uint32_t w = nb[id];
+            if (w == 0 || id == s) continue;
+            int kb;
+            const int32_t v = relax_cell(w, D, id, H, prm.clearance, &kb);
+            if (v < D[id]) { D[id] = v; changed = true; }
+        }
+        const bool wave_changed = __ballot(changed) != 0ull;
+        if ((tid & (WAVE - 1)) == 0) flag[(sweep & 1) * 4 + (tid >> 6)] = wave_changed ? 1 : 0;
+        __syncthreads();
+        const int32_t *f = flag + (sweep & 1) * 4;
+        if ((f[0] | f[1] | f[2] | f[3]) == 0) break;
+        if (sweep + 1 >= WH) { capped = true; break; }
+    }
+    if (tid < P * 9) {
+        const int i = tid / 9, k = tid - 9 * i;
+        bool b, n;
+        candidate_flags(c, itau, i6, grid, def, i, k, prm.sep_range * prm.sep_range, &b, &n);
+        bl[i * 16 + k] = b ? 1 : 0;
+        cr[i * 16 + k] = n ? 1 : 0;
+    } else if (tid >= 3 * WAVE && tid - 3 * WAVE < P) {
+        const int i = tid - 3 * WAVE;
+        kst[i] = heading(c, grid, D, nb, prm, def[i], def[P + i], eva);
+    }
+    __syncthreads();
+    if (tid < P) {
+        uint32_t bm = 0, cm = 0;
+        for (int k = 0; k < 9; k++) { bm |= (uint32_t)bl[tid * 16 + k] << k; cm |= (uint32_t)cr[tid * 16 + k] << k; }
+        actions[(size_t)env * P + tid] = choose(kst[tid], bm, cm);
+        if (dg.kstar) dg.kstar[(size_t)env * P + tid] = kst[tid];
+        if (dg.blocked) dg.blocked[(size_t)env * P + tid] = (uint16_t)bm;
+    }
+    if (dg.field)
+        for (int id = tid; id < WH; id += THREADS) dg.field[(size_t)env * WH + id] = D[id];
+    if (sweeps_out && tid == 0) sweeps_out[env] = sweep + 1;
+    if (capped && tid == 0) st.meta[(size_t)env * PE_META_INTS + PE_META_STATUS] |= PE_STATUS_PATH_CAP;
+}
+
+int pathfinder_check(const pe_config *c, const pe_pathfinder_params *prm, pe_pathfinder_params *out) {
+    if (c->W < 2 || c->H < 2 || c->W > 255 || c->H > 255 || c->W * c->H > PE_PATH_MAX_CELLS) return PE_ERR_BAD_CONFIG;
+    if (c->P < 2 || c->P > PE_MAX_P) return PE_ERR_BAD_CONFIG;
+    if (!(c->action_u[0][0] > 0.0) || std::isinf(c->action_u[0][0]) || !(c->def_tau > 0.0) || std::isinf(c->def_tau)) return PE_ERR_BAD_CONFIG;
+    if (!(c->def_collision_radius >= 0.0) || std::isinf(c->def_collision_radius) || !std::isfinite(c->def_dt)) return PE_ERR_BAD_CONFIG;
+    if (prm) *out = *prm;
+    else { out->lead = 0.5; out->sep_range = 2.0 * c->def_collision_radius; out->clearance = 10; }
+    out->pad0 = 0;
+    if (!(out->lead >= 0.0) || std::isinf(out->lead) || !(out->sep_range >= 0.0) || std::isinf(out->sep_range)) return PE_ERR_BAD_CONFIG;
+    if (out->clearance < 0 || out->clearance > 1000) return PE_ERR_BAD_CONFIG;
+    return 0;
 }
 
 __global__ void k_diag_norm2(int n, const double *a, const double *b, double *out, double c0, double y0, double c1, double y1) {
@@ -1579,6 +1700,73 @@ int pe_diag_launch_plan(const pe_config *cfg, int32_t form, pe_launch_plan *out)
     const int rc = pe_config_check(cfg);
     if (rc) return rc;
     *out = plan_launch(*cfg, (form & PE_FORM_OBS) != 0, (form & PE_FORM_EVA) != 0, (form & PE_FORM_REPLAN) != 0).p;
+    return 0;
+}
+
+static int launch_pathfinder(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, int32_t *actions, const pe_pathfinder_diag *diag,
+                             int32_t *sweeps, void *stream) {
+    if (!cfg || !st || !actions) return PE_ERR_NULL;
+    pe_pathfinder_params p;
+    const int rc = pathfinder_check(cfg, prm, &p);
+    if (rc) return rc;
+    if (st->N <= 0) return 0;
+    if (!st->grid || !st->def || !st->eva || !st->meta) return PE_ERR_NULL;
+    pe_pathfinder_diag dg;
+    memset(&dg, 0, sizeof dg);
+    if (diag) dg = *diag;
+    const size_t lds = pepath::lds_bytes(cfg->W * cfg->H, cfg->P);
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)k_pathfinder, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(k_pathfinder, dim3(st->N), dim3(pepath::THREADS), lds, (hipStream_t)stream, *cfg, *st, p, div_const_reciprocal(cfg->def_tau),
+                       div_const_reciprocal(6.0), actions, dg, sweeps);
+    return (int)hipGetLastError();
+}
+
+int pe_pursuer_pathfinder(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, int32_t *actions, const pe_pathfinder_diag *diag,
+                          void *stream) {
+    return launch_pathfinder(cfg, st, prm, actions, diag, nullptr, stream);
+}
+
+int pe_diag_pathfinder_sweeps(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, int32_t *actions, int32_t *sweeps, void *stream) {
+    if (!sweeps) return PE_ERR_NULL;
+    return launch_pathfinder(cfg, st, prm, actions, nullptr, sweeps, stream);
+}
+
+int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const double *def, const double *eva,
+                               const pe_pathfinder_params *prm, int32_t *actions, const pe_pathfinder_diag *diag) {
+    if (!cfg || !actions) return PE_ERR_NULL;
+    pe_pathfinder_params p;
+    const int rc = pathfinder_check(cfg, prm, &p);
+    if (rc) return rc;
+    if (N <= 0) return 0;
+    if (!grid || !def || !eva) return PE_ERR_NULL;
+    const pe_config &c = *cfg;
+    const int WH = c.W * c.H, P = c.P;
+    const double itau = div_const_reciprocal(c.def_tau), i6 = div_const_reciprocal(6.0);
+    std::vector<int32_t> D(WH);
+    std::vector<uint16_t> nb(WH);
+    std::vector<uint8_t> pen(WH);
+    for (int n = 0; n < N; n++) {
+        const uint8_t *g = grid + (size_t)n * WH;
+        const double *d = def + (size_t)n * 4 * P, *e = eva + (size_t)n * 4;
+        pepath::field_host(c, g, pepath::cell_id(c, e[0], e[1]), p.clearance, D.data(), pen.data(), nb.data());
+        if (diag && diag->field) memcpy(diag->field + (size_t)n * WH, D.data(), sizeof(int32_t) * WH);
+        for (int i = 0; i < P; i++) {
+            uint32_t bm = 0, cm = 0;
+            for (int k = 0; k < 9; k++) {
+                bool b, q;
+                pepath::candidate_flags(c, itau, i6, g, d, i, k, p.sep_range * p.sep_range, &b, &q);
+                bm |= (uint32_t)b << k;
+                cm |= (uint32_t)q << k;
+            }
+            const int ks = pepath::heading(c, g, D.data(), nb.data(), p, d[i], d[P + i], e);
+            actions[(size_t)n * P + i] = pepath::choose(ks, bm, cm);
+            if (diag && diag->kstar) diag->kstar[(size_t)n * P + i] = ks;
+            if (diag && diag->blocked) diag->blocked[(size_t)n * P + i] = (uint16_t)bm;
+        }
+    }
     return 0;
 }
 

@@ -12,14 +12,16 @@ import torch
 
 from . import ops
 from .mappo import MAPPO
+from .pursuit_baseline import EpisodeStats
 from .pursuit_env import Pursuit_Env
 
 
 @torch.no_grad()
-def evaluate(env, actor, cfg, init=None, return_actions=False):
+def evaluate(env, actor, cfg, init=None, return_actions=False, stats=None):
     """evaluator.py:106-201: one greedy episode per environment with the actor's PRIVATE history (hop k reads the
     actor's own embedding of step t-1-k).  Returns [episode_reward (N,), last step index T-1] like the reference
-    (which returns the last loop index, not a count)."""
+    (which returns the last loop index, not a count).  stats: a dict that receives the five episode quantities of
+    pursuit_baseline.STAT_KEYS for the network (accumulated on the device, one host read at the end); None changes nothing."""
     device = next(actor.parameters()).device
     env.reset(init)
     N, P, T = env.num_envs, env.num_defender, env.max_steps
@@ -33,6 +35,7 @@ def evaluate(env, actor, cfg, init=None, return_actions=False):
     raw = torch.zeros(N, P, device=device)
     obs = env.sim.new_obs(packed=True)  # LiDAR rows bit-packed, as in the rollout
     actions = []
+    acc = EpisodeStats(N, device) if stats is not None else None
     env.observe(obs)
     env.attacker_step()
     step = 0
@@ -52,6 +55,10 @@ def evaluate(env, actor, cfg, init=None, return_actions=False):
             env.sim.step(a_n, reward, raw)
             env.time_step += 1
         episode_reward += raw.sum(-1)
+        if acc is not None:
+            acc.add(raw, step)
+    if acc is not None:
+        stats.update(acc.result())
     out = [episode_reward, step]
     if return_actions:
         out.append(torch.stack(actions, 1))  # (N, T, P)

@@ -24,6 +24,14 @@ runtime.guidance_lead / guidance_sep_range / guidance_sep_gain) for one episode 
 prints the JSON keys of `--evaluate`, the yardstick to read a training log against:
 
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg5 --baseline guidance --eval-envs 2048
+
+`--baseline pathfinder` and `--baseline demon` are the same for the pursuit configurations (cfg1..cfg4): one episode of the scripted
+path-finding pursuers (pursuit_baseline.py; runtime.pathfinder_lead / pathfinder_sep_range / pathfinder_clearance),
+or of the reference's wall-blind `demon`, on --eval-envs environments of the evaluator's seeds; one JSON line with eval_return,
+eval_capture_rate, eval_first_contact, eval_contact_steps and eval_collision_steps:
+
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg2 --baseline pathfinder --eval-envs 2048
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg2 --baseline demon --eval-envs 2048
 """
 import argparse
 import json
@@ -36,6 +44,7 @@ from .e3d_agent import E3dTrainer, train_e3d
 from .guidance import BASELINES as SCRIPTED_BASELINES
 from .n2n_agent import N2nTrainer, train_n2n
 from .particle_agent import episode_triple
+from .pursuit_baseline import BASELINES as PURSUIT_BASELINES
 from .trainer import train_agent_multiprocessing
 
 BASELINES = ("cfg1", "cfg2", "cfg3", "cfg4", "cfg5", "cfg4_n2n")
@@ -51,16 +60,22 @@ def main(argv=None):
     ap.add_argument("--resume", metavar="DIR", default=None, help="load DIR/resume_rank{r}.pt before the first iteration")
     ap.add_argument("--evaluate", metavar="CWD", default=None,
                     help="env_3d / env_n2n: evaluate the weights saved under CWD on --eval-envs environments and exit")
-    ap.add_argument("--baseline", choices=SCRIPTED_BASELINES, default=None,
-                    help="env_3d / env_n2n: run the scripted pursuers on --eval-envs environments of the evaluation seeds and exit (no model)")
+    ap.add_argument("--baseline", choices=SCRIPTED_BASELINES + PURSUIT_BASELINES, default=None,
+                    help="run the scripted pursuers on --eval-envs environments of the evaluation seeds and exit (no model): guidance on "
+                         "env_3d / env_n2n, pathfinder or demon on the pursuit configurations")
     ap.add_argument("overrides", nargs="*", help="dotted overrides KEY=VALUE")
     args = ap.parse_args(argv)
     ov = parse_overrides(args.overrides)
     cfg = baseline_config(args.config, **ov) if args.config in BASELINES else load_config(args.config, **ov)
     env = str(cfg.runtime.get("env", "pursuit"))
+    if args.baseline in PURSUIT_BASELINES:
+        if env in ("e3d", "n2n"):
+            ap.error(f"--baseline {args.baseline} is for the pursuit configurations (cfg1..cfg4); runtime.env {env} takes --baseline guidance")
+        return baseline_pursuit(cfg, args.baseline, args.eval_envs)
     if args.baseline is not None:
         if env not in ("e3d", "n2n"):
-            ap.error("--baseline is for runtime.env e3d and n2n (cfg5, cfg4_n2n); the pursuit configurations have no scripted pursuers")
+            ap.error("--baseline guidance is for runtime.env e3d and n2n (cfg5, cfg4_n2n); the pursuit configurations take "
+                     "--baseline pathfinder or --baseline demon")
         return baseline_guidance(cfg, env, args.eval_envs)
     if args.evaluate is not None:
         if env not in ("e3d", "n2n"):
@@ -97,6 +112,17 @@ def baseline_guidance(cfg, env_kind, num_eval_envs):
     ret, captured, length = episode_triple(mod.guidance_episode(env))
     r, c, l = torch.stack((ret.mean(), captured.float().mean(), length.mean())).tolist()
     res = dict(eval_return=r, eval_capture_rate=c, eval_episode_length=l)
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def baseline_pursuit(cfg, policy, num_eval_envs):
+    """one episode of the scripted pursuers of a pursuit configuration on num_eval_envs environments with the evaluator's seed rule
+    (Pursuit_Env(cfg, num_envs, rank=10_000), the environments EvaluatorProc starts from); prints the five keys as one JSON line.  No
+    model, no process group."""
+    from .pursuit_baseline import scripted_episode
+    from .pursuit_env import Pursuit_Env
+    res = scripted_episode(Pursuit_Env(cfg, num_envs=int(num_eval_envs), rank=10_000), cfg, policy)
     print(json.dumps(res), flush=True)
     return res
 

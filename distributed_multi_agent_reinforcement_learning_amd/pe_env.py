@@ -64,6 +64,50 @@ class PeLaunchPlan(C.Structure):
                [(n, C.c_double) for n in ("inv_def_tau", "inv_eva_tau", "inv_six")]
 
 
+class PePathfinderParams(C.Structure):
+    """include/pe_env.h pe_pathfinder_params"""
+    _fields_ = [("lead", C.c_double), ("sep_range", C.c_double), ("clearance", C.c_int32), ("pad0", C.c_int32)]
+
+
+class PePathfinderDiag(C.Structure):
+    """include/pe_env.h pe_pathfinder_diag"""
+    _fields_ = [("field", C.c_void_p), ("kstar", C.c_void_p), ("blocked", C.c_void_p)]
+
+
+PATH_MAX_CELLS = 8192
+PATH_UNREACHED = 0x7FFFFFFF
+STATUS_PATH_CAP = 16
+
+
+def pathfinder_params(pe_cfg, lead=None, sep_range=None, clearance=None):
+    """the pathfinder's parameters with the defaults of include/pe_env.h (lead 0.5, sep_range 2 collision radii, clearance 10)"""
+    p = PePathfinderParams()
+    p.lead = 0.5 if lead is None else float(lead)
+    p.sep_range = 2.0 * pe_cfg.def_collision_radius if sep_range is None else float(sep_range)
+    p.clearance = 10 if clearance is None else int(clearance)
+    return p
+
+
+def pathfinder_host(pe_cfg, grid, defs, eva, lead=None, sep_range=None, clearance=None, diag=False):
+    """pe_pursuer_pathfinder_host on host arrays laid out like the device records: grid (N, W*H) u8, defs (N, 4, P) f64, eva (N, 4) f64.
+    Returns the (N, P) int32 actions, with diag=True also a dict of field (N, W*H) i32, kstar (N, P) i32, blocked (N, P) u16."""
+    L = load_library()
+    c = pe_cfg
+    g = np.ascontiguousarray(grid, np.uint8).reshape(-1, c.W * c.H)
+    N = g.shape[0]
+    d = np.ascontiguousarray(defs, np.float64).reshape(N, 4, c.P)
+    e = np.ascontiguousarray(eva, np.float64).reshape(N, 4)
+    prm = pathfinder_params(c, lead, sep_range, clearance)
+    actions = np.full((N, c.P), -1, np.int32)
+    dg, out = PePathfinderDiag(), None
+    if diag:
+        out = dict(field=np.zeros((N, c.W * c.H), np.int32), kstar=np.zeros((N, c.P), np.int32), blocked=np.zeros((N, c.P), np.uint16))
+        dg.field, dg.kstar, dg.blocked = _np(out["field"]), _np(out["kstar"]), _np(out["blocked"])
+    _check(L.pe_pursuer_pathfinder_host(C.byref(c), N, _np(g), _np(d), _np(e), C.byref(prm), _np(actions), C.byref(dg) if diag else None),
+           "pe_pursuer_pathfinder_host")
+    return (actions, out) if diag else actions
+
+
 FORM_STEP, FORM_OBS, FORM_EVA, FORM_REPLAN = 1, 2, 4, 8
 # the launch form of every entry point (pe_env_diag.h); evader_step and tick also exist with FORM_REPLAN
 FORMS = dict(observe=FORM_OBS, step=FORM_STEP, step_observe=FORM_STEP | FORM_OBS, evader_step=FORM_EVA, tick=FORM_STEP | FORM_OBS | FORM_EVA,
@@ -79,7 +123,8 @@ def launch_plan(pe_cfg, form):
 
 
 EXPORTS = ("pe_config_check", "pe_tick_lds_bytes", "pe_env_load", "pe_env_observe", "pe_evader_step", "pe_env_step",
-           "pe_env_demon", "pe_env_tick", "pe_env_step_observe", "pe_astar_batch", "pe_error_string")
+           "pe_env_demon", "pe_env_tick", "pe_env_step_observe", "pe_astar_batch", "pe_pursuer_pathfinder", "pe_pursuer_pathfinder_host",
+           "pe_error_string")
 
 _lib = None
 
@@ -123,6 +168,9 @@ def load_library():
         L.pe_reset_state_bytes.restype = C.c_int64
         L.pe_env_reset_seed.argtypes = [vp, C.c_int32, vp, vp, vp]
         L.pe_env_reset.argtypes = [vp, vp, vp, vp, C.c_int32, vp, C.c_int32, vp]
+        L.pe_pursuer_pathfinder.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.pe_diag_pathfinder_sweeps.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.pe_pursuer_pathfinder_host.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.pe_error_string.argtypes = [C.c_int]
         L.pe_error_string.restype = C.c_char_p
         _lib = L
@@ -131,7 +179,8 @@ def load_library():
 
 STATUS_NAMES = ((1, "target tape exhausted (raise runtime.tape_len)"), (2, "A* iteration cap reached"),
                 (4, "stored path tail underflow (raise runtime.max_path)"),
-                (8, "episode reset gave up: no valid placement after PE_RESET_MAX_DRAWS draws (map too crowded for this configuration)"))
+                (8, "episode reset gave up: no valid placement after PE_RESET_MAX_DRAWS draws (map too crowded for this configuration)"),
+                (16, "the pathfinder's distance field hit its sweep bound"))
 
 
 def status_or(meta):
@@ -372,6 +421,31 @@ class BatchedEnv:
         dirs = (C.c_double * 18)(*[v for cs in tables.action_table(1.0) for v in cs])
         _check(self.L.pe_env_demon(C.byref(self.c), C.byref(self.st), dirs, _ptr(out), _stream()), "pe_env_demon")
         return out
+
+    def pathfinder(self, out=None, lead=None, sep_range=None, clearance=None, diag=False):
+        """The scripted path-finding pursuers (include/pe_env.h pe_pursuer_pathfinder) for every environment ->
+        (N, P) int32 actions, the tensor `tick` takes; one launch on the current stream, no host read.  diag=True (or a dict of tensors
+        to fill) also returns field (N, W*H) i32, kstar (N, P) i32 and blocked (N, P) i16 (bit k: candidate k fails the static-map probe)."""
+        self._join()
+        c, N = self.c, self.N
+        if out is None:
+            out = torch.empty((N, c.P), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (N, c.P)
+        prm = pathfinder_params(c, lead, sep_range, clearance)
+        dg = PePathfinderDiag()
+        if diag:
+            if not isinstance(diag, dict):
+                diag = dict(field=torch.empty((N, c.W * c.H), dtype=torch.int32, device=self.device),
+                            kstar=torch.empty((N, c.P), dtype=torch.int32, device=self.device),
+                            blocked=torch.empty((N, c.P), dtype=torch.int16, device=self.device))
+            for k, dt in (("field", torch.int32), ("kstar", torch.int32), ("blocked", torch.int16)):
+                t = diag.get(k)
+                if t is not None:
+                    assert t.dtype == dt and t.is_contiguous(), k
+                    setattr(dg, k, t.data_ptr())
+        _check(self.L.pe_pursuer_pathfinder(C.byref(c), C.byref(self.st), C.byref(prm), _ptr(out), C.byref(dg) if diag else None, _stream()),
+               "pe_pursuer_pathfinder")
+        return (out, diag) if diag else out
 
     def _actions(self, actions):
         if actions.dtype != torch.int32:

@@ -171,6 +171,12 @@ class Pursuit_Env:
         (one launch, csrc/pe_env.hip k_demon; pinned by the demon actions recorded in the reference traces)."""
         return self.sim.demon()
 
+    def pathfinder(self, **kw):
+        """the scripted path-finding pursuers: actions from an obstacle-aware distance field to the evader, each
+        checked against the tick's own static-map probe -> (N, P) int32 (one launch, csrc/pe_env.hip k_pathfinder); the keyword
+        arguments are BatchedEnv.pathfinder's"""
+        return self.sim.pathfinder(**kw)
+
     def get_done(self):
         return self.time_step >= self.max_steps
 

@@ -454,8 +454,14 @@ def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval
     `runtime.async_eval: false` (or async_eval=False) evaluates inline on rank 0 (deterministic recorder rows per iteration).
     save_resume: a directory each rank writes its resume bundle to after every iteration; resume: the directory each rank loads its
     bundle from before the first one (main --save-resume / --resume)."""
-    from . import ray_shim
+    from . import pursuit_baseline, ray_shim
+    baseline_kind = pursuit_baseline.eval_baseline_options(cfg)   # validated before anything is built
     tr = Trainer(cfg)
+    tr.baseline = None
+    if baseline_kind is not None and tr.rank == 0:
+        # the yardstick (DESIGN.md 7n): one scripted episode on an evaluation environment of its own, once, before the first iteration
+        tr.baseline = pursuit_baseline.eval_baseline(cfg, baseline_kind, num_eval_envs)
+        print(json.dumps(tr.baseline), flush=True)
     if resume is not None:
         tr.load_resume(resume_path(resume, tr.rank))
     if async_eval is None:

@@ -37,7 +37,8 @@ extern "C" {
 enum { PE_META_T = 0, PE_META_PATH_LEN = 1, PE_META_TAPE_POS = 2, PE_META_COLLISION = 3, PE_META_PATH_CNT = 4,
        PE_META_ASTAR_EXP = 5, PE_META_STATUS = 6, PE_META_WP_HEAD = 7 /* waypoints popped since the last replan */ };
 /* meta[PE_META_STATUS] bits */
-enum { PE_STATUS_TAPE_EXHAUSTED = 1, PE_STATUS_ASTAR_CAP = 2, PE_STATUS_PATH_UNDERFLOW = 4, PE_STATUS_RESET_FAILED = 8 };
+enum { PE_STATUS_TAPE_EXHAUSTED = 1, PE_STATUS_ASTAR_CAP = 2, PE_STATUS_PATH_UNDERFLOW = 4, PE_STATUS_RESET_FAILED = 8,
+       PE_STATUS_PATH_CAP = 16 /* the pathfinder's distance field hit its W*H sweep bound (pe_pursuer_pathfinder) */ };
 /* The bits are STICKY on the device-reset path: pe_env_reset carries the finished episode's bits into the new episode's meta
  * record, so one read of meta[:, PE_META_STATUS] after any reset (or at any later time) reports every condition raised since
  * pe_env_reset_seed.  pe_env_load (host initial conditions) starts from 0. */
@@ -205,6 +206,27 @@ int pe_env_step_observe(const pe_config *cfg, const pe_state *st, const int32_t 
  * (true length, expansions). */
 int pe_astar_batch(int32_t W, int32_t H, int32_t n, const uint8_t *obs, const int32_t *sg, int16_t *out_path,
                    int32_t *out_len, int32_t max_path, void *stream);
+
+/* The scripted path-finding pursuers (the law is restated in tests/pe_pathfinder_ref.py): one launch, no
+ * host synchronisation, capturable in a graph.  Per environment an int32 distance field to the evader's cell over the occupancy
+ * grid (steps 10 / 14, no corner cutting, `clearance` added on cells that touch an obstacle), relaxed in LDS until a sweep
+ * changes nothing; per pursuer a desired heading (straight at a led aim point under a clear line of sight, else down the field) and
+ * the first of nine candidates, ordered around that heading, that the tick's own static-map probe accepts and that does not close on
+ * a lower-indexed team-mate within sep_range.  The sweep loop is bounded by W*H; hitting the bound sets PE_STATUS_PATH_CAP in
+ * meta[PE_META_STATUS].  Limits: W*H <= PE_PATH_MAX_CELLS, 2 <= P <= PE_MAX_P, action_u[0][0] > 0; anything else is
+ * PE_ERR_BAD_CONFIG before any launch.  prm == NULL selects the defaults (lead 0.5, sep_range 2 def_collision_radius, clearance 10). */
+#define PE_PATH_MAX_CELLS 8192
+#define PE_PATH_UNREACHED 0x7fffffff
+typedef struct pe_pathfinder_params { double lead, sep_range; int32_t clearance, pad0; } pe_pathfinder_params;
+/* optional outputs (any member, or the whole record, may be NULL): field [N][W*H] the distance field, kstar [N][P] the desired
+ * heading (0..7, 8 = none), blocked [N][P] bit k set when candidate k is rejected by the static-map probe (all nine bits) */
+typedef struct pe_pathfinder_diag { int32_t *field; int32_t *kstar; uint16_t *blocked; } pe_pathfinder_diag;
+/* actions: DEVICE [N][P] int32, the tensor pe_env_tick takes; diag members are DEVICE pointers */
+int pe_pursuer_pathfinder(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, int32_t *actions,
+                          const pe_pathfinder_diag *diag, void *stream);
+/* The host twin: the same row functions on HOST arrays laid out like the device records (grid [N][W*H], def [N][4][P], eva [N][4]). */
+int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const double *def, const double *eva,
+                               const pe_pathfinder_params *prm, int32_t *actions, const pe_pathfinder_diag *diag);
 
 const char *pe_error_string(int code);
 

@@ -42,6 +42,11 @@ typedef struct pe_launch_plan {
 } pe_launch_plan;
 int pe_diag_launch_plan(const pe_config *cfg, int32_t form, pe_launch_plan *out);
 
+/* pe_pursuer_pathfinder with one more output: sweeps [N] int32 (DEVICE), the sweeps the distance field of each environment took,
+ * the last one (which changed nothing) included.  Measurement only. */
+int pe_diag_pathfinder_sweeps(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, int32_t *actions, int32_t *sweeps,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif
