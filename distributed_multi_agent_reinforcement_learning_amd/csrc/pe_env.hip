@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include <cmath>
+#include <mutex>
 #include <vector>
 
 #include "pe_env.h"
@@ -1001,9 +1002,13 @@ namespace {
 // final values everywhere, so the loop ends exactly at the fixed point -- or at the W*H trip bound (a shortest path has fewer than W*H
 // edges and every sweep settles one more), which sets PE_STATUS_PATH_CAP.  The P x 9 (pursuer, candidate) pairs are evaluated one per lane
 // on waves 0..2 while lanes of wave 3 find the P headings; no atomics, no scratch, no host read.
-__global__ __launch_bounds__(pepath::THREADS) void k_pathfinder(const pe_config c, const pe_state st, const pe_pathfinder_params prm, const double itau,
-                                                                const double i6, int32_t *__restrict__ actions, const pe_pathfinder_diag dg,
-                                                                int32_t *__restrict__ sweeps_out) {
+// TEACH (k_pathfinder_teach, section 7o): the same body with a per-environment cached field and the imitation labels.  A hit loads D
+// from the cache and skips the sweeps; pen and nb are rebuilt either way (they depend on s: two passes, not a relaxation).  The
+// environment's workgroup is the only writer of its cache rows, so the counter and the key are plain stores.
+template <bool TEACH>
+__device__ __forceinline__ void pathfinder_body(const pe_config &c, const pe_state &st, const pe_pathfinder_params &prm, const double itau, const double i6,
+                                                int32_t *__restrict__ actions, const pe_pathfinder_diag &dg, int32_t *__restrict__ sweeps_out,
+                                                const pe_pathfinder_cache &ca, const pe_pathfinder_label &lb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using namespace pepath;
     const int env = blockIdx.x, tid = threadIdx.x, W = c.W, H = c.H, WH = W * H, P = c.P;
@@ -1028,10 +1033,16 @@ __global__ __launch_bounds__(pepath::THREADS) void k_pathfinder(const pe_config 
     if (tid < 4) eva[tid] = st.eva[(size_t)env * 4 + tid];
     __syncthreads();
     const int s = cell_id(c, eva[0], eva[1]);
+    bool hit = false;
+    if (TEACH && ca.key) hit = ca.key[2 * (size_t)env] == s && ca.key[2 * (size_t)env + 1] == prm.clearance;   // uniform over the workgroup
+    if (hit) {
+        const int32_t *fsrc = ca.field + (size_t)env * WH;
+        for (int id = tid; id < WH; id += THREADS) D[id] = fsrc[id];
+    }
     for (int id = tid; id < WH; id += THREADS) {
         const int x = id / H;
         pen[id] = pen_cell(c, grid, x, id - x * H, s);
-        D[id] = id == s ? 0 : UNREACHED;
+        if (!hit) D[id] = id == s ? 0 : UNREACHED;
     }
     __syncthreads();
     for (int id = tid; id < WH; id += THREADS) {
@@ -1041,7 +1052,7 @@ __global__ __launch_bounds__(pepath::THREADS) void k_pathfinder(const pe_config 
     __syncthreads();
     bool capped = false;
     int sweep = 0;
-    for (;; sweep++) {   // leaves after at most W*H sweeps
+    for (; !hit; sweep++) {   // leaves after at most W*H sweeps
         bool changed = false;
         for (int id = tid; id < WH; id += THREADS) {
             const uint32_t w = nb[id];
@@ -1057,6 +1068,18 @@ __global__ __launch_bounds__(pepath::THREADS) void k_pathfinder(const pe_config 
         if ((f[0] | f[1] | f[2] | f[3]) == 0) break;
         if (sweep + 1 >= WH) { capped = true; break; }
     }
+    if (TEACH && ca.key) {
+        if (hit) {
+            if (ca.hits && tid == 0) ca.hits[env] = ca.hits[env] + 1;
+        } else {   // every lane is past the barrier that followed its read of the key
+            int32_t *fdst = ca.field + (size_t)env * WH;
+            for (int id = tid; id < WH; id += THREADS) fdst[id] = D[id];
+            if (tid == 0) {
+                ca.key[2 * (size_t)env] = capped ? -1 : s;
+                ca.key[2 * (size_t)env + 1] = prm.clearance;
+            }
+        }
+    }
     if (tid < P * 9) {
         const int i = tid / 9, k = tid - 9 * i;
         bool b, n;
@@ -1071,14 +1094,31 @@ __global__ __launch_bounds__(pepath::THREADS) void k_pathfinder(const pe_config 
     if (tid < P) {
         uint32_t bm = 0, cm = 0;
         for (int k = 0; k < 9; k++) { bm |= (uint32_t)bl[tid * 16 + k] << k; cm |= (uint32_t)cr[tid * 16 + k] << k; }
-        actions[(size_t)env * P + tid] = choose(kst[tid], bm, cm);
+        const int32_t a = choose(kst[tid], bm, cm);
+        if (!TEACH || actions) actions[(size_t)env * P + tid] = a;
+        if (TEACH) {
+            if (lb.a_star) lb.a_star[(size_t)env * (size_t)lb.a_star_env_stride + tid] = (float)a;
+            if (lb.follow && lb.follow[env] != 0) lb.action[(size_t)env * P + tid] = a;
+        }
         if (dg.kstar) dg.kstar[(size_t)env * P + tid] = kst[tid];
         if (dg.blocked) dg.blocked[(size_t)env * P + tid] = (uint16_t)bm;
     }
     if (dg.field)
         for (int id = tid; id < WH; id += THREADS) dg.field[(size_t)env * WH + id] = D[id];
-    if (sweeps_out && tid == 0) sweeps_out[env] = sweep + 1;
+    if (sweeps_out && tid == 0) sweeps_out[env] = hit ? 0 : sweep + 1;
     if (capped && tid == 0) st.meta[(size_t)env * PE_META_INTS + PE_META_STATUS] |= PE_STATUS_PATH_CAP;
+}
+
+__global__ __launch_bounds__(pepath::THREADS) void k_pathfinder(const pe_config c, const pe_state st, const pe_pathfinder_params prm, const double itau,
+                                                                const double i6, int32_t *__restrict__ actions, const pe_pathfinder_diag dg,
+                                                                int32_t *__restrict__ sweeps_out) {
+    pathfinder_body<false>(c, st, prm, itau, i6, actions, dg, sweeps_out, pe_pathfinder_cache{}, pe_pathfinder_label{});
+}
+
+__global__ __launch_bounds__(pepath::THREADS) void k_pathfinder_teach(const pe_config c, const pe_state st, const pe_pathfinder_params prm, const double itau,
+                                                                      const double i6, int32_t *__restrict__ actions, const pe_pathfinder_diag dg,
+                                                                      const pe_pathfinder_cache ca, const pe_pathfinder_label lb) {
+    pathfinder_body<true>(c, st, prm, itau, i6, actions, dg, nullptr, ca, lb);
 }
 
 int pathfinder_check(const pe_config *c, const pe_pathfinder_params *prm, pe_pathfinder_params *out) {
@@ -1703,6 +1743,13 @@ int pe_diag_launch_plan(const pe_config *cfg, int32_t form, pe_launch_plan *out)
     return 0;
 }
 
+// the two instances' launch: argument checks, the raise of the dynamic-LDS limit (once per instance) and the launch itself
+static int pathfinder_lds(const void *kernel, std::once_flag &once, hipError_t &raised, size_t lds) {
+    if (lds <= 48 * 1024) return 0;
+    std::call_once(once, [&] { raised = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pepath::lds_bytes(PE_PATH_MAX_CELLS, PE_MAX_P)); });
+    return (int)raised;
+}
+
 static int launch_pathfinder(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, int32_t *actions, const pe_pathfinder_diag *diag,
                              int32_t *sweeps, void *stream) {
     if (!cfg || !st || !actions) return PE_ERR_NULL;
@@ -1715,10 +1762,10 @@ static int launch_pathfinder(const pe_config *cfg, const pe_state *st, const pe_
     memset(&dg, 0, sizeof dg);
     if (diag) dg = *diag;
     const size_t lds = pepath::lds_bytes(cfg->W * cfg->H, cfg->P);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_pathfinder, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    static std::once_flag once;
+    static hipError_t raised = hipSuccess;
+    const int e = pathfinder_lds((const void *)k_pathfinder, once, raised, lds);
+    if (e) return e;
     hipLaunchKernelGGL(k_pathfinder, dim3(st->N), dim3(pepath::THREADS), lds, (hipStream_t)stream, *cfg, *st, p, div_const_reciprocal(cfg->def_tau),
                        div_const_reciprocal(6.0), actions, dg, sweeps);
     return (int)hipGetLastError();
@@ -1734,15 +1781,48 @@ int pe_diag_pathfinder_sweeps(const pe_config *cfg, const pe_state *st, const pe
     return launch_pathfinder(cfg, st, prm, actions, nullptr, sweeps, stream);
 }
 
-int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const double *def, const double *eva,
-                               const pe_pathfinder_params *prm, int32_t *actions, const pe_pathfinder_diag *diag) {
-    if (!cfg || !actions) return PE_ERR_NULL;
-    pe_pathfinder_params p;
-    const int rc = pathfinder_check(cfg, prm, &p);
+// what both teach entry points refuse beyond pathfinder_check; fills the records a NULL stands for
+static int teach_check(const pe_config *cfg, const pe_pathfinder_params *prm, const pe_pathfinder_cache *cache, const pe_pathfinder_label *label,
+                       pe_pathfinder_params *p, pe_pathfinder_cache *ca, pe_pathfinder_label *lb) {
+    if (!cfg) return PE_ERR_NULL;
+    const int rc = pathfinder_check(cfg, prm, p);
     if (rc) return rc;
-    if (N <= 0) return 0;
-    if (!grid || !def || !eva) return PE_ERR_NULL;
-    const pe_config &c = *cfg;
+    memset(ca, 0, sizeof *ca);
+    memset(lb, 0, sizeof *lb);
+    if (cache) *ca = *cache;
+    if (label) *lb = *label;
+    if (cache && (!ca->field || !ca->key)) return PE_ERR_NULL;
+    if (lb->follow && !lb->action) return PE_ERR_NULL;
+    if (lb->a_star && lb->a_star_env_stride < cfg->P) return PE_ERR_BAD_CONFIG;
+    return 0;
+}
+
+int pe_pursuer_pathfinder_teach(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, const pe_pathfinder_cache *cache,
+                                const pe_pathfinder_label *label, int32_t *actions, const pe_pathfinder_diag *diag, void *stream) {
+    if (!st) return PE_ERR_NULL;
+    pe_pathfinder_params p;
+    pe_pathfinder_cache ca;
+    pe_pathfinder_label lb;
+    const int rc = teach_check(cfg, prm, cache, label, &p, &ca, &lb);
+    if (rc) return rc;
+    if (st->N <= 0) return 0;
+    if (!st->grid || !st->def || !st->eva || !st->meta) return PE_ERR_NULL;
+    pe_pathfinder_diag dg;
+    memset(&dg, 0, sizeof dg);
+    if (diag) dg = *diag;
+    const size_t lds = pepath::lds_bytes(cfg->W * cfg->H, cfg->P);
+    static std::once_flag once;
+    static hipError_t raised = hipSuccess;
+    const int e = pathfinder_lds((const void *)k_pathfinder_teach, once, raised, lds);
+    if (e) return e;
+    hipLaunchKernelGGL(k_pathfinder_teach, dim3(st->N), dim3(pepath::THREADS), lds, (hipStream_t)stream, *cfg, *st, p, div_const_reciprocal(cfg->def_tau),
+                       div_const_reciprocal(6.0), actions, dg, ca, lb);
+    return (int)hipGetLastError();
+}
+
+// the host twin of both instances: ca / lb all NULL is the plain pathfinder
+static void pathfinder_rows_host(const pe_config &c, int32_t N, const uint8_t *grid, const double *def, const double *eva, const pe_pathfinder_params &p,
+                                 const pe_pathfinder_cache &ca, const pe_pathfinder_label &lb, int32_t *actions, const pe_pathfinder_diag *diag) {
     const int WH = c.W * c.H, P = c.P;
     const double itau = div_const_reciprocal(c.def_tau), i6 = div_const_reciprocal(6.0);
     std::vector<int32_t> D(WH);
@@ -1751,7 +1831,19 @@ int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *g
     for (int n = 0; n < N; n++) {
         const uint8_t *g = grid + (size_t)n * WH;
         const double *d = def + (size_t)n * 4 * P, *e = eva + (size_t)n * 4;
-        pepath::field_host(c, g, pepath::cell_id(c, e[0], e[1]), p.clearance, D.data(), pen.data(), nb.data());
+        const int s = pepath::cell_id(c, e[0], e[1]);
+        if (ca.key && ca.key[2 * (size_t)n] == s && ca.key[2 * (size_t)n + 1] == p.clearance) {
+            memcpy(D.data(), ca.field + (size_t)n * WH, sizeof(int32_t) * WH);
+            pepath::words_host(c, g, s, pen.data(), nb.data());
+            if (ca.hits) ca.hits[n] += 1;
+        } else {
+            const int sweeps = pepath::field_host(c, g, s, p.clearance, D.data(), pen.data(), nb.data());
+            if (ca.key) {
+                memcpy(ca.field + (size_t)n * WH, D.data(), sizeof(int32_t) * WH);
+                ca.key[2 * (size_t)n] = sweeps < 0 ? -1 : s;
+                ca.key[2 * (size_t)n + 1] = p.clearance;
+            }
+        }
         if (diag && diag->field) memcpy(diag->field + (size_t)n * WH, D.data(), sizeof(int32_t) * WH);
         for (int i = 0; i < P; i++) {
             uint32_t bm = 0, cm = 0;
@@ -1762,11 +1854,39 @@ int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *g
                 cm |= (uint32_t)q << k;
             }
             const int ks = pepath::heading(c, g, D.data(), nb.data(), p, d[i], d[P + i], e);
-            actions[(size_t)n * P + i] = pepath::choose(ks, bm, cm);
+            const int32_t a = pepath::choose(ks, bm, cm);
+            if (actions) actions[(size_t)n * P + i] = a;
+            if (lb.a_star) lb.a_star[(size_t)n * (size_t)lb.a_star_env_stride + i] = (float)a;
+            if (lb.follow && lb.follow[n] != 0) lb.action[(size_t)n * P + i] = a;
             if (diag && diag->kstar) diag->kstar[(size_t)n * P + i] = ks;
             if (diag && diag->blocked) diag->blocked[(size_t)n * P + i] = (uint16_t)bm;
         }
     }
+}
+
+int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const double *def, const double *eva,
+                               const pe_pathfinder_params *prm, int32_t *actions, const pe_pathfinder_diag *diag) {
+    if (!cfg || !actions) return PE_ERR_NULL;
+    pe_pathfinder_params p;
+    const int rc = pathfinder_check(cfg, prm, &p);
+    if (rc) return rc;
+    if (N <= 0) return 0;
+    if (!grid || !def || !eva) return PE_ERR_NULL;
+    pathfinder_rows_host(*cfg, N, grid, def, eva, p, pe_pathfinder_cache{}, pe_pathfinder_label{}, actions, diag);
+    return 0;
+}
+
+int pe_pursuer_pathfinder_teach_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const double *def, const double *eva,
+                                     const pe_pathfinder_params *prm, const pe_pathfinder_cache *cache, const pe_pathfinder_label *label,
+                                     int32_t *actions, const pe_pathfinder_diag *diag) {
+    pe_pathfinder_params p;
+    pe_pathfinder_cache ca;
+    pe_pathfinder_label lb;
+    const int rc = teach_check(cfg, prm, cache, label, &p, &ca, &lb);
+    if (rc) return rc;
+    if (N <= 0) return 0;
+    if (!grid || !def || !eva) return PE_ERR_NULL;
+    pathfinder_rows_host(*cfg, N, grid, def, eva, p, ca, lb, actions, diag);
     return 0;
 }
 

@@ -147,16 +147,20 @@ __host__ __device__ inline int choose(int kstar, uint32_t blocked, uint32_t crow
     return 8;
 }
 
-// the host's schedule: in-place sweeps, forwards and backwards in turn, until one changes nothing.  Returns the sweeps, -1 at the bound.
-inline int field_host(const pe_config &c, const uint8_t *grid, int s, int32_t clearance, int32_t *D, uint8_t *pen, uint16_t *nb) {
-    const int W = c.W, H = c.H, WH = W * H;
+// the penalty bits and neighbour words of source s: all a cached field needs rebuilt around it (they depend on s, two passes)
+inline void words_host(const pe_config &c, const uint8_t *grid, int s, uint8_t *pen, uint16_t *nb) {
+    const int W = c.W, H = c.H;
     for (int x = 0; x < W; x++)
         for (int y = 0; y < H; y++) pen[x * H + y] = pen_cell(c, grid, x, y, s);
     for (int x = 0; x < W; x++)
-        for (int y = 0; y < H; y++) {
-            nb[x * H + y] = neighbour_word(c, grid, pen, x, y, s);
-            D[x * H + y] = UNREACHED;
-        }
+        for (int y = 0; y < H; y++) nb[x * H + y] = neighbour_word(c, grid, pen, x, y, s);
+}
+
+// the host's schedule: in-place sweeps, forwards and backwards in turn, until one changes nothing.  Returns the sweeps, -1 at the bound.
+inline int field_host(const pe_config &c, const uint8_t *grid, int s, int32_t clearance, int32_t *D, uint8_t *pen, uint16_t *nb) {
+    const int H = c.H, WH = c.W * H;
+    words_host(c, grid, s, pen, nb);
+    for (int id = 0; id < WH; id++) D[id] = UNREACHED;
     D[s] = 0;
     for (int sweep = 0; sweep < WH; sweep++) {
         bool changed = false;

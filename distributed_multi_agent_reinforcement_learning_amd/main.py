@@ -32,6 +32,12 @@ eval_capture_rate, eval_first_contact, eval_contact_steps and eval_collision_ste
 
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg2 --baseline pathfinder --eval-envs 2048
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg2 --baseline demon --eval-envs 2048
+
+algo.pathfinder_bc_iterations=K (cfg1..cfg4) makes the first K iterations an imitation warm start from the path-finding pursuers
+(pursuit_imitation.py; algo.pathfinder_bc_beta / pathfinder_bc_beta_decay / pathfinder_bc_lr,
+runtime.pathfinder_cache); each prints one JSON line with phase, bc_beta, bc_loss, bc_accuracy, critic_loss and pathfinder_hit_rate:
+
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg2 algo.pathfinder_bc_iterations=60 runtime.eval_baseline=pathfinder
 """
 import argparse
 import json

@@ -22,6 +22,8 @@ from .imitation import refuse_pursuit
 from .kickstart import refuse_pursuit as refuse_pursuit_kickstart
 from .model import build_actor_critic, pair_embeddings, pair_heads, sequence_forward_pair
 from .pe_env import status_or, status_text
+from .pursuit_baseline import pathfinder_options
+from .pursuit_imitation import follow_count, pursuit_imitation_options
 from .team_reward import team_reward_options
 from .update_diag import UpdateDiag, update_diag_options
 
@@ -63,6 +65,7 @@ class ReplayBuffer:
         self.p_dim = self.e_dim = self.o_dim = cfg.env.state_dim
         self.embedding_size = cfg.algo.embedding_dim
         self.depth = cfg.algo.depth
+        self.labelled = pursuit_imitation_options(cfg).on   # algo.pathfinder_bc_iterations > 0: the field a_star exists
         self.buffer = None
 
     def reset_buffer(self):
@@ -82,6 +85,8 @@ class ReplayBuffer:
         b["a_logprob_n"] = z(N, T, P)
         b["r"] = z(N, T, P)
         b["active"] = z(N, T, P)
+        if self.labelled:
+            b["a_star"] = z(N, T, P)   # the teacher's action of every tick (MAPPO.explore_expert)
         self.o_static = z(N, O, self.o_dim)
         self.o_kvalid = torch.zeros(N, dtype=torch.int32, device=self.device)
         b["o_state"] = self.o_static[:, None].expand(N, T, O, self.o_dim)
@@ -229,6 +234,9 @@ class MAPPO:
                              "reference's (leave target_kl out; algo.update_diagnostics reports the KL)")
         refuse_pursuit(cfg)   # algo.bc_iterations: env_3d / env_n2n only
         refuse_pursuit_kickstart(cfg)   # algo.bc_coef: likewise
+        # algo.pathfinder_bc_iterations: the flagship's own warm start, from the path-finding pursuers
+        self.pathfinder_bc = pursuit_imitation_options(cfg)
+        self.pathfinder_kw = pathfinder_options(cfg) if self.pathfinder_bc.on else None   # runtime.pathfinder_*: the teacher's parameters
         self.update_diagnostics, _ = update_diag_options(cfg)   # what the update did, from the loss launches
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
         self.epsilon, self.K_epochs, self.entropy_coef = a.epsilon, a.epochs, a.entropy_coef
@@ -274,9 +282,26 @@ class MAPPO:
         self.last_adv = self.last_v_target = None
         self.diag = UpdateDiag(self.device) if self.update_diagnostics else None
         self.last_update_diag = None   # algo.update_diagnostics: the dict of the last train() call
+        self._update_diag = self.diag   # the diagnostics of the train() call in progress (None in an imitation update)
+        self._imitating = False
+        # the imitation metric: (label hits, live rows) of one train(imitation=True) call, added to by every loss launch
+        self.bc_sums = torch.zeros(ops.BC_SUMS, dtype=torch.float64, device=self.device) if self.pathfinder_bc.on else None
+        self.bc_allreduce = None       # the trainer's allreduce_sum_: the two sums over ranks, in place
+        self.last_bc = None            # (hits, rows) of the last train(imitation=True) call
+        self.last_hit_rate = None      # explore_expert: cache hits / (environments x teacher launches) of the last call
 
     # ---- update (:638-723) ------------------------------------------------------------------------------------
-    def train(self, replay_buffer, total_steps, return_grads=True):
+    def train(self, replay_buffer, total_steps, return_grads=True, imitation=False):
+        """imitation (algo.pathfinder_bc_iterations): GAE, the mini-batch loop or _train_grouped, the accumulate-then-clip replay and the
+        gradient bucket as ever; the mini-batch loss is ops.bc_loss_cat on buffer["a_star"] (_minibatch_losses), the update diagnostics
+        and the learning-rate decay are skipped, and the two sums of the metric go over ranks and arrive in the call's one host read
+        (last_bc; bc_accuracy = hits / rows)."""
+        if imitation and self.bc_sums is None:
+            raise ValueError("train(imitation=True) needs algo.pathfinder_bc_iterations > 0 (the buffer has no a_star field otherwise)")
+        self._imitating = bool(imitation)
+        self._update_diag = None if imitation else self.diag
+        if imitation:
+            self.bc_sums.zero_()
         batch = replay_buffer.get_training_data(self.device) if hasattr(replay_buffer, "get_training_data") else replay_buffer.buffer
         o_static = replay_buffer.o_static
         N, T, P = batch["r"].shape
@@ -291,8 +316,8 @@ class MAPPO:
             self.grad_bucket.zero()          # persistent flat gradient storage (trainer.GradBucket): zeroed, not dropped
         else:
             self.ac_optimizer.zero_grad()
-        if self.diag is not None:   # algo.update_diagnostics: every loss call adds its eight sums (_minibatch_losses)
-            self.diag.begin()
+        if self._update_diag is not None:   # algo.update_diagnostics: every loss call adds its eight sums (_minibatch_losses)
+            self._update_diag.begin()
         starts = list(range(0, N, self.mini_batch_size))  # BatchSampler(SequentialSampler, mini_batch_size, drop_last=False)
         G = self._update_group(len(starts), min(self.mini_batch_size, N) * P, T)
         while G > 1:
@@ -311,8 +336,10 @@ class MAPPO:
                     self.grad_bucket.zero()
                 else:
                     self.ac_optimizer.zero_grad()
-                if self.diag is not None:
-                    self.diag.begin()
+                if self._update_diag is not None:
+                    self._update_diag.begin()
+                if imitation:
+                    self.bc_sums.zero_()
                 torch.cuda.empty_cache()
         for n0 in starts:
             n1 = min(n0 + self.mini_batch_size, N)
@@ -327,15 +354,21 @@ class MAPPO:
             (actor_loss + critic_loss).backward()
             if self.use_grad_clip:  # on the gradients accumulated so far, after every mini-batch
                 norm = torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
-                if self.diag is not None:
-                    self.diag.note_grad_norm(norm)
+                if self._update_diag is not None:
+                    self._update_diag.note_grad_norm(norm)
             object_critics = object_critics + critic_loss.detach().double()   # f64 sum on the device: no host sync per mini-batch
             object_actors = object_actors + actor_loss.detach().double()
             update_time += 1
-        if self.diag is not None:   # one read for the two losses, the eight sums and the gradient norm
-            (object_critics, object_actors), self.last_update_diag = self.diag.read(object_critics, object_actors)
+        if self._update_diag is not None:   # one read for the two losses, the eight sums and the gradient norm
+            (object_critics, object_actors), self.last_update_diag = self._update_diag.read(object_critics, object_actors)
+        if imitation:   # one read for the two losses and the two sums (all-reduced over ranks)
+            if self.bc_allreduce is not None:
+                self.bc_allreduce(self.bc_sums)
+            object_critics, object_actors, hits, live = torch.cat((torch.stack((object_critics, object_actors)), self.bc_sums)).tolist()
+            self.last_bc = (hits, live)
         object_critics, object_actors = float(object_critics), float(object_actors)
-        if self.use_lr_decay:
+        self._imitating, self._update_diag = False, self.diag
+        if self.use_lr_decay and not imitation:
             self.lr_decay(total_steps)
         if not return_grads:  # device-side path: gradients stay in .grad for the flat all-reduce
             return object_critics / update_time, object_actors / update_time, None, None
@@ -356,7 +389,14 @@ class MAPPO:
 
     def _minibatch_losses(self, batch, adv, v_target, n0, n1, prob, values_now):
         v_old = batch["v_n"][n0:n1, :-1] if self.use_value_clip else None
-        dk = {} if self.diag is None else {"diag": self.diag.sums}   # algo.update_diagnostics: the loss call adds its eight sums
+        if self._imitating:   # -log prob of the teacher's action; the critic's loss with the bits of ppo_loss_prob's
+            values = values_now.squeeze(-1)
+            if not ops.ppo_loss_prob_ok(prob, values):
+                raise RuntimeError("train(imitation=True): ops.ppo_loss_prob_ok(prob, values) does not hold (fp32 device tensors, prob (mb, T, P, "
+                                   "A <= 16) with a dense last dimension, values (mb, T, P)); the imitation loss has no other path")
+            return ops.bc_loss_cat(prob, batch["a_star"][n0:n1], values, batch["active"][n0:n1], v_old, v_target[n0:n1], self.epsilon,
+                                   self.use_value_clip, sums=self.bc_sums)
+        dk = {} if self._update_diag is None else {"diag": self._update_diag.sums}   # algo.update_diagnostics: the loss call adds its eight sums
         if ops.ppo_loss_prob_ok(prob, values_now.squeeze(-1)):
             # Categorical(prob).log_prob / .entropy() (get_logprob_and_entropy, :451-456) evaluated inside the loss launch
             return ops.ppo_loss_prob(prob, batch["a_n"][n0:n1], values_now.squeeze(-1), batch["a_logprob_n"][n0:n1], adv[n0:n1], batch["active"][n0:n1],
@@ -436,11 +476,31 @@ class MAPPO:
                 torch._foreach_add_(main_grads, segs.grads(k))
                 if self.use_grad_clip:  # on the gradients accumulated so far, after every mini-batch
                     norm = torch.nn.utils.clip_grad_norm_(self.ac_parameters, 5.0)
-                    if self.diag is not None:
-                        self.diag.note_grad_norm(norm)
+                    if self._update_diag is not None:
+                        self._update_diag.note_grad_norm(norm)
                 object_critics = object_critics + critic_loss.detach().double()
                 object_actors = object_actors + actor_loss.detach().double()
         return object_critics, object_actors
+
+    def bc_accuracy(self):
+        """the share of live rows whose argmax was the teacher's action in the last train(imitation=True) call"""
+        hits, live = self.last_bc
+        return hits / live if live else float("nan")
+
+    def set_lr(self, lr):
+        for p in self.ac_optimizer.param_groups:
+            p["lr"] = lr
+
+    def reset_optimizer(self, total_steps):
+        """the step from the imitation phase to PPO: Adam's moments and step count back to zero (the moments of a supervised loss say
+        nothing about the PPO gradient) and the learning rate back on the schedule"""
+        for st in self.ac_optimizer.state.values():
+            for key in ("step", "exp_avg", "exp_avg_sq"):
+                st[key].zero_()
+        if self.use_lr_decay:
+            self.lr_decay(total_steps)
+        else:
+            self.set_lr(self.lr)
 
     def lr_decay(self, total_steps):
         lr_now = self.lr * (1 - total_steps / self.max_train_steps)
@@ -449,33 +509,67 @@ class MAPPO:
         self.total_step = total_steps
 
     # ---- rollout (:731-827) -----------------------------------------------------------------------------------
-    def explore_env(self, env, num_episode, actions_override=None, init=None):
+    def explore_expert(self, env, num_episode, beta):
+        """explore_env with the teacher in the loop (algo.pathfinder_bc_iterations): every tick also takes one
+        env.pathfinder_teach launch between the policy step and the record -- the path-finding pursuers' actions become the labels
+        buffer["a_star"][:, t] of every environment and replace the network's in environments 0 .. round(beta N) - 1, which the record
+        launch then stores in a_n as executed.  v_n, a_logprob_n, the embeddings, the sampling counter and the tick's reward-norm state
+        are the network episode's own: a_logprob_n of a followed environment is the log-probability of the network's sample, not of
+        the executed action (the imitation loss does not read it)."""
+        if not self.pathfinder_bc.on:
+            raise ValueError("explore_expert needs algo.pathfinder_bc_iterations > 0 (the buffer has no a_star field otherwise)")
+        follow = torch.zeros(env.num_envs, dtype=torch.uint8, device=self.device)
+        follow[:follow_count(beta, env.num_envs)] = 1
+        return self.explore_env(env, num_episode, follow=follow)
+
+    def _teacher_cache(self, env):
+        """the teacher's distance-field cache for this environment batch (runtime.pathfinder_cache: false = None, every launch recomputes)"""
+        if not self.pathfinder_bc.cache:
+            return None
+        cache = getattr(self, "_pf_cache", None)
+        if cache is None or cache.field.shape[0] != env.num_envs or cache.field.device != env.sim.device:
+            cache = self._pf_cache = env.pathfinder_cache()
+        return cache
+
+    def explore_env(self, env, num_episode, actions_override=None, init=None, follow=None):
         N = env.num_envs
+        cache = self._teacher_cache(env) if follow is not None else None
+        if cache is not None:
+            cache.hits.zero_()
+        teach = {} if follow is None else dict(follow=follow, cache=cache)
         self.minibuffer = ReplayBuffer(self.cfg, N * num_episode, self.device).reset_buffer()
         exp_reward = 0.0
         sample_steps = 0
         for k in range(num_episode):
-            ep_reward, ep_steps = self.run_episode(env, num_episode=k, actions_override=actions_override, init=init)
+            ep_reward, ep_steps = self.run_episode(env, num_episode=k, actions_override=actions_override, init=init, **teach)
             # one read-back per episode: the mean return and the kernels' status bits (tape exhausted / A* cap / path
             # underflow silently break parity with the reference, so they are an error, not a statistic)
-            mean_r, bits = torch.stack((ep_reward.mean().double(), status_or(env.sim.meta).double())).tolist()
+            # (explore_expert: the cache's hit count so far rides in the same read)
+            tail = () if cache is None else (cache.hits.sum().double(),)
+            mean_r, bits, *hits = torch.stack((ep_reward.mean().double(), status_or(env.sim.meta).double(), *tail)).tolist()
             if bits:
                 raise RuntimeError("environment kernel status: " + status_text(int(bits)))
             exp_reward += float(mean_r)
             sample_steps += ep_steps * N
+        if follow is not None:
+            self.last_hit_rate = hits[0] / sample_steps if cache is not None else 0.0
         return exp_reward / num_episode, self.minibuffer, sample_steps
 
     @torch.no_grad()
-    def run_episode(self, env, num_episode=0, actions_override=None, init=None):
+    def run_episode(self, env, num_episode=0, actions_override=None, init=None, follow=None, cache=None):
         """N episodes in lockstep; rows [num_episode*N, (num_episode+1)*N) of the buffer.  Returns the per-environment
         episode reward (N,) and the episode length.  The per-tick policy program (actor + critic forward, history
         bookkeeping, sampling) runs on static device storage and is replayed as one captured hipGraph per tick
         (`runtime.use_graphs`), which removes ~70 launches of host overhead per tick; the eager path executes the very same
-        program, so both produce identical buffers."""
+        program, so both produce identical buffers.
+        follow (explore_expert): the (N,) uint8 mask of the environments that execute the teacher's action; every tick is labelled.
+        cache: the teacher's distance-field cache or None; emptied here after the reset, which rewrites the grid."""
         N, P, T, d = env.num_envs, env.num_defender, env.max_steps, self.depth
         buf = self.minibuffer.buffer
         rows = slice(num_episode * N, (num_episode + 1) * N)
         env.reset(init)
+        if cache is not None:
+            cache.clear()
         st = self._rollout_state(env)
         st.reset(env)
         self.minibuffer.o_static[rows].copy_(st.o_state)
@@ -494,6 +588,8 @@ class MAPPO:
                 st.replay_policy_step()
             else:
                 st.step()
+            if follow is not None:   # the teacher: labels for everybody, its action over the sample where follow is set (one launch)
+                env.pathfinder_teach(cache=cache, follow=follow, action=st.a_n, a_star=buf["a_star"][rows, t], **self.pathfinder_kw)
             items += [(st.v, buf["v_n"][rows, t]), (st.a_n, buf["a_n"][rows, t]),      # int32 -> float32 like the reference buffer
                       (st.logp, buf["a_logprob_n"][rows, t])]
             if d or self.record_unused_embeddings:  # the update reads the stored embeddings as FCRA history only (EmbeddingDataset2, :95-113)

@@ -74,6 +74,16 @@ class PePathfinderDiag(C.Structure):
     _fields_ = [("field", C.c_void_p), ("kstar", C.c_void_p), ("blocked", C.c_void_p)]
 
 
+class PePathfinderCache(C.Structure):
+    """include/pe_env.h pe_pathfinder_cache"""
+    _fields_ = [("field", C.c_void_p), ("key", C.c_void_p), ("hits", C.c_void_p)]
+
+
+class PePathfinderLabel(C.Structure):
+    """include/pe_env.h pe_pathfinder_label"""
+    _fields_ = [("follow", C.c_void_p), ("action", C.c_void_p), ("a_star", C.c_void_p), ("a_star_env_stride", C.c_int64)]
+
+
 PATH_MAX_CELLS = 8192
 PATH_UNREACHED = 0x7FFFFFFF
 STATUS_PATH_CAP = 16
@@ -108,6 +118,41 @@ def pathfinder_host(pe_cfg, grid, defs, eva, lead=None, sep_range=None, clearanc
     return (actions, out) if diag else actions
 
 
+def pathfinder_teach_host(pe_cfg, grid, defs, eva, cache=None, follow=None, action=None, a_star=None, lead=None, sep_range=None, clearance=None,
+                          diag=False):
+    """pe_pursuer_pathfinder_teach_host on host arrays laid out like pathfinder_host's.  cache: a dict of field (N, W*H) i32, key (N, 2)
+    i32 and optionally hits (N,) i32, updated in place; follow (N,) u8 and action (N, P) i32 (in/out); a_star: a float32 array or row
+    view whose first axis is the environment and whose last P elements per environment are contiguous.  Returns like pathfinder_host."""
+    L = load_library()
+    c = pe_cfg
+    g = np.ascontiguousarray(grid, np.uint8).reshape(-1, c.W * c.H)
+    N = g.shape[0]
+    d = np.ascontiguousarray(defs, np.float64).reshape(N, 4, c.P)
+    e = np.ascontiguousarray(eva, np.float64).reshape(N, 4)
+    prm = pathfinder_params(c, lead, sep_range, clearance)
+    actions = np.full((N, c.P), -1, np.int32)
+    ca, lb = PePathfinderCache(), PePathfinderLabel()
+    if cache is not None:
+        for k in ("field", "key", "hits"):
+            if cache.get(k) is not None:
+                assert cache[k].dtype == np.int32 and cache[k].flags.c_contiguous, k
+                setattr(ca, k, _np(cache[k]))
+    for k, a, dt in (("follow", follow, np.uint8), ("action", action, np.int32)):
+        if a is not None:
+            assert a.dtype == dt and a.flags.c_contiguous, k
+            setattr(lb, k, _np(a))
+    if a_star is not None:
+        assert a_star.dtype == np.float32 and a_star.shape[0] == N and a_star.shape[-1] == c.P and a_star.strides[-1] == 4 and a_star.strides[0] % 4 == 0
+        lb.a_star, lb.a_star_env_stride = _np(a_star), a_star.strides[0] // 4
+    dg, out = PePathfinderDiag(), None
+    if diag:
+        out = dict(field=np.zeros((N, c.W * c.H), np.int32), kstar=np.zeros((N, c.P), np.int32), blocked=np.zeros((N, c.P), np.uint16))
+        dg.field, dg.kstar, dg.blocked = _np(out["field"]), _np(out["kstar"]), _np(out["blocked"])
+    _check(L.pe_pursuer_pathfinder_teach_host(C.byref(c), N, _np(g), _np(d), _np(e), C.byref(prm), C.byref(ca) if cache is not None else None,
+                                              C.byref(lb), _np(actions), C.byref(dg) if diag else None), "pe_pursuer_pathfinder_teach_host")
+    return (actions, out) if diag else actions
+
+
 FORM_STEP, FORM_OBS, FORM_EVA, FORM_REPLAN = 1, 2, 4, 8
 # the launch form of every entry point (pe_env_diag.h); evader_step and tick also exist with FORM_REPLAN
 FORMS = dict(observe=FORM_OBS, step=FORM_STEP, step_observe=FORM_STEP | FORM_OBS, evader_step=FORM_EVA, tick=FORM_STEP | FORM_OBS | FORM_EVA,
@@ -124,7 +169,7 @@ def launch_plan(pe_cfg, form):
 
 EXPORTS = ("pe_config_check", "pe_tick_lds_bytes", "pe_env_load", "pe_env_observe", "pe_evader_step", "pe_env_step",
            "pe_env_demon", "pe_env_tick", "pe_env_step_observe", "pe_astar_batch", "pe_pursuer_pathfinder", "pe_pursuer_pathfinder_host",
-           "pe_error_string")
+           "pe_pursuer_pathfinder_teach", "pe_pursuer_pathfinder_teach_host", "pe_error_string")
 
 _lib = None
 
@@ -171,6 +216,8 @@ def load_library():
         L.pe_pursuer_pathfinder.argtypes = [vp, vp, vp, vp, vp, vp]
         L.pe_diag_pathfinder_sweeps.argtypes = [vp, vp, vp, vp, vp, vp]
         L.pe_pursuer_pathfinder_host.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
+        L.pe_pursuer_pathfinder_teach.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.pe_pursuer_pathfinder_teach_host.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pe_error_string.argtypes = [C.c_int]
         L.pe_error_string.restype = C.c_char_p
         _lib = L
@@ -243,6 +290,22 @@ def _np(a):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class PathfinderCache:
+    """The per-environment cached distance field of `BatchedEnv.pathfinder_teach` (include/pe_env.h pe_pathfinder_cache): field (N, W*H)
+    i32, key (N, 2) i32 (source cell, -1 = empty; clearance) and hits (N,) i32, counted up by the kernel on every hit."""
+
+    def __init__(self, N, WH, device):
+        self.field = torch.zeros((N, WH), dtype=torch.int32, device=device)
+        self.key = torch.full((N, 2), -1, dtype=torch.int32, device=device)
+        self.hits = torch.zeros((N,), dtype=torch.int32, device=device)
+        self.struct = PePathfinderCache()
+        self.struct.field, self.struct.key, self.struct.hits = self.field.data_ptr(), self.key.data_ptr(), self.hits.data_ptr()
+
+    def clear(self):
+        """empties every key (one device fill, capturable); the fields stay and are never read under an empty key"""
+        self.key[:, 0].fill_(-1)
 
 
 class BatchedEnv:
@@ -445,6 +508,50 @@ class BatchedEnv:
                     setattr(dg, k, t.data_ptr())
         _check(self.L.pe_pursuer_pathfinder(C.byref(c), C.byref(self.st), C.byref(prm), _ptr(out), C.byref(dg) if diag else None, _stream()),
                "pe_pursuer_pathfinder")
+        return (out, diag) if diag else out
+
+    def pathfinder_cache(self):
+        """a fresh, empty `PathfinderCache` for this batch of environments"""
+        return PathfinderCache(self.N, self.c.W * self.c.H, self.device)
+
+    def pathfinder_teach(self, out=None, cache=None, follow=None, action=None, a_star=None, lead=None, sep_range=None, clearance=None, diag=False):
+        """The pathfinder as a teacher (include/pe_env.h pe_pursuer_pathfinder_teach): `pathfinder`'s actions from
+        one launch that may reuse the distance field of the last launch and writes the imitation labels.  out: (N, P) int32 or None (not
+        written); cache: a `pathfinder_cache()` or None; follow (N,) uint8 with action (N, P) int32: the rows of `action` whose follow byte
+        is set are overwritten with the teacher's; a_star: float32, every row receives the teacher's action -- a contiguous (N, P) tensor
+        or a row view buf[rows, t] of an (N, T, P) one, the stride is taken from the view.
+        THE CALLER clears the cache (`cache.clear()`) after anything that writes the grid (`load`, a resetter's `reset`): a key only names
+        the evader's cell and the clearance, and nothing here guesses whether the map under it is still the same."""
+        self._join()
+        c, N = self.c, self.N
+        if out is not None:
+            assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (N, c.P)
+        prm = pathfinder_params(c, lead, sep_range, clearance)
+        lb = PePathfinderLabel()
+        if follow is not None:
+            assert follow.dtype == torch.uint8 and follow.is_contiguous() and follow.shape == (N,)
+            lb.follow = follow.data_ptr()
+        if action is not None:
+            assert action.dtype == torch.int32 and action.is_contiguous() and action.shape == (N, c.P)
+            lb.action = action.data_ptr()
+        if a_star is not None:
+            assert a_star.dtype == torch.float32 and a_star.shape == (N, c.P) and (c.P == 1 or a_star.stride(1) == 1)
+            lb.a_star, lb.a_star_env_stride = a_star.data_ptr(), a_star.stride(0) if N > 1 else c.P
+        dg = PePathfinderDiag()
+        if diag:
+            if not isinstance(diag, dict):
+                diag = dict(field=torch.empty((N, c.W * c.H), dtype=torch.int32, device=self.device),
+                            kstar=torch.empty((N, c.P), dtype=torch.int32, device=self.device),
+                            blocked=torch.empty((N, c.P), dtype=torch.int16, device=self.device))
+            for k, dt in (("field", torch.int32), ("kstar", torch.int32), ("blocked", torch.int16)):
+                t = diag.get(k)
+                if t is not None:
+                    assert t.dtype == dt and t.is_contiguous(), k
+                    setattr(dg, k, t.data_ptr())
+        if cache is not None:
+            assert cache.field.shape == (N, c.W * c.H)
+        _check(self.L.pe_pursuer_pathfinder_teach(C.byref(c), C.byref(self.st), C.byref(prm), C.byref(cache.struct) if cache is not None else None,
+                                                  C.byref(lb), _ptr(out), C.byref(dg) if diag else None, _stream()), "pe_pursuer_pathfinder_teach")
         return (out, diag) if diag else out
 
     def _actions(self, actions):

@@ -177,6 +177,16 @@ class Pursuit_Env:
         arguments are BatchedEnv.pathfinder's"""
         return self.sim.pathfinder(**kw)
 
+    def pathfinder_cache(self):
+        """an empty distance-field cache for `pathfinder_teach` (BatchedEnv.pathfinder_cache)"""
+        return self.sim.pathfinder_cache()
+
+    def pathfinder_teach(self, **kw):
+        """the pathfinder as a teacher: the same actions from one launch that may reuse a cached distance field
+        and writes the imitation labels (csrc/pe_env.hip k_pathfinder_teach); the keyword arguments are BatchedEnv.pathfinder_teach's.
+        The caller clears the cache after `reset`."""
+        return self.sim.pathfinder_teach(**kw)
+
     def get_done(self):
         return self.time_step >= self.max_steps
 

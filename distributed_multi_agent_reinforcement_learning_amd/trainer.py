@@ -21,6 +21,7 @@ from .imitation import check_entry as check_imitation_entry
 from .kickstart import check_entry as check_kickstart_entry
 from .minibatch_steps import check_entry as check_minibatch_steps_entry
 from .pursuit_env import Pursuit_Env
+from .pursuit_imitation import check_entry as check_pursuit_imitation_entry
 from .obs_norm import check_entry as check_obs_norm_entry
 from .value_norm import check_entry as check_value_norm_entry
 
@@ -370,29 +371,47 @@ class Trainer:
         self.agent.grad_bucket = self.bucket
         if self.agent.diag is not None:
             self.agent.diag.allreduce = allreduce_sum_   # algo.update_diagnostics: the eight sums over ranks; no group, no collective
+        self.agent.bc_allreduce = allreduce_sum_   # algo.pathfinder_bc_iterations: the two sums of the imitation metric, likewise
+        self.last_imitation = None   # the log entries of the last iteration when it was an imitation iteration
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.total_steps = 0
         self.iteration = 0
         self.last_log = (0.0, 0.0)
 
     def iterate(self):
-        """rollout + `epochs` updates; returns (env_steps_this_iteration_all_ranks, exp_reward)."""
+        """rollout + `epochs` updates; returns (env_steps_this_iteration_all_ranks, exp_reward).
+        algo.pathfinder_bc_iterations K: iterations 0 .. K - 1 imitate the path-finding pursuers (explore_expert, train(imitation=True)
+        at the constant rate pathfinder_bc_lr); iteration K starts PPO from cleared Adam moments.  The phase
+        follows from `iteration` alone, so a resumed run continues in it."""
         cfg, agent = self.cfg, self.agent
+        bc = agent.pathfinder_bc
+        imitating = self.iteration < bc.iterations
+        if bc.on and self.iteration == bc.iterations:
+            agent.reset_optimizer(self.total_steps)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
-        exp_r, buffer, steps = agent.explore_env(self.env, int(cfg.algo.sample_epi_num))
+        if imitating:
+            beta = bc.beta_at(self.iteration)
+            agent.set_lr(bc.lr)
+            exp_r, buffer, steps = agent.explore_expert(self.env, int(cfg.algo.sample_epi_num), beta)
+        else:
+            exp_r, buffer, steps = agent.explore_env(self.env, int(cfg.algo.sample_epi_num))
         ev[1].record()
         self.env.prefetch_reset()  # the next episode's reset (device: kernels on the side stream; host: a thread) runs while the GPU runs the update
         self.total_steps += steps * self.world
         for _ in range(int(cfg.algo.epochs)):
             with torch.enable_grad():
-                obj_c, obj_a, _, _ = agent.train(buffer, self.total_steps, return_grads=False)
+                obj_c, obj_a, _, _ = agent.train(buffer, self.total_steps, return_grads=False, **({"imitation": True} if imitating else {}))
             allreduce_sum_(self.bucket.flat)      # gradient SUM over ranks, in place in the bucket the optimiser reads
             agent.ac_optimizer.step()
-            if cfg.algo.use_lr_decay:
+            if cfg.algo.use_lr_decay and not imitating:
                 agent.lr_decay(self.total_steps)
             self.last_log = (obj_c, obj_a)
         ev[2].record()
+        self.last_imitation = None
+        if imitating:   # of the last update of the iteration, like last_log; the hit rate is this rank's rollout's
+            self.last_imitation = dict(phase="imitation", bc_beta=beta, bc_loss=self.last_log[1], bc_accuracy=agent.bc_accuracy(),
+                                       critic_loss=self.last_log[0], pathfinder_hit_rate=agent.last_hit_rate)
         self.iteration += 1
         self.last_events = ev  # (rollout incl. host reset, update) timings: read after a synchronize
         return steps * self.world, exp_r
@@ -410,6 +429,8 @@ class Trainer:
                       tape_pos=(env.sim.meta[:, 2] if pre is None else pre["tape_pos"]).cpu(), sample_counter=None if st is None else st.counter.cpu(),
                       resetter=env.resetter.get_state() if pre is None else env.resetter.get_state(pre["resetter"]), next_init=init,
                       num_envs=self.num_envs, world=self.world, rank=self.rank)
+        if agent.pathfinder_bc.on:   # algo.pathfinder_bc_iterations: the phase of an iteration follows from it and `iteration`; off: no entry
+            bundle["pathfinder_bc_iterations"] = agent.pathfinder_bc.iterations
         torch.save(bundle, path)
         if init is not None:
             env._prefetch = (_Done(), {"init": init})
@@ -419,6 +440,7 @@ class Trainer:
         if b["num_envs"] != self.num_envs or b["world"] != self.world:
             raise ValueError("resume bundle was written for another num_envs / world size")
         env, agent = self.env, self.agent
+        check_pursuit_imitation_entry(agent, b.get("pathfinder_bc_iterations"), f"resume bundle {path}")
         if getattr(env, "_dev_prefetch", None) is not None:    # a device reset issued ahead belongs to the run being replaced: let it finish, drop it
             torch.cuda.current_stream().wait_stream(env.sim._side)
             env._dev_prefetch = env._pre_reset = None
@@ -454,8 +476,10 @@ def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval
     `runtime.async_eval: false` (or async_eval=False) evaluates inline on rank 0 (deterministic recorder rows per iteration).
     save_resume: a directory each rank writes its resume bundle to after every iteration; resume: the directory each rank loads its
     bundle from before the first one (main --save-resume / --resume)."""
-    from . import pursuit_baseline, ray_shim
+    from . import pursuit_baseline, pursuit_imitation, ray_shim
     baseline_kind = pursuit_baseline.eval_baseline_options(cfg)   # validated before anything is built
+    if pursuit_imitation.pursuit_imitation_options(cfg).on:        # likewise: algo.pathfinder_bc_*, runtime.pathfinder_*
+        pursuit_baseline.pathfinder_options(cfg)
     tr = Trainer(cfg)
     tr.baseline = None
     if baseline_kind is not None and tr.rank == 0:
@@ -489,7 +513,9 @@ def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval
         steps, exp_r = tr.iterate()
         if tr.rank == 0:
             print(f"iteration {tr.iteration}: {steps} env-steps in {time.time() - t0:.2f}s")
-            if tr.agent.diag is not None:   # algo.update_diagnostics: the last update of the iteration, like last_log
+            if tr.last_imitation is not None:   # algo.pathfinder_bc_iterations: one line per imitation iteration
+                print(json.dumps(dict(iteration=tr.iteration, **tr.last_imitation)), flush=True)
+            elif tr.agent.diag is not None:   # algo.update_diagnostics: the last update of the iteration, like last_log
                 print(json.dumps(dict(iteration=tr.iteration, critic_loss=tr.last_log[0], actor_loss=tr.last_log[1], **tr.agent.last_update_diag)),
                       flush=True)
             if tr.iteration % eval_every == 0:

@@ -228,6 +228,36 @@ int pe_pursuer_pathfinder(const pe_config *cfg, const pe_state *st, const pe_pat
 int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const double *def, const double *eva,
                                const pe_pathfinder_params *prm, int32_t *actions, const pe_pathfinder_diag *diag);
 
+/* The pathfinder as a teacher inside a training rollout: the actions of pe_pursuer_pathfinder, exactly, from one
+ * launch that can reuse the last distance field and that writes the imitation labels itself.
+ * Cache: the field is the least fixed point of an integer system set by the grid, the source cell s and the clearance, so a field stored
+ * under the key (s, clearance) is the recomputed one bit for bit while the grid is unchanged.  A hit (key[n] == (s, prm.clearance)) loads
+ * the field instead of relaxing it and adds 1 to hits[n]; a miss builds the field as pe_pursuer_pathfinder does, stores it and writes the
+ * key -- with an empty cell (-1) when the sweep bound was hit (PE_STATUS_PATH_CAP).  THE CALLER empties the key (cell = -1) after
+ * anything that writes the grid (pe_env_reset, pe_env_load).
+ * Label: a_star receives the teacher's action of every environment as a float (a row view buffer[:, t] of an [N][T][P] tensor: the
+ * stride is T * P); action is overwritten with it in the environments whose follow byte is set and left alone elsewhere.
+ * Refused before any launch and without a write: whatever pe_pursuer_pathfinder refuses (PE_ERR_BAD_CONFIG); a_star with
+ * a_star_env_stride < P (PE_ERR_BAD_CONFIG); follow without action, a cache record whose field or key is NULL (PE_ERR_NULL). */
+typedef struct pe_pathfinder_cache {   /* all DEVICE; the whole record may be NULL = no cache */
+    int32_t *field;   /* [N][W*H]  the distance field of the last miss */
+    int32_t *key;     /* [N][2]    source cell (-1 = empty), clearance the field was built with */
+    int32_t *hits;    /* [N] or NULL: += 1 by the environment's workgroup on a hit */
+} pe_pathfinder_cache;
+typedef struct pe_pathfinder_label {   /* all DEVICE; the whole record may be NULL */
+    const uint8_t *follow;      /* [N] or NULL = nobody follows */
+    int32_t *action;            /* [N][P] in/out or NULL: overwritten with the teacher's action where follow[n] != 0 */
+    float *a_star;              /* or NULL: a_star[n * a_star_env_stride + i] = (float)teacher action, for EVERY n */
+    int64_t a_star_env_stride;  /* elements between environments, >= P */
+} pe_pathfinder_label;
+int pe_pursuer_pathfinder_teach(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, const pe_pathfinder_cache *cache,
+                                const pe_pathfinder_label *label, int32_t *actions /* [N][P] or NULL */, const pe_pathfinder_diag *diag,
+                                void *stream);
+/* The host twin: HOST arrays laid out like pe_pursuer_pathfinder_host's; the cache and label members are HOST pointers. */
+int pe_pursuer_pathfinder_teach_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const double *def, const double *eva,
+                                     const pe_pathfinder_params *prm, const pe_pathfinder_cache *cache, const pe_pathfinder_label *label,
+                                     int32_t *actions /* [N][P] or NULL */, const pe_pathfinder_diag *diag);
+
 const char *pe_error_string(int code);
 
 #ifdef __cplusplus
