@@ -5,7 +5,7 @@ A deterministic guidance law -- aim with lead at the (nearest active) evader, se
 from the records, in the tick's lane layout, and fed to the tick where the network's actions go (`run_episode(policy="guidance")`,
 `main --baseline guidance`, `runtime.eval_baseline: guidance`).  It is never trained on: it says what a sane hand-written controller
 captures on the seeds the trainers evaluate on."""
-import math
+from .options import distance
 
 LEAD_KEY, SEP_RANGE_KEY, SEP_GAIN_KEY = "runtime.guidance_lead", "runtime.guidance_sep_range", "runtime.guidance_sep_gain"
 BASELINE_KEY = "runtime.eval_baseline"
@@ -16,25 +16,11 @@ DEFAULT_SEP_KILL_RADII = 4.0   # guidance_sep_range defaults to this many kill r
 BASELINE_LOG_KEYS = ("baseline_return", "baseline_capture_rate", "baseline_episode_length")
 
 
-def _number(rt, name, key, default):
-    raw = rt.get(name, default)
-    if raw is None:
-        return None
-    try:
-        v = float(raw)
-    except (TypeError, ValueError):
-        raise ValueError(f"{key}: {raw!r} is not a number") from None
-    if not (math.isfinite(v) and v >= 0.0):
-        raise ValueError(f"{key}: {v} is not a finite number >= 0")
-    return v
-
-
 def guidance_options(cfg):
     """-> (lead, sep_range, sep_gain) of cfg.runtime, validated (ValueError naming the key); sep_range is None when the key is absent
     (the environment then takes 4 x its kill_radius)"""
     rt = cfg.get("runtime", {})
-    return (_number(rt, "guidance_lead", LEAD_KEY, DEFAULT_LEAD), _number(rt, "guidance_sep_range", SEP_RANGE_KEY, None),
-            _number(rt, "guidance_sep_gain", SEP_GAIN_KEY, DEFAULT_SEP_GAIN))
+    return distance(rt, LEAD_KEY, DEFAULT_LEAD), distance(rt, SEP_RANGE_KEY), distance(rt, SEP_GAIN_KEY, DEFAULT_SEP_GAIN)
 
 
 def eval_baseline_options(cfg):

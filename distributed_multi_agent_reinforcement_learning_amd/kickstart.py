@@ -9,7 +9,7 @@ mini-batch loss is ops.ppo_bc_loss_gauss / ops.ppo_bc_loss_cat: the PPO row and 
 term is the imitation phase's own loss (algo.bc_fit_std, bc_heading_wrap and bc_target_bound act on it as they do there), so the two
 phases optimise the same quantity.  The feature does not need an imitation phase: bc_coef > 0 with bc_iterations 0 is kickstarting from
 scratch.  With bc_coef 0 (the default) nothing here runs and no log line, buffer, checkpoint or resume bundle has a new entry."""
-import math
+from .options import count, real
 
 KEY = "algo.bc_coef"
 DEFAULT_DECAY, DEFAULT_ITERATIONS = 1.0, 0   # choices, not measurements (DESIGN.md section 7i)
@@ -35,26 +35,16 @@ class KickstartOptions:
         return (self.coef, self.decay, self.iterations)
 
 
-def _real(a, name, default):
-    raw = a.get(name, default)
-    if isinstance(raw, bool) or not isinstance(raw, (int, float)) or not math.isfinite(raw):
-        raise ValueError(f"algo.{name}: {raw!r} is not a finite number")
-    return float(raw)
-
-
 def kickstart_options(cfg):
     """-> KickstartOptions of cfg.algo, validated (ValueError naming the key)"""
     a = cfg.algo
-    coef = _real(a, "bc_coef", 0.0)
+    coef = real(a, KEY, 0.0)
     if not coef >= 0.0:
         raise ValueError(f"{KEY}: {coef} is not >= 0")
-    decay = _real(a, "bc_coef_decay", DEFAULT_DECAY)
+    decay = real(a, "algo.bc_coef_decay", DEFAULT_DECAY)
     if not 0.0 < decay <= 1.0:
         raise ValueError(f"algo.bc_coef_decay: {decay} is not in (0, 1]")
-    it = a.get("bc_coef_iterations", DEFAULT_ITERATIONS)
-    if isinstance(it, bool) or not isinstance(it, int) or it < 0:
-        raise ValueError(f"algo.bc_coef_iterations: {it!r} is not an integer >= 0")
-    return KickstartOptions(coef, decay, int(it))
+    return KickstartOptions(coef, decay, count(a, "algo.bc_coef_iterations", DEFAULT_ITERATIONS))
 
 
 def refuse_pursuit(cfg):

@@ -18,12 +18,13 @@ import numpy as np
 import torch
 
 from . import ops
-from .imitation import refuse_pursuit
+from .imitation import OptimizerSchedule, follow_mask, refuse_pursuit
 from .kickstart import refuse_pursuit as refuse_pursuit_kickstart
 from .model import build_actor_critic, pair_embeddings, pair_heads, sequence_forward_pair
 from .pe_env import status_or, status_text
 from .pursuit_baseline import pathfinder_options
-from .pursuit_imitation import follow_count, pursuit_imitation_options
+from .pursuit_imitation import pursuit_imitation_options
+from .readback import BcSums, read_back
 from .team_reward import team_reward_options
 from .update_diag import UpdateDiag, update_diag_options
 
@@ -206,7 +207,7 @@ def _gru_weights(gru):
     return types.SimpleNamespace(num_layers=gru.num_layers, **{n: getattr(gru, n) for n in names})
 
 
-class MAPPO:
+class MAPPO(OptimizerSchedule):
     def __init__(self, cfg, batch_size, mini_batch_size, agent_type):
         self.batch_size = batch_size
         self.mini_batch_size = mini_batch_size
@@ -284,9 +285,7 @@ class MAPPO:
         self.last_update_diag = None   # algo.update_diagnostics: the dict of the last train() call
         self._update_diag = self.diag   # the diagnostics of the train() call in progress (None in an imitation update)
         self._imitating = False
-        # the imitation metric: (label hits, live rows) of one train(imitation=True) call, added to by every loss launch
-        self.bc_sums = torch.zeros(ops.BC_SUMS, dtype=torch.float64, device=self.device) if self.pathfinder_bc.on else None
-        self.bc_allreduce = None       # the trainer's allreduce_sum_: the two sums over ranks, in place
+        self.bc = BcSums(self.device) if self.pathfinder_bc.on else None   # the imitation metric: (label hits, live rows)
         self.last_bc = None            # (hits, rows) of the last train(imitation=True) call
         self.last_hit_rate = None      # explore_expert: cache hits / (environments x teacher launches) of the last call
 
@@ -296,12 +295,12 @@ class MAPPO:
         gradient bucket as ever; the mini-batch loss is ops.bc_loss_cat on buffer["a_star"] (_minibatch_losses), the update diagnostics
         and the learning-rate decay are skipped, and the two sums of the metric go over ranks and arrive in the call's one host read
         (last_bc; bc_accuracy = hits / rows)."""
-        if imitation and self.bc_sums is None:
+        if imitation and self.bc is None:
             raise ValueError("train(imitation=True) needs algo.pathfinder_bc_iterations > 0 (the buffer has no a_star field otherwise)")
         self._imitating = bool(imitation)
         self._update_diag = None if imitation else self.diag
         if imitation:
-            self.bc_sums.zero_()
+            self.bc.sums.zero_()
         batch = replay_buffer.get_training_data(self.device) if hasattr(replay_buffer, "get_training_data") else replay_buffer.buffer
         o_static = replay_buffer.o_static
         N, T, P = batch["r"].shape
@@ -339,7 +338,7 @@ class MAPPO:
                 if self._update_diag is not None:
                     self._update_diag.begin()
                 if imitation:
-                    self.bc_sums.zero_()
+                    self.bc.sums.zero_()
                 torch.cuda.empty_cache()
         for n0 in starts:
             n1 = min(n0 + self.mini_batch_size, N)
@@ -359,14 +358,13 @@ class MAPPO:
             object_critics = object_critics + critic_loss.detach().double()   # f64 sum on the device: no host sync per mini-batch
             object_actors = object_actors + actor_loss.detach().double()
             update_time += 1
-        if self._update_diag is not None:   # one read for the two losses, the eight sums and the gradient norm
-            (object_critics, object_actors), self.last_update_diag = self._update_diag.read(object_critics, object_actors)
-        if imitation:   # one read for the two losses and the two sums (all-reduced over ranks)
-            if self.bc_allreduce is not None:
-                self.bc_allreduce(self.bc_sums)
-            object_critics, object_actors, hits, live = torch.cat((torch.stack((object_critics, object_actors)), self.bc_sums)).tolist()
-            self.last_bc = (hits, live)
-        object_critics, object_actors = float(object_critics), float(object_actors)
+        diag = self._update_diag   # one read for the two losses and, all-reduced over ranks, the imitation's two sums or the diagnostics' eight
+        (object_critics, object_actors), bc, sums, norm = read_back((object_critics, object_actors), self.bc if imitation else None, diag,
+                                                                    None if diag is None else (diag.grad_norm,))
+        if imitation:
+            self.last_bc = tuple(bc)
+        if diag is not None:
+            self.last_update_diag = diag.result(sums, norm[0])
         self._imitating, self._update_diag = False, self.diag
         if self.use_lr_decay and not imitation:
             self.lr_decay(total_steps)
@@ -395,7 +393,7 @@ class MAPPO:
                 raise RuntimeError("train(imitation=True): ops.ppo_loss_prob_ok(prob, values) does not hold (fp32 device tensors, prob (mb, T, P, "
                                    "A <= 16) with a dense last dimension, values (mb, T, P)); the imitation loss has no other path")
             return ops.bc_loss_cat(prob, batch["a_star"][n0:n1], values, batch["active"][n0:n1], v_old, v_target[n0:n1], self.epsilon,
-                                   self.use_value_clip, sums=self.bc_sums)
+                                   self.use_value_clip, sums=self.bc.sums)
         dk = {} if self._update_diag is None else {"diag": self._update_diag.sums}   # algo.update_diagnostics: the loss call adds its eight sums
         if ops.ppo_loss_prob_ok(prob, values_now.squeeze(-1)):
             # Categorical(prob).log_prob / .entropy() (get_logprob_and_entropy, :451-456) evaluated inside the loss launch
@@ -487,27 +485,6 @@ class MAPPO:
         hits, live = self.last_bc
         return hits / live if live else float("nan")
 
-    def set_lr(self, lr):
-        for p in self.ac_optimizer.param_groups:
-            p["lr"] = lr
-
-    def reset_optimizer(self, total_steps):
-        """the step from the imitation phase to PPO: Adam's moments and step count back to zero (the moments of a supervised loss say
-        nothing about the PPO gradient) and the learning rate back on the schedule"""
-        for st in self.ac_optimizer.state.values():
-            for key in ("step", "exp_avg", "exp_avg_sq"):
-                st[key].zero_()
-        if self.use_lr_decay:
-            self.lr_decay(total_steps)
-        else:
-            self.set_lr(self.lr)
-
-    def lr_decay(self, total_steps):
-        lr_now = self.lr * (1 - total_steps / self.max_train_steps)
-        for p in self.ac_optimizer.param_groups:
-            p["lr"] = lr_now
-        self.total_step = total_steps
-
     # ---- rollout (:731-827) -----------------------------------------------------------------------------------
     def explore_expert(self, env, num_episode, beta):
         """explore_env with the teacher in the loop (algo.pathfinder_bc_iterations): every tick also takes one
@@ -518,9 +495,7 @@ class MAPPO:
         the executed action (the imitation loss does not read it)."""
         if not self.pathfinder_bc.on:
             raise ValueError("explore_expert needs algo.pathfinder_bc_iterations > 0 (the buffer has no a_star field otherwise)")
-        follow = torch.zeros(env.num_envs, dtype=torch.uint8, device=self.device)
-        follow[:follow_count(beta, env.num_envs)] = 1
-        return self.explore_env(env, num_episode, follow=follow)
+        return self.explore_env(env, num_episode, follow=follow_mask(beta, env.num_envs, self.device))
 
     def _teacher_cache(self, env):
         """the teacher's distance-field cache for this environment batch (runtime.pathfinder_cache: false = None, every launch recomputes)"""

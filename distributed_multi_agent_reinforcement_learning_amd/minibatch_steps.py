@@ -6,16 +6,15 @@ gradient SUM over ranks, and one fused clip + Adam step (trainer.FusedAdam on tr
 parameters, gradients and moments).  The trainers' epoch loop then neither reduces nor steps.  With the option off (the default)
 nothing here runs: torch.optim.Adam, the loop and the files are today's."""
 
+from .options import flag
+
 KEY = "algo.minibatch_steps"
 MAX_GRAD_NORM = 5.0   # the clip of E3dMAPPO.train / N2nMAPPO.train (algo.use_grad_clip), as MAPPO.train's
 
 
 def minibatch_steps_options(cfg):
     """-> minibatch_steps of cfg.algo, validated (ValueError naming the key)"""
-    on = cfg.algo.get("minibatch_steps", False)
-    if not isinstance(on, bool):
-        raise ValueError(f"{KEY}: {on!r} is not true or false")
-    return on
+    return flag(cfg.algo, KEY, False)
 
 
 def check_entry(agent, entry, what):

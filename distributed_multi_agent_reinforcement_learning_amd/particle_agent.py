@@ -13,10 +13,11 @@ from . import kickstart as ks
 from . import ops
 from . import value_norm as vnorm
 from .minibatch_steps import MAX_GRAD_NORM, minibatch_steps_options
+from .readback import BcSums, read_back
 from .reward_shaping import reward_shaping_options
 from .team_reward import team_reward_options
 from .trainer import (BUCKET_ALIGN, FusedAdam, GradBucket, ParamBucket, ParticleRunState, allreduce_sum_, broadcast_weights_,
-                      enable_tuned_gemms, init_distributed, resume_path, save_resume_atomic)
+                      rank_setup, resume_path, save_resume_atomic)
 from .update_diag import LOG_KEYS, UpdateDiag, first_epoch_over, update_diag_options
 
 
@@ -41,14 +42,6 @@ def finish_env(env, cfg, training):
     return env
 
 
-class BcSums:
-    """the device side of the imitation metric: the two sums the bc loss launches of one train(imitation=True) call add to"""
-
-    def __init__(self, device):
-        self.sums = torch.zeros(ops.BC_SUMS, dtype=torch.float64, device=device)
-        self.allreduce = None      # the trainer's allreduce_sum_: the two sums over ranks, in place
-
-
 class KickSums:
     """the device side of the imitation term of teacher-regularised PPO (algo.bc_coef): the three sums the fused loss launches of one
     train(kick=...) call add to"""
@@ -58,7 +51,7 @@ class KickSums:
         self.allreduce = None      # the trainer's allreduce_sum_: the three sums over ranks, in place
 
 
-class ParticleMAPPO:
+class ParticleMAPPO(im.OptimizerSchedule):
     """rollout bookkeeping (explore_env) and PPO update (train) of a policy on a particle environment.  A subclass names its
     environment (ENV) and provides _options (its own keys, before the device check), _build (actor, critic, ac_parameters), _rollout
     (the storage of _state), _buffer_dims, new_buffer, run_episode, _bootstrap_value, _minibatch_loss, for algo.bc_iterations
@@ -169,9 +162,7 @@ class ParticleMAPPO:
         every environment and the executed actions of environments 0 .. round(beta N) - 1; everything else is run_episode's"""
         if not self.teacher:
             raise ValueError(f"explore_expert needs {im.KEY} > 0 (the buffer has no a_star field otherwise)")
-        follow = torch.zeros(env.num_envs, dtype=torch.uint8, device=self.device)
-        follow[:im.follow_count(beta, env.num_envs)] = 1
-        return self.explore_env(env, follow)
+        return self.explore_env(env, im.follow_mask(beta, env.num_envs, self.device))
 
     def _expert_tick(self, env, action, buf, t, follow):
         """the hook of explore_expert inside run_episode's loop, after the policy step and before env.step"""
@@ -247,60 +238,20 @@ class ParticleMAPPO:
             k += 1
         if self.use_lr_decay and not imitation:
             self.lr_decay(total_steps)
-        extra = () if opt is None else (opt.skipped,)   # the count of skipped steps rides in the read the call has anyway
-        if imitation:   # one read for the two losses, the skipped count and the two sums (all-reduced over ranks)
-            if self.bc.allreduce is not None:
-                self.bc.allreduce(self.bc.sums)
-            *head, s, c = torch.cat((torch.stack((obj_c, obj_a, *(e.double() for e in extra))), self.bc.sums)).tolist()
-            obj_c, obj_a, *extra = head
-            self.last_bc = (s, c)
-        elif diag is not None:   # one read for the two losses, the eight sums (all-reduced over ranks) and the gradient norm
-            tail = ()
-            if kick is not None:   # the three sums of the imitation term ride behind the skipped count
-                if self.kick_sums.allreduce is not None:
-                    self.kick_sums.allreduce(self.kick_sums.sums)
-                tail = tuple(self.kick_sums.sums)
-            (obj_c, obj_a, *extra), self.last_update_diag = diag.read(obj_c, obj_a, *extra, *tail)
-            if tail:
-                *extra, s, c, b = extra
-                self.last_kick = (s, c, b)
-        elif kick is not None:   # one read for the two losses, the skipped count and the three sums (all-reduced over ranks)
-            if self.kick_sums.allreduce is not None:
-                self.kick_sums.allreduce(self.kick_sums.sums)
-            *head, s, c, b = torch.cat((torch.stack((obj_c, obj_a, *(e.double() for e in extra))), self.kick_sums.sums)).tolist()
-            obj_c, obj_a, *extra = head
-            self.last_kick = (s, c, b)
-        elif opt is not None:
-            obj_c, obj_a, *extra = torch.stack((obj_c, obj_a, *extra)).tolist()
+        # one read for the two losses, the count of skipped steps and the sums of whichever features ran (each all-reduced over ranks)
+        (obj_c, obj_a, *skipped), bc, kicked, sums, norm = read_back(
+            (obj_c, obj_a) + (() if opt is None else (opt.skipped,)), self.bc if imitation else None,
+            self.kick_sums if kick is not None else None, diag, None if diag is None else (diag.grad_norm,))
+        if imitation:
+            self.last_bc = tuple(bc)
+        if kick is not None:
+            self.last_kick = tuple(kicked)
+        if diag is not None:
+            self.last_update_diag = diag.result(sums, norm[0])
         if opt is not None:
-            self.last_optimizer_steps, self.last_skipped_steps = k, int(extra[0] - opt.skipped_seen)
-            opt.skipped_seen = extra[0]
-        return float(obj_c) / k, float(obj_a) / k
-
-    def set_lr(self, lr):
-        for p in self.ac_optimizer.param_groups:
-            p["lr"] = lr
-
-    def reset_optimizer(self, total_steps):
-        """the step from the imitation phase to PPO: Adam's moments and step count back to zero (the moments of a supervised loss say
-        nothing about the PPO gradient) and the learning rate back on the schedule"""
-        opt = self.ac_optimizer
-        if isinstance(opt, FusedAdam):
-            opt.reset_moments()
-        else:
-            for st in opt.state.values():
-                for key in ("step", "exp_avg", "exp_avg_sq"):
-                    st[key].zero_()
-        if self.use_lr_decay:
-            self.lr_decay(total_steps)
-        else:
-            self.set_lr(self.lr)
-
-    def lr_decay(self, total_steps):
-        lr_now = self.lr * (1 - total_steps / self.max_train_steps)
-        for p in self.ac_optimizer.param_groups:
-            p["lr"] = lr_now
-        self.total_step = total_steps
+            self.last_optimizer_steps, self.last_skipped_steps = k, int(skipped[0] - opt.skipped_seen)
+            opt.skipped_seen = skipped[0]
+        return obj_c / k, obj_a / k
 
 
 class ParticleTrainer(ParticleRunState):
@@ -312,12 +263,7 @@ class ParticleTrainer(ParticleRunState):
     log_breakdown = False   # train_particle adds rollout_ms / update_ms to every log line
 
     def __init__(self, cfg, num_envs=None, num_eval_envs=64, eval_every=0, tuned_gemms=True):
-        self.rank, self.local_rank, self.world = init_distributed()
-        self.tuned_gemms = enable_tuned_gemms() if tuned_gemms else False
-        self.cfg = cfg
-        self.device = torch.device("cuda", self.local_rank % max(1, torch.cuda.device_count()))
-        torch.cuda.set_device(self.device)
-        self.num_envs = int(num_envs if num_envs is not None else cfg.runtime.num_envs)
+        rank_setup(self, cfg, num_envs, tuned_gemms)
         self.env = self.make_env(cfg, self.num_envs, self.rank, self.device)
         torch.manual_seed(int(cfg.runtime.get("seed", 0)))
         self.agent = self.agent_cls(cfg, self.num_envs, max(1, round(self.num_envs / 10)), self.device)
@@ -340,17 +286,12 @@ class ParticleTrainer(ParticleRunState):
     def iterate(self):
         """-> (env-steps of this iteration over all ranks, log record)"""
         cfg, agent = self.cfg, self.agent
-        bc = agent.imitation
-        imitating = self.iteration < bc.iterations   # algo.bc_iterations: the leading iterations imitate the scripted pursuers (DESIGN 7f)
-        if imitating:
-            agent.set_lr(bc.lr)   # constant over the phase
-        elif bc.on and self.iteration == bc.iterations:
-            agent.reset_optimizer(self.total_steps)   # the first PPO iteration starts from fresh moments, on the schedule
-        lam = 0.0 if imitating else agent.kick.coef_at(self.iteration - bc.iterations)   # algo.bc_coef: lambda_j of this PPO iteration (DESIGN 7i)
+        # algo.bc_iterations: the leading iterations imitate the scripted pursuers (DESIGN 7f)
+        imitating, beta = im.phase_step(agent, agent.imitation, self.iteration, self.total_steps)
+        lam = 0.0 if imitating else agent.kick.coef_at(self.iteration - agent.imitation.iterations)   # algo.bc_coef: lambda_j of this PPO iteration (DESIGN 7i)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
         if imitating:
-            beta = bc.beta_at(self.iteration)
             mean_r, buf, steps, stats = agent.explore_expert(self.env, beta)
         elif lam > 0.0:   # every tick labelled, no environment follows the teacher: the data stays on-policy
             mean_r, buf, steps, stats = agent.explore_expert(self.env, 0.0)

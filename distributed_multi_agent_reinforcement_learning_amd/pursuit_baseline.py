@@ -5,9 +5,9 @@ Two policies: "pathfinder" -- a distance field to the evader over the occupancy 
 static-map probe -- and "demon", the reference's straight-at-the-evader policy that is blind to walls.  Neither is trained on: an
 episode of one says what a hand-written controller scores on the seeds the evaluator uses (`main --baseline pathfinder`,
 `runtime.eval_baseline: pathfinder`), in the same five quantities `evaluator.evaluate(..., stats={})` reports for the network."""
-import math
-
 import torch
+
+from .options import distance
 
 LEAD_KEY, SEP_RANGE_KEY, CLEARANCE_KEY = "runtime.pathfinder_lead", "runtime.pathfinder_sep_range", "runtime.pathfinder_clearance"
 BASELINE_KEY = "runtime.eval_baseline"
@@ -18,30 +18,17 @@ STAT_KEYS = ("eval_return", "eval_capture_rate", "eval_first_contact", "eval_con
 BASELINE_LOG_KEYS = tuple("baseline_" + k[len("eval_"):] for k in STAT_KEYS)
 
 
-def _number(rt, name, key):
-    raw = rt.get(name, None)
-    if raw is None:
-        return None
-    try:
-        v = float(raw)
-    except (TypeError, ValueError):
-        raise ValueError(f"{key}: {raw!r} is not a number") from None
-    if not (math.isfinite(v) and v >= 0.0):
-        raise ValueError(f"{key}: {v} is not a finite number >= 0")
-    return v
-
-
 def pathfinder_options(cfg):
     """-> dict(lead, sep_range, clearance) of cfg.runtime, validated (ValueError naming the key); sep_range is None when the key is
     absent (the environment then takes 2 x its collision radius)"""
     rt = cfg.get("runtime", {})
-    lead = _number(rt, "pathfinder_lead", LEAD_KEY)
+    lead = distance(rt, LEAD_KEY)
     raw = rt.get("pathfinder_clearance", DEFAULT_CLEARANCE)
     if isinstance(raw, bool) or not isinstance(raw, int) and not (isinstance(raw, float) and float(raw).is_integer()):
         raise ValueError(f"{CLEARANCE_KEY}: {raw!r} is not an integer")
     if not 0 <= int(raw) <= MAX_CLEARANCE:
         raise ValueError(f"{CLEARANCE_KEY}: {int(raw)} is not in 0 .. {MAX_CLEARANCE}")
-    return dict(lead=DEFAULT_LEAD if lead is None else lead, sep_range=_number(rt, "pathfinder_sep_range", SEP_RANGE_KEY), clearance=int(raw))
+    return dict(lead=DEFAULT_LEAD if lead is None else lead, sep_range=distance(rt, SEP_RANGE_KEY), clearance=int(raw))
 
 
 def eval_baseline_options(cfg):

@@ -17,7 +17,7 @@ import torch.distributed as dist
 from . import ops
 from .evaluator import EvaluatorProc, draw_learning_curve
 from .mappo import MAPPO
-from .imitation import check_entry as check_imitation_entry
+from .imitation import check_entry as check_imitation_entry, phase_step
 from .kickstart import check_entry as check_kickstart_entry
 from .minibatch_steps import check_entry as check_minibatch_steps_entry
 from .pursuit_env import Pursuit_Env
@@ -67,6 +67,17 @@ def init_distributed(backend=None):
             torch.cuda.set_device(local_rank)
         dist.init_process_group(backend=backend, rank=rank, world_size=world)
     return rank, local_rank, world
+
+
+def rank_setup(trainer, cfg, num_envs, tuned_gemms):
+    """what both trainers start from: the rank in the job, the tuned GEMM table, the configuration, this rank's device and its number
+    of environments"""
+    trainer.rank, trainer.local_rank, trainer.world = init_distributed()
+    trainer.tuned_gemms = enable_tuned_gemms() if tuned_gemms else False
+    trainer.cfg = cfg
+    trainer.device = torch.device("cuda", trainer.local_rank % max(1, torch.cuda.device_count()))
+    torch.cuda.set_device(trainer.device)
+    trainer.num_envs = int(num_envs if num_envs is not None else cfg.runtime.num_envs)
 
 
 def allreduce_sum_(flat):
@@ -353,12 +364,7 @@ class Trainer:
     """One rank of the data-parallel job."""
 
     def __init__(self, cfg, num_envs=None, mini_batch_size=None, tuned_gemms=True):
-        self.rank, self.local_rank, self.world = init_distributed()
-        self.tuned_gemms = enable_tuned_gemms() if tuned_gemms else False
-        self.cfg = cfg
-        self.device = torch.device("cuda", self.local_rank % max(1, torch.cuda.device_count()))
-        torch.cuda.set_device(self.device)
-        self.num_envs = int(num_envs if num_envs is not None else cfg.runtime.num_envs)
+        rank_setup(self, cfg, num_envs, tuned_gemms)
         epi = int(cfg.algo.sample_epi_num)
         batch = self.num_envs * epi
         # main.py:48: mini_batch_size = round(num_workers * sample_epi_num / 10)
@@ -369,9 +375,9 @@ class Trainer:
         self.agent.sample_rank = self.rank  # disjoint action-sampling streams per rank (mappo.MAPPO.sample_rank)
         self.bucket = GradBucket(self.agent.ac_parameters)   # .grad of every parameter lives in one flat tensor
         self.agent.grad_bucket = self.bucket
-        if self.agent.diag is not None:
-            self.agent.diag.allreduce = allreduce_sum_   # algo.update_diagnostics: the eight sums over ranks; no group, no collective
-        self.agent.bc_allreduce = allreduce_sum_   # algo.pathfinder_bc_iterations: the two sums of the imitation metric, likewise
+        for part in (self.agent.diag, self.agent.bc):
+            if part is not None:   # algo.update_diagnostics: the eight sums / algo.pathfinder_bc_iterations: the two sums of the imitation
+                part.allreduce = allreduce_sum_   # metric over ranks; no group, no collective
         self.last_imitation = None   # the log entries of the last iteration when it was an imitation iteration
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.total_steps = 0
@@ -384,15 +390,10 @@ class Trainer:
         at the constant rate pathfinder_bc_lr); iteration K starts PPO from cleared Adam moments.  The phase
         follows from `iteration` alone, so a resumed run continues in it."""
         cfg, agent = self.cfg, self.agent
-        bc = agent.pathfinder_bc
-        imitating = self.iteration < bc.iterations
-        if bc.on and self.iteration == bc.iterations:
-            agent.reset_optimizer(self.total_steps)
+        imitating, beta = phase_step(agent, agent.pathfinder_bc, self.iteration, self.total_steps)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
         if imitating:
-            beta = bc.beta_at(self.iteration)
-            agent.set_lr(bc.lr)
             exp_r, buffer, steps = agent.explore_expert(self.env, int(cfg.algo.sample_epi_num), beta)
         else:
             exp_r, buffer, steps = agent.explore_env(self.env, int(cfg.algo.sample_epi_num))

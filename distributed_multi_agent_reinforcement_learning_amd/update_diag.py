@@ -10,6 +10,7 @@ import math
 import torch
 
 from . import ops
+from .readback import read_back
 
 KEY, KL_KEY = "algo.update_diagnostics", "algo.target_kl"
 DERIVED = ("approx_kl", "clip_fraction", "entropy", "explained_variance", "ratio_mean")
@@ -67,14 +68,14 @@ class UpdateDiag:
         torch.maximum(self.grad_norm, total_norm.detach().to(self.grad_norm.dtype), out=self.grad_norm)
         self.noted = True
 
+    def result(self, sums, grad_norm):
+        """the eight sums (over ranks) and the gradient norm as read_back delivered them -> the diagnostics dict"""
+        out = derive(sums)
+        out["grad_norm"] = grad_norm if self.noted else float("nan")   # (algo.use_grad_clip: false computes no norm)
+        self.last_sums = sums
+        return out
+
     def read(self, *scalars):
         """-> (the scalars as floats, the diagnostics dict): one device-to-host copy for all of it"""
-        if self.allreduce is not None:
-            self.allreduce(self.sums)
-        vals = torch.cat([torch.stack([torch.as_tensor(s, dtype=torch.float64, device=self.sums.device) for s in scalars]), self.sums,
-                          self.grad_norm.double().reshape(1)]).tolist()
-        k = len(scalars)
-        out = derive(vals[k:k + ops.PPO_DIAG_SUMS])
-        out["grad_norm"] = vals[-1] if self.noted else float("nan")   # (algo.use_grad_clip: false computes no norm)
-        self.last_sums = vals[k:k + ops.PPO_DIAG_SUMS]
-        return vals[:k], out
+        vals, sums, (norm,) = read_back(scalars, self, (self.grad_norm,))
+        return vals, self.result(sums, norm)
