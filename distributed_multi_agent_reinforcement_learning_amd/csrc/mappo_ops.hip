@@ -14,6 +14,7 @@
 
 #include "mappo_ops.h"
 #include "mappo_ops_diag.h"
+#include "gru_nets_check.hpp"
 #include "sb_common.hpp"
 #include "sb_wgrad.hpp"
 #include "ppo_diag.hpp"
@@ -2877,20 +2878,22 @@ int gru_gates_bwd(int32_t B, int32_t H, const float *dout, const float *dcarry, 
     return (int)hipGetLastError();
 }
 
-int gru_cell_fwd_multi(int32_t n_nets, const mo_gru_cell_net *nets, int32_t B, int32_t H, void *stream) {
-    if (n_nets < 1 || n_nets > MO_GRU_CELL_MAX_NETS || !nets || B < 1 || H != GRU_H) return MO_ERR_BAD_ARG;
-    GruCellNets a;
+// what the two cell launchers share: the records by value, the 16-row tiles and the CU count (256 where the device does not say)
+static int gru_cell_setup(int32_t n_nets, const mo_gru_cell_net *nets, int32_t B, GruCellNets &a, int &nblk) {
     memset(&a, 0, sizeof a);
-    for (int k = 0; k < n_nets; k++) {
-        const mo_gru_cell_net &m = nets[k];
-        if (!m.x || !m.h_prev || !m.w_ih || !m.w_hh || !m.b_ih || !m.b_hh || !m.h_out) return MO_ERR_BAD_ARG;
-        if (((uintptr_t)m.x & 15) || ((uintptr_t)m.h_prev & 15) || ((uintptr_t)m.w_ih & 15) || ((uintptr_t)m.w_hh & 15)) return MO_ERR_BAD_ARG;
-        a.n[k] = m;
-    }
-    const int nblk = (B + GRU_RB - 1) / GRU_RB;
+    memcpy(a.n, nets, (size_t)n_nets * sizeof *nets);
+    nblk = (B + GRU_RB - 1) / GRU_RB;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    int per = cus / n_nets;     // persistent workgroups per cell: one per CU in total
+    return cus;
+}
+
+int gru_cell_fwd_multi(int32_t n_nets, const mo_gru_cell_net *nets, int32_t B, int32_t H, void *stream) {
+    static_assert(GRU_H == GRU_NETS_H, "gru_nets_check.hpp checks H for these kernels");
+    if (!gru_cell_nets_ok(n_nets, nets, B, H, false)) return MO_ERR_BAD_ARG;
+    GruCellNets a;
+    int nblk;
+    int per = gru_cell_setup(n_nets, nets, B, a, nblk) / n_nets;     // persistent workgroups per cell: one per CU in total
     if (per < 1) per = 1;
     const int grid = nblk < per ? nblk : per;
     hipLaunchKernelGGL(k_gru_cell, dim3(grid, n_nets), dim3(512), 0, (hipStream_t)stream, (int)B, nblk, a);
@@ -2898,21 +2901,11 @@ int gru_cell_fwd_multi(int32_t n_nets, const mo_gru_cell_net *nets, int32_t B, i
 }
 
 int gru_cell_split_fwd_multi(int32_t n_nets, const mo_gru_cell_net *nets, int32_t B, int32_t H, void *stream) {
-    if (n_nets < 1 || n_nets > MO_GRU_CELL_MAX_NETS || !nets || B < 1 || H != GRU_H) return MO_ERR_BAD_ARG;
+    if (!gru_cell_nets_ok(n_nets, nets, B, H, true)) return MO_ERR_BAD_ARG;
     GruCellNets a;
-    memset(&a, 0, sizeof a);
-    for (int k = 0; k < n_nets; k++) {
-        const mo_gru_cell_net &m = nets[k];
-        if (!m.x || !m.h_prev || !m.w_ih || !m.w_hh || !m.b_ih || !m.b_hh || !m.h_out) return MO_ERR_BAD_ARG;
-        if (((uintptr_t)m.x & 15) || ((uintptr_t)m.h_prev & 15) || ((uintptr_t)m.w_ih & 15) || ((uintptr_t)m.w_hh & 15) || ((uintptr_t)m.h_out & 15))
-            return MO_ERR_BAD_ARG;
-        if (m.h_out == m.h_prev || m.h_out == m.x) return MO_ERR_BAD_ARG;   // two workgroups share a row tile: not in place
-        a.n[k] = m;
-    }
-    const int nblk = (B + GRU_RB - 1) / GRU_RB;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    int pairs = cus / n_nets / 2;   // persistent workgroup PAIRS per cell (the two halves of the hidden units): one workgroup per CU in total
+    int nblk;
+    // persistent workgroup PAIRS per cell (the two halves of the hidden units): one workgroup per CU in total
+    int pairs = gru_cell_setup(n_nets, nets, B, a, nblk) / n_nets / 2;
     if (pairs < 1) pairs = 1;
     if (pairs > nblk) pairs = nblk;
     hipLaunchKernelGGL(k_gru_cell_sb, dim3(2 * pairs, n_nets), dim3(512), 0, (hipStream_t)stream, (int)B, nblk, a);
@@ -2934,16 +2927,10 @@ int gru_cell_fwd(int32_t B, int32_t H, const float *x, const float *h_prev, cons
 int64_t gru_seq_save_elems(int32_t T, int32_t B) { return (int64_t)T * ((B + GRU_RB - 1) / GRU_RB) * 4 * 512 * 4; }
 
 int gru_seq_fwd_multi(int32_t n_nets, const mo_gru_seq_net *nets, int32_t T, int32_t B, int32_t H, int32_t gi_agents, void *stream) {
-    if (n_nets < 1 || n_nets > MO_GRU_MAX_NETS || !nets || T < 1 || B < 1 || H != GRU_H || gi_agents < 0 || (gi_agents && B % gi_agents)) return MO_ERR_BAD_ARG;
+    if (!gru_seq_nets_ok(n_nets, nets, T, B, H, gi_agents)) return MO_ERR_BAD_ARG;
     GruFwdNets a;
     memset(&a, 0, sizeof a);
-    for (int k = 0; k < n_nets; k++) {
-        const mo_gru_seq_net &m = nets[k];
-        if (!m.gi || !m.w_hh || !m.b_hh || !m.h0 || !m.out) return MO_ERR_BAD_ARG;
-        if ((((uintptr_t)m.gi | (uintptr_t)m.w_hh | (uintptr_t)m.b_hh | (uintptr_t)m.h0 | (uintptr_t)m.out | (uintptr_t)m.save) & 15)) return MO_ERR_BAD_ARG;
-        if (m.B < 0 || m.B > B || (gi_agents && m.B % gi_agents)) return MO_ERR_BAD_ARG;
-        a.n[k] = m;
-    }
+    memcpy(a.n, nets, (size_t)n_nets * sizeof *nets);
     const int nblk = (B + GRU_RB - 1) / GRU_RB;
     hipLaunchKernelGGL(k_gru_seq_fwd2, dim3(nblk, n_nets), dim3(512), 0, (hipStream_t)stream, T, B, a, (int)gi_agents);
     return (int)hipGetLastError();
@@ -2958,19 +2945,10 @@ int gru_seq_fwd(int32_t T, int32_t B, int32_t H, const float *gi, const float *w
 int64_t gru_seq_bwd_workspace(int32_t B) { return (int64_t)((B + GRU_RB - 1) / GRU_RB) * 4 * GRU_H * sizeof(float); }
 
 int gru_seq_bwd_multi(int32_t n_nets, const mo_gru_seq_bwd_net *nets, int32_t T, int32_t B, int32_t H, int32_t gi_agents, void *stream) {
-    if (n_nets < 1 || n_nets > MO_GRU_MAX_NETS || !nets || T < 1 || B < 1 || H != GRU_H || gi_agents < 0 || (gi_agents && B % gi_agents)) return MO_ERR_BAD_ARG;
+    if (!gru_seq_bwd_nets_ok(n_nets, nets, T, B, H, gi_agents)) return MO_ERR_BAD_ARG;
     GruBwdNets a;
     memset(&a, 0, sizeof a);
-    for (int k = 0; k < n_nets; k++) {
-        const mo_gru_seq_bwd_net &m = nets[k];
-        if (!m.dout || !m.save || !m.out || !m.h0 || !m.w_hh || !m.dgi || !m.dh0) return MO_ERR_BAD_ARG;
-        if ((m.dgh == nullptr) == (m.dnr == nullptr)) return MO_ERR_BAD_ARG;        // exactly one of the two forms
-        if ((m.db_ih || m.db_hh) && (!m.db_ih || !m.db_hh || !m.workspace)) return MO_ERR_BAD_ARG;
-        if ((((uintptr_t)m.dout | (uintptr_t)m.save | (uintptr_t)m.out | (uintptr_t)m.h0 | (uintptr_t)m.dgi | (uintptr_t)m.dgh | (uintptr_t)m.dnr |
-              (uintptr_t)m.dh0 | (uintptr_t)m.workspace) & 15)) return MO_ERR_BAD_ARG;
-        if (m.B < 0 || m.B > B || (gi_agents && m.B % gi_agents)) return MO_ERR_BAD_ARG;
-        a.n[k] = m;
-    }
+    memcpy(a.n, nets, (size_t)n_nets * sizeof *nets);
     const int nblk = (B + GRU_RB - 1) / GRU_RB;
     hipLaunchKernelGGL(k_gru_seq_bwd2, dim3(nblk, n_nets), dim3(512), 0, (hipStream_t)stream, T, B, a, (int)gi_agents);
     for (int k = 0; k < n_nets; k++)

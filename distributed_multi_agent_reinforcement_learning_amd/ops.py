@@ -1749,26 +1749,18 @@ PERSISTENT_GRU_MIN_T = 2  # sequences at least this long take the one-launch rec
 SEQ_MODE = os.environ.get("MAPPO_GRU_SEQ", os.environ.get("MAPPO_MATMUL", "split_bf16"))
 
 
-def _seq_fwd(L, arr, n, T, Bmax, H, agents):
-    if SEQ_MODE == "split_bf16":
-        _check(L.gru_seq_split_fwd_multi(n, C.cast(arr, C.c_void_p), T, Bmax, H, agents, _stream()), "gru_seq_split_fwd_multi")
-    else:
-        _check(L.gru_seq_fwd_multi(n, C.cast(arr, C.c_void_p), T, Bmax, H, agents, _stream()), "gru_seq_fwd_multi")
-
-
-def _seq_bwd(L, arr, n, T, Bmax, H, agents):
-    if SEQ_MODE == "split_bf16":
-        _check(L.gru_seq_split_bwd_multi(n, C.cast(arr, C.c_void_p), T, Bmax, H, agents, _stream()), "gru_seq_split_bwd_multi")
-    else:
-        _check(L.gru_seq_bwd_multi(n, C.cast(arr, C.c_void_p), T, Bmax, H, agents, _stream()), "gru_seq_bwd_multi")
+def _seq_launch(L, direction, arr, n, T, Bmax, H, agents):
+    """gru_seq[_split]_{fwd,bwd}_multi by SEQ_MODE and direction ("fwd" | "bwd"), looked up on L at every call"""
+    what = f"gru_seq_split_{direction}_multi" if SEQ_MODE == "split_bf16" else f"gru_seq_{direction}_multi"
+    _check(getattr(L, what)(n, C.cast(arr, C.c_void_p), T, Bmax, H, agents, _stream()), what)
 
 
 class _GRULayer(torch.autograd.Function):
-    """One torch.nn.GRU layer over a sequence: the input projection is one fp32 MFMA GEMM (rocBLAS / hipBLASLt), the
-    recurrence runs in the persistent kernel pair gru_seq_{fwd,bwd} (or, for short sequences / other sizes, a GEMM and the
-    gate kernels per step).  x: (T, B, I) time-major, or -- agents = P > 0 -- the (T B, I) rows of the encoder's output in
-    (episode, step, agent) order (sequence b = n P + p): the projection and its gradients then use the embedding as it lies
-    in memory (no permuted copy on the way in, none for the gradient on the way out).  out: (T, B, H) time-major."""
+    """One torch.nn.GRU layer over a sequence, step by step: the input projection is one GEMM (gru_input_projection), then per step
+    a library product for gh and the gate kernels gru_gates_{fwd,bwd}.  The path of the shapes the one-launch recurrence does not
+    cover (H != 128, T < PERSISTENT_GRU_MIN_T; ops.gru sends the others to _GRULayerMulti).  x: (T, B, I) time-major, or -- agents
+    = P > 0 -- the (T B, I) rows of the encoder's output in (episode, step, agent) order (sequence b = n P + p), gathered once into
+    time-major rows here and the gradient scattered back.  out: (T, B, H) time-major."""
 
     @staticmethod
     def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh, T, B, agents):
@@ -1776,37 +1768,19 @@ class _GRULayer(torch.autograd.Function):
         _need_gpu(x, "gru")
         I = x.shape[-1]
         H = w_hh.shape[1]
-        persistent = bool(H == 128 and T >= PERSISTENT_GRU_MIN_T)
         ctx.x_shape = x.shape
-        ctx.ungather = 0
-        if agents and not persistent:  # the per-step path is time-major only: gather the rows once
+        ctx.ungather = int(agents)
+        if agents:  # time-major only: gather the rows once
             x = x.reshape(B // agents, T, agents, I).permute(1, 0, 2, 3).reshape(T, B, I)
-            ctx.ungather = int(agents)
-            agents = 0
         x = x.contiguous()
         h0 = h0.contiguous()
         need = any(ctx.needs_input_grad)
         out = torch.empty((T, B, H), dtype=x.dtype, device=x.device)
         gi = gru_input_projection(x.reshape(T * B, I), w_ih, b_ih)
-        # the saved gates: (T, 4, B, H) planes for the per-step path; the persistent pair keeps them in its own lane order
-        save = None
-        if need:
-            save = (torch.empty(L.gru_seq_save_elems(T, B), dtype=x.dtype, device=x.device) if persistent
-                    else torch.empty((T, 4, B, H), dtype=x.dtype, device=x.device))
+        save = torch.empty((T, 4, B, H), dtype=x.dtype, device=x.device) if need else None   # the gates of every step, as planes
         b_hh = b_hh.contiguous()
         st = _stream()
-        ctx.persistent, ctx.dims, ctx.agents = persistent, (T, B, I), int(agents)
-        if persistent:  # whole recurrence in one launch, W_hh in registers (csrc/mappo_ops.hip k_gru_seq_fwd2 | csrc/sb_gru_seq.hpp)
-            whh = w_hh.detach().contiguous()
-            arr = (GruSeqNet * 1)()
-            a = arr[0]
-            a.gi, a.w_hh, a.b_hh, a.h0, a.out = gi.data_ptr(), whh.data_ptr(), b_hh.data_ptr(), h0.data_ptr(), out.data_ptr()
-            a.save = save.data_ptr() if need else None
-            a.B = B
-            _seq_fwd(L, arr, 1, T, B, H, int(agents))
-            if need:
-                ctx.save_for_backward(x, h0, w_ih, whh, out, save)
-            return out
+        ctx.dims = (T, B, I)
         gi = gi.reshape(T, B, 3 * H)
         gh = torch.empty((B, 3 * H), dtype=x.dtype, device=x.device)
         w_hh_t = w_hh.t()
@@ -1827,37 +1801,18 @@ class _GRULayer(torch.autograd.Function):
         T, B, I = ctx.dims
         H = w_hh.shape[1]
         dout = _dense16(dout)
-        dgi = torch.empty((T * B, 3 * H), dtype=x.dtype, device=x.device)   # rows in x's order
+        dgi = torch.empty((T * B, 3 * H), dtype=x.dtype, device=x.device)
+        dgh = torch.empty((T, B, 3 * H), dtype=x.dtype, device=x.device)
         dh_direct = torch.empty((B, H), dtype=x.dtype, device=x.device)
         dcarry = None
         st = _stream()
-        db_ih = db_hh = None
-        # dW_hh = [dr dz dnr]^T h_prev.  Time-major dgi rows line up with h_prev = out[t - 1], so dr, dz are stored once (dgi)
-        # and only dnr separately; with the encoder's row order (agents) the kernel writes the full time-major dgh as well.
-        split = bool(ctx.persistent and not ctx.agents)
-        dgh = None if split else torch.empty((T, B, 3 * H), dtype=x.dtype, device=x.device)
-        dnr = torch.empty((T, B, H), dtype=x.dtype, device=x.device) if split else None
-        if ctx.persistent:
-            db_ih = torch.empty(3 * H, dtype=x.dtype, device=x.device)
-            db_hh = torch.empty(3 * H, dtype=x.dtype, device=x.device)
-            ws = torch.empty(L.gru_seq_bwd_workspace(B), dtype=torch.uint8, device=x.device)
-            arr = (GruSeqBwdNet * 1)()
-            a = arr[0]
-            a.dout, a.save, a.out, a.h0, a.w_hh, a.dgi = dout.data_ptr(), save.data_ptr(), out.data_ptr(), h0.data_ptr(), w_hh.data_ptr(), dgi.data_ptr()
-            a.dgh = dgh.data_ptr() if dgh is not None else None
-            a.dnr = dnr.data_ptr() if dnr is not None else None
-            a.dh0, a.db_ih, a.db_hh, a.workspace = dh_direct.data_ptr(), db_ih.data_ptr(), db_hh.data_ptr(), ws.data_ptr()
-            a.B = B
-            _seq_bwd(L, arr, 1, T, B, H, ctx.agents)
-            dcarry = dh_direct
-        else:
-            dgi3 = dgi.view(T, B, 3 * H)
-            for t in range(T - 1, -1, -1):
-                hprev = out[t - 1] if t > 0 else h0
-                _check(L.gru_gates_bwd(B, H, _ptr(dout[t]), _ptr(dcarry), _ptr(save[t]), _ptr(hprev), _ptr(dgi3[t]), _ptr(dgh[t]),
-                                       _ptr(dh_direct), st), "gru_gates_bwd")
-                dcarry = torch.addmm(dh_direct, dgh[t], w_hh)
-        dw_hh = _gru_dw_hh(dgi, dgh, dnr, out, h0, T, B, H)
+        dgi3 = dgi.view(T, B, 3 * H)
+        for t in range(T - 1, -1, -1):
+            hprev = out[t - 1] if t > 0 else h0
+            _check(L.gru_gates_bwd(B, H, _ptr(dout[t]), _ptr(dcarry), _ptr(save[t]), _ptr(hprev), _ptr(dgi3[t]), _ptr(dgh[t]),
+                                   _ptr(dh_direct), st), "gru_gates_bwd")
+            dcarry = torch.addmm(dh_direct, dgh[t], w_hh)
+        dw_hh = _gru_dw_hh(dgi, dgh, None, out, h0, T, B, H)
         x2 = x.reshape(T * B, I)
         dw_ih = wgrad(dgi, x2)
         dx = None
@@ -1867,9 +1822,7 @@ class _GRULayer(torch.autograd.Function):
                 P = ctx.ungather
                 dx = dx.reshape(T, B // P, P, I).permute(1, 0, 2, 3)
             dx = dx.reshape(ctx.x_shape)
-        if db_ih is None:
-            db_ih, db_hh = dgi.sum(0), dgh.reshape(T * B, 3 * H).sum(0)
-        return dx, dcarry, dw_ih, dw_hh, db_ih, db_hh, None, None, None
+        return dx, dcarry, dw_ih, dw_hh, dgi.sum(0), dgh.reshape(T * B, 3 * H).sum(0), None, None, None
 
 
 class GruCellNet(C.Structure):
@@ -2144,9 +2097,14 @@ class GruSeqBwdNet(C.Structure):
 
 
 class _GRULayerMulti(torch.autograd.Function):
-    """The same layer of several independent GRUs (the actor's and the critic's, for one or several mini-batches: own weights, own
-    inputs, own number of sequences; same T and row order) with the recurrences of all of them in ONE persistent launch each way
-    (gru_seq_fwd_multi / gru_seq_bwd_multi); per network the arithmetic is that of _GRULayer's persistent path.
+    """One torch.nn.GRU layer (H = 128, T >= PERSISTENT_GRU_MIN_T) of one network (ops.gru) or the same layer of several independent
+    GRUs (ops.gru_multi: the actor's and the critic's, for one or several mini-batches: own weights, own inputs, own number of
+    sequences; same T and row order).  Per network the input projection is one GEMM (gru_input_projection); the recurrences of all
+    of them run in ONE persistent launch each way, W_hh in registers (gru_seq[_split]_{fwd,bwd}_multi by SEQ_MODE: csrc/mappo_ops.hip
+    k_gru_seq_fwd2 / bwd2 | csrc/sb_gru_seq.hpp); the gates are saved in the kernel pair's own lane order.  x: (T, B, I) time-major,
+    or -- agents = P > 0 -- the (T B, I) rows of the encoder's output in (episode, step, agent) order (sequence b = n P + p): the
+    projection and its gradients then use the embedding as it lies in memory (no permuted copy on the way in, none for the gradient
+    on the way out).  out: (T, B, H) time-major.
     args: T, Bs (sequences per network), agents, x_links (None, or per network the ReluLink of an input that came out of a ReLU and
     feeds this layer only -- its relu' and bias sum then ride in the input gradient), zero_h0 (the caller vouches that every h0 is all
     zeros -- the update's sequences start from the zero state: the first step then adds nothing to dW_hh), then per network
@@ -2178,7 +2136,7 @@ class _GRULayerMulti(torch.autograd.Function):
             keep.append((gi, whh, bhh))
             outs.append(out)
             saved += [x, h0, w_ih, whh, out, save]
-        _seq_fwd(L, arr, n, T, max(Bs), H, int(agents))
+        _seq_launch(L, "fwd", arr, n, T, max(Bs), H, int(agents))
         ctx.dims, ctx.agents, ctx.n = (T, tuple(Bs)), int(agents), n
         ctx.x_links, ctx.zero_h0 = x_links, bool(zero_h0)
         ctx.x_shapes = [ts[6 * k].shape for k in range(n)]
@@ -2193,7 +2151,9 @@ class _GRULayerMulti(torch.autograd.Function):
         n = ctx.n
         sv = ctx.saved_tensors
         H = 128
-        split = not ctx.agents      # time-major dgi rows: dr, dz stored once (see _GRULayer.backward)
+        # dW_hh = [dr dz dnr]^T h_prev.  Time-major dgi rows line up with h_prev = out[t - 1], so dr, dz are stored once (dgi)
+        # and only dnr separately; with the encoder's row order (agents) the kernel writes the full time-major dgh as well.
+        split = not ctx.agents
         arr = (GruSeqBwdNet * n)()
         per = []
         for k in range(n):
@@ -2213,7 +2173,7 @@ class _GRULayerMulti(torch.autograd.Function):
             a.dh0, a.db_ih, a.db_hh, a.workspace = dh0.data_ptr(), db_ih.data_ptr(), db_hh.data_ptr(), ws.data_ptr()
             a.B = B
             per.append((dout, dgi, dgh, dnr, dh0, db_ih, db_hh, ws))
-        _seq_bwd(L, arr, n, T, max(Bs), H, ctx.agents)
+        _seq_launch(L, "bwd", arr, n, T, max(Bs), H, ctx.agents)
         grads = [None, None, None, None, None]
         for k in range(n):
             x, h0, w_ih, w_hh, out, save = sv[6 * k: 6 * k + 6]
@@ -2306,7 +2266,9 @@ def gru(x, h0, gru_module, inplace_hidden=False, agents=0, steps=None):
     """torch.nn.GRU(x, h0) semantics (seq-first, unidirectional, no dropout) on the fused path.
     x (T, B, I), h0 (num_layers, B, H) -> out (T, B, H), h_n (num_layers, B, H).
     agents = P > 0: x is instead the (B T, I) rows of the encoder's output in (episode, step, agent) order with T = steps
-    (sequence b = n P + p); the first layer reads them in place (see _GRULayer), the result is time-major all the same.
+    (sequence b = n P + p); the first layer reads them in place (see _GRULayerMulti), the result is time-major all the same.
+    Per layer: H = 128 and T >= PERSISTENT_GRU_MIN_T take the one-launch recurrence (_GRULayerMulti with one network), a single
+    rollout step without autograd takes the fused cell (gru_cell_fwd), everything else goes step by step (_GRULayer).
     inplace_hidden (single rollout step only): the new hidden state overwrites h0 (each 16-row tile is read before it is
     written by the one workgroup that owns it) and h_n IS h0 -- no stack, no copy back into the rollout state."""
     hn = []
@@ -2328,6 +2290,8 @@ def gru(x, h0, gru_module, inplace_hidden=False, agents=0, steps=None):
                                                _ptr(w_hh.detach().contiguous()), _ptr(b_ih.detach().contiguous()),
                                                _ptr(b_hh.detach().contiguous()), _ptr(out), _stream()), "gru_cell_fwd")
             inp = out
+        elif w_hh.shape[1] == 128 and T >= PERSISTENT_GRU_MIN_T:   # the one-launch recurrence, a launch of one network
+            inp = _GRULayerMulti.apply(T, (B,), int(agents) if layer == 0 else 0, None, False, inp, h0[layer], w_ih, w_hh, b_ih, b_hh)[0]
         else:
             inp = _GRULayer.apply(inp, h0[layer], w_ih, w_hh, b_ih, b_hh, T, B, int(agents) if layer == 0 else 0)
         hn.append(inp[-1])

@@ -110,7 +110,7 @@ def test_threshold_cases_name_switches_of_ops_and_lie_on_both_sides():
     which is asserted here), so which side R and R + 1 lie on is asserted on the GPU
     (tests/test_autograd_nodes_gpu.py::test_both_sides_of_each_row_threshold): from _wgrad_ok for WGRAD_MIN_ROWS, _skinny_ok for
     SKINNY_MIN_ROWS, input_grad_masked for MASKED_GRAD_MIN_ROWS and encoder_tail_train_ok for ENCODER_TAIL_TRAIN_MIN_ROWS;
-    RELU_BWD_MIN_ROWS and PERSISTENT_GRU_MIN_T are compared inline (relu_bwd_colsum, _GRULayer.forward) and have no predicate: their
+    RELU_BWD_MIN_ROWS and PERSISTENT_GRU_MIN_T are compared inline (relu_bwd_colsum, ops.gru) and have no predicate: their
     side shows in the entry-point census alone."""
     from distributed_multi_agent_reinforcement_learning_amd import ops
     seen = set()

@@ -445,7 +445,7 @@ def _gru_census(mode):
 
 @pytest.mark.parametrize("mode", MODES)
 def test_gru_layers_under_every_gradient_subset(env, mode):
-    """_GRULayer through ops.gru, two layers, T in {2, 3}, 15 / 16 / 17 sequences (times 3 agents in the encoder's row order): the all-on
+    """ops.gru (_GRULayerMulti with one network per layer), two layers, T in {2, 3}, 15 / 16 / 17 sequences (times 3 agents in the encoder's row order): the all-on
     case and every subset of (x, h0, w_ih, w_hh, b_ih, b_hh per layer) at every shape"""
     env.ops.set_matmul_mode(mode)
     for T, B, a in cases.gru_shapes():
@@ -590,7 +590,7 @@ def test_both_sides_of_each_row_threshold(env):
     route changed.  Which side a setting lies on is also asserted from the predicate itself where the threshold has one that can be
     called on device tensors: WGRAD_MIN_ROWS (_wgrad_ok), SKINNY_MIN_ROWS (_skinny_ok), MASKED_GRAD_MIN_ROWS (input_grad_masked gives
     None below it) and ENCODER_TAIL_TRAIN_MIN_ROWS (encoder_tail_train_ok, also through the route DHGN._after_messages' rule takes).
-    RELU_BWD_MIN_ROWS and PERSISTENT_GRU_MIN_T are compared inline in relu_bwd_colsum and _GRULayer.forward, with no predicate to
+    RELU_BWD_MIN_ROWS and PERSISTENT_GRU_MIN_T are compared inline in relu_bwd_colsum and ops.gru, with no predicate to
     call: for them the entry-point census is the evidence (relu_bwd_colsum; the sequence launches against the per-step gate kernels)."""
     ops = env.ops
     ops.set_matmul_mode("split_bf16")

@@ -872,6 +872,50 @@ def test_gru_multi_grouped_ragged_equals_separate_calls():
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("T,B,agents", [(2, 17, 0), (3, 48, 3)])
+def test_gru_matches_the_single_net_abi(T, B, agents):
+    """ops.gru (one layer, the fp32 recurrence) against the documented single-network entry points gru_seq_fwd / gru_seq_bwd called
+    directly (INTEGRATION.md): time-major rows with the dnr form, the encoder's row order (16 episodes x 3 agents) with the dgh form;
+    the weight and input gradients built from the returned dgi as ops.py builds them.  The same launches on the same operands: out and
+    every gradient bit for bit."""
+    from distributed_multi_agent_reinforcement_learning_amd import ops
+    torch.manual_seed(10 * T + agents)
+    H = 128
+    g = torch.nn.GRU(H, H, 1).cuda()
+    x = torch.randn((T * B, H) if agents else (T, B, H), device="cuda", requires_grad=True)
+    h0 = torch.randn(1, B, H, device="cuda", requires_grad=True)
+    gout = torch.randn(T, B, H, device="cuda")
+    modes = ops.matmul_modes()
+    ops.SEQ_MODE = "fp32"
+    try:
+        out, h_n = ops.gru(x, h0, g, agents=agents, steps=T if agents else None)
+        (out * gout).sum().backward()
+        L, st, p = ops.load_library(), ops._stream(), ops._ptr
+
+        def new(*shape):
+            return torch.empty(shape, device="cuda")
+        with torch.no_grad():
+            w_ih, w_hh, b_ih, b_hh = g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0
+            x2 = x.reshape(T * B, H)
+            gi = ops.gru_input_projection(x2, w_ih, b_ih)
+            out2, save = new(T, B, H), new(L.gru_seq_save_elems(T, B))
+            assert L.gru_seq_fwd(T, B, H, p(gi), p(w_hh), p(b_hh), p(h0[0]), p(out2), p(save), agents, st) == 0
+            dgi, dh0, db_ih, db_hh = new(T * B, 3 * H), new(B, H), new(3 * H), new(3 * H)
+            dgh, dnr = (new(T, B, 3 * H), None) if agents else (None, new(T, B, H))
+            ws = torch.empty(L.gru_seq_bwd_workspace(B), dtype=torch.uint8, device="cuda")
+            assert L.gru_seq_bwd(T, B, H, p(gout), p(save), p(out2), p(h0[0]), p(w_hh), p(dgi), p(dgh), p(dnr), p(dh0), p(db_ih), p(db_hh), agents,
+                                 p(ws), st) == 0
+            dw_hh = ops._gru_dw_hh(dgi, dgh, dnr, out2, h0[0], T, B, H)
+            dw_ih = ops.wgrad(dgi, x2)
+            dx = ops.input_grad(dgi, w_ih).reshape(x.shape)
+    finally:
+        ops.restore_matmul_modes(modes)
+    assert torch.equal(h_n, out[-1:])
+    for name, got, want in (("out", out, out2), ("x.grad", x.grad, dx), ("h0.grad", h0.grad[0], dh0), ("w_ih.grad", w_ih.grad, dw_ih),
+                            ("w_hh.grad", w_hh.grad, dw_hh), ("b_ih.grad", b_ih.grad, db_ih), ("b_hh.grad", b_hh.grad, db_hh)):
+        assert got.shape == want.shape and torch.equal(got, want), name
+
+
 @pytest.mark.parametrize("B", [32768, 4096, 1030])
 def test_gru_step_multi_equals_separate_cells(B):
     """ops.gru_step_multi: actor's and critic's rollout GRU step, the two cells of every layer in one launch, hidden states updated in
