@@ -1005,69 +1005,138 @@ namespace {
 // TEACH (k_pathfinder_teach, section 7o): the same body with a per-environment cached field and the imitation labels.  A hit loads D
 // from the cache and skips the sweeps; pen and nb are rebuilt either way (they depend on s: two passes, not a relaxation).  The
 // environment's workgroup is the only writer of its cache rows, so the counter and the key are plain stores.
+// EPISODE (k_pathfinder_label_episode, section 7p): the same phases in a loop over the recorded states of one episode, with the grid, the
+// field and the words resident in LDS from tick to tick.
+//
+// The phases both bodies are made of.  pf_lds is the one LDS layout (pepath::lds_bytes).
+struct pf_lds {
+    double *def, *eva;     // [4][P], [4]: the tick's records, contiguous
+    int32_t *D, *flag, *kst;
+    uint16_t *nb;
+    uint8_t *grid, *pen, *bl, *cr;
+};
+
+__device__ __forceinline__ pf_lds pf_layout(unsigned char *smem, int WH, int P) {
+    const size_t WH16 = ((size_t)WH + 15) & ~(size_t)15;
+    pf_lds L;
+    L.def = (double *)smem;                            // [4][P]
+    L.eva = L.def + 4 * P;                             // [4]
+    L.D = (int32_t *)(L.eva + 4);                      // [WH]
+    L.flag = L.D + WH;                                 // [2][4] "this wave changed a cell", by sweep parity (+ padding to 16)
+    L.kst = L.flag + 16;                               // [PE_MAX_P]
+    L.nb = (uint16_t *)(L.kst + PE_MAX_P);             // [WH]
+    L.grid = (uint8_t *)(L.nb + WH);                   // [WH]
+    L.pen = L.grid + WH16;                             // [WH]
+    L.bl = L.pen + WH16;                               // [P][16] candidate k of pursuer i is blocked
+    L.cr = L.bl + 16 * PE_MAX_P;                       // [P][16] ... is crowded
+    return L;
+}
+
+// the environment's grid -> LDS, by words when W*H and the row's address allow it.  No barrier.
+__device__ __forceinline__ void pf_load_grid(const pf_lds &L, const uint8_t *__restrict__ gsrc, int WH, int tid) {
+    using namespace pepath;
+    if ((WH & 3) == 0 && (((uintptr_t)gsrc) & 3) == 0) {
+        for (int i = tid; i < (WH >> 2); i += THREADS) ((uint32_t *)L.grid)[i] = ((const uint32_t *)gsrc)[i];
+    } else {
+        for (int i = tid; i < WH; i += THREADS) L.grid[i] = gsrc[i];
+    }
+}
+
+// the penalty bits and the neighbour words of source s, and (init_field) the field's start D[s] = 0, UNREACHED elsewhere.  Needs the
+// grid complete (a barrier before); ends on a barrier.
+__device__ __forceinline__ void pf_words(const pe_config &c, const pf_lds &L, int s, bool init_field, int tid) {
+    using namespace pepath;
+    const int H = c.H, WH = c.W * H;
+    for (int id = tid; id < WH; id += THREADS) {
+        const int x = id / H;
+        L.pen[id] = pen_cell(c, L.grid, x, id - x * H, s);
+        if (init_field) L.D[id] = id == s ? 0 : UNREACHED;
+    }
+    __syncthreads();
+    for (int id = tid; id < WH; id += THREADS) {
+        const int x = id / H;
+        L.nb[id] = neighbour_word(c, L.grid, L.pen, x, id - x * H, s);
+    }
+    __syncthreads();
+}
+
+// relaxes the field in place until a sweep changes nothing; every lane leaves on the same barrier with the same result: true when
+// the W*H sweep bound was hit.  *sweeps = sweeps run.
+__device__ __forceinline__ bool pf_relax(const pe_config &c, const pf_lds &L, int s, int32_t clearance, int tid, int *sweeps) {
+    using namespace pepath;
+    const int H = c.H, WH = c.W * H;
+    bool capped = false;
+    int sweep = 0;
+    for (;; sweep++) {   // leaves after at most W*H sweeps
+        bool changed = false;
+        for (int id = tid; id < WH; id += THREADS) {
+            const uint32_t w = L.nb[id];
+            if (w == 0 || id == s) continue;
+            int kb;
+            const int32_t v = relax_cell(w, L.D, id, H, clearance, &kb);
+            if (v < L.D[id]) { L.D[id] = v; changed = true; }
+        }
+        const bool wave_changed = __ballot(changed) != 0ull;
+        if ((tid & (WAVE - 1)) == 0) L.flag[(sweep & 1) * 4 + (tid >> 6)] = wave_changed ? 1 : 0;
+        __syncthreads();
+        const int32_t *f = L.flag + (sweep & 1) * 4;
+        if ((f[0] | f[1] | f[2] | f[3]) == 0) break;
+        if (sweep + 1 >= WH) { capped = true; break; }
+    }
+    *sweeps = sweep + 1;
+    return capped;
+}
+
+// the P x 9 candidate flags on waves 0..2 and the P headings on wave 3, from def / eva / grid / D / nb in LDS.  Ends on a barrier,
+// after which no lane reads def or eva again.
+__device__ __forceinline__ void pf_evaluate(const pe_config &c, const pf_lds &L, const pe_pathfinder_params &prm, double itau, double i6, int tid) {
+    using namespace pepath;
+    const int P = c.P;
+    if (tid < P * 9) {
+        const int i = tid / 9, k = tid - 9 * i;
+        bool b, n;
+        candidate_flags(c, itau, i6, L.grid, L.def, i, k, prm.sep_range * prm.sep_range, &b, &n);
+        L.bl[i * 16 + k] = b ? 1 : 0;
+        L.cr[i * 16 + k] = n ? 1 : 0;
+    } else if (tid >= 3 * WAVE && tid - 3 * WAVE < P) {
+        const int i = tid - 3 * WAVE;
+        L.kst[i] = heading(c, L.grid, L.D, L.nb, prm, L.def[i], L.def[P + i], L.eva);
+    }
+    __syncthreads();
+}
+
+// pursuer i's choice from the flags and the heading pf_evaluate left; *blocked = its nine static-map bits
+__device__ __forceinline__ int32_t pf_choose(const pf_lds &L, int i, uint32_t *blocked) {
+    uint32_t bm = 0, cm = 0;
+    for (int k = 0; k < 9; k++) { bm |= (uint32_t)L.bl[i * 16 + k] << k; cm |= (uint32_t)L.cr[i * 16 + k] << k; }
+    *blocked = bm;
+    return pepath::choose(L.kst[i], bm, cm);
+}
+
 template <bool TEACH>
 __device__ __forceinline__ void pathfinder_body(const pe_config &c, const pe_state &st, const pe_pathfinder_params &prm, const double itau, const double i6,
                                                 int32_t *__restrict__ actions, const pe_pathfinder_diag &dg, int32_t *__restrict__ sweeps_out,
                                                 const pe_pathfinder_cache &ca, const pe_pathfinder_label &lb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using namespace pepath;
-    const int env = blockIdx.x, tid = threadIdx.x, W = c.W, H = c.H, WH = W * H, P = c.P;
-    const size_t WH16 = ((size_t)WH + 15) & ~(size_t)15;
-    double *def = (double *)smem;                      // [4][P]
-    double *eva = def + 4 * P;                         // [4]
-    int32_t *D = (int32_t *)(eva + 4);                 // [WH]
-    int32_t *flag = D + WH;                            // [2][4] "this wave changed a cell", by sweep parity (+ padding to 16)
-    int32_t *kst = flag + 16;                          // [PE_MAX_P]
-    uint16_t *nb = (uint16_t *)(kst + PE_MAX_P);       // [WH]
-    uint8_t *grid = (uint8_t *)(nb + WH);              // [WH]
-    uint8_t *pen = grid + WH16;                        // [WH]
-    uint8_t *bl = pen + WH16;                          // [P][16] candidate k of pursuer i is blocked
-    uint8_t *cr = bl + 16 * PE_MAX_P;                  // [P][16] ... is crowded
-    const uint8_t *gsrc = st.grid + (size_t)env * WH;
-    if ((WH & 3) == 0 && (((uintptr_t)gsrc) & 3) == 0) {
-        for (int i = tid; i < (WH >> 2); i += THREADS) ((uint32_t *)grid)[i] = ((const uint32_t *)gsrc)[i];
-    } else {
-        for (int i = tid; i < WH; i += THREADS) grid[i] = gsrc[i];
-    }
-    if (tid < 4 * P) def[tid] = st.def[(size_t)env * 4 * P + tid];
-    if (tid < 4) eva[tid] = st.eva[(size_t)env * 4 + tid];
+    const int env = blockIdx.x, tid = threadIdx.x, WH = c.W * c.H, P = c.P;
+    const pf_lds L = pf_layout(smem, WH, P);
+    int32_t *D = L.D;
+    pf_load_grid(L, st.grid + (size_t)env * WH, WH, tid);
+    if (tid < 4 * P) L.def[tid] = st.def[(size_t)env * 4 * P + tid];
+    if (tid < 4) L.eva[tid] = st.eva[(size_t)env * 4 + tid];
     __syncthreads();
-    const int s = cell_id(c, eva[0], eva[1]);
+    const int s = cell_id(c, L.eva[0], L.eva[1]);
     bool hit = false;
     if (TEACH && ca.key) hit = ca.key[2 * (size_t)env] == s && ca.key[2 * (size_t)env + 1] == prm.clearance;   // uniform over the workgroup
     if (hit) {
         const int32_t *fsrc = ca.field + (size_t)env * WH;
         for (int id = tid; id < WH; id += THREADS) D[id] = fsrc[id];
     }
-    for (int id = tid; id < WH; id += THREADS) {
-        const int x = id / H;
-        pen[id] = pen_cell(c, grid, x, id - x * H, s);
-        if (!hit) D[id] = id == s ? 0 : UNREACHED;
-    }
-    __syncthreads();
-    for (int id = tid; id < WH; id += THREADS) {
-        const int x = id / H;
-        nb[id] = neighbour_word(c, grid, pen, x, id - x * H, s);
-    }
-    __syncthreads();
+    pf_words(c, L, s, !hit, tid);
     bool capped = false;
-    int sweep = 0;
-    for (; !hit; sweep++) {   // leaves after at most W*H sweeps
-        bool changed = false;
-        for (int id = tid; id < WH; id += THREADS) {
-            const uint32_t w = nb[id];
-            if (w == 0 || id == s) continue;
-            int kb;
-            const int32_t v = relax_cell(w, D, id, H, prm.clearance, &kb);
-            if (v < D[id]) { D[id] = v; changed = true; }
-        }
-        const bool wave_changed = __ballot(changed) != 0ull;
-        if ((tid & (WAVE - 1)) == 0) flag[(sweep & 1) * 4 + (tid >> 6)] = wave_changed ? 1 : 0;
-        __syncthreads();
-        const int32_t *f = flag + (sweep & 1) * 4;
-        if ((f[0] | f[1] | f[2] | f[3]) == 0) break;
-        if (sweep + 1 >= WH) { capped = true; break; }
-    }
+    int sweeps = 0;
+    if (!hit) capped = pf_relax(c, L, s, prm.clearance, tid, &sweeps);
     if (TEACH && ca.key) {
         if (hit) {
             if (ca.hits && tid == 0) ca.hits[env] = ca.hits[env] + 1;
@@ -1080,21 +1149,11 @@ __device__ __forceinline__ void pathfinder_body(const pe_config &c, const pe_sta
             }
         }
     }
-    if (tid < P * 9) {
-        const int i = tid / 9, k = tid - 9 * i;
-        bool b, n;
-        candidate_flags(c, itau, i6, grid, def, i, k, prm.sep_range * prm.sep_range, &b, &n);
-        bl[i * 16 + k] = b ? 1 : 0;
-        cr[i * 16 + k] = n ? 1 : 0;
-    } else if (tid >= 3 * WAVE && tid - 3 * WAVE < P) {
-        const int i = tid - 3 * WAVE;
-        kst[i] = heading(c, grid, D, nb, prm, def[i], def[P + i], eva);
-    }
-    __syncthreads();
+    pf_evaluate(c, L, prm, itau, i6, tid);
     if (tid < P) {
-        uint32_t bm = 0, cm = 0;
-        for (int k = 0; k < 9; k++) { bm |= (uint32_t)bl[tid * 16 + k] << k; cm |= (uint32_t)cr[tid * 16 + k] << k; }
-        const int32_t a = choose(kst[tid], bm, cm);
+        const int32_t *kst = L.kst;
+        uint32_t bm;
+        const int32_t a = pf_choose(L, tid, &bm);
         if (!TEACH || actions) actions[(size_t)env * P + tid] = a;
         if (TEACH) {
             if (lb.a_star) lb.a_star[(size_t)env * (size_t)lb.a_star_env_stride + tid] = (float)a;
@@ -1105,8 +1164,80 @@ __device__ __forceinline__ void pathfinder_body(const pe_config &c, const pe_sta
     }
     if (dg.field)
         for (int id = tid; id < WH; id += THREADS) dg.field[(size_t)env * WH + id] = D[id];
-    if (sweeps_out && tid == 0) sweeps_out[env] = hit ? 0 : sweep + 1;
+    if (sweeps_out && tid == 0) sweeps_out[env] = hit ? 0 : sweeps;
     if (capped && tid == 0) st.meta[(size_t)env * PE_META_INTS + PE_META_STATUS] |= PE_STATUS_PATH_CAP;
+}
+
+// EPISODE: the labels of all T recorded ticks of one environment.  `resident` is the cell the field, pen and nb in LDS were built for
+// (-1: none); it lives in a register and every lane derives it from the same LDS values, so the rebuild branch is uniform.  A tick's
+// records are fetched into a register one tick ahead and staged at the top of the tick: the last reads of def / eva of the tick before
+// lie ahead of pf_evaluate's closing barrier, and the chooser lanes' reads of bl / cr / kst lie ahead of the staging barrier of the
+// next tick, so two barriers a tick order everything on a resident field.
+__device__ __forceinline__ void pathfinder_episode_body(const pe_config &c, const pe_state &st, const pe_pathfinder_params &prm, const double itau,
+                                                        const double i6, const pe_pathfinder_trace &tr, float *__restrict__ a_star,
+                                                        const int64_t a_env_stride, const int64_t a_tick_stride, int32_t *__restrict__ builds,
+                                                        const pe_pathfinder_diag &dg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    using namespace pepath;
+    const int env = blockIdx.x, tid = threadIdx.x, WH = c.W * c.H, P = c.P, T = tr.T;
+    const pf_lds L = pf_layout(smem, WH, P);
+    pf_load_grid(L, st.grid + (size_t)env * WH, WH, tid);
+    // lane tid < 4P carries def[tid], the next four lanes carry eva: one record element a lane and tick
+    const double *src = nullptr;
+    int64_t src_tick = 0;
+    if (tid < 4 * P) { src = tr.def + (size_t)env * (size_t)tr.def_env_stride + tid; src_tick = tr.def_tick_stride; }
+    else if (tid < 4 * P + 4) { src = tr.eva + (size_t)env * (size_t)tr.eva_env_stride + (tid - 4 * P); src_tick = tr.eva_tick_stride; }
+    double ahead = src ? src[0] : 0.0;
+    int resident = -1, n_builds = 0;
+    bool any_capped = false;
+    for (int t = 0; t < T; t++) {
+        if (src) L.def[tid] = ahead;   // eva follows def in LDS
+        if (src && t + 1 < T) ahead = src[(size_t)(t + 1) * (size_t)src_tick];
+        __syncthreads();   // the records (and at t = 0 the grid) are in LDS
+        const int s = cell_id(c, L.eva[0], L.eva[1]);
+        if (s != resident) {
+            pf_words(c, L, s, true, tid);
+            int sweeps;
+            const bool capped = pf_relax(c, L, s, prm.clearance, tid, &sweeps);
+            resident = capped ? -1 : s;
+            any_capped = any_capped || capped;
+            n_builds++;
+        }
+        pf_evaluate(c, L, prm, itau, i6, tid);
+        const bool last = t == T - 1;
+        if (tid < P) {
+            uint32_t bm;
+            const int32_t a = pf_choose(L, tid, &bm);
+            a_star[(size_t)env * (size_t)a_env_stride + (size_t)t * (size_t)a_tick_stride + tid] = (float)a;
+            if (last && dg.kstar) dg.kstar[(size_t)env * P + tid] = L.kst[tid];
+            if (last && dg.blocked) dg.blocked[(size_t)env * P + tid] = (uint16_t)bm;
+        }
+        if (last && dg.field)
+            for (int id = tid; id < WH; id += THREADS) dg.field[(size_t)env * WH + id] = L.D[id];
+    }
+    if (builds && tid == 0) builds[env] = n_builds;
+    if (any_capped && tid == 0) st.meta[(size_t)env * PE_META_INTS + PE_META_STATUS] |= PE_STATUS_PATH_CAP;
+}
+
+__global__ __launch_bounds__(pepath::THREADS) void k_pathfinder_label_episode(const pe_config c, const pe_state st, const pe_pathfinder_params prm,
+                                                                              const double itau, const double i6, const pe_pathfinder_trace tr,
+                                                                              float *__restrict__ a_star, const int64_t a_env_stride,
+                                                                              const int64_t a_tick_stride, int32_t *__restrict__ builds,
+                                                                              const pe_pathfinder_diag dg) {
+    pathfinder_episode_body(c, st, prm, itau, i6, tr, a_star, a_env_stride, a_tick_stride, builds, dg);
+}
+
+// one tick's row of a trace: every environment's def and eva records, one element a lane
+__global__ __launch_bounds__(256) void k_record_state(const int32_t N, const int32_t P, const double *__restrict__ def, const double *__restrict__ eva,
+                                                      double *__restrict__ def_out, const int64_t def_env_stride, double *__restrict__ eva_out,
+                                                      const int64_t eva_env_stride) {
+    const int rec = 4 * P + 4;
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= (int64_t)N * rec) return;
+    const int64_t n = g / rec;
+    const int j = (int)(g - n * rec);
+    if (j < 4 * P) def_out[n * def_env_stride + j] = def[n * 4 * P + j];
+    else eva_out[n * eva_env_stride + (j - 4 * P)] = eva[n * 4 + (j - 4 * P)];
 }
 
 __global__ __launch_bounds__(pepath::THREADS) void k_pathfinder(const pe_config c, const pe_state st, const pe_pathfinder_params prm, const double itau,
@@ -1820,9 +1951,79 @@ int pe_pursuer_pathfinder_teach(const pe_config *cfg, const pe_state *st, const 
     return (int)hipGetLastError();
 }
 
-// the host twin of both instances: ca / lb all NULL is the plain pathfinder
-static void pathfinder_rows_host(const pe_config &c, int32_t N, const uint8_t *grid, const double *def, const double *eva, const pe_pathfinder_params &p,
-                                 const pe_pathfinder_cache &ca, const pe_pathfinder_label &lb, int32_t *actions, const pe_pathfinder_diag *diag) {
+// what the episode entry points refuse beyond pathfinder_check
+static int episode_check(const pe_config *cfg, const pe_pathfinder_params *prm, const pe_pathfinder_trace *trace, const float *a_star,
+                         int64_t a_star_env_stride, int64_t a_star_tick_stride, pe_pathfinder_params *p) {
+    if (!cfg) return PE_ERR_NULL;
+    const int rc = pathfinder_check(cfg, prm, p);
+    if (rc) return rc;
+    if (!trace || !trace->def || !trace->eva || !a_star) return PE_ERR_NULL;
+    const int64_t P = cfg->P;
+    if (trace->T < 1 || a_star_env_stride < P || a_star_tick_stride < P) return PE_ERR_BAD_CONFIG;
+    if (trace->def_env_stride < 4 * P || trace->def_tick_stride < 4 * P || trace->eva_env_stride < 4 || trace->eva_tick_stride < 4) return PE_ERR_BAD_CONFIG;
+    return 0;
+}
+
+int pe_pathfinder_label_episode(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, const pe_pathfinder_trace *trace,
+                                float *a_star, int64_t a_star_env_stride, int64_t a_star_tick_stride, int32_t *builds,
+                                const pe_pathfinder_diag *diag, void *stream) {
+    if (!st) return PE_ERR_NULL;
+    pe_pathfinder_params p;
+    const int rc = episode_check(cfg, prm, trace, a_star, a_star_env_stride, a_star_tick_stride, &p);
+    if (rc) return rc;
+    if (st->N <= 0) return 0;
+    if (!st->grid || !st->meta) return PE_ERR_NULL;
+    pe_pathfinder_diag dg;
+    memset(&dg, 0, sizeof dg);
+    if (diag) dg = *diag;
+    const size_t lds = pepath::lds_bytes(cfg->W * cfg->H, cfg->P);
+    static std::once_flag once;
+    static hipError_t raised = hipSuccess;
+    const int e = pathfinder_lds((const void *)k_pathfinder_label_episode, once, raised, lds);
+    if (e) return e;
+    hipLaunchKernelGGL(k_pathfinder_label_episode, dim3(st->N), dim3(pepath::THREADS), lds, (hipStream_t)stream, *cfg, *st, p,
+                       div_const_reciprocal(cfg->def_tau), div_const_reciprocal(6.0), *trace, a_star, a_star_env_stride, a_star_tick_stride, builds, dg);
+    return (int)hipGetLastError();
+}
+
+static int record_state_check(const pe_config *cfg, const double *def, const double *eva, const double *def_out, int64_t def_env_stride,
+                              const double *eva_out, int64_t eva_env_stride) {
+    if (!cfg || !def || !eva || !def_out || !eva_out) return PE_ERR_NULL;
+    if (cfg->P < 1 || cfg->P > PE_MAX_P || def_env_stride < 4 * (int64_t)cfg->P || eva_env_stride < 4) return PE_ERR_BAD_CONFIG;
+    return 0;
+}
+
+int pe_env_record_state(const pe_config *cfg, const pe_state *st, double *def_out, int64_t def_env_stride, double *eva_out, int64_t eva_env_stride,
+                        void *stream) {
+    if (!st) return PE_ERR_NULL;
+    if (st->N <= 0) return cfg ? 0 : PE_ERR_NULL;
+    const int rc = record_state_check(cfg, st->def, st->eva, def_out, def_env_stride, eva_out, eva_env_stride);
+    if (rc) return rc;
+    const int64_t total = (int64_t)st->N * (4 * cfg->P + 4);
+    hipLaunchKernelGGL(k_record_state, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, st->N, cfg->P, st->def, st->eva, def_out,
+                       def_env_stride, eva_out, eva_env_stride);
+    return (int)hipGetLastError();
+}
+
+int pe_env_record_state_host(const pe_config *cfg, int32_t N, const double *def, const double *eva, double *def_out, int64_t def_env_stride,
+                             double *eva_out, int64_t eva_env_stride) {
+    if (N <= 0) return cfg ? 0 : PE_ERR_NULL;
+    const int rc = record_state_check(cfg, def, eva, def_out, def_env_stride, eva_out, eva_env_stride);
+    if (rc) return rc;
+    const int P = cfg->P;
+    for (int64_t n = 0; n < N; n++) {
+        for (int j = 0; j < 4 * P; j++) def_out[n * def_env_stride + j] = def[n * 4 * P + j];
+        for (int j = 0; j < 4; j++) eva_out[n * eva_env_stride + j] = eva[n * 4 + j];
+    }
+    return 0;
+}
+
+// the host twin of all three instances: the states come as a trace of T ticks (the per-tick twins pass their one state as a trace with
+// T = 1); ca / lb all NULL and T = 1 is the plain pathfinder.  Within an environment's ticks the field of the tick before stays resident
+// as in k_pathfinder_label_episode; actions, the follow rows and diag belong to the last tick.  a_tick: a_star's tick stride.
+static void pathfinder_rows_host(const pe_config &c, int32_t N, const uint8_t *grid, const pe_pathfinder_trace &tr, const pe_pathfinder_params &p,
+                                 const pe_pathfinder_cache &ca, const pe_pathfinder_label &lb, int64_t a_tick, int32_t *actions, int32_t *builds,
+                                 const pe_pathfinder_diag *diag) {
     const int WH = c.W * c.H, P = c.P;
     const double itau = div_const_reciprocal(c.def_tau), i6 = div_const_reciprocal(6.0);
     std::vector<int32_t> D(WH);
@@ -1830,38 +2031,76 @@ static void pathfinder_rows_host(const pe_config &c, int32_t N, const uint8_t *g
     std::vector<uint8_t> pen(WH);
     for (int n = 0; n < N; n++) {
         const uint8_t *g = grid + (size_t)n * WH;
-        const double *d = def + (size_t)n * 4 * P, *e = eva + (size_t)n * 4;
-        const int s = pepath::cell_id(c, e[0], e[1]);
-        if (ca.key && ca.key[2 * (size_t)n] == s && ca.key[2 * (size_t)n + 1] == p.clearance) {
-            memcpy(D.data(), ca.field + (size_t)n * WH, sizeof(int32_t) * WH);
-            pepath::words_host(c, g, s, pen.data(), nb.data());
-            if (ca.hits) ca.hits[n] += 1;
-        } else {
-            const int sweeps = pepath::field_host(c, g, s, p.clearance, D.data(), pen.data(), nb.data());
-            if (ca.key) {
-                memcpy(ca.field + (size_t)n * WH, D.data(), sizeof(int32_t) * WH);
-                ca.key[2 * (size_t)n] = sweeps < 0 ? -1 : s;
-                ca.key[2 * (size_t)n + 1] = p.clearance;
+        int resident = -1, n_builds = 0;
+        for (int t = 0; t < tr.T; t++) {
+            const double *d = tr.def + (size_t)n * (size_t)tr.def_env_stride + (size_t)t * (size_t)tr.def_tick_stride;
+            const double *e = tr.eva + (size_t)n * (size_t)tr.eva_env_stride + (size_t)t * (size_t)tr.eva_tick_stride;
+            const bool last = t == tr.T - 1;
+            const int s = pepath::cell_id(c, e[0], e[1]);
+            if (s == resident) {
+                // D, pen and nb stand
+            } else if (ca.key && ca.key[2 * (size_t)n] == s && ca.key[2 * (size_t)n + 1] == p.clearance) {
+                memcpy(D.data(), ca.field + (size_t)n * WH, sizeof(int32_t) * WH);
+                pepath::words_host(c, g, s, pen.data(), nb.data());
+                if (ca.hits) ca.hits[n] += 1;
+                resident = s;
+            } else {
+                const int sweeps = pepath::field_host(c, g, s, p.clearance, D.data(), pen.data(), nb.data());
+                resident = sweeps < 0 ? -1 : s;
+                n_builds++;
+                if (ca.key) {
+                    memcpy(ca.field + (size_t)n * WH, D.data(), sizeof(int32_t) * WH);
+                    ca.key[2 * (size_t)n] = resident;
+                    ca.key[2 * (size_t)n + 1] = p.clearance;
+                }
+            }
+            if (last && diag && diag->field) memcpy(diag->field + (size_t)n * WH, D.data(), sizeof(int32_t) * WH);
+            for (int i = 0; i < P; i++) {
+                uint32_t bm = 0, cm = 0;
+                for (int k = 0; k < 9; k++) {
+                    bool b, q;
+                    pepath::candidate_flags(c, itau, i6, g, d, i, k, p.sep_range * p.sep_range, &b, &q);
+                    bm |= (uint32_t)b << k;
+                    cm |= (uint32_t)q << k;
+                }
+                const int ks = pepath::heading(c, g, D.data(), nb.data(), p, d[i], d[P + i], e);
+                const int32_t a = pepath::choose(ks, bm, cm);
+                if (lb.a_star) lb.a_star[(size_t)n * (size_t)lb.a_star_env_stride + (size_t)t * (size_t)a_tick + i] = (float)a;
+                if (!last) continue;
+                if (actions) actions[(size_t)n * P + i] = a;
+                if (lb.follow && lb.follow[n] != 0) lb.action[(size_t)n * P + i] = a;
+                if (diag && diag->kstar) diag->kstar[(size_t)n * P + i] = ks;
+                if (diag && diag->blocked) diag->blocked[(size_t)n * P + i] = (uint16_t)bm;
             }
         }
-        if (diag && diag->field) memcpy(diag->field + (size_t)n * WH, D.data(), sizeof(int32_t) * WH);
-        for (int i = 0; i < P; i++) {
-            uint32_t bm = 0, cm = 0;
-            for (int k = 0; k < 9; k++) {
-                bool b, q;
-                pepath::candidate_flags(c, itau, i6, g, d, i, k, p.sep_range * p.sep_range, &b, &q);
-                bm |= (uint32_t)b << k;
-                cm |= (uint32_t)q << k;
-            }
-            const int ks = pepath::heading(c, g, D.data(), nb.data(), p, d[i], d[P + i], e);
-            const int32_t a = pepath::choose(ks, bm, cm);
-            if (actions) actions[(size_t)n * P + i] = a;
-            if (lb.a_star) lb.a_star[(size_t)n * (size_t)lb.a_star_env_stride + i] = (float)a;
-            if (lb.follow && lb.follow[n] != 0) lb.action[(size_t)n * P + i] = a;
-            if (diag && diag->kstar) diag->kstar[(size_t)n * P + i] = ks;
-            if (diag && diag->blocked) diag->blocked[(size_t)n * P + i] = (uint16_t)bm;
-        }
+        if (builds) builds[n] = n_builds;
     }
+}
+
+// the per-tick twins' one state as a trace
+static pe_pathfinder_trace one_tick_trace(const pe_config &c, const double *def, const double *eva) {
+    pe_pathfinder_trace tr;
+    memset(&tr, 0, sizeof tr);
+    tr.def = def; tr.def_env_stride = tr.def_tick_stride = 4 * (int64_t)c.P;
+    tr.eva = eva; tr.eva_env_stride = tr.eva_tick_stride = 4;
+    tr.T = 1;
+    return tr;
+}
+
+int pe_pathfinder_label_episode_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const pe_pathfinder_params *prm,
+                                     const pe_pathfinder_trace *trace, float *a_star, int64_t a_star_env_stride, int64_t a_star_tick_stride,
+                                     int32_t *builds, const pe_pathfinder_diag *diag) {
+    pe_pathfinder_params p;
+    const int rc = episode_check(cfg, prm, trace, a_star, a_star_env_stride, a_star_tick_stride, &p);
+    if (rc) return rc;
+    if (N <= 0) return 0;
+    if (!grid) return PE_ERR_NULL;
+    pe_pathfinder_label lb;
+    memset(&lb, 0, sizeof lb);
+    lb.a_star = a_star;
+    lb.a_star_env_stride = a_star_env_stride;
+    pathfinder_rows_host(*cfg, N, grid, *trace, p, pe_pathfinder_cache{}, lb, a_star_tick_stride, nullptr, builds, diag);
+    return 0;
 }
 
 int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const double *def, const double *eva,
@@ -1872,7 +2111,7 @@ int pe_pursuer_pathfinder_host(const pe_config *cfg, int32_t N, const uint8_t *g
     if (rc) return rc;
     if (N <= 0) return 0;
     if (!grid || !def || !eva) return PE_ERR_NULL;
-    pathfinder_rows_host(*cfg, N, grid, def, eva, p, pe_pathfinder_cache{}, pe_pathfinder_label{}, actions, diag);
+    pathfinder_rows_host(*cfg, N, grid, one_tick_trace(*cfg, def, eva), p, pe_pathfinder_cache{}, pe_pathfinder_label{}, 0, actions, nullptr, diag);
     return 0;
 }
 
@@ -1886,7 +2125,7 @@ int pe_pursuer_pathfinder_teach_host(const pe_config *cfg, int32_t N, const uint
     if (rc) return rc;
     if (N <= 0) return 0;
     if (!grid || !def || !eva) return PE_ERR_NULL;
-    pathfinder_rows_host(*cfg, N, grid, def, eva, p, ca, lb, actions, diag);
+    pathfinder_rows_host(*cfg, N, grid, one_tick_trace(*cfg, def, eva), p, ca, lb, 0, actions, nullptr, diag);
     return 0;
 }
 

@@ -18,10 +18,10 @@ KICK_SUMS = 3   # csrc/kickstart.hpp: the imitation metric's sum, the live-row c
 
 
 class KickstartOptions:
-    """the validated algo.bc_coef* keys; `on` is bc_coef > 0"""
+    """the validated algo.<prefix>coef* keys (`kickstart_options`); `on` is coef > 0, `key` the name of the coefficient's key"""
 
-    def __init__(self, coef, decay, iterations):
-        self.coef, self.decay, self.iterations = coef, decay, iterations
+    def __init__(self, coef, decay, iterations, key=KEY):
+        self.coef, self.decay, self.iterations, self.key = coef, decay, iterations, key
         self.on = coef > 0.0
 
     def coef_at(self, j):
@@ -35,16 +35,18 @@ class KickstartOptions:
         return (self.coef, self.decay, self.iterations)
 
 
-def kickstart_options(cfg):
-    """-> KickstartOptions of cfg.algo, validated (ValueError naming the key)"""
+def kickstart_options(cfg, prefix="bc_"):
+    """-> KickstartOptions of cfg.algo's <prefix>coef, <prefix>coef_decay and <prefix>coef_iterations (prefix "bc_", or "pathfinder_bc_" on
+    the flagship: pursuit_kickstart.py), validated (ValueError naming the key)"""
     a = cfg.algo
-    coef = real(a, KEY, 0.0)
+    key = "algo." + prefix + "coef"
+    coef = real(a, key, 0.0)
     if not coef >= 0.0:
-        raise ValueError(f"{KEY}: {coef} is not >= 0")
-    decay = real(a, "algo.bc_coef_decay", DEFAULT_DECAY)
+        raise ValueError(f"{key}: {coef} is not >= 0")
+    decay = real(a, key + "_decay", DEFAULT_DECAY)
     if not 0.0 < decay <= 1.0:
-        raise ValueError(f"algo.bc_coef_decay: {decay} is not in (0, 1]")
-    return KickstartOptions(coef, decay, count(a, "algo.bc_coef_iterations", DEFAULT_ITERATIONS))
+        raise ValueError(f"{key}_decay: {decay} is not in (0, 1]")
+    return KickstartOptions(coef, decay, count(a, key + "_iterations", DEFAULT_ITERATIONS), key)
 
 
 def refuse_pursuit(cfg):
@@ -54,11 +56,17 @@ def refuse_pursuit(cfg):
                          "pursuers (set bc_coef to 0)")
 
 
-def check_entry(agent, entry, what):
-    """ValueError naming the config key when a resume bundle's "bc_coef" entry (None: written with the feature off) is not this agent's
-    setting: lambda of every iteration follows from the three values, and others would not continue the run"""
+def check_options_entry(options, entry, what):
+    """ValueError naming the coefficient's config key when a resume bundle's entry of it (None: written with the feature off) is not
+    `options`: lambda of every iteration follows from the three values, and others would not continue the run"""
     theirs = None if entry is None else tuple(entry)
-    mine = agent.kick.entry() if agent.kick.on else None
+    mine = options.entry() if options.on else None
     if theirs != mine:
-        show = lambda e: "0 (off)" if e is None else f"{e[0]} (bc_coef_decay {e[1]}, bc_coef_iterations {e[2]})"
-        raise ValueError(f"{what} was written with {KEY}: {show(theirs)}, this agent has {KEY}: {show(mine)}")
+        name = options.key.partition(".")[2]
+        show = lambda e: "0 (off)" if e is None else f"{e[0]} ({name}_decay {e[1]}, {name}_iterations {e[2]})"
+        raise ValueError(f"{what} was written with {options.key}: {show(theirs)}, this agent has {options.key}: {show(mine)}")
+
+
+def check_entry(agent, entry, what):
+    """the "bc_coef" entry of a resume bundle against this agent's setting"""
+    check_options_entry(agent.kick, entry, what)

@@ -38,6 +38,13 @@ algo.pathfinder_bc_iterations=K (cfg1..cfg4) makes the first K iterations an imi
 runtime.pathfinder_cache); each prints one JSON line with phase, bc_beta, bc_loss, bc_accuracy, critic_loss and pathfinder_hit_rate:
 
     python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg2 algo.pathfinder_bc_iterations=60 runtime.eval_baseline=pathfinder
+
+algo.pathfinder_bc_coef=C (cfg1..cfg4, with or without a warm start) keeps the imitation term in the PPO loss with lambda_j = C
+pathfinder_bc_coef_decay^j in PPO iteration j, cut off after pathfinder_bc_coef_iterations when that is > 0 (pursuit_imitation.py, DESIGN.md
+section 7p; runtime.pathfinder_labeller=episode|tick); each such iteration prints one JSON line with bc_coef, bc_aux_loss, bc_accuracy
+and pathfinder_build_rate:
+
+    python -m distributed_multi_agent_reinforcement_learning_amd.main --config cfg2 algo.pathfinder_bc_iterations=16 algo.pathfinder_bc_coef=1.0 algo.pathfinder_bc_coef_decay=0.9
 """
 import argparse
 import json

@@ -23,8 +23,8 @@ from .kickstart import refuse_pursuit as refuse_pursuit_kickstart
 from .model import build_actor_critic, pair_embeddings, pair_heads, sequence_forward_pair
 from .pe_env import status_or, status_text
 from .pursuit_baseline import pathfinder_options
-from .pursuit_imitation import pursuit_imitation_options
-from .readback import BcSums, read_back
+from .pursuit_imitation import pursuit_imitation_options, pursuit_kickstart_options
+from .readback import BcSums, KickSums, read_back
 from .team_reward import team_reward_options
 from .update_diag import UpdateDiag, update_diag_options
 
@@ -66,7 +66,8 @@ class ReplayBuffer:
         self.p_dim = self.e_dim = self.o_dim = cfg.env.state_dim
         self.embedding_size = cfg.algo.embedding_dim
         self.depth = cfg.algo.depth
-        self.labelled = pursuit_imitation_options(cfg).on   # algo.pathfinder_bc_iterations > 0: the field a_star exists
+        # algo.pathfinder_bc_iterations > 0 or algo.pathfinder_bc_coef > 0: the field a_star exists
+        self.labelled = pursuit_imitation_options(cfg).on or pursuit_kickstart_options(cfg).on
         self.buffer = None
 
     def reset_buffer(self):
@@ -87,7 +88,7 @@ class ReplayBuffer:
         b["r"] = z(N, T, P)
         b["active"] = z(N, T, P)
         if self.labelled:
-            b["a_star"] = z(N, T, P)   # the teacher's action of every tick (MAPPO.explore_expert)
+            b["a_star"] = z(N, T, P)   # the teacher's action of every tick (MAPPO.explore_expert, explore_labelled)
         self.o_static = z(N, O, self.o_dim)
         self.o_kvalid = torch.zeros(N, dtype=torch.int32, device=self.device)
         b["o_state"] = self.o_static[:, None].expand(N, T, O, self.o_dim)
@@ -237,7 +238,10 @@ class MAPPO(OptimizerSchedule):
         refuse_pursuit_kickstart(cfg)   # algo.bc_coef: likewise
         # algo.pathfinder_bc_iterations: the flagship's own warm start, from the path-finding pursuers
         self.pathfinder_bc = pursuit_imitation_options(cfg)
-        self.pathfinder_kw = pathfinder_options(cfg) if self.pathfinder_bc.on else None   # runtime.pathfinder_*: the teacher's parameters
+        # algo.pathfinder_bc_coef: the imitation term stays in the PPO loss, decaying; runtime.pathfinder_labeller
+        self.pathfinder_kick = pursuit_kickstart_options(cfg)
+        self.teacher = self.pathfinder_bc.on or self.pathfinder_kick.on   # the rollout can be labelled: the buffer has the a_star field
+        self.pathfinder_kw = pathfinder_options(cfg) if self.teacher else None   # runtime.pathfinder_*: the teacher's parameters
         self.update_diagnostics, _ = update_diag_options(cfg)   # what the update did, from the loss launches
         self.max_train_steps, self.lr, self.gamma, self.lamda = a.max_train_steps, a.lr, a.gamma, a.lamda
         self.epsilon, self.K_epochs, self.entropy_coef = a.epsilon, a.epochs, a.entropy_coef
@@ -288,19 +292,32 @@ class MAPPO(OptimizerSchedule):
         self.bc = BcSums(self.device) if self.pathfinder_bc.on else None   # the imitation metric: (label hits, live rows)
         self.last_bc = None            # (hits, rows) of the last train(imitation=True) call
         self.last_hit_rate = None      # explore_expert: cache hits / (environments x teacher launches) of the last call
+        self.kick_sums = KickSums(self.device) if self.pathfinder_kick.on else None   # (label hits, live rows, sum of -log p[label])
+        self.last_kick = None          # the three sums of the last train(kick=) call
+        self.last_build_rate = None    # explore_labelled: distance fields built / (environments x ticks) of the last call
+        self._kick = None              # lambda of the train(kick=) call in progress
 
     # ---- update (:638-723) ------------------------------------------------------------------------------------
-    def train(self, replay_buffer, total_steps, return_grads=True, imitation=False):
+    def train(self, replay_buffer, total_steps, return_grads=True, imitation=False, kick=None):
         """imitation (algo.pathfinder_bc_iterations): GAE, the mini-batch loop or _train_grouped, the accumulate-then-clip replay and the
         gradient bucket as ever; the mini-batch loss is ops.bc_loss_cat on buffer["a_star"] (_minibatch_losses), the update diagnostics
         and the learning-rate decay are skipped, and the two sums of the metric go over ranks and arrive in the call's one host read
-        (last_bc; bc_accuracy = hits / rows)."""
+        (last_bc; bc_accuracy = hits / rows).
+        kick (algo.pathfinder_bc_coef): lambda > 0 -- a PPO update in every respect (diagnostics, learning-rate
+        decay) whose mini-batch loss is ops.ppo_bc_loss_cat, the PPO loss plus lambda times the imitation loss on buffer["a_star"] from
+        one launch; its three sums go over ranks and arrive in the same host read (last_kick).  None or 0: train() as it stands."""
         if imitation and self.bc is None:
             raise ValueError("train(imitation=True) needs algo.pathfinder_bc_iterations > 0 (the buffer has no a_star field otherwise)")
+        kick = float(kick) if (kick and not imitation) else None
+        if kick is not None and self.kick_sums is None:
+            raise ValueError("train(kick=) needs algo.pathfinder_bc_coef > 0 (the buffer has no a_star field otherwise)")
         self._imitating = bool(imitation)
+        self._kick = kick
         self._update_diag = None if imitation else self.diag
         if imitation:
             self.bc.sums.zero_()
+        if kick is not None:
+            self.kick_sums.sums.zero_()
         batch = replay_buffer.get_training_data(self.device) if hasattr(replay_buffer, "get_training_data") else replay_buffer.buffer
         o_static = replay_buffer.o_static
         N, T, P = batch["r"].shape
@@ -339,6 +356,8 @@ class MAPPO(OptimizerSchedule):
                     self._update_diag.begin()
                 if imitation:
                     self.bc.sums.zero_()
+                if kick is not None:
+                    self.kick_sums.sums.zero_()
                 torch.cuda.empty_cache()
         for n0 in starts:
             n1 = min(n0 + self.mini_batch_size, N)
@@ -358,14 +377,18 @@ class MAPPO(OptimizerSchedule):
             object_critics = object_critics + critic_loss.detach().double()   # f64 sum on the device: no host sync per mini-batch
             object_actors = object_actors + actor_loss.detach().double()
             update_time += 1
-        diag = self._update_diag   # one read for the two losses and, all-reduced over ranks, the imitation's two sums or the diagnostics' eight
-        (object_critics, object_actors), bc, sums, norm = read_back((object_critics, object_actors), self.bc if imitation else None, diag,
-                                                                    None if diag is None else (diag.grad_norm,))
+        # one read for the two losses and, all-reduced over ranks, the imitation's two sums, the kickstart's three or the diagnostics' eight
+        diag = self._update_diag
+        (object_critics, object_actors), bc, kicked, sums, norm = read_back(
+            (object_critics, object_actors), self.bc if imitation else None, self.kick_sums if kick is not None else None, diag,
+            None if diag is None else (diag.grad_norm,))
         if imitation:
             self.last_bc = tuple(bc)
+        if kick is not None:
+            self.last_kick = tuple(kicked)
         if diag is not None:
             self.last_update_diag = diag.result(sums, norm[0])
-        self._imitating, self._update_diag = False, self.diag
+        self._imitating, self._kick, self._update_diag = False, None, self.diag
         if self.use_lr_decay and not imitation:
             self.lr_decay(total_steps)
         if not return_grads:  # device-side path: gradients stay in .grad for the flat all-reduce
@@ -395,6 +418,14 @@ class MAPPO(OptimizerSchedule):
             return ops.bc_loss_cat(prob, batch["a_star"][n0:n1], values, batch["active"][n0:n1], v_old, v_target[n0:n1], self.epsilon,
                                    self.use_value_clip, sums=self.bc.sums)
         dk = {} if self._update_diag is None else {"diag": self._update_diag.sums}   # algo.update_diagnostics: the loss call adds its eight sums
+        if self._kick is not None:   # the PPO row and the imitation row of every sample in one launch; the critic's bits are ppo_loss_prob's
+            values = values_now.squeeze(-1)
+            if not ops.ppo_loss_prob_ok(prob, values):
+                raise RuntimeError("train(kick=): ops.ppo_loss_prob_ok(prob, values) does not hold (fp32 device tensors, prob (mb, T, P, "
+                                   "A <= 16) with a dense last dimension, values (mb, T, P)); the imitation loss has no other path")
+            return ops.ppo_bc_loss_cat(prob, batch["a_n"][n0:n1], batch["a_star"][n0:n1], values, batch["a_logprob_n"][n0:n1], adv[n0:n1],
+                                       batch["active"][n0:n1], v_old, v_target[n0:n1], self.epsilon, self.entropy_coef, self._kick,
+                                       self.use_value_clip, sums=self.kick_sums.sums, **dk)
         if ops.ppo_loss_prob_ok(prob, values_now.squeeze(-1)):
             # Categorical(prob).log_prob / .entropy() (get_logprob_and_entropy, :451-456) evaluated inside the loss launch
             return ops.ppo_loss_prob(prob, batch["a_n"][n0:n1], values_now.squeeze(-1), batch["a_logprob_n"][n0:n1], adv[n0:n1], batch["active"][n0:n1],
@@ -493,9 +524,37 @@ class MAPPO(OptimizerSchedule):
         launch then stores in a_n as executed.  v_n, a_logprob_n, the embeddings, the sampling counter and the tick's reward-norm state
         are the network episode's own: a_logprob_n of a followed environment is the log-probability of the network's sample, not of
         the executed action (the imitation loss does not read it)."""
-        if not self.pathfinder_bc.on:
-            raise ValueError("explore_expert needs algo.pathfinder_bc_iterations > 0 (the buffer has no a_star field otherwise)")
+        if not self.teacher:
+            raise ValueError("explore_expert needs algo.pathfinder_bc_iterations > 0 or algo.pathfinder_bc_coef > 0 (the buffer has no "
+                             "a_star field otherwise)")
         return self.explore_env(env, num_episode, follow=follow_mask(beta, env.num_envs, self.device))
+
+    def explore_labelled(self, env, num_episode):
+        """explore_env with every tick labelled by the path-finding pursuers and no environment following them (algo.pathfinder_bc_coef,
+        DESIGN.md section 7p): every field explore_env writes carries explore_env's bits, and buffer["a_star"] the teacher's action.
+        runtime.pathfinder_labeller `tick`: explore_expert(env, num_episode, 0.0), the teacher's launch inside every tick.  `episode`:
+        each tick records the state its step reads (env.record_state, one small launch) into a scratch trace that is reused every episode
+        and is no part of the buffer, and one env.pathfinder_label_episode launch after the last step labels the whole episode.
+        last_build_rate = distance fields built / (environments x ticks)."""
+        if not self.teacher:
+            raise ValueError("explore_labelled needs algo.pathfinder_bc_coef > 0 or algo.pathfinder_bc_iterations > 0 (the buffer has no "
+                             "a_star field otherwise)")
+        if self.pathfinder_kick.labeller == "tick":
+            out = self.explore_expert(env, num_episode, 0.0)
+            self.last_build_rate = 1.0 - self.last_hit_rate
+            return out
+        return self.explore_env(env, num_episode, trace=self._episode_trace(env))
+
+    def _episode_trace(self, env):
+        """the scratch trace of the episode labeller for this environment batch: def (N, T, 4, P) and eva (N, T, 4) float64, builds (N,)"""
+        tr = getattr(self, "_pf_trace", None)
+        N, T, P = env.num_envs, env.max_steps, env.num_defender
+        if tr is None or tr.defs.shape != (N, T, 4, P) or tr.defs.device != env.sim.device:
+            dev = env.sim.device
+            tr = self._pf_trace = types.SimpleNamespace(defs=torch.zeros((N, T, 4, P), dtype=torch.float64, device=dev),
+                                                        eva=torch.zeros((N, T, 4), dtype=torch.float64, device=dev),
+                                                        builds=torch.zeros((N,), dtype=torch.int32, device=dev))
+        return tr
 
     def _teacher_cache(self, env):
         """the teacher's distance-field cache for this environment batch (runtime.pathfinder_cache: false = None, every launch recomputes)"""
@@ -506,12 +565,15 @@ class MAPPO(OptimizerSchedule):
             cache = self._pf_cache = env.pathfinder_cache()
         return cache
 
-    def explore_env(self, env, num_episode, actions_override=None, init=None, follow=None):
+    def explore_env(self, env, num_episode, actions_override=None, init=None, follow=None, trace=None):
         N = env.num_envs
         cache = self._teacher_cache(env) if follow is not None else None
         if cache is not None:
             cache.hits.zero_()
         teach = {} if follow is None else dict(follow=follow, cache=cache)
+        if trace is not None:   # explore_labelled with the episode labeller
+            teach = dict(trace=trace)
+        builds = 0.0
         self.minibuffer = ReplayBuffer(self.cfg, N * num_episode, self.device).reset_buffer()
         exp_reward = 0.0
         sample_steps = 0
@@ -519,26 +581,34 @@ class MAPPO(OptimizerSchedule):
             ep_reward, ep_steps = self.run_episode(env, num_episode=k, actions_override=actions_override, init=init, **teach)
             # one read-back per episode: the mean return and the kernels' status bits (tape exhausted / A* cap / path
             # underflow silently break parity with the reference, so they are an error, not a statistic)
-            # (explore_expert: the cache's hit count so far rides in the same read)
+            # (explore_expert: the cache's hit count so far rides in the same read; explore_labelled: the episode's field builds)
             tail = () if cache is None else (cache.hits.sum().double(),)
+            if trace is not None:
+                tail = (trace.builds.sum().double(),)
             mean_r, bits, *hits = torch.stack((ep_reward.mean().double(), status_or(env.sim.meta).double(), *tail)).tolist()
             if bits:
                 raise RuntimeError("environment kernel status: " + status_text(int(bits)))
+            if trace is not None:
+                builds += hits[0]
             exp_reward += float(mean_r)
             sample_steps += ep_steps * N
         if follow is not None:
             self.last_hit_rate = hits[0] / sample_steps if cache is not None else 0.0
+        if trace is not None:
+            self.last_build_rate = builds / sample_steps
         return exp_reward / num_episode, self.minibuffer, sample_steps
 
     @torch.no_grad()
-    def run_episode(self, env, num_episode=0, actions_override=None, init=None, follow=None, cache=None):
+    def run_episode(self, env, num_episode=0, actions_override=None, init=None, follow=None, cache=None, trace=None):
         """N episodes in lockstep; rows [num_episode*N, (num_episode+1)*N) of the buffer.  Returns the per-environment
         episode reward (N,) and the episode length.  The per-tick policy program (actor + critic forward, history
         bookkeeping, sampling) runs on static device storage and is replayed as one captured hipGraph per tick
         (`runtime.use_graphs`), which removes ~70 launches of host overhead per tick; the eager path executes the very same
         program, so both produce identical buffers.
         follow (explore_expert): the (N,) uint8 mask of the environments that execute the teacher's action; every tick is labelled.
-        cache: the teacher's distance-field cache or None; emptied here after the reset, which rewrites the grid."""
+        cache: the teacher's distance-field cache or None; emptied here after the reset, which rewrites the grid.
+        trace (explore_labelled): the scratch trace of the episode labeller; every tick records the state its step reads, and one launch
+        after the last step writes the labels of the whole episode into buf["a_star"][rows] and the field builds into trace.builds."""
         N, P, T, d = env.num_envs, env.num_defender, env.max_steps, self.depth
         buf = self.minibuffer.buffer
         rows = slice(num_episode * N, (num_episode + 1) * N)
@@ -571,11 +641,15 @@ class MAPPO(OptimizerSchedule):
                 items += [(st.a_cur, buf["actor_historical_embedding"][rows, t + d]), (st.c_cur, buf["critic_historical_embedding"][rows, t + d])]
             # one launch records the tick (and adds the previous tick's raw reward to the episode return)
             ops.rollout_record(items, raw if t > 0 else None, episode_reward)
+            if trace is not None:   # the state the step below reads, which is what the per-tick teacher would have read
+                env.record_state(trace.defs[:, t], trace.eva[:, t])
             if t + 1 < T:
                 env.tick(st.a_n, st.obs, buf["r"][rows, t], raw)
             else:
                 env.sim.step(st.a_n, buf["r"][rows, t], raw)
                 env.time_step += 1
+        if trace is not None:   # the grid is still the episode's: the next reset comes after this launch
+            env.pathfinder_label_episode(trace.defs, trace.eva, buf["a_star"][rows], builds=trace.builds, **self.pathfinder_kw)
         episode_reward += raw.sum(-1)
         buf["active"][rows].fill_(1.0)
         # bootstrap value of the state after the last step (:807-825): only the critic's embedding enters the history

@@ -13,7 +13,7 @@ from . import kickstart as ks
 from . import ops
 from . import value_norm as vnorm
 from .minibatch_steps import MAX_GRAD_NORM, minibatch_steps_options
-from .readback import BcSums, read_back
+from .readback import BcSums, KickSums, read_back
 from .reward_shaping import reward_shaping_options
 from .team_reward import team_reward_options
 from .trainer import (BUCKET_ALIGN, FusedAdam, GradBucket, ParamBucket, ParticleRunState, allreduce_sum_, broadcast_weights_,
@@ -40,15 +40,6 @@ def finish_env(env, cfg, training):
         env.enable_reward_shaping(coef)
     env.set_guidance(*gd.guidance_options(cfg))
     return env
-
-
-class KickSums:
-    """the device side of the imitation term of teacher-regularised PPO (algo.bc_coef): the three sums the fused loss launches of one
-    train(kick=...) call add to"""
-
-    def __init__(self, device):
-        self.sums = torch.zeros(ks.KICK_SUMS, dtype=torch.float64, device=device)
-        self.allreduce = None      # the trainer's allreduce_sum_: the three sums over ranks, in place
 
 
 class ParticleMAPPO(im.OptimizerSchedule):

@@ -84,6 +84,12 @@ class PePathfinderLabel(C.Structure):
     _fields_ = [("follow", C.c_void_p), ("action", C.c_void_p), ("a_star", C.c_void_p), ("a_star_env_stride", C.c_int64)]
 
 
+class PePathfinderTrace(C.Structure):
+    """include/pe_env.h pe_pathfinder_trace"""
+    _fields_ = [("def_", C.c_void_p), ("def_env_stride", C.c_int64), ("def_tick_stride", C.c_int64),
+                ("eva", C.c_void_p), ("eva_env_stride", C.c_int64), ("eva_tick_stride", C.c_int64), ("T", C.c_int32), ("pad0", C.c_int32)]
+
+
 PATH_MAX_CELLS = 8192
 PATH_UNREACHED = 0x7FFFFFFF
 STATUS_PATH_CAP = 16
@@ -153,6 +159,63 @@ def pathfinder_teach_host(pe_cfg, grid, defs, eva, cache=None, follow=None, acti
     return (actions, out) if diag else actions
 
 
+def _stride(shape, strides, axis, record):
+    """the element stride of `axis`, or one record where the axis has a single entry (its stride then addresses nothing)"""
+    return int(strides[axis]) if shape[axis] > 1 else int(record)
+
+
+def _trace_struct(P, ptr, def_, eva, def_strides, eva_strides):
+    """pe_pathfinder_trace over def (N, T, 4, P) and eva (N, T, 4) views whose records are contiguous; strides in elements"""
+    N, T = def_.shape[0], def_.shape[1]
+    assert tuple(def_.shape) == (N, T, 4, P) and tuple(eva.shape) == (N, T, 4), "trace shapes"
+    assert (P == 1 or def_strides[3] == 1) and def_strides[2] == P and eva_strides[2] == 1, "trace records must be contiguous"
+    tr = PePathfinderTrace()
+    tr.def_, tr.eva, tr.T = ptr(def_), ptr(eva), T
+    tr.def_env_stride, tr.def_tick_stride = _stride(def_.shape, def_strides, 0, 4 * P * T), _stride(def_.shape, def_strides, 1, 4 * P)
+    tr.eva_env_stride, tr.eva_tick_stride = _stride(eva.shape, eva_strides, 0, 4 * T), _stride(eva.shape, eva_strides, 1, 4)
+    return tr
+
+
+def record_state_host(pe_cfg, defs, eva, def_row, eva_row):
+    """pe_env_record_state_host: defs (N, 4, P) and eva (N, 4) f64 copied into the rows def_row (N, 4, P) / eva_row (N, 4), float64 views
+    (trace[:, t]) whose records are contiguous; the environment strides are taken from the views."""
+    L = load_library()
+    c = pe_cfg
+    d = np.ascontiguousarray(defs, np.float64).reshape(-1, 4, c.P)
+    N = d.shape[0]
+    e = np.ascontiguousarray(eva, np.float64).reshape(N, 4)
+    assert def_row.dtype == np.float64 and def_row.shape == (N, 4, c.P) and def_row.strides[1:] == (8 * c.P, 8) and def_row.strides[0] % 8 == 0
+    assert eva_row.dtype == np.float64 and eva_row.shape == (N, 4) and eva_row.strides[1] == 8 and eva_row.strides[0] % 8 == 0
+    _check(L.pe_env_record_state_host(C.byref(c), N, _np(d), _np(e), _np(def_row), _stride(def_row.shape, [v // 8 for v in def_row.strides], 0, 4 * c.P),
+                                      _np(eva_row), _stride(eva_row.shape, [v // 8 for v in eva_row.strides], 0, 4)), "pe_env_record_state_host")
+
+
+def pathfinder_label_episode_host(pe_cfg, grid, trace_def, trace_eva, a_star, builds=None, lead=None, sep_range=None, clearance=None, diag=False):
+    """pe_pathfinder_label_episode_host: grid (N, W*H) u8; trace_def (N, T, 4, P) / trace_eva (N, T, 4) f64 and a_star (N, T, P) f32 arrays
+    or views with contiguous records, the strides are taken from the views; builds (N,) i32 or None.  Returns a_star, with diag=True also
+    the last tick's dict of field / kstar / blocked."""
+    L = load_library()
+    c = pe_cfg
+    g = np.ascontiguousarray(grid, np.uint8).reshape(-1, c.W * c.H)
+    N = g.shape[0]
+    assert trace_def.dtype == np.float64 and trace_eva.dtype == np.float64 and trace_def.shape[0] == N
+    assert all(v % 8 == 0 for v in trace_def.strides + trace_eva.strides)
+    tr = _trace_struct(c.P, _np, trace_def, trace_eva, [v // 8 for v in trace_def.strides], [v // 8 for v in trace_eva.strides])
+    assert a_star.dtype == np.float32 and a_star.shape == (N, tr.T, c.P) and a_star.strides[2] == 4 and all(v % 4 == 0 for v in a_star.strides)
+    if builds is not None:
+        assert builds.dtype == np.int32 and builds.shape == (N,) and builds.flags.c_contiguous
+    prm = pathfinder_params(c, lead, sep_range, clearance)
+    dg, out = PePathfinderDiag(), None
+    if diag:
+        out = dict(field=np.zeros((N, c.W * c.H), np.int32), kstar=np.zeros((N, c.P), np.int32), blocked=np.zeros((N, c.P), np.uint16))
+        dg.field, dg.kstar, dg.blocked = _np(out["field"]), _np(out["kstar"]), _np(out["blocked"])
+    a_str = [v // 4 for v in a_star.strides]
+    _check(L.pe_pathfinder_label_episode_host(C.byref(c), N, _np(g), C.byref(prm), C.byref(tr), _np(a_star), _stride(a_star.shape, a_str, 0, tr.T * c.P),
+                                              _stride(a_star.shape, a_str, 1, c.P), _np(builds) if builds is not None else None,
+                                              C.byref(dg) if diag else None), "pe_pathfinder_label_episode_host")
+    return (a_star, out) if diag else a_star
+
+
 FORM_STEP, FORM_OBS, FORM_EVA, FORM_REPLAN = 1, 2, 4, 8
 # the launch form of every entry point (pe_env_diag.h); evader_step and tick also exist with FORM_REPLAN
 FORMS = dict(observe=FORM_OBS, step=FORM_STEP, step_observe=FORM_STEP | FORM_OBS, evader_step=FORM_EVA, tick=FORM_STEP | FORM_OBS | FORM_EVA,
@@ -169,7 +232,8 @@ def launch_plan(pe_cfg, form):
 
 EXPORTS = ("pe_config_check", "pe_tick_lds_bytes", "pe_env_load", "pe_env_observe", "pe_evader_step", "pe_env_step",
            "pe_env_demon", "pe_env_tick", "pe_env_step_observe", "pe_astar_batch", "pe_pursuer_pathfinder", "pe_pursuer_pathfinder_host",
-           "pe_pursuer_pathfinder_teach", "pe_pursuer_pathfinder_teach_host", "pe_error_string")
+           "pe_pursuer_pathfinder_teach", "pe_pursuer_pathfinder_teach_host", "pe_env_record_state", "pe_env_record_state_host",
+           "pe_pathfinder_label_episode", "pe_pathfinder_label_episode_host", "pe_error_string")
 
 _lib = None
 
@@ -218,6 +282,10 @@ def load_library():
         L.pe_pursuer_pathfinder_host.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.pe_pursuer_pathfinder_teach.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.pe_pursuer_pathfinder_teach_host.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.pe_env_record_state.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64, vp]
+        L.pe_env_record_state_host.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int64, vp, C.c_int64]
+        L.pe_pathfinder_label_episode.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp]
+        L.pe_pathfinder_label_episode_host.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
         L.pe_error_string.argtypes = [C.c_int]
         L.pe_error_string.restype = C.c_char_p
         _lib = L
@@ -553,6 +621,48 @@ class BatchedEnv:
         _check(self.L.pe_pursuer_pathfinder_teach(C.byref(c), C.byref(self.st), C.byref(prm), C.byref(cache.struct) if cache is not None else None,
                                                   C.byref(lb), _ptr(out), C.byref(dg) if diag else None, _stream()), "pe_pursuer_pathfinder_teach")
         return (out, diag) if diag else out
+
+    def record_state(self, def_row, eva_row):
+        """One tick's row of an episode trace (include/pe_env.h pe_env_record_state): the pursuers' and the evader's records as the next
+        step will read them, copied into def_row (N, 4, P) / eva_row (N, 4) float64 -- views trace[:, t] of (N, T, 4, P) / (N, T, 4)
+        tensors, the environment strides are taken from the views.  One small launch on the current stream, after the evader step that
+        may still run on the side stream (the evader's record is written there)."""
+        self._join()
+        c, N = self.c, self.N
+        assert def_row.dtype == torch.float64 and def_row.shape == (N, 4, c.P) and def_row[0].is_contiguous()
+        assert eva_row.dtype == torch.float64 and eva_row.shape == (N, 4) and eva_row[0].is_contiguous()
+        _check(self.L.pe_env_record_state(C.byref(c), C.byref(self.st), _ptr(def_row), _stride(def_row.shape, def_row.stride(), 0, 4 * c.P),
+                                          _ptr(eva_row), _stride(eva_row.shape, eva_row.stride(), 0, 4), _stream()), "pe_env_record_state")
+
+    def pathfinder_label_episode(self, trace_def, trace_eva, a_star, builds=None, lead=None, sep_range=None, clearance=None, diag=False):
+        """The pathfinder's labels for a whole recorded episode in one launch (include/pe_env.h pe_pathfinder_label_episode, DESIGN.md
+        section 7p): trace_def (N, T, 4, P) / trace_eva (N, T, 4) float64 as `record_state` filled them, a_star (N, T, P) float32 -- a
+        tensor or a view such as buf[rows] whose records are contiguous, the strides are taken from the views; builds (N,) int32 or None:
+        the distance fields each environment built.  The grid must still be the episode's (label before the next reset).  diag=True (or
+        a dict of tensors to fill) also returns the LAST tick's field / kstar / blocked like `pathfinder`."""
+        self._join()
+        c, N = self.c, self.N
+        assert trace_def.dtype == torch.float64 and trace_eva.dtype == torch.float64 and trace_def.shape[0] == N
+        tr = _trace_struct(c.P, _ptr, trace_def, trace_eva, trace_def.stride(), trace_eva.stride())
+        assert a_star.dtype == torch.float32 and a_star.shape == (N, tr.T, c.P) and (c.P == 1 or a_star.stride(2) == 1)
+        if builds is not None:
+            assert builds.dtype == torch.int32 and builds.shape == (N,) and builds.is_contiguous()
+        prm = pathfinder_params(c, lead, sep_range, clearance)
+        dg = PePathfinderDiag()
+        if diag:
+            if not isinstance(diag, dict):
+                diag = dict(field=torch.empty((N, c.W * c.H), dtype=torch.int32, device=self.device),
+                            kstar=torch.empty((N, c.P), dtype=torch.int32, device=self.device),
+                            blocked=torch.empty((N, c.P), dtype=torch.int16, device=self.device))
+            for k, dt in (("field", torch.int32), ("kstar", torch.int32), ("blocked", torch.int16)):
+                t = diag.get(k)
+                if t is not None:
+                    assert t.dtype == dt and t.is_contiguous(), k
+                    setattr(dg, k, t.data_ptr())
+        _check(self.L.pe_pathfinder_label_episode(C.byref(c), C.byref(self.st), C.byref(prm), C.byref(tr), _ptr(a_star),
+                                                  _stride(a_star.shape, a_star.stride(), 0, tr.T * c.P), _stride(a_star.shape, a_star.stride(), 1, c.P),
+                                                  _ptr(builds), C.byref(dg) if diag else None, _stream()), "pe_pathfinder_label_episode")
+        return (a_star, diag) if diag else a_star
 
     def _actions(self, actions):
         if actions.dtype != torch.int32:

@@ -187,6 +187,15 @@ class Pursuit_Env:
         The caller clears the cache after `reset`."""
         return self.sim.pathfinder_teach(**kw)
 
+    def record_state(self, def_row, eva_row):
+        """one tick's row of an episode trace: the records the next step will read (BatchedEnv.record_state, one small launch)"""
+        self.sim.record_state(def_row, eva_row)
+
+    def pathfinder_label_episode(self, trace_def, trace_eva, a_star, **kw):
+        """the pathfinder's labels for a whole recorded episode in one launch (csrc/pe_env.hip
+        k_pathfinder_label_episode); the arguments are BatchedEnv.pathfinder_label_episode's.  Call it before the next `reset`."""
+        return self.sim.pathfinder_label_episode(trace_def, trace_eva, a_star, **kw)
+
     def get_done(self):
         return self.time_step >= self.max_steps
 

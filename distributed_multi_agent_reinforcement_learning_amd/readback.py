@@ -13,6 +13,15 @@ class BcSums:
         self.allreduce = None      # the trainer's allreduce_sum_: the two sums over ranks, in place
 
 
+class KickSums:
+    """the device side of the imitation term of teacher-regularised PPO (algo.bc_coef, algo.pathfinder_bc_coef): the three sums the fused
+    loss launches of one train(kick=...) call add to"""
+
+    def __init__(self, device):
+        self.sums = torch.zeros(ops.KICK_SUMS, dtype=torch.float64, device=device)
+        self.allreduce = None      # the trainer's allreduce_sum_: the three sums over ranks, in place
+
+
 def read_back(*groups):
     """groups: each a tuple of scalars (Python numbers, 0-dim tensors of any dtype), a part (`.sums`, an f64 device vector, and
     `.allreduce`, the trainer's in-place sum over ranks or None) or None (a feature that is off) -> one list of Python floats per

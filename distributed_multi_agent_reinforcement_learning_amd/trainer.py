@@ -21,7 +21,7 @@ from .imitation import check_entry as check_imitation_entry, phase_step
 from .kickstart import check_entry as check_kickstart_entry
 from .minibatch_steps import check_entry as check_minibatch_steps_entry
 from .pursuit_env import Pursuit_Env
-from .pursuit_imitation import check_entry as check_pursuit_imitation_entry
+from .pursuit_imitation import check_coef_entry as check_pursuit_kickstart_entry, check_entry as check_pursuit_imitation_entry
 from .obs_norm import check_entry as check_obs_norm_entry
 from .value_norm import check_entry as check_value_norm_entry
 
@@ -375,10 +375,11 @@ class Trainer:
         self.agent.sample_rank = self.rank  # disjoint action-sampling streams per rank (mappo.MAPPO.sample_rank)
         self.bucket = GradBucket(self.agent.ac_parameters)   # .grad of every parameter lives in one flat tensor
         self.agent.grad_bucket = self.bucket
-        for part in (self.agent.diag, self.agent.bc):
+        for part in (self.agent.diag, self.agent.bc, self.agent.kick_sums):
             if part is not None:   # algo.update_diagnostics: the eight sums / algo.pathfinder_bc_iterations: the two sums of the imitation
-                part.allreduce = allreduce_sum_   # metric over ranks; no group, no collective
+                part.allreduce = allreduce_sum_   # metric / algo.pathfinder_bc_coef: its three sums over ranks; no group, no collective
         self.last_imitation = None   # the log entries of the last iteration when it was an imitation iteration
+        self.last_kick = None        # ... when it was a PPO iteration with lambda_j > 0 (algo.pathfinder_bc_coef)
         broadcast_weights_([self.agent.actor, self.agent.critic])
         self.total_steps = 0
         self.iteration = 0
@@ -388,13 +389,18 @@ class Trainer:
         """rollout + `epochs` updates; returns (env_steps_this_iteration_all_ranks, exp_reward).
         algo.pathfinder_bc_iterations K: iterations 0 .. K - 1 imitate the path-finding pursuers (explore_expert, train(imitation=True)
         at the constant rate pathfinder_bc_lr); iteration K starts PPO from cleared Adam moments.  The phase
-        follows from `iteration` alone, so a resumed run continues in it."""
+        follows from `iteration` alone, so a resumed run continues in it.
+        algo.pathfinder_bc_coef: PPO iteration j = iteration - K has lambda_j = coef_at(j); while it is > 0 the rollout is explore_labelled
+        (on-policy, every tick labelled) and the update train(kick=lambda_j)."""
         cfg, agent = self.cfg, self.agent
         imitating, beta = phase_step(agent, agent.pathfinder_bc, self.iteration, self.total_steps)
+        lam = 0.0 if imitating else agent.pathfinder_kick.coef_at(self.iteration - agent.pathfinder_bc.iterations)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
         if imitating:
             exp_r, buffer, steps = agent.explore_expert(self.env, int(cfg.algo.sample_epi_num), beta)
+        elif lam > 0.0:
+            exp_r, buffer, steps = agent.explore_labelled(self.env, int(cfg.algo.sample_epi_num))
         else:
             exp_r, buffer, steps = agent.explore_env(self.env, int(cfg.algo.sample_epi_num))
         ev[1].record()
@@ -402,7 +408,8 @@ class Trainer:
         self.total_steps += steps * self.world
         for _ in range(int(cfg.algo.epochs)):
             with torch.enable_grad():
-                obj_c, obj_a, _, _ = agent.train(buffer, self.total_steps, return_grads=False, **({"imitation": True} if imitating else {}))
+                obj_c, obj_a, _, _ = agent.train(buffer, self.total_steps, return_grads=False,
+                                                 **({"imitation": True} if imitating else {"kick": lam} if lam > 0.0 else {}))
             allreduce_sum_(self.bucket.flat)      # gradient SUM over ranks, in place in the bucket the optimiser reads
             agent.ac_optimizer.step()
             if cfg.algo.use_lr_decay and not imitating:
@@ -413,6 +420,11 @@ class Trainer:
         if imitating:   # of the last update of the iteration, like last_log; the hit rate is this rank's rollout's
             self.last_imitation = dict(phase="imitation", bc_beta=beta, bc_loss=self.last_log[1], bc_accuracy=agent.bc_accuracy(),
                                        critic_loss=self.last_log[0], pathfinder_hit_rate=agent.last_hit_rate)
+        self.last_kick = None
+        if lam > 0.0:   # of the last update of the iteration: lambda_j, the unweighted imitation term and its metric; this rank's build rate
+            hits, live, nll = agent.last_kick
+            self.last_kick = dict(bc_coef=lam, bc_aux_loss=nll / live if live else float("nan"),
+                                  bc_accuracy=hits / live if live else float("nan"), pathfinder_build_rate=agent.last_build_rate)
         self.iteration += 1
         self.last_events = ev  # (rollout incl. host reset, update) timings: read after a synchronize
         return steps * self.world, exp_r
@@ -432,6 +444,8 @@ class Trainer:
                       num_envs=self.num_envs, world=self.world, rank=self.rank)
         if agent.pathfinder_bc.on:   # algo.pathfinder_bc_iterations: the phase of an iteration follows from it and `iteration`; off: no entry
             bundle["pathfinder_bc_iterations"] = agent.pathfinder_bc.iterations
+        if agent.pathfinder_kick.on:   # algo.pathfinder_bc_coef: lambda of an iteration follows from the three values; off: no entry
+            bundle["pathfinder_bc_coef"] = agent.pathfinder_kick.entry()
         torch.save(bundle, path)
         if init is not None:
             env._prefetch = (_Done(), {"init": init})
@@ -442,6 +456,7 @@ class Trainer:
             raise ValueError("resume bundle was written for another num_envs / world size")
         env, agent = self.env, self.agent
         check_pursuit_imitation_entry(agent, b.get("pathfinder_bc_iterations"), f"resume bundle {path}")
+        check_pursuit_kickstart_entry(agent, b.get("pathfinder_bc_coef"), f"resume bundle {path}")
         if getattr(env, "_dev_prefetch", None) is not None:    # a device reset issued ahead belongs to the run being replaced: let it finish, drop it
             torch.cuda.current_stream().wait_stream(env.sim._side)
             env._dev_prefetch = env._pre_reset = None
@@ -479,7 +494,8 @@ def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval
     bundle from before the first one (main --save-resume / --resume)."""
     from . import pursuit_baseline, pursuit_imitation, ray_shim
     baseline_kind = pursuit_baseline.eval_baseline_options(cfg)   # validated before anything is built
-    if pursuit_imitation.pursuit_imitation_options(cfg).on:        # likewise: algo.pathfinder_bc_*, runtime.pathfinder_*
+    teacher = pursuit_imitation.pursuit_imitation_options(cfg).on      # likewise: algo.pathfinder_bc_*, runtime.pathfinder_*
+    if pursuit_imitation.pursuit_kickstart_options(cfg).on or teacher:   # (algo.pathfinder_bc_coef*, runtime.pathfinder_labeller)
         pursuit_baseline.pathfinder_options(cfg)
     tr = Trainer(cfg)
     tr.baseline = None
@@ -516,6 +532,9 @@ def train_agent_multiprocessing(cfg, max_iterations=None, num_eval_envs=16, eval
             print(f"iteration {tr.iteration}: {steps} env-steps in {time.time() - t0:.2f}s")
             if tr.last_imitation is not None:   # algo.pathfinder_bc_iterations: one line per imitation iteration
                 print(json.dumps(dict(iteration=tr.iteration, **tr.last_imitation)), flush=True)
+            elif tr.last_kick is not None:    # algo.pathfinder_bc_coef: one line per PPO iteration with lambda_j > 0
+                more = {} if tr.agent.diag is None else dict(critic_loss=tr.last_log[0], actor_loss=tr.last_log[1], **tr.agent.last_update_diag)
+                print(json.dumps(dict(iteration=tr.iteration, **tr.last_kick, **more)), flush=True)
             elif tr.agent.diag is not None:   # algo.update_diagnostics: the last update of the iteration, like last_log
                 print(json.dumps(dict(iteration=tr.iteration, critic_loss=tr.last_log[0], actor_loss=tr.last_log[1], **tr.agent.last_update_diag)),
                       flush=True)

@@ -258,6 +258,40 @@ int pe_pursuer_pathfinder_teach_host(const pe_config *cfg, int32_t N, const uint
                                      const pe_pathfinder_params *prm, const pe_pathfinder_cache *cache, const pe_pathfinder_label *label,
                                      int32_t *actions /* [N][P] or NULL */, const pe_pathfinder_diag *diag);
 
+/* Labelling a whole on-policy episode after it ran.  While no environment follows the teacher, its labels
+ * influence nothing before the update and the grid is static within an episode, so the rollout only records the state each step read
+ * (pe_env_record_state, one small launch a tick) and ONE launch labels all T ticks afterwards: per environment the grid, the distance
+ * field and the neighbour words stay in LDS, and the field is rebuilt only on the ticks whose evader cell differs from the cell the
+ * resident field was built for.  The labels are pe_pursuer_pathfinder's on the same state, bit for bit.
+ *
+ * pe_env_record_state: def_out[n * def_env_stride + j] = st->def[n][j] (j < 4P) and eva_out[n * eva_env_stride + j] = st->eva[n][j]
+ * (j < 4) for every environment: one tick's row trace[:, t] of the two tensors below.  Strides in elements between environments.
+ * Refused without a write: a NULL pointer (PE_ERR_NULL), def_env_stride < 4P or eva_env_stride < 4 (PE_ERR_BAD_CONFIG). */
+int pe_env_record_state(const pe_config *cfg, const pe_state *st, double *def_out, int64_t def_env_stride, double *eva_out, int64_t eva_env_stride,
+                        void *stream);
+/* The host side of the same copy, on HOST arrays (def [N][4][P], eva [N][4]). */
+int pe_env_record_state_host(const pe_config *cfg, int32_t N, const double *def, const double *eva, double *def_out, int64_t def_env_stride,
+                             double *eva_out, int64_t eva_env_stride);
+typedef struct pe_pathfinder_trace {   /* DEVICE pointers; strides in elements */
+    const double *def;  int64_t def_env_stride, def_tick_stride;   /* [N][T][4][P]: record (n, t) at n * env_stride + t * tick_stride */
+    const double *eva;  int64_t eva_env_stride, eva_tick_stride;   /* [N][T][4] */
+    int32_t T, pad0;                                               /* ticks recorded, >= 1 */
+} pe_pathfinder_trace;
+/* a_star[n * a_star_env_stride + t * a_star_tick_stride + i] = (float)action of pursuer i at tick t; builds ([N] or NULL) = distance
+ * fields environment n built in the episode (1 + the ticks whose evader cell differs from the tick before, while no build hits the
+ * sweep bound); diag (or any member) may be NULL, its outputs are the LAST tick's.  st supplies N, grid and meta (PE_STATUS_PATH_CAP
+ * as in pe_pursuer_pathfinder; after a capped build nothing is resident, so the next tick builds again).
+ * One launch of one workgroup per environment, no atomics, no host read, capturable in a graph after one launch outside a capture.
+ * Refused before any launch and without a write: whatever pe_pursuer_pathfinder refuses; T < 1, an a_star stride < P, a def stride
+ * < 4P, an eva stride < 4 (PE_ERR_BAD_CONFIG); a NULL trace, trace pointer, a_star or grid (PE_ERR_NULL). */
+int pe_pathfinder_label_episode(const pe_config *cfg, const pe_state *st, const pe_pathfinder_params *prm, const pe_pathfinder_trace *trace,
+                                float *a_star, int64_t a_star_env_stride, int64_t a_star_tick_stride, int32_t *builds /* [N] or NULL */,
+                                const pe_pathfinder_diag *diag, void *stream);
+/* The host twin: HOST arrays; grid [N][W*H]; the trace members, a_star, builds and diag are HOST pointers. */
+int pe_pathfinder_label_episode_host(const pe_config *cfg, int32_t N, const uint8_t *grid, const pe_pathfinder_params *prm,
+                                     const pe_pathfinder_trace *trace, float *a_star, int64_t a_star_env_stride, int64_t a_star_tick_stride,
+                                     int32_t *builds /* [N] or NULL */, const pe_pathfinder_diag *diag);
+
 const char *pe_error_string(int code);
 
 #ifdef __cplusplus
