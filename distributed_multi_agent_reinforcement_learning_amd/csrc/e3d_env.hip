@@ -270,11 +270,19 @@ __global__ void k_aos_to_soa7(int N, int A, const double *aos, double *soa) {
     soa[i] = aos[(size_t)n * 7 * A + a * 7 + k];
 }
 
+// the lane layout of the tick and of the policy kernels: PT (group of lanes per environment) and the workgroups covering N environments
+int e3d_lanes(const e3d_config *c, int N, int *blocks) {
+    const int pt = c->P <= 8 ? 8 : (c->P <= 16 ? 16 : (c->P <= 32 ? 32 : 64));
+    const int envs_per_block = (WAVE / pt) * WPB;
+    *blocks = (N + envs_per_block - 1) / envs_per_block;
+    return pt;
+}
+
 template <bool TICK>
 int launch(const e3d_config *c, const e3d_state *st, const double *actions, const double *e_cmd, float *reward, uint8_t *active, uint8_t *done,
            const e3d_obs_out &o, hipStream_t s) {
-    const int pt = c->P <= 8 ? 8 : (c->P <= 16 ? 16 : (c->P <= 32 ? 32 : 64));
-    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    int blocks;
+    const int pt = e3d_lanes(c, st->N, &blocks);
     const E3dThr th{sq_threshold(c->kill_radius), sq_threshold(c->p_comm_range), sq_threshold(c->p_sen_range)};
 #define E3D_GO(PT) hipLaunchKernelGGL((k_e3d<PT, TICK>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, actions, e_cmd, reward, active, done, o, th)
     if (pt == 8) E3D_GO(8); else if (pt == 16) E3D_GO(16); else if (pt == 32) E3D_GO(32); else E3D_GO(64);
@@ -581,13 +589,24 @@ __global__ __launch_bounds__(WAVE * WPB) void k_e3d_shaping_begin(const e3d_conf
     phi[(size_t)env * P + a] = e3d_potential(st, env, P, a, p_on, e_on, coef);
 }
 
-template <bool SCALED, bool SHAPED, bool TEAM = false>
-int e3d_record_launch(const e3d_config *c, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io &io,
-                      const e3d_policy_acc &acc, double *rs, double gamma, double *phi, double coef, hipStream_t s, double alpha = 0.0) {
-    const int pt = c->P <= 8 ? 8 : (c->P <= 16 ? 16 : (c->P <= 32 ? 32 : 64));
-    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+// e3d_policy_record (include/policy_record.h): the checks, then one launch in the tick's lane layout; an option that is off passes the
+// kernel nullptr / 0.0 whatever the record holds
+template <bool SCALED, bool SHAPED, bool TEAM>
+int e3d_record_launch(const e3d_config *c, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
+                      const e3d_policy_acc *acc, const policy_record_opts &o, void *stream) {
+    if (!c || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value)) return E3D_ERR_NULL;
+    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return E3D_ERR_NULL;
+    const int rc = e3d_config_check(c);
+    if (rc) return rc;
+    if (TEAM && !team::coef_ok(o.alpha)) return E3D_ERR_BAD_CONFIG;
+    if (st->N < 1) return 0;
+    int blocks;
+    const int pt = e3d_lanes(c, st->N, &blocks);
     const double kill = sq_threshold(c->kill_radius);
-#define E3D_REC(PT) hipLaunchKernelGGL((k_e3d_policy_record<PT, SCALED, SHAPED, TEAM>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, reward, done, io, acc, kill, rs, gamma, phi, coef, alpha)
+    double *rs = SCALED ? o.rs : nullptr, *phi = SHAPED ? o.phi : nullptr;
+    const double gamma = SCALED || SHAPED ? o.gamma : 0.0, coef = SHAPED ? o.coef : 0.0, alpha = TEAM ? o.alpha : 0.0;
+    hipStream_t s = (hipStream_t)stream;
+#define E3D_REC(PT) hipLaunchKernelGGL((k_e3d_policy_record<PT, SCALED, SHAPED, TEAM>), dim3(blocks), dim3(WAVE * WPB), 0, s, *c, *st, reward, done, *io, *acc, kill, rs, gamma, phi, coef, alpha)
     if (pt == 8) E3D_REC(8); else if (pt == 16) E3D_REC(16); else if (pt == 32) E3D_REC(32); else E3D_REC(64);
 #undef E3D_REC
     return (int)hipGetLastError();
@@ -940,40 +959,20 @@ int e3d_obs_norm_update(double *norm_state, const double *sums, double *slots, i
 }
 
 int e3d_policy_record(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
-                      const e3d_policy_acc *acc, double *rs, double gamma, void *stream) {
-    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value)) return E3D_ERR_NULL;
-    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return E3D_ERR_NULL;
-    const int rc = e3d_config_check(cfg);
-    if (rc) return rc;
-    if (st->N < 1) return 0;
-    if (rs) return e3d_record_launch<true, false>(cfg, st, reward, done, *io, *acc, rs, gamma, nullptr, 0.0, (hipStream_t)stream);
-    return e3d_record_launch<false, false>(cfg, st, reward, done, *io, *acc, nullptr, 0.0, nullptr, 0.0, (hipStream_t)stream);
-}
-
-int e3d_policy_record_shaped(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
-                             const e3d_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream) {
-    if (!cfg || !st || !reward || !done || !io || !acc || !phi || !io->live || (io->v && !io->value)) return E3D_ERR_NULL;
-    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return E3D_ERR_NULL;
-    const int rc = e3d_config_check(cfg);
-    if (rc) return rc;
-    if (st->N < 1) return 0;
-    if (rs) return e3d_record_launch<true, true>(cfg, st, reward, done, *io, *acc, rs, gamma, phi, coef, (hipStream_t)stream);
-    return e3d_record_launch<false, true>(cfg, st, reward, done, *io, *acc, nullptr, gamma, phi, coef, (hipStream_t)stream);
-}
-
-int e3d_policy_record_team(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
-                           const e3d_policy_acc *acc, double alpha, double *phi, double coef, double gamma, double *rs, void *stream) {
-    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value)) return E3D_ERR_NULL;
-    if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return E3D_ERR_NULL;
-    const int rc = e3d_config_check(cfg);
-    if (rc) return rc;
-    if (!team::coef_ok(alpha)) return E3D_ERR_BAD_CONFIG;
-    if (st->N < 1) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (phi && rs) return e3d_record_launch<true, true, true>(cfg, st, reward, done, *io, *acc, rs, gamma, phi, coef, s, alpha);
-    if (phi) return e3d_record_launch<false, true, true>(cfg, st, reward, done, *io, *acc, nullptr, gamma, phi, coef, s, alpha);
-    if (rs) return e3d_record_launch<true, false, true>(cfg, st, reward, done, *io, *acc, rs, gamma, nullptr, 0.0, s, alpha);
-    return e3d_record_launch<false, false, true>(cfg, st, reward, done, *io, *acc, nullptr, 0.0, nullptr, 0.0, s, alpha);
+                      const e3d_policy_acc *acc, const policy_record_opts *opts, void *stream) {
+    const policy_record_opts off = {};
+    const policy_record_opts &o = opts ? *opts : off;
+    // <SCALED, SHAPED, TEAM>; the cases stand in the order in which the code object has always listed these kernels
+    switch ((o.rs ? 1 : 0) | (o.phi ? 2 : 0) | (o.team ? 4 : 0)) {
+        case 1: return e3d_record_launch<true, false, false>(cfg, st, reward, done, io, acc, o, stream);
+        case 0: return e3d_record_launch<false, false, false>(cfg, st, reward, done, io, acc, o, stream);
+        case 3: return e3d_record_launch<true, true, false>(cfg, st, reward, done, io, acc, o, stream);
+        case 2: return e3d_record_launch<false, true, false>(cfg, st, reward, done, io, acc, o, stream);
+        case 7: return e3d_record_launch<true, true, true>(cfg, st, reward, done, io, acc, o, stream);
+        case 6: return e3d_record_launch<false, true, true>(cfg, st, reward, done, io, acc, o, stream);
+        case 5: return e3d_record_launch<true, false, true>(cfg, st, reward, done, io, acc, o, stream);
+        default: return e3d_record_launch<false, false, true>(cfg, st, reward, done, io, acc, o, stream);
+    }
 }
 
 int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, double coef, void *stream) {
@@ -981,8 +980,8 @@ int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, d
     const int rc = e3d_config_check(cfg);
     if (rc) return rc;
     if (st->N < 1) return 0;
-    const int pt = cfg->P <= 8 ? 8 : (cfg->P <= 16 ? 16 : (cfg->P <= 32 ? 32 : 64));
-    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    int blocks;
+    const int pt = e3d_lanes(cfg, st->N, &blocks);
     hipStream_t s = (hipStream_t)stream;
 #define E3D_SB(PT) hipLaunchKernelGGL((k_e3d_shaping_begin<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, phi, coef)
     if (pt == 8) E3D_SB(8); else if (pt == 16) E3D_SB(16); else if (pt == 32) E3D_SB(32); else E3D_SB(64);
@@ -997,8 +996,8 @@ int e3d_pursuer_guidance(const e3d_config *cfg, const e3d_state *st, const e3d_g
     if (!guide::param_ok(params->lead) || !guide::param_ok(params->sep_range) || !guide::param_ok(params->sep_gain)) return E3D_ERR_BAD_CONFIG;
     if (st->N < 1) return 0;
     if (!st->p || !st->e) return E3D_ERR_NULL;
-    const int pt = cfg->P <= 8 ? 8 : (cfg->P <= 16 ? 16 : (cfg->P <= 32 ? 32 : 64));
-    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    int blocks;
+    const int pt = e3d_lanes(cfg, st->N, &blocks);
     hipStream_t s = (hipStream_t)stream;
 #define E3D_GD(PT) hipLaunchKernelGGL((k_e3d_guidance<PT>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, *params, actions)
     if (pt == 8) E3D_GD(8); else if (pt == 16) E3D_GD(16); else if (pt == 32) E3D_GD(32); else E3D_GD(64);
@@ -1015,8 +1014,8 @@ int e3d_pursuit_features(const e3d_config *cfg, const e3d_state *st, const e3d_o
     if (((uintptr_t)actor_feat | (uintptr_t)critic_feat) % 16) return E3D_ERR_BAD_CONFIG;   // the rows are stored as 16-byte lanes
     if (st->N < 1) return 0;
     if (!st->p || !st->e || !st->target || !st->time_step) return E3D_ERR_NULL;
-    const int pt = cfg->P <= 8 ? 8 : (cfg->P <= 16 ? 16 : (cfg->P <= 32 ? 32 : 64));
-    const int envs_per_block = (WAVE / pt) * WPB, blocks = (st->N + envs_per_block - 1) / envs_per_block;
+    int blocks;
+    const int pt = e3d_lanes(cfg, st->N, &blocks);
     hipStream_t s = (hipStream_t)stream;
     const int sensed = evader_obs == E3D_EVADER_OBS_SENSED;
 #define E3D_PF(PT, TEAM) hipLaunchKernelGGL((k_e3d_pursuit<PT, TEAM>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, *out, sensed, actor_feat, critic_feat)

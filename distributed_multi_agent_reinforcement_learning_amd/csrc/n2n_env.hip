@@ -503,19 +503,22 @@ __global__ __launch_bounds__(WAVE * WPB) void k_n2n_guidance(const n2n_config c,
     if (pv) actions[(size_t)env * P + a] = guide::n2n_command(pact != 0.0 && any, gx, gy);
 }
 
-// n2n_policy_record / n2n_policy_record_scaled / n2n_policy_record_shaped / n2n_policy_record_team: one launch, the tick's lane layout
-template <bool SCALED, bool SHAPED, bool TEAM = false>
+// n2n_policy_record (include/policy_record.h): the checks, then one launch in the tick's lane layout; an option that is off passes the
+// kernel nullptr / 0.0 whatever the record holds
+template <bool SCALED, bool SHAPED, bool TEAM>
 int n2n_record_launch(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                      const n2n_policy_acc *acc, double *rs, double gamma, double *phi, double coef, void *stream, double alpha = 0.0) {
-    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value) || (SCALED && !rs) || (SHAPED && !phi)) return N2N_ERR_NULL;
+                      const n2n_policy_acc *acc, const policy_record_opts &o, void *stream) {
+    if (!cfg || !st || !reward || !done || !io || !acc || !io->live || (io->v && !io->value)) return N2N_ERR_NULL;
     if (!acc->done_before || !acc->ended || !acc->captured || !acc->ret || !acc->length) return N2N_ERR_NULL;
     const int rc = n2n_config_check(cfg);
     if (rc) return rc;
-    if (TEAM && !team::coef_ok(alpha)) return N2N_ERR_BAD_CONFIG;
+    if (TEAM && !team::coef_ok(o.alpha)) return N2N_ERR_BAD_CONFIG;
     if (st->N < 1) return 0;
     int blocks;
     const int pt = n2n_lanes(cfg, st->N, &blocks);
     const double kill = sq_threshold(cfg->kill_radius);
+    double *rs = SCALED ? o.rs : nullptr, *phi = SHAPED ? o.phi : nullptr;
+    const double gamma = SCALED || SHAPED ? o.gamma : 0.0, coef = SHAPED ? o.coef : 0.0, alpha = TEAM ? o.alpha : 0.0;
     hipStream_t s = (hipStream_t)stream;
 #define N2N_REC(PT) hipLaunchKernelGGL((k_n2n_policy_record<PT, SCALED, SHAPED, TEAM>), dim3(blocks), dim3(WAVE * WPB), 0, s, *cfg, *st, reward, done, *io, *acc, kill, rs, gamma, phi, coef, alpha)
     if (pt == 8) N2N_REC(8); else if (pt == 16) N2N_REC(16); else if (pt == 32) N2N_REC(32); else N2N_REC(64);
@@ -607,27 +610,20 @@ int n2n_policy_inputs(const n2n_config *cfg, const n2n_state *st, const uint8_t 
 }
 
 int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                      const n2n_policy_acc *acc, void *stream) {
-    return n2n_record_launch<false, false>(cfg, st, reward, done, io, acc, nullptr, 0.0, nullptr, 0.0, stream);
-}
-
-int n2n_policy_record_scaled(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                             const n2n_policy_acc *acc, double *rs, double gamma, void *stream) {
-    return n2n_record_launch<true, false>(cfg, st, reward, done, io, acc, rs, gamma, nullptr, 0.0, stream);
-}
-
-int n2n_policy_record_shaped(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                             const n2n_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream) {
-    if (rs) return n2n_record_launch<true, true>(cfg, st, reward, done, io, acc, rs, gamma, phi, coef, stream);
-    return n2n_record_launch<false, true>(cfg, st, reward, done, io, acc, nullptr, gamma, phi, coef, stream);
-}
-
-int n2n_policy_record_team(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                           const n2n_policy_acc *acc, double alpha, double *phi, double coef, double gamma, double *rs, void *stream) {
-    if (phi && rs) return n2n_record_launch<true, true, true>(cfg, st, reward, done, io, acc, rs, gamma, phi, coef, stream, alpha);
-    if (phi) return n2n_record_launch<false, true, true>(cfg, st, reward, done, io, acc, nullptr, gamma, phi, coef, stream, alpha);
-    if (rs) return n2n_record_launch<true, false, true>(cfg, st, reward, done, io, acc, rs, gamma, nullptr, 0.0, stream, alpha);
-    return n2n_record_launch<false, false, true>(cfg, st, reward, done, io, acc, nullptr, 0.0, nullptr, 0.0, stream, alpha);
+                      const n2n_policy_acc *acc, const policy_record_opts *opts, void *stream) {
+    const policy_record_opts off = {};
+    const policy_record_opts &o = opts ? *opts : off;
+    // <SCALED, SHAPED, TEAM>; the cases stand in the order in which the code object has always listed these kernels
+    switch ((o.rs ? 1 : 0) | (o.phi ? 2 : 0) | (o.team ? 4 : 0)) {
+        case 0: return n2n_record_launch<false, false, false>(cfg, st, reward, done, io, acc, o, stream);
+        case 1: return n2n_record_launch<true, false, false>(cfg, st, reward, done, io, acc, o, stream);
+        case 3: return n2n_record_launch<true, true, false>(cfg, st, reward, done, io, acc, o, stream);
+        case 2: return n2n_record_launch<false, true, false>(cfg, st, reward, done, io, acc, o, stream);
+        case 7: return n2n_record_launch<true, true, true>(cfg, st, reward, done, io, acc, o, stream);
+        case 6: return n2n_record_launch<false, true, true>(cfg, st, reward, done, io, acc, o, stream);
+        case 5: return n2n_record_launch<true, false, true>(cfg, st, reward, done, io, acc, o, stream);
+        default: return n2n_record_launch<false, false, true>(cfg, st, reward, done, io, acc, o, stream);
+    }
 }
 
 int n2n_shaping_begin(const n2n_config *cfg, const n2n_state *st, double *phi, double coef, void *stream) {

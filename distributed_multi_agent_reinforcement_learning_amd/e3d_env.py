@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import build as _build
+from .policy_record import fill_acc, record_opts, rows
 
 
 class E3dConfig(C.Structure):
@@ -43,15 +44,6 @@ class E3dPolicyAcc(C.Structure):
 
 class E3dRecordIO(C.Structure):
     _fields_ = [(n, t) for k in ("live", "value", "r", "active", "v", "v_next", "live_next") for n, t in ((k, C.c_void_p), (k + "_rs", C.c_int64))]
-
-
-def _rows(t, shape, name):
-    """a float32 (N, ...) device tensor whose environment rows are dense (rows may be strided: buffer[:, t]) -> (pointer, row stride)"""
-    if t is None:
-        return None, 0
-    assert t.dtype == torch.float32 and t.is_cuda and tuple(t.shape) == tuple(shape), (name, tuple(t.shape), tuple(shape))
-    assert t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= t[0].numel()), f"{name}: rows must be dense"
-    return t.data_ptr(), t.stride(0)
 
 
 _lib = None
@@ -86,9 +78,7 @@ def load_library():
         L.e3d_obs_norm_slots.restype = C.c_int64
         L.e3d_obs_norm_reduce.argtypes = [vp, C.c_int64, vp, vp]
         L.e3d_obs_norm_update.argtypes = [vp, vp, vp, C.c_int64, vp]
-        L.e3d_policy_record.argtypes = [vp] * 7 + [C.c_double, vp]
-        L.e3d_policy_record_shaped.argtypes = [vp] * 7 + [C.c_double, C.c_double, vp, vp]
-        L.e3d_policy_record_team.argtypes = [vp] * 6 + [C.c_double, vp, C.c_double, C.c_double, vp, vp]
+        L.e3d_policy_record.argtypes = [vp] * 8
         L.e3d_shaping_begin.argtypes = [vp] * 3 + [C.c_double, vp]
         L.e3d_pursuer_guidance.argtypes = [vp] * 5
         L.e3d_pursuit_features.argtypes = [vp] * 3 + [C.c_int32] + [vp] * 3
@@ -290,7 +280,7 @@ class ParticleEnv:
             assert slots.dtype == torch.float64 and slots.is_contiguous() and slots.shape == (n, 2, 33) and slots.device == self.p.device
             if live is None:
                 raise ValueError("policy_features(slots=...) needs the live mask of the step")
-            live_ptr, live_rs = _rows(live, (N, P), "live")
+            live_ptr, live_rs = rows(live, (N, P), "live")
             slots_ptr = slots.data_ptr()
         _check(self.L.e3d_policy_features_norm(C.byref(self.c), C.byref(self.st), C.byref(self._obs_struct), C.c_void_p(actor_feat.data_ptr()),
                                                C.c_void_p(critic_feat.data_ptr()), C.c_void_p(norm_state.data_ptr()), C.c_double(float(clip)),
@@ -356,51 +346,22 @@ class ParticleEnv:
                       shaping_gamma=None, team_coef=None):
         """after step(): r = reward * live, active = live, v = value * live (row t of the buffer, None skips), v_next (row t + 1 of v_n)
         zeroed where the pursuer is inactive or its episode ended for a reason other than the time limit, live_next = the next step's
-        live mask (may be `live` itself); updates the accumulators of new_accumulators() (e3d_policy_record, include/e3d_env.h).
-        scale_gamma: the discount of the reference's RewardScaling; r is then the scaled reward * live and reward_scale
-        (enable_reward_scaling) advances, in the same launch.  shaping_gamma: the discount of the distance shaping; the reward (what
-        RewardScaling receives, when both are on) gains gamma Phi' - Phi on live rows and shaping_phi (enable_reward_shaping) advances,
-        still in that one launch (e3d_policy_record_shaped).  team_coef: alpha in [0, 1] of the team reward sharing; the reward that
-        enters the row, the shaping and the scaling is (1 - alpha) reward + alpha (sum_p reward * live) on live rows, in the same
-        launch (e3d_policy_record_team); the accumulators keep the raw reward."""
+        live mask (may be `live` itself); updates the accumulators of new_accumulators().  scale_gamma: the discount of the reference's
+        RewardScaling; r is then the scaled reward * live and reward_scale (enable_reward_scaling) advances.  shaping_gamma: the discount
+        of the distance shaping; the reward (what RewardScaling receives, when both are on) gains gamma Phi' - Phi on live rows and
+        shaping_phi (enable_reward_shaping) advances.  team_coef: alpha in [0, 1] of the team reward sharing; the reward that enters the
+        row, the shaping and the scaling is (1 - alpha) reward + alpha (sum_p reward * live) on live rows; the accumulators keep the raw
+        reward.  Whatever is asked for, it is one launch (e3d_policy_record, include/e3d_env.h; the options: include/policy_record.h)."""
         N, P = self.num_envs, self.p_num
         io = E3dRecordIO()
         for k, t in (("live", live), ("value", value), ("r", r), ("active", active), ("v", v), ("v_next", v_next), ("live_next", live_next)):
-            ptr, rs = _rows(t, (N, P), k)
+            ptr, rs = rows(t, (N, P), k)
             setattr(io, k, ptr)
             setattr(io, k + "_rs", rs)
-        a = E3dPolicyAcc()
-        for k, dt in (("done_before", torch.uint8), ("ended", torch.uint8), ("captured", torch.uint8), ("ret", torch.float32), ("length", torch.float32)):
-            t = acc[k]
-            assert t.dtype == dt and t.is_contiguous() and t.shape == (N,) and t.device == self.p.device, k
-            setattr(a, k, t.data_ptr())
-        rs_ptr, gamma = None, 0.0
-        if scale_gamma is not None:
-            rs = self.reward_scale
-            if rs is None:
-                raise RuntimeError("policy_record(scale_gamma=...) needs enable_reward_scaling() on this environment")
-            assert rs.dtype == torch.float64 and rs.is_contiguous() and rs.shape == (N, 1 + 3 * P) and rs.device == self.p.device
-            rs_ptr, gamma = rs.data_ptr(), float(scale_gamma)
-        args = (C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()), C.byref(io), C.byref(a))
-        if shaping_gamma is None:
-            if team_coef is not None:
-                _check(self.L.e3d_policy_record_team(*args, C.c_double(float(team_coef)), None, C.c_double(0.0), C.c_double(gamma),
-                                                     C.c_void_p(rs_ptr), _stream()), "e3d_policy_record_team")
-                return
-            _check(self.L.e3d_policy_record(*args, C.c_void_p(rs_ptr), C.c_double(gamma), _stream()), "e3d_policy_record")
-            return
-        phi = self.shaping_phi
-        if phi is None:
-            raise RuntimeError("policy_record(shaping_gamma=...) needs enable_reward_shaping() on this environment")
-        if scale_gamma is not None and float(scale_gamma) != float(shaping_gamma):
-            raise ValueError("policy_record: scale_gamma and shaping_gamma are one discount (algo.gamma)")
-        assert phi.dtype == torch.float64 and phi.is_contiguous() and phi.shape == (N, P) and phi.device == self.p.device
-        if team_coef is not None:
-            _check(self.L.e3d_policy_record_team(*args, C.c_double(float(team_coef)), C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef),
-                                                 C.c_double(float(shaping_gamma)), C.c_void_p(rs_ptr), _stream()), "e3d_policy_record_team")
-            return
-        _check(self.L.e3d_policy_record_shaped(*args, C.c_void_p(phi.data_ptr()), C.c_double(self.shaping_coef), C.c_double(float(shaping_gamma)),
-                                               C.c_void_p(rs_ptr), _stream()), "e3d_policy_record_shaped")
+        a = fill_acc(E3dPolicyAcc(), acc, N, self.p.device)
+        opts = record_opts(self, scale_gamma, shaping_gamma, team_coef)
+        _check(self.L.e3d_policy_record(C.byref(self.c), C.byref(self.st), C.c_void_p(self.reward_t.data_ptr()), C.c_void_p(self.done_t.data_ptr()),
+                                        C.byref(io), C.byref(a), C.byref(opts) if opts is not None else None, _stream()), "e3d_policy_record")
 
     # ---- scripted pursuers (guidance.py, DESIGN.md section 7e) --------------------------------------------------------------------------
     def set_guidance(self, lead=1.0, sep_range=None, sep_gain=1.0):

@@ -12,6 +12,7 @@
 #ifndef E3D_ENV_H
 #define E3D_ENV_H
 #include <stdint.h>
+#include "policy_record.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -100,7 +101,7 @@ typedef struct e3d_policy_acc {  /* per-environment episode accumulators [N], ze
 typedef struct e3d_record_io {
     const float *live;  int64_t live_rs;    /* [N][P] this step's live mask, required (first step: the active flags after reset) */
     const float *value; int64_t value_rs;   /* [N][P] the critic's value of this step, required with v                           */
-    float *r;      int64_t r_rs;            /* [N][P] reward * live (with rs: the scaled reward * live)                          */
+    float *r;      int64_t r_rs;            /* [N][P] reward * live, or what the options of policy_record.h make of it           */
     float *active; int64_t active_rs;       /* [N][P] live                                                                       */
     float *v;      int64_t v_rs;            /* [N][P] value * live                                                               */
     float *v_next; int64_t v_next_rs;       /* [N][P] set to 0 where the pursuer is inactive after the step or its environment
@@ -110,33 +111,16 @@ typedef struct e3d_record_io {
 } e3d_record_io;
 
 /* After e3d_env_tick: buffer row t, the next live mask and the accumulators from the tick's reward [N][P] and done [N] and the records
- * after it.  rs: NULL, or the RewardScaling state [N][1 + 3P] f64 (n, mean[P], S[P], R[P]; csrc/reward_scale.hpp, semantics as
- * n2n_policy_record_scaled of n2n_env.h) with its discount gamma: the reward row is then the scaled one for environments not done
- * before the step, and rs of the others is left untouched.  One launch, the tick's lane layout. */
+ * after it.  opts: NULL, or the reward options of policy_record.h (RewardScaling, distance shaping, team reward sharing), in the same
+ * launch.  One launch, the tick's lane layout.  Before any launch: a NULL argument (io->live, io->v without io->value and the five
+ * accumulators included) is E3D_ERR_NULL, then e3d_config_check, then with opts->team an alpha outside [0, 1] is E3D_ERR_BAD_CONFIG;
+ * N < 1 returns 0. */
 int e3d_policy_record(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
-                      const e3d_policy_acc *acc, double *rs, double gamma, void *stream);
-
-/* e3d_policy_record with potential-based distance shaping (algo.reward_shaping: distance; csrc/reward_shaping.hpp) on the reward row, in
- * the same launch.  phi [N][P] f64 carries the potential of the state a tick starts from: Phi(n, p) = -coef * |pos_p - pos_e| (x, y, z;
- * sqrt(dx dx + dy dy + dz dz) summed left to right), 0 when the pursuer or the evader is inactive.  e3d_shaping_begin writes Phi of the
- * current records (after a reset).  For an environment that was not done before the step: Phi' = Phi of the records after the tick,
- * Phi_next = 0 where v_next is zeroed (pursuer inactive after the step, or the episode ended, the time limit excepted), else Phi';
- * x = reward + (gamma Phi_next - phi) live; phi = Phi'; io->r = (float)x * live, or, with rs (NULL, or the RewardScaling state of
- * e3d_policy_record, discount gamma as well), the scaled x * live.  Environments done before the step leave phi (and rs) untouched.
- * acc->ret keeps the raw reward; everything but io->r is what e3d_policy_record writes. */
-int e3d_policy_record_shaped(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
-                             const e3d_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream);
+                      const e3d_policy_acc *acc, const policy_record_opts *opts, void *stream);
+/* phi [N][P] f64 = the shaping potential of the current records (after a reset), what opts->phi carries from tick to tick:
+ * Phi(n, p) = -coef * |pos_p - pos_e| (x, y, z; sqrt(dx dx + dy dy + dz dz) summed left to right), 0 when the pursuer or the evader is
+ * inactive. */
 int e3d_shaping_begin(const e3d_config *cfg, const e3d_state *st, double *phi, double coef, void *stream);
-
-/* e3d_policy_record with team reward sharing (algo.team_reward: alpha; csrc/team_reward.hpp), in the same launch.
- * For an environment that was not done before the step, with x = reward[P] and s = sum_k x_k live_k (f64, index order):
- * m_p = (1 - alpha) x_p + (alpha s) live_p takes the place of the raw reward in everything that follows: io->r = (float)m * live; with
- * phi (NULL: no shaping; else the state of e3d_policy_record_shaped with its coef and gamma) the shaping step receives m; with rs
- * (NULL: no scaling; else the RewardScaling state, discount gamma) the scaling step receives m, or the shaped m.  Environments done
- * before the step are what the siblings make of them.  acc->ret keeps the raw reward; everything but io->r, phi and rs is what
- * e3d_policy_record writes.  alpha must be a number in [0, 1]: E3D_ERR_BAD_CONFIG otherwise, before any launch. */
-int e3d_policy_record_team(const e3d_config *cfg, const e3d_state *st, const float *reward, const uint8_t *done, const e3d_record_io *io,
-                           const e3d_policy_acc *acc, double alpha, double *phi, double coef, double gamma, double *rs, void *stream);
 
 /* ---- scripted pursuers: a deterministic lead-pursuit law as a yardstick policy (csrc/guidance.hpp) ----
  * lead: the longest look-ahead in the environment's time units; a team-mate closer than sep_range pushes with weight sep_gain.

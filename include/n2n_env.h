@@ -10,6 +10,7 @@
 #ifndef N2N_ENV_H
 #define N2N_ENV_H
 #include <stdint.h>
+#include "policy_record.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -98,7 +99,7 @@ typedef struct n2n_policy_acc {  /* per-environment episode accumulators [N], ze
 typedef struct n2n_record_io {
     const float *live;  int64_t live_rs;    /* [N][P] this step's live mask (n2n_policy_inputs), required               */
     const float *value; int64_t value_rs;   /* [N][P] the critic's value of this step, required with v                  */
-    float *r;      int64_t r_rs;            /* [N][P] reward * live                                                     */
+    float *r;      int64_t r_rs;            /* [N][P] reward * live, or what the options of policy_record.h make of it  */
     float *active; int64_t active_rs;       /* [N][P] live                                                              */
     float *v;      int64_t v_rs;            /* [N][P] value * live                                                      */
     float *v_next; int64_t v_next_rs;       /* [N][P] set to 0 where the pursuer is inactive after the step or its
@@ -107,38 +108,16 @@ typedef struct n2n_record_io {
 
 /* Before the policy step: the DHGN's inputs from the records p, e, the tick's adjacencies and done_before [N] (NULL: none done). */
 int n2n_policy_inputs(const n2n_config *cfg, const n2n_state *st, const uint8_t *done_before, const n2n_policy_io *io, void *stream);
-/* After n2n_env_tick: buffer row t and the accumulators from the tick's reward [N][P] and done [N] and the records after it. */
+/* After n2n_env_tick: buffer row t and the accumulators from the tick's reward [N][P] and done [N] and the records after it.  opts: NULL,
+ * or the reward options of policy_record.h (RewardScaling, distance shaping, team reward sharing), in the same launch.  One launch, the
+ * tick's lane layout.  Before any launch: a NULL argument (io->live, io->v without io->value and the five accumulators included) is
+ * N2N_ERR_NULL, then n2n_config_check, then with opts->team an alpha outside [0, 1] is N2N_ERR_BAD_CONFIG; N < 1 returns 0. */
 int n2n_policy_record(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                      const n2n_policy_acc *acc, void *stream);
-/* n2n_policy_record with the reference's RewardScaling (DHGN/normalization.py:38-52, csrc/reward_scale.hpp) on the reward row, in the
- * same launch.  rs [N][1 + 3P] f64: n, mean[P], S[P], R[P] per environment; the caller zeroes it once (and R at every episode start:
- * RewardScaling.reset).  For an environment that was not done before the step, with x = reward[P] (every pursuer's, an inactive one's 0
- * included): R = gamma R + x; n += 1; n == 1: mean = std = R, else mean' = mean + (R - mean) / n, S += (R - mean)(R - mean'),
- * std = sqrt(S / n); io->r = (float)(x / (std + 1e-8)) * live.  Environments done before the step leave rs untouched (r = reward * live,
- * zero).  acc->ret keeps the raw reward.  Everything else as n2n_policy_record. */
-int n2n_policy_record_scaled(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                             const n2n_policy_acc *acc, double *rs, double gamma, void *stream);
-/* n2n_policy_record with potential-based distance shaping (algo.reward_shaping: distance; csrc/reward_shaping.hpp) on the reward row, in
- * the same launch.  phi [N][P] f64 carries the potential of the state a tick starts from: Phi(n, p) = -coef * min_k |pos_p - pos_k| over
- * the ACTIVE evaders k (x, y; sqrt(dx dx + dy dy)), 0 when the pursuer is inactive or no evader is active.  n2n_shaping_begin writes Phi
- * of the current records (after a reset).  For an environment that was not done before the step: Phi' = Phi of the records after the
- * tick, Phi_next = 0 where v_next is zeroed (pursuer inactive after the step, or the episode ended, the time limit excepted), else Phi';
- * x = reward + (gamma Phi_next - phi) live; phi = Phi'; io->r = (float)x * live, or, with rs (NULL, or the state of
- * n2n_policy_record_scaled, discount gamma as well), the scaled x * live.  Environments done before the step leave phi (and rs)
- * untouched.  acc->ret keeps the raw reward; everything but io->r is what n2n_policy_record writes. */
-int n2n_policy_record_shaped(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                             const n2n_policy_acc *acc, double *phi, double coef, double gamma, double *rs, void *stream);
+                      const n2n_policy_acc *acc, const policy_record_opts *opts, void *stream);
+/* phi [N][P] f64 = the shaping potential of the current records (after a reset), what opts->phi carries from tick to tick:
+ * Phi(n, p) = -coef * min_k |pos_p - pos_k| over the ACTIVE evaders k (x, y; sqrt(dx dx + dy dy)), 0 when the pursuer is inactive or no
+ * evader is active. */
 int n2n_shaping_begin(const n2n_config *cfg, const n2n_state *st, double *phi, double coef, void *stream);
-
-/* n2n_policy_record with team reward sharing (algo.team_reward: alpha; csrc/team_reward.hpp), in the same launch.
- * For an environment that was not done before the step, with x = reward[P] and s = sum_k x_k live_k (f64, index order):
- * m_p = (1 - alpha) x_p + (alpha s) live_p takes the place of the raw reward in everything that follows: io->r = (float)m * live; with
- * phi (NULL: no shaping; else the state of n2n_policy_record_shaped with its coef and gamma) the shaping step receives m; with rs
- * (NULL: no scaling; else the state of n2n_policy_record_scaled, discount gamma) the scaling step receives m, or the shaped m.
- * Environments done before the step are what the siblings make of them.  acc->ret keeps the raw reward; everything but io->r, phi and
- * rs is what n2n_policy_record writes.  alpha must be a number in [0, 1]: N2N_ERR_BAD_CONFIG otherwise, before any launch. */
-int n2n_policy_record_team(const n2n_config *cfg, const n2n_state *st, const float *reward, const uint8_t *done, const n2n_record_io *io,
-                           const n2n_policy_acc *acc, double alpha, double *phi, double coef, double gamma, double *rs, void *stream);
 
 /* ---- scripted pursuers: a deterministic lead-pursuit law as a yardstick policy (csrc/guidance.hpp) ----
  * lead: the longest look-ahead in the environment's time units; a team-mate closer than sep_range pushes with weight sep_gain.

@@ -1,5 +1,5 @@
 """numpy restatement of algo.use_reward_scaling: the reference's RewardScaling (DHGN/normalization.py:38-52) per environment slot,
-under the lockstep masks of the env_n2n / env_3d rollouts (csrc/reward_scale.hpp, n2n_policy_record_scaled, e3d_policy_record).
+under the lockstep masks of the env_n2n / env_3d rollouts (csrc/reward_scale.hpp, the scaling option of n2n_policy_record / e3d_policy_record).
 
 State (N, 1 + 3P) f64: n, mean[P], S[P], R[P] per environment.  Every operation is the reference's, elementwise in f64, so the
 results are the reference's bit for bit (tests/golden/reward_scaling.npz)."""

@@ -1,5 +1,5 @@
 """numpy restatement of algo.reward_shaping: distance -- potential-based shaping (Ng, Harada and Russell 1999) under the lockstep masks
-of the env_3d / env_n2n rollouts (csrc/reward_shaping.hpp, e3d_policy_record_shaped, n2n_policy_record_shaped, *_shaping_begin).
+of the env_3d / env_n2n rollouts (csrc/reward_shaping.hpp, the shaping option of e3d_policy_record / n2n_policy_record, *_shaping_begin).
 
 Records are the device's: p (N, C, P) and e (N, C, E) f64 with the coordinates in the first D rows (D = 2: env_n2n, C = 5; D = 3:
 env_3d, C = 7, e given as (N, 7) or (N, 7, 1)) and the active flag in the last row.  Every operation is elementwise f64 in the order

@@ -1,5 +1,5 @@
 """numpy restatement of algo.team_reward: team reward sharing under the lockstep masks of the env_3d / env_n2n rollouts
-(csrc/team_reward.hpp, e3d_policy_record_team, n2n_policy_record_team).
+(csrc/team_reward.hpp, the team option of e3d_policy_record / n2n_policy_record).
 
 One step of an environment that was not done before it: x_p the raw reward of pursuer p (fp32, widened), live_p its live mask (0 / 1),
 s = sum_k x_k live_k added in index order, m_p = (1 - alpha) x_p + (alpha s) live_p.  Every operation is f64 in the order of the

@@ -1,4 +1,4 @@
-"""GPU checks of algo.use_reward_scaling (the reference's RewardScaling in n2n_policy_record_scaled / e3d_policy_record) and of the
+"""GPU checks of algo.use_reward_scaling (the reference's RewardScaling as the scaling option of n2n_policy_record / e3d_policy_record) and of the
 env_3d record kernel: fixture replay through both kernels bit for bit, e3d_policy_record against a torch restatement of the
 bookkeeping it replaces, one training iteration per environment against tests/reward_scale_ref.py, and resume."""
 import os

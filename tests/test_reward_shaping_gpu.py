@@ -1,4 +1,4 @@
-"""GPU checks of algo.reward_shaping: distance (e3d_policy_record_shaped / n2n_policy_record_shaped and the *_shaping_begin launches):
+"""GPU checks of algo.reward_shaping: distance (the shaping option of e3d_policy_record / n2n_policy_record, include/policy_record.h, and the *_shaping_begin launches):
 the kernels against tests/shaping_ref.py bit for bit with and without reward scaling, every other output of the record launch byte
 for byte against the unshaped call, and the option in the trainers: off, on, deterministic, resumed."""
 import numpy as np

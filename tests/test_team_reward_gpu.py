@@ -1,4 +1,4 @@
-"""GPU checks of algo.team_reward (e3d_policy_record_team / n2n_policy_record_team): the record launch with sharing against
+"""GPU checks of algo.team_reward (the team option of e3d_policy_record / n2n_policy_record, include/policy_record.h): the record launch with sharing against
 tests/team_reward_ref.py bit for bit -- alone, with reward scaling, with distance shaping, with both --, every other output byte for
 byte against the unshared launch, alpha = 0 against the unshared entry points, determinism, and the option in the trainers: absent,
 on, deterministic, resumed, and out of evaluation and the scripted pursuers' episodes.
@@ -230,7 +230,7 @@ def test_bad_coefficient_and_missing_state_are_refused(kind):
     acc = env.new_accumulators()
     live = torch.ones(N, 4, device=DEV)
     for bad in (-0.1, 1.5, float("nan"), float("inf")):
-        with pytest.raises(RuntimeError, match="policy_record_team failed with code [34]0001"):
+        with pytest.raises(RuntimeError, match="policy_record failed with code [34]0001"):
             env.policy_record(acc, live, team_coef=bad)
     with pytest.raises(RuntimeError, match="enable_reward_scaling"):
         env.policy_record(acc, live, scale_gamma=GAMMA, team_coef=0.5)

@@ -231,7 +231,7 @@ def _bookkeeping(acc, raw, lv, value, done, p_after, e_after, ended_now):
 
 @pytest.mark.parametrize("case", wc.CASES, ids=wc.IDS)
 def test_record_launches_match_their_restatements_over_the_episode(case):
-    """the episode's 25 ticks through e3d_ / n2n_policy_record, _scaled, _shaped, _team and the three options together, each variant
+    """the episode's 25 ticks through e3d_ / n2n_policy_record with no option, with each of the three and with all three together, each variant
     with its own states: r (fp32), reward_scale and shaping_phi (f64) equal the restatements bit for bit (tests/reward_scale_ref.py,
     shaping_ref.py, team_reward_ref.py), environments done before the step untouched; active, v, v_next, live_next and the five
     accumulators are the plain launch's bytes, and the plain launch's are the bookkeeping's (env_n2n: n2n_policy_ref.policy_record)"""
