@@ -36,7 +36,9 @@ constexpr double PI = 3.14159265358979323846;
 
 __host__ __device__ inline double norm3(double a, double b, double c) { return sqrt(fma(c, c, fma(b, b, a * a))); }
 // `norm3(..) <= r` without the square root (sqrt is correctly rounded and monotonic): the squared norm -- the same fma chain the
-// norm takes the root of -- against the largest double t with sqrt(t) <= r, computed once per launch on the host
+// norm takes the root of -- against the largest double t with sqrt(t) <= r, computed once per launch on the host.
+// Held by tests/test_particle_config_gpu.py on states whose squared distance is t itself, one double above it, or on the other
+// side of it than the unfused sum (tests/particle_config_cases.py): t is not fl(r r) for r = 0.5, the default kill radius.
 __device__ __forceinline__ double sq3(double a, double b, double c) { return fma(c, c, fma(b, b, a * a)); }
 double sq_threshold(double r) {
     auto ok = [&](double t) { return sqrt(t) <= r; };

@@ -5,6 +5,8 @@ pp_in (N, P, P) and pe_in (N, P, E) are fp32.  The accumulators are a dict of nu
 ret, length (float32)."""
 import numpy as np
 
+from tests import shaping_ref
+
 
 def _rows4(rec, on):
     """(x, y, v cos phi, v sin phi) in float64, rounded to fp32; zero where `on` is false"""
@@ -30,16 +32,6 @@ def policy_inputs(p, e, pp_in, pe_in, done_before=None):
     return dict(p4=_rows4(p, live), e4=e4, e_ref=e_ref, live=live.astype(np.float32), pp_adj=pp, pe_adj=pe)
 
 
-def _sq_threshold(r):
-    """the largest double t with sqrt(t) <= r (csrc/n2n_env.hip sq_threshold)"""
-    t = r * r
-    while not np.sqrt(t) <= r:
-        t = np.nextafter(t, 0.0)
-    while np.sqrt(np.nextafter(t, np.inf)) <= r:
-        t = np.nextafter(t, np.inf)
-    return t
-
-
 def policy_record(p, e, target, reward, done, live, value, acc, kill_radius):
     """the state after the tick (records p, e), its reward (N,P) fp32 and done (N,) flags, this step's live (N,P) and value (N,P)
     -> (r, active, v, v_next_zero (N,P) bool) and the updated accumulators (a new dict)"""
@@ -48,9 +40,8 @@ def policy_record(p, e, target, reward, done, live, value, acc, kill_radius):
     rl = (reward.astype(np.float32) * live).astype(np.float32)
     v = (value.astype(np.float32) * live).astype(np.float32)
     p_on, e_on = p[:, 4] != 0, e[:, 4] != 0
-    dx, dy = e[:, 0] - target[:, 0:1], e[:, 1] - target[:, 1:2]
-    # the kernel's squared norm is fma(dy, dy, dx dx); the unfused sum differs only in the last bit, which the test records keep away from
-    reach = ((dx * dx + dy * dy) <= _sq_threshold(kill_radius)).any(-1)
+    # get_done's norm is sqrt(fma(dy, dy, dx dx)); tests/particle_config_cases.py has records on which the unfused sum decides otherwise
+    reach = shaping_ref.within(np.stack((e[:, 0] - target[:, 0:1], e[:, 1] - target[:, 1:2])), kill_radius).any(-1)
     pa, ea = p_on.sum(-1), e_on.sum(-1)
     out = {k: x.copy() for k, x in acc.items()}
     db = acc["done_before"].astype(bool)

@@ -4,6 +4,9 @@ of the env_3d / env_n2n rollouts (csrc/reward_shaping.hpp, the shaping option of
 Records are the device's: p (N, C, P) and e (N, C, E) f64 with the coordinates in the first D rows (D = 2: env_n2n, C = 5; D = 3:
 env_3d, C = 7, e given as (N, 7) or (N, 7, 1)) and the active flag in the last row.  Every operation is elementwise f64 in the order
 of the header (plain *, +, -, sqrt; squares summed left to right), so the kernels reproduce it bit for bit."""
+import math
+from fractions import Fraction
+
 import numpy as np
 
 
@@ -33,13 +36,28 @@ def potential(p, e, coef):
     return np.where(p_on & any_e, -coef * dmin, 0.0)
 
 
+def within(d, r):
+    """d (D, ...), D = 2 or 3 -> `norm(d) <= r` as the environments' range tests evaluate it (numpy's norm of a 2- or 3-vector):
+    sqrt(fma(c, c, fma(b, b, a a))) <= r.  numpy has no fma: where the plain sum of squares is within 1e-12 r r of r r -- it differs
+    from the chain by a few ulp at most -- the chain is evaluated in rationals, rounded once per fma; elsewhere the plain sum decides."""
+    d = np.asarray(d, np.float64)
+    sq = (d * d).sum(0)
+    out = np.asarray(np.sqrt(sq) <= r)
+    for k in zip(*np.nonzero(np.abs(sq - r * r) <= 1e-12 * r * r)):
+        s = float(d[0][k]) * float(d[0][k])
+        for x in d[1:]:
+            s = float(Fraction(float(x[k])) ** 2 + Fraction(s))
+        out[k] = math.sqrt(s) <= r
+    return out
+
+
 def ended_after(p, e, target, kill_radius):
     """(N,) the state in the records ends the episode for a reason other than the time limit: no pursuer active, no evader active
     (env_3d: the evader dead), or an evader within the kill radius of the target (get_done of either environment)"""
     p, e, target = np.asarray(p, np.float64), _e3(e), np.asarray(target, np.float64)
     D = dims(p)
     p_on, e_on = p[:, -1, :] != 0.0, e[:, -1, :] != 0.0
-    reach = np.sqrt(((e[:, :D, :] - target[:, :, None]) ** 2).sum(1)) <= kill_radius
+    reach = within((e[:, :D, :] - target[:, :, None]).transpose(1, 0, 2), kill_radius)
     return ~p_on.any(-1) | ~e_on.any(-1) | reach.any(-1)
 
 
