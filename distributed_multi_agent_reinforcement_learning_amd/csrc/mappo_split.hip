@@ -10,6 +10,7 @@
 #include "sb_encoder_tail.hpp"
 #include "sb_encoder_tail_bwd.hpp"
 #include "sb_gru_seq.hpp"
+#include "gnn_pairs.hpp"
 
 extern "C" {
 
@@ -138,6 +139,47 @@ int gru_seq_split_fwd_multi(int32_t n_nets, const mo_gru_seq_net *nets, int32_t 
 int gru_seq_split_bwd_multi(int32_t n_nets, const mo_gru_seq_bwd_net *nets, int32_t T, int32_t B, int32_t H, int32_t gi_agents, void *stream) {
     if (!gru_seq_bwd_nets_ok(n_nets, nets, T, B, H, gi_agents)) return MO_ERR_BAD_ARG;
     return launch_gru_seq_bwd_sb(n_nets, nets, T, B, gi_agents, (hipStream_t)stream);
+}
+
+// the checks of both gnn_pair_agg entry points -> 0 and the kernels' argument record, or MO_ERR_BAD_ARG
+static int gnn_pair_args(int64_t R, int32_t P, int32_t O, int32_t q_div, int32_t middle, int32_t embed, const float *p, const float *e, const float *o,
+                         const float *adj_p, const float *adj_e, const void *adj_o, int32_t adj_mode, const float *W1, const float *b1, const float *W2,
+                         const float *b2, GpArgs &a) {
+    if (R < 0 || P < 1 || P > GP_PMAX || O < 0 || P + 1 + O > GP_KMAX || q_div < 1 || R % q_div != 0 || middle != 128 || embed != 128) return MO_ERR_BAD_ARG;
+    if (adj_mode != GP_ADJ_TENSOR && adj_mode != GP_ADJ_ONES && adj_mode != GP_ADJ_BITS) return MO_ERR_BAD_ARG;
+    if (!p || !e || (O > 0 && !o) || !W1 || !b1 || !W2 || !b2) return MO_ERR_BAD_ARG;
+    if (adj_mode != GP_ADJ_ONES && (!adj_p || !adj_e || (O > 0 && !adj_o))) return MO_ERR_BAD_ARG;
+    if (((uintptr_t)p & 15) || ((uintptr_t)e & 15) || ((uintptr_t)o & 15) || ((uintptr_t)W2 & 15) || ((uintptr_t)b2 & 15) || ((uintptr_t)W1 & 3) ||
+        ((uintptr_t)b1 & 3) || ((uintptr_t)adj_p & 3) || ((uintptr_t)adj_e & 3) || ((uintptr_t)adj_o & 3))
+        return MO_ERR_BAD_ARG;
+    a = GpArgs{R, P, O, q_div, adj_mode, MO_ADJ_ROW_WORDS(O), p, e, o, adj_p, adj_e, adj_o, W1, b1, W2, b2};
+    return 0;
+}
+
+int gnn_pair_agg_fwd(int64_t R, int32_t P, int32_t O, int32_t q_div, int32_t middle, int32_t embed, const float *p, const float *e, const float *o,
+                     const float *adj_p, const float *adj_e, const void *adj_o, int32_t adj_mode, const float *W1, const float *b1, const float *W2,
+                     const float *b2, float *agg, void *stream) {
+    GpArgs a;
+    if (gnn_pair_args(R, P, O, q_div, middle, embed, p, e, o, adj_p, adj_e, adj_o, adj_mode, W1, b1, W2, b2, a) || !agg || ((uintptr_t)agg & 15))
+        return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_gnn_pair_fwd(a, agg, (hipStream_t)stream);
+}
+
+int64_t gnn_pair_agg_bwd_workspace(int64_t R, int32_t P) {
+    return R > 0 && P > 0 ? (int64_t)gp_bwd_grid(R, P) * GP_BLOCK * 4 : 0;
+}
+
+int gnn_pair_agg_bwd(int64_t R, int32_t P, int32_t O, int32_t q_div, int32_t middle, int32_t embed, const float *p, const float *e, const float *o,
+                     const float *adj_p, const float *adj_e, const void *adj_o, int32_t adj_mode, const float *W1, const float *b1, const float *W2,
+                     const float *b2, const float *d_agg, float *dW1, float *db1, float *dW2, float *db2, void *workspace, void *stream) {
+    GpArgs a;
+    if (gnn_pair_args(R, P, O, q_div, middle, embed, p, e, o, adj_p, adj_e, adj_o, adj_mode, W1, b1, W2, b2, a) || !d_agg || !dW1 || !db1 || !dW2 || !db2 ||
+        !workspace || ((uintptr_t)d_agg & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)dW1 & 3) || ((uintptr_t)db1 & 3) || ((uintptr_t)dW2 & 3) ||
+        ((uintptr_t)db2 & 3))
+        return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_gnn_pair_bwd(a, d_agg, dW1, db1, dW2, db2, (float *)workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

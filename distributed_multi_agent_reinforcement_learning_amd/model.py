@@ -445,7 +445,9 @@ class GnnEncoder(GnnExtractor):
       obstacle_differ_3hop/mappo_parallel.py:193);  last_comm_embedding = this network's own last two embeddings [t-2 | t-1]
       (:459-461, :526-527) -- MAPPO's history plumbing with algo.depth = 2 and a clean per-network history.
     The per-pair two-layer MLP (P K (2 F E + 2 E^2) flops per row: 51 MFLOP at P = 8, K = 185 -- seven times the whole DHGN network)
-    runs in plain torch GEMMs, row-chunked; it is an alternative for small batches, not a benchmark path."""
+    and the weighted sum run in the fused pair kernels (ops.gnn_pair_agg, csrc/gnn_pairs.hpp: no pair tensor in HBM, pairs with a zero
+    adjacency skipped, nothing saved for the backward) where ops.gnn_pair_agg_ok holds -- CUDA, widths 128, runtime.matmul: split_bf16;
+    anywhere else in plain torch GEMMs, row-chunked (DESIGN 7s has the measured times of both)."""
     HISTORY = 2
     PAIR_FEATURES = 7
     CHUNK_PAIRS = 1 << 21
@@ -474,6 +476,22 @@ class GnnEncoder(GnnExtractor):
         R, P = p.shape[0], p.shape[1]
         K = P + 1 + o.shape[1]
         last = torch.cat([hist[1], hist[0]], dim=-1).reshape(R, P, 2 * self.embedding_dim)  # hop k = the embedding of step t-1-k
+        l1, l2 = self.one_hop[0], self.one_hop[2]
+        pair_args = (p, e, o, adj_p, adj_e, adj_o, l1.weight, l1.bias, l2.weight, l2.bias, bool(is_critic), q_div)
+        if ops.gnn_pair_agg_ok(*pair_args):     # all R rows in one launch each way, no pair tensor (csrc/gnn_pairs.hpp)
+            agg = ops.gnn_pair_agg(*pair_args)
+            if is_critic:
+                comm = last.sum(dim=1, keepdim=True).expand(R, P, last.shape[-1]) / K
+            else:
+                if adj_o.dtype == torch.int32:
+                    adj_o = ops.unpack_adj_bits(adj_o, o.shape[1])
+                norm = torch.cat([adj_p, adj_e, adj_o], dim=-1).abs().sum(-1, keepdim=True).clamp_min(1e-12)
+                comm = torch.matmul(adj_p / norm, last)
+            y = self.bottleneck(torch.cat([agg, comm], dim=-1))
+            if out is not None:
+                out.copy_(y)
+                return out
+            return y
         step = max(q_div, (self.CHUNK_PAIRS // (P * K)) // q_div * q_div) if q_div > 1 else max(1, self.CHUNK_PAIRS // (P * K))
         parts = []
         for r0 in range(0, R, step):

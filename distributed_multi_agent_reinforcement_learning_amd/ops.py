@@ -23,7 +23,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "fused_adam_grid", "fused_adam_norm", "fused_adam_step", "fused_adam_advance_host", "fused_adam_rows_host", "bc_loss_workspace",
            "bc_loss_gauss_fwd_bwd", "bc_loss_gauss_ex_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "ppo_bc_loss_workspace",
            "ppo_bc_loss_gauss_fwd_bwd", "ppo_bc_loss_cat_fwd_bwd", "team_comm_mask", "team_attention_fwd", "team_attention_bwd",
-           "team_comm_mask_host", "team_attention_fwd_host", "team_attention_bwd_host", "mappo_ops_error_string")
+           "team_comm_mask_host", "team_attention_fwd_host", "team_attention_bwd_host", "gnn_pair_agg_fwd", "gnn_pair_agg_bwd",
+           "gnn_pair_agg_bwd_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -154,6 +155,10 @@ def load_library():
         L.team_attention_fwd_host.argtypes = [i64, i32, i32, vp, vp, vp, vp]
         L.team_attention_bwd_host.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp]
         L.sb_split_diag.argtypes = [i64, vp, vp, vp]
+        L.gnn_pair_agg_fwd.argtypes = [i64, i32, i32, i32, i32, i32] + [vp] * 6 + [i32] + [vp] * 6
+        L.gnn_pair_agg_bwd_workspace.argtypes = [i64, i32]
+        L.gnn_pair_agg_bwd_workspace.restype = i64
+        L.gnn_pair_agg_bwd.argtypes = [i64, i32, i32, i32, i32, i32] + [vp] * 6 + [i32] + [vp] * 11
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
         _lib = L
@@ -1858,6 +1863,86 @@ def set_matmul_mode(mode):
     global MATMUL_MODE, WGRAD_MODE, PROJ_MODE, SEQ_MODE
     set_cell_mode(mode)
     MATMUL_MODE = WGRAD_MODE = PROJ_MODE = SEQ_MODE = mode
+
+
+GNN_PAIR_FUSED = os.environ.get("MAPPO_GNN_PAIR_FUSED", "1") != "0"   # A/B switch (tools/ab_switch.py): off = GnnEncoder's torch GEMMs
+gnn_pair_calls = 0                                                     # forward launches of the fused pair kernels so far (tests)
+
+
+def _gnn_pair_mode(adj_o, ones):
+    return ADJ_ONES if ones else (ADJ_BITS if adj_o.dtype == torch.int32 else ADJ_TENSOR)
+
+
+def gnn_pair_agg_ok(p, e, o, adj_p, adj_e, adj_o, W1, b1, W2, b2, ones=False, q_div=1):
+    """whether the fused pair kernels (csrc/gnn_pairs.hpp) serve this call: the switch, split-bf16 arithmetic, the built library, fp32
+    contiguous CUDA operands, both widths 128, 7 pair features, the kernels' ranges of P and K"""
+    if not GNN_PAIR_FUSED or MATMUL_MODE != "split_bf16" or not p.is_cuda or not os.path.exists(lib_path()):
+        return False
+    if tuple(W1.shape) != (128, 7) or tuple(W2.shape) != (128, 128) or tuple(b1.shape) != (128,) or tuple(b2.shape) != (128,):
+        return False
+    if p.dim() != 3 or o.dim() != 3 or p.shape[2] != 4 or o.shape[2] != 4:
+        return False
+    R, P, O = p.shape[0], p.shape[1], o.shape[1]
+    if R == 0 or not 1 <= P <= 64 or P + 1 + O > 1024 or q_div < 1 or R % q_div or o.shape[0] * q_div != R or e.numel() != R * 4:
+        return False
+    ts = [p, e, o, W1, b1, W2, b2]
+    if not ones:
+        if adj_o.dtype == torch.int32:
+            if tuple(adj_o.shape) != (R, P, adj_row_words(O)) or not adj_o.is_contiguous():
+                return False
+        else:
+            ts.append(adj_o)
+            if tuple(adj_o.shape) != (R, P, O):
+                return False
+        if tuple(adj_p.shape) != (R, P, P) or adj_e.numel() != R * P:
+            return False
+        ts += [adj_p, adj_e]
+    return all(t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts)
+
+
+def _gnn_pair_args(p, e, o, adj_p, adj_e, adj_o, W1, b1, W2, b2, mode, q_div):
+    adj = (None, None, None) if mode == ADJ_ONES else (adj_p, adj_e, adj_o)
+    return (p.shape[0], p.shape[1], o.shape[1], q_div, W1.shape[0], W2.shape[0], _ptr(p), _ptr(e), _ptr(o), *[_ptr(t) for t in adj], mode,
+            _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2))
+
+
+class _GnnPairAgg(torch.autograd.Function):
+    """agg (R, P, 128) = sum_j normalised adj_ij * one_hop(x_ij) without the pair tensors; nothing saved but the inputs"""
+
+    @staticmethod
+    def forward(ctx, p, e, o, adj_p, adj_e, adj_o, W1, b1, W2, b2, ones, q_div):
+        global gnn_pair_calls
+        L = load_library()
+        _need_gpu(p, "gnn_pair_agg")
+        mode = _gnn_pair_mode(adj_o, ones)
+        ts = [t.detach() for t in (p, e, o, adj_p, adj_e, adj_o, W1, b1, W2, b2)]
+        agg = torch.empty((p.shape[0], p.shape[1], 128), dtype=torch.float32, device=p.device)
+        _check(L.gnn_pair_agg_fwd(*_gnn_pair_args(*ts, mode, q_div), _ptr(agg), _stream()), "gnn_pair_agg_fwd")
+        gnn_pair_calls += 1
+        ctx.save_for_backward(*ts)
+        ctx.mode, ctx.q_div = mode, q_div
+        return agg
+
+    @staticmethod
+    def backward(ctx, d_agg):
+        L = load_library()
+        ts = ctx.saved_tensors
+        dev, R, P = d_agg.device, ts[0].shape[0], ts[0].shape[1]
+        d_agg = _dense16(d_agg)
+        dW1, db1 = torch.empty((128, 7), dtype=torch.float32, device=dev), torch.empty(128, dtype=torch.float32, device=dev)
+        dW2, db2 = torch.empty((128, 128), dtype=torch.float32, device=dev), torch.empty(128, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.gnn_pair_agg_bwd_workspace(R, P), dtype=torch.uint8, device=dev)   # from torch: capturable
+        _check(L.gnn_pair_agg_bwd(*_gnn_pair_args(*ts, ctx.mode, ctx.q_div), _ptr(d_agg), _ptr(dW1), _ptr(db1), _ptr(dW2), _ptr(db2), _ptr(ws),
+                                  _stream()), "gnn_pair_agg_bwd")
+        return (None,) * 6 + (dW1, db1, dW2, db2, None, None)
+
+
+def gnn_pair_agg(p, e, o, adj_p, adj_e, adj_o, W1, b1, W2, b2, ones=False, q_div=1):
+    """GnnExtractor's one_hop over every (pursuer, entity) pair of a row and the sum weighted by the L1-normalised adjacency, in one launch
+    each way (include/mappo_ops.h gnn_pair_agg_fwd): p (R, P, 4), e (R, 4), o (R / q_div, O, 4); adj_p (R, P, P), adj_e (R, P[, 1]) and
+    adj_o (R, P, O) floats or the int32 words of pack_adj_bits; ones: the critic's all-ones adjacency -> (R, P, 128).  Gradients for
+    W1, b1, W2, b2 only.  Callers ask gnn_pair_agg_ok first: a shape the kernels do not serve raises."""
+    return _GnnPairAgg.apply(p, e, o, adj_p, adj_e, adj_o, W1, b1, W2, b2, bool(ones), int(q_div))
 
 
 SPLIT_LINEAR_SHAPES = {(128, 128), (128, 256), (128, 384), (256, 128), (384, 128)}    # (outputs, inputs) sb_gemm covers

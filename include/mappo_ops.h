@@ -347,6 +347,26 @@ int64_t sb_encoder_tail_bwd_workspace(void);
 int sb_encoder_tail_bwd(int64_t Rs, const float *g, int64_t ldg, const float *Ws, int64_t ldw, const float *w_agg, const uint8_t *emb_sign_bits,
                         int64_t ld_bytes, float *ga, int64_t ldga, float *d_m3, int64_t ldd, float *colsum, void *workspace, void *stream);
 
+/* The GnnExtractor encoder's pair MLP and weighted sum, fused (csrc/gnn_pairs.hpp; GnnEncoder.forward's first half).  Entities of row r: the P
+ * pursuers p [R][P][4], the evader e [R][4], the O obstacles o [R / q_div][O][4] (R % q_div == 0); K = P + 1 + O <= 1024, 1 <= P <= 64.
+ *   x_ij = [state_j - state_i, one-hot(type of j)],  h2_ij = relu(W2 relu(W1 x_ij + b1) + b2),   W1 [128][7], W2 [128][128] dense
+ *   agg[r][i] = sum_j (adj_ij / max(sum_j |adj_ij|, 1e-12)) h2_ij                                  agg [R][P][128]
+ * adj_mode MO_ADJ_TENSOR: adj = [adj_p [R][P][P] | adj_e [R][P] | adj_o [R][P][O]] floats; MO_ADJ_BITS: adj_o is uint32 [R][P][MO_ADJ_ROW_WORDS(O)];
+ * MO_ADJ_ONES: ones over all K (the adj pointers are not read).  Pairs with adj_ij == 0 are not computed; a row of zeros gives exact zeros.
+ * middle, embed: the widths of the two layers, 128 both (anything else: MO_ERR_BAD_ARG, as for bad sizes and null or misaligned pointers --
+ * 16 bytes for p, e, o, W2, b2, agg, d_agg, workspace; 4 for the rest -- before any launch).  R == 0 succeeds and writes nothing.
+ * No atomics: agg[r] depends on row r's inputs only, bit for bit.
+ * gnn_pair_agg_bwd: for the gradient d_agg [R][P][128] -> dW1 [128][7], db1 [128], dW2 [128][128], db2 [128] (overwritten; states and adjacency
+ * take no gradient).  The forward saves nothing: the activations are recomputed per tile.  One partial block per workgroup in `workspace`
+ * (>= gnn_pair_agg_bwd_workspace(R, P) bytes), added in a fixed order: the same bits from run to run. */
+int gnn_pair_agg_fwd(int64_t R, int32_t P, int32_t O, int32_t q_div, int32_t middle, int32_t embed, const float *p, const float *e, const float *o,
+                     const float *adj_p, const float *adj_e, const void *adj_o, int32_t adj_mode, const float *W1, const float *b1, const float *W2,
+                     const float *b2, float *agg, void *stream);
+int64_t gnn_pair_agg_bwd_workspace(int64_t R, int32_t P);
+int gnn_pair_agg_bwd(int64_t R, int32_t P, int32_t O, int32_t q_div, int32_t middle, int32_t embed, const float *p, const float *e, const float *o,
+                     const float *adj_p, const float *adj_e, const void *adj_o, int32_t adj_mode, const float *W1, const float *b1, const float *W2,
+                     const float *b2, const float *d_agg, float *dW1, float *db1, float *dW2, float *db2, void *workspace, void *stream);
+
 /*
  * PPO clipped-surrogate policy loss and clipped value loss of one mini-batch with their gradients
  * (DHGN/mappo_parallel.py:692-706):
