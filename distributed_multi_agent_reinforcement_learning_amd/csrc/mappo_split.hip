@@ -11,6 +11,7 @@
 #include "sb_encoder_tail_bwd.hpp"
 #include "sb_gru_seq.hpp"
 #include "gnn_pairs.hpp"
+#include "att_agg.hpp"
 
 extern "C" {
 
@@ -180,6 +181,58 @@ int gnn_pair_agg_bwd(int64_t R, int32_t P, int32_t O, int32_t q_div, int32_t mid
         return MO_ERR_BAD_ARG;
     if (R == 0) return 0;
     return launch_gnn_pair_bwd(a, d_agg, dW1, db1, dW2, db2, (float *)workspace, (hipStream_t)stream);
+}
+
+// one relation of the attention aggregator as the kernels take it, or not (K = 0: an empty relation, q and adj may be NULL)
+static bool att_rel_ok(const mo_att_rel &m, int32_t R, int32_t P) {
+    if (m.K < 0 || m.K > AA_KMAX || (m.din != 4 && m.din != 8) || m.q_div < 1 || R % m.q_div != 0 || m.adj_mode < 0 || m.adj_mode > 3) return false;
+    if (!m.W || !m.b || !m.alpha || ((uintptr_t)m.W & 15) || ((uintptr_t)m.b & 3) || ((uintptr_t)m.alpha & 3)) return false;
+    if (m.din == 8 && (!m.e || ((uintptr_t)m.e & 15) || (m.e_rs & 3) || m.e_rs < 4)) return false;
+    if (m.adj_mode == MO_ADJ_VALID && (!m.kvalid || ((uintptr_t)m.kvalid & 3))) return false;
+    if (m.K == 0) return true;
+    if (!m.q || ((uintptr_t)m.q & 15) || (m.q_rs & 3) || m.q_rs < 4 * (int64_t)m.K) return false;
+    if (m.adj_mode == MO_ADJ_TENSOR && (!m.adj || ((uintptr_t)m.adj & 3) || m.adj_rs < (int64_t)P * m.K)) return false;
+    if (m.adj_mode == MO_ADJ_BITS && (!m.adj || ((uintptr_t)m.adj & 3) || m.adj_rs < (int64_t)P * MO_ADJ_ROW_WORDS(m.K))) return false;
+    return true;
+}
+
+// the checks common to both entry points -> 0 and the kernels' argument record, or MO_ERR_BAD_ARG
+static int att_args(const mo_att_rel *rel, int n_rel, int32_t R, int32_t P, int32_t E, const float *p, int64_t p_rs, AaArgs &a) {
+    if (!rel || R < 0 || P < 1 || P > AA_PMAX || E != AA_E || !p || ((uintptr_t)p & 15) || (p_rs & 3) || p_rs < 4 * (int64_t)P) return MO_ERR_BAD_ARG;
+    int kmax = 4;
+    for (int r = 0; r < n_rel; r++) {
+        if (!att_rel_ok(rel[r], R, P)) return MO_ERR_BAD_ARG;
+        a.rel[r] = rel[r];
+        if (rel[r].K > kmax) kmax = rel[r].K;
+    }
+    for (int r = n_rel; r < 3; r++) a.rel[r] = rel[0];
+    a.n_rel = n_rel, a.R = R, a.P = P, a.kc = (kmax + 3) & ~3, a.p_rs = p_rs, a.p = p;
+    return 0;
+}
+
+int dhgn_att_agg3_fwd(const mo_att_rel *rel, int32_t R, int32_t P, int32_t E, const float *p, int64_t p_rs, float *out, int64_t out_stride,
+                      void *stream) {
+    AaArgs a;
+    if (att_args(rel, 3, R, P, E, p, p_rs, a) || !out || ((uintptr_t)out & 15) || out_stride < 3 * AA_E || (out_stride & 3)) return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_att_agg_fwd(a, out, out_stride, (hipStream_t)stream);
+}
+
+int64_t dhgn_att_agg_bwd_workspace(int32_t E, int32_t din) {
+    return E == AA_E && (din == 4 || din == 8) ? (int64_t)AA_MAX_GRID * 128 * (din + 2) * 4 : 0;
+}
+
+int dhgn_att_agg_bwd(int32_t R, int32_t P, int32_t K, int32_t E, int32_t din, const float *p, int64_t p_rs, const float *q, int64_t q_rs,
+                     int32_t q_div, const float *e, int64_t e_rs, const void *adj, int64_t adj_rs, int32_t adj_mode, const int32_t *kvalid,
+                     const float *W, const float *b, const float *alpha, const float *gout, int64_t gout_stride, float *dW, float *db,
+                     float *d_alpha, void *workspace, void *stream) {
+    const mo_att_rel rel = {K, din, q_div, adj_mode, q, q_rs, e, e_rs, adj, adj_rs, kvalid, W, b, alpha};
+    AaArgs a;
+    if (att_args(&rel, 1, R, P, E, p, p_rs, a) || !gout || ((uintptr_t)gout & 7) || gout_stride < AA_E || (gout_stride & 1) || !dW || !db || !d_alpha ||
+        !workspace || ((uintptr_t)dW & 3) || ((uintptr_t)db & 3) || ((uintptr_t)d_alpha & 3) || ((uintptr_t)workspace & 15))
+        return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_att_agg_bwd(a, gout, gout_stride, dW, db, d_alpha, (float *)workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@ Mirrors (reference paths) DHGN/mappo_parallel.py:116-387 `DHGN`, :390-474 `Share
   `torch.manual_seed` yields bit-identical initial weights.
 * forward is written on whole tensors (rows = environments or environment-steps) instead of the reference's
   DataLoader(batch_size=1) plumbing, and the relation message + mean aggregation runs in the fused HIP op
-  `ops.msg_agg` (csrc/mappo_ops.hip).  Only the working aggregator ('mean') exists.
+  `ops.msg_agg` (csrc/mappo_ops.hip).  The reference's only working aggregator is 'mean' (SURVEY Q14); `vertex_level_aggregator:
+  att` is ours, a softmax over the listed neighbours in the fused HIP op `ops.att_agg3` (csrc/att_agg.hpp).
 """
 import torch
 import torch.nn as nn
@@ -45,9 +46,13 @@ def _make_linear(n_in, n_out, is_sn, cls=nn.Linear):
 class DHGN(nn.Module):
     def __init__(self, input_dim, embedding_dim, is_sn, algo_config, device=None):
         super().__init__()
-        for key in ("vertex_level_aggregator", "fcra_aggregator"):
-            if getattr(algo_config, key) != "mean":
-                raise NotImplementedError(f"{key}={getattr(algo_config, key)!r}: only 'mean' works in the reference too")
+        if algo_config.fcra_aggregator != "mean":
+            raise NotImplementedError(f"fcra_aggregator={algo_config.fcra_aggregator!r}: only 'mean' works in the reference too")
+        self.att = algo_config.vertex_level_aggregator == "att"      # ours (ops.att_agg3): the reference's branch never ran
+        if not self.att and algo_config.vertex_level_aggregator != "mean":
+            raise NotImplementedError(f"vertex_level_aggregator={algo_config.vertex_level_aggregator!r}: 'mean' or 'att'")
+        if self.att and embedding_dim != 128:
+            raise ValueError(f"vertex_level_aggregator='att' needs embedding_dim=128 (got {embedding_dim}): the attention kernels exist for that width only")
         self.ReLU = nn.ReLU()
         self.MSG_layers = nn.ModuleList()
         self.AGG_layers = nn.ModuleDict()
@@ -67,6 +72,16 @@ class DHGN(nn.Module):
         self.AGG_layers["AGG_vertex_0"] = _make_linear(E, E, is_sn)  # shared by the three relations (:151-152, :278)
         for k in range(self.depth):
             self.AGG_layers[f"AGG_fcra_{k}"] = _make_linear(E, E, is_sn)
+        if self.att:   # last, and without a draw: every other parameter is what the same seed gives the 'mean' model, which 'att' starts as
+            self.alpha = nn.ParameterDict({f"AGG_vertex_{r}": nn.Parameter(torch.zeros(E, 1)) for r in range(self.num_relation)})
+
+    def _messages(self, p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid=None, q_div=1, e_ref=None):
+        """the three relation aggregates (R, P, 3, E) under the configured vertex-level aggregator"""
+        M = self.MSG_layers
+        args = (p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias)
+        if self.att:
+            return ops.att_agg3(*args, [self.alpha[f"AGG_vertex_{r}"] for r in range(3)], is_critic, o_kvalid, q_div, e_ref)
+        return ops.msg_agg3(*args, is_critic, o_kvalid, q_div, e_ref)
 
     # -- encoder (:241-304) ----------------------------------------------------------------------------
     def encoder(self, p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid=None, q_div=1, out=None, e_ref=None):
@@ -75,9 +90,7 @@ class DHGN(nn.Module):
         over the first o_kvalid[row] (real) obstacles, in training over all padded slots.
         env_n2n: e (R,K_e,4) with several evaders and e_ref (R,4) the one the defender relation's p_i - e term reads (None: e
         itself, K_e = 1); O = 0 is an empty obstacle relation."""
-        M = self.MSG_layers
-        m3 = ops.msg_agg3(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
-                          is_critic, o_kvalid, q_div, e_ref)                           # (R, P, 3, E)
+        m3 = self._messages(p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid, q_div, e_ref)   # (R, P, 3, E)
         return self._after_messages(p, m3, out)
 
     def _after_messages(self, p, m3, out=None):
@@ -113,8 +126,11 @@ class DHGN(nn.Module):
         """the update's encoder of actor and critic together -> (h0_actor, h0_critic): one message pass for both networks
         (ops.msg_agg3_pair_train), then the layers per network; same numbers as encoder(.., False) and encoder(.., True)."""
         M = self.MSG_layers
-        m3a, m3c = ops.msg_agg3_pair_train(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
-                                           q_div, e_ref)
+        if self.att:   # no shared pass under the softmax: one launch per network
+            m3a, m3c = [self._messages(p, e, o, adj_p, adj_e, adj_o, c, None, q_div, e_ref) for c in (False, True)]
+        else:
+            m3a, m3c = ops.msg_agg3_pair_train(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
+                                               q_div, e_ref)
         return self._after_messages(p, m3a), self._after_messages(p, m3c)
 
     # -- fixed-depth recursive aggregation over neighbours' historical embeddings (:204-233) --------------
@@ -161,10 +177,15 @@ class DHGN(nn.Module):
         else:
             h0 = out if out is not None else torch.empty((2, R, P, E), dtype=p.dtype, device=p.device)
         h0_2d = ops.block2d(h0)
-        fused_pos = ind == 4
-        # the message launch also leaves the semantic layer's position part (the same for both networks) in h0
-        m3 = ops.msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
-                               o_kvalid, q_div, pos=(Ws[:, :ind], self.semantic_layer.bias, h0) if fused_pos else None, e_ref=e_ref)   # (2, R, P, 3, E)
+        fused_pos = ind == 4 and not self.att
+        if self.att:   # one launch per network (the weights differ per neighbour, so the messages are not summed once for both)
+            with torch.no_grad():
+                m3 = torch.stack([self._messages(p, e, o, adj_p, adj_e, adj_o, False, None, q_div, e_ref),
+                                  self._messages(p, e, o, adj_p, adj_e, adj_o, True, o_kvalid, q_div, e_ref)])
+        else:
+            # the message launch also leaves the semantic layer's position part (the same for both networks) in h0
+            m3 = ops.msg_agg3_pair(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
+                                   o_kvalid, q_div, pos=(Ws[:, :ind], self.semantic_layer.bias, h0) if fused_pos else None, e_ref=e_ref)   # (2, R, P, 3, E)
         agg0 = self.AGG_layers["AGG_vertex_0"]
         m3_s, Wse = m3.view(2 * R * P, 3 * E), Ws[:, ind:]
         if fused_pos and ops.encoder_tail_ok(m3_s, agg0.weight, agg0.bias, Wse, h0_2d):

@@ -24,7 +24,7 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "bc_loss_gauss_fwd_bwd", "bc_loss_gauss_ex_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "ppo_bc_loss_workspace",
            "ppo_bc_loss_gauss_fwd_bwd", "ppo_bc_loss_cat_fwd_bwd", "team_comm_mask", "team_attention_fwd", "team_attention_bwd",
            "team_comm_mask_host", "team_attention_fwd_host", "team_attention_bwd_host", "gnn_pair_agg_fwd", "gnn_pair_agg_bwd",
-           "gnn_pair_agg_bwd_workspace", "mappo_ops_error_string")
+           "gnn_pair_agg_bwd_workspace", "dhgn_att_agg3_fwd", "dhgn_att_agg_bwd", "dhgn_att_agg_bwd_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -159,6 +159,10 @@ def load_library():
         L.gnn_pair_agg_bwd_workspace.argtypes = [i64, i32]
         L.gnn_pair_agg_bwd_workspace.restype = i64
         L.gnn_pair_agg_bwd.argtypes = [i64, i32, i32, i32, i32, i32] + [vp] * 6 + [i32] + [vp] * 11
+        L.dhgn_att_agg3_fwd.argtypes = [vp, i32, i32, i32, vp, i64, vp, i64, vp]
+        L.dhgn_att_agg_bwd_workspace.argtypes = [i32, i32]
+        L.dhgn_att_agg_bwd_workspace.restype = i64
+        L.dhgn_att_agg_bwd.argtypes = [i32, i32, i32, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32] + [vp] * 5 + [i64] + [vp] * 5
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
         _lib = L
@@ -590,6 +594,152 @@ def msg_agg3(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, is_critic, o_
         mode_o = ADJ_BITS
     return _MsgAgg3.apply(p, e, o, adj_p, adj_e, adj_o, o_kvalid if mode_o == ADJ_VALID else None, W0, b0, W1, b1, W2, b2, mode,
                           mode_o, q_div, e_ref)
+
+
+class AttRel(C.Structure):
+    """include/mappo_ops.h mo_att_rel: mo_msg_rel's fields plus alpha"""
+    _fields_ = MsgRel._fields_ + [("alpha", C.c_void_p)]
+
+
+att_agg_calls = 0     # forward launches of the fused attention aggregator so far (tests)
+ATT_CHUNK_ENTRIES = 1 << 24   # (rows, P, K, E) entries the torch formula materialises at once
+
+
+def att_agg_formula(p, q, e, a, W, b, alpha, q_div=1):
+    """One relation of the attention aggregator in plain torch, row-chunked (the specification of csrc/att_agg.hpp: CPU and float64
+    operands, and the yardstick of tools/bench_att_agg.py).  p (R,P,4), q (R/q_div,K,4), e (R,4)|None, a (R,P,K) -> (R,P,E)."""
+    R, P, K, E = p.shape[0], p.shape[1], q.shape[1], W.shape[0]
+    if K == 0 or R == 0:
+        return (W.sum() + b.sum() + alpha.sum()) * 0 + p.new_zeros(R, P, E)
+    step = max(1, ATT_CHUNK_ENTRIES // (P * K * E)) * q_div
+    outs = []
+    for r0 in range(0, R, step):
+        pc, ac = p[r0:r0 + step], a[r0:r0 + step]
+        x = pc[:, :, None] - q[r0 // q_div:(r0 + step) // q_div].repeat_interleave(q_div, 0)[:, None]
+        if e is not None:
+            x = torch.cat((x, (pc - e[r0:r0 + step, None])[:, :, None].expand_as(x)), -1)
+        m = torch.relu(F.linear(x, W, b))                                              # (n, P, K, E)
+        s = (m @ alpha).masked_fill(ac == 0, float("-inf"))
+        u = ac * torch.exp(s - s.amax(-1, keepdim=True).clamp_min(-3e38)).masked_fill(ac == 0, 0.0)
+        den = u.abs().sum(-1, keepdim=True)
+        outs.append((u[..., None] * m).sum(2) / torch.where(den > 0, den, torch.ones_like(den)))      # nothing listed: exact zeros
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+
+def _att_sources(p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid, q_div, e_ref):
+    """msg_agg3's mode selection -> ((q, e, adj, kvalid, mode, q_div) per relation)"""
+    mode = ADJ_ONES if is_critic else ADJ_TENSOR
+    mode_o = ADJ_VALID if (is_critic and o_kvalid is not None) else mode
+    if mode_o == ADJ_TENSOR and adj_o.dtype == torch.int32:
+        mode_o = ADJ_BITS
+    return ((p, _e_slot(e, e_ref, p.shape[0]), adj_p, None, mode, 1), (e, None, adj_e, None, mode, 1),
+            (o, None, adj_o, o_kvalid if mode_o == ADJ_VALID else None, mode_o, q_div))
+
+
+def _att_dense_adj(R, P, K, adj, kv, mode, q_div, like):
+    """the (R, P, K) weights an adjacency source stands for (the torch formula's operand)"""
+    if mode == ADJ_TENSOR:
+        return adj.to(like.dtype)
+    if mode == ADJ_BITS:
+        return unpack_adj_bits(adj, K).to(like.dtype)
+    if mode == ADJ_ONES:
+        return like.new_ones(R, P, K)
+    live = torch.arange(K, device=like.device)[None, :] < kv.repeat_interleave(q_div)[:, None]
+    return live.to(like.dtype)[:, None, :].expand(R, P, K)
+
+
+def _att_operand(t):
+    """rows as the kernels read them: dense, 16-byte aligned"""
+    return t if (t.is_contiguous() and t.data_ptr() % 16 == 0) else _dense16(t)
+
+
+def _att_workspace(device, din):
+    key = (device, "att", din, torch.cuda.current_stream().cuda_stream)
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.empty(load_library().dhgn_att_agg_bwd_workspace(128, din), dtype=torch.uint8, device=device)
+    return ws
+
+
+class _AttAgg3(torch.autograd.Function):
+    """The three relations under the attention aggregator in one node writing one (R, P, 3, E) tensor: one launch forward, one per
+    relation backward (gradients to W, b, alpha; nothing saved but the operands)."""
+
+    @staticmethod
+    def forward(ctx, p, srcs, *prm):
+        global att_agg_calls
+        L = load_library()
+        R, P = p.shape[0], p.shape[1]
+        E = prm[0].shape[0]
+        prm = [_dense16(t.detach()) for t in prm]          # W0, b0, alpha0, W1, ..
+        p = _att_operand(p)
+        rels, arr = [], (AttRel * 3)()
+        for r, (q, e, adj, kv, mode, qd) in enumerate(srcs):
+            q, e = _att_operand(q), (None if e is None else _att_operand(e))
+            adj = adj.contiguous() if mode in (ADJ_TENSOR, ADJ_BITS) else None
+            K, (W, b, al) = q.shape[1], prm[3 * r:3 * r + 3]
+            assert q.shape == (R // qd, K, 4) and R % qd == 0 and W.shape == (E, 8 if e is not None else 4) and al.shape == (E,)
+            if adj is not None:
+                assert adj.shape == (R, P, K if mode == ADJ_TENSOR else adj_row_words(K)) and adj.dtype == (torch.float32 if mode == ADJ_TENSOR else torch.int32)
+            if mode == ADJ_VALID:
+                assert kv.dtype == torch.int32 and kv.is_contiguous() and kv.shape[0] * qd == R
+            m = arr[r]
+            m.K, m.din, m.q_div, m.adj_mode = K, W.shape[1], qd, mode
+            m.q, m.q_rs = q.data_ptr(), 4 * K
+            if e is not None:
+                m.e, m.e_rs = e.data_ptr(), 4
+            if adj is not None:
+                m.adj, m.adj_rs = adj.data_ptr(), adj.shape[1] * adj.shape[2]
+            if mode == ADJ_VALID:
+                m.kvalid = kv.data_ptr()
+            m.W, m.b, m.alpha = W.data_ptr(), b.data_ptr(), al.data_ptr()
+            rels.append((q, e, adj, kv if mode == ADJ_VALID else None, mode, qd))
+        out = torch.empty((R, P, 3, E), dtype=torch.float32, device=p.device)
+        _check(L.dhgn_att_agg3_fwd(C.cast(arr, C.c_void_p), R, P, E, _ptr(p), 4 * P, _ptr(out), 3 * E, _stream()), "dhgn_att_agg3_fwd")
+        att_agg_calls += 1
+        ctx.rels = [(mode, qd, [t is not None for t in (e, adj, kv)]) for (q, e, adj, kv, mode, qd) in rels]
+        ctx.save_for_backward(p, *prm, *[t for rel in rels for t in rel[:4] if t is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        L = load_library()
+        saved = list(ctx.saved_tensors)
+        p, prm, rest = saved[0], saved[1:10], saved[10:]
+        R, P = p.shape[0], p.shape[1]
+        E = prm[0].shape[0]
+        gout = _dense16(gout)
+        grads = []
+        for r, (mode, qd, has) in enumerate(ctx.rels):
+            q = rest.pop(0)
+            e, adj, kv = [rest.pop(0) if h else None for h in has]
+            W, b, al = prm[3 * r:3 * r + 3]
+            K, din = q.shape[1], W.shape[1]
+            dW, db, dal = torch.empty_like(W), torch.empty_like(b), torch.empty_like(al)
+            _check(L.dhgn_att_agg_bwd(R, P, K, E, din, _ptr(p), 4 * P, _ptr(q), 4 * K, qd, _ptr(e), 4 if e is not None else 0, _ptr(adj),
+                                      adj.shape[1] * adj.shape[2] if adj is not None else 0, mode, _ptr(kv), _ptr(W), _ptr(b), _ptr(al),
+                                      C.c_void_p(gout.data_ptr() + 4 * r * E), 3 * E, _ptr(dW), _ptr(db), _ptr(dal), _ptr(_att_workspace(p.device, din)),
+                                      _stream()), "dhgn_att_agg_bwd")
+            grads += [dW, db, dal]
+        return (None, None) + tuple(grads)
+
+
+def att_agg3(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, alphas, is_critic, o_kvalid=None, q_div=1, e_ref=None):
+    """(R, P, 3, E): msg_agg3 with a softmax over the listed neighbours in place of the mean (`vertex_level_aggregator: att`):
+    out_i = sum_j u_ij m_ij / sum_j |u_ij|, u_ij = a_ij exp(alpha . m_ij - max).  alphas: three (E,) or (E, 1) vectors; operands and
+    mode selection as msg_agg3.  fp32 CUDA operands take the fused kernels (csrc/att_agg.hpp, E = 128 only -- any other width is an
+    error there); CPU and float64 operands are evaluated by att_agg_formula."""
+    srcs = _att_sources(p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid, q_div, e_ref)
+    als = [al.reshape(-1) for al in alphas]
+    Ws, bs = (W0, W1, W2), (b0, b1, b2)
+    if p.is_cuda and p.dtype == torch.float32:
+        if W0.shape[0] != 128:
+            raise RuntimeError(f"att_agg3: the attention kernels exist for embedding_dim 128 only (got {W0.shape[0]})")
+        return _AttAgg3.apply(p, srcs, *[t for r in range(3) for t in (Ws[r], bs[r], als[r])])
+    R, P = p.shape[0], p.shape[1]
+    outs = [att_agg_formula(p, q, ee, _att_dense_adj(R, P, q.shape[1], adj, kv, mode, qd, p), Ws[r], bs[r], als[r], qd)
+            for r, (q, ee, adj, kv, mode, qd) in enumerate(srcs)]
+    return torch.stack(outs, 2)
 
 
 def gae_advnorm(r, v, active, gamma, lamda, use_adv_norm=True):

@@ -130,6 +130,39 @@ int dhgn_msg_agg_ones_sorted_bwd(int32_t R, int32_t P, int32_t K, int32_t E, con
                                  void *partials, void *stream);
 
 /*
+ * The vertex-level ATTENTION aggregator (`algo.vertex_level_aggregator: att`; csrc/att_agg.hpp) -- ours: the reference's `att`
+ * branch never ran.  Messages as in dhgn_msg_agg_fwd, m_ij = ReLU(W [p_i - q_j, p_i - e] + b); instead of the mean,
+ *   s_ij = alpha . m_ij;  over the listed j (a_ij != 0):  M_i = max_j s_ij,  u_ij = a_ij exp(s_ij - M_i),
+ *   out_i = sum_j u_ij m_ij / sum_j |u_ij|          nothing listed: exact zeros;  alpha = 0: the numbers of dhgn_msg_agg_fwd.
+ * Arguments, row strides, q_div, kvalid and the four adjacency sources mean what they mean for dhgn_msg_agg_*; alpha [E] per relation.
+ * E == 128 only, 1 <= P <= 64, 0 <= K <= 1024 per relation, R a multiple of every q_div; p, q, e, W, out 16-byte aligned with row
+ * strides that are multiples of 4.  Anything else, a NULL or a misaligned pointer: MO_ERR_BAD_ARG before any launch or write.
+ * R == 0 succeeds and writes nothing; K == 0 writes zeros (forward) and exact-zero gradients (backward).
+ * dhgn_att_agg3_fwd: the three relations of one network in one launch, relation r into slot r of out [R][P][3][E] (out_stride >= 3 E,
+ * a multiple of 4).  One segment = one (relation, row, agent), one wave each; a segment's bits depend on its own inputs only.
+ * dhgn_att_agg_bwd: one relation; gradients to W, b, alpha only (states and adjacency are data): dW [E][din], db [E], d_alpha [E]
+ * OVERWRITTEN.  Nothing was saved by the forward: messages and weights are recomputed.  gout [R][P] vectors of E floats gout_stride
+ * (even, >= E) elements apart, 8-byte aligned; workspace: at least dhgn_att_agg_bwd_workspace(E, din) bytes, 16-byte aligned (per-workgroup
+ * partial blocks added in a fixed order: no atomics, the same bits from run to run).
+ */
+typedef struct mo_att_rel {
+    int32_t K, din, q_div, adj_mode;
+    const float *q; int64_t q_rs;       /* [R/q_div][K][4] */
+    const float *e; int64_t e_rs;       /* [R][4] or NULL (din == 4) */
+    const void *adj; int64_t adj_rs;    /* MO_ADJ_TENSOR: float [R][P][K]; MO_ADJ_BITS: packed words; else NULL */
+    const int32_t *kvalid;              /* MO_ADJ_VALID: [R/q_div] */
+    const float *W, *b;                 /* [E][din], [E] */
+    const float *alpha;                 /* [E] */
+} mo_att_rel;
+int dhgn_att_agg3_fwd(const mo_att_rel *rel /* [3] */, int32_t R, int32_t P, int32_t E, const float *p, int64_t p_row_stride, float *out,
+                      int64_t out_stride, void *stream);
+int64_t dhgn_att_agg_bwd_workspace(int32_t E, int32_t din);
+int dhgn_att_agg_bwd(int32_t R, int32_t P, int32_t K, int32_t E, int32_t din, const float *p, int64_t p_row_stride, const float *q,
+                     int64_t q_row_stride, int32_t q_div, const float *e, int64_t e_row_stride, const void *adj, int64_t adj_row_stride,
+                     int32_t adj_mode, const int32_t *kvalid, const float *W, const float *b, const float *alpha, const float *gout,
+                     int64_t gout_stride, float *dW, float *db, float *d_alpha, void *workspace, void *stream);
+
+/*
  * GAE reverse scan + value target + advantage normalisation (DHGN/mappo_parallel.py:643-658):
  *   delta = (r + gamma v[:,1:] - v[:,:-1]) * active ; gae_t = delta_t + gamma lamda gae_{t+1}
  *   v_target = adv + v[:,:-1] ; if use_adv_norm: adv = (adv - mean) / (std_unbiased + 1e-5) * active
