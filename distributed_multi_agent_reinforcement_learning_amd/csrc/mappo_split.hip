@@ -12,6 +12,7 @@
 #include "sb_gru_seq.hpp"
 #include "gnn_pairs.hpp"
 #include "att_agg.hpp"
+#include "fcra_att.hpp"
 
 extern "C" {
 
@@ -233,6 +234,46 @@ int dhgn_att_agg_bwd(int32_t R, int32_t P, int32_t K, int32_t E, int32_t din, co
         return MO_ERR_BAD_ARG;
     if (R == 0) return 0;
     return launch_att_agg_bwd(a, gout, gout_stride, dW, db, d_alpha, (float *)workspace, (hipStream_t)stream);
+}
+
+// alignment of the vectors the lanes read and write as float2
+static bool fa_ok8(const void *p) { return p && !((uintptr_t)p & 7); }
+
+int fcra_att_fwd_multi(int32_t n_jobs, const mo_fcra_att_job *jobs, int64_t R, int32_t P, int32_t E, const float *adj, int64_t adj_row_stride,
+                       int64_t out_stride, int32_t max_blocks, void *stream) {
+    if (n_jobs < 1 || n_jobs > MO_FCRA_ATT_MAX_JOBS || !jobs || R < 0 || P < 1 || P > FA_MAX_P || E != FA_E || out_stride < FA_E || (out_stride & 1) ||
+        max_blocks < 0 || ((uintptr_t)adj & 3) || (adj && adj_row_stride < (int64_t)P * P))
+        return MO_ERR_BAD_ARG;
+    FaJobs a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < n_jobs; k++) {
+        const mo_fcra_att_job &m = jobs[k];
+        if (!fa_ok8(m.bias) || !fa_ok8(m.alpha) || (!m.out_actor && !m.out_critic)) return MO_ERR_BAD_ARG;
+        if (m.out_actor && (!adj || !fa_ok8(m.out_actor) || !fa_ok8(m.y_actor))) return MO_ERR_BAD_ARG;
+        if (m.out_critic && (!fa_ok8(m.out_critic) || !fa_ok8(m.y_critic))) return MO_ERR_BAD_ARG;
+        a.j[k] = m;
+    }
+    if (R == 0) return 0;
+    return launch_fcra_att_fwd(a, n_jobs, R, P, adj, adj_row_stride, out_stride, max_blocks, (hipStream_t)stream);
+}
+
+int64_t fcra_att_bwd_workspace(int32_t E, int32_t max_blocks) {
+    if (E != FA_E || max_blocks < 0) return 0;
+    return (int64_t)(max_blocks > 0 && max_blocks < FA_MAX_GRID ? max_blocks : FA_MAX_GRID) * 2 * FA_E * 4;
+}
+
+int fcra_att_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *adj, int64_t adj_row_stride, const float *bias, const float *alpha,
+                 const float *out, int64_t out_stride, const float *g, int64_t g_stride, float *dy, float *db, float *d_alpha, void *workspace,
+                 int32_t max_blocks, void *stream) {
+    if (R < 0 || P < 1 || P > FA_MAX_P || E != FA_E || out_stride < FA_E || (out_stride & 1) || g_stride < FA_E || (g_stride & 1) || max_blocks < 0 ||
+        ((uintptr_t)adj & 3) || (adj && adj_row_stride < (int64_t)P * P))
+        return MO_ERR_BAD_ARG;
+    if (!fa_ok8(y) || !fa_ok8(bias) || !fa_ok8(alpha) || !fa_ok8(out) || !fa_ok8(g) || !fa_ok8(dy) || !db || !d_alpha || !workspace ||
+        ((uintptr_t)db & 3) || ((uintptr_t)d_alpha & 3) || ((uintptr_t)workspace & 15))
+        return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_fcra_att_bwd(R, P, y, adj, adj_row_stride, bias, alpha, out, out_stride, g, g_stride, dy, db, d_alpha, (float *)workspace, max_blocks,
+                               (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,8 @@ Mirrors (reference paths) DHGN/mappo_parallel.py:116-387 `DHGN`, :390-474 `Share
 * forward is written on whole tensors (rows = environments or environment-steps) instead of the reference's
   DataLoader(batch_size=1) plumbing, and the relation message + mean aggregation runs in the fused HIP op
   `ops.msg_agg` (csrc/mappo_ops.hip).  The reference's only working aggregator is 'mean' (SURVEY Q14); `vertex_level_aggregator:
-  att` is ours, a softmax over the listed neighbours in the fused HIP op `ops.att_agg3` (csrc/att_agg.hpp).
+  att` is ours, a softmax over the listed neighbours in the fused HIP op `ops.att_agg3` (csrc/att_agg.hpp), and so is
+  `fcra_aggregator: att`, a softmax over the team-mates' stored embeddings in every FCRA hop (`ops.fcra_att`, csrc/fcra_att.hpp).
 """
 import torch
 import torch.nn as nn
@@ -46,8 +47,11 @@ def _make_linear(n_in, n_out, is_sn, cls=nn.Linear):
 class DHGN(nn.Module):
     def __init__(self, input_dim, embedding_dim, is_sn, algo_config, device=None):
         super().__init__()
-        if algo_config.fcra_aggregator != "mean":
-            raise NotImplementedError(f"fcra_aggregator={algo_config.fcra_aggregator!r}: only 'mean' works in the reference too")
+        self.fcra_att = algo_config.fcra_aggregator == "att"         # ours (ops.fcra_att)
+        if not self.fcra_att and algo_config.fcra_aggregator != "mean":
+            raise NotImplementedError(f"fcra_aggregator={algo_config.fcra_aggregator!r}: 'mean' or 'att'")
+        if self.fcra_att and embedding_dim != 128:
+            raise ValueError(f"fcra_aggregator='att' needs embedding_dim=128 (got {embedding_dim}): the attention kernels exist for that width only")
         self.att = algo_config.vertex_level_aggregator == "att"      # ours (ops.att_agg3): the reference's branch never ran
         if not self.att and algo_config.vertex_level_aggregator != "mean":
             raise NotImplementedError(f"vertex_level_aggregator={algo_config.vertex_level_aggregator!r}: 'mean' or 'att'")
@@ -74,6 +78,11 @@ class DHGN(nn.Module):
             self.AGG_layers[f"AGG_fcra_{k}"] = _make_linear(E, E, is_sn)
         if self.att:   # last, and without a draw: every other parameter is what the same seed gives the 'mean' model, which 'att' starts as
             self.alpha = nn.ParameterDict({f"AGG_vertex_{r}": nn.Parameter(torch.zeros(E, 1)) for r in range(self.num_relation)})
+        if self.fcra_att:   # after the vertex alphas, without a draw either
+            if not self.att:
+                self.alpha = nn.ParameterDict()
+            for k in range(self.depth):
+                self.alpha[f"AGG_fcra_{k}"] = nn.Parameter(torch.zeros(E, 1))
 
     def _messages(self, p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid=None, q_div=1, e_ref=None):
         """the three relation aggregates (R, P, 3, E) under the configured vertex-level aggregator"""
@@ -142,8 +151,16 @@ class DHGN(nn.Module):
         for k in range(self.depth):
             aggk, fk = self.AGG_layers[f"AGG_fcra_{k}"], self.FCRA_layers[k]
             # matmul(normalize(adj or ones, p=1), hist[k]): one pass, the history slice read in place (hist is stored data)
-            nb = ops.fcra_mean(z_critic=hist[k]) if is_critic else ops.fcra_mean(z_actor=hist[k], adj=adj_p)
             last = k == self.depth - 1
+            if self.fcra_att:
+                # the softmax over the team-mates' embeddings of tick t-1-k: y = hist W^T is ops.linear's (its backward produces dW; a
+                # strided history slice is copied dense for it, one pass over R P E floats per hop), the attention kernel writes the left
+                # half of the hop's operand (ops.fcra_hop_att)
+                y = ops.linear(hist[k], aggk.weight)
+                h, carry = ops.fcra_hop_att(y, None if is_critic else adj_p, aggk.bias, self.alpha[f"AGG_fcra_{k}"], h, carry, fk.weight, fk.bias,
+                                            last, out if last else None)
+                continue
+            nb = ops.fcra_mean(z_critic=hist[k]) if is_critic else ops.fcra_mean(z_actor=hist[k], adj=adj_p)
             # FCRA_k([relu(AGG_k(nb)) | h]) as one K = 2E GEMM whose operand halves are written in place by their producers
             # (ops.fcra_hop); the last hop of a rollout lands in the static storage
             # (each hop's output feeds the next hop only: `carry` hands its operand buffer and its relu' to that hop)
@@ -226,7 +243,14 @@ class DHGN(nn.Module):
             za = lin(hist_a[k])
             zcs.append(za if hist_c[k] is hist_a[k] or hist_c[k].data_ptr() == hist_a[k].data_ptr() else lin(hist_c[k]))
             zas.append(za)
-        if d <= 4 and all(z.is_contiguous() for z in zas + zcs) and adj_p.dtype == torch.float32:
+        if self.fcra_att:   # the d softmaxes of both networks in ONE launch (a hop whose history is shared scores once)
+            adj_f = adj_p if adj_p.dtype == torch.float32 else adj_p.float()
+            for k0 in range(0, d, ops.FCRA_ATT_MAX_JOBS):
+                ks = range(k0, min(d, k0 + ops.FCRA_ATT_MAX_JOBS))
+                ops.fcra_att_pair_multi([zas[k].contiguous() for k in ks], [zcs[k].contiguous() for k in ks], adj_f,
+                                        [self.AGG_layers[f"AGG_fcra_{k}"].bias for k in ks], [self.alpha[f"AGG_fcra_{k}"] for k in ks],
+                                        [cats[k][..., :E] for k in ks])
+        elif d <= 4 and all(z.is_contiguous() for z in zas + zcs) and adj_p.dtype == torch.float32:
             ops.fcra_mean_pair_multi(zas, zcs, adj_p, [self.AGG_layers[f"AGG_fcra_{k}"].bias for k in range(d)], [cats[k][..., :E] for k in range(d)])
         else:
             for k in range(d):

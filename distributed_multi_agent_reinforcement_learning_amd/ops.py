@@ -24,7 +24,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "bc_loss_gauss_fwd_bwd", "bc_loss_gauss_ex_fwd_bwd", "bc_loss_cat_fwd_bwd", "e3d_bc_select", "n2n_bc_select", "ppo_bc_loss_workspace",
            "ppo_bc_loss_gauss_fwd_bwd", "ppo_bc_loss_cat_fwd_bwd", "team_comm_mask", "team_attention_fwd", "team_attention_bwd",
            "team_comm_mask_host", "team_attention_fwd_host", "team_attention_bwd_host", "gnn_pair_agg_fwd", "gnn_pair_agg_bwd",
-           "gnn_pair_agg_bwd_workspace", "dhgn_att_agg3_fwd", "dhgn_att_agg_bwd", "dhgn_att_agg_bwd_workspace", "mappo_ops_error_string")
+           "gnn_pair_agg_bwd_workspace", "dhgn_att_agg3_fwd", "dhgn_att_agg_bwd", "dhgn_att_agg_bwd_workspace", "fcra_att_fwd_multi", "fcra_att_bwd",
+           "fcra_att_bwd_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -163,6 +164,10 @@ def load_library():
         L.dhgn_att_agg_bwd_workspace.argtypes = [i32, i32]
         L.dhgn_att_agg_bwd_workspace.restype = i64
         L.dhgn_att_agg_bwd.argtypes = [i32, i32, i32, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32] + [vp] * 5 + [i64] + [vp] * 5
+        L.fcra_att_fwd_multi.argtypes = [i32, vp, i64, i32, i32, vp, i64, i64, i32, vp]
+        L.fcra_att_bwd_workspace.argtypes = [i32, i32]
+        L.fcra_att_bwd_workspace.restype = i64
+        L.fcra_att_bwd.argtypes = [i64, i32, i32, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
         _lib = L
@@ -1093,6 +1098,130 @@ def fcra_mean_pair_multi(zas, zcs, adj, biases, outs):
            "fcra_neighbour_mean_multi")
 
 
+class FcraAttJob(C.Structure):
+    """include/mappo_ops.h mo_fcra_att_job"""
+    _fields_ = [(n, C.c_void_p) for n in ("y_actor", "y_critic", "bias", "alpha", "out_actor", "out_critic")]
+
+
+FCRA_ATT_MAX_JOBS = 8      # include/mappo_ops.h MO_FCRA_ATT_MAX_JOBS
+fcra_att_calls = 0         # forward launches of the FCRA attention aggregator so far (tests)
+
+
+def fcra_att_formula(y, adj, bias, alpha):
+    """The FCRA attention aggregator in plain torch (the specification of csrc/fcra_att.hpp, DESIGN 7u: CPU and float64 operands, the
+    yardstick of tools/bench_fcra_att.py and the model-level reference).  y (.., P, E) = W h (no bias), adj (.., P, P) or None (the
+    critic's ones), bias (E,), alpha (E,) or (E, 1) -> relu(bias + sum_j w_ij y_j) (.., P, E)."""
+    P = y.shape[-2]
+    a = adj.to(y.dtype) if adj is not None else y.new_ones(y.shape[:-2] + (P, P))
+    s = F.leaky_relu(y + bias, 0.01) @ alpha.reshape(-1)                                  # (.., P): one score per neighbour
+    listed = a != 0
+    s = torch.where(listed, s[..., None, :].expand_as(a), torch.full_like(a, float("-inf")))
+    u = torch.where(listed, a * torch.exp(s - s.amax(-1, keepdim=True).clamp_min(-3e38).detach()), torch.zeros_like(a))
+    den = u.abs().sum(-1, keepdim=True)
+    return torch.relu((u / torch.where(den > 0, den, torch.ones_like(den))) @ y + bias)   # nothing listed: relu(bias)
+
+
+def _fcra_att_fwd(jobs, R, P, adj3, out_ld, max_blocks=0):
+    """one launch; jobs: (y_actor, y_critic, bias, alpha, out_actor, out_critic) tensors or None, bias / alpha dense (128,)"""
+    global fcra_att_calls
+    arr = (FcraAttJob * len(jobs))()
+    for a, job in zip(arr, jobs):
+        a.y_actor, a.y_critic, a.bias, a.alpha, a.out_actor, a.out_critic = [None if t is None else t.data_ptr() for t in job]
+    _check(load_library().fcra_att_fwd_multi(len(jobs), C.cast(arr, C.c_void_p), R, P, 128, _ptr(adj3), adj3.stride(0) if adj3 is not None else 0, out_ld,
+                                             max_blocks, _stream()), "fcra_att_fwd_multi")
+    fcra_att_calls += 1
+
+
+def _fcra_att_bwd(y3, adj3, bias, alpha, out, out_ld, g, g_ld, max_blocks=0):
+    """-> dy (R, P, E), db (E,), d_alpha (E,); out / g: tensors whose first element is row 0's, vectors out_ld / g_ld floats apart"""
+    L = load_library()
+    R, P, E = y3.shape
+    dy, db, dal = torch.empty_like(y3), torch.empty_like(bias), torch.empty_like(alpha)
+    key = (y3.device, "fcra_att", max_blocks, torch.cuda.current_stream().cuda_stream)
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.empty(L.fcra_att_bwd_workspace(E, max_blocks), dtype=torch.uint8, device=y3.device)
+    _check(L.fcra_att_bwd(R, P, E, _ptr(y3), _ptr(adj3), adj3.stride(0) if adj3 is not None else 0, _ptr(bias), _ptr(alpha), _ptr(out), out_ld, _ptr(g), g_ld,
+                          _ptr(dy), _ptr(db), _ptr(dal), _ptr(ws), max_blocks, _stream()), "fcra_att_bwd")
+    return dy, db, dal
+
+
+def _fcra_att_operands(y, adj, bias, alpha):
+    """the kernels' views: y (R, P, E) dense, adj (R, P, P) fp32 with dense rows or None, bias / alpha (E,) dense"""
+    P, E = y.shape[-2], y.shape[-1]
+    if E != 128:
+        raise RuntimeError(f"fcra_att: the attention kernels exist for embedding_dim 128 only (got {E})")
+    y3 = _dense16(y.detach()).reshape(-1, P, E)
+    adj3 = None
+    if adj is not None:
+        adj3 = adj.detach().reshape(-1, P, P)
+        if adj3.dtype != torch.float32 or not _rows_ok(adj3):
+            adj3 = adj3.float().contiguous()
+        assert adj3.shape[0] == y3.shape[0]
+    return y3, adj3, _dense16(bias.detach()), _dense16(alpha.detach().reshape(-1))
+
+
+class _FcraAtt(torch.autograd.Function):
+    """fcra_att on the fused kernels: one launch forward; backward one launch + the ordered reduce (dy, db, d_alpha; the forward saved
+    nothing beyond its output)."""
+
+    @staticmethod
+    def forward(ctx, y, adj, bias, alpha, out):
+        y3, adj3, b, al = _fcra_att_operands(y, adj, bias, alpha)
+        R, P, E = y3.shape
+        if out is None:
+            out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+        else:
+            assert out.numel() == y3.numel() and out.shape[-1] == E
+            ctx.mark_dirty(out)
+        ctx.out_ld = _vec_stride(out)   # dense, or the left half of an [agg | h] operand
+        _fcra_att_fwd([(None, y3, b, al, None, out) if adj3 is None else (y3, None, b, al, out, None)], R, P, adj3, ctx.out_ld)
+        ctx.save_for_backward(y3, adj3, b, al)
+        ctx.out, ctx.alpha_shape = out, alpha.shape     # a plain reference: `out` may be a view whose base is written elsewhere
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y3, adj3, b, al = ctx.saved_tensors
+        try:
+            g_ld = _vec_stride(g)
+        except AssertionError:
+            g, g_ld = g.contiguous(), g.shape[-1]
+        dy, db, dal = _fcra_att_bwd(y3, adj3, b, al, ctx.out, ctx.out_ld, g, g_ld)
+        return dy.reshape(g.shape), None, db, dal.reshape(ctx.alpha_shape), None
+
+
+def fcra_att(y, adj, bias, alpha, out=None):
+    """The FCRA hops' attention aggregator (`algo.fcra_aggregator: att`): relu(bias + sum_j w_ij y_j) with w a softmax of
+    the scores alpha . leaky_relu(y_j + bias) over the neighbours adj lists (adj=None: the critic's ones).  y (.., P, E) arrives from
+    ops.linear(hist_k, W) -- whose backward produces dW --, alpha (E,) or (E, 1).  out: storage written in place (dense or the left half
+    of an [agg | h] operand).  fp32 CUDA operands take the fused kernels (csrc/fcra_att.hpp, E = 128 only -- any other width is an
+    error there); CPU and float64 operands are evaluated by fcra_att_formula."""
+    if y.is_cuda and y.dtype == torch.float32:
+        return _FcraAtt.apply(y, adj, bias, alpha, out)
+    res = fcra_att_formula(y, adj, bias, alpha)
+    return res if out is None else out.copy_(res.reshape(out.shape))
+
+
+def fcra_att_pair_multi(zas, zcs, adj, biases, alphas, outs):
+    """fcra_att for actor (adj) and critic (ones) of several hops (za, zc, b, alpha, o) of one shape in ONE launch
+    (fcra_att_fwd_multi): the hops of a rollout tick read stored history, none reads another hop's result; a hop whose za and zc are
+    one tensor (the rollout's shared history) has its scores evaluated once.  za, zc: dense (R, P, E) products hist W^T;
+    o: (2, R, P, E) storage (possibly the left half of an [agg | h] operand).  No autograd."""
+    n = len(zas)
+    assert 1 <= n <= FCRA_ATT_MAX_JOBS and len(zcs) == n and len(biases) == n and len(alphas) == n and len(outs) == n
+    P, E = zas[0].shape[-2], zas[0].shape[-1]
+    R = zas[0].numel() // (P * E)
+    out_ld = _vec_stride(outs[0])
+    jobs = []
+    for za, zc, b, al, o in zip(zas, zcs, biases, alphas, outs):
+        assert za.is_contiguous() and zc.is_contiguous() and za.shape == zas[0].shape and zc.shape == zas[0].shape and _vec_stride(o) == out_ld
+        jobs.append((za, zc, _dense16(b.detach()), _dense16(al.detach().reshape(-1)), o[0], o[1]))
+    adj3 = adj.reshape(R, P, P)
+    assert adj3.dtype == torch.float32 and _rows_ok(adj3) and E == 128
+    _fcra_att_fwd(jobs, R, P, adj3, out_ld)
+
+
 RELU_BWD_MIN_ROWS = 4096
 
 
@@ -1528,6 +1657,80 @@ def fcra_hop(nb, h, carry, Wagg, bagg, Wf, bf, last, out=None):
     box = []
     y = _FcraHop.apply(nb, h, cat, Wagg, bagg, Wf, bf, bool(last), out, box, h_link, cat_bits)
     return y, (box[0], box[1], box[2])
+
+
+class _FcraHopAtt(torch.autograd.Function):
+    """_FcraHop's sibling for `algo.fcra_aggregator: att`:  h' = relu([agg | h] Wf^T + bf),  agg = fcra_att(y, adj, bagg, alpha) with
+    y = hist Wagg^T the caller's ops.linear (its backward produces dWagg from the dy returned here).  No inner AGG GEMM: the attention
+    kernel writes the left half of the [agg | h] operand through its column stride; the FCRA layer, its masked input gradient and
+    its weight gradient are _FcraHop's.  The operand's sign-bit blocks are not kept on this path (the attention kernel writes none):
+    the masked input gradient reads the operand itself."""
+
+    @staticmethod
+    def forward(ctx, y, adj, bagg, alpha, h, cat, Wf, bf, last, out, box, h_link=None):
+        E = Wf.shape[0]
+        rows = h.numel() // E
+        if cat is None:
+            cat = torch.empty((rows, 2 * E), dtype=h.dtype, device=h.device)
+            cat[:, E:].copy_(block2d(h))
+        else:
+            assert cat.shape == (rows, 2 * E) and cat.is_contiguous() and h.data_ptr() == cat.data_ptr() + E * cat.element_size()
+        y3, adj3, b, al = _fcra_att_operands(y, adj, bagg, alpha)
+        assert y3.shape[0] * y3.shape[1] == rows
+        _fcra_att_fwd([(None, y3, b, al, None, cat) if adj3 is None else (y3, None, b, al, cat, None)], y3.shape[0], y3.shape[1], adj3, 2 * E)
+        nxt = None
+        if out is not None:     # rollout: the caller's static storage (no autograd)
+            ctx.mark_dirty(out)
+            dst = block2d(out)
+        elif last:
+            dst = torch.empty((rows, E), dtype=h.dtype, device=h.device)
+        else:
+            nxt = torch.empty((rows, 2 * E), dtype=h.dtype, device=h.device)
+            dst = nxt[:, E:]
+        _hop_gemm(cat, Wf, bf, dst)
+        ctx.save_for_backward(y3, adj3, b, al, Wf)
+        ctx.cat, ctx.y = cat, dst          # plain references, as in _FcraHop
+        ctx.shapes = (y.shape, alpha.shape, h.shape)
+        ctx.h_link, ctx.y_link = h_link, ReluLink()
+        box += [nxt, ctx.y_link]
+        return dst.reshape(h.shape) if out is None else out
+
+    @staticmethod
+    def backward(ctx, g):
+        y3, adj3, b, al, Wf = ctx.saved_tensors
+        cat, y = ctx.cat, ctx.y
+        E = Wf.shape[0]
+        rows = cat.shape[0]
+        try:
+            g2 = block2d(g)
+        except AssertionError:
+            g2 = g.reshape(rows, E).contiguous()
+        if ctx.y_link.db is not None:                  # the consumer masked the gradient and summed its columns (ReluLink)
+            gin, dbf = g2, ctx.y_link.take()
+        else:
+            gin, dbf = relu_bwd_colsum(g2, y)
+        # [d agg | d h]: the left half's relu' is the attention backward's own (it reads the sign of agg; masking twice changes nothing),
+        # the right half's belongs to the previous hop's FCRA layer
+        fused = input_grad_masked(gin, Wf, cat, 2 * E if ctx.h_link is not None else E)
+        if fused is not None:
+            dcat, cs = fused
+            if ctx.h_link is not None and ctx.needs_input_grad[4]:
+                ctx.h_link.db = cs[E:]
+        else:
+            dcat = input_grad(gin, Wf)
+        dy, dbagg, dal = _fcra_att_bwd(y3, adj3, b, al, cat, 2 * E, dcat, dcat.stride(0))
+        dWf = wgrad(gin, cat)
+        y_shape, alpha_shape, h_shape = ctx.shapes
+        return dy.reshape(y_shape), None, dbagg, dal.reshape(alpha_shape), dcat[:, E:].reshape(h_shape), None, dWf, dbf, None, None, None, None
+
+
+def fcra_hop_att(y, adj, bagg, alpha, h, carry, Wf, bf, last, out=None):
+    """-> (h', carry'): fcra_hop under the attention aggregator (see _FcraHopAtt).  y = ops.linear(hist_k, Wagg) (.., P, E), adj (.., P, P)
+    or None (the critic's ones); carry: (the buffer whose right half h is | None, the ReluLink of h | None)."""
+    cat, h_link = carry if carry is not None else (None, None)
+    box = []
+    h2 = _FcraHopAtt.apply(y, adj, bagg, alpha, h, cat, Wf, bf, bool(last), out, box, h_link)
+    return h2, (box[0], box[1])
 
 
 FUSED_CELL_MIN_ROWS = 1024  # single-step batches at least this large take the fused cell kernel

@@ -671,6 +671,31 @@ typedef struct mo_nbr_job { const float *z_actor, *z_critic, *bias; float *out_a
 int fcra_neighbour_mean_multi(int32_t n_jobs, const mo_nbr_job *jobs, int32_t R, int32_t P, int32_t E, int32_t T, int64_t za_episode_stride,
                               int64_t za_step_stride, int64_t zc_episode_stride, int64_t zc_step_stride, const float *adj, int64_t adj_row_stride,
                               int32_t relu, int64_t out_stride, void *stream);
+/*
+ * The ATTENTION aggregator of the FCRA hops (`algo.fcra_aggregator: att`; csrc/fcra_att.hpp) -- ours: the reference's `att`
+ * branch never ran.  One hop, R rows of P agents, E features; y_j = W h_j is the caller's GEMM (no bias), [R][P][E] dense:
+ *   s_j = alpha . leaky_relu(y_j + bias, 0.01);  over the listed j of i (a_ij != 0):  M_i = max_j s_j,  u_ij = a_ij exp(s_j - M_i),
+ *   out_i = relu(bias + sum_j u_ij y_j / sum_j |u_ij|)      nothing listed: relu(bias);  alpha = 0: fcra_neighbour_mean(bias, relu) of y.
+ *   actor (out_actor != NULL): a = adj [R][P][P] (adj_row_stride >= P P elements between rows);  critic (out_critic != NULL): a = ones.
+ * fcra_att_fwd_multi: up to MO_FCRA_ATT_MAX_JOBS jobs (hops) of one shape in ONE launch; own y, bias [E], alpha [E] and outputs per job,
+ * either output may be NULL; a job whose y_actor == y_critic has its scores evaluated once.  out_*: [R][P] vectors of E floats out_stride
+ * (even, >= E) elements apart (2 E: the left half of the [agg | h] operand; the other half is not touched).
+ * fcra_att_bwd: one job, one network (adj NULL: ones).  out: what the forward wrote (read for the sign of pre only), g: d out, both
+ * through their own strides.  dy [R][P][E] dense, db [E], d_alpha [E] OVERWRITTEN; nothing else was saved, s, u, w are recomputed.
+ * workspace: at least fcra_att_bwd_workspace(E, max_blocks) bytes, 16-byte aligned (per-workgroup partial blocks added in a fixed order:
+ * no atomics, the same bits from run to run; a row's bits depend on that row's inputs only).
+ * max_blocks: 0 = the default grid; > 0 caps the workgroups of the launch (four rows in flight each).
+ * E == 128 only, 1 <= P <= 16; y, out, g, dy, bias, alpha 8-byte aligned.  Anything else, a NULL or misaligned pointer, an actor
+ * output without adj, a stride below E: MO_ERR_BAD_ARG before any launch or write.  R == 0 succeeds and writes nothing.
+ */
+#define MO_FCRA_ATT_MAX_JOBS 8
+typedef struct mo_fcra_att_job { const float *y_actor, *y_critic, *bias, *alpha; float *out_actor, *out_critic; } mo_fcra_att_job;
+int fcra_att_fwd_multi(int32_t n_jobs, const mo_fcra_att_job *jobs, int64_t R, int32_t P, int32_t E, const float *adj, int64_t adj_row_stride,
+                       int64_t out_stride, int32_t max_blocks, void *stream);
+int64_t fcra_att_bwd_workspace(int32_t E, int32_t max_blocks);
+int fcra_att_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *adj, int64_t adj_row_stride, const float *bias, const float *alpha,
+                 const float *out, int64_t out_stride, const float *g, int64_t g_stride, float *dy, float *db, float *d_alpha, void *workspace,
+                 int32_t max_blocks, void *stream);
 
 /*
  * ReLU backward and the bias gradient of the Linear in front of it in one pass (autograd: aten::threshold_backward, then
