@@ -69,7 +69,8 @@ __device__ __forceinline__ float aa_wave_sum(float v) {   // a + b == b + a: eve
     return v;
 }
 
-__device__ __forceinline__ float aa_adj(const mo_att_rel &m, int64_t r, int i, int j, int kv) {
+template <class Rel>   // mo_att_rel, or mo_msg_rel (csrc/pool_agg.hpp)
+__device__ __forceinline__ float aa_adj(const Rel &m, int64_t r, int i, int j, int kv) {
     if (m.adj_mode == MO_ADJ_TENSOR) return ((const float *)m.adj)[r * m.adj_rs + (int64_t)i * m.K + j];
     if (m.adj_mode == MO_ADJ_BITS)
         return (float)((((const uint32_t *)m.adj)[r * m.adj_rs + (int64_t)i * MO_ADJ_ROW_WORDS(m.K) + (j >> 5)] >> (j & 31)) & 1u);

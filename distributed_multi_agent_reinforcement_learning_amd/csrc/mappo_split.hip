@@ -13,6 +13,8 @@
 #include "gnn_pairs.hpp"
 #include "att_agg.hpp"
 #include "fcra_att.hpp"
+#include "fcra_pool.hpp"
+#include "pool_agg.hpp"
 
 extern "C" {
 
@@ -184,10 +186,14 @@ int gnn_pair_agg_bwd(int64_t R, int32_t P, int32_t O, int32_t q_div, int32_t mid
     return launch_gnn_pair_bwd(a, d_agg, dW1, db1, dW2, db2, (float *)workspace, (hipStream_t)stream);
 }
 
-// one relation of the attention aggregator as the kernels take it, or not (K = 0: an empty relation, q and adj may be NULL)
-static bool att_rel_ok(const mo_att_rel &m, int32_t R, int32_t P) {
+extern "C++" {   // (templates over the two relation records)
+// one relation of the attention / max-pool aggregator as the kernels take it, or not (K = 0: an empty relation, q and adj may be NULL)
+static bool agg_alpha_ok(const mo_att_rel &m) { return m.alpha && !((uintptr_t)m.alpha & 3); }
+static bool agg_alpha_ok(const mo_msg_rel &) { return true; }
+template <class Rel>
+static bool att_rel_ok(const Rel &m, int32_t R, int32_t P) {
     if (m.K < 0 || m.K > AA_KMAX || (m.din != 4 && m.din != 8) || m.q_div < 1 || R % m.q_div != 0 || m.adj_mode < 0 || m.adj_mode > 3) return false;
-    if (!m.W || !m.b || !m.alpha || ((uintptr_t)m.W & 15) || ((uintptr_t)m.b & 3) || ((uintptr_t)m.alpha & 3)) return false;
+    if (!m.W || !m.b || !agg_alpha_ok(m) || ((uintptr_t)m.W & 15) || ((uintptr_t)m.b & 3)) return false;
     if (m.din == 8 && (!m.e || ((uintptr_t)m.e & 15) || (m.e_rs & 3) || m.e_rs < 4)) return false;
     if (m.adj_mode == MO_ADJ_VALID && (!m.kvalid || ((uintptr_t)m.kvalid & 3))) return false;
     if (m.K == 0) return true;
@@ -198,7 +204,8 @@ static bool att_rel_ok(const mo_att_rel &m, int32_t R, int32_t P) {
 }
 
 // the checks common to both entry points -> 0 and the kernels' argument record, or MO_ERR_BAD_ARG
-static int att_args(const mo_att_rel *rel, int n_rel, int32_t R, int32_t P, int32_t E, const float *p, int64_t p_rs, AaArgs &a) {
+template <class Rel, class Args>
+static int att_args(const Rel *rel, int n_rel, int32_t R, int32_t P, int32_t E, const float *p, int64_t p_rs, Args &a) {
     if (!rel || R < 0 || P < 1 || P > AA_PMAX || E != AA_E || !p || ((uintptr_t)p & 15) || (p_rs & 3) || p_rs < 4 * (int64_t)P) return MO_ERR_BAD_ARG;
     int kmax = 4;
     for (int r = 0; r < n_rel; r++) {
@@ -210,6 +217,7 @@ static int att_args(const mo_att_rel *rel, int n_rel, int32_t R, int32_t P, int3
     a.n_rel = n_rel, a.R = R, a.P = P, a.kc = (kmax + 3) & ~3, a.p_rs = p_rs, a.p = p;
     return 0;
 }
+}  // extern "C++"
 
 int dhgn_att_agg3_fwd(const mo_att_rel *rel, int32_t R, int32_t P, int32_t E, const float *p, int64_t p_rs, float *out, int64_t out_stride,
                       void *stream) {
@@ -234,6 +242,31 @@ int dhgn_att_agg_bwd(int32_t R, int32_t P, int32_t K, int32_t E, int32_t din, co
         return MO_ERR_BAD_ARG;
     if (R == 0) return 0;
     return launch_att_agg_bwd(a, gout, gout_stride, dW, db, d_alpha, (float *)workspace, (hipStream_t)stream);
+}
+
+int dhgn_pool_agg3_fwd(const mo_msg_rel *rel, int32_t R, int32_t P, int32_t E, const float *p, int64_t p_rs, float *out, int64_t out_stride,
+                       void *stream) {
+    PaArgs a;
+    if (att_args(rel, 3, R, P, E, p, p_rs, a) || !out || ((uintptr_t)out & 15) || out_stride < 3 * AA_E || (out_stride & 3)) return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_pool_agg_fwd(a, out, out_stride, (hipStream_t)stream);
+}
+
+int64_t dhgn_pool_agg_bwd_workspace(int32_t E, int32_t din) {
+    return E == AA_E && (din == 4 || din == 8) ? (int64_t)PA_MAX_GRID * 128 * (din + 1) * 4 : 0;
+}
+
+int dhgn_pool_agg_bwd(int32_t R, int32_t P, int32_t K, int32_t E, int32_t din, const float *p, int64_t p_rs, const float *q, int64_t q_rs,
+                      int32_t q_div, const float *e, int64_t e_rs, const void *adj, int64_t adj_rs, int32_t adj_mode, const int32_t *kvalid,
+                      const float *W, const float *b, const float *gout, int64_t gout_stride, float *dW, float *db, void *workspace,
+                      void *stream) {
+    const mo_msg_rel rel = {K, din, q_div, adj_mode, q, q_rs, e, e_rs, adj, adj_rs, kvalid, W, b};
+    PaArgs a;
+    if (att_args(&rel, 1, R, P, E, p, p_rs, a) || !gout || ((uintptr_t)gout & 7) || gout_stride < AA_E || (gout_stride & 1) || !dW || !db ||
+        !workspace || ((uintptr_t)dW & 3) || ((uintptr_t)db & 3) || ((uintptr_t)workspace & 15))
+        return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_pool_agg_bwd(a, gout, gout_stride, dW, db, (float *)workspace, (hipStream_t)stream);
 }
 
 // alignment of the vectors the lanes read and write as float2
@@ -274,6 +307,40 @@ int fcra_att_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *a
     if (R == 0) return 0;
     return launch_fcra_att_bwd(R, P, y, adj, adj_row_stride, bias, alpha, out, out_stride, g, g_stride, dy, db, d_alpha, (float *)workspace, max_blocks,
                                (hipStream_t)stream);
+}
+
+int fcra_pool_fwd_multi(int32_t n_jobs, const mo_fcra_pool_job *jobs, int64_t R, int32_t P, int32_t E, const float *adj, int64_t adj_row_stride,
+                        int64_t out_stride, int32_t max_blocks, void *stream) {
+    if (n_jobs < 1 || n_jobs > MO_FCRA_POOL_MAX_JOBS || !jobs || R < 0 || P < 1 || P > FA_MAX_P || E != FA_E || out_stride < FA_E || (out_stride & 1) ||
+        max_blocks < 0 || ((uintptr_t)adj & 3) || (adj && adj_row_stride < (int64_t)P * P))
+        return MO_ERR_BAD_ARG;
+    FpJobs a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < n_jobs; k++) {
+        const mo_fcra_pool_job &m = jobs[k];
+        if (!fa_ok8(m.bias) || (!m.out_actor && !m.out_critic)) return MO_ERR_BAD_ARG;
+        if (m.out_actor && (!adj || !fa_ok8(m.out_actor) || !fa_ok8(m.y_actor))) return MO_ERR_BAD_ARG;
+        if (m.out_critic && (!fa_ok8(m.out_critic) || !fa_ok8(m.y_critic))) return MO_ERR_BAD_ARG;
+        a.j[k] = m;
+    }
+    if (R == 0) return 0;
+    return launch_fcra_pool_fwd(a, n_jobs, R, P, adj, adj_row_stride, out_stride, max_blocks, (hipStream_t)stream);
+}
+
+int64_t fcra_pool_bwd_workspace(int32_t E, int32_t max_blocks) {
+    if (E != FA_E || max_blocks < 0) return 0;
+    return (int64_t)(max_blocks > 0 && max_blocks < FA_MAX_GRID ? max_blocks : FA_MAX_GRID) * FA_E * 4;
+}
+
+int fcra_pool_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *adj, int64_t adj_row_stride, const float *out, int64_t out_stride,
+                  const float *g, int64_t g_stride, float *dy, float *db, void *workspace, int32_t max_blocks, void *stream) {
+    if (R < 0 || P < 1 || P > FA_MAX_P || E != FA_E || out_stride < FA_E || (out_stride & 1) || g_stride < FA_E || (g_stride & 1) || max_blocks < 0 ||
+        ((uintptr_t)adj & 3) || (adj && adj_row_stride < (int64_t)P * P))
+        return MO_ERR_BAD_ARG;
+    if (!fa_ok8(y) || !fa_ok8(out) || !fa_ok8(g) || !fa_ok8(dy) || !db || !workspace || ((uintptr_t)db & 3) || ((uintptr_t)workspace & 15))
+        return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_fcra_pool_bwd(R, P, y, adj, adj_row_stride, out, out_stride, g, g_stride, dy, db, (float *)workspace, max_blocks, (hipStream_t)stream);
 }
 
 }  // extern "C"

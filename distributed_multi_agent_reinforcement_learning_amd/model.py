@@ -9,6 +9,10 @@ Mirrors (reference paths) DHGN/mappo_parallel.py:116-387 `DHGN`, :390-474 `Share
   `ops.msg_agg` (csrc/mappo_ops.hip).  The reference's only working aggregator is 'mean' (SURVEY Q14); `vertex_level_aggregator:
   att` is ours, a softmax over the listed neighbours in the fused HIP op `ops.att_agg3` (csrc/att_agg.hpp), and so is
   `fcra_aggregator: att`, a softmax over the team-mates' stored embeddings in every FCRA hop (`ops.fcra_att`, csrc/fcra_att.hpp).
+  `pool` at either level is ours too (the reference's CustomMaxPool takes its arg-max over the feature axis and cannot be ported): the
+  GraphSAGE max-pool, an element-wise maximum over the listed neighbours with the AGG layer kept linear behind it, in the fused HIP ops
+  `ops.pool_agg3` (csrc/pool_agg.hpp) and `ops.fcra_pool` (csrc/fcra_pool.hpp), DESIGN 7v.  It adds no parameters: a `pool` model has
+  the `mean` model's state_dict, `.parameters()` order and initialisation stream.
 """
 import torch
 import torch.nn as nn
@@ -48,15 +52,21 @@ class DHGN(nn.Module):
     def __init__(self, input_dim, embedding_dim, is_sn, algo_config, device=None):
         super().__init__()
         self.fcra_att = algo_config.fcra_aggregator == "att"         # ours (ops.fcra_att)
-        if not self.fcra_att and algo_config.fcra_aggregator != "mean":
-            raise NotImplementedError(f"fcra_aggregator={algo_config.fcra_aggregator!r}: 'mean' or 'att'")
+        self.fcra_pool = algo_config.fcra_aggregator == "pool"       # ours (ops.fcra_pool)
+        if not (self.fcra_att or self.fcra_pool) and algo_config.fcra_aggregator != "mean":
+            raise NotImplementedError(f"fcra_aggregator={algo_config.fcra_aggregator!r}: 'mean', 'att' or 'pool'")
         if self.fcra_att and embedding_dim != 128:
             raise ValueError(f"fcra_aggregator='att' needs embedding_dim=128 (got {embedding_dim}): the attention kernels exist for that width only")
+        if self.fcra_pool and embedding_dim != 128:
+            raise ValueError(f"fcra_aggregator='pool' needs embedding_dim=128 (got {embedding_dim}): the max-pool kernels exist for that width only")
         self.att = algo_config.vertex_level_aggregator == "att"      # ours (ops.att_agg3): the reference's branch never ran
-        if not self.att and algo_config.vertex_level_aggregator != "mean":
-            raise NotImplementedError(f"vertex_level_aggregator={algo_config.vertex_level_aggregator!r}: 'mean' or 'att'")
+        self.pool = algo_config.vertex_level_aggregator == "pool"    # ours (ops.pool_agg3): no parameters of its own
+        if not (self.att or self.pool) and algo_config.vertex_level_aggregator != "mean":
+            raise NotImplementedError(f"vertex_level_aggregator={algo_config.vertex_level_aggregator!r}: 'mean', 'att' or 'pool'")
         if self.att and embedding_dim != 128:
             raise ValueError(f"vertex_level_aggregator='att' needs embedding_dim=128 (got {embedding_dim}): the attention kernels exist for that width only")
+        if self.pool and embedding_dim != 128:
+            raise ValueError(f"vertex_level_aggregator='pool' needs embedding_dim=128 (got {embedding_dim}): the max-pool kernels exist for that width only")
         self.ReLU = nn.ReLU()
         self.MSG_layers = nn.ModuleList()
         self.AGG_layers = nn.ModuleDict()
@@ -90,6 +100,8 @@ class DHGN(nn.Module):
         args = (p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias)
         if self.att:
             return ops.att_agg3(*args, [self.alpha[f"AGG_vertex_{r}"] for r in range(3)], is_critic, o_kvalid, q_div, e_ref)
+        if self.pool:
+            return ops.pool_agg3(*args, is_critic, o_kvalid, q_div, e_ref)
         return ops.msg_agg3(*args, is_critic, o_kvalid, q_div, e_ref)
 
     # -- encoder (:241-304) ----------------------------------------------------------------------------
@@ -135,7 +147,7 @@ class DHGN(nn.Module):
         """the update's encoder of actor and critic together -> (h0_actor, h0_critic): one message pass for both networks
         (ops.msg_agg3_pair_train), then the layers per network; same numbers as encoder(.., False) and encoder(.., True)."""
         M = self.MSG_layers
-        if self.att:   # no shared pass under the softmax: one launch per network
+        if self.att or self.pool:   # no shared pass under the softmax or the maximum: one launch per network
             m3a, m3c = [self._messages(p, e, o, adj_p, adj_e, adj_o, c, None, q_div, e_ref) for c in (False, True)]
         else:
             m3a, m3c = ops.msg_agg3_pair_train(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
@@ -152,13 +164,13 @@ class DHGN(nn.Module):
             aggk, fk = self.AGG_layers[f"AGG_fcra_{k}"], self.FCRA_layers[k]
             # matmul(normalize(adj or ones, p=1), hist[k]): one pass, the history slice read in place (hist is stored data)
             last = k == self.depth - 1
-            if self.fcra_att:
-                # the softmax over the team-mates' embeddings of tick t-1-k: y = hist W^T is ops.linear's (its backward produces dW; a
-                # strided history slice is copied dense for it, one pass over R P E floats per hop), the attention kernel writes the left
-                # half of the hop's operand (ops.fcra_hop_att)
+            if self.fcra_att or self.fcra_pool:
+                # the softmax (the maximum) over the team-mates' embeddings of tick t-1-k: y = hist W^T is ops.linear's (its backward
+                # produces dW; a strided history slice is copied dense for it, one pass over R P E floats per hop), the aggregator's kernel
+                # writes the left half of the hop's operand (ops.fcra_hop_att; no alpha: the max-pool, ops.fcra_hop_pool)
                 y = ops.linear(hist[k], aggk.weight)
-                h, carry = ops.fcra_hop_att(y, None if is_critic else adj_p, aggk.bias, self.alpha[f"AGG_fcra_{k}"], h, carry, fk.weight, fk.bias,
-                                            last, out if last else None)
+                h, carry = ops.fcra_hop_att(y, None if is_critic else adj_p, aggk.bias, self.alpha[f"AGG_fcra_{k}"] if self.fcra_att else None, h, carry,
+                                            fk.weight, fk.bias, last, out if last else None)
                 continue
             nb = ops.fcra_mean(z_critic=hist[k]) if is_critic else ops.fcra_mean(z_actor=hist[k], adj=adj_p)
             # FCRA_k([relu(AGG_k(nb)) | h]) as one K = 2E GEMM whose operand halves are written in place by their producers
@@ -194,8 +206,8 @@ class DHGN(nn.Module):
         else:
             h0 = out if out is not None else torch.empty((2, R, P, E), dtype=p.dtype, device=p.device)
         h0_2d = ops.block2d(h0)
-        fused_pos = ind == 4 and not self.att
-        if self.att:   # one launch per network (the weights differ per neighbour, so the messages are not summed once for both)
+        fused_pos = ind == 4 and not (self.att or self.pool)
+        if self.att or self.pool:   # one launch per network (the weights differ per neighbour / the maxima per list: no sum shared by both)
             with torch.no_grad():
                 m3 = torch.stack([self._messages(p, e, o, adj_p, adj_e, adj_o, False, None, q_div, e_ref),
                                   self._messages(p, e, o, adj_p, adj_e, adj_o, True, o_kvalid, q_div, e_ref)])
@@ -250,6 +262,12 @@ class DHGN(nn.Module):
                 ops.fcra_att_pair_multi([zas[k].contiguous() for k in ks], [zcs[k].contiguous() for k in ks], adj_f,
                                         [self.AGG_layers[f"AGG_fcra_{k}"].bias for k in ks], [self.alpha[f"AGG_fcra_{k}"] for k in ks],
                                         [cats[k][..., :E] for k in ks])
+        elif self.fcra_pool:   # likewise: the d maxima of both networks in ONE launch
+            adj_f = adj_p if adj_p.dtype == torch.float32 else adj_p.float()
+            for k0 in range(0, d, ops.FCRA_POOL_MAX_JOBS):
+                ks = range(k0, min(d, k0 + ops.FCRA_POOL_MAX_JOBS))
+                ops.fcra_pool_pair_multi([zas[k].contiguous() for k in ks], [zcs[k].contiguous() for k in ks], adj_f,
+                                         [self.AGG_layers[f"AGG_fcra_{k}"].bias for k in ks], [cats[k][..., :E] for k in ks])
         elif d <= 4 and all(z.is_contiguous() for z in zas + zcs) and adj_p.dtype == torch.float32:
             ops.fcra_mean_pair_multi(zas, zcs, adj_p, [self.AGG_layers[f"AGG_fcra_{k}"].bias for k in range(d)], [cats[k][..., :E] for k in range(d)])
         else:

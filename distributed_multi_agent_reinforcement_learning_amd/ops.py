@@ -25,7 +25,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "ppo_bc_loss_gauss_fwd_bwd", "ppo_bc_loss_cat_fwd_bwd", "team_comm_mask", "team_attention_fwd", "team_attention_bwd",
            "team_comm_mask_host", "team_attention_fwd_host", "team_attention_bwd_host", "gnn_pair_agg_fwd", "gnn_pair_agg_bwd",
            "gnn_pair_agg_bwd_workspace", "dhgn_att_agg3_fwd", "dhgn_att_agg_bwd", "dhgn_att_agg_bwd_workspace", "fcra_att_fwd_multi", "fcra_att_bwd",
-           "fcra_att_bwd_workspace", "mappo_ops_error_string")
+           "fcra_att_bwd_workspace", "dhgn_pool_agg3_fwd", "dhgn_pool_agg_bwd", "dhgn_pool_agg_bwd_workspace", "fcra_pool_fwd_multi", "fcra_pool_bwd",
+           "fcra_pool_bwd_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -168,6 +169,14 @@ def load_library():
         L.fcra_att_bwd_workspace.argtypes = [i32, i32]
         L.fcra_att_bwd_workspace.restype = i64
         L.fcra_att_bwd.argtypes = [i64, i32, i32, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
+        L.dhgn_pool_agg3_fwd.argtypes = [vp, i32, i32, i32, vp, i64, vp, i64, vp]
+        L.dhgn_pool_agg_bwd_workspace.argtypes = [i32, i32]
+        L.dhgn_pool_agg_bwd_workspace.restype = i64
+        L.dhgn_pool_agg_bwd.argtypes = [i32, i32, i32, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32] + [vp] * 4 + [i64] + [vp] * 4
+        L.fcra_pool_fwd_multi.argtypes = [i32, vp, i64, i32, i32, vp, i64, i64, i32, vp]
+        L.fcra_pool_bwd_workspace.argtypes = [i32, i32]
+        L.fcra_pool_bwd_workspace.restype = i64
+        L.fcra_pool_bwd.argtypes = [i64, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
         _lib = L
@@ -607,6 +616,7 @@ class AttRel(C.Structure):
 
 
 att_agg_calls = 0     # forward launches of the fused attention aggregator so far (tests)
+pool_agg_calls = 0    # forward launches of the fused max-pool aggregator so far (tests)
 ATT_CHUNK_ENTRIES = 1 << 24   # (rows, P, K, E) entries the torch formula materialises at once
 
 
@@ -658,32 +668,36 @@ def _att_operand(t):
     return t if (t.is_contiguous() and t.data_ptr() % 16 == 0) else _dense16(t)
 
 
-def _att_workspace(device, din):
-    key = (device, "att", din, torch.cuda.current_stream().cuda_stream)
+def _att_workspace(device, din, pool=False):
+    key = (device, "pool" if pool else "att", din, torch.cuda.current_stream().cuda_stream)
     ws = _workspaces.get(key)
     if ws is None:
-        ws = _workspaces[key] = torch.empty(load_library().dhgn_att_agg_bwd_workspace(128, din), dtype=torch.uint8, device=device)
+        L = load_library()
+        size = (L.dhgn_pool_agg_bwd_workspace if pool else L.dhgn_att_agg_bwd_workspace)(128, din)
+        ws = _workspaces[key] = torch.empty(size, dtype=torch.uint8, device=device)
     return ws
 
 
 class _AttAgg3(torch.autograd.Function):
-    """The three relations under the attention aggregator in one node writing one (R, P, 3, E) tensor: one launch forward, one per
-    relation backward (gradients to W, b, alpha; nothing saved but the operands)."""
+    """The three relations under the attention aggregator -- or, `pool`, the max-pool aggregator, whose relations carry no alpha -- in
+    one node writing one (R, P, 3, E) tensor: one launch forward, one per relation backward (gradients to W, b, alpha; nothing saved
+    but the operands)."""
 
     @staticmethod
-    def forward(ctx, p, srcs, *prm):
-        global att_agg_calls
+    def forward(ctx, p, srcs, pool, *prm):
+        global att_agg_calls, pool_agg_calls
         L = load_library()
         R, P = p.shape[0], p.shape[1]
         E = prm[0].shape[0]
-        prm = [_dense16(t.detach()) for t in prm]          # W0, b0, alpha0, W1, ..
+        prm = [_dense16(t.detach()) for t in prm]          # W0, b0, alpha0, W1, ..  (pool: W0, b0, W1, ..)
+        n = 2 if pool else 3
         p = _att_operand(p)
-        rels, arr = [], (AttRel * 3)()
+        rels, arr = [], ((MsgRel if pool else AttRel) * 3)()
         for r, (q, e, adj, kv, mode, qd) in enumerate(srcs):
             q, e = _att_operand(q), (None if e is None else _att_operand(e))
             adj = adj.contiguous() if mode in (ADJ_TENSOR, ADJ_BITS) else None
-            K, (W, b, al) = q.shape[1], prm[3 * r:3 * r + 3]
-            assert q.shape == (R // qd, K, 4) and R % qd == 0 and W.shape == (E, 8 if e is not None else 4) and al.shape == (E,)
+            K, (W, b), al = q.shape[1], prm[n * r:n * r + 2], None if pool else prm[n * r + 2]
+            assert q.shape == (R // qd, K, 4) and R % qd == 0 and W.shape == (E, 8 if e is not None else 4) and (pool or al.shape == (E,))
             if adj is not None:
                 assert adj.shape == (R, P, K if mode == ADJ_TENSOR else adj_row_words(K)) and adj.dtype == (torch.float32 if mode == ADJ_TENSOR else torch.int32)
             if mode == ADJ_VALID:
@@ -697,11 +711,18 @@ class _AttAgg3(torch.autograd.Function):
                 m.adj, m.adj_rs = adj.data_ptr(), adj.shape[1] * adj.shape[2]
             if mode == ADJ_VALID:
                 m.kvalid = kv.data_ptr()
-            m.W, m.b, m.alpha = W.data_ptr(), b.data_ptr(), al.data_ptr()
+            m.W, m.b = W.data_ptr(), b.data_ptr()
+            if not pool:
+                m.alpha = al.data_ptr()
             rels.append((q, e, adj, kv if mode == ADJ_VALID else None, mode, qd))
         out = torch.empty((R, P, 3, E), dtype=torch.float32, device=p.device)
-        _check(L.dhgn_att_agg3_fwd(C.cast(arr, C.c_void_p), R, P, E, _ptr(p), 4 * P, _ptr(out), 3 * E, _stream()), "dhgn_att_agg3_fwd")
-        att_agg_calls += 1
+        if pool:
+            _check(L.dhgn_pool_agg3_fwd(C.cast(arr, C.c_void_p), R, P, E, _ptr(p), 4 * P, _ptr(out), 3 * E, _stream()), "dhgn_pool_agg3_fwd")
+            pool_agg_calls += 1
+        else:
+            _check(L.dhgn_att_agg3_fwd(C.cast(arr, C.c_void_p), R, P, E, _ptr(p), 4 * P, _ptr(out), 3 * E, _stream()), "dhgn_att_agg3_fwd")
+            att_agg_calls += 1
+        ctx.pool = pool
         ctx.rels = [(mode, qd, [t is not None for t in (e, adj, kv)]) for (q, e, adj, kv, mode, qd) in rels]
         ctx.save_for_backward(p, *prm, *[t for rel in rels for t in rel[:4] if t is not None])
         return out
@@ -710,7 +731,9 @@ class _AttAgg3(torch.autograd.Function):
     def backward(ctx, gout):
         L = load_library()
         saved = list(ctx.saved_tensors)
-        p, prm, rest = saved[0], saved[1:10], saved[10:]
+        pool = ctx.pool
+        n = 2 if pool else 3
+        p, prm, rest = saved[0], saved[1:1 + 3 * n], saved[1 + 3 * n:]
         R, P = p.shape[0], p.shape[1]
         E = prm[0].shape[0]
         gout = _dense16(gout)
@@ -718,15 +741,24 @@ class _AttAgg3(torch.autograd.Function):
         for r, (mode, qd, has) in enumerate(ctx.rels):
             q = rest.pop(0)
             e, adj, kv = [rest.pop(0) if h else None for h in has]
-            W, b, al = prm[3 * r:3 * r + 3]
+            W, b = prm[n * r:n * r + 2]
             K, din = q.shape[1], W.shape[1]
-            dW, db, dal = torch.empty_like(W), torch.empty_like(b), torch.empty_like(al)
+            dW, db = torch.empty_like(W), torch.empty_like(b)
+            if pool:
+                _check(L.dhgn_pool_agg_bwd(R, P, K, E, din, _ptr(p), 4 * P, _ptr(q), 4 * K, qd, _ptr(e), 4 if e is not None else 0, _ptr(adj),
+                                           adj.shape[1] * adj.shape[2] if adj is not None else 0, mode, _ptr(kv), _ptr(W), _ptr(b),
+                                           C.c_void_p(gout.data_ptr() + 4 * r * E), 3 * E, _ptr(dW), _ptr(db), _ptr(_att_workspace(p.device, din, True)),
+                                           _stream()), "dhgn_pool_agg_bwd")
+                grads += [dW, db]
+                continue
+            al = prm[n * r + 2]
+            dal = torch.empty_like(al)
             _check(L.dhgn_att_agg_bwd(R, P, K, E, din, _ptr(p), 4 * P, _ptr(q), 4 * K, qd, _ptr(e), 4 if e is not None else 0, _ptr(adj),
                                       adj.shape[1] * adj.shape[2] if adj is not None else 0, mode, _ptr(kv), _ptr(W), _ptr(b), _ptr(al),
                                       C.c_void_p(gout.data_ptr() + 4 * r * E), 3 * E, _ptr(dW), _ptr(db), _ptr(dal), _ptr(_att_workspace(p.device, din)),
                                       _stream()), "dhgn_att_agg_bwd")
             grads += [dW, db, dal]
-        return (None, None) + tuple(grads)
+        return (None, None, None) + tuple(grads)
 
 
 def att_agg3(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, alphas, is_critic, o_kvalid=None, q_div=1, e_ref=None):
@@ -740,9 +772,46 @@ def att_agg3(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, alphas, is_cr
     if p.is_cuda and p.dtype == torch.float32:
         if W0.shape[0] != 128:
             raise RuntimeError(f"att_agg3: the attention kernels exist for embedding_dim 128 only (got {W0.shape[0]})")
-        return _AttAgg3.apply(p, srcs, *[t for r in range(3) for t in (Ws[r], bs[r], als[r])])
+        return _AttAgg3.apply(p, srcs, False, *[t for r in range(3) for t in (Ws[r], bs[r], als[r])])
     R, P = p.shape[0], p.shape[1]
     outs = [att_agg_formula(p, q, ee, _att_dense_adj(R, P, q.shape[1], adj, kv, mode, qd, p), Ws[r], bs[r], als[r], qd)
+            for r, (q, ee, adj, kv, mode, qd) in enumerate(srcs)]
+    return torch.stack(outs, 2)
+
+
+def pool_agg_formula(p, q, e, a, W, b, q_div=1):
+    """One relation of the max-pool aggregator in plain torch, row-chunked (the specification of csrc/pool_agg.hpp, DESIGN 7v -- ours, the
+    GraphSAGE max-pool with the AGG layer linear behind it; CPU and float64 operands, and the yardstick of tools/bench_pool.py):
+    out_i = relu(max over the j with a_ij != 0 of W [p_i - q_j, p_i - e] + b), nothing listed: exact zeros.
+    p (R,P,4), q (R/q_div,K,4), e (R,4)|None, a (R,P,K) -> (R,P,E)."""
+    R, P, K, E = p.shape[0], p.shape[1], q.shape[1], W.shape[0]
+    if K == 0 or R == 0:
+        return (W.sum() + b.sum()) * 0 + p.new_zeros(R, P, E)
+    step = max(1, ATT_CHUNK_ENTRIES // (P * K * E)) * q_div
+    outs = []
+    for r0 in range(0, R, step):
+        pc, ac = p[r0:r0 + step], a[r0:r0 + step]
+        x = pc[:, :, None] - q[r0 // q_div:(r0 + step) // q_div].repeat_interleave(q_div, 0)[:, None]
+        if e is not None:
+            x = torch.cat((x, (pc - e[r0:r0 + step, None])[:, :, None].expand_as(x)), -1)
+        z = F.linear(x, W, b).masked_fill((ac == 0)[..., None], float("-inf"))        # (n, P, K, E)
+        outs.append(torch.relu(z.amax(2)))                                             # nothing listed: relu(-inf) = 0, no gradient
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+
+def pool_agg3(p, e, o, adj_p, adj_e, adj_o, W0, b0, W1, b1, W2, b2, is_critic, o_kvalid=None, q_div=1, e_ref=None):
+    """(R, P, 3, E): msg_agg3 with an element-wise maximum over the listed neighbours in place of the mean (`vertex_level_aggregator:
+    pool`; ours): out_i = relu(max_j z_ij), the gradient to the first listed j that attains the maximum.  Operands and mode
+    selection as msg_agg3.  fp32 CUDA operands take the fused kernels (csrc/pool_agg.hpp, E = 128 only -- any other width is an error
+    there); CPU and float64 operands are evaluated by pool_agg_formula."""
+    srcs = _att_sources(p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid, q_div, e_ref)
+    Ws, bs = (W0, W1, W2), (b0, b1, b2)
+    if p.is_cuda and p.dtype == torch.float32:
+        if W0.shape[0] != 128:
+            raise RuntimeError(f"pool_agg3: the max-pool kernels exist for embedding_dim 128 only (got {W0.shape[0]})")
+        return _AttAgg3.apply(p, srcs, True, *[t for r in range(3) for t in (Ws[r], bs[r])])
+    R, P = p.shape[0], p.shape[1]
+    outs = [pool_agg_formula(p, q, ee, _att_dense_adj(R, P, q.shape[1], adj, kv, mode, qd, p), Ws[r], bs[r], qd)
             for r, (q, ee, adj, kv, mode, qd) in enumerate(srcs)]
     return torch.stack(outs, 2)
 
@@ -1147,10 +1216,11 @@ def _fcra_att_bwd(y3, adj3, bias, alpha, out, out_ld, g, g_ld, max_blocks=0):
 
 
 def _fcra_att_operands(y, adj, bias, alpha):
-    """the kernels' views: y (R, P, E) dense, adj (R, P, P) fp32 with dense rows or None, bias / alpha (E,) dense"""
+    """the kernels' views: y (R, P, E) dense, adj (R, P, P) fp32 with dense rows or None, bias / alpha (E,) dense (alpha None: max-pool)"""
     P, E = y.shape[-2], y.shape[-1]
     if E != 128:
-        raise RuntimeError(f"fcra_att: the attention kernels exist for embedding_dim 128 only (got {E})")
+        raise RuntimeError(f"fcra_att: the attention kernels exist for embedding_dim 128 only (got {E})" if alpha is not None else
+                           f"fcra_pool: the max-pool kernels exist for embedding_dim 128 only (got {E})")
     y3 = _dense16(y.detach()).reshape(-1, P, E)
     adj3 = None
     if adj is not None:
@@ -1158,7 +1228,7 @@ def _fcra_att_operands(y, adj, bias, alpha):
         if adj3.dtype != torch.float32 or not _rows_ok(adj3):
             adj3 = adj3.float().contiguous()
         assert adj3.shape[0] == y3.shape[0]
-    return y3, adj3, _dense16(bias.detach()), _dense16(alpha.detach().reshape(-1))
+    return y3, adj3, _dense16(bias.detach()), None if alpha is None else _dense16(alpha.detach().reshape(-1))
 
 
 class _FcraAtt(torch.autograd.Function):
@@ -1220,6 +1290,111 @@ def fcra_att_pair_multi(zas, zcs, adj, biases, alphas, outs):
     adj3 = adj.reshape(R, P, P)
     assert adj3.dtype == torch.float32 and _rows_ok(adj3) and E == 128
     _fcra_att_fwd(jobs, R, P, adj3, out_ld)
+
+
+class FcraPoolJob(C.Structure):
+    """include/mappo_ops.h mo_fcra_pool_job"""
+    _fields_ = [(n, C.c_void_p) for n in ("y_actor", "y_critic", "bias", "out_actor", "out_critic")]
+
+
+FCRA_POOL_MAX_JOBS = 8     # include/mappo_ops.h MO_FCRA_POOL_MAX_JOBS
+fcra_pool_calls = 0        # forward launches of the FCRA max-pool aggregator so far (tests)
+
+
+def fcra_pool_formula(y, adj, bias):
+    """The FCRA max-pool aggregator in plain torch (the specification of csrc/fcra_pool.hpp, DESIGN 7v -- ours; CPU and float64
+    operands, the yardstick of tools/bench_pool.py and the model-level reference).  y (.., P, E) = W h (no bias), adj (.., P, P) or
+    None (the critic's ones), bias (E,) -> relu(bias + max over the j with a_ij != 0 of y_j) (.., P, E); nothing listed: relu(bias)."""
+    if adj is None:
+        return torch.relu(y.amax(-2, keepdim=True) + bias).expand_as(y)
+    listed = adj != 0                                                                      # (.., P, P)
+    mx = y[..., None, :, :].masked_fill(~listed[..., None], float("-inf")).amax(-2)       # (.., P, E)
+    return torch.relu(torch.where(listed.any(-1, keepdim=True), mx, torch.zeros_like(mx)) + bias)
+
+
+def _fcra_pool_fwd(jobs, R, P, adj3, out_ld, max_blocks=0):
+    """one launch; jobs: (y_actor, y_critic, bias, out_actor, out_critic) tensors or None, bias dense (128,)"""
+    global fcra_pool_calls
+    arr = (FcraPoolJob * len(jobs))()
+    for a, job in zip(arr, jobs):
+        a.y_actor, a.y_critic, a.bias, a.out_actor, a.out_critic = [None if t is None else t.data_ptr() for t in job]
+    _check(load_library().fcra_pool_fwd_multi(len(jobs), C.cast(arr, C.c_void_p), R, P, 128, _ptr(adj3), adj3.stride(0) if adj3 is not None else 0, out_ld,
+                                              max_blocks, _stream()), "fcra_pool_fwd_multi")
+    fcra_pool_calls += 1
+
+
+def _fcra_pool_bwd(y3, adj3, out, out_ld, g, g_ld, max_blocks=0):
+    """-> dy (R, P, E), db (E,); out / g: tensors whose first element is row 0's, vectors out_ld / g_ld floats apart"""
+    L = load_library()
+    R, P, E = y3.shape
+    dy, db = torch.empty_like(y3), torch.empty(E, dtype=torch.float32, device=y3.device)
+    key = (y3.device, "fcra_pool", max_blocks, torch.cuda.current_stream().cuda_stream)
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.empty(L.fcra_pool_bwd_workspace(E, max_blocks), dtype=torch.uint8, device=y3.device)
+    _check(L.fcra_pool_bwd(R, P, E, _ptr(y3), _ptr(adj3), adj3.stride(0) if adj3 is not None else 0, _ptr(out), out_ld, _ptr(g), g_ld, _ptr(dy), _ptr(db),
+                           _ptr(ws), max_blocks, _stream()), "fcra_pool_bwd")
+    return dy, db
+
+
+class _FcraPool(torch.autograd.Function):
+    """fcra_pool on the fused kernels: one launch forward; backward one launch + the ordered reduce (dy, db; the forward saved nothing
+    beyond its output)."""
+
+    @staticmethod
+    def forward(ctx, y, adj, bias, out):
+        y3, adj3, b, _ = _fcra_att_operands(y, adj, bias, None)
+        R, P, E = y3.shape
+        if out is None:
+            out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+        else:
+            assert out.numel() == y3.numel() and out.shape[-1] == E
+            ctx.mark_dirty(out)
+        ctx.out_ld = _vec_stride(out)   # dense, or the left half of an [agg | h] operand
+        _fcra_pool_fwd([(None, y3, b, None, out) if adj3 is None else (y3, None, b, out, None)], R, P, adj3, ctx.out_ld)
+        ctx.save_for_backward(y3, adj3)
+        ctx.out = out                   # a plain reference: `out` may be a view whose base is written elsewhere
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y3, adj3 = ctx.saved_tensors
+        try:
+            g_ld = _vec_stride(g)
+        except AssertionError:
+            g, g_ld = g.contiguous(), g.shape[-1]
+        dy, db = _fcra_pool_bwd(y3, adj3, ctx.out, ctx.out_ld, g, g_ld)
+        return dy.reshape(g.shape), None, db, None
+
+
+def fcra_pool(y, adj, bias, out=None):
+    """The FCRA hops' max-pool aggregator (`algo.fcra_aggregator: pool`; ours): relu(bias + max_j y_j) over the neighbours adj
+    lists (adj=None: the critic's ones), the gradient to the first listed j that attains the maximum.  y (.., P, E) arrives from
+    ops.linear(hist_k, W) -- whose backward produces dW.  out: storage written in place (dense or the left half of an [agg | h]
+    operand).  fp32 CUDA operands take the fused kernels (csrc/fcra_pool.hpp, E = 128 only -- any other width is an error there); CPU
+    and float64 operands are evaluated by fcra_pool_formula."""
+    if y.is_cuda and y.dtype == torch.float32:
+        return _FcraPool.apply(y, adj, bias, out)
+    res = fcra_pool_formula(y, adj, bias)
+    return res if out is None else out.copy_(res.reshape(out.shape))
+
+
+def fcra_pool_pair_multi(zas, zcs, adj, biases, outs):
+    """fcra_pool for actor (adj) and critic (ones) of several hops (za, zc, b, o) of one shape in ONE launch (fcra_pool_fwd_multi), as
+    fcra_att_pair_multi: a hop whose za and zc are one tensor is loaded once.  za, zc: dense (R, P, E) products hist W^T; o: (2, R, P, E)
+    storage (possibly the left half of an [agg | h] operand).  No autograd."""
+    n = len(zas)
+    assert 1 <= n <= FCRA_POOL_MAX_JOBS and len(zcs) == n and len(biases) == n and len(outs) == n
+    P, E = zas[0].shape[-2], zas[0].shape[-1]
+    R = zas[0].numel() // (P * E)
+    out_ld = _vec_stride(outs[0])
+    jobs = []
+    for za, zc, b, o in zip(zas, zcs, biases, outs):
+        assert za.is_contiguous() and zc.is_contiguous() and za.shape == zas[0].shape and zc.shape == zas[0].shape and _vec_stride(o) == out_ld
+        jobs.append((za, zc, _dense16(b.detach()), o[0], o[1]))
+    adj3 = adj.reshape(R, P, P)
+    assert adj3.dtype == torch.float32 and _rows_ok(adj3) and E == 128
+    _fcra_pool_fwd(jobs, R, P, adj3, out_ld)
 
 
 RELU_BWD_MIN_ROWS = 4096
@@ -1664,7 +1839,8 @@ class _FcraHopAtt(torch.autograd.Function):
     y = hist Wagg^T the caller's ops.linear (its backward produces dWagg from the dy returned here).  No inner AGG GEMM: the attention
     kernel writes the left half of the [agg | h] operand through its column stride; the FCRA layer, its masked input gradient and
     its weight gradient are _FcraHop's.  The operand's sign-bit blocks are not kept on this path (the attention kernel writes none):
-    the masked input gradient reads the operand itself."""
+    the masked input gradient reads the operand itself.
+    alpha None: `algo.fcra_aggregator: pool`, agg = fcra_pool(y, adj, bagg) from the max-pool kernels (csrc/fcra_pool.hpp) in the same place."""
 
     @staticmethod
     def forward(ctx, y, adj, bagg, alpha, h, cat, Wf, bf, last, out, box, h_link=None):
@@ -1677,7 +1853,10 @@ class _FcraHopAtt(torch.autograd.Function):
             assert cat.shape == (rows, 2 * E) and cat.is_contiguous() and h.data_ptr() == cat.data_ptr() + E * cat.element_size()
         y3, adj3, b, al = _fcra_att_operands(y, adj, bagg, alpha)
         assert y3.shape[0] * y3.shape[1] == rows
-        _fcra_att_fwd([(None, y3, b, al, None, cat) if adj3 is None else (y3, None, b, al, cat, None)], y3.shape[0], y3.shape[1], adj3, 2 * E)
+        if alpha is None:
+            _fcra_pool_fwd([(None, y3, b, None, cat) if adj3 is None else (y3, None, b, cat, None)], y3.shape[0], y3.shape[1], adj3, 2 * E)
+        else:
+            _fcra_att_fwd([(None, y3, b, al, None, cat) if adj3 is None else (y3, None, b, al, cat, None)], y3.shape[0], y3.shape[1], adj3, 2 * E)
         nxt = None
         if out is not None:     # rollout: the caller's static storage (no autograd)
             ctx.mark_dirty(out)
@@ -1690,7 +1869,7 @@ class _FcraHopAtt(torch.autograd.Function):
         _hop_gemm(cat, Wf, bf, dst)
         ctx.save_for_backward(y3, adj3, b, al, Wf)
         ctx.cat, ctx.y = cat, dst          # plain references, as in _FcraHop
-        ctx.shapes = (y.shape, alpha.shape, h.shape)
+        ctx.shapes = (y.shape, None if alpha is None else alpha.shape, h.shape)
         ctx.h_link, ctx.y_link = h_link, ReluLink()
         box += [nxt, ctx.y_link]
         return dst.reshape(h.shape) if out is None else out
@@ -1718,10 +1897,14 @@ class _FcraHopAtt(torch.autograd.Function):
                 ctx.h_link.db = cs[E:]
         else:
             dcat = input_grad(gin, Wf)
-        dy, dbagg, dal = _fcra_att_bwd(y3, adj3, b, al, cat, 2 * E, dcat, dcat.stride(0))
-        dWf = wgrad(gin, cat)
         y_shape, alpha_shape, h_shape = ctx.shapes
-        return dy.reshape(y_shape), None, dbagg, dal.reshape(alpha_shape), dcat[:, E:].reshape(h_shape), None, dWf, dbf, None, None, None, None
+        if al is None:
+            (dy, dbagg), dal = _fcra_pool_bwd(y3, adj3, cat, 2 * E, dcat, dcat.stride(0)), None
+        else:
+            dy, dbagg, dal = _fcra_att_bwd(y3, adj3, b, al, cat, 2 * E, dcat, dcat.stride(0))
+            dal = dal.reshape(alpha_shape)
+        dWf = wgrad(gin, cat)
+        return dy.reshape(y_shape), None, dbagg, dal, dcat[:, E:].reshape(h_shape), None, dWf, dbf, None, None, None, None
 
 
 def fcra_hop_att(y, adj, bagg, alpha, h, carry, Wf, bf, last, out=None):
@@ -1731,6 +1914,11 @@ def fcra_hop_att(y, adj, bagg, alpha, h, carry, Wf, bf, last, out=None):
     box = []
     h2 = _FcraHopAtt.apply(y, adj, bagg, alpha, h, cat, Wf, bf, bool(last), out, box, h_link)
     return h2, (box[0], box[1])
+
+
+def fcra_hop_pool(y, adj, bagg, h, carry, Wf, bf, last, out=None):
+    """-> (h', carry'): fcra_hop under the max-pool aggregator: fcra_hop_att's node with no alpha (see _FcraHopAtt)."""
+    return fcra_hop_att(y, adj, bagg, None, h, carry, Wf, bf, last, out)
 
 
 FUSED_CELL_MIN_ROWS = 1024  # single-step batches at least this large take the fused cell kernel

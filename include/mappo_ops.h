@@ -163,6 +163,27 @@ int dhgn_att_agg_bwd(int32_t R, int32_t P, int32_t K, int32_t E, int32_t din, co
                      int64_t gout_stride, float *dW, float *db, float *d_alpha, void *workspace, void *stream);
 
 /*
+ * The vertex-level MAX-POOL aggregator (`algo.vertex_level_aggregator: pool`; csrc/pool_agg.hpp) -- ours: the reference's `pool`
+ * branch (CustomMaxPool) takes its arg-max over the feature axis and cannot be ported; this is the GraphSAGE max-pool aggregator.
+ * Pre-activations as in dhgn_msg_agg_fwd, z_ij = W [p_i - q_j, p_i - e] + b; over the listed j (a_ij != 0; the weight's value is not used):
+ *   out_i[u] = ReLU(max_j z_ij[u])                  nothing listed: exact zeros.
+ * Arguments, row strides, q_div, kvalid, the four adjacency sources, shape limits, alignment and refusals are dhgn_att_agg_*'s (above)
+ * without alpha: MO_ERR_BAD_ARG before any launch or write; R == 0 succeeds and writes nothing; K == 0 writes zeros / exact-zero gradients.
+ * dhgn_pool_agg3_fwd: the three relations of one network in one launch, relation r into slot r of out [R][P][3][E].
+ * dhgn_pool_agg_bwd: one relation; for every unit with out_i[u] > 0 the FIRST listed j that attains the maximum receives the gradient:
+ * dW[u, :] += g[u] x_ij*, db[u] += g[u]; dW [E][din], db [E] OVERWRITTEN.  Nothing was saved by the forward: the same walk through the
+ * same expression finds the arg-max again.  workspace: at least dhgn_pool_agg_bwd_workspace(E, din) bytes, 16-byte aligned
+ * (per-workgroup partial blocks added in a fixed order: no atomics, the same bits from run to run).
+ */
+int dhgn_pool_agg3_fwd(const mo_msg_rel *rel /* [3] */, int32_t R, int32_t P, int32_t E, const float *p, int64_t p_row_stride, float *out,
+                       int64_t out_stride, void *stream);
+int64_t dhgn_pool_agg_bwd_workspace(int32_t E, int32_t din);
+int dhgn_pool_agg_bwd(int32_t R, int32_t P, int32_t K, int32_t E, int32_t din, const float *p, int64_t p_row_stride, const float *q,
+                      int64_t q_row_stride, int32_t q_div, const float *e, int64_t e_row_stride, const void *adj, int64_t adj_row_stride,
+                      int32_t adj_mode, const int32_t *kvalid, const float *W, const float *b, const float *gout, int64_t gout_stride,
+                      float *dW, float *db, void *workspace, void *stream);
+
+/*
  * GAE reverse scan + value target + advantage normalisation (DHGN/mappo_parallel.py:643-658):
  *   delta = (r + gamma v[:,1:] - v[:,:-1]) * active ; gae_t = delta_t + gamma lamda gae_{t+1}
  *   v_target = adv + v[:,:-1] ; if use_adv_norm: adv = (adv - mean) / (std_unbiased + 1e-5) * active
@@ -696,6 +717,24 @@ int64_t fcra_att_bwd_workspace(int32_t E, int32_t max_blocks);
 int fcra_att_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *adj, int64_t adj_row_stride, const float *bias, const float *alpha,
                  const float *out, int64_t out_stride, const float *g, int64_t g_stride, float *dy, float *db, float *d_alpha, void *workspace,
                  int32_t max_blocks, void *stream);
+
+/*
+ * The MAX-POOL aggregator of the FCRA hops (`algo.fcra_aggregator: pool`; csrc/fcra_pool.hpp) -- ours, as the vertex level's.
+ * One hop, R rows of P agents, E features; y_j = W h_j is the caller's GEMM (no bias), [R][P][E] dense:
+ *   out_i[u] = relu(bias[u] + max over the listed j of i (a_ij != 0) of y_j[u])        nothing listed: relu(bias).
+ * fcra_pool_fwd_multi: fcra_att_fwd_multi's contract without alpha (jobs, actor = adj / critic = ones, a job whose y_actor == y_critic
+ * loads y once, out_stride, max_blocks, limits, alignment, refusals).
+ * fcra_pool_bwd: one job, one network (adj NULL: ones).  out: what the forward wrote (read for the sign only), g: d out.  With
+ * gp_i = [out_i > 0] g_i and j*(i, u) the first listed j that attains the maximum: dy_j[u] = sum over i with j*(i, u) = j of gp_i[u],
+ * db = sum_i gp_i; dy [R][P][E] dense, db [E] OVERWRITTEN.  workspace: at least fcra_pool_bwd_workspace(E, max_blocks) bytes, 16-byte aligned.
+ */
+#define MO_FCRA_POOL_MAX_JOBS 8
+typedef struct mo_fcra_pool_job { const float *y_actor, *y_critic, *bias; float *out_actor, *out_critic; } mo_fcra_pool_job;
+int fcra_pool_fwd_multi(int32_t n_jobs, const mo_fcra_pool_job *jobs, int64_t R, int32_t P, int32_t E, const float *adj, int64_t adj_row_stride,
+                        int64_t out_stride, int32_t max_blocks, void *stream);
+int64_t fcra_pool_bwd_workspace(int32_t E, int32_t max_blocks);
+int fcra_pool_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *adj, int64_t adj_row_stride, const float *out, int64_t out_stride,
+                  const float *g, int64_t g_stride, float *dy, float *db, void *workspace, int32_t max_blocks, void *stream);
 
 /*
  * ReLU backward and the bias gradient of the Linear in front of it in one pass (autograd: aten::threshold_backward, then
