@@ -15,6 +15,7 @@
 #include "fcra_att.hpp"
 #include "fcra_pool.hpp"
 #include "pool_agg.hpp"
+#include "sem_att.hpp"
 
 extern "C" {
 
@@ -132,6 +133,57 @@ int sb_encoder_tail_bwd(int64_t Rs, const float *g, int64_t ldg, const float *Ws
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     if (cus > 1024) return MO_ERR_BAD_ARG;         // (the workspace holds 1024 rows)
     return launch_sb_encoder_tail_bwd(Rs, g, ldg, Ws, ldw, w_agg, emb_sign_bits, ld_bytes, ga, ldga, d_m3, ldd, (float *)workspace, colsum, cus, st);
+}
+
+// the operands both forward variants of the semantic attention tail share
+static bool sem_att_fwd_ok(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *alpha, const float *Ws,
+                           int64_t ldw, const float *C, int64_t ldc, const float *Y, int64_t ldy) {
+    if (Rs < 0 || !m3 || !w_agg || !b_agg || !alpha || !Ws || !C || !Y || ldx < 384 || ldw < 384 || ldc < 128 || ldy < 128) return false;
+    return !((ldx & 3) || (ldw & 3) || (ldc & 3) || (ldy & 3) || ((uintptr_t)m3 & 15) || ((uintptr_t)w_agg & 15) || ((uintptr_t)b_agg & 15) ||
+             ((uintptr_t)alpha & 15) || ((uintptr_t)Ws & 15) || ((uintptr_t)C & 15) || ((uintptr_t)Y & 15));
+}
+
+int dhgn_sem_att_tail(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *alpha, const float *Ws, int64_t ldw,
+                      const float *C, int64_t ldc, float *Y, int64_t ldy, void *stream) {
+    if (!sem_att_fwd_ok(Rs, m3, ldx, w_agg, b_agg, alpha, Ws, ldw, C, ldc, Y, ldy)) return MO_ERR_BAD_ARG;
+    if (Rs == 0) return 0;
+    return launch_sem_att_fwd<false>(Rs, m3, ldx, w_agg, b_agg, alpha, Ws, ldw, C, ldc, Y, ldy, (hipStream_t)stream);
+}
+
+int dhgn_sem_att_tail_train(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *alpha, const float *Ws,
+                            int64_t ldw, const float *C, int64_t ldc, float *Y, int64_t ldy, float *emb, int64_t lde, uint8_t *emb_sign_bits,
+                            int64_t ld_bytes, float *gates, void *stream) {
+    if (!sem_att_fwd_ok(Rs, m3, ldx, w_agg, b_agg, alpha, Ws, ldw, C, ldc, Y, ldy) || !emb || !emb_sign_bits || !gates || lde < 384 || (lde & 3) ||
+        ld_bytes < 48 || ((uintptr_t)emb & 15) || ((uintptr_t)gates & 3))
+        return MO_ERR_BAD_ARG;
+    if (Rs == 0) return 0;
+    return launch_sem_att_fwd<true>(Rs, m3, ldx, w_agg, b_agg, alpha, Ws, ldw, C, ldc, Y, ldy, (hipStream_t)stream, emb, lde, emb_sign_bits, ld_bytes,
+                                    gates);
+}
+
+int64_t dhgn_sem_att_tail_bwd_workspace(void) { return (int64_t)SA_MAX_GRID * (384 + 128) * 4; }   // one row of partial sums per workgroup (<= CUs)
+
+int dhgn_sem_att_tail_bwd(int64_t Rs, const float *g, int64_t ldg, const float *Ws, int64_t ldw, const float *w_agg, const float *alpha, const float *emb,
+                          int64_t lde, const float *gates, float *ga, int64_t ldga, float *emb_scaled, int64_t ldes, float *d_m3, int64_t ldd,
+                          float *colsum, float *d_alpha, void *workspace, void *stream) {
+    if (Rs < 0 || !g || !Ws || !w_agg || !alpha || !emb || !gates || !ga || !emb_scaled || !d_m3 || !colsum || !d_alpha || !workspace || ldg < 128 ||
+        ldw < 384 || lde < 384 || ldga < 384 || ldes < 384 || ldd < 384)
+        return MO_ERR_BAD_ARG;
+    if ((ldg & 3) || (ldw & 3) || (lde & 3) || (ldga & 3) || (ldes & 3) || (ldd & 3) || ((uintptr_t)g & 15) || ((uintptr_t)Ws & 15) ||
+        ((uintptr_t)w_agg & 15) || ((uintptr_t)alpha & 15) || ((uintptr_t)emb & 15) || ((uintptr_t)gates & 3) || ((uintptr_t)ga & 15) ||
+        ((uintptr_t)emb_scaled & 15) || ((uintptr_t)d_m3 & 15) || ((uintptr_t)colsum & 3) || ((uintptr_t)d_alpha & 3) || ((uintptr_t)workspace & 15))
+        return MO_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    if (cus > SA_MAX_GRID) return MO_ERR_BAD_ARG;   // (the workspace holds SA_MAX_GRID rows)
+    if (Rs == 0) {   // nothing to add up: zero sums from the reduce over no partial rows
+        hipLaunchKernelGGL(k_sb_colsum_reduce, dim3(3), dim3(128), 0, st, 0, 384, (const float *)workspace, colsum);
+        hipLaunchKernelGGL(k_sb_colsum_reduce, dim3(1), dim3(128), 0, st, 0, 128, (const float *)workspace, d_alpha);
+        return (int)hipGetLastError();
+    }
+    return launch_sem_att_bwd(Rs, g, ldg, Ws, ldw, w_agg, alpha, emb, lde, gates, ga, ldga, emb_scaled, ldes, d_m3, ldd, colsum, d_alpha,
+                              (float *)workspace, cus, st);
 }
 
 int gru_seq_split_fwd_multi(int32_t n_nets, const mo_gru_seq_net *nets, int32_t T, int32_t B, int32_t H, int32_t gi_agents, void *stream) {

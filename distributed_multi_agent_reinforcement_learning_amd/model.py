@@ -13,6 +13,8 @@ Mirrors (reference paths) DHGN/mappo_parallel.py:116-387 `DHGN`, :390-474 `Share
   GraphSAGE max-pool, an element-wise maximum over the listed neighbours with the AGG layer kept linear behind it, in the fused HIP ops
   `ops.pool_agg3` (csrc/pool_agg.hpp) and `ops.fcra_pool` (csrc/fcra_pool.hpp), DESIGN 7v.  It adds no parameters: a `pool` model has
   the `mean` model's state_dict, `.parameters()` order and initialisation stream.
+  `semantic_level_aggregator: att` is ours as well (the reference left the branch commented out): a softmax over the three relation
+  embeddings between the AGG layer and the semantic layer, inside the fused encoder tail (`ops.sem_att_tail*`, csrc/sem_att.hpp).
 """
 import torch
 import torch.nn as nn
@@ -67,6 +69,11 @@ class DHGN(nn.Module):
             raise ValueError(f"vertex_level_aggregator='att' needs embedding_dim=128 (got {embedding_dim}): the attention kernels exist for that width only")
         if self.pool and embedding_dim != 128:
             raise ValueError(f"vertex_level_aggregator='pool' needs embedding_dim=128 (got {embedding_dim}): the max-pool kernels exist for that width only")
+        self.sem_att = getattr(algo_config, "semantic_level_aggregator", "mean") == "att"   # ours (ops.sem_att_tail*)
+        if not self.sem_att and getattr(algo_config, "semantic_level_aggregator", "mean") != "mean":
+            raise NotImplementedError(f"semantic_level_aggregator={algo_config.semantic_level_aggregator!r}: 'mean' or 'att'")
+        if self.sem_att and embedding_dim != 128:
+            raise ValueError(f"semantic_level_aggregator='att' needs embedding_dim=128 (got {embedding_dim}): the attention kernels exist for that width only")
         self.ReLU = nn.ReLU()
         self.MSG_layers = nn.ModuleList()
         self.AGG_layers = nn.ModuleDict()
@@ -93,6 +100,11 @@ class DHGN(nn.Module):
                 self.alpha = nn.ParameterDict()
             for k in range(self.depth):
                 self.alpha[f"AGG_fcra_{k}"] = nn.Parameter(torch.zeros(E, 1))
+        if self.sem_att:   # after every other parameter, without a draw: the model starts as the 'mean' model of the same seed
+            if not (self.att or self.fcra_att):   # the only alpha: registered anew, so that the key is the state_dict's last (behind the
+                del self.alpha                    # vertex and FCRA alphas otherwise, which keep their places)
+                self.alpha = nn.ParameterDict()
+            self.alpha["AGG_semantic"] = nn.Parameter(torch.zeros(E, 1))
 
     def _messages(self, p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid=None, q_div=1, e_ref=None):
         """the three relation aggregates (R, P, 3, E) under the configured vertex-level aggregator"""
@@ -121,6 +133,16 @@ class DHGN(nn.Module):
         agg0 = self.AGG_layers["AGG_vertex_0"]
         Ws = self.semantic_layer.weight
         pos = None
+        if self.sem_att:
+            # the softmax over the three relations sits between the two layers: position part first, then the fused tail accumulates the
+            # gated embedding part into it (an empty relation's relu(b_agg) takes part in the softmax: there is no presence mask here)
+            m3_s, Wse, al = m3.reshape(R * P, 3 * E), Ws[:, ind:], self.alpha["AGG_semantic"]
+            if out is not None:   # rollout: into the static storage
+                o2 = out.view(R * P, E)
+                torch.addmm(self.semantic_layer.bias, p.reshape(R * P, ind), Ws[:, :ind].t(), out=o2)
+                return ops.sem_att_tail(m3_s, agg0.weight, agg0.bias, al, Wse, o2).view(R, P, E)
+            pos = ops.linear_skinny(p.reshape(R * P, ind), Ws[:, :ind], self.semantic_layer.bias)
+            return ops.sem_att_tail_train(m3_s, agg0.weight, agg0.bias, al, Wse, pos).reshape(R, P, E)
         if out is None and ops.ENCODER_TAIL_TRAIN and torch.is_grad_enabled() and m3.is_contiguous():
             # the update: both layers as ONE launch forward and one backward, the embedding handed over in LDS (the same bits as the two
             # linear calls below, their gradients included); the position part first, the launch accumulates into it
@@ -217,7 +239,13 @@ class DHGN(nn.Module):
                                    o_kvalid, q_div, pos=(Ws[:, :ind], self.semantic_layer.bias, h0) if fused_pos else None, e_ref=e_ref)   # (2, R, P, 3, E)
         agg0 = self.AGG_layers["AGG_vertex_0"]
         m3_s, Wse = m3.view(2 * R * P, 3 * E), Ws[:, ind:]
-        if fused_pos and ops.encoder_tail_ok(m3_s, agg0.weight, agg0.bias, Wse, h0_2d):
+        if self.sem_att:
+            if not fused_pos:
+                torch.addmm(self.semantic_layer.bias, p.reshape(R * P, ind), Ws[:, :ind].t(), out=h0_2d[:R * P])
+                h0_2d[R * P:].copy_(h0_2d[:R * P])
+            # the position part (both networks' rows) is the addend of the fused tail; h0 may be the right half of the first hop's operand
+            ops.sem_att_tail(m3_s, agg0.weight, agg0.bias, self.alpha["AGG_semantic"], Wse, h0_2d)
+        elif fused_pos and ops.encoder_tail_ok(m3_s, agg0.weight, agg0.bias, Wse, h0_2d):
             # the AGG layer and the embedding part of the semantic layer as ONE launch: the (2 R P, 3 E) embedding never reaches
             # memory (ops.ENCODER_TAIL; the same bits as the two launches below)
             ops.encoder_tail(m3_s, agg0.weight, agg0.bias, Wse, h0_2d)

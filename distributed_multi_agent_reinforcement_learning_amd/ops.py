@@ -85,6 +85,11 @@ def load_library():
         L.sb_encoder_tail_bwd_workspace.argtypes = []
         L.sb_encoder_tail_bwd_workspace.restype = i64
         L.sb_encoder_tail_bwd.argtypes = [i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp]
+        L.dhgn_sem_att_tail.argtypes = [i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp]
+        L.dhgn_sem_att_tail_train.argtypes = [i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]
+        L.dhgn_sem_att_tail_bwd_workspace.argtypes = []
+        L.dhgn_sem_att_tail_bwd_workspace.restype = i64
+        L.dhgn_sem_att_tail_bwd.argtypes = [i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]
         L.gru_seq_fwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
         L.gru_seq_bwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
         L.gru_seq_split_fwd_multi.argtypes = [i32, vp, i32, i32, i32, i32, vp]
@@ -2655,6 +2660,122 @@ class _EncoderTailTrain(torch.autograd.Function):
 def encoder_tail_train(m3, w_agg, b_agg, Ws, addend):
     """see _EncoderTailTrain; the caller checks encoder_tail_train_ok.  addend must be a temporary: it becomes the result."""
     return _EncoderTailTrain.apply(m3, w_agg, b_agg, Ws, addend)
+
+
+# -- the semantic-level attention aggregator (`algo.semantic_level_aggregator: att`; csrc/sem_att.hpp, DESIGN 7w) ------------------------
+def sem_att_formula(m3, w_agg, b_agg, alpha, Ws, addend):
+    """h0 = addend + sum over r of g_r Ws_r emb_r with emb_r = relu(w_agg m3[:, r] + b_agg), s_r = alpha . emb_r and g = 3 softmax(s) over
+    the three relations, in plain torch ops: the specification of csrc/sem_att.hpp, and what CPU tensors, float64 operands and the
+    matmul modes other than split_bf16 take.  m3 (Rs, 384), Ws (128, 384), alpha (128, 1) or (128,), addend (Rs, 128)."""
+    Rs = m3.shape[0]
+    emb = torch.relu(m3.reshape(Rs * 3, 128) @ w_agg.t() + b_agg).view(Rs, 3, 128)
+    s = emb @ alpha.reshape(128)
+    e = torch.exp(s - s.max(dim=1, keepdim=True).values)
+    g = 3.0 * e / e.sum(dim=1, keepdim=True)
+    return addend + ((g.unsqueeze(2) * emb).reshape(Rs, 384) @ Ws.t())
+
+
+def _sem_att_operands_ok(m3, w_agg, b_agg, alpha, Ws, out):
+    """encoder_tail_ok's layout rules: fp32 CUDA operands, E = 128; m3 (Rs, 384) and out (Rs, 128) 2-D with unit column stride, row strides
+    multiples of 4 floats, 16-byte aligned; Ws (128, 384) may be a column block; w_agg, b_agg, alpha dense; m3 does not overlap out"""
+    if not m3.is_cuda or m3.dim() != 2 or out.dim() != 2 or m3.shape[1] != 384 or tuple(out.shape) != (m3.shape[0], 128) or tuple(Ws.shape) != (128, 384):
+        return False
+    if tuple(w_agg.shape) != (128, 128) or not w_agg.is_contiguous() or b_agg is None or tuple(b_agg.shape) != (128,) or not b_agg.is_contiguous():
+        return False
+    if alpha.numel() != 128 or not alpha.is_contiguous() or alpha.dtype != torch.float32 or alpha.data_ptr() % 16:
+        return False
+    for t in (m3, w_agg, Ws, out):
+        if t.dtype != torch.float32 or not _ld_ok(t):
+            return False
+    if b_agg.dtype != torch.float32 or b_agg.data_ptr() % 16:
+        return False
+    return not _overlap(m3, out)
+
+
+def sem_att_tail_ok(m3, w_agg, b_agg, alpha, Ws, out):
+    """operands the rollout's kernel covers: split mode, no autograd, the layout rules above.  No minimum row count."""
+    return CELL_MODE == "split_bf16" and not torch.is_grad_enabled() and _sem_att_operands_ok(m3, w_agg, b_agg, alpha, Ws, out)
+
+
+def sem_att_tail_train_ok(m3, w_agg, b_agg, alpha, Ws, addend):
+    """operands _SemAttTailTrain covers: split mode, the layout rules above, m3 and the addend dense.  No minimum row count."""
+    return (PROJ_MODE == "split_bf16" and _sem_att_operands_ok(m3, w_agg, b_agg, alpha, Ws, addend) and m3.is_contiguous()
+            and addend.is_contiguous())
+
+
+def sem_att_tail(m3, w_agg, b_agg, alpha, Ws, out):
+    """out <- sem_att_formula(.., addend=out), in place and without autograd: the rollout's encoder tail under the semantic attention as ONE
+    launch (include/mappo_ops.h dhgn_sem_att_tail); out may be a column block.  Operands the kernel does not cover take the formula."""
+    if not sem_att_tail_ok(m3, w_agg, b_agg, alpha, Ws, out):
+        with torch.no_grad():
+            out.copy_(sem_att_formula(m3, w_agg, b_agg, alpha, Ws, out))
+        return out
+    L = load_library()
+    _check(L.dhgn_sem_att_tail(m3.shape[0], _ptr(m3), m3.stride(0), _ptr(w_agg.detach()), _ptr(b_agg.detach()), _ptr(alpha.detach()), _ptr(Ws.detach()),
+                               Ws.stride(0), _ptr(out), out.stride(0), _ptr(out), out.stride(0), _stream()), "dhgn_sem_att_tail")
+    return out
+
+
+def sem_att_tail_train_fwd(m3, w_agg, b_agg, alpha, Ws, C, Y, emb, bits, gates):
+    """Y = sem_att_formula(.., addend=C) (C may be Y) with emb (Rs, 384), its sign bits (Rs, 48) and the gates (Rs, 3) written beside it
+    (include/mappo_ops.h dhgn_sem_att_tail_train).  No autograd, no checks beyond the entry point's."""
+    L = load_library()
+    _check(L.dhgn_sem_att_tail_train(m3.shape[0], _ptr(m3), m3.stride(0), _ptr(w_agg.detach()), _ptr(b_agg.detach()), _ptr(alpha.detach()),
+                                     _ptr(Ws.detach()), Ws.stride(0), _ptr(C), C.stride(0), _ptr(Y), Y.stride(0), _ptr(emb), emb.stride(0), _ptr(bits),
+                                     bits.stride(0), _ptr(gates), _stream()), "dhgn_sem_att_tail_train")
+    return Y
+
+
+def sem_att_tail_train_bwd(g, Ws, w_agg, alpha, emb, gates):
+    """-> (ga (Rs, 384), gate-scaled emb (Rs, 384), d_m3 (Rs, 384), column sums of ga (384,), d_alpha (128,)) for the gradient g (Rs, 128) of
+    the tail's result (include/mappo_ops.h dhgn_sem_att_tail_bwd).  No autograd."""
+    L = load_library()
+    Rs = g.shape[0]
+    ga, es, d_m3 = (torch.empty((Rs, 384), dtype=torch.float32, device=g.device) for _ in range(3))
+    cs = torch.empty(384, dtype=torch.float32, device=g.device)
+    da = torch.empty(128, dtype=torch.float32, device=g.device)
+    ws = torch.empty(L.dhgn_sem_att_tail_bwd_workspace(), dtype=torch.uint8, device=g.device)
+    _check(L.dhgn_sem_att_tail_bwd(Rs, _ptr(g), g.stride(0), _ptr(Ws.detach()), Ws.stride(0), _ptr(w_agg.detach()), _ptr(alpha.detach()), _ptr(emb),
+                                   emb.stride(0), _ptr(gates), _ptr(ga), ga.stride(0), _ptr(es), es.stride(0), _ptr(d_m3), d_m3.stride(0), _ptr(cs),
+                                   _ptr(da), _ptr(ws), _stream()), "dhgn_sem_att_tail_bwd")
+    return ga, es, d_m3, cs, da
+
+
+class _SemAttTailTrain(torch.autograd.Function):
+    """h0 = sem_att_formula(m3, w_agg, b_agg, alpha, Ws, addend), in place on the addend: one launch forward and one backward plus the two
+    weight-gradient products (csrc/sem_att.hpp)."""
+
+    @staticmethod
+    def forward(ctx, m3, w_agg, b_agg, alpha, Ws, addend):
+        Rs = m3.shape[0]
+        emb = torch.empty((Rs, 384), dtype=torch.float32, device=m3.device)
+        bits = torch.empty((Rs, 48), dtype=torch.uint8, device=m3.device)
+        gates = torch.empty((Rs, 3), dtype=torch.float32, device=m3.device)
+        ctx.mark_dirty(addend)
+        sem_att_tail_train_fwd(m3, w_agg, b_agg, alpha, Ws, addend, addend, emb, bits, gates)
+        ctx.save_for_backward(m3, emb, gates, w_agg, alpha, Ws)
+        return addend
+
+    @staticmethod
+    def backward(ctx, g):
+        m3, emb, gates, w_agg, alpha, Ws = ctx.saved_tensors
+        g2 = g.reshape(-1, 128)
+        if not _ld_ok(g2):
+            g2 = _dense16(g2)
+        ga, es, d_m3, cs, da = sem_att_tail_train_bwd(g2, Ws, w_agg, alpha, emb, gates)
+        need = ctx.needs_input_grad
+        dWa = wgrad(ga.view(-1, 128), m3.view(-1, 128)) if need[1] else None
+        db = cs.view(-1, 128).sum(0) if need[2] else None
+        dWs = wgrad(g2, es) if need[4] else None
+        return (d_m3 if need[0] else None), dWa, db, (da.view(alpha.shape) if need[3] else None), dWs, (g if need[5] else None)
+
+
+def sem_att_tail_train(m3, w_agg, b_agg, alpha, Ws, addend):
+    """h0 = sem_att_formula(..) under autograd.  fp32 CUDA operands in split mode take the fused node (in place on the addend, which must be
+    a temporary: it becomes the result); everything else the formula."""
+    if sem_att_tail_train_ok(m3, w_agg, b_agg, alpha, Ws, addend):
+        return _SemAttTailTrain.apply(m3, w_agg, b_agg, alpha, Ws, addend)
+    return sem_att_formula(m3, w_agg, b_agg, alpha, Ws, addend)
 
 
 # the update's Linear layers, their input gradients and the GRU input projections gi = x W_ih^T + b_ih: the BLAS library | sb_gemm

@@ -400,6 +400,30 @@ int sb_encoder_tail_train(int64_t Rs, const float *m3, int64_t ldx, const float 
 int64_t sb_encoder_tail_bwd_workspace(void);
 int sb_encoder_tail_bwd(int64_t Rs, const float *g, int64_t ldg, const float *Ws, int64_t ldw, const float *w_agg, const uint8_t *emb_sign_bits,
                         int64_t ld_bytes, float *ga, int64_t ldga, float *d_m3, int64_t ldd, float *colsum, void *workspace, void *stream);
+/* The encoder tail under the semantic-level ATTENTION aggregator (`algo.semantic_level_aggregator: att`; csrc/sem_att.hpp) -- ours:
+ * a softmax over the three relations between the AGG layer and the semantic layer.  For the Rs semantic rows s, with E = 128:
+ *   emb_r = relu(w_agg m3[s][r] + b_agg),  s_r = alpha . emb_r,  g_r = 3 exp(s_r - max s) / sum_q exp(s_q - max s)
+ *   Y[s]  = C[s] + sum over r of g_r Ws[:, 128 r .. 128 r + 127] emb_r                    (alpha = 0: g_r = 1, the mean tail's formula)
+ * Operands, strides and alignment as sb_encoder_tail (C may be Y, both may be column blocks; Ws a column block of the semantic weight);
+ * alpha [128] dense, 16-byte aligned.  Every row count is served (tiles of 16 rows); Rs == 0 succeeds and writes nothing.
+ * dhgn_sem_att_tail: the rollout's launch; the embedding does not reach memory.
+ * dhgn_sem_att_tail_train: the same bits in Y, and what the backward reads beside them: emb [Rs][384] (row stride lde), its sign bits
+ * emb_sign_bits [Rs][48] (row stride ld_bytes, sb_encoder_tail_train's layout) and the gates [Rs][3] (dense).
+ * dhgn_sem_att_tail_bwd: for the gradient g [Rs][128] (row stride ldg) of Y, with t_r = Ws_r^T g, c_r = t_r . emb_r,
+ *   ds_r = g_r (c_r - sum_q (g_q / 3) c_q),   ga[s][r] = (emb_r > 0) * (g_r t_r + ds_r alpha)   -> ga [Rs][384] (row stride ldga),
+ *   d_m3[s][r] = ga[s][r] w_agg -> d_m3 [Rs][384] (ldd),   emb_scaled[s][r] = g_r emb_r -> [Rs][384] (ldes; may be emb itself),
+ *   colsum[384] = column sums of ga,   d_alpha[128] = sum over s, r of ds_r emb_r.
+ * The weight gradients are the caller's two products: d Ws = g^T emb_scaled, d w_agg = ga^T m3.  Per-workgroup partial sums in `workspace`
+ * (>= dhgn_sem_att_tail_bwd_workspace() bytes, 16-byte aligned) are added in workgroup order: no atomics, the same bits every run. */
+int dhgn_sem_att_tail(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *alpha, const float *Ws, int64_t ldw,
+                      const float *C, int64_t ldc, float *Y, int64_t ldy, void *stream);
+int dhgn_sem_att_tail_train(int64_t Rs, const float *m3, int64_t ldx, const float *w_agg, const float *b_agg, const float *alpha, const float *Ws,
+                            int64_t ldw, const float *C, int64_t ldc, float *Y, int64_t ldy, float *emb, int64_t lde, uint8_t *emb_sign_bits,
+                            int64_t ld_bytes, float *gates, void *stream);
+int64_t dhgn_sem_att_tail_bwd_workspace(void);
+int dhgn_sem_att_tail_bwd(int64_t Rs, const float *g, int64_t ldg, const float *Ws, int64_t ldw, const float *w_agg, const float *alpha, const float *emb,
+                          int64_t lde, const float *gates, float *ga, int64_t ldga, float *emb_scaled, int64_t ldes, float *d_m3, int64_t ldd,
+                          float *colsum, float *d_alpha, void *workspace, void *stream);
 
 /* The GnnExtractor encoder's pair MLP and weighted sum, fused (csrc/gnn_pairs.hpp; GnnEncoder.forward's first half).  Entities of row r: the P
  * pursuers p [R][P][4], the evader e [R][4], the O obstacles o [R / q_div][O][4] (R % q_div == 0); K = P + 1 + O <= 1024, 1 <= P <= 64.
