@@ -14,6 +14,7 @@
 #include "att_agg.hpp"
 #include "fcra_att.hpp"
 #include "fcra_pool.hpp"
+#include "fcra_team.hpp"
 #include "pool_agg.hpp"
 #include "sem_att.hpp"
 
@@ -393,6 +394,54 @@ int fcra_pool_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *
         return MO_ERR_BAD_ARG;
     if (R == 0) return 0;
     return launch_fcra_pool_bwd(R, P, y, adj, adj_row_stride, out, out_stride, g, g_stride, dy, db, (float *)workspace, max_blocks, (hipStream_t)stream);
+}
+
+// a (T, episode stride, step stride) view whose rows are P dense vectors read as float2
+static bool ft_view_ok(int32_t P, int32_t T, int64_t es, int64_t ss) {
+    return es >= (int64_t)P * FT_E && !(es & 1) && (T == 1 || (ss >= (int64_t)P * FT_E && !(ss & 1)));
+}
+
+int fcra_team_fwd_multi(int32_t n_jobs, const mo_fcra_team_job *jobs, int32_t mode, int64_t R, int32_t P, int32_t E, int32_t T,
+                        int64_t ya_episode_stride, int64_t ya_step_stride, int64_t yc_episode_stride, int64_t yc_step_stride, const float *adj,
+                        int64_t adj_row_stride, int32_t relu, int64_t out_stride, int32_t max_blocks, void *stream) {
+    if (n_jobs < 1 || n_jobs > MO_FCRA_TEAM_MAX_JOBS || !jobs || (mode != MO_FCRA_TEAM_ATT && mode != MO_FCRA_TEAM_MEAN) || R < 0 || P < 1 ||
+        P > FT_MAX_P || E != FT_E || T < 1 || out_stride < FT_E || (out_stride & 1) || out_stride > FT_MAX_LD || max_blocks < 0 || ((uintptr_t)adj & 3) ||
+        (adj && adj_row_stride < (int64_t)P * P))
+        return MO_ERR_BAD_ARG;
+    const bool att = mode == MO_FCRA_TEAM_ATT;
+    FtJobs a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < n_jobs; k++) {
+        const mo_fcra_team_job &m = jobs[k];
+        if ((att ? !fa_ok8(m.bias) || !fa_ok8(m.alpha) : (m.bias && !fa_ok8(m.bias))) || (!m.out_actor && !m.out_critic)) return MO_ERR_BAD_ARG;
+        if (m.out_actor && (!adj || !fa_ok8(m.out_actor) || !fa_ok8(m.y_actor) || !ft_view_ok(P, T, ya_episode_stride, ya_step_stride)))
+            return MO_ERR_BAD_ARG;
+        if (m.out_critic && (!fa_ok8(m.out_critic) || !fa_ok8(m.y_critic) || !ft_view_ok(P, T, yc_episode_stride, yc_step_stride)))
+            return MO_ERR_BAD_ARG;
+        a.j[k] = m;
+    }
+    if (R == 0) return 0;
+    return launch_fcra_team_fwd(a, n_jobs, att, R, P, T, ya_episode_stride, ya_step_stride, yc_episode_stride, yc_step_stride, adj, adj_row_stride,
+                                att || relu, out_stride, max_blocks, (hipStream_t)stream);
+}
+
+int64_t fcra_team_bwd_workspace(int32_t E, int32_t max_blocks) {
+    if (E != FT_E || max_blocks < 0) return 0;
+    return (int64_t)(max_blocks > 0 && max_blocks < FT_MAX_GRID ? max_blocks : FT_MAX_GRID) * 2 * FT_E * 4;
+}
+
+int fcra_team_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *adj, int64_t adj_row_stride, const float *bias, const float *alpha,
+                  const float *out, int64_t out_stride, const float *g, int64_t g_stride, float *dy, float *db, float *d_alpha, void *workspace,
+                  int32_t max_blocks, void *stream) {
+    if (R < 0 || P < 1 || P > FT_MAX_P || E != FT_E || out_stride < FT_E || (out_stride & 1) || g_stride < FT_E || (g_stride & 1) || out_stride > FT_MAX_LD || g_stride > FT_MAX_LD || max_blocks < 0 ||
+        ((uintptr_t)adj & 3) || (adj && adj_row_stride < (int64_t)P * P))
+        return MO_ERR_BAD_ARG;
+    if (!fa_ok8(y) || !fa_ok8(bias) || !fa_ok8(alpha) || !fa_ok8(out) || !fa_ok8(g) || !fa_ok8(dy) || !db || !d_alpha || !workspace ||
+        ((uintptr_t)db & 3) || ((uintptr_t)d_alpha & 3) || ((uintptr_t)workspace & 15))
+        return MO_ERR_BAD_ARG;
+    if (R == 0) return 0;
+    return launch_fcra_team_bwd(R, P, y, adj, adj_row_stride, bias, alpha, out, out_stride, g, g_stride, dy, db, d_alpha, (float *)workspace, max_blocks,
+                                (hipStream_t)stream);
 }
 
 }  // extern "C"

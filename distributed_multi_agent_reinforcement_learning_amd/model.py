@@ -114,7 +114,26 @@ class DHGN(nn.Module):
             return ops.att_agg3(*args, [self.alpha[f"AGG_vertex_{r}"] for r in range(3)], is_critic, o_kvalid, q_div, e_ref)
         if self.pool:
             return ops.pool_agg3(*args, is_critic, o_kvalid, q_div, e_ref)
+        if self._large_team(p):
+            # the `mean` message kernels stop at 16 pursuers: above, the attention kernels with a ZERO alpha (u_ij = a_ij, the
+            # L1-normalised mean; a cached vector, no parameter -- its gradient is computed and dropped)
+            return ops.att_agg3(*args, [self._zero_alpha(p)] * 3, is_critic, o_kvalid, q_div, e_ref)
         return ops.msg_agg3(*args, is_critic, o_kvalid, q_div, e_ref)
+
+    def _large_team(self, p):
+        """more pursuers per row than the `mean` message kernels take: everything that shares a message pass between actor and
+        critic goes one launch per network instead, as under `att`"""
+        large = p.shape[1] > ops.FCRA_TEAM_MIN_P
+        if large and self.embedding_dim != 128:
+            raise ValueError(f"algo.embedding_dim={self.embedding_dim}: teams above {ops.FCRA_TEAM_MIN_P} pursuers need embedding_dim=128 "
+                             "(the large-team kernels exist for that width only)")
+        return large
+
+    def _zero_alpha(self, p):
+        z = self.__dict__.get("_zero_alpha_vec")
+        if z is None or z.device != p.device or z.dtype != p.dtype:
+            z = self.__dict__["_zero_alpha_vec"] = torch.zeros(self.embedding_dim, dtype=p.dtype, device=p.device)
+        return z
 
     # -- encoder (:241-304) ----------------------------------------------------------------------------
     def encoder(self, p, e, o, adj_p, adj_e, adj_o, is_critic, o_kvalid=None, q_div=1, out=None, e_ref=None):
@@ -169,7 +188,7 @@ class DHGN(nn.Module):
         """the update's encoder of actor and critic together -> (h0_actor, h0_critic): one message pass for both networks
         (ops.msg_agg3_pair_train), then the layers per network; same numbers as encoder(.., False) and encoder(.., True)."""
         M = self.MSG_layers
-        if self.att or self.pool:   # no shared pass under the softmax or the maximum: one launch per network
+        if self.att or self.pool or self._large_team(p):   # no shared pass under the softmax or the maximum: one launch per network
             m3a, m3c = [self._messages(p, e, o, adj_p, adj_e, adj_o, c, None, q_div, e_ref) for c in (False, True)]
         else:
             m3a, m3c = ops.msg_agg3_pair_train(p, e, o, adj_p, adj_e, adj_o, M[0].weight, M[0].bias, M[1].weight, M[1].bias, M[2].weight, M[2].bias,
@@ -228,8 +247,9 @@ class DHGN(nn.Module):
         else:
             h0 = out if out is not None else torch.empty((2, R, P, E), dtype=p.dtype, device=p.device)
         h0_2d = ops.block2d(h0)
-        fused_pos = ind == 4 and not (self.att or self.pool)
-        if self.att or self.pool:   # one launch per network (the weights differ per neighbour / the maxima per list: no sum shared by both)
+        per_net = self.att or self.pool or self._large_team(p)
+        fused_pos = ind == 4 and not per_net
+        if per_net:   # one launch per network (the weights differ per neighbour / the maxima per list: no sum shared by both)
             with torch.no_grad():
                 m3 = torch.stack([self._messages(p, e, o, adj_p, adj_e, adj_o, False, None, q_div, e_ref),
                                   self._messages(p, e, o, adj_p, adj_e, adj_o, True, o_kvalid, q_div, e_ref)])

@@ -67,8 +67,17 @@ class N2nMAPPO(ParticleMAPPO):
         if str(a.get("e3d_comm", "none")) != "none":
             raise ValueError(f"algo.e3d_comm: {a.get('e3d_comm')} is built for runtime.env e3d only; the DHGN encoder of env_n2n already passes "
                              "messages along pp_adj (leave the key out)")
-        if int(cfg.env.num_defender) > MAX_P:
-            raise ValueError(f"env.num_defender={cfg.env.num_defender}: the DHGN message kernels take at most {MAX_P} pursuers per row")
+        P, large = int(cfg.env.num_defender), bool(a.get("large_teams", False))
+        if P > MAX_P and not large:
+            raise ValueError(f"env.num_defender={P}: the DHGN message kernels take at most {MAX_P} pursuers per row; "
+                             f"algo.large_teams: true accepts up to {ops.FCRA_TEAM_MAX_P} (DESIGN 7x)")
+        if P > ops.FCRA_TEAM_MAX_P:
+            raise ValueError(f"env.num_defender={P}: at most {ops.FCRA_TEAM_MAX_P} pursuers (env_n2n and the large-team kernels)")
+        if P > MAX_P and str(a.get("fcra_aggregator", "mean")) == "pool":
+            raise ValueError(f"algo.fcra_aggregator: pool takes at most {MAX_P} pursuers (env.num_defender={P}); the large-team kernels "
+                             "serve mean and att")
+        if P > MAX_P and int(a.embedding_dim) != 128:
+            raise ValueError(f"algo.embedding_dim={a.embedding_dim}: teams above {MAX_P} pursuers need 128 (the large-team kernels' only width)")
         if int(cfg.env.state_dim) != 4 or int(cfg.env.action_dim) != 9 or int(a.num_relation) != 3:
             raise ValueError("env_n2n runs the pursuit model: env.state_dim 4, env.action_dim 9, algo.num_relation 3")
         self.depth = int(a.depth)

@@ -26,7 +26,7 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "team_comm_mask_host", "team_attention_fwd_host", "team_attention_bwd_host", "gnn_pair_agg_fwd", "gnn_pair_agg_bwd",
            "gnn_pair_agg_bwd_workspace", "dhgn_att_agg3_fwd", "dhgn_att_agg_bwd", "dhgn_att_agg_bwd_workspace", "fcra_att_fwd_multi", "fcra_att_bwd",
            "fcra_att_bwd_workspace", "dhgn_pool_agg3_fwd", "dhgn_pool_agg_bwd", "dhgn_pool_agg_bwd_workspace", "fcra_pool_fwd_multi", "fcra_pool_bwd",
-           "fcra_pool_bwd_workspace", "mappo_ops_error_string")
+           "fcra_pool_bwd_workspace", "fcra_team_fwd_multi", "fcra_team_bwd", "fcra_team_bwd_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -182,6 +182,10 @@ def load_library():
         L.fcra_pool_bwd_workspace.argtypes = [i32, i32]
         L.fcra_pool_bwd_workspace.restype = i64
         L.fcra_pool_bwd.argtypes = [i64, i32, i32, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp]
+        L.fcra_team_fwd_multi.argtypes = [i32, vp, i32, i64, i32, i32, i32, i64, i64, i64, i64, vp, i64, i32, i64, i32, vp]
+        L.fcra_team_bwd_workspace.argtypes = [i32, i32]
+        L.fcra_team_bwd_workspace.restype = i64
+        L.fcra_team_bwd.argtypes = L.fcra_att_bwd.argtypes
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
         _lib = L
@@ -1136,10 +1140,35 @@ def fcra_mean(z_actor=None, z_critic=None, adj=None, bias=None, relu=False, out=
     o_a = (out[0] if both else out) if z_actor is not None else None
     o_c = (out[1] if both else out) if z_critic is not None else None
     adj3 = adj.reshape(R, P, P) if adj is not None else None
+    if P > FCRA_TEAM_MIN_P:   # large teams: the matrix-pipe kernels (csrc/fcra_team.hpp)
+        b = None if bias is None else _dense16(bias.detach())
+        _fcra_team_fwd([(za, zc, b, None, o_a, o_c)], FCRA_TEAM_MEAN, R, P, T, (a_es, a_ts, c_es, c_ts), adj3, relu, out_ld)
+        return out
     _check(L.fcra_neighbour_mean(R, P, E, T, _ptr(za), a_es, a_ts, _ptr(zc), c_es, c_ts, _ptr(adj3), adj3.stride(0) if adj3 is not None else 0,
                                  _ptr(bias.detach() if bias is not None else None), int(bool(relu)), _ptr(o_a), _ptr(o_c), out_ld, _stream()),
            "fcra_neighbour_mean")
     return out
+
+
+FCRA_TEAM_MIN_P = 16      # teams ABOVE this take csrc/fcra_team.hpp (include/mappo_ops.h fcra_team_*); up to it nothing changes
+FCRA_TEAM_MAX_P = 64
+FCRA_TEAM_ATT, FCRA_TEAM_MEAN = 0, 1   # include/mappo_ops.h MO_FCRA_TEAM_ATT / MO_FCRA_TEAM_MEAN
+fcra_team_calls = 0       # forward launches of the large-team kernels so far (tests)
+
+
+def _fcra_team_fwd(jobs, mode, R, P, T, strides, adj3, relu, out_ld, max_blocks=0):
+    """one launch of the large-team kernels; jobs: (y_actor, y_critic, bias, alpha, out_actor, out_critic) tensors or None (the layout of
+    FcraAttJob = mo_fcra_team_job); strides: the (episode, step) strides of the actor's and the critic's view (see _nbr_view)"""
+    global fcra_team_calls
+    if jobs[0][0 if jobs[0][0] is not None else 1].shape[-1] != 128:
+        raise RuntimeError(f"fcra (teams above {FCRA_TEAM_MIN_P} pursuers): the large-team kernels exist for embedding_dim 128 only")
+    arr = (FcraAttJob * len(jobs))()
+    for a, job in zip(arr, jobs):
+        a.y_actor, a.y_critic, a.bias, a.alpha, a.out_actor, a.out_critic = [None if t is None else t.data_ptr() for t in job]
+    _check(load_library().fcra_team_fwd_multi(len(jobs), C.cast(arr, C.c_void_p), mode, R, P, 128, T, *strides, _ptr(adj3),
+                                              adj3.stride(0) if adj3 is not None else 0, int(bool(relu)), out_ld, max_blocks, _stream()),
+           "fcra_team_fwd_multi")
+    fcra_team_calls += 1
 
 
 class NbrJob(C.Structure):
@@ -1168,6 +1197,10 @@ def fcra_mean_pair_multi(zas, zcs, adj, biases, outs):
         a.z_actor, a.z_critic, a.bias, a.out_actor, a.out_critic = za.data_ptr(), zc.data_ptr(), b.data_ptr(), o[0].data_ptr(), o[1].data_ptr()
     adj3 = adj.reshape(R, P, P)
     assert adj3.dtype == torch.float32 and _rows_ok(adj3)
+    if P > FCRA_TEAM_MIN_P:
+        _fcra_team_fwd([(zas[k], zcs[k], _dense16(keep[k]), None, outs[k][0], outs[k][1]) for k in range(n)], FCRA_TEAM_MEAN, R, P, 1,
+                       (P * E, 0, P * E, 0), adj3, True, out_ld)
+        return
     _check(L.fcra_neighbour_mean_multi(n, C.cast(arr, C.c_void_p), R, P, E, 1, P * E, 0, P * E, 0, _ptr(adj3), adj3.stride(0), 1, out_ld, _stream()),
            "fcra_neighbour_mean_multi")
 
@@ -1198,6 +1231,8 @@ def fcra_att_formula(y, adj, bias, alpha):
 def _fcra_att_fwd(jobs, R, P, adj3, out_ld, max_blocks=0):
     """one launch; jobs: (y_actor, y_critic, bias, alpha, out_actor, out_critic) tensors or None, bias / alpha dense (128,)"""
     global fcra_att_calls
+    if P > FCRA_TEAM_MIN_P:
+        return _fcra_team_fwd(jobs, FCRA_TEAM_ATT, R, P, 1, (P * 128, 0, P * 128, 0), adj3, True, out_ld, max_blocks)
     arr = (FcraAttJob * len(jobs))()
     for a, job in zip(arr, jobs):
         a.y_actor, a.y_critic, a.bias, a.alpha, a.out_actor, a.out_critic = [None if t is None else t.data_ptr() for t in job]
@@ -1211,12 +1246,15 @@ def _fcra_att_bwd(y3, adj3, bias, alpha, out, out_ld, g, g_ld, max_blocks=0):
     L = load_library()
     R, P, E = y3.shape
     dy, db, dal = torch.empty_like(y3), torch.empty_like(bias), torch.empty_like(alpha)
-    key = (y3.device, "fcra_att", max_blocks, torch.cuda.current_stream().cuda_stream)
+    team = P > FCRA_TEAM_MIN_P
+    key = (y3.device, "fcra_team" if team else "fcra_att", max_blocks, torch.cuda.current_stream().cuda_stream)
     ws = _workspaces.get(key)
     if ws is None:
-        ws = _workspaces[key] = torch.empty(L.fcra_att_bwd_workspace(E, max_blocks), dtype=torch.uint8, device=y3.device)
-    _check(L.fcra_att_bwd(R, P, E, _ptr(y3), _ptr(adj3), adj3.stride(0) if adj3 is not None else 0, _ptr(bias), _ptr(alpha), _ptr(out), out_ld, _ptr(g), g_ld,
-                          _ptr(dy), _ptr(db), _ptr(dal), _ptr(ws), max_blocks, _stream()), "fcra_att_bwd")
+        ws = _workspaces[key] = torch.empty((L.fcra_team_bwd_workspace if team else L.fcra_att_bwd_workspace)(E, max_blocks), dtype=torch.uint8,
+                                            device=y3.device)
+    _check((L.fcra_team_bwd if team else L.fcra_att_bwd)(R, P, E, _ptr(y3), _ptr(adj3), adj3.stride(0) if adj3 is not None else 0, _ptr(bias), _ptr(alpha), _ptr(out), out_ld, _ptr(g), g_ld,
+                                                         _ptr(dy), _ptr(db), _ptr(dal), _ptr(ws), max_blocks, _stream()),
+           "fcra_team_bwd" if team else "fcra_att_bwd")
     return dy, db, dal
 
 
@@ -1320,6 +1358,9 @@ def fcra_pool_formula(y, adj, bias):
 def _fcra_pool_fwd(jobs, R, P, adj3, out_ld, max_blocks=0):
     """one launch; jobs: (y_actor, y_critic, bias, out_actor, out_critic) tensors or None, bias dense (128,)"""
     global fcra_pool_calls
+    if P > FCRA_TEAM_MIN_P:
+        raise RuntimeError(f"fcra_pool: the max-pool kernels take teams of up to {FCRA_TEAM_MIN_P} pursuers (got {P}); above that, set "
+                           "algo.fcra_aggregator to 'mean' or 'att'")
     arr = (FcraPoolJob * len(jobs))()
     for a, job in zip(arr, jobs):
         a.y_actor, a.y_critic, a.bias, a.out_actor, a.out_critic = [None if t is None else t.data_ptr() for t in job]

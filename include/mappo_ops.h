@@ -761,6 +761,36 @@ int fcra_pool_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *
                   const float *g, int64_t g_stride, float *dy, float *db, void *workspace, int32_t max_blocks, void *stream);
 
 /*
+ * The FCRA hop aggregators for LARGE TEAMS (csrc/fcra_team.hpp): per row a (P x P) weight matrix times the (P x E) block of
+ * vectors on the fp32 matrix pipe, a row per workgroup.  1 <= P <= 64, E == 128 only.  The numbers are those specified above:
+ *   mode MO_FCRA_TEAM_ATT   fcra_att_fwd_multi's (alpha per job; bias required; relu is ignored: always applied);
+ *   mode MO_FCRA_TEAM_MEAN  fcra_neighbour_mean_multi's: w_ij = a_ij / max(sum_j |a_ij|, 1e-12), critic a = ones; bias may be NULL, ReLU
+ *                           when relu != 0; alpha is not read.  Forward only.
+ * fcra_team_fwd_multi: up to MO_FCRA_TEAM_MAX_JOBS jobs of one shape in ONE launch, either output of a job may be NULL; a job whose actor
+ * and critic read the same vectors through the same strides is staged (and scored) once.  y_* are read in place: row r = (r / T, r % T)
+ * starts at (r / T) * episode_stride + (r % T) * step_stride (T = 1, episode_stride = P E: a dense [R][P][E] tensor), its P vectors dense.
+ * out_*: [R][P] vectors of E floats out_stride (even, E .. 2^20) elements apart (2 E: the left half of an [agg | h] operand; the other half
+ * is not touched).  max_blocks: 0 = the default grid; > 0 caps the persistent workgroups (one row in flight each).
+ * fcra_team_bwd (att): fcra_att_bwd's contract (one job, one network, adj NULL: ones; dy, db, d_alpha OVERWRITTEN; workspace of at least
+ * fcra_team_bwd_workspace(E, max_blocks) bytes, 16-byte aligned; no atomics, the same bits from run to run, a row's bits depend on that
+ * row's inputs only).
+ * y, out, g, dy, bias, alpha 8-byte aligned, T >= 1, episode and step strides even (episode >= P E; step >= P E when T > 1).  Anything
+ * else, a NULL or misaligned pointer, an actor output without adj, a stride below E or odd: MO_ERR_BAD_ARG before any launch or write.
+ * R == 0 succeeds and writes nothing.
+ */
+#define MO_FCRA_TEAM_MAX_JOBS 8
+#define MO_FCRA_TEAM_ATT 0
+#define MO_FCRA_TEAM_MEAN 1
+typedef struct mo_fcra_team_job { const float *y_actor, *y_critic, *bias, *alpha; float *out_actor, *out_critic; } mo_fcra_team_job;
+int fcra_team_fwd_multi(int32_t n_jobs, const mo_fcra_team_job *jobs, int32_t mode, int64_t R, int32_t P, int32_t E, int32_t T,
+                        int64_t ya_episode_stride, int64_t ya_step_stride, int64_t yc_episode_stride, int64_t yc_step_stride, const float *adj,
+                        int64_t adj_row_stride, int32_t relu, int64_t out_stride, int32_t max_blocks, void *stream);
+int64_t fcra_team_bwd_workspace(int32_t E, int32_t max_blocks);
+int fcra_team_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *adj, int64_t adj_row_stride, const float *bias, const float *alpha,
+                  const float *out, int64_t out_stride, const float *g, int64_t g_stride, float *dy, float *db, float *d_alpha, void *workspace,
+                  int32_t max_blocks, void *stream);
+
+/*
  * ReLU backward and the bias gradient of the Linear in front of it in one pass (autograd: aten::threshold_backward, then
  * grad.sum(0) re-reading it; MAPPO.train's loss.backward(), DHGN/mappo_parallel.py:660-708):
  *   gin [R][F] = gout * [y > 0] (y = the saved ReLU output);  colsum [F] = sum_r gin[r][:].
