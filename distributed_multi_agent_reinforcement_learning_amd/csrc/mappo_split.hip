@@ -15,6 +15,7 @@
 #include "fcra_att.hpp"
 #include "fcra_pool.hpp"
 #include "fcra_team.hpp"
+#include "layer_norm.hpp"
 #include "pool_agg.hpp"
 #include "sem_att.hpp"
 
@@ -442,6 +443,54 @@ int fcra_team_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *
     if (R == 0) return 0;
     return launch_fcra_team_bwd(R, P, y, adj, adj_row_stride, bias, alpha, out, out_stride, g, g_stride, dy, db, d_alpha, (float *)workspace, max_blocks,
                                 (hipStream_t)stream);
+}
+
+// rows of FN_E floats ld apart: a stride the float2 lanes can take
+static bool fn_ld_ok(int64_t ld) { return ld >= FN_E && !(ld & 1); }
+// do R rows from a (ld_a apart) and R rows from b (ld_b apart) share a byte?  (as whole extents: a view inside the other's gaps is refused too)
+static bool fn_overlap(const float *a, int64_t ld_a, const float *b, int64_t ld_b, int64_t R) {
+    const int64_t rows = R > 0 ? R - 1 : 0;
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)(rows * ld_a + FN_E) * 4, b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)(rows * ld_b + FN_E) * 4;
+    return a0 < b1 && b0 < a1;
+}
+static bool fn_common_ok(int32_t n_jobs, const mo_feat_norm_job *jobs, int64_t R, int32_t width, float eps, int32_t max_blocks) {
+    return n_jobs >= 1 && n_jobs <= MO_FEAT_NORM_MAX_JOBS && jobs && R >= 0 && width == FN_E && isfinite(eps) && eps > 0.f && max_blocks >= 0;
+}
+
+int feat_norm_fwd_multi(int32_t n_jobs, const mo_feat_norm_job *jobs, int64_t R, int32_t width, float eps, int32_t max_blocks, void *stream) {
+    if (!fn_common_ok(n_jobs, jobs, R, width, eps, max_blocks)) return MO_ERR_BAD_ARG;
+    FnJobs a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < n_jobs; k++) {
+        const mo_feat_norm_job &m = jobs[k];
+        if (!fa_ok8(m.x) || !fa_ok8(m.weight) || !fa_ok8(m.bias) || !fa_ok8(m.y) || !fn_ld_ok(m.ldx) || !fn_ld_ok(m.ldy) ||
+            fn_overlap(m.x, m.ldx, m.y, m.ldy, R))
+            return MO_ERR_BAD_ARG;
+        a.j[k] = m;
+    }
+    if (R == 0) return 0;
+    return launch_feat_norm_fwd(a, n_jobs, R, eps, max_blocks, (hipStream_t)stream);
+}
+
+int64_t feat_norm_bwd_workspace(int32_t width, int32_t n_jobs, int32_t max_blocks) {
+    if (width != FN_E || n_jobs < 1 || n_jobs > MO_FEAT_NORM_MAX_JOBS || max_blocks < 0) return 0;
+    return (int64_t)n_jobs * (max_blocks > 0 && max_blocks < FN_MAX_GRID ? max_blocks : FN_MAX_GRID) * 2 * FN_E * 4;
+}
+
+int feat_norm_bwd_multi(int32_t n_jobs, const mo_feat_norm_job *jobs, int64_t R, int32_t width, float eps, void *workspace, int32_t max_blocks,
+                        void *stream) {
+    if (!fn_common_ok(n_jobs, jobs, R, width, eps, max_blocks) || !workspace || ((uintptr_t)workspace & 15)) return MO_ERR_BAD_ARG;
+    FnJobs a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < n_jobs; k++) {
+        const mo_feat_norm_job &m = jobs[k];
+        if (!fa_ok8(m.x) || !fa_ok8(m.weight) || !fa_ok8(m.g) || !fa_ok8(m.dx) || !fa_ok8(m.d_weight) || !fa_ok8(m.d_bias) || !fn_ld_ok(m.ldx) ||
+            !fn_ld_ok(m.ldg) || !fn_ld_ok(m.lddx) || fn_overlap(m.x, m.ldx, m.dx, m.lddx, R))
+            return MO_ERR_BAD_ARG;
+        a.j[k] = m;
+    }
+    if (R == 0) return 0;
+    return launch_feat_norm_bwd(a, n_jobs, R, eps, (float *)workspace, max_blocks, (hipStream_t)stream);
 }
 
 }  // extern "C"

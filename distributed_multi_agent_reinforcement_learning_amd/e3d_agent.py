@@ -42,7 +42,7 @@ from . import obs_norm as onorm
 from . import ops
 from . import value_norm as vnorm
 from .e3d_env import CENTRAL_MAX_P, EVADER_OBS, PURSUIT_FEAT, ParticleEnv, central_feat
-from .model import HeadLinear, _make_linear, _ortho_linear, _Trunk
+from .model import FEAT_NORM_KEY, HeadLinear, _make_linear, _ortho_linear, _Trunk, layer_norm_options, norm_pair, norm_rollout
 from .particle_agent import ParticleMAPPO, ParticleTrainer, finish_env, train_particle
 
 FEAT = 16   # e3d_policy_features columns (include/e3d_env.h); algo.e3d_features: pursuit has PURSUIT_FEAT
@@ -127,6 +127,8 @@ class _E3dRollout:
         self.fa, self.fc = z(N, P, agent.feat_dim), z(N, P, agent.critic_feat_dim)
         self.hbuf_a, self.hbuf_c = z(2, L, N * P, H), z(2, L, N * P, H)
         self.action, self.env_action, self.logp, self.v = z(N, P, U), z(N, P, A, dt=torch.float64), z(N, P), z(N, P)
+        if agent.use_layer_norm:   # the normalised GRU features of a tick (the GRU's own output is the recurrent state: never in place)
+            self.na, self.nc = z(N * P, H), z(N * P, H)
         self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.live = z(N, P)   # this step's live mask (e3d_policy_record keeps it current)
@@ -227,6 +229,7 @@ class E3dMAPPO(ParticleMAPPO):
         # the width of the critic's rows; feat_dim stays the actor's
         self.critic_feat_dim = central_feat(int(cfg.env.num_defender)) if self.e3d_critic == "central" else self.feat_dim
         self.e3d_comm, self.e3d_comm_heads = e3d_comm_options(cfg)   # team attention in the actor
+        self.use_layer_norm = layer_norm_options(cfg)   # LayerNorm between the GRUs and the heads
         self.use_obs_norm, self.obs_norm_clip = onorm.obs_norm_options(cfg)   # running mean / std on the policy features
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
@@ -253,6 +256,8 @@ class E3dMAPPO(ParticleMAPPO):
         if self.e3d_comm == "attention":   # constructed last, after the critic: every other parameter keeps the generator draws of `none`
             self.actor.comm = TeamComm(self.embedding_dim, self.e3d_comm_heads).to(self.device)
             self.ac_parameters += list(self.actor.comm.parameters())
+        if self.use_layer_norm:   # after every other parameter and without a draw; last in ac_parameters: the actor's, then the critic's
+            self.ac_parameters += self.actor.add_feat_norm() + self.critic.add_feat_norm()
         self.obs_norm = onorm.ObsNorm(self.obs_norm_clip, self.device) if self.use_obs_norm else None
 
     # ---- rollout -------------------------------------------------------------------------------------------------------------
@@ -273,6 +278,8 @@ class E3dMAPPO(ParticleMAPPO):
         cur, nxt = st.t & 1, (st.t + 1) & 1
         fa, fc = ops.gru_step_multi([emb_a.reshape(-1, E), emb_c.reshape(-1, E)], [st.hbuf_a[cur], st.hbuf_c[cur]], [self.actor.GRU, self.critic.GRU],
                                     hiddens_out=[st.hbuf_a[nxt], st.hbuf_c[nxt]])
+        if self.use_layer_norm:
+            fa, fc = norm_rollout([self.actor, self.critic], [fa, fc], [st.na, st.nc])
         self.critic.head(fc.contiguous(), out=st.v)
         m = self.actor.Mean
         if self.policy_ex:
@@ -306,6 +313,8 @@ class E3dMAPPO(ParticleMAPPO):
         N, P = st.N, st.P
         emb_c = self.critic.shared_net(st.fc.view(N * P, self.critic_feat_dim))
         (fc,) = ops.gru_step_multi([emb_c.reshape(N * P, -1)], [st.hbuf_c[st.t & 1]], [self.critic.GRU], hiddens_out=[st.hbuf_c[(st.t + 1) & 1]])
+        if self.use_layer_norm:
+            (fc,) = norm_rollout([self.critic], [fc], [st.nc])
         return self.critic.head(fc.contiguous()).reshape(N, P)
 
     def new_buffer(self, N, T, P):
@@ -384,7 +393,7 @@ class E3dMAPPO(ParticleMAPPO):
             emb_a = self.actor.comm(emb_a, words.reshape(batch * steps, P))
         h0 = [torch.zeros(m.num_layers, batch * P, m.rnn_hidden_dim, dtype=emb_a.dtype, device=emb_a.device) for m in (self.actor, self.critic)]
         fa, fc = ops.gru_multi([emb_a, emb_c], h0, [self.actor.GRU, self.critic.GRU], agents=P, steps=steps, zero_state=True)
-        fa, fc = fa.reshape(steps, batch, P, -1), fc.reshape(steps, batch, P, -1)
+        fa, fc = norm_pair(self.actor, self.critic, fa.reshape(steps, batch, P, -1), fc.reshape(steps, batch, P, -1))
         mu = self.actor.Mean(fa).permute(1, 0, 2, 3)
         values = self.critic.Mean(fc).permute(1, 0, 2, 3)[..., 0]
         if not return_ls_raw:
@@ -447,6 +456,8 @@ class E3dMAPPO(ParticleMAPPO):
             meta.update(e3d_critic=self.e3d_critic)
         if getattr(self, "e3d_comm", "none") == "attention":
             meta.update(e3d_comm=self.e3d_comm, e3d_comm_heads=self.e3d_comm_heads)
+        if getattr(self, "use_layer_norm", False):
+            meta.update(use_layer_norm=True)
         return meta or None
 
     def check_policy_meta(self, meta, what):
@@ -456,6 +467,9 @@ class E3dMAPPO(ParticleMAPPO):
         entries was written with basic, sensed, local): other inputs fit neither the first layer nor what the weights were trained on;
         and e3d_comm with, where it is on, its head count (a file without the entry was written with none): the actor has the layer or not"""
         meta = meta or {}
+        theirs, mine = bool(meta.get("use_layer_norm", False)), bool(getattr(self, "use_layer_norm", False))
+        if theirs != mine:   # (a file without the entry was written with false: the networks have feat_norm or not)
+            raise ValueError(f"{what} was written with {FEAT_NORM_KEY}: {str(theirs).lower()}, this agent has {FEAT_NORM_KEY}: {str(mine).lower()}")
         for key, default in (("e3d_features", "basic"), ("e3d_evader_obs", "sensed"), ("e3d_critic", "local"), ("e3d_comm", "none"),
                              ("gauss_std", "param"), ("gauss_squash", "clip")):
             theirs, mine = meta.get(key, default), getattr(self, key, default)

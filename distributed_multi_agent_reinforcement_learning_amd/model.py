@@ -342,11 +342,64 @@ def _o_adj(obs):
     return obs["o_adj_bits"] if "o_adj_bits" in obs else obs["o_adj"]
 
 
+FEAT_NORM_KEY = "algo.use_layer_norm"
+
+
+def layer_norm_key(cfg):
+    """-> algo.use_layer_norm as a bool (default false); a command-line `true` / `false` arrives as a string and means what it says"""
+    v = cfg.algo.get("use_layer_norm", False)
+    if isinstance(v, str) and v.lower() in ("true", "false"):
+        v = v.lower() == "true"
+    if not isinstance(v, bool):
+        raise ValueError(f"{FEAT_NORM_KEY}: {v!r} is not true or false")
+    return v
+
+
+def layer_norm_options(cfg):
+    """-> algo.use_layer_norm (default false), validated: the kernels' only width is 128"""
+    on = layer_norm_key(cfg)
+    if on and int(cfg.algo.rnn_hidden_dim) != ops.FEAT_NORM_E:
+        raise ValueError(f"{FEAT_NORM_KEY}: true needs algo.rnn_hidden_dim {ops.FEAT_NORM_E} (the LayerNorm kernels' only width), "
+                         f"got algo.rnn_hidden_dim={cfg.algo.rnn_hidden_dim}")
+    return on
+
+
+def check_layer_norm_keys(agent, keys, what):
+    """ValueError naming the key when a file's state_dict keys belong to the other algo.use_layer_norm (before any tensor is loaded)"""
+    theirs, mine = any(k.startswith("feat_norm.") for k in keys), bool(getattr(agent, "use_layer_norm", False))
+    if theirs != mine:
+        raise ValueError(f"{what} was written with {FEAT_NORM_KEY}: {str(theirs).lower()}, this agent has {FEAT_NORM_KEY}: {str(mine).lower()}")
+
+
+class FeatNorm(nn.Module):
+    """the LayerNorm between the GRU stack and the heads (algo.use_layer_norm): weight ones, bias zeros -- no draw from the generator"""
+    eps = 1e-5
+
+    def __init__(self, width):
+        super().__init__()
+        self.weight, self.bias = nn.Parameter(torch.ones(width)), nn.Parameter(torch.zeros(width))
+
+
 class _Trunk(nn.Module):
     """shared_net -> GRU -> Mean, common to actor and critic.  use_rnn = False is the "MLP" ablation BASELINE config 1 names
     (the reference parses --use_rnn, MAPPO_parallel_main.py:261, and never reads it): encoder -> head, the GRU (whose
-    parameters stay in the module, so checkpoints keep their keys) is bypassed and the hidden state passes through untouched."""
+    parameters stay in the module, so checkpoints keep their keys) is bypassed and the hidden state passes through untouched.
+    use_layer_norm (algo.use_layer_norm; add_feat_norm): `feat_norm` normalises what feeds the heads."""
     use_rnn = True
+    use_layer_norm = False
+
+    def add_feat_norm(self):
+        """called once every other parameter exists: the new keys are the state_dict's last and the rest keeps its bits"""
+        self.feat_norm = FeatNorm(self.rnn_hidden_dim).to(self.GRU.weight_hh_l0.device)
+        self.use_layer_norm = True
+        return list(self.feat_norm.parameters())
+
+    def norm_features(self, feat):
+        """GRU features -> what the heads read, for the module's own forward paths (the agents normalise actor and critic together:
+        norm_pair below and ops.feat_norm in the rollout)"""
+        if not self.use_layer_norm:
+            return feat
+        return ops.feat_norm_train([feat], [self.feat_norm.weight], [self.feat_norm.bias], FeatNorm.eps)[0]
 
     def _rollout_features(self, embedding, hidden_state, inplace_hidden=False):
         R, P, E = embedding.shape
@@ -424,8 +477,8 @@ class SharedActor(_Trunk):
                               False, None, obs.get("q_div", 1), emb_out)
         if mode == 0:
             feat, hidden_state = self._rollout_features(emb, hidden_state, inplace_hidden)
-            return torch.softmax(self.Mean(feat), dim=-1), hidden_state, emb
-        feat = self._sequence_features(emb, batch, steps)                       # (steps, batch, P, H)
+            return torch.softmax(self.Mean(self.norm_features(feat)), dim=-1), hidden_state, emb
+        feat = self.norm_features(self._sequence_features(emb, batch, steps))  # (steps, batch, P, H)
         prob = torch.softmax(self.Mean(feat), dim=-1).permute(1, 0, 2, 3)       # the (.., A) result is what gets permuted
         return prob, None, emb
 
@@ -454,8 +507,8 @@ class SharedCritic(_Trunk):
                               True, kvalid, obs.get("q_div", 1), emb_out)
         if mode == 0:
             feat, hidden_state = self._rollout_features(emb, hidden_state, inplace_hidden)
-            return self.head(feat), hidden_state, emb
-        feat = self._sequence_features(emb, batch, steps)                       # (steps, batch, P, H)
+            return self.head(self.norm_features(feat)), hidden_state, emb
+        feat = self.norm_features(self._sequence_features(emb, batch, steps))  # (steps, batch, P, H)
         return self.Mean(feat).permute(1, 0, 2, 3)
 
 
@@ -475,8 +528,23 @@ def pair_embeddings(actor, critic, obs, hist_a, hist_c):
     return emb_a, emb_c
 
 
+def norm_pair(actor, critic, feat_a, feat_c):
+    """algo.use_layer_norm: both networks' GRU features through their feat_norm in ONE launch each way (ops.feat_norm_train); off: as
+    they are"""
+    if not actor.use_layer_norm:
+        return feat_a, feat_c
+    na, nc = actor.feat_norm, critic.feat_norm
+    return ops.feat_norm_train([feat_a, feat_c], [na.weight, nc.weight], [na.bias, nc.bias], FeatNorm.eps)
+
+
+def norm_rollout(nets, feats, outs):
+    """the rollout's form of norm_pair (no autograd): `feats` of `nets` into the static storage `outs`, one launch -> outs"""
+    return ops.feat_norm(feats, [m.feat_norm.weight for m in nets], [m.feat_norm.bias for m in nets], FeatNorm.eps, outs)
+
+
 def pair_heads(actor, critic, feat_a, feat_c):
     """the output layers on time-major GRU features (steps, batch, P, H) -> prob (batch, steps, P, A), values (batch, steps, P, 1)"""
+    feat_a, feat_c = norm_pair(actor, critic, feat_a, feat_c)
     return torch.softmax(actor.Mean(feat_a), dim=-1).permute(1, 0, 2, 3), critic.Mean(feat_c).permute(1, 0, 2, 3)
 
 
@@ -514,6 +582,8 @@ def build_actor_critic(cfg, device):
         raise ValueError(f"algo.encoder={kind!r}: 'dhgn' or 'gnn_extractor'")
     actor = SharedActor(enc, cfg.algo.embedding_dim, cfg.env.action_dim, cfg.algo.num_layers, cfg.algo.rnn_hidden_dim, is_sn=sn)
     critic = SharedCritic(enc_c, cfg.algo.embedding_dim, 1, cfg.algo.num_layers, cfg.algo.rnn_hidden_dim, is_sn=sn)
+    if layer_norm_options(cfg):   # after every other parameter, without a draw: the shared keys keep the off-model's bits
+        actor.add_feat_norm(), critic.add_feat_norm()
     if not bool(cfg.algo.get("use_rnn", True)):
         if cfg.algo.embedding_dim != cfg.algo.rnn_hidden_dim:
             raise ValueError("algo.use_rnn=false feeds the embedding to the heads: embedding_dim must equal rnn_hidden_dim")

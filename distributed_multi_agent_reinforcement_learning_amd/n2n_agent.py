@@ -16,7 +16,7 @@ import torch
 from . import guidance as gd
 from . import ops
 from . import value_norm as vnorm
-from .model import build_actor_critic, sequence_forward_pair
+from .model import build_actor_critic, check_layer_norm_keys, layer_norm_options, norm_rollout, sequence_forward_pair
 from .n2n_env import ParticleEnv
 from .particle_agent import ParticleMAPPO, ParticleTrainer, finish_env, train_particle
 
@@ -40,6 +40,8 @@ class _N2nRollout:
         self.hbuf_a, self.hbuf_c = z(2, L, N * P, H), z(2, L, N * P, H)
         self.a_n = torch.zeros((N, P), dtype=torch.int32, device=dev)
         self.logp, self.v = z(N, P), z(N, P)
+        if agent.use_layer_norm:   # the normalised GRU features of a tick (the GRU's own output is the recurrent state: never in place)
+            self.na, self.nc = z(N * P, H), z(N * P, H)
         self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.t = 0
@@ -81,6 +83,7 @@ class N2nMAPPO(ParticleMAPPO):
         if int(cfg.env.state_dim) != 4 or int(cfg.env.action_dim) != 9 or int(a.num_relation) != 3:
             raise ValueError("env_n2n runs the pursuit model: env.state_dim 4, env.action_dim 9, algo.num_relation 3")
         self.depth = int(a.depth)
+        self.use_layer_norm = layer_norm_options(cfg)   # LayerNorm between the GRUs and the heads
 
     def _build(self, cfg):
         if str(cfg.algo.get("encoder", "dhgn")).lower() != "dhgn":
@@ -92,6 +95,8 @@ class N2nMAPPO(ParticleMAPPO):
         # the parameter order of MAPPO.ac_parameters (the reference's, :631)
         self.ac_parameters = (list(enc.parameters()) + list(self.actor.GRU.parameters()) + list(self.critic.GRU.parameters())
                               + list(self.critic.Mean.parameters()) + list(self.actor.Mean.parameters()))
+        if self.use_layer_norm:   # last: the actor's, then the critic's
+            self.ac_parameters += list(self.actor.feat_norm.parameters()) + list(self.critic.feat_norm.parameters())
 
     # ---- rollout -------------------------------------------------------------------------------------------------------------
     def _rollout(self, env):
@@ -110,6 +115,8 @@ class N2nMAPPO(ParticleMAPPO):
         cur, nxt = st.t & 1, (st.t + 1) & 1
         fa, fc = ops.gru_step_multi([emb[0].reshape(-1, Em), emb[1].reshape(-1, Em)], [st.hbuf_a[cur], st.hbuf_c[cur]],
                                     [self.actor.GRU, self.critic.GRU], hiddens_out=[st.hbuf_a[nxt], st.hbuf_c[nxt]])
+        if self.use_layer_norm:
+            fa, fc = norm_rollout([self.actor, self.critic], [fa, fc], [st.na, st.nc])
         self.critic.head(fc.reshape(N, P, -1), out=st.v)
         w_a = self.actor.head_weight()
         ops.head_sample(fa.contiguous(), w_a, self.actor.Mean.bias, self.sample_seed, st.counter, st.ticket, (st.a_n, st.logp), greedy=greedy)
@@ -122,6 +129,8 @@ class N2nMAPPO(ParticleMAPPO):
         enc = self.critic.shared_net
         emb = enc(st.p4, st.e4, st.o, st.pp, st.pe, st.o_adj, hops_c, True, None, 1, None, e_ref=st.e_ref)
         (fc,) = ops.gru_step_multi([emb.reshape(N * P, -1)], [st.hbuf_c[st.t & 1]], [self.critic.GRU], hiddens_out=[st.hbuf_c[(st.t + 1) & 1]])
+        if self.use_layer_norm:
+            (fc,) = norm_rollout([self.critic], [fc], [st.nc])
         return self.critic.head(fc.reshape(N, P, -1)).reshape(N, P)
 
     def new_buffer(self, N, T, P, E):
@@ -239,13 +248,17 @@ class N2nMAPPO(ParticleMAPPO):
             os.remove(vn_path)
 
     def load_model(self, cwd, best=False):
-        """the weights save_model(cwd, best) wrote; ValueError when they belong to the other algo.use_value_norm"""
+        """the weights save_model(cwd, best) wrote; ValueError when they belong to the other algo.use_value_norm or algo.use_layer_norm
+        (the latter read off the files' keys)"""
         sfx = "_best" if best else ""
         vn_path = os.path.join(cwd, f"n2n_value_norm{sfx}.pth")
         entry = torch.load(vn_path, map_location="cpu") if os.path.exists(vn_path) else None
         vnorm.check_entry(self, entry, os.path.join(cwd, f"n2n_critic{sfx}.pth"), check_beta=False)
-        self.actor.load_state_dict(torch.load(os.path.join(cwd, f"n2n_actor{sfx}.pth"), map_location=self.device))
-        self.critic.load_state_dict(torch.load(os.path.join(cwd, f"n2n_critic{sfx}.pth"), map_location=self.device))
+        sds = [torch.load(os.path.join(cwd, f"n2n_{net}{sfx}.pth"), map_location=self.device) for net in ("actor", "critic")]
+        for sd, net in zip(sds, ("actor", "critic")):
+            check_layer_norm_keys(self, sd.keys(), os.path.join(cwd, f"n2n_{net}{sfx}.pth"))
+        self.actor.load_state_dict(sds[0])
+        self.critic.load_state_dict(sds[1])
         if self.value_norm is not None:
             self.value_norm.load_entry(entry)
 

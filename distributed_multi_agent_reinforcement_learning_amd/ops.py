@@ -26,7 +26,8 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "team_comm_mask_host", "team_attention_fwd_host", "team_attention_bwd_host", "gnn_pair_agg_fwd", "gnn_pair_agg_bwd",
            "gnn_pair_agg_bwd_workspace", "dhgn_att_agg3_fwd", "dhgn_att_agg_bwd", "dhgn_att_agg_bwd_workspace", "fcra_att_fwd_multi", "fcra_att_bwd",
            "fcra_att_bwd_workspace", "dhgn_pool_agg3_fwd", "dhgn_pool_agg_bwd", "dhgn_pool_agg_bwd_workspace", "fcra_pool_fwd_multi", "fcra_pool_bwd",
-           "fcra_pool_bwd_workspace", "fcra_team_fwd_multi", "fcra_team_bwd", "fcra_team_bwd_workspace", "mappo_ops_error_string")
+           "fcra_pool_bwd_workspace", "fcra_team_fwd_multi", "fcra_team_bwd", "fcra_team_bwd_workspace", "feat_norm_fwd_multi",
+           "feat_norm_bwd_multi", "feat_norm_bwd_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -186,6 +187,10 @@ def load_library():
         L.fcra_team_bwd_workspace.argtypes = [i32, i32]
         L.fcra_team_bwd_workspace.restype = i64
         L.fcra_team_bwd.argtypes = L.fcra_att_bwd.argtypes
+        L.feat_norm_fwd_multi.argtypes = [i32, vp, i64, i32, f32, i32, vp]
+        L.feat_norm_bwd_workspace.argtypes = [i32, i32, i32]
+        L.feat_norm_bwd_workspace.restype = i64
+        L.feat_norm_bwd_multi.argtypes = [i32, vp, i64, i32, f32, vp, i32, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
         _lib = L
@@ -3159,3 +3164,122 @@ def team_attention(qkv, words, heads):
     if G:
         _check(load_library().team_attention_fwd(G, P, H, _ptr(qkv), _ptr(words), _ptr(out), None, _stream()), "team_attention_fwd")
     return out
+
+
+# ---- LayerNorm on the GRU features (algo.use_layer_norm; csrc/layer_norm.hpp) ----------------------------------------------
+class FeatNormJob(C.Structure):   # include/mappo_ops.h mo_feat_norm_job
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("weight", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("ldy", C.c_int64),
+                ("g", C.c_void_p), ("ldg", C.c_int64), ("dx", C.c_void_p), ("lddx", C.c_int64), ("d_weight", C.c_void_p), ("d_bias", C.c_void_p)]
+
+
+FEAT_NORM_E = 128          # the kernels' only width
+FEAT_NORM_MAX_JOBS = 4     # include/mappo_ops.h MO_FEAT_NORM_MAX_JOBS
+FEAT_NORM_UNROLL = 4       # csrc/layer_norm.hpp FN_U: rows of a wave in flight in the forward
+feat_norm_calls = 0        # forward launches of the feature LayerNorm so far (tests)
+
+
+def _feat_rows(t, name, written=False):
+    """(.., 128) -> (the (R, 128) rows without a copy where the strides allow it, their stride in floats).  Rows that share storage (a
+    stride of 0 over a dimension of more than one entry) are refused, as the loss wrappers refuse them; written: `t` is an output, so
+    a layout that would need a copy is an error"""
+    assert all(s != 0 for n, s in zip(t.shape[:-1], t.stride()[:-1]) if n > 1), f"{name}: " + _SHARED_ROWS
+    if t.dim() == 2 and t.stride(1) == 1 and (t.shape[0] <= 1 or (t.stride(0) >= FEAT_NORM_E and t.stride(0) % 2 == 0)):
+        return t, (t.stride(0) if t.shape[0] > 1 else FEAT_NORM_E)
+    rows = t.reshape(-1, FEAT_NORM_E)
+    if not rows.is_contiguous():
+        rows = rows.contiguous()
+    assert not written or rows.data_ptr() == t.data_ptr(), f"{name}: the output's rows must be dense vectors one stride apart"
+    return rows, FEAT_NORM_E
+
+
+def _feat_norm_fused(xs):
+    return all(x.is_cuda and x.dtype == torch.float32 and x.shape[-1] == FEAT_NORM_E for x in xs)
+
+
+def _feat_norm_jobs(n):
+    if not 1 <= n <= FEAT_NORM_MAX_JOBS:
+        raise ValueError(f"feat_norm: 1 .. {FEAT_NORM_MAX_JOBS} networks a launch, got {n}")
+    return (FeatNormJob * n)()
+
+
+def _feat_norm_fwd(xs, weights, biases, eps, outs, max_blocks=0):
+    """one launch: xs / outs (R, 128) row views with their strides [(tensor, ld)], weights / biases dense (128,)"""
+    global feat_norm_calls
+    arr, R = _feat_norm_jobs(len(xs)), xs[0][0].shape[0]
+    for a, (x, ldx), w, b, (y, ldy) in zip(arr, xs, weights, biases, outs):
+        assert x.shape[0] == R and y.shape[0] == R and w.is_contiguous() and b.is_contiguous()
+        a.x, a.ldx, a.weight, a.bias, a.y, a.ldy = x.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), y.data_ptr(), ldy
+    if R:   # (an empty tensor has no address to pass)
+        _check(load_library().feat_norm_fwd_multi(len(xs), C.cast(arr, C.c_void_p), R, FEAT_NORM_E, eps, max_blocks, _stream()), "feat_norm_fwd_multi")
+        feat_norm_calls += 1
+
+
+def _feat_norm_bwd(xs, weights, gs, eps, max_blocks=0):
+    """one launch + the ordered reduce -> ([dx (R, 128)], [d_weight (128,)], [d_bias (128,)]); xs / gs as _feat_norm_fwd's views"""
+    L, n = load_library(), len(xs)
+    arr, R, dev = _feat_norm_jobs(n), xs[0][0].shape[0], xs[0][0].device
+    dxs = [torch.empty((R, FEAT_NORM_E), dtype=torch.float32, device=dev) for _ in range(n)]
+    dwb = torch.zeros((n, 2, FEAT_NORM_E), dtype=torch.float32, device=dev) if R == 0 else torch.empty((n, 2, FEAT_NORM_E), dtype=torch.float32, device=dev)
+    if R:
+        key = (dev, "feat_norm", n, max_blocks, torch.cuda.current_stream().cuda_stream)
+        ws = _workspaces.get(key)
+        if ws is None:
+            ws = _workspaces[key] = torch.empty(L.feat_norm_bwd_workspace(FEAT_NORM_E, n, max_blocks), dtype=torch.uint8, device=dev)
+        for k, (a, (x, ldx), w, (g, ldg)) in enumerate(zip(arr, xs, weights, gs)):
+            a.x, a.ldx, a.weight, a.g, a.ldg = x.data_ptr(), ldx, w.data_ptr(), g.data_ptr(), ldg
+            a.dx, a.lddx, a.d_weight, a.d_bias = dxs[k].data_ptr(), FEAT_NORM_E, dwb[k, 0].data_ptr(), dwb[k, 1].data_ptr()
+        _check(L.feat_norm_bwd_multi(n, C.cast(arr, C.c_void_p), R, FEAT_NORM_E, eps, _ptr(ws), max_blocks, _stream()), "feat_norm_bwd_multi")
+    return dxs, [dwb[k, 0] for k in range(n)], [dwb[k, 1] for k in range(n)]
+
+
+class _FeatNorm(torch.autograd.Function):
+    """feat_norm_train on the fused kernels: all networks in one launch forward, one launch + the ordered reduce backward; the forward
+    saves its inputs only (mean and rstd are recomputed)."""
+
+    @staticmethod
+    def forward(ctx, eps, n, *t):
+        xs, weights, biases = t[:n], [w.contiguous() for w in t[n:2 * n]], [b.contiguous() for b in t[2 * n:]]
+        rows = [_feat_rows(x, f"xs[{k}]") for k, x in enumerate(xs)]
+        ys = [torch.empty((r.shape[0], FEAT_NORM_E), dtype=torch.float32, device=r.device) for r, _ in rows]
+        _feat_norm_fwd(rows, weights, biases, eps, [(y, FEAT_NORM_E) for y in ys])
+        ctx.save_for_backward(*[r for r, _ in rows], *weights)
+        ctx.eps, ctx.lds = eps, [ld for _, ld in rows]
+        return tuple(y.reshape(x.shape) for y, x in zip(ys, xs))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        n = len(gs)
+        saved = ctx.saved_tensors
+        xs, weights = saved[:n], saved[n:]
+        gs = [torch.zeros_like(x) if g is None else g for g, x in zip(gs, xs)]
+        # (a gradient may arrive expand()ed -- rows sharing storage are fine to READ, but the row view below refuses them: copy those)
+        gs = [g.contiguous() if any(s == 0 for m, s in zip(g.shape[:-1], g.stride()[:-1]) if m > 1) else g for g in gs]
+        dxs, dws, dbs = _feat_norm_bwd(list(zip(xs, ctx.lds)), weights, [_feat_rows(g, "grad") for g in gs], ctx.eps)
+        return (None, None, *[dx.reshape(g.shape) for dx, g in zip(dxs, gs)], *dws, *dbs)
+
+
+def feat_norm_formula(x, weight, bias, eps):
+    """the specification: torch's layer_norm over the last dimension (CPU, float64 and widths other than 128)"""
+    return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
+
+
+def feat_norm(xs, weights, biases, eps, outs):
+    """LayerNorm over the last dimension of every xs[k] (.., 128) with its own weights[k], biases[k] (128,) into outs[k] (same rows; dense
+    vectors one stride apart, never xs[k] itself), all networks in ONE launch (csrc/layer_norm.hpp k_feat_norm_fwd).  The rollout's
+    form: no autograd, no allocation.  CPU, float64 or another width: feat_norm_formula.  -> outs"""
+    if _feat_norm_fused(xs):
+        _feat_norm_fwd([_feat_rows(x.detach(), f"xs[{k}]") for k, x in enumerate(xs)], [w.detach() for w in weights], [b.detach() for b in biases],
+                       float(eps), [_feat_rows(o, f"outs[{k}]", written=True) for k, o in enumerate(outs)])
+    else:
+        for x, w, b, o in zip(xs, weights, biases, outs):
+            o.copy_(feat_norm_formula(x.detach(), w.detach(), b.detach(), eps).reshape(o.shape))
+    return outs
+
+
+def feat_norm_train(xs, weights, biases, eps):
+    """-> [LayerNorm(xs[k]; weights[k], biases[k])], the update's form: ONE autograd node over the list of networks, one launch forward and
+    one launch + the ordered reduce backward (csrc/layer_norm.hpp; gradients to xs, weights, biases; the same bits from run to run).
+    CPU, float64 or another width: feat_norm_formula under torch's autograd."""
+    if _feat_norm_fused(xs):
+        return list(_FeatNorm.apply(float(eps), len(xs), *xs, *weights, *biases))
+    return [feat_norm_formula(x, w, b, eps) for x, w, b in zip(xs, weights, biases)]

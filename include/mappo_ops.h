@@ -791,6 +791,31 @@ int fcra_team_bwd(int64_t R, int32_t P, int32_t E, const float *y, const float *
                   int32_t max_blocks, void *stream);
 
 /*
+ * LayerNorm on the GRU features (`algo.use_layer_norm`; csrc/layer_norm.hpp): the numbers of torch's F.layer_norm over the
+ * `width` features of a row,  y = weight (x - mean) / sqrt(var + eps) + bias  (var biased), for up to MO_FEAT_NORM_MAX_JOBS jobs
+ * (networks) of R rows in ONE launch.  Rows are `width` dense floats, ldx / ldy / ldg / lddx (even, >= width) elements apart.
+ * feat_norm_fwd_multi reads x, weight, bias and writes y (never in place: y may not overlap x); the other fields are not read.
+ * feat_norm_bwd_multi reads x, weight, g (= d y) and OVERWRITES dx, d_weight [width], d_bias [width]: with gw = g weight and
+ * xh = (x - mean) rstd, dx = rstd (gw - mean(gw) - xh mean(gw xh)), d_weight = sum_r g xh, d_bias = sum_r g; mean and rstd are recomputed
+ * from x (nothing was saved); bias, y are not read; dx may not overlap x.  workspace: at least
+ * feat_norm_bwd_workspace(width, n_jobs, max_blocks) bytes, 16-byte aligned (per-workgroup partial blocks added in a fixed order: no
+ * atomics, the same bits from run to run; a row's dx depends on that row's inputs only).
+ * max_blocks: 0 = the default grid; > 0 caps the workgroups per job (four rows in flight each, the row loop unrolled).
+ * width == 128 only; 1 <= n_jobs <= MO_FEAT_NORM_MAX_JOBS; eps finite and > 0; every pointer read or written 8-byte aligned.  Anything
+ * else, R < 0, a NULL pointer, a stride below width or odd, y / dx overlapping x: MO_ERR_BAD_ARG before any launch or write.  R == 0
+ * succeeds and writes nothing.
+ */
+#define MO_FEAT_NORM_MAX_JOBS 4
+typedef struct mo_feat_norm_job {
+    const float *x; int64_t ldx; const float *weight, *bias; float *y; int64_t ldy;
+    const float *g; int64_t ldg; float *dx; int64_t lddx; float *d_weight, *d_bias;
+} mo_feat_norm_job;
+int feat_norm_fwd_multi(int32_t n_jobs, const mo_feat_norm_job *jobs, int64_t R, int32_t width, float eps, int32_t max_blocks, void *stream);
+int64_t feat_norm_bwd_workspace(int32_t width, int32_t n_jobs, int32_t max_blocks);
+int feat_norm_bwd_multi(int32_t n_jobs, const mo_feat_norm_job *jobs, int64_t R, int32_t width, float eps, void *workspace, int32_t max_blocks,
+                        void *stream);
+
+/*
  * ReLU backward and the bias gradient of the Linear in front of it in one pass (autograd: aten::threshold_backward, then
  * grad.sum(0) re-reading it; MAPPO.train's loss.backward(), DHGN/mappo_parallel.py:660-708):
  *   gin [R][F] = gout * [y > 0] (y = the saved ReLU output);  colsum [F] = sum_r gin[r][:].
