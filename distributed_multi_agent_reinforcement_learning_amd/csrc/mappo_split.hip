@@ -18,6 +18,7 @@
 #include "layer_norm.hpp"
 #include "pool_agg.hpp"
 #include "sem_att.hpp"
+#include "team_pool.hpp"
 
 extern "C" {
 
@@ -491,6 +492,40 @@ int feat_norm_bwd_multi(int32_t n_jobs, const mo_feat_norm_job *jobs, int64_t R,
     }
     if (R == 0) return 0;
     return launch_feat_norm_bwd(a, n_jobs, R, eps, (float *)workspace, max_blocks, (hipStream_t)stream);
+}
+
+// the arguments team_pool_fwd and team_pool_bwd share
+static bool tp_common_ok(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                         const float *score, const float *gate, int32_t max_blocks) {
+    return G >= 0 && P >= 1 && P <= TP_MAX_P && E == TP_E && fa_ok8(feat) && fn_ld_ok(feat_ld) && live && (live_u8 == 1 || (live_u8 == 0 && !((uintptr_t)live & 3))) &&
+           live_stride >= P && fa_ok8(score) && fa_ok8(gate) && max_blocks >= 0;
+}
+
+int team_pool_fwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                  const float *score, const float *gate, float *out, int64_t out_ld, int32_t max_blocks, void *stream) {
+    if (!tp_common_ok(G, P, E, feat, feat_ld, live, live_u8, live_stride, score, gate, max_blocks) || !fa_ok8(out) || !fn_ld_ok(out_ld) ||
+        fn_overlap(feat, feat_ld, out, out_ld, G * P))
+        return MO_ERR_BAD_ARG;
+    if (G == 0) return 0;
+    const TpArgs a = {feat, feat_ld, live, live_u8, live_stride, score, gate};
+    return launch_team_pool_fwd(a, out, out_ld, G, P, max_blocks, (hipStream_t)stream);
+}
+
+int64_t team_pool_bwd_workspace(int32_t E, int32_t max_blocks) {
+    if (E != TP_E || max_blocks < 0) return 0;
+    return (int64_t)(max_blocks > 0 && max_blocks < TP_MAX_GRID ? max_blocks : TP_MAX_GRID) * 2 * TP_E * 4;
+}
+
+int team_pool_bwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                  const float *score, const float *gate, const float *g, int64_t g_ld, float *d_feat, int64_t d_feat_ld, float *d_score, float *d_gate,
+                  void *workspace, int32_t max_blocks, void *stream) {
+    if (!tp_common_ok(G, P, E, feat, feat_ld, live, live_u8, live_stride, score, gate, max_blocks) || !fa_ok8(g) || !fn_ld_ok(g_ld) || !fa_ok8(d_feat) ||
+        !fn_ld_ok(d_feat_ld) || !fa_ok8(d_score) || !fa_ok8(d_gate) || !workspace || ((uintptr_t)workspace & 15) ||
+        fn_overlap(feat, feat_ld, d_feat, d_feat_ld, G * P) || fn_overlap(g, g_ld, d_feat, d_feat_ld, G * P))
+        return MO_ERR_BAD_ARG;
+    if (G == 0) return 0;
+    const TpArgs a = {feat, feat_ld, live, live_u8, live_stride, score, gate};
+    return launch_team_pool_bwd(a, g, g_ld, d_feat, d_feat_ld, d_score, d_gate, G, P, (float *)workspace, max_blocks, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -42,7 +42,8 @@ from . import obs_norm as onorm
 from . import ops
 from . import value_norm as vnorm
 from .e3d_env import CENTRAL_MAX_P, EVADER_OBS, PURSUIT_FEAT, ParticleEnv, central_feat
-from .model import FEAT_NORM_KEY, HeadLinear, _make_linear, _ortho_linear, _Trunk, layer_norm_options, norm_pair, norm_rollout
+from .model import (FEAT_NORM_KEY, TEAM_POOL_KEY, TEAM_POOL_MODES, HeadLinear, _make_linear, _ortho_linear, _Trunk, layer_norm_options, norm_pair,
+                    norm_rollout, pool_features, pool_rollout, team_pool_options)
 from .particle_agent import ParticleMAPPO, ParticleTrainer, finish_env, train_particle
 
 FEAT = 16   # e3d_policy_features columns (include/e3d_env.h); algo.e3d_features: pursuit has PURSUIT_FEAT
@@ -129,6 +130,8 @@ class _E3dRollout:
         self.action, self.env_action, self.logp, self.v = z(N, P, U), z(N, P, A, dt=torch.float64), z(N, P), z(N, P)
         if agent.use_layer_norm:   # the normalised GRU features of a tick (the GRU's own output is the recurrent state: never in place)
             self.na, self.nc = z(N * P, H), z(N * P, H)
+        if agent.critic_team_pool:   # the critic's pooled features of a tick
+            self.pc = z(N * P, H)
         self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.live = z(N, P)   # this step's live mask (e3d_policy_record keeps it current)
@@ -230,6 +233,7 @@ class E3dMAPPO(ParticleMAPPO):
         self.critic_feat_dim = central_feat(int(cfg.env.num_defender)) if self.e3d_critic == "central" else self.feat_dim
         self.e3d_comm, self.e3d_comm_heads = e3d_comm_options(cfg)   # team attention in the actor
         self.use_layer_norm = layer_norm_options(cfg)   # LayerNorm between the GRUs and the heads
+        self.critic_team_pool = team_pool_options(cfg)   # the critic's attention pool over the live team
         self.use_obs_norm, self.obs_norm_clip = onorm.obs_norm_options(cfg)   # running mean / std on the policy features
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
@@ -258,6 +262,8 @@ class E3dMAPPO(ParticleMAPPO):
             self.ac_parameters += list(self.actor.comm.parameters())
         if self.use_layer_norm:   # after every other parameter and without a draw; last in ac_parameters: the actor's, then the critic's
             self.ac_parameters += self.actor.add_feat_norm() + self.critic.add_feat_norm()
+        if self.critic_team_pool:   # behind feat_norm, likewise without a draw: the critic's last keys
+            self.ac_parameters += self.critic.add_team_pool()
         self.obs_norm = onorm.ObsNorm(self.obs_norm_clip, self.device) if self.use_obs_norm else None
 
     # ---- rollout -------------------------------------------------------------------------------------------------------------
@@ -280,6 +286,8 @@ class E3dMAPPO(ParticleMAPPO):
                                     hiddens_out=[st.hbuf_a[nxt], st.hbuf_c[nxt]])
         if self.use_layer_norm:
             fa, fc = norm_rollout([self.actor, self.critic], [fa, fc], [st.na, st.nc])
+        if self.critic_team_pool:
+            fc = pool_rollout(self.critic, fc, st.live, st.pc)
         self.critic.head(fc.contiguous(), out=st.v)
         m = self.actor.Mean
         if self.policy_ex:
@@ -315,6 +323,8 @@ class E3dMAPPO(ParticleMAPPO):
         (fc,) = ops.gru_step_multi([emb_c.reshape(N * P, -1)], [st.hbuf_c[st.t & 1]], [self.critic.GRU], hiddens_out=[st.hbuf_c[(st.t + 1) & 1]])
         if self.use_layer_norm:
             (fc,) = norm_rollout([self.critic], [fc], [st.nc])
+        if self.critic_team_pool:
+            fc = pool_rollout(self.critic, fc, st.live, st.pc)
         return self.critic.head(fc.contiguous()).reshape(N, P)
 
     def new_buffer(self, N, T, P):
@@ -382,10 +392,11 @@ class E3dMAPPO(ParticleMAPPO):
         return acc["ret"], acc["captured"] != 0, acc["length"]
 
     # ---- update ------------------------------------------------------------------------------------------------------------------
-    def sequence_forward(self, feat_a, feat_c, batch, steps, return_ls_raw=False, words=None):
+    def sequence_forward(self, feat_a, feat_c, batch, steps, return_ls_raw=False, words=None, live=None):
         """(batch, T, P, feat_dim / critic_feat_dim) features of whole episodes -> mu (batch, T, P, A) and values (batch, T, P), time-major views; with
         return_ls_raw also ls_raw (state mode: the LogStd head on the same GRU features, (batch, T, P, A); param mode: log_std);
-        words (algo.e3d_comm: attention): the (batch, T, P) hearing sets of the rows, whose groups are P consecutive rows"""
+        words (algo.e3d_comm: attention): the (batch, T, P) hearing sets of the rows, whose groups are P consecutive rows;
+        live (algo.critic_team_pool: attention): the rows' (batch, T, P) live mask, the buffer's `active`"""
         P = feat_a.shape[2]
         R = batch * steps * P
         emb_a, emb_c = self.actor.shared_net(feat_a.reshape(R, self.feat_dim)), self.critic.shared_net(feat_c.reshape(R, self.critic_feat_dim))
@@ -394,6 +405,7 @@ class E3dMAPPO(ParticleMAPPO):
         h0 = [torch.zeros(m.num_layers, batch * P, m.rnn_hidden_dim, dtype=emb_a.dtype, device=emb_a.device) for m in (self.actor, self.critic)]
         fa, fc = ops.gru_multi([emb_a, emb_c], h0, [self.actor.GRU, self.critic.GRU], agents=P, steps=steps, zero_state=True)
         fa, fc = norm_pair(self.actor, self.critic, fa.reshape(steps, batch, P, -1), fc.reshape(steps, batch, P, -1))
+        fc = pool_features(self.critic, fc, live)
         mu = self.actor.Mean(fa).permute(1, 0, 2, 3)
         values = self.critic.Mean(fc).permute(1, 0, 2, 3)[..., 0]
         if not return_ls_raw:
@@ -405,9 +417,13 @@ class E3dMAPPO(ParticleMAPPO):
         """the hearing sets of episodes [n0, n1) (algo.e3d_comm: attention; None without it: the buffer has no such field)"""
         return buf["comm"][n0:n1] if self.e3d_comm == "attention" else None
 
+    def _live(self, buf, n0, n1):
+        """the live mask of episodes [n0, n1) for the critic's pool (algo.critic_team_pool: attention; None without it)"""
+        return buf["active"][n0:n1] if self.critic_team_pool else None
+
     def _minibatch_loss(self, buf, n0, n1, adv, v_target, dk):
         mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True,
-                                                     words=self._words(buf, n0, n1))
+                                                     words=self._words(buf, n0, n1), live=self._live(buf, n0, n1))
         tail = self._loss_tail(buf, n0, n1, values, adv, v_target)
         if self.policy_ex:
             return ops.ppo_loss_gauss_ex(mu, ls_raw, *tail, log_std_min=self.log_std_min, log_std_max=self.log_std_max,
@@ -428,7 +444,7 @@ class E3dMAPPO(ParticleMAPPO):
 
     def _imitation_loss(self, buf, n0, n1, v_target, sums):
         mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True,
-                                                     words=self._words(buf, n0, n1))
+                                                     words=self._words(buf, n0, n1), live=self._live(buf, n0, n1))
         lo, hi = (self.log_std_min, self.log_std_max) if self.policy_ex else (-float("inf"), float("inf"))
         return ops.bc_loss_gauss(mu, ls_raw, buf["a_star"][n0:n1], *self._imitation_tail(buf, n0, n1, values, v_target), log_std_min=lo,
                                  log_std_max=hi, fit_std=self.imitation.fit_std, wrap0=self.bc_wrap0, sums=sums,
@@ -436,7 +452,7 @@ class E3dMAPPO(ParticleMAPPO):
 
     def _kick_loss(self, buf, n0, n1, adv, v_target, coef, sums, dk):
         mu, values, ls_raw = self.sequence_forward(buf["feat_a"][n0:n1], buf["feat_c"][n0:n1], n1 - n0, buf["r"].shape[1], return_ls_raw=True,
-                                                     words=self._words(buf, n0, n1))
+                                                     words=self._words(buf, n0, n1), live=self._live(buf, n0, n1))
         lo, hi = (self.log_std_min, self.log_std_max) if self.policy_ex else (-float("inf"), float("inf"))
         a_n, *tail = self._loss_tail(buf, n0, n1, values, adv, v_target)
         return ops.ppo_bc_loss_gauss(mu, ls_raw, a_n, buf["a_star"][n0:n1], *tail[:-1], coef, tail[-1], log_std_min=lo, log_std_max=hi,
@@ -458,6 +474,8 @@ class E3dMAPPO(ParticleMAPPO):
             meta.update(e3d_comm=self.e3d_comm, e3d_comm_heads=self.e3d_comm_heads)
         if getattr(self, "use_layer_norm", False):
             meta.update(use_layer_norm=True)
+        if getattr(self, "critic_team_pool", False):
+            meta.update(critic_team_pool=TEAM_POOL_MODES[1])
         return meta or None
 
     def check_policy_meta(self, meta, what):
@@ -470,6 +488,9 @@ class E3dMAPPO(ParticleMAPPO):
         theirs, mine = bool(meta.get("use_layer_norm", False)), bool(getattr(self, "use_layer_norm", False))
         if theirs != mine:   # (a file without the entry was written with false: the networks have feat_norm or not)
             raise ValueError(f"{what} was written with {FEAT_NORM_KEY}: {str(theirs).lower()}, this agent has {FEAT_NORM_KEY}: {str(mine).lower()}")
+        theirs, mine = meta.get("critic_team_pool", TEAM_POOL_MODES[0]), TEAM_POOL_MODES[int(bool(getattr(self, "critic_team_pool", False)))]
+        if theirs != mine:   # (a file without the entry was written with none: the critic has team_pool or not)
+            raise ValueError(f"{what} was written with {TEAM_POOL_KEY}: {theirs}, this agent has {TEAM_POOL_KEY}: {mine}")
         for key, default in (("e3d_features", "basic"), ("e3d_evader_obs", "sensed"), ("e3d_critic", "local"), ("e3d_comm", "none"),
                              ("gauss_std", "param"), ("gauss_squash", "clip")):
             theirs, mine = meta.get(key, default), getattr(self, key, default)

@@ -20,7 +20,7 @@ import torch
 from . import ops
 from .imitation import OptimizerSchedule, follow_mask, refuse_pursuit
 from .kickstart import refuse_pursuit as refuse_pursuit_kickstart
-from .model import build_actor_critic, layer_norm_key, pair_embeddings, pair_heads, sequence_forward_pair
+from .model import build_actor_critic, layer_norm_key, team_pool_key, pair_embeddings, pair_heads, sequence_forward_pair
 from .pe_env import status_or, status_text
 from .pursuit_baseline import pathfinder_options
 from .pursuit_imitation import pursuit_imitation_options, pursuit_kickstart_options
@@ -237,6 +237,9 @@ class MAPPO(OptimizerSchedule):
         if layer_norm_key(cfg):
             raise ValueError("algo.use_layer_norm: true is built for runtime.env n2n and e3d only; the pursuit networks are pinned to the "
                              "reference's (set use_layer_norm to false)")
+        if team_pool_key(cfg):
+            raise ValueError("algo.critic_team_pool: attention is built for runtime.env n2n and e3d only; the pursuit networks are pinned to "
+                             "the reference's (set critic_team_pool to none)")
         refuse_pursuit(cfg)   # algo.bc_iterations: env_3d / env_n2n only
         refuse_pursuit_kickstart(cfg)   # algo.bc_coef: likewise
         # algo.pathfinder_bc_iterations: the flagship's own warm start, from the path-finding pursuers

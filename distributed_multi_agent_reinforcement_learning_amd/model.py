@@ -380,6 +380,47 @@ class FeatNorm(nn.Module):
         self.weight, self.bias = nn.Parameter(torch.ones(width)), nn.Parameter(torch.zeros(width))
 
 
+TEAM_POOL_KEY = "algo.critic_team_pool"
+TEAM_POOL_MODES = ("none", "attention")
+
+
+def team_pool_key(cfg):
+    """-> algo.critic_team_pool == "attention" (default none); ValueError naming the key at any other value"""
+    v = str(cfg.algo.get("critic_team_pool", "none")).lower()
+    if v not in TEAM_POOL_MODES:
+        raise ValueError(f"{TEAM_POOL_KEY}: {v!r} is not one of {TEAM_POOL_MODES}")
+    return v == "attention"
+
+
+def team_pool_options(cfg):
+    """-> algo.critic_team_pool as a bool, validated: the kernels' only width is 128 and a group's live flags are
+    one 64-bit word"""
+    on = team_pool_key(cfg)
+    if on and int(cfg.algo.rnn_hidden_dim) != ops.TEAM_POOL_E:
+        raise ValueError(f"{TEAM_POOL_KEY}: attention needs algo.rnn_hidden_dim {ops.TEAM_POOL_E} (the pool kernels' only width), "
+                         f"got algo.rnn_hidden_dim={cfg.algo.rnn_hidden_dim}")
+    if on and int(cfg.env.num_defender) > ops.TEAM_POOL_MAX_P:
+        raise ValueError(f"{TEAM_POOL_KEY}: attention supports env.num_defender <= {ops.TEAM_POOL_MAX_P}, got {int(cfg.env.num_defender)}")
+    return on
+
+
+def check_team_pool_keys(agent, keys, what):
+    """ValueError naming the key when a critic file's state_dict keys belong to the other algo.critic_team_pool (before any tensor is loaded)"""
+    theirs, mine = any(k.startswith("team_pool.") for k in keys), bool(getattr(agent, "critic_team_pool", False))
+    if theirs != mine:
+        name = lambda on: TEAM_POOL_MODES[int(on)]
+        raise ValueError(f"{what} was written with {TEAM_POOL_KEY}: {name(theirs)}, this agent has {TEAM_POOL_KEY}: {name(mine)}")
+
+
+class TeamPool(nn.Module):
+    """the critic's attention pool over the live team-mates' GRU features (algo.critic_team_pool): score and gate are zeros -- no draw
+    from the generator, and with gate = 0 the critic is the off-critic to the bit"""
+
+    def __init__(self, width):
+        super().__init__()
+        self.score, self.gate = nn.Parameter(torch.zeros(width)), nn.Parameter(torch.zeros(width))
+
+
 class _Trunk(nn.Module):
     """shared_net -> GRU -> Mean, common to actor and critic.  use_rnn = False is the "MLP" ablation BASELINE config 1 names
     (the reference parses --use_rnn, MAPPO_parallel_main.py:261, and never reads it): encoder -> head, the GRU (whose
@@ -393,6 +434,14 @@ class _Trunk(nn.Module):
         self.feat_norm = FeatNorm(self.rnn_hidden_dim).to(self.GRU.weight_hh_l0.device)
         self.use_layer_norm = True
         return list(self.feat_norm.parameters())
+
+    use_team_pool = False
+
+    def add_team_pool(self):
+        """the critic's (algo.critic_team_pool), called once every other parameter exists, feat_norm included: the state_dict's last keys"""
+        self.team_pool = TeamPool(self.rnn_hidden_dim).to(self.GRU.weight_hh_l0.device)
+        self.use_team_pool = True
+        return list(self.team_pool.parameters())
 
     def norm_features(self, feat):
         """GRU features -> what the heads read, for the module's own forward paths (the agents normalise actor and critic together:
@@ -506,8 +555,10 @@ class SharedCritic(_Trunk):
         emb = self.shared_net(obs["p_state"], obs["e_state"], obs["o_state"], obs["p_adj"], obs["e_adj"], _o_adj(obs), hist,
                               True, kvalid, obs.get("q_div", 1), emb_out)
         if mode == 0:
+            assert not self.use_team_pool, "algo.critic_team_pool: the pool needs the live mask (pair_heads / pool_rollout apply it)"
             feat, hidden_state = self._rollout_features(emb, hidden_state, inplace_hidden)
             return self.head(self.norm_features(feat)), hidden_state, emb
+        assert not self.use_team_pool, "algo.critic_team_pool: the pool needs the live mask (pair_heads / pool_rollout apply it)"
         feat = self.norm_features(self._sequence_features(emb, batch, steps))  # (steps, batch, P, H)
         return self.Mean(feat).permute(1, 0, 2, 3)
 
@@ -542,13 +593,31 @@ def norm_rollout(nets, feats, outs):
     return ops.feat_norm(feats, [m.feat_norm.weight for m in nets], [m.feat_norm.bias for m in nets], FeatNorm.eps, outs)
 
 
-def pair_heads(actor, critic, feat_a, feat_c):
-    """the output layers on time-major GRU features (steps, batch, P, H) -> prob (batch, steps, P, A), values (batch, steps, P, 1)"""
+def pool_features(critic, feat_c, live):
+    """algo.critic_team_pool: the critic's time-major features (steps, batch, P, H) plus the gated attention pool of their live
+    team-mates, ONE launch each way (ops.team_pool_train); live: the rows' (batch, steps, P) mask, the buffer's `active`; off: as they are"""
+    if not critic.use_team_pool:
+        return feat_c
+    if live is None:
+        raise ValueError(f"{TEAM_POOL_KEY}: attention needs the rows' live mask")
+    return ops.team_pool_train(feat_c, live.permute(1, 0, 2), critic.team_pool.score, critic.team_pool.gate)
+
+
+def pool_rollout(critic, feat_c, live, out):
+    """the rollout's form of pool_features (no autograd): a tick's (N P, H) features under its (N, P) live mask into the static `out`"""
+    P = live.shape[-1]
+    return ops.team_pool(feat_c.reshape(-1, P, feat_c.shape[-1]), live, critic.team_pool.score, critic.team_pool.gate, out)
+
+
+def pair_heads(actor, critic, feat_a, feat_c, live=None):
+    """the output layers on time-major GRU features (steps, batch, P, H) -> prob (batch, steps, P, A), values (batch, steps, P, 1);
+    live: pool_features' mask (algo.critic_team_pool only)"""
     feat_a, feat_c = norm_pair(actor, critic, feat_a, feat_c)
+    feat_c = pool_features(critic, feat_c, live)
     return torch.softmax(actor.Mean(feat_a), dim=-1).permute(1, 0, 2, 3), critic.Mean(feat_c).permute(1, 0, 2, 3)
 
 
-def sequence_forward_pair(actor, critic, obs, hist_a, hist_c, batch, steps):
+def sequence_forward_pair(actor, critic, obs, hist_a, hist_c, batch, steps, live=None):
     """SharedActor.forward(mode 1) and SharedCritic.forward(mode 1) of one mini-batch together (DHGN/mappo_parallel.py:426-437,
     :503-520): the two encoders as before, then the two GRUs layer by layer with actor and critic in ONE persistent launch each way
     (ops.gru_multi) -- same numbers as the two module calls.  -> (prob (batch, steps, P, A), values (batch, steps, P, 1))."""
@@ -562,7 +631,7 @@ def sequence_forward_pair(actor, critic, obs, hist_a, hist_c, batch, steps):
                                h0, [actor.GRU, critic.GRU], agents=P, steps=steps,
                                x_links=[getattr(emb_a, "relu_link", None), getattr(emb_c, "relu_link", None)], zero_state=True)
         feat_a, feat_c = fa.reshape(steps, batch, P, actor.rnn_hidden_dim), fc.reshape(steps, batch, P, critic.rnn_hidden_dim)
-    return pair_heads(actor, critic, feat_a, feat_c)
+    return pair_heads(actor, critic, feat_a, feat_c, live)
 
 
 def build_actor_critic(cfg, device):
@@ -584,6 +653,8 @@ def build_actor_critic(cfg, device):
     critic = SharedCritic(enc_c, cfg.algo.embedding_dim, 1, cfg.algo.num_layers, cfg.algo.rnn_hidden_dim, is_sn=sn)
     if layer_norm_options(cfg):   # after every other parameter, without a draw: the shared keys keep the off-model's bits
         actor.add_feat_norm(), critic.add_feat_norm()
+    if team_pool_options(cfg):    # the critic's alone, behind feat_norm, likewise without a draw
+        critic.add_team_pool()
     if not bool(cfg.algo.get("use_rnn", True)):
         if cfg.algo.embedding_dim != cfg.algo.rnn_hidden_dim:
             raise ValueError("algo.use_rnn=false feeds the embedding to the heads: embedding_dim must equal rnn_hidden_dim")

@@ -16,7 +16,8 @@ import torch
 from . import guidance as gd
 from . import ops
 from . import value_norm as vnorm
-from .model import build_actor_critic, check_layer_norm_keys, layer_norm_options, norm_rollout, sequence_forward_pair
+from .model import (build_actor_critic, check_layer_norm_keys, check_team_pool_keys, layer_norm_options, norm_rollout, pool_rollout,
+                    sequence_forward_pair, team_pool_options)
 from .n2n_env import ParticleEnv
 from .particle_agent import ParticleMAPPO, ParticleTrainer, finish_env, train_particle
 
@@ -42,6 +43,8 @@ class _N2nRollout:
         self.logp, self.v = z(N, P), z(N, P)
         if agent.use_layer_norm:   # the normalised GRU features of a tick (the GRU's own output is the recurrent state: never in place)
             self.na, self.nc = z(N * P, H), z(N * P, H)
+        if agent.critic_team_pool:   # the critic's pooled features of a tick
+            self.pc = z(N * P, H)
         self.counter = torch.full((1,), int(agent.sample_rank) << 40, dtype=torch.int64, device=dev)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.t = 0
@@ -63,6 +66,7 @@ class N2nMAPPO(ParticleMAPPO):
 
     def _options(self, cfg):
         a = cfg.algo
+        self.critic_team_pool = team_pool_options(cfg)   # the critic's attention pool over the live team (first: its refusals name its key)
         if bool(a.get("use_obs_norm", False)):
             raise ValueError("algo.use_obs_norm: true is built for runtime.env e3d only; the env_n2n inputs are node states whose "
                              "differences the message kernels form and whose zero rows stand for absent nodes (set use_obs_norm to false)")
@@ -97,6 +101,8 @@ class N2nMAPPO(ParticleMAPPO):
                               + list(self.critic.Mean.parameters()) + list(self.actor.Mean.parameters()))
         if self.use_layer_norm:   # last: the actor's, then the critic's
             self.ac_parameters += list(self.actor.feat_norm.parameters()) + list(self.critic.feat_norm.parameters())
+        if self.critic_team_pool:
+            self.ac_parameters += list(self.critic.team_pool.parameters())
 
     # ---- rollout -------------------------------------------------------------------------------------------------------------
     def _rollout(self, env):
@@ -117,6 +123,8 @@ class N2nMAPPO(ParticleMAPPO):
                                     [self.actor.GRU, self.critic.GRU], hiddens_out=[st.hbuf_a[nxt], st.hbuf_c[nxt]])
         if self.use_layer_norm:
             fa, fc = norm_rollout([self.actor, self.critic], [fa, fc], [st.na, st.nc])
+        if self.critic_team_pool:
+            fc = pool_rollout(self.critic, fc, st.live, st.pc)
         self.critic.head(fc.reshape(N, P, -1), out=st.v)
         w_a = self.actor.head_weight()
         ops.head_sample(fa.contiguous(), w_a, self.actor.Mean.bias, self.sample_seed, st.counter, st.ticket, (st.a_n, st.logp), greedy=greedy)
@@ -131,6 +139,8 @@ class N2nMAPPO(ParticleMAPPO):
         (fc,) = ops.gru_step_multi([emb.reshape(N * P, -1)], [st.hbuf_c[st.t & 1]], [self.critic.GRU], hiddens_out=[st.hbuf_c[(st.t + 1) & 1]])
         if self.use_layer_norm:
             (fc,) = norm_rollout([self.critic], [fc], [st.nc])
+        if self.critic_team_pool:
+            fc = pool_rollout(self.critic, fc, st.live, st.pc)
         return self.critic.head(fc.reshape(N, P, -1)).reshape(N, P)
 
     def new_buffer(self, N, T, P, E):
@@ -212,7 +222,8 @@ class N2nMAPPO(ParticleMAPPO):
     def sequence_forward(self, buf, n0, n1):
         """-> prob (B, T, P, 9), values (B, T, P) of episodes [n0, n1) (model.sequence_forward_pair)"""
         obs, hist_a, hist_c = self.minibatch_inputs(buf, n0, n1)
-        prob, values = sequence_forward_pair(self.actor, self.critic, obs, hist_a, hist_c, n1 - n0, buf["r"].shape[1])
+        prob, values = sequence_forward_pair(self.actor, self.critic, obs, hist_a, hist_c, n1 - n0, buf["r"].shape[1],
+                                             live=buf["active"][n0:n1] if self.critic_team_pool else None)
         return prob, values[..., 0]
 
     def _minibatch_loss(self, buf, n0, n1, adv, v_target, dk):
@@ -257,6 +268,7 @@ class N2nMAPPO(ParticleMAPPO):
         sds = [torch.load(os.path.join(cwd, f"n2n_{net}{sfx}.pth"), map_location=self.device) for net in ("actor", "critic")]
         for sd, net in zip(sds, ("actor", "critic")):
             check_layer_norm_keys(self, sd.keys(), os.path.join(cwd, f"n2n_{net}{sfx}.pth"))
+        check_team_pool_keys(self, sds[1].keys(), os.path.join(cwd, f"n2n_critic{sfx}.pth"))
         self.actor.load_state_dict(sds[0])
         self.critic.load_state_dict(sds[1])
         if self.value_norm is not None:

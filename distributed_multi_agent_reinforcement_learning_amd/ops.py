@@ -27,7 +27,7 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "gnn_pair_agg_bwd_workspace", "dhgn_att_agg3_fwd", "dhgn_att_agg_bwd", "dhgn_att_agg_bwd_workspace", "fcra_att_fwd_multi", "fcra_att_bwd",
            "fcra_att_bwd_workspace", "dhgn_pool_agg3_fwd", "dhgn_pool_agg_bwd", "dhgn_pool_agg_bwd_workspace", "fcra_pool_fwd_multi", "fcra_pool_bwd",
            "fcra_pool_bwd_workspace", "fcra_team_fwd_multi", "fcra_team_bwd", "fcra_team_bwd_workspace", "feat_norm_fwd_multi",
-           "feat_norm_bwd_multi", "feat_norm_bwd_workspace", "mappo_ops_error_string")
+           "feat_norm_bwd_multi", "feat_norm_bwd_workspace", "team_pool_fwd", "team_pool_bwd", "team_pool_bwd_workspace", "mappo_ops_error_string")
 
 _lib = None
 
@@ -191,6 +191,10 @@ def load_library():
         L.feat_norm_bwd_workspace.argtypes = [i32, i32, i32]
         L.feat_norm_bwd_workspace.restype = i64
         L.feat_norm_bwd_multi.argtypes = [i32, vp, i64, i32, f32, vp, i32, vp]
+        L.team_pool_fwd.argtypes = [i64, i32, i32, vp, i64, vp, i32, i64, vp, vp, vp, i64, i32, vp]
+        L.team_pool_bwd_workspace.argtypes = [i32, i32]
+        L.team_pool_bwd_workspace.restype = i64
+        L.team_pool_bwd.argtypes = [i64, i32, i32, vp, i64, vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i32, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
         _lib = L
@@ -3283,3 +3287,109 @@ def feat_norm_train(xs, weights, biases, eps):
     if _feat_norm_fused(xs):
         return list(_FeatNorm.apply(float(eps), len(xs), *xs, *weights, *biases))
     return [feat_norm_formula(x, w, b, eps) for x, w, b in zip(xs, weights, biases)]
+
+
+# ---- attention-pooled team context for the critic (algo.critic_team_pool; csrc/team_pool.hpp) -------------------------------
+TEAM_POOL_E = 128          # the kernels' only width
+TEAM_POOL_MAX_P = 64       # one ballot word of live flags per group
+team_pool_calls = 0        # forward launches of the team pool so far (tests)
+
+
+def team_pool_formula(feat, live, score, gate):
+    """the specification (CPU, float64): feat (G, P, E), live (G, P) non-zero = live, score / gate (E,) ->
+    feat + gate * c, c = the softmax(score . f_j over the live j)-weighted sum of the live rows (nobody live: c = 0)"""
+    on = live != 0
+    s = (feat * score).sum(-1).masked_fill(~on, -torch.inf)
+    e = torch.where(on, torch.exp(s - s.max(-1, keepdim=True).values.clamp_min(torch.finfo(feat.dtype).min)), torch.zeros_like(s))
+    w = e / e.sum(-1, keepdim=True).clamp_min(torch.finfo(feat.dtype).tiny)
+    c = (w.unsqueeze(-1) * torch.where(on.unsqueeze(-1), feat, torch.zeros_like(feat))).sum(-2, keepdim=True)
+    return feat + gate * c
+
+
+def _team_pool_fused(feat):
+    return feat.is_cuda and feat.dtype == torch.float32 and feat.shape[-1] == TEAM_POOL_E
+
+
+def _team_pool_live(live, G, P):
+    """the (G, P) flags as the kernels read them: dense rows of fp32 or uint8 -> (tensor, is uint8)"""
+    if live.dtype == torch.bool:
+        live = live.view(torch.uint8)
+    assert live.dtype in (torch.float32, torch.uint8), f"live: fp32 or uint8 flags, got {live.dtype}"
+    live = live.reshape(G, P)
+    return (live if live.is_contiguous() else live.contiguous()), int(live.dtype == torch.uint8)
+
+
+def _team_pool_args(feat, live, score, gate):
+    """(.., P, 128) features, (.., P) flags -> the leading arguments of both entry points and what keeps their storage alive"""
+    P = feat.shape[-2]
+    if not 1 <= P <= TEAM_POOL_MAX_P:
+        raise ValueError(f"team_pool: teams of 1 .. {TEAM_POOL_MAX_P} pursuers, got {P}")
+    rows, ld = _feat_rows(feat.reshape(-1, TEAM_POOL_E) if feat.is_contiguous() else feat.contiguous().view(-1, TEAM_POOL_E), "feat")
+    G = rows.shape[0] // P
+    flags, u8 = _team_pool_live(live, G, P)
+    score, gate = score.contiguous(), gate.contiguous()
+    return (G, P, TEAM_POOL_E, _ptr(rows), ld, _ptr(flags), u8, P, _ptr(score), _ptr(gate)), (rows, flags, score, gate)
+
+
+def _team_pool_fwd(feat, live, score, gate, out, max_blocks=0):
+    global team_pool_calls
+    head, keep = _team_pool_args(feat, live, score, gate)
+    rows, ld = _feat_rows(out.view(-1, TEAM_POOL_E) if out.dim() != 2 else out, "out", written=True)
+    assert rows.shape[0] == keep[0].shape[0], "team_pool: out has other rows than feat"
+    if head[0]:   # (an empty tensor has no address to pass)
+        _check(load_library().team_pool_fwd(*head, _ptr(rows), ld, max_blocks, _stream()), "team_pool_fwd")
+        team_pool_calls += 1
+    return keep
+
+
+class _TeamPool(torch.autograd.Function):
+    """team_pool_train on the fused kernels: one launch forward, one launch + the ordered reduce backward; the forward saves its inputs
+    only (the weights and the context are recomputed)."""
+
+    @staticmethod
+    def forward(ctx, feat, live, score, gate):
+        out = torch.empty(feat.shape, dtype=torch.float32, device=feat.device)
+        rows, flags, score, gate = _team_pool_fwd(feat, live, score, gate, out)
+        ctx.save_for_backward(rows, flags, score, gate)
+        ctx.P = feat.shape[-2]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, flags, score, gate = ctx.saved_tensors
+        L, dev, P = load_library(), rows.device, ctx.P
+        G = rows.shape[0] // P
+        g = g.contiguous()
+        d_feat = torch.empty(g.shape, dtype=torch.float32, device=dev)
+        dsg = torch.zeros((2, TEAM_POOL_E), dtype=torch.float32, device=dev) if G == 0 else torch.empty((2, TEAM_POOL_E), dtype=torch.float32, device=dev)
+        if G:
+            key = (dev, "team_pool", torch.cuda.current_stream().cuda_stream)
+            ws = _workspaces.get(key)
+            if ws is None:
+                ws = _workspaces[key] = torch.empty(L.team_pool_bwd_workspace(TEAM_POOL_E, 0), dtype=torch.uint8, device=dev)
+            _check(L.team_pool_bwd(G, P, TEAM_POOL_E, _ptr(rows), rows.stride(0) if rows.shape[0] > 1 else TEAM_POOL_E, _ptr(flags), int(flags.dtype == torch.uint8), P,
+                                   _ptr(score), _ptr(gate), _ptr(g), TEAM_POOL_E, _ptr(d_feat), TEAM_POOL_E, _ptr(dsg[0]), _ptr(dsg[1]), _ptr(ws), 0, _stream()),
+                   "team_pool_bwd")
+        return d_feat, None, dsg[0], dsg[1]
+
+
+def team_pool(feat, live, score, gate, out=None):
+    """out = feat + gate * (the attention pool of the group's live rows): feat (.., P, 128), the P rows of a group consecutive, live
+    (.., P) fp32 / uint8 flags, into `out` (the same rows; static storage, never feat itself) in ONE launch (csrc/team_pool.hpp
+    k_team_pool_fwd).  The rollout's form: no autograd.  CPU, float64 or another width: team_pool_formula.  -> out"""
+    if out is None:
+        out = torch.empty(feat.shape, dtype=feat.dtype, device=feat.device)
+    if _team_pool_fused(feat):
+        _team_pool_fwd(feat.detach(), live, score.detach(), gate.detach(), out)
+    else:
+        out.copy_(team_pool_formula(feat.detach(), live, score.detach(), gate.detach()).reshape(out.shape))
+    return out
+
+
+def team_pool_train(feat, live, score, gate):
+    """-> feat + gate * pool, the update's form: ONE autograd node, one launch forward and one launch + the ordered reduce backward
+    (gradients to feat, score, gate; the same bits from run to run).  CPU, float64 or another width: team_pool_formula under torch's
+    autograd."""
+    if _team_pool_fused(feat):
+        return _TeamPool.apply(feat, live, score, gate)
+    return team_pool_formula(feat, live, score, gate)

@@ -20,7 +20,7 @@ from .mappo import MAPPO
 from .imitation import check_entry as check_imitation_entry, phase_step
 from .kickstart import check_entry as check_kickstart_entry
 from .minibatch_steps import check_entry as check_minibatch_steps_entry
-from .model import check_layer_norm_keys
+from .model import check_layer_norm_keys, check_team_pool_keys
 from .pursuit_env import Pursuit_Env
 from .pursuit_imitation import check_coef_entry as check_pursuit_kickstart_entry, check_entry as check_pursuit_imitation_entry
 from .obs_norm import check_entry as check_obs_norm_entry
@@ -306,6 +306,7 @@ class ParticleRunState:
         agent = self.agent
         agent.check_policy_meta(b.get("policy"), "resume bundle " + str(path))
         check_layer_norm_keys(agent, b["actor"].keys(), f"resume bundle {path}")   # algo.use_layer_norm: the networks have feat_norm or not
+        check_team_pool_keys(agent, b["critic"].keys(), f"resume bundle {path}")   # algo.critic_team_pool: the critic has team_pool or not
         theirs, mine = "reward_scaling" in b, agent.use_reward_scaling
         if theirs != mine:
             raise ValueError(f"resume bundle {path} was written with algo.use_reward_scaling: {str(theirs).lower()}, "

@@ -816,6 +816,27 @@ int feat_norm_bwd_multi(int32_t n_jobs, const mo_feat_norm_job *jobs, int64_t R,
                         void *stream);
 
 /*
+ * Attention-pooled team context for the critic (`algo.critic_team_pool: attention`; csrc/team_pool.hpp).  A group is P
+ * consecutive rows f_j of E floats (rows feat_ld apart, group g starts at row g P) with P live flags at live + g live_stride: fp32
+ * (live_u8 == 0) or uint8 (live_u8 == 1), non-zero = live.  With s_j = score . f_j and w the softmax of s over the live rows (maximum
+ * subtracted, fp32), c = sum_live w_j f_j (c = 0 when nobody is live), team_pool_fwd writes out_i = f_i + gate * c for EVERY row i of
+ * the group (gate element-wise; never in place: out may not overlap feat).
+ * team_pool_bwd reads feat, the flags, score, gate and g (= d out) and OVERWRITES d_feat (rows d_feat_ld apart; may not overlap feat
+ * or g), d_score [E] and d_gate [E]; the weights are recomputed from feat (nothing was saved).  workspace: at least
+ * team_pool_bwd_workspace(E, max_blocks) bytes, 16-byte aligned (per-workgroup partial blocks added in a fixed order: no atomics, the
+ * same bits from run to run; a group's out and d_feat depend on that group's rows and flags only).
+ * max_blocks: 0 = the default grid; > 0 caps the workgroups (four groups in flight each).
+ * E == 128 only; 1 <= P <= 64; strides even and >= E, live_stride >= P; float pointers 8-byte aligned, fp32 flags 4-byte.  Anything
+ * else, G < 0 or a NULL pointer: MO_ERR_BAD_ARG before any launch or write.  G == 0 succeeds and writes nothing.
+ */
+int team_pool_fwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                  const float *score, const float *gate, float *out, int64_t out_ld, int32_t max_blocks, void *stream);
+int64_t team_pool_bwd_workspace(int32_t E, int32_t max_blocks);
+int team_pool_bwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                  const float *score, const float *gate, const float *g, int64_t g_ld, float *d_feat, int64_t d_feat_ld, float *d_score, float *d_gate,
+                  void *workspace, int32_t max_blocks, void *stream);
+
+/*
  * ReLU backward and the bias gradient of the Linear in front of it in one pass (autograd: aten::threshold_backward, then
  * grad.sum(0) re-reading it; MAPPO.train's loss.backward(), DHGN/mappo_parallel.py:660-708):
  *   gin [R][F] = gout * [y > 0] (y = the saved ReLU output);  colsum [F] = sum_r gin[r][:].
