@@ -19,6 +19,7 @@
 #include "pool_agg.hpp"
 #include "sem_att.hpp"
 #include "team_pool.hpp"
+#include "team_pool_heads.hpp"
 
 extern "C" {
 
@@ -526,6 +527,29 @@ int team_pool_bwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t fe
     if (G == 0) return 0;
     const TpArgs a = {feat, feat_ld, live, live_u8, live_stride, score, gate};
     return launch_team_pool_bwd(a, g, g_ld, d_feat, d_feat_ld, d_score, d_gate, G, P, (float *)workspace, max_blocks, (hipStream_t)stream);
+}
+
+
+int team_pool_heads_fwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                        const float *score, const float *gate, float *out, int64_t out_ld, int32_t heads, int32_t max_blocks, void *stream) {
+    if (!tph_heads_ok(heads) || !tp_common_ok(G, P, E, feat, feat_ld, live, live_u8, live_stride, score, gate, max_blocks) || !fa_ok8(out) ||
+        !fn_ld_ok(out_ld) || fn_overlap(feat, feat_ld, out, out_ld, G * P))
+        return MO_ERR_BAD_ARG;
+    if (G == 0) return 0;
+    const TpArgs a = {feat, feat_ld, live, live_u8, live_stride, score, gate};
+    return launch_team_pool_heads_fwd(a, heads, out, out_ld, G, P, max_blocks, (hipStream_t)stream);
+}
+
+int team_pool_heads_bwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                        const float *score, const float *gate, const float *g, int64_t g_ld, float *d_feat, int64_t d_feat_ld, float *d_score,
+                        float *d_gate, void *workspace, int32_t heads, int32_t max_blocks, void *stream) {
+    if (!tph_heads_ok(heads) || !tp_common_ok(G, P, E, feat, feat_ld, live, live_u8, live_stride, score, gate, max_blocks) || !fa_ok8(g) ||
+        !fn_ld_ok(g_ld) || !fa_ok8(d_feat) || !fn_ld_ok(d_feat_ld) || !fa_ok8(d_score) || !fa_ok8(d_gate) || !workspace || ((uintptr_t)workspace & 15) ||
+        fn_overlap(feat, feat_ld, d_feat, d_feat_ld, G * P) || fn_overlap(g, g_ld, d_feat, d_feat_ld, G * P))
+        return MO_ERR_BAD_ARG;
+    if (G == 0) return 0;
+    const TpArgs a = {feat, feat_ld, live, live_u8, live_stride, score, gate};
+    return launch_team_pool_heads_bwd(a, heads, g, g_ld, d_feat, d_feat_ld, d_score, d_gate, G, P, (float *)workspace, max_blocks, (hipStream_t)stream);
 }
 
 }  // extern "C"

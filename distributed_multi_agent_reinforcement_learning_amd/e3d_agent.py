@@ -43,7 +43,7 @@ from . import ops
 from . import value_norm as vnorm
 from .e3d_env import CENTRAL_MAX_P, EVADER_OBS, PURSUIT_FEAT, ParticleEnv, central_feat
 from .model import (FEAT_NORM_KEY, TEAM_POOL_KEY, TEAM_POOL_MODES, HeadLinear, _make_linear, _ortho_linear, _Trunk, layer_norm_options, norm_pair,
-                    norm_rollout, pool_features, pool_rollout, team_pool_options)
+                    norm_rollout, pool_features, pool_rollout, check_team_pool_heads, team_pool_options)
 from .particle_agent import ParticleMAPPO, ParticleTrainer, finish_env, train_particle
 
 FEAT = 16   # e3d_policy_features columns (include/e3d_env.h); algo.e3d_features: pursuit has PURSUIT_FEAT
@@ -233,7 +233,7 @@ class E3dMAPPO(ParticleMAPPO):
         self.critic_feat_dim = central_feat(int(cfg.env.num_defender)) if self.e3d_critic == "central" else self.feat_dim
         self.e3d_comm, self.e3d_comm_heads = e3d_comm_options(cfg)   # team attention in the actor
         self.use_layer_norm = layer_norm_options(cfg)   # LayerNorm between the GRUs and the heads
-        self.critic_team_pool = team_pool_options(cfg)   # the critic's attention pool over the live team
+        self.critic_team_pool, self.critic_team_pool_heads = team_pool_options(cfg)   # the critic's attention pool over the live team (DESIGN.md sections 7z, 7z')
         self.use_obs_norm, self.obs_norm_clip = onorm.obs_norm_options(cfg)   # running mean / std on the policy features
         self.gauss_std, self.gauss_squash, self.log_std_min, self.log_std_max = gauss_policy_options(cfg)
         self.policy_ex = (self.gauss_std, self.gauss_squash) != ("param", "clip")   # the _ex kernels only when an option is on
@@ -263,7 +263,7 @@ class E3dMAPPO(ParticleMAPPO):
         if self.use_layer_norm:   # after every other parameter and without a draw; last in ac_parameters: the actor's, then the critic's
             self.ac_parameters += self.actor.add_feat_norm() + self.critic.add_feat_norm()
         if self.critic_team_pool:   # behind feat_norm, likewise without a draw: the critic's last keys
-            self.ac_parameters += self.critic.add_team_pool()
+            self.ac_parameters += self.critic.add_team_pool(self.critic_team_pool_heads)
         self.obs_norm = onorm.ObsNorm(self.obs_norm_clip, self.device) if self.use_obs_norm else None
 
     # ---- rollout -------------------------------------------------------------------------------------------------------------
@@ -476,6 +476,8 @@ class E3dMAPPO(ParticleMAPPO):
             meta.update(use_layer_norm=True)
         if getattr(self, "critic_team_pool", False):
             meta.update(critic_team_pool=TEAM_POOL_MODES[1])
+            if self.critic_team_pool_heads != 1:   # (one head: the entries of before)
+                meta.update(critic_team_pool_heads=self.critic_team_pool_heads)
         return meta or None
 
     def check_policy_meta(self, meta, what):
@@ -491,6 +493,7 @@ class E3dMAPPO(ParticleMAPPO):
         theirs, mine = meta.get("critic_team_pool", TEAM_POOL_MODES[0]), TEAM_POOL_MODES[int(bool(getattr(self, "critic_team_pool", False)))]
         if theirs != mine:   # (a file without the entry was written with none: the critic has team_pool or not)
             raise ValueError(f"{what} was written with {TEAM_POOL_KEY}: {theirs}, this agent has {TEAM_POOL_KEY}: {mine}")
+        check_team_pool_heads(self, meta.get("critic_team_pool_heads"), what)   # (heads split the same weights differently: the shapes would load)
         for key, default in (("e3d_features", "basic"), ("e3d_evader_obs", "sensed"), ("e3d_critic", "local"), ("e3d_comm", "none"),
                              ("gauss_std", "param"), ("gauss_squash", "clip")):
             theirs, mine = meta.get(key, default), getattr(self, key, default)

@@ -240,6 +240,9 @@ class MAPPO(OptimizerSchedule):
         if team_pool_key(cfg):
             raise ValueError("algo.critic_team_pool: attention is built for runtime.env n2n and e3d only; the pursuit networks are pinned to "
                              "the reference's (set critic_team_pool to none)")
+        if "critic_team_pool_heads" in cfg.algo:
+            raise ValueError("algo.critic_team_pool_heads belongs to algo.critic_team_pool: attention, built for runtime.env n2n and e3d only "
+                             "(leave critic_team_pool_heads out)")
         refuse_pursuit(cfg)   # algo.bc_iterations: env_3d / env_n2n only
         refuse_pursuit_kickstart(cfg)   # algo.bc_coef: likewise
         # algo.pathfinder_bc_iterations: the flagship's own warm start, from the path-finding pursuers

@@ -382,6 +382,7 @@ class FeatNorm(nn.Module):
 
 TEAM_POOL_KEY = "algo.critic_team_pool"
 TEAM_POOL_MODES = ("none", "attention")
+TEAM_POOL_HEADS_KEY = "algo.critic_team_pool_heads"
 
 
 def team_pool_key(cfg):
@@ -392,33 +393,57 @@ def team_pool_key(cfg):
     return v == "attention"
 
 
+def team_pool_heads_key(cfg, on):
+    """-> algo.critic_team_pool_heads (default 1), one of ops.TEAM_POOL_HEADS; ValueError naming the key at anything else, and naming both
+    keys at a value other than 1 without the pool"""
+    v = cfg.algo.get("critic_team_pool_heads", 1)
+    if isinstance(v, bool) or not isinstance(v, int) or v not in ops.TEAM_POOL_HEADS:
+        raise ValueError(f"{TEAM_POOL_HEADS_KEY}: {v!r} is not one of {ops.TEAM_POOL_HEADS}")
+    if v != 1 and not on:
+        raise ValueError(f"{TEAM_POOL_HEADS_KEY}: {v} needs {TEAM_POOL_KEY}: attention (the heads are the pool's)")
+    return v
+
+
 def team_pool_options(cfg):
-    """-> algo.critic_team_pool as a bool, validated: the kernels' only width is 128 and a group's live flags are
-    one 64-bit word"""
+    """-> (algo.critic_team_pool as a bool, algo.critic_team_pool_heads; DESIGN.md sections 7z, 7z'), validated: the kernels' only width
+    is 128 and a group's live flags are one 64-bit word"""
     on = team_pool_key(cfg)
+    heads = team_pool_heads_key(cfg, on)
     if on and int(cfg.algo.rnn_hidden_dim) != ops.TEAM_POOL_E:
         raise ValueError(f"{TEAM_POOL_KEY}: attention needs algo.rnn_hidden_dim {ops.TEAM_POOL_E} (the pool kernels' only width), "
                          f"got algo.rnn_hidden_dim={cfg.algo.rnn_hidden_dim}")
     if on and int(cfg.env.num_defender) > ops.TEAM_POOL_MAX_P:
         raise ValueError(f"{TEAM_POOL_KEY}: attention supports env.num_defender <= {ops.TEAM_POOL_MAX_P}, got {int(cfg.env.num_defender)}")
-    return on
+    return on, heads
 
 
-def check_team_pool_keys(agent, keys, what):
-    """ValueError naming the key when a critic file's state_dict keys belong to the other algo.critic_team_pool (before any tensor is loaded)"""
-    theirs, mine = any(k.startswith("team_pool.") for k in keys), bool(getattr(agent, "critic_team_pool", False))
+def check_team_pool_heads(agent, theirs, what):
+    """ValueError naming the key when a file's head count (None: it has none, which is 1) is not the agent's"""
+    theirs, mine = 1 if theirs is None else int(theirs), int(getattr(agent, "critic_team_pool_heads", 1))
+    if theirs != mine:
+        raise ValueError(f"{what} was written with {TEAM_POOL_HEADS_KEY}: {theirs}, this agent has {TEAM_POOL_HEADS_KEY}: {mine}")
+
+
+def check_team_pool_keys(agent, sd, what):
+    """ValueError naming the key when a critic file's state_dict belongs to the other algo.critic_team_pool, or to another
+    algo.critic_team_pool_heads (its team_pool.heads buffer; absent = 1) -- before any tensor is loaded"""
+    theirs, mine = any(k.startswith("team_pool.") for k in sd.keys()), bool(getattr(agent, "critic_team_pool", False))
     if theirs != mine:
         name = lambda on: TEAM_POOL_MODES[int(on)]
         raise ValueError(f"{what} was written with {TEAM_POOL_KEY}: {name(theirs)}, this agent has {TEAM_POOL_KEY}: {name(mine)}")
+    check_team_pool_heads(agent, sd.get("team_pool.heads"), what)
 
 
 class TeamPool(nn.Module):
     """the critic's attention pool over the live team-mates' GRU features (algo.critic_team_pool): score and gate are zeros -- no draw
     from the generator, and with gate = 0 the critic is the off-critic to the bit"""
 
-    def __init__(self, width):
+    def __init__(self, width, heads=1):
         super().__init__()
         self.score, self.gate = nn.Parameter(torch.zeros(width)), nn.Parameter(torch.zeros(width))
+        self.num_heads = int(heads)
+        if self.num_heads != 1:   # (the shapes do not tell the head counts apart: the state_dict says it; one head: the keys of before)
+            self.register_buffer("heads", torch.tensor(self.num_heads, dtype=torch.int64))
 
 
 class _Trunk(nn.Module):
@@ -437,9 +462,9 @@ class _Trunk(nn.Module):
 
     use_team_pool = False
 
-    def add_team_pool(self):
+    def add_team_pool(self, heads=1):
         """the critic's (algo.critic_team_pool), called once every other parameter exists, feat_norm included: the state_dict's last keys"""
-        self.team_pool = TeamPool(self.rnn_hidden_dim).to(self.GRU.weight_hh_l0.device)
+        self.team_pool = TeamPool(self.rnn_hidden_dim, heads).to(self.GRU.weight_hh_l0.device)
         self.use_team_pool = True
         return list(self.team_pool.parameters())
 
@@ -600,13 +625,14 @@ def pool_features(critic, feat_c, live):
         return feat_c
     if live is None:
         raise ValueError(f"{TEAM_POOL_KEY}: attention needs the rows' live mask")
-    return ops.team_pool_train(feat_c, live.permute(1, 0, 2), critic.team_pool.score, critic.team_pool.gate)
+    return ops.team_pool_train(feat_c, live.permute(1, 0, 2), critic.team_pool.score, critic.team_pool.gate, heads=critic.team_pool.num_heads)
 
 
 def pool_rollout(critic, feat_c, live, out):
     """the rollout's form of pool_features (no autograd): a tick's (N P, H) features under its (N, P) live mask into the static `out`"""
     P = live.shape[-1]
-    return ops.team_pool(feat_c.reshape(-1, P, feat_c.shape[-1]), live, critic.team_pool.score, critic.team_pool.gate, out)
+    return ops.team_pool(feat_c.reshape(-1, P, feat_c.shape[-1]), live, critic.team_pool.score, critic.team_pool.gate, out,
+                         heads=critic.team_pool.num_heads)
 
 
 def pair_heads(actor, critic, feat_a, feat_c, live=None):
@@ -653,8 +679,9 @@ def build_actor_critic(cfg, device):
     critic = SharedCritic(enc_c, cfg.algo.embedding_dim, 1, cfg.algo.num_layers, cfg.algo.rnn_hidden_dim, is_sn=sn)
     if layer_norm_options(cfg):   # after every other parameter, without a draw: the shared keys keep the off-model's bits
         actor.add_feat_norm(), critic.add_feat_norm()
-    if team_pool_options(cfg):    # the critic's alone, behind feat_norm, likewise without a draw
-        critic.add_team_pool()
+    pool, pool_heads = team_pool_options(cfg)
+    if pool:                      # the critic's alone, behind feat_norm, likewise without a draw
+        critic.add_team_pool(pool_heads)
     if not bool(cfg.algo.get("use_rnn", True)):
         if cfg.algo.embedding_dim != cfg.algo.rnn_hidden_dim:
             raise ValueError("algo.use_rnn=false feeds the embedding to the heads: embedding_dim must equal rnn_hidden_dim")

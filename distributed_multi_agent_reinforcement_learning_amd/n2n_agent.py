@@ -66,7 +66,8 @@ class N2nMAPPO(ParticleMAPPO):
 
     def _options(self, cfg):
         a = cfg.algo
-        self.critic_team_pool = team_pool_options(cfg)   # the critic's attention pool over the live team (first: its refusals name its key)
+        # the critic's attention pool over the live team and its heads (DESIGN.md sections 7z, 7z'; first: its refusals name its keys)
+        self.critic_team_pool, self.critic_team_pool_heads = team_pool_options(cfg)
         if bool(a.get("use_obs_norm", False)):
             raise ValueError("algo.use_obs_norm: true is built for runtime.env e3d only; the env_n2n inputs are node states whose "
                              "differences the message kernels form and whose zero rows stand for absent nodes (set use_obs_norm to false)")
@@ -268,7 +269,7 @@ class N2nMAPPO(ParticleMAPPO):
         sds = [torch.load(os.path.join(cwd, f"n2n_{net}{sfx}.pth"), map_location=self.device) for net in ("actor", "critic")]
         for sd, net in zip(sds, ("actor", "critic")):
             check_layer_norm_keys(self, sd.keys(), os.path.join(cwd, f"n2n_{net}{sfx}.pth"))
-        check_team_pool_keys(self, sds[1].keys(), os.path.join(cwd, f"n2n_critic{sfx}.pth"))
+        check_team_pool_keys(self, sds[1], os.path.join(cwd, f"n2n_critic{sfx}.pth"))
         self.actor.load_state_dict(sds[0])
         self.critic.load_state_dict(sds[1])
         if self.value_norm is not None:

@@ -27,7 +27,7 @@ EXPORTS = ("dhgn_msg_agg_fwd", "dhgn_msg_agg3_fwd", "dhgn_msg_agg_bwd", "dhgn_ms
            "gnn_pair_agg_bwd_workspace", "dhgn_att_agg3_fwd", "dhgn_att_agg_bwd", "dhgn_att_agg_bwd_workspace", "fcra_att_fwd_multi", "fcra_att_bwd",
            "fcra_att_bwd_workspace", "dhgn_pool_agg3_fwd", "dhgn_pool_agg_bwd", "dhgn_pool_agg_bwd_workspace", "fcra_pool_fwd_multi", "fcra_pool_bwd",
            "fcra_pool_bwd_workspace", "fcra_team_fwd_multi", "fcra_team_bwd", "fcra_team_bwd_workspace", "feat_norm_fwd_multi",
-           "feat_norm_bwd_multi", "feat_norm_bwd_workspace", "team_pool_fwd", "team_pool_bwd", "team_pool_bwd_workspace", "mappo_ops_error_string")
+           "feat_norm_bwd_multi", "feat_norm_bwd_workspace", "team_pool_fwd", "team_pool_bwd", "team_pool_bwd_workspace", "team_pool_heads_fwd", "team_pool_heads_bwd", "mappo_ops_error_string")
 
 _lib = None
 
@@ -195,6 +195,8 @@ def load_library():
         L.team_pool_bwd_workspace.argtypes = [i32, i32]
         L.team_pool_bwd_workspace.restype = i64
         L.team_pool_bwd.argtypes = [i64, i32, i32, vp, i64, vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i32, vp]
+        L.team_pool_heads_fwd.argtypes = [i64, i32, i32, vp, i64, vp, i32, i64, vp, vp, vp, i64, i32, i32, vp]
+        L.team_pool_heads_bwd.argtypes = [i64, i32, i32, vp, i64, vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, i32, i32, vp]
         L.mappo_ops_error_string.argtypes = [C.c_int]
         L.mappo_ops_error_string.restype = C.c_char_p
         _lib = L
@@ -3292,12 +3294,22 @@ def feat_norm_train(xs, weights, biases, eps):
 # ---- attention-pooled team context for the critic (algo.critic_team_pool; csrc/team_pool.hpp) -------------------------------
 TEAM_POOL_E = 128          # the kernels' only width
 TEAM_POOL_MAX_P = 64       # one ballot word of live flags per group
+TEAM_POOL_HEADS = (1, 2, 4, 8)   # algo.critic_team_pool_heads; above 1: csrc/team_pool_heads.hpp (DESIGN 7z')
 team_pool_calls = 0        # forward launches of the team pool so far (tests)
 
 
-def team_pool_formula(feat, live, score, gate):
+def team_pool_formula(feat, live, score, gate, heads=1):
     """the specification (CPU, float64): feat (G, P, E), live (G, P) non-zero = live, score / gate (E,) ->
-    feat + gate * c, c = the softmax(score . f_j over the live j)-weighted sum of the live rows (nobody live: c = 0)"""
+    feat + gate * c, c = the softmax(score . f_j over the live j)-weighted sum of the live rows (nobody live: c = 0);
+    heads > 1: head h owns features [h E / heads, (h + 1) E / heads), with scores, softmax and weights of its own"""
+    if heads != 1:
+        if heads not in TEAM_POOL_HEADS:
+            raise ValueError(f"team_pool: heads is one of {TEAM_POOL_HEADS}, got {heads!r}")
+        on, (E, D) = (live != 0).unsqueeze(-1), (feat.shape[-1], feat.shape[-1] // heads)
+        s = (feat * score).unflatten(-1, (heads, D)).sum(-1).masked_fill(~on, -torch.inf)                  # (.., P, heads)
+        e = torch.where(on, torch.exp(s - s.max(-2, keepdim=True).values.clamp_min(torch.finfo(feat.dtype).min)), torch.zeros_like(s))
+        w = (e / e.sum(-2, keepdim=True).clamp_min(torch.finfo(feat.dtype).tiny)).repeat_interleave(D, -1)  # (.., P, E)
+        return feat + gate * (w * torch.where(on, feat, torch.zeros_like(feat))).sum(-2, keepdim=True)
     on = live != 0
     s = (feat * score).sum(-1).masked_fill(~on, -torch.inf)
     e = torch.where(on, torch.exp(s - s.max(-1, keepdim=True).values.clamp_min(torch.finfo(feat.dtype).min)), torch.zeros_like(s))
@@ -3331,13 +3343,24 @@ def _team_pool_args(feat, live, score, gate):
     return (G, P, TEAM_POOL_E, _ptr(rows), ld, _ptr(flags), u8, P, _ptr(score), _ptr(gate)), (rows, flags, score, gate)
 
 
-def _team_pool_fwd(feat, live, score, gate, out, max_blocks=0):
+def _team_pool_heads(heads):
+    """-> the head count of a fused call (1: the single-head entry points, whose bits stay what they were)"""
+    if isinstance(heads, bool) or heads not in TEAM_POOL_HEADS:
+        raise ValueError(f"team_pool: heads is one of {TEAM_POOL_HEADS}, got {heads!r}")
+    return int(heads)
+
+
+def _team_pool_fwd(feat, live, score, gate, out, max_blocks=0, heads=1):
     global team_pool_calls
+    heads = _team_pool_heads(heads)
     head, keep = _team_pool_args(feat, live, score, gate)
     rows, ld = _feat_rows(out.view(-1, TEAM_POOL_E) if out.dim() != 2 else out, "out", written=True)
     assert rows.shape[0] == keep[0].shape[0], "team_pool: out has other rows than feat"
     if head[0]:   # (an empty tensor has no address to pass)
-        _check(load_library().team_pool_fwd(*head, _ptr(rows), ld, max_blocks, _stream()), "team_pool_fwd")
+        if heads == 1:
+            _check(load_library().team_pool_fwd(*head, _ptr(rows), ld, max_blocks, _stream()), "team_pool_fwd")
+        else:
+            _check(load_library().team_pool_heads_fwd(*head, _ptr(rows), ld, heads, max_blocks, _stream()), "team_pool_heads_fwd")
         team_pool_calls += 1
     return keep
 
@@ -3347,11 +3370,11 @@ class _TeamPool(torch.autograd.Function):
     only (the weights and the context are recomputed)."""
 
     @staticmethod
-    def forward(ctx, feat, live, score, gate):
+    def forward(ctx, feat, live, score, gate, heads=1):
         out = torch.empty(feat.shape, dtype=torch.float32, device=feat.device)
-        rows, flags, score, gate = _team_pool_fwd(feat, live, score, gate, out)
+        rows, flags, score, gate = _team_pool_fwd(feat, live, score, gate, out, heads=heads)
         ctx.save_for_backward(rows, flags, score, gate)
-        ctx.P = feat.shape[-2]
+        ctx.P, ctx.heads = feat.shape[-2], int(heads)
         return out
 
     @staticmethod
@@ -3367,29 +3390,33 @@ class _TeamPool(torch.autograd.Function):
             ws = _workspaces.get(key)
             if ws is None:
                 ws = _workspaces[key] = torch.empty(L.team_pool_bwd_workspace(TEAM_POOL_E, 0), dtype=torch.uint8, device=dev)
-            _check(L.team_pool_bwd(G, P, TEAM_POOL_E, _ptr(rows), rows.stride(0) if rows.shape[0] > 1 else TEAM_POOL_E, _ptr(flags), int(flags.dtype == torch.uint8), P,
-                                   _ptr(score), _ptr(gate), _ptr(g), TEAM_POOL_E, _ptr(d_feat), TEAM_POOL_E, _ptr(dsg[0]), _ptr(dsg[1]), _ptr(ws), 0, _stream()),
-                   "team_pool_bwd")
-        return d_feat, None, dsg[0], dsg[1]
+            head = (G, P, TEAM_POOL_E, _ptr(rows), rows.stride(0) if rows.shape[0] > 1 else TEAM_POOL_E, _ptr(flags), int(flags.dtype == torch.uint8), P,
+                    _ptr(score), _ptr(gate), _ptr(g), TEAM_POOL_E, _ptr(d_feat), TEAM_POOL_E, _ptr(dsg[0]), _ptr(dsg[1]), _ptr(ws))
+            if ctx.heads == 1:
+                _check(L.team_pool_bwd(*head, 0, _stream()), "team_pool_bwd")
+            else:
+                _check(L.team_pool_heads_bwd(*head, ctx.heads, 0, _stream()), "team_pool_heads_bwd")
+        return d_feat, None, dsg[0], dsg[1], None
 
 
-def team_pool(feat, live, score, gate, out=None):
+def team_pool(feat, live, score, gate, out=None, heads=1):
     """out = feat + gate * (the attention pool of the group's live rows): feat (.., P, 128), the P rows of a group consecutive, live
     (.., P) fp32 / uint8 flags, into `out` (the same rows; static storage, never feat itself) in ONE launch (csrc/team_pool.hpp
-    k_team_pool_fwd).  The rollout's form: no autograd.  CPU, float64 or another width: team_pool_formula.  -> out"""
+    k_team_pool_fwd; heads 2, 4 or 8: csrc/team_pool_heads.hpp k_team_pool_heads_fwd).  The rollout's form: no autograd.  CPU, float64
+    or another width: team_pool_formula.  -> out"""
     if out is None:
         out = torch.empty(feat.shape, dtype=feat.dtype, device=feat.device)
     if _team_pool_fused(feat):
-        _team_pool_fwd(feat.detach(), live, score.detach(), gate.detach(), out)
+        _team_pool_fwd(feat.detach(), live, score.detach(), gate.detach(), out, heads=heads)
     else:
-        out.copy_(team_pool_formula(feat.detach(), live, score.detach(), gate.detach()).reshape(out.shape))
+        out.copy_(team_pool_formula(feat.detach(), live, score.detach(), gate.detach(), heads=heads).reshape(out.shape))
     return out
 
 
-def team_pool_train(feat, live, score, gate):
+def team_pool_train(feat, live, score, gate, heads=1):
     """-> feat + gate * pool, the update's form: ONE autograd node, one launch forward and one launch + the ordered reduce backward
     (gradients to feat, score, gate; the same bits from run to run).  CPU, float64 or another width: team_pool_formula under torch's
     autograd."""
     if _team_pool_fused(feat):
-        return _TeamPool.apply(feat, live, score, gate)
-    return team_pool_formula(feat, live, score, gate)
+        return _TeamPool.apply(feat, live, score, gate, _team_pool_heads(heads))
+    return team_pool_formula(feat, live, score, gate, heads=heads)

@@ -306,7 +306,7 @@ class ParticleRunState:
         agent = self.agent
         agent.check_policy_meta(b.get("policy"), "resume bundle " + str(path))
         check_layer_norm_keys(agent, b["actor"].keys(), f"resume bundle {path}")   # algo.use_layer_norm: the networks have feat_norm or not
-        check_team_pool_keys(agent, b["critic"].keys(), f"resume bundle {path}")   # algo.critic_team_pool: the critic has team_pool or not
+        check_team_pool_keys(agent, b["critic"], f"resume bundle {path}")   # algo.critic_team_pool(_heads): the critic has team_pool or not, and its heads
         theirs, mine = "reward_scaling" in b, agent.use_reward_scaling
         if theirs != mine:
             raise ValueError(f"resume bundle {path} was written with algo.use_reward_scaling: {str(theirs).lower()}, "

@@ -837,6 +837,20 @@ int team_pool_bwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t fe
                   void *workspace, int32_t max_blocks, void *stream);
 
 /*
+ * The team pool with `heads` = 2, 4 or 8 attention heads (`algo.critic_team_pool_heads`; csrc/team_pool_heads.hpp, DESIGN 7z').  Head h
+ * owns features [h E / heads, (h + 1) E / heads): s_j^h is score . f_j over that slice alone, w^h the softmax of s^h over the live rows,
+ * and c[u] = sum_live w_j^{h(u)} f_j[u]; out, d_feat, d_score and d_gate are team_pool_fwd's / team_pool_bwd's with w_j taken per head
+ * (no 1 / sqrt(E / heads) factor: score absorbs it).  Arguments, strides, alignment, the workspace (team_pool_bwd_workspace) and every
+ * refusal are team_pool_fwd's / team_pool_bwd's; heads not in {2, 4, 8} is MO_ERR_BAD_ARG as well (one head: call team_pool_fwd /
+ * team_pool_bwd).  Deterministic in the same sense.
+ */
+int team_pool_heads_fwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                        const float *score, const float *gate, float *out, int64_t out_ld, int32_t heads, int32_t max_blocks, void *stream);
+int team_pool_heads_bwd(int64_t G, int32_t P, int32_t E, const float *feat, int64_t feat_ld, const void *live, int32_t live_u8, int64_t live_stride,
+                        const float *score, const float *gate, const float *g, int64_t g_ld, float *d_feat, int64_t d_feat_ld, float *d_score,
+                        float *d_gate, void *workspace, int32_t heads, int32_t max_blocks, void *stream);
+
+/*
  * ReLU backward and the bias gradient of the Linear in front of it in one pass (autograd: aten::threshold_backward, then
  * grad.sum(0) re-reading it; MAPPO.train's loss.backward(), DHGN/mappo_parallel.py:660-708):
  *   gin [R][F] = gout * [y > 0] (y = the saved ReLU output);  colsum [F] = sum_r gin[r][:].

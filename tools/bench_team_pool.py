@@ -2,7 +2,8 @@
 times.  One process per line:
     python tools/bench_team_pool.py --config cfg5 --shape minibatch [--out profiles/team_pool_kernel_times.jsonl]
   --shape rollout: the groups of a tick (runtime.num_envs);  --shape minibatch: those of an update's mini-batch (round(num_envs / 10)
-  episodes x env.max_steps);  --groups N / --pursuers P: any other shape
+  episodes x env.max_steps);  --groups N / --pursuers P: any other shape;  --heads H: algo.critic_team_pool_heads (2, 4, 8: the kernels of
+  csrc/team_pool_heads.hpp, with the one-head kernels on the same tensors beside them as h1_*)
 Two yardsticks on the same tensors in the same process: the torch formula (ops.team_pool_formula, forward, and forward + autograd), and
 the bytes the kernels must move -- forward: read feat, write out (1 KB a row); backward: read feat and g, write d feat (1.5 KB) -- as
 achieved TB/s."""
@@ -25,6 +26,7 @@ def main():
     ap.add_argument("--shape", choices=["rollout", "minibatch"], default="minibatch")
     ap.add_argument("--groups", type=int, default=0)
     ap.add_argument("--pursuers", type=int, default=0)
+    ap.add_argument("--heads", type=int, choices=list(ops.TEAM_POOL_HEADS), default=1)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=None)
@@ -40,18 +42,26 @@ def main():
     g, out = torch.randn(G, P, E, device="cuda"), torch.empty(G, P, E, device="cuda")
     leaves = (feat, score, gate)
     calls = ops.team_pool_calls
-    ms = {"fused": timed(lambda: torch.autograd.grad(ops.team_pool_train(feat, live, score, gate), leaves, g), a.warmup, a.iters)}
-    ms["torch"] = timed(lambda: torch.autograd.grad(ops.team_pool_formula(feat, live, score, gate), leaves, g), a.warmup, a.iters)
+    H = a.heads
+    ms = {"fused": timed(lambda: torch.autograd.grad(ops.team_pool_train(feat, live, score, gate, heads=H), leaves, g), a.warmup, a.iters)}
+    ms["torch"] = timed(lambda: torch.autograd.grad(ops.team_pool_formula(feat, live, score, gate, heads=H), leaves, g), a.warmup, a.iters)
+    if H != 1:
+        ms["h1"] = timed(lambda: torch.autograd.grad(ops.team_pool_train(feat, live, score, gate), leaves, g), a.warmup, a.iters)
     with torch.no_grad():
-        ms["fwd"] = timed(lambda: ops.team_pool(feat, live, score, gate, out), a.warmup, a.iters)
-        ms["torch_fwd"] = timed(lambda: ops.team_pool_formula(feat, live, score, gate), a.warmup, a.iters)
-    assert ops.team_pool_calls == calls + 2 * (a.warmup + a.iters)
+        ms["fwd"] = timed(lambda: ops.team_pool(feat, live, score, gate, out, heads=H), a.warmup, a.iters)
+        ms["torch_fwd"] = timed(lambda: ops.team_pool_formula(feat, live, score, gate, heads=H), a.warmup, a.iters)
+        if H != 1:
+            ms["h1_fwd"] = timed(lambda: ops.team_pool(feat, live, score, gate, out), a.warmup, a.iters)
+    assert ops.team_pool_calls == calls + (2 if H == 1 else 4) * (a.warmup + a.iters)
     rows = G * P * E * 4
-    line = {"tool": "bench_team_pool", "config": a.config, "shape": "groups" if a.groups else a.shape, "G": G, "P": P,
+    line = {"tool": "bench_team_pool", "config": a.config, "shape": "groups" if a.groups else a.shape, "G": G, "P": P, "heads": H,
             "fwd_ms": round(ms["fwd"], 4), "fwd_bwd_ms": round(ms["fused"], 4), "torch_fwd_ms": round(ms["torch_fwd"], 4),
             "torch_fwd_bwd_ms": round(ms["torch"], 4), "torch_over_fused_fwd": round(ms["torch_fwd"] / ms["fwd"], 3),
             "torch_over_fused_fwd_bwd": round(ms["torch"] / ms["fused"], 3), "fwd_tb_s": round(2 * rows / ms["fwd"] / 1e9, 3),
             "fwd_bwd_tb_s": round(5 * rows / ms["fused"] / 1e9, 3), "device": torch.cuda.get_device_name(0)}
+    if H != 1:
+        line.update(h1_fwd_ms=round(ms["h1_fwd"], 4), h1_fwd_bwd_ms=round(ms["h1"], 4), fwd_over_h1=round(ms["fwd"] / ms["h1_fwd"], 3),
+                    fwd_bwd_over_h1=round(ms["fused"] / ms["h1"], 3))
     text = json.dumps(line)
     print(text)
     if a.out:
